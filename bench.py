@@ -17,6 +17,10 @@ profiles/ and stamped with the sha256 of the kernel sources) / the kernel's laun
 reference algorithm's own flop count (oracle counters; the index skips most of that work) is reported beside it as `work_skipped_vs_reference`.
 `cpu_baseline` is the oracle (restatement of the reference's rayon CPU path; the Rust reference cannot be built here) timed on the host cores --
 a checker used as a reported baseline, never part of the product path.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, frame_checksum, set-up and kernel times).  `--full`
+adds everything else: `roofline` (with `reference_algorithm`), `cpu_baseline`, `first_frame` and `host_fb` (each of the last three can still be left
+out with its --no-* option).  `--dump-outputs DIR` writes the frame of the last timed step to DIR (dump_outputs()).
 """
 from __future__ import annotations
 
@@ -25,6 +29,7 @@ import hashlib
 import importlib
 import json
 import os
+import shutil
 import socket
 import subprocess
 import sys
@@ -46,6 +51,24 @@ def kernel_source_sha256() -> str:
         with open(os.path.join(ROOT, rel), "rb") as f:
             h.update(f.read())
     return h.hexdigest()
+
+
+DUMP_BYTES = 64 * 10**6            # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(frame, out_dir) -> None:
+    """--dump-outputs: the frame of the last timed step as the caller receives it (one 0x00RRGGBB word per pixel) as float32 channel values
+    [H, W, 3] in frame_rgb.npy.  A frame larger than DUMP_BYTES is written as a fixed sample of its pixels (seed 0: the same pixels for the same
+    width and height): frame_rgb.npy [n, 3] and their row-major pixel indices in frame_pixel_index.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rgb = np.stack([(frame >> 16) & 255, (frame >> 8) & 255, frame & 255], -1).astype(np.float32)
+    if rgb.nbytes > DUMP_BYTES:
+        n = (DUMP_BYTES - 4096) // (3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(frame.size, n, replace=False))
+        rgb = rgb.reshape(-1, 3)[idx]
+        np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "frame_rgb.npy"), rgb)
 
 
 def algorithmic_flops(c: dict) -> float:
@@ -109,12 +132,13 @@ def supervise(args, argv) -> int:
     rank = int(os.environ.get("RANK", "0"))
     force_one = os.environ.get("RRT_BENCH_FORCE_DIST") == "1" and args.gpus == 1
     paths = ["torch", "lib"] if args.gather == "auto" else [args.gather]
-    base = _strip_opt(argv, "--gather")
+    base = _strip_opt(_strip_opt(argv, "--gather"), "--dump-outputs")
+    dump_dir = lambda pth: os.path.join(args.dump_outputs, f"gather_{pth}")   # each path's child dumps apart; the reported path's files are kept
     lines, info = {}, {}
     for k, path in enumerate(paths):
         timeout = args.lib_timeout if path == "lib" else args.torch_timeout
         env = dict(os.environ)
-        child = [os.path.abspath(__file__)] + base + ["--gather", path, "--child"]
+        child = [os.path.abspath(__file__)] + base + ["--gather", path, "--child"] + (["--dump-outputs", dump_dir(path)] if args.dump_outputs else [])
         if under_launcher:
             env["MASTER_PORT"] = str(int(os.environ.get("MASTER_PORT", "29500")) + 11 + k)
             env.pop("TORCHELASTIC_USE_AGENT_STORE", None)      # the children rendezvous among themselves: rank 0's child hosts the store on the new port
@@ -149,6 +173,12 @@ def supervise(args, argv) -> int:
         if "torch" in lines and "lib" in lines and lines["lib"]["frame_checksum"] != lines["torch"]["frame_checksum"]:
             best = lines["torch"]; summary["lib"]["error"] = "frame differs from the torch path's"
         best["gather_paths"] = summary
+        if args.dump_outputs:
+            src = dump_dir(best["gather"])
+            for f in os.listdir(src):
+                os.replace(os.path.join(src, f), os.path.join(args.dump_outputs, f))
+            for pth in paths:
+                shutil.rmtree(dump_dir(pth), ignore_errors=True)
         print(json.dumps(best), flush=True)
     return 0 if finished else 1
 
@@ -169,11 +199,15 @@ def main() -> None:
     ap.add_argument("--torch-timeout", type=float, default=300.0, help="N > 1: seconds the torch-gather child group may take before the supervisor kills it")
     ap.add_argument("--child", action="store_true", help="internal: this process is one rank of ONE gather path's child group (started by the supervisor)")
     ap.add_argument("--walk", choices=("auto", "lane", "bundle", "ray"), default="auto", help="traversal variant: auto = the library measures all three on the second frame of a size (the product default); the others force one (developer A/B)")
+    ap.add_argument("--full", action="store_true", help="also measure and report what the headline does not need: roofline, cpu_baseline, first_frame, host_fb")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step to DIR as .npy (dump_outputs())")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-first-frame", action="store_true", help="skip the cold time-to-first-frame measurement (first_frame_ms)")
     ap.add_argument("--no-host-fb", action="store_true", help="skip the boundary-inclusive rrt_render timings (frame_ms_host_fb)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU time of the bounded cpu_baseline leg (3 samples)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if (args.gpus > 1 or os.environ.get("RRT_BENCH_FORCE_DIST") == "1") and not args.child:
         raise SystemExit(supervise(args, sys.argv[1:]))            # GPU-free from here on: every gather path runs in fresh child processes
@@ -407,6 +441,8 @@ def main() -> None:
                 m["gather_ms"] = float(np.mean([a.elapsed_time(b) for a, b in gather_ev]))   # side stream: wait for the RCCL gather of the slot + de-tile
         if rank == 0:
             m["frame"] = fb.cpu().numpy().view(np.uint32).copy()
+            if args.dump_outputs:
+                dump_outputs(m["frame"], args.dump_outputs)
         return m
 
     def build_out(m, gather_label):
@@ -417,6 +453,24 @@ def main() -> None:
         ms_per_step = elapsed / args.steps * 1e3
         frame = m["frame"]
         workload_key = f"{'soup' + str(rt.info['n_tris']) if scene_name.startswith('soup') else scene_name}@{W}x{H}"
+
+        teapot = scene_name == "model2.obj"
+        out = {"metric": "Mrays/s (primary) at 1920x1080, Utah teapot (model2.obj)" if (teapot and (W, H) == (1920, 1080)) else f"Mrays/s (primary) at {W}x{H}, {scene_name}",
+               "value": round(rays_primary / (elapsed / args.steps) / 1e6, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+               "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+               "data": "reference scene assets/model2.obj (teapot+table+mirror, 6334 triangles), camera/lights of main.rs" if teapot else f"synthetic ({scene_name}: SURVEY.md 8d soup recipe)" if scene_name.startswith("soup") else f"reference scene {scene_name}",
+               "config": {"workload": f"{scene_name} {W}x{H}, 4 sub-samples/pixel, shadow rays + depth-5 mirror reflection, f64",
+                          "rays_primary_per_frame": rays_primary,
+                          "partition": "single launch" if not multi else f"8x8-pixel tiles round-robin over {world} GPUs + RCCL gather to GPU 0, " + (f"inside the library (rrt_multi_enqueue), {DEPTH} frames in flight" if in_lib else "torch.distributed.gather, " + ("one frame at a time" if simple[0] else f"{DEPTH} frames in flight (one stream per slot)")),
+                          "octree_nodes": rt.info["n_nodes"], "triangles": rt.info["n_tris"], "filter_variant": rrt.VARIANT_NAMES[rt.last_stats()["filter_variant"]]},
+               "frame_ms": round(ms_per_step, 4), "kernel_ms": round(kernel_ms, 4), "host_enqueue_ms_per_step": round(host_enqueue_ms, 4), "setup_ms": setup,
+               **({"rehearsal": "gloo on one GPU: NOT a benchmark result"} if rehearsal else {}),
+               "frame_checksum": int(np.bitwise_xor.reduce(frame.ravel().astype(np.uint64) * np.arange(1, frame.size + 1, dtype=np.uint64)))}
+        if multi:
+            out.update({"gather": gather_label, "pipeline_fallback": pipeline_fallback, "pipeline_error": pipeline_error, "kernel_ms_per_rank_min": round(kernel_ms_min, 4),
+                        "kernel_ms_per_rank_max": round(kernel_ms_max, 4), "gather_ms": round(gather_ms, 4) if gather_ms is not None else None})
+        if not args.full:
+            return out
 
         # --- boundary-inclusive frame: rrt_render into a HOST framebuffer, as the Rust host's Canvas.buffer receives it (engine.rs:127,246-250)
         host_fb = None
@@ -593,21 +647,6 @@ def main() -> None:
                                                "counters_source": counters_src,
                                                "rays_all_kinds": int(counters["rays_primary"] + counters["rays_shadow"] + counters["rays_reflect"])}
 
-        teapot = scene_name == "model2.obj"
-        out = {"metric": "Mrays/s (primary) at 1920x1080, Utah teapot (model2.obj)" if (teapot and (W, H) == (1920, 1080)) else f"Mrays/s (primary) at {W}x{H}, {scene_name}",
-               "value": round(rays_primary / (elapsed / args.steps) / 1e6, 3), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-               "data": "reference scene assets/model2.obj (teapot+table+mirror, 6334 triangles), camera/lights of main.rs" if teapot else f"synthetic ({scene_name}: SURVEY.md 8d soup recipe)" if scene_name.startswith("soup") else f"reference scene {scene_name}",
-               "config": {"workload": f"{scene_name} {W}x{H}, 4 sub-samples/pixel, shadow rays + depth-5 mirror reflection, f64",
-                          "rays_primary_per_frame": rays_primary,
-                          "partition": "single launch" if not multi else f"8x8-pixel tiles round-robin over {world} GPUs + RCCL gather to GPU 0, " + (f"inside the library (rrt_multi_enqueue), {DEPTH} frames in flight" if in_lib else "torch.distributed.gather, " + ("one frame at a time" if simple[0] else f"{DEPTH} frames in flight (one stream per slot)")),
-                          "octree_nodes": rt.info["n_nodes"], "triangles": rt.info["n_tris"], "filter_variant": rrt.VARIANT_NAMES[rt.last_stats()["filter_variant"]]},
-               "frame_ms": round(ms_per_step, 4), "kernel_ms": round(kernel_ms, 4), "host_enqueue_ms_per_step": round(host_enqueue_ms, 4), "setup_ms": setup,
-               **({"rehearsal": "gloo on one GPU: NOT a benchmark result"} if rehearsal else {}),
-               "frame_checksum": int(np.bitwise_xor.reduce(frame.ravel().astype(np.uint64) * np.arange(1, frame.size + 1, dtype=np.uint64)))}
-        if multi:
-            out.update({"gather": gather_label, "pipeline_fallback": pipeline_fallback, "pipeline_error": pipeline_error, "kernel_ms_per_rank_min": round(kernel_ms_min, 4),
-                        "kernel_ms_per_rank_max": round(kernel_ms_max, 4), "gather_ms": round(gather_ms, 4) if gather_ms is not None else None})
         if host_fb is not None:
             out.update({"frame_ms_host_fb": host_fb["frame_ms_host_fb"], "host_fb": host_fb})
         if first is not None:

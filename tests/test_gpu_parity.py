@@ -474,7 +474,7 @@ def test_bench_multi_gpu_choreography_single_rank():
         lines = [l for l in r.stdout.splitlines() if l.strip()]
         assert len(lines) == 1, r.stdout
         return json.loads(lines[0])
-    single = run({})
+    single = run({}, "--full")                                                            # --full: host_fb and first_frame are asserted below
     both = run({"RRT_BENCH_FORCE_DIST": "1"})                                             # default (auto): K steps of each path, the faster one reported
     inlib = run({"RRT_BENCH_FORCE_DIST": "1"}, "--gather", "lib")                         # the library's own gather (rrt_dist_create / rrt_multi_enqueue)
     piped = run({"RRT_BENCH_FORCE_DIST": "1"}, "--gather", "torch")

@@ -8,7 +8,7 @@ Compiles the three units of render.hip (RRT_TU = 1, 2, 3 with the Makefile's swi
   * a VALU instruction that writes EXEC (v_cmpx*, v_readfirstlane is not one) followed within 5 instructions by any DPP instruction          -> hazard.
 Prints every finding with its kernel and line; exit status 1 if any.  The product's inline asm keeps its s_nop INSIDE the block whose first
 instruction is the DPP read (render.hip: RRT_DPP_STEP_U32, RRT_DPP12), so a clean run is the expected state whatever the scheduler does."""
-import os, re, subprocess, sys
+import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from _kflags import kflags
@@ -25,8 +25,8 @@ def regs(tok):
     return out
 
 
-def compile_unit(tu, extra):
-    out = f"/tmp/render_tu{tu}.s"
+def compile_unit(tu, extra, out_dir):
+    out = os.path.join(out_dir, f"render_tu{tu}.s")
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", *kflags(UNITS[tu]), f"-DRRT_TU={tu}",
            "-S", "--cuda-device-only", "-o", out, os.path.join(ROOT, "rust-ray-tracer_amd", "csrc", "render.hip"), *extra]
     subprocess.run(cmd, check=True, capture_output=True)
@@ -72,13 +72,14 @@ def scan(path):
 
 def main(extra):
     bad = 0
-    for tu in UNITS:
-        path = compile_unit(tu, extra)
-        f = scan(path)
-        n_dpp = sum(1 for l in open(path) if "_dpp" in l or "row_shr" in l)
-        print(f"RRT_TU={tu} ({UNITS[tu]}): {n_dpp} DPP instructions, {len(f)} hazards")
-        for k, ln, msg in f[:20]: print(f"  {k}:{ln}: {msg}")
-        bad += len(f)
+    with tempfile.TemporaryDirectory() as tmp:                      # private to this run: another user's or run's files cannot be in the way
+        for tu in UNITS:
+            path = compile_unit(tu, extra, tmp)
+            f = scan(path)
+            n_dpp = sum(1 for l in open(path) if "_dpp" in l or "row_shr" in l)
+            print(f"RRT_TU={tu} ({UNITS[tu]}): {n_dpp} DPP instructions, {len(f)} hazards")
+            for k, ln, msg in f[:20]: print(f"  {k}:{ln}: {msg}")
+            bad += len(f)
     return 1 if bad else 0
 
 

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 STEPS=${STEPS:-50}
-BENCH="python3 $ROOT/bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --no-host-fb $*"
+BENCH="python3 $ROOT/bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline --no-host-fb $*"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.log 2>&1
 echo "trace rc=$?"
 # PMC passes kept separate (TCC slots: FETCH_SIZE 3, WRITE_SIZE 2 -- MI355X_MICROARCH.md) and never combined with tracing
