@@ -53,6 +53,7 @@ def lib():
         L.oracle_scene_create.argtypes = [C.c_uint32, _dp, _dp, _dp, _u32p, C.c_uint32, C.POINTER(OMaterial), C.c_uint32, C.POINTER(OTexture),
                                           C.c_uint32, C.POINTER(OLight), OVec3, _dp]
         L.oracle_scene_destroy.argtypes = [_P]; L.oracle_scene_destroy.restype = None
+        L.oracle_scene_set_options.argtypes = [_P, C.c_double, C.c_uint32]; L.oracle_scene_set_options.restype = None
         L.oracle_octree_num_nodes.argtypes = [_P]; L.oracle_octree_num_nodes.restype = C.c_uint32
         L.oracle_octree_max_depth.argtypes = [_P]; L.oracle_octree_max_depth.restype = C.c_uint32
         L.oracle_octree_own_total.argtypes = [_P]; L.oracle_octree_own_total.restype = C.c_uint32
@@ -79,9 +80,11 @@ def _v(p):
 
 class OracleScene:
     """pos/uv/nrm [n,3,3] f64, mat [n] u32, materials: dicts (ka,kd,ks,ns,kr,tex,bump), textures: [h,w,3] u8 arrays,
-    lights: (kind, intensity, (x,y,z)), origin (x,y,z), root (min_x,max_x,min_y,max_y,min_z,max_z)."""
+    lights: (kind, intensity, (x,y,z)), origin (x,y,z), root (min_x,max_x,min_y,max_y,min_z,max_z).
+    surface_offset / max_reflection_depth: the RayTracer options (raytracer.rs:17, :20); the defaults are the reference's constants."""
 
-    def __init__(self, pos, uv, nrm, mat, materials, textures, lights, origin, root=(-20.0, 20.0, -20.0, 20.0, -20.0, 20.0)):
+    def __init__(self, pos, uv, nrm, mat, materials, textures, lights, origin, root=(-20.0, 20.0, -20.0, 20.0, -20.0, 20.0),
+                 surface_offset=1e-4, max_reflection_depth=5):
         L = lib()
         pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 9); uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 9)
         nrm = np.ascontiguousarray(nrm, np.float64).reshape(-1, 9); mat = np.ascontiguousarray(mat, np.uint32)
@@ -99,6 +102,8 @@ class OracleScene:
         self.n_tris = pos.shape[0]
         self._h = _P(L.oracle_scene_create(pos.shape[0], _d(pos), _d(uv), _d(nrm), mat.ctypes.data_as(_u32p), len(materials), cm,
                                            len(self._tex_keep), ct, len(lights), cl, _v(origin), _d(r)))
+        if surface_offset != 1e-4 or max_reflection_depth != 5:
+            L.oracle_scene_set_options(self._h, float(surface_offset), int(max_reflection_depth))
         self.origin = tuple(map(float, origin))
 
     def __del__(self):

@@ -34,8 +34,10 @@ static inline ovec3 vnormalised(ovec3 a) { return vdiv(a, vlength(a)); }        
 #define RMAX(a, b) fmax((a), (b))
 
 #define F64_EPSILON 2.220446049250313e-16 /* f64::EPSILON, ray.rs:66,89 */
-static const double SURFACE_OFFSET = 0.0001;       /* raytracer.rs:17 */
-#define MAX_REFLECTION_DEPTH 5u                    /* raytracer.rs:20 */
+/* Defaults of the two RayTracer options (raytracer.rs:17, :20); each scene carries its own copy, settable by
+ * oracle_scene_set_options so that tests can check the product's non-default RrtOptions against the oracle. */
+#define DEFAULT_SURFACE_OFFSET 0.0001
+#define DEFAULT_MAX_REFLECTION_DEPTH 5u
 
 /* ------------------------------------------------------------------ data model */
 typedef struct { double min[3], max[3]; } oaabb;   /* aabb.rs:4-8 */
@@ -64,6 +66,8 @@ struct oracle_scene {
     otexture *tex; uint32_t n_tex;
     olight *lights; uint32_t n_lights;
     ovec3 origin;
+    double surface_offset;           /* raytracer.rs:17 */
+    uint32_t max_reflection_depth;   /* raytracer.rs:20 */
 };
 
 /* ------------------------------------------------------------------ Aabb, aabb.rs:25-60 */
@@ -171,6 +175,8 @@ oracle_scene *oracle_scene_create(uint32_t n_tris, const double *pos, const doub
     s->tex = malloc(sizeof(otexture) * (n_tex ? n_tex : 1)); memcpy(s->tex, tex, sizeof(otexture) * n_tex); s->n_tex = n_tex;
     s->lights = malloc(sizeof(olight) * (n_lights ? n_lights : 1)); memcpy(s->lights, lights, sizeof(olight) * n_lights); s->n_lights = n_lights;
     s->origin = origin;
+    s->surface_offset = DEFAULT_SURFACE_OFFSET;
+    s->max_reflection_depth = DEFAULT_MAX_REFLECTION_DEPTH;
     /* Octree::new, octree.rs:23-39 */
     push_aabb(s, aabb_new(root[0], root[1], root[2], root[3], root[4], root[5]));
     push_node(s, 0);
@@ -184,6 +190,11 @@ oracle_scene *oracle_scene_create(uint32_t n_tris, const double *pos, const doub
         push_triangle(s, i);
     }
     return s;
+}
+
+void oracle_scene_set_options(oracle_scene *s, double surface_offset, uint32_t max_reflection_depth) {
+    s->surface_offset = surface_offset;
+    s->max_reflection_depth = max_reflection_depth;
 }
 
 void oracle_scene_destroy(oracle_scene *s) {
@@ -340,7 +351,7 @@ static ovec3 get_normal_at_intersection(const oracle_scene *s, const otrihit *hi
 
 static int light_reaches_point(const oracle_scene *s, ovec3 origin, ovec3 normal, ovec3 target, ocounters *c) { /* raytracer.rs:164-188: true when NOT occluded */
     ovec3 direction = vsub(target, origin);
-    ovec3 new_origin = vadd(origin, vmul(normal, SURFACE_OFFSET));
+    ovec3 new_origin = vadd(origin, vmul(normal, s->surface_offset));
     oray ray = { new_origin, direction };
     double max_t = vlength(direction);
     otrihit h;
@@ -405,10 +416,10 @@ static ocolor get_ray_colour_recursive(const oracle_scene *s, ovec3 origin, ovec
     ovec3 local = v3((double)col.r * li.x, (double)col.g * li.y, (double)col.b * li.z);   /* raytracer.rs:67-71 */
 
     double reflectivity = m->kr;
-    if (reflectivity > 0.0 && depth < MAX_REFLECTION_DEPTH) {                  /* raytracer.rs:76 */
+    if (reflectivity > 0.0 && depth < s->max_reflection_depth) {       /* raytracer.rs:76 */
         double d_dot_n = vdot(direction, n);
         ovec3 reflect_dir = vnormalised(vsub(direction, vmul(vmul(n, 2.0), d_dot_n)));    /* raytracer.rs:79 */
-        ovec3 reflect_origin = vadd(p, vmul(n, SURFACE_OFFSET));               /* raytracer.rs:82 */
+        ovec3 reflect_origin = vadd(p, vmul(n, s->surface_offset));           /* raytracer.rs:82 */
         c->rays_reflect++;
         ocolor rc = get_ray_colour_recursive(s, reflect_origin, reflect_dir, depth + 1, c);
         ovec3 reflected = v3((double)rc.r, (double)rc.g, (double)rc.b);

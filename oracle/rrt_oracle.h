@@ -49,6 +49,9 @@ oracle_scene *oracle_scene_create(uint32_t n_tris, const double *pos, const doub
                                   uint32_t n_tex, const otexture *tex, uint32_t n_lights, const olight *lights,
                                   ovec3 origin, const double root[6]);
 void oracle_scene_destroy(oracle_scene *s);
+/* RayTracer options (raytracer.rs:17, :20): the shadow- and reflection-ray origin offset along the normal, and
+ * the recursion limit of get_ray_colour.  oracle_scene_create sets the reference's constants, 1e-4 and 5. */
+void oracle_scene_set_options(oracle_scene *s, double surface_offset, uint32_t max_reflection_depth);
 
 /* octree introspection (structure parity with the product's flattened tree) */
 uint32_t oracle_octree_num_nodes(const oracle_scene *s);

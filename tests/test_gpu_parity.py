@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import ASSETS, GOLDEN, channels, max_channel_diff, oracle_scene_for
+from conftest import ASSETS, GOLDEN, channels, lights_tuple, max_channel_diff, oracle_scene_for
 
 pytestmark = pytest.mark.gpu
 COLOUR_TOL = 1   # per RGB channel, BASELINE.json
@@ -136,9 +136,8 @@ def test_mirror_and_shadow_pixels_present(teapot_rt, teapot_oracle):
 
 def test_options_viewport_offset_depth(rrt, teapot, ob):
     lights = rrt.default_lights()
-    rt = rrt.RayTracer(teapot, lights, rrt.Vector3d(0.5, 2.5, -9.0), max_reflection_depth=2, viewport=(1.5, 1.0, 1.25))
+    rt = rrt.RayTracer(teapot, lights, rrt.Vector3d(0.5, 2.5, -9.0), surface_offset=3e-3, max_reflection_depth=2, viewport=(1.5, 1.0, 1.25))
     osc = oracle_scene_for(ob, rrt, teapot, lights, (0.5, 2.5, -9.0))
-    # the oracle hard-codes depth 5 / offset 1e-4 like the reference, so compare on a frame crop without mirror influence: rays only
     o = np.tile([0.5, 2.5, -9.0], (64, 1)); d = np.stack([np.linspace(-0.3, 0.6, 64), np.full(64, -0.12), np.ones(64)], -1)
     hit, t, u, v, tri = rt.intersect_rays(o, d)
     for i in range(64):
@@ -147,7 +146,15 @@ def test_options_viewport_offset_depth(rrt, teapot, ob):
     ref, _ = osc.render(96, 64, viewport=(1.5, 1.0, 1.25))
     gpu = rrt.RayTracer(teapot, lights, rrt.Vector3d(0.5, 2.5, -9.0), viewport=(1.5, 1.0, 1.25)).render(96, 64)
     assert_frame_close(gpu, ref, "viewport 1.5x1x1.25")
-    assert rt.render(96, 64).shape == (64, 96)
+    # the whole frame of the depth-2, offset-3e-3 raytracer against the oracle with the same options; the options must change the frame
+    pos, uv, nrm, mat = teapot.triangles()
+    osc2 = ob.OracleScene(pos, uv, nrm, mat, teapot.materials(), teapot.textures(), lights_tuple(lights), (0.5, 2.5, -9.0),
+                          surface_offset=3e-3, max_reflection_depth=2)
+    ref2, _ = osc2.render(96, 64, viewport=(1.5, 1.0, 1.25), n_threads=16)
+    got = rt.render(96, 64)
+    assert got.shape == (64, 96)
+    assert_frame_close(got, ref2, "viewport 1.5x1x1.25, depth 2, offset 3e-3")
+    assert (ref2 != ref).sum() > 20, "depth 2 / offset 3e-3 must change the frame"
 
 
 @pytest.mark.parametrize("name,w,h", [("model2.obj", 640, 480), ("model2.obj", 1920, 1080), ("model3.obj", 480, 360), ("model.obj", 333, 211)])

@@ -25,12 +25,12 @@ TEX = [np.full((2, 2, 3), 200, np.uint8)]
 ROOT10 = (-10.0, 10.0, -10.0, 10.0, -10.0, 10.0)
 
 
-def tiny_scene(ob, tris, root=ROOT10, lights=((0, 1.0, (0, 0, 0)),), mats=MAT, tex=TEX, mat_ids=None, uv=None, nrm=None):
+def tiny_scene(ob, tris, root=ROOT10, lights=((0, 1.0, (0, 0, 0)),), mats=MAT, tex=TEX, mat_ids=None, uv=None, nrm=None, **options):
     pos = np.asarray(tris, np.float64).reshape(-1, 3, 3)
     n = len(pos)
     uv = np.zeros((n, 3, 3)) if uv is None else np.asarray(uv, np.float64)
     nrm = np.tile([0.0, 0.0, -1.0], (n, 3, 1)) if nrm is None else np.asarray(nrm, np.float64)
-    return ob.OracleScene(pos, uv, nrm, np.zeros(n, np.uint32) if mat_ids is None else mat_ids, mats, tex, list(lights), (0, 0, -5), root)
+    return ob.OracleScene(pos, uv, nrm, np.zeros(n, np.uint32) if mat_ids is None else mat_ids, mats, tex, list(lights), (0, 0, -5), root, **options)
 
 
 # ------------------------------------------------------------------ Moller-Trumbore, ray.rs:56-94
@@ -201,18 +201,53 @@ def test_shadow_break_drops_later_lights(ob):
 
 
 def test_mirror_recursion_depth_and_quantisation(ob):
-    """Two facing mirrors: the recursion stops at depth 5 (raytracer.rs:20,76) and every level quantises to u8 (raytracer.rs:85-101)."""
+    """Two facing mirrors: the recursion stops at max_reflection_depth (5 by default, raytracer.rs:20,76) and every level quantises to u8
+    (raytracer.rs:85-101).  The mirrors' local colours differ (100 and 0) and kr = 0.75, so every extra bounce level changes the answer."""
     m1 = [(-8, -8, 5), (8, -8, 5), (0, 8, 5)]
     m2 = [(-8, -8, -8), (8, -8, -8), (0, 8, -8)]
     nrm = np.array([np.tile([0, 0, -1.0], (3, 1)), np.tile([0, 0, 1.0], (3, 1))])
-    mats = [dict(ka=(1, 1, 1), kd=(0, 0, 0), ks=(0, 0, 0), ns=-1.0, kr=0.5, tex=0, bump=-1)]
-    s = tiny_scene(ob, [m1, m2], lights=((0, 0.5, (0, 0, 0)),), mats=mats, nrm=nrm)
-    c = s.get_ray_colour((0, 0, -5), (0, 0, 1))
-    # local = 200*0.5 = 100 at every level; depth 5 is terminal: 100; then c = trunc(50 + c/2) five times
-    want = 100
-    for _ in range(5):
-        want = int(100 * 0.5 + want * 0.5)
-    assert c == (want << 16 | want << 8 | want)
+    mats = [dict(ka=(1, 1, 1), kd=(0, 0, 0), ks=(0, 0, 0), ns=-1.0, kr=0.75, tex=0, bump=-1),
+            dict(ka=(0, 0, 0), kd=(0, 0, 0), ks=(0, 0, 0), ns=-1.0, kr=0.75, tex=0, bump=-1)]
+    local = (100, 0)                                       # texel 200 * ka * ambient 0.5: level d hits m1 (even d) or m2 (odd d)
+
+    def want(depth):
+        c = local[depth % 2]                               # level `depth` is terminal: its local colour, no reflection
+        for d in range(depth - 1, -1, -1):                 # unwind: trunc(local * (1 - kr) + c * kr), exact in f64
+            c = int(local[d % 2] * 0.25 + c * 0.75)
+        return c
+
+    wants = []
+    for depth in [None] + list(range(9)):
+        opts = {} if depth is None else dict(max_reflection_depth=depth)
+        s = tiny_scene(ob, [m1, m2], lights=((0, 0.5, (0, 0, 0)),), mats=mats, mat_ids=np.array([0, 1], np.uint32), nrm=nrm, **opts)
+        w = want(5 if depth is None else depth)
+        assert s.get_ray_colour((0, 0, -5), (0, 0, 1)) == (w << 16 | w << 8 | w), depth
+        if depth is not None:
+            wants.append(w)
+    assert wants == [100, 25, 81, 38, 70, 46, 64, 50, 61]                   # depth 0 is the first mirror's own colour; every level counts
+
+
+def test_surface_offset_moves_the_shadow_ray_origin(ob):
+    """light_reaches_point (raytracer.rs:164-188) starts the shadow ray at point + normal * SURFACE_OFFSET (raytracer.rs:17).  A floor at z = 5 (normal
+    towards the light, -z), a thin occluder 0.5 above it over the probe point and a point light above both: with offset 1e-4 the shadow ray meets the
+    occluder, the light `break`s the loop and [Point, Ambient] gives black; with offset 1.0 the ray starts above the occluder (z = 4) and the probe is lit."""
+    floor = [(-8, -8, 5), (8, -8, 5), (0, 8, 5)]
+    occluder = [(-0.2, -0.3, 4.5), (0.2, -0.3, 4.5), (0, 0.2, 4.5)]
+    nrm = np.tile([0.0, 0.0, -1.0], (2, 3, 1))
+    mats = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=0, bump=-1)]   # ns = -1: no specular term (raytracer.rs:286)
+    tex = [np.full((2, 2, 3), 201, np.uint8)]
+    lights = [(1, 0.5, (0, -0.1, 0)), (0, 0.25, (0, 0, 0))]
+    probe_o, probe_d = (6.0, 0.0, -5.0), (-0.6, -0.01, 1.0)        # passes beside the occluder (x = 0.3 at z = 4.5), hits the floor at (0, -0.1, 5)
+    near = tiny_scene(ob, [floor, occluder], lights=lights, mats=mats, tex=tex, nrm=nrm)
+    far = tiny_scene(ob, [floor, occluder], lights=lights, mats=mats, tex=tex, nrm=nrm, surface_offset=1.0)
+    hit, t, u, v, tri = near.intersect(probe_o, probe_d)
+    assert hit and tri == 0 and abs(t - 10.0) < 1e-12
+    assert near.intersect((0, -0.1, 4.9999), (0, 0, -5), 5.0)[4] == 1   # the offset-1e-4 shadow ray meets the occluder at t = 0.09998
+    assert near.get_ray_colour(probe_o, probe_d) == 0x000000         # occluded point light first: the ambient term is never added
+    # lit: 201 * (ambient 0.25 + diffuse 0.5 * cos) with cos = n.l / |l| = 5 / 5.000001 (light 5 above the probe, straight up the normal):
+    # 201 * 0.7499999 = 150.74998 -> 150 per channel
+    assert far.get_ray_colour(probe_o, probe_d) == 0x969696
+    assert tiny_scene(ob, [floor, occluder], lights=lights, mats=mats, tex=tex, nrm=nrm, surface_offset=1e-4).get_ray_colour(probe_o, probe_d) == 0
 
 
 # ------------------------------------------------------------------ frame driver, engine.rs:146-158, 186-255
