@@ -720,7 +720,7 @@ int create_raytracer(const rrt_light* lights, uint32_t n_lights, rrt_vec3 origin
     DevScene& S = rt->scene;
     S.cull_enabled = (o.flags & RRT_FLAG_NO_CULL) ? 0u : 1u;
     S.cull_half_over_limit = S.cull_limit > 0.0f ? 0.5f / S.cull_limit : 0.0f;
-    S.inner_shrink = (S.cull_enabled && (rt->all_inside_root || std::getenv("RRT_FORCE_CERTAIN_HIT") /* developer: shows what the flag guards against */) && !std::getenv("RRT_NO_CERTAIN_HIT")) ? (float)(2.0 * rt->filter_pad) : 0.0f;   // 2 x the pad the boxes were built with; render.hip, single-candidate child test
+    S.inner_shrink = (S.cull_enabled && rt->all_inside_root) ? (float)(2.0 * rt->filter_pad) : 0.0f;   // 2 x the pad the boxes were built with; render.hip, single-candidate child test
     S.n_suspects = rt->n_suspects;
     S.n_lights = n_lights; S.max_reflection_depth = o.max_reflection_depth; S.stack_levels = max_depth > 1 ? max_depth - 1 : 1;   // (stack_levels: only internal nodes push a frame; the deepest level holds leaves)
     S.origin[0] = origin.x; S.origin[1] = origin.y; S.origin[2] = origin.z;

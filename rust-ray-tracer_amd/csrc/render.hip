@@ -17,7 +17,7 @@
 //   * one lane = one ray; one 64-lane wave = the 8x8 sub-sample rays of a 4x4-pixel tile; one wave per workgroup.
 //   * the recursion of ray.rs:104-168 is an explicit per-lane stack in LDS (own_t, own_slot, sorted-children word,
 //     first_child per level), laid out [level][field][lane] so every access is bank-conflict free.
-//   * the wave walks the octree NODE-COHERENTLY: each step picks one pending node (the first pending lane's), and
+//   * the wave walks the octree NODE-COHERENTLY: each step picks one pending node (the deepest pending lane's), and
 //     every lane parked at that node processes it together.  Node record, the node's triangles and its children's
 //     boxes are then wave-uniform, so they are fetched with SCALAR loads (s_load via the constant address space)
 //     into SGPRs and cost no vector-memory traffic; VALU does only the f64 math.
@@ -116,13 +116,9 @@ __device__ __forceinline__ double quot(double num, double den, double r) {
 // 16-SGPR tuple is spilled and reloaded WITH the tuple (16 v_writelane / v_readlane per use of one pointer once SGPRs run short, which they do in
 // the own-list loops: box bursts take 32-64 of the 102).  An empty asm makes each pointer a value of its own, 2 SGPRs, spilled alone.
 template <class T> __device__ __forceinline__ T* own_sgprs(T* p) {
-#ifdef RRT_NO_OWN_SGPRS
-    return p;
-#else
     unsigned long long r = (unsigned long long)p;
     asm volatile("" : "+s"(r));
     return (T*)r;
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------ LDS stack
@@ -323,29 +319,16 @@ __device__ __forceinline__ bool slab32(const UBox& b, const Ray32& r) {
     const float tmax = fminf(fminf(fx, fy), fz);
     return tmin <= tmax;
 }
-// Wave-uniform box, its record's first six dwords as three SGPR pairs p0 = {cx, cy}, p1 = {cz, hx}, p2 = {hy, hz}: five packed FMAs give all nine
-// values (v_pk_fma_f32 with an SGPR-pair operand issues in the time of ONE v_fma_f32 with an SGPR operand -- 4.5 cycles per SIMD, measured,
-// tools/probes/issue_probe.hip; min/max cost as much, hence the clamp in place of a separate max with 0): 7 VALU instructions where the plain form
-// above takes 13.
-__device__ __forceinline__ void slab32_pk(unsigned long long p0, unsigned long long p1, unsigned long long p2, const Ray32& r, float& tmin, float& tmax) {
-    f32x2 T, TZ, X, Y, Z;
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(T) : "s"(p0), "v"(r.i01), "v"(r.n01));                                        // {cx ix + nx, cy iy + ny}
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(TZ) : "s"(p1), "v"(r.izaz), "v"(r.nz0));                                     // {cz iz + nz, (unused)}
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0] neg_lo:[1,0,0]" : "=v"(X) : "s"(p1), "v"(r.a01), "v"(T));    // tcx -/+ hx |ix|
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,1] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "=v"(Y) : "s"(p2), "v"(r.a01), "v"(T));    // tcy -/+ hy |iy|
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,1,0] neg_lo:[1,0,0]" : "=v"(Z) : "s"(p2), "v"(r.izaz), "v"(TZ));  // tcz -/+ hz |iz|
-    asm("v_max3_f32 %0, %1, %2, %3 clamp" : "=v"(tmin) : "v"(X.x), "v"(Y.x), "v"(Z.x));
-    tmax = fminf(fminf(X.y, Y.y), Z.y);
-}
 __device__ __forceinline__ unsigned long long sgpr_pair(uint32_t lo, uint32_t hi) { return ((unsigned long long)hi << 32) | lo; }
 // ---- the box test as ONE asm block (round 3).  Written as one asm statement per instruction (round 2), every dependent pair picked up a compiler
 // s_nop: the hazard recognizer cannot see into inline asm, counts an asm statement as zero wait states and assumes the worst (a partial-register
 // write) of every asm that produces a VGPR -- 3-4 s_nop per box, 0.36 G per 100 k-soup frame, a quarter of the test's instructions, none of them needed
 // by the hardware (full-width VALU results forward with the ordinary interlock).  In one block nothing is inserted.  The temporaries are PINNED
 // (v118..v125): sub-registers of a 64-bit operand cannot be named in an asm template, v_max3/v_min3 need the halves of the packed results.
-#ifndef RRT_NO_FUSED_BOX
-#define RRT_FUSED_BOX 1
-#endif
+// The wave-uniform box is its record's first six dwords as three SGPR pairs p0 = {cx, cy}, p1 = {cz, hx}, p2 = {hy, hz}: five packed FMAs give all
+// nine values (v_pk_fma_f32 with an SGPR-pair operand issues in the time of ONE v_fma_f32 with an SGPR operand -- 4.5 cycles per SIMD, measured,
+// tools/probes/issue_probe.hip; min/max cost as much, hence the clamp in place of a separate max with 0): 7 VALU instructions where the per-lane form
+// above (slab32) takes 13.
 #define RRT_BOX_TMP "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125"
 #define RRT_BOX_SLAB                                                                                                                     \
     "v_pk_fma_f32 v[118:119], %[p0], %[i01], %[n01]\n\t"                                          /* T  = {cx ix + nx, cy iy + ny} */   \
@@ -366,7 +349,6 @@ __device__ __forceinline__ unsigned long long box_mask(unsigned long long p0, un
 // burst are tested from the LAST to the first and each result is shifted in from below (acc = 2 acc + hit: one v_addc_co_u32 with the compare's mask
 // as carry-in; the wave's word likewise with s_addc_u32), so box i ends up at bit i whatever the count.
 __device__ __forceinline__ void box_test_shift(unsigned long long p0, unsigned long long p1, unsigned long long p2, const Ray32& r, uint32_t& lane_acc, uint32_t& wave_acc) {
-#ifdef RRT_FUSED_BOX
     unsigned long long m;
     asm(RRT_BOX_SLAB
         "v_cmp_le_f32_e64 %[m], v124, v125\n\t"
@@ -375,17 +357,9 @@ __device__ __forceinline__ void box_test_shift(unsigned long long p0, unsigned l
     // (the wave's word in a statement of its own: with the scalar accumulator as an in/out operand of the block above the backend fails with
     //  "illegal VGPR to SGPR copy"; an SGPR dependency between two asm statements costs no s_nop)
     asm("s_cmp_lg_u64 %1, 0\n\ts_addc_u32 %0, %0, %0" : "+s"(wave_acc) : "s"(m) : "scc");
-#else
-    float tmin, tmax;
-    slab32_pk(p0, p1, p2, r, tmin, tmax);
-    unsigned long long m;
-    asm("v_cmp_le_f32_e64 %1, %2, %3\n\tv_addc_co_u32_e64 %0, vcc, %0, %0, %1" : "+v"(lane_acc), "=&s"(m) : "v"(tmin), "v"(tmax) : "vcc");
-    asm("s_cmp_lg_u64 %1, 0\n\ts_addc_u32 %0, %0, %0" : "+s"(wave_acc) : "s"(m) : "scc");
-#endif
 }
 // the reach filter's form: the result lands at bit k (children are often absent, so nothing is shifted)
 template <int k> __device__ __forceinline__ void box_test_bit(unsigned long long p0, unsigned long long p1, unsigned long long p2, const Ray32& r, uint32_t& lane_bits, uint32_t& wave_bits) {
-#ifdef RRT_FUSED_BOX
     unsigned long long m; uint32_t t;
     asm(RRT_BOX_SLAB
         "v_cmp_le_f32_e64 %[m], v124, v125\n\t"
@@ -395,24 +369,11 @@ template <int k> __device__ __forceinline__ void box_test_bit(unsigned long long
         "s_cselect_b32 %[t], %[bit], 0\n\t"
         "s_or_b32 %[wb], %[wb], %[t]"
         : [lb] "+v"(lane_bits), [wb] "+s"(wave_bits), [m] "=&s"(m), [t] "=&s"(t) : RRT_BOX_IN(p0, p1, p2, r), [k] "n"(k), [bit] "n"(1 << k) : "scc", RRT_BOX_TMP);
-#else
-    float tmin, tmax;
-    slab32_pk(p0, p1, p2, r, tmin, tmax);
-    const bool h = tmin <= tmax;
-    lane_bits |= h ? (1u << k) : 0u;
-    wave_bits |= (__builtin_amdgcn_ballot_w64(h) != 0ull) ? (1u << k) : 0u;
-#endif
 }
 __device__ __forceinline__ unsigned long long slab32_u_mask(const UBox& b, const Ray32& r) {      // a wave-uniform box held as a UBox (super-cluster records): hit mask
     const unsigned long long p0 = sgpr_pair(__builtin_bit_cast(uint32_t, b.cx), __builtin_bit_cast(uint32_t, b.cy)), p1 = sgpr_pair(__builtin_bit_cast(uint32_t, b.cz), __builtin_bit_cast(uint32_t, b.hx)),
                              p2 = sgpr_pair(__builtin_bit_cast(uint32_t, b.hy), __builtin_bit_cast(uint32_t, b.hz));
-#ifdef RRT_FUSED_BOX
     return box_mask(p0, p1, p2, r);
-#else
-    float tmin, tmax;
-    slab32_pk(p0, p1, p2, r, tmin, tmax);
-    return __builtin_amdgcn_ballot_w64(tmin <= tmax);
-#endif
 }
 
 // Exactness guard: must the index filter stay off for this ray?  Only rays that start at the raytracer's origin can be
@@ -553,22 +514,18 @@ __device__ __forceinline__ Bundle make_bundle(bool active, V3 o, V3 d, const Ray
     return B;
 }
 // Is the bundle worth testing boxes against (lane-filter kernel: long own lists switch to boxes in lanes when it is)?  Every axis: directions of
-// one sign, reciprocal directions within RRT_TIGHT_INV of the smallest, anchor spread below `slack` (RRT_TIGHT_SLACK of the filter's coordinate limit)
+// one sign, reciprocal directions within kTightInv of the smallest, anchor spread below `slack` (kTightSlack of the filter's coordinate limit)
 // in space.  A speed heuristic only: both filters are exact.  Tuned on the soups with the final kernels (1 M soup @4K, slack as a fraction of the
 // limit: 1/16384 27.5 ms, 1/1024 26.9, 1/384 26.5, 1/256 26.3, 1/192 26.7, 1/128 27.6, 1/64 33.8 -- a cliff, hence the margin; reciprocal spread
 // 0.1 -> 1.6: -0.3 ms; the 100 k soup moves by 1 %, the teapot's kernel does not use it).
-#ifndef RRT_TIGHT_INV
-#define RRT_TIGHT_INV 1.6f
-#endif
-#ifndef RRT_TIGHT_SLACK
-#define RRT_TIGHT_SLACK (1.0f / 384.0f)
-#endif
+constexpr float kTightInv = 1.6f;
+constexpr float kTightSlack = 1.0f / 384.0f;
 __device__ __forceinline__ bool bundle_is_tight(const Bundle& B, float slack) {
     bool ok = true;
 #define RRT_TIGHT(il, ih, ml, mh)                                                                               \
     {                                                                                                           \
         const float lo = fminf(fabsf(il), fabsf(ih));                                                           \
-        ok = ok && (il > 0.0f) == (ih > 0.0f) && lo > 0.0f && (ih - il) <= RRT_TIGHT_INV * lo && (mh - ml) <= slack * lo;  \
+        ok = ok && (il > 0.0f) == (ih > 0.0f) && lo > 0.0f && (ih - il) <= kTightInv * lo && (mh - ml) <= slack * lo;  \
     }
     RRT_TIGHT(B.ilx, B.ihx, B.mlx, B.mhx) RRT_TIGHT(B.ily, B.ihy, B.mly, B.mhy) RRT_TIGHT(B.ilz, B.ihz, B.mlz, B.mhz)
 #undef RRT_TIGHT
@@ -667,17 +624,6 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
     uint32_t cur = 0;        // node this lane has to enter next
     uint32_t crank = 0;      // position of `cur` among its parent's sorted children (0 = the nearest): tie-break of the pick below
     uint32_t sp = 0;         // number of frames on this lane's stack == depth of `cur`
-#ifdef RRT_PREFETCH_NODES
-    // Node records come through dependent SCALAR loads at the start of every visit, and on the soups most of them miss the L2 (140 k nodes x 96 B):
-    // the s_memtime stamps put 42 % of a wave's time between "pick the node" and "its record is here".  A lane knows the node it will enter next as
-    // soon as it has pushed / unwound -- usually many visits before the wave gets to it -- so it touches that record with a VECTOR load then (the
-    // texture-address path idles in this kernel: TA busy 8 %, profiles/r03_mem_lane100k.json); the scalar load later finds the line in the L2.  The
-    // loaded words are kept (fake use at the next prefetch) so that the register is not recycled while the load is in flight.
-    uint32_t pf_tail = 0;
-#if RRT_PREFETCH_NODES > 1
-    uint32_t pf_head = 0;
-#endif
-#endif
     double ret_t = kInf; uint32_t ret_slot = kNone;
     const RRT_CONSTANT DevNode* nodes = (const RRT_CONSTANT DevNode*)own_sgprs(S.nodes);
     const RRT_CONSTANT DevTriGeom* geom = (const RRT_CONSTANT DevTriGeom*)own_sgprs(S.geom);
@@ -693,30 +639,19 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
     // The lane-filter kernel builds the bundle too (about 150 instructions per walk): where the wave's rays form a tight bundle -- a primary tile,
     // the shadow rays of a tile towards one light -- its LONG own lists (the straddler lists of the upper nodes: thousands of triangles at the root
     // of a large soup) are searched with boxes in lanes, 64 boxes per instruction, instead of one wave-uniform box at a time.
-#ifndef RRT_BUNDLE_TAU
-#define RRT_BUNDLE_TAU (any_ok ? 1.0f : 0.0f)
-#endif
-#ifndef RRT_HYBRID_MIN_SUPERS
-#define RRT_HYBRID_MIN_SUPERS 2u
-#endif
-#ifndef RRT_HYBRID_MIN_TRIS
-#define RRT_HYBRID_MIN_TRIS 8u
-#endif
     Bundle BU{};
     bool long_lists_in_lanes = false;
-    if constexpr (kBundle) BU = make_bundle(active, o, d, r32, RRT_BUNDLE_TAU);
-#ifndef RRT_NO_HYBRID
+    if constexpr (kBundle) BU = make_bundle(active, o, d, r32, any_ok ? 1.0f : 0.0f);
     if constexpr (!kBundle) {
         // (parked in LDS rather than held in 15 SGPRs for the whole walk: scalar registers are what the lane-filter kernel is shortest of)
         const Bundle B0 = make_bundle(active, o, d, r32, any_ok ? 1.0f : 0.0f);
-        long_lists_in_lanes = bundle_is_tight(B0, S.cull_limit * RRT_TIGHT_SLACK);
+        long_lists_in_lanes = bundle_is_tight(B0, S.cull_limit * kTightSlack);
         if (stk.lane == 0u) {
             float* q = stk.park();
             q[0] = B0.cx; q[1] = B0.cy; q[2] = B0.cz; q[3] = B0.ilx; q[4] = B0.ihx; q[5] = B0.ily; q[6] = B0.ihy; q[7] = B0.ilz; q[8] = B0.ihz;
             q[9] = B0.mlx; q[10] = B0.mhx; q[11] = B0.mly; q[12] = B0.mhy; q[13] = B0.mlz; q[14] = B0.mhz;
         }
     }
-#endif
 
 #if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
     prof.secondary = !(o.x == S.origin[0] && o.y == S.origin[1] && o.z == S.origin[2]); prof.pad = (double)S.cull_limit / 131072.0;   // pad = magnitude / 2^15, cull_limit = 4 magnitude
@@ -726,44 +661,19 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
     for (;;) {
         const unsigned long long pending = __builtin_amdgcn_ballot_w64(!done);
         if (pending == 0) break;
-#ifndef RRT_LEADER_FIRST   // default: a wave-wide reduction picks the node (below); -DRRT_LEADER_FIRST = the first pending lane's node (round 1: 6 % slower than smallest-id on the 100k soup)
         // WHICH pending node the wave visits next decides how many lanes share a visit, and a visit costs the same ~800 instructions whoever takes part.
         // Round 3: the DEEPEST pending lane's node (ties: smallest id) -- depth-first for the wave as a whole.  Lanes deep in the tree finish their
         // subtrees and come back up to where the others are parked before those nodes are processed, so a node is visited once with everybody who will
         // ever need it, instead of early with few lanes and again for the late-comers (rounds 1-2 took the smallest id, a breadth-first-like order:
         // 17.8 of 64 lanes per visit on the 100 k soup).  Any order gives the same per-lane results.  100 k soup 11.8 -> 8.9 ms, 1 M soup 26.0 -> 22.9 ms,
-        // teapot 0.894 -> 0.882 ms (profiles/r03_ab_pick_policy.txt; largest id first: 8.95 / 23.5; shallowest first: 11.87 / 26.06).
-#ifndef RRT_WAVE_FOOTPRINT
-#define RRT_WAVE_FOOTPRINT 0
-#endif
-#ifndef RRT_PICK_POLICY
-#define RRT_PICK_POLICY 5
-#endif
-#ifndef RRT_PICK_POLICY_BUNDLE
-#define RRT_PICK_POLICY_BUNDLE 5   /* the bundle-filter kernel (coherent frames) hardly cares: teapot 0.872 -> 0.865 ms with the lane-filter kernel's order, 4K unchanged */
-#endif
-        constexpr int kPick = kBundle ? RRT_PICK_POLICY_BUNDLE : RRT_PICK_POLICY;
-        uint32_t unode;
-        if constexpr (kPick == 5) {
-            // deepest pending lane first; among those the lane that has come least far through its parent's sorted children (its node is the nearer one: lanes that
-            // finish it may still move on to the farther ones, never back), then the smaller id.  23 bits of the id in the key: larger scenes only lose the last tie-break.
-            const uint32_t key = done ? 0xFFFFFFFFu : (((63u - sp) << 26) | (crank << 23) | (cur & 0x007FFFFFu));
-            const uint32_t kmin = wave_min_u32(key);
-            unode = (uint32_t)__builtin_amdgcn_readlane((int)cur, __builtin_ctzll(__builtin_amdgcn_ballot_w64(key == kmin)));
-        } else if constexpr (kPick == 3) {
-            // deepest pending lane first, ties to the smaller id.  The key keeps 26 bits of the id; the node itself is read from a lane that holds the
-            // winning key, so larger scenes only lose the tie-break (any pending lane's node is a valid pick).
-            const uint32_t key = done ? 0xFFFFFFFFu : (((63u - sp) << 26) | (cur & 0x03FFFFFFu));
-            const uint32_t kmin = wave_min_u32(key);
-            unode = (uint32_t)__builtin_amdgcn_readlane((int)cur, __builtin_ctzll(__builtin_amdgcn_ballot_w64(key == kmin)));
-        } else if constexpr (kPick == 0) unode = wave_min_u32(done ? 0xFFFFFFFFu : cur);                          // rounds 1-2: smallest id
-        else if constexpr (kPick == 1) unode = ~wave_min_u32(done ? 0xFFFFFFFFu : ~cur);                          // largest id (newest nodes first)
-        else if constexpr (kPick == 2) unode = wave_min_u32(done ? 0xFFFFFFFFu : ((sp << 26) | cur)) & 0x03FFFFFFu;   // shallowest first (ids < 2^26)
-        else unode = 0x03FFFFFFu - (wave_min_u32(done ? 0xFFFFFFFFu : (((63u - sp) << 26) | (0x03FFFFFFu - cur))) & 0x03FFFFFFu);   // deepest first, ties to the larger id
-#else
-        const int leader = __builtin_ctzll(pending);
-        const uint32_t unode = __builtin_amdgcn_readlane(cur, leader);   // wave-uniform node id
-#endif
+        // teapot 0.894 -> 0.882 ms (profiles/r03_ab_pick_policy.txt; largest id first: 8.95 / 23.5; shallowest first: 11.87 / 26.06).  The bundle-filter
+        // kernel (coherent frames) hardly cares: teapot 0.872 -> 0.865 ms with the lane-filter kernel's order, 4K unchanged.  Round 1 measured the first
+        // pending lane's node in place of a wave-wide reduction: 6 % slower than smallest-id on the 100 k soup.  The other orders were removed.
+        // Deepest pending lane first; among those the lane that has come least far through its parent's sorted children (its node is the nearer one: lanes that
+        // finish it may still move on to the farther ones, never back), then the smaller id.  23 bits of the id in the key: larger scenes only lose the last tie-break.
+        const uint32_t key = done ? 0xFFFFFFFFu : (((63u - sp) << 26) | (crank << 23) | (cur & 0x007FFFFFu));
+        const uint32_t kmin = wave_min_u32(key);
+        const uint32_t unode = (uint32_t)__builtin_amdgcn_readlane((int)cur, __builtin_ctzll(__builtin_amdgcn_ballot_w64(key == kmin)));
         const UHead N = load_uhead(nodes + unode);
         const uint32_t fc = N.first_child, sb = N.sup_begin, sc = N.sup_count, fl = N.flags;
         PROF_ADD(0, 1); PROF_ADD(1, __popcll(__ballot(!done && cur == unode)));
@@ -798,7 +708,7 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
                                 box_test_bit<k>(sgpr_pair(v[off], v[off + 1]), sgpr_pair(v[off + 2], v[off + 3]), sgpr_pair(v[off + 4], v[off + 5]), r32, lane_reach, reach);  \
                             }                                                                                                      \
                         }
-                        // (Children are often absent, so the results are OR-ed in at their own bit rather than shifted in as box_hit_shift does: the
+                        // (Children are often absent, so the results are OR-ed in at their own bit rather than shifted in as box_test_shift does: the
                         // zeros to shift in for absent children cost more than the shift saves.  Measured, teapot / 100 k soup / 1 M soup: the packed
                         // arithmetic gains the lane-filter kernel 2 % on the soups and costs the bundle-filter kernel 4 % on the teapot -- register
                         // pairs in a kernel that is short of VGPRs -- so each kernel gets the form that suits it.)
@@ -961,10 +871,9 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
         // Boxes in lanes: all 64 lanes work here (wave-uniform control flow), each lane testing ONE box of the current level against the
         // wave's ray bundle; survivors are compacted and expanded to the next level; only the triangles that survive are tested, by the
         // lanes parked at this node.
+        constexpr uint32_t kHybridMinSupers = 2u, kHybridMinTris = 8u;
         bool in_lanes = kBundle;
-#ifndef RRT_NO_HYBRID
-        if constexpr (!kBundle) in_lanes = long_lists_in_lanes && (sc >= RRT_HYBRID_MIN_SUPERS || N.s0_count > RRT_HYBRID_MIN_TRIS);
-#endif
+        if constexpr (!kBundle) in_lanes = long_lists_in_lanes && (sc >= kHybridMinSupers || N.s0_count > kHybridMinTris);
         if (in_lanes) {
         if ((fl & 0x100u) && sc) {
             const uint32_t lane = stk.lane, sub = lane & 7u, grp = lane >> 3;
@@ -1049,11 +958,6 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
                             continue;
                         }
                     }
-#ifdef RRT_SKIP_CBOX_MAX
-                    // A short list in one cluster (90 % of a soup's internal nodes hold <= 8 triangles of their own): its cluster box is one more dependent
-                    // scalar load and test in front of the triangle boxes, which are few -- go to them directly.
-                    if (sc == 1 && tn <= RRT_SKIP_CBOX_MAX) { own_cluster_lane(PROF_ARG tboxes, geom, tb, tn, r32, o, d, own_t, own_slot, own_pos); SP = SN; continue; }
-#endif
                     if (hs_mask != 0ull) {
                         // the (up to) 8 cluster boxes of this super-cluster in bursts of 4; cluster c covers slots tb+8c .. tb+8c+7
                         const RRT_CONSTANT u32x16* cb = (const RRT_CONSTANT u32x16*)(cboxes + (tb >> 3));
@@ -1140,14 +1044,6 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
                     returning = false;                                   // child returned None -> try the next child
                 }
             }
-#ifdef RRT_PREFETCH_NODES
-            asm volatile("" :: "v"(pf_tail));
-            if (!done) pf_tail = *reinterpret_cast<const volatile uint32_t*>(reinterpret_cast<const char*>((const DevNode*)nodes + cur) + 64);
-#if RRT_PREFETCH_NODES > 1
-            asm volatile("" :: "v"(pf_head));
-            if (!done) pf_head = *reinterpret_cast<const volatile uint32_t*>((const DevNode*)nodes + cur);
-#endif
-#endif
             PROF_T(3);
         }
     }
@@ -1399,11 +1295,7 @@ __device__ __forceinline__ V3 specular_term(double sw, double intensity, V3 norm
     if (sw != -1.0) {
         const V3 r = ((normal * 2.0) * dot(normal, l)) - l;
         const double r_dot_v = dot(r, v);
-#ifdef RRT_ABL_NOPOW     /* ablation build only: timing experiment, wrong pixels */
-        if (r_dot_v > 0.0) return (ks * intensity) * (r_dot_v / (length(r) * len_v));
-#else
         if (r_dot_v > 0.0) return (ks * intensity) * pow(r_dot_v / (length(r) * len_v), sw);
-#endif
     }
     return mk(0.0, 0.0, 0.0);
 }
@@ -1470,9 +1362,6 @@ __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, co
                     }
                     n = normalised(nn);                                                  // raytracer.rs:161
                     li = 0;                                                              // compute_lighting_intensity, raytracer.rs:199-203
-#ifdef RRT_ABL_NOLIGHTS  /* ablation build only: primary hit set-up, then stop */
-                    li = S.n_lights;
-#endif
                 }
             } else {
                 // --- result of the shadow ray for point light li (raytracer.rs:232-237): occluded -> `break` out of the whole light loop
@@ -1503,12 +1392,6 @@ __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, co
                     const V3 vdir = neg(seg_d);
                     const double len_n = length(n), len_v = length(vdir);                // |normal|, |v|: the reference recomputes them per light, same value
                     V3 I = mk(0.0, 0.0, 0.0);
-#ifdef RRT_ABL_NOLIGHTS
-                    I = mk(1.0, 1.0, 1.0); n_eval = 0;
-#endif
-#ifdef RRT_ABL_NOLIGHTMATH   /* ablation build only: shadow rays traced, light arithmetic skipped */
-                    I = mk(0.5, 0.5, 0.5); n_eval = 0;
-#endif
                     for (uint32_t k = 0; k < n_eval; ++k) {
                         const DevLight& L = S.lights[k];
                         if (L.kind == 0u) {                                              // Ambient, raytracer.rs:207-209
@@ -1555,18 +1438,10 @@ __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, co
 // Waves per SIMD (register budget) per traversal variant, measured on MI355X with the code-generation switches of the Makefile: 4 everywhere
 // (128 VGPRs).  The lane-filter kernel ran best at 5 (96 VGPRs) until its spills were cut down; now 4 is 2 % faster on both soups (12.3 -> 12.1 ms,
 // 28.2 -> 27.7 ms) and 6 is 20 % slower.  The bundle-filter kernel: 3 -> +20 %, 5 -> +11 %.  The ray walk: 3 -> +11 %, 5 -> +21 %.
-#ifndef RRT_WAVES_LANE
-#define RRT_WAVES_LANE 4
-#endif
-#ifndef RRT_WAVES_BUNDLE
-#define RRT_WAVES_BUNDLE 4
-#endif
-#ifndef RRT_WAVES_RAY
-#define RRT_WAVES_RAY 4
-#endif
+constexpr int kWavesPerSimd = 4;
 #if RRT_TU_FRAME || RRT_TU_LANE
 template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWalk == kWalkBundle ? RRT_WAVES_BUNDLE : kWalk == kWalkLane ? RRT_WAVES_LANE : RRT_WAVES_RAY) void render_kernel(const DevScene S, const FrameParams F, uint32_t* __restrict__ out) {
+__global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScene S, const FrameParams F, uint32_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const uint32_t lane = threadIdx.x;
     const Stack stk{lds + kParkBytes, lane};
@@ -1582,13 +1457,9 @@ __global__ __launch_bounds__(64, kWalk == kWalkBundle ? RRT_WAVES_BUNDLE : kWalk
     const uint32_t tile = F.tile_begin + local_tile * F.world + F.rank;
     const bool tile_ok = tile < F.tile_end;
     const uint32_t tx = tile_ok ? tile % F.tiles_x : 0, ty = tile_ok ? tile / F.tiles_x : 0;
-#if RRT_WAVE_FOOTPRINT == 1        // 8 x 2 pixels per wave (experiment: 32-byte row segments instead of 16)
-    const uint32_t px = tx * 8 + (pix & 7u);
-    const uint32_t py = ty * 8 + quad * 2 + (pix >> 3);
-#else                               // 4 x 4 pixels per wave
+    // 4 x 4 pixels per wave (8 x 2, for 32-byte row segments instead of 16, was measured and removed: DESIGN.md section 4)
     const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
     const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
-#endif
     const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
     // put_pixel (engine.rs:146-158): new_x = x + W/2, new_y = H - (y + H/2); draw_scene loops x in [-W/2, W/2), y in [-H/2, H/2)
     // (engine.rs:198,205).  Pixels with no (x,y) in range stay 0 (Canvas::new, engine.rs:135): row 0 (rows 0,1 for odd H) and,
@@ -1606,13 +1477,11 @@ __global__ __launch_bounds__(64, kWalk == kWalkBundle ? RRT_WAVES_BUNDLE : kWalk
 #endif
     const uint32_t c = trace_colour<kWalk, kGroups>(PROF_ARG S, stk, traced, ld3(S.origin), dir);
 #if defined(RRT_PROFILE) && defined(RRT_PROF_WAVETIME)
-#ifndef RRT_MEMTIME_TICKS_PER_US
-#define RRT_MEMTIME_TICKS_PER_US 100ull
-#endif
     {   // developer build: how long each wave lived (s_memrealtime: the constant 100 MHz clock; s_memtime counts shader cycles), one count per wave into
         // power-of-two buckets of microseconds, the longest in slot 16
+        constexpr unsigned long long kRealtimeTicksPerUs = 100ull;
         const unsigned long long ticks = __builtin_amdgcn_s_memrealtime() - wave_rt0;
-        const uint32_t us = (uint32_t)(ticks / RRT_MEMTIME_TICKS_PER_US);
+        const uint32_t us = (uint32_t)(ticks / kRealtimeTicksPerUs);
         const uint32_t bucket = us < 2u ? 0u : (uint32_t)(31 - __builtin_clz(us));                 // 0: < 2 us, b: [2^b, 2^(b+1)) us
         if (lane == 0) { atomicAdd(S.prof + (bucket < 15u ? bucket : 15u), 1ull); atomicMax(S.prof + 16, ticks); }
     }

@@ -1,5 +1,5 @@
 """Developer tool: registers, spills, scratch and occupancy of every kernel of render.hip (hipcc -Rpass-analysis=kernel-resource-usage).
-   python tools/kernel_resources.py [extra hipcc flags, e.g. -DRRT_WAVES_LANE=4]"""
+   python tools/kernel_resources.py [extra hipcc flags, e.g. -DRRT_TU=3]"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "rust-ray-tracer_amd", "csrc")
