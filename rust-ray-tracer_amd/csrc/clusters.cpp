@@ -27,12 +27,17 @@ constexpr double kPadFraction = 1.0 / 32768.0;   // 2^-15 of the scene magnitude
 
 struct TriBox { double lo[3], hi[3], c[3]; };
 
+// f64::min / max (aabb.rs:25-47): a NaN operand yields the other one, as the GPU set-up's fmin / fmax (scene_build.hip) -- std::min / max would
+// keep a NaN in first place, and the two set-ups' triangle boxes would differ for a triangle with a NaN vertex
+inline double rmin(double a, double b) { return a != a ? b : b != b ? a : std::min(a, b); }
+inline double rmax(double a, double b) { return a != a ? b : b != b ? a : std::max(a, b); }
+
 TriBox tri_box(const Triangle& t) {
     TriBox b;
     const double x[3][3] = {{t.v1.x, t.v2.x, t.v3.x}, {t.v1.y, t.v2.y, t.v3.y}, {t.v1.z, t.v2.z, t.v3.z}};
     for (int k = 0; k < 3; k++) {
-        b.lo[k] = std::min(x[k][0], std::min(x[k][1], x[k][2]));
-        b.hi[k] = std::max(x[k][0], std::max(x[k][1], x[k][2]));
+        b.lo[k] = rmin(x[k][0], rmin(x[k][1], x[k][2]));
+        b.hi[k] = rmax(x[k][0], rmax(x[k][1], x[k][2]));
         b.c[k] = (b.lo[k] + b.hi[k]) * 0.5;
         if (b.c[k] != b.c[k]) b.c[k] = 0.0;   // NaN coordinates: keep (centroid, position) a strict total order (the splits below rank by it)
     }

@@ -30,6 +30,15 @@ static_assert(sizeof(DevNode) == 96, "DevNode must be 96 bytes");
 
 struct DevTriGeom { double v1[3], e1[3], e2[3]; uint32_t pos, _pad; };   // 80 B; pos = position in the node's own list (tie-break, ray.rs:124)
 static_assert(sizeof(DevTriGeom) == 80, "DevTriGeom must be 80 bytes");
+// An edge of a triangle with a NaN or infinite vertex can be NaN, and which NaN a subtraction returns (sign, payload) differs between the host CPU
+// and the GPU.  Both set-ups store every NaN edge component as the one quiet NaN 0x7FF8000000000000, so that their records stay byte-identical.
+// (Through integer bits: a compiler may treat a select between a NaN and x as x.)  The traversal only ever sees "some NaN" either way.
+__host__ __device__ inline double edge_canon(double x) {
+    uint64_t b; __builtin_memcpy(&b, &x, 8);
+    if ((b & 0x7FF0000000000000ull) == 0x7FF0000000000000ull && (b & 0x000FFFFFFFFFFFFFull) != 0ull) b = 0x7FF8000000000000ull;
+    __builtin_memcpy(&x, &b, 8);
+    return x;
+}
 
 // own-list index (clusters.cpp): padded f32 boxes, rounded outward
 // A super-cluster owns the slots [tri_begin, tri_begin + tri_count), tri_begin a multiple of 8, tri_count <= 64; its cluster c is the

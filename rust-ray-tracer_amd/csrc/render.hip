@@ -293,7 +293,10 @@ __device__ __forceinline__ Ray32 make_ray32(V3 o, V3 d, float limit, float half_
     const float dmax = fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz));
     // (dmax > 1e-10: a component below 1e-20 is treated as parallel, which is only right while the ray cannot cross the scene -- t <= 2 limit / dmax -- by
     // moving along that axis; dmax < 1e8: the parallel axes' slab values are bounded by 1.25e30 dmax and must stay finite)
-    const bool cull = enabled && fabsf(ox) < limit && fabsf(oy) < limit && fabsf(oz) < limit && dmax < limit && dmax > 1e-10f && dmax < 1e8f;
+    // (fmaxf drops a NaN component, so NaN directions are excluded explicitly: their lane keeps the filter off, and its bundle anchor never enters
+    // make_bundle's bounds)
+    const bool finite_d = dx == dx && dy == dy && dz == dz;
+    const bool cull = enabled && fabsf(ox) < limit && fabsf(oy) < limit && fabsf(oz) < limit && finite_d && dmax < limit && dmax > 1e-10f && dmax < 1e8f;
     const float sigma = cull ? dmax * half_over_limit : 0.0f;
     // v_rcp_f32 (1 ulp) is plenty for a filter whose boxes are padded by ~1e-5 of the scene: an IEEE divide would cost ten instructions each
     const float ix = !cull ? 0.0f : (fabsf(dx) < 1e-20f ? 1e30f : __builtin_amdgcn_rcpf(dx)) * sigma;
@@ -507,7 +510,10 @@ __device__ __forceinline__ Bundle make_bundle(bool active, V3 o, V3 d, const Ray
     if (B.ilx < 0.0f && B.ihx > 0.0f) { B.ilx = -kBig; B.ihx = kBig; }
     if (B.ily < 0.0f && B.ihy > 0.0f) { B.ily = -kBig; B.ihy = kBig; }
     if (B.ilz < 0.0f && B.ihz > 0.0f) { B.ilz = -kBig; B.ihz = kBig; }
+    // The anchor goes to 0 with them: the leader may be such a lane, and its anchor NaN or infinite (the shadow ray of a NaN shading normal starts at
+    // a NaN point), which would make (b - c) * 0 NaN in bundle_hit and every box a MISS for the whole wave.
     if (act == 0ull || __builtin_amdgcn_ballot_w64(active && r.ix() == 0.0f && r.iy() == 0.0f && r.iz() == 0.0f) != 0ull) {
+        B.cx = B.cy = B.cz = 0.0f;
         B.ilx = B.ihx = B.ily = B.ihy = B.ilz = B.ihz = 0.0f; B.mlx = B.mhx = B.mly = B.mhy = B.mlz = B.mhz = 0.0f;
     }
     B.amx = fmaxf(fabsf(B.ilx), fabsf(B.ihx)); B.amy = fmaxf(fabsf(B.ily), fabsf(B.ihy)); B.amz = fmaxf(fabsf(B.ilz), fabsf(B.ihz));

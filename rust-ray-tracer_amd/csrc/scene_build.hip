@@ -407,8 +407,8 @@ __global__ void __launch_bounds__(kBlock) k_idx_slots(Idx X) {   // per slot: ge
     else {
         const Triangle& t = X.tris[tri];
         g.v1[0] = t.v1.x; g.v1[1] = t.v1.y; g.v1[2] = t.v1.z;
-        g.e1[0] = t.v2.x - t.v1.x; g.e1[1] = t.v2.y - t.v1.y; g.e1[2] = t.v2.z - t.v1.z;   // ray.rs:60
-        g.e2[0] = t.v3.x - t.v1.x; g.e2[1] = t.v3.y - t.v1.y; g.e2[2] = t.v3.z - t.v1.z;   // ray.rs:61
+        g.e1[0] = edge_canon(t.v2.x - t.v1.x); g.e1[1] = edge_canon(t.v2.y - t.v1.y); g.e1[2] = edge_canon(t.v2.z - t.v1.z);   // ray.rs:60
+        g.e2[0] = edge_canon(t.v3.x - t.v1.x); g.e2[1] = edge_canon(t.v3.y - t.v1.y); g.e2[2] = edge_canon(t.v3.z - t.v1.z);   // ray.rs:61
         g.pos = X.slot_pos[s]; g._pad = 0;
         a.uv[0] = t.t1.x; a.uv[1] = t.t1.y; a.uv[2] = t.t2.x; a.uv[3] = t.t2.y; a.uv[4] = t.t3.x; a.uv[5] = t.t3.y;
         a.nrm[0] = t.n1.x; a.nrm[1] = t.n1.y; a.nrm[2] = t.n1.z; a.nrm[3] = t.n2.x; a.nrm[4] = t.n2.y; a.nrm[5] = t.n2.z;

@@ -380,3 +380,115 @@ def test_oracle_colours_match_the_references_only_image(rrt, ob, teapot, teapot_
         assert len(sel) > 2000
         d = np.abs(mine[sel[:, 0], sel[:, 1]] - m["front_rgb"].astype(np.int64)[sel[:, 0] - r0, sel[:, 1] - c0]).max(-1)
         assert d.max() <= 8 and (d <= 1).mean() >= 0.95, (d.max(), (d <= 1).mean(), (d == 0).mean())
+
+
+# ------------------------------------------------------------------ texel addressing, bump maps and colour arithmetic at their edges
+def _rust_as_usize(x):
+    """Rust `f64 as usize` (64-bit): NaN and everything <= 0 give 0, >= 2^64 and +inf saturate to 2^64 - 1."""
+    if not x > 0.0:
+        return 0
+    return 2**64 - 1 if x >= 2.0**64 else int(x)
+
+
+def _texel_probe(ob, w, h, uv, o, d, tri=((-4, -4, 0), (4, -4, 0), (0, 4, 0))):
+    """Colour of the texel the oracle reads for the ray (o, d) on one triangle with per-vertex uv, under ambient light 1 (texel colour = pixel colour),
+    and the texel (x, y) derived in Python from the oracle's barycentrics with the reference's operation order (raytracer.rs:43-53)."""
+    yy, xx = np.mgrid[0:h, 0:w]
+    tex = np.stack([xx * 20 + 1, yy * 20 + 2, np.full_like(xx, 7)], -1).astype(np.uint8)    # texel (x, y) -> (20x + 1, 20y + 2, 7)
+    mats = [dict(ka=(1, 1, 1), kd=(0, 0, 0), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=0, bump=-1)]
+    s = tiny_scene(ob, [tri], lights=((0, 1.0, (0, 0, 0)),), mats=mats, tex=[tex], uv=np.asarray(uv, np.float64).reshape(1, 3, 3))
+    hit, t, u, v, _ = s.intersect(o, d)
+    assert hit
+    wb = 1.0 - u - v
+    tx = uv[1][0] * u + uv[2][0] * v + uv[0][0] * wb
+    ty = uv[1][1] * u + uv[2][1] * v + uv[0][1] * wb
+    xi, yi = _rust_as_usize(tx * float(w)) % w, _rust_as_usize(ty * float(h)) % h
+    c = s.get_ray_colour(o, d)
+    return ((c >> 16) & 255, (c >> 8) & 255, c & 255), (xi * 20 + 1, yi * 20 + 2, 7), (tx * w, ty * h, xi, yi)
+
+
+NAN = float("nan")
+V1_RAY = ((-4.0, -4.0, -5.0), (0.0, 0.0, 1.0))                 # hits vertex v1 exactly: u = v = 0, w = 1 (ray.rs:75,82 keep it)
+MID_RAY = ((0.3, -1.1, -5.0), (0.0, 0.0, 1.0))                 # an interior point: u, v, w all in (0, 1)
+
+
+def test_texel_index_non_power_of_two_sizes(ob):
+    """raytracer.rs:52-53 on textures whose sides are not powers of two: (x as usize) % width for x below 2^32, in [2^32, 2^64), at and beyond 2^64
+    (saturating: (2^64 - 1) % w), +inf, NaN, -inf and -0 (all 0).  At v1 the uv of v1 comes through exactly (w = 1, u = v = 0), except where another
+    vertex's uv is infinite: inf * 0 = NaN there, so the index is 0."""
+    sizes = ((1, 3), (3, 5), (5, 7), (7, 6), (6, 10), (10, 1))
+    for w, h in sizes:
+        cases = [  # (uv of v1, uv of v2, uv of v3), ray, expected (x index, y index) -- None: derived only
+            ([(2.5 / w, 4.5 / h, 0), (0.1, 0.2, 0), (0.3, 0.4, 0)], V1_RAY, (2 % w, 4 % h)),                               # below 2^32
+            ([((2**40 + 5) / w, (2**33 + 3) / h, 0), (0, 0, 0), (0, 0, 0)], V1_RAY, None),                                    # [2^32, 2^64)
+            ([(float(2**40 + 5), float(2**50 + 7), 0), (0, 0, 0), (0, 0, 0)], V1_RAY, ((2**40 + 5) * w % w, (2**50 + 7) * h % h)),   # exact products
+            ([(1e25, 2.0**64, 0), (0, 0, 0), (0, 0, 0)], V1_RAY, ((2**64 - 1) % w, (2**64 - 1) % h)),                         # >= 2^64: saturates
+            ([(INF, INF, 0), (0, 0, 0), (0, 0, 0)], V1_RAY, ((2**64 - 1) % w, (2**64 - 1) % h)),                              # +inf: saturates
+            ([(NAN, -INF, 0), (0, 0, 0), (0, 0, 0)], V1_RAY, (0, 0)),                                                         # NaN, -inf -> 0
+            ([(-0.0, -3.25, 0), (0, 0, 0), (0, 0, 0)], V1_RAY, (0, 0)),                                                       # -0, negative -> 0
+            ([(0.1, 0.1, 0), (INF, 2.0**70, 0), (0.2, INF, 0)], V1_RAY, (0, 0)),                                              # inf * u(=0) = NaN
+            ([(0.1, 0.1, 0), (INF, 2.0**70, 0), (0.2, 0.3, 0)], MID_RAY, ((2**64 - 1) % w, (2**64 - 1) % h)),                 # interior: inf, 2^70 * u
+            ([(3.7, 1.3, 0), (-2.2, 5.9, 0), (11.1, -0.4, 0)], MID_RAY, None),                                                # ordinary interpolation
+            ([((2**36 + 0.5) / w, 1e10, 0), ((2**36 + 9.25) / w, 3e9, 0), (2**36 / w, 7e9, 0)], MID_RAY, None),               # interpolated, >= 2^32
+        ]
+        for uv, (o, d), want in cases:
+            got, derived, (fx, fy, xi, yi) = _texel_probe(ob, w, h, uv, o, d)
+            assert got == derived, (w, h, uv, fx, fy)
+            if want is not None:
+                assert (xi, yi) == want, (w, h, uv, fx, fy, xi, yi, want)
+    assert (2**64 - 1) % 3 == 0 and (2**64 - 1) % 7 == 1            # the saturated index: 0 for w = 3, 1 for w = 7
+    got, _, (fx, _, xi, _) = _texel_probe(ob, 7, 3, [((2**40 + 5) / 7, 0.5, 0), (0, 0, 0), (0, 0, 0)], *V1_RAY)
+    assert 2**32 <= fx < 2**64 and xi == int(fx) % 7 and got[0] == xi * 20 + 1
+
+
+def _bump_scene(ob, tex_wh, bump):
+    """One triangle facing the camera (vertex normals (0, 0, -1)), uniform colour texture 200 of tex_wh = (w, h), bump map `bump` ([h, w, 3]), one
+    directional light (0, 0, -1) of intensity 1 and kd = 1: the pixel is trunc(200 * n.l) for the bumped normal n."""
+    tw, th = tex_wh
+    mats = [dict(ka=(0, 0, 0), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=0, bump=1)]
+    return tex_wh, lambda uv: tiny_scene(ob, [((-4, -4, 0), (4, -4, 0), (0, 4, 0))], lights=((2, 1.0, (0, 0, -1)),), mats=mats,
+                                         tex=[np.full((th, tw, 3), 200, np.uint8), np.ascontiguousarray(bump, np.uint8)],
+                                         uv=np.asarray(uv, np.float64).reshape(1, 3, 3))
+
+
+def test_bump_map_of_another_width(ob):
+    """raytracer.rs:127-128 addresses the bump map with the COLOUR texture's (x, y) and the BUMP map's width: index = bump.width * y + x.  Hand-derived
+    normals (raytracer.rs:130-161) for n = (0, 0, -1): t = n x (0, 1, 0) = (1, -0, 0), b = n x t = (0, -1, 0), so bump texel c gives the normal
+    (bv.x, -bv.y, -bv.z) with bv = 2 c / |c| - 1, and the light (0, 0, -1) sees n.l = bv.z / |bv|:
+      (0, 0, 255): bv = (-1, -1, 1), n.l = 1 / sqrt(3) -> trunc(200 / sqrt(3)) = 115;
+      (128, 128, 255): n.l = 0.92636 -> 185;   (40, 40, 255): n.l = 0.69660 -> 139;   (255, 0, 0): bv.z = -1, n.l < 0 -> no diffuse, 0."""
+    right, wrong, other = (0, 0, 255), (128, 128, 255), (255, 0, 0)
+    for (tw, th), (bw, bh), (x, y) in (((3, 2), (5, 2), (2, 1)),       # wider bump map: index 5 * 1 + 2 = 7 -> bump row 1, column 2
+                                        ((3, 2), (5, 2), (1, 0)),
+                                        ((3, 2), (2, 4), (2, 0)),       # narrower, taller: index 2 * 0 + 2 = 2 wraps to bump row 1, column 0
+                                        ((3, 2), (2, 4), (2, 1)),       # index 2 * 1 + 2 = 4 -> bump row 2, column 0
+                                        ((8, 3), (4, 4), (7, 2))):      # exactly fitting: index 4 * 2 + 7 = 15, the bump map's last texel
+        bump = np.empty((bh, bw, 3), np.uint8); bump[:] = other
+        k = bw * y + x
+        own = (int((y + 0.5) / th * bh) % bh, int((x + 0.5) / tw * bw) % bw)    # the texel the bump map's OWN (x, y) would address: must not be read
+        bump[own] = wrong                                               # (the exactly fitting case: both are the last texel)
+        bump[k // bw, k % bw] = right
+        _, mk = _bump_scene(ob, (tw, th), bump)
+        s = mk([((x + 0.5) / tw, (y + 0.5) / th, 0), (0, 0, 0), (0, 0, 0)])
+        assert s.get_ray_colour(*V1_RAY) == 0x737373, ((tw, th), (bw, bh), (x, y))              # 115
+    for c, want in (((128, 128, 255), 185), ((40, 40, 255), 139), ((255, 0, 0), 0)):
+        _, mk = _bump_scene(ob, (1, 1), np.array([[c]], np.uint8))
+        assert mk([(0.5, 0.5, 0), (0, 0, 0), (0, 0, 0)]).get_ray_colour(*V1_RAY) == want * 0x010101, c
+
+
+def test_colour_arithmetic_edges(ob):
+    """clamp_u8 of NaN is 0 and of +inf 255 (raytracer.rs:97-108); kr = 1 over an infinite local colour blends inf * (1 - 1) = NaN -> black
+    (raytracer.rs:95); ns = -1 is the 'no specular' sentinel (raytracer.rs:286) and nextafter(-1, 0) is not."""
+    L = ob.lib()
+    assert L.oracle_clamp_u8(INF) == 255 and L.oracle_clamp_u8(-INF) == 0 and L.oracle_clamp_u8(NAN) == 0 and L.oracle_clamp_u8(-0.0) == 0
+    assert L.oracle_f64_as_usize(2.0**64) == 2**64 - 1 and L.oracle_f64_as_usize(2.0**64 - 2048) == 2**64 - 2048 and L.oracle_f64_as_usize(-INF) == 0
+    tri = [((-4, -4, 0), (4, -4, 0), (0, 4, 0))]
+    tex = [np.full((2, 2, 3), 200, np.uint8)]
+    probe = ((0.0, -1.0, -5.0), (0.0, 0.0, 1.0))                     # reflects straight back (n = (0, 0, -1)) and misses: reflected colour white
+    for kr, want in ((1.0, 0x000000), (0.5, 0xFFFFFF), (0.0, 0xFFFFFF)):
+        mats = [dict(ka=(1, 1, 1), kd=(0, 0, 0), ks=(0, 0, 0), ns=-1.0, kr=kr, tex=0, bump=-1)]
+        assert tiny_scene(ob, tri, lights=((0, INF, (0, 0, 0)),), mats=mats, tex=tex).get_ray_colour(*probe) == want, kr
+    # specular only: n = v = l = (0, 0, -1), so r = l and r.v / (|r| |v|) = 1, pow(1, ns) = 1: 200 * ks 1 * intensity 0.5 = 100 unless ns == -1
+    for ns, want in ((-1.0, 0), (math.nextafter(-1.0, 0.0), 100), (-5.0, 100), (0.0, 100), (INF, 100), (NAN, 100)):
+        mats = [dict(ka=(0, 0, 0), kd=(0, 0, 0), ks=(1, 1, 1), ns=ns, kr=0.0, tex=0, bump=-1)]
+        assert tiny_scene(ob, tri, lights=((2, 0.5, (0, 0, -1)),), mats=mats, tex=tex).get_ray_colour(*probe) == want * 0x010101, ns
