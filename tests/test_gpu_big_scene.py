@@ -7,14 +7,12 @@
   * a sample of the band's rays within +-1 per channel of the oracle (measured 0).
 """
 import os
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from conftest import channels, lights_tuple
-from test_gpu_build import MATS, OCT_KEYS, SCENE_BUFS, TEX, assert_same_octree
-from test_gpu_configs import ORIGIN, row_dirs
+from conftest import channels
+from gpu_checks import MATS, ORIGIN, POOL, SCENE_BUFS, TEX, assert_frame_close, assert_same_octree, oracle_for, row_dirs
 
 pytestmark = pytest.mark.gpu
 N = int(os.environ.get("RRT_BIG_SCENE_N", 4_000_000))
@@ -46,7 +44,7 @@ def test_four_million_triangles_from_arrays(rrt, ob):
         g, h = gpu.buffer(name), host.buffer(name)
         assert g.shape == h.shape and np.array_equal(g, h), f"scene buffer {name} differs between the GPU and the host set-up"
     del host, g, h
-    osc = ob.OracleScene(pos, uv, nrm, mat, MATS, TEX, lights_tuple(lights), ORIGIN)
+    osc = oracle_for(ob, dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=MATS, textures=TEX), lights)
     assert_same_octree(tree, osc.octree(), "GPU build vs oracle build")
 
     w, h = 3840, 2160
@@ -59,8 +57,6 @@ def test_four_million_triangles_from_arrays(rrt, ob):
     assert np.array_equal(c_fast, c_exact), f"{(c_fast != c_exact).sum()} of {len(d)} band rays differ between the indexed and the reference-order mode"
     assert np.array_equal(channels(c_fast.reshape(rows, 4, w)).sum(1) // 4, channels(frame[r0:r0 + rows])), "band rays mixed per pixel differ from the frame's rows"
     idx = np.random.default_rng(6).choice(len(d), 1500, replace=False)
-    with ThreadPoolExecutor(16) as pool:
-        want = np.fromiter(pool.map(lambda i: osc.get_ray_colour(ORIGIN, d[i]), idx), np.uint32, len(idx))
-    diff = np.abs(channels(want) - channels(c_fast[idx])).max()
-    assert diff <= 1, f"sampled band rays differ from the oracle by {diff}"
+    want = np.fromiter(POOL.map(lambda i: osc.get_ray_colour(ORIGIN, d[i]), idx), np.uint32, len(idx))
+    diff = assert_frame_close(c_fast[idx], want, "sampled band rays").max()
     print(f"frame kernel {gpu.last_stats()['kernel_ms']:.2f} ms; {len(d)} band rays identical in both modes; {len(idx)} sampled rays within {diff} of the oracle")

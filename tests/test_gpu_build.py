@@ -15,63 +15,10 @@ import numpy as np
 import pytest
 
 from conftest import ASSETS
+from gpu_checks import (FORCED_MODES, N_THREADS, ORIGIN, assert_frame_close, assert_same_buffers, assert_same_octree, assert_walks_match, check_scene,
+                        oracle_for, scene_from)
 
 pytestmark = pytest.mark.gpu
-
-MATS = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(1, 1, 1), ns=240.0, kr=0.0, tex=0, bump=-1)]
-TEX = [np.full((2, 2, 3), 200, np.uint8)]
-OCT_KEYS = ("aabb", "first_child", "tri_count", "own_off", "own_idx")
-SCENE_BUFS = ("nodes", "geom", "attr", "supers", "cboxes", "child_boxes", "tboxes")
-
-
-def scene_from(rrt, pos, root=None):
-    pos = np.asarray(pos, np.float64).reshape(-1, 3, 3)
-    n = len(pos)
-    rng = np.random.default_rng(n)
-    uv = rng.random((n, 3, 3)); nrm = rng.normal(size=(n, 3, 3))
-    return rrt.SceneData.from_arrays(pos, uv, nrm, np.zeros(n, np.uint32), MATS, TEX, **({} if root is None else {"root": root}))
-
-
-def assert_same_octree(a, b, what):
-    for k in OCT_KEYS:
-        assert a[k].shape == b[k].shape, f"{what}: {k} shape {a[k].shape} vs {b[k].shape}"
-        if not np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)):
-            bad = np.flatnonzero((a[k] != b[k]).reshape(len(a[k]), -1).any(1))
-            raise AssertionError(f"{what}: {k} differs in {len(bad)} rows, first {bad[:5]}: {a[k][bad[:3]]} vs {b[k][bad[:3]]}")
-    assert a["max_depth"] == b["max_depth"], (what, a["max_depth"], b["max_depth"])
-
-
-def assert_same_buffers(gpu, host, what, rec=32):
-    for name in SCENE_BUFS:
-        g, h = gpu.buffer(name), host.buffer(name)
-        assert g.shape == h.shape, f"{what}: {name} is {g.shape[0]} bytes on the GPU path, {h.shape[0]} on the host path"
-        if not np.array_equal(g, h):
-            size = {"nodes": 96, "geom": 80, "attr": 128}.get(name, rec)
-            bad = np.flatnonzero((g.reshape(-1, size) != h.reshape(-1, size)).any(1))
-            raise AssertionError(f"{what}: {name} differs in {len(bad)} of {len(g) // size} records, first {bad[:8]};\n gpu  {g.reshape(-1, size)[bad[0]].view(np.uint32)}\n host {h.reshape(-1, size)[bad[0]].view(np.uint32)}")
-    ng, nh = gpu.last_stats()["origin_plane_triangles"], host.last_stats()["origin_plane_triangles"]
-    assert ng == nh, f"{what}: {ng} origin-plane suspects on the GPU path, {nh} on the host path"
-    if ng <= 64:                                              # beyond RRT_MAX_SUSPECTS the list is not read (every ray from the origin runs unfiltered)
-        gs, hs = gpu.buffer("suspects").reshape(-1, 32), host.buffer("suspects").reshape(-1, 32)
-        assert sorted(map(bytes, gs)) == sorted(map(bytes, hs)), f"{what}: origin-plane suspects differ ({len(gs)} vs {len(hs)})"
-
-
-def check_scene(rrt, sd, what, ob=None, no_cull_too=True, origin=None):
-    lights = rrt.default_lights()
-    kw = {} if origin is None else {"origin": origin}
-    gpu = rrt.RayTracer(sd, lights, **kw)
-    tree = gpu.octree()
-    assert_same_octree(tree, sd.octree(), what + " (GPU build vs host build)")
-    assert tree["info"] == sd.info, (what, tree["info"], sd.info)
-    if ob is not None:
-        pos, uv, nrm, mat = sd.triangles()
-        osc = ob.OracleScene(pos, uv, nrm, mat, sd.materials(), sd.textures(), [(l.kind, l.intensity, (l.v.x, l.v.y, l.v.z)) for l in lights], (0.0, 2.0, -10.0))
-        assert_same_octree(tree, osc.octree(), what + " (GPU build vs oracle build)")
-    host = rrt.RayTracer(sd, lights, host_setup=True, **kw)
-    assert_same_buffers(gpu, host, what)
-    if no_cull_too:
-        assert_same_buffers(rrt.RayTracer(sd, lights, no_cull=True, **kw), rrt.RayTracer(sd, lights, no_cull=True, host_setup=True, **kw), what + " [no_cull]")
-    return gpu, host
 
 
 @pytest.mark.parametrize("name", ["model.obj", "model2.obj", "model3.obj"])
@@ -137,7 +84,7 @@ def test_gpu_build_kat_scenes(rrt, ob):
 def test_gpu_build_origin_suspects(rrt):
     """Triangles whose plane passes through the raytracer's origin (exactness guard): the GPU search finds the set the host search finds."""
     rng = np.random.default_rng(11)
-    origin = np.array([0.0, 2.0, -10.0])
+    origin = np.array(ORIGIN)
     pos = rng.random((2000, 3, 3)) * 10 - 5
     for i in range(40):                                                     # 40 triangles in planes through the origin
         a, b = rng.normal(size=3), rng.normal(size=3)
@@ -218,12 +165,9 @@ def test_random_scenes_render_like_the_oracle(rrt, ob):
         c = rng.uniform([-6, -1, -4], [6, 6, 12], (n, 1, 3)); pos = c + rng.normal(size=(n, 3, 3)) * 10 ** rng.uniform(-1.5, 0.3)
         uv = rng.uniform(-2, 3, (n, 3, 3)); nrm = rng.normal(size=(n, 3, 3)); mat = (rng.random(n) < 0.15).astype(np.uint32)
         rt = rrt.RayTracer.from_arrays(pos, uv, nrm, mat, mats, texs, lights)
-        osc = ob.OracleScene(pos, uv, nrm, mat, mats, texs, [(l.kind, l.intensity, (l.v.x, l.v.y, l.v.z)) for l in lights], (0.0, 2.0, -10.0))
-        ref, _ = osc.render(96, 72)
+        ref, _ = oracle_for(ob, dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=mats, textures=texs), lights).render(96, 72, n_threads=N_THREADS)
         got = rt.render(96, 72)
-        ch = lambda a: np.stack([(a >> 16) & 255, (a >> 8) & 255, a & 255], -1).astype(np.int64)
-        d = np.abs(ch(got) - ch(ref)).max()
-        assert d <= 1, f"random scene {trial} ({n} triangles): GPU frame differs from the oracle by {d}"
-        for mode in ("lane", "bundle", "ray"):
-            assert np.array_equal(rrt.RayTracer.from_arrays(pos, uv, nrm, mat, mats, texs, lights, box_filter=mode).render(96, 72), got), (trial, mode)
+        assert_frame_close(got, ref, f"random scene {trial} ({n} triangles)")
+        assert_walks_match(lambda mode: rrt.RayTracer.from_arrays(pos, uv, nrm, mat, mats, texs, lights, box_filter=mode), [got], [(96, 72)],
+                           f"random scene {trial}", FORCED_MODES)
         assert np.array_equal(rrt.RayTracer.from_arrays(pos, uv, nrm, mat, mats, texs, lights, no_cull=True).render(96, 72), got), (trial, "no_cull")

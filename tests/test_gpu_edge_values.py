@@ -1,7 +1,7 @@
 """Edge values on the GPU against the CPU oracle: texel addressing, bump maps of another size, degenerate shading values, material / light / option
 extremes, max_t at its boundary, non-finite rays and non-finite geometry, and a scene loaded end to end from .obj / .mtl / BMP files.
 
-Each case is checked three ways, as tests/test_gpu_lighting.py does:
+Each case is checked three ways, as tests/test_gpu_lighting.py does, with the checks of tests/gpu_checks.py:
   (a) the default, lane-filter, bundle-filter and ray-walk frames (and get_ray_colours on chosen rays) are bit-identical to the reference-order
       mode (RRT_FLAG_NO_CULL);
   (b) the reference-order frame matches the oracle's: bit for bit where no material evaluates pow() (ks = 0 or ns = -1), else within COLOUR_TOL per
@@ -17,20 +17,15 @@ import struct
 import numpy as np
 import pytest
 
-from conftest import channels, lights_tuple
-from test_gpu_build import check_scene
-from test_gpu_configs import POOL, row_dirs
-from test_gpu_lighting import _box, _checker, _flat_normals, _quad
+from conftest import channels
+from gpu_checks import (ALL_MODES, COLOUR_TOL, N_THREADS, POOL, ROOT_BOX, assert_frame_close, assert_walks_match, check_scene, checker,
+                        closed_box, flat_normals, oracle_for, quad, row_dirs)
+from gpu_checks import ORIGIN as TEAPOT_ORIGIN
 
 pytestmark = pytest.mark.gpu
-COLOUR_TOL = 1
 W, H = 96, 72
-MODES = (None, "lane", "bundle", "ray")
-ROOT = (-20.0, 20.0, -20.0, 20.0, -20.0, 20.0)
 ORIGIN = (0.0, 0.0, -10.0)                 # hand-built scenes: the plane z = 0 fills the 96 x 72 frame over [-5, 5]^2
-TEAPOT_ORIGIN = (0.0, 2.0, -10.0)
 INF, NAN = float("inf"), float("nan")
-N_THREADS = 16
 
 
 def rust_as_usize(x):
@@ -49,10 +44,6 @@ def _exact(materials):
     return all(m["ns"] == -1.0 or tuple(m["ks"]) == (0, 0, 0) for m in materials)
 
 
-def _oracle(ob, A, lights, origin, **opt):
-    return ob.OracleScene(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"], lights_tuple(lights), origin, ROOT, **opt)
-
-
 def _sample_dirs(w=W, h=H, step=5):
     """Sub-sample directions (engine.rs:207-236) of every `step`-th pixel of every `step`-th row: the chosen rays for get_ray_colours."""
     return np.concatenate([row_dirs(w, h, r, np.arange(0, 2 * (w // 2), step)).reshape(-1, 3) for r in range(1, h, step)])
@@ -68,29 +59,20 @@ def primary_hits(osc, origin, w=W, h=H):
 def run_case(rrt, ob, name, A, lights, origin=ORIGIN, exact=None, **opt):
     """(a) and (b) for one scene; returns (oracle scene, oracle frame)."""
     exact = _exact(A["materials"]) if exact is None else exact
-    sd = rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"], ROOT)
-    osc = _oracle(ob, A, lights, origin, **opt)
+    tol = 0 if exact else COLOUR_TOL
+    sd = rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"], ROOT_BOX)
+    osc = oracle_for(ob, A, lights, origin, **opt)
     V = rrt.Vector3d(*origin)
     ref_rt = rrt.RayTracer(sd, lights, V, no_cull=True, **opt)
     gpu = ref_rt.render(W, H)
     ref = osc.render(W, H, n_threads=N_THREADS)[0]
-    d = np.abs(channels(gpu) - channels(ref)).max(-1)
-    if exact:
-        assert (d == 0).all(), f"{name}: {(d > 0).sum()} pixels not bit-equal to the oracle (max channel diff {d.max()}), no pow() in this scene"
-    else:
-        assert d.max() <= COLOUR_TOL, f"{name}: max channel diff {d.max()} on {(d > COLOUR_TOL).sum()} pixels"
+    d = assert_frame_close(gpu, ref, name, tol)
     D = _sample_dirs()
     O = np.tile(origin, (len(D), 1))
     ref_cols = ref_rt.get_ray_colours(O, D)
     oc = np.fromiter(POOL.map(lambda i: osc.get_ray_colour(O[i], D[i]), range(len(D))), np.uint32, len(D))
-    dc = np.abs(channels(ref_cols) - channels(oc)).max(-1)
-    assert dc.max() <= (0 if exact else COLOUR_TOL), f"{name}: get_ray_colours differs from the oracle on {(dc > 0).sum()} of {len(D)} rays"
-    for mode in MODES:
-        rt = rrt.RayTracer(sd, lights, V, box_filter=mode, **opt)
-        bad = int((rt.render(W, H) != gpu).sum())
-        assert bad == 0, f"{name}, walk {mode}: {bad} pixels differ from the reference-order frame"
-        bad = int((rt.get_ray_colours(O, D) != ref_cols).sum())
-        assert bad == 0, f"{name}, walk {mode}: {bad} of {len(D)} ray colours differ from the reference-order mode"
+    assert_frame_close(ref_cols, oc, f"{name}: get_ray_colours", tol)
+    assert_walks_match(lambda mode: rrt.RayTracer(sd, lights, V, box_filter=mode, **opt), [gpu], [(W, H)], name, rays=(O, D, ref_cols))
     print(f"\n[edge] {name}: {(d > 0).sum()} px not bit-equal to the oracle ({'exact' if exact else 'pow'})", end="")
     return osc, ref
 
@@ -103,7 +85,7 @@ def teeth(name, counts, minimum):
 
 # ------------------------------------------------------------------ scene building
 def _panel(x0, x1, y0, y1, z=0.0):
-    return _quad((x0, y0, z), (x1, y0, z), (x1, y1, z), (x0, y1, z))
+    return quad((x0, y0, z), (x1, y0, z), (x1, y1, z), (x0, y1, z))
 
 
 def _build(panels, materials, textures, nrm=None):
@@ -120,7 +102,7 @@ def _build(panels, materials, textures, nrm=None):
             else:
                 uv.append(np.asarray(f[k], np.float64))
     pos = np.asarray(pos); uv = np.asarray(uv, np.float64); mat = np.asarray(mat, np.uint32)
-    nrm = _flat_normals(pos, ORIGIN) if nrm is None else np.asarray(nrm, np.float64)
+    nrm = flat_normals(pos, ORIGIN) if nrm is None else np.asarray(nrm, np.float64)
     return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=materials, textures=textures)
 
 
@@ -214,7 +196,7 @@ def _bump_scene(seed=0xB0B):
     uvf = lambda a, b: (a * 2.3 - 0.15, b * 1.7 + 0.05)
     panels = [(_panel(-4.9, -1.75, 0.05, 4.9), 0, uvf), (_panel(-1.6, 1.6, 0.05, 4.9), 1, uvf), (_panel(1.75, 4.9, 0.05, 4.9), 2, uvf),
               (_panel(-4.9, -1.75, -4.9, -0.05), 3, lambda a, b: (a * 0.999, b * 0.999)), (_panel(-1.6, 1.6, -4.9, -0.05), 4, uvf)]
-    mirror = _quad((1.75, -4.9, -1.5), (4.9, -4.9, 0.5), (4.9, -0.05, 0.5), (1.75, -0.05, -1.5))      # turned towards the other panels
+    mirror = quad((1.75, -4.9, -1.5), (4.9, -4.9, 0.5), (4.9, -0.05, 0.5), (1.75, -0.05, -1.5))      # turned towards the other panels
     panels.append((mirror, 5, uvf))
     back = _panel(-12.0, 12.0, -12.0, 12.0, z=-11.0)                                                   # behind the camera: what the mirror shows
     panels.append((back, 4, uvf))
@@ -274,14 +256,14 @@ def test_bump_map_size_check(rrt):
 # ------------------------------------------------------------------ degenerate shading normals
 def _degenerate_scene(seed=0xDE6):
     rng = np.random.default_rng(seed)
-    textures = [_rand_tex(rng, 4, 4), _rand_tex(rng, 5, 3), _checker((200, 200, 200), (60, 90, 120), 4)]
+    textures = [_rand_tex(rng, 4, 4), _rand_tex(rng, 5, 3), checker((200, 200, 200), (60, 90, 120), 4)]
     materials = [_mat(0), _mat(1, kr=0.5, ka=0.4), _mat(2, kd=0.9)]
     uvf = lambda a, b: (a * 1.3, b * 0.9)
     panels = [(_panel(-4.9, -1.75, 0.05, 4.9), 0, uvf), (_panel(-1.6, 1.6, 0.05, 4.9), 0, uvf), (_panel(1.75, 4.9, 0.05, 4.9), 0, uvf),
-              (_quad((-4.9, -4.9, -1.0), (-1.75, -4.9, 1.0), (-1.75, -0.05, 1.0), (-4.9, -0.05, -1.0)), 1, uvf),       # mirrors
-              (_quad((-1.6, -4.9, 1.0), (1.6, -4.9, -1.0), (1.6, -0.05, -1.0), (-1.6, -0.05, 1.0)), 1, uvf),
+              (quad((-4.9, -4.9, -1.0), (-1.75, -4.9, 1.0), (-1.75, -0.05, 1.0), (-4.9, -0.05, -1.0)), 1, uvf),       # mirrors
+              (quad((-1.6, -4.9, 1.0), (1.6, -4.9, -1.0), (1.6, -0.05, -1.0), (-1.6, -0.05, 1.0)), 1, uvf),
               (_panel(1.75, 4.9, -4.9, -0.05), 2, uvf),
-              (_box((1.0, 1.0, -4.0), (2.0, 2.0, -3.0)), 2, uvf),                                                    # an occluder for the point light
+              (closed_box((1.0, 1.0, -4.0), (2.0, 2.0, -3.0)), 2, uvf),                                              # an occluder for the point light
               (_panel(-12.0, 12.0, -12.0, 12.0, z=-11.0), 2, uvf)]
     A = _build(panels, materials, textures)
     nrm = A["nrm"]
@@ -318,17 +300,17 @@ def test_degenerate_normals(rrt, ob):
 def _extreme_scene(floor=None, wall=None, mirror=None, box=None):
     """Floor, back wall, a mirror turned towards them and a closed box; each material's values can be replaced."""
     rng = np.random.default_rng(0xE7)
-    textures = [_checker((200, 180, 150), (90, 110, 140)), _rand_tex(rng, 5, 3), _checker((230, 230, 230), (40, 60, 80), 4), _rand_tex(rng, 3, 7)]
+    textures = [checker((200, 180, 150), (90, 110, 140)), _rand_tex(rng, 5, 3), checker((230, 230, 230), (40, 60, 80), 4), _rand_tex(rng, 3, 7)]
     base = [_mat(0, ka=0.6, kd=0.8, ks=0.5, ns=20.0), _mat(1, ka=0.5, kd=0.7), _mat(2, ka=0.6, kd=0.5, kr=0.6), _mat(3, ka=0.7, kd=0.9, ks=0.6, ns=8.0)]
     for m, over in zip(base, (floor, wall, mirror, box)):
         m.update(over or {})
     uvf = lambda a, b: (a * 2.1, b * 1.3)
-    panels = [(_quad((-6, -3, -4), (6, -3, -4), (6, -3, 8), (-6, -3, 8)), 0, uvf),
+    panels = [(quad((-6, -3, -4), (6, -3, -4), (6, -3, 8), (-6, -3, 8)), 0, uvf),
               (_panel(-6, 6, -3, 6, z=8.0), 1, uvf),
-              (_quad((2.5, -3, -2), (6, -3, 3), (6, 4, 3), (2.5, 4, -2)), 2, uvf),
-              (_box((-3.0, -3.0, 1.0), (-1.0, -1.0, 3.0)), 3, uvf)]
+              (quad((2.5, -3, -2), (6, -3, 3), (6, 4, 3), (2.5, 4, -2)), 2, uvf),
+              (closed_box((-3.0, -3.0, 1.0), (-1.0, -1.0, 3.0)), 3, uvf)]
     A = _build(panels, base, textures)
-    A["nrm"] = _flat_normals(A["pos"], (0.0, 0.0, 0.0))
+    A["nrm"] = flat_normals(A["pos"], (0.0, 0.0, 0.0))
     return A
 
 
@@ -368,11 +350,11 @@ def test_material_light_option_extremes(rrt, ob, case):
     A = _extreme_scene(*over)
     osc, ref = run_case(rrt, ob, case, A, _lights(rrt, lights), **opt)
     nA = _extreme_scene(*n_over)
-    nref = _oracle(ob, nA, _lights(rrt, n_lights or BASE_LIGHTS), ORIGIN, **(opt if n_opt is None else n_opt)).render(W, H, n_threads=N_THREADS)[0]
+    nref = oracle_for(ob, nA, _lights(rrt, n_lights or BASE_LIGHTS), ORIGIN, **(opt if n_opt is None else n_opt)).render(W, H, n_threads=N_THREADS)[0]
     if case == "kr_denormal":                         # 1 - 5e-324 == 1: the frame equals kr = 0's, but every mirror hit traces its reflection
         hits = sum(int(A["mat"][h[4]]) == 2 for h in primary_hits(osc, ORIGIN))
         teeth(case, {"mirror hits (reflection traced)": hits}, {"mirror hits (reflection traced)": min_teeth})
-        kr0 = _oracle(ob, _extreme_scene(None, None, {"kr": 0.0}, None), _lights(rrt, lights), ORIGIN).render(W, H, n_threads=N_THREADS)[0]
+        kr0 = oracle_for(ob, _extreme_scene(None, None, {"kr": 0.0}, None), _lights(rrt, lights), ORIGIN).render(W, H, n_threads=N_THREADS)[0]
         assert np.array_equal(ref, kr0)
         return
     diff = int((nref != ref).sum())
@@ -404,7 +386,7 @@ def test_max_t_boundary(rrt, teapot, teapot_oracle, boundary_rays):
     variants = {"T": T, "next_up": np.nextafter(T, INF), "next_down": np.nextafter(T, -INF), "nan": NAN, "0": 0.0, "-0": -0.0, "-1": -1.0,
                 "-inf": -INF, "5e-324": 5e-324}
     rts = {"no_cull": rrt.RayTracer(teapot, rrt.default_lights(), no_cull=True)}
-    rts.update({str(m): rrt.RayTracer(teapot, rrt.default_lights(), box_filter=m) for m in MODES})
+    rts.update({str(m): rrt.RayTracer(teapot, rrt.default_lights(), box_filter=m) for m in ALL_MODES})
     changed = 0
     for name, mt in variants.items():
         M = np.broadcast_to(np.asarray(mt, np.float64), (len(O),))
@@ -457,14 +439,14 @@ def test_non_finite_rays(rrt, teapot, teapot_oracle, ordinary_rays):
     ord_hit = list(POOL.map(lambda i: teapot_oracle.intersect(OO[i], OD[i]), range(k)))
     ord_col = np.fromiter(POOL.map(lambda i: teapot_oracle.get_ray_colour(OO[i], OD[i]), range(k)), np.uint32, k)
     rts = {"no_cull": rrt.RayTracer(teapot, rrt.default_lights(), no_cull=True)}
-    rts.update({str(m): rrt.RayTracer(teapot, rrt.default_lights(), box_filter=m) for m in MODES})
+    rts.update({str(m): rrt.RayTracer(teapot, rrt.default_lights(), box_filter=m) for m in ALL_MODES})
     n_mixed = 0
     for mode, rt in rts.items():
         base_hit, base_t, base_u, base_v, base_tri = rt.intersect_rays(OO, OD)
         base_col = rt.get_ray_colours(OO, OD)
         for i in range(k):                                           # the ordinary rays alone against the oracle
             assert bool(base_hit[i]) == ord_hit[i][0] and (not ord_hit[i][0] or (base_t[i], base_u[i], base_v[i], base_tri[i]) == ord_hit[i][1:]), (mode, i)
-        assert np.abs(channels(base_col[:k]) - channels(ord_col)).max() <= COLOUR_TOL, mode
+        assert_frame_close(base_col[:k], ord_col, f"walk {mode}: ordinary ray colours")
         for n in (1, 63, 65, 64 * 1024 + 1):
             slots = [np.array([s]) for s in range(ns)] if n == 1 else [np.linspace(0, n - 1, ns).astype(np.int64)]
             for pos in slots:
@@ -507,7 +489,7 @@ def test_non_finite_geometry(rrt, ob):
     nb = len(pos) - len(A["pos"])
     A = dict(A, pos=pos, uv=np.concatenate([A["uv"], np.zeros((nb, 3, 3))]), nrm=np.concatenate([A["nrm"], np.tile([0.0, 0.0, -1.0], (nb, 3, 1))]),
              mat=np.concatenate([A["mat"], np.zeros(nb, np.uint32)]))
-    sd = rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"], ROOT)
+    sd = rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"], ROOT_BOX)
     check_scene(rrt, sd, "non-finite geometry", ob)
     osc, _ = run_case(rrt, ob, "non-finite geometry", A, _lights(rrt, BASE_LIGHTS))
     bad_ids = {i for i in range(len(pos)) if not np.isfinite(pos[i]).all()}

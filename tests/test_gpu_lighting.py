@@ -14,30 +14,22 @@ checked one by one against the band criterion; a difference outside the band fai
 import numpy as np
 import pytest
 
-from conftest import channels, lights_tuple
-from test_gpu_configs import _in_noise_band, row_dirs, sample_rays
+from conftest import channels
+from gpu_checks import (FORCED_MODES, N_THREADS, ORIGIN, ROOT_BOX, assert_frame_close, assert_walks_match, checker, closed_box, flat_normals,
+                        in_noise_band, oracle_for, quad, row_dirs, sample_rays)
 
 pytestmark = pytest.mark.gpu
-COLOUR_TOL = 1          # per RGB channel: only pow() (raytracer.rs:295) may differ by an ulp between glibc and OCML
-N_THREADS = 16          # oracle render threads
 SIZES = ((160, 120), (97, 61))
-MODES = (None, "lane", "bundle", "ray")
-TEAPOT_ORIGIN = (0.0, 2.0, -10.0)
 
 
 @pytest.fixture(scope="module")
 def teapot_arrays(teapot):
     pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures(), root=(-20.0, 20.0, -20.0, 20.0, -20.0, 20.0))
-
-
-def _oracle(ob, A, lights, origin, surface_offset=1e-4, max_reflection_depth=5):
-    return ob.OracleScene(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"], lights_tuple(lights), origin, A["root"],
-                          surface_offset=surface_offset, max_reflection_depth=max_reflection_depth)
+    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures(), root=ROOT_BOX)
 
 
 def _oracle_frame(ob, A, lights, origin, w, h, **opt):
-    return _oracle(ob, A, lights, origin, **opt).render(w, h, n_threads=N_THREADS)[0]
+    return oracle_for(ob, A, lights, origin, **opt).render(w, h, n_threads=N_THREADS)[0]
 
 
 def _shade_normal(A, tri, u, v):
@@ -87,39 +79,30 @@ def _secondary_rays(osc, A, lights, o, d, offset, max_depth):
     return out
 
 
-def _check_walks_against_no_cull(rrt, name, sd, A, osc, lights, origin, opt, sizes, frames, band_ok):
-    """(b): every walk variant's frame equals the reference-order frame.  With band_ok, a pixel may differ only if one of its four sub-sample rays
-    casts a shadow or reflection ray inside the exactness band of some triangle (the criterion of test_gpu_configs.py case C); returns the count of
-    such pixels."""
-    n_band = 0
-    tris = A["pos"]; pad = max(abs(x) for x in A["root"]) / 32768.0       # clusters.cpp: 2^-15 of the scene magnitude
-    for mode in MODES:
-        rt = rrt.RayTracer(sd, lights, rrt.Vector3d(*origin), box_filter=mode, **opt)
-        for (w, h), ref in zip(sizes, frames):
-            bad = np.argwhere(rt.render(w, h) != ref)
-            assert band_ok or len(bad) == 0, f"{name}, walk {mode}, {w}x{h}: {len(bad)} pixels differ from the reference-order frame"
-            for r, c in bad:
-                rays = [ray for d in row_dirs(w, h, r, [c])[:, 0]
-                        for ray in _secondary_rays(osc, A, lights, np.array(origin), d, opt.get("surface_offset", 1e-4), opt.get("max_reflection_depth", 5))]
-                assert any(_in_noise_band(tris, o, d, pad) for o, d in rays), \
-                    f"{name}, walk {mode}, {w}x{h}: pixel ({r}, {c}) differs from the reference-order frame outside the exactness band"
-                n_band += 1
-    return n_band
+def _pixel_in_band(osc, A, lights, origin, opt, w, h, r, c):
+    """Whether one of the pixel's four sub-sample rays casts a shadow or reflection ray inside the exactness band of some triangle (the criterion
+    of test_gpu_configs.py case C): only such a pixel may differ from the reference-order frame."""
+    pad = max(abs(x) for x in A["root"]) / 32768.0                         # clusters.cpp: 2^-15 of the scene magnitude
+    rays = [ray for d in row_dirs(w, h, r, [c])[:, 0]
+            for ray in _secondary_rays(osc, A, lights, np.array(origin), d, opt.get("surface_offset", 1e-4), opt.get("max_reflection_depth", 5))]
+    return any(in_noise_band(A["pos"], o, d, pad) for o, d in rays)
 
 
 def run_case(rrt, ob, sd, A, name, lights, origin, neighbour, min_teeth, band_ok=False, sizes=SIZES, **opt):
-    """(a), (b) and (c) for one configuration; returns the reference-order frames.  neighbour = (lights, opt) of the neighbouring configuration."""
+    """(a), (b) and (c) for one configuration; returns the reference-order frames.  neighbour = (lights, opt) of the neighbouring configuration.
+    With band_ok, (b) lets a pixel differ where _pixel_in_band holds, and the count of such pixels is printed."""
     exact = rrt.RayTracer(sd, lights, rrt.Vector3d(*origin), no_cull=True, **opt)
-    osc = _oracle(ob, A, lights, origin, **opt)
+    osc = oracle_for(ob, A, lights, origin, **opt)
     frames, refs, report = [], [], []
     for w, h in sizes:
         gpu = exact.render(w, h)
         ref = osc.render(w, h, n_threads=N_THREADS)[0]
-        d = np.abs(channels(gpu) - channels(ref)).max(-1)
-        assert d.max() <= COLOUR_TOL, f"{name} {w}x{h}: max channel diff {d.max()} on {(d > COLOUR_TOL).sum()} pixels"
+        d = assert_frame_close(gpu, ref, f"{name} {w}x{h}")
         report.append(f"{w}x{h}: {(d > 0).sum()} px not bit-equal to the oracle")
         frames.append(gpu); refs.append(ref)
-    n_band = _check_walks_against_no_cull(rrt, name, sd, A, osc, lights, origin, opt, sizes, frames, band_ok)
+    in_band = (lambda w, h, r, c: _pixel_in_band(osc, A, lights, origin, opt, w, h, r, c)) if band_ok else None
+    n_band = assert_walks_match(lambda mode: rrt.RayTracer(sd, lights, rrt.Vector3d(*origin), box_filter=mode, **opt), frames, sizes, name,
+                                in_band=in_band)
     teeth = int((_oracle_frame(ob, A, neighbour[0], origin, *sizes[0], **neighbour[1]) != refs[0]).sum())
     assert teeth >= min_teeth, f"{name}: differs from its neighbouring configuration on only {teeth} pixels (< {min_teeth})"
     print(f"\n[lighting] {name}: {'; '.join(report)}; teeth {teeth} px (min {min_teeth})" + (f"; band pixels {n_band}" if band_ok else ""))
@@ -147,7 +130,7 @@ def _teapot_lights(rrt, teapot_arrays):
         "break_drops_ambient": ([L.Point(0.4, V(0.0, -3.0, 0.0)), L.Ambient(0.5), L.Point(0.5, V(4.0, 8.0, -12.0))],
                                 [L.Ambient(0.5), L.Point(0.4, V(0.0, -3.0, 0.0)), L.Point(0.5, V(4.0, 8.0, -12.0))], 4000),
         "opposite_points": ([L.Ambient(0.2), L.Point(0.5, V(-12.0, 4.0, -2.0)), L.Point(0.5, V(12.0, 4.0, 2.0))], None, 5000),
-        "point_at_origin": ([L.Ambient(0.3), L.Point(0.6, V(*TEAPOT_ORIGIN))], None, 5000),
+        "point_at_origin": ([L.Ambient(0.3), L.Point(0.6, V(*ORIGIN))], None, 5000),
         "point_at_vertex": ([L.Ambient(0.3), L.Point(0.6, V(*map(float, vertex)))], None, 5000),
         "point_inside_teapot": ([L.Ambient(0.3), L.Point(0.6, V(0.0, 1.5, 0.0)), L.Point(0.4, V(-7.0, 1.0, -15.0))], None, 5000),
         "point_outside_root": ([L.Ambient(0.3), L.Point(0.6, V(25.0, 10.0, -25.0))], None, 5000),
@@ -170,7 +153,7 @@ BAND_CASES = ("point_at_vertex",)    # a light on a mesh vertex: shadow rays of 
 def test_teapot_light_lists(rrt, ob, teapot, teapot_arrays, case):
     lights, neighbour, min_teeth = _teapot_lights(rrt, teapot_arrays)[case]
     neighbour = rrt.default_lights() if neighbour is None else neighbour
-    frames = run_case(rrt, ob, teapot, teapot_arrays, case, lights, TEAPOT_ORIGIN, (neighbour, {}), min_teeth, band_ok=case in BAND_CASES)
+    frames = run_case(rrt, ob, teapot, teapot_arrays, case, lights, ORIGIN, (neighbour, {}), min_teeth, band_ok=case in BAND_CASES)
     f = frames[0][1:]
     if case == "empty":                                          # no light: every hit is black, every miss white, mixed per pixel
         c = channels(f)
@@ -178,7 +161,7 @@ def test_teapot_light_lists(rrt, ob, teapot, teapot_arrays, case):
         assert (f == 0).sum() > 5000 and (f == 0xFFFFFF).sum() > 5000
     elif case == "zero_directional":                             # |l| = 0: n.l = 0 gives no diffuse, r = 0 no specular -- the ambient-only frame
         w, h = SIZES[0]
-        assert np.array_equal(frames[0], _oracle_frame(ob, teapot_arrays, lights[:1], TEAPOT_ORIGIN, w, h))
+        assert np.array_equal(frames[0], _oracle_frame(ob, teapot_arrays, lights[:1], ORIGIN, w, h))
     elif case == "negative_and_saturating":
         assert (f == 0xFFFFFF).sum() > 9000 and (f == 0).sum() > 1000   # lit hits clamp to white (misses alone: ~7800), shadowed ones to black
     elif case == "break_drops_ambient":                          # the light under the table is occluded for most of the frame: black there
@@ -187,16 +170,14 @@ def test_teapot_light_lists(rrt, ob, teapot, teapot_arrays, case):
 
 def test_sixteen_lights_ray_colours(rrt, ob, teapot, teapot_arrays):
     """get_ray_colours against oracle.get_ray_colour with the 16-light list: primary sub-sample rays plus shadow- and reflection-shaped rays
-    (test_gpu_configs.sample_rays), in all three walk variants."""
+    (gpu_checks.sample_rays), in all three walk variants."""
     lights = _teapot_lights(rrt, teapot_arrays)["sixteen_lights"][0]
-    osc = _oracle(ob, teapot_arrays, lights, TEAPOT_ORIGIN)
+    osc = oracle_for(ob, teapot_arrays, lights)
     O, D, _ = sample_rays(osc, 160, 120, 1500, np.random.default_rng(1616), lights)
     assert len(O) > 5000
     ref = np.fromiter((osc.get_ray_colour(O[i], D[i]) for i in range(len(O))), np.uint32, len(O))
-    for mode in ("lane", "bundle", "ray"):
-        got = rrt.RayTracer(teapot, lights, box_filter=mode).get_ray_colours(O, D)
-        d = np.abs(channels(got) - channels(ref)).max(-1)
-        assert d.max() <= COLOUR_TOL, f"walk {mode}: {(d > COLOUR_TOL).sum()} of {len(O)} rays differ from the oracle by more than {COLOUR_TOL}"
+    for mode in FORCED_MODES:
+        assert_frame_close(rrt.RayTracer(teapot, lights, box_filter=mode).get_ray_colours(O, D), ref, f"walk {mode}: ray colours")
 
 
 def test_invalid_lights_and_depth_are_rejected(rrt, teapot):
@@ -209,40 +190,14 @@ def test_invalid_lights_and_depth_are_rejected(rrt, teapot):
 
 
 # ------------------------------------------------------------------ hand-built scenes
-def _quad(a, b, c, d):
-    return [[a, b, c], [a, c, d]]
-
-
-def _box(lo, hi):
-    (x0, y0, z0), (x1, y1, z1) = lo, hi
-    p = [(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)]
-    faces = ((0, 1, 2, 3), (5, 4, 7, 6), (4, 0, 3, 7), (1, 5, 6, 2), (3, 2, 6, 7), (4, 5, 1, 0))
-    return [t for f in faces for t in _quad(*(p[i] for i in f))]
-
-
-def _flat_normals(tris, towards):
-    """Per-triangle face normals, flipped to face the point `towards`."""
-    t = np.asarray(tris, np.float64)
-    n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]); n /= np.linalg.norm(n, axis=1)[:, None]
-    flip = ((np.asarray(towards) - t.mean(1)) * n).sum(1) < 0
-    n[flip] *= -1
-    return np.repeat(n[:, None], 3, 1)
-
-
-def _checker(c0, c1, k=8):
-    yy, xx = np.mgrid[0:k, 0:k]
-    t = np.where(((xx + yy) % 2 == 0)[..., None], np.array(c0, np.uint8), np.array(c1, np.uint8))
-    return np.ascontiguousarray(t.astype(np.uint8))
-
-
 def _scene(rrt, groups, towards, materials, textures):
     """groups: [(triangles, material id)]; uv from x/z (or x/y) so that textures vary across every surface."""
     tris = [t for g, _ in groups for t in g]
     mat = np.array([m for g, m in groups for _ in g], np.uint32)
     pos = np.asarray(tris, np.float64)
     uv = np.zeros_like(pos); uv[..., 0] = pos[..., 0] * 0.13 + pos[..., 2] * 0.07; uv[..., 1] = pos[..., 1] * 0.11 + pos[..., 2] * 0.05
-    nrm = _flat_normals(tris, towards)
-    A = dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=materials, textures=textures, root=(-20.0, 20.0, -20.0, 20.0, -20.0, 20.0))
+    nrm = flat_normals(tris, towards)
+    A = dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=materials, textures=textures, root=ROOT_BOX)
     return rrt.SceneData.from_arrays(pos, uv, nrm, mat, materials, textures), A
 
 
@@ -254,12 +209,12 @@ def _shadow_box_scene(rrt):
     mats = [dict(ka=(1, 1, 1), kd=(0.9, 0.9, 0.9), ks=(0.3, 0.3, 0.3), ns=20.0, kr=0.0, tex=0, bump=-1),
             dict(ka=(0.8, 0.8, 0.8), kd=(0.7, 0.7, 0.7), ks=(0.5, 0.5, 0.5), ns=60.0, kr=0.0, tex=1, bump=-1),
             dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=2, bump=-1)]
-    tex = [_checker((200, 180, 150), (90, 110, 140)), _checker((150, 220, 120), (60, 60, 60), 4), np.full((2, 2, 3), 230, np.uint8)]
-    groups = [(_quad((-6, 0, -4), (6, 0, -4), (6, 0, 8), (-6, 0, 8)), 0),            # floor
-              (_quad((-6, 0, 8), (6, 0, 8), (6, 7, 8), (-6, 7, 8)), 1),              # back wall
-              (_quad((-6, 0, -4), (-6, 0, 8), (-6, 7, 8), (-6, 7, -4)), 1),          # left wall
-              (_quad((-1.5, 2, 0), (1.5, 2, 0), (1.5, 2, 2.5), (-1.5, 2, 2.5)), 2),  # blocker, 2 above the floor
-              (_box((2, 0, 3), (4, 2, 5)), 1)]                                       # closed box
+    tex = [checker((200, 180, 150), (90, 110, 140)), checker((150, 220, 120), (60, 60, 60), 4), np.full((2, 2, 3), 230, np.uint8)]
+    groups = [(quad((-6, 0, -4), (6, 0, -4), (6, 0, 8), (-6, 0, 8)), 0),            # floor
+              (quad((-6, 0, 8), (6, 0, 8), (6, 7, 8), (-6, 7, 8)), 1),              # back wall
+              (quad((-6, 0, -4), (-6, 0, 8), (-6, 7, 8), (-6, 7, -4)), 1),          # left wall
+              (quad((-1.5, 2, 0), (1.5, 2, 0), (1.5, 2, 2.5), (-1.5, 2, 2.5)), 2),  # blocker, 2 above the floor
+              (closed_box((2, 0, 3), (4, 2, 5)), 1)]                                 # closed box
     return _scene(rrt, groups, (0.0, 3.0, 1.0), mats, tex)
 
 
@@ -299,12 +254,12 @@ def _corridor_scene(rrt):
             dict(ka=(1, 1, 1), kd=(0.8, 0.8, 0.8), ks=(0.6, 0.6, 0.6), ns=40.0, kr=0.75, tex=1, bump=-1),
             dict(ka=(1, 1, 1), kd=(0.7, 0.7, 0.7), ks=(0.2, 0.2, 0.2), ns=10.0, kr=0.6, tex=2, bump=-1),
             dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=3, bump=-1)]
-    tex = [_checker((250, 40, 30), (200, 20, 60), 4), _checker((20, 40, 250), (60, 20, 200), 4), _checker((30, 240, 40), (90, 200, 20), 4),
-           _checker((180, 180, 180), (90, 90, 90))]
-    groups = [(_quad((-15, -10, 8), (15, -10, 8), (15, 10, 8), (-15, 10, 8)), 0),
-              (_quad((-15, -10, -12), (15, -10, -12), (15, 10, -12), (-15, 10, -12)), 1),
-              (_quad((4, -3, -6), (9, -3, 0), (9, 6, 0), (4, 6, -6)), 2),                # oblique, 50 degrees to the corridor's axis
-              (_quad((-15, -3, -12), (15, -3, -12), (15, -3, 8), (-15, -3, 8)), 3)]       # floor
+    tex = [checker((250, 40, 30), (200, 20, 60), 4), checker((20, 40, 250), (60, 20, 200), 4), checker((30, 240, 40), (90, 200, 20), 4),
+           checker((180, 180, 180), (90, 90, 90))]
+    groups = [(quad((-15, -10, 8), (15, -10, 8), (15, 10, 8), (-15, 10, 8)), 0),
+              (quad((-15, -10, -12), (15, -10, -12), (15, 10, -12), (-15, 10, -12)), 1),
+              (quad((4, -3, -6), (9, -3, 0), (9, 6, 0), (4, 6, -6)), 2),                # oblique, 50 degrees to the corridor's axis
+              (quad((-15, -3, -12), (15, -3, -12), (15, -3, 8), (-15, -3, 8)), 3)]       # floor
     return _scene(rrt, groups, (0.0, 1.0, -2.0), mats, tex)
 
 
@@ -339,7 +294,7 @@ OFFSET_TEETH = {"teapot": {0.0: 3000, 1e-12: 20, 1e-6: 20, 1e-4: 200, 1e-2: 200,
 @pytest.mark.parametrize("offset", OFFSETS)
 def test_surface_offset_teapot(rrt, ob, teapot, teapot_arrays, offset):
     lights = rrt.default_lights()
-    run_case(rrt, ob, teapot, teapot_arrays, f"teapot/offset {offset:g}", lights, TEAPOT_ORIGIN, (lights, dict(surface_offset=NEIGHBOUR_OFFSET[offset])),
+    run_case(rrt, ob, teapot, teapot_arrays, f"teapot/offset {offset:g}", lights, ORIGIN, (lights, dict(surface_offset=NEIGHBOUR_OFFSET[offset])),
              OFFSET_TEETH["teapot"][offset], band_ok=offset == 0.0, surface_offset=offset)
 
 

@@ -9,10 +9,11 @@ import os
 import numpy as np
 import pytest
 
-from conftest import ASSETS, GOLDEN, channels, lights_tuple, max_channel_diff, oracle_scene_for
+from conftest import ASSETS, GOLDEN, channels, oracle_scene_for
+from gpu_checks import (N_THREADS, ORIGIN, assert_frame_close, assert_rays_match_oracle, assert_walks_match, check_rows_against_oracle,
+                        oracle_for)
 
 pytestmark = pytest.mark.gpu
-COLOUR_TOL = 1   # per RGB channel, BASELINE.json
 
 
 def _free_port():
@@ -39,16 +40,11 @@ def teapot_rt(rrt, teapot):
     return rrt.RayTracer(teapot, rrt.default_lights(), rrt.DEFAULT_ORIGIN, device=0)
 
 
-def assert_frame_close(gpu, ref, what):
-    d = np.abs(channels(gpu) - channels(ref))
-    assert d.max() <= COLOUR_TOL, f"{what}: max channel diff {d.max()} on {(d.max(-1) > COLOUR_TOL).sum()} pixels"
-
-
 @pytest.mark.parametrize("w,h", [(64, 48), (97, 61), (160, 120), (1, 1), (2, 2), (8, 3), (640, 480)])
 def test_teapot_frames_match_oracle(teapot_rt, teapot_oracle, w, h):
     """configs[0] scene (model2.obj) incl. 640x480, odd sizes (unwritten last column / rows 0-1) and degenerate sizes."""
     gpu = teapot_rt.render(w, h)
-    ref, _ = teapot_oracle.render(w, h)
+    ref, _ = teapot_oracle.render(w, h, n_threads=N_THREADS)
     assert_frame_close(gpu, ref, f"{w}x{h}")
     assert (gpu[0] == 0).all()                                   # row 0 never written (engine.rs:146-158)
     assert np.array_equal(gpu == 0, ref == 0)
@@ -69,7 +65,7 @@ def test_golden_fixtures(rrt, name):
     assert np.array_equal(tri[m], g["ray_tri"][m])
     assert np.array_equal(t[m], g["ray_t"][m]) and np.array_equal(u[m], g["ray_u"][m]) and np.array_equal(v[m], g["ray_v"][m])   # bit-exact
     col = rt.get_ray_colours(g["ray_o"], g["ray_d"])
-    assert np.abs(channels(col) - channels(g["ray_col"])).max() <= COLOUR_TOL
+    assert_frame_close(col, g["ray_col"], f"{name} ray colours")
 
 
 def test_random_rays_with_max_t_bit_exact(teapot_rt, teapot_oracle):
@@ -80,13 +76,9 @@ def test_random_rays_with_max_t_bit_exact(teapot_rt, teapot_oracle):
     o[:200, 0] = 0.0; d[:100, 0] = 0.0          # on the root split plane x = 0, some with d.x = 0 (NaN slab path)
     o[200:300, 1] = 0.0; o[300:400, 2] = 0.0
     mt = rng.uniform(0.5, 30.0, n); mt[::5] = np.inf
-    hit, t, u, v, tri = teapot_rt.intersect_rays(o, d, mt)
-    for i in range(n):
-        rh, rt_, ru, rv, rtri = teapot_oracle.intersect(o[i], d[i], mt[i])
-        assert bool(hit[i]) == rh, i
-        if rh:
-            assert (t[i], u[i], v[i], tri[i]) == (rt_, ru, rv, rtri), i
-    assert 0.2 < hit.mean() < 0.95
+    got = teapot_rt.intersect_rays(o, d, mt)
+    assert_rays_match_oracle(got, teapot_oracle, o, d, mt, "random rays with max_t")
+    assert 0.2 < got[0].mean() < 0.95
 
 
 @pytest.mark.parametrize("mode", ["lane", "bundle", "ray"])
@@ -101,34 +93,24 @@ def test_extreme_ray_magnitudes_bit_exact(rrt, teapot, teapot_oracle, mode):
     d *= scale[:, None]
     o[400:450, 0] = 1e-300; o[450:500, 1] = 5e-201 ; o[500:550, 2] = 0.0; o[550:, 0] = 2.0 ** -1060   # denormal
     rt = rrt.RayTracer(teapot, rrt.default_lights(), box_filter=mode)
-    hit, t, u, v, tri = rt.intersect_rays(o, d)
-    n_hit = 0
-    for i in range(n):
-        rh, rt_, ru, rv, rtri = teapot_oracle.intersect(o[i], d[i])
-        assert bool(hit[i]) == rh, i
-        if rh:
-            n_hit += 1
-            assert (t[i], u[i], v[i], tri[i]) == (rt_, ru, rv, rtri), i
+    n_hit = assert_rays_match_oracle(rt.intersect_rays(o, d), teapot_oracle, o, d, what=f"extreme magnitudes, walk {mode}")
     assert n_hit > 100
 
 
 def test_center_column_nan_path(teapot_rt, teapot_oracle):
     """Column w/2: d.x = 0 at origin.x = 0 == the root split plane -> (0-0)/0 = NaN in the slab test (ray.rs:22-23)."""
     w, h = 128, 96
-    gpu = teapot_rt.render(w, h); ref, _ = teapot_oracle.render(w, h)
+    gpu = teapot_rt.render(w, h); ref, _ = teapot_oracle.render(w, h, n_threads=N_THREADS)
     assert_frame_close(gpu[:, w // 2 - 1:w // 2 + 2], ref[:, w // 2 - 1:w // 2 + 2], "centre columns")
     ys = np.linspace(-0.4, 0.4, 257)
-    o = np.tile([0.0, 2.0, -10.0], (len(ys), 1)); d = np.stack([np.zeros_like(ys), ys, np.ones_like(ys)], -1)
-    hit, t, u, v, tri = teapot_rt.intersect_rays(o, d)
-    for i in range(len(ys)):
-        rh, rt_, ru, rv, rtri = teapot_oracle.intersect(o[i], d[i])
-        assert (bool(hit[i]), tri[i] if rh else 0) == (rh, rtri if rh else 0) and (not rh or t[i] == rt_)
+    o = np.tile(ORIGIN, (len(ys), 1)); d = np.stack([np.zeros_like(ys), ys, np.ones_like(ys)], -1)
+    assert_rays_match_oracle(teapot_rt.intersect_rays(o, d), teapot_oracle, o, d, what="centre column rays", uv=False)
 
 
 def test_mirror_and_shadow_pixels_present(teapot_rt, teapot_oracle):
     """The frame exercises reflection (Kr 0.95 mirror, model2.obj:25977-25990) and the shadow `break`; both must match the oracle."""
     w, h = 320, 240
-    gpu = teapot_rt.render(w, h); ref, cnt = teapot_oracle.render(w, h)
+    gpu = teapot_rt.render(w, h); ref, cnt = teapot_oracle.render(w, h, n_threads=N_THREADS)
     assert cnt["rays_reflect"] > 1000 and cnt["rays_shadow"] > cnt["rays_primary"] // 2
     assert_frame_close(gpu, ref, "320x240")
     assert (ref == 0xFFFFFF).sum() > 100                         # miss pixels are WHITE
@@ -139,18 +121,15 @@ def test_options_viewport_offset_depth(rrt, teapot, ob):
     rt = rrt.RayTracer(teapot, lights, rrt.Vector3d(0.5, 2.5, -9.0), surface_offset=3e-3, max_reflection_depth=2, viewport=(1.5, 1.0, 1.25))
     osc = oracle_scene_for(ob, rrt, teapot, lights, (0.5, 2.5, -9.0))
     o = np.tile([0.5, 2.5, -9.0], (64, 1)); d = np.stack([np.linspace(-0.3, 0.6, 64), np.full(64, -0.12), np.ones(64)], -1)
-    hit, t, u, v, tri = rt.intersect_rays(o, d)
-    for i in range(64):
-        rh, rt_, ru, rv, rtri = osc.intersect(o[i], d[i])
-        assert bool(hit[i]) == rh and (not rh or (t[i], tri[i]) == (rt_, rtri))
-    ref, _ = osc.render(96, 64, viewport=(1.5, 1.0, 1.25))
+    assert_rays_match_oracle(rt.intersect_rays(o, d), osc, o, d, what="viewport rays", uv=False)
+    ref, _ = osc.render(96, 64, viewport=(1.5, 1.0, 1.25), n_threads=N_THREADS)
     gpu = rrt.RayTracer(teapot, lights, rrt.Vector3d(0.5, 2.5, -9.0), viewport=(1.5, 1.0, 1.25)).render(96, 64)
     assert_frame_close(gpu, ref, "viewport 1.5x1x1.25")
     # the whole frame of the depth-2, offset-3e-3 raytracer against the oracle with the same options; the options must change the frame
     pos, uv, nrm, mat = teapot.triangles()
-    osc2 = ob.OracleScene(pos, uv, nrm, mat, teapot.materials(), teapot.textures(), lights_tuple(lights), (0.5, 2.5, -9.0),
-                          surface_offset=3e-3, max_reflection_depth=2)
-    ref2, _ = osc2.render(96, 64, viewport=(1.5, 1.0, 1.25), n_threads=16)
+    A = dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
+    osc2 = oracle_for(ob, A, lights, (0.5, 2.5, -9.0), surface_offset=3e-3, max_reflection_depth=2)
+    ref2, _ = osc2.render(96, 64, viewport=(1.5, 1.0, 1.25), n_threads=N_THREADS)
     got = rt.render(96, 64)
     assert got.shape == (64, 96)
     assert_frame_close(got, ref2, "viewport 1.5x1x1.25, depth 2, offset 3e-3")
@@ -238,18 +217,7 @@ def test_full_size_properties_1080p(teapot_rt, teapot_oracle):
     assert st["rays_primary"] == 4 * 1920 * 1079 and st["kernel_ms"] > 0
     rng = np.random.default_rng(3)
     rows = sorted(set(rng.integers(1, h, 6).tolist()) | {1, h // 2, h - 1})
-    o = np.tile([0.0, 2.0, -10.0], (4 * w, 1))
-    L = None
-    for r in rows:
-        y = (h - h // 2) - r
-        xs = np.arange(-(w // 2), w // 2, dtype=np.float64)
-        d = np.empty((4, w, 3)); d[..., 2] = 1.0
-        d[0, :, 0] = xs * (1.0 / w); d[1, :, 0] = (xs + 0.5) * (1.0 / w); d[2, :, 0] = d[0, :, 0]; d[3, :, 0] = d[1, :, 0]
-        d[0, :, 1] = y * (1.0 / h); d[1, :, 1] = d[0, :, 1]; d[2, :, 1] = (y + 0.5) * (1.0 / h); d[3, :, 1] = d[2, :, 1]
-        cols = np.array([[teapot_oracle.get_ray_colour((0.0, 2.0, -10.0), d[k, i]) for i in range(0, w, 16)] for k in range(4)], np.uint32)
-        mixed = (channels(cols).sum(0) // 4)
-        got = channels(a[r, 0:w:16])
-        assert np.abs(got - mixed).max() <= COLOUR_TOL, r
+    check_rows_against_oracle(a, teapot_oracle, w, h, rows, 16)
 
 
 def test_soup_scene_matches_oracle(rrt, ob):
@@ -260,7 +228,7 @@ def test_soup_scene_matches_oracle(rrt, ob):
     lights = rrt.default_lights()
     rt = rrt.RayTracer(sd, lights)
     osc = oracle_scene_for(ob, rrt, sd, lights)
-    gpu = rt.render(200, 150); ref, _ = osc.render(200, 150)
+    gpu = rt.render(200, 150); ref, _ = osc.render(200, 150, n_threads=N_THREADS)
     assert_frame_close(gpu, ref, "soup 20k 200x150")
     assert ((ref != 0xFFFFFF) & (ref != 0)).mean() > 0.2
 
@@ -270,14 +238,13 @@ def test_tiny_scenes_edge_cases(rrt, ob):
     mats = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(1, 1, 1), ns=240.0, kr=0.3, tex=0, bump=-1)]
     tex = [np.arange(48, dtype=np.uint8).reshape(4, 4, 3)]
     lights = rrt.default_lights()
-    lt = [(l.kind, l.intensity, (l.v.x, l.v.y, l.v.z)) for l in lights]
     for tris in (np.zeros((0, 3, 3)), np.array([[[-3, 0, 2], [3, 0, 2], [0, 5, 2.5]]], np.float64),
                  np.array([[[-3, 0, 2], [3, 0, 2], [0, 5, 2.5]], [[50, 50, 50], [51, 50, 50], [50, 51, 50]], [[-2, 1, 1], [2, 1, 1], [0, 3, 1.2]]], np.float64)):
         n = len(tris)
         uv = np.tile([[0.1, 0.2, 0], [0.9, 0.1, 0], [0.5, 0.8, 0]], (n, 1, 1)).astype(np.float64); nrm = np.tile([0.0, 0.1, -1.0], (n, 3, 1))
         sd = rrt.SceneData.from_arrays(tris, uv, nrm, np.zeros(n, np.uint32), mats, tex)
-        osc = ob.OracleScene(tris, uv, nrm, np.zeros(n, np.uint32), mats, tex, lt, (0, 2, -10))
-        gpu = rrt.RayTracer(sd, lights).render(40, 30); ref, _ = osc.render(40, 30)
+        osc = oracle_for(ob, dict(pos=tris, uv=uv, nrm=nrm, mat=np.zeros(n, np.uint32), materials=mats, textures=tex), lights)
+        gpu = rrt.RayTracer(sd, lights).render(40, 30); ref, _ = osc.render(40, 30, n_threads=N_THREADS)
         assert_frame_close(gpu, ref, f"{n} triangles")
 
 
@@ -299,7 +266,7 @@ def _random_scene(rng, kind):
         tris += [[(0.0, 0, 1), (0.0, 4, 1), (0.0, 4, 5)], [(0.0, 0, 1), (0.0, 4, 5), (0.0, 0, 5)]]
         tris += [[(-4, -0.5, -2), (4, -0.5, -2), (0, -0.5, 9)]]
     elif kind == "noise":                                # triangles built (in f64) INSIDE planes that contain the camera origin and one sub-sample ray each:
-        o = np.array([0.0, 2.0, -10.0])                  # that ray is coplanar with them up to rounding, a = e1.(d x e2) is pure noise of either sign
+        o = np.array(ORIGIN)                             # that ray is coplanar with them up to rounding, a = e1.(d x e2) is pure noise of either sign
         for (px, py) in [(10, 7), (-21.5, 3), (5, -12.5), (0.5, 0.5), (33, -8)]:
             d0 = np.array([px / 128.0, py / 96.0, 1.0])
             for k in range(6):
@@ -338,16 +305,13 @@ def test_adversarial_random_scenes(rrt, ob, kind):
     rng = np.random.default_rng({"grid": 1, "coplanar": 2, "slivers": 3, "soup": 4, "noise": 5}[kind])
     tris, uv, nrm, mat, mats, tex = _random_scene(rng, kind)
     lights = rrt.default_lights()
-    lt = [(l.kind, l.intensity, (l.v.x, l.v.y, l.v.z)) for l in lights]
     sd = rrt.SceneData.from_arrays(tris, uv, nrm, mat, mats, tex)
-    osc = ob.OracleScene(tris, uv, nrm, mat, mats, tex, lt, (0, 2, -10))
+    osc = oracle_for(ob, dict(pos=tris, uv=uv, nrm=nrm, mat=mat, materials=mats, textures=tex), lights)
     w, h = 128, 96                                        # even sizes: the rows y = 0 (d.y = 0) and the column x = 0 (d.x = 0) are sampled
-    ref, _ = osc.render(w, h)
+    ref, _ = osc.render(w, h, n_threads=N_THREADS)
     exact = rrt.RayTracer(sd, lights, no_cull=True).render(w, h)
     assert_frame_close(exact, ref, f"{kind} no_cull vs oracle")
-    for mode in (None, "lane", "bundle", "ray"):
-        got = rrt.RayTracer(sd, lights, box_filter=mode).render(w, h)
-        assert np.array_equal(got, exact), f"{kind}: filter {mode} differs from no_cull on {(got != exact).sum()} pixels"
+    assert_walks_match(lambda mode: rrt.RayTracer(sd, lights, box_filter=mode), [exact], [(w, h)], kind)
 
 
 def test_cpp_host_cli_matches_python_host(rrt, teapot_rt, tmp_path):
@@ -413,23 +377,17 @@ def test_deep_octree_rays_bit_exact(rrt, ob, mode):
     sd = rrt.SceneData.from_arrays(tris, uv, nrm, np.zeros(n, np.uint32), mats, tex)
     assert sd.info["max_depth"] >= 18, sd.info
     lights = rrt.default_lights()
-    osc = ob.OracleScene(tris, uv, nrm, np.zeros(n, np.uint32), mats, tex, [(l.kind, l.intensity, (l.v.x, l.v.y, l.v.z)) for l in lights], (0, 2, -10))
-    cam = np.array([0.0, 2.0, -10.0])
+    osc = oracle_for(ob, dict(pos=tris, uv=uv, nrm=nrm, mat=np.zeros(n, np.uint32), materials=mats, textures=tex), lights)
+    cam = np.array(ORIGIN)
     cen = tris[:-1].mean(1)
     ext = np.abs(tris[:-1] - cen[:, None, :]).max((1, 2))
     targets = np.concatenate([cen, cen + rng.normal(size=cen.shape) * ext[:, None] * 0.6, cen + rng.normal(size=cen.shape) * ext[:, None] * 3.0])
     o = np.tile(cam, (len(targets), 1)); d = targets - cam
     rt = rrt.RayTracer(sd, lights, no_cull=True) if mode == "no_cull" else rrt.RayTracer(sd, lights, box_filter=mode)
-    hit, t, u, v, tri = rt.intersect_rays(o, d)
-    small = 0
-    for i in range(len(targets)):
-        rh, rt_, ru, rv, rtri = osc.intersect(o[i], d[i])
-        assert bool(hit[i]) == rh, i
-        if rh:
-            assert (t[i], u[i], v[i], tri[i]) == (rt_, ru, rv, rtri), i
-            small += rtri != n - 1
-    assert small > 100                                           # the tiny triangles in the deep leaves are really being hit
-    assert_frame_close(rt.render(64, 48), osc.render(64, 48)[0], "deep-octree frame")
+    hit, _, _, _, tri = got = rt.intersect_rays(o, d)
+    assert_rays_match_oracle(got, osc, o, d, what=f"deep octree, walk {mode}")
+    assert (hit & (tri != n - 1)).sum() > 100                    # the tiny triangles in the deep leaves are really being hit
+    assert_frame_close(rt.render(64, 48), osc.render(64, 48, n_threads=N_THREADS)[0], "deep-octree frame")
 
 
 def test_long_own_list_with_group_records(rrt, ob):
@@ -450,21 +408,18 @@ def test_long_own_list_with_group_records(rrt, ob):
     sd = rrt.SceneData.from_arrays(tris, uv, nrm, np.zeros(n, np.uint32), mats, tex)
     assert sd.info["root_own_count"] > 24 * 64, sd.info
     lights = rrt.default_lights()
-    osc = ob.OracleScene(tris, uv, nrm, np.zeros(n, np.uint32), mats, tex, [(l.kind, l.intensity, (l.v.x, l.v.y, l.v.z)) for l in lights], (0, 2, -10))
-    ref, _ = osc.render(160, 120)
+    osc = oracle_for(ob, dict(pos=tris, uv=uv, nrm=nrm, mat=np.zeros(n, np.uint32), materials=mats, textures=tex), lights)
+    ref, _ = osc.render(160, 120, n_threads=N_THREADS)
     assert ((ref != 0xFFFFFF) & (ref != 0)).mean() > 0.02
     exact = rrt.RayTracer(sd, lights, no_cull=True).render(160, 120)
     assert_frame_close(exact, ref, "long list, reference order")
-    for mode in ("lane", "bundle", "ray", None):
-        assert np.array_equal(rrt.RayTracer(sd, lights, box_filter=mode).render(160, 120), exact), mode
-    cam = np.array([0.0, 2.0, -10.0])
+    assert_walks_match(lambda mode: rrt.RayTracer(sd, lights, box_filter=mode), [exact], [(160, 120)], "long list")
+    cam = np.array(ORIGIN)
     tgt = tris.mean(1)[::7] + rng.normal(size=(len(tris[::7]), 3)) * 0.02
     o = np.tile(cam, (len(tgt), 1)); d = tgt - cam
-    hit, t, u, v, tri = rrt.RayTracer(sd, lights, box_filter="lane").intersect_rays(o, d)
-    for i in range(len(tgt)):
-        rh, rt_, ru, rv, rtri = osc.intersect(o[i], d[i])
-        assert bool(hit[i]) == rh and (not rh or (t[i], u[i], v[i], tri[i]) == (rt_, ru, rv, rtri)), i
-    assert hit.mean() > 0.5
+    got = rrt.RayTracer(sd, lights, box_filter="lane").intersect_rays(o, d)
+    assert_rays_match_oracle(got, osc, o, d, what="long list, lane filter")
+    assert got[0].mean() > 0.5
 
 
 def test_bench_multi_gpu_choreography_single_rank():
@@ -559,7 +514,6 @@ def test_triangles_poking_out_of_the_root_box(rrt, ob):
     mats = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0.3, 0.3, 0.3), ns=40.0, kr=0.0, tex=0, bump=-1)]
     tex = [rng.integers(0, 256, (8, 8, 3), dtype=np.uint8)]
     lights = rrt.default_lights()
-    lt = [(l.kind, l.intensity, (l.v.x, l.v.y, l.v.z)) for l in lights]
     def scene(reach):
         tris = []
         for _ in range(400):                                            # a wall of small triangles inside the root
@@ -581,11 +535,10 @@ def test_triangles_poking_out_of_the_root_box(rrt, ob):
         pos, uv, nrm, mat = scene(reach)
         sd = rrt.SceneData.from_arrays(pos, uv, nrm, mat, mats, tex, root=root)
         for origin in ((0.0, 0.0, -3.5), (1.5, 0.4, -3.0)):                # (inside the filter's range of 4 x the scene magnitude: farther origins switch the fp32 filters off altogether)
-            osc = ob.OracleScene(pos, uv, nrm, mat, mats, tex, lt, origin, root=root)
-            want, _ = osc.render(480, 360)
-            for mode in (None, "bundle", "lane", "ray"):
-                got = rrt.RayTracer(sd, lights, rrt.Vector3d(*origin), box_filter=mode).render(480, 360)
-                assert np.array_equal(got, want), (reach, origin, mode, int((got != want).sum()))
+            osc = oracle_for(ob, dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=mats, textures=tex, root=root), lights, origin)
+            want, _ = osc.render(480, 360, n_threads=N_THREADS)
+            assert_walks_match(lambda mode: rrt.RayTracer(sd, lights, rrt.Vector3d(*origin), box_filter=mode), [want], [(480, 360)],
+                               f"reach {reach}, origin {origin}, against the oracle")
         assert ((want != 0xFFFFFF) & (want != 0)).mean() > 0.02
 
 
@@ -636,7 +589,7 @@ def test_gpu_frame_matches_the_references_screenshot(rrt, teapot, teapot_rt):
     ok = np.ones(len(rows), bool); low = np.full(len(rows), np.inf)
     for dx, dy in ((0, 0), (.5, 0), (0, .5), (.5, .5)):
         d = np.stack([(x + dx) * (1.0 / W), (y + dy) * (1.0 / H), np.ones(len(x))], -1)
-        hit, t, _, _, tri = teapot_rt.intersect_rays(np.tile([0.0, 2.0, -10.0], (len(x), 1)), d)
+        hit, t, _, _, tri = teapot_rt.intersect_rays(np.tile(ORIGIN, (len(x), 1)), d)
         ok &= hit & (mat[np.minimum(tri, len(mat) - 1)] == teapot_mat)
         low = np.minimum(low, np.where(hit, 2.0 + d[:, 1] * t, np.inf))
     sel = ok & (low >= 0.6)

@@ -16,16 +16,17 @@ A = os.path.join(ROOT, "assets")
 configs = [("configs[0] teapot 640x480", os.path.join(A, "model2.obj"), 640, 480), ("configs[1] teapot 1920x1080", os.path.join(A, "model2.obj"), 1920, 1080),
            ("configs[2] 100k soup 1920x1080", syn.ensure_soup(A, 100000, syn.SEED_100K), 1920, 1080), ("configs[3] teapot 3840x2160", os.path.join(A, "model2.obj"), 3840, 2160),
            ("configs[4] 1M soup 3840x2160", syn.ensure_soup(A, 1000000, syn.SEED_1M), 3840, 2160)]
-# ---- self-check of the counter: the construction of tests/test_gpu_configs.py case C -- 400 triangles built in f64 INSIDE planes through an apex that is
-# not the raytracer's origin, 200 000 rays from that apex lying in those planes to rounding.  The reference's Moller-Trumbore accepts a few per cent of
-# such pairs (rounding noise): every one of them is a secondary-ray pair (origin != the raytracer's) and must be counted as in-band.
+# ---- self-check of the counter: the construction of case C of tests/test_gpu_configs.py (test_filter_exactness_guard_near_coplanar_rays_at_scale), built
+# by tests/gpu_checks.py -- 400 triangles built in f64 INSIDE planes through an apex that is not the raytracer's origin, 200 000 rays from that apex lying
+# in those planes to rounding.  The reference's Moller-Trumbore accepts a few per cent of such pairs (rounding noise): every one of them is a secondary-ray
+# pair (origin != the raytracer's) and must be counted as in-band.
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_gpu_configs as tc
+import gpu_checks as gc
 rng = np.random.default_rng(55)
 apex = np.array([1.5, 1.0, -8.0])
-tris, planes = tc._plane_scene(rng, apex, 40, 10, 1000)
-sd = tc._scene_data(rrt, tris)
-O, D = tc._coplanar_rays(rng, tris, planes, 400, apex, 200_000)
+tris, planes = gc.plane_scene(rng, apex, 40, 10, 1000)
+sd = gc.plane_scene_data(rrt, tris)
+O, D = gc.coplanar_rays(rng, tris, planes, 400, apex, 200_000)
 rt = rrt.RayTracer(sd, rrt.default_lights(), no_cull=True)
 buf = (C.c_uint64 * 4)()
 L.rrt_prof_band_counters(rt._h, buf); hit = rt.intersect_rays(O, D)[0]; L.rrt_prof_band_counters(rt._h, buf)
