@@ -147,7 +147,7 @@ def run(args):
     env = dict(os.environ, RRT_LIB=os.environ.get("RRT_BBPROF_LIB", os.path.join(ROOT, "rust-ray-tracer_amd", "librrt_hip_dev.so")),
                RRT_DEV_HSACO=os.environ.get("RRT_BBPROF_HSACO", HSACO), RRT_DEV_BBPROF_OUT=COUNTS)
     if os.path.exists(COUNTS): os.remove(COUNTS)
-    subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-host-fb", *args], env=env, check=True)
+    subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-host-fb", *args], env=env, check=True, timeout=600)
     print("->", COUNTS)
 
 

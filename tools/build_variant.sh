@@ -1,5 +1,5 @@
 #!/bin/bash
-# Developer tool: build a variant of librrt_hip.so for A/B timing (tools/ab_variants.sh, tools/ab_multi.py):
+# Developer tool: build a variant of librrt_hip.so for A/B timing (tools/ab_multi.py):
 #   tools/build_variant.sh <name> "<extra hipcc flags>" [alternative render.hip]     -> rust-ray-tracer_amd/librrt_hip_<name>.so
 # (variants are *_<name>.so; only librrt_hip.so is the product).  One compilation unit, the frame kernels' code-generation switches (csrc/Makefile:
 # KFLAGS) unless KFLAGS is set in the environment: the per-ray kernels of a variant are therefore built with the frame kernels' switches.
