@@ -453,26 +453,70 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
     RRT_DPP_STEP_U32(v, "row_bcast:31 row_mask:0xc bank_mask:0xf");
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
-// Twelve f32 min-reductions at once, step by step across all twelve registers: dependent DPP operations are then 12 instructions apart and need
-// no wait states (only the first step follows ordinary VALU writes).  All inputs are finite or +-inf, never NaN.
-#define RRT_DPP12(pre, ctrl)                                                                                         \
-    asm volatile(pre "v_min_f32_dpp %0, %0, %0 " ctrl "\n\tv_min_f32_dpp %1, %1, %1 " ctrl "\n\tv_min_f32_dpp %2, %2, %2 " ctrl "\n\t"    \
-                 "v_min_f32_dpp %3, %3, %3 " ctrl "\n\tv_min_f32_dpp %4, %4, %4 " ctrl "\n\tv_min_f32_dpp %5, %5, %5 " ctrl "\n\t"    \
-                 "v_min_f32_dpp %6, %6, %6 " ctrl "\n\tv_min_f32_dpp %7, %7, %7 " ctrl "\n\tv_min_f32_dpp %8, %8, %8 " ctrl "\n\t"    \
-                 "v_min_f32_dpp %9, %9, %9 " ctrl "\n\tv_min_f32_dpp %10, %10, %10 " ctrl "\n\tv_min_f32_dpp %11, %11, %11 " ctrl     \
-                 : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]), "+v"(x[9]), "+v"(x[10]), "+v"(x[11]))
+// Twelve f32 min-reductions over the wave, folded TOGETHER instead of one butterfly per value (72 DPP + 12 v_readlane before): min over floats that
+// are finite or +-inf, never NaN, is exactly associative and commutative, so any reduction tree gives the same bits.  A lane is (row, bank, q) =
+// (lane / 16, lane / 4 % 4, lane % 4); a DPP write can be masked per bank, which lets one fold step also merge two registers into one:
+//   1. banks 0<->1, 2<->3 (row_shl:4 into banks 0, 2; the partner value with row_shr:4 into banks 1, 3 of the SAME register): 12 registers -> 6,
+//      each holding value 2j in banks 0, 2 and value 2j+1 in banks 1, 3;
+//   2. banks {0,1}<->{2,3} (row_shl:8 / row_shr:8 likewise): 6 -> 3 registers, one value per bank: {0..3}, {4..7}, {8..11};
+//   3. rows: v_permlane32_swap of two registers + min folds rows {0,1}<->{2,3} of both into one (a lone register is swapped with its copy), then
+//      v_permlane16_swap + min folds rows 0<->1, 2<->3: one register, values 0..3 in row 0, 8..11 in rows 1 and 3, 4..7 in row 2;
+//   4. the four lanes of each bank (quad_perm), on that one register; value k is then read from the first lane of its bank.
+// 27 VALU + 12 v_readlane.  Wait states (inline asm gets none, cdna guide 5.7): a VALU write followed by a DPP or v_permlane*_swap read of the same
+// VGPR needs 2; the steps are ordered so that independent instructions supply them and `s_nop` fills in where there are none.  All of it is ONE
+// block: the producers of x[] may be the instructions directly before it (hence the leading s_nop 1), and nothing can be scheduled into it.
+#define RRT_FOLD(dst, src, ctrl, banks) "v_min_f32_dpp " dst ", " src ", " src " " ctrl " row_mask:0xf bank_mask:" banks "\n\t"
 __device__ __forceinline__ void wave_min12_f32(float (&x)[12]) {
-    // (the wait states sit INSIDE the block that holds the first DPP read: an s_nop in a statement of its own can be scheduled away from it, and the
-    //  compiler's hazard recognizer does not look into inline asm -- the x[] producers may be the instructions directly before this block)
-    RRT_DPP12("s_nop 1\n\t", "row_shr:1 row_mask:0xf bank_mask:0xf");
-    RRT_DPP12("", "row_shr:2 row_mask:0xf bank_mask:0xf");
-    RRT_DPP12("", "row_shr:4 row_mask:0xf bank_mask:0xf");
-    RRT_DPP12("", "row_shr:8 row_mask:0xf bank_mask:0xf");
-    RRT_DPP12("", "row_bcast:15 row_mask:0xa bank_mask:0xf");
-    RRT_DPP12("", "row_bcast:31 row_mask:0xc bank_mask:0xf");
+    asm volatile("s_nop 1\n\t"
+                 RRT_FOLD("%0", "%0", "row_shl:4", "0x5") RRT_FOLD("%2", "%2", "row_shl:4", "0x5") RRT_FOLD("%4", "%4", "row_shl:4", "0x5")
+                 RRT_FOLD("%6", "%6", "row_shl:4", "0x5") RRT_FOLD("%8", "%8", "row_shl:4", "0x5") RRT_FOLD("%10", "%10", "row_shl:4", "0x5")
+                 RRT_FOLD("%0", "%1", "row_shr:4", "0xa") RRT_FOLD("%2", "%3", "row_shr:4", "0xa") RRT_FOLD("%4", "%5", "row_shr:4", "0xa")
+                 RRT_FOLD("%6", "%7", "row_shr:4", "0xa") RRT_FOLD("%8", "%9", "row_shr:4", "0xa") RRT_FOLD("%10", "%11", "row_shr:4", "0xa")
+                 RRT_FOLD("%0", "%0", "row_shl:8", "0x3") RRT_FOLD("%4", "%4", "row_shl:8", "0x3") RRT_FOLD("%8", "%8", "row_shl:8", "0x3")
+                 RRT_FOLD("%0", "%2", "row_shr:8", "0xc") RRT_FOLD("%4", "%6", "row_shr:8", "0xc") RRT_FOLD("%8", "%10", "row_shr:8", "0xc")
+                 "v_mov_b32 %1, %8\n\t"
+                 "v_permlane32_swap_b32 %0, %4\n\t"          /* %4 was written three instructions back */
+                 "v_min_f32 %0, %0, %4\n\t"
+                 "v_permlane32_swap_b32 %8, %1\n\t"          /* %1 was written three instructions back */
+                 "v_min_f32 %8, %8, %1\n\t"
+                 "s_nop 1\n\t"
+                 "v_permlane16_swap_b32 %0, %8\n\t"
+                 "v_min_f32 %0, %0, %8\n\t"
+                 "s_nop 1\n\t"
+                 "v_min_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_min_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+                 : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]), "+v"(x[8]), "+v"(x[9]), "+v"(x[10]), "+v"(x[11]));
+    const int r = __builtin_bit_cast(int, x[0]);
+    constexpr int at[12] = {0, 4, 8, 12, 32, 36, 40, 44, 16, 20, 24, 28};
 #pragma unroll
-    for (int i = 0; i < 12; i++) x[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x[i]), 63));
+    for (int i = 0; i < 12; i++) x[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(r, at[i]));
 }
+// The same for six values (a bundle with one origin, make_bundle): step 1 leaves {0,1}, {2,3}, {4,5}; step 2 leaves 0..3 by bank in one register
+// and 4, 5 in banks 0, 1 of another; step 3 puts 0..3 into row 0 and 4, 5 into row 2.  16 VALU + 6 v_readlane.
+__device__ __forceinline__ void wave_min6_f32(float (&x)[6]) {
+    asm volatile("s_nop 1\n\t"
+                 RRT_FOLD("%0", "%0", "row_shl:4", "0x5") RRT_FOLD("%2", "%2", "row_shl:4", "0x5") RRT_FOLD("%4", "%4", "row_shl:4", "0x5")
+                 RRT_FOLD("%0", "%1", "row_shr:4", "0xa") RRT_FOLD("%2", "%3", "row_shr:4", "0xa") RRT_FOLD("%4", "%5", "row_shr:4", "0xa")
+                 RRT_FOLD("%0", "%0", "row_shl:8", "0x3") RRT_FOLD("%0", "%2", "row_shr:8", "0xc") RRT_FOLD("%4", "%4", "row_shl:8", "0x3")
+                 "s_nop 1\n\t"
+                 "v_permlane32_swap_b32 %0, %4\n\t"
+                 "v_min_f32 %0, %0, %4\n\t"
+                 "v_mov_b32 %1, %0\n\t"
+                 "s_nop 1\n\t"
+                 "v_permlane16_swap_b32 %0, %1\n\t"
+                 "v_min_f32 %0, %0, %1\n\t"
+                 "s_nop 1\n\t"
+                 "v_min_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_min_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+                 : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]));
+    const int r = __builtin_bit_cast(int, x[0]);
+    constexpr int at[6] = {0, 4, 8, 12, 32, 36};
+#pragma unroll
+    for (int i = 0; i < 6; i++) x[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(r, at[i]));
+}
+#undef RRT_FOLD
 
 // ---- the wave's ray bundle, for the boxes-in-lanes filter (RRT_BUNDLE).  A slab value of lane l is a_l(b) = b*inv_l - o_l*inv_l
 // = (b - c)*inv_l + m_l with m_l = (c - o_l)*inv_l and c a common reference point (the first active lane's origin: m_l = 0 for a bundle
@@ -482,7 +526,9 @@ struct Bundle { float cx, cy, cz, ilx, ihx, ily, ihy, ilz, ihz, mlx, mhx, mly, m
 // The rays are anchored at their point of parameter tau: q_l = o_l + tau d_l, and (b - o_l) inv_l = (b - q_l) inv_l + tau.  tau = 0 (the origin) is
 // tight for rays that start together (a primary tile), tau = 1 for shadow rays, which end together at the light (raytracer.rs:170-174: origin + dir
 // = light + 1e-4 n): their origins are spread along the tile's view rays, their far ends are not.
-__device__ __forceinline__ Bundle make_bundle(bool active, V3 o, V3 d, const Ray32& r, float tau) {
+// one_origin (wave-uniform): every active lane's ray starts at the same point and tau is 0 (the primary rays of a tile).  Every m_l is then
+// (c - c) * inv_l + 0 = +-0, so only the six inv bounds are reduced and the m bounds are 0 (a zero of either sign decides nothing in bundle_hit).
+__device__ __forceinline__ Bundle make_bundle(bool active, bool one_origin, V3 o, V3 d, const Ray32& r, float tau) {
     Bundle B;
     const unsigned long long act = __builtin_amdgcn_ballot_w64(active);
     const int leader = act ? __builtin_ctzll(act) : 0;
@@ -494,11 +540,18 @@ __device__ __forceinline__ Bundle make_bundle(bool active, V3 o, V3 d, const Ray
     const float mx = (B.cx - ox) * r.ix() + ts, my = (B.cy - oy) * r.iy() + ts, mz = (B.cz - oz) * r.iz() + ts;
     const float pinf = __builtin_huge_valf();
     // min over the active lanes of x and of -x (max = -min(-x)); inactive lanes hold +inf
-    float x[12] = {active ? r.ix() : pinf, active ? -r.ix() : pinf, active ? r.iy() : pinf, active ? -r.iy() : pinf, active ? r.iz() : pinf, active ? -r.iz() : pinf,
-                   active ? mx : pinf,   active ? -mx : pinf,   active ? my : pinf,   active ? -my : pinf,   active ? mz : pinf,   active ? -mz : pinf};
-    wave_min12_f32(x);
-    B.ilx = x[0]; B.ihx = -x[1]; B.ily = x[2]; B.ihy = -x[3]; B.ilz = x[4]; B.ihz = -x[5];
-    B.mlx = x[6]; B.mhx = -x[7]; B.mly = x[8]; B.mhy = -x[9]; B.mlz = x[10]; B.mhz = -x[11];
+    if (one_origin) {
+        float x[6] = {active ? r.ix() : pinf, active ? -r.ix() : pinf, active ? r.iy() : pinf, active ? -r.iy() : pinf, active ? r.iz() : pinf, active ? -r.iz() : pinf};
+        wave_min6_f32(x);
+        B.ilx = x[0]; B.ihx = -x[1]; B.ily = x[2]; B.ihy = -x[3]; B.ilz = x[4]; B.ihz = -x[5];
+        B.mlx = B.mhx = B.mly = B.mhy = B.mlz = B.mhz = 0.0f;
+    } else {
+        float x[12] = {active ? r.ix() : pinf, active ? -r.ix() : pinf, active ? r.iy() : pinf, active ? -r.iy() : pinf, active ? r.iz() : pinf, active ? -r.iz() : pinf,
+                       active ? mx : pinf,   active ? -mx : pinf,   active ? my : pinf,   active ? -my : pinf,   active ? mz : pinf,   active ? -mz : pinf};
+        wave_min12_f32(x);
+        B.ilx = x[0]; B.ihx = -x[1]; B.ily = x[2]; B.ihy = -x[3]; B.ilz = x[4]; B.ihz = -x[5];
+        B.mlx = x[6]; B.mhx = -x[7]; B.mly = x[8]; B.mhy = -x[9]; B.mlz = x[10]; B.mhz = -x[11];
+    }
     // An axis whose directions have mixed signs in the wave gives no bound: its inv interval becomes [-FLT_MAX, FLT_MAX], whose products are
     // -inf/+inf (or 0 for a plane through c) -- no constraint, no NaN.  A lane with the filter off (inv = 0) switches the whole bundle test
     // off: all-zero intervals make every slab value 0 and every box a hit.
@@ -616,10 +669,11 @@ __device__ __forceinline__ void own_cluster_lane(PROF_DECL const RRT_CONSTANT De
 // Must be called from wave-uniform control flow; lanes with active == false take no part.
 // Result: slot == kNone <=> None; otherwise (t, slot) of the returned triangle.
 // any_ok: the caller only uses Some/None of the result (shadow query, raytracer.rs:181-187).
+// one_origin (wave-uniform): the caller knows that every active lane's ray starts at the same point and that any_ok is false (make_bundle).
 // kBundle selects the own-list filter: false = every lane tests each box against its own ray (64 rays x 1 box per instruction);
 // true = boxes in lanes against the wave's ray bundle (64 boxes x 1 bundle per instruction).  Same results either way.
 template <bool kBundle, bool kGroups>
-__device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stack& stk, bool active, bool any_ok, bool filter_ok, V3 o, V3 d, double max_t,
+__device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stack& stk, bool active, bool any_ok, bool filter_ok, bool one_origin, V3 o, V3 d, double max_t,
                                          double& out_t, uint32_t& out_slot) {
     constexpr bool kLeaf = !kBundle;   // leaf children are tested at their parent by the lane-filter kernel only (measured: the extra code costs the bundle kernel 12 % on the teapot)
     bool done = !active;
@@ -643,10 +697,10 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
     // of a large soup) are searched with boxes in lanes, 64 boxes per instruction, instead of one wave-uniform box at a time.
     Bundle BU{};
     bool long_lists_in_lanes = false;
-    if constexpr (kBundle) BU = make_bundle(active, o, d, r32, any_ok ? 1.0f : 0.0f);
+    if constexpr (kBundle) BU = make_bundle(active, one_origin, o, d, r32, any_ok ? 1.0f : 0.0f);
     if constexpr (!kBundle) {
         // (parked in LDS rather than held in 15 SGPRs for the whole walk: scalar registers are what the lane-filter kernel is shortest of)
-        const Bundle B0 = make_bundle(active, o, d, r32, any_ok ? 1.0f : 0.0f);
+        const Bundle B0 = make_bundle(active, one_origin, o, d, r32, any_ok ? 1.0f : 0.0f);
         long_lists_in_lanes = bundle_is_tight(B0, S.cull_limit * kTightSlack);
         if (stk.lane == 0u) {
             float* q = stk.park();
@@ -660,6 +714,7 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
 #endif
     PROF_ADD(6, 1); PROF_ADD(7, __popcll(__ballot(active)));
     PROF_T(5);                                                           // [5] traverse set-up (ray32) + whatever ran since the last stamp outside
+    bool at_root = true;                                                 // wave-uniform: no node of this walk has been visited yet
     for (;;) {
         const unsigned long long pending = __builtin_amdgcn_ballot_w64(!done);
         if (pending == 0) break;
@@ -673,9 +728,17 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
         // pending lane's node in place of a wave-wide reduction: 6 % slower than smallest-id on the 100 k soup.  The other orders were removed.
         // Deepest pending lane first; among those the lane that has come least far through its parent's sorted children (its node is the nearer one: lanes that
         // finish it may still move on to the farther ones, never back), then the smaller id.  23 bits of the id in the key: larger scenes only lose the last tie-break.
-        const uint32_t key = done ? 0xFFFFFFFFu : (((63u - sp) << 26) | (crank << 23) | (cur & 0x007FFFFFu));
-        const uint32_t kmin = wave_min_u32(key);
-        const uint32_t unode = (uint32_t)__builtin_amdgcn_readlane((int)cur, __builtin_ctzll(__builtin_amdgcn_ballot_w64(key == kmin)));
+        // The first visit of a walk needs no pick: every pending lane stands at the root (cur = 0, sp = 0 above).  One scalar branch per visit; the
+        // loop body is not peeled (a second copy of it would cost instruction cache and registers).  Bundle-filter kernel only: the branch costs the
+        // lane-filter kernel ten SGPR spills and 1.7 % on the 100 k soup.  (Measured and removed: the same shortcut whenever all pending lanes stand at
+        // one node -- 98 % of the teapot's later visits -- gains nothing; the pick is not on the critical path.  profiles/r04_walk_cost_ab.txt)
+        uint32_t unode = 0;
+        if (!(kBundle && at_root)) {
+            const uint32_t key = done ? 0xFFFFFFFFu : (((63u - sp) << 26) | (crank << 23) | (cur & 0x007FFFFFu));
+            const uint32_t kmin = wave_min_u32(key);
+            unode = (uint32_t)__builtin_amdgcn_readlane((int)cur, __builtin_ctzll(__builtin_amdgcn_ballot_w64(key == kmin)));
+        }
+        at_root = false;
         const UHead N = load_uhead(nodes + unode);
         const uint32_t fc = N.first_child, sb = N.sup_begin, sc = N.sup_count, fl = N.flags;
         PROF_ADD(0, 1); PROF_ADD(1, __popcll(__ballot(!done && cur == unode)));
@@ -1002,10 +1065,20 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
             if (!(fl & 0x100u)) {                                        // triangle_count == 0 -> None, ray.rs:112-114
                 returning = true; ret_slot = kNone; ret_t = kInf;
             }
-            // A shadow query at the root that already holds an own hit (t < max_t) returns Some whatever the children do
-            // (ray.rs:163-167 picks child or own, both Some), and only Some/None is used (raytracer.rs:183-187): stop here.
+            // A shadow query whose node holds an own hit with t < max_t is finished, at any depth: this node returns Some(t' <= own_t) whatever its
+            // children do (ray.rs:163-167 picks child or own, both Some); the walk came here in the reference's order, so every earlier sibling at every
+            // level has returned None, every ancestor's loop breaks on this Some (ray.rs:155-160) and hands a t'' <= own_t upwards, and at the root
+            // t'' < max_t wins against whatever its own list held.  Only Some/None is used (raytracer.rs:183-187): no children, no unwinding (sp = 0
+            // makes the loop below stop at once).  At the root own_t starts at max_t, so every own hit qualifies; below it own_t starts at +inf and the
+            // comparison decides -- an own hit BEYOND max_t proves nothing (a child hit with t >= max_t and no own hit at the root is None), and a NaN
+            // or non-positive max_t fails the comparison.  The bundle-filter kernel keeps the rule at the root only: below the root it costs that
+            // kernel 25 SGPR spills and the teapot frame 1.3 %, while the lane-filter kernel gains 5 % on the 100 k soup (profiles/r04_walk_cost_ab.txt).
+            // Same results either way (tests/test_gpu_shadow_exit.py).
+            else if (any_ok && own_slot != kNone && (kBundle ? sp == 0 : own_t < max_t)) {
+                returning = true; ret_slot = own_slot; ret_t = own_t; sp = 0;
+            }
             // A node none of whose children is entered (leaf, or no child box hit) returns its own result: ray.rs:163-167 with child_dist = inf.
-            else if (nchild == 0 || (any_ok && sp == 0 && own_slot != kNone)) {
+            else if (nchild == 0) {
                 returning = true; ret_slot = own_slot; ret_t = own_t;
             } else {
                 stk.own_slot(sp) = own_slot; stk.meta(sp) = order | (nchild << 24); stk.fc(sp) = fc | (leaf_hit << 24);   // first_child < 2^24 whenever leaf bits exist (clusters.cpp)
@@ -1228,7 +1301,8 @@ __device__ __forceinline__ void traverse_ray(PROF_DECL const DevScene& S, const 
         // ---- return / push / unwind: ray.rs:152-167, as in traverse()
         bool returning;
         if (!(fl & 0x100u)) { returning = true; ret_slot = kNone; ret_t = kInf; }                    // triangle_count == 0 -> None, ray.rs:112-114
-        else if (nchild == 0 || (any_ok && sp == 0 && own_slot != kNone)) { returning = true; ret_slot = own_slot; ret_t = own_t; }
+        else if (any_ok && own_slot != kNone && own_t < max_t) { returning = true; ret_slot = own_slot; ret_t = own_t; sp = 0; }   // shadow query: finished, as in traverse()
+        else if (nchild == 0) { returning = true; ret_slot = own_slot; ret_t = own_t; }
         else {
             stk.own_slot(sp) = own_slot; stk.meta(sp) = order | (nchild << 24); stk.fc(sp) = fc | (leaf_hit << 24);
             sp++;
@@ -1302,7 +1376,8 @@ __device__ __forceinline__ V3 specular_term(double sw, double intensity, V3 norm
 // RayTracer::get_ray_colour (raytracer.rs:29-112) for 64 lanes; wave-uniform call.  Returns 0x00RRGGBB.
 // kWalk: 0 = node-coherent walk, lane filter; 1 = node-coherent walk, bundle filter; 2 = ray walk (one node per lane)
 constexpr int kWalkLane = 0, kWalkBundle = 1, kWalkRay = 2;
-template <int kWalk, bool kGroups>
+// kOneOrigin: every lane's `origin` is the same point (the frame kernels: the raytracer's origin; the per-ray kernels take the caller's rays).
+template <int kWalk, bool kGroups, bool kOneOrigin>
 __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, const Stack& stk, bool active, V3 origin, V3 direction) {
     bool live = active;
     bool in_shadow = false;                 // false: the ray in flight is a segment (primary/reflection) ray; true: a shadow ray
@@ -1315,12 +1390,14 @@ __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, co
     double st_local[RRT_MAX_REFLECT][3]; double st_kr[RRT_MAX_REFLECT];
     const bool first_unfiltered = origin_ray_in_suspect_plane(S, origin, direction);   // exactness guard for the primary segment (false for all but constructed scenes)
 
+    bool one_origin = kOneOrigin;           // wave-uniform: the walk about to start is the wave's first, every live lane's ray is its primary ray from `origin`
     while (__any(live)) {
         double t; uint32_t slot;
         PROF_T(4);                                                       // [4] shading / state machine between traversals
         if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, live, in_shadow, !(first_unfiltered && depth == 0u && !in_shadow), ro, rd, rmax, t, slot);
         else
-        traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, live, in_shadow, !(first_unfiltered && depth == 0u && !in_shadow), ro, rd, rmax, t, slot);
+        traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, live, in_shadow, !(first_unfiltered && depth == 0u && !in_shadow), one_origin, ro, rd, rmax, t, slot);
+        one_origin = false;                 // later walks mix shadow and reflection rays of the lanes' own hit points
         if (live) {
             const bool found = slot != kNone;
             if (!in_shadow) {
@@ -1474,7 +1551,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
     Prof prof{}; prof.last = __builtin_amdgcn_s_memtime();
     const unsigned long long wave_rt0 = __builtin_amdgcn_s_memrealtime(); (void)wave_rt0;
 #endif
-    const uint32_t c = trace_colour<kWalk, kGroups>(PROF_ARG S, stk, traced, ld3(S.origin), dir);
+    const uint32_t c = trace_colour<kWalk, kGroups, true>(PROF_ARG S, stk, traced, ld3(S.origin), dir);
 #if defined(RRT_PROFILE) && defined(RRT_PROF_WAVETIME)
     {   // developer build: how long each wave lived (s_memrealtime: the constant 100 MHz clock; s_memtime counts shader cycles), one count per wave into
         // power-of-two buckets of microseconds, the longest in slot 16
@@ -1529,7 +1606,7 @@ __global__ __launch_bounds__(64) void ray_colour_kernel(const DevScene S, uint32
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    const uint32_t c = trace_colour<kWalk, true>(PROF_ARG S, stk, ok, o, d);
+    const uint32_t c = trace_colour<kWalk, true, false>(PROF_ARG S, stk, ok, o, d);
 #if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
     for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
 #endif
@@ -1551,7 +1628,7 @@ __global__ __launch_bounds__(64) void intersect_kernel(const DevScene S, uint32_
     Prof prof{}; prof.last = 0;
 #endif
     if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, ok, false, !origin_ray_in_suspect_plane(S, o, d), o, d, mt, t, slot);
-    else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, ok, false, !origin_ray_in_suspect_plane(S, o, d), o, d, mt, t, slot);
+    else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, ok, false, !origin_ray_in_suspect_plane(S, o, d), false, o, d, mt, t, slot);
 #if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
     for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
 #endif

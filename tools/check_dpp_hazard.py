@@ -3,11 +3,11 @@
    python tools/check_dpp_hazard.py [extra hipcc flags, e.g. -mllvm -amdgpu-sched-strategy=iterative-ilp]
 
 Compiles the three units of render.hip (RRT_TU = 1, 2, 3 with the Makefile's switches for each) to assembly and, per kernel, walks every basic block:
-  * a VALU instruction that writes VGPR v followed within 2 instructions (s_nop N counts as N + 1) by a DPP instruction that READS v  -> hazard
-    (CDNA3/4 ISA 4.5: "VALU writes VGPR -> VALU DPP reads that VGPR: 2 wait states");
+  * a VALU instruction that writes VGPR v followed within 2 instructions (s_nop N counts as N + 1) by a DPP instruction or a v_permlane*_swap
+    that READS v  -> hazard (CDNA3/4 ISA 4.5: "VALU writes VGPR -> VALU DPP reads that VGPR: 2 wait states"; the swaps of gfx950 likewise);
   * a VALU instruction that writes EXEC (v_cmpx*, v_readfirstlane is not one) followed within 5 instructions by any DPP instruction          -> hazard.
 Prints every finding with its kernel and line; exit status 1 if any.  The product's inline asm keeps its s_nop INSIDE the block whose first
-instruction is the DPP read (render.hip: RRT_DPP_STEP_U32, RRT_DPP12), so a clean run is the expected state whatever the scheduler does."""
+instruction is the DPP read (render.hip: RRT_DPP_STEP_U32, wave_min12_f32, wave_min6_f32), so a clean run is the expected state whatever the scheduler does."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -51,9 +51,10 @@ def scan(path):
             continue
         is_valu = op.startswith("v_")
         operands = [a.strip() for a in args.split(",")]
-        if is_valu and ("dpp" in op or "row_shr" in args or "row_bcast" in args or "quad_perm" in args or "row_shl" in args or "wave_" in args):
+        swap = is_valu and op.startswith("v_permlane")              # v_permlane16/32_swap read (and write) BOTH operands; same 2 wait states after a VALU write
+        if swap or (is_valu and ("dpp" in op or "row_shr" in args or "row_bcast" in args or "quad_perm" in args or "row_shl" in args or "wave_" in args)):
             srcs = set()
-            for a in operands[1:]: srcs |= regs(a.split(" ")[0])
+            for a in (operands if swap else operands[1:]): srcs |= regs(a.split(" ")[0])
             dist = 0
             for w, written, wexec, text, ln in reversed(window):
                 if dist < 2 and written & srcs:
@@ -62,7 +63,7 @@ def scan(path):
                     findings.append((kernel, lineno, f"DPP {dist} wait states after a VALU write of EXEC (line {ln}: {text})  <-  {line}"))
                 dist += w
                 if dist >= 5: break
-        written = regs(operands[0]) if is_valu and operands else set()
+        written = (regs(args) if swap else regs(operands[0])) if is_valu and operands else set()
         wexec = is_valu and op.startswith("v_cmpx")
         window.append((1, written, wexec, line, lineno))
         if op.startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc", "s_swappc")): window = []
@@ -76,7 +77,7 @@ def main(extra):
         for tu in UNITS:
             path = compile_unit(tu, extra, tmp)
             f = scan(path)
-            n_dpp = sum(1 for l in open(path) if "_dpp" in l or "row_shr" in l)
+            n_dpp = sum(1 for l in open(path) if "_dpp" in l or "row_shr" in l or "v_permlane" in l)
             print(f"RRT_TU={tu} ({UNITS[tu]}): {n_dpp} DPP instructions, {len(f)} hazards")
             for k, ln, msg in f[:20]: print(f"  {k}:{ln}: {msg}")
             bad += len(f)
