@@ -76,6 +76,10 @@ typedef struct { const uint8_t *rgb; uint32_t width, height; } rrt_texture;
  * over the own lists, and the device records.  HOST_SETUP does the same on the host's cores (csrc/octree.cpp, clusters.cpp) and uploads the result:
  * the two paths produce the same bytes in HBM (tests/test_gpu_build.py); the flag exists for that check and for A/B timing. */
 #define RRT_FLAG_HOST_SETUP 16u
+/* Chain shortcut: below a parent, a run of internal nodes with one non-empty child each and at most four own triangles
+ * in all is skipped by the rays that certainly cross the box of the run's end and miss the boxes of those triangles; the bundle-filter walk
+ * then enters the end directly.  Same results; this flag turns the shortcut off (tests, A/B timing). */
+#define RRT_FLAG_NO_CHAIN_SHORTCUT (1u << 5)   /* 32; a developer switch, not one of the five flags above that tests/test_abi.py pins as the Python mirror's set */
 
 /* Render constants that the reference hard-codes; NULL => these defaults. */
 typedef struct {
@@ -234,8 +238,13 @@ int rrt_raytracer_get_octree(const rrt_raytracer *rt, rrt_model_info *info, doub
                              uint32_t *own_off, uint32_t *own_idx);
 /* Test / developer introspection: the bytes of one scene buffer in HBM.  out == NULL asks for the size only. */
 enum { RRT_BUF_NODES = 0, RRT_BUF_GEOM, RRT_BUF_ATTR, RRT_BUF_SUPERS, RRT_BUF_CBOXES, RRT_BUF_CHILD_BOXES, RRT_BUF_TBOXES, RRT_BUF_SUSPECTS,
-       RRT_BUF_OCT_BOX, RRT_BUF_OCT_FIRST_CHILD, RRT_BUF_OCT_TRI_COUNT, RRT_BUF_OCT_OWN_OFF, RRT_BUF_OCT_OWN_IDX, RRT_BUF_SLOT_TRI, RRT_BUF_SLOT_POS };
+       RRT_BUF_OCT_BOX, RRT_BUF_OCT_FIRST_CHILD, RRT_BUF_OCT_TRI_COUNT, RRT_BUF_OCT_OWN_OFF, RRT_BUF_OCT_OWN_IDX, RRT_BUF_SLOT_TRI, RRT_BUF_SLOT_POS, RRT_BUF_CHAINS };
 int rrt_raytracer_get_buffer(const rrt_raytracer *rt, uint32_t which, void *out, size_t capacity, size_t *bytes);
+
+/* Chain records of this raytracer's scene (see RRT_FLAG_NO_CHAIN_SHORTCUT): the number of chains that have one and the number of chain nodes they
+ * cover.  Both 0 when the shortcut cannot apply (RRT_FLAG_NO_CULL, a triangle poking out of the root box, 2^24 nodes or more); the flag that turns
+ * the shortcut off does not change them.  Either pointer may be NULL. */
+int rrt_raytracer_get_chain_info(const rrt_raytracer *rt, uint32_t *n_chains, uint32_t *n_chain_nodes);
 
 int rrt_last_stats(const rrt_raytracer *rt, rrt_stats *out);
 /* Time of the set-up stages that run once per scene (the reference does all of them inside parse_obj_file_lines, utils.rs:139-213, before its one

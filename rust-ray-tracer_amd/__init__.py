@@ -31,9 +31,9 @@ class RrtError(RuntimeError):
         self.detail = detail
 
 
-FLAG_NO_CULL, FLAG_LANE_FILTER, FLAG_BUNDLE_FILTER, FLAG_RAY_WALK, FLAG_HOST_SETUP = 1, 2, 4, 8, 16   # RRT_FLAG_*, include/rrt.h
+FLAG_NO_CULL, FLAG_LANE_FILTER, FLAG_BUNDLE_FILTER, FLAG_RAY_WALK, FLAG_HOST_SETUP, FLAG_NO_CHAIN_SHORTCUT = 1, 2, 4, 8, 16, 32   # RRT_FLAG_*, include/rrt.h
 BUFFERS = ("nodes", "geom", "attr", "supers", "cboxes", "child_boxes", "tboxes", "suspects", "oct_box", "oct_first_child", "oct_tri_count", "oct_own_off",
-           "oct_own_idx", "slot_tri", "slot_pos")   # RRT_BUF_*
+           "oct_own_idx", "slot_tri", "slot_pos", "chains")   # RRT_BUF_*
 VARIANT_NAMES = ("lane", "bundle", "ray")   # rrt_stats.filter_variant
 
 # status codes, include/rrt.h
@@ -113,6 +113,7 @@ SYMBOLS = {
     "rrt_intersect_rays": (C.c_int, [_P, C.c_uint32, _dp, _dp, _dp, _u8p, _dp, _dp, _dp, _u32p]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
     "rrt_last_stats": (C.c_int, [_P, C.POINTER(CStats)]),
     "rrt_get_setup_times": (C.c_int, [_P, _P, C.POINTER(CSetupTimes)]),
     "rrt_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -312,16 +313,17 @@ class RayTracer:
 
     def __init__(self, scene_data: SceneData, lights: Iterable[Light], origin: Vector3d = DEFAULT_ORIGIN, device: int = 0,
                  surface_offset: float = 0.0001, max_reflection_depth: int = 5, viewport=(1.0, 1.0, 1.0), no_cull: bool = False,
-                 box_filter: Optional[str] = None, host_setup: bool = False):
+                 box_filter: Optional[str] = None, host_setup: bool = False, chain_shortcut: bool = True):
         """no_cull=True (RRT_FLAG_NO_CULL): walk every own list in full, in list order, as ray.rs:119-129; default uses the cluster boxes.
         box_filter: None = rule of thumb on the first frame of a size, measured on the second, "lane" / "bundle" / "ray" = forced (RRT_FLAG_LANE_FILTER / RRT_FLAG_BUNDLE_FILTER /
         RRT_FLAG_RAY_WALK); same pixels.  host_setup=True (RRT_FLAG_HOST_SETUP): octree, index and records built on the host and uploaded (default: built on
-        the GPU, csrc/scene_build.hip); same bytes in HBM."""
+        the GPU, csrc/scene_build.hip); same bytes in HBM.  chain_shortcut=False (RRT_FLAG_NO_CHAIN_SHORTCUT): the bundle-filter walk enters every node of a
+        one-child chain; same results."""
         self.scene_data, self.lights, self.origin, self.device = scene_data, list(lights), origin, device
         cl = (CLight * max(1, len(self.lights)))()
         for i, l in enumerate(self.lights):
             cl[i] = CLight(l.kind, 0, float(l.intensity), l.v._c())
-        flags = (FLAG_NO_CULL if no_cull else 0) | (FLAG_HOST_SETUP if host_setup else 0) | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter]
+        flags = (FLAG_NO_CULL if no_cull else 0) | (FLAG_HOST_SETUP if host_setup else 0) | (0 if chain_shortcut else FLAG_NO_CHAIN_SHORTCUT) | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter]
         opt = COptions(surface_offset, max_reflection_depth, flags, *map(float, viewport))
         out = _P()
         _check(lib().rrt_raytracer_create(scene_data._h, cl, len(self.lights), origin._c(), C.byref(opt), device, C.byref(out)), "rrt_raytracer_create")
@@ -356,6 +358,13 @@ class RayTracer:
         info = CModelInfo()
         _check(lib().rrt_raytracer_get_octree(self._h, C.byref(info), None, None, None, None, None), "rrt_raytracer_get_octree")
         return {k: getattr(info, k) for k, _ in CModelInfo._fields_}
+
+    @property
+    def chain_info(self) -> dict:
+        """rrt_raytracer_get_chain_info: chains that have a shortcut record, and the chain nodes those records cover."""
+        a = C.c_uint32(0); b = C.c_uint32(0)
+        _check(lib().rrt_raytracer_get_chain_info(self._h, C.byref(a), C.byref(b)), "rrt_raytracer_get_chain_info")
+        return {"n_chains": a.value, "n_chain_nodes": b.value}
 
     def octree(self) -> dict:
         """The octree this raytracer's GPU set-up built (rrt_raytracer_get_octree): same dict as SceneData.octree(), plus "info"."""

@@ -41,6 +41,7 @@ struct rrt_raytracer {
     void* host_fb = nullptr;         // device framebuffer kept between rrt_render calls (host-buffer entry point)
     size_t host_fb_bytes = 0;
     uint32_t n_suspects = 0;         // triangles whose plane contains the origin (exactness guard, clusters.cpp)
+    const rrt::DevChain* chains = nullptr; uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records as the set-up wrote them (scene.chains is this or nullptr: create_raytracer)
     double index_ms = 0, upload_ms = 0, hip_init_ms = 0;  // set-up stages of rrt_raytracer_create
     double octree_ms = 0, create_ms = 0;                  // GPU set-up: octree build on the device; wall time of the whole rrt_raytracer_create
     bool gpu_setup = false;                               // scene built on the device (default) or on the host (RRT_FLAG_HOST_SETUP)
@@ -451,7 +452,7 @@ int rrt_decode_image_file(const char* path, uint8_t** rgb, uint32_t* width, uint
 namespace {
 
 // ids of rrt_raytracer_get_buffer (rrt.h: RRT_BUF_*)
-enum { kBufNodes = 0, kBufGeom, kBufAttr, kBufSupers, kBufCboxes, kBufChildBoxes, kBufTboxes, kBufSuspects, kBufOctBox, kBufOctFirstChild, kBufOctTriCount, kBufOctOwnOff, kBufOctOwnIdx, kBufSlotTri, kBufSlotPos, kBufCount };
+enum { kBufNodes = 0, kBufGeom, kBufAttr, kBufSupers, kBufCboxes, kBufChildBoxes, kBufTboxes, kBufSuspects, kBufOctBox, kBufOctFirstChild, kBufOctTriCount, kBufOctOwnOff, kBufOctOwnIdx, kBufSlotTri, kBufSlotPos, kBufChains, kBufCount };
 
 // what a set-up needs of a scene besides its triangles: materials and RGB8 textures (borrowed views)
 struct SceneTables { const rrt_material* mats; uint32_t n_mats; std::vector<rrt_texture> tex; };
@@ -549,7 +550,7 @@ void setup_on_host(rrt_raytracer* rt, const Model& M, rrt_vec3 origin, const rrt
         size_t need = (size_t)1 << 20;
         for (auto& t : M.textures) need += t.rgb.size() + 256;
         need += n_nodes * sizeof(DevNode) + n_slots_c * (sizeof(DevTriGeom) + sizeof(DevTriAttr)) + 4096;
-        need += (CS.supers.size() + CS.cboxes.size() + CS.child_boxes.size() + CS.tboxes.size()) * 32 + 4096;
+        need += (CS.supers.size() + CS.cboxes.size() + CS.child_boxes.size() + CS.tboxes.size()) * 32 + 4096 + CS.chains.size() * sizeof(DevChain) + 256;
         need += M.materials.size() * sizeof(DevMaterial) + M.textures.size() * sizeof(DevTexture) + (RRT_MAX_SUSPECTS + 1) * sizeof(DevSuspect);
         HIP_TRY(hipMalloc(&rt->arena, need));
         rt->allocs.push_back(rt->arena);
@@ -565,6 +566,8 @@ void setup_on_host(rrt_raytracer* rt, const Model& M, rrt_vec3 origin, const rrt
     S.cboxes = upload(rt, CS.cboxes.data(), CS.cboxes.size());               keep(kBufCboxes, S.cboxes, CS.cboxes.size() * sizeof(DevClusterBox));
     S.child_boxes = upload(rt, CS.child_boxes.data(), CS.child_boxes.size()); keep(kBufChildBoxes, S.child_boxes, CS.child_boxes.size() * sizeof(DevClusterBox));
     S.tboxes = upload(rt, CS.tboxes.data(), CS.tboxes.size());               keep(kBufTboxes, S.tboxes, CS.tboxes.size() * sizeof(DevClusterBox));
+    rt->chains = upload(rt, CS.chains.data(), CS.chains.size());             keep(kBufChains, rt->chains, CS.chains.size() * sizeof(DevChain));
+    rt->n_chains = (uint32_t)CS.chains.size(); rt->n_chain_nodes = CS.n_chain_nodes;
     S.has_groups = CS.has_groups ? 1u : 0u;
     S.bounds_plain = 1u;
     for (size_t i = 0; i < n_nodes; i++) { const DevNode& d = nodes[i];
@@ -662,6 +665,8 @@ void setup_on_gpu(rrt_raytracer* rt, const TriSource& src, uint32_t n_tris, cons
     keep(kBufOctBox, G.oct_box, (size_t)G.n_nodes * 48); keep(kBufOctFirstChild, G.oct_first_child, (size_t)G.n_nodes * 4); keep(kBufOctTriCount, G.oct_tri_count, (size_t)G.n_nodes * 4);
     keep(kBufOctOwnOff, G.oct_own_off, ((size_t)G.n_nodes + 1) * 4); keep(kBufOctOwnIdx, G.oct_own_idx, (size_t)G.n_in_tree * 4);
     keep(kBufSlotTri, G.slot_tri, (size_t)G.n_slots_total * 4); keep(kBufSlotPos, G.slot_pos, (size_t)G.n_slots_total * 4);
+    keep(kBufChains, G.chains, (size_t)G.n_chains * sizeof(DevChain));
+    rt->chains = G.chains; rt->n_chains = G.n_chains; rt->n_chain_nodes = G.n_chain_nodes;
     rt->scene_bytes += (size_t)G.n_nodes * sizeof(DevNode) + (size_t)G.n_slots_total * (sizeof(DevTriGeom) + sizeof(DevTriAttr))
                      + ((size_t)G.n_sup_records + G.n_clusters + 8 + (G.n_nodes > 1 ? G.n_nodes - 1 : 0) + 8 + G.n_list_slots + 8) * 32;
     S.has_groups = G.has_groups; S.bounds_plain = G.bounds_plain;
@@ -721,6 +726,9 @@ int create_raytracer(const rrt_light* lights, uint32_t n_lights, rrt_vec3 origin
     S.cull_enabled = (o.flags & RRT_FLAG_NO_CULL) ? 0u : 1u;
     S.cull_half_over_limit = S.cull_limit > 0.0f ? 0.5f / S.cull_limit : 0.0f;
     S.inner_shrink = (S.cull_enabled && rt->all_inside_root) ? (float)(2.0 * rt->filter_pad) : 0.0f;   // 2 x the pad the boxes were built with; render.hip, single-candidate child test
+    // The chain shortcut rests on the same "subtree box inside the octant box" argument as inner_shrink; without it the records stay unused.
+    if (!(S.inner_shrink > 0.0f)) { rt->n_chains = 0; rt->n_chain_nodes = 0; }
+    S.chains = (rt->n_chains && !(o.flags & RRT_FLAG_NO_CHAIN_SHORTCUT)) ? rt->chains : nullptr;
     S.n_suspects = rt->n_suspects;
     S.n_lights = n_lights; S.max_reflection_depth = o.max_reflection_depth; S.stack_levels = max_depth > 1 ? max_depth - 1 : 1;   // (stack_levels: only internal nodes push a frame; the deepest level holds leaves)
     S.origin[0] = origin.x; S.origin[1] = origin.y; S.origin[2] = origin.z;
@@ -799,6 +807,15 @@ int rrt_raytracer_get_octree(const rrt_raytracer* rt, rrt_model_info* info, doub
             info->root_own_count = off[1] - off[0];
             for (size_t i = 0; i + 1 < off.size(); i++) info->max_own_count = std::max(info->max_own_count, off[i + 1] - off[i]);
         }
+        return RRT_OK;
+    });
+}
+
+int rrt_raytracer_get_chain_info(const rrt_raytracer* rt, uint32_t* n_chains, uint32_t* n_chain_nodes) {
+    return guarded([&]() -> int {
+        if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+        if (n_chains) *n_chains = rt->n_chains;
+        if (n_chain_nodes) *n_chain_nodes = rt->n_chain_nodes;
         return RRT_OK;
     });
 }

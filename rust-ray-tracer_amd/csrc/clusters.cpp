@@ -262,6 +262,41 @@ void build_clusters(const Model& m, bool enable_cull, ClusterSet& out) {
     for (int i = 0; i < 8; i++) out.child_boxes.push_back(DevClusterBox{});
     // ---- device form of every box record (the spare all-zero records become the point box at the origin: they are only ever read past a count)
     boxes_to_centre_half(out.supers); boxes_to_centre_half(out.cboxes); boxes_to_centre_half(out.tboxes); boxes_to_centre_half(out.child_boxes);
+
+    // ---- chain records (device_scene.hpp: DevChain).  Heads in node-id order: a head is a chain node whose parent is the root or no chain node.
+    // (No records without the index -- the boxes would be the no-cull boxes -- nor for trees whose frame words have no room for the redirect mask.)
+    if (!enable_cull || !inline_leaves) return;
+    auto is_chain_node = [&](uint32_t c) {
+        if (!T.first_child[c]) return false;
+        int n = 0;
+        for (uint32_t k = 0; k < 8; k++) n += T.tri_count[T.first_child[c] + k] ? 1 : 0;
+        return n == 1;
+    };
+    auto next_in_chain = [&](uint32_t c) { for (uint32_t k = 0; k < 8; k++) if (T.tri_count[T.first_child[c] + k]) return T.first_child[c] + k; return 0u; };
+    std::vector<std::pair<uint32_t, DevChain>> found;                   // (head, record); a node's children need not be numbered in the order of the parents
+    for (uint32_t P = 0; P < n_nodes; P++) {
+        if (!T.first_child[P] || (P != 0 && is_chain_node(P))) continue;
+        for (uint32_t c = T.first_child[P]; c < T.first_child[P] + 8; c++) {
+            if (!is_chain_node(c)) continue;
+            uint32_t tris = 0, len = 0, D = c;
+            for (; is_chain_node(D); D = next_in_chain(D)) { tris += T.own_off[D + 1] - T.own_off[D]; len++; }
+            if (tris > kChainMaxTris) continue;
+            DevChain R{};
+            const DevClusterBox& DB = out.child_boxes[D - 1];
+            for (int k = 0; k < 3; k++) { R.c[k] = DB.c[k]; R.h[k] = DB.h[k]; }
+            R.end_node = D; R.n_tris = tris;
+            uint32_t j = 0;
+            for (uint32_t q = c; q != D; q = next_in_chain(q)) {
+                const uint32_t n_own = T.own_off[q + 1] - T.own_off[q];                       // (<= kChainMaxTris: one super-cluster, one cluster, slots in list order)
+                for (uint32_t i = 0; i < n_own; i++) R.tri[j++] = out.tboxes[out.supers[out.node_sup_begin[q]].tri_begin + i];
+            }
+            for (; j < kChainMaxTris; j++) { for (int k = 0; k < 3; k++) { R.tri[j].c[k] = 0.0f; R.tri[j].h[k] = -FLT_MAX; } }
+            found.emplace_back(c, R);
+            out.n_chain_nodes += len;
+        }
+    }
+    std::sort(found.begin(), found.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    for (auto& [c, R] : found) { out.chains.push_back(R); out.child_boxes[c - 1]._pad[1] = (uint32_t)out.chains.size(); }
 }
 
 namespace {

@@ -52,6 +52,17 @@ struct DevSuper { union { float lo[3]; float c[3]; }; union { float hi[3]; float
 struct DevClusterBox { union { float lo[3]; float c[3]; }; union { float hi[3]; float h[3]; }; uint32_t _pad[2]; };             // 32 B
 static_assert(sizeof(DevClusterBox) == 32 && sizeof(DevSuper) == 32, "cluster records must be 32 bytes");
 
+// Chain shortcut (render.hip "chain shortcut").  A CHAIN NODE is an internal node with exactly one non-empty child; a chain is a
+// maximal run of them below some parent: head d1, d2, ..., down to the first node D on that path that is not a chain node (the chain's END).  The
+// reference's tree has such runs wherever the scene is small against the root box (octree.rs:77-80: the first triangle that reaches a node stays in it).
+// A chain whose nodes' own lists hold at most kChainMaxTris triangles in all gets one record: D's padded subtree box (a copy of
+// D's child_boxes record), D's node id, the number of those own triangles and their padded boxes (copies of their tboxes records) in chain order; unused
+// triangle records are the empty box.  The child_boxes record of the head carries 1 + the record's index in _pad[1] (0: no chain record).
+constexpr uint32_t kChainMaxTris = 4;   // K.  Every chain node owns at least one triangle, so K also bounds the length of a chain that gets a record.  Measured on the
+                                        // teapot frame: K = 2 / 4 / 8 give the same time (profiles/r05_chain_shortcut.txt)
+struct DevChain { float c[3], h[3]; uint32_t end_node, n_tris; DevClusterBox tri[kChainMaxTris]; };                             // 160 B
+static_assert(sizeof(DevChain) == 32 + 32 * kChainMaxTris, "DevChain must be a box record plus kChainMaxTris box records");
+
 struct DevTriAttr {                                                // 128 B: one cache line per shaded hit
     double uv[6];                // t1.x,t1.y, t2.x,t2.y, t3.x,t3.y (raytracer.rs:45-50 read x,y only)
     double nrm[9];               // n1, n2, n3
@@ -96,6 +107,8 @@ struct DevScene {                // passed to kernels by value (kernarg segment 
     const DevSuspect* suspects;
     float inner_shrink;          // 2 x the filter's pad when every triangle of the tree lies inside the root box (a child's subtree box then lies inside its octant box), else 0: render.hip, RRT_CERTAIN_HIT
     uint32_t bounds_plain;       // every node plane (lo, mid, hi) is 0 or has magnitude in [2^-200, 2^200]: the walk may share the reciprocal of a ray's direction across its slab quotients (render.hip, RayRcp)
+    const DevChain* chains;      // chain records (above), or nullptr when the shortcut is off: no record, inner_shrink == 0, RRT_FLAG_NO_CHAIN_SHORTCUT.  (Behind the
+                                 // fields the other kernels read: where a pointer sits among the first sixteen words of the kernarg segment shapes their scalar loads.)
     DevLight lights[RRT_MAX_LIGHTS];
 #ifdef RRT_PROFILE
     unsigned long long* prof;    // developer build only (make prof): 16 wave-level work counters + 8 s_memtime region timers, see tools/profile_counters.py
@@ -137,6 +150,8 @@ struct ClusterSet {
     std::vector<uint32_t> slot_tri, slot_pos;          // per device slot: triangle index in push order (kPadSlot for padding), position in its node's own list
     std::vector<uint32_t> node_sup_begin, node_sup_count;
     std::vector<uint32_t> node_leaf_slot;              // slot of the triangle of a single-triangle leaf that is tested at its parent (kPadSlot otherwise)
+    std::vector<DevChain> chains;                      // one per qualifying chain, in the order of their heads' node ids (child_boxes carries the references)
+    uint32_t n_chain_nodes = 0;                        // chain nodes covered by those records
     bool has_groups = false;                           // some list got group records
     bool inline_leaves = false;                        // single-triangle leaves are tested at their parents (node_leaf_slot, DevNode::leaf_base)
     uint32_t n_list_slots = 0;                         // slots [0, n_list_slots) belong to own lists (cboxes/tboxes cover these); leaf slots follow

@@ -665,6 +665,31 @@ __device__ __forceinline__ void own_cluster_lane(PROF_DECL const RRT_CONSTANT De
     }
 }
 
+// CHAIN SHORTCUT (device_scene.hpp: DevChain), bundle-filter kernel.  Node c, which this lane is about to enter, heads a chain
+// c = d1 -> d2 -> ... -> D of internal nodes with one non-empty child each.  A lane whose ray (a) passes the fp32 slab test of D's subtree box SHRUNK by
+// inner_shrink and (b) misses the padded box of every own triangle of the chain gets from every chain node exactly what D returns: by (a) the
+// reference's f64 intersect_aabb returns Some for the octant boxes of d2, ..., D -- they all contain D's subtree box, shrunk by twice the pad; the
+// argument of the single-candidate test in traverse -- so each chain node, entered with max_t = +inf, enters its one non-empty child (the empty ones
+// return None at once, ray.rs:112); by (b) its own list gives None (the index's guarantee: a pair the reference accepts lies inside the padded box), so
+// ray.rs:163-167 hands the child's result up unchanged, Some or None.  Such a lane enters D directly and never visits the chain nodes; the frame it
+// returns to is the parent's either way.  Lanes with the filter off (sigma == 0: no-cull mode, non-finite or out-of-scale rays, the origin-suspect
+// guard) and lanes that fail (a) or (b) enter c as before; `mine` in traverse compares node ids only, so both kinds share D's visit.
+// Per-lane loads: the lanes of a wave that get here together nearly always ask for the same record.
+__device__ __forceinline__ uint32_t chain_target(const DevScene& S, const DevClusterBox* child_boxes, uint32_t c, const Ray32& r32) {
+    const DevChain* chains = S.chains;
+    if (chains == nullptr || !(r32.sigma > 0.0f)) return c;
+    const DevChain* R = chains + (child_boxes[c - 1u]._pad[1] - 1u);       // (the frame bit that led here says the reference is there)
+    UBox DB; DB.cx = R->c[0]; DB.cy = R->c[1]; DB.cz = R->c[2];
+    DB.hx = R->h[0] - S.inner_shrink; DB.hy = R->h[1] - S.inner_shrink; DB.hz = R->h[2] - S.inner_shrink; DB.a = 0; DB.b = 0;
+    bool ok = DB.hx >= 0.0f && DB.hy >= 0.0f && DB.hz >= 0.0f && slab32(DB, r32);
+    const uint32_t n_tris = R->n_tris;
+    for (uint32_t j = 0; j < n_tris; j++) {
+        UBox TB; TB.cx = R->tri[j].c[0]; TB.cy = R->tri[j].c[1]; TB.cz = R->tri[j].c[2]; TB.hx = R->tri[j].h[0]; TB.hy = R->tri[j].h[1]; TB.hz = R->tri[j].h[2]; TB.a = 0; TB.b = 0;
+        ok = ok && !slab32(TB, r32);
+    }
+    return ok ? R->end_node : c;
+}
+
 // Ray::intersect_with_octant_with_max_t(octree, 0, max_t), ray.rs:104-168, for all 64 lanes at once.
 // Must be called from wave-uniform control flow; lanes with active == false take no part.
 // Result: slot == kNone <=> None; otherwise (t, slot) of the returned triangle.
@@ -742,6 +767,7 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
         const UHead N = load_uhead(nodes + unode);
         const uint32_t fc = N.first_child, sb = N.sup_begin, sc = N.sup_count, fl = N.flags;
         PROF_ADD(0, 1); PROF_ADD(1, __popcll(__ballot(!done && cur == unode)));
+        PROF_ADD(15, (fc != 0u && __builtin_popcount(fl & 0xFFu) == 1) ? 1 : 0);   // [15] visits of chain nodes (internal, one non-empty child)
         PROF_T(0);                                                       // [0] pick node + node record load
         const bool mine = !done && cur == unode;
         uint32_t order = 0, nchild = 0;
@@ -756,6 +782,7 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
                     // (1) conservative fp32 filter against the TIGHT bounds of each non-empty child's subtree (clusters.cpp): a child the ray cannot
                     // reach returns None like an empty one, so it is dropped here; `reach` = children some lane may still hit (wave-uniform).
                     uint32_t lane_reach = 0, reach = 0;
+                    uint32_t cmask = 0;                                                                    // bit k: child k heads a chain that has a record (chain_target; wave-uniform)
                     {
                         const RRT_CONSTANT u32x16* cbx = (const RRT_CONSTANT u32x16*)(child_boxes + (fc - 1u));
 #define RRT_CB(k, v, off)                                                                                                          \
@@ -774,10 +801,20 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
                         // zeros to shift in for absent children cost more than the shift saves.  Measured, teapot / 100 k soup / 1 M soup: the packed
                         // arithmetic gains the lane-filter kernel 2 % on the soups and costs the bundle-filter kernel 4 % on the teapot -- register
                         // pairs in a kernel that is short of VGPRs -- so each kernel gets the form that suits it.)
-                        if (fl & 0x0Fu) { const u32x16 b01 = cbx[0], b23 = cbx[1]; RRT_CB(0, b01, 0) RRT_CB(1, b01, 8) RRT_CB(2, b23, 0) RRT_CB(3, b23, 8) }
-                        if (fl & 0xF0u) { const u32x16 b45 = cbx[2], b67 = cbx[3]; RRT_CB(4, b45, 0) RRT_CB(5, b45, 8) RRT_CB(6, b67, 0) RRT_CB(7, b67, 8) }
+                        // (chain references, kBundle: a record of an absent child holds none, so the words are looked at whatever `fl` says; nearly every burst has none)
+#define RRT_CM(k0, a, b)                                                                                                           \
+                        if constexpr (kBundle) {                                                                                   \
+                            if ((a[7] | a[15] | b[7] | b[15]) != 0u)                                                               \
+                                cmask |= ((a[7] ? 1u : 0u) | (a[15] ? 2u : 0u) | (b[7] ? 4u : 0u) | (b[15] ? 8u : 0u)) << k0;      \
+                        }
+                        if (fl & 0x0Fu) { const u32x16 b01 = cbx[0], b23 = cbx[1]; RRT_CB(0, b01, 0) RRT_CB(1, b01, 8) RRT_CB(2, b23, 0) RRT_CB(3, b23, 8) RRT_CM(0, b01, b23) }
+                        if (fl & 0xF0u) { const u32x16 b45 = cbx[2], b67 = cbx[3]; RRT_CB(4, b45, 0) RRT_CB(5, b45, 8) RRT_CB(6, b67, 0) RRT_CB(7, b67, 8) RRT_CM(4, b45, b67) }
+#undef RRT_CM
 #undef RRT_CB
                     }
+                    // (the frame's first_child word is written here, where the chain bits are at hand, not with the rest of the frame at the push: a frame
+                    //  that is never pushed leaves a stale word above the stack top, which the next push overwrites)
+                    if constexpr (kBundle) stk.fc(sp) = fc | (cmask << 24);
                     // (2) The eight children are cut from this node's box by its three mid planes (octree.rs:136-225), so their 48 slab bounds are
                     // only nine distinct planes {lo, mid, hi} x {x, y, z}, all in the node record: the reference's quotient (bound - o)/d
                     // (ray.rs:22-27) is formed ONCE per plane that some reachable child uses (6..9 IEEE divides per node instead of 6 per
@@ -1081,7 +1118,7 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
             else if (nchild == 0) {
                 returning = true; ret_slot = own_slot; ret_t = own_t;
             } else {
-                stk.own_slot(sp) = own_slot; stk.meta(sp) = order | (nchild << 24); stk.fc(sp) = fc | (leaf_hit << 24);   // first_child < 2^24 whenever leaf bits exist (clusters.cpp)
+                stk.own_slot(sp) = own_slot; stk.meta(sp) = order | (nchild << 24); if constexpr (!kBundle) stk.fc(sp) = fc | (leaf_hit << 24);   // first_child < 2^24 whenever leaf bits exist (clusters.cpp)
                 sp++;
                 returning = false;
             }
@@ -1093,8 +1130,10 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
                     if (cursor < n) {                                    // next sorted child, entered with max_t = +inf (ray.rs:153)
                         stk.meta(sp - 1) = m + (1u << 28);
                         const uint32_t fcw = stk.fc(sp - 1), k = (m >> (3u * cursor)) & 7u;
-                        const uint32_t fcm = kLeaf ? S.fc_mask : 0xFFFFFFFFu;
+                        const uint32_t fcm = kLeaf ? S.fc_mask : 0x00FFFFFFu;   // (the bundle-filter kernel only runs trees below 2^24 nodes: launch_render)
                         if (!(((fcw & ~fcm) >> (24u + k)) & 1u)) { cur = (fcw & fcm) + k; crank = cursor; break; }
+                        // this child heads a chain: the lane enters the chain's end in its place if its ray allows it (chain_target)
+                        if constexpr (kBundle) { cur = chain_target(S, (const DevClusterBox*)child_boxes, (fcw & fcm) + k, r32); crank = cursor; break; }
                         // a leaf child whose triangle this ray hits (tested at the parent, above): it returns Some(t, triangle) without a visit;
                         // a leaf's own record holds its dense slot in leaf_base (it has no children to describe)
                         ret_slot = ((const DevNode*)nodes)[(fcw & fcm) + k].leaf_base;
@@ -1692,7 +1731,10 @@ static int dev_hsaco_launch(const DevScene& s, const FrameParams& f, uint32_t* d
 }
 #endif
 
+// The bundle-filter walk keeps the chain bits of a frame above a 24-bit first_child: a tree of 2^24 nodes or more (fc_mask says so) runs the lane filter
+// in its place.  Same results; such a tree has tens of millions of triangles, far from the coherent frames the bundle filter is for.
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk) {
+    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;
     const uint32_t n_tiles = f.tile_end > f.tile_begin ? f.tile_end - f.tile_begin : 0u;
     const uint32_t local_tiles = (n_tiles + f.world - 1) / f.world;
     if (local_tiles == 0) return 0;
@@ -1744,6 +1786,7 @@ int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_
 
 #if RRT_TU_RAYS
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk) {
+    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;    // as launch_render
     if (n == 0) return 0;
     const dim3 grid((n + 63) / 64), block(64);
     const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
@@ -1755,6 +1798,7 @@ int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, c
 
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
                      uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream, int walk) {
+    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;    // as launch_render
     if (n == 0) return 0;
     const dim3 grid((n + 63) / 64), block(64);
     const uint32_t lds = stack_bytes_per_wave(s.stack_levels);

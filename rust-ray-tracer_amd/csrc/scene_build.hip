@@ -255,7 +255,8 @@ struct Idx {
     const Triangle* tris;
     uint32_t *a_slots, *a_sup, *a_leaf;                            // per node: slots (multiple of 8), super-cluster records, "is an inline leaf"
     uint32_t *slot_base, *sup_base, *leaf_rank;                    // their exclusive prefix sums (n_nodes + 1)
-    uint32_t* flags;                                               // [0] has_groups, [1] max own count, [2] bounds_plain violated, [3] suspects found
+    uint32_t *a_chain, *chain_rank; DevChain* chains;              // per node: "is the head of a chain that gets a record" (device_scene.hpp: DevChain), its prefix sum, the records
+    uint32_t* flags;                                               // [0] has_groups, [1] max own count, [2] bounds_plain violated, [3] suspects found, [4] chain nodes covered by records
     uint32_t *perm_a, *perm_b; double *cen_a, *cen_b;              // per own-list entry: position in the node's list, centroid; double-buffered
     uint32_t *slot_tri, *slot_pos, *cluster_node;
     float* cl_lohi;                                                // [clusters][6] padded f32 (lo, hi) before the centre/half form
@@ -505,6 +506,57 @@ __global__ void __launch_bounds__(kBlock) k_idx_child_boxes(Idx X) {
     }
     to_centre_half(B.lo, B.hi);
     X.child_boxes[c - 1u] = B;
+}
+
+// chain records (clusters.cpp, end of build_clusters; device_scene.hpp: DevChain).  One thread per PARENT: it decides for its eight children.
+__device__ __forceinline__ bool is_chain_node(const Idx& X, uint32_t c) {
+    const uint32_t fc = X.ffc[c];
+    if (!fc) return false;
+    int n = 0;
+    for (uint32_t k = 0; k < 8u; k++) n += X.ftc[fc + k] ? 1 : 0;
+    return n == 1;
+}
+__device__ __forceinline__ uint32_t next_in_chain(const Idx& X, uint32_t c) {
+    const uint32_t fc = X.ffc[c];
+    for (uint32_t k = 0; k < 8u; k++) if (X.ftc[fc + k]) return fc + k;
+    return 0u;
+}
+__global__ void __launch_bounds__(kBlock) k_chain_heads(Idx X) {
+    const uint32_t P = blockIdx.x * kBlock + threadIdx.x;
+    if (P > X.n_nodes) return;
+    if (P == X.n_nodes || P == 0u) X.a_chain[P] = 0u;
+    if (P == X.n_nodes) return;
+    const uint32_t fc = X.ffc[P];
+    if (!fc) return;
+    const bool heads_here = X.enable_cull && X.inline_leaves && (P == 0u || !is_chain_node(X, P));
+    for (uint32_t c = fc; c < fc + 8u; c++) {
+        uint32_t head = 0u;
+        if (heads_here && is_chain_node(X, c)) {
+            uint32_t tris = 0, len = 0;
+            for (uint32_t D = c; is_chain_node(X, D); D = next_in_chain(X, D)) { tris += X.own_off[D + 1] - X.own_off[D]; len++; }
+            if (tris <= kChainMaxTris) { head = 1u; atomicAdd(&X.flags[4], len); }
+        }
+        X.a_chain[c] = head;
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_chain_records(Idx X) {   // after k_idx_slots (tboxes) and k_idx_child_boxes
+    const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= X.n_nodes || !X.a_chain[c]) return;
+    uint32_t D = c;
+    while (is_chain_node(X, D)) D = next_in_chain(X, D);
+    DevChain R{};
+    const DevClusterBox DB = X.child_boxes[D - 1u];
+    for (int k = 0; k < 3; k++) { R.c[k] = DB.c[k]; R.h[k] = DB.h[k]; }
+    R.end_node = D;
+    uint32_t j = 0;
+    for (uint32_t q = c; q != D; q = next_in_chain(X, q)) {
+        const uint32_t n_own = X.own_off[q + 1] - X.own_off[q];       // (<= kChainMaxTris: one cluster, slots in list order)
+        for (uint32_t i = 0; i < n_own; i++) R.tri[j++] = X.tboxes[X.slot_base[q] + i];
+    }
+    R.n_tris = j;
+    for (; j < kChainMaxTris; j++) for (int k = 0; k < 3; k++) { R.tri[j].c[k] = 0.0f; R.tri[j].h[k] = -FLT_MAX; }
+    X.chains[X.chain_rank[c]] = R;
+    X.child_boxes[c - 1u]._pad[1] = X.chain_rank[c] + 1u;
 }
 
 __global__ void __launch_bounds__(kBlock) k_idx_nodes(Idx X, const double* fbox) {   // DevNode records (api.cpp's fill loop)
@@ -803,7 +855,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     const size_t oct_bytes = (size_t)n_nodes * (48 + 4 + 4) + ((size_t)n_nodes + 1) * 4 + (size_t)n * 4 + 4096;
     DevFree t2;
     DevArena A2;
-    A2.cap = oct_bytes + (size_t)n_nodes * (4 /*tmp2final*/ + 4 /*newblock*/ + 6 * 4 /*a_*, bases*/ + 48 /*nb*/) + (size_t)(n_nodes + 1) * 4 * 4 + (size_t)n * (2 * 4 + 2 * 24) + (64 << 10);
+    A2.cap = oct_bytes + (size_t)n_nodes * (4 /*tmp2final*/ + 4 /*newblock*/ + 6 * 4 /*a_*, bases*/ + 48 /*nb*/) + (size_t)(n_nodes + 1) * 4 * 6 + (size_t)n * (2 * 4 + 2 * 24) + (64 << 10);
     HB_TRY(hipMalloc(&t2.p, A2.cap)); A2.base = static_cast<char*>(t2.p);
     lap("hipMalloc temporaries 2");
     Remap R{};
@@ -852,12 +904,14 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     X.ffc = R.ffc; X.ftc = R.ftc; X.own_off = own_off; X.own_idx = val_out; X.skey = key_out; X.tbox = S.tbox; X.tris = d_tris;
     X.a_slots = A2.take<uint32_t>(n_nodes + 1); X.a_sup = A2.take<uint32_t>(n_nodes + 1); X.a_leaf = A2.take<uint32_t>(n_nodes + 1);
     X.slot_base = A2.take<uint32_t>(n_nodes + 1); X.sup_base = A2.take<uint32_t>(n_nodes + 1); X.leaf_rank = A2.take<uint32_t>(n_nodes + 1);
+    X.a_chain = A2.take<uint32_t>(n_nodes + 1); X.chain_rank = A2.take<uint32_t>(n_nodes + 1);
     X.flags = A2.take<uint32_t>(8);
     X.nb = A2.take<unsigned long long>(6 * (size_t)n_nodes);
     X.perm_a = A2.take<uint32_t>(n_in); X.perm_b = A2.take<uint32_t>(n_in); X.cen_a = A2.take<double>(3 * (size_t)n_in); X.cen_b = A2.take<double>(3 * (size_t)n_in);
     HB_TRY(hipMemsetAsync(X.flags, 0, 8 * sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_idx_sizes, dim3(grid_for((size_t)n_nodes + 1)), dim3(kBlock), 0, st, X);
-    for (auto pr : {std::pair<uint32_t*, uint32_t*>{X.a_slots, X.slot_base}, {X.a_sup, X.sup_base}, {X.a_leaf, X.leaf_rank}}) {
+    hipLaunchKernelGGL(k_chain_heads, dim3(grid_for((size_t)n_nodes + 1)), dim3(kBlock), 0, st, X);
+    for (auto pr : {std::pair<uint32_t*, uint32_t*>{X.a_slots, X.slot_base}, {X.a_sup, X.sup_base}, {X.a_leaf, X.leaf_rank}, {X.a_chain, X.chain_rank}}) {
         size_t b = prim_bytes;
         HB_TRY(rocprim::exclusive_scan(prim_tmp, b, pr.first, pr.second, 0u, (size_t)n_nodes + 1, rocprim::plus<uint32_t>(), st));
     }
@@ -865,11 +919,15 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     HB_TRY(hipMemcpyAsync(h_ctr + 1, X.sup_base + n_nodes, 4, hipMemcpyDeviceToHost, st));
     HB_TRY(hipMemcpyAsync(h_ctr + 2, X.leaf_rank + n_nodes, 4, hipMemcpyDeviceToHost, st));
     HB_TRY(hipMemcpyAsync(h_ctr + 3, X.flags, 8, hipMemcpyDeviceToHost, st));
+    HB_TRY(hipMemcpyAsync(h_ctr + 5, X.chain_rank + n_nodes, 4, hipMemcpyDeviceToHost, st));
+    HB_TRY(hipMemcpyAsync(h_ctr + 6, X.flags + 4, 4, hipMemcpyDeviceToHost, st));
     HB_TRY(hipStreamSynchronize(st));
     const uint32_t n_list_slots = h_ctr[0], n_sup = h_ctr[1], n_leaves = h_ctr[2], has_groups = h_ctr[3], max_own = h_ctr[4];
     const uint32_t n_slots_total = n_list_slots + n_leaves, n_cl = n_list_slots / 8;
     out.n_list_slots = n_list_slots; out.n_slots_total = n_slots_total; out.n_sup_records = n_sup; out.n_clusters = n_cl; out.has_groups = has_groups; out.inline_leaves = X.inline_leaves; out.max_own = max_own;
     X.n_list_slots = n_list_slots; X.n_slots_total = n_slots_total;
+    const uint32_t n_chains = h_ctr[5];
+    out.n_chains = n_chains; out.n_chain_nodes = h_ctr[6];
     lap("index sizes + scans");
 
     // ---- third allocation: what the trace kernels read (kept) + the octree (kept) in one piece; slot-sized temporaries in a piece of their own
@@ -877,7 +935,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
         size_t need = (size_t)1 << 16;
         need += (size_t)n_nodes * sizeof(DevNode) + (size_t)(n_slots_total + 1) * (sizeof(DevTriGeom) + sizeof(DevTriAttr));
         need += ((size_t)n_sup + 1 + n_cl + 8 + n_nodes + 8 + n_list_slots + 8) * 32 + (RRT_MAX_SUSPECTS + 2) * sizeof(DevSuspect);
-        need += oct_bytes + (size_t)(n_slots_total + 8) * 8 + 16 * 256;
+        need += oct_bytes + (size_t)(n_slots_total + 8) * 8 + 17 * 256 + ((size_t)n_chains + 1) * sizeof(DevChain);
         HB_TRY(hipMalloc(&out.scene_alloc, need)); out.scene_alloc_bytes = need;
     }
     DevArena A3; A3.base = static_cast<char*>(out.scene_alloc); A3.cap = out.scene_alloc_bytes;
@@ -887,6 +945,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     out.oct_box = A3.take<double>(6 * (size_t)n_nodes); out.oct_first_child = A3.take<uint32_t>(n_nodes); out.oct_tri_count = A3.take<uint32_t>(n_nodes);
     out.oct_own_off = A3.take<uint32_t>(n_nodes + 1); out.oct_own_idx = A3.take<uint32_t>(n_in);
     out.slot_tri = A3.take<uint32_t>(n_slots_total + 8); out.slot_pos = A3.take<uint32_t>(n_slots_total + 8);
+    out.chains = A3.take<DevChain>(n_chains); X.chains = out.chains;
     HB_TRY(hipMemcpyAsync(out.oct_box, R.fbox, sizeof(double) * 6 * n_nodes, hipMemcpyDeviceToDevice, st));
     HB_TRY(hipMemcpyAsync(out.oct_first_child, R.ffc, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, st));
     HB_TRY(hipMemcpyAsync(out.oct_tri_count, R.ftc, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, st));
@@ -927,6 +986,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     for (size_t L = level_begin.size() - 1; L-- > 0;)
         hipLaunchKernelGGL(k_idx_sweep, dim3(grid_for(level_begin[L + 1] - level_begin[L])), dim3(kBlock), 0, st, X, R.tmp2final, level_begin[L], level_begin[L + 1]);
     hipLaunchKernelGGL(k_idx_child_boxes, dim3(grid_for((size_t)n_nodes + 8)), dim3(kBlock), 0, st, X);
+    if (n_chains) hipLaunchKernelGGL(k_chain_records, dim3(grid_for(n_nodes)), dim3(kBlock), 0, st, X);
     hipLaunchKernelGGL(k_idx_nodes, dim3(grid_for(n_nodes)), dim3(kBlock), 0, st, X, R.fbox);
 
     // ---- exactness guard (clusters.cpp: find_origin_suspects)

@@ -19,6 +19,7 @@ struct GpuScene {
     DevNode* nodes = nullptr; DevTriGeom* geom = nullptr; DevTriAttr* attr = nullptr;
     DevSuper* supers = nullptr; DevClusterBox* cboxes = nullptr; DevClusterBox* child_boxes = nullptr; DevClusterBox* tboxes = nullptr;
     DevSuspect* suspects = nullptr;
+    DevChain* chains = nullptr; uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records (device_scene.hpp: DevChain) and the chain nodes they cover
     // flattened octree, final ids (octree.rs numbering): same allocation
     double* oct_box = nullptr;          // [n_nodes][6] lo xyz, hi xyz
     uint32_t* oct_first_child = nullptr, *oct_tri_count = nullptr, *oct_own_off = nullptr /* n_nodes + 1 */, *oct_own_idx = nullptr /* n_in_tree */;

@@ -1,5 +1,6 @@
 """Developer tool: wave-level work counters of the trace kernel (needs `make -C rust-ray-tracer_amd/csrc prof`).
-   RRT_LIB=rust-ray-tracer_amd/librrt_hip_prof.so python tools/profile_counters.py [W H] [scene.obj]"""
+   RRT_LIB=rust-ray-tracer_amd/librrt_hip_prof.so python tools/profile_counters.py [W H] [scene.obj]
+   RRT_FILTER=lane|bundle|ray forces a walk; RRT_NO_CHAIN=1 turns the chain shortcut off (RRT_FLAG_NO_CHAIN_SHORTCUT)."""
 import ctypes as C, importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,14 +13,14 @@ if scene.startswith("soup"):   # soup100000 / soup1000000: generated on the spot
     syn = importlib.import_module("rust-ray-tracer_amd.synthetic"); n = int(scene[4:])
     scene = syn.ensure_soup(os.path.join(ROOT, "assets"), n, syn.SEED_100K if n == 100000 else syn.SEED_1M if n == 1000000 else 0x5EED0003)
 sd = rrt.parse_obj_file(scene)
-rt = rrt.RayTracer(sd, rrt.default_lights(), box_filter=os.environ.get("RRT_FILTER") or None)
+rt = rrt.RayTracer(sd, rrt.default_lights(), box_filter=os.environ.get("RRT_FILTER") or None, chain_shortcut=os.environ.get("RRT_NO_CHAIN") != "1")
 L = rrt.lib()
 L.rrt_prof_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 buf = (C.c_uint64 * 24)()
 rt.render(W, H); L.rrt_prof_counters(rt._h, buf)       # warm + clear
 rt.render(W, H); ms = rt.last_stats()["kernel_ms"]; L.rrt_prof_counters(rt._h, buf)
 c = list(buf)
-names = ["node_visits(wave)", "node_visit_lanes", "tri_iters(wave)", "tri_lane_tests", "tri_box_tests(wave)", "single_candidate_decided_in_fp32(wave)", "traverse_calls(wave)", "traverse_lanes", "slab_iters(wave)", "slab_lane_tests", "super_tests(wave)", "cluster_tests(wave)", "internal_visits(wave)", "shade_blocks(wave-divergent)", "slab_exact_fallbacks(wave)"]
+names = ["node_visits(wave)", "node_visit_lanes", "tri_iters(wave)", "tri_lane_tests", "tri_box_tests(wave)", "single_candidate_decided_in_fp32(wave)", "traverse_calls(wave)", "traverse_lanes", "slab_iters(wave)", "slab_lane_tests", "super_tests(wave)", "cluster_tests(wave)", "internal_visits(wave)", "shade_blocks(wave-divergent)", "slab_exact_fallbacks(wave)", "chain_node_visits(wave)"]
 for i, n in enumerate(names):
     print(f"{n:24s} {c[i]:>16,d}")
 print(f"kernel_ms (counters build) {ms:.2f}")
