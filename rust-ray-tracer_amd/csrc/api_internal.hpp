@@ -1,0 +1,90 @@
+// api_internal.hpp -- what the units behind include/rrt.h share: the two handle types, the one place that turns exceptions into status codes, and
+// the few helpers more than one of them needs.  api.cpp: models and process-wide calls; raytracer.cpp: creation and scene set-up; frames.cpp:
+// every launch; multi.cpp: N GPUs of one node.
+#pragma once
+#include <cstdint>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "device_memory.hpp"
+#include "device_scene.hpp"
+#include "hip_check.hpp"
+#include "model.hpp"
+#include "scene_build.hpp"
+
+struct rrt_model { rrt::Model m; };
+
+struct rrt_raytracer {
+    int device = 0;
+    rrt::DevScene scene{};
+    rrt_options opt{};
+    rrt::BuiltScene built;           // the scene's buffers (one allocation) and counts, as the GPU or the host set-up built them
+    rrt::DevBuf table_mem; rrt::DevArena tables;   // textures, material table, texture table (one allocation)
+#ifdef RRT_PROFILE
+    rrt::DevBuf prof_mem;
+#endif
+    uint64_t scene_bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    rrt_stats stats{};
+    bool stats_pending = false;
+    bool launched = false;           // some launch has been recorded in `stats`
+    int walk = 0;                    // traversal variant used by this raytracer's frame launches: 0 lane filter, 1 bundle filter, 2 ray walk (see rrt.h)
+    int walk_rays = -1;              // ... and by its per-ray entry points (rrt_get_ray_colours / rrt_intersect_rays): -1 = not measured yet (rays_variant)
+    bool variant_forced = false;
+    rrt::DevBuf host_fb;             // device framebuffer kept between rrt_render calls (host-buffer entry point)
+    size_t host_fb_bytes = 0;
+    uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records in use (built.n_chains, or 0 where the shortcut's precondition fails: create_raytracer)
+    double upload_ms = 0, hip_init_ms = 0, create_ms = 0;   // set-up stages of rrt_raytracer_create besides built.ms_octree / ms_index; wall time of the whole call
+    bool gpu_setup = false;          // scene built on the device (default) or on the host (RRT_FLAG_HOST_SETUP)
+    struct Buf { const void* p = nullptr; size_t bytes = 0; } bufs[16];   // rrt_raytracer_get_buffer
+    hipStream_t own_stream = nullptr;   // rrt_render's stream: the device's shared set-up stream (staging.hpp: setup_stream; not owned)
+    uint32_t tuned_w = 0, tuned_h = 0, tuned_world = 0;   // frame size the variant below belongs to
+    uint32_t size_frames = 0;        // frames rendered at that size so far
+    bool size_measured = false;      // ... and whether the variants have been timed on it (second frame of a size)
+};
+
+namespace rrt {
+
+template <class F> int guarded(F&& f) {
+    try { return f(); }
+    catch (const Error& e) { set_error_detail(e.detail); return e.status; }
+    catch (const HipFail& h) {
+        set_error_detail(std::string(h.what) + ": " + hipGetErrorString(h.e));
+        (void)hipGetLastError();
+        return (h.e == hipErrorOutOfMemory) ? RRT_ERR_OOM : (h.e == hipErrorNoDevice || h.e == hipErrorInvalidDevice) ? RRT_ERR_NO_DEVICE : RRT_ERR_HIP;
+    }
+    catch (const std::bad_alloc&) { set_error_detail("host allocation failed"); return RRT_ERR_OOM; }
+    catch (const std::exception& e) { set_error_detail(e.what()); return RRT_ERR_INVALID_ARG; }
+    catch (...) { set_error_detail("unknown failure"); return RRT_ERR_INVALID_ARG; }
+}
+
+struct DeviceGuard {
+    int prev = 0;
+    explicit DeviceGuard(int dev) { HIP_TRY(hipGetDevice(&prev)); if (prev != dev) HIP_TRY(hipSetDevice(dev)); cur = dev; }
+    ~DeviceGuard() { if (prev != cur) (void)hipSetDevice(prev); }
+    int cur = 0;
+};
+
+inline void check_frame(const rrt_raytracer* rt, uint32_t width, uint32_t height) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (width == 0 || height == 0 || (uint64_t)width * height > 0x7FFFFFFFull) throw Error{RRT_ERR_INVALID_ARG, "bad frame size"};
+}
+
+inline Box default_root(const double* root) {
+    Box b;
+    if (root) { b.lo[0] = root[0]; b.hi[0] = root[1]; b.lo[1] = root[2]; b.hi[1] = root[3]; b.lo[2] = root[4]; b.hi[2] = root[5]; }
+    else for (int k = 0; k < 3; k++) { b.lo[k] = -20.0; b.hi[k] = 20.0; }   // utils.rs:145
+    return b;
+}
+
+// what a set-up needs of a scene besides its triangles: materials and RGB8 textures (borrowed views).  api.cpp
+struct SceneTables { const rrt_material* mats; uint32_t n_mats; std::vector<rrt_texture> tex; };
+SceneTables tables_of(const Model& M);
+void validate_tables(const SceneTables& T);
+
+// The warm-up thread (api.cpp: DeviceWarmer): the loaders start it, rrt_raytracer_create waits for it.
+void warm_up_start();
+void warm_up_join();
+
+}  // namespace rrt

@@ -12,7 +12,7 @@
 #include <cmath>
 #include <numeric>
 
-#include "device_scene.hpp"
+#include "clusters.hpp"
 #include "model.hpp"
 #include "parallel.hpp"
 
@@ -298,9 +298,6 @@ void build_clusters(const Model& m, bool enable_cull, ClusterSet& out) {
     std::sort(found.begin(), found.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
     for (auto& [c, R] : found) { out.chains.push_back(R); out.child_boxes[c - 1]._pad[1] = (uint32_t)out.chains.size(); }
 }
-
-namespace {
-}  // namespace
 
 // ---- exactness guard ------------------------------------------------------------------------------------------------------------------
 // The box filters drop a (ray, triangle) pair when the ray misses the triangle's padded box.  That is exact as long as a pair the reference's

@@ -1,0 +1,358 @@
+// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, per-ray queries, the choice of traversal variant, and
+// the statistics of the last launch.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "api_internal.hpp"
+#include "staging.hpp"
+
+namespace {
+
+using namespace rrt;
+
+FrameParams frame_params(const rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t rank, uint32_t world, bool tiled) {
+    FrameParams f{};
+    f.width = width; f.height = height;
+    f.x_scale = rt->opt.vp_w / (double)width;      // engine.rs:189
+    f.y_scale = rt->opt.vp_h / (double)height;     // engine.rs:190
+    f.z_value = rt->opt.vp_d;                      // engine.rs:191
+    f.tiles_x = (width + 7) / 8; f.tiles_y = (height + 7) / 8;
+    f.rank = rank; f.world = world; f.tiled_output = tiled ? 1u : 0u;
+    f.tile_begin = 0; f.tile_end = f.tiles_x * f.tiles_y; f.row_begin = 0; f.row_end = height;
+    // XCD-aware block order (render.hip): worth 2-4 % where the scene is far larger than an XCD's L2 (100 k / 1 M-triangle soups), costs 4 % on the teapot
+    // (profiles/r03_xcd_chunk_sweep.txt; chunks as 64 x 64-pixel squares instead of 512 x 8 strips: 1 % slower again): on for scenes of 50 000 triangle slots and more.
+    static const int forced = [] { const char* e = std::getenv("RRT_XCD_CHUNK"); return e ? std::atoi(e) : -1; }();
+    f.xcd_chunk = forced >= 0 ? (uint32_t)forced : (rt->scene.n_slots >= 50000u ? 256u : 0u);
+    return f;
+}
+
+// All traversal variants produce identical pixels; which is faster depends on how coherent the rays of a wave are (scene, camera, frame size).
+// The reference renders ONE frame per run, so the first frame of a size costs nothing extra: it runs the variant a measured rule picks (node-coherent
+// walk; bundle filter when the frame has more than ~1200 primary rays per triangle, lane filter below).  A caller that comes back for a SECOND
+// frame of the same size is rendering repeatedly, and that frame is first rendered with every variant (each twice: the first run warms caches) on the
+// caller's buffer and stream, timed with HIP events; the fastest is kept for that size.  This synchronises the stream once per size.
+void tune_variant(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void* stream) {
+    if (rt->variant_forced) return;
+    if (!(rt->tuned_w == f.width && rt->tuned_h == f.height && rt->tuned_world == f.world)) {
+        rt->tuned_w = f.width; rt->tuned_h = f.height; rt->tuned_world = f.world;
+        rt->size_frames = 0; rt->size_measured = false;
+        // First frame of a size (for a host that renders one frame per run, as the reference does, this IS the choice): the bundle filter pays once the
+        // frame holds enough rays per triangle for a 4x4-pixel wave to stay inside few nodes and long lists -- measured over 3 models x 5 frame sizes
+        // and the 100 k soup (profiles/r03_variant_sweep.json, re-measured with the final kernels: bundle wins at >= 1234 primary rays per triangle, by 4-12 %;
+        // lane filter wins at <= 719, by 12-180 %; nothing measured in between).
+        const double rays_per_triangle = 4.0 * (double)f.width * (double)f.height / (double)(rt->scene.n_slots ? rt->scene.n_slots : 1u);
+        rt->walk = rays_per_triangle > 1200.0 ? 1 : 0;
+    }
+    if (rt->size_measured) return;
+    if (++rt->size_frames < 2) return;
+    rt->size_measured = true;
+    constexpr int kVariants = 3;
+    float ms[kVariants] = {0, 0, 0};
+    if (f.world == 1) {
+        for (int variant = 0; variant < kVariants; variant++)
+            for (int rep = 0; rep < 2; rep++) {
+                HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
+                HIP_TRY((hipError_t)launch_render(rt->scene, f, d_out, stream, variant));
+                HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
+                HIP_TRY(hipEventSynchronize(rt->ev1));
+                HIP_TRY(hipEventElapsedTime(&ms[variant], rt->ev0, rt->ev1));
+            }
+    } else {
+        // One rank's share of a frame is a SHORT launch (a few waves per wave slot): alone it is bound by the latency of its last waves, not by
+        // throughput, and a multi-GPU host keeps several frames in flight on separate streams precisely to hide that (bench.py).
+        // So the variants are compared the way they will run: three launches at once on three streams, wall time per variant.
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        OwnedStream st[3];
+        for (auto& q : st) HIP_TRY(hipStreamCreateWithFlags(&q.h, hipStreamNonBlocking));
+        for (int variant = 0; variant < kVariants; variant++)
+            for (int rep = 0; rep < 2; rep++) {                           // rep 0 warms up
+                HIP_TRY(hipEventRecord(rt->ev0, st[0].h));
+                for (int round = 0; round < 2; round++)
+                    for (auto& q : st) HIP_TRY((hipError_t)launch_render(rt->scene, f, d_out, q.h, variant));   // same pixels from every launch: the overlapping writes agree
+                for (int i = 1; i < 3; i++) HIP_TRY(hipStreamSynchronize(st[i].h));
+                HIP_TRY(hipEventRecord(rt->ev1, st[0].h));
+                HIP_TRY(hipEventSynchronize(rt->ev1));
+                HIP_TRY(hipEventElapsedTime(&ms[variant], rt->ev0, rt->ev1));
+            }
+    }
+    rt->walk = 0;
+    for (int variant = 1; variant < kVariants; variant++) if (ms[variant] < ms[rt->walk]) rt->walk = variant;
+}
+
+// The per-ray entry points take whatever rays the caller has: a coherent pixel grid or rays in all directions, and the three traversal variants are
+// up to 5x apart on those (scattered rays: the ray walk; tools/random_rays_probe.py).  The first batch of at least kTuneMinRays rays is therefore
+// used to measure them on its first kTuneSample rays (each twice, the first run warms caches; same outputs from every variant), and the fastest is
+// kept for later calls.  A forced variant (RRT_FLAG_*_FILTER / RAY_WALK / NO_CULL) is used as is; smaller batches run the frame variant.
+constexpr uint32_t kTuneMinRays = 16384, kTuneSample = 65536;
+template <class Launch> int rays_variant(rrt_raytracer* rt, uint32_t n, Launch&& launch) {
+    if (rt->variant_forced) return rt->walk;
+    if (rt->walk_rays >= 0) return rt->walk_rays;
+    if (n < kTuneMinRays) return rt->walk;
+    const uint32_t m = n < kTuneSample ? n : kTuneSample;
+    float best = 0; int best_v = 0;
+    for (int variant = 0; variant < 3; variant++) {
+        float ms = 0;
+        for (int rep = 0; rep < 2; rep++) {
+            HIP_TRY(hipEventRecord(rt->ev0, nullptr));
+            HIP_TRY((hipError_t)launch(m, variant));
+            HIP_TRY(hipEventRecord(rt->ev1, nullptr));
+            HIP_TRY(hipEventSynchronize(rt->ev1));
+            HIP_TRY(hipEventElapsedTime(&ms, rt->ev0, rt->ev1));
+        }
+        if (variant == 0 || ms < best) { best = ms; best_v = variant; }
+    }
+    rt->walk_rays = best_v;
+    return best_v;
+}
+// (kernel time of a per-ray launch into rrt_stats, like a frame's)
+void record_rays(rrt_raytracer* rt, uint32_t n, int variant) {
+    rt->stats.width = n; rt->stats.height = 1; rt->stats.rays_primary = n;
+    rt->stats.scene_bytes = rt->scene_bytes; rt->stats.filter_variant = (uint32_t)variant; rt->stats.origin_plane_triangles = rt->built.n_suspects;
+    rt->stats_pending = true; rt->launched = true;
+}
+
+void record_launch(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t rank, uint32_t world) {
+    rt->stats.width = width; rt->stats.height = height;
+    const uint64_t wt = 2ull * (width / 2), ht = height >= 2 ? (uint64_t)(2 * (height / 2) - 1) : 0;   // traced pixels: see render_kernel
+    rt->stats.rays_primary = world == 1 ? 4ull * wt * ht : 0;   // per-rank share is not tracked
+    (void)rank;
+    rt->stats.scene_bytes = rt->scene_bytes;
+    rt->stats.filter_variant = (uint32_t)rt->walk; rt->stats.origin_plane_triangles = rt->built.n_suspects;
+    rt->stats_pending = true; rt->launched = true;
+}
+
+// one frame (or one rank's tiles of it) into a device buffer on the caller's stream, timed by the raytracer's events
+void launch_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t rank, uint32_t world, bool tiled, void* d_out, void* stream) {
+    DeviceGuard guard(rt->device);
+    const FrameParams f = frame_params(rt, width, height, rank, world, tiled);
+    tune_variant(rt, f, static_cast<uint32_t*>(d_out), stream);
+    HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
+    HIP_TRY((hipError_t)launch_render(rt->scene, f, static_cast<uint32_t*>(d_out), stream, rt->walk));
+    HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
+    record_launch(rt, width, height, rank, world);
+}
+
+// the device-side frame of the host-framebuffer entry points: kept and reused from call to call, grown when a larger frame comes
+uint32_t* host_fb(rrt_raytracer* rt, size_t bytes) {
+    if (rt->host_fb_bytes < bytes) {
+        rt->host_fb.reset(); rt->host_fb_bytes = 0;
+        rt->host_fb = dev_alloc(bytes);
+        rt->host_fb_bytes = bytes;
+    }
+    return static_cast<uint32_t*>(rt->host_fb.h);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t rrt_tiles_per_rank(uint32_t width, uint32_t height, uint32_t world) {
+    if (world == 0) return 0;
+    const uint32_t n = ((width + 7) / 8) * ((height + 7) / 8);
+    return (n + world - 1) / world;
+}
+
+int rrt_render_tiles_device(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t rank, uint32_t world, void* d_tiles, void* stream) {
+    return guarded([&]() -> int {
+        check_frame(rt, width, height);
+        if (!d_tiles || world == 0 || rank >= world) throw Error{RRT_ERR_INVALID_ARG, "bad rank/world/buffer"};
+        launch_frame(rt, width, height, rank, world, true, d_tiles, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_device(rrt_raytracer* rt, uint32_t width, uint32_t height, void* d_fb, void* stream) {
+    return guarded([&]() -> int {
+        check_frame(rt, width, height);
+        if (!d_fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
+        launch_frame(rt, width, height, 0, 1, false, d_fb, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_detile_device(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t world, const void* d_gathered, void* d_fb, void* stream) {
+    return guarded([&]() -> int {
+        check_frame(rt, width, height);
+        if (!d_gathered || !d_fb || world == 0) throw Error{RRT_ERR_INVALID_ARG, "bad argument"};
+        DeviceGuard guard(rt->device);
+        HIP_TRY((hipError_t)launch_detile(width, height, world, static_cast<const uint32_t*>(d_gathered), static_cast<uint32_t*>(d_fb), stream));
+        return RRT_OK;
+    });
+}
+
+// Page-locks a caller-owned framebuffer (e.g. the Rust host's Canvas.buffer, engine.rs:127) so that rrt_render can DMA the frame straight
+// into it.  Optional: rrt_render works on pageable memory too, through a pinned staging buffer and one extra host copy.
+int rrt_host_buffer_register(void* ptr, size_t bytes) {
+    return guarded([&]() -> int {
+        if (!ptr || !bytes) throw Error{RRT_ERR_INVALID_ARG, "null buffer"};
+        HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
+        return RRT_OK;
+    });
+}
+int rrt_host_buffer_unregister(void* ptr) {
+    return guarded([&]() -> int {
+        if (!ptr) throw Error{RRT_ERR_INVALID_ARG, "null buffer"};
+        HIP_TRY(hipHostUnregister(ptr));
+        return RRT_OK;
+    });
+}
+
+int rrt_render(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t* out_fb) {
+    return guarded([&]() -> int {
+        check_frame(rt, width, height);
+        if (!out_fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
+        DeviceGuard guard(rt->device);
+        const size_t bytes = sizeof(uint32_t) * (size_t)width * height;
+        uint32_t* d_fb = host_fb(rt, bytes);
+        if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
+        launch_frame(rt, width, height, 0, 1, false, d_fb, rt->own_stream);
+        // Is the caller's framebuffer page-locked (rrt_host_buffer_register, hipHostMalloc, ...)?  Then one asynchronous DMA into it.
+        hipPointerAttribute_t attr{};
+        const bool pinned = hipPointerGetAttributes(&attr, out_fb) == hipSuccess && attr.type == hipMemoryTypeHost;
+        if (!pinned) (void)hipGetLastError();
+        if (pinned) {
+            HIP_TRY(hipMemcpyAsync(out_fb, d_fb, bytes, hipMemcpyDeviceToHost, rt->own_stream));
+            HIP_TRY(hipStreamSynchronize(rt->own_stream));                 // blocking: the frame is in out_fb on return
+            return RRT_OK;
+        }
+        // Pageable framebuffer: through the device's pinned staging ring, chunk DMAs running ahead of the copies out (staging.cpp)
+        staged_download(out_fb, d_fb, bytes, rt->own_stream);
+        return RRT_OK;
+    });
+}
+
+// Scene::draw_scene as the reference paces it (engine.rs:196-253): the scene rows y in [-H/2, H/2) in chunks of `chunk_rows` (50 there), each chunk
+// traced, put into the canvas (put_pixel, engine.rs:146-158: scene row y -> canvas row H - (y + H/2), i.e. bottom-up), then canvas.update().
+int rrt_render_progressive(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t* out_fb, uint32_t chunk_rows, rrt_update_fn on_update, void* user) {
+    return guarded([&]() -> int {
+        check_frame(rt, width, height);
+        if (!out_fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
+        if (chunk_rows == 0) chunk_rows = 50;                              // engine.rs:195
+        DeviceGuard guard(rt->device);
+        const size_t bytes = sizeof(uint32_t) * (size_t)width * height;
+        uint32_t* d_fb = host_fb(rt, bytes);
+        FrameParams f = frame_params(rt, width, height, 0, 1, false);
+        tune_variant(rt, f, d_fb, nullptr);                               // (first frame of a new size: picks the filter variant on the full frame)
+        HIP_TRY(hipMemsetAsync(d_fb, 0, bytes, nullptr));                  // Canvas::new, engine.rs:135
+        std::memset(out_fb, 0, bytes);
+        const int64_t H = height, half = H / 2;
+        HIP_TRY(hipEventRecord(rt->ev0, nullptr));
+        for (int64_t cs = -half; cs < half; cs += chunk_rows) {            // engine.rs:198-199
+            const int64_t ce = std::min<int64_t>(cs + chunk_rows, half);
+            // canvas rows of the scene rows [cs, ce): H - (y + H/2); the row that lands on H (y = -H/2) is rejected by put_pixel (engine.rs:152-155)
+            const int64_t r_lo = H - (ce - 1 + half), r_hi = std::min<int64_t>(H - (cs + half), H - 1);   // inclusive
+            if (r_lo <= r_hi) {
+                f.row_begin = (uint32_t)r_lo; f.row_end = (uint32_t)r_hi + 1;
+                f.tile_begin = (f.row_begin / 8) * f.tiles_x; f.tile_end = ((f.row_end + 7) / 8) * f.tiles_x;
+                HIP_TRY((hipError_t)launch_render(rt->scene, f, d_fb, nullptr, rt->walk));
+                HIP_TRY(hipMemcpy(out_fb + (size_t)f.row_begin * width, d_fb + (size_t)f.row_begin * width,
+                                  sizeof(uint32_t) * (size_t)width * (f.row_end - f.row_begin), hipMemcpyDeviceToHost));
+            }
+            if (on_update) on_update(user, out_fb, width, height, r_lo <= r_hi ? (uint32_t)r_lo : 0u, r_lo <= r_hi ? (uint32_t)(r_hi - r_lo + 1) : 0u);   // canvas.update(), engine.rs:253
+        }
+        HIP_TRY(hipEventRecord(rt->ev1, nullptr));
+        record_launch(rt, width, height, 0, 1);
+        return RRT_OK;
+    });
+}
+
+int rrt_get_ray_colours(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, uint32_t* colours) {
+    return guarded([&]() -> int {
+        if (!rt || (n && (!origins || !dirs || !colours))) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        const DevBuf b_o = dev_alloc(sizeof(double) * 3 * (size_t)n), b_d = dev_alloc(sizeof(double) * 3 * (size_t)n), b_c = dev_alloc(sizeof(uint32_t) * (size_t)n);
+        double *d_o = static_cast<double*>(b_o.h), *d_d = static_cast<double*>(b_d.h); uint32_t* d_c = static_cast<uint32_t*>(b_c.h);
+        HIP_TRY(hipMemcpy(d_o, origins, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_d, dirs, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+        const int variant = rays_variant(rt, n, [&](uint32_t m, int v) { return launch_ray_colours(rt->scene, m, d_o, d_d, d_c, nullptr, v); });
+        HIP_TRY(hipEventRecord(rt->ev0, nullptr));
+        HIP_TRY((hipError_t)launch_ray_colours(rt->scene, n, d_o, d_d, d_c, nullptr, variant));
+        HIP_TRY(hipEventRecord(rt->ev1, nullptr));
+        record_rays(rt, n, variant);
+        HIP_TRY(hipMemcpy(colours, d_c, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        return (int)RRT_OK;
+    });
+}
+
+int rrt_intersect_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t,
+                       uint8_t* hit, double* t, double* u, double* v, uint32_t* tri) {
+    return guarded([&]() -> int {
+        if (!rt || (n && (!origins || !dirs || !hit || !t || !u || !v || !tri))) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        const size_t N = n;
+        const size_t sizes[8] = {24 * N, 24 * N, 8 * N, N, 8 * N, 8 * N, 8 * N, 4 * N};
+        DevBuf owned[8]; void* bufs[8];
+        for (int i = 0; i < 8; i++) { owned[i] = dev_alloc(sizes[i]); bufs[i] = owned[i].h; }
+        HIP_TRY(hipMemcpy(bufs[0], origins, 24 * N, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(bufs[1], dirs, 24 * N, hipMemcpyHostToDevice));
+        if (max_t) HIP_TRY(hipMemcpy(bufs[2], max_t, 8 * N, hipMemcpyHostToDevice));
+        auto launch = [&](uint32_t m, int v) {
+            return launch_intersect(rt->scene, m, (const double*)bufs[0], (const double*)bufs[1], max_t ? (const double*)bufs[2] : nullptr,
+                                    (uint8_t*)bufs[3], (double*)bufs[4], (double*)bufs[5], (double*)bufs[6], (uint32_t*)bufs[7], nullptr, v);
+        };
+        const int variant = rays_variant(rt, n, launch);
+        HIP_TRY(hipEventRecord(rt->ev0, nullptr));
+        HIP_TRY((hipError_t)launch(n, variant));
+        HIP_TRY(hipEventRecord(rt->ev1, nullptr));
+        record_rays(rt, n, variant);
+        HIP_TRY(hipMemcpy(hit, bufs[3], N, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(t, bufs[4], 8 * N, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(u, bufs[5], 8 * N, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(v, bufs[6], 8 * N, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tri, bufs[7], 4 * N, hipMemcpyDeviceToHost));
+        return (int)RRT_OK;
+    });
+}
+
+#ifdef RRT_PROFILE
+// developer build only: read and clear the 16 work counters
+int rrt_prof_counters(rrt_raytracer* rt, unsigned long long* out16) {
+    return guarded([&]() -> int {
+        DeviceGuard guard(rt->device);
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out16, rt->scene.prof, 24 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(rt->scene.prof, 0, 24 * sizeof(unsigned long long)));
+        return RRT_OK;
+    });
+}
+// developer build `make band`: read and clear the four (alpha, delta)-band pair counters (render.hip: band_count)
+int rrt_prof_band_counters(rrt_raytracer* rt, unsigned long long* out4) {
+    return guarded([&]() -> int {
+        DeviceGuard guard(rt->device);
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out4, rt->scene.prof + 24, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(rt->scene.prof + 24, 0, 4 * sizeof(unsigned long long)));
+        return RRT_OK;
+    });
+}
+#endif
+
+int rrt_last_stats(const rrt_raytracer* rt_c, rrt_stats* out) {
+    return guarded([&]() -> int {
+        rrt_raytracer* rt = const_cast<rrt_raytracer*>(rt_c);
+        if (!rt || !out) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
+        if (rt->stats_pending) {
+            DeviceGuard guard(rt->device);
+            HIP_TRY(hipEventSynchronize(rt->ev1));
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, rt->ev0, rt->ev1));
+            rt->stats.kernel_ms = ms;
+            rt->stats_pending = false;
+        }
+        if (!rt->launched) rt->stats.filter_variant = (uint32_t)rt->walk;   // (before the first launch: the forced variant, or 0)
+        rt->stats.origin_plane_triangles = rt->built.n_suspects; rt->stats.scene_bytes = rt->scene_bytes;
+        {   // the exactness band of the index (clusters.cpp: find_origin_suspects has the per-pair formulas)
+            const double mag = (double)rt->scene.cull_limit / 4.0, pad = mag / 32768.0, eps = 0x1p-53;
+            rt->stats.filter_pad = rt->scene.cull_enabled ? pad : 0.0;
+            rt->stats.filter_alpha_unit = (rt->scene.cull_enabled && pad > 0) ? 8.0 * 64.0 * eps * mag / pad : 0.0;
+            rt->stats.filter_delta_unit = (rt->scene.cull_enabled && pad > 0) ? 2.0 * (rt->stats.filter_alpha_unit * mag + 64.0 * eps * mag) : 0.0;
+        }
+        *out = rt->stats;
+        return RRT_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // scene_build.hip -- the once-per-scene set-up on the GPU: what the reference does inside its parser, one triangle at a time
 // (src/file_management/utils.rs:192-198 -> Octree::push_triangle, src/collision/octree.rs:41-241), restated LEVEL-PARALLEL and order-exact, followed
 // by this build's own-list index (clusters.cpp) and the device records the trace kernels read.  Every array it produces is byte-identical to what the
-// host path (octree.cpp + clusters.cpp + the fill loops of api.cpp, RRT_FLAG_HOST_SETUP) produces for finite input; tests/test_gpu_build.py checks that.
+// host path (octree.cpp + clusters.cpp + the fill loops of host_build.cpp, RRT_FLAG_HOST_SETUP) produces for finite input; tests/test_gpu_build.py checks that.
 //
 // Why the insertion of octree.rs:54-108 is level-parallel.  At a node the arrivals, in push order, are a1 < a2 < ...:
 //   * a1 finds an empty leaf and stays (octree.rs:77-78);
@@ -25,16 +25,14 @@
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <memory>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "parallel.hpp"
 #include "scene_build.hpp"
+#include "staging.hpp"
 
 namespace rrt {
 namespace {
@@ -43,8 +41,6 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr int kBlock = 256;
 constexpr uint32_t kClusterTris = 8, kSuperTris = 64, kGroupSupers = 8, kGroupThreshold = 24;   // clusters.cpp
 constexpr double kPadFraction = 1.0 / 32768.0;
-
-#define HB_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) throw HipBuildFail{(int)_e, #expr}; } while (0)
 
 static_assert(sizeof(Triangle) == 224, "Triangle is uploaded as is: 27 doubles + the material index");
 
@@ -395,7 +391,7 @@ __global__ void __launch_bounds__(kBlock) k_idx_leaf_slots(Idx X) {   // the sec
     X.slot_tri[s] = X.own_idx[X.own_off[F]]; X.slot_pos[s] = 0u;
 }
 
-__global__ void __launch_bounds__(kBlock) k_idx_slots(Idx X) {   // per slot: geometry, attributes, padded per-triangle box (api.cpp's fill loops, clusters.cpp)
+__global__ void __launch_bounds__(kBlock) k_idx_slots(Idx X) {   // per slot: geometry, attributes, padded per-triangle box (host_build.cpp's fill loops, clusters.cpp)
     const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= X.n_slots_total + 8u) return;
     if (s >= X.n_slots_total) {                                 // the 8 spare box records after the list slots (all-zero boxes in centre/half form)
@@ -559,7 +555,7 @@ __global__ void __launch_bounds__(kBlock) k_chain_records(Idx X) {   // after k_
     X.child_boxes[c - 1u]._pad[1] = X.chain_rank[c] + 1u;
 }
 
-__global__ void __launch_bounds__(kBlock) k_idx_nodes(Idx X, const double* fbox) {   // DevNode records (api.cpp's fill loop)
+__global__ void __launch_bounds__(kBlock) k_idx_nodes(Idx X, const double* fbox) {   // DevNode records (host_build.cpp's fill loop)
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= X.n_nodes) return;
     DevNode d;
@@ -631,126 +627,9 @@ __global__ void k_set_root(Oct S) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct DevArena {
-    char* base = nullptr; size_t cap = 0, used = 0;
-    template <class T> T* take(size_t count) {
-        const size_t bytes = (sizeof(T) * (count ? count : 1) + 255) & ~(size_t)255;
-        if (used + bytes > cap) throw Error{RRT_ERR_OOM, "internal: set-up arena too small"};
-        T* p = reinterpret_cast<T*>(base + used); used += bytes; return p;
-    }
-};
-struct DevFree { void* p = nullptr; ~DevFree() { if (p) (void)hipFree(p); } };
-
-// ---- pinned staging: one ring of page-locked chunks per device, shared by every upload and every pageable-framebuffer download of the process.
-// A slot's event says when the DMA that last used it has finished; a slot is waited for right before it is reused, never at the end of a call.
-struct StagingRing {
-    static constexpr int kSlots = 8; static constexpr size_t kSlotBytes = (size_t)4 << 20;
-    char* mem = nullptr; hipEvent_t ev[kSlots] = {}; bool busy[kSlots] = {}; size_t next = 0; hipStream_t stream = nullptr, stream2 = nullptr;
-    void ensure() {
-        if (mem) return;
-        HB_TRY(hipHostMalloc((void**)&mem, kSlots * kSlotBytes, hipHostMallocDefault));
-        for (auto& e : ev) HB_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HB_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));   // the device's set-up stream (creating one costs ~3 ms: done once, by the warm-up thread when it runs)
-        HB_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));  // uploads beside the build (upload_stream)
-    }
-    int acquire() {                                                     // next slot, free to be written
-        const int s = (int)(next++ % kSlots);
-        if (busy[s]) { HB_TRY(hipEventSynchronize(ev[s])); busy[s] = false; }
-        return s;
-    }
-    void release(int s, hipStream_t st) { HB_TRY(hipEventRecord(ev[s], st)); busy[s] = true; }
-};
-constexpr int kMaxDevices = 64;
-std::mutex g_ring_mu;
-StagingRing g_rings[kMaxDevices];
-StagingRing& ring_of_current_device() {                                 // (caller holds g_ring_mu)
-    int dev = 0;
-    HB_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) throw Error{RRT_ERR_INVALID_ARG, "device index beyond the staging table"};
-    g_rings[dev].ensure();
-    return g_rings[dev];
-}
-// parallel memcpy on the host pool (copies out of the ring on the frame path: one core moves ~10 GB/s)
-void copy_bytes(char* dst, const char* src, size_t len) {
-    if (len < ((size_t)2 << 20)) { std::memcpy(dst, src, len); return; }
-    parallel_ranges(len, (len + 3) / 4, [&](size_t b, size_t e, size_t) { std::memcpy(dst + b, src + b, e - b); });
-}
-
 }  // namespace
 
-void staged_upload_warm() { try { std::lock_guard<std::mutex> lk(g_ring_mu); (void)ring_of_current_device(); } catch (...) { (void)hipGetLastError(); } }
-
-void* setup_stream() { std::lock_guard<std::mutex> lk(g_ring_mu); return ring_of_current_device().stream; }
-void* upload_stream() { std::lock_guard<std::mutex> lk(g_ring_mu); return ring_of_current_device().stream2; }
-
-void staged_upload(void* dst, const void* src, size_t bytes, void* stream_) {
-    if (!bytes) return;
-    hipStream_t stream = (hipStream_t)stream_;
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, src) == hipSuccess && attr.type == hipMemoryTypeHost) {   // already page-locked: one DMA
-        HB_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
-        return;
-    }
-    (void)hipGetLastError();
-    std::lock_guard<std::mutex> lk(g_ring_mu);
-    StagingRing& R = ring_of_current_device();
-    const size_t S = StagingRing::kSlotBytes, n_chunks = (bytes + S - 1) / S;
-    // One task per ring slot (host pool), each an independent pipeline: wait for the slot's last DMA, fill the slot from `src`, enqueue its DMA, take the next
-    // chunk -- so the copies into page-locked memory (the slow part: one core moves ~10 GB/s) run on several cores while the DMA engine drains
-    // the finished slots.  Chunks land at disjoint destinations: their order on the stream does not matter.
-    const unsigned workers = (unsigned)std::min<size_t>(std::min<size_t>(StagingRing::kSlots, n_chunks), host_threads());
-    int dev = 0;
-    HB_TRY(hipGetDevice(&dev));
-    std::atomic<size_t> next_chunk{0};
-    std::vector<int> err(workers, 0);
-    auto run = [&](unsigned w) {
-        if (hipSetDevice(dev) != hipSuccess) { err[w] = (int)hipGetLastError(); return; }        // (HIP's current device is per thread, and a pool worker keeps its last one)
-        char* stage = R.mem + (size_t)w * S;
-        for (size_t c; (c = next_chunk.fetch_add(1)) < n_chunks;) {
-            const size_t off = c * S, len = std::min(S, bytes - off);
-            hipError_t e = hipSuccess;
-            if (R.busy[w]) { e = hipEventSynchronize(R.ev[w]); R.busy[w] = false; }
-            if (e == hipSuccess) { std::memcpy(stage, static_cast<const char*>(src) + off, len); e = hipMemcpyAsync(static_cast<char*>(dst) + off, stage, len, hipMemcpyHostToDevice, stream); }
-            if (e == hipSuccess) { e = hipEventRecord(R.ev[w], stream); R.busy[w] = true; }
-            if (e != hipSuccess) { err[w] = (int)e; return; }
-        }
-    };
-    parallel_ranges(workers, 1, [&](size_t b, size_t e, size_t) { for (size_t w = b; w < e; w++) run((unsigned)w); });
-    for (int e : err) if (e) throw HipBuildFail{e, "staged_upload (pinned-staging host-to-device copy)"};
-    // src has been read completely: it may be freed.  dst is complete once `stream` has drained; the slots guard themselves (busy + event).
-}
-
-// Device -> pageable host memory through the ring: chunk DMAs run ahead while the finished chunks are copied out (a pageable hipMemcpy stages through
-// the runtime's own bounce buffers serially; a frame-sized pinned buffer of the caller's own costs milliseconds to allocate -- more than the
-// reference's one frame takes to trace).  Blocking: dst is complete on return.  Everything enqueued on `stream` before the call is waited for.
-void staged_download(void* dst, const void* src_dev, size_t bytes, void* stream_) {
-    if (!bytes) return;
-    hipStream_t stream = (hipStream_t)stream_;
-    std::lock_guard<std::mutex> lk(g_ring_mu);
-    StagingRing& R = ring_of_current_device();
-    size_t chunk = (bytes / 8 + 0xFFFFF) & ~(size_t)0xFFFFF;              // about 8 chunks per frame, whole MiB, at most a slot
-    chunk = std::min(std::max(chunk, (size_t)1 << 20), StagingRing::kSlotBytes);
-    const size_t n_chunks = (bytes + chunk - 1) / chunk;
-    int slot_of[StagingRing::kSlots];
-    size_t issued = 0;
-    auto issue = [&](size_t c) {
-        const int slot = R.acquire();
-        const size_t off = c * chunk, len = std::min(chunk, bytes - off);
-        HB_TRY(hipMemcpyAsync(R.mem + (size_t)slot * StagingRing::kSlotBytes, static_cast<const char*>(src_dev) + off, len, hipMemcpyDeviceToHost, stream));
-        R.release(slot, stream);
-        slot_of[c % StagingRing::kSlots] = slot;
-    };
-    for (; issued < n_chunks && issued < (size_t)StagingRing::kSlots; issued++) issue(issued);
-    for (size_t c = 0; c < n_chunks; c++) {
-        const int slot = slot_of[c % StagingRing::kSlots];
-        HB_TRY(hipEventSynchronize(R.ev[slot])); R.busy[slot] = false;
-        const size_t off = c * chunk, len = std::min(chunk, bytes - off);
-        copy_bytes(static_cast<char*>(dst) + off, R.mem + (size_t)slot * StagingRing::kSlotBytes, len);
-        if (issued < n_chunks) issue(issued++);
-    }
-}
-
-void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool enable_cull, const double origin[3], void* stream_, GpuScene& out, const std::function<void()>& after_upload) {
+void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool enable_cull, const double origin[3], void* stream_, BuiltScene& out, const std::function<void()>& after_upload) {
     hipStream_t st = (hipStream_t)stream_;
     const bool trace = std::getenv("RRT_SETUP_TRACE") != nullptr;          // developer: host wall time of every stage (synchronising: not the production timing)
     auto lap = [&, last = std::chrono::steady_clock::now()](const char* what) mutable {
@@ -761,7 +640,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     };
     hipEvent_t evs[4] = {};
     struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{evs};
-    for (auto& e : evs) HB_TRY(hipEventCreate(&e));
+    for (auto& e : evs) HIP_TRY(hipEventCreate(&e));
 
     // ---- temporaries, first part: everything whose size follows from the triangle count.  A subdivision has a distinct trigger triangle and
     // triangle 0 triggers none, so there are at most n - 1 of them: 1 + 8 (n - 1) nodes bound every scene.
@@ -770,18 +649,18 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     size_t scan_bytes = 0, sort_bytes = 0;
     {
         size_t b = 0;
-        HB_TRY(rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, std::max<size_t>(cap + 1, n + 1), rocprim::plus<uint32_t>(), st)); scan_bytes = b;
-        HB_TRY(rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n ? n : 1, 0, 32, st)); sort_bytes = b;
+        HIP_TRY(rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, std::max<size_t>(cap + 1, n + 1), rocprim::plus<uint32_t>(), st)); scan_bytes = b;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n ? n : 1, 0, 32, st)); sort_bytes = b;
     }
     const size_t prim_bytes = std::max(scan_bytes, sort_bytes) + 256;
-    DevFree t1;
+    DevBuf t1;
     DevArena A1;
     A1.cap = (size_t)n * (sizeof(Triangle) + (src.tris ? 0 : 27 * 8 + 4) + 48 + 3 * 4 + 4 /*rank*/ + 4 * 4 /*key,val in/out*/) + cap * (48 + 4 * 4) + (cap / 8 + 1) * 8 + prim_bytes + (64 << 10);
     lap("events, rocPRIM size queries");
-    HB_TRY(hipMalloc(&t1.p, A1.cap)); A1.base = static_cast<char*>(t1.p);
+    t1 = dev_alloc(A1.cap); A1.base = static_cast<char*>(t1.h);
     lap("hipMalloc temporaries 1");
 
-    HB_TRY(hipEventRecord(evs[0], st));
+    HIP_TRY(hipEventRecord(evs[0], st));
     Triangle* d_tris = A1.take<Triangle>(n);
     if (src.tris) staged_upload(d_tris, src.tris, sizeof(Triangle) * (size_t)n, st);
     // The caller's own arrays: the octree needs the positions only, so they go up first and the tree is built while the other two thirds (texture
@@ -793,17 +672,17 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     if (!src.tris && n) {
         d_pos = A1.take<double>(9 * (size_t)n); d_uv = A1.take<double>(9 * (size_t)n); d_nrm = A1.take<double>(9 * (size_t)n); d_mat = A1.take<uint32_t>(n);
         staged_upload(d_pos, src.pos, 72 * (size_t)n, st);
-        HB_TRY(hipEventCreateWithFlags(&ev_attr, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ev_attr, hipEventDisableTiming));
         hipStream_t st2 = (hipStream_t)upload_stream();
         int dev = 0;
-        HB_TRY(hipGetDevice(&dev));
+        HIP_TRY(hipGetDevice(&dev));
         attr_task.reset(new AsyncTask([=, &src] {
-            HB_TRY(hipSetDevice(dev));                                  // (HIP's current device is per thread, and a pool worker keeps its last one)
+            HIP_TRY(hipSetDevice(dev));                                  // (HIP's current device is per thread, and a pool worker keeps its last one)
             staged_upload(d_uv, src.uv, 72 * (size_t)n, st2); staged_upload(d_nrm, src.nrm, 72 * (size_t)n, st2); staged_upload(d_mat, src.mat, 4 * (size_t)n, st2);
-            HB_TRY(hipEventRecord(ev_attr, st2));
+            HIP_TRY(hipEventRecord(ev_attr, st2));
         }));
     }
-    HB_TRY(hipEventRecord(evs[1], st));
+    HIP_TRY(hipEventRecord(evs[1], st));
     if (after_upload) after_upload();
     lap("triangle upload (pinned staging)");
 
@@ -819,10 +698,10 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     for (int a = 0; a < 3; a++) { S.rlo[a] = root.lo[a]; S.rhi[a] = root.hi[a]; }
 
     uint32_t* h_ctr = nullptr;                                         // pinned read-back words
-    HB_TRY(hipHostMalloc((void**)&h_ctr, 64 * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&h_ctr, 64 * sizeof(uint32_t), hipHostMallocDefault));
     struct HostFree { void* p; ~HostFree() { if (p) (void)hipHostFree(p); } } hf{h_ctr};
     lap("hipHostMalloc read-back words");
-    auto read_words = [&](const uint32_t* dev, int count) { HB_TRY(hipMemcpyAsync(h_ctr, dev, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, st)); HB_TRY(hipStreamSynchronize(st)); };
+    auto read_words = [&](const uint32_t* dev, int count) { HIP_TRY(hipMemcpyAsync(h_ctr, dev, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); };
 
     // ---- level loop (octree.rs:54-108 for every triangle at once)
     hipLaunchKernelGGL(k_set_root, dim3(1), dim3(1), 0, st, S);
@@ -846,17 +725,17 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
         if (level_begin.size() > RRT_MAX_OCTREE_DEPTH)
             throw Error{RRT_ERR_DEPTH, "octree depth exceeds RRT_MAX_OCTREE_DEPTH (" + std::to_string(RRT_MAX_OCTREE_DEPTH) + "): coincident triangles? (octree.rs:79-92)"};
     }
-    HB_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     lap("octree level loop");
     level_begin.push_back(n_nodes);                                     // level L = temporary ids [level_begin[L], level_begin[L + 1])
-    out.n_nodes = n_nodes; out.max_depth = (uint32_t)level_begin.size() - 1;
+    out.n_tris = n; out.n_nodes = n_nodes; out.max_depth = (uint32_t)level_begin.size() - 1;
 
     // ---- second allocation: the octree in the reference's numbering (kept), and the node-sized temporaries
     const size_t oct_bytes = (size_t)n_nodes * (48 + 4 + 4) + ((size_t)n_nodes + 1) * 4 + (size_t)n * 4 + 4096;
-    DevFree t2;
+    DevBuf t2;
     DevArena A2;
     A2.cap = oct_bytes + (size_t)n_nodes * (4 /*tmp2final*/ + 4 /*newblock*/ + 6 * 4 /*a_*, bases*/ + 48 /*nb*/) + (size_t)(n_nodes + 1) * 4 * 6 + (size_t)n * (2 * 4 + 2 * 24) + (64 << 10);
-    HB_TRY(hipMalloc(&t2.p, A2.cap)); A2.base = static_cast<char*>(t2.p);
+    t2 = dev_alloc(A2.cap); A2.base = static_cast<char*>(t2.h);
     lap("hipMalloc temporaries 2");
     Remap R{};
     R.n_nodes = n_nodes; R.n_blocks = n_blocks; R.n = n;
@@ -868,31 +747,31 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     R.key = key_in; R.val = val_in; R.own_count = own_count;
     if (n) {
         size_t b = prim_bytes;
-        HB_TRY(rocprim::exclusive_scan(prim_tmp, b, S.trig, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        HIP_TRY(rocprim::exclusive_scan(prim_tmp, b, S.trig, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
     }
     if (n_blocks) hipLaunchKernelGGL(k_newblock, dim3(grid_for(n_blocks)), dim3(kBlock), 0, st, R);
     hipLaunchKernelGGL(k_remap_nodes, dim3(grid_for(n_nodes)), dim3(kBlock), 0, st, R);
-    HB_TRY(hipMemsetAsync(own_count, 0, sizeof(uint32_t) * ((size_t)n_nodes + 2), st));
+    HIP_TRY(hipMemsetAsync(own_count, 0, sizeof(uint32_t) * ((size_t)n_nodes + 2), st));
     unsigned key_bits = 1; while ((1ull << key_bits) <= (unsigned long long)n_nodes) key_bits++;
-    DevFree sort_tmp;                                                   // only when this bit range needs more than the up-front query said
+    DevBuf sort_tmp;                                                   // only when this bit range needs more than the up-front query said
     if (n) {
         hipLaunchKernelGGL(k_tri_keys, dim3(grid_for(n)), dim3(kBlock), 0, st, R);
         // rocPRIM picks the sort's algorithm (and with it the size of its temporary storage) from the element count AND the bit range, so the need is
         // asked again for the range actually sorted: the 32-bit query above is a lower bound only (4 M triangles, 23 bits: more).
         size_t b = 0;
-        HB_TRY(rocprim::radix_sort_pairs(nullptr, b, key_in, key_out, val_in, val_out, (size_t)n, 0u, key_bits, st));
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, b, key_in, key_out, val_in, val_out, (size_t)n, 0u, key_bits, st));
         void* tmp = prim_tmp;
-        if (b > prim_bytes) { HB_TRY(hipMalloc(&sort_tmp.p, b)); tmp = sort_tmp.p; } else b = prim_bytes;
-        HB_TRY(rocprim::radix_sort_pairs(tmp, b, key_in, key_out, val_in, val_out, (size_t)n, 0u, key_bits, st));
+        if (b > prim_bytes) { sort_tmp = dev_alloc(b); tmp = sort_tmp.h; } else b = prim_bytes;
+        HIP_TRY(rocprim::radix_sort_pairs(tmp, b, key_in, key_out, val_in, val_out, (size_t)n, 0u, key_bits, st));
     }
     {
         size_t b = prim_bytes;
-        HB_TRY(rocprim::exclusive_scan(prim_tmp, b, own_count, own_off, 0u, (size_t)n_nodes + 1, rocprim::plus<uint32_t>(), st));
+        HIP_TRY(rocprim::exclusive_scan(prim_tmp, b, own_count, own_off, 0u, (size_t)n_nodes + 1, rocprim::plus<uint32_t>(), st));
     }
     read_words(own_off + n_nodes, 1);
     const uint32_t n_in = h_ctr[0];
     out.n_in_tree = n_in;
-    HB_TRY(hipEventRecord(evs[2], st));
+    HIP_TRY(hipEventRecord(evs[2], st));
     lap("remap, own-list sort");
 
     // ---- index sizes
@@ -908,37 +787,37 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     X.flags = A2.take<uint32_t>(8);
     X.nb = A2.take<unsigned long long>(6 * (size_t)n_nodes);
     X.perm_a = A2.take<uint32_t>(n_in); X.perm_b = A2.take<uint32_t>(n_in); X.cen_a = A2.take<double>(3 * (size_t)n_in); X.cen_b = A2.take<double>(3 * (size_t)n_in);
-    HB_TRY(hipMemsetAsync(X.flags, 0, 8 * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(X.flags, 0, 8 * sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_idx_sizes, dim3(grid_for((size_t)n_nodes + 1)), dim3(kBlock), 0, st, X);
     hipLaunchKernelGGL(k_chain_heads, dim3(grid_for((size_t)n_nodes + 1)), dim3(kBlock), 0, st, X);
     for (auto pr : {std::pair<uint32_t*, uint32_t*>{X.a_slots, X.slot_base}, {X.a_sup, X.sup_base}, {X.a_leaf, X.leaf_rank}, {X.a_chain, X.chain_rank}}) {
         size_t b = prim_bytes;
-        HB_TRY(rocprim::exclusive_scan(prim_tmp, b, pr.first, pr.second, 0u, (size_t)n_nodes + 1, rocprim::plus<uint32_t>(), st));
+        HIP_TRY(rocprim::exclusive_scan(prim_tmp, b, pr.first, pr.second, 0u, (size_t)n_nodes + 1, rocprim::plus<uint32_t>(), st));
     }
-    HB_TRY(hipMemcpyAsync(h_ctr, X.slot_base + n_nodes, 4, hipMemcpyDeviceToHost, st));
-    HB_TRY(hipMemcpyAsync(h_ctr + 1, X.sup_base + n_nodes, 4, hipMemcpyDeviceToHost, st));
-    HB_TRY(hipMemcpyAsync(h_ctr + 2, X.leaf_rank + n_nodes, 4, hipMemcpyDeviceToHost, st));
-    HB_TRY(hipMemcpyAsync(h_ctr + 3, X.flags, 8, hipMemcpyDeviceToHost, st));
-    HB_TRY(hipMemcpyAsync(h_ctr + 5, X.chain_rank + n_nodes, 4, hipMemcpyDeviceToHost, st));
-    HB_TRY(hipMemcpyAsync(h_ctr + 6, X.flags + 4, 4, hipMemcpyDeviceToHost, st));
-    HB_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h_ctr, X.slot_base + n_nodes, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_ctr + 1, X.sup_base + n_nodes, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_ctr + 2, X.leaf_rank + n_nodes, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_ctr + 3, X.flags, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_ctr + 5, X.chain_rank + n_nodes, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_ctr + 6, X.flags + 4, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     const uint32_t n_list_slots = h_ctr[0], n_sup = h_ctr[1], n_leaves = h_ctr[2], has_groups = h_ctr[3], max_own = h_ctr[4];
     const uint32_t n_slots_total = n_list_slots + n_leaves, n_cl = n_list_slots / 8;
-    out.n_list_slots = n_list_slots; out.n_slots_total = n_slots_total; out.n_sup_records = n_sup; out.n_clusters = n_cl; out.has_groups = has_groups; out.inline_leaves = X.inline_leaves; out.max_own = max_own;
+    out.n_list_slots = n_list_slots; out.n_slots_total = n_slots_total; out.n_sup_records = n_sup; out.n_clusters = n_cl; out.has_groups = has_groups; out.inline_leaves = X.inline_leaves;
     X.n_list_slots = n_list_slots; X.n_slots_total = n_slots_total;
     const uint32_t n_chains = h_ctr[5];
     out.n_chains = n_chains; out.n_chain_nodes = h_ctr[6];
     lap("index sizes + scans");
 
     // ---- third allocation: what the trace kernels read (kept) + the octree (kept) in one piece; slot-sized temporaries in a piece of their own
+    DevArena A3;
     {
         size_t need = (size_t)1 << 16;
         need += (size_t)n_nodes * sizeof(DevNode) + (size_t)(n_slots_total + 1) * (sizeof(DevTriGeom) + sizeof(DevTriAttr));
         need += ((size_t)n_sup + 1 + n_cl + 8 + n_nodes + 8 + n_list_slots + 8) * 32 + (RRT_MAX_SUSPECTS + 2) * sizeof(DevSuspect);
         need += oct_bytes + (size_t)(n_slots_total + 8) * 8 + 17 * 256 + ((size_t)n_chains + 1) * sizeof(DevChain);
-        HB_TRY(hipMalloc(&out.scene_alloc, need)); out.scene_alloc_bytes = need;
+        out.alloc = dev_alloc(need); A3.base = static_cast<char*>(out.alloc.h); A3.cap = need;
     }
-    DevArena A3; A3.base = static_cast<char*>(out.scene_alloc); A3.cap = out.scene_alloc_bytes;
     out.nodes = A3.take<DevNode>(n_nodes); out.geom = A3.take<DevTriGeom>(n_slots_total); out.attr = A3.take<DevTriAttr>(n_slots_total);
     out.supers = A3.take<DevSuper>(n_sup); out.cboxes = A3.take<DevClusterBox>(n_cl + 8); out.child_boxes = A3.take<DevClusterBox>((n_nodes > 1 ? n_nodes - 1 : 0) + 8);
     out.tboxes = A3.take<DevClusterBox>(n_list_slots + 8); out.suspects = A3.take<DevSuspect>(RRT_MAX_SUSPECTS + 1);
@@ -946,14 +825,14 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     out.oct_own_off = A3.take<uint32_t>(n_nodes + 1); out.oct_own_idx = A3.take<uint32_t>(n_in);
     out.slot_tri = A3.take<uint32_t>(n_slots_total + 8); out.slot_pos = A3.take<uint32_t>(n_slots_total + 8);
     out.chains = A3.take<DevChain>(n_chains); X.chains = out.chains;
-    HB_TRY(hipMemcpyAsync(out.oct_box, R.fbox, sizeof(double) * 6 * n_nodes, hipMemcpyDeviceToDevice, st));
-    HB_TRY(hipMemcpyAsync(out.oct_first_child, R.ffc, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, st));
-    HB_TRY(hipMemcpyAsync(out.oct_tri_count, R.ftc, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, st));
-    HB_TRY(hipMemcpyAsync(out.oct_own_off, own_off, 4 * ((size_t)n_nodes + 1), hipMemcpyDeviceToDevice, st));
-    if (n_in) HB_TRY(hipMemcpyAsync(out.oct_own_idx, val_out, 4 * (size_t)n_in, hipMemcpyDeviceToDevice, st));
-    DevFree t3; DevArena A4;
+    HIP_TRY(hipMemcpyAsync(out.oct_box, R.fbox, sizeof(double) * 6 * n_nodes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(out.oct_first_child, R.ffc, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(out.oct_tri_count, R.ftc, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(out.oct_own_off, own_off, 4 * ((size_t)n_nodes + 1), hipMemcpyDeviceToDevice, st));
+    if (n_in) HIP_TRY(hipMemcpyAsync(out.oct_own_idx, val_out, 4 * (size_t)n_in, hipMemcpyDeviceToDevice, st));
+    DevBuf t3; DevArena A4;
     A4.cap = (size_t)(n_cl + 8) * (4 + 24) + (RRT_MAX_SUSPECTS + 2) * sizeof(SuspectOut) + 4096;
-    HB_TRY(hipMalloc(&t3.p, A4.cap)); A4.base = static_cast<char*>(t3.p);
+    t3 = dev_alloc(A4.cap); A4.base = static_cast<char*>(t3.h);
     X.slot_tri = out.slot_tri; X.slot_pos = out.slot_pos; X.cluster_node = A4.take<uint32_t>(n_cl + 8); X.cl_lohi = A4.take<float>(6 * (size_t)(n_cl + 8));
     X.supers = out.supers; X.cboxes = out.cboxes; X.tboxes = out.tboxes; X.child_boxes = out.child_boxes; X.nodes = out.nodes; X.geom = out.geom; X.attr = out.attr;
     lap("hipMalloc scene + temporaries 3, octree copies");
@@ -977,7 +856,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     hipLaunchKernelGGL(k_idx_leaf_slots, dim3(grid_for(n_nodes)), dim3(kBlock), 0, st, X);
     if (attr_task) {                                                   // the records are needed from here on (k_idx_slots, k_suspects)
         attr_task->wait();
-        HB_TRY(hipStreamWaitEvent(st, ev_attr, 0));
+        HIP_TRY(hipStreamWaitEvent(st, ev_attr, 0));
         hipLaunchKernelGGL(k_pack_triangles, dim3(grid_for(n)), dim3(kBlock), 0, st, d_pos, d_uv, d_nrm, d_mat, n, d_tris);
     }
     hipLaunchKernelGGL(k_idx_slots, dim3(grid_for((size_t)n_slots_total + 8)), dim3(kBlock), 0, st, X);
@@ -993,27 +872,27 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     SuspectOut* d_sus = A4.take<SuspectOut>(RRT_MAX_SUSPECTS + 2);
     uint32_t* d_sus_count = X.flags + 3;
     if (enable_cull && n && out.pad > 0) hipLaunchKernelGGL(k_suspects, dim3(grid_for(n)), dim3(kBlock), 0, st, d_tris, S.own, n, origin[0], origin[1], origin[2], out.pad, d_sus_count, d_sus);
-    HB_TRY(hipGetLastError());
-    HB_TRY(hipEventRecord(evs[3], st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(evs[3], st));
     lap("scatter, records, boxes, sweep, suspects");
     read_words(X.flags, 4);
     out.bounds_plain = h_ctr[2] ? 0u : 1u;
     out.n_suspects = h_ctr[3];
     if (out.n_suspects && out.n_suspects <= RRT_MAX_SUSPECTS) {          // deterministic order (by triangle index): the appends above land in any order
         std::vector<SuspectOut> hs(out.n_suspects);
-        HB_TRY(hipMemcpy(hs.data(), d_sus, sizeof(SuspectOut) * hs.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hs.data(), d_sus, sizeof(SuspectOut) * hs.size(), hipMemcpyDeviceToHost));
         std::sort(hs.begin(), hs.end(), [](const SuspectOut& a, const SuspectOut& b) { return a.tri < b.tri; });
         std::vector<DevSuspect> ds(hs.size());
         for (size_t i = 0; i < hs.size(); i++) ds[i] = hs[i].s;
-        HB_TRY(hipMemcpy(out.suspects, ds.data(), sizeof(DevSuspect) * ds.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(out.suspects, ds.data(), sizeof(DevSuspect) * ds.size(), hipMemcpyHostToDevice));
     }
-    HB_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(st));
     float ms = 0;
-    HB_TRY(hipEventElapsedTime(&ms, evs[0], evs[1])); out.ms_upload = ms;
-    HB_TRY(hipEventElapsedTime(&ms, evs[1], evs[2])); out.ms_octree = ms;
-    HB_TRY(hipEventElapsedTime(&ms, evs[2], evs[3])); out.ms_index = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, evs[0], evs[1])); out.ms_upload = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, evs[1], evs[2])); out.ms_octree = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, evs[2], evs[3])); out.ms_index = ms;
     lap("read-backs, suspects");
-    for (DevFree* f : {&t3, &t2, &t1}) { if (f->p) (void)hipFree(f->p); f->p = nullptr; }
+    for (DevBuf* f : {&t3, &t2, &t1}) f->reset();
     lap("hipFree temporaries");
 }
 

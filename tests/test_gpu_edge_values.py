@@ -240,7 +240,7 @@ def test_bump_maps(rrt, ob):
 
 
 def test_bump_map_size_check(rrt):
-    """validate_model (api.cpp): the bump index bump.width * y + x (raytracer.rs:127-128) over every colour texel must stay inside the bump map.  An 8 x 3
+    """validate_tables (api.cpp; validate_model and rrt_raytracer_create_from_arrays both go through it): the bump index bump.width * y + x (raytracer.rs:127-128) over every colour texel must stay inside the bump map.  An 8 x 3
     colour texture addresses up to 4 * 2 + 7 = 15 in a 4-wide bump map: 4 x 4 fits exactly; a 9 x 3 colour texture (index 16) is one texel short."""
     tri = np.array([[[-1, 0, 2], [1, 0, 2], [0, 1, 2]]], np.float64)
     uv = np.zeros((1, 3, 3)); nrm = np.tile([0.0, 0.0, -1.0], (1, 3, 1))
