@@ -102,7 +102,7 @@ typedef struct {
     uint64_t rays_primary;            /* 4 * pixels actually traced */
     uint64_t scene_bytes;             /* bytes resident in HBM for this raytracer (geometry+octree+textures) */
     uint32_t filter_variant;          /* 0 = LANE filter, 1 = BUNDLE filter, 2 = RAY walk (forced, or measured on the first frame of this size) */
-    uint32_t origin_plane_triangles;  /* triangles whose plane contains the raytracer's origin to rounding distance: rays from the origin that lie
+    uint32_t origin_plane_triangles;  /* triangles whose plane contains the raytracer's origin (the current eye, rrt_raytracer_set_camera) to rounding distance: rays from it that lie
                                        * in such a plane run with the index filters off (exactness guard); 0 for ordinary scenes */
     /* The index's exactness band.  filter_pad = absolute padding of every index box (2^-15 of the scene magnitude).  A (ray,
      * triangle) pair can only be treated differently from the reference-order walk if the ray's direction is within alpha of the triangle's plane AND
@@ -164,6 +164,29 @@ int rrt_raytracer_create_from_arrays(uint32_t n_tris, const double *pos, const d
                                      const rrt_light *lights, uint32_t n_lights, rrt_vec3 origin, const rrt_options *opt, int device,
                                      rrt_raytracer **out);
 void rrt_raytracer_destroy(rrt_raytracer *rt);
+
+/* Camera.  The reference looks from RayTracer.origin down +z with y up (main.rs:59-67, engine.rs:207-211); here eye and view basis can be set between frames.
+ * eye = RayTracer.origin; the sub-sample ray through scene point (a, b, c) = (xd*x_scale, yd*y_scale, z_value) of engine.rs:207-236 has direction
+ * right*a + up*b + forward*c, per component k:  d.k = (right.k*a + up.k*b) + forward.k*c  -- five f64 operations, each rounded on its own.  The library
+ * neither normalises nor orthogonalises the basis (the reference's directions are not unit vectors either): a scaled, sheared or mirrored basis is the
+ * caller's business.  Creation pose: eye = origin, right/up/forward = (1,0,0) (0,1,0) (0,0,1): exactly the reference's directions. */
+typedef struct { rrt_vec3 eye, right, up, forward; } rrt_camera;          /* 96 bytes */
+/* Applies to every frame-shaped launch made after it returns (rrt_render, rrt_render_device, rrt_render_tiles_device, rrt_render_progressive and the
+ * rrt_multi_* calls through the raytracers they hold: set the camera on each of them, or on each rank, between rrt_multi_sync and the next enqueue).  The
+ * per-ray entry points keep taking the caller's own rays; their exactness guard is keyed to the current eye.  cam == NULL: back to the creation pose.
+ * RRT_ERR_INVALID_ARG for a NULL rt or a non-finite component (the pose in force stays).
+ * BLOCKING, and it must not overlap frames of this raytracer that are still in flight: frames enqueued with rrt_render_device, rrt_render_tiles_device or
+ * rrt_multi_enqueue must have been synchronised by the caller first (rrt_render and rrt_render_progressive return with nothing in flight).
+ * A new eye costs one pass over the resident triangles on the GPU and one read-back: the exactness guard (rrt_stats.origin_plane_triangles, RRT_BUF_SUSPECTS)
+ * is recomputed for it, with the list a fresh rrt_raytracer_create at that origin would produce; a RRT_FLAG_NO_CULL raytracer has no guard and only stores
+ * the pose.  An eye bit-equal to the current one costs no GPU work and no synchronisation: a pure rotation is free.
+ * The traversal variant measured for a frame size (RRT_FLAG_LANE_FILTER above) is NOT measured again after a camera change. */
+int rrt_raytracer_set_camera(rrt_raytracer *rt, const rrt_camera *cam);
+int rrt_raytracer_get_camera(const rrt_raytracer *rt, rrt_camera *out);
+/* Host only, no GPU.  Left-handed like the reference (x right, y up, z forward): forward = normalised(target - eye), right = normalised(cross(up_hint,
+ * forward)), up = cross(forward, right).  RRT_ERR_INVALID_ARG when target == eye, when up_hint is parallel to the view direction (or zero), or when any
+ * component is non-finite. */
+int rrt_camera_look_at(rrt_vec3 eye, rrt_vec3 target, rrt_vec3 up_hint, rrt_camera *out);
 
 /* Scene::draw_scene (engine.rs:186-255) + Canvas::put_pixel (engine.rs:146-158): fills out_fb[width*height]
  * (host memory), 0x00RRGGBB (entities.rs:32-36), row 0 = top; pixels the reference never writes (row 0, and for

@@ -61,6 +61,10 @@ class COptions(C.Structure):
                 ("vp_w", C.c_double), ("vp_h", C.c_double), ("vp_d", C.c_double)]
 
 
+class CCamera(C.Structure):          # rrt_camera, 96 bytes
+    _fields_ = [("eye", Vec3), ("right", Vec3), ("up", Vec3), ("forward", Vec3)]
+
+
 class CModelInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_tris", "n_tris_in_tree", "n_nodes", "max_depth", "n_mats", "n_tex", "root_own_count", "max_own_count")]
 
@@ -93,6 +97,9 @@ SYMBOLS = {
     "rrt_raytracer_create_from_arrays": (C.c_int, [C.c_uint32, _dp, _dp, _dp, _u32p, C.c_uint32, C.POINTER(CMaterial), C.c_uint32, C.POINTER(CTexture), _dp,
                                                   C.POINTER(CLight), C.c_uint32, Vec3, C.POINTER(COptions), C.c_int, C.POINTER(_P)]),
     "rrt_raytracer_destroy": (None, [_P]),
+    "rrt_raytracer_set_camera": (C.c_int, [_P, C.POINTER(CCamera)]),
+    "rrt_raytracer_get_camera": (C.c_int, [_P, C.POINTER(CCamera)]),
+    "rrt_camera_look_at": (C.c_int, [Vec3, Vec3, Vec3, C.POINTER(CCamera)]),
     "rrt_render": (C.c_int, [_P, C.c_uint32, C.c_uint32, _u32p]),
     "rrt_host_buffer_register": (C.c_int, [_P, C.c_size_t]),
     "rrt_host_buffer_unregister": (C.c_int, [_P]),
@@ -203,6 +210,23 @@ def default_lights() -> list:
 
 DEFAULT_ORIGIN = Vector3d(0.0, 2.0, -10.0)   # src/main.rs:62-66
 DEFAULT_ROOT = (-20.0, 20.0, -20.0, 20.0, -20.0, 20.0)   # src/file_management/utils.rs:145
+
+
+def _vec3(v) -> Vec3:
+    """A Vector3d or any three numbers."""
+    return v._c() if isinstance(v, Vector3d) else Vec3(*map(float, v))
+
+
+def _camera_dict(c: CCamera) -> dict:
+    return {n: (getattr(c, n).x, getattr(c, n).y, getattr(c, n).z) for n, _ in CCamera._fields_}
+
+
+def look_at(eye, target, up=(0.0, 1.0, 0.0)) -> dict:
+    """rrt_camera_look_at (host only): the pose at `eye` looking at `target`, left-handed like the reference (x right, y up, z forward), as a dict
+    eye / right / up / forward of 3-tuples -- RayTracer.set_camera(**look_at(...)) applies it."""
+    c = CCamera()
+    _check(lib().rrt_camera_look_at(_vec3(eye), _vec3(target), _vec3(up), C.byref(c)), "rrt_camera_look_at")
+    return _camera_dict(c)
 
 
 class _Arrays:
@@ -386,6 +410,25 @@ class RayTracer:
         out = np.empty(nb.value, np.uint8)
         _check(lib().rrt_raytracer_get_buffer(self._h, which, out.ctypes.data_as(_P), nb.value, None), "rrt_raytracer_get_buffer")
         return out
+
+    # the camera (rrt.h: rrt_camera).  Blocking; no frame of this raytracer may be in flight.
+    def set_camera(self, eye, right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0)) -> None:
+        """rrt_raytracer_set_camera: frames are taken from `eye`; the ray through scene point (a, b, c) has direction right*a + up*b + forward*c.  A new eye
+        recomputes the exactness guard on the GPU; an unchanged eye (a pure rotation) costs nothing."""
+        c = CCamera(_vec3(eye), _vec3(right), _vec3(up), _vec3(forward))
+        _check(lib().rrt_raytracer_set_camera(self._h, C.byref(c)), "rrt_raytracer_set_camera")
+
+    def look_at(self, eye, target, up=(0.0, 1.0, 0.0)) -> None:
+        self.set_camera(**look_at(eye, target, up))
+
+    def reset_camera(self) -> None:
+        """Back to the creation pose: eye = origin, looking down +z with y up."""
+        _check(lib().rrt_raytracer_set_camera(self._h, None), "rrt_raytracer_set_camera")
+
+    def camera(self) -> dict:
+        c = CCamera()
+        _check(lib().rrt_raytracer_get_camera(self._h, C.byref(c)), "rrt_raytracer_get_camera")
+        return _camera_dict(c)
 
     # raytracer.rs:29, batched
     def get_ray_colours(self, origins, dirs) -> np.ndarray:

@@ -42,6 +42,12 @@ struct rrt_raytracer {
     uint32_t tuned_w = 0, tuned_h = 0, tuned_world = 0;   // frame size the variant below belongs to
     uint32_t size_frames = 0;        // frames rendered at that size so far
     bool size_measured = false;      // ... and whether the variants have been timed on it (second frame of a size)
+    // Camera (rrt_raytracer_set_camera, camera.cpp).  The eye is scene.origin; the basis goes into every FrameParams (frames.cpp: frame_params).
+    rrt_camera cam{};                // pose in force
+    rrt_vec3 origin0{};              // the eye this raytracer was created with (the creation pose)
+    // The exactness guard of an eye other than the creation one: list, counter and search records in an allocation of the raytracer's own, made when the
+    // eye first moves (the build's list is sized for its own finds only).  scene.suspects / scene.n_suspects always describe the eye in force.
+    rrt::DevBuf guard_mem;
 };
 
 namespace rrt {

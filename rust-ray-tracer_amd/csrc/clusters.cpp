@@ -11,6 +11,7 @@
 #include <cfloat>
 #include <cmath>
 #include <numeric>
+#include <utility>
 
 #include "clusters.hpp"
 #include "model.hpp"
@@ -315,9 +316,9 @@ void find_origin_suspects(const Model& m, const double origin[3], double pad, st
     if (!(pad > 0)) return;
     const double eps = 0x1p-53;
     const std::vector<uint32_t>& idx = host_tree(m).own_idx;
-    std::vector<std::vector<DevSuspect>> found(host_threads());
+    std::vector<std::vector<std::pair<uint32_t, DevSuspect>>> found(host_threads());
     parallel_ranges(idx.size(), 1 << 15, [&](size_t ib, size_t ie, size_t part) {
-    std::vector<DevSuspect>& out = found[part];
+    std::vector<std::pair<uint32_t, DevSuspect>>& out = found[part];
     for (size_t ii = ib; ii < ie; ii++) {
         const Triangle& t = m.triangles[idx[ii]];
         const double e1[3] = {t.v2.x - t.v1.x, t.v2.y - t.v1.y, t.v2.z - t.v1.z}, e2[3] = {t.v3.x - t.v1.x, t.v3.y - t.v1.y, t.v3.z - t.v1.z};
@@ -337,10 +338,14 @@ void find_origin_suspects(const Model& m, const double origin[3], double pad, st
         DevSuspect q{};
         for (int k = 0; k < 3; k++) q.n[k] = ln > 0 ? n[k] / ln : 0.0;
         q.alpha2 = alpha >= 1.0 ? 4.0 : alpha * alpha;
-        out.push_back(q);
+        out.emplace_back(idx[ii], q);
     }
     });
-    for (auto& f : found) out.insert(out.end(), f.begin(), f.end());
+    // in push order, like the GPU searches (scene_build.hip): the list of an eye is the same bytes whichever path found it, at creation or after a move
+    std::vector<std::pair<uint32_t, DevSuspect>> all;
+    for (auto& f : found) all.insert(all.end(), f.begin(), f.end());
+    std::sort(all.begin(), all.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    for (auto& f : all) out.push_back(f.second);
 }
 
 }  // namespace rrt

@@ -125,6 +125,9 @@ struct FrameParams {
     // A launch may cover a band of the frame only (progressive display, engine.rs:196-253): the tiles [tile_begin, tile_end) in row-major tile
     // order, and of those only the canvas rows [row_begin, row_end).  The whole frame: tile_begin = 0, tile_end = tiles_x*tiles_y, rows [0, height).
     uint32_t tile_begin, tile_end, row_begin, row_end;
+    // View basis (rrt.h: rrt_camera), behind everything the kernels read before: the sub-sample ray through (a, b, c) = (xd*x_scale, yd*y_scale, z_value) has
+    // direction right*a + up*b + forward*c.  Wave-uniform kernel arguments: they stay in scalar registers until the direction has been formed.
+    double right[3], up[3], forward[3];
 };
 
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
@@ -134,6 +137,11 @@ int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk);
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
                      uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream, int walk);
+// Exactness guard for a new eye (scene_build.hip: k_suspects_resident): searches the resident list slots geom[0, n_list_slots) and appends up to
+// RRT_MAX_SUSPECTS + 1 records {push index, suspect} to d_out, counting every find in *d_count (zeroed here, on `stream`).  Not synchronised.
+struct SuspectRecord { uint32_t tri; uint32_t _pad; DevSuspect s; };
+int launch_suspects_resident(const DevTriGeom* geom, const DevTriAttr* attr, uint32_t n_list_slots, const double eye[3], double pad,
+                             uint32_t* d_count, SuspectRecord* d_out, void* stream);
 uint32_t stack_bytes_per_wave(uint32_t levels);
 void preload_kernels();
 

@@ -20,6 +20,10 @@ FrameParams frame_params(const rrt_raytracer* rt, uint32_t width, uint32_t heigh
     f.tiles_x = (width + 7) / 8; f.tiles_y = (height + 7) / 8;
     f.rank = rank; f.world = world; f.tiled_output = tiled ? 1u : 0u;
     f.tile_begin = 0; f.tile_end = f.tiles_x * f.tiles_y; f.row_begin = 0; f.row_end = height;
+    const rrt_camera& c = rt->cam;                 // rrt_raytracer_set_camera; the eye itself is rt->scene.origin
+    f.right[0] = c.right.x; f.right[1] = c.right.y; f.right[2] = c.right.z;
+    f.up[0] = c.up.x; f.up[1] = c.up.y; f.up[2] = c.up.z;
+    f.forward[0] = c.forward.x; f.forward[1] = c.forward.y; f.forward[2] = c.forward.z;
     // XCD-aware block order (render.hip): worth 2-4 % where the scene is far larger than an XCD's L2 (100 k / 1 M-triangle soups), costs 4 % on the teapot
     // (profiles/r03_xcd_chunk_sweep.txt; chunks as 64 x 64-pixel squares instead of 512 x 8 strips: 1 % slower again): on for scenes of 50 000 triangle slots and more.
     static const int forced = [] { const char* e = std::getenv("RRT_XCD_CHUNK"); return e ? std::atoi(e) : -1; }();
@@ -108,7 +112,7 @@ template <class Launch> int rays_variant(rrt_raytracer* rt, uint32_t n, Launch&&
 // (kernel time of a per-ray launch into rrt_stats, like a frame's)
 void record_rays(rrt_raytracer* rt, uint32_t n, int variant) {
     rt->stats.width = n; rt->stats.height = 1; rt->stats.rays_primary = n;
-    rt->stats.scene_bytes = rt->scene_bytes; rt->stats.filter_variant = (uint32_t)variant; rt->stats.origin_plane_triangles = rt->built.n_suspects;
+    rt->stats.scene_bytes = rt->scene_bytes; rt->stats.filter_variant = (uint32_t)variant; rt->stats.origin_plane_triangles = rt->scene.n_suspects;
     rt->stats_pending = true; rt->launched = true;
 }
 
@@ -118,7 +122,7 @@ void record_launch(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t 
     rt->stats.rays_primary = world == 1 ? 4ull * wt * ht : 0;   // per-rank share is not tracked
     (void)rank;
     rt->stats.scene_bytes = rt->scene_bytes;
-    rt->stats.filter_variant = (uint32_t)rt->walk; rt->stats.origin_plane_triangles = rt->built.n_suspects;
+    rt->stats.filter_variant = (uint32_t)rt->walk; rt->stats.origin_plane_triangles = rt->scene.n_suspects;
     rt->stats_pending = true; rt->launched = true;
 }
 
@@ -343,7 +347,7 @@ int rrt_last_stats(const rrt_raytracer* rt_c, rrt_stats* out) {
             rt->stats_pending = false;
         }
         if (!rt->launched) rt->stats.filter_variant = (uint32_t)rt->walk;   // (before the first launch: the forced variant, or 0)
-        rt->stats.origin_plane_triangles = rt->built.n_suspects; rt->stats.scene_bytes = rt->scene_bytes;
+        rt->stats.origin_plane_triangles = rt->scene.n_suspects; rt->stats.scene_bytes = rt->scene_bytes;
         {   // the exactness band of the index (clusters.cpp: find_origin_suspects has the per-pair formulas)
             const double mag = (double)rt->scene.cull_limit / 4.0, pad = mag / 32768.0, eps = 0x1p-53;
             rt->stats.filter_pad = rt->scene.cull_enabled ? pad : 0.0;

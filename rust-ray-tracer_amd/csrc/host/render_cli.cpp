@@ -1,6 +1,7 @@
 // render_cli.cpp -- the reference's `main` (src/main.rs:17-83) over the C++ host mirror: argv[1] = .obj, hard-coded lights and camera,
 // Scene::new(W,H).draw_scene(rt), "It took ... to draw the scene"; the minifb window loop (main.rs:80-82) is replaced by writing a binary PPM.
-//   render_cli <file.obj> [out.ppm] [width height] [--progressive]     (--progressive: the reference's 50-row chunks with an update after each, engine.rs:196-253)
+//   render_cli <file.obj> [out.ppm] [width height] [--progressive] [eye_x eye_y eye_z target_x target_y target_z]
+// (--progressive: the reference's 50-row chunks with an update after each, engine.rs:196-253; the six trailing numbers: look from eye at target, y up)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +17,13 @@ int main(int argc, char** argv) {
         std::printf("using model file: %s\n", argv[1]);                                                                                   // main.rs:26
         SceneData scene_data = parse_obj_file(argv[1]);
         RayTracer rt(scene_data, default_lights(), default_origin());
+        int first_pose = 5;                                                                                                               // after <obj> <ppm> <w> <h>
+        if (argc > first_pose && std::string(argv[first_pose]) == "--progressive") first_pose++;
+        if (argc >= first_pose + 6) {
+            double p[6];
+            for (int i = 0; i < 6; i++) p[i] = std::atof(argv[first_pose + i]);
+            rt.look_at({p[0], p[1], p[2]}, {p[3], p[4], p[5]});
+        }
         Scene scene(W, H);
         scene.draw_scene(rt);                                                                                                             // first frame: uploads code, tunes the filter
         const auto t0 = std::chrono::steady_clock::now();

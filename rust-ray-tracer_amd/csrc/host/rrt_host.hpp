@@ -71,6 +71,16 @@ public:
         check(rrt_get_ray_colours(rt_, 1, o, d, &c), "get_ray_colour");
         return c;
     }
+    // The camera (rrt.h: rrt_camera): the ray through scene point (a, b, c) has direction right*a + up*b + forward*c.  Blocking; no frame in flight.
+    void set_camera(Vector3d eye, Vector3d right = {1, 0, 0}, Vector3d up = {0, 1, 0}, Vector3d forward = {0, 0, 1}) {
+        const rrt_camera c{{eye.x, eye.y, eye.z}, {right.x, right.y, right.z}, {up.x, up.y, up.z}, {forward.x, forward.y, forward.z}};
+        check(rrt_raytracer_set_camera(rt_, &c), "set_camera");
+    }
+    void look_at(Vector3d eye, Vector3d target, Vector3d up_hint = {0, 1, 0}) {
+        rrt_camera c;
+        check(rrt_camera_look_at({eye.x, eye.y, eye.z}, {target.x, target.y, target.z}, {up_hint.x, up_hint.y, up_hint.z}, &c), "look_at");
+        check(rrt_raytracer_set_camera(rt_, &c), "look_at");
+    }
     rrt_raytracer* handle() const { return rt_; }
     rrt_stats last_stats() const { rrt_stats s; check(rrt_last_stats(rt_, &s), "rrt_last_stats"); return s; }
 private:

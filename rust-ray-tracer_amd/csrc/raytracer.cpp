@@ -169,6 +169,8 @@ int create_raytracer(const rrt_light* lights, uint32_t n_lights, rrt_vec3 origin
     S.n_suspects = G.n_suspects;
     S.n_lights = n_lights; S.max_reflection_depth = o.max_reflection_depth; S.stack_levels = G.max_depth > 1 ? G.max_depth - 1 : 1;   // (stack_levels: only internal nodes push a frame; the deepest level holds leaves)
     S.origin[0] = origin.x; S.origin[1] = origin.y; S.origin[2] = origin.z;
+    rt->origin0 = origin;
+    rt->cam = rrt_camera{origin, {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};   // the reference's view: down +z, y up (engine.rs:207-211)
     S.surface_offset = o.surface_offset;
     for (uint32_t i = 0; i < n_lights; i++) {
         S.lights[i].kind = lights[i].kind; S.lights[i]._pad = 0; S.lights[i].intensity = lights[i].intensity;

@@ -1585,7 +1585,13 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
     const int32_t y = (H - H / 2) - (int32_t)py;
     const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;                      // engine.rs:207-236: sub-samples (x,y),(x+.5,y),(x,y+.5),(x+.5,y+.5)
     const double yd = (sub & 2u) ? ((double)y + 0.5) : (double)y;
-    const V3 dir = mk(xd * F.x_scale, yd * F.y_scale, F.z_value);
+    // The ray through scene point (a, b, c) in the view basis (rrt.h: rrt_camera): right*a + up*b + forward*c, per component two products, a sum, a product,
+    // a sum, each rounded on its own (no fma: the tests restate this order).  With the creation pose (1,0,0) (0,1,0) (0,0,1) these are (a, b, c)
+    // themselves: 1*a == a, 0*b == +-0 and a + +-0 == a.  The basis is wave-uniform (kernel arguments, scalar registers) and dead after these lines.
+    const double sa = xd * F.x_scale, sb = yd * F.y_scale, sc = F.z_value;
+    const V3 dir = mk((F.right[0] * sa + F.up[0] * sb) + F.forward[0] * sc,
+                      (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
+                      (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = __builtin_amdgcn_s_memtime();
     const unsigned long long wave_rt0 = __builtin_amdgcn_s_memrealtime(); (void)wave_rt0;

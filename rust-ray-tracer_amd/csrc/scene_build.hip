@@ -579,34 +579,55 @@ __global__ void __launch_bounds__(kBlock) k_idx_nodes(Idx X, const double* fbox)
     X.nodes[i] = d;
 }
 
-// exactness guard of the index: clusters.cpp find_origin_suspects, per triangle of the tree
-struct SuspectOut { uint32_t tri; uint32_t _pad; DevSuspect s; };
-__global__ void __launch_bounds__(kBlock) k_suspects(const Triangle* tris, const uint32_t* own, uint32_t n, double ox, double oy, double oz, double pad, uint32_t* count, SuspectOut* out) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n || own[i] == kNone) return;
-    const Triangle& t = tris[i];
+// exactness guard of the index: clusters.cpp find_origin_suspects for one triangle (v1 and its two edges) and the eye o.  One body for the search at
+// creation (k_suspects: edges from the triangle array) and the search for a new eye (k_suspects_resident: the same edges as the device records hold them).
+__device__ __forceinline__ bool suspect_of(const double v1[3], const double e1[3], const double e2[3], double ox, double oy, double oz, double pad, DevSuspect& q) {
     const double eps = 0x1p-53;
-    const double e1[3] = {t.v2.x - t.v1.x, t.v2.y - t.v1.y, t.v2.z - t.v1.z}, e2[3] = {t.v3.x - t.v1.x, t.v3.y - t.v1.y, t.v3.z - t.v1.z};
-    const double s[3] = {ox - t.v1.x, oy - t.v1.y, oz - t.v1.z};
+    const double s[3] = {ox - v1[0], oy - v1[1], oz - v1[2]};
     const double nn[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
     const double l1 = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), l2 = sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
     const double ln = sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]), ls = sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
-    if (!(l1 > 0) || !(l2 > 0)) return;
-    if (!isfinite(l1 + l2 + ls)) return;
+    if (!(l1 > 0) || !(l2 > 0)) return false;             // (also a padding slot's all-zero edges, and NaN edges -- canonised or not)
+    if (!isfinite(l1 + l2 + ls)) return false;
     const double R = ls + fmax(l1, l2);
     const double sinphi = ln / (l1 * l2);
     double alpha, delta;
     if (!(sinphi > 1e-300)) { alpha = 2.0; delta = INFINITY; }
     else { alpha = 8.0 * 64.0 * eps * R / (pad * sinphi); delta = 2.0 * (alpha * R + 64.0 * eps * R) / sinphi; }
     const double rho = ln > 0 ? fabs(s[0] * nn[0] + s[1] * nn[1] + s[2] * nn[2]) / ln : 0.0;
-    if (!(rho <= delta)) return;
+    if (!(rho <= delta)) return false;
+    for (int a = 0; a < 3; a++) q.n[a] = ln > 0 ? nn[a] / ln : 0.0;
+    q.alpha2 = alpha >= 1.0 ? 4.0 : alpha * alpha;
+    return true;
+}
+__device__ __forceinline__ void suspect_append(uint32_t tri, const DevSuspect& q, uint32_t* count, SuspectRecord* out) {
     const uint32_t k = atomicAdd(count, 1u);
-    if (k > RRT_MAX_SUSPECTS) return;
-    SuspectOut q{};
-    q.tri = i;
-    for (int a = 0; a < 3; a++) q.s.n[a] = ln > 0 ? nn[a] / ln : 0.0;
-    q.s.alpha2 = alpha >= 1.0 ? 4.0 : alpha * alpha;
-    out[k] = q;
+    if (k > RRT_MAX_SUSPECTS) return;                     // (the count goes on: beyond the cap only it is read)
+    SuspectRecord r{};
+    r.tri = tri; r.s = q;
+    out[k] = r;
+}
+__global__ void __launch_bounds__(kBlock) k_suspects(const Triangle* tris, const uint32_t* own, uint32_t n, double ox, double oy, double oz, double pad, uint32_t* count, SuspectRecord* out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || own[i] == kNone) return;
+    const Triangle& t = tris[i];
+    const double v1[3] = {t.v1.x, t.v1.y, t.v1.z};
+    const double e1[3] = {t.v2.x - t.v1.x, t.v2.y - t.v1.y, t.v2.z - t.v1.z}, e2[3] = {t.v3.x - t.v1.x, t.v3.y - t.v1.y, t.v3.z - t.v1.z};
+    DevSuspect q;
+    if (suspect_of(v1, e1, e2, ox, oy, oz, pad, q)) suspect_append(i, q, count, out);
+}
+// The same search over what stays resident after the build (rrt_raytracer_set_camera: the triangle array is gone): the LIST slots [0, n_list_slots) hold
+// every triangle of the tree exactly once -- the dense slots behind them repeat the triangles of single-triangle leaves and are not visited -- with
+// v1 and the edges k_suspects recomputes (k_idx_slots: the same subtractions, a NaN canonised: skipped either way); a padding slot has all-zero
+// edges and is skipped by the zero-edge test.  The record carries the push index (DevTriAttr::orig), read only for a find.
+__global__ void __launch_bounds__(kBlock) k_suspects_resident(const DevTriGeom* __restrict__ geom, const DevTriAttr* __restrict__ attr, uint32_t n_list_slots,
+                                                              double ox, double oy, double oz, double pad, uint32_t* count, SuspectRecord* out) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_list_slots) return;
+    const DevTriGeom& g = geom[s];
+    const double v1[3] = {g.v1[0], g.v1[1], g.v1[2]}, e1[3] = {g.e1[0], g.e1[1], g.e1[2]}, e2[3] = {g.e2[0], g.e2[1], g.e2[2]};
+    DevSuspect q;
+    if (suspect_of(v1, e1, e2, ox, oy, oz, pad, q)) suspect_append(attr[s].orig, q, count, out);
 }
 
 // the caller's arrays -> Triangle records (rrt_raytracer_create_from_arrays): the layout rrt_model_from_arrays produces on the host
@@ -831,7 +852,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     HIP_TRY(hipMemcpyAsync(out.oct_own_off, own_off, 4 * ((size_t)n_nodes + 1), hipMemcpyDeviceToDevice, st));
     if (n_in) HIP_TRY(hipMemcpyAsync(out.oct_own_idx, val_out, 4 * (size_t)n_in, hipMemcpyDeviceToDevice, st));
     DevBuf t3; DevArena A4;
-    A4.cap = (size_t)(n_cl + 8) * (4 + 24) + (RRT_MAX_SUSPECTS + 2) * sizeof(SuspectOut) + 4096;
+    A4.cap = (size_t)(n_cl + 8) * (4 + 24) + (RRT_MAX_SUSPECTS + 2) * sizeof(SuspectRecord) + 4096;
     t3 = dev_alloc(A4.cap); A4.base = static_cast<char*>(t3.h);
     X.slot_tri = out.slot_tri; X.slot_pos = out.slot_pos; X.cluster_node = A4.take<uint32_t>(n_cl + 8); X.cl_lohi = A4.take<float>(6 * (size_t)(n_cl + 8));
     X.supers = out.supers; X.cboxes = out.cboxes; X.tboxes = out.tboxes; X.child_boxes = out.child_boxes; X.nodes = out.nodes; X.geom = out.geom; X.attr = out.attr;
@@ -869,7 +890,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     hipLaunchKernelGGL(k_idx_nodes, dim3(grid_for(n_nodes)), dim3(kBlock), 0, st, X, R.fbox);
 
     // ---- exactness guard (clusters.cpp: find_origin_suspects)
-    SuspectOut* d_sus = A4.take<SuspectOut>(RRT_MAX_SUSPECTS + 2);
+    SuspectRecord* d_sus = A4.take<SuspectRecord>(RRT_MAX_SUSPECTS + 2);
     uint32_t* d_sus_count = X.flags + 3;
     if (enable_cull && n && out.pad > 0) hipLaunchKernelGGL(k_suspects, dim3(grid_for(n)), dim3(kBlock), 0, st, d_tris, S.own, n, origin[0], origin[1], origin[2], out.pad, d_sus_count, d_sus);
     HIP_TRY(hipGetLastError());
@@ -879,9 +900,9 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     out.bounds_plain = h_ctr[2] ? 0u : 1u;
     out.n_suspects = h_ctr[3];
     if (out.n_suspects && out.n_suspects <= RRT_MAX_SUSPECTS) {          // deterministic order (by triangle index): the appends above land in any order
-        std::vector<SuspectOut> hs(out.n_suspects);
-        HIP_TRY(hipMemcpy(hs.data(), d_sus, sizeof(SuspectOut) * hs.size(), hipMemcpyDeviceToHost));
-        std::sort(hs.begin(), hs.end(), [](const SuspectOut& a, const SuspectOut& b) { return a.tri < b.tri; });
+        std::vector<SuspectRecord> hs(out.n_suspects);
+        HIP_TRY(hipMemcpy(hs.data(), d_sus, sizeof(SuspectRecord) * hs.size(), hipMemcpyDeviceToHost));
+        std::sort(hs.begin(), hs.end(), [](const SuspectRecord& a, const SuspectRecord& b) { return a.tri < b.tri; });
         std::vector<DevSuspect> ds(hs.size());
         for (size_t i = 0; i < hs.size(); i++) ds[i] = hs[i].s;
         HIP_TRY(hipMemcpy(out.suspects, ds.data(), sizeof(DevSuspect) * ds.size(), hipMemcpyHostToDevice));
@@ -894,6 +915,15 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     lap("read-backs, suspects");
     for (DevBuf* f : {&t3, &t2, &t1}) f->reset();
     lap("hipFree temporaries");
+}
+
+int launch_suspects_resident(const DevTriGeom* geom, const DevTriAttr* attr, uint32_t n_list_slots, const double eye[3], double pad, uint32_t* d_count, SuspectRecord* d_out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(d_count, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return (int)e;
+    if (n_list_slots == 0) return 0;
+    hipLaunchKernelGGL(k_suspects_resident, dim3(grid_for(n_list_slots)), dim3(kBlock), 0, st, geom, attr, n_list_slots, eye[0], eye[1], eye[2], pad, d_count, d_out);
+    return (int)hipGetLastError();
 }
 
 }  // namespace rrt

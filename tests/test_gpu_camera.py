@@ -1,0 +1,303 @@
+"""The movable camera (include/rrt.h: rrt_camera, rrt_raytracer_set_camera) on the GPU: frames from a moved and rotated pose against the oracle's
+intersector and shader, against a raytracer created at the new eye, and against the same raytracer's per-ray entry point; the exactness guard of
+the index following the eye.
+
+Direction arithmetic (the contract of rrt.h, restated in `pose_dirs`): the sub-sample ray through scene point (a, b, c) = (xd*x_scale, yd*y_scale, z_value)
+has, per component k,  d.k = (right.k*a + up.k*b) + forward.k*c  -- five f64 operations, each rounded on its own; numpy's elementwise operations
+round each one the same way, so the GPU-against-GPU comparisons below are bit for bit.
+
+Every comparison with the oracle asserts that at least half of the compared pixels have a sub-sample ray the oracle's intersector says hits, so an
+all-background frame cannot pass.  The six poses look at (0, 1, 0) on model2.obj; the oracle's intersector gives 63 % .. 87 % of their primary rays
+hitting at 48 x 48.  ONE place cannot meet that condition as first written: "translation equals re-creation" renders from each eye with the IDENTITY
+basis (that is what a raytracer created at that origin renders), and looking down +z from these eyes the oracle itself sees little or nothing of the
+scene -- pixels with a hit at 48 x 48: (6,3,-8) 13 %, (-7,4,-6) 4 %, (9,2,1) 0 %, (0,9,-4) 0 %, (4,1.5,7) 0 %, (0,2,-6) 70 % -- whatever the code under test
+does.  That test therefore keeps every eye and both of its comparisons in the identity view (bit-equal to the fresh raytracer; within COLOUR_TOL of the
+oracle's frame), and ADDS for every eye the same two comparisons in the view rotated towards the target, where the half-of-the-pixels condition is
+asserted: no eye is left with an all-background check only.
+"""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, channels
+from gpu_checks import (ALL_MODES, FORCED_MODES, MATS, N_THREADS, ORIGIN, POOL, TEX, assert_frame_close, coplanar_rays, oracle_for, plane_scene,
+                        plane_scene_data, row_dirs)
+
+pytestmark = pytest.mark.gpu
+
+TARGET = (0.0, 1.0, 0.0)
+EYES = ((6.0, 3.0, -8.0), (-7.0, 4.0, -6.0), (9.0, 2.0, 1.0), (0.0, 9.0, -4.0), (4.0, 1.5, 7.0), (0.0, 2.0, -6.0))
+IDENTITY = dict(right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0))
+MIN_PIXELS = 512                                   # compared with the oracle per pose, at least
+
+
+def pose_dirs(cam, w, h, rows, xs):
+    """[len(rows), 4, len(xs), 3]: the four sub-sample directions of the pixels (row, x) of a w x h frame in the pose `cam`, in the contract's order."""
+    R, U, F = (np.asarray(cam[k], np.float64) for k in ("right", "up", "forward"))
+    out = np.empty((len(rows), 4, len(xs), 3))
+    for i, r in enumerate(rows):
+        abc = row_dirs(w, h, r, xs)                # (a, b, c) of engine.rs:207-236 with the default viewport: c = 1.0
+        a, b, c = abc[..., 0:1], abc[..., 1:2], abc[..., 2:3]
+        out[i] = (R * a + U * b) + F * c
+    return out
+
+
+def mix4(cols):
+    """Color::mix (entities.rs:49-69) over axis 1 (the four sub-samples): channel sums, truncating / 4 -> packed 0x00RRGGBB."""
+    ch = channels(cols).sum(1) // 4
+    return ((ch[..., 0] << 16) | (ch[..., 1] << 8) | ch[..., 2]).astype(np.uint32)
+
+
+def traced_rows(h):
+    return np.arange(h - 2 * (h // 2) + 1, h)     # rows the reference writes (engine.rs:146-158)
+
+
+def oracle_pixels(osc, cam, w, h, rows, xs, what):
+    """The oracle's pixels (rows, xs) of a w x h frame in the pose `cam`: get_ray_colour of the four sub-sample rays + Color::mix.  Asserts that there are at
+    least MIN_PIXELS of them and that at least half have a sub-sample ray the oracle's intersector says hits."""
+    eye = cam["eye"]
+    d = pose_dirs(cam, w, h, rows, xs)
+    flat = d.reshape(-1, 3)
+    cols = np.fromiter(POOL.map(lambda v: osc.get_ray_colour(eye, v), flat), np.uint32, len(flat)).reshape(d.shape[:3])
+    hits = np.fromiter(POOL.map(lambda v: osc.intersect(eye, v)[0], flat), bool, len(flat)).reshape(d.shape[:3])
+    n_px = len(rows) * len(xs)
+    frac = hits.any(1).mean()
+    print(f"{what}: {n_px} pixels compared, {frac:.3f} of them with a hit, {hits.mean():.3f} of their rays hit")
+    assert n_px >= MIN_PIXELS, f"{what}: {n_px} pixels compared (< {MIN_PIXELS})"
+    assert frac >= 0.5, f"{what}: only {frac:.3f} of the compared pixels have a sub-sample ray that hits (< 0.5)"
+    return mix4(cols)
+
+
+def frame_from_own_rays(rt, cam, w, h):
+    """The frame rebuilt from the raytracer's own per-ray entry point: get_ray_colours(eye, d) of every traced pixel's sub-samples, mixed."""
+    rows, xs = traced_rows(h), np.arange(2 * (w // 2))
+    d = pose_dirs(cam, w, h, rows, xs)
+    cols = rt.get_ray_colours(np.tile(cam["eye"], (d.size // 3, 1)), d.reshape(-1, 3)).reshape(d.shape[:3])
+    fb = np.zeros((h, w), np.uint32)
+    fb[np.ix_(rows, xs)] = mix4(cols)
+    return fb
+
+
+@pytest.fixture(scope="module")
+def teapot_arrays(teapot):
+    pos, uv, nrm, mat = teapot.triangles()
+    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
+
+
+@pytest.fixture(scope="module")
+def teapot_osc(ob, rrt, teapot_arrays):
+    return oracle_for(ob, teapot_arrays, rrt.default_lights())
+
+
+# ------------------------------------------------------------------ 1
+def test_default_pose_is_unchanged(rrt, teapot):
+    """Before any set_camera, after set_camera with the creation pose and after reset_camera(): the same bits, and the golden frames within COLOUR_TOL."""
+    g = np.load(os.path.join(GOLDEN, "model2.npz"))
+    for mode in ALL_MODES:
+        rt = rrt.RayTracer(teapot, rrt.default_lights(), box_filter=mode)
+        assert rt.camera() == dict(eye=ORIGIN, **IDENTITY)
+        for (w, h) in ((64, 48), (97, 61)):
+            before = rt.render(w, h)
+            assert_frame_close(before, g[f"fb_{w}x{h}"], f"walk {mode}, {w}x{h}, golden frame")
+            rt.set_camera(ORIGIN, **IDENTITY)
+            assert np.array_equal(rt.render(w, h), before), (mode, w, h, "set_camera(creation pose)")
+            rt.look_at(EYES[0], TARGET)
+            assert not np.array_equal(rt.render(w, h), before), (mode, w, h, "a moved camera renders another frame")
+            rt.reset_camera()
+            assert rt.camera() == dict(eye=ORIGIN, **IDENTITY)
+            assert np.array_equal(rt.render(w, h), before), (mode, w, h, "reset_camera()")
+
+
+# ------------------------------------------------------------------ 2
+@pytest.mark.parametrize("eye", EYES)
+def test_translation_equals_recreation(rrt, ob, teapot, teapot_arrays, eye):
+    """Created at ORIGIN then moved to `eye` == created at `eye`, bit for bit, at 97 x 61, for the three forced walks and the default; the same frames
+    within COLOUR_TOL of the oracle's frame from that origin.  Then both raytracers turned towards the target: equal again, and against the oracle's
+    per-ray colours with the half-of-the-pixels-hit condition (module docstring: why the identity view cannot carry it)."""
+    w, h = 97, 61
+    lights = rrt.default_lights()
+    osc = oracle_for(ob, teapot_arrays, lights, origin=eye)
+    ref, _ = osc.render(w, h, n_threads=N_THREADS)
+    turned = rrt.look_at(eye, TARGET)
+    rows, xs = traced_rows(h)[::2], np.arange(0, 2 * (w // 2), 3)            # 30 rows x 32 columns = 960 pixels
+    ref_turned = oracle_pixels(osc, turned, w, h, rows, xs, f"eye {eye}, turned to the target")
+    for mode in FORCED_MODES + (None,):
+        moved = rrt.RayTracer(teapot, lights, box_filter=mode)
+        moved.set_camera(eye, **IDENTITY)
+        fresh = rrt.RayTracer(teapot, lights, rrt.Vector3d(*eye), box_filter=mode)
+        got = moved.render(w, h)
+        assert_frame_close(got, fresh.render(w, h), f"eye {eye}, walk {mode}: moved vs created there", tol=0)
+        assert_frame_close(got, ref, f"eye {eye}, walk {mode}: moved vs oracle frame")
+        assert np.array_equal(got == 0, ref == 0)
+        assert moved.last_stats()["origin_plane_triangles"] == fresh.last_stats()["origin_plane_triangles"]
+        moved.set_camera(**turned); fresh.set_camera(**turned)
+        got = moved.render(w, h)
+        assert_frame_close(got, fresh.render(w, h), f"eye {eye}, walk {mode}, turned: moved vs created there", tol=0)
+        assert_frame_close(got[np.ix_(rows, xs)], ref_turned, f"eye {eye}, walk {mode}, turned: moved vs oracle rays")
+
+
+# ------------------------------------------------------------------ 3
+@pytest.mark.parametrize("eye", EYES)
+def test_rotation_against_the_oracle_and_the_per_ray_entry_point(rrt, teapot, teapot_osc, eye):
+    """look_at(eye -> target) at 64 x 48: every second column of every traced row (1504 pixels) against oracle.get_ray_colour + Color::mix within COLOUR_TOL;
+    the whole frame against the same raytracer's get_ray_colours of numpy-built directions, bit for bit, for the three forced walks."""
+    w, h = 64, 48
+    cam = rrt.look_at(eye, TARGET)
+    rows, xs = traced_rows(h), np.arange(0, w, 2)
+    frames = []
+    for mode in FORCED_MODES:
+        rt = rrt.RayTracer(teapot, rrt.default_lights(), box_filter=mode)
+        rt.look_at(eye, TARGET)
+        assert rt.camera() == cam
+        got = rt.render(w, h)
+        own = frame_from_own_rays(rt, cam, w, h)
+        bad = np.argwhere(got != own)
+        assert len(bad) == 0, f"eye {eye}, walk {mode}: {len(bad)} pixels differ from the raytracer's own get_ray_colours (first {bad[:3].tolist()})"
+        frames.append(got)
+    assert np.array_equal(frames[0], frames[1]) and np.array_equal(frames[0], frames[2])
+    assert_frame_close(frames[0][np.ix_(rows, xs)], oracle_pixels(teapot_osc, cam, w, h, rows, xs, f"eye {eye} -> target"), f"eye {eye} -> target: frame vs oracle rays")
+
+
+# ------------------------------------------------------------------ 4
+def test_every_frame_shaped_entry_point_follows_the_camera(rrt, teapot):
+    torch = pytest.importorskip("torch")
+    w, h = 203, 117
+    rt = rrt.RayTracer(teapot, rrt.default_lights())
+    still = rt.render(w, h)
+    rt.look_at(EYES[1], TARGET)
+    full = rt.render(w, h)
+    assert not np.array_equal(full, still)
+    assert np.array_equal(frame_from_own_rays(rt, rt.camera(), w, h), full)
+    assert np.array_equal(rt.render_progressive(w, h, chunk_rows=13), full), "render_progressive"
+    assert np.array_equal(rt.render_registered(w, h), full), "render_registered"
+    fb = torch.empty((h, w), dtype=torch.int32, device="cuda")
+    rt.render_into(fb, w, h)
+    torch.cuda.synchronize()
+    assert np.array_equal(fb.cpu().numpy().view(np.uint32), full), "render_into"
+    world = 3
+    tpr = rrt.tiles_per_rank(w, h, world)
+    gathered = torch.empty((world, tpr * 64), dtype=torch.int32, device="cuda")
+    for r in range(world):
+        rt.render_tiles_into(gathered[r], w, h, r, world)
+    torch.cuda.synchronize()
+    assert np.array_equal(rrt.detile_host(gathered.cpu().numpy().view(np.uint32), w, h, world), full), "tiles, world 3"
+    mg = rrt.MultiGpu([rt], loopback=True)
+    assert np.array_equal(mg.render(w, h), full), "MultiGpu(loopback)"
+    mg.sync()
+    rt.look_at(EYES[4], TARGET)                                              # between rrt_multi_sync and the next frame
+    other = rt.render(w, h)
+    assert not np.array_equal(other, full)
+    assert np.array_equal(mg.render(w, h), other), "MultiGpu(loopback) after another move"
+    del mg
+
+
+# ------------------------------------------------------------------ 5
+APEX = np.array([1.25, 0.75, -3.5])
+
+
+def suspect_scene(n_in_planes):
+    """The scene of test_gpu_build_origin_suspects (tests/test_gpu_build.py) around APEX instead of the creation origin: 2000 random triangles, of which
+    n_in_planes lie in planes through APEX."""
+    rng = np.random.default_rng(11)
+    pos = rng.random((2000, 3, 3)) * 10 - 5
+    for i in range(n_in_planes):
+        a, b = rng.normal(size=3), rng.normal(size=3)
+        c = APEX + a * 3 + b
+        pos[i * 7] = [c, c + a, c + b]
+    n = len(pos)
+    rng2 = np.random.default_rng(n)
+    return pos, rng2.random((n, 3, 3)), rng2.normal(size=(n, 3, 3)), np.zeros(n, np.uint32)
+
+
+def test_the_guard_moves_with_the_eye(rrt):
+    lights = rrt.default_lights()
+    pos, uv, nrm, mat = suspect_scene(40)
+    sd = rrt.SceneData.from_arrays(pos, uv, nrm, mat, MATS, TEX)
+    E = rrt.Vector3d(*APEX)
+    makers = {"default set-up": lambda o: rrt.RayTracer(sd, lights, o),
+              "host set-up": lambda o: rrt.RayTracer(sd, lights, o, host_setup=True),
+              "from arrays": lambda o: rrt.RayTracer.from_arrays(pos, uv, nrm, mat, MATS, TEX, lights, o)}
+    lists = {}
+    for what, make in makers.items():
+        rt = make(rrt.DEFAULT_ORIGIN)
+        n0, b0 = rt.last_stats()["origin_plane_triangles"], rt.buffer("suspects")
+        fresh = make(E)
+        nE, bE = fresh.last_stats()["origin_plane_triangles"], fresh.buffer("suspects")
+        assert 40 <= nE <= 64 and len(bE) == 32 * nE, (what, nE)
+        rt.set_camera(tuple(APEX))
+        assert rt.last_stats()["origin_plane_triangles"] == nE, (what, rt.last_stats()["origin_plane_triangles"], nE)
+        assert np.array_equal(rt.buffer("suspects"), bE), f"{what}: the moved raytracer's suspect list is not the list of one created at the apex"
+        assert np.array_equal(rt.render(64, 48), fresh.render(64, 48)), what
+        assert rt.last_stats()["origin_plane_triangles"] == nE
+        rt.reset_camera()
+        assert rt.last_stats()["origin_plane_triangles"] == n0, (what, "back at the creation origin")
+        assert np.array_equal(rt.buffer("suspects"), b0), f"{what}: back at the creation origin the list differs from the one it was created with"
+        lists[what] = bE
+    assert all(np.array_equal(b, lists["default set-up"]) for b in lists.values()), "the three creation paths give different lists for one eye"
+    # more than RRT_MAX_SUSPECTS such triangles: only the count is kept, every ray from the eye runs unfiltered
+    pos, uv, nrm, mat = suspect_scene(90)
+    sd = rrt.SceneData.from_arrays(pos, uv, nrm, mat, MATS, TEX)
+    rt, fresh, exact = rrt.RayTracer(sd, lights), rrt.RayTracer(sd, lights, E), rrt.RayTracer(sd, lights, E, no_cull=True)
+    rt.set_camera(tuple(APEX))
+    n = rt.last_stats()["origin_plane_triangles"]
+    assert n == fresh.last_stats()["origin_plane_triangles"] >= 90 and len(rt.buffer("suspects")) == 0 == len(fresh.buffer("suspects"))
+    assert np.array_equal(rt.render(96, 72), fresh.render(96, 72)) and np.array_equal(rt.render(96, 72), exact.render(96, 72))
+    rt.reset_camera()
+    assert rt.last_stats()["origin_plane_triangles"] == rrt.RayTracer(sd, lights).last_stats()["origin_plane_triangles"]
+
+
+# ------------------------------------------------------------------ 6
+def test_the_guard_works_after_a_move(rrt):
+    """10^5 rays constructed inside the planes of 60 triangles through an apex E that is not the creation origin: after set_camera(eye=E) every forced
+    walk agrees bit for bit with the reference-order (no_cull) walk, and so does a frame from E along one of the planes."""
+    rng = np.random.default_rng(5)
+    E = np.array([1.5, 1.0, -8.0])
+    lights = rrt.default_lights()
+    tris, planes = plane_scene(rng, E, 6, 10, 3000)
+    sd = plane_scene_data(rrt, tris)
+    N = 100_000
+    O, D = coplanar_rays(rng, tris, planes, 60, E, N)
+    exact_rt = rrt.RayTracer(sd, lights, no_cull=True)
+    exact_rt.set_camera(tuple(E))                                             # (no guard there: only the pose is stored)
+    assert exact_rt.last_stats()["origin_plane_triangles"] == 0
+    exact = exact_rt.intersect_rays(O, D)
+    assert 0.2 < exact[0].mean() <= 1.0
+    for mode in FORCED_MODES:
+        rt = rrt.RayTracer(sd, lights, box_filter=mode)
+        assert rt.last_stats()["origin_plane_triangles"] == 0                 # nothing passes through the creation origin
+        rt.set_camera(tuple(E))
+        assert rt.last_stats()["origin_plane_triangles"] == 60
+        for name, x, y in zip(("hit", "t", "u", "v", "tri"), rt.intersect_rays(O, D), exact):
+            bad = x != y
+            assert not bad.any(), f"walk {mode}: {name} differs from the reference-order walk on {bad.sum()} of {N} rays (first: ray {int(np.argmax(bad))})"
+    d0 = planes[0][0]
+    rt = rrt.RayTracer(sd, lights)
+    rt.look_at(tuple(E), tuple(E + d0)); exact_rt.look_at(tuple(E), tuple(E + d0))
+    got = rt.render(256, 192)
+    assert np.array_equal(got, exact_rt.render(256, 192)), "frame from the apex along a plane: default vs no_cull"
+    print(f"frame from the apex: {(got[1:] != 0xFFFFFF).mean():.3f} of its pixels are not background")
+    assert (got[1:] != 0xFFFFFF).any()                                        # not an all-background frame
+
+
+# ------------------------------------------------------------------ 7
+def test_pure_rotation_leaves_the_guard_alone_and_bad_poses_are_refused(rrt):
+    lights = rrt.default_lights()
+    pos, uv, nrm, mat = suspect_scene(40)
+    rt = rrt.RayTracer(rrt.SceneData.from_arrays(pos, uv, nrm, mat, MATS, TEX), lights)
+    rt.set_camera(tuple(APEX))
+    before = rt.buffer("suspects")
+    assert len(before) >= 40 * 32
+    cam = rrt.look_at(tuple(APEX), TARGET)
+    rt.set_camera(**cam)                                                      # same eye, another basis
+    assert np.array_equal(rt.buffer("suspects"), before) and rt.camera() == cam
+    frame = rt.render(64, 48)
+    nan, inf = float("nan"), float("inf")
+    for bad in (dict(eye=(nan, 0, 0)), dict(eye=(0, 0, inf)), dict(eye=tuple(APEX), right=(1, nan, 0)), dict(eye=tuple(APEX), up=(0, -inf, 0)),
+                dict(eye=(1, 2, 3), forward=(0, 0, nan))):
+        with pytest.raises(rrt.RrtError) as e:
+            rt.set_camera(**bad)
+        assert e.value.status == rrt.ERR_INVALID_ARG
+        assert rt.camera() == cam, "a refused pose must leave the previous one in force"
+    assert np.array_equal(rt.buffer("suspects"), before)
+    assert np.array_equal(rt.render(64, 48), frame)

@@ -19,7 +19,7 @@ for l in out.splitlines():
     if t.startswith("Function Name"):
         if line: print(line)
         name = subprocess.run(["c++filt", t.split(":", 1)[1].strip()], capture_output=True, text=True).stdout.strip()
-        line = name.split("(")[0].replace("rrt::(anonymous namespace)::", "").replace("void ", "") + ": "
+        line = name.replace("rrt::(anonymous namespace)::", "").replace("void ", "").split("(")[0] + ": "
     else:
         k, v = t.split(":", 1)
         if k.strip() in keep: line += k.strip().split(" [")[0] + "=" + v.strip() + "  "
