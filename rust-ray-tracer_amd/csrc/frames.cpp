@@ -349,7 +349,8 @@ int rrt_last_stats(const rrt_raytracer* rt_c, rrt_stats* out) {
         if (!rt->launched) rt->stats.filter_variant = (uint32_t)rt->walk;   // (before the first launch: the forced variant, or 0)
         rt->stats.origin_plane_triangles = rt->scene.n_suspects; rt->stats.scene_bytes = rt->scene_bytes;
         {   // the exactness band of the index (clusters.cpp: find_origin_suspects has the per-pair formulas)
-            const double mag = (double)rt->scene.cull_limit / 4.0, pad = mag / 32768.0, eps = 0x1p-53;
+            // (from the build's own f64 values: cull_limit is their fp32 rounding, and +inf for a scene beyond 2^126)
+            const double mag = rt->built.scene_magnitude, pad = rt->built.pad, eps = 0x1p-53;
             rt->stats.filter_pad = rt->scene.cull_enabled ? pad : 0.0;
             rt->stats.filter_alpha_unit = (rt->scene.cull_enabled && pad > 0) ? 8.0 * 64.0 * eps * mag / pad : 0.0;
             rt->stats.filter_delta_unit = (rt->scene.cull_enabled && pad > 0) ? 2.0 * (rt->stats.filter_alpha_unit * mag + 64.0 * eps * mag) : 0.0;

@@ -304,7 +304,13 @@ __device__ __forceinline__ Ray32 make_ray32(V3 o, V3 d, float limit, float half_
     const float iz = !cull ? 0.0f : (fabsf(dz) < 1e-20f ? 1e30f : __builtin_amdgcn_rcpf(dz)) * sigma;
     Ray32 r;
     r.i01.x = ix; r.i01.y = iy; r.izaz.x = iz; r.izaz.y = fabsf(iz);
-    r.n01.x = -ox * ix; r.n01.y = -oy * iy; r.nz0.x = -oz * iz; r.nz0.y = 0.0f;
+    // (v_mul_legacy_f32: 0 * x = 0 for EVERY x, otherwise the IEEE product.  With the filter off inv is 0 and n has to be 0 too, but an origin beyond fp32's
+    // range converts to +-inf and the IEEE product inf * 0 = NaN made every box a miss for that lane where it has to be a hit.  Same instruction count as
+    // the plain products; selecting n = 0 instead costs three v_cndmask per walk: +0.5 % on the teapot frame, +0.8 % on the 100 k soup, measured)
+    float nx, ny, nz;
+    asm("v_mul_legacy_f32_e64 %0, -%3, %4\n\tv_mul_legacy_f32_e64 %1, -%5, %6\n\tv_mul_legacy_f32_e64 %2, -%7, %8"
+        : "=&v"(nx), "=&v"(ny), "=&v"(nz) : "v"(ox), "v"(ix), "v"(oy), "v"(iy), "v"(oz), "v"(iz));
+    r.n01.x = nx; r.n01.y = ny; r.nz0.x = nz; r.nz0.y = 0.0f;
     r.a01.x = fabsf(ix); r.a01.y = fabsf(iy);
     r.sigma = sigma;
     return r;

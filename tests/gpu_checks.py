@@ -6,7 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from conftest import channels, lights_tuple, oracle_scene_for
+from conftest import channels, lights_tuple
 
 COLOUR_TOL = 1                               # per RGB channel: only pow() (raytracer.rs:295) may differ by an ulp between glibc and OCML
 ALL_MODES = (None, "lane", "bundle", "ray")  # the autotuned default and the three forced walk variants
@@ -117,14 +117,28 @@ def sample_rays(osc, w, h, n_primary, rng, lights):
     return O, D, M
 
 
-def in_noise_band(tris, o, d, pad):
-    """Host restatement of the exactness criterion (clusters.cpp, find_origin_suspects) for ONE ray against every triangle: is the ray's origin within
-    delta of a triangle's plane AND its direction within alpha of parallel to it?  Outside that band the index is provably exact."""
+def noise_band_terms(tris, o, pad):
+    """The origin's part of the exactness criterion (clusters.cpp, find_origin_suspects), per triangle: (n, |n|, alpha, delta, rho) -- the plane normal,
+    the angle and distance thresholds, and the distance of `o` from the plane."""
     e1 = tris[:, 1] - tris[:, 0]; e2 = tris[:, 2] - tris[:, 0]; s = o - tris[:, 0]
     n = np.cross(e1, e2); ln = np.linalg.norm(n, axis=1); l1 = np.linalg.norm(e1, axis=1); l2 = np.linalg.norm(e2, axis=1)
     R = np.linalg.norm(s, axis=1) + np.maximum(l1, l2); sinphi = ln / (l1 * l2); eps = 2.0 ** -53
     alpha = 8 * 64 * eps * R / (pad * sinphi); delta = 2 * (alpha * R + 64 * eps * R) / sinphi
-    rho = np.abs((s * n).sum(1)) / ln; sina = np.abs(n @ d) / (ln * np.linalg.norm(d))
+    rho = np.abs((s * n).sum(1)) / ln
+    return n, ln, alpha, delta, rho
+
+
+def origin_within_delta(tris, o, pad):
+    """Per triangle: does `o` lie within delta of its plane (the origin term of the criterion alone: what makes a triangle a suspect of the eye `o`)?"""
+    _, _, _, delta, rho = noise_band_terms(tris, o, pad)
+    return rho <= delta
+
+
+def in_noise_band(tris, o, d, pad):
+    """Host restatement of the exactness criterion (clusters.cpp, find_origin_suspects) for ONE ray against every triangle: is the ray's origin within
+    delta of a triangle's plane AND its direction within alpha of parallel to it?  Outside that band the index is provably exact."""
+    n, ln, alpha, delta, rho = noise_band_terms(tris, o, pad)
+    sina = np.abs(n @ d) / (ln * np.linalg.norm(d))
     return bool(((rho <= delta) & (sina <= alpha)).any())
 
 
@@ -161,12 +175,12 @@ def coplanar_rays(rng, tris, planes, n_plane_tris, apex, N):
     return np.tile(apex, (N, 1)), D
 
 
-def plane_scene_data(rrt, tris):
+def plane_scene_data(rrt, tris, root=ROOT_BOX):
     """SceneData of plane_scene's triangles: one material, fixed uv and normals."""
     n = len(tris)
     nrm = np.tile([0.0, 0.1, -1.0], (n, 3, 1)); uv = np.tile([[0.1, 0.2, 0], [0.9, 0.1, 0], [0.5, 0.8, 0]], (n, 1, 1)).astype(np.float64)
     mats = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(1, 1, 1), ns=240.0, kr=0.0, tex=0, bump=-1)]
-    return rrt.SceneData.from_arrays(tris, uv, nrm, np.zeros(n, np.uint32), mats, [np.arange(48, dtype=np.uint8).reshape(4, 4, 3)])
+    return rrt.SceneData.from_arrays(tris, uv, nrm, np.zeros(n, np.uint32), mats, [np.arange(48, dtype=np.uint8).reshape(4, 4, 3)], root=root)
 
 
 # ------------------------------------------------------------------ hand-built geometry
@@ -200,7 +214,7 @@ def checker(c0, c1, k=8):
 MATS = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(1, 1, 1), ns=240.0, kr=0.0, tex=0, bump=-1)]
 TEX = [np.full((2, 2, 3), 200, np.uint8)]
 OCT_KEYS = ("aabb", "first_child", "tri_count", "own_off", "own_idx")
-SCENE_BUFS = ("nodes", "geom", "attr", "supers", "cboxes", "child_boxes", "tboxes")
+SCENE_BUFS = ("nodes", "geom", "attr", "supers", "cboxes", "child_boxes", "tboxes", "chains")
 
 
 def scene_from(rrt, pos, root=None):
@@ -225,7 +239,7 @@ def assert_same_buffers(gpu, host, what, rec=32):
         g, h = gpu.buffer(name), host.buffer(name)
         assert g.shape == h.shape, f"{what}: {name} is {g.shape[0]} bytes on the GPU path, {h.shape[0]} on the host path"
         if not np.array_equal(g, h):
-            size = {"nodes": 96, "geom": 80, "attr": 128}.get(name, rec)
+            size = {"nodes": 96, "geom": 80, "attr": 128, "chains": 160}.get(name, rec)
             bad = np.flatnonzero((g.reshape(-1, size) != h.reshape(-1, size)).any(1))
             raise AssertionError(f"{what}: {name} differs in {len(bad)} of {len(g) // size} records, first {bad[:8]};\n gpu  {g.reshape(-1, size)[bad[0]].view(np.uint32)}\n host {h.reshape(-1, size)[bad[0]].view(np.uint32)}")
     ng, nh = gpu.last_stats()["origin_plane_triangles"], host.last_stats()["origin_plane_triangles"]
@@ -236,17 +250,155 @@ def assert_same_buffers(gpu, host, what, rec=32):
 
 
 def check_scene(rrt, sd, what, ob=None, no_cull_too=True, origin=None):
-    """The GPU set-up's octree equals the host build's (and with ob, the oracle's); its scene buffers equal the host set-up's (and without the index)."""
+    """The GPU set-up's octree equals the host build's (and with ob, the oracle's, built on the same root box); its scene buffers equal the host
+    set-up's (and without the index); its index pad is 2^-15 of the root's largest |coordinate|."""
     lights = rrt.default_lights()
     kw = {} if origin is None else {"origin": origin}
     gpu = rrt.RayTracer(sd, lights, **kw)
     tree = gpu.octree()
     assert_same_octree(tree, sd.octree(), what + " (GPU build vs host build)")
     assert tree["info"] == sd.info, f"{what}: info {tree['info']} vs {sd.info}"
+    lo, hi = sd.octree()["aabb"][0, :3], sd.octree()["aabb"][0, 3:]                     # node 0 is the root box the scene was given (min xyz, max xyz)
     if ob is not None:
-        assert_same_octree(tree, oracle_scene_for(ob, rrt, sd, lights).octree(), what + " (GPU build vs oracle build)")
+        pos, uv, nrm, mat = sd.triangles()
+        root = (lo[0], hi[0], lo[1], hi[1], lo[2], hi[2])
+        osc = ob.OracleScene(pos, uv, nrm, mat, sd.materials(), sd.textures(), lights_tuple(lights), (0.0, 2.0, -10.0), root)
+        assert_same_octree(tree, osc.octree(), what + " (GPU build vs oracle build)")
+    pad, want = gpu.last_stats()["filter_pad"], float(np.abs(np.concatenate([lo, hi])).max()) / 32768.0
+    assert pad == want, f"{what}: filter_pad {pad!r}, but 2^-15 of the root's magnitude is {want!r}"
     host = rrt.RayTracer(sd, lights, host_setup=True, **kw)
     assert_same_buffers(gpu, host, what)
     if no_cull_too:
         assert_same_buffers(rrt.RayTracer(sd, lights, no_cull=True, **kw), rrt.RayTracer(sd, lights, no_cull=True, host_setup=True, **kw), what + " [no_cull]")
     return gpu, host
+
+
+# ------------------------------------------------------------------ the hand-built chain scenes (tests/test_gpu_chain_shortcut.py describes them)
+CHAIN_PAD = 20.0 * 2.0 ** -15                             # the index pad of a +-20 root (clusters.cpp: kPadFraction of the scene magnitude)
+CHAIN_CAMERA = (0.0, 2.0, -10.0)
+
+
+class PlainLight:
+    def __init__(self, kind, intensity, v):
+        self.kind, self.intensity, self.v = kind, intensity, self
+        self.x, self.y, self.z = v
+
+
+CHAIN_LIGHTS = [PlainLight(0, 0.3, (0.0, 0.0, 0.0)), PlainLight(1, 0.6, (-4.0, 9.0, -6.0)), PlainLight(2, 0.2, (0.5, 1.0, -1.0))]
+
+
+def rrt_lights_of(rrt, lights):
+    """The package's Light objects of any lights with kind / intensity / v.x, v.y, v.z."""
+    return [rrt.Light(int(l.kind), float(l.intensity), rrt.Vector3d(float(l.v.x), float(l.v.y), float(l.v.z))) for l in lights]
+
+
+def chain_rrt_lights(rrt):
+    return rrt_lights_of(rrt, CHAIN_LIGHTS)
+
+
+CHAIN_ROOT_TRI = [(-15, -15, -15), (-14, -15, -15), (-15, -14, -15)]
+CHAIN_C1 = [(2, 2, 1.5), (3, 2, 1.5), (2, 3, 1.5)]
+CHAIN_C2 = [(7, 7, 7), (8, 7, 7), (7, 8, 7)]
+CHAIN_D_TRIS = {"big": [(1, 1, 3), (4, 1, 3), (1, 4, 3)], "lo": [(1, 1, 2), (2, 1, 2), (1, 2, 2)], "hi": [(3, 3, 3.75), (4, 3, 3.75), (3, 4, 3.75)],
+                "tie": [(2, 2, 1.5), (2.5, 2, 1.5), (2, 2.5, 1.5)], "behind": [(2, 2, 2.25), (3, 2, 2.25), (2, 3, 2.25)],
+                "graze": [(5 - 2.0 ** -20, 1, 3.5), (5 - 2.0 ** -20, 4, 3.5), (3, 1, 3.5)], "lo2": [(0.25, 0.25, 0.5), (0.5, 0.25, 0.5), (0.25, 0.5, 0.5)]}
+
+
+def chain_arrays(tris, scale=1.0, extra=()):
+    pos = np.asarray(list(tris), np.float64) * scale
+    if len(extra): pos = np.concatenate([pos, np.asarray(extra, np.float64)])
+    n = len(pos)
+    rng = np.random.default_rng(n)
+    nrm = np.tile([0.0, 0.1, -1.0], (n, 3, 1)); uv = rng.random((n, 3, 3))
+    mats = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.4, tex=0, bump=-1)]
+    return dict(pos=pos, uv=uv, nrm=nrm, mat=np.zeros(n, np.uint32), materials=mats, textures=[checker((230, 200, 170), (120, 140, 160))], root=ROOT_BOX)
+
+
+def chain_scene(which):
+    """name -> (arrays, names of the triangles).  Push order matters: the first triangle that reaches a node stays in it."""
+    d = list(CHAIN_D_TRIS.items())
+    if which == "main":                       # root <- CHAIN_ROOT_TRI; d1 <- CHAIN_C1; d2 <- CHAIN_C2; D <- the rest
+        names = ["root", "c1", "c2"] + [k for k, _ in d]
+        return chain_arrays([CHAIN_ROOT_TRI, CHAIN_C1, CHAIN_C2] + [t for _, t in d]), names
+    if which == "leaf_end":                   # the chain ends in a leaf that holds one triangle
+        return chain_arrays([CHAIN_ROOT_TRI, CHAIN_C1, CHAIN_C2, CHAIN_D_TRIS["big"]]), ["root", "c1", "c2", "big"]
+    if which == "long_lists":                 # d1 keeps six triangles: five of them straddle its split planes
+        strad = [[(9, 9, 9 + 0.25 * i), (11, 9, 9 + 0.25 * i), (9, 11, 9 + 0.25 * i)] for i in range(5)]
+        names = ["root", "c1"] + ["strad"] * 5 + ["c2"] + [k for k, _ in d]
+        return chain_arrays([CHAIN_ROOT_TRI, CHAIN_C1] + strad + [CHAIN_C2] + [t for _, t in d]), names
+    if which == "non_root_parent":            # the main scene at half size below P = [0,20]^3, whose child [10,20]^3 holds a triangle too
+        names = ["root", "p_own", "other"] + ["c1", "c2"] + [k for k, _ in d]
+        half = lambda t: [tuple(0.5 * c for c in v) for v in t]
+        return chain_arrays([CHAIN_ROOT_TRI, [(9, 9, 12), (11, 9, 12), (9, 11, 12)], [(14, 14, 14), (15, 14, 14), (14, 15, 14)]] + [half(CHAIN_C1), half(CHAIN_C2)] + [half(t) for _, t in d]), names
+    if which == "pokes_out":                  # a triangle that crosses the root's face: no "subtree box inside octant box" argument, no shortcut
+        names = ["root", "c1", "c2"] + [k for k, _ in d] + ["poke"]
+        return chain_arrays([CHAIN_ROOT_TRI, CHAIN_C1, CHAIN_C2] + [t for _, t in d] + [[(19, 1, 1), (21, 1, 1), (19, 2, 1)]]), names
+    raise KeyError(which)
+
+
+def chain_z_rays(xs, ys, z0=-5.0):
+    O = np.array([(x, y, z0) for x in xs for y in ys], np.float64)
+    return O, np.tile([0.0, 0.0, 1.0], (len(O), 1))
+
+
+def chain_main_rays():
+    """name -> (O, D, M).  Dyadic coordinates and axis-parallel directions keep every t exact."""
+    R = {}
+    g = np.arange(2.0625, 3.0, 0.0625)
+    O, D = chain_z_rays(g, g); R["on_c1"] = (O, D, np.full(len(O), np.inf))                                   # case 1: over CHAIN_C1 (and TIE, BEHIND, BIG behind it)
+    O, D = chain_z_rays(np.arange(7.0625, 8.0, 0.125), np.arange(7.0625, 8.0, 0.125)); R["on_c2"] = (O, D, np.full(len(O), np.inf))   # case 2: CHAIN_C2, outside D's subtree box
+    Ob = np.array([(7.25 + 9.0, 7.25, 7.0 - 9.0), (7.5, 7.25 + 6.0, 7.0 - 6.0)]); Db = np.array([(-1.0, 0.0, 1.0), (0.0, -1.0, 1.0)])  # ... and slanted, through the head's box
+    # ... and through an empty corner of D's subtree box first (points P), then into CHAIN_C2: only the triangle-box condition keeps these lanes on the chain
+    P = np.array([(4.5 + 0.03125 * i, 3.875 - 0.03125 * j, 1.0) for i in range(6) for j in range(6)]); T = np.array([(7.25, 7.25, 7.0)]) - P
+    R["on_c2"] = (np.concatenate([R["on_c2"][0], Ob, P - 3.0 * T]), np.concatenate([R["on_c2"][1], Db, T]), np.full(len(O) + 2 + len(P), np.inf))
+    R["through_end"] = (P - 3.0 * T, T, np.full(len(P), np.inf))                                            # (the same rays on their own, for the CPU proof)
+    s = np.array([-1.5, -1.0, -0.75, -0.5, -0.25, 0.0, 0.25, 0.5, 0.75, 1.0, 1.5]) * CHAIN_PAD                # case 3: within a pad of the faces of D's subtree box
+    band = [(5.0 + CHAIN_PAD + e, y, -5.0) for e in s for y in (1.5, 2.5, 3.5)] + [(x, 4.0 + CHAIN_PAD + e, -5.0) for e in s for x in (1.25, 2.0)] + \
+           [(0.25 - CHAIN_PAD + e, y, -5.0) for e in s for y in (0.3, 0.4)]
+    graze = [(x, y, -5.0) for x in (5.0, 5.0 - 2.0 ** -20, 5.0 - 2.0 ** -21, 5.0 - 2.0 ** -19, 5.0 + 2.0 ** -40, 10.0, 10.0 - 2.0 ** -40, 0.0, 2.0 ** -40) for y in np.arange(1.125, 4.0, 0.25)]
+    O = np.array(band + graze); R["band"] = (O, np.tile([0.0, 0.0, 1.0], (len(O), 1)), np.full(len(O), np.inf))
+    O, D = chain_z_rays(np.arange(7.0625, 7.7, 0.125), (7.125, 7.25))                                         # case 4: shadow queries that only CHAIN_C2 can occlude (t = 12)
+    Os = np.concatenate([O, O, P - 3.0 * T, P - 3.0 * T]); Ds = np.concatenate([D, D, T, T])          # (CHAIN_C2 lies at t = 4 of the slanted rays)
+    R["shadow"] = (Os, Ds, np.concatenate([np.full(len(O), 13.0), np.full(len(O), 11.0), np.full(len(P), 5.0), np.full(len(P), 3.5)]))
+    return R
+
+
+# ------------------------------------------------------------------ frames of a posed camera (include/rrt.h: rrt_camera) against the oracle
+MIN_PIXELS = 512                                   # compared with the oracle per pose, at least
+
+
+def pose_dirs(cam, w, h, rows, xs):
+    """[len(rows), 4, len(xs), 3]: the four sub-sample directions of the pixels (row, x) of a w x h frame in the pose `cam`, in the contract's order."""
+    R, U, F = (np.asarray(cam[k], np.float64) for k in ("right", "up", "forward"))
+    out = np.empty((len(rows), 4, len(xs), 3))
+    for i, r in enumerate(rows):
+        abc = row_dirs(w, h, r, xs)                # (a, b, c) of engine.rs:207-236 with the default viewport: c = 1.0
+        a, b, c = abc[..., 0:1], abc[..., 1:2], abc[..., 2:3]
+        out[i] = (R * a + U * b) + F * c
+    return out
+
+
+def mix4(cols):
+    """Color::mix (entities.rs:49-69) over axis 1 (the four sub-samples): channel sums, truncating / 4 -> packed 0x00RRGGBB."""
+    ch = channels(cols).sum(1) // 4
+    return ((ch[..., 0] << 16) | (ch[..., 1] << 8) | ch[..., 2]).astype(np.uint32)
+
+
+def traced_rows(h):
+    return np.arange(h - 2 * (h // 2) + 1, h)     # rows the reference writes (engine.rs:146-158)
+
+
+def oracle_pixels(osc, cam, w, h, rows, xs, what):
+    """The oracle's pixels (rows, xs) of a w x h frame in the pose `cam`: get_ray_colour of the four sub-sample rays + Color::mix.  Asserts that there are at
+    least MIN_PIXELS of them and that at least half have a sub-sample ray the oracle's intersector says hits."""
+    eye = cam["eye"]
+    d = pose_dirs(cam, w, h, rows, xs)
+    flat = d.reshape(-1, 3)
+    cols = np.fromiter(POOL.map(lambda v: osc.get_ray_colour(eye, v), flat), np.uint32, len(flat)).reshape(d.shape[:3])
+    hits = np.fromiter(POOL.map(lambda v: osc.intersect(eye, v)[0], flat), bool, len(flat)).reshape(d.shape[:3])
+    n_px = len(rows) * len(xs)
+    frac = hits.any(1).mean()
+    print(f"{what}: {n_px} pixels compared, {frac:.3f} of them with a hit, {hits.mean():.3f} of their rays hit")
+    assert n_px >= MIN_PIXELS, f"{what}: {n_px} pixels compared (< {MIN_PIXELS})"
+    assert frac >= 0.5, f"{what}: only {frac:.3f} of the compared pixels have a sub-sample ray that hits (< 0.5)"
+    return mix4(cols)

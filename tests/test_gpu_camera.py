@@ -20,53 +20,15 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, channels
-from gpu_checks import (ALL_MODES, FORCED_MODES, MATS, N_THREADS, ORIGIN, POOL, TEX, assert_frame_close, coplanar_rays, oracle_for, plane_scene,
-                        plane_scene_data, row_dirs)
+from conftest import GOLDEN
+from gpu_checks import (ALL_MODES, FORCED_MODES, MATS, N_THREADS, ORIGIN, TEX, assert_frame_close, coplanar_rays, mix4, oracle_for, oracle_pixels, plane_scene,
+                        plane_scene_data, pose_dirs, traced_rows)
 
 pytestmark = pytest.mark.gpu
 
 TARGET = (0.0, 1.0, 0.0)
 EYES = ((6.0, 3.0, -8.0), (-7.0, 4.0, -6.0), (9.0, 2.0, 1.0), (0.0, 9.0, -4.0), (4.0, 1.5, 7.0), (0.0, 2.0, -6.0))
 IDENTITY = dict(right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0))
-MIN_PIXELS = 512                                   # compared with the oracle per pose, at least
-
-
-def pose_dirs(cam, w, h, rows, xs):
-    """[len(rows), 4, len(xs), 3]: the four sub-sample directions of the pixels (row, x) of a w x h frame in the pose `cam`, in the contract's order."""
-    R, U, F = (np.asarray(cam[k], np.float64) for k in ("right", "up", "forward"))
-    out = np.empty((len(rows), 4, len(xs), 3))
-    for i, r in enumerate(rows):
-        abc = row_dirs(w, h, r, xs)                # (a, b, c) of engine.rs:207-236 with the default viewport: c = 1.0
-        a, b, c = abc[..., 0:1], abc[..., 1:2], abc[..., 2:3]
-        out[i] = (R * a + U * b) + F * c
-    return out
-
-
-def mix4(cols):
-    """Color::mix (entities.rs:49-69) over axis 1 (the four sub-samples): channel sums, truncating / 4 -> packed 0x00RRGGBB."""
-    ch = channels(cols).sum(1) // 4
-    return ((ch[..., 0] << 16) | (ch[..., 1] << 8) | ch[..., 2]).astype(np.uint32)
-
-
-def traced_rows(h):
-    return np.arange(h - 2 * (h // 2) + 1, h)     # rows the reference writes (engine.rs:146-158)
-
-
-def oracle_pixels(osc, cam, w, h, rows, xs, what):
-    """The oracle's pixels (rows, xs) of a w x h frame in the pose `cam`: get_ray_colour of the four sub-sample rays + Color::mix.  Asserts that there are at
-    least MIN_PIXELS of them and that at least half have a sub-sample ray the oracle's intersector says hits."""
-    eye = cam["eye"]
-    d = pose_dirs(cam, w, h, rows, xs)
-    flat = d.reshape(-1, 3)
-    cols = np.fromiter(POOL.map(lambda v: osc.get_ray_colour(eye, v), flat), np.uint32, len(flat)).reshape(d.shape[:3])
-    hits = np.fromiter(POOL.map(lambda v: osc.intersect(eye, v)[0], flat), bool, len(flat)).reshape(d.shape[:3])
-    n_px = len(rows) * len(xs)
-    frac = hits.any(1).mean()
-    print(f"{what}: {n_px} pixels compared, {frac:.3f} of them with a hit, {hits.mean():.3f} of their rays hit")
-    assert n_px >= MIN_PIXELS, f"{what}: {n_px} pixels compared (< {MIN_PIXELS})"
-    assert frac >= 0.5, f"{what}: only {frac:.3f} of the compared pixels have a sub-sample ray that hits (< 0.5)"
-    return mix4(cols)
 
 
 def frame_from_own_rays(rt, cam, w, h):

@@ -29,26 +29,13 @@ import numpy as np
 import pytest
 
 from conftest import ASSETS
-from gpu_checks import COLOUR_TOL, FORCED_MODES, N_THREADS, ROOT_BOX, assert_frame_close, assert_rays_match_oracle, checker, oracle_for
+from gpu_checks import (CHAIN_CAMERA as CAMERA, CHAIN_D_TRIS as D_TRIS, CHAIN_LIGHTS as LIGHTS, CHAIN_PAD as PAD, COLOUR_TOL, FORCED_MODES, N_THREADS,
+                        ROOT_BOX, assert_frame_close, assert_rays_match_oracle, chain_main_rays as _main_rays, chain_rrt_lights as _rrt_lights,
+                        chain_scene as _scene, chain_z_rays as _z_rays, checker, oracle_for)
 
 EPS = 2.220446049250313e-16
 K = 4                                                     # kChainMaxTris, device_scene.hpp
-PAD = 20.0 * 2.0 ** -15                                   # the index pad of a +-20 root (clusters.cpp: kPadFraction of the scene magnitude)
-CAMERA = (0.0, 2.0, -10.0)
 NAN, INF = float("nan"), float("inf")
-
-
-class _Light:
-    def __init__(self, kind, intensity, v):
-        self.kind, self.intensity, self.v = kind, intensity, self
-        self.x, self.y, self.z = v
-
-
-LIGHTS = [_Light(0, 0.3, (0.0, 0.0, 0.0)), _Light(1, 0.6, (-4.0, 9.0, -6.0)), _Light(2, 0.2, (0.5, 1.0, -1.0))]
-
-
-def _rrt_lights(rrt):
-    return [rrt.Light.Ambient(0.3), rrt.Light.Point(0.6, rrt.Vector3d(-4.0, 9.0, -6.0)), rrt.Light.Directional(0.2, rrt.Vector3d(0.5, 1.0, -1.0))]
 
 
 # ------------------------------------------------------------------ chains of an octree, by the definition
@@ -94,72 +81,7 @@ def brute_force(pos, o, d):
     return np.where(ok, t, np.nan)
 
 
-# ------------------------------------------------------------------ the hand-built scenes
-ROOT_TRI = [(-15, -15, -15), (-14, -15, -15), (-15, -14, -15)]
-C1 = [(2, 2, 1.5), (3, 2, 1.5), (2, 3, 1.5)]
-C2 = [(7, 7, 7), (8, 7, 7), (7, 8, 7)]
-D_TRIS = {"big": [(1, 1, 3), (4, 1, 3), (1, 4, 3)], "lo": [(1, 1, 2), (2, 1, 2), (1, 2, 2)], "hi": [(3, 3, 3.75), (4, 3, 3.75), (3, 4, 3.75)],
-          "tie": [(2, 2, 1.5), (2.5, 2, 1.5), (2, 2.5, 1.5)], "behind": [(2, 2, 2.25), (3, 2, 2.25), (2, 3, 2.25)],
-          "graze": [(5 - 2.0 ** -20, 1, 3.5), (5 - 2.0 ** -20, 4, 3.5), (3, 1, 3.5)], "lo2": [(0.25, 0.25, 0.5), (0.5, 0.25, 0.5), (0.25, 0.5, 0.5)]}
-
-
-def _arrays(tris, scale=1.0, extra=()):
-    pos = np.asarray(list(tris), np.float64) * scale
-    if len(extra): pos = np.concatenate([pos, np.asarray(extra, np.float64)])
-    n = len(pos)
-    rng = np.random.default_rng(n)
-    nrm = np.tile([0.0, 0.1, -1.0], (n, 3, 1)); uv = rng.random((n, 3, 3))
-    mats = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.4, tex=0, bump=-1)]
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=np.zeros(n, np.uint32), materials=mats, textures=[checker((230, 200, 170), (120, 140, 160))], root=ROOT_BOX)
-
-
-def _scene(which):
-    """name -> (arrays, names of the triangles).  Push order matters: the first triangle that reaches a node stays in it."""
-    d = list(D_TRIS.items())
-    if which == "main":                       # root <- ROOT_TRI; d1 <- C1; d2 <- C2; D <- the rest
-        names = ["root", "c1", "c2"] + [k for k, _ in d]
-        return _arrays([ROOT_TRI, C1, C2] + [t for _, t in d]), names
-    if which == "leaf_end":                   # the chain ends in a leaf that holds one triangle
-        return _arrays([ROOT_TRI, C1, C2, D_TRIS["big"]]), ["root", "c1", "c2", "big"]
-    if which == "long_lists":                 # d1 keeps six triangles: five of them straddle its split planes
-        strad = [[(9, 9, 9 + 0.25 * i), (11, 9, 9 + 0.25 * i), (9, 11, 9 + 0.25 * i)] for i in range(5)]
-        names = ["root", "c1"] + ["strad"] * 5 + ["c2"] + [k for k, _ in d]
-        return _arrays([ROOT_TRI, C1] + strad + [C2] + [t for _, t in d]), names
-    if which == "non_root_parent":            # the main scene at half size below P = [0,20]^3, whose child [10,20]^3 holds a triangle too
-        names = ["root", "p_own", "other"] + ["c1", "c2"] + [k for k, _ in d]
-        half = lambda t: [tuple(0.5 * c for c in v) for v in t]
-        return _arrays([ROOT_TRI, [(9, 9, 12), (11, 9, 12), (9, 11, 12)], [(14, 14, 14), (15, 14, 14), (14, 15, 14)]] + [half(C1), half(C2)] + [half(t) for _, t in d]), names
-    if which == "pokes_out":                  # a triangle that crosses the root's face: no "subtree box inside octant box" argument, no shortcut
-        names = ["root", "c1", "c2"] + [k for k, _ in d] + ["poke"]
-        return _arrays([ROOT_TRI, C1, C2] + [t for _, t in d] + [[(19, 1, 1), (21, 1, 1), (19, 2, 1)]]), names
-    raise KeyError(which)
-
-
-def _z_rays(xs, ys, z0=-5.0):
-    O = np.array([(x, y, z0) for x in xs for y in ys], np.float64)
-    return O, np.tile([0.0, 0.0, 1.0], (len(O), 1))
-
-
-def _main_rays():
-    """name -> (O, D, M).  Dyadic coordinates and axis-parallel directions keep every t exact."""
-    R = {}
-    g = np.arange(2.0625, 3.0, 0.0625)
-    O, D = _z_rays(g, g); R["on_c1"] = (O, D, np.full(len(O), INF))                                   # case 1: over C1 (and TIE, BEHIND, BIG behind it)
-    O, D = _z_rays(np.arange(7.0625, 8.0, 0.125), np.arange(7.0625, 8.0, 0.125)); R["on_c2"] = (O, D, np.full(len(O), INF))   # case 2: C2, outside D's subtree box
-    Ob = np.array([(7.25 + 9.0, 7.25, 7.0 - 9.0), (7.5, 7.25 + 6.0, 7.0 - 6.0)]); Db = np.array([(-1.0, 0.0, 1.0), (0.0, -1.0, 1.0)])  # ... and slanted, through the head's box
-    # ... and through an empty corner of D's subtree box first (points P), then into C2: only the triangle-box condition keeps these lanes on the chain
-    P = np.array([(4.5 + 0.03125 * i, 3.875 - 0.03125 * j, 1.0) for i in range(6) for j in range(6)]); T = np.array([(7.25, 7.25, 7.0)]) - P
-    R["on_c2"] = (np.concatenate([R["on_c2"][0], Ob, P - 3.0 * T]), np.concatenate([R["on_c2"][1], Db, T]), np.full(len(O) + 2 + len(P), INF))
-    R["through_end"] = (P - 3.0 * T, T, np.full(len(P), INF))                                            # (the same rays on their own, for the CPU proof)
-    s = np.array([-1.5, -1.0, -0.75, -0.5, -0.25, 0.0, 0.25, 0.5, 0.75, 1.0, 1.5]) * PAD                # case 3: within a pad of the faces of D's subtree box
-    band = [(5.0 + PAD + e, y, -5.0) for e in s for y in (1.5, 2.5, 3.5)] + [(x, 4.0 + PAD + e, -5.0) for e in s for x in (1.25, 2.0)] + \
-           [(0.25 - PAD + e, y, -5.0) for e in s for y in (0.3, 0.4)]
-    graze = [(x, y, -5.0) for x in (5.0, 5.0 - 2.0 ** -20, 5.0 - 2.0 ** -21, 5.0 - 2.0 ** -19, 5.0 + 2.0 ** -40, 10.0, 10.0 - 2.0 ** -40, 0.0, 2.0 ** -40) for y in np.arange(1.125, 4.0, 0.25)]
-    O = np.array(band + graze); R["band"] = (O, np.tile([0.0, 0.0, 1.0], (len(O), 1)), np.full(len(O), INF))
-    O, D = _z_rays(np.arange(7.0625, 7.7, 0.125), (7.125, 7.25))                                         # case 4: shadow queries that only C2 can occlude (t = 12)
-    Os = np.concatenate([O, O, P - 3.0 * T, P - 3.0 * T]); Ds = np.concatenate([D, D, T, T])          # (C2 lies at t = 4 of the slanted rays)
-    R["shadow"] = (Os, Ds, np.concatenate([np.full(len(O), 13.0), np.full(len(O), 11.0), np.full(len(P), 5.0), np.full(len(P), 3.5)]))
-    return R
+# ------------------------------------------------------------------ the hand-built scenes: gpu_checks.py (chain_scene, chain_main_rays)
 
 
 def _edge_rays():
