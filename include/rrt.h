@@ -171,12 +171,13 @@ void rrt_raytracer_destroy(rrt_raytracer *rt);
  * neither normalises nor orthogonalises the basis (the reference's directions are not unit vectors either): a scaled, sheared or mirrored basis is the
  * caller's business.  Creation pose: eye = origin, right/up/forward = (1,0,0) (0,1,0) (0,0,1): exactly the reference's directions. */
 typedef struct { rrt_vec3 eye, right, up, forward; } rrt_camera;          /* 96 bytes */
-/* Applies to every frame-shaped launch made after it returns (rrt_render, rrt_render_device, rrt_render_tiles_device, rrt_render_progressive and the
+/* Applies to every frame-shaped launch made after it returns (rrt_render, rrt_render_device, rrt_render_tiles_device, rrt_render_progressive, the visibility calls and the
  * rrt_multi_* calls through the raytracers they hold: set the camera on each of them, or on each rank, between rrt_multi_sync and the next enqueue).  The
  * per-ray entry points keep taking the caller's own rays; their exactness guard is keyed to the current eye.  cam == NULL: back to the creation pose.
  * RRT_ERR_INVALID_ARG for a NULL rt or a non-finite component (the pose in force stays).
- * BLOCKING, and it must not overlap frames of this raytracer that are still in flight: frames enqueued with rrt_render_device, rrt_render_tiles_device or
- * rrt_multi_enqueue must have been synchronised by the caller first (rrt_render and rrt_render_progressive return with nothing in flight).
+ * BLOCKING, and it must not overlap frames of this raytracer that are still in flight: frames enqueued with rrt_render_device, rrt_render_tiles_device,
+ * rrt_render_visibility_device or rrt_multi_enqueue must have been synchronised by the caller first (rrt_render, rrt_render_progressive, rrt_render_visibility
+ * and rrt_pick return with nothing in flight).
  * A new eye costs one pass over the resident triangles on the GPU and one read-back: the exactness guard (rrt_stats.origin_plane_triangles, RRT_BUF_SUSPECTS)
  * is recomputed for it, with the list a fresh rrt_raytracer_create at that origin would produce; a RRT_FLAG_NO_CULL raytracer has no guard and only stores
  * the pose.  An eye bit-equal to the current one costs no GPU work and no synchronisation: a pure rotation is free.
@@ -201,6 +202,35 @@ int rrt_host_buffer_unregister(void *ptr);
 
 /* Same, framebuffer in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default), not synchronised. */
 int rrt_render_device(rrt_raytracer *rt, uint32_t width, uint32_t height, void *d_fb, void *stream);
+
+/* Visibility buffers: the first-hit geometry of a frame's primary rays, which the frame kernels compute on the way to a colour and do not keep.  For
+ * picking, selection and snapping (what is under this pixel), depth compositing, edge detection on triangle ids, a denoiser's albedo.
+ * The ray of canvas pixel (px, py), sub-sample s is exactly the one a frame traces for it in the current pose (rrt_camera above; the vp_* options apply).
+ * Per ray:  hit, t, u, v, tri = what rrt_intersect_rays returns for that origin and direction with max_t = NULL, its miss convention included (hit 0,
+ * t = u = v = 0.0, tri = 0xFFFFFFFF);  albedo = the colour-texture texel the reference samples at the hit (raytracer.rs:43-55), 0x00RRGGBB, before lighting
+ * and without the bump map; a miss gives 0x00FFFFFF, the reference's background.  Pixels the reference never traces (canvas row 0, row 1 for odd heights,
+ * the last column for odd widths) are written as hit 0, t = u = v = 0.0, tri = 0xFFFFFFFF, albedo 0: every element of every requested plane inside the
+ * region is written, the caller need not clear anything.
+ * One launch of one walk per ray, in the traversal variant a flag forces, else the one kept for this frame size, else the first-frame rule's choice for it
+ * (RRT_FLAG_LANE_FILTER above).  These calls do not count as frames of that size: they never trigger the measurement and leave the kept variant alone.
+ * rrt_last_stats afterwards: kernel_ms and filter_variant of this launch, width / height = the frame size, rays_primary = 4 * the traced pixels inside the region.
+ * RRT_ERR_INVALID_ARG, before any GPU work: NULL rt or planes struct, all six plane pointers NULL, a bad frame size, a region with w == 0 or h == 0 or one
+ * that sticks out of the frame; rrt_pick: px >= width, py >= height or out == NULL.
+ * Not covered: the rank/world tile partition, the rrt_multi_* path and the progressive path.  A multi-GPU host splits the frame with regions. */
+/* A rectangle of canvas pixels: columns [x0, x0+w), rows [y0, y0+h), row 0 = top.  NULL where a region is taken = the whole frame. */
+typedef struct { uint32_t x0, y0, w, h; } rrt_region;                       /* 16 bytes */
+/* Output planes of a visibility frame, each [region.h][region.w][4], row-major.  The last index is the sub-sample in the order of
+ * engine.rs:207-236: (x,y), (x+.5,y), (x,y+.5), (x+.5,y+.5).  Any pointer may be NULL (that plane is not written), but at least one is set. */
+typedef struct { uint8_t *hit; double *t, *u, *v; uint32_t *tri; uint32_t *albedo; } rrt_visibility;   /* 48 bytes */
+/* Planes in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default), not synchronised. */
+int rrt_render_visibility_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                                 const rrt_visibility *d_planes, void *stream);
+/* Planes in host memory; blocking.  Only the requested planes are downloaded (from one device allocation kept between calls). */
+int rrt_render_visibility(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                          const rrt_visibility *planes);
+typedef struct { uint32_t hit, tri; double t, u, v; uint32_t albedo, _pad; } rrt_pick_result;           /* 40 bytes */
+/* Sub-sample 0 of canvas pixel (px, py) of a width x height frame in the current pose: one tile's launch.  Blocking. */
+int rrt_pick(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t px, uint32_t py, rrt_pick_result *out);
 
 /* Screen-tile partition for N GPUs (one process per GPU): the frame is cut into 8x8-pixel tiles, tile k (row-major)
  * belongs to rank k % world.  Renders this rank's tiles into d_tiles[rrt_tiles_per_rank][64] (tile-major, device).

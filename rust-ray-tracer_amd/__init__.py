@@ -65,6 +65,22 @@ class CCamera(C.Structure):          # rrt_camera, 96 bytes
     _fields_ = [("eye", Vec3), ("right", Vec3), ("up", Vec3), ("forward", Vec3)]
 
 
+class CRegion(C.Structure):          # rrt_region, 16 bytes
+    _fields_ = [(n, C.c_uint32) for n in ("x0", "y0", "w", "h")]
+
+
+class CVisibility(C.Structure):      # rrt_visibility, 48 bytes: host or device pointers, NULL = plane not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("hit", "t", "u", "v", "tri", "albedo")]
+
+
+class CPickResult(C.Structure):      # rrt_pick_result, 40 bytes
+    _fields_ = [("hit", C.c_uint32), ("tri", C.c_uint32), ("t", C.c_double), ("u", C.c_double), ("v", C.c_double), ("albedo", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+PLANES = ("hit", "t", "u", "v", "tri", "albedo")   # the planes of rrt_visibility, in its order
+PLANE_DTYPES = dict(hit=np.uint8, t=np.float64, u=np.float64, v=np.float64, tri=np.uint32, albedo=np.uint32)
+
+
 class CModelInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_tris", "n_tris_in_tree", "n_nodes", "max_depth", "n_mats", "n_tex", "root_own_count", "max_own_count")]
 
@@ -104,6 +120,9 @@ SYMBOLS = {
     "rrt_host_buffer_register": (C.c_int, [_P, C.c_size_t]),
     "rrt_host_buffer_unregister": (C.c_int, [_P]),
     "rrt_render_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "rrt_render_visibility_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), _P]),
+    "rrt_render_visibility": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility)]),
+    "rrt_pick": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CPickResult)]),
     "rrt_tiles_per_rank": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rrt_render_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
     "rrt_detile_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P]),
@@ -480,6 +499,31 @@ class RayTracer:
         assert gathered_tensor.numel() == tiles_per_rank(width, height, world) * 64 * world and fb_tensor.numel() == width * height
         _check(lib().rrt_detile_device(self._h, width, height, world, _P(gathered_tensor.data_ptr()), _P(fb_tensor.data_ptr()), _P(_stream(stream))),
                "rrt_detile_device")
+
+    # visibility buffers (rrt.h: rrt_render_visibility): first-hit geometry of the frame's primary rays.  region = (x0, y0, w, h) in canvas pixels, None = the frame
+    def visibility(self, width: int, height: int, region=None, planes=PLANES) -> dict:
+        """rrt_render_visibility: {plane: array [h][w][4]} of the region (last index: the sub-sample), only the planes asked for.  hit uint8, t / u / v
+        float64, tri uint32 (push order, 0xFFFFFFFF = miss), albedo uint32 0x00RRGGBB."""
+        h, w = (height, width) if region is None else (int(region[3]), int(region[2]))
+        out = {n: np.empty((h, w, 4), PLANE_DTYPES[n]) for n in planes}
+        cv = CVisibility(**{n: a.ctypes.data for n, a in out.items()})
+        _check(lib().rrt_render_visibility(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv)), "rrt_render_visibility")
+        return out
+
+    def visibility_into(self, tensors: dict, width: int, height: int, region=None, stream: Optional[int] = None):
+        """rrt_render_visibility_device: tensors = {plane: contiguous device tensor of 4*w*h elements of the plane's size}; enqueued, not synchronised."""
+        n = 4 * (width * height if region is None else int(region[2]) * int(region[3]))
+        for name, t in tensors.items():
+            assert t.is_cuda and t.is_contiguous() and t.numel() == n and t.element_size() == np.dtype(PLANE_DTYPES[name]).itemsize, name
+        cv = CVisibility(**{name: t.data_ptr() for name, t in tensors.items()})
+        _check(lib().rrt_render_visibility_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv),
+                                                  _P(_stream(stream))), "rrt_render_visibility_device")
+
+    def pick(self, width: int, height: int, px: int, py: int) -> dict:
+        """rrt_pick: what sub-sample 0 of canvas pixel (px, py) sees: dict hit (bool), tri, t, u, v, albedo."""
+        r = CPickResult()
+        _check(lib().rrt_pick(self._h, width, height, px, py, C.byref(r)), "rrt_pick")
+        return dict(hit=bool(r.hit), tri=r.tri, t=r.t, u=r.u, v=r.v, albedo=r.albedo)
 
     # pre-bound launchers for per-frame loops (bench.py): all argument conversion is done once, the returned callable is one ctypes call
     def bind_render(self, fb_tensor, width: int, height: int, stream: Optional[int] = None):

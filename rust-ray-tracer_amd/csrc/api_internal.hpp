@@ -34,6 +34,8 @@ struct rrt_raytracer {
     bool variant_forced = false;
     rrt::DevBuf host_fb;             // device framebuffer kept between rrt_render calls (host-buffer entry point)
     size_t host_fb_bytes = 0;
+    rrt::DevBuf vis_buf;             // device planes kept between rrt_render_visibility / rrt_pick calls (host-pointer entry points)
+    size_t vis_buf_bytes = 0;
     uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records in use (built.n_chains, or 0 where the shortcut's precondition fails: create_raytracer)
     double upload_ms = 0, hip_init_ms = 0, create_ms = 0;   // set-up stages of rrt_raytracer_create besides built.ms_octree / ms_index; wall time of the whole call
     bool gpu_setup = false;          // scene built on the device (default) or on the host (RRT_FLAG_HOST_SETUP)
@@ -83,6 +85,9 @@ inline Box default_root(const double* root) {
     else for (int k = 0; k < 3; k++) { b.lo[k] = -20.0; b.hi[k] = 20.0; }   // utils.rs:145
     return b;
 }
+
+// The visibility planes of a region of a frame (render.hip: visibility_kernel); as the launchers of device_scene.hpp: hipError_t cast to int.
+int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int walk);
 
 // what a set-up needs of a scene besides its triangles: materials and RGB8 textures (borrowed views).  api.cpp
 struct SceneTables { const rrt_material* mats; uint32_t n_mats; std::vector<rrt_texture> tex; };

@@ -130,6 +130,18 @@ struct FrameParams {
     double right[3], up[3], forward[3];
 };
 
+// Argument of the visibility kernels (render.hip: visibility_kernel; rrt.h: rrt_render_visibility_device): the frame, the region of it that is wanted
+// and the output planes.  Of a kernel of its own, so that FrameParams and DevScene -- arguments of the other kernels -- stay as they are.
+// The launch covers the 8x8-pixel tiles that intersect the region, in row-major order: tiles_w of them per row from tile (tile_x0, tile_y0);
+// F.tile_begin / F.tile_end = [0, their number), F.rank / F.world = 0 / 1.  The region is the columns [col_begin, col_end) of the rows
+// [F.row_begin, F.row_end); every plane is [rows][columns][4 sub-samples], and a null plane is not written.
+struct VisParams {
+    FrameParams F;
+    uint32_t col_begin, col_end;
+    uint32_t tile_x0, tile_y0, tiles_w, _pad;
+    uint8_t* hit; double *t, *u, *v; uint32_t* tri; uint32_t* albedo;
+};
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);

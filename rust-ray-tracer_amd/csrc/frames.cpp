@@ -1,4 +1,4 @@
-// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, per-ray queries, the choice of traversal variant, and
+// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility buffers, per-ray queries, the choice of traversal variant, and
 // the statistics of the last launch.
 #include <algorithm>
 #include <cstdlib>
@@ -36,17 +36,21 @@ FrameParams frame_params(const rrt_raytracer* rt, uint32_t width, uint32_t heigh
 // walk; bundle filter when the frame has more than ~1200 primary rays per triangle, lane filter below).  A caller that comes back for a SECOND
 // frame of the same size is rendering repeatedly, and that frame is first rendered with every variant (each twice: the first run warms caches) on the
 // caller's buffer and stream, timed with HIP events; the fastest is kept for that size.  This synchronises the stream once per size.
+// First frame of a size (for a host that renders one frame per run, as the reference does, this IS the choice): the bundle filter pays once the
+// frame holds enough rays per triangle for a 4x4-pixel wave to stay inside few nodes and long lists -- measured over 3 models x 5 frame sizes
+// and the 100 k soup (profiles/r03_variant_sweep.json, re-measured with the final kernels: bundle wins at >= 1234 primary rays per triangle, by 4-12 %;
+// lane filter wins at <= 719, by 12-180 %; nothing measured in between).
+int first_frame_variant(const rrt_raytracer* rt, uint32_t width, uint32_t height) {
+    const double rays_per_triangle = 4.0 * (double)width * (double)height / (double)(rt->scene.n_slots ? rt->scene.n_slots : 1u);
+    return rays_per_triangle > 1200.0 ? 1 : 0;
+}
+
 void tune_variant(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void* stream) {
     if (rt->variant_forced) return;
     if (!(rt->tuned_w == f.width && rt->tuned_h == f.height && rt->tuned_world == f.world)) {
         rt->tuned_w = f.width; rt->tuned_h = f.height; rt->tuned_world = f.world;
         rt->size_frames = 0; rt->size_measured = false;
-        // First frame of a size (for a host that renders one frame per run, as the reference does, this IS the choice): the bundle filter pays once the
-        // frame holds enough rays per triangle for a 4x4-pixel wave to stay inside few nodes and long lists -- measured over 3 models x 5 frame sizes
-        // and the 100 k soup (profiles/r03_variant_sweep.json, re-measured with the final kernels: bundle wins at >= 1234 primary rays per triangle, by 4-12 %;
-        // lane filter wins at <= 719, by 12-180 %; nothing measured in between).
-        const double rays_per_triangle = 4.0 * (double)f.width * (double)f.height / (double)(rt->scene.n_slots ? rt->scene.n_slots : 1u);
-        rt->walk = rays_per_triangle > 1200.0 ? 1 : 0;
+        rt->walk = first_frame_variant(rt, f.width, f.height);
     }
     if (rt->size_measured) return;
     if (++rt->size_frames < 2) return;
@@ -137,6 +141,111 @@ void launch_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t r
     record_launch(rt, width, height, rank, world);
 }
 
+// ---- visibility buffers (rrt.h: rrt_render_visibility_device).  One launch of visibility_kernel over the tiles the region touches.
+// The variant: the forced one, else the one kept for this frame size, else the first-frame rule's.  Reads the tuning state, never writes it: a
+// visibility or pick call is not a frame of that size.
+int visibility_variant(const rrt_raytracer* rt, uint32_t width, uint32_t height) {
+    if (rt->variant_forced) return rt->walk;
+    if (rt->tuned_w == width && rt->tuned_h == height && rt->tuned_world == 1u) return rt->walk;
+    return first_frame_variant(rt, width, height);
+}
+
+constexpr int kPlanes = 6;
+constexpr size_t kPlaneElem[kPlanes] = {1, 8, 8, 8, 4, 4};   // hit, t, u, v, tri, albedo: bytes per sub-sample
+
+// every check of a visibility call, before any GPU work; returns the region in force
+rrt_region check_visibility(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* planes) {
+    check_frame(rt, width, height);
+    if (!planes) throw Error{RRT_ERR_INVALID_ARG, "null planes struct"};
+    if (!planes->hit && !planes->t && !planes->u && !planes->v && !planes->tri && !planes->albedo) throw Error{RRT_ERR_INVALID_ARG, "no plane requested: all six pointers are null"};
+    const rrt_region r = region ? *region : rrt_region{0, 0, width, height};
+    if (r.w == 0 || r.h == 0) throw Error{RRT_ERR_INVALID_ARG, "empty region"};
+    if ((uint64_t)r.x0 + r.w > width || (uint64_t)r.y0 + r.h > height) throw Error{RRT_ERR_INVALID_ARG, "region sticks out of the frame"};
+    return r;
+}
+
+void record_visibility(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, int variant) {
+    rt->stats.width = width; rt->stats.height = height;
+    // traced pixels (render_kernel): columns [0, 2*(W/2)), rows [H - 2*(H/2) + 1, H), cut to the region
+    const uint64_t col_end = std::min<uint64_t>((uint64_t)r.x0 + r.w, 2ull * (width / 2)), row_begin = std::max<uint64_t>(r.y0, (uint64_t)height - 2ull * (height / 2) + 1);
+    const uint64_t cols = col_end > r.x0 ? col_end - r.x0 : 0, rows = (uint64_t)r.y0 + r.h > row_begin ? (uint64_t)r.y0 + r.h - row_begin : 0;
+    rt->stats.rays_primary = 4ull * cols * rows;
+    rt->stats.scene_bytes = rt->scene_bytes;
+    rt->stats.filter_variant = (uint32_t)variant; rt->stats.origin_plane_triangles = rt->scene.n_suspects;
+    rt->stats_pending = true; rt->launched = true;
+}
+
+// the planes of region r (checked) into device memory on the caller's stream, timed by the raytracer's events
+void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes, void* stream) {
+    VisParams p{};
+    p.F = frame_params(rt, width, height, 0, 1, false);
+    p.F.row_begin = r.y0; p.F.row_end = r.y0 + r.h;
+    p.col_begin = r.x0; p.col_end = r.x0 + r.w;
+    p.tile_x0 = r.x0 / 8; p.tile_y0 = r.y0 / 8;
+    p.tiles_w = (p.col_end + 7) / 8 - p.tile_x0;
+    p.F.tile_begin = 0; p.F.tile_end = p.tiles_w * ((p.F.row_end + 7) / 8 - p.tile_y0);
+    p.hit = d_planes.hit; p.t = d_planes.t; p.u = d_planes.u; p.v = d_planes.v; p.tri = d_planes.tri; p.albedo = d_planes.albedo;
+    const int variant = visibility_variant(rt, width, height);
+    HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
+    HIP_TRY((hipError_t)launch_visibility(rt->scene, p, stream, variant));
+    HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
+    record_visibility(rt, width, height, r, variant);
+}
+
+// Host forms: the wanted planes of n sub-samples carved out of the raytracer's kept device allocation (grown when a larger request comes), each on a
+// 256-byte boundary; returns the bytes in use.
+size_t kept_planes(rrt_raytracer* rt, size_t n, const void* const want[kPlanes], void* dev[kPlanes]) {
+    size_t need = 0;
+    for (int k = 0; k < kPlanes; k++) if (want[k]) need += (kPlaneElem[k] * n + 255) & ~(size_t)255;
+    if (rt->vis_buf_bytes < need) {
+        rt->vis_buf.reset(); rt->vis_buf_bytes = 0;
+        rt->vis_buf = dev_alloc(need);
+        rt->vis_buf_bytes = need;
+    }
+    DevArena arena{static_cast<char*>(rt->vis_buf.h), rt->vis_buf_bytes, 0};
+    for (int k = 0; k < kPlanes; k++) dev[k] = want[k] ? arena.take<char>(kPlaneElem[k] * n) : nullptr;
+    return arena.used;
+}
+rrt_visibility planes_of(void* const p[kPlanes]) { return rrt_visibility{(uint8_t*)p[0], (double*)p[1], (double*)p[2], (double*)p[3], (uint32_t*)p[4], (uint32_t*)p[5]}; }
+
+void visibility_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& planes) {
+    DeviceGuard guard(rt->device);
+    void* host[kPlanes] = {planes.hit, planes.t, planes.u, planes.v, planes.tri, planes.albedo};
+    void* dev[kPlanes];
+    const size_t n = 4 * (size_t)r.w * r.h;
+    kept_planes(rt, n, host, dev);
+    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
+    launch_visibility_frame(rt, width, height, r, planes_of(dev), rt->own_stream);
+    for (int k = 0; k < kPlanes; k++) {
+        if (!host[k]) continue;
+        // as rrt_render: one asynchronous DMA into a page-locked plane, a pageable one through the device's pinned staging ring
+        hipPointerAttribute_t attr{};
+        const bool pinned = hipPointerGetAttributes(&attr, host[k]) == hipSuccess && attr.type == hipMemoryTypeHost;
+        if (!pinned) (void)hipGetLastError();
+        if (pinned) HIP_TRY(hipMemcpyAsync(host[k], dev[k], kPlaneElem[k] * n, hipMemcpyDeviceToHost, rt->own_stream));
+        else staged_download(host[k], dev[k], kPlaneElem[k] * n, rt->own_stream);
+    }
+    HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the planes are in the caller's memory on return
+}
+
+// One pixel: a one-tile launch into the kept allocation and ONE copy of its six 256-byte plane slots back.
+rrt_pick_result pick_pixel(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t px, uint32_t py) {
+    DeviceGuard guard(rt->device);
+    alignas(8) char back[kPlanes * 256];
+    const void* const all[kPlanes] = {back, back, back, back, back, back};   // (every plane wanted)
+    void* dev[kPlanes];
+    const size_t used = kept_planes(rt, 4, all, dev);                        // the pixel's four sub-samples; sub-sample 0 is the answer
+    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
+    launch_visibility_frame(rt, width, height, rrt_region{px, py, 1, 1}, planes_of(dev), rt->own_stream);
+    HIP_TRY(hipMemcpyAsync(back, rt->vis_buf.h, used, hipMemcpyDeviceToHost, rt->own_stream));
+    HIP_TRY(hipStreamSynchronize(rt->own_stream));
+    rrt_pick_result out{};
+    uint8_t hit; std::memcpy(&hit, back, 1); out.hit = hit;
+    std::memcpy(&out.t, back + 256, 8); std::memcpy(&out.u, back + 512, 8); std::memcpy(&out.v, back + 768, 8);
+    std::memcpy(&out.tri, back + 1024, 4); std::memcpy(&out.albedo, back + 1280, 4);
+    return out;
+}
+
 // the device-side frame of the host-framebuffer entry points: kept and reused from call to call, grown when a larger frame comes
 uint32_t* host_fb(rrt_raytracer* rt, size_t bytes) {
     if (rt->host_fb_bytes < bytes) {
@@ -171,6 +280,33 @@ int rrt_render_device(rrt_raytracer* rt, uint32_t width, uint32_t height, void* 
         check_frame(rt, width, height);
         if (!d_fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
         launch_frame(rt, width, height, 0, 1, false, d_fb, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_visibility_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* d_planes, void* stream) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_visibility(rt, width, height, region, d_planes);
+        DeviceGuard guard(rt->device);
+        launch_visibility_frame(rt, width, height, r, *d_planes, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_visibility(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* planes) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_visibility(rt, width, height, region, planes);
+        visibility_to_host(rt, width, height, r, *planes);
+        return RRT_OK;
+    });
+}
+
+int rrt_pick(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t px, uint32_t py, rrt_pick_result* out) {
+    return guarded([&]() -> int {
+        check_frame(rt, width, height);
+        if (!out) throw Error{RRT_ERR_INVALID_ARG, "null result"};
+        if (px >= width || py >= height) throw Error{RRT_ERR_INVALID_ARG, "pixel outside the frame"};
+        *out = pick_pixel(rt, width, height, px, py);
         return RRT_OK;
     });
 }

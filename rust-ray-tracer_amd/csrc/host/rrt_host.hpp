@@ -81,6 +81,16 @@ public:
         check(rrt_camera_look_at({eye.x, eye.y, eye.z}, {target.x, target.y, target.z}, {up_hint.x, up_hint.y, up_hint.z}, &c), "look_at");
         check(rrt_raytracer_set_camera(rt_, &c), "look_at");
     }
+    // Visibility buffers (rrt.h: rrt_render_visibility): the planes of a region (nullptr = the whole frame), each [h][w][4 sub-samples]; blocking.
+    void visibility(uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility& planes) {
+        check(rrt_render_visibility(rt_, width, height, region, &planes), "visibility");
+    }
+    // what sub-sample 0 of canvas pixel (px, py) sees; blocking
+    rrt_pick_result pick(uint32_t width, uint32_t height, uint32_t px, uint32_t py) {
+        rrt_pick_result r;
+        check(rrt_pick(rt_, width, height, px, py, &r), "pick");
+        return r;
+    }
     rrt_raytracer* handle() const { return rt_; }
     rrt_stats last_stats() const { rrt_stats s; check(rrt_last_stats(rt_, &s), "rrt_last_stats"); return s; }
 private:

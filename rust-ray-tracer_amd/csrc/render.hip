@@ -30,8 +30,8 @@
 #include "device_scene.hpp"
 
 // The library compiles this file THREE times (csrc/Makefile), same device functions, different code-generation switches per group of kernels:
-//   -DRRT_TU=1  the bundle-filter frame kernel, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
-//   -DRRT_TU=3  the lane-filter and ray-walk frame kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
+//   -DRRT_TU=1  the bundle-filter frame kernel and visibility kernel, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
+//   -DRRT_TU=3  the lane-filter and ray-walk frame and visibility kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
 //   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
@@ -1632,6 +1632,84 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
     }
 }
 
+// Visibility buffers (rrt.h: rrt_render_visibility_device): the first hit of every primary ray of a region of the frame -- hit, t, u, v, triangle and the
+// colour-texture texel -- instead of a colour.  The waves, their rays and their guard are render_kernel's; each ray is walked once, as intersect_kernel
+// walks it, but from the one origin (one_origin: the bundle and the parked origin are the frame kernels').  A wave covers the tile quadrant its block index
+// says; lanes outside the region or the frame are inactive for the walk and store nothing.
+// Planes are [row][column][sub-sample]: the 16 lanes of one pixel row of a wave (4 pixels x 4 sub-samples) write one contiguous segment, 128 B of an f64
+// plane, 64 B of tri / albedo, 16 B of hit.  The plane pointers are kernel arguments: each test is wave-uniform.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const DevScene S, const VisParams P) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t lane = threadIdx.x;
+    const Stack stk{lds + kParkBytes, lane};
+    const FrameParams& F = P.F;
+    // Block order, tile quadrant, pixel, sub-sample and direction: render_kernel's, restated (a shared helper changed the register allocation of the frame
+    // kernels: profiles/visibility_kernel_resources.txt).  The tiles are those of the region's tile rectangle instead of a rank's share of the frame.
+    uint32_t blk = blockIdx.x;
+    if (F.xcd_chunk) {
+        const uint32_t C = F.xcd_chunk, full = (gridDim.x / (8u * C)) * (8u * C);
+        if (blk < full) { const uint32_t xcd = blk & 7u, i = blk >> 3; blk = ((i / C) * 8u + xcd) * C + (i % C); }
+    }
+    const uint32_t local_tile = blk >> 2, quad = blk & 3u;
+    const uint32_t pix = lane >> 2, sub = lane & 3u;
+    const bool tile_ok = local_tile < F.tile_end;
+    const uint32_t tx = P.tile_x0 + (tile_ok ? local_tile % P.tiles_w : 0), ty = P.tile_y0 + (tile_ok ? local_tile / P.tiles_w : 0);
+    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
+    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
+    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
+    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;   // col_end <= width, row_end <= height
+    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;   // the pixels the reference traces (render_kernel)
+    const int32_t x = (int32_t)px - W / 2;
+    const int32_t y = (H - H / 2) - (int32_t)py;
+    const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;                      // engine.rs:207-236
+    const double yd = (sub & 2u) ? ((double)y + 0.5) : (double)y;
+    const double sa = xd * F.x_scale, sb = yd * F.y_scale, sc = F.z_value;             // (right*a + up*b) + forward*c, five operations per component: rrt.h, rrt_camera
+    const V3 o = ld3(S.origin), d = mk((F.right[0] * sa + F.up[0] * sb) + F.forward[0] * sc,
+                                       (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
+                                       (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    double t; uint32_t slot;
+    if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, traced, false, !origin_ray_in_suspect_plane(S, o, d), o, d, kInf, t, slot);
+    else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, traced, false, !origin_ray_in_suspect_plane(S, o, d), true, o, d, kInf, t, slot);
+    if (!in_region) return;
+    const bool found = traced && slot != kNone;
+    double u = 0, v = 0;
+    uint32_t tri = kNone;
+    if (found) {
+        double t2;
+        mt_full(S.geom + slot, o, d, t2, u, v);
+        tri = S.attr[slot].orig;
+    } else {
+        t = 0;                                                                           // the miss convention of intersect_kernel; a pixel the reference never traces reads as a miss
+    }
+    const size_t i = (((size_t)(py - F.row_begin) * (P.col_end - P.col_begin)) + (px - P.col_begin)) * 4 + sub;
+    if (P.albedo) {
+        uint32_t col = traced ? 0x00FFFFFFu : 0u;                                        // WHITE, raytracer.rs:109-111; 0 as Canvas::new where nothing is traced
+        if (found) {
+            // --- the texel of the hit, raytracer.rs:43-55, as trace_colour reads it
+            const DevTriAttr& A = S.attr[slot];
+            const DevMaterial& M = S.mats[A.mat];
+            const DevTexture T = M.tex_desc;
+            const double w = 1.0 - u - v;                                                // raytracer.rs:43
+            const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;                // raytracer.rs:45-47
+            const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;                // raytracer.rs:48-50
+            const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);    // raytracer.rs:52
+            const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);  // raytracer.rs:53
+            const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);          // raytracer.rs:55
+            col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
+        }
+        P.albedo[i] = col;
+    }
+    if (P.hit) P.hit[i] = found ? 1 : 0;
+    if (P.t) P.t[i] = t;
+    if (P.u) P.u[i] = u;
+    if (P.v) P.v[i] = v;
+    if (P.tri) P.tri[i] = tri;
+}
+
 #endif   // RRT_TU_FRAME || RRT_TU_LANE
 #if RRT_TU_FRAME
 __global__ __launch_bounds__(256) void detile_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t world, uint32_t tiles_per_rank,
@@ -1764,6 +1842,21 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
     return (int)hipGetLastError();
 }
 
+// The visibility planes of a region of a frame (device_scene.hpp: VisParams), one block per quadrant of the tiles the region touches.  The bundle
+// filter's fallback for trees of 2^24 nodes or more is launch_render's.
+int launch_visibility_lane_ray(const DevScene& s, const VisParams& p, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int walk) {
+    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;
+    const uint32_t n_tiles = p.F.tile_end;
+    if (n_tiles == 0) return 0;
+    const dim3 grid(n_tiles * 4), block(64);
+    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
+    if (walk != kWalkBundle) return launch_visibility_lane_ray(s, p, stream, walk, n_tiles * 4, lds);
+    if (s.has_groups) hipLaunchKernelGGL((visibility_kernel<kWalkBundle, true>), grid, block, lds, (hipStream_t)stream, s, p);
+    else hipLaunchKernelGGL((visibility_kernel<kWalkBundle, false>), grid, block, lds, (hipStream_t)stream, s, p);
+    return (int)hipGetLastError();
+}
+
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
     const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
     const uint32_t tpr = (tiles_x * tiles_y + world - 1) / world;
@@ -1791,6 +1884,18 @@ int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_
     } else {
         if (s.has_groups) hipLaunchKernelGGL((render_kernel<kWalkLane, true>), grid, block, lds, q, s, f, d_out);
         else hipLaunchKernelGGL((render_kernel<kWalkLane, false>), grid, block, lds, q, s, f, d_out);
+    }
+    return (int)hipGetLastError();
+}
+int launch_visibility_lane_ray(const DevScene& s, const VisParams& p, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+    const dim3 grid(n_blocks), block(64);
+    const hipStream_t q = (hipStream_t)stream;
+    if (walk == kWalkRay) {
+        if (s.has_groups) hipLaunchKernelGGL((visibility_kernel<kWalkRay, true>), grid, block, lds, q, s, p);
+        else hipLaunchKernelGGL((visibility_kernel<kWalkRay, false>), grid, block, lds, q, s, p);
+    } else {
+        if (s.has_groups) hipLaunchKernelGGL((visibility_kernel<kWalkLane, true>), grid, block, lds, q, s, p);
+        else hipLaunchKernelGGL((visibility_kernel<kWalkLane, false>), grid, block, lds, q, s, p);
     }
     return (int)hipGetLastError();
 }
