@@ -175,9 +175,10 @@ typedef struct { rrt_vec3 eye, right, up, forward; } rrt_camera;          /* 96 
  * rrt_multi_* calls through the raytracers they hold: set the camera on each of them, or on each rank, between rrt_multi_sync and the next enqueue).  The
  * per-ray entry points keep taking the caller's own rays; their exactness guard is keyed to the current eye.  cam == NULL: back to the creation pose.
  * RRT_ERR_INVALID_ARG for a NULL rt or a non-finite component (the pose in force stays).
- * BLOCKING, and it must not overlap frames of this raytracer that are still in flight: frames enqueued with rrt_render_device, rrt_render_tiles_device,
- * rrt_render_visibility_device or rrt_multi_enqueue must have been synchronised by the caller first (rrt_render, rrt_render_progressive, rrt_render_visibility
- * and rrt_pick return with nothing in flight).
+ * BLOCKING, and it must not overlap launches of this raytracer that are still in flight: frames enqueued with rrt_render_device, rrt_render_tiles_device,
+ * rrt_render_visibility_device or rrt_multi_enqueue, and ray batches enqueued with rrt_intersect_rays_device, rrt_get_ray_colours_device or
+ * rrt_occluded_rays_device (their exactness guard reads the suspect list of the current eye), must have been synchronised by the caller first (rrt_render,
+ * rrt_render_progressive, rrt_render_visibility, rrt_pick and the host forms of the per-ray calls return with nothing in flight).
  * A new eye costs one pass over the resident triangles on the GPU and one read-back: the exactness guard (rrt_stats.origin_plane_triangles, RRT_BUF_SUSPECTS)
  * is recomputed for it, with the list a fresh rrt_raytracer_create at that origin would produce; a RRT_FLAG_NO_CULL raytracer has no guard and only stores
  * the pose.  An eye bit-equal to the current one costs no GPU work and no synchronisation: a pure rotation is free.
@@ -284,6 +285,39 @@ int rrt_get_ray_colours(rrt_raytracer *rt, uint32_t n, const double *origins, co
  * push order.  max_t may be NULL (= +inf, ray.rs:96-102). */
 int rrt_intersect_rays(rrt_raytracer *rt, uint32_t n, const double *origins, const double *dirs, const double *max_t,
                        uint8_t *hit, double *t, double *u, double *v, uint32_t *tri);
+
+/* Some/None of the same walk, for a host that asks "is this point lit from there" (light baking, ambient occlusion, a moved light's shadow mask, line of
+ * sight): occluded[i] = 1 / 0 = hit[i] of rrt_intersect_rays for the same origin, direction and max_t, byte for byte.  It is the reference's
+ * Ray::intersect_with_octant_with_max_t(octree, 0, max_t) reduced to Some/None, NOT "any triangle anywhere on the segment": max_t bounds the root's own
+ * list and the final comparison only, children are entered with +inf, the first sorted child that returns Some ends the loop (ray.rs:104-168), and a NaN or
+ * non-positive max_t gives 0.  max_t may be NULL (= +inf).  The walk stops at the first node that proves Some, computes no u, v or
+ * triangle index and writes one byte per ray.
+ * The reference's shadow query triangle_exists_between_points (raytracer.rs:164-188) forms its ray as origin = point + normal * surface_offset,
+ * direction = target - origin (not normalised), max_t = |direction| (raytracer.rs:170-179) and returns `true` for None, i.e. for "lit": the negation of
+ * occluded[i].  The library does not form these rays: like the other per-ray entry points this one takes the caller's own, and the default mode's
+ * exactness band applies in the same way (RRT_FLAG_NO_CULL above: the guard is keyed to the current eye, secondary rays are not guarded).
+ * Host arrays, blocking; the traversal variant is measured as for the two calls above (same thresholds, same kept variant). */
+int rrt_occluded_rays(rrt_raytracer *rt, uint32_t n, const double *origins, const double *dirs, const double *max_t, uint8_t *occluded);
+
+/* Device-resident ray batches: the three per-ray queries on device pointers of rt's device, enqueued on `stream` (hipStream_t, NULL = default), not
+ * synchronised.  No device allocation, no free, no copy and no measurement is made: nothing on the path serialises the caller's stream.  Per ray the
+ * results are exactly those of the host forms, the miss convention of rrt_intersect_rays included (hit 0, t = u = v = 0.0, tri = 0xFFFFFFFF).
+ * rrt_intersect_rays_device: any of the five output pointers may be NULL (that array is not written), at least one is set; with d_u and d_v both NULL the
+ * second Moller-Trumbore that yields u and v is skipped.  d_max_t NULL = +inf.
+ * Traversal variant: the forced one; else the one kept for per-ray calls (by an earlier host batch of at least 16384 rays, or by rrt_tune_rays_device);
+ * else the frame variant, which is what small host batches run.
+ * RRT_ERR_INVALID_ARG, before any GPU work, here and in rrt_occluded_rays: NULL rt; NULL origins or dirs with n > 0; every output NULL with n > 0.  n = 0 is
+ * RRT_OK with nothing enqueued.  rrt_last_stats afterwards: as after the host forms (width = n, height = 1), kernel_ms from events on the caller's stream. */
+int rrt_intersect_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_origins, const double *d_dirs, const double *d_max_t,
+                              uint8_t *d_hit, double *d_t, double *d_u, double *d_v, uint32_t *d_tri, void *stream);
+int rrt_get_ray_colours_device(rrt_raytracer *rt, uint32_t n, const double *d_origins, const double *d_dirs, uint32_t *d_colours, void *stream);
+int rrt_occluded_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_origins, const double *d_dirs, const double *d_max_t,
+                             uint8_t *d_occluded, void *stream);
+/* BLOCKING: measures the three traversal variants on a device-resident batch -- each twice on its first min(n, 65536) rays, closest-hit query, outputs into
+ * memory the library owns, launched on the default stream (the rays must be complete in memory: synchronise the stream that wrote them first) -- and keeps
+ * the fastest for later per-ray calls, host and device forms alike, replacing an earlier choice.  Any n >= 1 is measured; whether the sample stands for the
+ * rays to come is the caller's business.  A raytracer with a forced variant does no GPU work and reports that variant.  variant_out may be NULL. */
+int rrt_tune_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_origins, const double *d_dirs, const double *d_max_t, uint32_t *variant_out);
 
 /* The octree of a raytracer whose set-up ran on the GPU (the default), read back from its device: same layout as rrt_model_get_octree; info (may be
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */

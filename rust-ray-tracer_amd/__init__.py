@@ -137,6 +137,11 @@ SYMBOLS = {
     "rrt_render_progressive": (C.c_int, [_P, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _P, _P]),
     "rrt_get_ray_colours": (C.c_int, [_P, C.c_uint32, _dp, _dp, _u32p]),
     "rrt_intersect_rays": (C.c_int, [_P, C.c_uint32, _dp, _dp, _dp, _u8p, _dp, _dp, _dp, _u32p]),
+    "rrt_occluded_rays": (C.c_int, [_P, C.c_uint32, _dp, _dp, _dp, _u8p]),
+    "rrt_intersect_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rrt_get_ray_colours_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P]),
+    "rrt_occluded_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "rrt_tune_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _u32p]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
@@ -470,6 +475,53 @@ class RayTracer:
                                         tri.ctypes.data_as(_u32p)), "rrt_intersect_rays")
         return hit.astype(bool), t, u, v, tri
 
+    # Some/None of the same walk (rrt.h: rrt_occluded_rays): the reference's shadow query without its negation
+    def occluded(self, origins, dirs, max_t=None) -> np.ndarray:
+        o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3); d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+        assert o.shape == d.shape
+        n = o.shape[0]
+        mt = None if max_t is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_t, np.float64), (n,)))
+        out = np.empty(n, np.uint8)
+        _check(lib().rrt_occluded_rays(self._h, n, _d(o), _d(d), None if mt is None else _d(mt), out.ctypes.data_as(_u8p)), "rrt_occluded_rays")
+        return out.astype(bool)
+
+    # device-resident ray batches (rrt.h: rrt_intersect_rays_device): origins_t / dirs_t are float64 device tensors of 3 n elements, max_t_t of n; enqueued, not synchronised
+    def occluded_into(self, origins_t, dirs_t, out_t, max_t_t=None, stream: Optional[int] = None):
+        """rrt_occluded_rays_device: out_t = device tensor of n one-byte elements, 1 = occluded."""
+        n = _ray_batch(origins_t, dirs_t, max_t_t)
+        _device_tensor(out_t, n, 1, "out")
+        _check(lib().rrt_occluded_rays_device(self._h, n, _P(origins_t.data_ptr()), _P(dirs_t.data_ptr()), _P(max_t_t.data_ptr()) if max_t_t is not None else None,
+                                              _P(out_t.data_ptr()), _P(_stream(stream))), "rrt_occluded_rays_device")
+
+    def intersect_rays_into(self, origins_t, dirs_t, out: dict, max_t_t=None, stream: Optional[int] = None):
+        """rrt_intersect_rays_device: out = {name: device tensor of n elements} for any subset of hit (1 byte), t, u, v (float64), tri (4 bytes); the others are not
+        computed."""
+        n = _ray_batch(origins_t, dirs_t, max_t_t)
+        assert set(out) <= set(PLANES[:5]), sorted(out)
+        for name, t in out.items():
+            _device_tensor(t, n, np.dtype(PLANE_DTYPES[name]).itemsize, name)
+        p = [_P(out[name].data_ptr()) if name in out else None for name in PLANES[:5]]
+        _check(lib().rrt_intersect_rays_device(self._h, n, _P(origins_t.data_ptr()), _P(dirs_t.data_ptr()), _P(max_t_t.data_ptr()) if max_t_t is not None else None,
+                                               *p, _P(_stream(stream))), "rrt_intersect_rays_device")
+
+    def get_ray_colours_into(self, origins_t, dirs_t, colours_t, stream: Optional[int] = None):
+        """rrt_get_ray_colours_device: colours_t = device tensor of n four-byte elements, 0x00RRGGBB."""
+        n = _ray_batch(origins_t, dirs_t, None)
+        _device_tensor(colours_t, n, 4, "colours")
+        _check(lib().rrt_get_ray_colours_device(self._h, n, _P(origins_t.data_ptr()), _P(dirs_t.data_ptr()), _P(colours_t.data_ptr()), _P(_stream(stream))),
+               "rrt_get_ray_colours_device")
+
+    def tune_rays(self, origins_t, dirs_t, max_t_t=None) -> int:
+        """rrt_tune_rays_device (blocking): measures the three traversal variants on this device-resident batch and keeps the fastest for later per-ray calls;
+        returns it (an index into VARIANT_NAMES).  The current torch stream is synchronised first: the measurement runs on the default stream."""
+        n = _ray_batch(origins_t, dirs_t, max_t_t)
+        import torch
+        torch.cuda.current_stream().synchronize()
+        v = C.c_uint32(0)
+        _check(lib().rrt_tune_rays_device(self._h, n, _P(origins_t.data_ptr()), _P(dirs_t.data_ptr()), _P(max_t_t.data_ptr()) if max_t_t is not None else None,
+                                          C.byref(v)), "rrt_tune_rays_device")
+        return int(v.value)
+
     # engine.rs:196-253: chunked draw with an update after every chunk (on_update(fb, first_row, n_rows) stands in for canvas.update())
     def render_progressive(self, width: int, height: int, on_update=None, chunk_rows: int = 50) -> np.ndarray:
         fb = np.empty((height, width), np.uint32)
@@ -642,6 +694,23 @@ class MultiGpu:
         v = C.c_double(-1.0)
         _check(lib().rrt_multi_last_gather_ms(self._h, C.byref(v)), "rrt_multi_last_gather_ms")
         return v.value
+
+
+def _device_tensor(t, n: int, itemsize: int, name: str):
+    """What every _into form asserts of a tensor before the library sees its pointer (a numpy array fails here, without a GPU)."""
+    assert getattr(t, "is_cuda", False), f"{name}: not a device tensor"
+    assert t.is_contiguous() and t.element_size() == itemsize and t.numel() == n, f"{name}: want {n} contiguous elements of {itemsize} bytes"
+
+
+def _ray_batch(origins_t, dirs_t, max_t_t) -> int:
+    """Checks a device-resident ray batch (float64 tensors: origins and directions of 3 n elements, max_t of n or None); returns n."""
+    assert getattr(origins_t, "is_cuda", False), "origins: not a device tensor"
+    n, rem = divmod(origins_t.numel(), 3)
+    assert rem == 0, "origins: the element count is not a multiple of 3"
+    _device_tensor(origins_t, 3 * n, 8, "origins"); _device_tensor(dirs_t, 3 * n, 8, "dirs")
+    if max_t_t is not None:
+        _device_tensor(max_t_t, n, 8, "max_t")
+    return n
 
 
 def _stream(stream: Optional[int]) -> int:

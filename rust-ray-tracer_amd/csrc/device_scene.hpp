@@ -149,6 +149,9 @@ int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk);
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
                      uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream, int walk);
+// (any of the five outputs of launch_intersect may be null: that array is not written)
+// Some/None of the same walk as a shadow query (render.hip: occlusion_kernel): d_occluded[n] = 1 / 0
+int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream, int walk);
 // Exactness guard for a new eye (scene_build.hip: k_suspects_resident): searches the resident list slots geom[0, n_list_slots) and appends up to
 // RRT_MAX_SUSPECTS + 1 records {push index, suspect} to d_out, counting every find in *d_count (zeroed here, on `stream`).  Not synchronised.
 struct SuspectRecord { uint32_t tri; uint32_t _pad; DevSuspect s; };

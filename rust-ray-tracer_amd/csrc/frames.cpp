@@ -113,6 +113,17 @@ template <class Launch> int rays_variant(rrt_raytracer* rt, uint32_t n, Launch&&
     rt->walk_rays = best_v;
     return best_v;
 }
+// The device forms (rrt_intersect_rays_device, ...) never measure: the forced variant, else the one kept for per-ray calls, else the frame variant.
+int device_rays_variant(const rrt_raytracer* rt) {
+    if (rt->variant_forced) return rt->walk;
+    return rt->walk_rays >= 0 ? rt->walk_rays : rt->walk;
+}
+// every check of a per-ray call, before any GPU work; n == 0 is a no-op
+void check_rays(const rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, bool any_output) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (n && (!origins || !dirs)) throw Error{RRT_ERR_INVALID_ARG, "null ray origins or directions"};
+    if (n && !any_output) throw Error{RRT_ERR_INVALID_ARG, "no output requested: every output pointer is null"};
+}
 // (kernel time of a per-ray launch into rrt_stats, like a frame's)
 void record_rays(rrt_raytracer* rt, uint32_t n, int variant) {
     rt->stats.width = n; rt->stats.height = 1; rt->stats.rays_primary = n;
@@ -443,6 +454,98 @@ int rrt_intersect_rays(rrt_raytracer* rt, uint32_t n, const double* origins, con
         HIP_TRY(hipMemcpy(u, bufs[5], 8 * N, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(v, bufs[6], 8 * N, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(tri, bufs[7], 4 * N, hipMemcpyDeviceToHost));
+        return (int)RRT_OK;
+    });
+}
+
+// ---- device-resident ray batches (rrt.h): no allocation, no copy, no synchronisation; timed by the raytracer's events on the caller's stream, as rrt_render_device
+int rrt_intersect_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
+                              uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream) {
+    return guarded([&]() -> int {
+        check_rays(rt, n, d_origins, d_dirs, d_hit || d_t || d_u || d_v || d_tri);
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        const int variant = device_rays_variant(rt);
+        HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
+        HIP_TRY((hipError_t)launch_intersect(rt->scene, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri, stream, variant));
+        HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
+        record_rays(rt, n, variant);
+        return (int)RRT_OK;
+    });
+}
+
+int rrt_get_ray_colours_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream) {
+    return guarded([&]() -> int {
+        check_rays(rt, n, d_origins, d_dirs, d_colours != nullptr);
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        const int variant = device_rays_variant(rt);
+        HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
+        HIP_TRY((hipError_t)launch_ray_colours(rt->scene, n, d_origins, d_dirs, d_colours, stream, variant));
+        HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
+        record_rays(rt, n, variant);
+        return (int)RRT_OK;
+    });
+}
+
+int rrt_occluded_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream) {
+    return guarded([&]() -> int {
+        check_rays(rt, n, d_origins, d_dirs, d_occluded != nullptr);
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        const int variant = device_rays_variant(rt);
+        HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
+        HIP_TRY((hipError_t)launch_occlusion(rt->scene, n, d_origins, d_dirs, d_max_t, d_occluded, stream, variant));
+        HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
+        record_rays(rt, n, variant);
+        return (int)RRT_OK;
+    });
+}
+
+// Host form: as rrt_intersect_rays (uploads, the measurement rule of rays_variant on this kernel, one download).
+int rrt_occluded_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, uint8_t* occluded) {
+    return guarded([&]() -> int {
+        check_rays(rt, n, origins, dirs, occluded != nullptr);
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        const size_t N = n;
+        const DevBuf b_o = dev_alloc(24 * N), b_d = dev_alloc(24 * N), b_m = dev_alloc(8 * N), b_x = dev_alloc(N);
+        const double *d_o = static_cast<const double*>(b_o.h), *d_d = static_cast<const double*>(b_d.h), *d_m = max_t ? static_cast<const double*>(b_m.h) : nullptr;
+        uint8_t* d_x = static_cast<uint8_t*>(b_x.h);
+        HIP_TRY(hipMemcpy(b_o.h, origins, 24 * N, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b_d.h, dirs, 24 * N, hipMemcpyHostToDevice));
+        if (max_t) HIP_TRY(hipMemcpy(b_m.h, max_t, 8 * N, hipMemcpyHostToDevice));
+        auto launch = [&](uint32_t m, int v) { return launch_occlusion(rt->scene, m, d_o, d_d, d_m, d_x, nullptr, v); };
+        const int variant = rays_variant(rt, n, launch);
+        HIP_TRY(hipEventRecord(rt->ev0, nullptr));
+        HIP_TRY((hipError_t)launch(n, variant));
+        HIP_TRY(hipEventRecord(rt->ev1, nullptr));
+        record_rays(rt, n, variant);
+        HIP_TRY(hipMemcpy(occluded, d_x, N, hipMemcpyDeviceToHost));
+        return (int)RRT_OK;
+    });
+}
+
+// Blocking: the measurement of rays_variant on a batch that is already on the device, whatever its size; the result replaces an earlier one.  The
+// outputs go to an allocation of the raytracer's own, kept between calls.  The launches run on the null stream: the rays must be complete in memory.
+int rrt_tune_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint32_t* variant_out) {
+    return guarded([&]() -> int {
+        check_rays(rt, n, d_origins, d_dirs, true);
+        if (n && !rt->variant_forced) {
+            DeviceGuard guard(rt->device);
+            const uint32_t m = n < kTuneSample ? n : kTuneSample;
+            constexpr size_t kBytes = (size_t)kTuneSample * (1 + 8 + 8 + 8 + 4);   // hit, t, u, v, tri of the largest sample (each a multiple of 256 bytes)
+            if (rt->tune_buf_bytes < kBytes) {
+                rt->tune_buf.reset(); rt->tune_buf_bytes = 0;
+                rt->tune_buf = dev_alloc(kBytes);
+                rt->tune_buf_bytes = kBytes;
+            }
+            DevArena arena{static_cast<char*>(rt->tune_buf.h), rt->tune_buf_bytes, 0};
+            uint8_t* hit = arena.take<uint8_t>(m); double *t = arena.take<double>(m), *u = arena.take<double>(m), *v = arena.take<double>(m); uint32_t* tri = arena.take<uint32_t>(m);
+            rt->walk_rays = -1;                                                   // (measure again: rays_variant keeps what it finds)
+            rays_variant(rt, kTuneMinRays, [&](uint32_t, int variant) { return launch_intersect(rt->scene, m, d_origins, d_dirs, d_max_t, hit, t, u, v, tri, nullptr, variant); });
+        }
+        if (variant_out) *variant_out = (uint32_t)device_rays_variant(rt);
         return (int)RRT_OK;
     });
 }

@@ -33,7 +33,7 @@
 //   -DRRT_TU=1  the bundle-filter frame kernel and visibility kernel, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
 //   -DRRT_TU=3  the lane-filter and ray-walk frame and visibility kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
-//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel (default scheduler: max-ILP costs scattered rays 17 %).
+//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
 #ifndef RRT_TU
 #define RRT_TU 0
@@ -703,7 +703,8 @@ __device__ __forceinline__ uint32_t chain_target(const DevScene& S, const DevClu
 // one_origin (wave-uniform): the caller knows that every active lane's ray starts at the same point and that any_ok is false (make_bundle).
 // kBundle selects the own-list filter: false = every lane tests each box against its own ray (64 rays x 1 box per instruction);
 // true = boxes in lanes against the wave's ray bundle (64 boxes x 1 bundle per instruction).  Same results either way.
-template <bool kBundle, bool kGroups>
+// kFarAnchor = false (occlusion_kernel): a shadow query's bundle is anchored at the origins like any other ray's, not at the far ends (make_bundle: tau).
+template <bool kBundle, bool kGroups, bool kFarAnchor = true>
 __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stack& stk, bool active, bool any_ok, bool filter_ok, bool one_origin, V3 o, V3 d, double max_t,
                                          double& out_t, uint32_t& out_slot) {
     constexpr bool kLeaf = !kBundle;   // leaf children are tested at their parent by the lane-filter kernel only (measured: the extra code costs the bundle kernel 12 % on the teapot)
@@ -728,7 +729,7 @@ __device__ __forceinline__ void traverse(PROF_DECL const DevScene& S, const Stac
     // of a large soup) are searched with boxes in lanes, 64 boxes per instruction, instead of one wave-uniform box at a time.
     Bundle BU{};
     bool long_lists_in_lanes = false;
-    if constexpr (kBundle) BU = make_bundle(active, one_origin, o, d, r32, any_ok ? 1.0f : 0.0f);
+    if constexpr (kBundle) BU = make_bundle(active, one_origin, o, d, r32, (any_ok && kFarAnchor) ? 1.0f : 0.0f);
     if constexpr (!kBundle) {
         // (parked in LDS rather than held in 15 SGPRs for the whole walk: scalar registers are what the lane-filter kernel is shortest of)
         const Bundle B0 = make_bundle(active, one_origin, o, d, r32, any_ok ? 1.0f : 0.0f);
@@ -1762,10 +1763,47 @@ __global__ __launch_bounds__(64) void intersect_kernel(const DevScene S, uint32_
     for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
 #endif
     if (!ok) return;
-    if (slot == kNone) { hit[i] = 0; t_out[i] = 0; u_out[i] = 0; v_out[i] = 0; tri_out[i] = kNone; return; }
+    // Any output may be null (rrt.h: rrt_intersect_rays_device): the pointers are kernel arguments, so every test below is wave-uniform.
+    if (slot == kNone) {
+        if (hit) hit[i] = 0;
+        if (t_out) t_out[i] = 0;
+        if (u_out) u_out[i] = 0;
+        if (v_out) v_out[i] = 0;
+        if (tri_out) tri_out[i] = kNone;
+        return;
+    }
     double t2, u = 0, v = 0;
-    mt_full(S.geom + slot, o, d, t2, u, v);
-    hit[i] = 1; t_out[i] = t; u_out[i] = u; v_out[i] = v; tri_out[i] = S.attr[slot].orig;
+    if (u_out || v_out) mt_full(S.geom + slot, o, d, t2, u, v);
+    if (hit) hit[i] = 1;
+    if (t_out) t_out[i] = t;
+    if (u_out) u_out[i] = u;
+    if (v_out) v_out[i] = v;
+    if (tri_out) tri_out[i] = S.attr[slot].orig;
+}
+
+// Some/None of the same walk (rrt.h: rrt_occluded_rays): one byte per ray.  The walk runs as a shadow query (any_ok: traverse / traverse_ray stop at the
+// first node whose own list proves Some, see the comment at that rule), with intersect_kernel's guard; no second Moller-Trumbore, no t, no attribute load.
+template <int kWalk>
+__global__ __launch_bounds__(64) void occlusion_kernel(const DevScene S, uint32_t n, const double* __restrict__ origins, const double* __restrict__ dirs,
+                                                       const double* __restrict__ max_t, uint8_t* __restrict__ occluded) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const Stack stk{lds + kParkBytes, threadIdx.x};
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    const bool ok = i < n;
+    const V3 o = ok ? ld3(origins + 3 * (size_t)i) : mk(0, 0, 0), d = ok ? ld3(dirs + 3 * (size_t)i) : mk(0, 0, 1);
+    const double mt = (ok && max_t) ? max_t[i] : kInf;
+    double t; uint32_t slot;
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, ok, true, !origin_ray_in_suspect_plane(S, o, d), o, d, mt, t, slot);
+    // (kFarAnchor = false: the frame kernels anchor the bundle of a tile's shadow rays at the light, where they end together; a caller's batch need not end
+    // anywhere together, and on the rays of tools/ray_batch_bench.py that do, the anchor at the origins is the faster one: DESIGN.md section 4)
+    else traverse<kWalk == kWalkBundle, true, false>(PROF_ARG S, stk, ok, true, !origin_ray_in_suspect_plane(S, o, d), false, o, d, mt, t, slot);
+#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
+    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
+#endif
+    if (ok) occluded[i] = slot != kNone ? 1 : 0;
 }
 #endif   // RRT_TU_RAYS
 
@@ -1922,6 +1960,17 @@ int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, con
     if (walk == kWalkBundle) hipLaunchKernelGGL(intersect_kernel<kWalkBundle>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
     else if (walk == kWalkRay) hipLaunchKernelGGL(intersect_kernel<kWalkRay>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
     else hipLaunchKernelGGL(intersect_kernel<kWalkLane>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
+    return (int)hipGetLastError();
+}
+
+int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream, int walk) {
+    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;    // as launch_render
+    if (n == 0) return 0;
+    const dim3 grid((n + 63) / 64), block(64);
+    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
+    if (walk == kWalkBundle) hipLaunchKernelGGL(occlusion_kernel<kWalkBundle>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
+    else if (walk == kWalkRay) hipLaunchKernelGGL(occlusion_kernel<kWalkRay>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
+    else hipLaunchKernelGGL(occlusion_kernel<kWalkLane>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
     return (int)hipGetLastError();
 }
 #endif   // RRT_TU_RAYS
