@@ -190,6 +190,43 @@ int rrt_raytracer_get_camera(const rrt_raytracer *rt, rrt_camera *out);
  * component is non-finite. */
 int rrt_camera_look_at(rrt_vec3 eye, rrt_vec3 target, rrt_vec3 up_hint, rrt_camera *out);
 
+/* Scene updates: the lights and the triangles of a living raytracer, between frames.  Materials, textures, options, flags and the camera pose stay as they
+ * are, resident; nothing is uploaded or allocated again that does not depend on the triangles.  All five calls follow the contract of
+ * rrt_raytracer_set_camera: every launch made after the call returns sees the change (frames, tiles, progressive frames, the visibility calls, the per-ray
+ * calls in host and device form, and the rrt_multi_* calls through the raytracers they hold: set it on each of them, or on each rank, between
+ * rrt_multi_sync and the next enqueue), and the call must not overlap launches of this raytracer that are still in flight.
+ *
+ * rrt_raytracer_set_lights: host work only, no GPU call and no synchronisation (the lights travel with the kernel arguments).  The checks of creation
+ * apply -- n_lights > 16, a kind > 2 or a NULL list with n_lights > 0 is RRT_ERR_INVALID_ARG and the list in force stays; n_lights == 0 is valid.  Order
+ * is kept: the reference's light loop (raytracer.rs) breaks out on its conditions, so order changes pixels.  Works on a RRT_FLAG_HOST_SETUP raytracer too.
+ * rrt_raytracer_get_lights: the list in force; out may be NULL to ask for the count only, capacity < count with a non-NULL out is RRT_ERR_INVALID_ARG. */
+int rrt_raytracer_set_lights(rrt_raytracer *rt, const rrt_light *lights, uint32_t n_lights);
+int rrt_raytracer_get_lights(const rrt_raytracer *rt, rrt_light *out, uint32_t capacity, uint32_t *n_lights);
+/* rrt_raytracer_set_triangles: new triangles, arrays as rrt_raytracer_create_from_arrays (mat[i] indexes the RESIDENT material table and is checked against
+ * it).  BLOCKING.  Afterwards the raytracer is what rrt_raytracer_create_from_arrays would have made from these arrays with this raytracer's materials,
+ * textures, options and flags, the lights and the camera pose in force: every RRT_BUF_* buffer, rrt_raytracer_get_octree, rrt_raytracer_get_chain_info,
+ * rrt_stats.scene_bytes, every frame and every ray query; rrt_stats.origin_plane_triangles and RRT_BUF_SUSPECTS are those of the CURRENT eye, and
+ * rrt_raytracer_set_camera(NULL) still returns to the creation pose.  n_tris may differ from before and may be 0.  root as there, except that NULL means the
+ * root box in force.  Octree, index and records are built on the GPU by the kernels of creation (rrt_get_setup_times then reports octree_ms, index_ms and
+ * upload_ms of the latest build; create_ms and hip_init_ms stay).  What the raytracer measured on the old scene is forgotten -- the traversal variant kept for
+ * a frame size with that size's frame count, and the variant kept for per-ray calls -- so the next frame of a size is a first frame again (the rule then sees
+ * the new triangle count); a forced variant stays.
+ * ALL OR NOTHING: on any failure -- RRT_ERR_INVALID_ARG (NULL array with n_tris > 0, material index out of range), RRT_ERR_DEPTH, RRT_ERR_OOM, a HIP error that
+ * leaves the device usable -- the old scene stays in force, intact and renderable.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer.
+ * rrt_raytracer_set_triangles_device: the same from arrays in device memory of rt's device (positions computed there by a simulation or skinning step: no
+ * PCIe transfer), borrowed for the call only.  The build waits on an event recorded on `stream` (hipStream_t, NULL = default), so the caller need not
+ * synchronise the stream that writes the arrays; the call itself is still BLOCKING (the build reads counters back).  The material indices are counted
+ * against the resident table by a kernel before anything is built: any out of range is RRT_ERR_INVALID_ARG.
+ * MEMORY KEPT: from the first update on, the raytracer keeps the build's temporary device allocations and the scene allocation the update retired, and
+ * the next update reuses each that is large enough (no hipMalloc, no hipFree -- which synchronises the device -- per update).  That is of the order of
+ * 1.1 kB per triangle of the largest update so far (about 1 GB for a million triangles) plus one more copy of the scene.
+ * rrt_raytracer_release_update_memory frees it (RRT_OK for any valid handle; the next update allocates again); creation itself keeps nothing. */
+int rrt_raytracer_set_triangles(rrt_raytracer *rt, uint32_t n_tris, const double *pos, const double *uv, const double *nrm,
+                                const uint32_t *mat, const double *root);
+int rrt_raytracer_set_triangles_device(rrt_raytracer *rt, uint32_t n_tris, const double *d_pos, const double *d_uv, const double *d_nrm,
+                                       const uint32_t *d_mat, const double *root, void *stream);
+int rrt_raytracer_release_update_memory(rrt_raytracer *rt);
+
 /* Scene::draw_scene (engine.rs:186-255) + Canvas::put_pixel (engine.rs:146-158): fills out_fb[width*height]
  * (host memory), 0x00RRGGBB (entities.rs:32-36), row 0 = top; pixels the reference never writes (row 0, and for
  * odd sizes row 1 / the last column) are 0 as in Canvas::new (engine.rs:135).  Blocking. */

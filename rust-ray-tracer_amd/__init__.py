@@ -116,6 +116,11 @@ SYMBOLS = {
     "rrt_raytracer_set_camera": (C.c_int, [_P, C.POINTER(CCamera)]),
     "rrt_raytracer_get_camera": (C.c_int, [_P, C.POINTER(CCamera)]),
     "rrt_camera_look_at": (C.c_int, [Vec3, Vec3, Vec3, C.POINTER(CCamera)]),
+    "rrt_raytracer_set_lights": (C.c_int, [_P, C.POINTER(CLight), C.c_uint32]),
+    "rrt_raytracer_get_lights": (C.c_int, [_P, C.POINTER(CLight), C.c_uint32, _u32p]),
+    "rrt_raytracer_set_triangles": (C.c_int, [_P, C.c_uint32, _dp, _dp, _dp, _u32p, _dp]),
+    "rrt_raytracer_set_triangles_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _dp, _P]),
+    "rrt_raytracer_release_update_memory": (C.c_int, [_P]),
     "rrt_render": (C.c_int, [_P, C.c_uint32, C.c_uint32, _u32p]),
     "rrt_host_buffer_register": (C.c_int, [_P, C.c_size_t]),
     "rrt_host_buffer_unregister": (C.c_int, [_P]),
@@ -367,14 +372,15 @@ class RayTracer:
         RRT_FLAG_RAY_WALK); same pixels.  host_setup=True (RRT_FLAG_HOST_SETUP): octree, index and records built on the host and uploaded (default: built on
         the GPU, csrc/scene_build.hip); same bytes in HBM.  chain_shortcut=False (RRT_FLAG_NO_CHAIN_SHORTCUT): the bundle-filter walk enters every node of a
         one-child chain; same results."""
-        self.scene_data, self.lights, self.origin, self.device = scene_data, list(lights), origin, device
-        cl = (CLight * max(1, len(self.lights)))()
-        for i, l in enumerate(self.lights):
+        self.scene_data, self.origin, self.device = scene_data, origin, device
+        lights = list(lights)                                  # (not kept: lights() asks the library for the list in force)
+        cl = (CLight * max(1, len(lights)))()
+        for i, l in enumerate(lights):
             cl[i] = CLight(l.kind, 0, float(l.intensity), l.v._c())
         flags = (FLAG_NO_CULL if no_cull else 0) | (FLAG_HOST_SETUP if host_setup else 0) | (0 if chain_shortcut else FLAG_NO_CHAIN_SHORTCUT) | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter]
         opt = COptions(surface_offset, max_reflection_depth, flags, *map(float, viewport))
         out = _P()
-        _check(lib().rrt_raytracer_create(scene_data._h, cl, len(self.lights), origin._c(), C.byref(opt), device, C.byref(out)), "rrt_raytracer_create")
+        _check(lib().rrt_raytracer_create(scene_data._h, cl, len(lights), origin._c(), C.byref(opt), device, C.byref(out)), "rrt_raytracer_create")
         self._h = out
 
     @classmethod
@@ -382,16 +388,17 @@ class RayTracer:
                     device: int = 0, root=DEFAULT_ROOT, no_cull: bool = False, box_filter: Optional[str] = None) -> "RayTracer":
         """rrt_raytracer_create_from_arrays: the raytracer straight from the host's arrays (no SceneData / rrt_model, no host copy of the scene)."""
         self = cls.__new__(cls)
-        self.scene_data, self.lights, self.origin, self.device = None, list(lights), origin, device
+        self.scene_data, self.origin, self.device = None, origin, device
+        lights = list(lights)
         a = _marshal_arrays(pos, uv, nrm, mat, materials, textures, root)
-        cl = (CLight * max(1, len(self.lights)))()
-        for i, l in enumerate(self.lights):
+        cl = (CLight * max(1, len(lights)))()
+        for i, l in enumerate(lights):
             cl[i] = CLight(l.kind, 0, float(l.intensity), l.v._c())
         flags = (FLAG_NO_CULL if no_cull else 0) | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter]
         opt = COptions(0.0001, 5, flags, 1.0, 1.0, 1.0)
         out = _P()
         _check(lib().rrt_raytracer_create_from_arrays(a.n, _d(a.pos), _d(a.uv), _d(a.nrm), a.mat.ctypes.data_as(_u32p), len(materials), a.cm, len(a.keep), a.ct, a.r,
-                                                      cl, len(self.lights), origin._c(), C.byref(opt), device, C.byref(out)), "rrt_raytracer_create_from_arrays")
+                                                      cl, len(lights), origin._c(), C.byref(opt), device, C.byref(out)), "rrt_raytracer_create_from_arrays")
         self._h = out
         return self
 
@@ -453,6 +460,61 @@ class RayTracer:
         c = CCamera()
         _check(lib().rrt_raytracer_get_camera(self._h, C.byref(c)), "rrt_raytracer_get_camera")
         return _camera_dict(c)
+
+    # scene updates (rrt.h: rrt_raytracer_set_lights, rrt_raytracer_set_triangles).  No launch of this raytracer may be in flight.
+    def set_lights(self, lights: Iterable[Light]) -> None:
+        """rrt_raytracer_set_lights: the light list of every launch from now on, in this order (host work only)."""
+        lights = list(lights)
+        cl = (CLight * max(1, len(lights)))()
+        for i, l in enumerate(lights):
+            cl[i] = CLight(l.kind, 0, float(l.intensity), l.v._c())
+        _check(lib().rrt_raytracer_set_lights(self._h, cl, len(lights)), "rrt_raytracer_set_lights")
+
+    def lights(self) -> list:
+        """rrt_raytracer_get_lights: the list the kernels get, as Light objects."""
+        n = C.c_uint32(0)
+        _check(lib().rrt_raytracer_get_lights(self._h, None, 0, C.byref(n)), "rrt_raytracer_get_lights")
+        cl = (CLight * max(1, n.value))()
+        _check(lib().rrt_raytracer_get_lights(self._h, cl, n.value, C.byref(n)), "rrt_raytracer_get_lights")
+        return [Light(l.kind, l.intensity, Vector3d(l.v.x, l.v.y, l.v.z)) for l in cl[:n.value]]
+
+    def set_triangles(self, pos, uv, nrm, mat, root=None) -> None:
+        """rrt_raytracer_set_triangles (blocking): new triangles from host arrays ([n,3,3] float64 x 3, [n] uint32 indexing the resident materials); octree,
+        index and records are rebuilt on the GPU, everything else stays resident.  root=None: the root box in force.  All or nothing."""
+        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 9); uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 9)
+        nrm = np.ascontiguousarray(nrm, np.float64).reshape(-1, 9); mat = np.ascontiguousarray(mat, np.uint32).reshape(-1)
+        n = pos.shape[0]
+        if not (uv.shape[0] == nrm.shape[0] == mat.shape[0] == n):
+            raise ValueError(f"set_triangles: {n} positions, {uv.shape[0]} uv, {nrm.shape[0]} normals, {mat.shape[0]} material indices")
+        r = None if root is None else (C.c_double * 6)(*map(float, root))
+        _check(lib().rrt_raytracer_set_triangles(self._h, n, _d(pos), _d(uv), _d(nrm), mat.ctypes.data_as(_u32p), r), "rrt_raytracer_set_triangles")
+
+    def set_triangles_from(self, pos_t, uv_t, nrm_t, mat_t, root=None, stream: Optional[int] = None) -> None:
+        """rrt_raytracer_set_triangles_device (blocking): the same from torch tensors on this raytracer's device -- pos_t / uv_t / nrm_t float64 of 9 n
+        elements, mat_t of n four-byte integers -- read where they lie.  The build waits for the work `stream` (default: the current torch stream) holds, so
+        the kernels that write the tensors need not have finished.  ValueError, before any call, for a tensor that is not on a GPU, not contiguous or of the
+        wrong dtype or size."""
+        import torch
+        try:
+            assert getattr(pos_t, "is_cuda", False), "pos: not a device tensor"
+            n, rem = divmod(pos_t.numel(), 9)
+            assert rem == 0, "pos: the element count is not a multiple of 9"
+            for t, name in ((pos_t, "pos"), (uv_t, "uv"), (nrm_t, "nrm")):
+                _device_tensor(t, 9 * n, 8, name)
+                assert t.dtype == torch.float64, f"{name}: want float64, got {t.dtype}"
+            _device_tensor(mat_t, n, 4, "mat")
+            assert mat_t.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)), f"mat: want a 4-byte integer dtype, got {mat_t.dtype}"
+            for t, name in ((pos_t, "pos"), (uv_t, "uv"), (nrm_t, "nrm"), (mat_t, "mat")):
+                assert t.device.index in (None, self.device), f"{name}: on device {t.device.index}, the raytracer is on {self.device}"
+        except AssertionError as e:
+            raise ValueError(f"set_triangles_from: {e}") from None
+        r = None if root is None else (C.c_double * 6)(*map(float, root))
+        _check(lib().rrt_raytracer_set_triangles_device(self._h, n, _P(pos_t.data_ptr()), _P(uv_t.data_ptr()), _P(nrm_t.data_ptr()), _P(mat_t.data_ptr()), r,
+                                                        _P(_stream(stream))), "rrt_raytracer_set_triangles_device")
+
+    def release_update_memory(self) -> None:
+        """rrt_raytracer_release_update_memory: frees the device memory kept between set_triangles calls (the next one allocates again)."""
+        _check(lib().rrt_raytracer_release_update_memory(self._h), "rrt_raytracer_release_update_memory")
 
     # raytracer.rs:29, batched
     def get_ray_colours(self, origins, dirs) -> np.ndarray:

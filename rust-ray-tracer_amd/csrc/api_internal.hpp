@@ -1,6 +1,6 @@
 // api_internal.hpp -- what the units behind include/rrt.h share: the two handle types, the one place that turns exceptions into status codes, and
-// the few helpers more than one of them needs.  api.cpp: models and process-wide calls; raytracer.cpp: creation and scene set-up; frames.cpp:
-// every launch; multi.cpp: N GPUs of one node.
+// the few helpers more than one of them needs.  api.cpp: models and process-wide calls; raytracer.cpp: creation and scene set-up; scene_update.cpp: lights and
+// triangles of a living raytracer; frames.cpp: every launch; multi.cpp: N GPUs of one node.
 #pragma once
 #include <cstdint>
 #include <new>
@@ -52,6 +52,11 @@ struct rrt_raytracer {
     // The exactness guard of an eye other than the creation one: list, counter and search records in an allocation of the raytracer's own, made when the
     // eye first moves (the build's list is sized for its own finds only).  scene.suspects / scene.n_suspects always describe the eye in force.
     rrt::DevBuf guard_mem;
+    // Scene updates (scene_update.cpp).  The root box in force (rrt_raytracer_set_triangles with root == NULL builds on it again), the share of scene_bytes
+    // that belongs to `built` (adopt_built_scene), and the device memory kept between updates (rrt_raytracer_release_update_memory frees it).
+    rrt::Box root{};
+    uint64_t built_bytes = 0;
+    rrt::BuildMemory update_mem;
 };
 
 namespace rrt {
@@ -95,6 +100,11 @@ int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int w
 struct SceneTables { const rrt_material* mats; uint32_t n_mats; std::vector<rrt_texture> tex; };
 SceneTables tables_of(const Model& M);
 void validate_tables(const SceneTables& T);
+
+// raytracer.cpp, shared with scene_update.cpp: rt->built becomes the raytracer's scene; the checks of a light list (throws Error) and its store.
+void adopt_built_scene(rrt_raytracer* rt);
+void check_lights(const rrt_light* lights, uint32_t n_lights);
+void store_lights(rrt_raytracer* rt, const rrt_light* lights, uint32_t n_lights);
 
 // The warm-up thread (api.cpp: DeviceWarmer): the loaders start it, rrt_raytracer_create waits for it.
 void warm_up_start();

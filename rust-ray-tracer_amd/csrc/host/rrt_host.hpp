@@ -81,6 +81,31 @@ public:
         check(rrt_camera_look_at({eye.x, eye.y, eye.z}, {target.x, target.y, target.z}, {up_hint.x, up_hint.y, up_hint.z}, &c), "look_at");
         check(rrt_raytracer_set_camera(rt_, &c), "look_at");
     }
+    // Scene updates (rrt.h: rrt_raytracer_set_lights, rrt_raytracer_set_triangles): between frames, nothing of this raytracer in flight.
+    void set_lights(const std::vector<Light>& lights) {
+        std::vector<rrt_light> raw;
+        for (const Light& l : lights) raw.push_back(l.raw);
+        check(rrt_raytracer_set_lights(rt_, raw.data(), (uint32_t)raw.size()), "set_lights");
+    }
+    std::vector<Light> lights() const {
+        uint32_t n = 0;
+        check(rrt_raytracer_get_lights(rt_, nullptr, 0, &n), "lights");
+        std::vector<rrt_light> raw(n ? n : 1);
+        check(rrt_raytracer_get_lights(rt_, raw.data(), n, &n), "lights");
+        std::vector<Light> out;
+        for (uint32_t i = 0; i < n; i++) out.push_back(Light{raw[i]});
+        return out;
+    }
+    // pos / uv / nrm: [n][3][3] doubles, mat[n] indexes the resident materials; root = nullptr: the root box in force.  Blocking, all or nothing.
+    void set_triangles(uint32_t n_tris, const double* pos, const double* uv, const double* nrm, const uint32_t* mat, const double* root = nullptr) {
+        check(rrt_raytracer_set_triangles(rt_, n_tris, pos, uv, nrm, mat, root), "set_triangles");
+    }
+    // ... the same from arrays in device memory of this raytracer's device; the build waits for what `stream` (a hipStream_t) holds.  Blocking.
+    void set_triangles_device(uint32_t n_tris, const double* d_pos, const double* d_uv, const double* d_nrm, const uint32_t* d_mat, const double* root = nullptr,
+                              void* stream = nullptr) {
+        check(rrt_raytracer_set_triangles_device(rt_, n_tris, d_pos, d_uv, d_nrm, d_mat, root, stream), "set_triangles_device");
+    }
+    void release_update_memory() { check(rrt_raytracer_release_update_memory(rt_), "release_update_memory"); }
     // Visibility buffers (rrt.h: rrt_render_visibility): the planes of a region (nullptr = the whole frame), each [h][w][4 sub-samples]; blocking.
     void visibility(uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility& planes) {
         check(rrt_render_visibility(rt_, width, height, region, &planes), "visibility");

@@ -1,5 +1,6 @@
 // raytracer.cpp -- rrt_raytracer_create / _create_from_arrays / _destroy and the getters of what the set-up built.  The scene is built by
-// gpu_build_scene or host_build_scene (scene_build.hpp); this unit uploads textures and tables beside it and adopts the result.
+// gpu_build_scene or host_build_scene (scene_build.hpp); this unit uploads textures and tables beside it and adopts the result (adopt_built_scene, which
+// scene_update.cpp calls too).
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -56,10 +57,17 @@ void upload_tables(rrt_raytracer* rt, const std::vector<DevTexture>& texs, const
     S.mats = d_m; S.tex = d_t; S.n_mats = (uint32_t)mats.size(); S.n_tex = (uint32_t)texs.size();
 }
 
-// What either set-up built (rt->built) becomes the raytracer's scene: the kernels' pointers and scalars, the table of rrt_raytracer_get_buffer,
-// the statistics.  A buffer the builder did not keep on the device (null) is reported with size 0.
+}  // namespace
+
+namespace rrt {
+
+// What a set-up built (rt->built) becomes the raytracer's scene: the kernels' pointers and every scalar that follows from the build, the table of
+// rrt_raytracer_get_buffer, the chain counts, scene_bytes.  A buffer the builder did not keep on the device (null) is reported with size 0.  Creation and
+// rrt_raytracer_set_triangles both end here, so neither can forget one of them.  Needs rt->opt; the eye the build searched its exactness guard for is
+// the one in force afterwards (scene.suspects / n_suspects describe it).  Host work only: nothing here can fail.
 void adopt_built_scene(rrt_raytracer* rt) {
     const BuiltScene& G = rt->built;
+    const rrt_options& o = rt->opt;
     DevScene& S = rt->scene;
     S.nodes = G.nodes; S.geom = G.geom; S.attr = G.attr; S.supers = G.supers; S.cboxes = G.cboxes; S.child_boxes = G.child_boxes; S.tboxes = G.tboxes; S.suspects = G.suspects;
     S.n_nodes = G.n_nodes; S.n_slots = G.n_in_tree;
@@ -77,10 +85,39 @@ void adopt_built_scene(rrt_raytracer* rt) {
         {kBufSlotTri, G.slot_tri, (size_t)G.n_slots_total * 4}, {kBufSlotPos, G.slot_pos, (size_t)G.n_slots_total * 4},
         {kBufChains, G.chains, (size_t)G.n_chains * sizeof(DevChain)}};
     for (const auto& k : kept) { rt->bufs[k.id].p = k.p; rt->bufs[k.id].bytes = k.p ? k.bytes : 0; }
+    S.cull_enabled = (o.flags & RRT_FLAG_NO_CULL) ? 0u : 1u;
+    S.cull_half_over_limit = S.cull_limit > 0.0f ? 0.5f / S.cull_limit : 0.0f;
+    S.inner_shrink = (S.cull_enabled && G.all_inside_root) ? (float)(2.0 * G.pad) : 0.0f;   // 2 x the pad the boxes were built with; render.hip, single-candidate child test
+    // The chain shortcut rests on the same "subtree box inside the octant box" argument as inner_shrink; without it the records stay unused.
     rt->n_chains = G.n_chains; rt->n_chain_nodes = G.n_chain_nodes;
-    rt->scene_bytes += (size_t)G.n_nodes * sizeof(DevNode) + (size_t)G.n_slots_total * (sizeof(DevTriGeom) + sizeof(DevTriAttr))
-                     + ((size_t)G.n_sup_records + n_cboxes + n_child_boxes + n_tboxes) * 32;
+    if (!(S.inner_shrink > 0.0f)) { rt->n_chains = 0; rt->n_chain_nodes = 0; }
+    S.chains = (rt->n_chains && !(o.flags & RRT_FLAG_NO_CHAIN_SHORTCUT)) ? G.chains : nullptr;
+    S.n_suspects = G.n_suspects;
+    S.stack_levels = G.max_depth > 1 ? G.max_depth - 1 : 1;   // (only internal nodes push a frame; the deepest level holds leaves)
+    const uint64_t bytes = (uint64_t)G.n_nodes * sizeof(DevNode) + (uint64_t)G.n_slots_total * (sizeof(DevTriGeom) + sizeof(DevTriAttr))
+                         + ((uint64_t)G.n_sup_records + n_cboxes + n_child_boxes + n_tboxes) * 32;
+    rt->scene_bytes += bytes - rt->built_bytes;                           // (an update replaces the share of the scene it retired)
+    rt->built_bytes = bytes;
 }
+
+void check_lights(const rrt_light* lights, uint32_t n_lights) {
+    if (n_lights && !lights) throw Error{RRT_ERR_INVALID_ARG, "null light list"};
+    if (n_lights > RRT_MAX_LIGHTS) throw Error{RRT_ERR_INVALID_ARG, "too many lights (max 16)"};
+    for (uint32_t i = 0; i < n_lights; i++) if (lights[i].kind > 2) throw Error{RRT_ERR_INVALID_ARG, "bad light kind"};
+}
+
+void store_lights(rrt_raytracer* rt, const rrt_light* lights, uint32_t n_lights) {
+    DevScene& S = rt->scene;
+    S.n_lights = n_lights;
+    for (uint32_t i = 0; i < n_lights; i++) {
+        S.lights[i].kind = lights[i].kind; S.lights[i]._pad = 0; S.lights[i].intensity = lights[i].intensity;
+        S.lights[i].v[0] = lights[i].v.x; S.lights[i].v[1] = lights[i].v.y; S.lights[i].v[2] = lights[i].v.z;
+    }
+}
+
+}  // namespace rrt
+
+namespace {
 
 // ---- set-up on the HOST (RRT_FLAG_HOST_SETUP): host_build_scene (host_build.cpp), then textures and tables on the null stream.
 void setup_on_host(rrt_raytracer* rt, const Model& M, rrt_vec3 origin, const rrt_options& o) {
@@ -137,9 +174,8 @@ void setup_on_gpu(rrt_raytracer* rt, const TriSource& src, uint32_t n_tris, cons
 // rrt_raytracer_create and rrt_raytracer_create_from_arrays: everything but where the triangles come from
 int create_raytracer(const rrt_light* lights, uint32_t n_lights, rrt_vec3 origin, const rrt_options* opt, int device, rrt_raytracer** out,
                      const std::function<void(rrt_raytracer*, const rrt_options&)>& setup) {
-    if (!out || (n_lights && !lights)) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
-    if (n_lights > RRT_MAX_LIGHTS) throw Error{RRT_ERR_INVALID_ARG, "too many lights (max 16)"};
-    for (uint32_t i = 0; i < n_lights; i++) if (lights[i].kind > 2) throw Error{RRT_ERR_INVALID_ARG, "bad light kind"};
+    if (!out) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
+    check_lights(lights, n_lights);
     rrt_options o;
     if (opt) o = *opt; else { o.surface_offset = 0.0001; o.max_reflection_depth = 5; o.flags = 0; o.vp_w = o.vp_h = o.vp_d = 1.0; }
     if (o.max_reflection_depth > RRT_MAX_REFLECT) throw Error{RRT_ERR_INVALID_ARG, "max_reflection_depth > 8"};
@@ -158,24 +194,13 @@ int create_raytracer(const rrt_light* lights, uint32_t n_lights, rrt_vec3 origin
     rt->device = device; rt->opt = o;
     setup(rt.get(), o);
 
-    const BuiltScene& G = rt->built;
-    DevScene& S = rt->scene;
-    S.cull_enabled = (o.flags & RRT_FLAG_NO_CULL) ? 0u : 1u;
-    S.cull_half_over_limit = S.cull_limit > 0.0f ? 0.5f / S.cull_limit : 0.0f;
-    S.inner_shrink = (S.cull_enabled && G.all_inside_root) ? (float)(2.0 * G.pad) : 0.0f;   // 2 x the pad the boxes were built with; render.hip, single-candidate child test
-    // The chain shortcut rests on the same "subtree box inside the octant box" argument as inner_shrink; without it the records stay unused.
-    if (!(S.inner_shrink > 0.0f)) { rt->n_chains = 0; rt->n_chain_nodes = 0; }
-    S.chains = (rt->n_chains && !(o.flags & RRT_FLAG_NO_CHAIN_SHORTCUT)) ? G.chains : nullptr;
-    S.n_suspects = G.n_suspects;
-    S.n_lights = n_lights; S.max_reflection_depth = o.max_reflection_depth; S.stack_levels = G.max_depth > 1 ? G.max_depth - 1 : 1;   // (stack_levels: only internal nodes push a frame; the deepest level holds leaves)
+    DevScene& S = rt->scene;                                              // (what follows from the build: adopt_built_scene, in `setup`)
+    S.max_reflection_depth = o.max_reflection_depth;
     S.origin[0] = origin.x; S.origin[1] = origin.y; S.origin[2] = origin.z;
     rt->origin0 = origin;
     rt->cam = rrt_camera{origin, {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};   // the reference's view: down +z, y up (engine.rs:207-211)
     S.surface_offset = o.surface_offset;
-    for (uint32_t i = 0; i < n_lights; i++) {
-        S.lights[i].kind = lights[i].kind; S.lights[i]._pad = 0; S.lights[i].intensity = lights[i].intensity;
-        S.lights[i].v[0] = lights[i].v.x; S.lights[i].v[1] = lights[i].v.y; S.lights[i].v[2] = lights[i].v.z;
-    }
+    store_lights(rt.get(), lights, n_lights);
 #ifdef RRT_PROFILE
     rt->prof_mem = dev_alloc(32 * sizeof(unsigned long long)); HIP_TRY(hipMemset(rt->prof_mem.h, 0, 32 * sizeof(unsigned long long)));
     S.prof = static_cast<unsigned long long*>(rt->prof_mem.h);
@@ -198,7 +223,7 @@ int rrt_raytracer_create(const rrt_model* m, const rrt_light* lights, uint32_t n
         if (!m) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
         const Model& M = m->m;
         return create_raytracer(lights, n_lights, origin, opt, device, out, [&](rrt_raytracer* rt, const rrt_options& o) {
-            rt->gpu_setup = !(o.flags & RRT_FLAG_HOST_SETUP);
+            rt->gpu_setup = !(o.flags & RRT_FLAG_HOST_SETUP); rt->root = M.root;
             if (rt->gpu_setup) { TriSource src; src.tris = M.triangles.data(); setup_on_gpu(rt, src, (uint32_t)M.triangles.size(), M.root, tables_of(M), origin, o); }
             else setup_on_host(rt, M, origin, o);
         });
@@ -222,7 +247,7 @@ int rrt_raytracer_create_from_arrays(uint32_t n_tris, const double* pos, const d
         warm_up_start();
         const Box box = default_root(root);
         return create_raytracer(lights, n_lights, origin, opt, device, out, [&](rrt_raytracer* rt, const rrt_options& o) {
-            rt->gpu_setup = true;
+            rt->gpu_setup = true; rt->root = box;
             TriSource src; src.pos = pos; src.uv = uv; src.nrm = nrm; src.mat = mat;
             setup_on_gpu(rt, src, n_tris, box, T, origin, o);
         });

@@ -642,6 +642,18 @@ __global__ void __launch_bounds__(kBlock) k_pack_triangles(const double* __restr
     t.mat = mat[i]; t._pad = 0;
     out[i] = t;
 }
+// Device arrays of a scene update (rrt_raytracer_set_triangles_device) cannot be checked on the host: the number of material indices outside the resident
+// table, which the frame kernels would read out of bounds.  Grid-stride; a block adds its count with one atomic.
+__global__ void __launch_bounds__(kBlock) k_count_bad_materials(const uint32_t* __restrict__ mat, uint32_t n, uint32_t n_mats, uint32_t* count) {
+    __shared__ uint32_t block_count;
+    if (threadIdx.x == 0) block_count = 0u;
+    __syncthreads();
+    uint32_t mine = 0;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) mine += mat[i] >= n_mats ? 1u : 0u;
+    if (mine) atomicAdd(&block_count, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_count) atomicAdd(count, block_count);
+}
 __global__ void k_set_root(Oct S) {
     for (int a = 0; a < 3; a++) { S.nbox[a] = S.rlo[a]; S.nbox[3 + a] = S.rhi[a]; }
     S.first[0] = kNone; S.second[0] = kNone; S.cnt[0] = 0u; S.child_base[0] = 0u; S.ctr[0] = 0u; S.ctr[1] = 0u; S.ctr[2] = 0u;
@@ -650,7 +662,8 @@ __global__ void k_set_root(Oct S) {
 // ------------------------------------------------------------------------------------------------ host side
 }  // namespace
 
-void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool enable_cull, const double origin[3], void* stream_, BuiltScene& out, const std::function<void()>& after_upload) {
+void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool enable_cull, const double origin[3], void* stream_, BuiltScene& out, const std::function<void()>& after_upload,
+                     BuildMemory* keep) {
     hipStream_t st = (hipStream_t)stream_;
     const bool trace = std::getenv("RRT_SETUP_TRACE") != nullptr;          // developer: host wall time of every stage (synchronising: not the production timing)
     auto lap = [&, last = std::chrono::steady_clock::now()](const char* what) mutable {
@@ -676,9 +689,14 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     const size_t prim_bytes = std::max(scan_bytes, sort_bytes) + 256;
     DevBuf t1;
     DevArena A1;
-    A1.cap = (size_t)n * (sizeof(Triangle) + (src.tris ? 0 : 27 * 8 + 4) + 48 + 3 * 4 + 4 /*rank*/ + 4 * 4 /*key,val in/out*/) + cap * (48 + 4 * 4) + (cap / 8 + 1) * 8 + prim_bytes + (64 << 10);
+    A1.cap = (size_t)n * (sizeof(Triangle) + (src.tris || src.on_device ? 0 : 27 * 8 + 4) + 48 + 3 * 4 + 4 /*rank*/ + 4 * 4 /*key,val in/out*/) + cap * (48 + 4 * 4) + (cap / 8 + 1) * 8 + prim_bytes + (64 << 10);
     lap("events, rocPRIM size queries");
-    t1 = dev_alloc(A1.cap); A1.base = static_cast<char*>(t1.h);
+    // (a temporary: the raytracer's kept piece during an update, else an allocation of this call, freed at its end)
+    auto temporary = [&](DevBuf& own, BuildMemory::Piece BuildMemory::* kept, size_t bytes) -> char* {
+        if (keep) return static_cast<char*>((keep->*kept).at_least(bytes));
+        own = dev_alloc(bytes); return static_cast<char*>(own.h);
+    };
+    A1.base = temporary(t1, &BuildMemory::t1, A1.cap);
     lap("hipMalloc temporaries 1");
 
     HIP_TRY(hipEventRecord(evs[0], st));
@@ -690,7 +708,9 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     hipEvent_t ev_attr = nullptr;
     struct EvOne { hipEvent_t& e; ~EvOne() { if (e) (void)hipEventDestroy(e); } } ev_attr_guard{ev_attr};
     std::unique_ptr<AsyncTask> attr_task;
-    if (!src.tris && n) {
+    if (src.on_device && n) {                                           // the caller's device arrays, read where they lie
+        d_pos = const_cast<double*>(src.pos); d_uv = const_cast<double*>(src.uv); d_nrm = const_cast<double*>(src.nrm); d_mat = const_cast<uint32_t*>(src.mat);
+    } else if (!src.tris && n) {
         d_pos = A1.take<double>(9 * (size_t)n); d_uv = A1.take<double>(9 * (size_t)n); d_nrm = A1.take<double>(9 * (size_t)n); d_mat = A1.take<uint32_t>(n);
         staged_upload(d_pos, src.pos, 72 * (size_t)n, st);
         HIP_TRY(hipEventCreateWithFlags(&ev_attr, hipEventDisableTiming));
@@ -756,7 +776,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     DevBuf t2;
     DevArena A2;
     A2.cap = oct_bytes + (size_t)n_nodes * (4 /*tmp2final*/ + 4 /*newblock*/ + 6 * 4 /*a_*, bases*/ + 48 /*nb*/) + (size_t)(n_nodes + 1) * 4 * 6 + (size_t)n * (2 * 4 + 2 * 24) + (64 << 10);
-    t2 = dev_alloc(A2.cap); A2.base = static_cast<char*>(t2.h);
+    A2.base = temporary(t2, &BuildMemory::t2, A2.cap);
     lap("hipMalloc temporaries 2");
     Remap R{};
     R.n_nodes = n_nodes; R.n_blocks = n_blocks; R.n = n;
@@ -782,7 +802,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
         size_t b = 0;
         HIP_TRY(rocprim::radix_sort_pairs(nullptr, b, key_in, key_out, val_in, val_out, (size_t)n, 0u, key_bits, st));
         void* tmp = prim_tmp;
-        if (b > prim_bytes) { sort_tmp = dev_alloc(b); tmp = sort_tmp.h; } else b = prim_bytes;
+        if (b > prim_bytes) tmp = temporary(sort_tmp, &BuildMemory::sort, b); else b = prim_bytes;
         HIP_TRY(rocprim::radix_sort_pairs(tmp, b, key_in, key_out, val_in, val_out, (size_t)n, 0u, key_bits, st));
     }
     {
@@ -837,7 +857,9 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
         need += (size_t)n_nodes * sizeof(DevNode) + (size_t)(n_slots_total + 1) * (sizeof(DevTriGeom) + sizeof(DevTriAttr));
         need += ((size_t)n_sup + 1 + n_cl + 8 + n_nodes + 8 + n_list_slots + 8) * 32 + (RRT_MAX_SUSPECTS + 2) * sizeof(DevSuspect);
         need += oct_bytes + (size_t)(n_slots_total + 8) * 8 + 17 * 256 + ((size_t)n_chains + 1) * sizeof(DevChain);
-        out.alloc = dev_alloc(need); A3.base = static_cast<char*>(out.alloc.h); A3.cap = need;
+        if (keep && keep->scene.buf.h && keep->scene.bytes >= need) { out.alloc = std::move(keep->scene.buf); out.alloc_bytes = keep->scene.bytes; keep->scene.bytes = 0; }
+        else { if (keep) keep->scene.release(); out.alloc = dev_alloc(need); out.alloc_bytes = need; }
+        A3.base = static_cast<char*>(out.alloc.h); A3.cap = need;
     }
     out.nodes = A3.take<DevNode>(n_nodes); out.geom = A3.take<DevTriGeom>(n_slots_total); out.attr = A3.take<DevTriAttr>(n_slots_total);
     out.supers = A3.take<DevSuper>(n_sup); out.cboxes = A3.take<DevClusterBox>(n_cl + 8); out.child_boxes = A3.take<DevClusterBox>((n_nodes > 1 ? n_nodes - 1 : 0) + 8);
@@ -853,7 +875,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     if (n_in) HIP_TRY(hipMemcpyAsync(out.oct_own_idx, val_out, 4 * (size_t)n_in, hipMemcpyDeviceToDevice, st));
     DevBuf t3; DevArena A4;
     A4.cap = (size_t)(n_cl + 8) * (4 + 24) + (RRT_MAX_SUSPECTS + 2) * sizeof(SuspectRecord) + 4096;
-    t3 = dev_alloc(A4.cap); A4.base = static_cast<char*>(t3.h);
+    A4.base = temporary(t3, &BuildMemory::t3, A4.cap);
     X.slot_tri = out.slot_tri; X.slot_pos = out.slot_pos; X.cluster_node = A4.take<uint32_t>(n_cl + 8); X.cl_lohi = A4.take<float>(6 * (size_t)(n_cl + 8));
     X.supers = out.supers; X.cboxes = out.cboxes; X.tboxes = out.tboxes; X.child_boxes = out.child_boxes; X.nodes = out.nodes; X.geom = out.geom; X.attr = out.attr;
     lap("hipMalloc scene + temporaries 3, octree copies");
@@ -878,6 +900,8 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     if (attr_task) {                                                   // the records are needed from here on (k_idx_slots, k_suspects)
         attr_task->wait();
         HIP_TRY(hipStreamWaitEvent(st, ev_attr, 0));
+    }
+    if (d_pos) {
         hipLaunchKernelGGL(k_pack_triangles, dim3(grid_for(n)), dim3(kBlock), 0, st, d_pos, d_uv, d_nrm, d_mat, n, d_tris);
     }
     hipLaunchKernelGGL(k_idx_slots, dim3(grid_for((size_t)n_slots_total + 8)), dim3(kBlock), 0, st, X);
@@ -913,8 +937,17 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     HIP_TRY(hipEventElapsedTime(&ms, evs[1], evs[2])); out.ms_octree = ms;
     HIP_TRY(hipEventElapsedTime(&ms, evs[2], evs[3])); out.ms_index = ms;
     lap("read-backs, suspects");
-    for (DevBuf* f : {&t3, &t2, &t1}) f->reset();
+    for (DevBuf* f : {&sort_tmp, &t3, &t2, &t1}) f->reset();
     lap("hipFree temporaries");
+}
+
+int launch_count_bad_materials(const uint32_t* d_mat, uint32_t n, uint32_t n_mats, uint32_t* d_count, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(d_count, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return (int)e;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_count_bad_materials, dim3(std::min(grid_for(n), 1024u)), dim3(kBlock), 0, st, d_mat, n, n_mats, d_count);
+    return (int)hipGetLastError();
 }
 
 int launch_suspects_resident(const DevTriGeom* geom, const DevTriAttr* attr, uint32_t n_list_slots, const double eye[3], double pad, uint32_t* d_count, SuspectRecord* d_out, void* stream) {

@@ -18,6 +18,7 @@ namespace rrt {
 // device until the raytracer is destroyed so that rrt_raytracer_get_octree can hand it out.  A buffer the builder does not keep stays null.
 struct BuiltScene {
     DevBuf alloc;   // ONE allocation, carved up into every buffer below
+    size_t alloc_bytes = 0;   // its size (an update hands a retired one to the next build: BuildMemory)
     DevNode* nodes = nullptr; DevTriGeom* geom = nullptr; DevTriAttr* attr = nullptr;
     DevSuper* supers = nullptr; DevClusterBox* cboxes = nullptr; DevClusterBox* child_boxes = nullptr; DevClusterBox* tboxes = nullptr;
     DevSuspect* suspects = nullptr;
@@ -36,13 +37,34 @@ struct BuiltScene {
 
 // The triangles either as the model's array (Triangle records, SceneData.triangles) or as the caller's own arrays (rrt_raytracer_create_from_arrays:
 // pos / uv / nrm [n][3][3] doubles, mat [n]) -- those are uploaded as they are and packed into Triangle records on the device.
-struct TriSource { const Triangle* tris = nullptr; const double* pos = nullptr; const double* uv = nullptr; const double* nrm = nullptr; const uint32_t* mat = nullptr; };
-// Builds the scene on the current HIP device from `src` (HOST arrays, uploaded here through pinned staging).  enable_cull = !RRT_FLAG_NO_CULL.
-// Throws rrt::Error (RRT_ERR_DEPTH when the octree is deeper than RRT_MAX_OCTREE_DEPTH) or HipFail.
+// With on_device set, pos / uv / nrm / mat are DEVICE pointers of the current device (rrt_raytracer_set_triangles_device): the build reads them where they
+// lie, nothing is staged or uploaded, and the caller has ordered the build stream behind whatever wrote them.
+struct TriSource { const Triangle* tris = nullptr; const double* pos = nullptr; const double* uv = nullptr; const double* nrm = nullptr; const uint32_t* mat = nullptr;
+                   bool on_device = false; };
+// Device memory a raytracer keeps between the builds of its scene updates (rrt_raytracer_set_triangles), so that an update makes no hipMalloc and no
+// hipFree (which synchronises the device): the build's three temporaries, the sort's extra storage where rocPRIM wanted any, and the scene allocation the
+// last update retired.  A piece is reused when it is large enough and replaced by a larger one otherwise.
+struct BuildMemory {
+    struct Piece {
+        DevBuf buf; size_t bytes = 0;
+        void* at_least(size_t need) { if (bytes < need || !buf.h) { buf.reset(); bytes = 0; buf = dev_alloc(need); bytes = need; } return buf.h; }
+        void release() { buf.reset(); bytes = 0; }
+    };
+    Piece t1, t2, t3, sort, scene;
+    void release() { for (Piece* p : {&t1, &t2, &t3, &sort, &scene}) p->release(); }
+};
+// Builds the scene on the current HIP device from `src` (host arrays, uploaded here through pinned staging, or device arrays: TriSource).
+// enable_cull = !RRT_FLAG_NO_CULL.  Throws rrt::Error (RRT_ERR_DEPTH when the octree is deeper than RRT_MAX_OCTREE_DEPTH) or HipFail; `out` is then
+// to be discarded.
 // `after_upload` (may be empty) is called once the triangles have been handed to the staging ring, before the octree build: the caller's other uploads
 // (textures) can start there, beside the build, without competing with the triangles for the ring.
+// `keep` (may be null: every temporary is allocated and freed here, as creation does) lends and keeps the device memory of the build; out.alloc may
+// then be keep->scene's allocation.
 void gpu_build_scene(const TriSource& src, uint32_t n_tris, const Box& root, bool enable_cull, const double origin[3], void* stream, BuiltScene& out,
-                     const std::function<void()>& after_upload = {});
+                     const std::function<void()>& after_upload = {}, BuildMemory* keep = nullptr);
+// Number of i < n with d_mat[i] >= n_mats (d_mat in device memory), through the counter d_count (device, 4 bytes): enqueued on `stream`, not synchronised.
+// hipError_t cast to int.
+int launch_count_bad_materials(const uint32_t* d_mat, uint32_t n, uint32_t n_mats, uint32_t* d_count, void* stream);
 
 // The same scene from the model's host octree (host_tree(m)).  Keeps no octree, slot_tri or slot_pos on the device.  Returns after a
 // hipDeviceSynchronize: the host arrays it uploaded from are gone.  Same exceptions.
