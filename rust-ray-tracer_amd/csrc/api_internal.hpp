@@ -30,14 +30,11 @@ struct rrt_raytracer {
     bool stats_pending = false;
     bool launched = false;           // some launch has been recorded in `stats`
     int walk = 0;                    // traversal variant used by this raytracer's frame launches: 0 lane filter, 1 bundle filter, 2 ray walk (see rrt.h)
-    int walk_rays = -1;              // ... and by its per-ray entry points (rrt_get_ray_colours / rrt_intersect_rays / rrt_occluded_rays and their _device forms): -1 = not measured yet (rays_variant, rrt_tune_rays_device)
+    int walk_rays = -1;              // ... and by its per-ray entry points (rrt_get_ray_colours / rrt_intersect_rays / rrt_occluded_rays and their _device forms): -1 = not measured yet (frames.cpp: measure_rays)
     bool variant_forced = false;
-    rrt::DevBuf host_fb;             // device framebuffer kept between rrt_render calls (host-buffer entry point)
-    size_t host_fb_bytes = 0;
-    rrt::DevBuf vis_buf;             // device planes kept between rrt_render_visibility / rrt_pick calls (host-pointer entry points)
-    size_t vis_buf_bytes = 0;
-    rrt::DevBuf tune_buf;            // outputs of the measurement launches of rrt_tune_rays_device, kept between calls
-    size_t tune_buf_bytes = 0;
+    rrt::KeptBuf host_fb;            // device framebuffer kept between rrt_render / rrt_render_progressive calls (host-framebuffer entry points), grown when a larger frame comes
+    rrt::KeptBuf vis_buf;            // device planes kept between rrt_render_visibility / rrt_pick calls (host-pointer entry points)
+    rrt::KeptBuf tune_buf;           // outputs of the measurement launches of rrt_tune_rays_device
     uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records in use (built.n_chains, or 0 where the shortcut's precondition fails: create_raytracer)
     double upload_ms = 0, hip_init_ms = 0, create_ms = 0;   // set-up stages of rrt_raytracer_create besides built.ms_octree / ms_index; wall time of the whole call
     bool gpu_setup = false;          // scene built on the device (default) or on the host (RRT_FLAG_HOST_SETUP)
@@ -92,9 +89,6 @@ inline Box default_root(const double* root) {
     else for (int k = 0; k < 3; k++) { b.lo[k] = -20.0; b.hi[k] = 20.0; }   // utils.rs:145
     return b;
 }
-
-// The visibility planes of a region of a frame (render.hip: visibility_kernel); as the launchers of device_scene.hpp: hipError_t cast to int.
-int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int walk);
 
 // what a set-up needs of a scene besides its triangles: materials and RGB8 textures (borrowed views).  api.cpp
 struct SceneTables { const rrt_material* mats; uint32_t n_mats; std::vector<rrt_texture> tex; };

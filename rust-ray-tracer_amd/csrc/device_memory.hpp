@@ -1,4 +1,4 @@
-// device_memory.hpp -- owners of HIP handles and the bump allocator that carves one device allocation into buffers.
+// device_memory.hpp -- owners of HIP handles, the device buffer kept and grown between calls, and the bump allocator that carves one device allocation into buffers.
 #pragma once
 #include <cstddef>
 
@@ -21,6 +21,14 @@ template <class T, hipError_t (*Destroy)(T)> struct HipOwned {
 using DevBuf = HipOwned<void*, hipFree>;
 using OwnedStream = HipOwned<hipStream_t, hipStreamDestroy>;
 inline DevBuf dev_alloc(size_t bytes) { void* p = nullptr; HIP_TRY(hipMalloc(&p, bytes)); return DevBuf(p); }
+// A device allocation kept between calls and grown when a larger request comes: the old one is freed first, and after a failed allocation it holds nothing.
+struct KeptBuf {
+    DevBuf mem; size_t bytes = 0;
+    void* at_least(size_t need) {
+        if (bytes < need) { mem.reset(); bytes = 0; mem = dev_alloc(need); bytes = need; }
+        return mem.h;
+    }
+};
 
 // Scene buffers are carved out of ONE device allocation (a hipMalloc per buffer costs milliseconds each: 15 of them were most of the teapot's
 // upload time).  Every buffer starts on a 256-byte boundary; an empty one still gets an address of its own.  The arena does not own `base`.

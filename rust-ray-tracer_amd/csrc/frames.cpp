@@ -1,5 +1,7 @@
 // frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility buffers, per-ray queries, the choice of traversal variant, and
-// the statistics of the last launch.
+// the statistics of the last launch.  Every launch goes through ONE seam, timed_launch + record (the raytracer's two events around it, what it traced into rrt_stats), and
+// every measurement of the variants through fastest_variant.  The host forms add a kept device buffer (device_memory.hpp: KeptBuf) or one allocation per call, and
+// staged_download for the way back.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +33,44 @@ FrameParams frame_params(const rrt_raytracer* rt, uint32_t width, uint32_t heigh
     return f;
 }
 
+// ---- the one timed launch and the one record of it.
+// `launch` (returns hipError_t, as int) between the raytracer's two events on `stream`: rrt_last_stats reads the time between them.
+template <class Launch> void timed_launch(rrt_raytracer* rt, void* stream, Launch&& launch) {
+    HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
+    HIP_TRY((hipError_t)launch());
+    HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
+}
+// (blocking) the time between the two events of the last timed_launch
+float elapsed_ms(rrt_raytracer* rt) {
+    float ms = 0;
+    HIP_TRY(hipEventSynchronize(rt->ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, rt->ev0, rt->ev1));
+    return ms;
+}
+// traced pixels (render_kernel): columns [0, 2*(W/2)), rows [H - 2*(H/2) + 1, H) -- of a region, and of the whole frame
+uint64_t traced_pixels_in(const rrt_region& r, uint32_t width, uint32_t height) {
+    const uint64_t col_end = std::min<uint64_t>((uint64_t)r.x0 + r.w, 2ull * (width / 2)), row_begin = std::max<uint64_t>(r.y0, (uint64_t)height - 2ull * (height / 2) + 1);
+    const uint64_t cols = col_end > r.x0 ? col_end - r.x0 : 0, rows = (uint64_t)r.y0 + r.h > row_begin ? (uint64_t)r.y0 + r.h - row_begin : 0;
+    return cols * rows;
+}
+uint64_t traced_pixels(uint32_t width, uint32_t height) { return traced_pixels_in(rrt_region{0, 0, width, height}, width, height); }
+// what the last launch was, into rrt_stats: a frame's size, or (n, 1) for n rays; rays_primary is 0 for a rank's share (not tracked)
+void record(rrt_raytracer* rt, uint32_t width, uint32_t height, uint64_t rays_primary, int variant) {
+    rt->stats.width = width; rt->stats.height = height; rt->stats.rays_primary = rays_primary;
+    rt->stats.scene_bytes = rt->scene_bytes; rt->stats.filter_variant = (uint32_t)variant; rt->stats.origin_plane_triangles = rt->scene.n_suspects;
+    rt->stats_pending = true; rt->launched = true;
+}
+// Every variant twice (the first run warms caches), the second time counts; the fastest, the lowest index on a tie.  time_one(variant) -> ms, blocking.
+template <class TimeOne> int fastest_variant(TimeOne&& time_one) {
+    float best = 0; int best_v = 0;
+    for (int variant = 0; variant < 3; variant++) {
+        (void)time_one(variant);
+        const float ms = time_one(variant);
+        if (variant == 0 || ms < best) { best = ms; best_v = variant; }
+    }
+    return best_v;
+}
+
 // All traversal variants produce identical pixels; which is faster depends on how coherent the rays of a wave are (scene, camera, frame size).
 // The reference renders ONE frame per run, so the first frame of a size costs nothing extra: it runs the variant a measured rule picks (node-coherent
 // walk; bundle filter when the frame has more than ~1200 primary rays per triangle, lane filter below).  A caller that comes back for a SECOND
@@ -55,37 +95,28 @@ void tune_variant(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void
     if (rt->size_measured) return;
     if (++rt->size_frames < 2) return;
     rt->size_measured = true;
-    constexpr int kVariants = 3;
-    float ms[kVariants] = {0, 0, 0};
     if (f.world == 1) {
-        for (int variant = 0; variant < kVariants; variant++)
-            for (int rep = 0; rep < 2; rep++) {
-                HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
-                HIP_TRY((hipError_t)launch_render(rt->scene, f, d_out, stream, variant));
-                HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
-                HIP_TRY(hipEventSynchronize(rt->ev1));
-                HIP_TRY(hipEventElapsedTime(&ms[variant], rt->ev0, rt->ev1));
-            }
-    } else {
-        // One rank's share of a frame is a SHORT launch (a few waves per wave slot): alone it is bound by the latency of its last waves, not by
-        // throughput, and a multi-GPU host keeps several frames in flight on separate streams precisely to hide that (bench.py).
-        // So the variants are compared the way they will run: three launches at once on three streams, wall time per variant.
-        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-        OwnedStream st[3];
-        for (auto& q : st) HIP_TRY(hipStreamCreateWithFlags(&q.h, hipStreamNonBlocking));
-        for (int variant = 0; variant < kVariants; variant++)
-            for (int rep = 0; rep < 2; rep++) {                           // rep 0 warms up
-                HIP_TRY(hipEventRecord(rt->ev0, st[0].h));
-                for (int round = 0; round < 2; round++)
-                    for (auto& q : st) HIP_TRY((hipError_t)launch_render(rt->scene, f, d_out, q.h, variant));   // same pixels from every launch: the overlapping writes agree
-                for (int i = 1; i < 3; i++) HIP_TRY(hipStreamSynchronize(st[i].h));
-                HIP_TRY(hipEventRecord(rt->ev1, st[0].h));
-                HIP_TRY(hipEventSynchronize(rt->ev1));
-                HIP_TRY(hipEventElapsedTime(&ms[variant], rt->ev0, rt->ev1));
-            }
+        rt->walk = fastest_variant([&](int variant) {
+            timed_launch(rt, stream, [&] { return launch_render(rt->scene, f, d_out, stream, variant); });
+            return elapsed_ms(rt);
+        });
+        return;
     }
-    rt->walk = 0;
-    for (int variant = 1; variant < kVariants; variant++) if (ms[variant] < ms[rt->walk]) rt->walk = variant;
+    // One rank's share of a frame is a SHORT launch (a few waves per wave slot): alone it is bound by the latency of its last waves, not by
+    // throughput, and a multi-GPU host keeps several frames in flight on separate streams precisely to hide that (bench.py).
+    // So the variants are compared the way they will run: three launches at once on three streams, wall time per variant.
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    OwnedStream st[3];
+    for (auto& q : st) HIP_TRY(hipStreamCreateWithFlags(&q.h, hipStreamNonBlocking));
+    rt->walk = fastest_variant([&](int variant) {
+        timed_launch(rt, st[0].h, [&] {
+            for (int round = 0; round < 2; round++)
+                for (auto& q : st) HIP_TRY((hipError_t)launch_render(rt->scene, f, d_out, q.h, variant));   // same pixels from every launch: the overlapping writes agree
+            for (int i = 1; i < 3; i++) HIP_TRY(hipStreamSynchronize(st[i].h));
+            return 0;
+        });
+        return elapsed_ms(rt);
+    });
 }
 
 // The per-ray entry points take whatever rays the caller has: a coherent pixel grid or rays in all directions, and the three traversal variants are
@@ -93,25 +124,19 @@ void tune_variant(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void
 // used to measure them on its first kTuneSample rays (each twice, the first run warms caches; same outputs from every variant), and the fastest is
 // kept for later calls.  A forced variant (RRT_FLAG_*_FILTER / RAY_WALK / NO_CULL) is used as is; smaller batches run the frame variant.
 constexpr uint32_t kTuneMinRays = 16384, kTuneSample = 65536;
+// the measurement: launch(variant) on the null stream; the result replaces an earlier one
+template <class Launch> int measure_rays(rrt_raytracer* rt, Launch&& launch) {
+    return rt->walk_rays = fastest_variant([&](int variant) {
+        timed_launch(rt, nullptr, [&] { return launch(variant); });
+        return elapsed_ms(rt);
+    });
+}
+// the policy of the host forms; launch(m, variant) traces the first m rays of the batch
 template <class Launch> int rays_variant(rrt_raytracer* rt, uint32_t n, Launch&& launch) {
     if (rt->variant_forced) return rt->walk;
     if (rt->walk_rays >= 0) return rt->walk_rays;
     if (n < kTuneMinRays) return rt->walk;
-    const uint32_t m = n < kTuneSample ? n : kTuneSample;
-    float best = 0; int best_v = 0;
-    for (int variant = 0; variant < 3; variant++) {
-        float ms = 0;
-        for (int rep = 0; rep < 2; rep++) {
-            HIP_TRY(hipEventRecord(rt->ev0, nullptr));
-            HIP_TRY((hipError_t)launch(m, variant));
-            HIP_TRY(hipEventRecord(rt->ev1, nullptr));
-            HIP_TRY(hipEventSynchronize(rt->ev1));
-            HIP_TRY(hipEventElapsedTime(&ms, rt->ev0, rt->ev1));
-        }
-        if (variant == 0 || ms < best) { best = ms; best_v = variant; }
-    }
-    rt->walk_rays = best_v;
-    return best_v;
+    return measure_rays(rt, [&](int variant) { return launch(std::min(n, kTuneSample), variant); });
 }
 // The device forms (rrt_intersect_rays_device, ...) never measure: the forced variant, else the one kept for per-ray calls, else the frame variant.
 int device_rays_variant(const rrt_raytracer* rt) {
@@ -119,26 +144,10 @@ int device_rays_variant(const rrt_raytracer* rt) {
     return rt->walk_rays >= 0 ? rt->walk_rays : rt->walk;
 }
 // every check of a per-ray call, before any GPU work; n == 0 is a no-op
-void check_rays(const rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, bool any_output) {
+void check_rays(const rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, bool outputs_ok) {
     if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
     if (n && (!origins || !dirs)) throw Error{RRT_ERR_INVALID_ARG, "null ray origins or directions"};
-    if (n && !any_output) throw Error{RRT_ERR_INVALID_ARG, "no output requested: every output pointer is null"};
-}
-// (kernel time of a per-ray launch into rrt_stats, like a frame's)
-void record_rays(rrt_raytracer* rt, uint32_t n, int variant) {
-    rt->stats.width = n; rt->stats.height = 1; rt->stats.rays_primary = n;
-    rt->stats.scene_bytes = rt->scene_bytes; rt->stats.filter_variant = (uint32_t)variant; rt->stats.origin_plane_triangles = rt->scene.n_suspects;
-    rt->stats_pending = true; rt->launched = true;
-}
-
-void record_launch(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t rank, uint32_t world) {
-    rt->stats.width = width; rt->stats.height = height;
-    const uint64_t wt = 2ull * (width / 2), ht = height >= 2 ? (uint64_t)(2 * (height / 2) - 1) : 0;   // traced pixels: see render_kernel
-    rt->stats.rays_primary = world == 1 ? 4ull * wt * ht : 0;   // per-rank share is not tracked
-    (void)rank;
-    rt->stats.scene_bytes = rt->scene_bytes;
-    rt->stats.filter_variant = (uint32_t)rt->walk; rt->stats.origin_plane_triangles = rt->scene.n_suspects;
-    rt->stats_pending = true; rt->launched = true;
+    if (n && !outputs_ok) throw Error{RRT_ERR_INVALID_ARG, "null output: a device form needs one output pointer at least, a host form every one of its outputs"};
 }
 
 // one frame (or one rank's tiles of it) into a device buffer on the caller's stream, timed by the raytracer's events
@@ -146,10 +155,8 @@ void launch_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t r
     DeviceGuard guard(rt->device);
     const FrameParams f = frame_params(rt, width, height, rank, world, tiled);
     tune_variant(rt, f, static_cast<uint32_t*>(d_out), stream);
-    HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
-    HIP_TRY((hipError_t)launch_render(rt->scene, f, static_cast<uint32_t*>(d_out), stream, rt->walk));
-    HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
-    record_launch(rt, width, height, rank, world);
+    timed_launch(rt, stream, [&] { return launch_render(rt->scene, f, static_cast<uint32_t*>(d_out), stream, rt->walk); });
+    record(rt, width, height, world == 1 ? 4 * traced_pixels(width, height) : 0, rt->walk);
 }
 
 // ---- visibility buffers (rrt.h: rrt_render_visibility_device).  One launch of visibility_kernel over the tiles the region touches.
@@ -175,17 +182,6 @@ rrt_region check_visibility(const rrt_raytracer* rt, uint32_t width, uint32_t he
     return r;
 }
 
-void record_visibility(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, int variant) {
-    rt->stats.width = width; rt->stats.height = height;
-    // traced pixels (render_kernel): columns [0, 2*(W/2)), rows [H - 2*(H/2) + 1, H), cut to the region
-    const uint64_t col_end = std::min<uint64_t>((uint64_t)r.x0 + r.w, 2ull * (width / 2)), row_begin = std::max<uint64_t>(r.y0, (uint64_t)height - 2ull * (height / 2) + 1);
-    const uint64_t cols = col_end > r.x0 ? col_end - r.x0 : 0, rows = (uint64_t)r.y0 + r.h > row_begin ? (uint64_t)r.y0 + r.h - row_begin : 0;
-    rt->stats.rays_primary = 4ull * cols * rows;
-    rt->stats.scene_bytes = rt->scene_bytes;
-    rt->stats.filter_variant = (uint32_t)variant; rt->stats.origin_plane_triangles = rt->scene.n_suspects;
-    rt->stats_pending = true; rt->launched = true;
-}
-
 // the planes of region r (checked) into device memory on the caller's stream, timed by the raytracer's events
 void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes, void* stream) {
     VisParams p{};
@@ -197,10 +193,8 @@ void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height,
     p.F.tile_begin = 0; p.F.tile_end = p.tiles_w * ((p.F.row_end + 7) / 8 - p.tile_y0);
     p.hit = d_planes.hit; p.t = d_planes.t; p.u = d_planes.u; p.v = d_planes.v; p.tri = d_planes.tri; p.albedo = d_planes.albedo;
     const int variant = visibility_variant(rt, width, height);
-    HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
-    HIP_TRY((hipError_t)launch_visibility(rt->scene, p, stream, variant));
-    HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
-    record_visibility(rt, width, height, r, variant);
+    timed_launch(rt, stream, [&] { return launch_visibility(rt->scene, p, stream, variant); });
+    record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
 }
 
 // Host forms: the wanted planes of n sub-samples carved out of the raytracer's kept device allocation (grown when a larger request comes), each on a
@@ -208,12 +202,7 @@ void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height,
 size_t kept_planes(rrt_raytracer* rt, size_t n, const void* const want[kPlanes], void* dev[kPlanes]) {
     size_t need = 0;
     for (int k = 0; k < kPlanes; k++) if (want[k]) need += (kPlaneElem[k] * n + 255) & ~(size_t)255;
-    if (rt->vis_buf_bytes < need) {
-        rt->vis_buf.reset(); rt->vis_buf_bytes = 0;
-        rt->vis_buf = dev_alloc(need);
-        rt->vis_buf_bytes = need;
-    }
-    DevArena arena{static_cast<char*>(rt->vis_buf.h), rt->vis_buf_bytes, 0};
+    DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
     for (int k = 0; k < kPlanes; k++) dev[k] = want[k] ? arena.take<char>(kPlaneElem[k] * n) : nullptr;
     return arena.used;
 }
@@ -227,15 +216,8 @@ void visibility_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, cons
     kept_planes(rt, n, host, dev);
     if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
     launch_visibility_frame(rt, width, height, r, planes_of(dev), rt->own_stream);
-    for (int k = 0; k < kPlanes; k++) {
-        if (!host[k]) continue;
-        // as rrt_render: one asynchronous DMA into a page-locked plane, a pageable one through the device's pinned staging ring
-        hipPointerAttribute_t attr{};
-        const bool pinned = hipPointerGetAttributes(&attr, host[k]) == hipSuccess && attr.type == hipMemoryTypeHost;
-        if (!pinned) (void)hipGetLastError();
-        if (pinned) HIP_TRY(hipMemcpyAsync(host[k], dev[k], kPlaneElem[k] * n, hipMemcpyDeviceToHost, rt->own_stream));
-        else staged_download(host[k], dev[k], kPlaneElem[k] * n, rt->own_stream);
-    }
+    // (a page-locked plane's copy is only enqueued here: all of those are in flight before the one wait below)
+    for (int k = 0; k < kPlanes; k++) if (host[k]) staged_download(host[k], dev[k], kPlaneElem[k] * n, rt->own_stream);
     HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the planes are in the caller's memory on return
 }
 
@@ -248,7 +230,7 @@ rrt_pick_result pick_pixel(rrt_raytracer* rt, uint32_t width, uint32_t height, u
     const size_t used = kept_planes(rt, 4, all, dev);                        // the pixel's four sub-samples; sub-sample 0 is the answer
     if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
     launch_visibility_frame(rt, width, height, rrt_region{px, py, 1, 1}, planes_of(dev), rt->own_stream);
-    HIP_TRY(hipMemcpyAsync(back, rt->vis_buf.h, used, hipMemcpyDeviceToHost, rt->own_stream));
+    HIP_TRY(hipMemcpyAsync(back, rt->vis_buf.mem.h, used, hipMemcpyDeviceToHost, rt->own_stream));
     HIP_TRY(hipStreamSynchronize(rt->own_stream));
     rrt_pick_result out{};
     uint8_t hit; std::memcpy(&hit, back, 1); out.hit = hit;
@@ -257,14 +239,43 @@ rrt_pick_result pick_pixel(rrt_raytracer* rt, uint32_t width, uint32_t height, u
     return out;
 }
 
-// the device-side frame of the host-framebuffer entry points: kept and reused from call to call, grown when a larger frame comes
-uint32_t* host_fb(rrt_raytracer* rt, size_t bytes) {
-    if (rt->host_fb_bytes < bytes) {
-        rt->host_fb.reset(); rt->host_fb_bytes = 0;
-        rt->host_fb = dev_alloc(bytes);
-        rt->host_fb_bytes = bytes;
-    }
-    return static_cast<uint32_t*>(rt->host_fb.h);
+// ---- per-ray queries.  The device forms (rrt.h: rrt_intersect_rays_device, ...): no allocation, no copy, no synchronisation; launch(variant) on the caller's stream.
+template <class Launch> int device_ray_query(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, bool any_output, void* stream, Launch&& launch) {
+    check_rays(rt, n, d_origins, d_dirs, any_output);
+    if (n == 0) return RRT_OK;
+    DeviceGuard guard(rt->device);
+    const int variant = device_rays_variant(rt);
+    timed_launch(rt, stream, [&] { return launch(variant); });
+    record(rt, n, 1, n, variant);
+    return RRT_OK;
+}
+// The host forms: rays and the optional max_t up, launch(m, d_origins, d_dirs, d_max_t, d_out, variant) on the null stream (the variant by rays_variant, measured on a
+// first large batch), every output down; blocking.  All of it in ONE device allocation of the call's own: nothing is kept between calls.
+struct HostOut { void* host; size_t elem; };   // an output array of the caller's and its bytes per ray
+template <size_t K, class Launch>
+int host_ray_query(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, const HostOut (&out)[K], Launch&& launch) {
+    bool every_output = true;
+    for (const HostOut& o : out) every_output = every_output && o.host;
+    check_rays(rt, n, origins, dirs, every_output);
+    if (n == 0) return RRT_OK;
+    DeviceGuard guard(rt->device);
+    const size_t N = n;
+    const auto slot = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };   // (what DevArena::take hands out)
+    size_t need = 2 * slot(24 * N) + (max_t ? slot(8 * N) : 0);
+    for (const HostOut& o : out) need += slot(o.elem * N);
+    const DevBuf mem = dev_alloc(need);
+    DevArena arena{static_cast<char*>(mem.h), need, 0};
+    double *d_o = arena.take<double>(3 * N), *d_d = arena.take<double>(3 * N), *d_m = max_t ? arena.take<double>(N) : nullptr;
+    void* d_out[K];
+    for (size_t k = 0; k < K; k++) d_out[k] = arena.take<char>(out[k].elem * N);
+    HIP_TRY(hipMemcpy(d_o, origins, 24 * N, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d, dirs, 24 * N, hipMemcpyHostToDevice));
+    if (max_t) HIP_TRY(hipMemcpy(d_m, max_t, 8 * N, hipMemcpyHostToDevice));
+    const int variant = rays_variant(rt, n, [&](uint32_t m, int v) { return launch(m, d_o, d_d, d_m, d_out, v); });
+    timed_launch(rt, nullptr, [&] { return launch(n, d_o, d_d, d_m, d_out, variant); });
+    record(rt, n, 1, n, variant);
+    for (size_t k = 0; k < K; k++) HIP_TRY(hipMemcpy(out[k].host, d_out[k], out[k].elem * N, hipMemcpyDeviceToHost));
+    return RRT_OK;
 }
 
 }  // namespace
@@ -355,20 +366,11 @@ int rrt_render(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t* out
         if (!out_fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
         DeviceGuard guard(rt->device);
         const size_t bytes = sizeof(uint32_t) * (size_t)width * height;
-        uint32_t* d_fb = host_fb(rt, bytes);
+        uint32_t* d_fb = static_cast<uint32_t*>(rt->host_fb.at_least(bytes));
         if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
         launch_frame(rt, width, height, 0, 1, false, d_fb, rt->own_stream);
-        // Is the caller's framebuffer page-locked (rrt_host_buffer_register, hipHostMalloc, ...)?  Then one asynchronous DMA into it.
-        hipPointerAttribute_t attr{};
-        const bool pinned = hipPointerGetAttributes(&attr, out_fb) == hipSuccess && attr.type == hipMemoryTypeHost;
-        if (!pinned) (void)hipGetLastError();
-        if (pinned) {
-            HIP_TRY(hipMemcpyAsync(out_fb, d_fb, bytes, hipMemcpyDeviceToHost, rt->own_stream));
-            HIP_TRY(hipStreamSynchronize(rt->own_stream));                 // blocking: the frame is in out_fb on return
-            return RRT_OK;
-        }
-        // Pageable framebuffer: through the device's pinned staging ring, chunk DMAs running ahead of the copies out (staging.cpp)
-        staged_download(out_fb, d_fb, bytes, rt->own_stream);
+        staged_download(out_fb, d_fb, bytes, rt->own_stream);              // page-locked out_fb (rrt_host_buffer_register, ...): one DMA; pageable: through the staging ring
+        HIP_TRY(hipStreamSynchronize(rt->own_stream));                     // blocking: the frame is in out_fb on return
         return RRT_OK;
     });
 }
@@ -382,168 +384,99 @@ int rrt_render_progressive(rrt_raytracer* rt, uint32_t width, uint32_t height, u
         if (chunk_rows == 0) chunk_rows = 50;                              // engine.rs:195
         DeviceGuard guard(rt->device);
         const size_t bytes = sizeof(uint32_t) * (size_t)width * height;
-        uint32_t* d_fb = host_fb(rt, bytes);
+        uint32_t* d_fb = static_cast<uint32_t*>(rt->host_fb.at_least(bytes));
         FrameParams f = frame_params(rt, width, height, 0, 1, false);
         tune_variant(rt, f, d_fb, nullptr);                               // (first frame of a new size: picks the filter variant on the full frame)
         HIP_TRY(hipMemsetAsync(d_fb, 0, bytes, nullptr));                  // Canvas::new, engine.rs:135
         std::memset(out_fb, 0, bytes);
         const int64_t H = height, half = H / 2;
-        HIP_TRY(hipEventRecord(rt->ev0, nullptr));
-        for (int64_t cs = -half; cs < half; cs += chunk_rows) {            // engine.rs:198-199
-            const int64_t ce = std::min<int64_t>(cs + chunk_rows, half);
-            // canvas rows of the scene rows [cs, ce): H - (y + H/2); the row that lands on H (y = -H/2) is rejected by put_pixel (engine.rs:152-155)
-            const int64_t r_lo = H - (ce - 1 + half), r_hi = std::min<int64_t>(H - (cs + half), H - 1);   // inclusive
-            if (r_lo <= r_hi) {
-                f.row_begin = (uint32_t)r_lo; f.row_end = (uint32_t)r_hi + 1;
-                f.tile_begin = (f.row_begin / 8) * f.tiles_x; f.tile_end = ((f.row_end + 7) / 8) * f.tiles_x;
-                HIP_TRY((hipError_t)launch_render(rt->scene, f, d_fb, nullptr, rt->walk));
-                HIP_TRY(hipMemcpy(out_fb + (size_t)f.row_begin * width, d_fb + (size_t)f.row_begin * width,
-                                  sizeof(uint32_t) * (size_t)width * (f.row_end - f.row_begin), hipMemcpyDeviceToHost));
+        timed_launch(rt, nullptr, [&] {                                   // ONE pair of events around all the bands
+            for (int64_t cs = -half; cs < half; cs += chunk_rows) {        // engine.rs:198-199
+                const int64_t ce = std::min<int64_t>(cs + chunk_rows, half);
+                // canvas rows of the scene rows [cs, ce): H - (y + H/2); the row that lands on H (y = -H/2) is rejected by put_pixel (engine.rs:152-155)
+                const int64_t r_lo = H - (ce - 1 + half), r_hi = std::min<int64_t>(H - (cs + half), H - 1);   // inclusive
+                if (r_lo <= r_hi) {
+                    f.row_begin = (uint32_t)r_lo; f.row_end = (uint32_t)r_hi + 1;
+                    f.tile_begin = (f.row_begin / 8) * f.tiles_x; f.tile_end = ((f.row_end + 7) / 8) * f.tiles_x;
+                    HIP_TRY((hipError_t)launch_render(rt->scene, f, d_fb, nullptr, rt->walk));
+                    HIP_TRY(hipMemcpy(out_fb + (size_t)f.row_begin * width, d_fb + (size_t)f.row_begin * width,
+                                      sizeof(uint32_t) * (size_t)width * (f.row_end - f.row_begin), hipMemcpyDeviceToHost));
+                }
+                if (on_update) on_update(user, out_fb, width, height, r_lo <= r_hi ? (uint32_t)r_lo : 0u, r_lo <= r_hi ? (uint32_t)(r_hi - r_lo + 1) : 0u);   // canvas.update(), engine.rs:253
             }
-            if (on_update) on_update(user, out_fb, width, height, r_lo <= r_hi ? (uint32_t)r_lo : 0u, r_lo <= r_hi ? (uint32_t)(r_hi - r_lo + 1) : 0u);   // canvas.update(), engine.rs:253
-        }
-        HIP_TRY(hipEventRecord(rt->ev1, nullptr));
-        record_launch(rt, width, height, 0, 1);
+            return 0;
+        });
+        record(rt, width, height, 4 * traced_pixels(width, height), rt->walk);
         return RRT_OK;
     });
 }
 
 int rrt_get_ray_colours(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, uint32_t* colours) {
     return guarded([&]() -> int {
-        if (!rt || (n && (!origins || !dirs || !colours))) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
-        if (n == 0) return (int)RRT_OK;
-        DeviceGuard guard(rt->device);
-        const DevBuf b_o = dev_alloc(sizeof(double) * 3 * (size_t)n), b_d = dev_alloc(sizeof(double) * 3 * (size_t)n), b_c = dev_alloc(sizeof(uint32_t) * (size_t)n);
-        double *d_o = static_cast<double*>(b_o.h), *d_d = static_cast<double*>(b_d.h); uint32_t* d_c = static_cast<uint32_t*>(b_c.h);
-        HIP_TRY(hipMemcpy(d_o, origins, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_d, dirs, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
-        const int variant = rays_variant(rt, n, [&](uint32_t m, int v) { return launch_ray_colours(rt->scene, m, d_o, d_d, d_c, nullptr, v); });
-        HIP_TRY(hipEventRecord(rt->ev0, nullptr));
-        HIP_TRY((hipError_t)launch_ray_colours(rt->scene, n, d_o, d_d, d_c, nullptr, variant));
-        HIP_TRY(hipEventRecord(rt->ev1, nullptr));
-        record_rays(rt, n, variant);
-        HIP_TRY(hipMemcpy(colours, d_c, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
-        return (int)RRT_OK;
+        const HostOut out[] = {{colours, 4}};
+        return host_ray_query(rt, n, origins, dirs, nullptr, out, [&](uint32_t m, const double* o, const double* d, const double*, void* const* x, int variant) {
+            return launch_ray_colours(rt->scene, m, o, d, (uint32_t*)x[0], nullptr, variant);
+        });
     });
 }
 
+// (the host form wants all five outputs; rrt_intersect_rays_device writes the ones it is given)
 int rrt_intersect_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t,
                        uint8_t* hit, double* t, double* u, double* v, uint32_t* tri) {
     return guarded([&]() -> int {
-        if (!rt || (n && (!origins || !dirs || !hit || !t || !u || !v || !tri))) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
-        if (n == 0) return (int)RRT_OK;
-        DeviceGuard guard(rt->device);
-        const size_t N = n;
-        const size_t sizes[8] = {24 * N, 24 * N, 8 * N, N, 8 * N, 8 * N, 8 * N, 4 * N};
-        DevBuf owned[8]; void* bufs[8];
-        for (int i = 0; i < 8; i++) { owned[i] = dev_alloc(sizes[i]); bufs[i] = owned[i].h; }
-        HIP_TRY(hipMemcpy(bufs[0], origins, 24 * N, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(bufs[1], dirs, 24 * N, hipMemcpyHostToDevice));
-        if (max_t) HIP_TRY(hipMemcpy(bufs[2], max_t, 8 * N, hipMemcpyHostToDevice));
-        auto launch = [&](uint32_t m, int v) {
-            return launch_intersect(rt->scene, m, (const double*)bufs[0], (const double*)bufs[1], max_t ? (const double*)bufs[2] : nullptr,
-                                    (uint8_t*)bufs[3], (double*)bufs[4], (double*)bufs[5], (double*)bufs[6], (uint32_t*)bufs[7], nullptr, v);
-        };
-        const int variant = rays_variant(rt, n, launch);
-        HIP_TRY(hipEventRecord(rt->ev0, nullptr));
-        HIP_TRY((hipError_t)launch(n, variant));
-        HIP_TRY(hipEventRecord(rt->ev1, nullptr));
-        record_rays(rt, n, variant);
-        HIP_TRY(hipMemcpy(hit, bufs[3], N, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(t, bufs[4], 8 * N, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(u, bufs[5], 8 * N, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(v, bufs[6], 8 * N, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tri, bufs[7], 4 * N, hipMemcpyDeviceToHost));
-        return (int)RRT_OK;
+        const HostOut out[] = {{hit, 1}, {t, 8}, {u, 8}, {v, 8}, {tri, 4}};
+        return host_ray_query(rt, n, origins, dirs, max_t, out, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
+            return launch_intersect(rt->scene, m, o, d, mt, (uint8_t*)x[0], (double*)x[1], (double*)x[2], (double*)x[3], (uint32_t*)x[4], nullptr, variant);
+        });
     });
 }
 
-// ---- device-resident ray batches (rrt.h): no allocation, no copy, no synchronisation; timed by the raytracer's events on the caller's stream, as rrt_render_device
+int rrt_occluded_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, uint8_t* occluded) {
+    return guarded([&]() -> int {
+        const HostOut out[] = {{occluded, 1}};
+        return host_ray_query(rt, n, origins, dirs, max_t, out, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
+            return launch_occlusion(rt->scene, m, o, d, mt, (uint8_t*)x[0], nullptr, variant);
+        });
+    });
+}
+
 int rrt_intersect_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
                               uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream) {
     return guarded([&]() -> int {
-        check_rays(rt, n, d_origins, d_dirs, d_hit || d_t || d_u || d_v || d_tri);
-        if (n == 0) return (int)RRT_OK;
-        DeviceGuard guard(rt->device);
-        const int variant = device_rays_variant(rt);
-        HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
-        HIP_TRY((hipError_t)launch_intersect(rt->scene, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri, stream, variant));
-        HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
-        record_rays(rt, n, variant);
-        return (int)RRT_OK;
+        return device_ray_query(rt, n, d_origins, d_dirs, d_hit || d_t || d_u || d_v || d_tri, stream, [&](int variant) {
+            return launch_intersect(rt->scene, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri, stream, variant);
+        });
     });
 }
 
 int rrt_get_ray_colours_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream) {
     return guarded([&]() -> int {
-        check_rays(rt, n, d_origins, d_dirs, d_colours != nullptr);
-        if (n == 0) return (int)RRT_OK;
-        DeviceGuard guard(rt->device);
-        const int variant = device_rays_variant(rt);
-        HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
-        HIP_TRY((hipError_t)launch_ray_colours(rt->scene, n, d_origins, d_dirs, d_colours, stream, variant));
-        HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
-        record_rays(rt, n, variant);
-        return (int)RRT_OK;
+        return device_ray_query(rt, n, d_origins, d_dirs, d_colours != nullptr, stream, [&](int variant) {
+            return launch_ray_colours(rt->scene, n, d_origins, d_dirs, d_colours, stream, variant);
+        });
     });
 }
 
 int rrt_occluded_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream) {
     return guarded([&]() -> int {
-        check_rays(rt, n, d_origins, d_dirs, d_occluded != nullptr);
-        if (n == 0) return (int)RRT_OK;
-        DeviceGuard guard(rt->device);
-        const int variant = device_rays_variant(rt);
-        HIP_TRY(hipEventRecord(rt->ev0, (hipStream_t)stream));
-        HIP_TRY((hipError_t)launch_occlusion(rt->scene, n, d_origins, d_dirs, d_max_t, d_occluded, stream, variant));
-        HIP_TRY(hipEventRecord(rt->ev1, (hipStream_t)stream));
-        record_rays(rt, n, variant);
-        return (int)RRT_OK;
+        return device_ray_query(rt, n, d_origins, d_dirs, d_occluded != nullptr, stream, [&](int variant) {
+            return launch_occlusion(rt->scene, n, d_origins, d_dirs, d_max_t, d_occluded, stream, variant);
+        });
     });
 }
 
-// Host form: as rrt_intersect_rays (uploads, the measurement rule of rays_variant on this kernel, one download).
-int rrt_occluded_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, uint8_t* occluded) {
-    return guarded([&]() -> int {
-        check_rays(rt, n, origins, dirs, occluded != nullptr);
-        if (n == 0) return (int)RRT_OK;
-        DeviceGuard guard(rt->device);
-        const size_t N = n;
-        const DevBuf b_o = dev_alloc(24 * N), b_d = dev_alloc(24 * N), b_m = dev_alloc(8 * N), b_x = dev_alloc(N);
-        const double *d_o = static_cast<const double*>(b_o.h), *d_d = static_cast<const double*>(b_d.h), *d_m = max_t ? static_cast<const double*>(b_m.h) : nullptr;
-        uint8_t* d_x = static_cast<uint8_t*>(b_x.h);
-        HIP_TRY(hipMemcpy(b_o.h, origins, 24 * N, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b_d.h, dirs, 24 * N, hipMemcpyHostToDevice));
-        if (max_t) HIP_TRY(hipMemcpy(b_m.h, max_t, 8 * N, hipMemcpyHostToDevice));
-        auto launch = [&](uint32_t m, int v) { return launch_occlusion(rt->scene, m, d_o, d_d, d_m, d_x, nullptr, v); };
-        const int variant = rays_variant(rt, n, launch);
-        HIP_TRY(hipEventRecord(rt->ev0, nullptr));
-        HIP_TRY((hipError_t)launch(n, variant));
-        HIP_TRY(hipEventRecord(rt->ev1, nullptr));
-        record_rays(rt, n, variant);
-        HIP_TRY(hipMemcpy(occluded, d_x, N, hipMemcpyDeviceToHost));
-        return (int)RRT_OK;
-    });
-}
-
-// Blocking: the measurement of rays_variant on a batch that is already on the device, whatever its size; the result replaces an earlier one.  The
+// Blocking: measure_rays on the first kTuneSample rays of a batch that is already on the device, whatever its size; the result replaces an earlier one.  The
 // outputs go to an allocation of the raytracer's own, kept between calls.  The launches run on the null stream: the rays must be complete in memory.
 int rrt_tune_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint32_t* variant_out) {
     return guarded([&]() -> int {
         check_rays(rt, n, d_origins, d_dirs, true);
         if (n && !rt->variant_forced) {
             DeviceGuard guard(rt->device);
-            const uint32_t m = n < kTuneSample ? n : kTuneSample;
+            const uint32_t m = std::min(n, kTuneSample);
             constexpr size_t kBytes = (size_t)kTuneSample * (1 + 8 + 8 + 8 + 4);   // hit, t, u, v, tri of the largest sample (each a multiple of 256 bytes)
-            if (rt->tune_buf_bytes < kBytes) {
-                rt->tune_buf.reset(); rt->tune_buf_bytes = 0;
-                rt->tune_buf = dev_alloc(kBytes);
-                rt->tune_buf_bytes = kBytes;
-            }
-            DevArena arena{static_cast<char*>(rt->tune_buf.h), rt->tune_buf_bytes, 0};
+            DevArena arena{static_cast<char*>(rt->tune_buf.at_least(kBytes)), kBytes, 0};
             uint8_t* hit = arena.take<uint8_t>(m); double *t = arena.take<double>(m), *u = arena.take<double>(m), *v = arena.take<double>(m); uint32_t* tri = arena.take<uint32_t>(m);
-            rt->walk_rays = -1;                                                   // (measure again: rays_variant keeps what it finds)
-            rays_variant(rt, kTuneMinRays, [&](uint32_t, int variant) { return launch_intersect(rt->scene, m, d_origins, d_dirs, d_max_t, hit, t, u, v, tri, nullptr, variant); });
+            measure_rays(rt, [&](int variant) { return launch_intersect(rt->scene, m, d_origins, d_dirs, d_max_t, hit, t, u, v, tri, nullptr, variant); });
         }
         if (variant_out) *variant_out = (uint32_t)device_rays_variant(rt);
         return (int)RRT_OK;
@@ -579,10 +512,7 @@ int rrt_last_stats(const rrt_raytracer* rt_c, rrt_stats* out) {
         if (!rt || !out) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
         if (rt->stats_pending) {
             DeviceGuard guard(rt->device);
-            HIP_TRY(hipEventSynchronize(rt->ev1));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, rt->ev0, rt->ev1));
-            rt->stats.kernel_ms = ms;
+            rt->stats.kernel_ms = elapsed_ms(rt);
             rt->stats_pending = false;
         }
         if (!rt->launched) rt->stats.filter_variant = (uint32_t)rt->walk;   // (before the first launch: the forced variant, or 0)

@@ -67,8 +67,7 @@ struct Member {                      // one rank that lives in this process
     uint32_t* gathered[kMaxSlots] = {};   // rank 0 only: [world][tiles_per_rank][64]
     hipEvent_t done[kMaxSlots] = {};      // rank 0 only: the slot's frame is de-tiled
     hipEvent_t traced[kMaxSlots] = {};    // rank 0 only: its own tiles are traced (start of the wait for the peers)
-    uint32_t* fb = nullptr;               // rank 0 only: frame kept for the host-framebuffer entry point
-    size_t fb_bytes = 0;
+    KeptBuf fb;                           // rank 0 only: frame kept for the host-framebuffer entry point
 };
 
 }  // namespace
@@ -231,7 +230,7 @@ void rrt_multi_destroy(rrt_multi* g) {
             DeviceGuard guard(m.rt->device);
             if (m.comm) (void)rccl().CommDestroy(m.comm);
             for (uint32_t s = 0; s < kMaxSlots; s++) { if (m.stream[s]) (void)hipStreamDestroy(m.stream[s]); if (m.done[s]) (void)hipEventDestroy(m.done[s]); if (m.traced[s]) (void)hipEventDestroy(m.traced[s]); }
-            if (m.fb) (void)hipFree(m.fb);
+            m.fb = KeptBuf{};                                                 // (freed here, on its device)
         }
     } catch (...) {}
     delete g;
@@ -280,13 +279,13 @@ int rrt_render_multi(rrt_multi* g, uint32_t width, uint32_t height, uint32_t* ou
         if (root) {
             if (!out_fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
             DeviceGuard guard(root->rt->device);
-            if (root->fb_bytes < bytes) { if (root->fb) (void)hipFree(root->fb); root->fb = nullptr; root->fb_bytes = 0; HIP_TRY(hipMalloc((void**)&root->fb, bytes)); root->fb_bytes = bytes; }
+            root->fb.at_least(bytes);
         }
         const uint32_t slot = g->next_slot;
-        multi_enqueue(g, width, height, root ? root->fb : nullptr);
+        multi_enqueue(g, width, height, root ? root->fb.mem.h : nullptr);
         if (root) {
             DeviceGuard guard(root->rt->device);
-            HIP_TRY(hipMemcpyAsync(out_fb, root->fb, bytes, hipMemcpyDeviceToHost, root->stream[slot]));   // pinned (rrt_host_buffer_register) or pageable destination
+            HIP_TRY(hipMemcpyAsync(out_fb, root->fb.mem.h, bytes, hipMemcpyDeviceToHost, root->stream[slot]));   // pinned (rrt_host_buffer_register) or pageable destination
         }
         multi_sync(g);                                                    // blocking: the frame is in out_fb on return
         return RRT_OK;

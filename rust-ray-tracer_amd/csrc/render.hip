@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "device_scene.hpp"
 
@@ -1807,7 +1808,21 @@ __global__ __launch_bounds__(64) void occlusion_kernel(const DevScene S, uint32_
 }
 #endif   // RRT_TU_RAYS
 
+// ---- host side of the launchers below: a runtime choice of kernel as a compile-time one.  f receives a std::integral_constant and names its instantiation.
+// (the lane-filter and ray-walk frame kernels have a unit of their own, which must not instantiate the bundle-filter ones: its dispatch is the two-way one)
+template <class F> int with_lane_or_ray_walk(int walk, F&& f) {
+    return walk == kWalkRay ? f(std::integral_constant<int, kWalkRay>{}) : f(std::integral_constant<int, kWalkLane>{});
+}
+template <class F> int with_walk(int walk, F&& f) { return walk == kWalkBundle ? f(std::integral_constant<int, kWalkBundle>{}) : with_lane_or_ray_walk(walk, f); }
+// (two instantiations per walk: the group-record handling of long own lists, clusters.cpp, is compiled in only for scenes that have such lists --
+// its few instructions in the super-cluster loop cost the other scenes 5 % through register allocation alone, measured)
+template <class F> int with_groups(const DevScene& s, F&& f) { return s.has_groups ? f(std::true_type{}) : f(std::false_type{}); }
+
 }  // namespace
+
+// The bundle-filter walk keeps the chain bits of a frame above a 24-bit first_child: a tree of 2^24 nodes or more (fc_mask says so) runs the lane filter
+// in its place.  Same results; such a tree has tens of millions of triangles, far from the coherent frames the bundle filter is for.
+inline int effective_walk(const DevScene& s, int walk) { return (walk == kWalkBundle && s.fc_mask != 0x00FFFFFFu) ? kWalkLane : walk; }
 
 #if RRT_TU_FRAME
 // Forces the code object of this library onto the current device (HIP loads it lazily, ~80 ms for these kernels): called from a helper thread
@@ -1859,40 +1874,35 @@ static int dev_hsaco_launch(const DevScene& s, const FrameParams& f, uint32_t* d
 }
 #endif
 
-// The bundle-filter walk keeps the chain bits of a frame above a 24-bit first_child: a tree of 2^24 nodes or more (fc_mask says so) runs the lane filter
-// in its place.  Same results; such a tree has tens of millions of triangles, far from the coherent frames the bundle filter is for.
+// One frame, or the band / the rank's share of it that f describes: one block per quadrant of its tiles.
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk) {
-    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;
+    walk = effective_walk(s, walk);
     const uint32_t n_tiles = f.tile_end > f.tile_begin ? f.tile_end - f.tile_begin : 0u;
     const uint32_t local_tiles = (n_tiles + f.world - 1) / f.world;
     if (local_tiles == 0) return 0;
-#ifdef RRT_DEV_HSACO
-    if (getenv("RRT_DEV_HSACO")) return dev_hsaco_launch(s, f, d_out, (hipStream_t)stream, walk, dim3(local_tiles * 4), stack_bytes_per_wave(s.stack_levels));
-#endif
-    // (two instantiations per walk: the group-record handling of long own lists, clusters.cpp, is compiled in only for scenes that have such lists --
-    // its few instructions in the super-cluster loop cost the other scenes 5 % through register allocation alone, measured)
-    const dim3 grid(local_tiles * 4), block(64);
     const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    const hipStream_t q = (hipStream_t)stream;
+#ifdef RRT_DEV_HSACO
+    if (getenv("RRT_DEV_HSACO")) return dev_hsaco_launch(s, f, d_out, (hipStream_t)stream, walk, dim3(local_tiles * 4), lds);
+#endif
     if (walk != kWalkBundle) return launch_render_lane_ray(s, f, d_out, stream, walk, local_tiles * 4, lds);
-    if (s.has_groups) hipLaunchKernelGGL((render_kernel<kWalkBundle, true>), grid, block, lds, q, s, f, d_out);
-    else hipLaunchKernelGGL((render_kernel<kWalkBundle, false>), grid, block, lds, q, s, f, d_out);
-    return (int)hipGetLastError();
+    return with_groups(s, [&](auto groups) {
+        hipLaunchKernelGGL((render_kernel<kWalkBundle, groups()>), dim3(local_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, f, d_out);
+        return (int)hipGetLastError();
+    });
 }
 
-// The visibility planes of a region of a frame (device_scene.hpp: VisParams), one block per quadrant of the tiles the region touches.  The bundle
-// filter's fallback for trees of 2^24 nodes or more is launch_render's.
+// The visibility planes of a region of a frame (device_scene.hpp: VisParams), one block per quadrant of the tiles the region touches.
 int launch_visibility_lane_ray(const DevScene& s, const VisParams& p, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
 int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int walk) {
-    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;
+    walk = effective_walk(s, walk);
     const uint32_t n_tiles = p.F.tile_end;
     if (n_tiles == 0) return 0;
-    const dim3 grid(n_tiles * 4), block(64);
     const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
     if (walk != kWalkBundle) return launch_visibility_lane_ray(s, p, stream, walk, n_tiles * 4, lds);
-    if (s.has_groups) hipLaunchKernelGGL((visibility_kernel<kWalkBundle, true>), grid, block, lds, (hipStream_t)stream, s, p);
-    else hipLaunchKernelGGL((visibility_kernel<kWalkBundle, false>), grid, block, lds, (hipStream_t)stream, s, p);
-    return (int)hipGetLastError();
+    return with_groups(s, [&](auto groups) {
+        hipLaunchKernelGGL((visibility_kernel<kWalkBundle, groups()>), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, p);
+        return (int)hipGetLastError();
+    });
 }
 
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
@@ -1914,64 +1924,49 @@ void preload_kernels_lane_ray() {
     (void)hipGetLastError();
 }
 int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
-    const dim3 grid(n_blocks), block(64);
-    const hipStream_t q = (hipStream_t)stream;
-    if (walk == kWalkRay) {
-        if (s.has_groups) hipLaunchKernelGGL((render_kernel<kWalkRay, true>), grid, block, lds, q, s, f, d_out);
-        else hipLaunchKernelGGL((render_kernel<kWalkRay, false>), grid, block, lds, q, s, f, d_out);
-    } else {
-        if (s.has_groups) hipLaunchKernelGGL((render_kernel<kWalkLane, true>), grid, block, lds, q, s, f, d_out);
-        else hipLaunchKernelGGL((render_kernel<kWalkLane, false>), grid, block, lds, q, s, f, d_out);
-    }
-    return (int)hipGetLastError();
+    return with_lane_or_ray_walk(walk, [&](auto w) {
+        return with_groups(s, [&](auto groups) {
+            hipLaunchKernelGGL((render_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, f, d_out);
+            return (int)hipGetLastError();
+        });
+    });
 }
 int launch_visibility_lane_ray(const DevScene& s, const VisParams& p, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
-    const dim3 grid(n_blocks), block(64);
-    const hipStream_t q = (hipStream_t)stream;
-    if (walk == kWalkRay) {
-        if (s.has_groups) hipLaunchKernelGGL((visibility_kernel<kWalkRay, true>), grid, block, lds, q, s, p);
-        else hipLaunchKernelGGL((visibility_kernel<kWalkRay, false>), grid, block, lds, q, s, p);
-    } else {
-        if (s.has_groups) hipLaunchKernelGGL((visibility_kernel<kWalkLane, true>), grid, block, lds, q, s, p);
-        else hipLaunchKernelGGL((visibility_kernel<kWalkLane, false>), grid, block, lds, q, s, p);
-    }
-    return (int)hipGetLastError();
+    return with_lane_or_ray_walk(walk, [&](auto w) {
+        return with_groups(s, [&](auto groups) {
+            hipLaunchKernelGGL((visibility_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, p);
+            return (int)hipGetLastError();
+        });
+    });
 }
 #endif   // RRT_TU_LANE
 
 #if RRT_TU_RAYS
+// The per-ray launchers: one lane per ray, 64 rays per block; the bundle filter's fallback is launch_render's.
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk) {
-    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;    // as launch_render
     if (n == 0) return 0;
-    const dim3 grid((n + 63) / 64), block(64);
-    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk == kWalkBundle) hipLaunchKernelGGL(ray_colour_kernel<kWalkBundle>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_colours);
-    else if (walk == kWalkRay) hipLaunchKernelGGL(ray_colour_kernel<kWalkRay>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_colours);
-    else hipLaunchKernelGGL(ray_colour_kernel<kWalkLane>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_colours);
-    return (int)hipGetLastError();
+    return with_walk(effective_walk(s, walk), [&](auto w) {
+        hipLaunchKernelGGL(ray_colour_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_colours);
+        return (int)hipGetLastError();
+    });
 }
 
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
                      uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream, int walk) {
-    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;    // as launch_render
     if (n == 0) return 0;
-    const dim3 grid((n + 63) / 64), block(64);
-    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk == kWalkBundle) hipLaunchKernelGGL(intersect_kernel<kWalkBundle>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
-    else if (walk == kWalkRay) hipLaunchKernelGGL(intersect_kernel<kWalkRay>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
-    else hipLaunchKernelGGL(intersect_kernel<kWalkLane>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
-    return (int)hipGetLastError();
+    return with_walk(effective_walk(s, walk), [&](auto w) {
+        hipLaunchKernelGGL(intersect_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t,
+                           d_hit, d_t, d_u, d_v, d_tri);
+        return (int)hipGetLastError();
+    });
 }
 
 int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream, int walk) {
-    walk = (walk == 1 && s.fc_mask != 0x00FFFFFFu) ? 0 : walk;    // as launch_render
     if (n == 0) return 0;
-    const dim3 grid((n + 63) / 64), block(64);
-    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk == kWalkBundle) hipLaunchKernelGGL(occlusion_kernel<kWalkBundle>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
-    else if (walk == kWalkRay) hipLaunchKernelGGL(occlusion_kernel<kWalkRay>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
-    else hipLaunchKernelGGL(occlusion_kernel<kWalkLane>, grid, block, lds, (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
-    return (int)hipGetLastError();
+    return with_walk(effective_walk(s, walk), [&](auto w) {
+        hipLaunchKernelGGL(occlusion_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
+        return (int)hipGetLastError();
+    });
 }
 #endif   // RRT_TU_RAYS
 

@@ -92,12 +92,19 @@ void staged_upload(void* dst, const void* src, size_t bytes, void* stream_) {
     // src has been read completely: it may be freed.  dst is complete once `stream` has drained; the slots guard themselves (busy + event).
 }
 
-// Device -> pageable host memory through the ring: chunk DMAs run ahead while the finished chunks are copied out (a pageable hipMemcpy stages through
-// the runtime's own bounce buffers serially; a frame-sized pinned buffer of the caller's own costs milliseconds to allocate -- more than the
-// reference's one frame takes to trace).  Blocking: dst is complete on return.  Everything enqueued on `stream` before the call is waited for.
+// Device -> host memory, page-locked or not.  A page-locked `dst` (rrt_host_buffer_register, hipHostMalloc, ...) gets ONE asynchronous DMA.  A pageable one goes
+// through the ring: chunk DMAs run ahead while the finished chunks are copied out (a pageable hipMemcpy stages through the runtime's own bounce buffers
+// serially; a frame-sized pinned buffer of the caller's own costs milliseconds to allocate -- more than the reference's one frame takes to trace), which
+// waits for everything enqueued on `stream` before the call.  Either way dst is complete once the caller has synchronised `stream` (staging.hpp).
 void staged_download(void* dst, const void* src_dev, size_t bytes, void* stream_) {
     if (!bytes) return;
     hipStream_t stream = (hipStream_t)stream_;
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, dst) == hipSuccess && attr.type == hipMemoryTypeHost) {
+        HIP_TRY(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, stream));
+        return;
+    }
+    (void)hipGetLastError();                                              // ("not registered" is sticky)
     std::lock_guard<std::mutex> lk(g_ring_mu);
     StagingRing& R = ring_of_current_device();
     size_t chunk = (bytes / 8 + 0xFFFFF) & ~(size_t)0xFFFFF;              // about 8 chunks per frame, whole MiB, at most a slot

@@ -1,5 +1,5 @@
 // staging.hpp -- process-wide transfer infrastructure: one ring of page-locked chunks and two non-blocking streams per device, shared by the
-// scene set-up's uploads (scene_build.hip, raytracer.cpp) and by every host-framebuffer frame (frames.cpp).  A failed HIP call throws HipFail.
+// scene set-up's uploads (scene_build.hip, raytracer.cpp) and by every download of a frame or of its visibility planes into host memory (frames.cpp).  A failed HIP call throws HipFail.
 #pragma once
 #include <cstddef>
 
@@ -11,7 +11,8 @@ namespace rrt {
 // must stay valid and unchanged until `stream` has drained (every caller here synchronises the stream before its source goes away).
 void staged_upload(void* dst, const void* src, size_t bytes, void* stream);
 void staged_upload_warm();    // allocates the current device's ring and set-up streams (called from the warm-up thread so that the first upload does not pay for it)
-// Device memory -> pageable host memory through the same ring, blocking (chunk DMAs run ahead of the copies out of the ring).
+// Device memory -> host memory on `stream`: page-locked `dst` as ONE asynchronous DMA, pageable `dst` through the same ring (chunk DMAs run ahead of the
+// copies out of the ring).  The data is in `dst` once the caller has synchronised `stream`; for pageable `dst` it is already there on return.
 void staged_download(void* dst, const void* src_dev, size_t bytes, void* stream);
 // The current device's shared non-blocking stream (hipStream_t) for set-up work and blocking host-framebuffer renders: creating a stream costs
 // milliseconds, the reference's whole frame takes less.  Owned by the library; never destroyed.
