@@ -270,6 +270,47 @@ typedef struct { uint32_t hit, tri; double t, u, v; uint32_t albedo, _pad; } rrt
 /* Sub-sample 0 of canvas pixel (px, py) of a width x height frame in the current pose: one tile's launch.  Blocking. */
 int rrt_pick(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t px, uint32_t py, rrt_pick_result *out);
 
+/* Surface buffers: what the reference holds at the first hit of a frame's primary rays on its way to a colour, and does not keep -- the hit point, the shading
+ * normal, the material and which lights reach the point.  With the albedo plane above this is what a host needs to shade deferred, to relight a still camera
+ * without walking the primaries again, to feed a denoiser its normal and albedo, to bake a moved light's shadow mask, and to form its own shadow, reflection or
+ * ambient-occlusion rays on the GPU for the device-resident batch calls below.
+ * The ray of canvas pixel (px, py), sub-sample s is the one rrt_render_visibility* defines: the primary ray a frame traces for it in the current pose.
+ * Per ray with a hit:
+ *   point    = origin + direction * t (raytracer.rs:39), t as in the visibility plane;
+ *   normal   = the value get_normal_at_intersection returns (raytracer.rs:114-162): the barycentric interpolation, the bump map where the material has one --
+ *              read at the colour texture's texel indices with the bump texture's width, through the tangent frame built from the normal -- and the final
+ *              normalisation: the n that the reference's shading uses for the primary segment;
+ *   material = the index of the hit triangle's material in the material table (rrt_material order);
+ *   lights   = a bit mask over the light list in force, bit k for light k (k < n_lights <= 16): 1 for an Ambient or Directional light; for a Point light 1
+ *              when the reference's shadow query triangle_exists_between_points (raytracer.rs:164-188) from this hit reports "lit" and 0 when it reports
+ *              occluded -- origin = point + normal * surface_offset, direction = light - point, max_t = |direction|: the negation of rrt_occluded_rays for
+ *              that ray.  Bits >= n_lights are 0.  EVERY point light is tested, also those behind the `break` with which the reference's light loop ends at
+ *              the first occluded point light (raytracer.rs:235-237): the lights that loop adds up are [0, ctz(~mask)).
+ * A miss inside the traced area: point = normal = (0.0, 0.0, 0.0), material = 0xFFFFFFFF, lights = 0.  Pixels the reference never traces (canvas row 0, row 1
+ * for odd heights, the last column for odd widths) are written the same way: every element of every requested plane inside the region is written.
+ * vis / d_vis non-NULL: its non-NULL planes are written by the same launch, byte for byte as rrt_render_visibility* writes them for that region -- one launch
+ * then yields everything a deferred shader needs.  All six of its pointers may be NULL.
+ * `lights` NULL: no shadow ray is walked, the launch costs one walk per ray and the shading arithmetic of the hit.
+ * Traversal variant, tuning state and rrt_last_stats as the visibility calls: the forced variant, else the one kept for this frame size, else the first-frame
+ * rule's; the call never triggers or alters a measurement; kernel_ms and filter_variant of this launch, width / height = the frame size, rays_primary = 4 * the
+ * traced pixels inside the region (shadow rays are not counted).
+ * Exactness: the shadow walks are the frame kernels' shadow walks -- default mode, not guarded, the band documented under RRT_FLAG_NO_CULL -- so the mask is the
+ * one a frame uses.
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer as it was: NULL rt, NULL planes struct, all four surface pointers NULL, a bad frame size, a
+ * region with w == 0 or h == 0 or one that sticks out of the frame.
+ * rrt_raytracer_set_camera, rrt_raytracer_set_lights and rrt_raytracer_set_triangles[_device] apply to every surface launch made after they return, and must
+ * not overlap one that is still in flight (rrt_render_surface returns with nothing in flight; rrt_render_surface_device must be synchronised by the caller).
+ * Not covered, as for the visibility calls: the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+/* Output planes of a surface frame.  point, normal: [region.h][region.w][4][3] doubles (x, y, z);  material, lights: [region.h][region.w][4] uint32.
+ * Sub-sample order and region as rrt_visibility / rrt_region.  Any pointer may be NULL, at least one is set. */
+typedef struct { double *point, *normal; uint32_t *material, *lights; } rrt_surface;      /* 32 bytes */
+/* Planes in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default), not synchronised. */
+int rrt_render_surface_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                              const rrt_visibility *d_vis /* may be NULL */, const rrt_surface *d_planes, void *stream);
+/* Planes in host memory; blocking.  Only the requested planes are downloaded (from the device allocation the visibility calls keep). */
+int rrt_render_surface(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                       const rrt_visibility *vis /* may be NULL */, const rrt_surface *planes);
+
 /* Screen-tile partition for N GPUs (one process per GPU): the frame is cut into 8x8-pixel tiles, tile k (row-major)
  * belongs to rank k % world.  Renders this rank's tiles into d_tiles[rrt_tiles_per_rank][64] (tile-major, device).
  * After a gather (or all-gather) of the per-rank buffers (RCCL, done by the caller), rrt_detile_device turns

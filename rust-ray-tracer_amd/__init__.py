@@ -81,6 +81,15 @@ PLANES = ("hit", "t", "u", "v", "tri", "albedo")   # the planes of rrt_visibilit
 PLANE_DTYPES = dict(hit=np.uint8, t=np.float64, u=np.float64, v=np.float64, tri=np.uint32, albedo=np.uint32)
 
 
+class CSurface(C.Structure):         # rrt_surface, 32 bytes: host or device pointers, NULL = plane not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("point", "normal", "material", "lights")]
+
+
+SURFACE_PLANES = ("point", "normal", "material", "lights")   # the planes of rrt_surface, in its order
+SURFACE_DTYPES = dict(point=np.float64, normal=np.float64, material=np.uint32, lights=np.uint32)
+SURFACE_WIDTHS = dict(point=3, normal=3, material=1, lights=1)   # elements per sub-sample
+
+
 class CModelInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_tris", "n_tris_in_tree", "n_nodes", "max_depth", "n_mats", "n_tex", "root_own_count", "max_own_count")]
 
@@ -127,6 +136,8 @@ SYMBOLS = {
     "rrt_render_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "rrt_render_visibility_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), _P]),
     "rrt_render_visibility": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility)]),
+    "rrt_render_surface_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface), _P]),
+    "rrt_render_surface": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface)]),
     "rrt_pick": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CPickResult)]),
     "rrt_tiles_per_rank": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rrt_render_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
@@ -638,6 +649,35 @@ class RayTracer:
         r = CPickResult()
         _check(lib().rrt_pick(self._h, width, height, px, py, C.byref(r)), "rrt_pick")
         return dict(hit=bool(r.hit), tri=r.tri, t=r.t, u=r.u, v=r.v, albedo=r.albedo)
+
+    # surface buffers (rrt.h: rrt_render_surface): hit point, shading normal, material index and light mask of the frame's primary rays
+    def surface(self, width: int, height: int, region=None, planes=SURFACE_PLANES, visibility=()) -> dict:
+        """rrt_render_surface: {plane: array} of the region, only the planes asked for.  point / normal float64 [h][w][4][3], material / lights uint32
+        [h][w][4] (material 0xFFFFFFFF = miss; lights: bit k = light k reaches the point), and the visibility planes named in `visibility` ([h][w][4], as
+        visibility() returns them) from the same launch."""
+        h, w = (height, width) if region is None else (int(region[3]), int(region[2]))
+        out = {n: np.empty((h, w, 4, 3) if SURFACE_WIDTHS[n] == 3 else (h, w, 4), SURFACE_DTYPES[n]) for n in planes}
+        vis = {n: np.empty((h, w, 4), PLANE_DTYPES[n]) for n in visibility}
+        cs = CSurface(**{n: a.ctypes.data for n, a in out.items()})
+        cv = CVisibility(**{n: a.ctypes.data for n, a in vis.items()})
+        _check(lib().rrt_render_surface(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv) if vis else None,
+                                        C.byref(cs)), "rrt_render_surface")
+        out.update(vis)
+        return out
+
+    def surface_into(self, tensors: dict, width: int, height: int, region=None, stream: Optional[int] = None):
+        """rrt_render_surface_device: tensors = {plane: contiguous device tensor}, keys from SURFACE_PLANES (12*w*h float64 for point / normal, 4*w*h four-byte
+        elements for material / lights) and from PLANES (4*w*h elements of the plane's size); enqueued, not synchronised."""
+        n = 4 * (width * height if region is None else int(region[2]) * int(region[3]))
+        for name, t in tensors.items():
+            if name in SURFACE_DTYPES:
+                _device_tensor(t, n * SURFACE_WIDTHS[name], np.dtype(SURFACE_DTYPES[name]).itemsize, name)
+            else:
+                _device_tensor(t, n, np.dtype(PLANE_DTYPES[name]).itemsize, name)
+        cs = CSurface(**{name: t.data_ptr() for name, t in tensors.items() if name in SURFACE_DTYPES})
+        cv = CVisibility(**{name: t.data_ptr() for name, t in tensors.items() if name not in SURFACE_DTYPES})
+        _check(lib().rrt_render_surface_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv), C.byref(cs),
+                                               _P(_stream(stream))), "rrt_render_surface_device")
 
     # pre-bound launchers for per-frame loops (bench.py): all argument conversion is done once, the returned callable is one ctypes call
     def bind_render(self, fb_tensor, width: int, height: int, stream: Optional[int] = None):

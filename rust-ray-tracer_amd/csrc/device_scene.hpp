@@ -142,11 +142,21 @@ struct VisParams {
     uint8_t* hit; double *t, *u, *v; uint32_t* tri; uint32_t* albedo;
 };
 
+// Argument of the surface kernels (render.hip: surface_kernel; rrt.h: rrt_render_surface_device): a VisParams -- frame, region, tile rectangle and the
+// visibility planes, every one of which may be null here -- plus the four surface planes.  point and normal are [rows][columns][4 sub-samples][3], material and
+// lights [rows][columns][4 sub-samples]; a null plane is not written, and a null `lights` also means that no shadow ray is walked.
+struct SurfaceParams {
+    VisParams V;
+    double *point, *normal; uint32_t *material, *lights;
+};
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);
 // the visibility planes of a region of a frame (render.hip: visibility_kernel)
 int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int walk);
+// the surface planes (and any visibility planes) of a region of a frame (render.hip: surface_kernel)
+int launch_surface(const DevScene& s, const SurfaceParams& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk);
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,

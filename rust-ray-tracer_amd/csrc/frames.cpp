@@ -1,4 +1,4 @@
-// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility buffers, per-ray queries, the choice of traversal variant, and
+// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility and surface buffers, per-ray queries, the choice of traversal variant, and
 // the statistics of the last launch.  Every launch goes through ONE seam, timed_launch + record (the raytracer's two events around it, what it traced into rrt_stats), and
 // every measurement of the variants through fastest_variant.  The host forms add a kept device buffer (device_memory.hpp: KeptBuf) or one allocation per call, and
 // staged_download for the way back.
@@ -168,8 +168,9 @@ int visibility_variant(const rrt_raytracer* rt, uint32_t width, uint32_t height)
     return first_frame_variant(rt, width, height);
 }
 
-constexpr int kPlanes = 6;
-constexpr size_t kPlaneElem[kPlanes] = {1, 8, 8, 8, 4, 4};   // hit, t, u, v, tri, albedo: bytes per sub-sample
+constexpr int kPlanes = 6, kSurfacePlanes = 4, kAllPlanes = kPlanes + kSurfacePlanes;
+constexpr size_t kPlaneElem[kAllPlanes] = {1, 8, 8, 8, 4, 4,    // hit, t, u, v, tri, albedo: bytes per sub-sample
+                                           24, 24, 4, 4};        // point, normal, material, lights (rrt_surface)
 
 // every check of a visibility call, before any GPU work; returns the region in force
 rrt_region check_visibility(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* planes) {
@@ -182,8 +183,8 @@ rrt_region check_visibility(const rrt_raytracer* rt, uint32_t width, uint32_t he
     return r;
 }
 
-// the planes of region r (checked) into device memory on the caller's stream, timed by the raytracer's events
-void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes, void* stream) {
+// the kernels' argument for region r (checked) of a frame and these planes
+VisParams vis_params(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes) {
     VisParams p{};
     p.F = frame_params(rt, width, height, 0, 1, false);
     p.F.row_begin = r.y0; p.F.row_end = r.y0 + r.h;
@@ -192,6 +193,12 @@ void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height,
     p.tiles_w = (p.col_end + 7) / 8 - p.tile_x0;
     p.F.tile_begin = 0; p.F.tile_end = p.tiles_w * ((p.F.row_end + 7) / 8 - p.tile_y0);
     p.hit = d_planes.hit; p.t = d_planes.t; p.u = d_planes.u; p.v = d_planes.v; p.tri = d_planes.tri; p.albedo = d_planes.albedo;
+    return p;
+}
+
+// the planes of region r (checked) into device memory on the caller's stream, timed by the raytracer's events
+void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes, void* stream) {
+    const VisParams p = vis_params(rt, width, height, r, d_planes);
     const int variant = visibility_variant(rt, width, height);
     timed_launch(rt, stream, [&] { return launch_visibility(rt->scene, p, stream, variant); });
     record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
@@ -199,11 +206,12 @@ void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height,
 
 // Host forms: the wanted planes of n sub-samples carved out of the raytracer's kept device allocation (grown when a larger request comes), each on a
 // 256-byte boundary; returns the bytes in use.
-size_t kept_planes(rrt_raytracer* rt, size_t n, const void* const want[kPlanes], void* dev[kPlanes]) {
+// (count = kPlanes: the visibility planes; kAllPlanes: those and the surface planes behind them)
+size_t kept_planes(rrt_raytracer* rt, size_t n, const void* const* want, void** dev, int count = kPlanes) {
     size_t need = 0;
-    for (int k = 0; k < kPlanes; k++) if (want[k]) need += (kPlaneElem[k] * n + 255) & ~(size_t)255;
+    for (int k = 0; k < count; k++) if (want[k]) need += (kPlaneElem[k] * n + 255) & ~(size_t)255;
     DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
-    for (int k = 0; k < kPlanes; k++) dev[k] = want[k] ? arena.take<char>(kPlaneElem[k] * n) : nullptr;
+    for (int k = 0; k < count; k++) dev[k] = want[k] ? arena.take<char>(kPlaneElem[k] * n) : nullptr;
     return arena.used;
 }
 rrt_visibility planes_of(void* const p[kPlanes]) { return rrt_visibility{(uint8_t*)p[0], (double*)p[1], (double*)p[2], (double*)p[3], (uint32_t*)p[4], (uint32_t*)p[5]}; }
@@ -237,6 +245,39 @@ rrt_pick_result pick_pixel(rrt_raytracer* rt, uint32_t width, uint32_t height, u
     std::memcpy(&out.t, back + 256, 8); std::memcpy(&out.u, back + 512, 8); std::memcpy(&out.v, back + 768, 8);
     std::memcpy(&out.tri, back + 1024, 4); std::memcpy(&out.albedo, back + 1280, 4);
     return out;
+}
+
+// ---- surface buffers (rrt.h: rrt_render_surface_device).  One launch of surface_kernel over the tiles the region touches; variant, tuning state and stats as the
+// visibility calls.  every check, before any GPU work; returns the region in force
+rrt_region check_surface(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* planes) {
+    check_frame(rt, width, height);
+    if (!planes) throw Error{RRT_ERR_INVALID_ARG, "null surface planes struct"};
+    if (!planes->point && !planes->normal && !planes->material && !planes->lights) throw Error{RRT_ERR_INVALID_ARG, "no surface plane requested: all four pointers are null"};
+    const rrt_region r = region ? *region : rrt_region{0, 0, width, height};
+    if (r.w == 0 || r.h == 0) throw Error{RRT_ERR_INVALID_ARG, "empty region"};
+    if ((uint64_t)r.x0 + r.w > width || (uint64_t)r.y0 + r.h > height) throw Error{RRT_ERR_INVALID_ARG, "region sticks out of the frame"};
+    return r;
+}
+
+void launch_surface_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* stream) {
+    SurfaceParams q{};
+    q.V = vis_params(rt, width, height, r, d_vis);
+    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.lights = d_planes.lights;
+    const int variant = visibility_variant(rt, width, height);
+    timed_launch(rt, stream, [&] { return launch_surface(rt->scene, q, stream, variant); });
+    record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
+}
+
+void surface_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& vis, const rrt_surface& planes) {
+    DeviceGuard guard(rt->device);
+    void* host[kAllPlanes] = {vis.hit, vis.t, vis.u, vis.v, vis.tri, vis.albedo, planes.point, planes.normal, planes.material, planes.lights};
+    void* dev[kAllPlanes];
+    const size_t n = 4 * (size_t)r.w * r.h;
+    kept_planes(rt, n, host, dev, kAllPlanes);
+    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
+    launch_surface_frame(rt, width, height, r, planes_of(dev), rrt_surface{(double*)dev[6], (double*)dev[7], (uint32_t*)dev[8], (uint32_t*)dev[9]}, rt->own_stream);
+    for (int k = 0; k < kAllPlanes; k++) if (host[k]) staged_download(host[k], dev[k], kPlaneElem[k] * n, rt->own_stream);
+    HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the planes are in the caller's memory on return
 }
 
 // ---- per-ray queries.  The device forms (rrt.h: rrt_intersect_rays_device, ...): no allocation, no copy, no synchronisation; launch(variant) on the caller's stream.
@@ -319,6 +360,24 @@ int rrt_render_visibility(rrt_raytracer* rt, uint32_t width, uint32_t height, co
     return guarded([&]() -> int {
         const rrt_region r = check_visibility(rt, width, height, region, planes);
         visibility_to_host(rt, width, height, r, *planes);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_surface_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* d_vis, const rrt_surface* d_planes,
+                              void* stream) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_surface(rt, width, height, region, d_planes);
+        DeviceGuard guard(rt->device);
+        launch_surface_frame(rt, width, height, r, d_vis ? *d_vis : rrt_visibility{}, *d_planes, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_surface(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* vis, const rrt_surface* planes) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_surface(rt, width, height, region, planes);
+        surface_to_host(rt, width, height, r, vis ? *vis : rrt_visibility{}, *planes);
         return RRT_OK;
     });
 }

@@ -110,6 +110,11 @@ public:
     void visibility(uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility& planes) {
         check(rrt_render_visibility(rt_, width, height, region, &planes), "visibility");
     }
+    // Surface buffers (rrt.h: rrt_render_surface): hit point, shading normal, material index and light mask of a region's primary rays (nullptr = the whole
+    // frame), point / normal [h][w][4][3], material / lights [h][w][4]; vis (may be nullptr): visibility planes from the same launch.  Blocking.
+    void surface(uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface& planes, const rrt_visibility* vis = nullptr) {
+        check(rrt_render_surface(rt_, width, height, region, vis, &planes), "surface");
+    }
     // what sub-sample 0 of canvas pixel (px, py) sees; blocking
     rrt_pick_result pick(uint32_t width, uint32_t height, uint32_t px, uint32_t py) {
         rrt_pick_result r;

@@ -31,8 +31,8 @@
 #include "device_scene.hpp"
 
 // The library compiles this file THREE times (csrc/Makefile), same device functions, different code-generation switches per group of kernels:
-//   -DRRT_TU=1  the bundle-filter frame kernel and visibility kernel, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
-//   -DRRT_TU=3  the lane-filter and ray-walk frame and visibility kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
+//   -DRRT_TU=1  the bundle-filter frame, visibility and surface kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
+//   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility and surface kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
 //   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
@@ -1712,6 +1712,129 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const Dev
     if (P.tri) P.tri[i] = tri;
 }
 
+// Surface buffers (rrt.h: rrt_render_surface_device): per primary ray of a region of the frame the hit point, the shading normal, the material index and
+// the mask of the lights that reach the point -- what trace_colour holds for the primary segment on its way to a colour -- and, if asked for, the
+// visibility planes of the same rays from the same launch.  Waves, rays, guard, region and plane layout are visibility_kernel's (point and normal: three
+// doubles per sub-sample, 384 B per pixel row of a wave).
+// ONE call site of the walk, as in trace_colour: the first turn of the loop walks the primary rays (one_origin, guarded), every later turn the shadow rays
+// of all hit lanes towards ONE point light, with the arguments trace_colour gives a shadow walk (any_ok, filter_ok, not one_origin, far anchor).  Which
+// turn it is, and which light, is wave-uniform: the lights are kernel arguments.  Every point light is walked, also those behind the reference's `break`
+// (raytracer.rs:235-237).  Without a lights plane (a kernel argument: wave-uniform) the loop ends after the first turn.
+// No lane leaves before the last walk: the walks need the whole wave in uniform control flow.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevScene S, const SurfaceParams Q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t lane = threadIdx.x;
+    const Stack stk{lds + kParkBytes, lane};
+    const VisParams& P = Q.V;
+    const FrameParams& F = P.F;
+    // Block order, tile quadrant, pixel, sub-sample and direction: visibility_kernel's, restated (see there)
+    uint32_t blk = blockIdx.x;
+    if (F.xcd_chunk) {
+        const uint32_t C = F.xcd_chunk, full = (gridDim.x / (8u * C)) * (8u * C);
+        if (blk < full) { const uint32_t xcd = blk & 7u, i = blk >> 3; blk = ((i / C) * 8u + xcd) * C + (i % C); }
+    }
+    const uint32_t local_tile = blk >> 2, quad = blk & 3u;
+    const uint32_t pix = lane >> 2, sub = lane & 3u;
+    const bool tile_ok = local_tile < F.tile_end;
+    const uint32_t tx = P.tile_x0 + (tile_ok ? local_tile % P.tiles_w : 0), ty = P.tile_y0 + (tile_ok ? local_tile / P.tiles_w : 0);
+    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
+    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
+    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
+    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;   // col_end <= width, row_end <= height
+    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;   // the pixels the reference traces (render_kernel)
+    const int32_t x = (int32_t)px - W / 2;
+    const int32_t y = (H - H / 2) - (int32_t)py;
+    const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;                      // engine.rs:207-236
+    const double yd = (sub & 2u) ? ((double)y + 0.5) : (double)y;
+    const double sa = xd * F.x_scale, sb = yd * F.y_scale, sc = F.z_value;             // (right*a + up*b) + forward*c, five operations per component: rrt.h, rrt_camera
+    const V3 o = ld3(S.origin), d = mk((F.right[0] * sa + F.up[0] * sb) + F.forward[0] * sc,
+                                       (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
+                                       (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const bool first_ok = !origin_ray_in_suspect_plane(S, o, d);                      // exactness guard of the primary walk (visibility_kernel)
+    const uint32_t n_lights = Q.lights ? S.n_lights : 0u;                              // no lights plane: no shadow walk
+    bool found = false;
+    bool shadow = false;                                                               // wave-uniform: the walk about to start is a shadow walk, towards light li
+    uint32_t li = 0;
+    double t = 0, u = 0, v = 0;
+    uint32_t tri = kNone, mat = kNone, mask = 0;
+    uint32_t col = traced ? 0x00FFFFFFu : 0u;                                          // WHITE, raytracer.rs:109-111; 0 as Canvas::new where nothing is traced
+    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
+    V3 ro = o, rd = d; double rmax = kInf;
+    for (;;) {
+        double wt; uint32_t wslot;
+        const bool active = shadow ? found : traced;
+        if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, active, shadow, shadow || first_ok, ro, rd, rmax, wt, wslot);
+        else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, active, shadow, shadow || first_ok, !shadow, ro, rd, rmax, wt, wslot);
+        if (!shadow) {
+            shadow = true;
+            found = traced && wslot != kNone;
+            if (found) {
+                // --- hit: raytracer.rs:39-57, as trace_colour
+                double t2;
+                mt_full(S.geom + wslot, o, d, t2, u, v);
+                const DevTriAttr& A = S.attr[wslot];
+                t = wt;
+                tri = A.orig;
+                p = o + d * wt;                                                          // raytracer.rs:39
+                mat = A.mat;
+                const DevMaterial& M = S.mats[mat];
+                const DevTexture T = M.tex_desc;
+                const double w = 1.0 - u - v;                                            // raytracer.rs:43
+                const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;            // raytracer.rs:45-47
+                const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;            // raytracer.rs:48-50
+                const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);    // raytracer.rs:52
+                const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);  // raytracer.rs:53
+                const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);      // raytracer.rs:55
+                col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
+                // get_normal_at_intersection, raytracer.rs:114-162
+                V3 nn = (ld3(A.nrm + 3) * u + ld3(A.nrm + 6) * v) + ld3(A.nrm) * w;      // raytracer.rs:122-124
+                if (M.bump >= 0) {
+                    const DevTexture B = M.bump_desc;
+                    const uint8_t* bp = B.rgb + 3ull * ((uint64_t)B.width * tyi + txi);  // raytracer.rs:127-128 (colour-texture indices, bump width)
+                    V3 bv = mk((double)bp[0], (double)bp[1], (double)bp[2]);
+                    bv = normalised(bv);
+                    bv = (bv * 2.0) - mk(1.0, 1.0, 1.0);                                 // raytracer.rs:130-135
+                    V3 tg = cross(nn, mk(0.0, 1.0, 0.0));                                // raytracer.rs:137-141
+                    double len_tg = length(tg);
+                    if (len_tg == 0.0) { tg = cross(nn, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }   // raytracer.rs:143-149
+                    tg = div3(tg, len_tg);                                               // raytracer.rs:151
+                    const V3 bt = normalised(cross(nn, tg));                             // raytracer.rs:152
+                    nn = mk(dot(bv, tg), dot(bv, bt), dot(bv, nn));                      // raytracer.rs:154-158
+                }
+                n = normalised(nn);                                                      // raytracer.rs:161
+            }
+            if (!__any(found)) break;                                                    // no hit in the wave: nothing to ask the lights
+        } else {
+            if (found && wslot == kNone) mask |= 1u << li;                               // triangle_exists_between_points says "lit" for None, raytracer.rs:181-187
+            li++;
+        }
+        // the light list up to the next point light (raytracer.rs:205-255): Ambient and Directional lights reach every hit
+        while (li < n_lights && S.lights[li].kind != 1u) { if (found) mask |= 1u << li; li++; }
+        if (li >= n_lights) break;
+        const V3 dir = ld3(S.lights[li].v) - p;                                          // the shadow ray, raytracer.rs:164-188, as trace_colour forms it
+        ro = p + n * S.surface_offset;
+        rd = dir;
+        rmax = length(dir);
+    }
+    if (!in_region) return;
+    const size_t i = (((size_t)(py - F.row_begin) * (P.col_end - P.col_begin)) + (px - P.col_begin)) * 4 + sub;
+    if (Q.point) { Q.point[3 * i] = p.x; Q.point[3 * i + 1] = p.y; Q.point[3 * i + 2] = p.z; }
+    if (Q.normal) { Q.normal[3 * i] = n.x; Q.normal[3 * i + 1] = n.y; Q.normal[3 * i + 2] = n.z; }
+    if (Q.material) Q.material[i] = mat;
+    if (Q.lights) Q.lights[i] = mask;
+    // the visibility planes, as visibility_kernel writes them
+    if (P.albedo) P.albedo[i] = col;
+    if (P.hit) P.hit[i] = found ? 1 : 0;
+    if (P.t) P.t[i] = t;
+    if (P.u) P.u[i] = u;
+    if (P.v) P.v[i] = v;
+    if (P.tri) P.tri[i] = tri;
+}
+
 #endif   // RRT_TU_FRAME || RRT_TU_LANE
 #if RRT_TU_FRAME
 __global__ __launch_bounds__(256) void detile_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t world, uint32_t tiles_per_rank,
@@ -1905,6 +2028,20 @@ int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int w
     });
 }
 
+// The surface planes of a region of a frame (device_scene.hpp: SurfaceParams): the grid of launch_visibility.
+int launch_surface_lane_ray(const DevScene& s, const SurfaceParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+int launch_surface(const DevScene& s, const SurfaceParams& q, void* stream, int walk) {
+    walk = effective_walk(s, walk);
+    const uint32_t n_tiles = q.V.F.tile_end;
+    if (n_tiles == 0) return 0;
+    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
+    if (walk != kWalkBundle) return launch_surface_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
+    return with_groups(s, [&](auto groups) {
+        hipLaunchKernelGGL((surface_kernel<kWalkBundle, groups()>), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
+        return (int)hipGetLastError();
+    });
+}
+
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
     const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
     const uint32_t tpr = (tiles_x * tiles_y + world - 1) / world;
@@ -1935,6 +2072,14 @@ int launch_visibility_lane_ray(const DevScene& s, const VisParams& p, void* stre
     return with_lane_or_ray_walk(walk, [&](auto w) {
         return with_groups(s, [&](auto groups) {
             hipLaunchKernelGGL((visibility_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, p);
+            return (int)hipGetLastError();
+        });
+    });
+}
+int launch_surface_lane_ray(const DevScene& s, const SurfaceParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+    return with_lane_or_ray_walk(walk, [&](auto w) {
+        return with_groups(s, [&](auto groups) {
+            hipLaunchKernelGGL((surface_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
             return (int)hipGetLastError();
         });
     });
