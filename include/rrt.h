@@ -190,8 +190,8 @@ int rrt_raytracer_get_camera(const rrt_raytracer *rt, rrt_camera *out);
  * component is non-finite. */
 int rrt_camera_look_at(rrt_vec3 eye, rrt_vec3 target, rrt_vec3 up_hint, rrt_camera *out);
 
-/* Scene updates: the lights and the triangles of a living raytracer, between frames.  Materials, textures, options, flags and the camera pose stay as they
- * are, resident; nothing is uploaded or allocated again that does not depend on the triangles.  All five calls follow the contract of
+/* Scene updates: the lights, the material table and the triangles of a living raytracer, between frames.  Textures, options, flags and the camera pose stay as
+ * they are, resident; nothing is uploaded or allocated again that does not depend on what changed.  All the calls follow the contract of
  * rrt_raytracer_set_camera: every launch made after the call returns sees the change (frames, tiles, progressive frames, the visibility calls, the per-ray
  * calls in host and device form, and the rrt_multi_* calls through the raytracers they hold: set it on each of them, or on each rank, between
  * rrt_multi_sync and the next enqueue), and the call must not overlap launches of this raytracer that are still in flight.
@@ -202,6 +202,16 @@ int rrt_camera_look_at(rrt_vec3 eye, rrt_vec3 target, rrt_vec3 up_hint, rrt_came
  * rrt_raytracer_get_lights: the list in force; out may be NULL to ask for the count only, capacity < count with a non-NULL out is RRT_ERR_INVALID_ARG. */
 int rrt_raytracer_set_lights(rrt_raytracer *rt, const rrt_light *lights, uint32_t n_lights);
 int rrt_raytracer_get_lights(const rrt_raytracer *rt, rrt_light *out, uint32_t capacity, uint32_t *n_lights);
+/* rrt_raytracer_set_materials: a new material table over the resident one, as rrt_raytracer_set_camera BLOCKING, applied to every launch made after it returns
+ * and not to overlap launches in flight.  One small host-to-device copy into the table at its resident address: no texture is uploaded, nothing is rebuilt, the
+ * traversal variants measured so far stay.  ALL OR NOTHING, RRT_ERR_INVALID_ARG with the table in force untouched for: n_mats different from the resident count
+ * (the triangles index the table), a NULL list with n_mats > 0, `tex` outside [0, n_tex), `bump` outside [-1, n_tex), and -- the check of creation -- a bump map
+ * too small for the texel indices of the colour texture that address it (raytracer.rs:127-128).  Works on a RRT_FLAG_HOST_SETUP raytracer too.  Afterwards the
+ * raytracer is, frame for frame and plane for plane, the one rrt_raytracer_create_from_arrays makes from the same arrays with the new table; what kept surface
+ * planes are worth after an edit is tabulated under rrt_shade_surface below.
+ * rrt_raytracer_get_materials: the table in force; out may be NULL to ask for the count only, capacity < count with a non-NULL out is RRT_ERR_INVALID_ARG. */
+int rrt_raytracer_set_materials(rrt_raytracer *rt, const rrt_material *mats, uint32_t n_mats);
+int rrt_raytracer_get_materials(const rrt_raytracer *rt, rrt_material *out, uint32_t capacity, uint32_t *n_mats);
 /* rrt_raytracer_set_triangles: new triangles, arrays as rrt_raytracer_create_from_arrays (mat[i] indexes the RESIDENT material table and is checked against
  * it).  BLOCKING.  Afterwards the raytracer is what rrt_raytracer_create_from_arrays would have made from these arrays with this raytracer's materials,
  * textures, options and flags, the lights and the camera pose in force: every RRT_BUF_* buffer, rrt_raytracer_get_octree, rrt_raytracer_get_chain_info,
@@ -310,6 +320,49 @@ int rrt_render_surface_device(rrt_raytracer *rt, uint32_t width, uint32_t height
 /* Planes in host memory; blocking.  Only the requested planes are downloaded (from the device allocation the visibility calls keep). */
 int rrt_render_surface(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
                        const rrt_visibility *vis /* may be NULL */, const rrt_surface *planes);
+
+/* Shading from kept buffers: finishes a frame from the planes rrt_render_surface* wrote for it, with the lights and materials in force NOW, without walking
+ * a primary ray.  For relighting and material edits under a still camera: move a dimmer, turn the sun, edit a material, shade again.
+ * vis / d_vis and planes / d_planes are the structs the caller gave rrt_render_surface[_device] for the same frame size and region, in that layout
+ * ([region.h][region.w][4], point and normal x 3 doubles).  READ: vis->albedo, planes->point, planes->normal, planes->material -- all four required -- and
+ * planes->lights, which may be NULL.  The other five visibility pointers are ignored.  WRITTEN: out_fb / d_fb, [region.h][region.w] pixels, 0x00RRGGBB: each
+ * the reference's Color::mix (entities.rs:49-69) of its four sub-samples; pixels the reference never traces (canvas row 0, row 1 of an odd height, the last
+ * column of an odd width) are 0; every pixel of the region is written.  With region == NULL the output is exactly the framebuffer of rrt_render_device.
+ * Input and output must not overlap.
+ * CONTRACT.  If the planes are the ones rrt_render_surface* wrote for this frame size, region, pose and scene, the output is the same region of the frame
+ * rrt_render produces with the lights and materials in force now, bit for bit.  Keeping the planes valid is the caller's business:
+ *
+ *   change since the planes were written                                              planes that are stale
+ *   rrt_raytracer_set_camera, rrt_raytracer_set_triangles[_device]                    all
+ *   set_lights: position of a Point light, kind or index of any light, list length    `lights` only (pass it as NULL)
+ *   set_lights: intensities, or the vector of an Ambient or Directional light         none
+ *   set_materials: `tex` of a material                                                `albedo`, `normal` (the bump texel is read at the colour texture's indices)
+ *   set_materials: `bump`                                                             `normal`
+ *   set_materials: ka, kd, ks, ns, kr                                                 none
+ *
+ * Per sub-sample of a traced pixel: material >= n_mats (0xFFFFFFFF, a miss, included) gives 0x00FFFFFF, the reference's background (raytracer.rs:109-111) -- no
+ * table is read out of bounds whatever the planes hold.  Otherwise the sub-sample is the primary segment's hit as the reference holds it after
+ * get_normal_at_intersection: point, normal, material, colour = the low 24 bits of albedo; the segment's direction is recomputed from the pixel, the sub-sample
+ * and the current pose by the five operations of rrt_camera.  With `lights`, the lights the depth-0 sum adds up are [0, min(ctz(~mask), n_lights)) and no depth-0
+ * shadow ray is walked; with `lights` NULL the depth-0 shadow rays are formed and walked as a frame walks them, the `break` at the first occluded point light
+ * (raytracer.rs:235-237) included.  From there on it is the reference's get_ray_colour: compute_lighting_intensity, the reflection chain up to
+ * max_reflection_depth with its shadow rays always walked, the u8 quantisation at every level of the unwind.
+ * Exactness: no primary ray is walked, so the primary segment's guard (rrt_stats.origin_plane_triangles) has nothing to do; every walk of this call is a
+ * secondary walk of a frame -- default mode, not guarded, the band documented under RRT_FLAG_NO_CULL.
+ * Cost: pixels none of whose neighbours in a 4x4 block hits a mirror, shaded with a mask, walk nothing at all.
+ * Traversal variant, tuning state and rrt_last_stats as the surface calls: the forced variant, else the one kept for this frame size, else the first-frame rule's;
+ * the call never triggers or alters a measurement; kernel_ms and filter_variant of this launch, width / height = the frame size, rays_primary = 4 * the traced
+ * pixels inside the region.
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer and the output as they were: NULL rt, either struct NULL, a required plane NULL, a NULL
+ * output, a bad frame size, a region with w == 0 or h == 0 or one that sticks out of the frame.
+ * rrt_shade_surface_device: planes and framebuffer in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default), not synchronised.
+ * rrt_shade_surface: planes and framebuffer in host memory; blocking: the planes are uploaded into the device allocation the visibility calls keep, the region's
+ * pixels downloaded, and nothing is in flight on return.
+ * Not covered, as for the visibility calls: the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+int rrt_shade_surface_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                             const rrt_visibility *d_vis, const rrt_surface *d_planes, void *d_fb, void *stream);
+int rrt_shade_surface(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                      const rrt_visibility *vis, const rrt_surface *planes, uint32_t *out_fb);
 
 /* Screen-tile partition for N GPUs (one process per GPU): the frame is cut into 8x8-pixel tiles, tile k (row-major)
  * belongs to rank k % world.  Renders this rank's tiles into d_tiles[rrt_tiles_per_rank][64] (tile-major, device).

@@ -127,6 +127,8 @@ SYMBOLS = {
     "rrt_camera_look_at": (C.c_int, [Vec3, Vec3, Vec3, C.POINTER(CCamera)]),
     "rrt_raytracer_set_lights": (C.c_int, [_P, C.POINTER(CLight), C.c_uint32]),
     "rrt_raytracer_get_lights": (C.c_int, [_P, C.POINTER(CLight), C.c_uint32, _u32p]),
+    "rrt_raytracer_set_materials": (C.c_int, [_P, C.POINTER(CMaterial), C.c_uint32]),
+    "rrt_raytracer_get_materials": (C.c_int, [_P, C.POINTER(CMaterial), C.c_uint32, _u32p]),
     "rrt_raytracer_set_triangles": (C.c_int, [_P, C.c_uint32, _dp, _dp, _dp, _u32p, _dp]),
     "rrt_raytracer_set_triangles_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _dp, _P]),
     "rrt_raytracer_release_update_memory": (C.c_int, [_P]),
@@ -138,6 +140,8 @@ SYMBOLS = {
     "rrt_render_visibility": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility)]),
     "rrt_render_surface_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface), _P]),
     "rrt_render_surface": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface)]),
+    "rrt_shade_surface_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface), _P, _P]),
+    "rrt_shade_surface": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface), _u32p]),
     "rrt_pick": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CPickResult)]),
     "rrt_tiles_per_rank": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rrt_render_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
@@ -489,6 +493,24 @@ class RayTracer:
         _check(lib().rrt_raytracer_get_lights(self._h, cl, n.value, C.byref(n)), "rrt_raytracer_get_lights")
         return [Light(l.kind, l.intensity, Vector3d(l.v.x, l.v.y, l.v.z)) for l in cl[:n.value]]
 
+    def set_materials(self, materials: Sequence[dict]) -> None:
+        """rrt_raytracer_set_materials (blocking): a new material table (dicts ka, kd, ks, ns, kr, tex, bump) over the resident one, of the same length; textures,
+        scene and measured variants stay.  All or nothing."""
+        materials = list(materials)
+        cm = (CMaterial * max(1, len(materials)))()
+        for i, m in enumerate(materials):
+            cm[i] = CMaterial(Vec3(*m["ka"]), Vec3(*m["kd"]), Vec3(*m["ks"]), float(m["ns"]), float(m["kr"]), int(m["tex"]), int(m.get("bump", -1)))
+        _check(lib().rrt_raytracer_set_materials(self._h, cm, len(materials)), "rrt_raytracer_set_materials")
+
+    def materials(self) -> list:
+        """rrt_raytracer_get_materials: the table in force, as the dicts SceneData.materials() returns."""
+        n = C.c_uint32(0)
+        _check(lib().rrt_raytracer_get_materials(self._h, None, 0, C.byref(n)), "rrt_raytracer_get_materials")
+        cm = (CMaterial * max(1, n.value))()
+        _check(lib().rrt_raytracer_get_materials(self._h, cm, n.value, C.byref(n)), "rrt_raytracer_get_materials")
+        v = lambda a: (a.x, a.y, a.z)
+        return [dict(ka=v(m.ka), kd=v(m.kd), ks=v(m.ks), ns=m.ns, kr=m.kr, tex=m.tex, bump=m.bump) for m in cm[:n.value]]
+
     def set_triangles(self, pos, uv, nrm, mat, root=None) -> None:
         """rrt_raytracer_set_triangles (blocking): new triangles from host arrays ([n,3,3] float64 x 3, [n] uint32 indexing the resident materials); octree,
         index and records are rebuilt on the GPU, everything else stays resident.  root=None: the root box in force.  All or nothing."""
@@ -678,6 +700,41 @@ class RayTracer:
         cv = CVisibility(**{name: t.data_ptr() for name, t in tensors.items() if name not in SURFACE_DTYPES})
         _check(lib().rrt_render_surface_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv), C.byref(cs),
                                                _P(_stream(stream))), "rrt_render_surface_device")
+
+    # shading from kept buffers (rrt.h: rrt_shade_surface): the frame of the planes surface() returned, with the lights and materials in force now
+    def shade(self, width: int, height: int, planes: dict, region=None) -> np.ndarray:
+        """rrt_shade_surface: planes = dict with point, normal ([h][w][4][3] float64), material, albedo ([h][w][4] uint32) and optionally lights, as
+        surface(..., visibility=("albedo",)) returns them for this size and region; returns the region's pixels, [h][w] uint32 0x00RRGGBB.  Without `lights`
+        the depth-0 shadow rays are walked again.  Other keys are ignored; a missing required plane is passed as NULL (the library refuses it)."""
+        h, w = (height, width) if region is None else (int(region[3]), int(region[2]))
+        keep = {}
+        for name in ("point", "normal", "material", "lights", "albedo"):
+            if planes.get(name) is not None:
+                dtype = SURFACE_DTYPES.get(name, np.uint32)
+                keep[name] = np.ascontiguousarray(planes[name], dtype)
+                want = (h, w, 4, 3) if SURFACE_WIDTHS.get(name) == 3 else (h, w, 4)
+                if keep[name].shape != want:
+                    raise ValueError(f"shade: plane {name} has shape {keep[name].shape}, want {want}")
+        cs = CSurface(**{n: a.ctypes.data for n, a in keep.items() if n != "albedo"})
+        cv = CVisibility(**({"albedo": keep["albedo"].ctypes.data} if "albedo" in keep else {}))
+        fb = np.empty((h, w), np.uint32)
+        _check(lib().rrt_shade_surface(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv), C.byref(cs),
+                                       fb.ctypes.data_as(_u32p)), "rrt_shade_surface")
+        return fb
+
+    def shade_into(self, fb_tensor, tensors: dict, width: int, height: int, region=None, stream: Optional[int] = None):
+        """rrt_shade_surface_device: tensors = {plane: contiguous device tensor} with point, normal, material, albedo and optionally lights, as surface_into
+        filled them; fb_tensor = w*h four-byte elements of the region; enqueued, not synchronised."""
+        px = width * height if region is None else int(region[2]) * int(region[3])
+        _device_tensor(fb_tensor, px, 4, "fb")
+        for name in ("point", "normal", "material", "lights", "albedo"):
+            if tensors.get(name) is not None:
+                _device_tensor(tensors[name], 4 * px * SURFACE_WIDTHS.get(name, 1), 8 if SURFACE_WIDTHS.get(name) == 3 else 4, name)
+        ptr = lambda name: tensors[name].data_ptr() if tensors.get(name) is not None else None
+        cs = CSurface(point=ptr("point"), normal=ptr("normal"), material=ptr("material"), lights=ptr("lights"))
+        cv = CVisibility(albedo=ptr("albedo"))
+        _check(lib().rrt_shade_surface_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv), C.byref(cs),
+                                              _P(fb_tensor.data_ptr()), _P(_stream(stream))), "rrt_shade_surface_device")
 
     # pre-bound launchers for per-frame loops (bench.py): all argument conversion is done once, the returned callable is one ctypes call
     def bind_render(self, fb_tensor, width: int, height: int, stream: Optional[int] = None):

@@ -1,5 +1,5 @@
 // api_internal.hpp -- what the units behind include/rrt.h share: the two handle types, the one place that turns exceptions into status codes, and
-// the few helpers more than one of them needs.  api.cpp: models and process-wide calls; raytracer.cpp: creation and scene set-up; scene_update.cpp: lights and
+// the few helpers more than one of them needs.  api.cpp: models and process-wide calls; raytracer.cpp: creation and scene set-up; scene_update.cpp: lights, materials and
 // triangles of a living raytracer; frames.cpp: every launch; multi.cpp: N GPUs of one node.
 #pragma once
 #include <cstdint>
@@ -21,6 +21,10 @@ struct rrt_raytracer {
     rrt_options opt{};
     rrt::BuiltScene built;           // the scene's buffers (one allocation) and counts, as the GPU or the host set-up built them
     rrt::DevBuf table_mem; rrt::DevArena tables;   // textures, material table, texture table (one allocation)
+    // Host copies of the two small tables, kept for rrt_raytracer_set_materials / _get_materials: the material table in force, and the descriptors of the
+    // resident textures (device pointer, width, height) that a new table's DevMaterial::tex_desc / bump_desc are filled from.
+    std::vector<rrt_material> materials;
+    std::vector<rrt::DevTexture> tex_descs;
 #ifdef RRT_PROFILE
     rrt::DevBuf prof_mem;
 #endif
@@ -99,6 +103,8 @@ void validate_tables(const SceneTables& T);
 void adopt_built_scene(rrt_raytracer* rt);
 void check_lights(const rrt_light* lights, uint32_t n_lights);
 void store_lights(rrt_raytracer* rt, const rrt_light* lights, uint32_t n_lights);
+// the device record of material `s` with its texture descriptors inline, from the descriptors of the resident textures (s.tex / s.bump checked by the caller)
+DevMaterial dev_material(const rrt_material& s, const std::vector<DevTexture>& texs);
 
 // The warm-up thread (api.cpp: DeviceWarmer): the loaders start it, rrt_raytracer_create waits for it.
 void warm_up_start();

@@ -150,6 +150,15 @@ struct SurfaceParams {
     double *point, *normal; uint32_t *material, *lights;
 };
 
+// Argument of the shade kernels (render.hip: shade_kernel; rrt.h: rrt_shade_surface_device): a VisParams -- frame, region and tile rectangle; its six plane
+// pointers are unused -- plus the five planes the kernel READS, laid out as the surface launch wrote them for that region, and the framebuffer it writes:
+// [rows][columns] pixels of the region.  `lights` may be null: the depth-0 shadow rays are then walked.
+struct ShadeParams {
+    VisParams V;
+    const double *point, *normal; const uint32_t *material, *albedo, *lights;
+    uint32_t* out;
+};
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);
@@ -157,6 +166,8 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
 int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int walk);
 // the surface planes (and any visibility planes) of a region of a frame (render.hip: surface_kernel)
 int launch_surface(const DevScene& s, const SurfaceParams& q, void* stream, int walk);
+// the pixels of a region of a frame from its kept planes (render.hip: shade_kernel)
+int launch_shade(const DevScene& s, const ShadeParams& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk);
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,

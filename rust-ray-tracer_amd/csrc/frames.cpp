@@ -1,4 +1,4 @@
-// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility and surface buffers, per-ray queries, the choice of traversal variant, and
+// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility and surface buffers, frames shaded from those buffers, per-ray queries, the choice of traversal variant, and
 // the statistics of the last launch.  Every launch goes through ONE seam, timed_launch + record (the raytracer's two events around it, what it traced into rrt_stats), and
 // every measurement of the variants through fastest_variant.  The host forms add a kept device buffer (device_memory.hpp: KeptBuf) or one allocation per call, and
 // staged_download for the way back.
@@ -280,6 +280,51 @@ void surface_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const r
     HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the planes are in the caller's memory on return
 }
 
+// ---- shading from kept planes (rrt.h: rrt_shade_surface_device).  One launch of shade_kernel over the tiles the region touches; variant, tuning state and stats as the
+// surface calls.  every check, before any GPU work; returns the region in force
+rrt_region check_shade(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* vis, const rrt_surface* planes, const void* out) {
+    check_frame(rt, width, height);
+    if (!vis || !planes) throw Error{RRT_ERR_INVALID_ARG, "null planes struct: shading reads the albedo plane of the visibility struct and the planes of the surface struct"};
+    if (!vis->albedo || !planes->point || !planes->normal || !planes->material) throw Error{RRT_ERR_INVALID_ARG, "null plane: albedo, point, normal and material are all required"};
+    if (!out) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
+    const rrt_region r = region ? *region : rrt_region{0, 0, width, height};
+    if (r.w == 0 || r.h == 0) throw Error{RRT_ERR_INVALID_ARG, "empty region"};
+    if ((uint64_t)r.x0 + r.w > width || (uint64_t)r.y0 + r.h > height) throw Error{RRT_ERR_INVALID_ARG, "region sticks out of the frame"};
+    return r;
+}
+
+// the pixels of region r (checked) from planes in device memory into d_fb on the caller's stream, timed by the raytracer's events
+void launch_shade_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* d_fb, void* stream) {
+    ShadeParams q{};
+    q.V = vis_params(rt, width, height, r, rrt_visibility{});            // (the kernel writes no plane)
+    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.albedo = d_vis.albedo; q.lights = d_planes.lights;
+    q.out = static_cast<uint32_t*>(d_fb);
+    const int variant = visibility_variant(rt, width, height);
+    timed_launch(rt, stream, [&] { return launch_shade(rt->scene, q, stream, variant); });
+    record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
+}
+
+// Host form: the given planes up into the kept allocation of the visibility calls, the launch, the region's pixels down; nothing in flight on return.
+void shade_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& vis, const rrt_surface& planes, uint32_t* out_fb) {
+    DeviceGuard guard(rt->device);
+    constexpr int kIn = 5;
+    const void* host[kIn] = {planes.point, planes.normal, planes.material, vis.albedo, planes.lights};
+    constexpr size_t elem[kIn] = {24, 24, 4, 4, 4};                      // bytes per sub-sample
+    const size_t n = 4 * (size_t)r.w * r.h, fb_bytes = sizeof(uint32_t) * (size_t)r.w * r.h;
+    size_t need = (fb_bytes + 255) & ~(size_t)255;
+    for (int k = 0; k < kIn; k++) if (host[k]) need += (elem[k] * n + 255) & ~(size_t)255;
+    DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
+    void* dev[kIn];
+    for (int k = 0; k < kIn; k++) dev[k] = host[k] ? arena.take<char>(elem[k] * n) : nullptr;
+    uint32_t* d_fb = arena.take<uint32_t>((size_t)r.w * r.h);
+    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
+    for (int k = 0; k < kIn; k++) if (host[k]) staged_upload(dev[k], host[k], elem[k] * n, rt->own_stream);
+    rrt_visibility d_vis{}; d_vis.albedo = (uint32_t*)dev[3];
+    launch_shade_frame(rt, width, height, r, d_vis, rrt_surface{(double*)dev[0], (double*)dev[1], (uint32_t*)dev[2], (uint32_t*)dev[4]}, d_fb, rt->own_stream);
+    staged_download(out_fb, d_fb, fb_bytes, rt->own_stream);
+    HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the pixels are in the caller's memory, and its planes are no longer read, on return
+}
+
 // ---- per-ray queries.  The device forms (rrt.h: rrt_intersect_rays_device, ...): no allocation, no copy, no synchronisation; launch(variant) on the caller's stream.
 template <class Launch> int device_ray_query(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, bool any_output, void* stream, Launch&& launch) {
     check_rays(rt, n, d_origins, d_dirs, any_output);
@@ -378,6 +423,25 @@ int rrt_render_surface(rrt_raytracer* rt, uint32_t width, uint32_t height, const
     return guarded([&]() -> int {
         const rrt_region r = check_surface(rt, width, height, region, planes);
         surface_to_host(rt, width, height, r, vis ? *vis : rrt_visibility{}, *planes);
+        return RRT_OK;
+    });
+}
+
+int rrt_shade_surface_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* d_vis, const rrt_surface* d_planes,
+                             void* d_fb, void* stream) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_shade(rt, width, height, region, d_vis, d_planes, d_fb);
+        DeviceGuard guard(rt->device);
+        launch_shade_frame(rt, width, height, r, *d_vis, *d_planes, d_fb, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_shade_surface(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* vis, const rrt_surface* planes,
+                      uint32_t* out_fb) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_shade(rt, width, height, region, vis, planes, out_fb);
+        shade_from_host(rt, width, height, r, *vis, *planes, out_fb);
         return RRT_OK;
     });
 }

@@ -39,16 +39,14 @@ void upload_materials_and_textures(rrt_raytracer* rt, const SceneTables& T, hipS
         texs[i].rgb = d; texs[i].width = T.tex[i].width; texs[i].height = T.tex[i].height;
     }
     mats.resize(T.n_mats);
-    for (size_t i = 0; i < mats.size(); i++) {
-        const rrt_material& s = T.mats[i]; DevMaterial& d = mats[i];
-        d.ka[0] = s.ka.x; d.ka[1] = s.ka.y; d.ka[2] = s.ka.z; d.kd[0] = s.kd.x; d.kd[1] = s.kd.y; d.kd[2] = s.kd.z;
-        d.ks[0] = s.ks.x; d.ks[1] = s.ks.y; d.ks[2] = s.ks.z; d.ns = s.ns; d.kr = s.kr; d.tex = s.tex; d.bump = s.bump;
-        d.tex_desc = texs[s.tex]; d.bump_desc = s.bump >= 0 ? texs[s.bump] : DevTexture{nullptr, 0, 0};
-    }
+    for (size_t i = 0; i < mats.size(); i++) mats[i] = dev_material(T.mats[i], texs);
 }
 
-// the two small tables, on `st` (asynchronous: the vectors must outlive the caller's synchronise)
-void upload_tables(rrt_raytracer* rt, const std::vector<DevTexture>& texs, const std::vector<DevMaterial>& mats, hipStream_t st) {
+// the two small tables, on `st` (asynchronous: the vectors must outlive the caller's synchronise); the raytracer keeps host copies of the material table and
+// of the texture descriptors (rrt_raytracer_set_materials)
+void upload_tables(rrt_raytracer* rt, const SceneTables& T, const std::vector<DevTexture>& texs, const std::vector<DevMaterial>& mats, hipStream_t st) {
+    rt->materials.assign(T.mats, T.mats + T.n_mats);
+    rt->tex_descs = texs;
     DevMaterial* d_m = rt->tables.take<DevMaterial>(mats.size());
     DevTexture* d_t = rt->tables.take<DevTexture>(texs.size());
     if (!mats.empty()) HIP_TRY(hipMemcpyAsync(d_m, mats.data(), mats.size() * sizeof(DevMaterial), hipMemcpyHostToDevice, st));
@@ -100,6 +98,14 @@ void adopt_built_scene(rrt_raytracer* rt) {
     rt->built_bytes = bytes;
 }
 
+DevMaterial dev_material(const rrt_material& s, const std::vector<DevTexture>& texs) {
+    DevMaterial d{};
+    d.ka[0] = s.ka.x; d.ka[1] = s.ka.y; d.ka[2] = s.ka.z; d.kd[0] = s.kd.x; d.kd[1] = s.kd.y; d.kd[2] = s.kd.z;
+    d.ks[0] = s.ks.x; d.ks[1] = s.ks.y; d.ks[2] = s.ks.z; d.ns = s.ns; d.kr = s.kr; d.tex = s.tex; d.bump = s.bump;
+    d.tex_desc = texs[s.tex]; d.bump_desc = s.bump >= 0 ? texs[s.bump] : DevTexture{nullptr, 0, 0};
+    return d;
+}
+
 void check_lights(const rrt_light* lights, uint32_t n_lights) {
     if (n_lights && !lights) throw Error{RRT_ERR_INVALID_ARG, "null light list"};
     if (n_lights > RRT_MAX_LIGHTS) throw Error{RRT_ERR_INVALID_ARG, "too many lights (max 16)"};
@@ -128,7 +134,7 @@ void setup_on_host(rrt_raytracer* rt, const Model& M, rrt_vec3 origin, const rrt
     alloc_tables(rt, T);
     std::vector<DevTexture> texs; std::vector<DevMaterial> mats;
     upload_materials_and_textures(rt, T, nullptr, texs, mats);
-    upload_tables(rt, texs, mats, nullptr);
+    upload_tables(rt, T, texs, mats, nullptr);
     adopt_built_scene(rt);
     HIP_TRY(hipDeviceSynchronize());
     rt->upload_ms = rt->built.ms_upload + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -164,7 +170,7 @@ void setup_on_gpu(rrt_raytracer* rt, const TriSource& src, uint32_t n_tris, cons
     tex_task->wait();
     lap("texture upload joined");
     adopt_built_scene(rt);
-    upload_tables(rt, texs, mats, st);   // small tables go through the same stream
+    upload_tables(rt, T, texs, mats, st);   // small tables go through the same stream
     HIP_TRY(hipStreamSynchronize(st_tex));
     HIP_TRY(hipStreamSynchronize(st));
     lap("final synchronise");

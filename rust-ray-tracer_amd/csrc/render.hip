@@ -31,8 +31,8 @@
 #include "device_scene.hpp"
 
 // The library compiles this file THREE times (csrc/Makefile), same device functions, different code-generation switches per group of kernels:
-//   -DRRT_TU=1  the bundle-filter frame, visibility and surface kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
-//   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility and surface kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
+//   -DRRT_TU=1  the bundle-filter frame, visibility, surface and shade kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
+//   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility, surface and shade kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
 //   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
@@ -1835,6 +1835,194 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevSce
     if (P.tri) P.tri[i] = tri;
 }
 
+// Shading from kept buffers (rrt.h: rrt_shade_surface_device): the colour of every pixel of a region of the frame from the planes surface_kernel wrote for it --
+// point, normal, material, albedo and, if given, the lights mask -- with the lights and materials in force NOW.  No primary ray is walked: a sub-sample starts
+// as the primary segment's hit as trace_colour holds it after get_normal_at_intersection (p, n, mat, col; the segment direction is recomputed from the pixel
+// and the pose), and from there on it is trace_colour: the light list, compute_lighting_intensity, the reflection chain with its shadow rays, the unwind.
+// trace_colour's state machine, rotated: a turn SHADES first (the light list of the hit a lane holds, up to the next shadow ray or to the hit's colour and its
+// reflection ray) and WALKS second (the shadow or reflection rays the shading left in flight), so a wave none of whose lanes needs a ray -- non-mirror hits with
+// a mask, misses -- leaves without calling the walk at all.  ONE call site of the walk; every ray is a secondary ray (not one_origin, filters on, any_ok for a
+// shadow ray).  With a mask the lights the depth-0 sum adds up are [0, min(ctz(~mask), n_lights)) and no depth-0 shadow ray is formed; without one (a kernel
+// argument: wave-uniform) they are walked as a frame walks them, the `break` at the first occluded point light included.
+// A material index at or beyond the table (0xFFFFFFFF: a miss) is WHITE; no other value of the caller's planes is used as an index.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene S, const ShadeParams Q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t lane = threadIdx.x;
+    const Stack stk{lds + kParkBytes, lane};
+    const VisParams& P = Q.V;
+    const FrameParams& F = P.F;
+    // Block order, tile quadrant, pixel, sub-sample and direction: surface_kernel's, restated (see visibility_kernel)
+    uint32_t blk = blockIdx.x;
+    if (F.xcd_chunk) {
+        const uint32_t C = F.xcd_chunk, full = (gridDim.x / (8u * C)) * (8u * C);
+        if (blk < full) { const uint32_t xcd = blk & 7u, i = blk >> 3; blk = ((i / C) * 8u + xcd) * C + (i % C); }
+    }
+    const uint32_t local_tile = blk >> 2, quad = blk & 3u;
+    const uint32_t pix = lane >> 2, sub = lane & 3u;
+    const bool tile_ok = local_tile < F.tile_end;
+    const uint32_t tx = P.tile_x0 + (tile_ok ? local_tile % P.tiles_w : 0), ty = P.tile_y0 + (tile_ok ? local_tile / P.tiles_w : 0);
+    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
+    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
+    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
+    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;   // col_end <= width, row_end <= height
+    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;   // the pixels the reference traces (render_kernel)
+    const int32_t x = (int32_t)px - W / 2;
+    const int32_t y = (H - H / 2) - (int32_t)py;
+    const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;                      // engine.rs:207-236
+    const double yd = (sub & 2u) ? ((double)y + 0.5) : (double)y;
+    const double sa = xd * F.x_scale, sb = yd * F.y_scale, sc = F.z_value;             // (right*a + up*b) + forward*c, five operations per component: rrt.h, rrt_camera
+    V3 seg_d = mk((F.right[0] * sa + F.up[0] * sb) + F.forward[0] * sc,
+                  (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
+                  (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    // (pixel index inside the region; the element index of a sub-sample is 4 * that + sub.  Only lanes inside the region use either.)
+    const size_t pixel_i = ((size_t)(py - F.row_begin) * (P.col_end - P.col_begin)) + (px - P.col_begin);
+    const size_t i = pixel_i * 4 + sub;
+    // ---- the five values: the primary segment's hit
+    bool live = false;                      // the lane holds a hit whose colour is not known yet
+    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
+    uint32_t col = 0, mat = 0, li = 0, depth = 0;
+    uint32_t n_eval = 0;                    // lights [0, n_eval) contribute (an occluded point light ends the loop, raytracer.rs:235-237)
+    uint32_t term = 0x00FFFFFFu;            // colour of the last segment; WHITE for a miss, raytracer.rs:109-111
+    if (traced) {
+        mat = Q.material[i];
+        if (mat < S.n_mats) {               // (0xFFFFFFFF, a miss, and anything else beyond the table: WHITE)
+            live = true;
+            p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
+            col = Q.albedo[i] & 0x00FFFFFFu;
+            if (Q.lights) {                 // the kept mask answers the depth-0 shadow queries: the light loop below is skipped for this hit
+                const uint32_t first_dark = (uint32_t)__builtin_ctz(~Q.lights[i] | (1u << RRT_MAX_LIGHTS));   // (n_lights <= 16: bits at and above it never count)
+                n_eval = first_dark < S.n_lights ? first_dark : S.n_lights;
+                li = 0xFFFFu;
+            }
+        }
+    }
+    bool in_shadow = false;                 // false: the ray in flight is a reflection ray; true: a shadow ray
+    V3 ro = mk(0, 0, 0), rd = mk(0, 0, 1); double rmax = kInf;
+    double st_local[RRT_MAX_REFLECT][3]; double st_kr[RRT_MAX_REFLECT];
+    for (;;) {
+        // ---- shade: every live lane holds a hit (p, n, mat, col, seg_d) and stands at light li of its list
+        if (live) {
+            // the light list (raytracer.rs:205-255) up to the next point light, whose shadow ray (raytracer.rs:164-188) is walked next: trace_colour's
+            while (li < S.n_lights && !in_shadow) {
+                const DevLight& L = S.lights[li];
+                if (L.kind == 1u) {
+                    const V3 dir = ld3(L.v) - p;
+                    ro = p + n * S.surface_offset;
+                    rd = dir;
+                    rmax = length(dir);
+                    in_shadow = true;
+                } else {
+                    li++;
+                }
+            }
+            if (!in_shadow) {
+                if (li != 0xFFFFu) n_eval = S.n_lights;
+                // --- compute_lighting_intensity, raytracer.rs:192-258
+                const DevMaterial& M = S.mats[mat];
+                const V3 vdir = neg(seg_d);
+                const double len_n = length(n), len_v = length(vdir);
+                V3 I = mk(0.0, 0.0, 0.0);
+                for (uint32_t k = 0; k < n_eval; ++k) {
+                    const DevLight& L = S.lights[k];
+                    if (L.kind == 0u) {                                              // Ambient, raytracer.rs:207-209
+                        I = I + ld3(M.ka) * L.intensity;
+                    } else {                                                         // Directional (raytracer.rs:210-227) / unoccluded Point (raytracer.rs:239-252)
+                        const V3 l = (L.kind == 2u) ? ld3(L.v) : ld3(L.v) - p;
+                        const double n_dot_l = dot(n, l);
+                        I = I + diffuse_term(L.intensity, n_dot_l, len_n, length(l), ld3(M.kd));
+                        I = I + specular_term(M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks));
+                    }
+                }
+                // --- raytracer.rs:67-108
+                const V3 local = mk((double)((col >> 16) & 255u) * I.x, (double)((col >> 8) & 255u) * I.y, (double)(col & 255u) * I.z);
+                const double kr = M.kr;
+                if (kr > 0.0 && depth < S.max_reflection_depth) {                    // raytracer.rs:76
+                    st_local[depth][0] = local.x; st_local[depth][1] = local.y; st_local[depth][2] = local.z; st_kr[depth] = kr;
+                    const double d_dot_n = dot(seg_d, n);
+                    rd = normalised(seg_d - (n * 2.0) * d_dot_n);                    // raytracer.rs:79
+                    ro = p + n * S.surface_offset;                                   // raytracer.rs:82
+                    rmax = kInf;
+                    depth++;
+                } else {
+                    term = (clamp_u8(local.x) << 16) | (clamp_u8(local.y) << 8) | clamp_u8(local.z);   // raytracer.rs:104-108
+                    live = false;
+                }
+            }
+        }
+        if (!__any(live)) break;                                                     // no ray in flight in the wave
+        // ---- walk: the shadow and reflection rays in flight, together
+        double t; uint32_t slot;
+        if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, live, in_shadow, true, ro, rd, rmax, t, slot);
+        else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, live, in_shadow, true, false, ro, rd, rmax, t, slot);
+        if (live) {
+            const bool found = slot != kNone;
+            if (!in_shadow) {
+                if (!found) {
+                    term = 0x00FFFFFFu; live = false;                                // WHITE, raytracer.rs:109-111
+                } else {
+                    // --- hit: raytracer.rs:39-57, as trace_colour
+                    double u = 0, v = 0, t2;
+                    mt_full(S.geom + slot, ro, rd, t2, u, v);
+                    const DevTriAttr& A = S.attr[slot];
+                    seg_d = rd;
+                    p = ro + rd * t;                                                 // raytracer.rs:39
+                    mat = A.mat;
+                    const DevMaterial& M = S.mats[mat];
+                    const DevTexture T = M.tex_desc;
+                    const double w = 1.0 - u - v;                                    // raytracer.rs:43
+                    const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;    // raytracer.rs:45-47
+                    const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;    // raytracer.rs:48-50
+                    const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);    // raytracer.rs:52
+                    const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);  // raytracer.rs:53
+                    const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);           // raytracer.rs:55
+                    col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
+                    // get_normal_at_intersection, raytracer.rs:114-162
+                    V3 nn = (ld3(A.nrm + 3) * u + ld3(A.nrm + 6) * v) + ld3(A.nrm) * w;           // raytracer.rs:122-124
+                    if (M.bump >= 0) {
+                        const DevTexture B = M.bump_desc;
+                        const uint8_t* bp = B.rgb + 3ull * ((uint64_t)B.width * tyi + txi);       // raytracer.rs:127-128 (colour-texture indices, bump width)
+                        V3 bv = mk((double)bp[0], (double)bp[1], (double)bp[2]);
+                        bv = normalised(bv);
+                        bv = (bv * 2.0) - mk(1.0, 1.0, 1.0);                         // raytracer.rs:130-135
+                        V3 tg = cross(nn, mk(0.0, 1.0, 0.0));                        // raytracer.rs:137-141
+                        double len_tg = length(tg);
+                        if (len_tg == 0.0) { tg = cross(nn, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }   // raytracer.rs:143-149
+                        tg = div3(tg, len_tg);                                       // raytracer.rs:151
+                        const V3 bt = normalised(cross(nn, tg));                     // raytracer.rs:152
+                        nn = mk(dot(bv, tg), dot(bv, bt), dot(bv, nn));              // raytracer.rs:154-158
+                    }
+                    n = normalised(nn);                                              // raytracer.rs:161
+                    li = 0;                                                          // compute_lighting_intensity, raytracer.rs:199-203
+                }
+            } else {
+                // --- result of the shadow ray for point light li (raytracer.rs:232-237): occluded -> `break` out of the whole light loop
+                if (found) { n_eval = li; li = 0xFFFFu; }
+                else li++;
+                in_shadow = false;
+            }
+        }
+    }
+    // unwind the reflection chain, innermost first (raytracer.rs:85-101): every level quantises to u8 before blending
+    uint32_t c = term;
+    for (uint32_t k = depth; k-- > 0;) {
+        const double kr = st_kr[k];
+        const double fx = st_local[k][0] * (1.0 - kr) + (double)((c >> 16) & 255u) * kr;
+        const double fy = st_local[k][1] * (1.0 - kr) + (double)((c >> 8) & 255u) * kr;
+        const double fz = st_local[k][2] * (1.0 - kr) + (double)(c & 255u) * kr;
+        c = (clamp_u8(fx) << 16) | (clamp_u8(fy) << 8) | clamp_u8(fz);
+    }
+    // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
+    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
+    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
+    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
+    const uint32_t mixed = traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;   // 0 as Canvas::new where nothing is traced
+    if (sub == 0 && in_region) Q.out[pixel_i] = mixed;
+}
+
 #endif   // RRT_TU_FRAME || RRT_TU_LANE
 #if RRT_TU_FRAME
 __global__ __launch_bounds__(256) void detile_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t world, uint32_t tiles_per_rank,
@@ -2042,6 +2230,20 @@ int launch_surface(const DevScene& s, const SurfaceParams& q, void* stream, int 
     });
 }
 
+// The pixels of a region of a frame from its kept planes (device_scene.hpp: ShadeParams): the grid of launch_surface.
+int launch_shade_lane_ray(const DevScene& s, const ShadeParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+int launch_shade(const DevScene& s, const ShadeParams& q, void* stream, int walk) {
+    walk = effective_walk(s, walk);
+    const uint32_t n_tiles = q.V.F.tile_end;
+    if (n_tiles == 0) return 0;
+    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
+    if (walk != kWalkBundle) return launch_shade_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
+    return with_groups(s, [&](auto groups) {
+        hipLaunchKernelGGL((shade_kernel<kWalkBundle, groups()>), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
+        return (int)hipGetLastError();
+    });
+}
+
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
     const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
     const uint32_t tpr = (tiles_x * tiles_y + world - 1) / world;
@@ -2080,6 +2282,14 @@ int launch_surface_lane_ray(const DevScene& s, const SurfaceParams& q, void* str
     return with_lane_or_ray_walk(walk, [&](auto w) {
         return with_groups(s, [&](auto groups) {
             hipLaunchKernelGGL((surface_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
+            return (int)hipGetLastError();
+        });
+    });
+}
+int launch_shade_lane_ray(const DevScene& s, const ShadeParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+    return with_lane_or_ray_walk(walk, [&](auto w) {
+        return with_groups(s, [&](auto groups) {
+            hipLaunchKernelGGL((shade_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
             return (int)hipGetLastError();
         });
     });

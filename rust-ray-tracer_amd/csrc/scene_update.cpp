@@ -1,6 +1,6 @@
-// scene_update.cpp -- rrt_raytracer_set_lights / _get_lights, rrt_raytracer_set_triangles / _set_triangles_device and
+// scene_update.cpp -- rrt_raytracer_set_lights / _get_lights, rrt_raytracer_set_materials / _get_materials, rrt_raytracer_set_triangles / _set_triangles_device and
 // rrt_raytracer_release_update_memory: the scene of a living raytracer.  Lights live in DevScene and travel with the kernel arguments, so a new list is
-// host work.  New triangles run the creation's build again (scene_build.hip: gpu_build_scene) into a second BuiltScene, from host arrays or from arrays
+// host work.  A new material table is one small copy over the resident one.  New triangles run the creation's build again (scene_build.hip: gpu_build_scene) into a second BuiltScene, from host arrays or from arrays
 // already in device memory, and swap it in after the last call that can fail: textures, tables, options, lights and the camera pose stay resident, and
 // the old scene stays in force, intact, on any failure.
 #include <atomic>
@@ -68,6 +68,38 @@ int rrt_raytracer_get_lights(const rrt_raytracer* rt, rrt_light* out, uint32_t c
         if (out && capacity < S.n_lights) throw Error{RRT_ERR_INVALID_ARG, "light array too small"};
         if (n_lights) *n_lights = S.n_lights;
         if (out) for (uint32_t i = 0; i < S.n_lights; i++) out[i] = rrt_light{S.lights[i].kind, 0u, S.lights[i].intensity, {S.lights[i].v[0], S.lights[i].v[1], S.lights[i].v[2]}};
+        return RRT_OK;
+    });
+}
+
+// One copy of the new table over the resident one, at its address (DevScene::mats stays); textures, scene and tuning state are not touched.  Every check runs
+// before the copy: the table in force stays on a refusal.
+int rrt_raytracer_set_materials(rrt_raytracer* rt, const rrt_material* mats, uint32_t n_mats) {
+    return guarded([&]() -> int {
+        if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+        if (n_mats != rt->scene.n_mats) throw Error{RRT_ERR_INVALID_ARG, "the number of materials differs from the resident table's (the triangles index it)"};
+        if (n_mats && !mats) throw Error{RRT_ERR_INVALID_ARG, "null material list"};
+        if (n_mats == 0) return (int)RRT_OK;
+        for (uint32_t i = 0; i < n_mats; i++) if (mats[i].bump < -1) throw Error{RRT_ERR_INVALID_ARG, "material bump index out of range (-1 = none)"};
+        SceneTables T{mats, n_mats, {}};                                  // (the checks of creation: texture and bump indices, a bump map too small for the texels that address it)
+        for (const DevTexture& t : rt->tex_descs) T.tex.push_back(rrt_texture{t.rgb, t.width, t.height});
+        validate_tables(T);
+        std::vector<DevMaterial> table(n_mats);
+        for (uint32_t i = 0; i < n_mats; i++) table[i] = dev_material(mats[i], rt->tex_descs);
+        DeviceGuard guard(rt->device);
+        HIP_TRY(hipMemcpy(const_cast<DevMaterial*>(rt->scene.mats), table.data(), table.size() * sizeof(DevMaterial), hipMemcpyHostToDevice));   // blocking
+        rt->materials.assign(mats, mats + n_mats);
+        return (int)RRT_OK;
+    });
+}
+
+int rrt_raytracer_get_materials(const rrt_raytracer* rt, rrt_material* out, uint32_t capacity, uint32_t* n_mats) {
+    return guarded([&]() -> int {
+        if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+        const uint32_t n = (uint32_t)rt->materials.size();
+        if (out && capacity < n) throw Error{RRT_ERR_INVALID_ARG, "material array too small"};
+        if (n_mats) *n_mats = n;
+        if (out) for (uint32_t i = 0; i < n; i++) out[i] = rt->materials[i];
         return RRT_OK;
     });
 }
