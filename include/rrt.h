@@ -283,7 +283,7 @@ int rrt_pick(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t px, ui
 /* Surface buffers: what the reference holds at the first hit of a frame's primary rays on its way to a colour, and does not keep -- the hit point, the shading
  * normal, the material and which lights reach the point.  With the albedo plane above this is what a host needs to shade deferred, to relight a still camera
  * without walking the primaries again, to feed a denoiser its normal and albedo, to bake a moved light's shadow mask, and to form its own shadow, reflection or
- * ambient-occlusion rays on the GPU for the device-resident batch calls below.
+ * ambient-occlusion rays on the GPU for the device-resident batch calls below (hemisphere rays of a fixed table in one launch: rrt_ambient_surface below).
  * The ray of canvas pixel (px, py), sub-sample s is the one rrt_render_visibility* defines: the primary ray a frame traces for it in the current pose.
  * Per ray with a hit:
  *   point    = origin + direction * t (raytracer.rs:39), t as in the visibility plane;
@@ -363,6 +363,52 @@ int rrt_shade_surface_device(rrt_raytracer *rt, uint32_t width, uint32_t height,
                              const rrt_visibility *d_vis, const rrt_surface *d_planes, void *d_fb, void *stream);
 int rrt_shade_surface(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
                       const rrt_visibility *vis, const rrt_surface *planes, uint32_t *out_fb);
+
+/* Ambient occlusion from kept buffers: which of n hemisphere rays from every first hit of a frame are blocked, from the planes rrt_render_surface* wrote for
+ * it, in ONE launch that forms the rays in registers.  (The same rays through rrt_occluded_rays_device cost 56 bytes of device memory each, written and read
+ * again: over 6 GB for a 1920 x 1080 frame with 16 samples.)  For an ambient term under a still camera, for baking, for a contact-shadow mask.
+ * planes / d_planes is the struct the caller gave rrt_render_surface[_device] for the same frame size and region, in that layout.  READ: point, normal and
+ * material, all three required; `lights` is ignored.
+ * samples: n directions (sx, sy, sz) in the tangent frame of a hit -- sz along the normal -- and one max_t for all rays, as rrt_occluded_rays takes it (+inf is
+ * valid).  The table lies in HOST memory in both forms, is borrowed for the call and travels in the kernel arguments, as the lights do.
+ * Per sub-sample of a traced pixel: material >= n_mats (0xFFFFFFFF, a miss, included) is a miss -- the rule of rrt_shade_surface; no table is indexed with a
+ * caller's value.  Otherwise, with point p and normal n exactly as stored, the tangent frame is the reference's (raytracer.rs:137-152):
+ *   tg = cross(n, (0,1,0));  if length(tg) == 0: tg = cross(n, (0,0,1));  tg = tg / length(tg);  bt = normalised(cross(n, tg))
+ * and the ray of sample k = (sx, sy, sz) is
+ *   origin = p + n * surface_offset;   direction.c = (tg.c*sx + bt.c*sy) + n.c*sz  per component -- five f64 operations, each rounded on its own, the shape of
+ *   rrt_camera;   max_t = samples->max_t.
+ * occluded: bit k = what rrt_occluded_rays returns for exactly that ray, byte for byte; bits at and above n are 0.  A miss gives 0, and so does a pixel the
+ * reference never traces (canvas row 0, row 1 of an odd height, the last column of an odd width).
+ * grey, one value per pixel, in exact integer arithmetic: open = the sum over the four sub-samples of n for a miss and n - popcount(occluded) for a hit;
+ * g = (510*open + 4*n) / (8*n), truncating -- 255 * open / (4n) rounded half up; the pixel is g * 0x010101.  A pixel the reference never traces is 0.
+ * The rays are not rotated per pixel and the grey value is not cosine-weighted: the mask lets the host weight.
+ * Every element of every requested plane inside the region is written.  Inputs and outputs must not overlap.
+ * A non-finite point or normal in the caller's planes gives unspecified bits for that sub-sample, and no fault.
+ * Exactness: no primary ray is walked; every walk of this call is a shadow walk of a frame -- default mode, not guarded, the band documented under
+ * RRT_FLAG_NO_CULL -- as the shadow walks of rrt_render_surface and rrt_shade_surface are.
+ * Keeping the planes valid is the caller's business; the table under rrt_shade_surface says when: point, normal and material go stale with camera and triangle
+ * changes (and normal with the `tex` / `bump` edits listed there), never with a change of lights.
+ * Traversal variant, tuning state and rrt_last_stats as the surface calls: the forced variant, else the one kept for this frame size, else the first-frame rule's;
+ * the call never triggers or alters a measurement; kernel_ms and filter_variant of this launch, width / height = the frame size, rays_primary = 4 * the traced
+ * pixels inside the region (the hemisphere rays are not counted).
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer and the outputs as they were: NULL rt, planes, samples or out; a NULL required plane; both
+ * outputs NULL; n == 0 or n > RRT_MAX_AMBIENT_SAMPLES; NULL dirs; a non-finite direction component; max_t NaN or <= 0; a bad frame size; a region with w == 0 or
+ * h == 0 or one that sticks out of the frame.
+ * rrt_ambient_surface_device: planes and outputs in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default): no allocation, no copy and
+ * no synchronisation.
+ * rrt_ambient_surface: planes and outputs in host memory; blocking: the three planes are uploaded into the device allocation the visibility calls keep, only the
+ * requested outputs are downloaded, and nothing is in flight on return.
+ * Not covered, as for the surface calls: the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+#define RRT_MAX_AMBIENT_SAMPLES 32
+/* dirs: n x 3 doubles (sx, sy, sz) in the tangent frame of the hit, HOST memory in both forms, borrowed for the call.  max_t as rrt_occluded_rays takes it. */
+typedef struct { const double *dirs; uint32_t n, _pad; double max_t; } rrt_ambient_samples;   /* 24 bytes */
+/* occluded: [region.h][region.w][4] uint32;  grey: [region.h][region.w] uint32.  Either may be NULL, not both. */
+typedef struct { uint32_t *occluded; uint32_t *grey; } rrt_ambient;                            /* 16 bytes */
+int rrt_ambient_surface_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                               const rrt_surface *d_planes, const rrt_ambient_samples *samples,
+                               const rrt_ambient *d_out, void *stream);
+int rrt_ambient_surface(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                        const rrt_surface *planes, const rrt_ambient_samples *samples, const rrt_ambient *out);
 
 /* Screen-tile partition for N GPUs (one process per GPU): the frame is cut into 8x8-pixel tiles, tile k (row-major)
  * belongs to rank k % world.  Renders this rank's tiles into d_tiles[rrt_tiles_per_rank][64] (tile-major, device).

@@ -90,6 +90,18 @@ SURFACE_DTYPES = dict(point=np.float64, normal=np.float64, material=np.uint32, l
 SURFACE_WIDTHS = dict(point=3, normal=3, material=1, lights=1)   # elements per sub-sample
 
 
+class CAmbientSamples(C.Structure):  # rrt_ambient_samples, 24 bytes: dirs = n x 3 host doubles in the tangent frame of a hit
+    _fields_ = [("dirs", C.POINTER(C.c_double)), ("n", C.c_uint32), ("_pad", C.c_uint32), ("max_t", C.c_double)]
+
+
+class CAmbient(C.Structure):         # rrt_ambient, 16 bytes: host or device pointers, NULL = plane not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("occluded", "grey")]
+
+
+MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
+AMBIENT_OUTPUTS = ("occluded", "grey")   # the planes of rrt_ambient, in its order: [h][w][4] masks, [h][w] pixels, both uint32
+
+
 class CModelInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_tris", "n_tris_in_tree", "n_nodes", "max_depth", "n_mats", "n_tex", "root_own_count", "max_own_count")]
 
@@ -142,6 +154,8 @@ SYMBOLS = {
     "rrt_render_surface": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface)]),
     "rrt_shade_surface_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface), _P, _P]),
     "rrt_shade_surface": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface), _u32p]),
+    "rrt_ambient_surface_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CSurface), C.POINTER(CAmbientSamples), C.POINTER(CAmbient), _P]),
+    "rrt_ambient_surface": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CSurface), C.POINTER(CAmbientSamples), C.POINTER(CAmbient)]),
     "rrt_pick": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CPickResult)]),
     "rrt_tiles_per_rank": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rrt_render_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
@@ -736,6 +750,45 @@ class RayTracer:
         _check(lib().rrt_shade_surface_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv), C.byref(cs),
                                               _P(fb_tensor.data_ptr()), _P(_stream(stream))), "rrt_shade_surface_device")
 
+    # ambient occlusion from kept buffers (rrt.h: rrt_ambient_surface): which of the hemisphere rays `dirs` from every first hit are blocked
+    def ambient(self, width: int, height: int, planes: dict, dirs, max_t: float = float("inf"), region=None, outputs=AMBIENT_OUTPUTS) -> dict:
+        """rrt_ambient_surface: planes = dict with point, normal ([h][w][4][3] float64) and material ([h][w][4] uint32) as surface() returns them for this size
+        and region (other keys are ignored; a missing plane is passed as NULL, which the library refuses); dirs = [n][3] directions in the tangent frame of a
+        hit (z along the normal), n <= MAX_AMBIENT_SAMPLES; max_t as occluded() takes it.  Returns {"occluded": [h][w][4] uint32, bit k = ray k is blocked,
+        "grey": [h][w] uint32 0x00GGGGGG, the share of open rays}, only the outputs asked for."""
+        h, w = (height, width) if region is None else (int(region[3]), int(region[2]))
+        keep = {}
+        for name in ("point", "normal", "material"):
+            if planes.get(name) is not None:
+                keep[name] = np.ascontiguousarray(planes[name], SURFACE_DTYPES[name])
+                want = (h, w, 4, 3) if SURFACE_WIDTHS[name] == 3 else (h, w, 4)
+                if keep[name].shape != want:
+                    raise ValueError(f"ambient: plane {name} has shape {keep[name].shape}, want {want}")
+        d, cs = _ambient_samples(dirs, max_t)
+        out = {n: np.empty((h, w, 4) if n == "occluded" else (h, w), np.uint32) for n in outputs}
+        _check(lib().rrt_ambient_surface(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))),
+                                         C.byref(CSurface(**{n: a.ctypes.data for n, a in keep.items()})), C.byref(cs),
+                                         C.byref(CAmbient(**{n: a.ctypes.data for n, a in out.items()}))), "rrt_ambient_surface")
+        return out
+
+    def ambient_into(self, out_tensors: dict, plane_tensors: dict, dirs, max_t: float, width: int, height: int, region=None, stream: Optional[int] = None):
+        """rrt_ambient_surface_device: plane_tensors = {plane: contiguous device tensor} with point, normal and material as surface_into filled them;
+        out_tensors = {"occluded": 4*w*h four-byte elements, "grey": w*h four-byte elements} of the region, either or both; dirs (host, [n][3]) and max_t as
+        ambient(); enqueued, not synchronised."""
+        px = width * height if region is None else int(region[2]) * int(region[3])
+        assert set(out_tensors) <= set(AMBIENT_OUTPUTS), sorted(out_tensors)
+        for name, t in out_tensors.items():
+            _device_tensor(t, 4 * px if name == "occluded" else px, 4, name)
+        for name in ("point", "normal", "material"):
+            if plane_tensors.get(name) is not None:
+                _device_tensor(plane_tensors[name], 4 * px * SURFACE_WIDTHS[name], np.dtype(SURFACE_DTYPES[name]).itemsize, name)
+        ptr = lambda name: plane_tensors[name].data_ptr() if plane_tensors.get(name) is not None else None
+        d, cs = _ambient_samples(dirs, max_t)
+        _check(lib().rrt_ambient_surface_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))),
+                                                C.byref(CSurface(point=ptr("point"), normal=ptr("normal"), material=ptr("material"))), C.byref(cs),
+                                                C.byref(CAmbient(**{n: t.data_ptr() for n, t in out_tensors.items()})), _P(_stream(stream))),
+               "rrt_ambient_surface_device")
+
     # pre-bound launchers for per-frame loops (bench.py): all argument conversion is done once, the returned callable is one ctypes call
     def bind_render(self, fb_tensor, width: int, height: int, stream: Optional[int] = None):
         assert fb_tensor.is_cuda and fb_tensor.is_contiguous() and fb_tensor.numel() == width * height and fb_tensor.element_size() == 4
@@ -853,6 +906,12 @@ class MultiGpu:
         v = C.c_double(-1.0)
         _check(lib().rrt_multi_last_gather_ms(self._h, C.byref(v)), "rrt_multi_last_gather_ms")
         return v.value
+
+
+def _ambient_samples(dirs, max_t):
+    """(the [n][3] float64 array, which must outlive the call, and the rrt_ambient_samples that points at it)"""
+    d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+    return d, CAmbientSamples(dirs=d.ctypes.data_as(_dp), n=len(d), max_t=float(max_t))
 
 
 def _device_tensor(t, n: int, itemsize: int, name: str):

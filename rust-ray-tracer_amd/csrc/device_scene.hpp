@@ -159,6 +159,23 @@ struct ShadeParams {
     uint32_t* out;
 };
 
+// Argument of the ambient kernels (render.hip: ambient_kernel; rrt.h: rrt_ambient_surface_device): a VisParams -- frame, region and tile rectangle; its six plane
+// pointers are unused -- plus the three planes the kernel READS, laid out as the surface launch wrote them for that region, the two planes it writes (occluded:
+// [rows][columns][4 sub-samples] masks; grey: [rows][columns] pixels; either may be null, not both) and the sample table: n_samples directions in the tangent
+// frame of a hit, and the max_t of every ray.  The table travels in the kernel arguments, as the lights do: wave-uniform, read with scalar loads.
+#ifndef RRT_MAX_AMBIENT_SAMPLES
+#define RRT_MAX_AMBIENT_SAMPLES 32
+#endif
+struct AmbientParams {
+    VisParams V;
+    const double *point, *normal; const uint32_t* material;
+    uint32_t *occluded, *grey;
+    uint32_t n_samples, _pad;
+    double max_t;
+    double dirs[RRT_MAX_AMBIENT_SAMPLES][3];
+};
+static_assert(sizeof(DevScene) + sizeof(AmbientParams) < 4096, "the arguments of ambient_kernel must fit the 4 KB kernel-argument segment");
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);
@@ -168,6 +185,8 @@ int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int w
 int launch_surface(const DevScene& s, const SurfaceParams& q, void* stream, int walk);
 // the pixels of a region of a frame from its kept planes (render.hip: shade_kernel)
 int launch_shade(const DevScene& s, const ShadeParams& q, void* stream, int walk);
+// the occlusion masks and the grey pixels of a region of a frame from its kept planes (render.hip: ambient_kernel)
+int launch_ambient(const DevScene& s, const AmbientParams& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk);
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,

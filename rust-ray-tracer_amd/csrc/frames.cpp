@@ -1,8 +1,9 @@
-// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility and surface buffers, frames shaded from those buffers, per-ray queries, the choice of traversal variant, and
+// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility and surface buffers, frames shaded and ambient occlusion from those buffers, per-ray queries, the choice of traversal variant, and
 // the statistics of the last launch.  Every launch goes through ONE seam, timed_launch + record (the raytracer's two events around it, what it traced into rrt_stats), and
 // every measurement of the variants through fastest_variant.  The host forms add a kept device buffer (device_memory.hpp: KeptBuf) or one allocation per call, and
 // staged_download for the way back.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -325,6 +326,65 @@ void shade_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const r
     HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the pixels are in the caller's memory, and its planes are no longer read, on return
 }
 
+// ---- ambient occlusion from kept planes (rrt.h: rrt_ambient_surface_device).  One launch of ambient_kernel over the tiles the region touches; variant, tuning state and
+// stats as the surface calls.  every check, before any GPU work; returns the region in force
+rrt_region check_ambient(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* planes, const rrt_ambient_samples* samples,
+                         const rrt_ambient* out) {
+    check_frame(rt, width, height);
+    if (!planes || !samples || !out) throw Error{RRT_ERR_INVALID_ARG, "null struct: ambient occlusion takes the surface planes, the sample table and the output planes"};
+    if (!planes->point || !planes->normal || !planes->material) throw Error{RRT_ERR_INVALID_ARG, "null plane: point, normal and material are all required"};
+    if (!out->occluded && !out->grey) throw Error{RRT_ERR_INVALID_ARG, "no output requested: occluded and grey are both null"};
+    if (samples->n == 0 || samples->n > RRT_MAX_AMBIENT_SAMPLES) throw Error{RRT_ERR_INVALID_ARG, "bad sample count: 1 to RRT_MAX_AMBIENT_SAMPLES directions"};
+    if (!samples->dirs) throw Error{RRT_ERR_INVALID_ARG, "null sample directions"};
+    for (uint32_t k = 0; k < 3 * samples->n; k++)
+        if (!std::isfinite(samples->dirs[k])) throw Error{RRT_ERR_INVALID_ARG, "a sample direction has a non-finite component"};
+    if (!(samples->max_t > 0.0)) throw Error{RRT_ERR_INVALID_ARG, "max_t is NaN or not positive"};
+    const rrt_region r = region ? *region : rrt_region{0, 0, width, height};
+    if (r.w == 0 || r.h == 0) throw Error{RRT_ERR_INVALID_ARG, "empty region"};
+    if ((uint64_t)r.x0 + r.w > width || (uint64_t)r.y0 + r.h > height) throw Error{RRT_ERR_INVALID_ARG, "region sticks out of the frame"};
+    return r;
+}
+
+// the masks and grey pixels of region r (checked) from planes in device memory on the caller's stream, timed by the raytracer's events.  The sample table is
+// copied into the kernel's argument here: no device memory holds it.
+void launch_ambient_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_surface& d_planes, const rrt_ambient_samples& samples,
+                          const rrt_ambient& d_out, void* stream) {
+    AmbientParams q{};
+    q.V = vis_params(rt, width, height, r, rrt_visibility{});            // (the kernel writes no visibility plane)
+    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material;
+    q.occluded = d_out.occluded; q.grey = d_out.grey;
+    q.n_samples = samples.n; q.max_t = samples.max_t;
+    std::memcpy(q.dirs, samples.dirs, sizeof(double) * 3 * samples.n);
+    const int variant = visibility_variant(rt, width, height);
+    timed_launch(rt, stream, [&] { return launch_ambient(rt->scene, q, stream, variant); });
+    record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
+}
+
+// Host form: the three planes up into the kept allocation of the visibility calls, the launch, the requested outputs down; nothing in flight on return.
+void ambient_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_surface& planes, const rrt_ambient_samples& samples,
+                       const rrt_ambient& out) {
+    DeviceGuard guard(rt->device);
+    constexpr int kIn = 3, kOut = 2;
+    const void* host[kIn] = {planes.point, planes.normal, planes.material};
+    constexpr size_t elem[kIn] = {24, 24, 4};                            // bytes per sub-sample
+    void* back[kOut] = {out.occluded, out.grey};
+    const size_t n = 4 * (size_t)r.w * r.h;
+    const size_t out_bytes[kOut] = {sizeof(uint32_t) * n, sizeof(uint32_t) * (size_t)r.w * r.h};
+    size_t need = 0;
+    for (int k = 0; k < kIn; k++) need += (elem[k] * n + 255) & ~(size_t)255;
+    for (int k = 0; k < kOut; k++) if (back[k]) need += (out_bytes[k] + 255) & ~(size_t)255;
+    DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
+    void *dev[kIn], *d_back[kOut];
+    for (int k = 0; k < kIn; k++) dev[k] = arena.take<char>(elem[k] * n);
+    for (int k = 0; k < kOut; k++) d_back[k] = back[k] ? arena.take<char>(out_bytes[k]) : nullptr;
+    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
+    for (int k = 0; k < kIn; k++) staged_upload(dev[k], host[k], elem[k] * n, rt->own_stream);
+    launch_ambient_frame(rt, width, height, r, rrt_surface{(double*)dev[0], (double*)dev[1], (uint32_t*)dev[2], nullptr}, samples,
+                         rrt_ambient{(uint32_t*)d_back[0], (uint32_t*)d_back[1]}, rt->own_stream);
+    for (int k = 0; k < kOut; k++) if (back[k]) staged_download(back[k], d_back[k], out_bytes[k], rt->own_stream);
+    HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the outputs are in the caller's memory, and its planes are no longer read, on return
+}
+
 // ---- per-ray queries.  The device forms (rrt.h: rrt_intersect_rays_device, ...): no allocation, no copy, no synchronisation; launch(variant) on the caller's stream.
 template <class Launch> int device_ray_query(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, bool any_output, void* stream, Launch&& launch) {
     check_rays(rt, n, d_origins, d_dirs, any_output);
@@ -442,6 +502,25 @@ int rrt_shade_surface(rrt_raytracer* rt, uint32_t width, uint32_t height, const 
     return guarded([&]() -> int {
         const rrt_region r = check_shade(rt, width, height, region, vis, planes, out_fb);
         shade_from_host(rt, width, height, r, *vis, *planes, out_fb);
+        return RRT_OK;
+    });
+}
+
+int rrt_ambient_surface_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* d_planes,
+                               const rrt_ambient_samples* samples, const rrt_ambient* d_out, void* stream) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_ambient(rt, width, height, region, d_planes, samples, d_out);
+        DeviceGuard guard(rt->device);
+        launch_ambient_frame(rt, width, height, r, *d_planes, *samples, *d_out, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_ambient_surface(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* planes,
+                        const rrt_ambient_samples* samples, const rrt_ambient* out) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_ambient(rt, width, height, region, planes, samples, out);
+        ambient_from_host(rt, width, height, r, *planes, *samples, *out);
         return RRT_OK;
     });
 }

@@ -31,8 +31,8 @@
 #include "device_scene.hpp"
 
 // The library compiles this file THREE times (csrc/Makefile), same device functions, different code-generation switches per group of kernels:
-//   -DRRT_TU=1  the bundle-filter frame, visibility, surface and shade kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
-//   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility, surface and shade kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
+//   -DRRT_TU=1  the bundle-filter frame, visibility, surface, shade and ambient kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
+//   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility, surface, shade and ambient kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
 //   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
@@ -2023,6 +2023,83 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
     if (sub == 0 && in_region) Q.out[pixel_i] = mixed;
 }
 
+// Ambient occlusion from kept buffers (rrt.h: rrt_ambient_surface_device): per sub-sample of a region of the frame a mask of which of n hemisphere rays from its
+// hit are occluded, and per pixel the share of open rays as a grey value, from the point, normal and material planes surface_kernel wrote.  No primary ray is
+// walked.  A lane loads its hit and builds the reference's tangent frame (raytracer.rs:137-152, the helpers of surface_kernel's bump frame) ONCE; the loop is over
+// the SAMPLES: sample k of the table -- kernel arguments, wave-uniform, scalar registers -- gives every hit lane of the wave its ray k, so a turn walks the 64
+// rays that share a direction in their tangent frames (neighbouring hits of one surface: nearly parallel rays from nearly the same place, a tight bundle) and
+// keeps one bit per lane.  The rays live in registers only.
+// ONE call site of the walk, with the arguments surface_kernel gives a shadow turn (any_ok, filters on, not one_origin, active = the lane holds a hit).  A wave
+// with no hit writes its zeros and leaves without calling the walk; no lane leaves before the last walk.
+// A material index at or beyond the table (0xFFFFFFFF: a miss) is a miss; no value of the caller's planes is used as an index.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevScene S, const AmbientParams Q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t lane = threadIdx.x;
+    const Stack stk{lds + kParkBytes, lane};
+    const VisParams& P = Q.V;
+    const FrameParams& F = P.F;
+    // Block order, tile quadrant, pixel and sub-sample: shade_kernel's, restated (see visibility_kernel); no direction is formed from the pixel here
+    uint32_t blk = blockIdx.x;
+    if (F.xcd_chunk) {
+        const uint32_t C = F.xcd_chunk, full = (gridDim.x / (8u * C)) * (8u * C);
+        if (blk < full) { const uint32_t xcd = blk & 7u, i = blk >> 3; blk = ((i / C) * 8u + xcd) * C + (i % C); }
+    }
+    const uint32_t local_tile = blk >> 2, quad = blk & 3u;
+    const uint32_t pix = lane >> 2, sub = lane & 3u;
+    const bool tile_ok = local_tile < F.tile_end;
+    const uint32_t tx = P.tile_x0 + (tile_ok ? local_tile % P.tiles_w : 0), ty = P.tile_y0 + (tile_ok ? local_tile / P.tiles_w : 0);
+    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
+    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
+    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
+    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;   // col_end <= width, row_end <= height
+    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;   // the pixels the reference traces (render_kernel)
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    // (pixel index inside the region; the element index of a sub-sample is 4 * that + sub.  Only lanes inside the region use either.)
+    const size_t pixel_i = ((size_t)(py - F.row_begin) * (P.col_end - P.col_begin)) + (px - P.col_begin);
+    const size_t i = pixel_i * 4 + sub;
+    // ---- the lane's hit
+    bool hit = false;
+    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
+    if (traced && Q.material[i] < S.n_mats) {   // (0xFFFFFFFF, a miss, and anything else beyond the table: a miss -- shade_kernel's rule)
+        hit = true;
+        p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
+    }
+    const uint32_t n_samples = Q.n_samples;
+    uint32_t mask = 0;
+    if (__any(hit)) {
+        // the tangent frame of the hit, raytracer.rs:137-152, once for all samples
+        V3 tg = mk(0, 0, 0), bt = mk(0, 0, 0);
+        if (hit) {
+            tg = cross(n, mk(0.0, 1.0, 0.0));                                            // raytracer.rs:137-141
+            double len_tg = length(tg);
+            if (len_tg == 0.0) { tg = cross(n, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }   // raytracer.rs:143-149
+            tg = div3(tg, len_tg);                                                       // raytracer.rs:151
+            bt = normalised(cross(n, tg));                                               // raytracer.rs:152
+        }
+        const V3 ro = p + n * S.surface_offset;                                          // the origin of a shadow ray, raytracer.rs:170
+        for (uint32_t k = 0; k < n_samples; k++) {
+            const double sx = Q.dirs[k][0], sy = Q.dirs[k][1], sz = Q.dirs[k][2];        // wave-uniform
+            // (tg*sx + bt*sy) + n*sz, per component five operations, each rounded on its own: the shape of rrt_camera.  (a lane without a hit takes no part; its
+            // ray is a harmless one)
+            const V3 rd = hit ? mk((tg.x * sx + bt.x * sy) + n.x * sz, (tg.y * sx + bt.y * sy) + n.y * sz, (tg.z * sx + bt.z * sy) + n.z * sz) : mk(0, 0, 1);
+            double wt; uint32_t wslot;
+            if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, hit, true, true, ro, rd, Q.max_t, wt, wslot);
+            else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, hit, true, true, false, ro, rd, Q.max_t, wt, wslot);
+            if (hit && wslot != kNone) mask |= 1u << k;
+        }
+    }
+    // ---- grey: the open rays of the pixel's four sub-samples = 4 consecutive lanes, summed as render_kernel sums Color::mix; 255 * open / (4 n), rounded half up
+    uint32_t open = traced ? (hit ? n_samples - (uint32_t)__popc(mask) : n_samples) : 0u;
+    open += __shfl_xor(open, 1);
+    open += __shfl_xor(open, 2);
+    if (!in_region) return;
+    if (Q.occluded) Q.occluded[i] = mask;
+    if (Q.grey && sub == 0) Q.grey[pixel_i] = traced ? ((510u * open + 4u * n_samples) / (8u * n_samples)) * 0x010101u : 0u;
+}
+
 #endif   // RRT_TU_FRAME || RRT_TU_LANE
 #if RRT_TU_FRAME
 __global__ __launch_bounds__(256) void detile_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t world, uint32_t tiles_per_rank,
@@ -2244,6 +2321,20 @@ int launch_shade(const DevScene& s, const ShadeParams& q, void* stream, int walk
     });
 }
 
+// The occlusion masks and grey pixels of a region of a frame from its kept planes (device_scene.hpp: AmbientParams): the grid of launch_shade.
+int launch_ambient_lane_ray(const DevScene& s, const AmbientParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+int launch_ambient(const DevScene& s, const AmbientParams& q, void* stream, int walk) {
+    walk = effective_walk(s, walk);
+    const uint32_t n_tiles = q.V.F.tile_end;
+    if (n_tiles == 0) return 0;
+    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
+    if (walk != kWalkBundle) return launch_ambient_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
+    return with_groups(s, [&](auto groups) {
+        hipLaunchKernelGGL((ambient_kernel<kWalkBundle, groups()>), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
+        return (int)hipGetLastError();
+    });
+}
+
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
     const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
     const uint32_t tpr = (tiles_x * tiles_y + world - 1) / world;
@@ -2290,6 +2381,14 @@ int launch_shade_lane_ray(const DevScene& s, const ShadeParams& q, void* stream,
     return with_lane_or_ray_walk(walk, [&](auto w) {
         return with_groups(s, [&](auto groups) {
             hipLaunchKernelGGL((shade_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
+            return (int)hipGetLastError();
+        });
+    });
+}
+int launch_ambient_lane_ray(const DevScene& s, const AmbientParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+    return with_lane_or_ray_walk(walk, [&](auto w) {
+        return with_groups(s, [&](auto groups) {
+            hipLaunchKernelGGL((ambient_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
             return (int)hipGetLastError();
         });
     });
