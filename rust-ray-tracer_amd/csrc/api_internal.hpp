@@ -37,13 +37,14 @@ struct rrt_raytracer {
     int walk_rays = -1;              // ... and by its per-ray entry points (rrt_get_ray_colours / rrt_intersect_rays / rrt_occluded_rays and their _device forms): -1 = not measured yet (frames.cpp: measure_rays)
     bool variant_forced = false;
     rrt::KeptBuf host_fb;            // device framebuffer kept between rrt_render / rrt_render_progressive calls (host-framebuffer entry points), grown when a larger frame comes
-    rrt::KeptBuf vis_buf;            // device planes kept between rrt_render_visibility / rrt_pick calls (host-pointer entry points)
+    rrt::KeptBuf vis_buf;            // device planes kept between the host forms of the region calls: rrt_render_visibility, rrt_pick, rrt_render_surface,
+                                     // rrt_shade_surface, rrt_ambient_surface (frames.cpp: with_kept_planes carves it anew in every call)
     rrt::KeptBuf tune_buf;           // outputs of the measurement launches of rrt_tune_rays_device
     uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records in use (built.n_chains, or 0 where the shortcut's precondition fails: create_raytracer)
     double upload_ms = 0, hip_init_ms = 0, create_ms = 0;   // set-up stages of rrt_raytracer_create besides built.ms_octree / ms_index; wall time of the whole call
     bool gpu_setup = false;          // scene built on the device (default) or on the host (RRT_FLAG_HOST_SETUP)
     struct Buf { const void* p = nullptr; size_t bytes = 0; } bufs[16];   // rrt_raytracer_get_buffer
-    hipStream_t own_stream = nullptr;   // rrt_render's stream: the device's shared set-up stream (staging.hpp: setup_stream; not owned)
+    hipStream_t own_stream = nullptr;   // the stream of the calls that bring results into host memory (frames.cpp: own_stream), set at the first of them
     uint32_t tuned_w = 0, tuned_h = 0, tuned_world = 0;   // frame size the variant below belongs to
     uint32_t size_frames = 0;        // frames rendered at that size so far
     bool size_measured = false;      // ... and whether the variants have been timed on it (second frame of a size)

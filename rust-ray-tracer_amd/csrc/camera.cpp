@@ -17,7 +17,7 @@ bool finite3(const rrt_vec3& v) { return std::isfinite(v.x) && std::isfinite(v.y
 
 // layout of rrt_raytracer::guard_mem: the list the kernels read, then -- in one piece, read back with one copy -- the counter and the search's records
 constexpr size_t kListBytes = sizeof(DevSuspect) * (RRT_MAX_SUSPECTS + 1);
-constexpr size_t kCountOff = (kListBytes + 255) & ~(size_t)255;
+constexpr size_t kCountOff = slot_bytes(kListBytes);
 struct SearchResult { uint32_t count, _pad; SuspectRecord rec[RRT_MAX_SUSPECTS + 1]; };
 static_assert(offsetof(SearchResult, rec) == 8 && sizeof(SuspectRecord) == 40, "counter and records are read back as one block");
 

@@ -179,14 +179,10 @@ static_assert(sizeof(DevScene) + sizeof(AmbientParams) < 4096, "the arguments of
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);
-// the visibility planes of a region of a frame (render.hip: visibility_kernel)
-int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int walk);
-// the surface planes (and any visibility planes) of a region of a frame (render.hip: surface_kernel)
-int launch_surface(const DevScene& s, const SurfaceParams& q, void* stream, int walk);
-// the pixels of a region of a frame from its kept planes (render.hip: shade_kernel)
-int launch_shade(const DevScene& s, const ShadeParams& q, void* stream, int walk);
-// the occlusion masks and the grey pixels of a region of a frame from its kept planes (render.hip: ambient_kernel)
-int launch_ambient(const DevScene& s, const AmbientParams& q, void* stream, int walk);
+// A region of a frame (render.hip: launch_region), for Params = VisParams (visibility_kernel: the visibility planes), SurfaceParams (surface_kernel: the surface
+// planes and any visibility planes), ShadeParams (shade_kernel: the pixels from kept planes) and AmbientParams (ambient_kernel: occlusion masks and grey pixels from
+// kept planes).  Defined and instantiated for these four in render.hip.
+template <class Params> int launch_region(const DevScene& s, const Params& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk);
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,

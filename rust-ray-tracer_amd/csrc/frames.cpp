@@ -1,7 +1,11 @@
-// frames.cpp -- every launch behind include/rrt.h: frames into device or host framebuffers, their visibility and surface buffers, frames shaded and ambient occlusion from those buffers, per-ray queries, the choice of traversal variant, and
-// the statistics of the last launch.  Every launch goes through ONE seam, timed_launch + record (the raytracer's two events around it, what it traced into rrt_stats), and
-// every measurement of the variants through fastest_variant.  The host forms add a kept device buffer (device_memory.hpp: KeptBuf) or one allocation per call, and
-// staged_download for the way back.
+// frames.cpp -- every launch behind include/rrt.h.
+//   Frames: into a device framebuffer or a rank's tiles, into host memory, progressively.
+//   Regions of a frame: visibility and surface buffers, frames shaded and ambient occlusion from kept buffers, the pick of one pixel.
+//   Per-ray queries, the choice of the traversal variant, and the statistics of the last launch.
+// Every launch goes through ONE seam: timed_launch (the raytracer's two events around it) and record (what it traced, into rrt_stats).  Every measurement of the
+// variants goes through fastest_variant.  The region calls share one check of the region (region_in_force), one launch (launch_region_frame) and, for their host
+// forms, one routine that carves the kept device allocation and copies the planes up and down (with_kept_planes).  The host forms of the per-ray queries make one
+// allocation per call.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -160,24 +164,18 @@ void launch_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t r
     record(rt, width, height, world == 1 ? 4 * traced_pixels(width, height) : 0, rt->walk);
 }
 
-// ---- visibility buffers (rrt.h: rrt_render_visibility_device).  One launch of visibility_kernel over the tiles the region touches.
+// ---- regions of a frame: visibility buffers, surface buffers, shading and ambient occlusion from kept buffers, pick.  Each is one launch of its kernel over the tiles
+// the region touches (rrt.h: rrt_render_visibility_device, rrt_render_surface_device, rrt_shade_surface_device, rrt_ambient_surface_device).
 // The variant: the forced one, else the one kept for this frame size, else the first-frame rule's.  Reads the tuning state, never writes it: a
-// visibility or pick call is not a frame of that size.
+// region call is not a frame of that size.
 int visibility_variant(const rrt_raytracer* rt, uint32_t width, uint32_t height) {
     if (rt->variant_forced) return rt->walk;
     if (rt->tuned_w == width && rt->tuned_h == height && rt->tuned_world == 1u) return rt->walk;
     return first_frame_variant(rt, width, height);
 }
 
-constexpr int kPlanes = 6, kSurfacePlanes = 4, kAllPlanes = kPlanes + kSurfacePlanes;
-constexpr size_t kPlaneElem[kAllPlanes] = {1, 8, 8, 8, 4, 4,    // hit, t, u, v, tri, albedo: bytes per sub-sample
-                                           24, 24, 4, 4};        // point, normal, material, lights (rrt_surface)
-
-// every check of a visibility call, before any GPU work; returns the region in force
-rrt_region check_visibility(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* planes) {
-    check_frame(rt, width, height);
-    if (!planes) throw Error{RRT_ERR_INVALID_ARG, "null planes struct"};
-    if (!planes->hit && !planes->t && !planes->u && !planes->v && !planes->tri && !planes->albedo) throw Error{RRT_ERR_INVALID_ARG, "no plane requested: all six pointers are null"};
+// The region in force: the caller's, or the whole frame; the last check of every region call, after those of its own arguments.
+rrt_region region_in_force(uint32_t width, uint32_t height, const rrt_region* region) {
     const rrt_region r = region ? *region : rrt_region{0, 0, width, height};
     if (r.w == 0 || r.h == 0) throw Error{RRT_ERR_INVALID_ARG, "empty region"};
     if ((uint64_t)r.x0 + r.w > width || (uint64_t)r.y0 + r.h > height) throw Error{RRT_ERR_INVALID_ARG, "region sticks out of the frame"};
@@ -197,50 +195,87 @@ VisParams vis_params(const rrt_raytracer* rt, uint32_t width, uint32_t height, c
     return p;
 }
 
-// the planes of region r (checked) into device memory on the caller's stream, timed by the raytracer's events
-void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes, void* stream) {
-    const VisParams p = vis_params(rt, width, height, r, d_planes);
+// The one region launch: the finished kernel argument q of region r (checked) on the caller's stream, timed by the raytracer's events and recorded.
+template <class Params> void launch_region_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const Params& q, void* stream) {
     const int variant = visibility_variant(rt, width, height);
-    timed_launch(rt, stream, [&] { return launch_visibility(rt->scene, p, stream, variant); });
+    timed_launch(rt, stream, [&] { return launch_region(rt->scene, q, stream, variant); });
     record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
 }
 
-// Host forms: the wanted planes of n sub-samples carved out of the raytracer's kept device allocation (grown when a larger request comes), each on a
-// 256-byte boundary; returns the bytes in use.
-// (count = kPlanes: the visibility planes; kAllPlanes: those and the surface planes behind them)
-size_t kept_planes(rrt_raytracer* rt, size_t n, const void* const* want, void** dev, int count = kPlanes) {
-    size_t need = 0;
-    for (int k = 0; k < count; k++) if (want[k]) need += (kPlaneElem[k] * n + 255) & ~(size_t)255;
-    DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
-    for (int k = 0; k < count; k++) dev[k] = want[k] ? arena.take<char>(kPlaneElem[k] * n) : nullptr;
-    return arena.used;
+// ---- the host forms of the region calls.  A plane of the caller's in host memory, and where it lives in the raytracer's kept device allocation for one call.
+enum : int { kCarve = 0, kUp = 1, kDown = 2 };       // copied host -> device before the launch, device -> host after it (kUp | kDown: both), or only carved
+struct HostPlane {
+    void* host;              // the caller's pointer; null: the plane is not wanted, it gets no device memory and `dev` stays null
+    size_t elem, count;      // bytes per element, elements
+    int dir;
+    void* dev = nullptr;
+    size_t bytes() const { return elem * count; }
+};
+HostPlane plane_up(const void* host, size_t elem, size_t count) { return HostPlane{const_cast<void*>(host), elem, count, kUp}; }   // (an input is only read)
+HostPlane plane_down(void* host, size_t elem, size_t count) { return HostPlane{host, elem, count, kDown}; }
+// The six visibility planes of n sub-samples into pl[0, 6), in the order of rrt_visibility -- hit, t, u, v, tri, albedo -- and back as device pointers.  (rrt_pick
+// relies on this order: see pick_pixel.)
+constexpr int kPlanes = 6;
+void visibility_planes(HostPlane* pl, const rrt_visibility& v, size_t n, int dir) {
+    pl[0] = {v.hit, 1, n, dir}; pl[1] = {v.t, 8, n, dir}; pl[2] = {v.u, 8, n, dir}; pl[3] = {v.v, 8, n, dir}; pl[4] = {v.tri, 4, n, dir}; pl[5] = {v.albedo, 4, n, dir};
 }
-rrt_visibility planes_of(void* const p[kPlanes]) { return rrt_visibility{(uint8_t*)p[0], (double*)p[1], (double*)p[2], (double*)p[3], (uint32_t*)p[4], (uint32_t*)p[5]}; }
+rrt_visibility device_visibility(const HostPlane* pl) {
+    return rrt_visibility{(uint8_t*)pl[0].dev, (double*)pl[1].dev, (double*)pl[2].dev, (double*)pl[3].dev, (uint32_t*)pl[4].dev, (uint32_t*)pl[5].dev};
+}
+
+// the raytracer's own stream, for the calls that bring results into host memory: the device's shared set-up stream (staging.hpp: setup_stream; not owned)
+hipStream_t own_stream(rrt_raytracer* rt) {
+    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
+    return rt->own_stream;
+}
+
+// One host-form call: the wanted planes carved out of the raytracer's kept device allocation (grown when a larger request comes) IN THE ORDER OF `planes` from offset
+// 0, each in a slot of its own (device_memory.hpp: slot_bytes); the inputs up, launch(stream) on the raytracer's own stream, the outputs down, one wait.  Blocking:
+// on return the outputs are in the caller's memory and its inputs are no longer read.
+// (a page-locked plane's copy is only enqueued: all of those are in flight before the one wait)
+template <size_t K, class Launch> void with_kept_planes(rrt_raytracer* rt, HostPlane (&planes)[K], Launch&& launch) {
+    size_t need = 0;
+    for (const HostPlane& p : planes) if (p.host) need += slot_bytes(p.bytes());
+    DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
+    for (HostPlane& p : planes) if (p.host) p.dev = arena.take<char>(p.bytes());
+    const hipStream_t stream = own_stream(rt);
+    for (const HostPlane& p : planes) if (p.host && (p.dir & kUp)) staged_upload(p.dev, p.host, p.bytes(), stream);
+    launch(stream);
+    for (const HostPlane& p : planes) if (p.host && (p.dir & kDown)) staged_download(p.host, p.dev, p.bytes(), stream);
+    HIP_TRY(hipStreamSynchronize(stream));
+}
+
+// ---- visibility buffers.  every check of a visibility call, before any GPU work; returns the region in force
+rrt_region check_visibility(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* planes) {
+    check_frame(rt, width, height);
+    if (!planes) throw Error{RRT_ERR_INVALID_ARG, "null planes struct"};
+    if (!planes->hit && !planes->t && !planes->u && !planes->v && !planes->tri && !planes->albedo) throw Error{RRT_ERR_INVALID_ARG, "no plane requested: all six pointers are null"};
+    return region_in_force(width, height, region);
+}
+
+// the planes of region r (checked) into device memory
+void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes, void* stream) {
+    launch_region_frame(rt, width, height, r, vis_params(rt, width, height, r, d_planes), stream);
+}
 
 void visibility_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& planes) {
     DeviceGuard guard(rt->device);
-    void* host[kPlanes] = {planes.hit, planes.t, planes.u, planes.v, planes.tri, planes.albedo};
-    void* dev[kPlanes];
-    const size_t n = 4 * (size_t)r.w * r.h;
-    kept_planes(rt, n, host, dev);
-    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
-    launch_visibility_frame(rt, width, height, r, planes_of(dev), rt->own_stream);
-    // (a page-locked plane's copy is only enqueued here: all of those are in flight before the one wait below)
-    for (int k = 0; k < kPlanes; k++) if (host[k]) staged_download(host[k], dev[k], kPlaneElem[k] * n, rt->own_stream);
-    HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the planes are in the caller's memory on return
+    HostPlane pl[kPlanes];
+    visibility_planes(pl, planes, 4 * (size_t)r.w * r.h, kDown);
+    with_kept_planes(rt, pl, [&](void* stream) { launch_visibility_frame(rt, width, height, r, device_visibility(pl), stream); });
 }
 
-// One pixel: a one-tile launch into the kept allocation and ONE copy of its six 256-byte plane slots back.
+// One pixel: a one-tile launch into the kept allocation and ONE copy of its six plane slots back.  All six planes of the pixel's four sub-samples are wanted and fit
+// a slot each, so plane k starts at byte 256 * k of the allocation, in the order of visibility_planes; sub-sample 0 is the answer.
 rrt_pick_result pick_pixel(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t px, uint32_t py) {
     DeviceGuard guard(rt->device);
     alignas(8) char back[kPlanes * 256];
-    const void* const all[kPlanes] = {back, back, back, back, back, back};   // (every plane wanted)
-    void* dev[kPlanes];
-    const size_t used = kept_planes(rt, 4, all, dev);                        // the pixel's four sub-samples; sub-sample 0 is the answer
-    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
-    launch_visibility_frame(rt, width, height, rrt_region{px, py, 1, 1}, planes_of(dev), rt->own_stream);
-    HIP_TRY(hipMemcpyAsync(back, rt->vis_buf.mem.h, used, hipMemcpyDeviceToHost, rt->own_stream));
-    HIP_TRY(hipStreamSynchronize(rt->own_stream));
+    HostPlane pl[kPlanes];
+    visibility_planes(pl, rrt_visibility{(uint8_t*)back, (double*)back, (double*)back, (double*)back, (uint32_t*)back, (uint32_t*)back}, 4, kCarve);   // (every plane wanted)
+    with_kept_planes(rt, pl, [&](void* stream) {
+        launch_visibility_frame(rt, width, height, rrt_region{px, py, 1, 1}, device_visibility(pl), stream);
+        HIP_TRY(hipMemcpyAsync(back, pl[0].dev, sizeof back, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    });
     rrt_pick_result out{};
     uint8_t hit; std::memcpy(&hit, back, 1); out.hit = hit;
     std::memcpy(&out.t, back + 256, 8); std::memcpy(&out.u, back + 512, 8); std::memcpy(&out.v, back + 768, 8);
@@ -248,86 +283,63 @@ rrt_pick_result pick_pixel(rrt_raytracer* rt, uint32_t width, uint32_t height, u
     return out;
 }
 
-// ---- surface buffers (rrt.h: rrt_render_surface_device).  One launch of surface_kernel over the tiles the region touches; variant, tuning state and stats as the
-// visibility calls.  every check, before any GPU work; returns the region in force
+// ---- surface buffers.  every check, before any GPU work; returns the region in force
 rrt_region check_surface(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* planes) {
     check_frame(rt, width, height);
     if (!planes) throw Error{RRT_ERR_INVALID_ARG, "null surface planes struct"};
     if (!planes->point && !planes->normal && !planes->material && !planes->lights) throw Error{RRT_ERR_INVALID_ARG, "no surface plane requested: all four pointers are null"};
-    const rrt_region r = region ? *region : rrt_region{0, 0, width, height};
-    if (r.w == 0 || r.h == 0) throw Error{RRT_ERR_INVALID_ARG, "empty region"};
-    if ((uint64_t)r.x0 + r.w > width || (uint64_t)r.y0 + r.h > height) throw Error{RRT_ERR_INVALID_ARG, "region sticks out of the frame"};
-    return r;
+    return region_in_force(width, height, region);
 }
 
 void launch_surface_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* stream) {
     SurfaceParams q{};
     q.V = vis_params(rt, width, height, r, d_vis);
     q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.lights = d_planes.lights;
-    const int variant = visibility_variant(rt, width, height);
-    timed_launch(rt, stream, [&] { return launch_surface(rt->scene, q, stream, variant); });
-    record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
+    launch_region_frame(rt, width, height, r, q, stream);
 }
 
 void surface_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& vis, const rrt_surface& planes) {
     DeviceGuard guard(rt->device);
-    void* host[kAllPlanes] = {vis.hit, vis.t, vis.u, vis.v, vis.tri, vis.albedo, planes.point, planes.normal, planes.material, planes.lights};
-    void* dev[kAllPlanes];
     const size_t n = 4 * (size_t)r.w * r.h;
-    kept_planes(rt, n, host, dev, kAllPlanes);
-    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
-    launch_surface_frame(rt, width, height, r, planes_of(dev), rrt_surface{(double*)dev[6], (double*)dev[7], (uint32_t*)dev[8], (uint32_t*)dev[9]}, rt->own_stream);
-    for (int k = 0; k < kAllPlanes; k++) if (host[k]) staged_download(host[k], dev[k], kPlaneElem[k] * n, rt->own_stream);
-    HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the planes are in the caller's memory on return
+    HostPlane pl[kPlanes + 4];
+    visibility_planes(pl, vis, n, kDown);
+    pl[6] = plane_down(planes.point, 24, n); pl[7] = plane_down(planes.normal, 24, n); pl[8] = plane_down(planes.material, 4, n); pl[9] = plane_down(planes.lights, 4, n);
+    with_kept_planes(rt, pl, [&](void* stream) {
+        launch_surface_frame(rt, width, height, r, device_visibility(pl), rrt_surface{(double*)pl[6].dev, (double*)pl[7].dev, (uint32_t*)pl[8].dev, (uint32_t*)pl[9].dev}, stream);
+    });
 }
 
-// ---- shading from kept planes (rrt.h: rrt_shade_surface_device).  One launch of shade_kernel over the tiles the region touches; variant, tuning state and stats as the
-// surface calls.  every check, before any GPU work; returns the region in force
+// ---- shading from kept planes.  every check, before any GPU work; returns the region in force
 rrt_region check_shade(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_visibility* vis, const rrt_surface* planes, const void* out) {
     check_frame(rt, width, height);
     if (!vis || !planes) throw Error{RRT_ERR_INVALID_ARG, "null planes struct: shading reads the albedo plane of the visibility struct and the planes of the surface struct"};
     if (!vis->albedo || !planes->point || !planes->normal || !planes->material) throw Error{RRT_ERR_INVALID_ARG, "null plane: albedo, point, normal and material are all required"};
     if (!out) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
-    const rrt_region r = region ? *region : rrt_region{0, 0, width, height};
-    if (r.w == 0 || r.h == 0) throw Error{RRT_ERR_INVALID_ARG, "empty region"};
-    if ((uint64_t)r.x0 + r.w > width || (uint64_t)r.y0 + r.h > height) throw Error{RRT_ERR_INVALID_ARG, "region sticks out of the frame"};
-    return r;
+    return region_in_force(width, height, region);
 }
 
-// the pixels of region r (checked) from planes in device memory into d_fb on the caller's stream, timed by the raytracer's events
+// the pixels of region r (checked) from planes in device memory into d_fb
 void launch_shade_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* d_fb, void* stream) {
     ShadeParams q{};
     q.V = vis_params(rt, width, height, r, rrt_visibility{});            // (the kernel writes no plane)
     q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.albedo = d_vis.albedo; q.lights = d_planes.lights;
     q.out = static_cast<uint32_t*>(d_fb);
-    const int variant = visibility_variant(rt, width, height);
-    timed_launch(rt, stream, [&] { return launch_shade(rt->scene, q, stream, variant); });
-    record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
+    launch_region_frame(rt, width, height, r, q, stream);
 }
 
-// Host form: the given planes up into the kept allocation of the visibility calls, the launch, the region's pixels down; nothing in flight on return.
+// Host form: the given planes up, the region's pixels down.
 void shade_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& vis, const rrt_surface& planes, uint32_t* out_fb) {
     DeviceGuard guard(rt->device);
-    constexpr int kIn = 5;
-    const void* host[kIn] = {planes.point, planes.normal, planes.material, vis.albedo, planes.lights};
-    constexpr size_t elem[kIn] = {24, 24, 4, 4, 4};                      // bytes per sub-sample
-    const size_t n = 4 * (size_t)r.w * r.h, fb_bytes = sizeof(uint32_t) * (size_t)r.w * r.h;
-    size_t need = (fb_bytes + 255) & ~(size_t)255;
-    for (int k = 0; k < kIn; k++) if (host[k]) need += (elem[k] * n + 255) & ~(size_t)255;
-    DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
-    void* dev[kIn];
-    for (int k = 0; k < kIn; k++) dev[k] = host[k] ? arena.take<char>(elem[k] * n) : nullptr;
-    uint32_t* d_fb = arena.take<uint32_t>((size_t)r.w * r.h);
-    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
-    for (int k = 0; k < kIn; k++) if (host[k]) staged_upload(dev[k], host[k], elem[k] * n, rt->own_stream);
-    rrt_visibility d_vis{}; d_vis.albedo = (uint32_t*)dev[3];
-    launch_shade_frame(rt, width, height, r, d_vis, rrt_surface{(double*)dev[0], (double*)dev[1], (uint32_t*)dev[2], (uint32_t*)dev[4]}, d_fb, rt->own_stream);
-    staged_download(out_fb, d_fb, fb_bytes, rt->own_stream);
-    HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the pixels are in the caller's memory, and its planes are no longer read, on return
+    const size_t px = (size_t)r.w * r.h, n = 4 * px;
+    HostPlane pl[] = {plane_up(planes.point, 24, n), plane_up(planes.normal, 24, n), plane_up(planes.material, 4, n), plane_up(vis.albedo, 4, n), plane_up(planes.lights, 4, n),
+                      plane_down(out_fb, sizeof(uint32_t), px)};
+    with_kept_planes(rt, pl, [&](void* stream) {
+        rrt_visibility d_vis{}; d_vis.albedo = (uint32_t*)pl[3].dev;
+        launch_shade_frame(rt, width, height, r, d_vis, rrt_surface{(double*)pl[0].dev, (double*)pl[1].dev, (uint32_t*)pl[2].dev, (uint32_t*)pl[4].dev}, pl[5].dev, stream);
+    });
 }
 
-// ---- ambient occlusion from kept planes (rrt.h: rrt_ambient_surface_device).  One launch of ambient_kernel over the tiles the region touches; variant, tuning state and
-// stats as the surface calls.  every check, before any GPU work; returns the region in force
+// ---- ambient occlusion from kept planes.  every check, before any GPU work; returns the region in force
 rrt_region check_ambient(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* planes, const rrt_ambient_samples* samples,
                          const rrt_ambient* out) {
     check_frame(rt, width, height);
@@ -339,14 +351,10 @@ rrt_region check_ambient(const rrt_raytracer* rt, uint32_t width, uint32_t heigh
     for (uint32_t k = 0; k < 3 * samples->n; k++)
         if (!std::isfinite(samples->dirs[k])) throw Error{RRT_ERR_INVALID_ARG, "a sample direction has a non-finite component"};
     if (!(samples->max_t > 0.0)) throw Error{RRT_ERR_INVALID_ARG, "max_t is NaN or not positive"};
-    const rrt_region r = region ? *region : rrt_region{0, 0, width, height};
-    if (r.w == 0 || r.h == 0) throw Error{RRT_ERR_INVALID_ARG, "empty region"};
-    if ((uint64_t)r.x0 + r.w > width || (uint64_t)r.y0 + r.h > height) throw Error{RRT_ERR_INVALID_ARG, "region sticks out of the frame"};
-    return r;
+    return region_in_force(width, height, region);
 }
 
-// the masks and grey pixels of region r (checked) from planes in device memory on the caller's stream, timed by the raytracer's events.  The sample table is
-// copied into the kernel's argument here: no device memory holds it.
+// the masks and grey pixels of region r (checked) from planes in device memory.  The sample table is copied into the kernel's argument here: no device memory holds it.
 void launch_ambient_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_surface& d_planes, const rrt_ambient_samples& samples,
                           const rrt_ambient& d_out, void* stream) {
     AmbientParams q{};
@@ -355,34 +363,20 @@ void launch_ambient_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, co
     q.occluded = d_out.occluded; q.grey = d_out.grey;
     q.n_samples = samples.n; q.max_t = samples.max_t;
     std::memcpy(q.dirs, samples.dirs, sizeof(double) * 3 * samples.n);
-    const int variant = visibility_variant(rt, width, height);
-    timed_launch(rt, stream, [&] { return launch_ambient(rt->scene, q, stream, variant); });
-    record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
+    launch_region_frame(rt, width, height, r, q, stream);
 }
 
-// Host form: the three planes up into the kept allocation of the visibility calls, the launch, the requested outputs down; nothing in flight on return.
+// Host form: the three planes up, the requested outputs down.
 void ambient_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_surface& planes, const rrt_ambient_samples& samples,
                        const rrt_ambient& out) {
     DeviceGuard guard(rt->device);
-    constexpr int kIn = 3, kOut = 2;
-    const void* host[kIn] = {planes.point, planes.normal, planes.material};
-    constexpr size_t elem[kIn] = {24, 24, 4};                            // bytes per sub-sample
-    void* back[kOut] = {out.occluded, out.grey};
-    const size_t n = 4 * (size_t)r.w * r.h;
-    const size_t out_bytes[kOut] = {sizeof(uint32_t) * n, sizeof(uint32_t) * (size_t)r.w * r.h};
-    size_t need = 0;
-    for (int k = 0; k < kIn; k++) need += (elem[k] * n + 255) & ~(size_t)255;
-    for (int k = 0; k < kOut; k++) if (back[k]) need += (out_bytes[k] + 255) & ~(size_t)255;
-    DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
-    void *dev[kIn], *d_back[kOut];
-    for (int k = 0; k < kIn; k++) dev[k] = arena.take<char>(elem[k] * n);
-    for (int k = 0; k < kOut; k++) d_back[k] = back[k] ? arena.take<char>(out_bytes[k]) : nullptr;
-    if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
-    for (int k = 0; k < kIn; k++) staged_upload(dev[k], host[k], elem[k] * n, rt->own_stream);
-    launch_ambient_frame(rt, width, height, r, rrt_surface{(double*)dev[0], (double*)dev[1], (uint32_t*)dev[2], nullptr}, samples,
-                         rrt_ambient{(uint32_t*)d_back[0], (uint32_t*)d_back[1]}, rt->own_stream);
-    for (int k = 0; k < kOut; k++) if (back[k]) staged_download(back[k], d_back[k], out_bytes[k], rt->own_stream);
-    HIP_TRY(hipStreamSynchronize(rt->own_stream));                         // blocking: the outputs are in the caller's memory, and its planes are no longer read, on return
+    const size_t px = (size_t)r.w * r.h, n = 4 * px;
+    HostPlane pl[] = {plane_up(planes.point, 24, n), plane_up(planes.normal, 24, n), plane_up(planes.material, 4, n),
+                      plane_down(out.occluded, sizeof(uint32_t), n), plane_down(out.grey, sizeof(uint32_t), px)};
+    with_kept_planes(rt, pl, [&](void* stream) {
+        launch_ambient_frame(rt, width, height, r, rrt_surface{(double*)pl[0].dev, (double*)pl[1].dev, (uint32_t*)pl[2].dev, nullptr}, samples,
+                             rrt_ambient{(uint32_t*)pl[3].dev, (uint32_t*)pl[4].dev}, stream);
+    });
 }
 
 // ---- per-ray queries.  The device forms (rrt.h: rrt_intersect_rays_device, ...): no allocation, no copy, no synchronisation; launch(variant) on the caller's stream.
@@ -406,9 +400,8 @@ int host_ray_query(rrt_raytracer* rt, uint32_t n, const double* origins, const d
     if (n == 0) return RRT_OK;
     DeviceGuard guard(rt->device);
     const size_t N = n;
-    const auto slot = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };   // (what DevArena::take hands out)
-    size_t need = 2 * slot(24 * N) + (max_t ? slot(8 * N) : 0);
-    for (const HostOut& o : out) need += slot(o.elem * N);
+    size_t need = 2 * slot_bytes(24 * N) + (max_t ? slot_bytes(8 * N) : 0);
+    for (const HostOut& o : out) need += slot_bytes(o.elem * N);
     const DevBuf mem = dev_alloc(need);
     DevArena arena{static_cast<char*>(mem.h), need, 0};
     double *d_o = arena.take<double>(3 * N), *d_d = arena.take<double>(3 * N), *d_m = max_t ? arena.take<double>(N) : nullptr;
@@ -569,10 +562,10 @@ int rrt_render(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t* out
         DeviceGuard guard(rt->device);
         const size_t bytes = sizeof(uint32_t) * (size_t)width * height;
         uint32_t* d_fb = static_cast<uint32_t*>(rt->host_fb.at_least(bytes));
-        if (!rt->own_stream) rt->own_stream = (hipStream_t)setup_stream();
-        launch_frame(rt, width, height, 0, 1, false, d_fb, rt->own_stream);
-        staged_download(out_fb, d_fb, bytes, rt->own_stream);              // page-locked out_fb (rrt_host_buffer_register, ...): one DMA; pageable: through the staging ring
-        HIP_TRY(hipStreamSynchronize(rt->own_stream));                     // blocking: the frame is in out_fb on return
+        const hipStream_t stream = own_stream(rt);
+        launch_frame(rt, width, height, 0, 1, false, d_fb, stream);
+        staged_download(out_fb, d_fb, bytes, stream);                      // page-locked out_fb (rrt_host_buffer_register, ...): one DMA; pageable: through the staging ring
+        HIP_TRY(hipStreamSynchronize(stream));                             // blocking: the frame is in out_fb on return
         return RRT_OK;
     });
 }

@@ -1452,7 +1452,8 @@ __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, co
                     term = 0x00FFFFFFu; live = false;                                    // WHITE, raytracer.rs:109-111
                 } else {
                     PROF_ADD(13, 1);
-                    // --- hit: raytracer.rs:39-57
+                    // --- hit: raytracer.rs:39-57.  The ORIGINAL of surface_of_hit and tangent_frame (below, for the region kernels), written out here: calling
+                    // them from this function changes the register allocation of every render_kernel (profiles/region_kernels_shared_setup.txt).
                     double u = 0, v = 0, t2;
                     mt_full(S.geom + slot, ro, rd, t2, u, v);
                     const DevTriAttr& A = S.attr[slot];
@@ -1634,20 +1635,14 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
     }
 }
 
-// Visibility buffers (rrt.h: rrt_render_visibility_device): the first hit of every primary ray of a region of the frame -- hit, t, u, v, triangle and the
-// colour-texture texel -- instead of a colour.  The waves, their rays and their guard are render_kernel's; each ray is walked once, as intersect_kernel
-// walks it, but from the one origin (one_origin: the bundle and the parked origin are the frame kernels').  A wave covers the tile quadrant its block index
-// says; lanes outside the region or the frame are inactive for the walk and store nothing.
-// Planes are [row][column][sub-sample]: the 16 lanes of one pixel row of a wave (4 pixels x 4 sub-samples) write one contiguous segment, 128 B of an f64
-// plane, 64 B of tri / albedo, 16 B of hit.  The plane pointers are kernel arguments: each test is wave-uniform.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const DevScene S, const VisParams P) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const uint32_t lane = threadIdx.x;
-    const Stack stk{lds + kParkBytes, lane};
+// ---- what the region kernels (visibility, surface, shade, ambient) share.  render_kernel and trace_colour do NOT call these: a helper shared with them changes the
+// register allocation of the frame kernels (profiles/visibility_kernel_resources.txt, profiles/region_kernels_shared_setup.txt), so they keep the original text.
+// A lane of a region launch: block order, tile quadrant, pixel and sub-sample are render_kernel's, but the tiles are those of the region's tile rectangle (tiles_w per
+// row from (tile_x0, tile_y0)) instead of a rank's share of the frame.  in_region: the pixel lies in the region (col_end <= width, row_end <= height); only such lanes
+// store anything.  traced: it is also one of the pixels the reference traces (render_kernel); only such lanes walk a primary ray or read a kept plane.
+struct RegionLane { uint32_t px, py, sub; bool in_region, traced; };
+__device__ __forceinline__ RegionLane region_lane(const VisParams& P, uint32_t lane) {
     const FrameParams& F = P.F;
-    // Block order, tile quadrant, pixel, sub-sample and direction: render_kernel's, restated (a shared helper changed the register allocation of the frame
-    // kernels: profiles/visibility_kernel_resources.txt).  The tiles are those of the region's tile rectangle instead of a rank's share of the frame.
     uint32_t blk = blockIdx.x;
     if (F.xcd_chunk) {
         const uint32_t C = F.xcd_chunk, full = (gridDim.x / (8u * C)) * (8u * C);
@@ -1660,16 +1655,79 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const Dev
     const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
     const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
     const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
-    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;   // col_end <= width, row_end <= height
-    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;   // the pixels the reference traces (render_kernel)
+    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;
+    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;
+    return RegionLane{px, py, sub, in_region, traced};
+}
+// The pixel's index inside the region, [rows][columns]; the element index of a sub-sample in a [rows][columns][4] plane is 4 * that + sub.  Only lanes inside the
+// region use either.
+__device__ __forceinline__ size_t region_pixel(const VisParams& P, const RegionLane& L) {
+    return ((size_t)(L.py - P.F.row_begin) * (P.col_end - P.col_begin)) + (L.px - P.col_begin);
+}
+// The direction of the primary ray of sub-sample `sub` of canvas pixel (px, py), as render_kernel forms it: the sub-samples (x,y),(x+.5,y),(x,y+.5),(x+.5,y+.5) of
+// engine.rs:207-236, then (right*a + up*b) + forward*c, five operations per component, each rounded on its own (rrt.h: rrt_camera).
+__device__ __forceinline__ V3 primary_direction(const FrameParams& F, uint32_t px, uint32_t py, uint32_t sub) {
+    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
     const int32_t x = (int32_t)px - W / 2;
     const int32_t y = (H - H / 2) - (int32_t)py;
-    const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;                      // engine.rs:207-236
+    const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;
     const double yd = (sub & 2u) ? ((double)y + 0.5) : (double)y;
-    const double sa = xd * F.x_scale, sb = yd * F.y_scale, sc = F.z_value;             // (right*a + up*b) + forward*c, five operations per component: rrt.h, rrt_camera
-    const V3 o = ld3(S.origin), d = mk((F.right[0] * sa + F.up[0] * sb) + F.forward[0] * sc,
-                                       (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
-                                       (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
+    const double sa = xd * F.x_scale, sb = yd * F.y_scale, sc = F.z_value;
+    return mk((F.right[0] * sa + F.up[0] * sb) + F.forward[0] * sc,
+              (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
+              (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
+}
+// The tangent frame of a normal (raytracer.rs:137-152): tg = normalised(nn x Y), or of nn x Z where that is the zero vector, and bt = normalised(nn x tg).
+__device__ __forceinline__ void tangent_frame(V3 nn, V3& tg, V3& bt) {
+    tg = cross(nn, mk(0.0, 1.0, 0.0));                                                   // raytracer.rs:137-141
+    double len_tg = length(tg);
+    if (len_tg == 0.0) { tg = cross(nn, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }       // raytracer.rs:143-149
+    tg = div3(tg, len_tg);                                                               // raytracer.rs:151 (t.length() again: same value)
+    bt = normalised(cross(nn, tg));                                                      // raytracer.rs:152
+}
+// The attributes of the hit of list slot `slot` at barycentrics (u, v), raytracer.rs:43-57 and get_normal_at_intersection (raytracer.rs:114-162), as trace_colour
+// forms them: the material index, the colour-texture texel 0x00RRGGBB and the shading normal.
+__device__ __forceinline__ void surface_of_hit(const DevScene& S, uint32_t slot, double u, double v, uint32_t& mat, uint32_t& col, V3& n) {
+    const DevTriAttr& A = S.attr[slot];
+    mat = A.mat;
+    const DevMaterial& M = S.mats[mat];
+    const DevTexture T = M.tex_desc;
+    const double w = 1.0 - u - v;                                                        // raytracer.rs:43
+    const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;                        // raytracer.rs:45-47
+    const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;                        // raytracer.rs:48-50
+    const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);           // raytracer.rs:52
+    const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);         // raytracer.rs:53
+    const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);                  // raytracer.rs:55
+    col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
+    V3 nn = (ld3(A.nrm + 3) * u + ld3(A.nrm + 6) * v) + ld3(A.nrm) * w;                  // raytracer.rs:122-124
+    if (M.bump >= 0) {
+        const DevTexture B = M.bump_desc;
+        const uint8_t* bp = B.rgb + 3ull * ((uint64_t)B.width * tyi + txi);              // raytracer.rs:127-128 (colour-texture indices, bump width)
+        V3 bv = mk((double)bp[0], (double)bp[1], (double)bp[2]);
+        bv = normalised(bv);
+        bv = (bv * 2.0) - mk(1.0, 1.0, 1.0);                                             // raytracer.rs:130-135
+        V3 tg, bt;
+        tangent_frame(nn, tg, bt);
+        nn = mk(dot(bv, tg), dot(bv, bt), dot(bv, nn));                                  // raytracer.rs:154-158
+    }
+    n = normalised(nn);                                                                  // raytracer.rs:161
+}
+
+// Visibility buffers (rrt.h: rrt_render_visibility_device): the first hit of every primary ray of a region of the frame -- hit, t, u, v, triangle and the
+// colour-texture texel -- instead of a colour.  The waves, their rays and their guard are render_kernel's; each ray is walked once, as intersect_kernel
+// walks it, but from the one origin (one_origin: the bundle and the parked origin are the frame kernels').  A wave covers the tile quadrant its block index
+// says; lanes outside the region or the frame are inactive for the walk and store nothing.
+// Planes are [row][column][sub-sample]: the 16 lanes of one pixel row of a wave (4 pixels x 4 sub-samples) write one contiguous segment, 128 B of an f64
+// plane, 64 B of tri / albedo, 16 B of hit.  The plane pointers are kernel arguments: each test is wave-uniform.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const DevScene S, const VisParams P) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t lane = threadIdx.x;
+    const Stack stk{lds + kParkBytes, lane};
+    const RegionLane L = region_lane(P, lane);
+    const uint32_t sub = L.sub;
+    const bool in_region = L.in_region, traced = L.traced;
+    const V3 o = ld3(S.origin), d = primary_direction(P.F, L.px, L.py, sub);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
@@ -1687,7 +1745,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const Dev
     } else {
         t = 0;                                                                           // the miss convention of intersect_kernel; a pixel the reference never traces reads as a miss
     }
-    const size_t i = (((size_t)(py - F.row_begin) * (P.col_end - P.col_begin)) + (px - P.col_begin)) * 4 + sub;
+    const size_t i = region_pixel(P, L) * 4 + sub;
     if (P.albedo) {
         uint32_t col = traced ? 0x00FFFFFFu : 0u;                                        // WHITE, raytracer.rs:109-111; 0 as Canvas::new where nothing is traced
         if (found) {
@@ -1727,30 +1785,10 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevSce
     const uint32_t lane = threadIdx.x;
     const Stack stk{lds + kParkBytes, lane};
     const VisParams& P = Q.V;
-    const FrameParams& F = P.F;
-    // Block order, tile quadrant, pixel, sub-sample and direction: visibility_kernel's, restated (see there)
-    uint32_t blk = blockIdx.x;
-    if (F.xcd_chunk) {
-        const uint32_t C = F.xcd_chunk, full = (gridDim.x / (8u * C)) * (8u * C);
-        if (blk < full) { const uint32_t xcd = blk & 7u, i = blk >> 3; blk = ((i / C) * 8u + xcd) * C + (i % C); }
-    }
-    const uint32_t local_tile = blk >> 2, quad = blk & 3u;
-    const uint32_t pix = lane >> 2, sub = lane & 3u;
-    const bool tile_ok = local_tile < F.tile_end;
-    const uint32_t tx = P.tile_x0 + (tile_ok ? local_tile % P.tiles_w : 0), ty = P.tile_y0 + (tile_ok ? local_tile / P.tiles_w : 0);
-    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
-    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
-    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
-    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;   // col_end <= width, row_end <= height
-    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;   // the pixels the reference traces (render_kernel)
-    const int32_t x = (int32_t)px - W / 2;
-    const int32_t y = (H - H / 2) - (int32_t)py;
-    const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;                      // engine.rs:207-236
-    const double yd = (sub & 2u) ? ((double)y + 0.5) : (double)y;
-    const double sa = xd * F.x_scale, sb = yd * F.y_scale, sc = F.z_value;             // (right*a + up*b) + forward*c, five operations per component: rrt.h, rrt_camera
-    const V3 o = ld3(S.origin), d = mk((F.right[0] * sa + F.up[0] * sb) + F.forward[0] * sc,
-                                       (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
-                                       (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
+    const RegionLane L = region_lane(P, lane);
+    const uint32_t sub = L.sub;
+    const bool in_region = L.in_region, traced = L.traced;
+    const V3 o = ld3(S.origin), d = primary_direction(P.F, L.px, L.py, sub);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
@@ -1773,39 +1811,13 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevSce
             shadow = true;
             found = traced && wslot != kNone;
             if (found) {
-                // --- hit: raytracer.rs:39-57, as trace_colour
+                // --- hit: raytracer.rs:39-57
                 double t2;
                 mt_full(S.geom + wslot, o, d, t2, u, v);
-                const DevTriAttr& A = S.attr[wslot];
                 t = wt;
-                tri = A.orig;
+                tri = S.attr[wslot].orig;
                 p = o + d * wt;                                                          // raytracer.rs:39
-                mat = A.mat;
-                const DevMaterial& M = S.mats[mat];
-                const DevTexture T = M.tex_desc;
-                const double w = 1.0 - u - v;                                            // raytracer.rs:43
-                const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;            // raytracer.rs:45-47
-                const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;            // raytracer.rs:48-50
-                const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);    // raytracer.rs:52
-                const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);  // raytracer.rs:53
-                const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);      // raytracer.rs:55
-                col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
-                // get_normal_at_intersection, raytracer.rs:114-162
-                V3 nn = (ld3(A.nrm + 3) * u + ld3(A.nrm + 6) * v) + ld3(A.nrm) * w;      // raytracer.rs:122-124
-                if (M.bump >= 0) {
-                    const DevTexture B = M.bump_desc;
-                    const uint8_t* bp = B.rgb + 3ull * ((uint64_t)B.width * tyi + txi);  // raytracer.rs:127-128 (colour-texture indices, bump width)
-                    V3 bv = mk((double)bp[0], (double)bp[1], (double)bp[2]);
-                    bv = normalised(bv);
-                    bv = (bv * 2.0) - mk(1.0, 1.0, 1.0);                                 // raytracer.rs:130-135
-                    V3 tg = cross(nn, mk(0.0, 1.0, 0.0));                                // raytracer.rs:137-141
-                    double len_tg = length(tg);
-                    if (len_tg == 0.0) { tg = cross(nn, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }   // raytracer.rs:143-149
-                    tg = div3(tg, len_tg);                                               // raytracer.rs:151
-                    const V3 bt = normalised(cross(nn, tg));                             // raytracer.rs:152
-                    nn = mk(dot(bv, tg), dot(bv, bt), dot(bv, nn));                      // raytracer.rs:154-158
-                }
-                n = normalised(nn);                                                      // raytracer.rs:161
+                surface_of_hit(S, wslot, u, v, mat, col, n);
             }
             if (!__any(found)) break;                                                    // no hit in the wave: nothing to ask the lights
         } else {
@@ -1821,7 +1833,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevSce
         rmax = length(dir);
     }
     if (!in_region) return;
-    const size_t i = (((size_t)(py - F.row_begin) * (P.col_end - P.col_begin)) + (px - P.col_begin)) * 4 + sub;
+    const size_t i = region_pixel(P, L) * 4 + sub;
     if (Q.point) { Q.point[3 * i] = p.x; Q.point[3 * i + 1] = p.y; Q.point[3 * i + 2] = p.z; }
     if (Q.normal) { Q.normal[3 * i] = n.x; Q.normal[3 * i + 1] = n.y; Q.normal[3 * i + 2] = n.z; }
     if (Q.material) Q.material[i] = mat;
@@ -1851,36 +1863,14 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
     const uint32_t lane = threadIdx.x;
     const Stack stk{lds + kParkBytes, lane};
     const VisParams& P = Q.V;
-    const FrameParams& F = P.F;
-    // Block order, tile quadrant, pixel, sub-sample and direction: surface_kernel's, restated (see visibility_kernel)
-    uint32_t blk = blockIdx.x;
-    if (F.xcd_chunk) {
-        const uint32_t C = F.xcd_chunk, full = (gridDim.x / (8u * C)) * (8u * C);
-        if (blk < full) { const uint32_t xcd = blk & 7u, i = blk >> 3; blk = ((i / C) * 8u + xcd) * C + (i % C); }
-    }
-    const uint32_t local_tile = blk >> 2, quad = blk & 3u;
-    const uint32_t pix = lane >> 2, sub = lane & 3u;
-    const bool tile_ok = local_tile < F.tile_end;
-    const uint32_t tx = P.tile_x0 + (tile_ok ? local_tile % P.tiles_w : 0), ty = P.tile_y0 + (tile_ok ? local_tile / P.tiles_w : 0);
-    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
-    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
-    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
-    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;   // col_end <= width, row_end <= height
-    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;   // the pixels the reference traces (render_kernel)
-    const int32_t x = (int32_t)px - W / 2;
-    const int32_t y = (H - H / 2) - (int32_t)py;
-    const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;                      // engine.rs:207-236
-    const double yd = (sub & 2u) ? ((double)y + 0.5) : (double)y;
-    const double sa = xd * F.x_scale, sb = yd * F.y_scale, sc = F.z_value;             // (right*a + up*b) + forward*c, five operations per component: rrt.h, rrt_camera
-    V3 seg_d = mk((F.right[0] * sa + F.up[0] * sb) + F.forward[0] * sc,
-                  (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
-                  (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
+    const RegionLane L = region_lane(P, lane);
+    const uint32_t sub = L.sub;
+    const bool in_region = L.in_region, traced = L.traced;
+    V3 seg_d = primary_direction(P.F, L.px, L.py, sub);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    // (pixel index inside the region; the element index of a sub-sample is 4 * that + sub.  Only lanes inside the region use either.)
-    const size_t pixel_i = ((size_t)(py - F.row_begin) * (P.col_end - P.col_begin)) + (px - P.col_begin);
-    const size_t i = pixel_i * 4 + sub;
+    const size_t pixel_i = region_pixel(P, L), i = pixel_i * 4 + sub;
     // ---- the five values: the primary segment's hit
     bool live = false;                      // the lane holds a hit whose colour is not known yet
     V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
@@ -1964,38 +1954,12 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
                 if (!found) {
                     term = 0x00FFFFFFu; live = false;                                // WHITE, raytracer.rs:109-111
                 } else {
-                    // --- hit: raytracer.rs:39-57, as trace_colour
+                    // --- hit: raytracer.rs:39-57
                     double u = 0, v = 0, t2;
                     mt_full(S.geom + slot, ro, rd, t2, u, v);
-                    const DevTriAttr& A = S.attr[slot];
                     seg_d = rd;
                     p = ro + rd * t;                                                 // raytracer.rs:39
-                    mat = A.mat;
-                    const DevMaterial& M = S.mats[mat];
-                    const DevTexture T = M.tex_desc;
-                    const double w = 1.0 - u - v;                                    // raytracer.rs:43
-                    const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;    // raytracer.rs:45-47
-                    const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;    // raytracer.rs:48-50
-                    const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);    // raytracer.rs:52
-                    const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);  // raytracer.rs:53
-                    const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);           // raytracer.rs:55
-                    col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
-                    // get_normal_at_intersection, raytracer.rs:114-162
-                    V3 nn = (ld3(A.nrm + 3) * u + ld3(A.nrm + 6) * v) + ld3(A.nrm) * w;           // raytracer.rs:122-124
-                    if (M.bump >= 0) {
-                        const DevTexture B = M.bump_desc;
-                        const uint8_t* bp = B.rgb + 3ull * ((uint64_t)B.width * tyi + txi);       // raytracer.rs:127-128 (colour-texture indices, bump width)
-                        V3 bv = mk((double)bp[0], (double)bp[1], (double)bp[2]);
-                        bv = normalised(bv);
-                        bv = (bv * 2.0) - mk(1.0, 1.0, 1.0);                         // raytracer.rs:130-135
-                        V3 tg = cross(nn, mk(0.0, 1.0, 0.0));                        // raytracer.rs:137-141
-                        double len_tg = length(tg);
-                        if (len_tg == 0.0) { tg = cross(nn, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }   // raytracer.rs:143-149
-                        tg = div3(tg, len_tg);                                       // raytracer.rs:151
-                        const V3 bt = normalised(cross(nn, tg));                     // raytracer.rs:152
-                        nn = mk(dot(bv, tg), dot(bv, bt), dot(bv, nn));              // raytracer.rs:154-158
-                    }
-                    n = normalised(nn);                                              // raytracer.rs:161
+                    surface_of_hit(S, slot, u, v, mat, col, n);
                     li = 0;                                                          // compute_lighting_intensity, raytracer.rs:199-203
                 }
             } else {
@@ -2038,28 +2002,13 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevSce
     const uint32_t lane = threadIdx.x;
     const Stack stk{lds + kParkBytes, lane};
     const VisParams& P = Q.V;
-    const FrameParams& F = P.F;
-    // Block order, tile quadrant, pixel and sub-sample: shade_kernel's, restated (see visibility_kernel); no direction is formed from the pixel here
-    uint32_t blk = blockIdx.x;
-    if (F.xcd_chunk) {
-        const uint32_t C = F.xcd_chunk, full = (gridDim.x / (8u * C)) * (8u * C);
-        if (blk < full) { const uint32_t xcd = blk & 7u, i = blk >> 3; blk = ((i / C) * 8u + xcd) * C + (i % C); }
-    }
-    const uint32_t local_tile = blk >> 2, quad = blk & 3u;
-    const uint32_t pix = lane >> 2, sub = lane & 3u;
-    const bool tile_ok = local_tile < F.tile_end;
-    const uint32_t tx = P.tile_x0 + (tile_ok ? local_tile % P.tiles_w : 0), ty = P.tile_y0 + (tile_ok ? local_tile / P.tiles_w : 0);
-    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
-    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
-    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
-    const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;   // col_end <= width, row_end <= height
-    const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;   // the pixels the reference traces (render_kernel)
+    const RegionLane L = region_lane(P, lane);                                           // (no direction is formed from the pixel here)
+    const uint32_t sub = L.sub;
+    const bool in_region = L.in_region, traced = L.traced;
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    // (pixel index inside the region; the element index of a sub-sample is 4 * that + sub.  Only lanes inside the region use either.)
-    const size_t pixel_i = ((size_t)(py - F.row_begin) * (P.col_end - P.col_begin)) + (px - P.col_begin);
-    const size_t i = pixel_i * 4 + sub;
+    const size_t pixel_i = region_pixel(P, L), i = pixel_i * 4 + sub;
     // ---- the lane's hit
     bool hit = false;
     V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
@@ -2070,15 +2019,9 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevSce
     const uint32_t n_samples = Q.n_samples;
     uint32_t mask = 0;
     if (__any(hit)) {
-        // the tangent frame of the hit, raytracer.rs:137-152, once for all samples
+        // the tangent frame of the hit, once for all samples
         V3 tg = mk(0, 0, 0), bt = mk(0, 0, 0);
-        if (hit) {
-            tg = cross(n, mk(0.0, 1.0, 0.0));                                            // raytracer.rs:137-141
-            double len_tg = length(tg);
-            if (len_tg == 0.0) { tg = cross(n, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }   // raytracer.rs:143-149
-            tg = div3(tg, len_tg);                                                       // raytracer.rs:151
-            bt = normalised(cross(n, tg));                                               // raytracer.rs:152
-        }
+        if (hit) tangent_frame(n, tg, bt);
         const V3 ro = p + n * S.surface_offset;                                          // the origin of a shadow ray, raytracer.rs:170
         for (uint32_t k = 0; k < n_samples; k++) {
             const double sx = Q.dirs[k][0], sy = Q.dirs[k][1], sz = Q.dirs[k][2];        // wave-uniform
@@ -2100,6 +2043,11 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevSce
     if (Q.grey && sub == 0) Q.grey[pixel_i] = traced ? ((510u * open + 4u * n_samples) / (8u * n_samples)) * 0x010101u : 0u;
 }
 
+// For the region launchers below: the kernel that takes a parameter type (device_scene.hpp: VisParams, SurfaceParams, ShadeParams, AmbientParams).
+template <int kWalk, bool kGroups> auto region_kernel(const VisParams&) { return &visibility_kernel<kWalk, kGroups>; }
+template <int kWalk, bool kGroups> auto region_kernel(const SurfaceParams&) { return &surface_kernel<kWalk, kGroups>; }
+template <int kWalk, bool kGroups> auto region_kernel(const ShadeParams&) { return &shade_kernel<kWalk, kGroups>; }
+template <int kWalk, bool kGroups> auto region_kernel(const AmbientParams&) { return &ambient_kernel<kWalk, kGroups>; }
 #endif   // RRT_TU_FRAME || RRT_TU_LANE
 #if RRT_TU_FRAME
 __global__ __launch_bounds__(256) void detile_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t world, uint32_t tiles_per_rank,
@@ -2217,6 +2165,7 @@ inline int effective_walk(const DevScene& s, int walk) { return (walk == kWalkBu
 // while the host is still parsing the scene (api.cpp, warm_device_async).
 void preload_kernels_lane_ray();
 int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+template <class Params> int launch_region_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
 void preload_kernels() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_kernel<kWalkBundle, false>));
@@ -2279,61 +2228,26 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
     });
 }
 
-// The visibility planes of a region of a frame (device_scene.hpp: VisParams), one block per quadrant of the tiles the region touches.
-int launch_visibility_lane_ray(const DevScene& s, const VisParams& p, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
-int launch_visibility(const DevScene& s, const VisParams& p, void* stream, int walk) {
+// (the region inside a parameter type)
+inline const VisParams& region_of(const VisParams& p) { return p; }
+template <class Params> const VisParams& region_of(const Params& q) { return q.V; }
+// One region launch: one block per quadrant of the tiles the region touches.  This unit instantiates the bundle-filter kernels only; the other walks go to the
+// lane unit's launch_region_lane_ray.
+template <class Params> int launch_region(const DevScene& s, const Params& q, void* stream, int walk) {
     walk = effective_walk(s, walk);
-    const uint32_t n_tiles = p.F.tile_end;
+    const uint32_t n_tiles = region_of(q).F.tile_end;
     if (n_tiles == 0) return 0;
     const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk != kWalkBundle) return launch_visibility_lane_ray(s, p, stream, walk, n_tiles * 4, lds);
+    if (walk != kWalkBundle) return launch_region_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
     return with_groups(s, [&](auto groups) {
-        hipLaunchKernelGGL((visibility_kernel<kWalkBundle, groups()>), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, p);
+        hipLaunchKernelGGL((region_kernel<kWalkBundle, groups()>(q)), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
         return (int)hipGetLastError();
     });
 }
-
-// The surface planes of a region of a frame (device_scene.hpp: SurfaceParams): the grid of launch_visibility.
-int launch_surface_lane_ray(const DevScene& s, const SurfaceParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
-int launch_surface(const DevScene& s, const SurfaceParams& q, void* stream, int walk) {
-    walk = effective_walk(s, walk);
-    const uint32_t n_tiles = q.V.F.tile_end;
-    if (n_tiles == 0) return 0;
-    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk != kWalkBundle) return launch_surface_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
-    return with_groups(s, [&](auto groups) {
-        hipLaunchKernelGGL((surface_kernel<kWalkBundle, groups()>), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
-        return (int)hipGetLastError();
-    });
-}
-
-// The pixels of a region of a frame from its kept planes (device_scene.hpp: ShadeParams): the grid of launch_surface.
-int launch_shade_lane_ray(const DevScene& s, const ShadeParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
-int launch_shade(const DevScene& s, const ShadeParams& q, void* stream, int walk) {
-    walk = effective_walk(s, walk);
-    const uint32_t n_tiles = q.V.F.tile_end;
-    if (n_tiles == 0) return 0;
-    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk != kWalkBundle) return launch_shade_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
-    return with_groups(s, [&](auto groups) {
-        hipLaunchKernelGGL((shade_kernel<kWalkBundle, groups()>), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
-        return (int)hipGetLastError();
-    });
-}
-
-// The occlusion masks and grey pixels of a region of a frame from its kept planes (device_scene.hpp: AmbientParams): the grid of launch_shade.
-int launch_ambient_lane_ray(const DevScene& s, const AmbientParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
-int launch_ambient(const DevScene& s, const AmbientParams& q, void* stream, int walk) {
-    walk = effective_walk(s, walk);
-    const uint32_t n_tiles = q.V.F.tile_end;
-    if (n_tiles == 0) return 0;
-    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk != kWalkBundle) return launch_ambient_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
-    return with_groups(s, [&](auto groups) {
-        hipLaunchKernelGGL((ambient_kernel<kWalkBundle, groups()>), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
-        return (int)hipGetLastError();
-    });
-}
+template int launch_region(const DevScene&, const VisParams&, void*, int);
+template int launch_region(const DevScene&, const SurfaceParams&, void*, int);
+template int launch_region(const DevScene&, const ShadeParams&, void*, int);
+template int launch_region(const DevScene&, const AmbientParams&, void*, int);
 
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
     const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
@@ -2361,38 +2275,18 @@ int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_
         });
     });
 }
-int launch_visibility_lane_ray(const DevScene& s, const VisParams& p, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+template <class Params> int launch_region_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
     return with_lane_or_ray_walk(walk, [&](auto w) {
         return with_groups(s, [&](auto groups) {
-            hipLaunchKernelGGL((visibility_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, p);
+            hipLaunchKernelGGL((region_kernel<w(), groups()>(q)), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
             return (int)hipGetLastError();
         });
     });
 }
-int launch_surface_lane_ray(const DevScene& s, const SurfaceParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
-    return with_lane_or_ray_walk(walk, [&](auto w) {
-        return with_groups(s, [&](auto groups) {
-            hipLaunchKernelGGL((surface_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
-            return (int)hipGetLastError();
-        });
-    });
-}
-int launch_shade_lane_ray(const DevScene& s, const ShadeParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
-    return with_lane_or_ray_walk(walk, [&](auto w) {
-        return with_groups(s, [&](auto groups) {
-            hipLaunchKernelGGL((shade_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
-            return (int)hipGetLastError();
-        });
-    });
-}
-int launch_ambient_lane_ray(const DevScene& s, const AmbientParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
-    return with_lane_or_ray_walk(walk, [&](auto w) {
-        return with_groups(s, [&](auto groups) {
-            hipLaunchKernelGGL((ambient_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
-            return (int)hipGetLastError();
-        });
-    });
-}
+template int launch_region_lane_ray(const DevScene&, const VisParams&, void*, int, uint32_t, uint32_t);
+template int launch_region_lane_ray(const DevScene&, const SurfaceParams&, void*, int, uint32_t, uint32_t);
+template int launch_region_lane_ray(const DevScene&, const ShadeParams&, void*, int, uint32_t, uint32_t);
+template int launch_region_lane_ray(const DevScene&, const AmbientParams&, void*, int, uint32_t, uint32_t);
 #endif   // RRT_TU_LANE
 
 #if RRT_TU_RAYS

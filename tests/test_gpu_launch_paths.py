@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from ambient_checks import T8, T8_MAX_T
 from conftest import ASSETS
 from gpu_checks import traced_rows
 
@@ -62,7 +63,19 @@ def device_planes(torch, rrt, w, h, names=None):
 
 def planes_to_host(torch, rrt, tensors):
     torch.cuda.synchronize()
-    return {n: t.cpu().numpy().view(rrt.PLANE_DTYPES[n]) for n, t in tensors.items()}
+    return {n: t.cpu().numpy().view(rrt.SURFACE_DTYPES.get(n) or rrt.PLANE_DTYPES[n]) for n, t in tensors.items()}
+
+
+def device_surface_planes(torch, rrt, w, h, visibility=()):
+    """The four surface planes, and the visibility planes named, as surface_into takes them."""
+    out = {n: torch.empty((h, w, 4, 3) if rrt.SURFACE_WIDTHS[n] == 3 else (h, w, 4), dtype=torch.float64 if rrt.SURFACE_WIDTHS[n] == 3 else torch.int32, device="cuda")
+           for n in rrt.SURFACE_PLANES}
+    out.update(device_planes(torch, rrt, w, h, visibility))
+    return out
+
+
+def device_ambient_outputs(torch, w, h):
+    return dict(occluded=torch.empty((h, w, 4), dtype=torch.int32, device="cuda"), grey=torch.empty((h, w), dtype=torch.int32, device="cuda"))
 
 
 # ------------------------------------------------------------------ 1
@@ -82,6 +95,12 @@ def test_every_entry_point_records_its_launch(rrt, torch, model):
     col = torch.empty(N_RAYS, dtype=torch.int32, device="cuda")
     px, py = 12, 9
     assert traced_pixels_in((px, py, 1, 1), W, H) == 1 and traced_pixels_in((0, 0, 1, 1), W, H) == 0
+    region_rays = 4 * traced_pixels_in(REGION, W, H)
+    rw, rh = REGION[2:]
+    vis_t, vis_rt = device_planes(torch, rrt, W, H), device_planes(torch, rrt, rw, rh)
+    surf_t, amb_t = device_surface_planes(torch, rrt, W, H, ("albedo",)), device_ambient_outputs(torch, W, H)
+    kept = rt.surface(W, H, visibility=("albedo",))                  # the planes the host forms of shade and ambient read
+    kept_r = rt.surface(W, H, region=REGION, visibility=("albedo",))
     table = [
         ("render", lambda: rt.render(W, H), (W, H), frame_rays),
         ("render_into", lambda: rt.render_into(fb, W, H), (W, H), frame_rays),
@@ -92,6 +111,17 @@ def test_every_entry_point_records_its_launch(rrt, torch, model):
         ("visibility of a region", lambda: rt.visibility(W, H, region=REGION), (W, H), 4 * traced_pixels_in(REGION, W, H)),
         ("pick of a traced pixel", lambda: rt.pick(W, H, px, py), (W, H), 4),
         ("pick of pixel (0, 0)", lambda: rt.pick(W, H, 0, 0), (W, H), 0),
+        ("visibility_into", lambda: rt.visibility_into(vis_t, W, H), (W, H), frame_rays),
+        ("visibility_into of a region", lambda: rt.visibility_into(vis_rt, W, H, region=REGION), (W, H), region_rays),
+        ("surface", lambda: rt.surface(W, H), (W, H), frame_rays),
+        ("surface of a region", lambda: rt.surface(W, H, region=REGION), (W, H), region_rays),
+        ("surface_into", lambda: rt.surface_into(surf_t, W, H), (W, H), frame_rays),
+        ("shade", lambda: rt.shade(W, H, kept), (W, H), frame_rays),
+        ("shade of a region", lambda: rt.shade(W, H, kept_r, region=REGION), (W, H), region_rays),
+        ("shade_into", lambda: rt.shade_into(fb, surf_t, W, H), (W, H), frame_rays),      # (surf_t: filled by the surface_into row)
+        ("ambient", lambda: rt.ambient(W, H, kept, T8, T8_MAX_T), (W, H), frame_rays),
+        ("ambient of a region", lambda: rt.ambient(W, H, kept_r, T8, T8_MAX_T, region=REGION), (W, H), region_rays),
+        ("ambient_into", lambda: rt.ambient_into(amb_t, surf_t, T8, T8_MAX_T, W, H), (W, H), frame_rays),
         ("get_ray_colours", lambda: rt.get_ray_colours(o, d), (N_RAYS, 1), N_RAYS),
         ("intersect_rays", lambda: rt.intersect_rays(o, d), (N_RAYS, 1), N_RAYS),
         ("occluded", lambda: rt.occluded(o, d), (N_RAYS, 1), N_RAYS),
@@ -99,7 +129,7 @@ def test_every_entry_point_records_its_launch(rrt, torch, model):
         ("intersect_rays_into", lambda: rt.intersect_rays_into(to, td, five), (N_RAYS, 1), N_RAYS),
         ("occluded_into", lambda: rt.occluded_into(to, td, occ), (N_RAYS, 1), N_RAYS),
     ]
-    assert 0 < 4 * traced_pixels_in(REGION, W, H) < frame_rays
+    assert 0 < region_rays < frame_rays
     for what, call, size, rays in table:
         call()
         torch.cuda.synchronize()
@@ -130,22 +160,48 @@ def test_the_kept_framebuffer_grows_and_is_reused(rrt, model, fresh_frames):
 
 
 def test_the_kept_planes_grow_and_are_reused(rrt, torch, model):
+    """ONE raytracer (`host`) runs the host forms of all five users of the kept allocation in turn, so that it grows, is used in part and changes its layout
+    between calls; every result against the device form of the same call on another raytracer (`rt`), which never touches a kept allocation."""
     rt = rrt.RayTracer(model, rrt.default_lights())
     tensors = device_planes(torch, rrt, W2, H2)
     rt.visibility_into(tensors, W2, H2)
     full = planes_to_host(torch, rrt, tensors)
     assert full["hit"].any(), "an empty frame proves nothing"
     x0, y0, w, h = REGION
+    crop = lambda planes: {n: np.ascontiguousarray(a[y0:y0 + h, x0:x0 + w]) for n, a in planes.items()}
     host = rrt.RayTracer(model, rrt.default_lights())
-    assert_same_planes(host.visibility(W2, H2, region=REGION), {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, "a small region first")
+    assert_same_planes(host.visibility(W2, H2, region=REGION), crop(full), "a small region first")
     assert_same_planes(host.visibility(W2, H2), full, "then the whole frame")
+    # surface of the whole frame, all ten planes: the largest layout
+    surf_t = device_surface_planes(torch, rrt, W2, H2, rrt.PLANES)
+    rt.surface_into(surf_t, W2, H2)
+    surf = planes_to_host(torch, rrt, surf_t)
+    assert_same_planes({n: surf[n] for n in rrt.PLANES}, full, "the visibility planes of the surface launch")
+    assert (surf["lights"] != 0).any() and (surf["material"] != 0xFFFFFFFF).any(), "an empty frame proves nothing"
+    assert_same_planes(host.surface(W2, H2, visibility=rrt.PLANES), surf, "all ten planes of the whole frame")
     ys, xs = np.nonzero(full["hit"][:, :, 0])
     px, py = int(xs[0]), int(ys[0])
     got = host.pick(W2, H2, px, py)
     assert got["hit"] and got["tri"] == full["tri"][py, px, 0] and got["albedo"] == full["albedo"][py, px, 0], got
     assert all(bits(np.float64(got[n])) == bits(full[n][py, px, 0]) for n in "tuv"), got
+    # shade of the region from those planes: five inputs up, a framebuffer down
+    kept_r = crop(surf)
+    kept_rt = {n: torch.tensor(a.view(np.int32) if a.dtype == np.uint32 else a, device="cuda") for n, a in kept_r.items()}
+    fb_t = torch.empty((h, w), dtype=torch.int32, device="cuda")
+    rt.shade_into(fb_t, kept_rt, W2, H2, region=REGION)
+    torch.cuda.synchronize()
+    fb = fb_t.cpu().numpy().view(np.uint32)
+    assert (fb != 0).any() and (fb != 0x00FFFFFF).any(), "an empty region proves nothing"
+    assert_same_planes(dict(fb=host.shade(W2, H2, kept_r, region=REGION)), dict(fb=fb), "shade of the region after the pick")
+    # ambient occlusion of the whole frame, both outputs: three inputs up, two outputs of different sizes down
+    amb_t = device_ambient_outputs(torch, W2, H2)
+    rt.ambient_into(amb_t, surf_t, T8, T8_MAX_T, W2, H2)
+    torch.cuda.synchronize()
+    amb = {n: t.cpu().numpy().view(np.uint32) for n, t in amb_t.items()}
+    assert (amb["occluded"] != 0).any() and (amb["grey"] != 0).any(), "an empty frame proves nothing"
+    assert_same_planes(host.ambient(W2, H2, surf, T8, T8_MAX_T), amb, "ambient occlusion of the whole frame")
     assert_same_planes(host.visibility(W2, H2, region=REGION, planes=("t", "tri")),
-                       {n: full[n][y0:y0 + h, x0:x0 + w] for n in ("t", "tri")}, "a small region after the pick")
+                       {n: full[n][y0:y0 + h, x0:x0 + w] for n in ("t", "tri")}, "a small region after the rest")
 
 
 def test_tune_rays_below_and_above_the_sample(rrt, torch, model):
