@@ -77,17 +77,8 @@ class CPickResult(C.Structure):      # rrt_pick_result, 40 bytes
     _fields_ = [("hit", C.c_uint32), ("tri", C.c_uint32), ("t", C.c_double), ("u", C.c_double), ("v", C.c_double), ("albedo", C.c_uint32), ("_pad", C.c_uint32)]
 
 
-PLANES = ("hit", "t", "u", "v", "tri", "albedo")   # the planes of rrt_visibility, in its order
-PLANE_DTYPES = dict(hit=np.uint8, t=np.float64, u=np.float64, v=np.float64, tri=np.uint32, albedo=np.uint32)
-
-
 class CSurface(C.Structure):         # rrt_surface, 32 bytes: host or device pointers, NULL = plane not wanted
     _fields_ = [(n, C.c_void_p) for n in ("point", "normal", "material", "lights")]
-
-
-SURFACE_PLANES = ("point", "normal", "material", "lights")   # the planes of rrt_surface, in its order
-SURFACE_DTYPES = dict(point=np.float64, normal=np.float64, material=np.uint32, lights=np.uint32)
-SURFACE_WIDTHS = dict(point=3, normal=3, material=1, lights=1)   # elements per sub-sample
 
 
 class CAmbientSamples(C.Structure):  # rrt_ambient_samples, 24 bytes: dirs = n x 3 host doubles in the tangent frame of a hit
@@ -99,7 +90,24 @@ class CAmbient(C.Structure):         # rrt_ambient, 16 bytes: host or device poi
 
 
 MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
-AMBIENT_OUTPUTS = ("occluded", "grey")   # the planes of rrt_ambient, in its order: [h][w][4] masks, [h][w] pixels, both uint32
+
+# The plane table: every plane of rrt_visibility, rrt_surface and rrt_ambient, in the struct's order, as (dtype, elements per sub-sample, True = one value per
+# sub-sample, [h][w][4](...), False = one per pixel, [h][w]).  Everything else the binding knows about a plane is derived from it.
+_PLANES_OF = {
+    CVisibility: dict(hit=(np.uint8, 1, True), t=(np.float64, 1, True), u=(np.float64, 1, True), v=(np.float64, 1, True), tri=(np.uint32, 1, True),
+                      albedo=(np.uint32, 1, True)),
+    CSurface: dict(point=(np.float64, 3, True), normal=(np.float64, 3, True), material=(np.uint32, 1, True), lights=(np.uint32, 1, True)),
+    CAmbient: dict(occluded=(np.uint32, 1, True), grey=(np.uint32, 1, False)),
+}
+PLANE_TABLE = {n: row for rows in _PLANES_OF.values() for n, row in rows.items()}
+PLANES = tuple(_PLANES_OF[CVisibility])                                       # the planes of rrt_visibility, in its order
+PLANE_DTYPES = {n: row[0] for n, row in _PLANES_OF[CVisibility].items()}
+SURFACE_PLANES = tuple(_PLANES_OF[CSurface])                                  # the planes of rrt_surface, in its order
+SURFACE_DTYPES = {n: row[0] for n, row in _PLANES_OF[CSurface].items()}
+SURFACE_WIDTHS = {n: row[1] for n, row in _PLANES_OF[CSurface].items()}       # elements per sub-sample
+AMBIENT_OUTPUTS = tuple(_PLANES_OF[CAmbient])                                 # the planes of rrt_ambient, in its order: [h][w][4] masks, [h][w] pixels
+SHADE_INPUTS = SURFACE_PLANES + ("albedo",)                                   # what rrt_shade_surface reads (lights optional)
+AMBIENT_INPUTS = SURFACE_PLANES[:3]                                           # what rrt_ambient_surface reads
 
 
 class CModelInfo(C.Structure):
@@ -115,6 +123,11 @@ class CStats(C.Structure):
 class CSetupTimes(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("read_ms", "parse_ms", "texture_ms", "octree_ms", "index_ms", "upload_ms", "hip_init_ms", "create_ms", "gpu_setup")]
 
+
+# every struct of include/rrt.h and the class that mirrors it (tests/test_abi.py compares sizes and offsets with what the header's compiler gives)
+STRUCTS = {"rrt_vec3": Vec3, "rrt_light": CLight, "rrt_material": CMaterial, "rrt_texture": CTexture, "rrt_options": COptions, "rrt_camera": CCamera,
+           "rrt_region": CRegion, "rrt_visibility": CVisibility, "rrt_pick_result": CPickResult, "rrt_surface": CSurface,
+           "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
 
 # every symbol include/rrt.h declares: (restype, argtypes)
 _P = C.c_void_p
@@ -220,14 +233,233 @@ def _check(status: int, what: str):
         raise RrtError(status, f"{what} failed [{L.rrt_strerror(status).decode()}]", detail)
 
 
-def _d(a: np.ndarray):
-    return a.ctypes.data_as(_dp)
+def _call(name: str, *args) -> None:
+    """One library call by its entry point's name; a status other than RRT_OK raises RrtError naming it."""
+    _check(getattr(lib(), name)(*args), name)
 
 
 def device_count() -> int:
     n = C.c_int(0)
-    _check(lib().rrt_device_count(C.byref(n)), "rrt_device_count")
+    _call("rrt_device_count", C.byref(n))
     return n.value
+
+
+def tiles_per_rank(width: int, height: int, world: int) -> int:
+    return int(lib().rrt_tiles_per_rank(width, height, world))
+
+
+# ---------------------------------------------------------------------------------------------- marshalling: one helper per kind of argument
+def _host_pointer(ptype):
+    """array -> the pointer of this type the library reads or fills (None = NULL)"""
+    return lambda a: None if a is None else a.ctypes.data_as(ptype)
+
+
+_d, _u32, _u8 = _host_pointer(_dp), _host_pointer(_u32p), _host_pointer(_u8p)
+
+
+def _ptr(t):
+    """A device tensor as the void* the library gets (None = NULL)."""
+    return None if t is None else _P(t.data_ptr())
+
+
+def _stream(stream: Optional[int]) -> int:
+    if stream is not None:
+        return stream
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _vec3(v) -> Vec3:
+    """A Vector3d or any three numbers."""
+    return v._c() if isinstance(v, Vector3d) else Vec3(*map(float, v))
+
+
+def _tuple3(v: Vec3) -> tuple:
+    return (v.x, v.y, v.z)
+
+
+def _struct_dict(s: C.Structure) -> dict:
+    return {n: getattr(s, n) for n, _ in s._fields_}
+
+
+def _camera_dict(c: CCamera) -> dict:
+    return {n: _tuple3(v) for n, v in _struct_dict(c).items()}
+
+
+def _root(root):
+    """A root box as six doubles (None = NULL: the default box, or the one in force)."""
+    return None if root is None else (C.c_double * 6)(*map(float, root))
+
+
+def _array(ctype, n: int):
+    """n elements of `ctype`, zeroed; at least one, so that an empty list still has an address."""
+    return (ctype * max(1, n))()
+
+
+def _c_lights(lights: Iterable["Light"]):
+    """(rrt_light array of at least one element, the number of lights)"""
+    lights = list(lights)
+    cl = _array(CLight, len(lights))
+    for i, l in enumerate(lights):
+        cl[i] = CLight(l.kind, 0, float(l.intensity), l.v._c())
+    return cl, len(lights)
+
+
+def _c_materials(materials: Sequence[dict]):
+    """(rrt_material array of at least one element, the number of materials); dicts ka, kd, ks, ns, kr, tex and optionally bump (absent = -1, none)."""
+    materials = list(materials)
+    cm = _array(CMaterial, len(materials))
+    for i, m in enumerate(materials):
+        cm[i] = CMaterial(Vec3(*m["ka"]), Vec3(*m["kd"]), Vec3(*m["ks"]), float(m["ns"]), float(m["kr"]), int(m["tex"]), int(m.get("bump", -1)))
+    return cm, len(materials)
+
+
+def _material_dicts(cm, n: int) -> list:
+    return [dict(ka=_tuple3(m.ka), kd=_tuple3(m.kd), ks=_tuple3(m.ks), ns=m.ns, kr=m.kr, tex=m.tex, bump=m.bump) for m in cm[:n]]
+
+
+def _counted(name: str, handle, ctype):
+    """The getters that report a count: ask for it, then fill an array of that many `ctype` (at least one); returns (array, count)."""
+    n = C.c_uint32(0)
+    _call(name, handle, None, 0, C.byref(n))
+    arr = _array(ctype, n.value)
+    _call(name, handle, arr, n.value, C.byref(n))
+    return arr, n.value
+
+
+def _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut) -> COptions:
+    flags = ((FLAG_NO_CULL if no_cull else 0) | (FLAG_HOST_SETUP if host_setup else 0) | (0 if chain_shortcut else FLAG_NO_CHAIN_SHORTCUT)
+             | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter])
+    return COptions(surface_offset, max_reflection_depth, flags, *map(float, viewport))
+
+
+def _tri_arrays(pos, uv, nrm, mat):
+    """Triangles as the library reads them: pos / uv / nrm [n,9] float64, mat [n] uint32, all contiguous (no copy of an array that already is)."""
+    return (*(np.ascontiguousarray(a, np.float64).reshape(-1, 9) for a in (pos, uv, nrm)), np.ascontiguousarray(mat, np.uint32).reshape(-1))
+
+
+def _scene_args(pos, uv, nrm, mat, materials, textures, root):
+    """The ten scene arguments rrt_model_from_arrays and rrt_raytracer_create_from_arrays share, and the arrays they point into (to be kept until the call
+    returned).  No copies of arrays that are already contiguous float64 / uint32 / uint8."""
+    pos, uv, nrm, mat = _tri_arrays(pos, uv, nrm, mat)
+    cm, n_mats = _c_materials(materials)
+    keep = [np.ascontiguousarray(t, np.uint8) for t in textures]
+    ct = _array(CTexture, len(keep))
+    for i, t in enumerate(keep):
+        ct[i] = CTexture(_u8(t), t.shape[1], t.shape[0])
+    return (pos.shape[0], _d(pos), _d(uv), _d(nrm), _u32(mat), n_mats, cm, len(keep), ct, _root(root)), (pos, uv, nrm, mat, keep)
+
+
+def _octree_arrays(info: dict):
+    """(the dict both octree() methods return, its five arrays as the arguments of rrt_model_get_octree / rrt_raytracer_get_octree)"""
+    n = info["n_nodes"]
+    o = dict(aabb=np.empty((n, 6)), first_child=np.empty(n, np.uint32), tri_count=np.empty(n, np.uint32), own_off=np.empty(n + 1, np.uint32),
+             own_idx=np.empty(info["n_tris_in_tree"], np.uint32))
+    return dict(o, max_depth=info["max_depth"]), (_d(o["aabb"]), _u32(o["first_child"]), _u32(o["tri_count"]), _u32(o["own_off"]), _u32(o["own_idx"]))
+
+
+def _host_rays(origins, dirs, max_t=None):
+    """Host rays as the library reads them: origins and directions [n,3] float64, max_t None or n doubles (a scalar is broadcast)."""
+    o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3); d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+    assert o.shape == d.shape
+    mt = None if max_t is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_t, np.float64), (o.shape[0],)))
+    return o, d, mt
+
+
+def _device_tensor(t, n: int, itemsize: int, name: str):
+    """What every _into form asserts of a tensor before the library sees its pointer (a numpy array fails here, without a GPU)."""
+    assert getattr(t, "is_cuda", False), f"{name}: not a device tensor"
+    assert t.is_contiguous() and t.element_size() == itemsize and t.numel() == n, f"{name}: want {n} contiguous elements of {itemsize} bytes"
+
+
+def _batch_size(t, per: int, name: str) -> int:
+    """n of a device tensor that leads a batch with `per` elements for each of n items"""
+    assert getattr(t, "is_cuda", False), f"{name}: not a device tensor"
+    n, rem = divmod(t.numel(), per)
+    assert rem == 0, f"{name}: the element count is not a multiple of {per}"
+    return n
+
+
+def _ray_batch(origins_t, dirs_t, max_t_t) -> int:
+    """Checks a device-resident ray batch (float64 tensors: origins and directions of 3 n elements, max_t of n or None); returns n."""
+    n = _batch_size(origins_t, 3, "origins")
+    _device_tensor(origins_t, 3 * n, 8, "origins"); _device_tensor(dirs_t, 3 * n, 8, "dirs")
+    if max_t_t is not None:
+        _device_tensor(max_t_t, n, 8, "max_t")
+    return n
+
+
+def _ambient_samples(dirs, max_t):
+    """(the [n][3] float64 array, which must outlive the call, and the rrt_ambient_samples that points at it)"""
+    d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+    return d, CAmbientSamples(dirs=_d(d), n=len(d), max_t=float(max_t))
+
+
+def _region(width: int, height: int, region):
+    """region = (x0, y0, w, h) in canvas pixels, None = the frame: (rrt_region by reference or NULL, width, height of what the call covers)."""
+    if region is None:
+        return None, width, height
+    x0, y0, w, h = map(int, region)
+    return C.byref(CRegion(x0, y0, w, h)), w, h
+
+
+def _plane_shape(name: str, w: int, h: int) -> tuple:
+    _, width, per_sample = PLANE_TABLE[name]
+    return (h, w) + ((4,) if per_sample else ()) + ((width,) if width > 1 else ())
+
+
+def _alloc_planes(cls, names, w: int, h: int) -> dict:
+    """{plane: uninitialised host array of the table's shape and dtype for a w x h region}, for planes of the struct `cls`"""
+    return {n: np.empty(_plane_shape(n, w, h), _PLANES_OF[cls][n][0]) for n in names}
+
+
+def _host_planes(what: str, planes: dict, names, w: int, h: int) -> dict:
+    """The caller's host planes among `names` as contiguous arrays of the table's dtype; absent or None planes are left out (NULL for the library), a
+    wrong shape is a ValueError."""
+    keep = {}
+    for name in names:
+        if planes.get(name) is not None:
+            keep[name] = np.ascontiguousarray(planes[name], PLANE_TABLE[name][0])
+            if keep[name].shape != _plane_shape(name, w, h):
+                raise ValueError(f"{what}: plane {name} has shape {keep[name].shape}, want {_plane_shape(name, w, h)}")
+    return keep
+
+
+def _device_planes(tensors: dict, names, w: int, h: int) -> dict:
+    """The caller's device planes among `names`, each checked by _device_tensor against the table; absent or None planes are left out."""
+    keep = {}
+    for name in names:
+        if tensors.get(name) is not None:
+            _device_tensor(tensors[name], int(np.prod(_plane_shape(name, w, h))), np.dtype(PLANE_TABLE[name][0]).itemsize, name)
+            keep[name] = tensors[name]
+    return keep
+
+
+def _plane_struct(cls, planes: dict):
+    """The planes that belong to rrt_visibility / rrt_surface / rrt_ambient `cls`, host arrays or device tensors, by reference; the others stay NULL."""
+    return C.byref(cls(**{n: (a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()) for n, a in planes.items() if n in _PLANES_OF[cls]}))
+
+
+def _bound(name: str, *args):
+    """A launcher for per-frame loops: `args` were converted once, the callable is one library call and one comparison (bench.py)."""
+    fn = getattr(lib(), name)
+
+    def launch():
+        rc = fn(*args)
+        if rc != OK:
+            _check(rc, name)
+    return launch
+
+
+class _Handle:
+    """An object of the library behind self._h, destroyed once with the entry point named by _destroy (never after the library is gone)."""
+    _h = None
+    _destroy = ""
+
+    def __del__(self):
+        h, self._h = self._h, None
+        if h and _lib is not None:
+            getattr(_lib, self._destroy)(h)
 
 
 # ---------------------------------------------------------------------------------------------- reference-shaped host types
@@ -268,50 +500,20 @@ def default_lights() -> list:
 
 DEFAULT_ORIGIN = Vector3d(0.0, 2.0, -10.0)   # src/main.rs:62-66
 DEFAULT_ROOT = (-20.0, 20.0, -20.0, 20.0, -20.0, 20.0)   # src/file_management/utils.rs:145
-
-
-def _vec3(v) -> Vec3:
-    """A Vector3d or any three numbers."""
-    return v._c() if isinstance(v, Vector3d) else Vec3(*map(float, v))
-
-
-def _camera_dict(c: CCamera) -> dict:
-    return {n: (getattr(c, n).x, getattr(c, n).y, getattr(c, n).z) for n, _ in CCamera._fields_}
+SURFACE_OFFSET, MAX_REFLECTION_DEPTH, VIEWPORT = 0.0001, 5, (1.0, 1.0, 1.0)   # rrt_options' defaults: raytracer.rs:17, raytracer.rs:20, engine.rs:113-119
 
 
 def look_at(eye, target, up=(0.0, 1.0, 0.0)) -> dict:
     """rrt_camera_look_at (host only): the pose at `eye` looking at `target`, left-handed like the reference (x right, y up, z forward), as a dict
     eye / right / up / forward of 3-tuples -- RayTracer.set_camera(**look_at(...)) applies it."""
     c = CCamera()
-    _check(lib().rrt_camera_look_at(_vec3(eye), _vec3(target), _vec3(up), C.byref(c)), "rrt_camera_look_at")
+    _call("rrt_camera_look_at", _vec3(eye), _vec3(target), _vec3(up), C.byref(c))
     return _camera_dict(c)
 
 
-class _Arrays:
-    pass
-
-
-def _marshal_arrays(pos, uv, nrm, mat, materials, textures, root):
-    """ctypes views of a scene held in numpy arrays (no copies of arrays that are already contiguous float64 / uint32 / uint8)."""
-    a = _Arrays()
-    a.pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 9)
-    a.uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 9)
-    a.nrm = np.ascontiguousarray(nrm, np.float64).reshape(-1, 9)
-    a.mat = np.ascontiguousarray(mat, np.uint32)
-    a.n = a.pos.shape[0]
-    a.cm = (CMaterial * max(1, len(materials)))()
-    for i, m in enumerate(materials):
-        a.cm[i] = CMaterial(Vec3(*m["ka"]), Vec3(*m["kd"]), Vec3(*m["ks"]), float(m["ns"]), float(m["kr"]), int(m["tex"]), int(m.get("bump", -1)))
-    a.keep = [np.ascontiguousarray(t, np.uint8) for t in textures]
-    a.ct = (CTexture * max(1, len(a.keep)))()
-    for i, t in enumerate(a.keep):
-        a.ct[i] = CTexture(t.ctypes.data_as(_u8p), t.shape[1], t.shape[0])
-    a.r = (C.c_double * 6)(*root)
-    return a
-
-
-class SceneData:
+class SceneData(_Handle):
     """SceneData (scenedata.rs:5-13): triangles in push order + materials + decoded textures + the octree."""
+    _destroy = "rrt_model_destroy"
 
     def __init__(self, handle: int):
         self._h = _P(handle)
@@ -323,60 +525,49 @@ class SceneData:
         also where a too-deep tree (RRT_ERR_DEPTH) is reported on the host side."""
         if self._info is None:
             info = CModelInfo()
-            _check(lib().rrt_model_get_info(self._h, C.byref(info)), "rrt_model_get_info")
-            self._info = {n: getattr(info, n) for n, _ in CModelInfo._fields_}
+            _call("rrt_model_get_info", self._h, C.byref(info))
+            self._info = _struct_dict(info)
         return self._info
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.rrt_model_destroy(h)
 
     @staticmethod
     def from_arrays(pos, uv, nrm, mat, materials: Sequence[dict], textures: Sequence[np.ndarray], root=DEFAULT_ROOT) -> "SceneData":
         """pos/uv/nrm: [n,3,3] float64; mat: [n] uint32; materials: dicts ka,kd,ks,ns,kr,tex,bump; textures: [h,w,3] uint8."""
-        a = _marshal_arrays(pos, uv, nrm, mat, materials, textures, root)
+        scene, _keep = _scene_args(pos, uv, nrm, mat, materials, textures, root)
         out = _P()
-        _check(lib().rrt_model_from_arrays(a.n, _d(a.pos), _d(a.uv), _d(a.nrm), a.mat.ctypes.data_as(_u32p), len(materials), a.cm, len(a.keep), a.ct, a.r, C.byref(out)),
-               "rrt_model_from_arrays")
+        _call("rrt_model_from_arrays", *scene, C.byref(out))
         return SceneData(out.value)
 
     # --- accessors
     def triangles(self):
         n = self.info["n_tris"]
         pos, uv, nrm, mat = (np.empty((n, 3, 3)), np.empty((n, 3, 3)), np.empty((n, 3, 3)), np.empty(n, np.uint32))
-        _check(lib().rrt_model_get_triangles(self._h, _d(pos), _d(uv), _d(nrm), mat.ctypes.data_as(_u32p)), "rrt_model_get_triangles")
+        _call("rrt_model_get_triangles", self._h, _d(pos), _d(uv), _d(nrm), _u32(mat))
         return pos, uv, nrm, mat
 
     def materials(self) -> list:
         n = self.info["n_mats"]
-        cm = (CMaterial * max(1, n))()
-        _check(lib().rrt_model_get_materials(self._h, cm), "rrt_model_get_materials")
-        v = lambda a: (a.x, a.y, a.z)
-        return [dict(ka=v(m.ka), kd=v(m.kd), ks=v(m.ks), ns=m.ns, kr=m.kr, tex=m.tex, bump=m.bump) for m in cm[:n]]
+        cm = _array(CMaterial, n)
+        _call("rrt_model_get_materials", self._h, cm)
+        return _material_dicts(cm, n)
 
     def texture(self, i: int) -> np.ndarray:
         t = CTexture()
-        _check(lib().rrt_model_get_texture(self._h, i, C.byref(t)), "rrt_model_get_texture")
+        _call("rrt_model_get_texture", self._h, i, C.byref(t))
         return np.ctypeslib.as_array(t.rgb, shape=(t.height, t.width, 3)).copy()
 
     def textures(self) -> list:
         return [self.texture(i) for i in range(self.info["n_tex"])]
 
     def octree(self) -> dict:
-        n = self.info["n_nodes"]
-        aabb = np.empty((n, 6)); fc = np.empty(n, np.uint32); tc = np.empty(n, np.uint32); off = np.empty(n + 1, np.uint32)
-        idx = np.empty(self.info["n_tris_in_tree"], np.uint32)
-        u = lambda a: a.ctypes.data_as(_u32p)
-        _check(lib().rrt_model_get_octree(self._h, _d(aabb), u(fc), u(tc), u(off), u(idx)), "rrt_model_get_octree")
-        return dict(aabb=aabb, first_child=fc, tri_count=tc, own_off=off, own_idx=idx, max_depth=self.info["max_depth"])
+        out, arrays = _octree_arrays(self.info)
+        _call("rrt_model_get_octree", self._h, *arrays)
+        return out
 
 
 def parse_obj_file(path: str, root=DEFAULT_ROOT) -> SceneData:
     """fs::read_to_string + parse_obj_file_lines (src/main.rs:28-30, src/file_management/utils.rs:139-213)."""
-    r = (C.c_double * 6)(*root)
     out = _P()
-    _check(lib().rrt_model_load_obj(os.fsencode(path), r, C.byref(out)), f"parse_obj_file({path})")
+    _check(lib().rrt_model_load_obj(os.fsencode(path), _root(root), C.byref(out)), f"parse_obj_file({path})")
     return SceneData(out.value)
 
 
@@ -390,11 +581,12 @@ def decode_image_file(path: str) -> np.ndarray:
         lib().rrt_free(p)
 
 
-class RayTracer:
+class RayTracer(_Handle):
     """RayTracer{scene_data, lights, origin} (raytracer.rs:22-26), uploaded once to one MI355X."""
+    _destroy = "rrt_raytracer_destroy"
 
     def __init__(self, scene_data: SceneData, lights: Iterable[Light], origin: Vector3d = DEFAULT_ORIGIN, device: int = 0,
-                 surface_offset: float = 0.0001, max_reflection_depth: int = 5, viewport=(1.0, 1.0, 1.0), no_cull: bool = False,
+                 surface_offset: float = SURFACE_OFFSET, max_reflection_depth: int = MAX_REFLECTION_DEPTH, viewport=VIEWPORT, no_cull: bool = False,
                  box_filter: Optional[str] = None, host_setup: bool = False, chain_shortcut: bool = True):
         """no_cull=True (RRT_FLAG_NO_CULL): walk every own list in full, in list order, as ray.rs:119-129; default uses the cluster boxes.
         box_filter: None = rule of thumb on the first frame of a size, measured on the second, "lane" / "bundle" / "ray" = forced (RRT_FLAG_LANE_FILTER / RRT_FLAG_BUNDLE_FILTER /
@@ -402,14 +594,10 @@ class RayTracer:
         the GPU, csrc/scene_build.hip); same bytes in HBM.  chain_shortcut=False (RRT_FLAG_NO_CHAIN_SHORTCUT): the bundle-filter walk enters every node of a
         one-child chain; same results."""
         self.scene_data, self.origin, self.device = scene_data, origin, device
-        lights = list(lights)                                  # (not kept: lights() asks the library for the list in force)
-        cl = (CLight * max(1, len(lights)))()
-        for i, l in enumerate(lights):
-            cl[i] = CLight(l.kind, 0, float(l.intensity), l.v._c())
-        flags = (FLAG_NO_CULL if no_cull else 0) | (FLAG_HOST_SETUP if host_setup else 0) | (0 if chain_shortcut else FLAG_NO_CHAIN_SHORTCUT) | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter]
-        opt = COptions(surface_offset, max_reflection_depth, flags, *map(float, viewport))
+        cl, n_lights = _c_lights(lights)                       # (not kept: lights() asks the library for the list in force)
+        opt = _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut)
         out = _P()
-        _check(lib().rrt_raytracer_create(scene_data._h, cl, len(lights), origin._c(), C.byref(opt), device, C.byref(out)), "rrt_raytracer_create")
+        _call("rrt_raytracer_create", scene_data._h, cl, n_lights, origin._c(), C.byref(opt), device, C.byref(out))
         self._h = out
 
     @classmethod
@@ -418,123 +606,89 @@ class RayTracer:
         """rrt_raytracer_create_from_arrays: the raytracer straight from the host's arrays (no SceneData / rrt_model, no host copy of the scene)."""
         self = cls.__new__(cls)
         self.scene_data, self.origin, self.device = None, origin, device
-        lights = list(lights)
-        a = _marshal_arrays(pos, uv, nrm, mat, materials, textures, root)
-        cl = (CLight * max(1, len(lights)))()
-        for i, l in enumerate(lights):
-            cl[i] = CLight(l.kind, 0, float(l.intensity), l.v._c())
-        flags = (FLAG_NO_CULL if no_cull else 0) | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter]
-        opt = COptions(0.0001, 5, flags, 1.0, 1.0, 1.0)
+        scene, _keep = _scene_args(pos, uv, nrm, mat, materials, textures, root)
+        cl, n_lights = _c_lights(lights)
+        opt = _options(SURFACE_OFFSET, MAX_REFLECTION_DEPTH, VIEWPORT, no_cull, box_filter, False, True)
         out = _P()
-        _check(lib().rrt_raytracer_create_from_arrays(a.n, _d(a.pos), _d(a.uv), _d(a.nrm), a.mat.ctypes.data_as(_u32p), len(materials), a.cm, len(a.keep), a.ct, a.r,
-                                                      cl, len(lights), origin._c(), C.byref(opt), device, C.byref(out)), "rrt_raytracer_create_from_arrays")
+        _call("rrt_raytracer_create_from_arrays", *scene, cl, n_lights, origin._c(), C.byref(opt), device, C.byref(out))
         self._h = out
         return self
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.rrt_raytracer_destroy(h)
 
     @property
     def info(self) -> dict:
         """rrt_model_info of the octree this raytracer's GPU set-up built (no host-side tree is built for it)."""
         info = CModelInfo()
-        _check(lib().rrt_raytracer_get_octree(self._h, C.byref(info), None, None, None, None, None), "rrt_raytracer_get_octree")
-        return {k: getattr(info, k) for k, _ in CModelInfo._fields_}
+        _call("rrt_raytracer_get_octree", self._h, C.byref(info), None, None, None, None, None)
+        return _struct_dict(info)
 
     @property
     def chain_info(self) -> dict:
         """rrt_raytracer_get_chain_info: chains that have a shortcut record, and the chain nodes those records cover."""
         a = C.c_uint32(0); b = C.c_uint32(0)
-        _check(lib().rrt_raytracer_get_chain_info(self._h, C.byref(a), C.byref(b)), "rrt_raytracer_get_chain_info")
+        _call("rrt_raytracer_get_chain_info", self._h, C.byref(a), C.byref(b))
         return {"n_chains": a.value, "n_chain_nodes": b.value}
 
     def octree(self) -> dict:
         """The octree this raytracer's GPU set-up built (rrt_raytracer_get_octree): same dict as SceneData.octree(), plus "info"."""
-        info = CModelInfo()
-        _check(lib().rrt_raytracer_get_octree(self._h, C.byref(info), None, None, None, None, None), "rrt_raytracer_get_octree")
-        n = info.n_nodes
-        aabb = np.empty((n, 6)); fc = np.empty(n, np.uint32); tc = np.empty(n, np.uint32); off = np.empty(n + 1, np.uint32)
-        idx = np.empty(info.n_tris_in_tree, np.uint32)
-        u = lambda a: a.ctypes.data_as(_u32p)
-        _check(lib().rrt_raytracer_get_octree(self._h, None, _d(aabb), u(fc), u(tc), u(off), u(idx)), "rrt_raytracer_get_octree")
-        return dict(aabb=aabb, first_child=fc, tri_count=tc, own_off=off, own_idx=idx, max_depth=info.max_depth,
-                    info={k: getattr(info, k) for k, _ in CModelInfo._fields_})
+        info = self.info
+        out, arrays = _octree_arrays(info)
+        _call("rrt_raytracer_get_octree", self._h, None, *arrays)
+        return dict(out, info=info)
 
     def buffer(self, name: str) -> np.ndarray:
         """Raw bytes of one scene buffer in HBM (rrt_raytracer_get_buffer; tests compare the GPU set-up with the host set-up)."""
         which = BUFFERS.index(name)
         nb = C.c_size_t(0)
-        _check(lib().rrt_raytracer_get_buffer(self._h, which, None, 0, C.byref(nb)), "rrt_raytracer_get_buffer")
+        _call("rrt_raytracer_get_buffer", self._h, which, None, 0, C.byref(nb))
         out = np.empty(nb.value, np.uint8)
-        _check(lib().rrt_raytracer_get_buffer(self._h, which, out.ctypes.data_as(_P), nb.value, None), "rrt_raytracer_get_buffer")
+        _call("rrt_raytracer_get_buffer", self._h, which, out.ctypes.data_as(_P), nb.value, None)
         return out
 
     # the camera (rrt.h: rrt_camera).  Blocking; no frame of this raytracer may be in flight.
     def set_camera(self, eye, right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0)) -> None:
         """rrt_raytracer_set_camera: frames are taken from `eye`; the ray through scene point (a, b, c) has direction right*a + up*b + forward*c.  A new eye
         recomputes the exactness guard on the GPU; an unchanged eye (a pure rotation) costs nothing."""
-        c = CCamera(_vec3(eye), _vec3(right), _vec3(up), _vec3(forward))
-        _check(lib().rrt_raytracer_set_camera(self._h, C.byref(c)), "rrt_raytracer_set_camera")
+        _call("rrt_raytracer_set_camera", self._h, C.byref(CCamera(_vec3(eye), _vec3(right), _vec3(up), _vec3(forward))))
 
     def look_at(self, eye, target, up=(0.0, 1.0, 0.0)) -> None:
         self.set_camera(**look_at(eye, target, up))
 
     def reset_camera(self) -> None:
         """Back to the creation pose: eye = origin, looking down +z with y up."""
-        _check(lib().rrt_raytracer_set_camera(self._h, None), "rrt_raytracer_set_camera")
+        _call("rrt_raytracer_set_camera", self._h, None)
 
     def camera(self) -> dict:
         c = CCamera()
-        _check(lib().rrt_raytracer_get_camera(self._h, C.byref(c)), "rrt_raytracer_get_camera")
+        _call("rrt_raytracer_get_camera", self._h, C.byref(c))
         return _camera_dict(c)
 
     # scene updates (rrt.h: rrt_raytracer_set_lights, rrt_raytracer_set_triangles).  No launch of this raytracer may be in flight.
     def set_lights(self, lights: Iterable[Light]) -> None:
         """rrt_raytracer_set_lights: the light list of every launch from now on, in this order (host work only)."""
-        lights = list(lights)
-        cl = (CLight * max(1, len(lights)))()
-        for i, l in enumerate(lights):
-            cl[i] = CLight(l.kind, 0, float(l.intensity), l.v._c())
-        _check(lib().rrt_raytracer_set_lights(self._h, cl, len(lights)), "rrt_raytracer_set_lights")
+        _call("rrt_raytracer_set_lights", self._h, *_c_lights(lights))
 
     def lights(self) -> list:
         """rrt_raytracer_get_lights: the list the kernels get, as Light objects."""
-        n = C.c_uint32(0)
-        _check(lib().rrt_raytracer_get_lights(self._h, None, 0, C.byref(n)), "rrt_raytracer_get_lights")
-        cl = (CLight * max(1, n.value))()
-        _check(lib().rrt_raytracer_get_lights(self._h, cl, n.value, C.byref(n)), "rrt_raytracer_get_lights")
-        return [Light(l.kind, l.intensity, Vector3d(l.v.x, l.v.y, l.v.z)) for l in cl[:n.value]]
+        cl, n = _counted("rrt_raytracer_get_lights", self._h, CLight)
+        return [Light(l.kind, l.intensity, Vector3d(*_tuple3(l.v))) for l in cl[:n]]
 
     def set_materials(self, materials: Sequence[dict]) -> None:
         """rrt_raytracer_set_materials (blocking): a new material table (dicts ka, kd, ks, ns, kr, tex, bump) over the resident one, of the same length; textures,
         scene and measured variants stay.  All or nothing."""
-        materials = list(materials)
-        cm = (CMaterial * max(1, len(materials)))()
-        for i, m in enumerate(materials):
-            cm[i] = CMaterial(Vec3(*m["ka"]), Vec3(*m["kd"]), Vec3(*m["ks"]), float(m["ns"]), float(m["kr"]), int(m["tex"]), int(m.get("bump", -1)))
-        _check(lib().rrt_raytracer_set_materials(self._h, cm, len(materials)), "rrt_raytracer_set_materials")
+        _call("rrt_raytracer_set_materials", self._h, *_c_materials(materials))
 
     def materials(self) -> list:
         """rrt_raytracer_get_materials: the table in force, as the dicts SceneData.materials() returns."""
-        n = C.c_uint32(0)
-        _check(lib().rrt_raytracer_get_materials(self._h, None, 0, C.byref(n)), "rrt_raytracer_get_materials")
-        cm = (CMaterial * max(1, n.value))()
-        _check(lib().rrt_raytracer_get_materials(self._h, cm, n.value, C.byref(n)), "rrt_raytracer_get_materials")
-        v = lambda a: (a.x, a.y, a.z)
-        return [dict(ka=v(m.ka), kd=v(m.kd), ks=v(m.ks), ns=m.ns, kr=m.kr, tex=m.tex, bump=m.bump) for m in cm[:n.value]]
+        return _material_dicts(*_counted("rrt_raytracer_get_materials", self._h, CMaterial))
 
     def set_triangles(self, pos, uv, nrm, mat, root=None) -> None:
         """rrt_raytracer_set_triangles (blocking): new triangles from host arrays ([n,3,3] float64 x 3, [n] uint32 indexing the resident materials); octree,
         index and records are rebuilt on the GPU, everything else stays resident.  root=None: the root box in force.  All or nothing."""
-        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 9); uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 9)
-        nrm = np.ascontiguousarray(nrm, np.float64).reshape(-1, 9); mat = np.ascontiguousarray(mat, np.uint32).reshape(-1)
+        pos, uv, nrm, mat = _tri_arrays(pos, uv, nrm, mat)
         n = pos.shape[0]
         if not (uv.shape[0] == nrm.shape[0] == mat.shape[0] == n):
             raise ValueError(f"set_triangles: {n} positions, {uv.shape[0]} uv, {nrm.shape[0]} normals, {mat.shape[0]} material indices")
-        r = None if root is None else (C.c_double * 6)(*map(float, root))
-        _check(lib().rrt_raytracer_set_triangles(self._h, n, _d(pos), _d(uv), _d(nrm), mat.ctypes.data_as(_u32p), r), "rrt_raytracer_set_triangles")
+        _call("rrt_raytracer_set_triangles", self._h, n, _d(pos), _d(uv), _d(nrm), _u32(mat), _root(root))
 
     def set_triangles_from(self, pos_t, uv_t, nrm_t, mat_t, root=None, stream: Optional[int] = None) -> None:
         """rrt_raytracer_set_triangles_device (blocking): the same from torch tensors on this raytracer's device -- pos_t / uv_t / nrm_t float64 of 9 n
@@ -543,9 +697,7 @@ class RayTracer:
         wrong dtype or size."""
         import torch
         try:
-            assert getattr(pos_t, "is_cuda", False), "pos: not a device tensor"
-            n, rem = divmod(pos_t.numel(), 9)
-            assert rem == 0, "pos: the element count is not a multiple of 9"
+            n = _batch_size(pos_t, 9, "pos")
             for t, name in ((pos_t, "pos"), (uv_t, "uv"), (nrm_t, "nrm")):
                 _device_tensor(t, 9 * n, 8, name)
                 assert t.dtype == torch.float64, f"{name}: want float64, got {t.dtype}"
@@ -555,20 +707,17 @@ class RayTracer:
                 assert t.device.index in (None, self.device), f"{name}: on device {t.device.index}, the raytracer is on {self.device}"
         except AssertionError as e:
             raise ValueError(f"set_triangles_from: {e}") from None
-        r = None if root is None else (C.c_double * 6)(*map(float, root))
-        _check(lib().rrt_raytracer_set_triangles_device(self._h, n, _P(pos_t.data_ptr()), _P(uv_t.data_ptr()), _P(nrm_t.data_ptr()), _P(mat_t.data_ptr()), r,
-                                                        _P(_stream(stream))), "rrt_raytracer_set_triangles_device")
+        _call("rrt_raytracer_set_triangles_device", self._h, n, _ptr(pos_t), _ptr(uv_t), _ptr(nrm_t), _ptr(mat_t), _root(root), _P(_stream(stream)))
 
     def release_update_memory(self) -> None:
         """rrt_raytracer_release_update_memory: frees the device memory kept between set_triangles calls (the next one allocates again)."""
-        _check(lib().rrt_raytracer_release_update_memory(self._h), "rrt_raytracer_release_update_memory")
+        _call("rrt_raytracer_release_update_memory", self._h)
 
     # raytracer.rs:29, batched
     def get_ray_colours(self, origins, dirs) -> np.ndarray:
-        o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3); d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
-        assert o.shape == d.shape
+        o, d, _ = _host_rays(origins, dirs)
         out = np.empty(o.shape[0], np.uint32)
-        _check(lib().rrt_get_ray_colours(self._h, o.shape[0], _d(o), _d(d), out.ctypes.data_as(_u32p)), "rrt_get_ray_colours")
+        _call("rrt_get_ray_colours", self._h, o.shape[0], _d(o), _d(d), _u32(out))
         return out
 
     def get_ray_colour(self, origin: Vector3d, direction: Vector3d) -> int:
@@ -576,22 +725,17 @@ class RayTracer:
 
     # ray.rs:96-168, batched
     def intersect_rays(self, origins, dirs, max_t=None):
-        o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3); d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+        o, d, mt = _host_rays(origins, dirs, max_t)
         n = o.shape[0]
-        mt = None if max_t is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_t, np.float64), (n,)))
         hit = np.empty(n, np.uint8); t = np.empty(n); u = np.empty(n); v = np.empty(n); tri = np.empty(n, np.uint32)
-        _check(lib().rrt_intersect_rays(self._h, n, _d(o), _d(d), None if mt is None else _d(mt), hit.ctypes.data_as(_u8p), _d(t), _d(u), _d(v),
-                                        tri.ctypes.data_as(_u32p)), "rrt_intersect_rays")
+        _call("rrt_intersect_rays", self._h, n, _d(o), _d(d), _d(mt), _u8(hit), _d(t), _d(u), _d(v), _u32(tri))
         return hit.astype(bool), t, u, v, tri
 
     # Some/None of the same walk (rrt.h: rrt_occluded_rays): the reference's shadow query without its negation
     def occluded(self, origins, dirs, max_t=None) -> np.ndarray:
-        o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3); d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
-        assert o.shape == d.shape
-        n = o.shape[0]
-        mt = None if max_t is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_t, np.float64), (n,)))
-        out = np.empty(n, np.uint8)
-        _check(lib().rrt_occluded_rays(self._h, n, _d(o), _d(d), None if mt is None else _d(mt), out.ctypes.data_as(_u8p)), "rrt_occluded_rays")
+        o, d, mt = _host_rays(origins, dirs, max_t)
+        out = np.empty(o.shape[0], np.uint8)
+        _call("rrt_occluded_rays", self._h, o.shape[0], _d(o), _d(d), _d(mt), _u8(out))
         return out.astype(bool)
 
     # device-resident ray batches (rrt.h: rrt_intersect_rays_device): origins_t / dirs_t are float64 device tensors of 3 n elements, max_t_t of n; enqueued, not synchronised
@@ -599,8 +743,7 @@ class RayTracer:
         """rrt_occluded_rays_device: out_t = device tensor of n one-byte elements, 1 = occluded."""
         n = _ray_batch(origins_t, dirs_t, max_t_t)
         _device_tensor(out_t, n, 1, "out")
-        _check(lib().rrt_occluded_rays_device(self._h, n, _P(origins_t.data_ptr()), _P(dirs_t.data_ptr()), _P(max_t_t.data_ptr()) if max_t_t is not None else None,
-                                              _P(out_t.data_ptr()), _P(_stream(stream))), "rrt_occluded_rays_device")
+        _call("rrt_occluded_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), _ptr(out_t), _P(_stream(stream)))
 
     def intersect_rays_into(self, origins_t, dirs_t, out: dict, max_t_t=None, stream: Optional[int] = None):
         """rrt_intersect_rays_device: out = {name: device tensor of n elements} for any subset of hit (1 byte), t, u, v (float64), tri (4 bytes); the others are not
@@ -609,16 +752,14 @@ class RayTracer:
         assert set(out) <= set(PLANES[:5]), sorted(out)
         for name, t in out.items():
             _device_tensor(t, n, np.dtype(PLANE_DTYPES[name]).itemsize, name)
-        p = [_P(out[name].data_ptr()) if name in out else None for name in PLANES[:5]]
-        _check(lib().rrt_intersect_rays_device(self._h, n, _P(origins_t.data_ptr()), _P(dirs_t.data_ptr()), _P(max_t_t.data_ptr()) if max_t_t is not None else None,
-                                               *p, _P(_stream(stream))), "rrt_intersect_rays_device")
+        _call("rrt_intersect_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), *(_ptr(out.get(name)) for name in PLANES[:5]),
+              _P(_stream(stream)))
 
     def get_ray_colours_into(self, origins_t, dirs_t, colours_t, stream: Optional[int] = None):
         """rrt_get_ray_colours_device: colours_t = device tensor of n four-byte elements, 0x00RRGGBB."""
         n = _ray_batch(origins_t, dirs_t, None)
         _device_tensor(colours_t, n, 4, "colours")
-        _check(lib().rrt_get_ray_colours_device(self._h, n, _P(origins_t.data_ptr()), _P(dirs_t.data_ptr()), _P(colours_t.data_ptr()), _P(_stream(stream))),
-               "rrt_get_ray_colours_device")
+        _call("rrt_get_ray_colours_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(colours_t), _P(_stream(stream)))
 
     def tune_rays(self, origins_t, dirs_t, max_t_t=None) -> int:
         """rrt_tune_rays_device (blocking): measures the three traversal variants on this device-resident batch and keeps the fastest for later per-ray calls;
@@ -627,8 +768,7 @@ class RayTracer:
         import torch
         torch.cuda.current_stream().synchronize()
         v = C.c_uint32(0)
-        _check(lib().rrt_tune_rays_device(self._h, n, _P(origins_t.data_ptr()), _P(dirs_t.data_ptr()), _P(max_t_t.data_ptr()) if max_t_t is not None else None,
-                                          C.byref(v)), "rrt_tune_rays_device")
+        _call("rrt_tune_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), C.byref(v))
         return int(v.value)
 
     # engine.rs:196-253: chunked draw with an update after every chunk (on_update(fb, first_row, n_rows) stands in for canvas.update())
@@ -636,54 +776,71 @@ class RayTracer:
         fb = np.empty((height, width), np.uint32)
         UPD = C.CFUNCTYPE(None, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
         cb = UPD(lambda user, p, w, h, r0, n: on_update(fb, int(r0), int(n))) if on_update is not None else None
-        _check(lib().rrt_render_progressive(self._h, width, height, fb.ctypes.data_as(_u32p), chunk_rows, C.cast(cb, _P) if cb is not None else None, None),
-               "rrt_render_progressive")
+        _call("rrt_render_progressive", self._h, width, height, _u32(fb), chunk_rows, C.cast(cb, _P) if cb is not None else None, None)
         return fb
 
     # engine.rs:186 via the C ABI, host framebuffer
     def render(self, width: int, height: int) -> np.ndarray:
         fb = np.empty((height, width), np.uint32)
-        _check(lib().rrt_render(self._h, width, height, fb.ctypes.data_as(_u32p)), "rrt_render")
+        _call("rrt_render", self._h, width, height, _u32(fb))
+        return fb
+
+    def render_registered(self, width: int, height: int, fb: Optional[np.ndarray] = None) -> np.ndarray:
+        """rrt_render into a page-locked framebuffer (rrt_host_buffer_register): the frame arrives by one asynchronous DMA."""
+        if fb is None:
+            fb = np.empty((height, width), np.uint32)
+        p = _P(fb.ctypes.data)
+        _call("rrt_host_buffer_register", p, fb.nbytes)
+        try:
+            _call("rrt_render", self._h, width, height, _u32(fb))
+        finally:
+            _call("rrt_host_buffer_unregister", p)
         return fb
 
     # device-resident variants (torch tensors are plumbing: data_ptr + current stream)
     def render_into(self, fb_tensor, width: int, height: int, stream: Optional[int] = None):
-        assert fb_tensor.is_cuda and fb_tensor.is_contiguous() and fb_tensor.numel() == width * height and fb_tensor.element_size() == 4
-        _check(lib().rrt_render_device(self._h, width, height, _P(fb_tensor.data_ptr()), _P(_stream(stream))), "rrt_render_device")
+        self.bind_render(fb_tensor, width, height, stream)()
 
     def render_tiles_into(self, tiles_tensor, width: int, height: int, rank: int, world: int, stream: Optional[int] = None):
-        need = tiles_per_rank(width, height, world) * 64
-        assert tiles_tensor.is_cuda and tiles_tensor.is_contiguous() and tiles_tensor.numel() == need and tiles_tensor.element_size() == 4
-        _check(lib().rrt_render_tiles_device(self._h, width, height, rank, world, _P(tiles_tensor.data_ptr()), _P(_stream(stream))), "rrt_render_tiles_device")
+        self.bind_render_tiles(tiles_tensor, width, height, rank, world, stream)()
 
     def detile_into(self, gathered_tensor, fb_tensor, width: int, height: int, world: int, stream: Optional[int] = None):
-        assert gathered_tensor.numel() == tiles_per_rank(width, height, world) * 64 * world and fb_tensor.numel() == width * height
-        _check(lib().rrt_detile_device(self._h, width, height, world, _P(gathered_tensor.data_ptr()), _P(fb_tensor.data_ptr()), _P(_stream(stream))),
-               "rrt_detile_device")
+        self.bind_detile(gathered_tensor, fb_tensor, width, height, world, stream)()
+
+    # pre-bound launchers for per-frame loops (bench.py): all argument conversion is done once, the returned callable is one ctypes call
+    def bind_render(self, fb_tensor, width: int, height: int, stream: Optional[int] = None):
+        _device_tensor(fb_tensor, width * height, 4, "fb")
+        return _bound("rrt_render_device", self._h, C.c_uint32(width), C.c_uint32(height), _ptr(fb_tensor), _P(_stream(stream)))
+
+    def bind_render_tiles(self, tiles_tensor, width: int, height: int, rank: int, world: int, stream: Optional[int] = None):
+        _device_tensor(tiles_tensor, tiles_per_rank(width, height, world) * 64, 4, "tiles")
+        return _bound("rrt_render_tiles_device", self._h, C.c_uint32(width), C.c_uint32(height), C.c_uint32(rank), C.c_uint32(world), _ptr(tiles_tensor),
+                      _P(_stream(stream)))
+
+    def bind_detile(self, gathered_tensor, fb_tensor, width: int, height: int, world: int, stream: Optional[int] = None):
+        _device_tensor(gathered_tensor, tiles_per_rank(width, height, world) * 64 * world, 4, "gathered")
+        _device_tensor(fb_tensor, width * height, 4, "fb")
+        return _bound("rrt_detile_device", self._h, C.c_uint32(width), C.c_uint32(height), C.c_uint32(world), _ptr(gathered_tensor), _ptr(fb_tensor),
+                      _P(_stream(stream)))
 
     # visibility buffers (rrt.h: rrt_render_visibility): first-hit geometry of the frame's primary rays.  region = (x0, y0, w, h) in canvas pixels, None = the frame
     def visibility(self, width: int, height: int, region=None, planes=PLANES) -> dict:
         """rrt_render_visibility: {plane: array [h][w][4]} of the region (last index: the sub-sample), only the planes asked for.  hit uint8, t / u / v
         float64, tri uint32 (push order, 0xFFFFFFFF = miss), albedo uint32 0x00RRGGBB."""
-        h, w = (height, width) if region is None else (int(region[3]), int(region[2]))
-        out = {n: np.empty((h, w, 4), PLANE_DTYPES[n]) for n in planes}
-        cv = CVisibility(**{n: a.ctypes.data for n, a in out.items()})
-        _check(lib().rrt_render_visibility(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv)), "rrt_render_visibility")
+        reg, w, h = _region(width, height, region)
+        out = _alloc_planes(CVisibility, planes, w, h)
+        _call("rrt_render_visibility", self._h, width, height, reg, _plane_struct(CVisibility, out))
         return out
 
     def visibility_into(self, tensors: dict, width: int, height: int, region=None, stream: Optional[int] = None):
         """rrt_render_visibility_device: tensors = {plane: contiguous device tensor of 4*w*h elements of the plane's size}; enqueued, not synchronised."""
-        n = 4 * (width * height if region is None else int(region[2]) * int(region[3]))
-        for name, t in tensors.items():
-            assert t.is_cuda and t.is_contiguous() and t.numel() == n and t.element_size() == np.dtype(PLANE_DTYPES[name]).itemsize, name
-        cv = CVisibility(**{name: t.data_ptr() for name, t in tensors.items()})
-        _check(lib().rrt_render_visibility_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv),
-                                                  _P(_stream(stream))), "rrt_render_visibility_device")
+        reg, w, h = _region(width, height, region)
+        _call("rrt_render_visibility_device", self._h, width, height, reg, _plane_struct(CVisibility, _device_planes(tensors, tensors, w, h)), _P(_stream(stream)))
 
     def pick(self, width: int, height: int, px: int, py: int) -> dict:
         """rrt_pick: what sub-sample 0 of canvas pixel (px, py) sees: dict hit (bool), tri, t, u, v, albedo."""
         r = CPickResult()
-        _check(lib().rrt_pick(self._h, width, height, px, py, C.byref(r)), "rrt_pick")
+        _call("rrt_pick", self._h, width, height, px, py, C.byref(r))
         return dict(hit=bool(r.hit), tri=r.tri, t=r.t, u=r.u, v=r.v, albedo=r.albedo)
 
     # surface buffers (rrt.h: rrt_render_surface): hit point, shading normal, material index and light mask of the frame's primary rays
@@ -691,64 +848,38 @@ class RayTracer:
         """rrt_render_surface: {plane: array} of the region, only the planes asked for.  point / normal float64 [h][w][4][3], material / lights uint32
         [h][w][4] (material 0xFFFFFFFF = miss; lights: bit k = light k reaches the point), and the visibility planes named in `visibility` ([h][w][4], as
         visibility() returns them) from the same launch."""
-        h, w = (height, width) if region is None else (int(region[3]), int(region[2]))
-        out = {n: np.empty((h, w, 4, 3) if SURFACE_WIDTHS[n] == 3 else (h, w, 4), SURFACE_DTYPES[n]) for n in planes}
-        vis = {n: np.empty((h, w, 4), PLANE_DTYPES[n]) for n in visibility}
-        cs = CSurface(**{n: a.ctypes.data for n, a in out.items()})
-        cv = CVisibility(**{n: a.ctypes.data for n, a in vis.items()})
-        _check(lib().rrt_render_surface(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv) if vis else None,
-                                        C.byref(cs)), "rrt_render_surface")
+        reg, w, h = _region(width, height, region)
+        out, vis = _alloc_planes(CSurface, planes, w, h), _alloc_planes(CVisibility, visibility, w, h)
+        _call("rrt_render_surface", self._h, width, height, reg, _plane_struct(CVisibility, vis) if vis else None, _plane_struct(CSurface, out))
         out.update(vis)
         return out
 
     def surface_into(self, tensors: dict, width: int, height: int, region=None, stream: Optional[int] = None):
         """rrt_render_surface_device: tensors = {plane: contiguous device tensor}, keys from SURFACE_PLANES (12*w*h float64 for point / normal, 4*w*h four-byte
         elements for material / lights) and from PLANES (4*w*h elements of the plane's size); enqueued, not synchronised."""
-        n = 4 * (width * height if region is None else int(region[2]) * int(region[3]))
-        for name, t in tensors.items():
-            if name in SURFACE_DTYPES:
-                _device_tensor(t, n * SURFACE_WIDTHS[name], np.dtype(SURFACE_DTYPES[name]).itemsize, name)
-            else:
-                _device_tensor(t, n, np.dtype(PLANE_DTYPES[name]).itemsize, name)
-        cs = CSurface(**{name: t.data_ptr() for name, t in tensors.items() if name in SURFACE_DTYPES})
-        cv = CVisibility(**{name: t.data_ptr() for name, t in tensors.items() if name not in SURFACE_DTYPES})
-        _check(lib().rrt_render_surface_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv), C.byref(cs),
-                                               _P(_stream(stream))), "rrt_render_surface_device")
+        reg, w, h = _region(width, height, region)
+        keep = _device_planes(tensors, tensors, w, h)
+        _call("rrt_render_surface_device", self._h, width, height, reg, _plane_struct(CVisibility, keep), _plane_struct(CSurface, keep), _P(_stream(stream)))
 
     # shading from kept buffers (rrt.h: rrt_shade_surface): the frame of the planes surface() returned, with the lights and materials in force now
     def shade(self, width: int, height: int, planes: dict, region=None) -> np.ndarray:
         """rrt_shade_surface: planes = dict with point, normal ([h][w][4][3] float64), material, albedo ([h][w][4] uint32) and optionally lights, as
         surface(..., visibility=("albedo",)) returns them for this size and region; returns the region's pixels, [h][w] uint32 0x00RRGGBB.  Without `lights`
         the depth-0 shadow rays are walked again.  Other keys are ignored; a missing required plane is passed as NULL (the library refuses it)."""
-        h, w = (height, width) if region is None else (int(region[3]), int(region[2]))
-        keep = {}
-        for name in ("point", "normal", "material", "lights", "albedo"):
-            if planes.get(name) is not None:
-                dtype = SURFACE_DTYPES.get(name, np.uint32)
-                keep[name] = np.ascontiguousarray(planes[name], dtype)
-                want = (h, w, 4, 3) if SURFACE_WIDTHS.get(name) == 3 else (h, w, 4)
-                if keep[name].shape != want:
-                    raise ValueError(f"shade: plane {name} has shape {keep[name].shape}, want {want}")
-        cs = CSurface(**{n: a.ctypes.data for n, a in keep.items() if n != "albedo"})
-        cv = CVisibility(**({"albedo": keep["albedo"].ctypes.data} if "albedo" in keep else {}))
+        reg, w, h = _region(width, height, region)
+        keep = _host_planes("shade", planes, SHADE_INPUTS, w, h)
         fb = np.empty((h, w), np.uint32)
-        _check(lib().rrt_shade_surface(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv), C.byref(cs),
-                                       fb.ctypes.data_as(_u32p)), "rrt_shade_surface")
+        _call("rrt_shade_surface", self._h, width, height, reg, _plane_struct(CVisibility, keep), _plane_struct(CSurface, keep), _u32(fb))
         return fb
 
     def shade_into(self, fb_tensor, tensors: dict, width: int, height: int, region=None, stream: Optional[int] = None):
         """rrt_shade_surface_device: tensors = {plane: contiguous device tensor} with point, normal, material, albedo and optionally lights, as surface_into
         filled them; fb_tensor = w*h four-byte elements of the region; enqueued, not synchronised."""
-        px = width * height if region is None else int(region[2]) * int(region[3])
-        _device_tensor(fb_tensor, px, 4, "fb")
-        for name in ("point", "normal", "material", "lights", "albedo"):
-            if tensors.get(name) is not None:
-                _device_tensor(tensors[name], 4 * px * SURFACE_WIDTHS.get(name, 1), 8 if SURFACE_WIDTHS.get(name) == 3 else 4, name)
-        ptr = lambda name: tensors[name].data_ptr() if tensors.get(name) is not None else None
-        cs = CSurface(point=ptr("point"), normal=ptr("normal"), material=ptr("material"), lights=ptr("lights"))
-        cv = CVisibility(albedo=ptr("albedo"))
-        _check(lib().rrt_shade_surface_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))), C.byref(cv), C.byref(cs),
-                                              _P(fb_tensor.data_ptr()), _P(_stream(stream))), "rrt_shade_surface_device")
+        reg, w, h = _region(width, height, region)
+        _device_tensor(fb_tensor, w * h, 4, "fb")
+        keep = _device_planes(tensors, SHADE_INPUTS, w, h)
+        _call("rrt_shade_surface_device", self._h, width, height, reg, _plane_struct(CVisibility, keep), _plane_struct(CSurface, keep), _ptr(fb_tensor),
+              _P(_stream(stream)))
 
     # ambient occlusion from kept buffers (rrt.h: rrt_ambient_surface): which of the hemisphere rays `dirs` from every first hit are blocked
     def ambient(self, width: int, height: int, planes: dict, dirs, max_t: float = float("inf"), region=None, outputs=AMBIENT_OUTPUTS) -> dict:
@@ -756,103 +887,44 @@ class RayTracer:
         and region (other keys are ignored; a missing plane is passed as NULL, which the library refuses); dirs = [n][3] directions in the tangent frame of a
         hit (z along the normal), n <= MAX_AMBIENT_SAMPLES; max_t as occluded() takes it.  Returns {"occluded": [h][w][4] uint32, bit k = ray k is blocked,
         "grey": [h][w] uint32 0x00GGGGGG, the share of open rays}, only the outputs asked for."""
-        h, w = (height, width) if region is None else (int(region[3]), int(region[2]))
-        keep = {}
-        for name in ("point", "normal", "material"):
-            if planes.get(name) is not None:
-                keep[name] = np.ascontiguousarray(planes[name], SURFACE_DTYPES[name])
-                want = (h, w, 4, 3) if SURFACE_WIDTHS[name] == 3 else (h, w, 4)
-                if keep[name].shape != want:
-                    raise ValueError(f"ambient: plane {name} has shape {keep[name].shape}, want {want}")
-        d, cs = _ambient_samples(dirs, max_t)
-        out = {n: np.empty((h, w, 4) if n == "occluded" else (h, w), np.uint32) for n in outputs}
-        _check(lib().rrt_ambient_surface(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))),
-                                         C.byref(CSurface(**{n: a.ctypes.data for n, a in keep.items()})), C.byref(cs),
-                                         C.byref(CAmbient(**{n: a.ctypes.data for n, a in out.items()}))), "rrt_ambient_surface")
+        reg, w, h = _region(width, height, region)
+        keep = _host_planes("ambient", planes, AMBIENT_INPUTS, w, h)
+        _d_keep, samples = _ambient_samples(dirs, max_t)
+        out = _alloc_planes(CAmbient, outputs, w, h)
+        _call("rrt_ambient_surface", self._h, width, height, reg, _plane_struct(CSurface, keep), C.byref(samples), _plane_struct(CAmbient, out))
         return out
 
     def ambient_into(self, out_tensors: dict, plane_tensors: dict, dirs, max_t: float, width: int, height: int, region=None, stream: Optional[int] = None):
         """rrt_ambient_surface_device: plane_tensors = {plane: contiguous device tensor} with point, normal and material as surface_into filled them;
         out_tensors = {"occluded": 4*w*h four-byte elements, "grey": w*h four-byte elements} of the region, either or both; dirs (host, [n][3]) and max_t as
         ambient(); enqueued, not synchronised."""
-        px = width * height if region is None else int(region[2]) * int(region[3])
+        reg, w, h = _region(width, height, region)
         assert set(out_tensors) <= set(AMBIENT_OUTPUTS), sorted(out_tensors)
-        for name, t in out_tensors.items():
-            _device_tensor(t, 4 * px if name == "occluded" else px, 4, name)
-        for name in ("point", "normal", "material"):
-            if plane_tensors.get(name) is not None:
-                _device_tensor(plane_tensors[name], 4 * px * SURFACE_WIDTHS[name], np.dtype(SURFACE_DTYPES[name]).itemsize, name)
-        ptr = lambda name: plane_tensors[name].data_ptr() if plane_tensors.get(name) is not None else None
-        d, cs = _ambient_samples(dirs, max_t)
-        _check(lib().rrt_ambient_surface_device(self._h, width, height, None if region is None else C.byref(CRegion(*map(int, region))),
-                                                C.byref(CSurface(point=ptr("point"), normal=ptr("normal"), material=ptr("material"))), C.byref(cs),
-                                                C.byref(CAmbient(**{n: t.data_ptr() for n, t in out_tensors.items()})), _P(_stream(stream))),
-               "rrt_ambient_surface_device")
-
-    # pre-bound launchers for per-frame loops (bench.py): all argument conversion is done once, the returned callable is one ctypes call
-    def bind_render(self, fb_tensor, width: int, height: int, stream: Optional[int] = None):
-        assert fb_tensor.is_cuda and fb_tensor.is_contiguous() and fb_tensor.numel() == width * height and fb_tensor.element_size() == 4
-        fn, h, w_, h_, p, st = lib().rrt_render_device, self._h, C.c_uint32(width), C.c_uint32(height), _P(fb_tensor.data_ptr()), _P(_stream(stream))
-
-        def launch():
-            rc = fn(h, w_, h_, p, st)
-            if rc != OK:
-                _check(rc, "rrt_render_device")
-        return launch
-
-    def bind_render_tiles(self, tiles_tensor, width: int, height: int, rank: int, world: int, stream: Optional[int] = None):
-        assert tiles_tensor.is_cuda and tiles_tensor.is_contiguous() and tiles_tensor.numel() == tiles_per_rank(width, height, world) * 64
-        fn, h, st = lib().rrt_render_tiles_device, self._h, _P(_stream(stream))
-        args = (C.c_uint32(width), C.c_uint32(height), C.c_uint32(rank), C.c_uint32(world), _P(tiles_tensor.data_ptr()))
-
-        def launch():
-            rc = fn(h, *args, st)
-            if rc != OK:
-                _check(rc, "rrt_render_tiles_device")
-        return launch
-
-    def bind_detile(self, gathered_tensor, fb_tensor, width: int, height: int, world: int, stream: Optional[int] = None):
-        assert gathered_tensor.numel() == tiles_per_rank(width, height, world) * 64 * world and fb_tensor.numel() == width * height
-        fn, h, st = lib().rrt_detile_device, self._h, _P(_stream(stream))
-        args = (C.c_uint32(width), C.c_uint32(height), C.c_uint32(world), _P(gathered_tensor.data_ptr()), _P(fb_tensor.data_ptr()))
-
-        def launch():
-            rc = fn(h, *args, st)
-            if rc != OK:
-                _check(rc, "rrt_detile_device")
-        return launch
+        out, keep = _device_planes(out_tensors, AMBIENT_OUTPUTS, w, h), _device_planes(plane_tensors, AMBIENT_INPUTS, w, h)
+        _d_keep, samples = _ambient_samples(dirs, max_t)
+        _call("rrt_ambient_surface_device", self._h, width, height, reg, _plane_struct(CSurface, keep), C.byref(samples), _plane_struct(CAmbient, out),
+              _P(_stream(stream)))
 
     def setup_times(self) -> dict:
         """Wall ms of the once-per-scene stages: read, parse, texture decode, octree (model) + index, upload (this raytracer)."""
         t = CSetupTimes()
-        _check(lib().rrt_get_setup_times(self.scene_data._h if self.scene_data is not None else None, self._h, C.byref(t)), "rrt_get_setup_times")
-        return {n: getattr(t, n) for n, _ in CSetupTimes._fields_}
-
-    def render_registered(self, width: int, height: int, fb: Optional[np.ndarray] = None) -> np.ndarray:
-        """rrt_render into a page-locked framebuffer (rrt_host_buffer_register): the frame arrives by one asynchronous DMA."""
-        if fb is None:
-            fb = np.empty((height, width), np.uint32)
-        p = _P(fb.ctypes.data)
-        _check(lib().rrt_host_buffer_register(p, fb.nbytes), "rrt_host_buffer_register")
-        try:
-            _check(lib().rrt_render(self._h, width, height, fb.ctypes.data_as(_u32p)), "rrt_render")
-        finally:
-            _check(lib().rrt_host_buffer_unregister(p), "rrt_host_buffer_unregister")
-        return fb
+        _call("rrt_get_setup_times", self.scene_data._h if self.scene_data is not None else None, self._h, C.byref(t))
+        return _struct_dict(t)
 
     def last_stats(self) -> dict:
         s = CStats()
-        _check(lib().rrt_last_stats(self._h, C.byref(s)), "rrt_last_stats")
-        return {n: getattr(s, n) for n, _ in CStats._fields_}
+        _call("rrt_last_stats", self._h, C.byref(s))
+        return _struct_dict(s)
 
 
 MULTI_LOOPBACK = 1   # RRT_MULTI_LOOPBACK
 
 
-class MultiGpu:
+class MultiGpu(_Handle):
     """The N GPUs of one node behind one handle (include/rrt.h, rrt_multi): the screen-tile partition, the RCCL gather to rank 0 and the de-tiling
     all happen inside the library.  MultiGpu(raytracers) = one process driving every GPU (rrt_multi_create); MultiGpu.dist(rt, rank, world, unique_id)
     = one process per GPU (rrt_dist_create; rank 0 makes the id with MultiGpu.unique_id() and the caller broadcasts it)."""
+    _destroy = "rrt_multi_destroy"
 
     def __init__(self, raytracers: Sequence["RayTracer"], frames_in_flight: int = 1, loopback: bool = False, _handle=None):
         self._keep = list(raytracers)
@@ -861,87 +933,42 @@ class MultiGpu:
             return
         arr = (_P * len(self._keep))(*[rt._h for rt in self._keep])
         out = _P()
-        _check(lib().rrt_multi_create(arr, len(self._keep), frames_in_flight, MULTI_LOOPBACK if loopback else 0, C.byref(out)), "rrt_multi_create")
+        _call("rrt_multi_create", arr, len(self._keep), frames_in_flight, MULTI_LOOPBACK if loopback else 0, C.byref(out))
         self._h = out
 
     @staticmethod
     def unique_id() -> bytes:
         buf = C.create_string_buffer(128)
-        _check(lib().rrt_dist_unique_id(buf), "rrt_dist_unique_id")
+        _call("rrt_dist_unique_id", buf)
         return buf.raw
 
     @staticmethod
     def dist(rt: "RayTracer", rank: int, world: int, unique_id: Optional[bytes], frames_in_flight: int = 1) -> "MultiGpu":
         out = _P()
         idbuf = C.create_string_buffer(unique_id, 128) if unique_id is not None else None
-        _check(lib().rrt_dist_create(rt._h, rank, world, idbuf, frames_in_flight, C.byref(out)), "rrt_dist_create")
+        _call("rrt_dist_create", rt._h, rank, world, idbuf, frames_in_flight, C.byref(out))
         return MultiGpu([rt], _handle=out)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.rrt_multi_destroy(h)
 
     def render(self, width: int, height: int) -> np.ndarray:
         """Blocking Scene::draw_scene over all GPUs, host framebuffer (rrt_render_multi)."""
         fb = np.empty((height, width), np.uint32)
-        _check(lib().rrt_render_multi(self._h, width, height, fb.ctypes.data_as(_u32p)), "rrt_render_multi")
+        _call("rrt_render_multi", self._h, width, height, _u32(fb))
         return fb
 
     def bind_enqueue(self, fb_tensor, width: int, height: int):
         """One ctypes call per frame: trace -> gather -> de-tile enqueued on the next slot (fb_tensor on rank 0's GPU, None elsewhere)."""
-        fn, h, w_, h_ = lib().rrt_multi_enqueue, self._h, C.c_uint32(width), C.c_uint32(height)
-        p = _P(fb_tensor.data_ptr()) if fb_tensor is not None else _P()
-
-        def enqueue():
-            rc = fn(h, w_, h_, p)
-            if rc != OK:
-                _check(rc, "rrt_multi_enqueue")
-        return enqueue
+        return _bound("rrt_multi_enqueue", self._h, C.c_uint32(width), C.c_uint32(height), _ptr(fb_tensor))
 
     def sync(self) -> None:
-        _check(lib().rrt_multi_sync(self._h), "rrt_multi_sync")
+        _call("rrt_multi_sync", self._h)
 
     def last_gather_ms(self) -> float:
         v = C.c_double(-1.0)
-        _check(lib().rrt_multi_last_gather_ms(self._h, C.byref(v)), "rrt_multi_last_gather_ms")
+        _call("rrt_multi_last_gather_ms", self._h, C.byref(v))
         return v.value
 
 
-def _ambient_samples(dirs, max_t):
-    """(the [n][3] float64 array, which must outlive the call, and the rrt_ambient_samples that points at it)"""
-    d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
-    return d, CAmbientSamples(dirs=d.ctypes.data_as(_dp), n=len(d), max_t=float(max_t))
-
-
-def _device_tensor(t, n: int, itemsize: int, name: str):
-    """What every _into form asserts of a tensor before the library sees its pointer (a numpy array fails here, without a GPU)."""
-    assert getattr(t, "is_cuda", False), f"{name}: not a device tensor"
-    assert t.is_contiguous() and t.element_size() == itemsize and t.numel() == n, f"{name}: want {n} contiguous elements of {itemsize} bytes"
-
-
-def _ray_batch(origins_t, dirs_t, max_t_t) -> int:
-    """Checks a device-resident ray batch (float64 tensors: origins and directions of 3 n elements, max_t of n or None); returns n."""
-    assert getattr(origins_t, "is_cuda", False), "origins: not a device tensor"
-    n, rem = divmod(origins_t.numel(), 3)
-    assert rem == 0, "origins: the element count is not a multiple of 3"
-    _device_tensor(origins_t, 3 * n, 8, "origins"); _device_tensor(dirs_t, 3 * n, 8, "dirs")
-    if max_t_t is not None:
-        _device_tensor(max_t_t, n, 8, "max_t")
-    return n
-
-
-def _stream(stream: Optional[int]) -> int:
-    if stream is not None:
-        return stream
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def tiles_per_rank(width: int, height: int, world: int) -> int:
-    return int(lib().rrt_tiles_per_rank(width, height, world))
-
-
+# ---------------------------------------------------------------------------------------------- host mirrors of the tile partition
 def tile_owner_map(width: int, height: int, world: int) -> np.ndarray:
     """[tiles_y, tiles_x] rank owning each 8x8-pixel tile (tile k -> k % world) -- host mirror of the kernel's partition."""
     tx, ty = (width + 7) // 8, (height + 7) // 8
@@ -958,6 +985,7 @@ def detile_host(gathered: np.ndarray, width: int, height: int, world: int) -> np
     return tiles.transpose(0, 2, 1, 3).reshape(ty * 8, tx * 8)[:height, :width].copy()
 
 
+# ---------------------------------------------------------------------------------------------- the reference's canvas and scene
 class Canvas:                        # src/scene/engine.rs:123-167 minus the minifb window
     def __init__(self, width: int, height: int, on_update=None):
         self.width, self.height = width, height
