@@ -496,6 +496,52 @@ int rrt_occluded_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_orig
  * rays to come is the caller's business.  A raytracer with a forced variant does no GPU work and reports that variant.  variant_out may be NULL. */
 int rrt_tune_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_origins, const double *d_dirs, const double *d_max_t, uint32_t *variant_out);
 
+/* Surface attributes and bounce rays of arbitrary rays: per ray of a batch the full surface record of its first hit -- what rrt_render_surface* gives for a
+ * frame's primary rays -- and the reference's own next ray from there.  For the G-buffers of what a mirror shows, second-bounce ambient occlusion, baking and
+ * probes from points that are not the eye, and any integrator that keeps its rays on the GPU: a whole reflection chain of get_ray_colour_recursive
+ * (raytracer.rs:29-112) can be followed level by level, feeding next_origin / next_dir of one call to the next, without restating reference arithmetic outside
+ * the library.
+ * Per ray i with origin o, direction d and bound m = max_t[i] (max_t NULL = +inf):
+ *   hit, t, u, v, tri = exactly what rrt_intersect_rays returns for (o, d, m), byte for byte, its miss convention (hit 0, t = u = v = 0.0, tri = 0xFFFFFFFF) and
+ *              its max_t rule included: a NaN or non-positive max_t is a miss.  Such a ray takes part in no walk: it is the way to pass a dead ray in a batch
+ *              of fixed size;
+ *   albedo   = the colour-texture texel of the hit, 0x00RRGGBB, as the visibility planes define it; a miss gives 0x00FFFFFF, the reference's background;
+ *   point    = o + d * t (raytracer.rs:39);
+ *   normal, material = as rrt_surface defines them: the value of get_normal_at_intersection (raytracer.rs:114-162) and the index in the material table;
+ *   lights   = as rrt_surface defines it, bit k for light k: 1 for an Ambient or Directional light; for a Point light the negation of what rrt_occluded_rays
+ *              returns for origin = point + normal * surface_offset, direction = light - point, max_t = |direction|.  Every point light is tested, also those
+ *              behind the reference's `break` (raytracer.rs:235-237).  Bits >= n_lights are 0;
+ *   next_origin = point + normal * surface_offset (raytracer.rs:82): the origin of the reflection ray, and of the shadow and ambient rays of the hit;
+ *   next_dir = normalised(d - (normal * 2.0) * dot(d, normal)) (raytracer.rs:78-79), the reflection ray's direction as a frame forms it.  It is written for
+ *              every hit, whatever the material's kr: whether the reference would reflect there (kr > 0, depth below max_reflection_depth) is the caller's
+ *              decision, taken from `material`.
+ * A miss gives point = normal = next_origin = next_dir = (0.0, 0.0, 0.0), material = 0xFFFFFFFF, lights = 0.
+ * Any of the twelve pointers may be NULL (that array is not written), at least one is set.  What is not asked for is not computed: without `lights` no shadow
+ * ray is walked; without albedo, normal, material, lights, next_origin and next_dir no attribute of the hit is loaded; without those and u and v the second
+ * Moller-Trumbore is skipped -- hit / t / tri alone run the one walk of rrt_intersect_rays_device and nothing else.  Inputs and outputs must not overlap.  A non-finite origin or
+ * direction gives unspecified bits for that ray, and no fault.
+ * Exactness: the first walk is rrt_intersect_rays' walk, its guard included (keyed to the current eye); the shadow walks are the frame kernels' shadow walks --
+ * default mode, not guarded, the band documented under RRT_FLAG_NO_CULL.
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer as it was: NULL rt; NULL struct; all twelve pointers NULL with n > 0; NULL origins or dirs
+ * with n > 0.  n = 0 is RRT_OK with nothing enqueued.
+ * rrt_last_stats afterwards: as after the other per-ray calls (width = n, height = 1, rays_primary = n; shadow rays are not counted).
+ * rrt_surface_rays_device: rays and arrays in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default): no allocation, no copy, no
+ * synchronisation and no measurement; the traversal variant by the rule of rrt_intersect_rays_device.
+ * rrt_surface_rays: rays and arrays in host memory; blocking.  One device allocation of the call's own; only the requested arrays are downloaded.  The traversal
+ * variant is measured on a first large batch as for the other host forms (same thresholds, same kept variant).
+ * rrt_raytracer_set_camera (the guard's eye), set_lights, set_materials and set_triangles[_device] apply to every call made after they return.
+ * Not covered: the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+typedef struct {
+    uint8_t *hit; double *t, *u, *v; uint32_t *tri, *albedo;   /* [n] each                */
+    double *point, *normal;                                   /* [n][3]                  */
+    uint32_t *material, *lights;                              /* [n]                     */
+    double *next_origin, *next_dir;                           /* [n][3]                  */
+} rrt_ray_surface;                                            /* 12 pointers, 96 bytes   */
+int rrt_surface_rays(rrt_raytracer *rt, uint32_t n, const double *origins, const double *dirs, const double *max_t,
+                     const rrt_ray_surface *out);
+int rrt_surface_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_origins, const double *d_dirs, const double *d_max_t,
+                            const rrt_ray_surface *d_out, void *stream);
+
 /* The octree of a raytracer whose set-up ran on the GPU (the default), read back from its device: same layout as rrt_model_get_octree; info (may be
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */
 int rrt_raytracer_get_octree(const rrt_raytracer *rt, rrt_model_info *info, double *aabb, uint32_t *first_child, uint32_t *tri_count,

@@ -89,6 +89,10 @@ class CAmbient(C.Structure):         # rrt_ambient, 16 bytes: host or device poi
     _fields_ = [(n, C.c_void_p) for n in ("occluded", "grey")]
 
 
+class CRaySurface(C.Structure):      # rrt_ray_surface, 96 bytes: host or device pointers, NULL = array not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("hit", "t", "u", "v", "tri", "albedo", "point", "normal", "material", "lights", "next_origin", "next_dir")]
+
+
 MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
 
 # The plane table: every plane of rrt_visibility, rrt_surface and rrt_ambient, in the struct's order, as (dtype, elements per sub-sample, True = one value per
@@ -100,6 +104,8 @@ _PLANES_OF = {
     CAmbient: dict(occluded=(np.uint32, 1, True), grey=(np.uint32, 1, False)),
 }
 PLANE_TABLE = {n: row for rows in _PLANES_OF.values() for n, row in rows.items()}
+# rrt_ray_surface: the visibility and surface planes' rows per RAY of a batch ([n], [n][3]) and the two vectors of the reference's next ray
+_PLANES_OF[CRaySurface] = dict(**_PLANES_OF[CVisibility], **_PLANES_OF[CSurface], next_origin=(np.float64, 3, True), next_dir=(np.float64, 3, True))
 PLANES = tuple(_PLANES_OF[CVisibility])                                       # the planes of rrt_visibility, in its order
 PLANE_DTYPES = {n: row[0] for n, row in _PLANES_OF[CVisibility].items()}
 SURFACE_PLANES = tuple(_PLANES_OF[CSurface])                                  # the planes of rrt_surface, in its order
@@ -108,6 +114,7 @@ SURFACE_WIDTHS = {n: row[1] for n, row in _PLANES_OF[CSurface].items()}       # 
 AMBIENT_OUTPUTS = tuple(_PLANES_OF[CAmbient])                                 # the planes of rrt_ambient, in its order: [h][w][4] masks, [h][w] pixels
 SHADE_INPUTS = SURFACE_PLANES + ("albedo",)                                   # what rrt_shade_surface reads (lights optional)
 AMBIENT_INPUTS = SURFACE_PLANES[:3]                                           # what rrt_ambient_surface reads
+RAY_SURFACE_PLANES = tuple(_PLANES_OF[CRaySurface])                           # the arrays of rrt_ray_surface, in its order
 
 
 class CModelInfo(C.Structure):
@@ -127,7 +134,7 @@ class CSetupTimes(C.Structure):
 # every struct of include/rrt.h and the class that mirrors it (tests/test_abi.py compares sizes and offsets with what the header's compiler gives)
 STRUCTS = {"rrt_vec3": Vec3, "rrt_light": CLight, "rrt_material": CMaterial, "rrt_texture": CTexture, "rrt_options": COptions, "rrt_camera": CCamera,
            "rrt_region": CRegion, "rrt_visibility": CVisibility, "rrt_pick_result": CPickResult, "rrt_surface": CSurface,
-           "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
+           "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_ray_surface": CRaySurface, "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
 
 # every symbol include/rrt.h declares: (restype, argtypes)
 _P = C.c_void_p
@@ -189,6 +196,8 @@ SYMBOLS = {
     "rrt_get_ray_colours_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P]),
     "rrt_occluded_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P]),
     "rrt_tune_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _u32p]),
+    "rrt_surface_rays": (C.c_int, [_P, C.c_uint32, _dp, _dp, _dp, C.POINTER(CRaySurface)]),
+    "rrt_surface_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.POINTER(CRaySurface), _P]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
@@ -438,6 +447,13 @@ def _device_planes(tensors: dict, names, w: int, h: int) -> dict:
 def _plane_struct(cls, planes: dict):
     """The planes that belong to rrt_visibility / rrt_surface / rrt_ambient `cls`, host arrays or device tensors, by reference; the others stay NULL."""
     return C.byref(cls(**{n: (a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()) for n, a in planes.items() if n in _PLANES_OF[cls]}))
+
+
+def _ray_plane(name: str):
+    """(dtype, elements per ray) of an array of rrt_ray_surface; an unknown name is a ValueError"""
+    if name not in _PLANES_OF[CRaySurface]:
+        raise ValueError(f"surface_rays: unknown plane {name!r}, want names from {RAY_SURFACE_PLANES}")
+    return _PLANES_OF[CRaySurface][name][:2]
 
 
 def _bound(name: str, *args):
@@ -770,6 +786,26 @@ class RayTracer(_Handle):
         v = C.c_uint32(0)
         _call("rrt_tune_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), C.byref(v))
         return int(v.value)
+
+    # the surface record of arbitrary rays (rrt.h: rrt_surface_rays): what surface() gives for the frame's primary rays, for the caller's own, and the next ray
+    def surface_rays(self, origins, dirs, max_t=None, planes=RAY_SURFACE_PLANES) -> dict:
+        """rrt_surface_rays: {name: array} for the names asked for, from RAY_SURFACE_PLANES: hit uint8, t / u / v float64, tri / albedo / material / lights uint32
+        [n]; point / normal / next_origin / next_dir float64 [n][3] (next_*: the reference's reflection ray from the hit).  A ray with a NaN or non-positive
+        max_t is a miss in every array."""
+        o, d, mt = _host_rays(origins, dirs, max_t)
+        n = o.shape[0]
+        out = {name: np.empty((n, width) if width > 1 else (n,), dtype) for name, (dtype, width) in ((name, _ray_plane(name)) for name in planes)}
+        _call("rrt_surface_rays", self._h, n, _d(o), _d(d), _d(mt), _plane_struct(CRaySurface, out))
+        return out
+
+    def surface_rays_into(self, origins_t, dirs_t, out: dict, max_t_t=None, stream: Optional[int] = None):
+        """rrt_surface_rays_device: out = {name: contiguous device tensor} for any subset of RAY_SURFACE_PLANES -- n elements of the array's item size, 3 n for
+        point / normal / next_origin / next_dir; the others are not computed.  Enqueued, not synchronised."""
+        n = _ray_batch(origins_t, dirs_t, max_t_t)
+        for name, t in out.items():
+            dtype, width = _ray_plane(name)
+            _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
+        _call("rrt_surface_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), _plane_struct(CRaySurface, out), _P(_stream(stream)))
 
     # engine.rs:196-253: chunked draw with an update after every chunk (on_update(fb, first_row, n_rows) stands in for canvas.update())
     def render_progressive(self, width: int, height: int, on_update=None, chunk_rows: int = 50) -> np.ndarray:

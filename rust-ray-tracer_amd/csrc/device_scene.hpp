@@ -176,6 +176,16 @@ struct AmbientParams {
 };
 static_assert(sizeof(DevScene) + sizeof(AmbientParams) < 4096, "the arguments of ambient_kernel must fit the 4 KB kernel-argument segment");
 
+// Argument of the per-ray surface kernels (render.hip: surface_rays_kernel; rrt.h: rrt_surface_rays_device): the twelve output arrays of a batch of n rays, in
+// the order and layout of rrt_ray_surface -- [n] each, point / normal / next_origin / next_dir [n][3].  A null array is not written; which are null also decides
+// what the kernel computes at all (no `lights`: no shadow walk).
+struct RaySurfaceParams {
+    uint8_t* hit; double *t, *u, *v; uint32_t *tri, *albedo;
+    double *point, *normal; uint32_t *material, *lights;
+    double *next_origin, *next_dir;
+};
+static_assert(sizeof(RaySurfaceParams) == 96, "RaySurfaceParams mirrors rrt_ray_surface: twelve pointers");
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);
@@ -190,6 +200,8 @@ int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, con
 // (any of the five outputs of launch_intersect may be null: that array is not written)
 // Some/None of the same walk as a shadow query (render.hip: occlusion_kernel): d_occluded[n] = 1 / 0
 int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream, int walk);
+// The full surface record of every ray's first hit and the reference's next ray (render.hip: surface_rays_kernel); any array of q may be null, not all
+int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, void* stream, int walk);
 // Exactness guard for a new eye (scene_build.hip: k_suspects_resident): searches the resident list slots geom[0, n_list_slots) and appends up to
 // RRT_MAX_SUSPECTS + 1 records {push index, suspect} to d_out, counting every find in *d_count (zeroed here, on `stream`).  Not synchronised.
 struct SuspectRecord { uint32_t tri; uint32_t _pad; DevSuspect s; };

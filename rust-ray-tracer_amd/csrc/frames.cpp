@@ -152,7 +152,7 @@ int device_rays_variant(const rrt_raytracer* rt) {
 void check_rays(const rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, bool outputs_ok) {
     if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
     if (n && (!origins || !dirs)) throw Error{RRT_ERR_INVALID_ARG, "null ray origins or directions"};
-    if (n && !outputs_ok) throw Error{RRT_ERR_INVALID_ARG, "null output: a device form needs one output pointer at least, a host form every one of its outputs"};
+    if (n && !outputs_ok) throw Error{RRT_ERR_INVALID_ARG, "null output: a device form and rrt_surface_rays need one output pointer at least, the other host forms every one of their outputs"};
 }
 
 // one frame (or one rank's tiles of it) into a device buffer on the caller's stream, timed by the raytracer's events
@@ -391,30 +391,49 @@ template <class Launch> int device_ray_query(rrt_raytracer* rt, uint32_t n, cons
 }
 // The host forms: rays and the optional max_t up, launch(m, d_origins, d_dirs, d_max_t, d_out, variant) on the null stream (the variant by rays_variant, measured on a
 // first large batch), every output down; blocking.  All of it in ONE device allocation of the call's own: nothing is kept between calls.
+// kEveryOutput: the call wants each of its outputs; kAnyOutput (rrt_surface_rays): one at least -- a null output gets no device memory, d_out[k] is null for the
+// launch and nothing is downloaded for it.
 struct HostOut { void* host; size_t elem; };   // an output array of the caller's and its bytes per ray
+enum OutputRule { kEveryOutput, kAnyOutput };
 template <size_t K, class Launch>
-int host_ray_query(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, const HostOut (&out)[K], Launch&& launch) {
-    bool every_output = true;
-    for (const HostOut& o : out) every_output = every_output && o.host;
-    check_rays(rt, n, origins, dirs, every_output);
+int host_ray_query(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, const HostOut (&out)[K], Launch&& launch,
+                   OutputRule rule = kEveryOutput) {
+    bool every_output = true, any_output = false;
+    for (const HostOut& o : out) { every_output = every_output && o.host; any_output = any_output || o.host; }
+    check_rays(rt, n, origins, dirs, rule == kAnyOutput ? any_output : every_output);
     if (n == 0) return RRT_OK;
     DeviceGuard guard(rt->device);
     const size_t N = n;
     size_t need = 2 * slot_bytes(24 * N) + (max_t ? slot_bytes(8 * N) : 0);
-    for (const HostOut& o : out) need += slot_bytes(o.elem * N);
+    for (const HostOut& o : out) if (o.host) need += slot_bytes(o.elem * N);
     const DevBuf mem = dev_alloc(need);
     DevArena arena{static_cast<char*>(mem.h), need, 0};
     double *d_o = arena.take<double>(3 * N), *d_d = arena.take<double>(3 * N), *d_m = max_t ? arena.take<double>(N) : nullptr;
     void* d_out[K];
-    for (size_t k = 0; k < K; k++) d_out[k] = arena.take<char>(out[k].elem * N);
+    for (size_t k = 0; k < K; k++) d_out[k] = out[k].host ? arena.take<char>(out[k].elem * N) : nullptr;
     HIP_TRY(hipMemcpy(d_o, origins, 24 * N, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_d, dirs, 24 * N, hipMemcpyHostToDevice));
     if (max_t) HIP_TRY(hipMemcpy(d_m, max_t, 8 * N, hipMemcpyHostToDevice));
     const int variant = rays_variant(rt, n, [&](uint32_t m, int v) { return launch(m, d_o, d_d, d_m, d_out, v); });
     timed_launch(rt, nullptr, [&] { return launch(n, d_o, d_d, d_m, d_out, variant); });
     record(rt, n, 1, n, variant);
-    for (size_t k = 0; k < K; k++) HIP_TRY(hipMemcpy(out[k].host, d_out[k], out[k].elem * N, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < K; k++) if (out[k].host) HIP_TRY(hipMemcpy(out[k].host, d_out[k], out[k].elem * N, hipMemcpyDeviceToHost));
     return RRT_OK;
+}
+
+// ---- the surface record of arbitrary rays (rrt.h: rrt_surface_rays).  The twelve arrays of an rrt_ray_surface in its order, as bytes per ray ...
+constexpr size_t kRaySurfaceArrays = 12;
+constexpr size_t kRaySurfaceElem[kRaySurfaceArrays] = {1, 8, 8, 8, 4, 4, 24, 24, 4, 4, 24, 24};
+static_assert(sizeof(rrt_ray_surface) == kRaySurfaceArrays * sizeof(void*) && sizeof(RaySurfaceParams) == sizeof(rrt_ray_surface), "rrt_ray_surface is twelve pointers");
+// ... and as the kernels' argument
+RaySurfaceParams ray_surface_params(const rrt_ray_surface& o) {
+    return RaySurfaceParams{o.hit, o.t, o.u, o.v, o.tri, o.albedo, o.point, o.normal, o.material, o.lights, o.next_origin, o.next_dir};
+}
+// every check of the struct, before any GPU work; true: an array is asked for
+bool ray_surface_wanted(const rrt_raytracer* rt, const rrt_ray_surface* out) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (!out) throw Error{RRT_ERR_INVALID_ARG, "null ray surface struct"};
+    return out->hit || out->t || out->u || out->v || out->tri || out->albedo || out->point || out->normal || out->material || out->lights || out->next_origin || out->next_dir;
 }
 
 }  // namespace
@@ -656,6 +675,29 @@ int rrt_occluded_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_orig
     return guarded([&]() -> int {
         return device_ray_query(rt, n, d_origins, d_dirs, d_occluded != nullptr, stream, [&](int variant) {
             return launch_occlusion(rt->scene, n, d_origins, d_dirs, d_max_t, d_occluded, stream, variant);
+        });
+    });
+}
+
+int rrt_surface_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, const rrt_ray_surface* out) {
+    return guarded([&]() -> int {
+        (void)ray_surface_wanted(rt, out);                                 // (whether one is asked for is host_ray_query's own check: kAnyOutput)
+        void* const host[kRaySurfaceArrays] = {out->hit, out->t, out->u, out->v, out->tri, out->albedo, out->point, out->normal, out->material, out->lights,
+                                               out->next_origin, out->next_dir};
+        HostOut arrays[kRaySurfaceArrays];
+        for (size_t k = 0; k < kRaySurfaceArrays; k++) arrays[k] = HostOut{host[k], kRaySurfaceElem[k]};
+        return host_ray_query(rt, n, origins, dirs, max_t, arrays, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
+            const rrt_ray_surface dev{(uint8_t*)x[0], (double*)x[1], (double*)x[2], (double*)x[3], (uint32_t*)x[4], (uint32_t*)x[5], (double*)x[6], (double*)x[7],
+                                      (uint32_t*)x[8], (uint32_t*)x[9], (double*)x[10], (double*)x[11]};
+            return launch_surface_rays(rt->scene, m, o, d, mt, ray_surface_params(dev), nullptr, variant);
+        }, kAnyOutput);
+    });
+}
+
+int rrt_surface_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const rrt_ray_surface* d_out, void* stream) {
+    return guarded([&]() -> int {
+        return device_ray_query(rt, n, d_origins, d_dirs, ray_surface_wanted(rt, d_out), stream, [&](int variant) {
+            return launch_surface_rays(rt->scene, n, d_origins, d_dirs, d_max_t, ray_surface_params(*d_out), stream, variant);
         });
     });
 }

@@ -34,7 +34,7 @@
 //   -DRRT_TU=1  the bundle-filter frame, visibility, surface, shade and ambient kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
 //   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility, surface, shade and ambient kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
-//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel (default scheduler: max-ILP costs scattered rays 17 %).
+//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel, surface_rays_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
 #ifndef RRT_TU
 #define RRT_TU 0
@@ -1557,6 +1557,43 @@ __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, co
     return c;
 }
 
+// (tangent_frame and surface_of_hit serve the region kernels AND surface_rays_kernel of the per-ray unit, so they stand in front of the per-unit regions)
+// The tangent frame of a normal (raytracer.rs:137-152): tg = normalised(nn x Y), or of nn x Z where that is the zero vector, and bt = normalised(nn x tg).
+__device__ __forceinline__ void tangent_frame(V3 nn, V3& tg, V3& bt) {
+    tg = cross(nn, mk(0.0, 1.0, 0.0));                                                   // raytracer.rs:137-141
+    double len_tg = length(tg);
+    if (len_tg == 0.0) { tg = cross(nn, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }       // raytracer.rs:143-149
+    tg = div3(tg, len_tg);                                                               // raytracer.rs:151 (t.length() again: same value)
+    bt = normalised(cross(nn, tg));                                                      // raytracer.rs:152
+}
+// The attributes of the hit of list slot `slot` at barycentrics (u, v), raytracer.rs:43-57 and get_normal_at_intersection (raytracer.rs:114-162), as trace_colour
+// forms them: the material index, the colour-texture texel 0x00RRGGBB and the shading normal.
+__device__ __forceinline__ void surface_of_hit(const DevScene& S, uint32_t slot, double u, double v, uint32_t& mat, uint32_t& col, V3& n) {
+    const DevTriAttr& A = S.attr[slot];
+    mat = A.mat;
+    const DevMaterial& M = S.mats[mat];
+    const DevTexture T = M.tex_desc;
+    const double w = 1.0 - u - v;                                                        // raytracer.rs:43
+    const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;                        // raytracer.rs:45-47
+    const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;                        // raytracer.rs:48-50
+    const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);           // raytracer.rs:52
+    const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);         // raytracer.rs:53
+    const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);                  // raytracer.rs:55
+    col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
+    V3 nn = (ld3(A.nrm + 3) * u + ld3(A.nrm + 6) * v) + ld3(A.nrm) * w;                  // raytracer.rs:122-124
+    if (M.bump >= 0) {
+        const DevTexture B = M.bump_desc;
+        const uint8_t* bp = B.rgb + 3ull * ((uint64_t)B.width * tyi + txi);              // raytracer.rs:127-128 (colour-texture indices, bump width)
+        V3 bv = mk((double)bp[0], (double)bp[1], (double)bp[2]);
+        bv = normalised(bv);
+        bv = (bv * 2.0) - mk(1.0, 1.0, 1.0);                                             // raytracer.rs:130-135
+        V3 tg, bt;
+        tangent_frame(nn, tg, bt);
+        nn = mk(dot(bv, tg), dot(bv, bt), dot(bv, nn));                                  // raytracer.rs:154-158
+    }
+    n = normalised(nn);                                                                  // raytracer.rs:161
+}
+
 // ------------------------------------------------------------------------------------------------ kernels
 // One wave per workgroup; workgroup b renders quadrant (b & 3) of this rank's local tile (b >> 2).
 // Waves per SIMD (register budget) per traversal variant, measured on MI355X with the code-generation switches of the Makefile: 4 everywhere
@@ -1677,42 +1714,6 @@ __device__ __forceinline__ V3 primary_direction(const FrameParams& F, uint32_t p
               (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
               (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
 }
-// The tangent frame of a normal (raytracer.rs:137-152): tg = normalised(nn x Y), or of nn x Z where that is the zero vector, and bt = normalised(nn x tg).
-__device__ __forceinline__ void tangent_frame(V3 nn, V3& tg, V3& bt) {
-    tg = cross(nn, mk(0.0, 1.0, 0.0));                                                   // raytracer.rs:137-141
-    double len_tg = length(tg);
-    if (len_tg == 0.0) { tg = cross(nn, mk(0.0, 0.0, 1.0)); len_tg = length(tg); }       // raytracer.rs:143-149
-    tg = div3(tg, len_tg);                                                               // raytracer.rs:151 (t.length() again: same value)
-    bt = normalised(cross(nn, tg));                                                      // raytracer.rs:152
-}
-// The attributes of the hit of list slot `slot` at barycentrics (u, v), raytracer.rs:43-57 and get_normal_at_intersection (raytracer.rs:114-162), as trace_colour
-// forms them: the material index, the colour-texture texel 0x00RRGGBB and the shading normal.
-__device__ __forceinline__ void surface_of_hit(const DevScene& S, uint32_t slot, double u, double v, uint32_t& mat, uint32_t& col, V3& n) {
-    const DevTriAttr& A = S.attr[slot];
-    mat = A.mat;
-    const DevMaterial& M = S.mats[mat];
-    const DevTexture T = M.tex_desc;
-    const double w = 1.0 - u - v;                                                        // raytracer.rs:43
-    const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;                        // raytracer.rs:45-47
-    const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;                        // raytracer.rs:48-50
-    const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);           // raytracer.rs:52
-    const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);         // raytracer.rs:53
-    const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);                  // raytracer.rs:55
-    col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
-    V3 nn = (ld3(A.nrm + 3) * u + ld3(A.nrm + 6) * v) + ld3(A.nrm) * w;                  // raytracer.rs:122-124
-    if (M.bump >= 0) {
-        const DevTexture B = M.bump_desc;
-        const uint8_t* bp = B.rgb + 3ull * ((uint64_t)B.width * tyi + txi);              // raytracer.rs:127-128 (colour-texture indices, bump width)
-        V3 bv = mk((double)bp[0], (double)bp[1], (double)bp[2]);
-        bv = normalised(bv);
-        bv = (bv * 2.0) - mk(1.0, 1.0, 1.0);                                             // raytracer.rs:130-135
-        V3 tg, bt;
-        tangent_frame(nn, tg, bt);
-        nn = mk(dot(bv, tg), dot(bv, bt), dot(bv, nn));                                  // raytracer.rs:154-158
-    }
-    n = normalised(nn);                                                                  // raytracer.rs:161
-}
-
 // Visibility buffers (rrt.h: rrt_render_visibility_device): the first hit of every primary ray of a region of the frame -- hit, t, u, v, triangle and the
 // colour-texture texel -- instead of a colour.  The waves, their rays and their guard are render_kernel's; each ray is walked once, as intersect_kernel
 // walks it, but from the one origin (one_origin: the bundle and the parked origin are the frame kernels').  A wave covers the tile quadrant its block index
@@ -2142,6 +2143,96 @@ __global__ __launch_bounds__(64) void occlusion_kernel(const DevScene S, uint32_
 #endif
     if (ok) occluded[i] = slot != kNone ? 1 : 0;
 }
+
+// The full surface record of an arbitrary ray's first hit and the reference's next ray from there (rrt.h: rrt_surface_rays_device): surface_kernel's loop behind
+// the front end of the per-ray kernels.  ONE call site of the walk.  The first turn walks the caller's rays with intersect_kernel's arguments (closest hit, its
+// guard, not one_origin); every later turn walks the shadow rays of all hit lanes towards ONE point light with the arguments surface_kernel gives a shadow walk
+// (any_ok, filters on, not one_origin; the rays of a turn end at one light, so the bundle's anchor is the frame kernels': the far ends).  Which turn it is, and
+// which light, is wave-uniform: the lights are kernel arguments.  Every point light is walked, also those behind the reference's `break` (raytracer.rs:235-237).
+// A ray whose bound is NaN or not positive is a miss of intersect_kernel's walk whatever the scene holds; it takes part in no walk here.
+// The twelve output pointers are kernel arguments, so each test on them is wave-uniform: no `lights`: no shadow walk; none of albedo, normal, material, lights,
+// next_origin, next_dir: no attribute load; none of those nor u nor v: no second Moller-Trumbore.  A wave without a hit leaves the loop after the first turn.
+// No lane leaves before the last walk: the walks need the whole wave in uniform control flow.
+// Four waves per SIMD like the frame kernels, unlike the other per-ray kernels: uncapped it takes 134-149 VGPRs and runs at 3 waves; capped it spills 16-38 VGPRs
+// (36-92 B of scratch) and is 5-18 % faster on 11 of the 12 measured cases (profiles/ray_surface_kernel_resources.txt, profiles/ray_surface.json).
+template <int kWalk>
+__global__ __launch_bounds__(64, kWavesPerSimd) void surface_rays_kernel(const DevScene S, uint32_t n_rays, const double* __restrict__ origins, const double* __restrict__ dirs,
+                                                          const double* __restrict__ max_t, const RaySurfaceParams Q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const Stack stk{lds + kParkBytes, threadIdx.x};
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    const bool ok = i < n_rays;
+    const V3 o = ok ? ld3(origins + 3 * (size_t)i) : mk(0, 0, 0), d = ok ? ld3(dirs + 3 * (size_t)i) : mk(0, 0, 1);
+    const double mt = (ok && max_t) ? max_t[i] : kInf;
+    const bool alive = ok && mt > 0.0;                                                 // (false for a NaN bound too)
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const bool first_ok = !origin_ray_in_suspect_plane(S, o, d);                       // exactness guard of the first walk (intersect_kernel)
+    const bool want_attr = Q.albedo || Q.normal || Q.material || Q.lights || Q.next_origin || Q.next_dir;
+    const bool want_uv = Q.u || Q.v || want_attr;
+    const uint32_t n_lights = Q.lights ? S.n_lights : 0u;                              // no lights array: no shadow walk
+    bool found = false;
+    bool shadow = false;                                                               // wave-uniform: the walk about to start is a shadow walk, towards light li
+    uint32_t li = 0;
+    double t = 0, u = 0, v = 0;
+    uint32_t tri = kNone, mat = kNone, mask = 0, col = 0x00FFFFFFu;                    // WHITE, raytracer.rs:109-111
+    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
+    V3 ro = o, rd = d; double rmax = mt;
+    for (;;) {
+        double wt; uint32_t wslot;
+        const bool active = shadow ? found : alive;
+        if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, active, shadow, shadow || first_ok, ro, rd, rmax, wt, wslot);
+        else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, active, shadow, shadow || first_ok, false, ro, rd, rmax, wt, wslot);
+        if (!shadow) {
+            shadow = true;
+            found = alive && wslot != kNone;
+            if (found) {
+                // --- hit: raytracer.rs:39-57
+                t = wt;
+                p = o + d * wt;                                                          // raytracer.rs:39
+                if (Q.tri) tri = S.attr[wslot].orig;
+                if (want_uv) { double t2; mt_full(S.geom + wslot, o, d, t2, u, v); }
+                if (want_attr) surface_of_hit(S, wslot, u, v, mat, col, n);
+            }
+            if (!__any(found)) break;                                                    // no hit in the wave: nothing to ask the lights
+        } else {
+            if (found && wslot == kNone) mask |= 1u << li;                               // triangle_exists_between_points says "lit" for None, raytracer.rs:181-187
+            li++;
+        }
+        // the light list up to the next point light (raytracer.rs:205-255): Ambient and Directional lights reach every hit
+        while (li < n_lights && S.lights[li].kind != 1u) { if (found) mask |= 1u << li; li++; }
+        if (li >= n_lights) break;
+        const V3 dir = ld3(S.lights[li].v) - p;                                          // the shadow ray, raytracer.rs:164-188, as trace_colour forms it
+        ro = p + n * S.surface_offset;
+        rd = dir;
+        rmax = length(dir);
+    }
+#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
+    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
+#endif
+    if (!ok) return;
+    if (Q.hit) Q.hit[i] = found ? 1 : 0;
+    if (Q.t) Q.t[i] = t;
+    if (Q.u) Q.u[i] = u;
+    if (Q.v) Q.v[i] = v;
+    if (Q.tri) Q.tri[i] = tri;
+    if (Q.albedo) Q.albedo[i] = col;
+    const size_t j = 3 * (size_t)i;
+    if (Q.point) { Q.point[j] = p.x; Q.point[j + 1] = p.y; Q.point[j + 2] = p.z; }
+    if (Q.normal) { Q.normal[j] = n.x; Q.normal[j + 1] = n.y; Q.normal[j + 2] = n.z; }
+    if (Q.material) Q.material[i] = mat;
+    if (Q.lights) Q.lights[i] = mask;
+    if (Q.next_origin) {
+        const V3 q = found ? p + n * S.surface_offset : mk(0, 0, 0);                     // raytracer.rs:82
+        Q.next_origin[j] = q.x; Q.next_origin[j + 1] = q.y; Q.next_origin[j + 2] = q.z;
+    }
+    if (Q.next_dir) {
+        V3 r = mk(0, 0, 0);
+        if (found) { const double d_dot_n = dot(d, n); r = normalised(d - (n * 2.0) * d_dot_n); }   // raytracer.rs:78-79, as trace_colour forms it
+        Q.next_dir[j] = r.x; Q.next_dir[j + 1] = r.y; Q.next_dir[j + 2] = r.z;
+    }
+}
 #endif   // RRT_TU_RAYS
 
 // ---- host side of the launchers below: a runtime choice of kernel as a compile-time one.  f receives a std::integral_constant and names its instantiation.
@@ -2313,6 +2404,14 @@ int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, con
     if (n == 0) return 0;
     return with_walk(effective_walk(s, walk), [&](auto w) {
         hipLaunchKernelGGL(occlusion_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
+        return (int)hipGetLastError();
+    });
+}
+
+int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, void* stream, int walk) {
+    if (n == 0) return 0;
+    return with_walk(effective_walk(s, walk), [&](auto w) {
+        hipLaunchKernelGGL(surface_rays_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, q);
         return (int)hipGetLastError();
     });
 }
