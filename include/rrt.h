@@ -542,6 +542,58 @@ int rrt_surface_rays(rrt_raytracer *rt, uint32_t n, const double *origins, const
 int rrt_surface_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_origins, const double *d_dirs, const double *d_max_t,
                             const rrt_ray_surface *d_out, void *stream);
 
+/* Shading of arbitrary rays from kept records: finishes the rays of a batch from the records rrt_surface_rays* wrote for them, with the lights and materials in
+ * force NOW, without walking the rays again -- what rrt_shade_surface does for a frame's primary rays, for the caller's own.  For relighting and material edits of
+ * the G-buffers of what a mirror shows, of probes and bake points that are not the eye, and for an integrator that keeps its rays on the GPU and follows a
+ * reflection chain level by level with rrt_surface_rays_device: `local` and `kr` are what a level of get_ray_colour_recursive mixes the level below into
+ * (raytracer.rs:89-101).
+ * rec / d_rec is the struct the caller gave rrt_surface_rays[_device] for these n rays, in that layout.  READ: albedo, point, normal, material -- all four required
+ * -- and lights, which may be NULL.  The other seven pointers are ignored.  dirs / d_dirs, [n][3], required: the rays' directions, the segment direction that
+ * compute_lighting_intensity (as v = -d) and the reflection ray use.  Origins are not needed: the point is stored.
+ * depth: the recursion depth of get_ray_colour_recursive at which the batch stands, one value for all rays: 0 for rays a caller would hand rrt_get_ray_colours,
+ * k for the rays of level k of a chain.  Any value is valid; depth >= max_reflection_depth means direct lighting only.
+ * WRITTEN, per ray i; any of the three pointers may be NULL (that array is not written), at least one is set:
+ *   material[i] >= n_mats (0xFFFFFFFF, a miss or a dead ray, included): colour = 0x00FFFFFF, the reference's background (raytracer.rs:109-111), local = (0.0, 0.0, 0.0),
+ *            kr = 0.0 -- the rule of rrt_shade_surface; no table is read out of bounds whatever the arrays hold, no value of them is used as an index, and only the
+ *            low 24 bits of albedo count.  Otherwise the record is the hit of a segment standing at `depth`, as the reference holds it after
+ *            get_normal_at_intersection.  With `lights`, the lights the segment's sum adds up are [0, min(ctz(~mask), n_lights)) and no shadow ray of this hit is
+ *            walked; with `lights` NULL its shadow rays are formed and walked as a frame walks them, the `break` at the first occluded point light
+ *            (raytracer.rs:235-237) included;
+ *   local  = the f64 `local` colour of raytracer.rs:67-71 -- the albedo's channels times compute_lighting_intensity -- unquantised;
+ *   kr     = the material's kr where the reference reflects at this hit (kr > 0 and depth < max_reflection_depth, raytracer.rs:76), else 0.0;
+ *   colour = the reference's result for this segment, 0x00RRGGBB.  Where kr == 0.0: local, each channel clamped to [0, 255] and truncated.  Where kr > 0.0 the
+ *            reflection chain is traced from point + normal * surface_offset along normalised(d - (normal * 2.0) * dot(d, normal)) up to max_reflection_depth,
+ *            its shadow rays always walked, every level of the unwind quantised to u8 (raytracer.rs:85-101), exactly as rrt_shade_surface does from depth 0.
+ * What is not asked for is not computed: with colour NULL no reflection ray is formed or walked; with colour NULL and `lights` given the launch walks nothing at
+ * all.  With a mask, a wave of 64 consecutive rays none of which hits a mirror walks nothing either.
+ * CONTRACT.  If the records are those rrt_surface_rays* wrote for the rays (o, d) in this scene, colour with depth = 0 is what rrt_get_ray_colours returns for
+ * (o, d) with the lights and materials in force now, bit for bit.  Keeping the records valid is the caller's business:
+ *
+ *   change since the records were written                                             arrays that are stale
+ *   rrt_raytracer_set_triangles[_device]                                              all
+ *   set_lights: position of a Point light, kind or index of any light, list length    `lights` only (pass it as NULL)
+ *   set_lights: intensities, or the vector of an Ambient or Directional light         none
+ *   set_materials: `tex` of a material                                                `albedo`, `normal` (the bump texel is read at the colour texture's indices)
+ *   set_materials: `bump`                                                             `normal`
+ *   set_materials: ka, kd, ks, ns, kr                                                 none
+ *   rrt_raytracer_set_camera                                                          none: the rays are the caller's
+ *
+ * Exactness: every walk of this call is a secondary walk of a frame -- default mode, not guarded, the band documented under RRT_FLAG_NO_CULL.
+ * A non-finite direction, point or normal gives unspecified values for that ray, and no fault.  Inputs and outputs must not overlap.
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer and the outputs as they were: NULL rt; NULL rec or out; all three outputs NULL with n > 0;
+ * NULL dirs or a NULL required array with n > 0.  n = 0 is RRT_OK with nothing enqueued.
+ * rrt_last_stats afterwards: as after the other per-ray calls (width = n, height = 1, rays_primary = n; shadow and reflection rays are not counted).
+ * rrt_shade_rays_device: arrays in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default): no allocation, no copy, no synchronisation and
+ * no measurement; the traversal variant by the rule of rrt_intersect_rays_device.
+ * rrt_shade_rays: arrays in host memory; blocking.  One device allocation of the call's own; dirs and the four or five arrays it reads are uploaded, only the
+ * requested outputs downloaded.  It never measures the variants -- it has no origins to measure a walk on -- and picks its variant by the device form's rule.
+ * rrt_raytracer_set_lights, set_materials and set_triangles[_device] apply to every call made after they return.
+ * Not covered: per-ray depths, an ambient-occlusion call for ray records, the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+typedef struct { uint32_t *colour; double *local; double *kr; } rrt_ray_shade;   /* 24 bytes; colour [n], local [n][3], kr [n] */
+int rrt_shade_rays(rrt_raytracer *rt, uint32_t n, const double *dirs, const rrt_ray_surface *rec, uint32_t depth, const rrt_ray_shade *out);
+int rrt_shade_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_dirs, const rrt_ray_surface *d_rec, uint32_t depth, const rrt_ray_shade *d_out,
+                          void *stream);
+
 /* The octree of a raytracer whose set-up ran on the GPU (the default), read back from its device: same layout as rrt_model_get_octree; info (may be
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */
 int rrt_raytracer_get_octree(const rrt_raytracer *rt, rrt_model_info *info, double *aabb, uint32_t *first_child, uint32_t *tri_count,

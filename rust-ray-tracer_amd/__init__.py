@@ -93,6 +93,10 @@ class CRaySurface(C.Structure):      # rrt_ray_surface, 96 bytes: host or device
     _fields_ = [(n, C.c_void_p) for n in ("hit", "t", "u", "v", "tri", "albedo", "point", "normal", "material", "lights", "next_origin", "next_dir")]
 
 
+class CRayShade(C.Structure):        # rrt_ray_shade, 24 bytes: host or device pointers, NULL = array not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("colour", "local", "kr")]
+
+
 MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
 
 # The plane table: every plane of rrt_visibility, rrt_surface and rrt_ambient, in the struct's order, as (dtype, elements per sub-sample, True = one value per
@@ -115,6 +119,10 @@ AMBIENT_OUTPUTS = tuple(_PLANES_OF[CAmbient])                                 # 
 SHADE_INPUTS = SURFACE_PLANES + ("albedo",)                                   # what rrt_shade_surface reads (lights optional)
 AMBIENT_INPUTS = SURFACE_PLANES[:3]                                           # what rrt_ambient_surface reads
 RAY_SURFACE_PLANES = tuple(_PLANES_OF[CRaySurface])                           # the arrays of rrt_ray_surface, in its order
+# rrt_ray_shade: per RAY the colour, the unquantised local colour and the kr of the hit its record holds
+_PLANES_OF[CRayShade] = dict(colour=(np.uint32, 1, True), local=(np.float64, 3, True), kr=(np.float64, 1, True))
+RAY_SHADE_OUTPUTS = tuple(_PLANES_OF[CRayShade])                              # the arrays of rrt_ray_shade, in its order
+RAY_SHADE_INPUTS = SHADE_INPUTS                                               # what rrt_shade_rays reads of an rrt_ray_surface (lights optional)
 
 
 class CModelInfo(C.Structure):
@@ -134,7 +142,7 @@ class CSetupTimes(C.Structure):
 # every struct of include/rrt.h and the class that mirrors it (tests/test_abi.py compares sizes and offsets with what the header's compiler gives)
 STRUCTS = {"rrt_vec3": Vec3, "rrt_light": CLight, "rrt_material": CMaterial, "rrt_texture": CTexture, "rrt_options": COptions, "rrt_camera": CCamera,
            "rrt_region": CRegion, "rrt_visibility": CVisibility, "rrt_pick_result": CPickResult, "rrt_surface": CSurface,
-           "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_ray_surface": CRaySurface, "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
+           "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_ray_surface": CRaySurface, "rrt_ray_shade": CRayShade, "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
 
 # every symbol include/rrt.h declares: (restype, argtypes)
 _P = C.c_void_p
@@ -198,6 +206,8 @@ SYMBOLS = {
     "rrt_tune_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _u32p]),
     "rrt_surface_rays": (C.c_int, [_P, C.c_uint32, _dp, _dp, _dp, C.POINTER(CRaySurface)]),
     "rrt_surface_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.POINTER(CRaySurface), _P]),
+    "rrt_shade_rays": (C.c_int, [_P, C.c_uint32, _dp, C.POINTER(CRaySurface), C.c_uint32, C.POINTER(CRayShade)]),
+    "rrt_shade_rays_device": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(CRaySurface), C.c_uint32, C.POINTER(CRayShade), _P]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
@@ -449,11 +459,18 @@ def _plane_struct(cls, planes: dict):
     return C.byref(cls(**{n: (a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()) for n, a in planes.items() if n in _PLANES_OF[cls]}))
 
 
-def _ray_plane(name: str):
-    """(dtype, elements per ray) of an array of rrt_ray_surface; an unknown name is a ValueError"""
-    if name not in _PLANES_OF[CRaySurface]:
-        raise ValueError(f"surface_rays: unknown plane {name!r}, want names from {RAY_SURFACE_PLANES}")
-    return _PLANES_OF[CRaySurface][name][:2]
+def _ray_plane(name: str, cls=CRaySurface, what: str = "surface_rays"):
+    """(dtype, elements per ray) of an array of rrt_ray_surface, or of rrt_ray_shade `cls`; an unknown name is a ValueError"""
+    if name not in _PLANES_OF[cls]:
+        raise ValueError(f"{what}: unknown {'plane' if cls is CRaySurface else 'output'} {name!r}, want names from {tuple(_PLANES_OF[cls])}")
+    return _PLANES_OF[cls][name][:2]
+
+
+def _ray_records(what: str, planes: dict) -> dict:
+    """The arrays of an rrt_ray_surface that rrt_shade_rays reads, of the caller's `planes` (host arrays or device tensors): {name: (array, dtype, elements per
+    ray)}.  Every name must be one of RAY_SURFACE_PLANES (ValueError otherwise); None and the arrays the call ignores are left out (NULL for the library)."""
+    rows = {name: (a,) + _ray_plane(name, what=what) for name, a in planes.items()}
+    return {name: row for name, row in rows.items() if row[0] is not None and name in RAY_SHADE_INPUTS}
 
 
 def _bound(name: str, *args):
@@ -806,6 +823,36 @@ class RayTracer(_Handle):
             dtype, width = _ray_plane(name)
             _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
         _call("rrt_surface_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), _plane_struct(CRaySurface, out), _P(_stream(stream)))
+
+    # shading of arbitrary rays from kept records (rrt.h: rrt_shade_rays): what shade() does for a frame's planes, for the arrays surface_rays wrote
+    def shade_rays(self, dirs, planes: dict, depth: int = 0, outputs=("colour",)) -> dict:
+        """rrt_shade_rays: {name: array} for the names asked for, from RAY_SHADE_OUTPUTS -- colour uint32 [n] 0x00RRGGBB, local float64 [n][3] (the unquantised
+        local colour), kr float64 [n] -- of the rays with the directions `dirs` whose records `planes` holds ({name: array} as surface_rays returns it: albedo,
+        point, normal and material are read, lights if it is there; the others are ignored), with the lights and materials in force now.  depth: the recursion
+        depth at which the batch stands.  With depth 0 and the records surface_rays wrote for (origins, dirs), colour is get_ray_colours(origins, dirs)."""
+        d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+        n = d.shape[0]
+        rec = {name: np.ascontiguousarray(a, dtype) for name, (a, dtype, width) in _ray_records("shade_rays", planes).items()}
+        for name, a in rec.items():
+            assert a.size == n * _ray_plane(name)[1], f"shade_rays: array {name} has {a.size} elements for {n} rays"
+        out = {name: np.empty((n, width) if width > 1 else (n,), dtype) for name, (dtype, width) in ((name, _ray_plane(name, CRayShade, "shade_rays")) for name in outputs)}
+        _call("rrt_shade_rays", self._h, n, _d(d), _plane_struct(CRaySurface, rec), int(depth), _plane_struct(CRayShade, out))
+        return out
+
+    def shade_rays_into(self, out: dict, dirs_t, planes: dict, depth: int = 0, stream: Optional[int] = None):
+        """rrt_shade_rays_device: out = {name: contiguous device tensor} for any subset of RAY_SHADE_OUTPUTS (n four-byte elements, 3 n and n float64; the others
+        are not computed -- without colour no reflection ray is walked); dirs_t float64 of 3 n elements; planes = {name: device tensor} as surface_rays_into
+        filled them (albedo, point, normal, material, and lights or not).  Enqueued, not synchronised."""
+        n = _batch_size(dirs_t, 3, "dirs")
+        _device_tensor(dirs_t, 3 * n, 8, "dirs")
+        rec = _ray_records("shade_rays_into", planes)
+        for name, (t, dtype, width) in rec.items():
+            _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
+        for name, t in out.items():
+            dtype, width = _ray_plane(name, CRayShade, "shade_rays_into")
+            _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
+        _call("rrt_shade_rays_device", self._h, n, _ptr(dirs_t), _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), int(depth),
+              _plane_struct(CRayShade, out), _P(_stream(stream)))
 
     # engine.rs:196-253: chunked draw with an update after every chunk (on_update(fb, first_row, n_rows) stands in for canvas.update())
     def render_progressive(self, width: int, height: int, on_update=None, chunk_rows: int = 50) -> np.ndarray:

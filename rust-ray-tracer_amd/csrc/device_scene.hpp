@@ -186,6 +186,16 @@ struct RaySurfaceParams {
 };
 static_assert(sizeof(RaySurfaceParams) == 96, "RaySurfaceParams mirrors rrt_ray_surface: twelve pointers");
 
+// Argument of the per-ray shade kernels (render.hip: shade_rays_kernel; rrt.h: rrt_shade_rays_device): the six arrays the kernel READS -- the rays' directions and
+// the records the per-ray surface launch wrote for them, [n] each, dirs / point / normal [n][3]; `lights` may be null: the shadow rays of the records' hits are
+// then walked -- the three it writes (colour [n], local [n][3], kr [n]; any may be null, not all: a null array is not written, and a null `colour` also means
+// that no reflection ray is formed) and the recursion depth at which the batch stands.
+struct ShadeRaysParams {
+    const double *dirs, *point, *normal; const uint32_t *material, *albedo, *lights;
+    uint32_t* colour; double *local, *kr;
+    uint32_t depth, _pad;
+};
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);
@@ -202,6 +212,8 @@ int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, con
 int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream, int walk);
 // The full surface record of every ray's first hit and the reference's next ray (render.hip: surface_rays_kernel); any array of q may be null, not all
 int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, void* stream, int walk);
+// The colour, the unquantised local colour and the kr of every ray from its kept record (render.hip: shade_rays_kernel); any output of q may be null, not all
+int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, void* stream, int walk);
 // Exactness guard for a new eye (scene_build.hip: k_suspects_resident): searches the resident list slots geom[0, n_list_slots) and appends up to
 // RRT_MAX_SUSPECTS + 1 records {push index, suspect} to d_out, counting every find in *d_count (zeroed here, on `stream`).  Not synchronised.
 struct SuspectRecord { uint32_t tri; uint32_t _pad; DevSuspect s; };

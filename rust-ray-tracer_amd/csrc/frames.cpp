@@ -5,7 +5,7 @@
 // Every launch goes through ONE seam: timed_launch (the raytracer's two events around it) and record (what it traced, into rrt_stats).  Every measurement of the
 // variants goes through fastest_variant.  The region calls share one check of the region (region_in_force), one launch (launch_region_frame) and, for their host
 // forms, one routine that carves the kept device allocation and copies the planes up and down (with_kept_planes).  The host forms of the per-ray queries make one
-// allocation per call.
+// allocation per call (host_ray_query; shade_rays_from_host for the one call that takes records instead of origins).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -380,14 +380,18 @@ void ambient_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const
 }
 
 // ---- per-ray queries.  The device forms (rrt.h: rrt_intersect_rays_device, ...): no allocation, no copy, no synchronisation; launch(variant) on the caller's stream.
-template <class Launch> int device_ray_query(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, bool any_output, void* stream, Launch&& launch) {
-    check_rays(rt, n, d_origins, d_dirs, any_output);
+// (device_ray_launch: the same for a call that has made its own checks -- rrt_shade_rays_device has no origins for check_rays)
+template <class Launch> int device_ray_launch(rrt_raytracer* rt, uint32_t n, void* stream, Launch&& launch) {
     if (n == 0) return RRT_OK;
     DeviceGuard guard(rt->device);
     const int variant = device_rays_variant(rt);
     timed_launch(rt, stream, [&] { return launch(variant); });
     record(rt, n, 1, n, variant);
     return RRT_OK;
+}
+template <class Launch> int device_ray_query(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, bool any_output, void* stream, Launch&& launch) {
+    check_rays(rt, n, d_origins, d_dirs, any_output);
+    return device_ray_launch(rt, n, stream, launch);
 }
 // The host forms: rays and the optional max_t up, launch(m, d_origins, d_dirs, d_max_t, d_out, variant) on the null stream (the variant by rays_variant, measured on a
 // first large batch), every output down; blocking.  All of it in ONE device allocation of the call's own: nothing is kept between calls.
@@ -434,6 +438,43 @@ bool ray_surface_wanted(const rrt_raytracer* rt, const rrt_ray_surface* out) {
     if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
     if (!out) throw Error{RRT_ERR_INVALID_ARG, "null ray surface struct"};
     return out->hit || out->t || out->u || out->v || out->tri || out->albedo || out->point || out->normal || out->material || out->lights || out->next_origin || out->next_dir;
+}
+
+// ---- shading of arbitrary rays from kept records (rrt.h: rrt_shade_rays).  every check, before any GPU work; n == 0 is a no-op for valid handles and structs
+void check_shade_rays(const rrt_raytracer* rt, uint32_t n, const double* dirs, const rrt_ray_surface* rec, const rrt_ray_shade* out) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (!rec || !out) throw Error{RRT_ERR_INVALID_ARG, "null struct: shading rays reads the ray surface struct and writes the ray shade struct"};
+    if (n && !out->colour && !out->local && !out->kr) throw Error{RRT_ERR_INVALID_ARG, "no output requested: colour, local and kr are all null"};
+    if (n && !dirs) throw Error{RRT_ERR_INVALID_ARG, "null ray directions"};
+    if (n && (!rec->albedo || !rec->point || !rec->normal || !rec->material)) throw Error{RRT_ERR_INVALID_ARG, "null array: albedo, point, normal and material are all required"};
+}
+// the kernels' argument from arrays in device memory
+ShadeRaysParams shade_rays_params(const double* d_dirs, const rrt_ray_surface& d_rec, uint32_t depth, const rrt_ray_shade& d_out) {
+    return ShadeRaysParams{d_dirs, d_rec.point, d_rec.normal, d_rec.material, d_rec.albedo, d_rec.lights, d_out.colour, d_out.local, d_out.kr, depth, 0u};
+}
+// Host form (checked), host_ray_query's sibling for a call without origins: the directions and the four or five arrays it reads up, one launch on the null stream
+// in the variant of the device forms -- nothing is measured: there are no origins to measure a walk on -- the requested outputs down; blocking.  All of it in ONE
+// device allocation of the call's own.
+int shade_rays_from_host(rrt_raytracer* rt, uint32_t n, const double* dirs, const rrt_ray_surface& rec, uint32_t depth, const rrt_ray_shade& out) {
+    if (n == 0) return RRT_OK;
+    DeviceGuard guard(rt->device);
+    const size_t N = n;
+    HostPlane pl[] = {plane_up(dirs, 24, N), plane_up(rec.point, 24, N), plane_up(rec.normal, 24, N), plane_up(rec.material, 4, N), plane_up(rec.albedo, 4, N),
+                      plane_up(rec.lights, 4, N), plane_down(out.colour, 4, N), plane_down(out.local, 24, N), plane_down(out.kr, 8, N)};
+    size_t need = 0;
+    for (const HostPlane& p : pl) if (p.host) need += slot_bytes(p.bytes());
+    const DevBuf mem = dev_alloc(need);
+    DevArena arena{static_cast<char*>(mem.h), need, 0};
+    for (HostPlane& p : pl) if (p.host) p.dev = arena.take<char>(p.bytes());
+    for (const HostPlane& p : pl) if (p.host && (p.dir & kUp)) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
+    rrt_ray_surface d_rec{};
+    d_rec.point = (double*)pl[1].dev; d_rec.normal = (double*)pl[2].dev; d_rec.material = (uint32_t*)pl[3].dev; d_rec.albedo = (uint32_t*)pl[4].dev; d_rec.lights = (uint32_t*)pl[5].dev;
+    const ShadeRaysParams q = shade_rays_params((const double*)pl[0].dev, d_rec, depth, rrt_ray_shade{(uint32_t*)pl[6].dev, (double*)pl[7].dev, (double*)pl[8].dev});
+    const int variant = device_rays_variant(rt);
+    timed_launch(rt, nullptr, [&] { return launch_shade_rays(rt->scene, n, q, nullptr, variant); });
+    record(rt, n, 1, n, variant);
+    for (const HostPlane& p : pl) if (p.host && (p.dir & kDown)) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
+    return RRT_OK;
 }
 
 }  // namespace
@@ -698,6 +739,22 @@ int rrt_surface_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origi
     return guarded([&]() -> int {
         return device_ray_query(rt, n, d_origins, d_dirs, ray_surface_wanted(rt, d_out), stream, [&](int variant) {
             return launch_surface_rays(rt->scene, n, d_origins, d_dirs, d_max_t, ray_surface_params(*d_out), stream, variant);
+        });
+    });
+}
+
+int rrt_shade_rays(rrt_raytracer* rt, uint32_t n, const double* dirs, const rrt_ray_surface* rec, uint32_t depth, const rrt_ray_shade* out) {
+    return guarded([&]() -> int {
+        check_shade_rays(rt, n, dirs, rec, out);
+        return shade_rays_from_host(rt, n, dirs, *rec, depth, *out);
+    });
+}
+
+int rrt_shade_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_dirs, const rrt_ray_surface* d_rec, uint32_t depth, const rrt_ray_shade* d_out, void* stream) {
+    return guarded([&]() -> int {
+        check_shade_rays(rt, n, d_dirs, d_rec, d_out);
+        return device_ray_launch(rt, n, stream, [&](int variant) {
+            return launch_shade_rays(rt->scene, n, shade_rays_params(d_dirs, *d_rec, depth, *d_out), stream, variant);
         });
     });
 }

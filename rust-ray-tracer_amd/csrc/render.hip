@@ -34,7 +34,7 @@
 //   -DRRT_TU=1  the bundle-filter frame, visibility, surface, shade and ambient kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
 //   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility, surface, shade and ambient kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
-//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel, surface_rays_kernel (default scheduler: max-ILP costs scattered rays 17 %).
+//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel, surface_rays_kernel, shade_rays_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
 #ifndef RRT_TU
 #define RRT_TU 0
@@ -2233,6 +2233,156 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_rays_kernel(const D
         Q.next_dir[j] = r.x; Q.next_dir[j + 1] = r.y; Q.next_dir[j + 2] = r.z;
     }
 }
+
+// Shading of arbitrary rays from kept records (rrt.h: rrt_shade_rays_device): shade_kernel's state machine behind the front end of the per-ray kernels.  A ray
+// starts as the hit its record holds -- point, normal, material, the low 24 bits of albedo, and the caller's direction as the segment direction -- of a segment of
+// get_ray_colour_recursive that stands at recursion depth Q.depth, with the lights and materials in force NOW.  A turn SHADES first and WALKS second, as in
+// shade_kernel: a wave none of whose lanes has a ray in flight -- matte hits with a mask, dead rays -- leaves without calling the walk.  ONE call site of the walk
+// with shade_kernel's arguments: every ray is a secondary ray (filters on, not one_origin, any_ok for a shadow ray).
+// What the batch's first level yields is kept in slot 0 of the stack: `local`, the unquantised colour of raytracer.rs:67-71, and `kr`, the material's where the
+// reference reflects there (kr > 0 and Q.depth below max_reflection_depth), else 0.0.  Slots are indexed by level - Q.depth; `room` levels may still reflect, so a
+// Q.depth at or beyond max_reflection_depth gives direct lighting only, whatever its value.
+// The pointers and Q.depth are kernel arguments, so each test on them is wave-uniform: with a mask no shadow ray of the record's hit is formed; without `colour` no
+// reflection ray is formed, and with both no lane ever has a ray in flight: the walk is not called.
+// A material index at or beyond the table (0xFFFFFFFF: a miss or a dead ray) is WHITE, (0, 0, 0) and 0.0; no value of the caller's arrays is used as an index.
+// Lanes beyond the batch are dead rays that store nothing; no lane leaves before the last walk, the stores come after the loop.
+// Four waves per SIMD like surface_rays_kernel, unlike ray_colour_kernel: uncapped it takes 143-159 VGPRs and runs at 3 waves; capped it spills 0 / 2 / 29 VGPRs
+// (bundle / lane / ray walk) and is 5-18 % faster in every measured case that takes more than 1.4 ms, 18 of 24 cases in all; it loses 2-8 % on the teapot's
+// reflection rays (bundle filter, ray walk) and 0.01-0.07 ms in the ray walk's launches that walk nothing (profiles/shade_rays_kernel_resources.txt,
+// profiles/shade_rays.json).
+template <int kWalk>
+__global__ __launch_bounds__(64, kWavesPerSimd) void shade_rays_kernel(const DevScene S, uint32_t n_rays, const ShadeRaysParams Q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const Stack stk{lds + kParkBytes, threadIdx.x};
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    const bool ok = i < n_rays;
+    const size_t j = 3 * (size_t)i;
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const uint32_t room = Q.depth < S.max_reflection_depth ? S.max_reflection_depth - Q.depth : 0u;   // levels from the batch's own on that may reflect (raytracer.rs:76)
+    // ---- the record: the hit of the batch's own segment
+    bool live = false;                      // the lane holds a hit whose colour is not known yet
+    V3 seg_d = mk(0, 0, 1), p = mk(0, 0, 0), n = mk(0, 0, 0);
+    uint32_t col = 0, mat = 0, li = 0, lvl = 0;   // lvl: levels below the batch's own = the stack slot of the hit the lane holds
+    uint32_t n_eval = 0;                    // lights [0, n_eval) contribute (an occluded point light ends the loop, raytracer.rs:235-237)
+    uint32_t term = 0x00FFFFFFu;            // colour of the last segment; WHITE for a miss, raytracer.rs:109-111
+    if (ok) {
+        mat = Q.material[i];
+        if (mat < S.n_mats) {               // (0xFFFFFFFF, a miss or a dead ray, and anything else beyond the table: WHITE)
+            live = true;
+            seg_d = ld3(Q.dirs + j); p = ld3(Q.point + j); n = ld3(Q.normal + j);
+            col = Q.albedo[i] & 0x00FFFFFFu;
+            if (Q.lights) {                 // the kept mask answers the shadow queries of this hit: the light loop below is skipped for it
+                const uint32_t first_dark = (uint32_t)__builtin_ctz(~Q.lights[i] | (1u << RRT_MAX_LIGHTS));   // (n_lights <= 16: bits at and above it never count)
+                n_eval = first_dark < S.n_lights ? first_dark : S.n_lights;
+                li = 0xFFFFu;
+            }
+        }
+    }
+    bool in_shadow = false;                 // false: the ray in flight is a reflection ray; true: a shadow ray
+    V3 ro = mk(0, 0, 0), rd = mk(0, 0, 1); double rmax = kInf;
+    double st_local[RRT_MAX_REFLECT][3]; double st_kr[RRT_MAX_REFLECT];
+    st_local[0][0] = st_local[0][1] = st_local[0][2] = 0.0; st_kr[0] = 0.0;             // what a dead ray reports
+    for (;;) {
+        // ---- shade: every live lane holds a hit (p, n, mat, col, seg_d) and stands at light li of its list
+        if (live) {
+            // the light list (raytracer.rs:205-255) up to the next point light, whose shadow ray (raytracer.rs:164-188) is walked next: trace_colour's
+            while (li < S.n_lights && !in_shadow) {
+                const DevLight& L = S.lights[li];
+                if (L.kind == 1u) {
+                    const V3 dir = ld3(L.v) - p;
+                    ro = p + n * S.surface_offset;
+                    rd = dir;
+                    rmax = length(dir);
+                    in_shadow = true;
+                } else {
+                    li++;
+                }
+            }
+            if (!in_shadow) {
+                if (li != 0xFFFFu) n_eval = S.n_lights;
+                // --- compute_lighting_intensity, raytracer.rs:192-258
+                const DevMaterial& M = S.mats[mat];
+                const V3 vdir = neg(seg_d);
+                const double len_n = length(n), len_v = length(vdir);
+                V3 I = mk(0.0, 0.0, 0.0);
+                for (uint32_t k = 0; k < n_eval; ++k) {
+                    const DevLight& L = S.lights[k];
+                    if (L.kind == 0u) {                                              // Ambient, raytracer.rs:207-209
+                        I = I + ld3(M.ka) * L.intensity;
+                    } else {                                                         // Directional (raytracer.rs:210-227) / unoccluded Point (raytracer.rs:239-252)
+                        const V3 l = (L.kind == 2u) ? ld3(L.v) : ld3(L.v) - p;
+                        const double n_dot_l = dot(n, l);
+                        I = I + diffuse_term(L.intensity, n_dot_l, len_n, length(l), ld3(M.kd));
+                        I = I + specular_term(M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks));
+                    }
+                }
+                // --- raytracer.rs:67-108
+                const V3 local = mk((double)((col >> 16) & 255u) * I.x, (double)((col >> 8) & 255u) * I.y, (double)(col & 255u) * I.z);
+                const double kr = M.kr;
+                const bool reflects = kr > 0.0 && lvl < room;                        // raytracer.rs:76
+                if (reflects || lvl == 0u) {                                         // (slot 0 also carries the `local` and `kr` outputs)
+                    st_local[lvl][0] = local.x; st_local[lvl][1] = local.y; st_local[lvl][2] = local.z; st_kr[lvl] = reflects ? kr : 0.0;
+                }
+                if (reflects && Q.colour) {                                          // (no colour asked for: no reflection ray)
+                    const double d_dot_n = dot(seg_d, n);
+                    rd = normalised(seg_d - (n * 2.0) * d_dot_n);                    // raytracer.rs:79
+                    ro = p + n * S.surface_offset;                                   // raytracer.rs:82
+                    rmax = kInf;
+                    lvl++;
+                } else {
+                    term = (clamp_u8(local.x) << 16) | (clamp_u8(local.y) << 8) | clamp_u8(local.z);   // raytracer.rs:104-108
+                    live = false;
+                }
+            }
+        }
+        if (!__any(live)) break;                                                     // no ray in flight in the wave
+        // ---- walk: the shadow and reflection rays in flight, together
+        double t; uint32_t slot;
+        if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, live, in_shadow, true, ro, rd, rmax, t, slot);
+        else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, live, in_shadow, true, false, ro, rd, rmax, t, slot);
+        if (live) {
+            const bool found = slot != kNone;
+            if (!in_shadow) {
+                if (!found) {
+                    term = 0x00FFFFFFu; live = false;                                // WHITE, raytracer.rs:109-111
+                } else {
+                    // --- hit: raytracer.rs:39-57
+                    double u = 0, v = 0, t2;
+                    mt_full(S.geom + slot, ro, rd, t2, u, v);
+                    seg_d = rd;
+                    p = ro + rd * t;                                                 // raytracer.rs:39
+                    surface_of_hit(S, slot, u, v, mat, col, n);
+                    li = 0;                                                          // compute_lighting_intensity, raytracer.rs:199-203
+                }
+            } else {
+                // --- result of the shadow ray for point light li (raytracer.rs:232-237): occluded -> `break` out of the whole light loop
+                if (found) { n_eval = li; li = 0xFFFFu; }
+                else li++;
+                in_shadow = false;
+            }
+        }
+    }
+#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
+    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
+#endif
+    if (!ok) return;
+    if (Q.local) { Q.local[j] = st_local[0][0]; Q.local[j + 1] = st_local[0][1]; Q.local[j + 2] = st_local[0][2]; }
+    if (Q.kr) Q.kr[i] = st_kr[0];
+    if (Q.colour) {
+        // unwind the reflection chain, innermost first (raytracer.rs:85-101): every level quantises to u8 before blending
+        uint32_t c = term;
+        for (uint32_t k = lvl; k-- > 0;) {
+            const double kr = st_kr[k];
+            const double fx = st_local[k][0] * (1.0 - kr) + (double)((c >> 16) & 255u) * kr;
+            const double fy = st_local[k][1] * (1.0 - kr) + (double)((c >> 8) & 255u) * kr;
+            const double fz = st_local[k][2] * (1.0 - kr) + (double)(c & 255u) * kr;
+            c = (clamp_u8(fx) << 16) | (clamp_u8(fy) << 8) | clamp_u8(fz);
+        }
+        Q.colour[i] = c;
+    }
+}
 #endif   // RRT_TU_RAYS
 
 // ---- host side of the launchers below: a runtime choice of kernel as a compile-time one.  f receives a std::integral_constant and names its instantiation.
@@ -2412,6 +2562,14 @@ int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, 
     if (n == 0) return 0;
     return with_walk(effective_walk(s, walk), [&](auto w) {
         hipLaunchKernelGGL(surface_rays_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, q);
+        return (int)hipGetLastError();
+    });
+}
+
+int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, void* stream, int walk) {
+    if (n == 0) return 0;
+    return with_walk(effective_walk(s, walk), [&](auto w) {
+        hipLaunchKernelGGL(shade_rays_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, q);
         return (int)hipGetLastError();
     });
 }
