@@ -80,6 +80,10 @@ typedef struct { const uint8_t *rgb; uint32_t width, height; } rrt_texture;
  * in all is skipped by the rays that certainly cross the box of the run's end and miss the boxes of those triangles; the bundle-filter walk
  * then enters the end directly.  Same results; this flag turns the shortcut off (tests, A/B timing). */
 #define RRT_FLAG_NO_CHAIN_SHORTCUT (1u << 5)   /* 32; a developer switch, not one of the five flags above that tests/test_abi.py pins as the Python mirror's set */
+/* Specular skip: a specular term that the f64 sum of a hit's lighting certainly absorbs -- I + term == I bit for bit, decided
+ * from an fp32 upper bound (csrc/specular_skip.hpp) -- is not evaluated: no pow, no sqrt, no divide.  Same results; this flag evaluates every term
+ * (tests, A/B timing). */
+#define RRT_FLAG_NO_SPECULAR_SKIP (1u << 6)    /* 64; a developer switch like the one above */
 
 /* Render constants that the reference hard-codes; NULL => these defaults. */
 typedef struct {

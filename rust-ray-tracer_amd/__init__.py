@@ -31,7 +31,7 @@ class RrtError(RuntimeError):
         self.detail = detail
 
 
-FLAG_NO_CULL, FLAG_LANE_FILTER, FLAG_BUNDLE_FILTER, FLAG_RAY_WALK, FLAG_HOST_SETUP, FLAG_NO_CHAIN_SHORTCUT = 1, 2, 4, 8, 16, 32   # RRT_FLAG_*, include/rrt.h
+FLAG_NO_CULL, FLAG_LANE_FILTER, FLAG_BUNDLE_FILTER, FLAG_RAY_WALK, FLAG_HOST_SETUP, FLAG_NO_CHAIN_SHORTCUT, FLAG_NO_SPECULAR_SKIP = 1, 2, 4, 8, 16, 32, 64   # RRT_FLAG_*, include/rrt.h
 BUFFERS = ("nodes", "geom", "attr", "supers", "cboxes", "child_boxes", "tboxes", "suspects", "oct_box", "oct_first_child", "oct_tri_count", "oct_own_off",
            "oct_own_idx", "slot_tri", "slot_pos", "chains")   # RRT_BUF_*
 VARIANT_NAMES = ("lane", "bundle", "ray")   # rrt_stats.filter_variant
@@ -346,8 +346,9 @@ def _counted(name: str, handle, ctype):
     return arr, n.value
 
 
-def _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut) -> COptions:
+def _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut, specular_skip=True) -> COptions:
     flags = ((FLAG_NO_CULL if no_cull else 0) | (FLAG_HOST_SETUP if host_setup else 0) | (0 if chain_shortcut else FLAG_NO_CHAIN_SHORTCUT)
+             | (0 if specular_skip else FLAG_NO_SPECULAR_SKIP)
              | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter])
     return COptions(surface_offset, max_reflection_depth, flags, *map(float, viewport))
 
@@ -620,28 +621,29 @@ class RayTracer(_Handle):
 
     def __init__(self, scene_data: SceneData, lights: Iterable[Light], origin: Vector3d = DEFAULT_ORIGIN, device: int = 0,
                  surface_offset: float = SURFACE_OFFSET, max_reflection_depth: int = MAX_REFLECTION_DEPTH, viewport=VIEWPORT, no_cull: bool = False,
-                 box_filter: Optional[str] = None, host_setup: bool = False, chain_shortcut: bool = True):
+                 box_filter: Optional[str] = None, host_setup: bool = False, chain_shortcut: bool = True, specular_skip: bool = True):
         """no_cull=True (RRT_FLAG_NO_CULL): walk every own list in full, in list order, as ray.rs:119-129; default uses the cluster boxes.
         box_filter: None = rule of thumb on the first frame of a size, measured on the second, "lane" / "bundle" / "ray" = forced (RRT_FLAG_LANE_FILTER / RRT_FLAG_BUNDLE_FILTER /
         RRT_FLAG_RAY_WALK); same pixels.  host_setup=True (RRT_FLAG_HOST_SETUP): octree, index and records built on the host and uploaded (default: built on
         the GPU, csrc/scene_build.hip); same bytes in HBM.  chain_shortcut=False (RRT_FLAG_NO_CHAIN_SHORTCUT): the bundle-filter walk enters every node of a
-        one-child chain; same results."""
+        one-child chain; same results.  specular_skip=False (RRT_FLAG_NO_SPECULAR_SKIP): every specular term is evaluated, also those the lighting sum absorbs
+        bit for bit; same results."""
         self.scene_data, self.origin, self.device = scene_data, origin, device
         cl, n_lights = _c_lights(lights)                       # (not kept: lights() asks the library for the list in force)
-        opt = _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut)
+        opt = _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut, specular_skip)
         out = _P()
         _call("rrt_raytracer_create", scene_data._h, cl, n_lights, origin._c(), C.byref(opt), device, C.byref(out))
         self._h = out
 
     @classmethod
     def from_arrays(cls, pos, uv, nrm, mat, materials: Sequence[dict], textures: Sequence[np.ndarray], lights: Iterable[Light], origin: Vector3d = DEFAULT_ORIGIN,
-                    device: int = 0, root=DEFAULT_ROOT, no_cull: bool = False, box_filter: Optional[str] = None) -> "RayTracer":
+                    device: int = 0, root=DEFAULT_ROOT, no_cull: bool = False, box_filter: Optional[str] = None, specular_skip: bool = True) -> "RayTracer":
         """rrt_raytracer_create_from_arrays: the raytracer straight from the host's arrays (no SceneData / rrt_model, no host copy of the scene)."""
         self = cls.__new__(cls)
         self.scene_data, self.origin, self.device = None, origin, device
         scene, _keep = _scene_args(pos, uv, nrm, mat, materials, textures, root)
         cl, n_lights = _c_lights(lights)
-        opt = _options(SURFACE_OFFSET, MAX_REFLECTION_DEPTH, VIEWPORT, no_cull, box_filter, False, True)
+        opt = _options(SURFACE_OFFSET, MAX_REFLECTION_DEPTH, VIEWPORT, no_cull, box_filter, False, True, specular_skip)
         out = _P()
         _call("rrt_raytracer_create_from_arrays", *scene, cl, n_lights, origin._c(), C.byref(opt), device, C.byref(out))
         self._h = out

@@ -104,6 +104,8 @@ struct DevScene {                // passed to kernels by value (kernarg segment 
     uint32_t cull_enabled;
     uint32_t has_groups;         // some own list carries group records (clusters.cpp): launches use the kernel instantiation that handles them
     uint32_t n_suspects;         // triangles whose plane passes through `origin` (see DevSuspect); more than RRT_MAX_SUSPECTS: every ray from `origin` runs unfiltered
+    uint32_t specular_all;       // RRT_FLAG_NO_SPECULAR_SKIP: every specular term is evaluated, also those the f64 sum certainly absorbs (specular_skip.hpp).  (In what
+                                 // was padding in front of the pointer below: no other field moves.)
     const DevSuspect* suspects;
     float inner_shrink;          // 2 x the filter's pad when every triangle of the tree lies inside the root box (a child's subtree box then lies inside its octant box), else 0: render.hip, RRT_CERTAIN_HIT
     uint32_t bounds_plain;       // every node plane (lo, mid, hi) is 0 or has magnitude in [2^-200, 2^200]: the walk may share the reciprocal of a ray's direction across its slab quotients (render.hip, RayRcp)
@@ -111,7 +113,7 @@ struct DevScene {                // passed to kernels by value (kernarg segment 
                                  // fields the other kernels read: where a pointer sits among the first sixteen words of the kernarg segment shapes their scalar loads.)
     DevLight lights[RRT_MAX_LIGHTS];
 #ifdef RRT_PROFILE
-    unsigned long long* prof;    // developer build only (make prof): 16 wave-level work counters + 8 s_memtime region timers, see tools/profile_counters.py
+    unsigned long long* prof;    // developer build only (make prof): 16 wave-level work counters + 6 s_memtime region timers + the specular pair, see tools/profile_counters.py
 #endif
 };
 

@@ -206,6 +206,7 @@ int create_raytracer(const rrt_light* lights, uint32_t n_lights, rrt_vec3 origin
     rt->origin0 = origin;
     rt->cam = rrt_camera{origin, {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};   // the reference's view: down +z, y up (engine.rs:207-211)
     S.surface_offset = o.surface_offset;
+    S.specular_all = (o.flags & RRT_FLAG_NO_SPECULAR_SKIP) ? 1u : 0u;
     store_lights(rt.get(), lights, n_lights);
 #ifdef RRT_PROFILE
     rt->prof_mem = dev_alloc(32 * sizeof(unsigned long long)); HIP_TRY(hipMemset(rt->prof_mem.h, 0, 32 * sizeof(unsigned long long)));

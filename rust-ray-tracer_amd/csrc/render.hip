@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "device_scene.hpp"
+#include "specular_skip.hpp"
 
 // The library compiles this file THREE times (csrc/Makefile), same device functions, different code-generation switches per group of kernels:
 //   -DRRT_TU=1  the bundle-filter frame, visibility, surface, shade and ambient kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
@@ -404,7 +405,7 @@ __device__ __forceinline__ bool origin_ray_in_suspect_plane(const DevScene& S, V
 
 // ------------------------------------------------------------------------------------------------ developer counters
 #ifdef RRT_PROFILE
-struct Prof { unsigned long long c[16]; unsigned long long t[8]; unsigned long long last; unsigned long long b[4]; double pad; bool secondary; };
+struct Prof { unsigned long long c[18]; unsigned long long t[8]; unsigned long long last; unsigned long long b[4]; double pad; bool secondary; };
 #define PROF_DECL Prof& prof,
 #define PROF_ARG prof,
 // Counters are per WAVE: whichever lane is the first active one at the increment adds to its own copy, and every lane's copies are summed at the end
@@ -1411,11 +1412,26 @@ __device__ __forceinline__ V3 diffuse_term(double intensity, double n_dot_l, dou
     if (n_dot_l <= 0.0) return mk(0.0, 0.0, 0.0);
     return div3((kd * intensity) * n_dot_l, len_n * len_l);
 }
-__device__ __forceinline__ V3 specular_term(double sw, double intensity, V3 normal, V3 v, double len_v, V3 l, V3 ks) { // raytracer.rs:279-304
+// `I` is the running sum as it stands after the diffuse addition.  Where the f64 addition I + term certainly returns I (specular_skip.hpp has the proof;
+// `skip` is the scene's wave-uniform permission, off with RRT_FLAG_NO_SPECULAR_SKIP) the term is not evaluated and +0 is added instead: same I, bit for bit
+// (every channel of such a lane's I is a positive number).  The decision r.v > 0 stays the f64 one; the fp32 estimate needs nothing in f64 beyond r and r.v.  The divergent
+// `if (need)` is the wave-level skip: length(r), the divide and pow run under the mask of the lanes that need them, and a wave without one branches over them.
+__device__ __forceinline__ V3 specular_term(PROF_DECL bool skip, double sw, double intensity, V3 normal, V3 v, double len_v, V3 l, V3 ks, V3 I) { // raytracer.rs:279-304
     if (sw != -1.0) {
         const V3 r = ((normal * 2.0) * dot(normal, l)) - l;
         const double r_dot_v = dot(r, v);
-        if (r_dot_v > 0.0) return (ks * intensity) * pow(r_dot_v / (length(r) * len_v), sw);
+        if (r_dot_v > 0.0) {
+            PROF_ADD(16, 1);                                                     // [16] specular blocks entered by a wave
+            bool need = true;
+            if (skip) {
+                const float e2 = spec_log2_pow_x2((float)r_dot_v, spec_sumsq_f32(r.x, r.y, r.z), spec_sq_f32(len_v), (float)sw);
+                need = !spec_absorbed3(e2, ks.x, ks.y, ks.z, intensity, I.x, I.y, I.z);
+            }
+            if (need) {
+                PROF_ADD(17, 1);                                                 // [17] ... in which some lane needed pow
+                return (ks * intensity) * pow(r_dot_v / (length(r) * len_v), sw);
+            }
+        }
     }
     return mk(0.0, 0.0, 0.0);
 }
@@ -1524,7 +1540,7 @@ __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, co
                             const V3 l = (L.kind == 2u) ? ld3(L.v) : ld3(L.v) - p;
                             const double n_dot_l = dot(n, l);
                             I = I + diffuse_term(L.intensity, n_dot_l, len_n, length(l), ld3(M.kd));
-                            I = I + specular_term(M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks));
+                            I = I + specular_term(PROF_ARG !S.specular_all, M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks), I);
                         }
                     }
                     // --- raytracer.rs:67-108
@@ -1655,6 +1671,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
 #elif defined(RRT_PROFILE)
     PROF_T(4);
     for (int i = 0; i < 16; i++) if (prof.c[i]) atomicAdd(S.prof + i, prof.c[i]);
+    for (int i = 16; i < 18; i++) if (prof.c[i]) atomicAdd(S.prof + 6 + i, prof.c[i]);          // (the specular pair: slots 22, 23, behind the six region timers)
     if (lane == 0) { for (int i = 0; i < 8; i++) if (prof.t[i]) atomicAdd(S.prof + 16 + i, prof.t[i]); }
     for (int i = 0; i < 4; i++) if (prof.b[i]) atomicAdd(S.prof + 24 + i, prof.b[i]);        // (per lane: band_count events are per ray)
 #endif
@@ -1925,7 +1942,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
                         const V3 l = (L.kind == 2u) ? ld3(L.v) : ld3(L.v) - p;
                         const double n_dot_l = dot(n, l);
                         I = I + diffuse_term(L.intensity, n_dot_l, len_n, length(l), ld3(M.kd));
-                        I = I + specular_term(M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks));
+                        I = I + specular_term(PROF_ARG !S.specular_all, M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks), I);
                     }
                 }
                 // --- raytracer.rs:67-108
@@ -2315,7 +2332,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_rays_kernel(const Dev
                         const V3 l = (L.kind == 2u) ? ld3(L.v) : ld3(L.v) - p;
                         const double n_dot_l = dot(n, l);
                         I = I + diffuse_term(L.intensity, n_dot_l, len_n, length(l), ld3(M.kd));
-                        I = I + specular_term(M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks));
+                        I = I + specular_term(PROF_ARG !S.specular_all, M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks), I);
                     }
                 }
                 // --- raytracer.rs:67-108

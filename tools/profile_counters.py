@@ -1,6 +1,7 @@
 """Developer tool: wave-level work counters of the trace kernel (needs `make -C rust-ray-tracer_amd/csrc prof`).
    RRT_LIB=rust-ray-tracer_amd/librrt_hip_prof.so python tools/profile_counters.py [W H] [scene.obj]
-   RRT_FILTER=lane|bundle|ray forces a walk; RRT_NO_CHAIN=1 turns the chain shortcut off (RRT_FLAG_NO_CHAIN_SHORTCUT)."""
+   RRT_FILTER=lane|bundle|ray forces a walk; RRT_NO_CHAIN=1 turns the chain shortcut off (RRT_FLAG_NO_CHAIN_SHORTCUT), RRT_NO_SPECULAR_SKIP=1 the specular
+   skip (RRT_FLAG_NO_SPECULAR_SKIP)."""
 import ctypes as C, importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +14,8 @@ if scene.startswith("soup"):   # soup100000 / soup1000000: generated on the spot
     syn = importlib.import_module("rust-ray-tracer_amd.synthetic"); n = int(scene[4:])
     scene = syn.ensure_soup(os.path.join(ROOT, "assets"), n, syn.SEED_100K if n == 100000 else syn.SEED_1M if n == 1000000 else 0x5EED0003)
 sd = rrt.parse_obj_file(scene)
-rt = rrt.RayTracer(sd, rrt.default_lights(), box_filter=os.environ.get("RRT_FILTER") or None, chain_shortcut=os.environ.get("RRT_NO_CHAIN") != "1")
+rt = rrt.RayTracer(sd, rrt.default_lights(), box_filter=os.environ.get("RRT_FILTER") or None, chain_shortcut=os.environ.get("RRT_NO_CHAIN") != "1",
+                  specular_skip=os.environ.get("RRT_NO_SPECULAR_SKIP") != "1")
 L = rrt.lib()
 L.rrt_prof_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 buf = (C.c_uint64 * 24)()
@@ -23,6 +25,10 @@ c = list(buf)
 names = ["node_visits(wave)", "node_visit_lanes", "tri_iters(wave)", "tri_lane_tests", "tri_box_tests(wave)", "single_candidate_decided_in_fp32(wave)", "traverse_calls(wave)", "traverse_lanes", "slab_iters(wave)", "slab_lane_tests", "super_tests(wave)", "cluster_tests(wave)", "internal_visits(wave)", "shade_blocks(wave-divergent)", "slab_exact_fallbacks(wave)", "chain_node_visits(wave)"]
 for i, n in enumerate(names):
     print(f"{n:24s} {c[i]:>16,d}")
+# the specular pair sits behind the six region timers (render.hip: render_kernel): specular blocks a wave entered (some lane with r.v > 0), and those in which
+# some lane's term was not certainly absorbed, so that length(r), the divide and pow ran
+print(f"{'specular_blocks(wave)':24s} {c[22]:>16,d}")
+print(f"{'specular_pow_blocks(wave)':24s} {c[23]:>16,d}   ({100.0 * c[23] / max(1, c[22]):.1f} % of the entered blocks still need pow)")
 print(f"kernel_ms (counters build) {ms:.2f}")
 tn = ["pick node + record load", "children (reach, quotients, slab, rank)", "own list (boxes + MT)", "push / unwind", "shading + state machine", "traverse set-up"]
 tt = sum(c[16:22]) or 1
