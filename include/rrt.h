@@ -592,11 +592,51 @@ int rrt_surface_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_origi
  * rrt_shade_rays: arrays in host memory; blocking.  One device allocation of the call's own; dirs and the four or five arrays it reads are uploaded, only the
  * requested outputs downloaded.  It never measures the variants -- it has no origins to measure a walk on -- and picks its variant by the device form's rule.
  * rrt_raytracer_set_lights, set_materials and set_triangles[_device] apply to every call made after they return.
- * Not covered: per-ray depths, an ambient-occlusion call for ray records, the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+ * Not covered: per-ray depths, the rank/world tile partition, the rrt_multi_* path and the progressive path. */
 typedef struct { uint32_t *colour; double *local; double *kr; } rrt_ray_shade;   /* 24 bytes; colour [n], local [n][3], kr [n] */
 int rrt_shade_rays(rrt_raytracer *rt, uint32_t n, const double *dirs, const rrt_ray_surface *rec, uint32_t depth, const rrt_ray_shade *out);
 int rrt_shade_rays_device(rrt_raytracer *rt, uint32_t n, const double *d_dirs, const rrt_ray_surface *d_rec, uint32_t depth, const rrt_ray_shade *d_out,
                           void *stream);
+
+/* Ambient occlusion for arbitrary ray records: which of n hemisphere rays from every hit of a batch are blocked, from the records rrt_surface_rays* wrote for it, in
+ * ONE launch that forms the rays in registers -- what rrt_ambient_surface does for a frame's first hits, for the caller's own rays, with a rotation of the sample
+ * table per record.  For second-bounce ambient occlusion (the records of next_origin / next_dir), for probes and bake points that are not the eye, and for a
+ * frame's own planes: flattened to [n] they are valid records, so this call also gives a frame a rotated fan.
+ * rec / d_rec is the struct the caller gave rrt_surface_rays[_device] for these n rays, in that layout.  READ: point, normal and material, all three required; the
+ * other nine pointers are ignored.  Origins and directions of the rays are not needed.
+ * samples: the table of rrt_ambient_surface -- n directions (sx, sy, sz) in the tangent frame of a hit, sz along the normal, and one max_t for all rays (+inf is
+ * valid).  It lies in HOST memory in both forms, is borrowed for the call and travels in the kernel arguments.
+ * rot / d_rot: [n][2] doubles, (c, s) per record -- the cosine and sine of the angle by which the record's fan is turned about its normal -- or NULL.  It lies where
+ * the records lie.  The library neither normalises (c, s) nor checks c*c + s*s = 1: a scaled or mirrored pair is the caller's business, as the camera basis is.
+ * Per record i: material[i] >= n_mats (0xFFFFFFFF, a miss or a dead ray, included) is a miss -- the rule of rrt_shade_rays and rrt_ambient_surface; no value of the
+ * caller's arrays is used as an index.  Otherwise, with point p and normal n exactly as stored and tg, bt the reference's tangent frame as rrt_ambient_surface
+ * defines it, the ray of sample k = (sx, sy, sz) is
+ *   origin = p + n * surface_offset;   max_t = samples->max_t;
+ *   rot == NULL:          direction.c = (tg.c*sx + bt.c*sy) + n.c*sz  per component -- exactly the ray of rrt_ambient_surface;
+ *   rot != NULL, (c, s) = rot[i]:   rx = sx*c - sy*s;  ry = sx*s + sy*c  -- six f64 operations, each rounded on its own -- and
+ *                         direction.c = (tg.c*rx + bt.c*ry) + n.c*sz.
+ * WRITTEN; either pointer may be NULL (that array is not written), not both; every element of every requested array is written:
+ *   occluded[i]: bit k = what rrt_occluded_rays returns for exactly that ray, byte for byte; bits at and above n are 0.  A miss gives 0.
+ *   open[i]:     samples->n - popcount(occluded[i]) for a hit; samples->n for a miss or a dead record -- the rule by which `grey` counts a miss as open.
+ * A non-finite point, normal or rot pair gives unspecified bits for that record, and no fault.  Inputs and outputs must not overlap.
+ * Exactness: as for rrt_ambient_surface: every walk of this call is a shadow walk of a frame -- default mode, not guarded, the band documented under
+ * RRT_FLAG_NO_CULL.
+ * Keeping the records valid is the caller's business; the table under rrt_shade_rays says when for point, normal and material.  A change of lights never matters,
+ * rrt_raytracer_set_camera never matters.
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer and the outputs as they were: NULL rt, rec, samples or out; with n > 0 a NULL required array
+ * or both outputs NULL; and, whatever n is, every refusal rrt_ambient_surface makes for its table: n == 0 or n > RRT_MAX_AMBIENT_SAMPLES; NULL dirs; a non-finite
+ * direction component; max_t NaN or <= 0.  n = 0 with valid structs is RRT_OK with nothing enqueued.
+ * rrt_last_stats afterwards: as after the other per-ray calls (width = n, height = 1, rays_primary = n; the hemisphere rays are not counted).
+ * rrt_ambient_rays_device: arrays in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default): no allocation, no copy, no synchronisation and
+ * no measurement; the traversal variant by the rule of rrt_intersect_rays_device.
+ * rrt_ambient_rays: arrays in host memory; blocking.  One device allocation of the call's own; the three arrays it reads are uploaded, and rot if it is given;
+ * only the requested outputs are downloaded.  It never measures the variants and picks its variant by the device form's rule, as rrt_shade_rays does.
+ * Not covered: a max_t per ray, weights per sample (the mask lets the host weight), the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+typedef struct { uint32_t *occluded; uint32_t *open; } rrt_ray_ambient;   /* 16 bytes; [n] each; either may be NULL, not both */
+int rrt_ambient_rays(rrt_raytracer *rt, uint32_t n, const rrt_ray_surface *rec, const double *rot /* [n][2], may be NULL */,
+                     const rrt_ambient_samples *samples, const rrt_ray_ambient *out);
+int rrt_ambient_rays_device(rrt_raytracer *rt, uint32_t n, const rrt_ray_surface *d_rec, const double *d_rot,
+                            const rrt_ambient_samples *samples, const rrt_ray_ambient *d_out, void *stream);
 
 /* The octree of a raytracer whose set-up ran on the GPU (the default), read back from its device: same layout as rrt_model_get_octree; info (may be
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */

@@ -97,6 +97,10 @@ class CRayShade(C.Structure):        # rrt_ray_shade, 24 bytes: host or device p
     _fields_ = [(n, C.c_void_p) for n in ("colour", "local", "kr")]
 
 
+class CRayAmbient(C.Structure):      # rrt_ray_ambient, 16 bytes: host or device pointers, NULL = array not wanted
+    _fields_ = [(n, C.c_void_p) for n in ("occluded", "open")]
+
+
 MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
 
 # The plane table: every plane of rrt_visibility, rrt_surface and rrt_ambient, in the struct's order, as (dtype, elements per sub-sample, True = one value per
@@ -123,6 +127,10 @@ RAY_SURFACE_PLANES = tuple(_PLANES_OF[CRaySurface])                           # 
 _PLANES_OF[CRayShade] = dict(colour=(np.uint32, 1, True), local=(np.float64, 3, True), kr=(np.float64, 1, True))
 RAY_SHADE_OUTPUTS = tuple(_PLANES_OF[CRayShade])                              # the arrays of rrt_ray_shade, in its order
 RAY_SHADE_INPUTS = SHADE_INPUTS                                               # what rrt_shade_rays reads of an rrt_ray_surface (lights optional)
+# rrt_ray_ambient: per RAY the mask of occluded hemisphere rays and the count of open ones
+_PLANES_OF[CRayAmbient] = dict(occluded=(np.uint32, 1, True), open=(np.uint32, 1, True))
+RAY_AMBIENT_OUTPUTS = tuple(_PLANES_OF[CRayAmbient])                          # the arrays of rrt_ray_ambient, in its order
+RAY_AMBIENT_INPUTS = AMBIENT_INPUTS                                           # what rrt_ambient_rays reads of an rrt_ray_surface
 
 
 class CModelInfo(C.Structure):
@@ -142,7 +150,8 @@ class CSetupTimes(C.Structure):
 # every struct of include/rrt.h and the class that mirrors it (tests/test_abi.py compares sizes and offsets with what the header's compiler gives)
 STRUCTS = {"rrt_vec3": Vec3, "rrt_light": CLight, "rrt_material": CMaterial, "rrt_texture": CTexture, "rrt_options": COptions, "rrt_camera": CCamera,
            "rrt_region": CRegion, "rrt_visibility": CVisibility, "rrt_pick_result": CPickResult, "rrt_surface": CSurface,
-           "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_ray_surface": CRaySurface, "rrt_ray_shade": CRayShade, "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
+           "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_ray_surface": CRaySurface, "rrt_ray_shade": CRayShade, "rrt_ray_ambient": CRayAmbient,
+           "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
 
 # every symbol include/rrt.h declares: (restype, argtypes)
 _P = C.c_void_p
@@ -208,6 +217,8 @@ SYMBOLS = {
     "rrt_surface_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.POINTER(CRaySurface), _P]),
     "rrt_shade_rays": (C.c_int, [_P, C.c_uint32, _dp, C.POINTER(CRaySurface), C.c_uint32, C.POINTER(CRayShade)]),
     "rrt_shade_rays_device": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(CRaySurface), C.c_uint32, C.POINTER(CRayShade), _P]),
+    "rrt_ambient_rays": (C.c_int, [_P, C.c_uint32, C.POINTER(CRaySurface), _dp, C.POINTER(CAmbientSamples), C.POINTER(CRayAmbient)]),
+    "rrt_ambient_rays_device": (C.c_int, [_P, C.c_uint32, C.POINTER(CRaySurface), _P, C.POINTER(CAmbientSamples), C.POINTER(CRayAmbient), _P]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
@@ -461,17 +472,18 @@ def _plane_struct(cls, planes: dict):
 
 
 def _ray_plane(name: str, cls=CRaySurface, what: str = "surface_rays"):
-    """(dtype, elements per ray) of an array of rrt_ray_surface, or of rrt_ray_shade `cls`; an unknown name is a ValueError"""
+    """(dtype, elements per ray) of an array of rrt_ray_surface, or of rrt_ray_shade / rrt_ray_ambient `cls`; an unknown name is a ValueError"""
     if name not in _PLANES_OF[cls]:
         raise ValueError(f"{what}: unknown {'plane' if cls is CRaySurface else 'output'} {name!r}, want names from {tuple(_PLANES_OF[cls])}")
     return _PLANES_OF[cls][name][:2]
 
 
-def _ray_records(what: str, planes: dict) -> dict:
-    """The arrays of an rrt_ray_surface that rrt_shade_rays reads, of the caller's `planes` (host arrays or device tensors): {name: (array, dtype, elements per
-    ray)}.  Every name must be one of RAY_SURFACE_PLANES (ValueError otherwise); None and the arrays the call ignores are left out (NULL for the library)."""
+def _ray_records(what: str, planes: dict, inputs=RAY_SHADE_INPUTS) -> dict:
+    """The arrays of an rrt_ray_surface that a call reads -- `inputs`: rrt_shade_rays' by default -- of the caller's `planes` (host arrays or device tensors):
+    {name: (array, dtype, elements per ray)}.  Every name must be one of RAY_SURFACE_PLANES (ValueError otherwise); None and the arrays the call ignores are left
+    out (NULL for the library)."""
     rows = {name: (a,) + _ray_plane(name, what=what) for name, a in planes.items()}
-    return {name: row for name, row in rows.items() if row[0] is not None and name in RAY_SHADE_INPUTS}
+    return {name: row for name, row in rows.items() if row[0] is not None and name in inputs}
 
 
 def _bound(name: str, *args):
@@ -855,6 +867,42 @@ class RayTracer(_Handle):
             _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
         _call("rrt_shade_rays_device", self._h, n, _ptr(dirs_t), _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), int(depth),
               _plane_struct(CRayShade, out), _P(_stream(stream)))
+
+    # ambient occlusion for ray records (rrt.h: rrt_ambient_rays): what ambient() does for a frame's planes, for the arrays surface_rays wrote, with a rotation per record
+    def ambient_rays(self, planes: dict, dirs, max_t: float = float("inf"), rot=None, outputs=RAY_AMBIENT_OUTPUTS) -> dict:
+        """rrt_ambient_rays: {name: array} for the names asked for, from RAY_AMBIENT_OUTPUTS -- occluded uint32 [n], bit k = ray k of the record's fan is blocked;
+        open uint32 [n], the number of open rays (all of them for a miss) -- of the records `planes` holds ({name: array} as surface_rays returns it: point, normal
+        and material are read; the others are ignored).  dirs: [n_samples][3] directions in the tangent frame of a hit, as ambient() takes them; rot: None or
+        [n][2] float64, (cos, sin) of the angle by which each record's fan is turned about its normal."""
+        rec = {name: np.ascontiguousarray(a, dtype) for name, (a, dtype, width) in _ray_records("ambient_rays", planes, RAY_AMBIENT_INPUTS).items()}
+        assert "material" in rec, "ambient_rays: the records have no material array"
+        n = rec["material"].size
+        for name, a in rec.items():
+            assert a.size == n * _ray_plane(name)[1], f"ambient_rays: array {name} has {a.size} elements for {n} rays"
+        r = None if rot is None else np.ascontiguousarray(rot, np.float64)
+        assert r is None or r.size == 2 * n, f"ambient_rays: rot has {r.size} elements for {n} rays"
+        _d_keep, samples = _ambient_samples(dirs, max_t)
+        out = {name: np.empty(n, dtype) for name, (dtype, width) in ((name, _ray_plane(name, CRayAmbient, "ambient_rays")) for name in outputs)}
+        _call("rrt_ambient_rays", self._h, n, _plane_struct(CRaySurface, rec), _d(r), C.byref(samples), _plane_struct(CRayAmbient, out))
+        return out
+
+    def ambient_rays_into(self, out: dict, planes: dict, dirs, max_t: float, rot_t=None, stream: Optional[int] = None):
+        """rrt_ambient_rays_device: out = {name: contiguous device tensor of n four-byte elements} for any subset of RAY_AMBIENT_OUTPUTS; planes = {name: device
+        tensor} as surface_rays_into filled them (point, normal, material); rot_t None or a float64 device tensor of 2 n elements.  The sample table `dirs` is a
+        host array.  Enqueued, not synchronised."""
+        rec = _ray_records("ambient_rays_into", planes, RAY_AMBIENT_INPUTS)
+        assert "material" in rec, "ambient_rays_into: the records have no material array"
+        n = _batch_size(rec["material"][0], 1, "material")
+        for name, (t, dtype, width) in rec.items():
+            _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
+        if rot_t is not None:
+            _device_tensor(rot_t, 2 * n, 8, "rot")
+        for name, t in out.items():
+            dtype, width = _ray_plane(name, CRayAmbient, "ambient_rays_into")
+            _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
+        _d_keep, samples = _ambient_samples(dirs, max_t)
+        _call("rrt_ambient_rays_device", self._h, n, _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), _ptr(rot_t), C.byref(samples),
+              _plane_struct(CRayAmbient, out), _P(_stream(stream)))
 
     # engine.rs:196-253: chunked draw with an update after every chunk (on_update(fb, first_row, n_rows) stands in for canvas.update())
     def render_progressive(self, width: int, height: int, on_update=None, chunk_rows: int = 50) -> np.ndarray:

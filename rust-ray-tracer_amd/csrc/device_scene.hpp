@@ -198,6 +198,20 @@ struct ShadeRaysParams {
     uint32_t depth, _pad;
 };
 
+// Argument of the per-ray ambient kernels (render.hip: ambient_rays_kernel; rrt.h: rrt_ambient_rays_device): the three arrays the kernel READS -- the records the
+// per-ray surface launch wrote for a batch of n rays, point / normal [n][3], material [n] -- the optional rotation (rot: [n][2], (c, s) per record; null: the
+// samples enter the tangent frame as they are), the two arrays it writes (occluded [n] masks, open [n] counts; either may be null, not both) and the sample table
+// of AmbientParams, which travels in the kernel arguments in the same way.
+struct AmbientRaysParams {
+    const double *point, *normal; const uint32_t* material;
+    const double* rot;
+    uint32_t *occluded, *open;
+    uint32_t n_samples, _pad;
+    double max_t;
+    double dirs[RRT_MAX_AMBIENT_SAMPLES][3];
+};
+static_assert(sizeof(DevScene) + sizeof(uint64_t) + sizeof(AmbientRaysParams) < 4096, "the arguments of ambient_rays_kernel must fit the 4 KB kernel-argument segment");
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);
@@ -216,6 +230,8 @@ int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, con
 int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, void* stream, int walk);
 // The colour, the unquantised local colour and the kr of every ray from its kept record (render.hip: shade_rays_kernel); any output of q may be null, not all
 int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, void* stream, int walk);
+// The occlusion mask and the count of open rays of every record's hemisphere fan (render.hip: ambient_rays_kernel); either output of q may be null, not both
+int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, void* stream, int walk);
 // Exactness guard for a new eye (scene_build.hip: k_suspects_resident): searches the resident list slots geom[0, n_list_slots) and appends up to
 // RRT_MAX_SUSPECTS + 1 records {push index, suspect} to d_out, counting every find in *d_count (zeroed here, on `stream`).  Not synchronised.
 struct SuspectRecord { uint32_t tri; uint32_t _pad; DevSuspect s; };

@@ -339,18 +339,22 @@ void shade_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const r
     });
 }
 
-// ---- ambient occlusion from kept planes.  every check, before any GPU work; returns the region in force
+// ---- ambient occlusion from kept planes and from ray records.  The checks of a sample table (not null), for both
+void check_ambient_samples(const rrt_ambient_samples& samples) {
+    if (samples.n == 0 || samples.n > RRT_MAX_AMBIENT_SAMPLES) throw Error{RRT_ERR_INVALID_ARG, "bad sample count: 1 to RRT_MAX_AMBIENT_SAMPLES directions"};
+    if (!samples.dirs) throw Error{RRT_ERR_INVALID_ARG, "null sample directions"};
+    for (uint32_t k = 0; k < 3 * samples.n; k++)
+        if (!std::isfinite(samples.dirs[k])) throw Error{RRT_ERR_INVALID_ARG, "a sample direction has a non-finite component"};
+    if (!(samples.max_t > 0.0)) throw Error{RRT_ERR_INVALID_ARG, "max_t is NaN or not positive"};
+}
+// every check of a frame's call, before any GPU work; returns the region in force
 rrt_region check_ambient(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* planes, const rrt_ambient_samples* samples,
                          const rrt_ambient* out) {
     check_frame(rt, width, height);
     if (!planes || !samples || !out) throw Error{RRT_ERR_INVALID_ARG, "null struct: ambient occlusion takes the surface planes, the sample table and the output planes"};
     if (!planes->point || !planes->normal || !planes->material) throw Error{RRT_ERR_INVALID_ARG, "null plane: point, normal and material are all required"};
     if (!out->occluded && !out->grey) throw Error{RRT_ERR_INVALID_ARG, "no output requested: occluded and grey are both null"};
-    if (samples->n == 0 || samples->n > RRT_MAX_AMBIENT_SAMPLES) throw Error{RRT_ERR_INVALID_ARG, "bad sample count: 1 to RRT_MAX_AMBIENT_SAMPLES directions"};
-    if (!samples->dirs) throw Error{RRT_ERR_INVALID_ARG, "null sample directions"};
-    for (uint32_t k = 0; k < 3 * samples->n; k++)
-        if (!std::isfinite(samples->dirs[k])) throw Error{RRT_ERR_INVALID_ARG, "a sample direction has a non-finite component"};
-    if (!(samples->max_t > 0.0)) throw Error{RRT_ERR_INVALID_ARG, "max_t is NaN or not positive"};
+    check_ambient_samples(*samples);
     return region_in_force(width, height, region);
 }
 
@@ -472,6 +476,48 @@ int shade_rays_from_host(rrt_raytracer* rt, uint32_t n, const double* dirs, cons
     const ShadeRaysParams q = shade_rays_params((const double*)pl[0].dev, d_rec, depth, rrt_ray_shade{(uint32_t*)pl[6].dev, (double*)pl[7].dev, (double*)pl[8].dev});
     const int variant = device_rays_variant(rt);
     timed_launch(rt, nullptr, [&] { return launch_shade_rays(rt->scene, n, q, nullptr, variant); });
+    record(rt, n, 1, n, variant);
+    for (const HostPlane& p : pl) if (p.host && (p.dir & kDown)) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
+    return RRT_OK;
+}
+
+// ---- ambient occlusion for ray records (rrt.h: rrt_ambient_rays).  every check, before any GPU work; the structs and the table are checked for n == 0 too
+void check_ambient_rays(const rrt_raytracer* rt, uint32_t n, const rrt_ray_surface* rec, const rrt_ambient_samples* samples, const rrt_ray_ambient* out) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (!rec || !samples || !out) throw Error{RRT_ERR_INVALID_ARG, "null struct: ambient occlusion of rays takes the ray surface struct, the sample table and the ray ambient struct"};
+    if (n && (!rec->point || !rec->normal || !rec->material)) throw Error{RRT_ERR_INVALID_ARG, "null array: point, normal and material are all required"};
+    if (n && !out->occluded && !out->open) throw Error{RRT_ERR_INVALID_ARG, "no output requested: occluded and open are both null"};
+    check_ambient_samples(*samples);
+}
+// the kernels' argument from arrays in device memory.  The sample table is copied into it here: no device memory holds it.
+AmbientRaysParams ambient_rays_params(const rrt_ray_surface& d_rec, const double* d_rot, const rrt_ambient_samples& samples, const rrt_ray_ambient& d_out) {
+    AmbientRaysParams q{};
+    q.point = d_rec.point; q.normal = d_rec.normal; q.material = d_rec.material;
+    q.rot = d_rot;
+    q.occluded = d_out.occluded; q.open = d_out.open;
+    q.n_samples = samples.n; q.max_t = samples.max_t;
+    std::memcpy(q.dirs, samples.dirs, sizeof(double) * 3 * samples.n);
+    return q;
+}
+// Host form (checked), shade_rays_from_host's sibling: the three arrays and the optional rotations up, one launch on the null stream in the variant of the device
+// forms -- nothing is measured -- the requested outputs down; blocking.  All of it in ONE device allocation of the call's own.
+int ambient_rays_from_host(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface& rec, const double* rot, const rrt_ambient_samples& samples, const rrt_ray_ambient& out) {
+    if (n == 0) return RRT_OK;
+    DeviceGuard guard(rt->device);
+    const size_t N = n;
+    HostPlane pl[] = {plane_up(rec.point, 24, N), plane_up(rec.normal, 24, N), plane_up(rec.material, 4, N), plane_up(rot, 16, N),
+                      plane_down(out.occluded, 4, N), plane_down(out.open, 4, N)};
+    size_t need = 0;
+    for (const HostPlane& p : pl) if (p.host) need += slot_bytes(p.bytes());
+    const DevBuf mem = dev_alloc(need);
+    DevArena arena{static_cast<char*>(mem.h), need, 0};
+    for (HostPlane& p : pl) if (p.host) p.dev = arena.take<char>(p.bytes());
+    for (const HostPlane& p : pl) if (p.host && (p.dir & kUp)) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
+    rrt_ray_surface d_rec{};
+    d_rec.point = (double*)pl[0].dev; d_rec.normal = (double*)pl[1].dev; d_rec.material = (uint32_t*)pl[2].dev;
+    const AmbientRaysParams q = ambient_rays_params(d_rec, (const double*)pl[3].dev, samples, rrt_ray_ambient{(uint32_t*)pl[4].dev, (uint32_t*)pl[5].dev});
+    const int variant = device_rays_variant(rt);
+    timed_launch(rt, nullptr, [&] { return launch_ambient_rays(rt->scene, n, q, nullptr, variant); });
     record(rt, n, 1, n, variant);
     for (const HostPlane& p : pl) if (p.host && (p.dir & kDown)) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
     return RRT_OK;
@@ -755,6 +801,23 @@ int rrt_shade_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_dirs, c
         check_shade_rays(rt, n, d_dirs, d_rec, d_out);
         return device_ray_launch(rt, n, stream, [&](int variant) {
             return launch_shade_rays(rt->scene, n, shade_rays_params(d_dirs, *d_rec, depth, *d_out), stream, variant);
+        });
+    });
+}
+
+int rrt_ambient_rays(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface* rec, const double* rot, const rrt_ambient_samples* samples, const rrt_ray_ambient* out) {
+    return guarded([&]() -> int {
+        check_ambient_rays(rt, n, rec, samples, out);
+        return ambient_rays_from_host(rt, n, *rec, rot, *samples, *out);
+    });
+}
+
+int rrt_ambient_rays_device(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface* d_rec, const double* d_rot, const rrt_ambient_samples* samples,
+                            const rrt_ray_ambient* d_out, void* stream) {
+    return guarded([&]() -> int {
+        check_ambient_rays(rt, n, d_rec, samples, d_out);
+        return device_ray_launch(rt, n, stream, [&](int variant) {
+            return launch_ambient_rays(rt->scene, n, ambient_rays_params(*d_rec, d_rot, *samples, *d_out), stream, variant);
         });
     });
 }

@@ -35,7 +35,7 @@
 //   -DRRT_TU=1  the bundle-filter frame, visibility, surface, shade and ambient kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
 //   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility, surface, shade and ambient kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
-//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel, surface_rays_kernel, shade_rays_kernel (default scheduler: max-ILP costs scattered rays 17 %).
+//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel, surface_rays_kernel, shade_rays_kernel, ambient_rays_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
 #ifndef RRT_TU
 #define RRT_TU 0
@@ -2400,6 +2400,65 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_rays_kernel(const Dev
         Q.colour[i] = c;
     }
 }
+// Ambient occlusion for arbitrary ray records (rrt.h: rrt_ambient_rays_device): ambient_kernel's sample loop behind the front end of the per-ray kernels.  A lane
+// loads its record -- point, normal, material, as the per-ray surface launch wrote them -- and builds the reference's tangent frame (raytracer.rs:137-152) ONCE;
+// the loop is over the SAMPLES: sample k of the table -- kernel arguments, wave-uniform -- gives every hit lane of the wave its ray k, and a turn keeps one bit
+// per lane.  The rays live in registers only.
+// With Q.rot -- a kernel-argument pointer: the test is wave-uniform -- the lane's (c, s) is loaded once and every sample is turned about the normal before it
+// enters the frame: rx = sx*c - sy*s, ry = sx*s + sy*c, six operations, each rounded on its own, then ambient_kernel's five per component on (rx, ry, sz).
+// ONE call site of the walk, with the arguments ambient_kernel gives it (any_ok, filters on, not one_origin, active = the lane holds a hit); groups on, as in
+// every per-ray kernel.  A wave with no hit writes its zeros / n and leaves without calling the walk; no lane leaves before the last walk, the stores come after
+// the loop, lanes beyond the batch store nothing.
+// A material index at or beyond the table (0xFFFFFFFF: a miss or a dead ray) is a miss; no value of the caller's arrays is used as an index.
+// Registers, scratch and occupancy are recorded, not tuned: profiles/ambient_rays_kernel_resources.txt.
+template <int kWalk>
+__global__ __launch_bounds__(64, kWavesPerSimd) void ambient_rays_kernel(const DevScene S, uint32_t n_rays, const AmbientRaysParams Q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const Stack stk{lds + kParkBytes, threadIdx.x};
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    const bool ok = i < n_rays;
+    const size_t j = 3 * (size_t)i;
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    // ---- the lane's record
+    bool hit = false;
+    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
+    double c = 1.0, s = 0.0;
+    if (ok && Q.material[i] < S.n_mats) {       // (0xFFFFFFFF, a miss or a dead ray, and anything else beyond the table: a miss -- shade_rays_kernel's rule)
+        hit = true;
+        p = ld3(Q.point + j); n = ld3(Q.normal + j);
+        if (Q.rot) { c = Q.rot[2 * (size_t)i]; s = Q.rot[2 * (size_t)i + 1]; }
+    }
+    const uint32_t n_samples = Q.n_samples;
+    uint32_t mask = 0;
+    if (__any(hit)) {
+        // the tangent frame of the hit, once for all samples
+        V3 tg = mk(0, 0, 0), bt = mk(0, 0, 0);
+        if (hit) tangent_frame(n, tg, bt);
+        const V3 ro = p + n * S.surface_offset;                                          // the origin of a shadow ray, raytracer.rs:170
+        for (uint32_t k = 0; k < n_samples; k++) {
+            const double sz = Q.dirs[k][2];                                              // wave-uniform
+            double sx = Q.dirs[k][0], sy = Q.dirs[k][1];
+            if (Q.rot) {                                                                 // the sample turned by the record's (c, s)
+                const double rx = sx * c - sy * s, ry = sx * s + sy * c;
+                sx = rx; sy = ry;
+            }
+            // (tg*sx + bt*sy) + n*sz, ambient_kernel's five operations per component.  (a lane without a hit takes no part; its ray is a harmless one)
+            const V3 rd = hit ? mk((tg.x * sx + bt.x * sy) + n.x * sz, (tg.y * sx + bt.y * sy) + n.y * sz, (tg.z * sx + bt.z * sy) + n.z * sz) : mk(0, 0, 1);
+            double wt; uint32_t wslot;
+            if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, hit, true, true, ro, rd, Q.max_t, wt, wslot);
+            else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, hit, true, true, false, ro, rd, Q.max_t, wt, wslot);
+            if (hit && wslot != kNone) mask |= 1u << k;
+        }
+    }
+#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
+    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
+#endif
+    if (!ok) return;
+    if (Q.occluded) Q.occluded[i] = mask;
+    if (Q.open) Q.open[i] = n_samples - (uint32_t)__popc(mask);                          // (a miss: mask 0, every ray open -- the rule of ambient_kernel's grey)
+}
 #endif   // RRT_TU_RAYS
 
 // ---- host side of the launchers below: a runtime choice of kernel as a compile-time one.  f receives a std::integral_constant and names its instantiation.
@@ -2587,6 +2646,14 @@ int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, v
     if (n == 0) return 0;
     return with_walk(effective_walk(s, walk), [&](auto w) {
         hipLaunchKernelGGL(shade_rays_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, q);
+        return (int)hipGetLastError();
+    });
+}
+
+int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, void* stream, int walk) {
+    if (n == 0) return 0;
+    return with_walk(effective_walk(s, walk), [&](auto w) {
+        hipLaunchKernelGGL(ambient_rays_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, q);
         return (int)hipGetLastError();
     });
 }
