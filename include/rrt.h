@@ -638,6 +638,50 @@ int rrt_ambient_rays(rrt_raytracer *rt, uint32_t n, const rrt_ray_surface *rec, 
 int rrt_ambient_rays_device(rrt_raytracer *rt, uint32_t n, const rrt_ray_surface *d_rec, const double *d_rot,
                             const rrt_ambient_samples *samples, const rrt_ray_ambient *d_out, void *stream);
 
+/* Stable compaction of ray batches and records, and its inverse: between two stages of a per-ray pipeline (rrt_surface_rays_device -> rrt_shade_rays_device ->
+ * rrt_ambient_rays_device) a batch thins out -- misses drop out, only mirror hits reflect, only hits have an ambient fan.  These calls move the survivors to the
+ * front of a batch that KEEPS ITS LENGTH n and fill the tail with dead entries, on the device and without a read-back of the count: the next stage is enqueued with
+ * the same n, a NaN max_t is a dead ray and material = 0xFFFFFFFF a dead record for every per-ray call, and a wave of 64 dead entries walks nothing.
+ * d_src / d_dst: two rrt_ray_set -- the rays (origins, dirs [n][3]), their bounds (max_t [n]), the rotations of rrt_ambient_rays (rot [n][2]) and the twelve
+ * arrays of an rrt_ray_surface, in the layouts of the calls that take them.  Any pointer may be NULL.  What is non-NULL in dst is gathered from the same array of
+ * src, which must then be non-NULL -- except max_t: dst.max_t with src.max_t == NULL writes +inf for the survivors, so that a batch that had no bounds gets one
+ * that can say "dead".  Arrays of src may alias each other: a record's next_origin / next_dir as src.origins / src.dirs is the intended use.  dst, index, count and
+ * scratch must overlap neither src (or flag) nor each other.
+ * select, sel[i] per entry i:
+ *   RRT_SELECT_HIT     src.rec.material[i] < n_mats -- the hit rule of rrt_shade_rays and rrt_ambient_rays; src.rec.material is required;
+ *   RRT_SELECT_MIRROR  that, and kr > 0.0 for that material in the table in force NOW (rrt_raytracer_set_materials before the call changes the selection).
+ *                      Whether depth < max_reflection_depth stays the caller's decision; src.rec.material is required;
+ *   RRT_SELECT_FLAG    flag[i] != 0; flag / d_flag [n] bytes is required (the other modes ignore it), and src and dst may both be NULL: only index and count
+ *                      are wanted then.
+ * RESULT, a stable partition:  count = the number of i with sel[i];  for j < count, index[j] = the j-th smallest such i and element j of every dst array is
+ * element index[j] of the src array, copied byte for byte -- NaN payloads and -0.0 are preserved, no arithmetic touches a value;  for count <= j < n,
+ * index[j] = 0xFFFFFFFF and element j of every dst array holds the dead value: max_t = NaN (0x7FF8000000000000), material = tri = 0xFFFFFFFF,
+ * albedo = 0x00FFFFFF, hit = 0, lights = 0, rot = (1.0, 0.0), every other double 0.0 -- the miss values of rrt_surface_rays.  index and count may each be NULL;
+ * with n > 0 at least one of index, count and the arrays of dst is set.  Every element of every requested output is written; the result is the same bits on
+ * every run.
+ * Scratch: rrt_compact_scratch_bytes(n) bytes of device memory, 4-byte aligned, whose contents before and after mean nothing: 0 for n == 0, never smaller for a
+ * larger n, about 4 bytes per 1024 entries.  The device form refuses a smaller scratch_bytes, and a NULL d_scratch when the size is above 0.
+ * rrt_compact_rays_device: everything but the structs themselves in device memory of rt's device; three small kernels enqueued on `stream` (hipStream_t, NULL =
+ * default): no allocation, no copy to the host, no synchronisation, no measurement.  These are not ray calls: rrt_last_stats stays as it was, in both forms.
+ * rrt_compact_rays: everything in host memory; blocking.  One device allocation of the call's own; only what the call reads is uploaded, only what was asked for
+ * is downloaded.
+ * rrt_scatter_rays[_device], the inverse, expands a stage's results back to source order: for j in [0, n), if index[j] < n then dst[index[j]] = src[j], elem_bytes
+ * bytes each; every other entry, 0xFFFFFFFF included, is skipped.  Elements of dst that no j names are left as they were: the caller prefills them (0 for
+ * `occluded`, samples->n for `open`).  elem_bytes is 1, 4, 8, 16 or 24, and the arrays are aligned to min(elem_bytes, 8).  An index that occurs twice gives one of
+ * the values, and no fault.  src, dst and index [n elements each] must not overlap.  The host form is blocking and carries dst up and down.
+ * RRT_ERR_INVALID_ARG, before any GPU work, before the handle is looked at, and leaving the outputs and the raytracer as they were: NULL rt; an unknown select; an
+ * elem_bytes other than the five; and with n > 0: a NULL array the mode requires, an array of dst without its array of src (max_t excepted), every output NULL,
+ * a scratch too small or NULL, a NULL index, src or dst of a scatter.  n == 0 is RRT_OK with nothing enqueued; rrt_compact_rays then writes *count = 0. */
+enum { RRT_SELECT_HIT = 0, RRT_SELECT_MIRROR = 1, RRT_SELECT_FLAG = 2 };
+typedef struct { double *origins, *dirs, *max_t, *rot; rrt_ray_surface rec; } rrt_ray_set;   /* 128 bytes; [n][3], [n][3], [n], [n][2], 12 record arrays; any may be NULL */
+size_t rrt_compact_scratch_bytes(uint32_t n);
+int rrt_compact_rays_device(rrt_raytracer *rt, uint32_t n, uint32_t select, const uint8_t *d_flag, const rrt_ray_set *d_src, const rrt_ray_set *d_dst,
+                            uint32_t *d_index, uint32_t *d_count, void *d_scratch, size_t scratch_bytes, void *stream);
+int rrt_compact_rays(rrt_raytracer *rt, uint32_t n, uint32_t select, const uint8_t *flag, const rrt_ray_set *src, const rrt_ray_set *dst,
+                     uint32_t *index, uint32_t *count);
+int rrt_scatter_rays_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_index, uint32_t elem_bytes, const void *d_src, void *d_dst, void *stream);
+int rrt_scatter_rays(rrt_raytracer *rt, uint32_t n, const uint32_t *index, uint32_t elem_bytes, const void *src, void *dst);
+
 /* The octree of a raytracer whose set-up ran on the GPU (the default), read back from its device: same layout as rrt_model_get_octree; info (may be
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */
 int rrt_raytracer_get_octree(const rrt_raytracer *rt, rrt_model_info *info, double *aabb, uint32_t *first_child, uint32_t *tri_count,

@@ -101,7 +101,13 @@ class CRayAmbient(C.Structure):      # rrt_ray_ambient, 16 bytes: host or device
     _fields_ = [(n, C.c_void_p) for n in ("occluded", "open")]
 
 
+class CRaySet(C.Structure):          # rrt_ray_set, 128 bytes: host or device pointers, NULL = array not wanted; rec = the twelve arrays of rrt_ray_surface
+    _fields_ = [(n, C.c_void_p) for n in ("origins", "dirs", "max_t", "rot")] + [("rec", CRaySurface)]
+
+
 MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
+SELECT_MODES = ("hit", "mirror", "flag")   # RRT_SELECT_HIT, RRT_SELECT_MIRROR, RRT_SELECT_FLAG
+DEAD_INDEX = 0xFFFFFFFF              # index of a tail slot of a compacted batch
 
 # The plane table: every plane of rrt_visibility, rrt_surface and rrt_ambient, in the struct's order, as (dtype, elements per sub-sample, True = one value per
 # sub-sample, [h][w][4](...), False = one per pixel, [h][w]).  Everything else the binding knows about a plane is derived from it.
@@ -131,6 +137,9 @@ RAY_SHADE_INPUTS = SHADE_INPUTS                                               # 
 _PLANES_OF[CRayAmbient] = dict(occluded=(np.uint32, 1, True), open=(np.uint32, 1, True))
 RAY_AMBIENT_OUTPUTS = tuple(_PLANES_OF[CRayAmbient])                          # the arrays of rrt_ray_ambient, in its order
 RAY_AMBIENT_INPUTS = AMBIENT_INPUTS                                           # what rrt_ambient_rays reads of an rrt_ray_surface
+# rrt_ray_set: per ENTRY of a batch the ray, its bound, the rotation of its ambient fan and the twelve arrays of its record
+_PLANES_OF[CRaySet] = dict(origins=(np.float64, 3, True), dirs=(np.float64, 3, True), max_t=(np.float64, 1, True), rot=(np.float64, 2, True), **_PLANES_OF[CRaySurface])
+RAY_SET_ARRAYS = tuple(_PLANES_OF[CRaySet])                                   # the arrays of rrt_ray_set, in its order
 
 
 class CModelInfo(C.Structure):
@@ -151,6 +160,7 @@ class CSetupTimes(C.Structure):
 STRUCTS = {"rrt_vec3": Vec3, "rrt_light": CLight, "rrt_material": CMaterial, "rrt_texture": CTexture, "rrt_options": COptions, "rrt_camera": CCamera,
            "rrt_region": CRegion, "rrt_visibility": CVisibility, "rrt_pick_result": CPickResult, "rrt_surface": CSurface,
            "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_ray_surface": CRaySurface, "rrt_ray_shade": CRayShade, "rrt_ray_ambient": CRayAmbient,
+           "rrt_ray_set": CRaySet,
            "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
 
 # every symbol include/rrt.h declares: (restype, argtypes)
@@ -219,6 +229,11 @@ SYMBOLS = {
     "rrt_shade_rays_device": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(CRaySurface), C.c_uint32, C.POINTER(CRayShade), _P]),
     "rrt_ambient_rays": (C.c_int, [_P, C.c_uint32, C.POINTER(CRaySurface), _dp, C.POINTER(CAmbientSamples), C.POINTER(CRayAmbient)]),
     "rrt_ambient_rays_device": (C.c_int, [_P, C.c_uint32, C.POINTER(CRaySurface), _P, C.POINTER(CAmbientSamples), C.POINTER(CRayAmbient), _P]),
+    "rrt_compact_scratch_bytes": (C.c_size_t, [C.c_uint32]),
+    "rrt_compact_rays_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.POINTER(CRaySet), C.POINTER(CRaySet), _P, _P, _P, C.c_size_t, _P]),
+    "rrt_compact_rays": (C.c_int, [_P, C.c_uint32, C.c_uint32, _u8p, C.POINTER(CRaySet), C.POINTER(CRaySet), _u32p, _u32p]),
+    "rrt_scatter_rays_device": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
+    "rrt_scatter_rays": (C.c_int, [_P, C.c_uint32, _u32p, C.c_uint32, _P, _P]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
@@ -484,6 +499,26 @@ def _ray_records(what: str, planes: dict, inputs=RAY_SHADE_INPUTS) -> dict:
     out (NULL for the library)."""
     rows = {name: (a,) + _ray_plane(name, what=what) for name, a in planes.items()}
     return {name: row for name, row in rows.items() if row[0] is not None and name in inputs}
+
+
+def _ray_set(arrays: dict):
+    """An rrt_ray_set of host arrays or device tensors {name: array} with names from RAY_SET_ARRAYS, by reference; None when there are none (NULL)."""
+    if not arrays:
+        return None
+    at = {n: (a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()) for n, a in arrays.items()}
+    return C.byref(CRaySet(rec=CRaySurface(**{n: p for n, p in at.items() if n in _PLANES_OF[CRaySurface]}),
+                           **{n: p for n, p in at.items() if n not in _PLANES_OF[CRaySurface]}))
+
+
+def _select(select: str, what: str) -> int:
+    if select not in SELECT_MODES:
+        raise ValueError(f"{what}: unknown select {select!r}, want one of {SELECT_MODES}")
+    return SELECT_MODES.index(select)
+
+
+def compact_scratch_bytes(n: int) -> int:
+    """rrt_compact_scratch_bytes: the device scratch compact_rays_into needs for a batch of n entries."""
+    return int(lib().rrt_compact_scratch_bytes(int(n)))
 
 
 def _bound(name: str, *args):
@@ -903,6 +938,82 @@ class RayTracer(_Handle):
         _d_keep, samples = _ambient_samples(dirs, max_t)
         _call("rrt_ambient_rays_device", self._h, n, _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), _ptr(rot_t), C.byref(samples),
               _plane_struct(CRayAmbient, out), _P(_stream(stream)))
+
+    # compaction of ray batches and records, and its inverse (rrt.h: rrt_compact_rays, rrt_scatter_rays): the survivors to the front of a batch that keeps its length
+    def compact_rays(self, planes: dict, select: str = "hit", flag=None, origins=None, dirs=None, max_t=None, rot=None) -> dict:
+        """rrt_compact_rays: {"index": uint32 [n], "count": int, name: the gathered array} for every array given -- `planes` ({name: array} as surface_rays
+        returns it, any of RAY_SURFACE_PLANES; may be empty) and origins / dirs [n][3], max_t [n], rot [n][2].  select: "hit" (material < n_mats), "mirror" (and
+        kr > 0 in the table in force) or "flag" (flag[i] != 0, uint8 [n]).  The survivors come first, in their order; the tail holds dead entries (max_t NaN,
+        material 0xFFFFFFFF, rrt.h) and index DEAD_INDEX.  max_t=True: no bound is read, the survivors get +inf."""
+        sel = _select(select, "compact_rays")
+        src = {name: np.ascontiguousarray(a, dtype) for name, (a, dtype, width) in _ray_records("compact_rays", planes, RAY_SURFACE_PLANES).items()}
+        for name, a in (("origins", origins), ("dirs", dirs), ("max_t", max_t), ("rot", rot)):
+            if a is not None and a is not True:
+                src[name] = np.ascontiguousarray(a, np.float64)
+        f = None if flag is None else np.ascontiguousarray(flag, np.uint8)
+        lead = f if sel == 2 else src.get("material")
+        assert lead is not None, f"compact_rays: select {select!r} needs {'a flag array' if sel == 2 else 'a material array'}"
+        n = lead.size
+        assert f is None or f.size == n, f"compact_rays: flag has {f.size} elements for {n} entries"
+        for name, a in src.items():
+            assert a.size == n * _ray_plane(name, CRaySet, "compact_rays")[1], f"compact_rays: array {name} has {a.size} elements for {n} entries"
+        out = {name: np.empty_like(a) for name, a in src.items()}
+        if max_t is True:
+            out["max_t"] = np.empty(n, np.float64)
+        index, count = np.empty(n, np.uint32), C.c_uint32(0)
+        _call("rrt_compact_rays", self._h, n, sel, _u8(f), _ray_set(src), _ray_set(out), _u32(index), C.byref(count))
+        return dict(out, index=index, count=int(count.value))
+
+    def compact_rays_into(self, out: dict, src: dict, select: str, index_t, count_t, scratch_t, flag_t=None, stream: Optional[int] = None):
+        """rrt_compact_rays_device: out / src = {name: contiguous device tensor} with names from RAY_SET_ARRAYS -- n elements of the array's item size, 3 n for the
+        vectors, 2 n for rot; every array of out but max_t needs its array of src.  index_t: n four-byte elements or None; count_t: one four-byte element or None;
+        scratch_t: a device tensor of at least compact_scratch_bytes(n) bytes (None for n == 0); flag_t: n bytes, for select "flag".  n is the length of flag_t
+        for "flag", of src["material"] otherwise.  Enqueued, not synchronised; last_stats stays as it was."""
+        sel = _select(select, "compact_rays_into")
+        lead = flag_t if sel == 2 else src.get("material")
+        assert lead is not None, f"compact_rays_into: select {select!r} needs {'a flag tensor' if sel == 2 else 'a material tensor'}"
+        n = _batch_size(lead, 1, "flag" if sel == 2 else "material")
+        if flag_t is not None:
+            _device_tensor(flag_t, n, 1, "flag")
+        for what, arrays in (("src", src), ("out", out)):
+            for name, t in arrays.items():
+                dtype, width = _ray_plane(name, CRaySet, "compact_rays_into")
+                _device_tensor(t, width * n, np.dtype(dtype).itemsize, f"{what} {name}")
+        if index_t is not None:
+            _device_tensor(index_t, n, 4, "index")
+        if count_t is not None:
+            _device_tensor(count_t, 1, 4, "count")
+        scratch_bytes = 0
+        if scratch_t is not None:
+            assert getattr(scratch_t, "is_cuda", False) and scratch_t.is_contiguous(), "scratch: not a contiguous device tensor"
+            scratch_bytes = scratch_t.numel() * scratch_t.element_size()
+        _call("rrt_compact_rays_device", self._h, n, sel, _ptr(flag_t), _ray_set(src), _ray_set(out), _ptr(index_t), _ptr(count_t), _ptr(scratch_t),
+              scratch_bytes, _P(_stream(stream)))
+
+    def scatter_rays(self, index, src, dst) -> np.ndarray:
+        """rrt_scatter_rays: dst[index[j]] = src[j] for every j with index[j] < n; index uint32 [n], src and dst arrays of n elements of 1, 4, 8, 16 or 24 bytes
+        (dst: a contiguous, writable array of src's dtype, written in place and returned; elements no j names stay)."""
+        idx = np.ascontiguousarray(index, np.uint32).reshape(-1)
+        n = idx.size
+        assert isinstance(dst, np.ndarray) and dst.flags.c_contiguous and dst.flags.writeable, "scatter_rays: dst is not a contiguous writable array"
+        s = np.ascontiguousarray(src, dst.dtype)
+        assert s.size == dst.size and s.nbytes == dst.nbytes and (n == 0 or s.nbytes % n == 0), f"scatter_rays: src has {s.size} elements and dst {dst.size} for {n} entries"
+        _call("rrt_scatter_rays", self._h, n, _u32(idx), s.nbytes // n if n else s.itemsize, _P(s.ctypes.data), _P(dst.ctypes.data))
+        return dst
+
+    def scatter_rays_into(self, index_t, src_t, dst_t, stream: Optional[int] = None):
+        """rrt_scatter_rays_device: index_t n four-byte elements, src_t and dst_t contiguous device tensors of n elements of 1, 4, 8, 16 or 24 bytes (k n elements
+        of a k-wide array).  Enqueued, not synchronised."""
+        n = _batch_size(index_t, 1, "index")
+        _device_tensor(index_t, n, 4, "index")
+        assert getattr(src_t, "is_cuda", False), "src: not a device tensor"
+        per, rem = divmod(src_t.numel(), n) if n else (1, 0)
+        assert rem == 0 and per >= 1, f"src: {src_t.numel()} elements for {n} entries"
+        _device_tensor(src_t, per * n, src_t.element_size(), "src")
+        _device_tensor(dst_t, per * n, src_t.element_size(), "dst")
+        _call("rrt_scatter_rays_device", self._h, n, _ptr(index_t), per * src_t.element_size(), _ptr(src_t), _ptr(dst_t), _P(_stream(stream)))
+
+    compact_scratch_bytes = staticmethod(compact_scratch_bytes)
 
     # engine.rs:196-253: chunked draw with an update after every chunk (on_update(fb, first_row, n_rows) stands in for canvas.update())
     def render_progressive(self, width: int, height: int, on_update=None, chunk_rows: int = 50) -> np.ndarray:

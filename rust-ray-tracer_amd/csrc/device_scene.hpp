@@ -212,6 +212,35 @@ struct AmbientRaysParams {
 };
 static_assert(sizeof(DevScene) + sizeof(uint64_t) + sizeof(AmbientRaysParams) < 4096, "the arguments of ambient_rays_kernel must fit the 4 KB kernel-argument segment");
 
+// Argument of the compaction kernels (compact.hip; rrt.h: rrt_compact_rays_device).  RaySetPtrs mirrors rrt_ray_set: the rays, their bounds and rotations and the
+// twelve record arrays of a batch, [n] each with the element widths of rrt.h; a null array of `dst` is not written, and only the arrays `dst` asks for are read of
+// `src` -- besides `material`, which the HIT and MIRROR selections read.  dst.max_t with a null src.max_t: +inf for the survivors.
+struct RaySetPtrs {
+    double *origins, *dirs, *max_t, *rot;
+    uint8_t* hit; double *t, *u, *v; uint32_t *tri, *albedo;
+    double *point, *normal; uint32_t *material, *lights;
+    double *next_origin, *next_dir;
+};
+static_assert(sizeof(RaySetPtrs) == 128, "RaySetPtrs mirrors rrt_ray_set: sixteen pointers");
+// A count / place block covers a tile of kCompactTile consecutive entries; the scratch holds one uint32 per tile and the total behind them.
+constexpr uint32_t kCompactTile = 1024;
+constexpr uint32_t compact_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + kCompactTile - 1) / kCompactTile); }
+struct CompactParams {
+    RaySetPtrs src, dst;
+    const uint8_t* flag;         // RRT_SELECT_FLAG
+    const DevMaterial* mats;     // RRT_SELECT_MIRROR: the resident table
+    uint32_t* index;             // [n], or null
+    uint32_t* tiles;             // the scratch: [compact_tiles(n) + 1]
+    uint32_t n, select, n_mats;
+    uint32_t any_dst;            // some array of `dst` is set (with a null `index` and none of them, only the count is wanted: nothing is placed)
+};
+
+// kernel launches (compact.hip).  Both return hipError_t cast to int; nothing is synchronised.
+// count, scan and place of q on `stream`; the total goes to q.tiles[compact_tiles(q.n)] and, if it is not null, to *d_count
+int launch_compact(const CompactParams& q, uint32_t* d_count, void* stream);
+// d_dst[d_index[j]] = d_src[j], elem_bytes (1, 4, 8, 16 or 24) each, for every j in [0, n) with d_index[j] < n
+int launch_scatter(uint32_t n, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream);
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);

@@ -2,6 +2,7 @@
 //   Frames: into a device framebuffer or a rank's tiles, into host memory, progressively.
 //   Regions of a frame: visibility and surface buffers, frames shaded and ambient occlusion from kept buffers, the pick of one pixel.
 //   Per-ray queries, the choice of the traversal variant, and the statistics of the last launch.
+//   Compaction of ray batches and records between two per-ray stages, and its inverse (compact.hip): no ray is traced, so these go past timed_launch and record.
 // Every launch goes through ONE seam: timed_launch (the raytracer's two events around it) and record (what it traced, into rrt_stats).  Every measurement of the
 // variants goes through fastest_variant.  The region calls share one check of the region (region_in_force), one launch (launch_region_frame) and, for their host
 // forms, one routine that carves the kept device allocation and copies the planes up and down (with_kept_planes).  The host forms of the per-ray queries make one
@@ -523,6 +524,96 @@ int ambient_rays_from_host(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface&
     return RRT_OK;
 }
 
+// ---- compaction of ray batches and records, and its inverse (rrt.h: rrt_compact_rays, rrt_scatter_rays).  These are not ray calls: no timed_launch, no record.
+// The sixteen arrays of an rrt_ray_set in its order, as bytes per entry ...
+constexpr size_t kRaySetArrays = 16, kRaySetMaxT = 2, kRaySetMaterial = 4 + 8;
+constexpr size_t kRaySetElem[kRaySetArrays] = {24, 24, 8, 16, 1, 8, 8, 8, 4, 4, 24, 24, 4, 4, 24, 24};
+static_assert(sizeof(rrt_ray_set) == kRaySetArrays * sizeof(void*) && sizeof(RaySetPtrs) == sizeof(rrt_ray_set), "rrt_ray_set is sixteen pointers");
+// ... as an array of pointers (a NULL struct: sixteen NULLs) and as the kernels' argument
+struct RaySetArrays { void* p[kRaySetArrays]; };
+RaySetArrays ray_set_arrays(const rrt_ray_set* s) {
+    RaySetArrays a{};
+    if (s) std::memcpy(a.p, s, sizeof a.p);
+    return a;
+}
+RaySetPtrs ray_set_ptrs(const RaySetArrays& a) {
+    RaySetPtrs q;
+    std::memcpy(&q, a.p, sizeof q);
+    return q;
+}
+size_t compact_scratch_bytes(uint32_t n) { return n ? sizeof(uint32_t) * ((size_t)compact_tiles(n) + 1) : 0; }
+// every check of a compaction but the scratch's, before any GPU work and before the handle is looked at
+void check_compact(const rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* flag, const RaySetArrays& src, const RaySetArrays& dst,
+                   const uint32_t* index, const uint32_t* count) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (select > RRT_SELECT_FLAG) throw Error{RRT_ERR_INVALID_ARG, "unknown select: want RRT_SELECT_HIT, RRT_SELECT_MIRROR or RRT_SELECT_FLAG"};
+    if (n == 0) return;
+    if (select == RRT_SELECT_FLAG ? !flag : !src.p[kRaySetMaterial])
+        throw Error{RRT_ERR_INVALID_ARG, select == RRT_SELECT_FLAG ? "null flag array: RRT_SELECT_FLAG reads it" : "null src.rec.material: RRT_SELECT_HIT and RRT_SELECT_MIRROR read it"};
+    bool any_output = index || count;
+    for (size_t k = 0; k < kRaySetArrays; k++) {
+        if (dst.p[k] && !src.p[k] && k != kRaySetMaxT) throw Error{RRT_ERR_INVALID_ARG, "an array of dst without its array of src (only max_t may be synthesised)"};
+        any_output = any_output || dst.p[k];
+    }
+    if (!any_output) throw Error{RRT_ERR_INVALID_ARG, "no output requested: index, count and every array of dst are null"};
+}
+// the kernels' argument from arrays in device memory (checked)
+CompactParams compact_params(const rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* d_flag, const RaySetArrays& d_src, const RaySetArrays& d_dst,
+                             uint32_t* d_index, void* d_scratch) {
+    CompactParams q{};
+    q.src = ray_set_ptrs(d_src); q.dst = ray_set_ptrs(d_dst);
+    q.flag = d_flag; q.mats = rt->scene.mats;
+    q.index = d_index; q.tiles = static_cast<uint32_t*>(d_scratch);
+    q.n = n; q.select = select; q.n_mats = rt->scene.n_mats;
+    for (void* p : d_dst.p) if (p) q.any_dst = 1u;
+    return q;
+}
+// Host form (checked): what the call reads up -- the flags or the materials, and the src array of every dst array; an array that src names twice goes up once --
+// the three launches on the null stream, the requested outputs down; blocking.  All of it, the scratch included, in ONE device allocation of the call's own.
+int compact_from_host(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* flag, const RaySetArrays& src, const RaySetArrays& dst, uint32_t* index, uint32_t* count) {
+    if (n == 0) { if (count) *count = 0; return RRT_OK; }
+    DeviceGuard guard(rt->device);
+    const size_t N = n;
+    HostPlane up[kRaySetArrays], down[kRaySetArrays];
+    for (size_t k = 0; k < kRaySetArrays; k++) {
+        const bool read = src.p[k] && (dst.p[k] || (k == kRaySetMaterial && select != RRT_SELECT_FLAG));
+        up[k] = plane_up(read ? src.p[k] : nullptr, kRaySetElem[k], N);
+        for (size_t e = 0; e < k; e++) if (up[k].host && up[e].host == up[k].host && up[e].elem == up[k].elem) up[k].dir = kCarve;   // an alias of up[e]: see below
+        down[k] = plane_down(dst.p[k], kRaySetElem[k], N);
+    }
+    HostPlane more[] = {plane_up(select == RRT_SELECT_FLAG ? flag : nullptr, 1, N), plane_down(index, 4, N), plane_down(count, 4, 1)};
+    const size_t scratch = compact_scratch_bytes(n);
+    size_t need = slot_bytes(scratch);
+    for (const HostPlane& p : up) if (p.host && p.dir == kUp) need += slot_bytes(p.bytes());
+    for (const HostPlane& p : down) if (p.host) need += slot_bytes(p.bytes());
+    for (const HostPlane& p : more) if (p.host) need += slot_bytes(p.bytes());
+    const DevBuf mem = dev_alloc(need);
+    DevArena arena{static_cast<char*>(mem.h), need, 0};
+    void* d_scratch = arena.take<char>(scratch);
+    for (size_t k = 0; k < kRaySetArrays; k++) {
+        if (!up[k].host) continue;
+        if (up[k].dir == kUp) { up[k].dev = arena.take<char>(up[k].bytes()); continue; }
+        for (size_t e = 0; e < k; e++) if (up[e].host == up[k].host && up[e].dir == kUp) up[k].dev = up[e].dev;
+    }
+    for (HostPlane& p : down) if (p.host) p.dev = arena.take<char>(p.bytes());
+    for (HostPlane& p : more) if (p.host) p.dev = arena.take<char>(p.bytes());
+    for (const HostPlane& p : up) if (p.host && p.dir == kUp) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
+    if (more[0].host) HIP_TRY(hipMemcpy(more[0].dev, more[0].host, more[0].bytes(), hipMemcpyHostToDevice));
+    RaySetArrays d_src{}, d_dst{};
+    for (size_t k = 0; k < kRaySetArrays; k++) { d_src.p[k] = up[k].dev; d_dst.p[k] = down[k].dev; }
+    const CompactParams q = compact_params(rt, n, select, (const uint8_t*)more[0].dev, d_src, d_dst, (uint32_t*)more[1].dev, d_scratch);
+    HIP_TRY((hipError_t)launch_compact(q, (uint32_t*)more[2].dev, nullptr));
+    for (const HostPlane& p : down) if (p.host) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
+    for (const HostPlane& p : more) if (p.host && (p.dir & kDown)) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
+    return RRT_OK;
+}
+// every check of a scatter, before any GPU work and before the handle is looked at
+void check_scatter(const rrt_raytracer* rt, uint32_t n, const uint32_t* index, uint32_t elem_bytes, const void* src, const void* dst) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8 && elem_bytes != 16 && elem_bytes != 24) throw Error{RRT_ERR_INVALID_ARG, "bad elem_bytes: want 1, 4, 8, 16 or 24"};
+    if (n && (!index || !src || !dst)) throw Error{RRT_ERR_INVALID_ARG, "null array: a scatter takes index, src and dst"};
+}
+
 }  // namespace
 
 extern "C" {
@@ -819,6 +910,58 @@ int rrt_ambient_rays_device(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface
         return device_ray_launch(rt, n, stream, [&](int variant) {
             return launch_ambient_rays(rt->scene, n, ambient_rays_params(*d_rec, d_rot, *samples, *d_out), stream, variant);
         });
+    });
+}
+
+size_t rrt_compact_scratch_bytes(uint32_t n) { return compact_scratch_bytes(n); }
+
+int rrt_compact_rays(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* flag, const rrt_ray_set* src, const rrt_ray_set* dst, uint32_t* index, uint32_t* count) {
+    return guarded([&]() -> int {
+        const RaySetArrays s = ray_set_arrays(src), d = ray_set_arrays(dst);
+        check_compact(rt, n, select, flag, s, d, index, count);
+        return compact_from_host(rt, n, select, flag, s, d, index, count);
+    });
+}
+
+int rrt_compact_rays_device(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* d_flag, const rrt_ray_set* d_src, const rrt_ray_set* d_dst,
+                            uint32_t* d_index, uint32_t* d_count, void* d_scratch, size_t scratch_bytes, void* stream) {
+    return guarded([&]() -> int {
+        const RaySetArrays s = ray_set_arrays(d_src), d = ray_set_arrays(d_dst);
+        check_compact(rt, n, select, d_flag, s, d, d_index, d_count);
+        if (n == 0) return (int)RRT_OK;
+        if (scratch_bytes < compact_scratch_bytes(n) || !d_scratch) throw Error{RRT_ERR_INVALID_ARG, "scratch too small or null: want rrt_compact_scratch_bytes(n) bytes of device memory"};
+        DeviceGuard guard(rt->device);
+        HIP_TRY((hipError_t)launch_compact(compact_params(rt, n, select, d_flag, s, d, d_index, d_scratch), d_count, stream));
+        return (int)RRT_OK;
+    });
+}
+
+int rrt_scatter_rays(rrt_raytracer* rt, uint32_t n, const uint32_t* index, uint32_t elem_bytes, const void* src, void* dst) {
+    return guarded([&]() -> int {
+        check_scatter(rt, n, index, elem_bytes, src, dst);
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        const size_t N = n;
+        HostPlane pl[] = {plane_up(index, 4, N), plane_up(src, elem_bytes, N), HostPlane{dst, elem_bytes, N, kUp | kDown}};
+        size_t need = 0;
+        for (const HostPlane& p : pl) need += slot_bytes(p.bytes());
+        const DevBuf mem = dev_alloc(need);
+        DevArena arena{static_cast<char*>(mem.h), need, 0};
+        for (HostPlane& p : pl) p.dev = arena.take<char>(p.bytes());
+        for (const HostPlane& p : pl) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
+        HIP_TRY((hipError_t)launch_scatter(n, (const uint32_t*)pl[0].dev, elem_bytes, pl[1].dev, pl[2].dev, nullptr));
+        HIP_TRY(hipMemcpy(dst, pl[2].dev, pl[2].bytes(), hipMemcpyDeviceToHost));
+        return (int)RRT_OK;
+    });
+}
+
+int rrt_scatter_rays_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream) {
+    return guarded([&]() -> int {
+        check_scatter(rt, n, d_index, elem_bytes, d_src, d_dst);
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        HIP_TRY((hipError_t)launch_scatter(n, d_index, elem_bytes, d_src, d_dst, stream));
+        return (int)RRT_OK;
     });
 }
 
