@@ -38,7 +38,7 @@ struct rrt_raytracer {
     bool variant_forced = false;
     rrt::KeptBuf host_fb;            // device framebuffer kept between rrt_render / rrt_render_progressive calls (host-framebuffer entry points), grown when a larger frame comes
     rrt::KeptBuf vis_buf;            // device planes kept between the host forms of the region calls: rrt_render_visibility, rrt_pick, rrt_render_surface,
-                                     // rrt_shade_surface, rrt_ambient_surface (frames.cpp: with_kept_planes carves it anew in every call)
+                                     // rrt_shade_surface, rrt_ambient_surface (frames.cpp: with_kept_planes carves it anew in every call; the per-ray host forms keep nothing: with_call_planes)
     rrt::KeptBuf tune_buf;           // outputs of the measurement launches of rrt_tune_rays_device
     uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records in use (built.n_chains, or 0 where the shortcut's precondition fails: create_raytracer)
     double upload_ms = 0, hip_init_ms = 0, create_ms = 0;   // set-up stages of rrt_raytracer_create besides built.ms_octree / ms_index; wall time of the whole call

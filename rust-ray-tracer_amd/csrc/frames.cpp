@@ -5,8 +5,9 @@
 //   Compaction of ray batches and records between two per-ray stages, and its inverse (compact.hip): no ray is traced, so these go past timed_launch and record.
 // Every launch goes through ONE seam: timed_launch (the raytracer's two events around it) and record (what it traced, into rrt_stats).  Every measurement of the
 // variants goes through fastest_variant.  The region calls share one check of the region (region_in_force), one launch (launch_region_frame) and, for their host
-// forms, one routine that carves the kept device allocation and copies the planes up and down (with_kept_planes).  The host forms of the per-ray queries make one
-// allocation per call (host_ray_query; shade_rays_from_host for the one call that takes records instead of origins).
+// forms, one routine that carves the kept device allocation and copies the planes up and down (with_kept_planes).  The host forms of the per-ray calls, of compaction
+// and of scatter share its sibling for a call that owns its memory (with_call_planes: one allocation per call, blocking copies, the null stream), and every per-ray
+// launch that does not measure is timed and recorded in one place (recorded_ray_launch).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -230,20 +231,40 @@ hipStream_t own_stream(rrt_raytracer* rt) {
     return rt->own_stream;
 }
 
+// The two pure pieces of a host-form call: the device bytes the wanted planes of a list need, a slot each (device_memory.hpp: slot_bytes), and their carving out of
+// an arena IN THE ORDER OF THE LIST.
+template <size_t K> size_t planes_bytes(const HostPlane (&planes)[K]) {
+    size_t need = 0;
+    for (const HostPlane& p : planes) if (p.host) need += slot_bytes(p.bytes());
+    return need;
+}
+template <size_t K> void carve_planes(HostPlane (&planes)[K], DevArena arena) {
+    for (HostPlane& p : planes) if (p.host) p.dev = arena.take<char>(p.bytes());
+}
+
 // One host-form call: the wanted planes carved out of the raytracer's kept device allocation (grown when a larger request comes) IN THE ORDER OF `planes` from offset
 // 0, each in a slot of its own (device_memory.hpp: slot_bytes); the inputs up, launch(stream) on the raytracer's own stream, the outputs down, one wait.  Blocking:
 // on return the outputs are in the caller's memory and its inputs are no longer read.
 // (a page-locked plane's copy is only enqueued: all of those are in flight before the one wait)
 template <size_t K, class Launch> void with_kept_planes(rrt_raytracer* rt, HostPlane (&planes)[K], Launch&& launch) {
-    size_t need = 0;
-    for (const HostPlane& p : planes) if (p.host) need += slot_bytes(p.bytes());
-    DevArena arena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0};
-    for (HostPlane& p : planes) if (p.host) p.dev = arena.take<char>(p.bytes());
+    const size_t need = planes_bytes(planes);
+    carve_planes(planes, DevArena{static_cast<char*>(rt->vis_buf.at_least(need)), rt->vis_buf.bytes, 0});
     const hipStream_t stream = own_stream(rt);
     for (const HostPlane& p : planes) if (p.host && (p.dir & kUp)) staged_upload(p.dev, p.host, p.bytes(), stream);
     launch(stream);
     for (const HostPlane& p : planes) if (p.host && (p.dir & kDown)) staged_download(p.host, p.dev, p.bytes(), stream);
     HIP_TRY(hipStreamSynchronize(stream));
+}
+// Its sibling for a call that owns its memory (the per-ray calls, compaction, scatter): the wanted planes carved from offset 0 of ONE device allocation made here and
+// freed on return, or on a throw -- nothing is kept between calls; the inputs up, launch() on the null stream, the outputs down, every copy blocking: no wait of its own.
+// (not one routine with with_kept_planes: kept or own allocation, own or null stream, staged or blocking copies, one wait or none -- it would branch on its caller)
+template <size_t K, class Launch> void with_call_planes(HostPlane (&planes)[K], Launch&& launch) {
+    const size_t need = planes_bytes(planes);
+    const DevBuf mem = dev_alloc(need);
+    carve_planes(planes, DevArena{static_cast<char*>(mem.h), need, 0});
+    for (const HostPlane& p : planes) if (p.host && (p.dir & kUp)) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
+    launch();
+    for (const HostPlane& p : planes) if (p.host && (p.dir & kDown)) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
 }
 
 // ---- visibility buffers.  every check of a visibility call, before any GPU work; returns the region in force
@@ -384,14 +405,18 @@ void ambient_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const
     });
 }
 
-// ---- per-ray queries.  The device forms (rrt.h: rrt_intersect_rays_device, ...): no allocation, no copy, no synchronisation; launch(variant) on the caller's stream.
+// ---- per-ray queries.  The one recorded per-ray launch that does not measure: launch(variant) of n rays on `stream`, in the variant of the device forms.
+template <class Launch> void recorded_ray_launch(rrt_raytracer* rt, uint32_t n, void* stream, Launch&& launch) {
+    const int variant = device_rays_variant(rt);
+    timed_launch(rt, stream, [&] { return launch(variant); });
+    record(rt, n, 1, n, variant);
+}
+// The device forms (rrt.h: rrt_intersect_rays_device, ...): no allocation, no copy, no synchronisation; launch(variant) on the caller's stream.
 // (device_ray_launch: the same for a call that has made its own checks -- rrt_shade_rays_device has no origins for check_rays)
 template <class Launch> int device_ray_launch(rrt_raytracer* rt, uint32_t n, void* stream, Launch&& launch) {
     if (n == 0) return RRT_OK;
     DeviceGuard guard(rt->device);
-    const int variant = device_rays_variant(rt);
-    timed_launch(rt, stream, [&] { return launch(variant); });
-    record(rt, n, 1, n, variant);
+    recorded_ray_launch(rt, n, stream, launch);
     return RRT_OK;
 }
 template <class Launch> int device_ray_query(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, bool any_output, void* stream, Launch&& launch) {
@@ -399,34 +424,28 @@ template <class Launch> int device_ray_query(rrt_raytracer* rt, uint32_t n, cons
     return device_ray_launch(rt, n, stream, launch);
 }
 // The host forms: rays and the optional max_t up, launch(m, d_origins, d_dirs, d_max_t, d_out, variant) on the null stream (the variant by rays_variant, measured on a
-// first large batch), every output down; blocking.  All of it in ONE device allocation of the call's own: nothing is kept between calls.
+// first large batch), every output down; blocking (with_call_planes).  out[k]: the caller's array of output k as a plane of n elements (plane_down).
 // kEveryOutput: the call wants each of its outputs; kAnyOutput (rrt_surface_rays): one at least -- a null output gets no device memory, d_out[k] is null for the
 // launch and nothing is downloaded for it.
-struct HostOut { void* host; size_t elem; };   // an output array of the caller's and its bytes per ray
 enum OutputRule { kEveryOutput, kAnyOutput };
 template <size_t K, class Launch>
-int host_ray_query(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, const HostOut (&out)[K], Launch&& launch,
+int host_ray_query(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, const HostPlane (&out)[K], Launch&& launch,
                    OutputRule rule = kEveryOutput) {
     bool every_output = true, any_output = false;
-    for (const HostOut& o : out) { every_output = every_output && o.host; any_output = any_output || o.host; }
+    for (const HostPlane& o : out) { every_output = every_output && o.host; any_output = any_output || o.host; }
     check_rays(rt, n, origins, dirs, rule == kAnyOutput ? any_output : every_output);
     if (n == 0) return RRT_OK;
     DeviceGuard guard(rt->device);
-    const size_t N = n;
-    size_t need = 2 * slot_bytes(24 * N) + (max_t ? slot_bytes(8 * N) : 0);
-    for (const HostOut& o : out) if (o.host) need += slot_bytes(o.elem * N);
-    const DevBuf mem = dev_alloc(need);
-    DevArena arena{static_cast<char*>(mem.h), need, 0};
-    double *d_o = arena.take<double>(3 * N), *d_d = arena.take<double>(3 * N), *d_m = max_t ? arena.take<double>(N) : nullptr;
-    void* d_out[K];
-    for (size_t k = 0; k < K; k++) d_out[k] = out[k].host ? arena.take<char>(out[k].elem * N) : nullptr;
-    HIP_TRY(hipMemcpy(d_o, origins, 24 * N, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, dirs, 24 * N, hipMemcpyHostToDevice));
-    if (max_t) HIP_TRY(hipMemcpy(d_m, max_t, 8 * N, hipMemcpyHostToDevice));
-    const int variant = rays_variant(rt, n, [&](uint32_t m, int v) { return launch(m, d_o, d_d, d_m, d_out, v); });
-    timed_launch(rt, nullptr, [&] { return launch(n, d_o, d_d, d_m, d_out, variant); });
-    record(rt, n, 1, n, variant);
-    for (size_t k = 0; k < K; k++) if (out[k].host) HIP_TRY(hipMemcpy(out[k].host, d_out[k], out[k].elem * N, hipMemcpyDeviceToHost));
+    HostPlane pl[3 + K] = {plane_up(origins, 24, n), plane_up(dirs, 24, n), plane_up(max_t, 8, n)};
+    std::copy(out, out + K, pl + 3);
+    with_call_planes(pl, [&] {
+        const double *d_o = (const double*)pl[0].dev, *d_d = (const double*)pl[1].dev, *d_m = (const double*)pl[2].dev;
+        void* d_out[K];
+        for (size_t k = 0; k < K; k++) d_out[k] = pl[3 + k].dev;
+        const int variant = rays_variant(rt, n, [&](uint32_t m, int v) { return launch(m, d_o, d_d, d_m, d_out, v); });
+        timed_launch(rt, nullptr, [&] { return launch(n, d_o, d_d, d_m, d_out, variant); });
+        record(rt, n, 1, n, variant);
+    });
     return RRT_OK;
 }
 
@@ -457,28 +476,20 @@ void check_shade_rays(const rrt_raytracer* rt, uint32_t n, const double* dirs, c
 ShadeRaysParams shade_rays_params(const double* d_dirs, const rrt_ray_surface& d_rec, uint32_t depth, const rrt_ray_shade& d_out) {
     return ShadeRaysParams{d_dirs, d_rec.point, d_rec.normal, d_rec.material, d_rec.albedo, d_rec.lights, d_out.colour, d_out.local, d_out.kr, depth, 0u};
 }
-// Host form (checked), host_ray_query's sibling for a call without origins: the directions and the four or five arrays it reads up, one launch on the null stream
-// in the variant of the device forms -- nothing is measured: there are no origins to measure a walk on -- the requested outputs down; blocking.  All of it in ONE
-// device allocation of the call's own.
+// Host form (checked), for a call without origins: the directions and the four or five arrays it reads up, one launch on the null stream in the variant of the
+// device forms -- nothing is measured: there are no origins to measure a walk on -- the requested outputs down; blocking (with_call_planes).
 int shade_rays_from_host(rrt_raytracer* rt, uint32_t n, const double* dirs, const rrt_ray_surface& rec, uint32_t depth, const rrt_ray_shade& out) {
     if (n == 0) return RRT_OK;
     DeviceGuard guard(rt->device);
     const size_t N = n;
     HostPlane pl[] = {plane_up(dirs, 24, N), plane_up(rec.point, 24, N), plane_up(rec.normal, 24, N), plane_up(rec.material, 4, N), plane_up(rec.albedo, 4, N),
                       plane_up(rec.lights, 4, N), plane_down(out.colour, 4, N), plane_down(out.local, 24, N), plane_down(out.kr, 8, N)};
-    size_t need = 0;
-    for (const HostPlane& p : pl) if (p.host) need += slot_bytes(p.bytes());
-    const DevBuf mem = dev_alloc(need);
-    DevArena arena{static_cast<char*>(mem.h), need, 0};
-    for (HostPlane& p : pl) if (p.host) p.dev = arena.take<char>(p.bytes());
-    for (const HostPlane& p : pl) if (p.host && (p.dir & kUp)) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
-    rrt_ray_surface d_rec{};
-    d_rec.point = (double*)pl[1].dev; d_rec.normal = (double*)pl[2].dev; d_rec.material = (uint32_t*)pl[3].dev; d_rec.albedo = (uint32_t*)pl[4].dev; d_rec.lights = (uint32_t*)pl[5].dev;
-    const ShadeRaysParams q = shade_rays_params((const double*)pl[0].dev, d_rec, depth, rrt_ray_shade{(uint32_t*)pl[6].dev, (double*)pl[7].dev, (double*)pl[8].dev});
-    const int variant = device_rays_variant(rt);
-    timed_launch(rt, nullptr, [&] { return launch_shade_rays(rt->scene, n, q, nullptr, variant); });
-    record(rt, n, 1, n, variant);
-    for (const HostPlane& p : pl) if (p.host && (p.dir & kDown)) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
+    with_call_planes(pl, [&] {
+        rrt_ray_surface d_rec{};
+        d_rec.point = (double*)pl[1].dev; d_rec.normal = (double*)pl[2].dev; d_rec.material = (uint32_t*)pl[3].dev; d_rec.albedo = (uint32_t*)pl[4].dev; d_rec.lights = (uint32_t*)pl[5].dev;
+        const ShadeRaysParams q = shade_rays_params((const double*)pl[0].dev, d_rec, depth, rrt_ray_shade{(uint32_t*)pl[6].dev, (double*)pl[7].dev, (double*)pl[8].dev});
+        recorded_ray_launch(rt, n, nullptr, [&](int variant) { return launch_shade_rays(rt->scene, n, q, nullptr, variant); });
+    });
     return RRT_OK;
 }
 
@@ -500,27 +511,20 @@ AmbientRaysParams ambient_rays_params(const rrt_ray_surface& d_rec, const double
     std::memcpy(q.dirs, samples.dirs, sizeof(double) * 3 * samples.n);
     return q;
 }
-// Host form (checked), shade_rays_from_host's sibling: the three arrays and the optional rotations up, one launch on the null stream in the variant of the device
-// forms -- nothing is measured -- the requested outputs down; blocking.  All of it in ONE device allocation of the call's own.
+// Host form (checked): the three arrays and the optional rotations up, one launch on the null stream in the variant of the device forms -- nothing is measured --
+// the requested outputs down; blocking (with_call_planes).
 int ambient_rays_from_host(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface& rec, const double* rot, const rrt_ambient_samples& samples, const rrt_ray_ambient& out) {
     if (n == 0) return RRT_OK;
     DeviceGuard guard(rt->device);
     const size_t N = n;
     HostPlane pl[] = {plane_up(rec.point, 24, N), plane_up(rec.normal, 24, N), plane_up(rec.material, 4, N), plane_up(rot, 16, N),
                       plane_down(out.occluded, 4, N), plane_down(out.open, 4, N)};
-    size_t need = 0;
-    for (const HostPlane& p : pl) if (p.host) need += slot_bytes(p.bytes());
-    const DevBuf mem = dev_alloc(need);
-    DevArena arena{static_cast<char*>(mem.h), need, 0};
-    for (HostPlane& p : pl) if (p.host) p.dev = arena.take<char>(p.bytes());
-    for (const HostPlane& p : pl) if (p.host && (p.dir & kUp)) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
-    rrt_ray_surface d_rec{};
-    d_rec.point = (double*)pl[0].dev; d_rec.normal = (double*)pl[1].dev; d_rec.material = (uint32_t*)pl[2].dev;
-    const AmbientRaysParams q = ambient_rays_params(d_rec, (const double*)pl[3].dev, samples, rrt_ray_ambient{(uint32_t*)pl[4].dev, (uint32_t*)pl[5].dev});
-    const int variant = device_rays_variant(rt);
-    timed_launch(rt, nullptr, [&] { return launch_ambient_rays(rt->scene, n, q, nullptr, variant); });
-    record(rt, n, 1, n, variant);
-    for (const HostPlane& p : pl) if (p.host && (p.dir & kDown)) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
+    with_call_planes(pl, [&] {
+        rrt_ray_surface d_rec{};
+        d_rec.point = (double*)pl[0].dev; d_rec.normal = (double*)pl[1].dev; d_rec.material = (uint32_t*)pl[2].dev;
+        const AmbientRaysParams q = ambient_rays_params(d_rec, (const double*)pl[3].dev, samples, rrt_ray_ambient{(uint32_t*)pl[4].dev, (uint32_t*)pl[5].dev});
+        recorded_ray_launch(rt, n, nullptr, [&](int variant) { return launch_ambient_rays(rt->scene, n, q, nullptr, variant); });
+    });
     return RRT_OK;
 }
 
@@ -568,43 +572,31 @@ CompactParams compact_params(const rrt_raytracer* rt, uint32_t n, uint32_t selec
     for (void* p : d_dst.p) if (p) q.any_dst = 1u;
     return q;
 }
-// Host form (checked): what the call reads up -- the flags or the materials, and the src array of every dst array; an array that src names twice goes up once --
-// the three launches on the null stream, the requested outputs down; blocking.  All of it, the scratch included, in ONE device allocation of the call's own.
+// Host form (checked): what the call reads up -- the src array of every dst array, the materials or the flags -- the three launches on the null stream, the
+// requested outputs down; blocking (with_call_planes: the scratch is its first plane).  A host array that src names twice (the intended use: next_origin as
+// origins, next_dir as dirs) goes up once: the later entry is no plane of the list and reads the device copy of the earlier one, from[k].
 int compact_from_host(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* flag, const RaySetArrays& src, const RaySetArrays& dst, uint32_t* index, uint32_t* count) {
     if (n == 0) { if (count) *count = 0; return RRT_OK; }
     DeviceGuard guard(rt->device);
     const size_t N = n;
-    HostPlane up[kRaySetArrays], down[kRaySetArrays];
+    enum : size_t { kScratch, kSrc, kDst = kSrc + kRaySetArrays, kFlag = kDst + kRaySetArrays, kIndex, kCount, kEnd };
+    HostPlane pl[kEnd];
+    pl[kScratch] = HostPlane{rt, 1, compact_scratch_bytes(n), kCarve};     // (only carved: a host pointer that is not null says it is wanted)
+    size_t from[kRaySetArrays];
     for (size_t k = 0; k < kRaySetArrays; k++) {
         const bool read = src.p[k] && (dst.p[k] || (k == kRaySetMaterial && select != RRT_SELECT_FLAG));
-        up[k] = plane_up(read ? src.p[k] : nullptr, kRaySetElem[k], N);
-        for (size_t e = 0; e < k; e++) if (up[k].host && up[e].host == up[k].host && up[e].elem == up[k].elem) up[k].dir = kCarve;   // an alias of up[e]: see below
-        down[k] = plane_down(dst.p[k], kRaySetElem[k], N);
+        from[k] = kSrc + k;
+        for (size_t e = 0; read && e < k; e++) if (pl[kSrc + e].host == src.p[k] && kRaySetElem[e] == kRaySetElem[k]) from[k] = kSrc + e;
+        pl[kSrc + k] = plane_up(read && from[k] == kSrc + k ? src.p[k] : nullptr, kRaySetElem[k], N);
+        pl[kDst + k] = plane_down(dst.p[k], kRaySetElem[k], N);
     }
-    HostPlane more[] = {plane_up(select == RRT_SELECT_FLAG ? flag : nullptr, 1, N), plane_down(index, 4, N), plane_down(count, 4, 1)};
-    const size_t scratch = compact_scratch_bytes(n);
-    size_t need = slot_bytes(scratch);
-    for (const HostPlane& p : up) if (p.host && p.dir == kUp) need += slot_bytes(p.bytes());
-    for (const HostPlane& p : down) if (p.host) need += slot_bytes(p.bytes());
-    for (const HostPlane& p : more) if (p.host) need += slot_bytes(p.bytes());
-    const DevBuf mem = dev_alloc(need);
-    DevArena arena{static_cast<char*>(mem.h), need, 0};
-    void* d_scratch = arena.take<char>(scratch);
-    for (size_t k = 0; k < kRaySetArrays; k++) {
-        if (!up[k].host) continue;
-        if (up[k].dir == kUp) { up[k].dev = arena.take<char>(up[k].bytes()); continue; }
-        for (size_t e = 0; e < k; e++) if (up[e].host == up[k].host && up[e].dir == kUp) up[k].dev = up[e].dev;
-    }
-    for (HostPlane& p : down) if (p.host) p.dev = arena.take<char>(p.bytes());
-    for (HostPlane& p : more) if (p.host) p.dev = arena.take<char>(p.bytes());
-    for (const HostPlane& p : up) if (p.host && p.dir == kUp) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
-    if (more[0].host) HIP_TRY(hipMemcpy(more[0].dev, more[0].host, more[0].bytes(), hipMemcpyHostToDevice));
-    RaySetArrays d_src{}, d_dst{};
-    for (size_t k = 0; k < kRaySetArrays; k++) { d_src.p[k] = up[k].dev; d_dst.p[k] = down[k].dev; }
-    const CompactParams q = compact_params(rt, n, select, (const uint8_t*)more[0].dev, d_src, d_dst, (uint32_t*)more[1].dev, d_scratch);
-    HIP_TRY((hipError_t)launch_compact(q, (uint32_t*)more[2].dev, nullptr));
-    for (const HostPlane& p : down) if (p.host) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
-    for (const HostPlane& p : more) if (p.host && (p.dir & kDown)) HIP_TRY(hipMemcpy(p.host, p.dev, p.bytes(), hipMemcpyDeviceToHost));
+    pl[kFlag] = plane_up(select == RRT_SELECT_FLAG ? flag : nullptr, 1, N); pl[kIndex] = plane_down(index, 4, N); pl[kCount] = plane_down(count, 4, 1);
+    with_call_planes(pl, [&] {
+        RaySetArrays d_src{}, d_dst{};
+        for (size_t k = 0; k < kRaySetArrays; k++) { d_src.p[k] = pl[from[k]].dev; d_dst.p[k] = pl[kDst + k].dev; }
+        const CompactParams q = compact_params(rt, n, select, (const uint8_t*)pl[kFlag].dev, d_src, d_dst, (uint32_t*)pl[kIndex].dev, pl[kScratch].dev);
+        HIP_TRY((hipError_t)launch_compact(q, (uint32_t*)pl[kCount].dev, nullptr));
+    });
     return RRT_OK;
 }
 // every check of a scatter, before any GPU work and before the handle is looked at
@@ -805,7 +797,7 @@ int rrt_render_progressive(rrt_raytracer* rt, uint32_t width, uint32_t height, u
 
 int rrt_get_ray_colours(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, uint32_t* colours) {
     return guarded([&]() -> int {
-        const HostOut out[] = {{colours, 4}};
+        const HostPlane out[] = {plane_down(colours, 4, n)};
         return host_ray_query(rt, n, origins, dirs, nullptr, out, [&](uint32_t m, const double* o, const double* d, const double*, void* const* x, int variant) {
             return launch_ray_colours(rt->scene, m, o, d, (uint32_t*)x[0], nullptr, variant);
         });
@@ -816,7 +808,7 @@ int rrt_get_ray_colours(rrt_raytracer* rt, uint32_t n, const double* origins, co
 int rrt_intersect_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t,
                        uint8_t* hit, double* t, double* u, double* v, uint32_t* tri) {
     return guarded([&]() -> int {
-        const HostOut out[] = {{hit, 1}, {t, 8}, {u, 8}, {v, 8}, {tri, 4}};
+        const HostPlane out[] = {plane_down(hit, 1, n), plane_down(t, 8, n), plane_down(u, 8, n), plane_down(v, 8, n), plane_down(tri, 4, n)};
         return host_ray_query(rt, n, origins, dirs, max_t, out, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
             return launch_intersect(rt->scene, m, o, d, mt, (uint8_t*)x[0], (double*)x[1], (double*)x[2], (double*)x[3], (uint32_t*)x[4], nullptr, variant);
         });
@@ -825,7 +817,7 @@ int rrt_intersect_rays(rrt_raytracer* rt, uint32_t n, const double* origins, con
 
 int rrt_occluded_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, uint8_t* occluded) {
     return guarded([&]() -> int {
-        const HostOut out[] = {{occluded, 1}};
+        const HostPlane out[] = {plane_down(occluded, 1, n)};
         return host_ray_query(rt, n, origins, dirs, max_t, out, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
             return launch_occlusion(rt->scene, m, o, d, mt, (uint8_t*)x[0], nullptr, variant);
         });
@@ -860,13 +852,13 @@ int rrt_occluded_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_orig
 int rrt_surface_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, const rrt_ray_surface* out) {
     return guarded([&]() -> int {
         (void)ray_surface_wanted(rt, out);                                 // (whether one is asked for is host_ray_query's own check: kAnyOutput)
-        void* const host[kRaySurfaceArrays] = {out->hit, out->t, out->u, out->v, out->tri, out->albedo, out->point, out->normal, out->material, out->lights,
-                                               out->next_origin, out->next_dir};
-        HostOut arrays[kRaySurfaceArrays];
-        for (size_t k = 0; k < kRaySurfaceArrays; k++) arrays[k] = HostOut{host[k], kRaySurfaceElem[k]};
+        void* host[kRaySurfaceArrays];
+        std::memcpy(host, out, sizeof host);
+        HostPlane arrays[kRaySurfaceArrays];
+        for (size_t k = 0; k < kRaySurfaceArrays; k++) arrays[k] = plane_down(host[k], kRaySurfaceElem[k], n);
         return host_ray_query(rt, n, origins, dirs, max_t, arrays, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
-            const rrt_ray_surface dev{(uint8_t*)x[0], (double*)x[1], (double*)x[2], (double*)x[3], (uint32_t*)x[4], (uint32_t*)x[5], (double*)x[6], (double*)x[7],
-                                      (uint32_t*)x[8], (uint32_t*)x[9], (double*)x[10], (double*)x[11]};
+            rrt_ray_surface dev;
+            std::memcpy(&dev, x, sizeof dev);
             return launch_surface_rays(rt->scene, m, o, d, mt, ray_surface_params(dev), nullptr, variant);
         }, kAnyOutput);
     });
@@ -941,16 +933,8 @@ int rrt_scatter_rays(rrt_raytracer* rt, uint32_t n, const uint32_t* index, uint3
         check_scatter(rt, n, index, elem_bytes, src, dst);
         if (n == 0) return (int)RRT_OK;
         DeviceGuard guard(rt->device);
-        const size_t N = n;
-        HostPlane pl[] = {plane_up(index, 4, N), plane_up(src, elem_bytes, N), HostPlane{dst, elem_bytes, N, kUp | kDown}};
-        size_t need = 0;
-        for (const HostPlane& p : pl) need += slot_bytes(p.bytes());
-        const DevBuf mem = dev_alloc(need);
-        DevArena arena{static_cast<char*>(mem.h), need, 0};
-        for (HostPlane& p : pl) p.dev = arena.take<char>(p.bytes());
-        for (const HostPlane& p : pl) HIP_TRY(hipMemcpy(p.dev, p.host, p.bytes(), hipMemcpyHostToDevice));
-        HIP_TRY((hipError_t)launch_scatter(n, (const uint32_t*)pl[0].dev, elem_bytes, pl[1].dev, pl[2].dev, nullptr));
-        HIP_TRY(hipMemcpy(dst, pl[2].dev, pl[2].bytes(), hipMemcpyDeviceToHost));
+        HostPlane pl[] = {plane_up(index, 4, n), plane_up(src, elem_bytes, n), HostPlane{dst, elem_bytes, n, kUp | kDown}};   // (dst up too: the entries no index names keep their values)
+        with_call_planes(pl, [&] { HIP_TRY((hipError_t)launch_scatter(n, (const uint32_t*)pl[0].dev, elem_bytes, pl[1].dev, pl[2].dev, nullptr)); });
         return (int)RRT_OK;
     });
 }

@@ -2607,55 +2607,40 @@ template int launch_region_lane_ray(const DevScene&, const AmbientParams&, void*
 #endif   // RRT_TU_LANE
 
 #if RRT_TU_RAYS
-// The per-ray launchers: one lane per ray, 64 rays per block; the bundle filter's fallback is launch_render's.
-int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk) {
+// The per-ray launchers: one lane per ray, 64 rays per block; the bundle filter's fallback is launch_render's.  kernel_of(w) names the kernel's instantiation for
+// walk w; its arguments are the scene, n and args.
+template <class KernelOf, class... Args>
+int launch_per_ray(const DevScene& s, uint32_t n, void* stream, int walk, KernelOf&& kernel_of, const Args&... args) {
     if (n == 0) return 0;
     return with_walk(effective_walk(s, walk), [&](auto w) {
-        hipLaunchKernelGGL(ray_colour_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_colours);
+        hipLaunchKernelGGL(kernel_of(w), dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, args...);
         return (int)hipGetLastError();
     });
+}
+
+int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk) {
+    return launch_per_ray(s, n, stream, walk, [](auto w) { return &ray_colour_kernel<w()>; }, d_origins, d_dirs, d_colours);
 }
 
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
                      uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream, int walk) {
-    if (n == 0) return 0;
-    return with_walk(effective_walk(s, walk), [&](auto w) {
-        hipLaunchKernelGGL(intersect_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t,
-                           d_hit, d_t, d_u, d_v, d_tri);
-        return (int)hipGetLastError();
-    });
+    return launch_per_ray(s, n, stream, walk, [](auto w) { return &intersect_kernel<w()>; }, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
 }
 
 int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream, int walk) {
-    if (n == 0) return 0;
-    return with_walk(effective_walk(s, walk), [&](auto w) {
-        hipLaunchKernelGGL(occlusion_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, d_occluded);
-        return (int)hipGetLastError();
-    });
+    return launch_per_ray(s, n, stream, walk, [](auto w) { return &occlusion_kernel<w()>; }, d_origins, d_dirs, d_max_t, d_occluded);
 }
 
 int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, void* stream, int walk) {
-    if (n == 0) return 0;
-    return with_walk(effective_walk(s, walk), [&](auto w) {
-        hipLaunchKernelGGL(surface_rays_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, d_origins, d_dirs, d_max_t, q);
-        return (int)hipGetLastError();
-    });
+    return launch_per_ray(s, n, stream, walk, [](auto w) { return &surface_rays_kernel<w()>; }, d_origins, d_dirs, d_max_t, q);
 }
 
 int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, void* stream, int walk) {
-    if (n == 0) return 0;
-    return with_walk(effective_walk(s, walk), [&](auto w) {
-        hipLaunchKernelGGL(shade_rays_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, q);
-        return (int)hipGetLastError();
-    });
+    return launch_per_ray(s, n, stream, walk, [](auto w) { return &shade_rays_kernel<w()>; }, q);
 }
 
 int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, void* stream, int walk) {
-    if (n == 0) return 0;
-    return with_walk(effective_walk(s, walk), [&](auto w) {
-        hipLaunchKernelGGL(ambient_rays_kernel<w()>, dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, q);
-        return (int)hipGetLastError();
-    });
+    return launch_per_ray(s, n, stream, walk, [](auto w) { return &ambient_rays_kernel<w()>; }, q);
 }
 #endif   // RRT_TU_RAYS
 

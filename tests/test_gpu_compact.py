@@ -160,6 +160,18 @@ def test_the_synthesised_bound(rrt, teapot):
     assert int(bits(got["max_t"])[-1]) == 0x7FF8000000000000
 
 
+@pytest.mark.parametrize("n", (1, 1025))
+def test_a_host_array_named_twice_in_src(rrt, teapot, n):
+    """The intended use of the host form (rrt.h): next_origin as origins, next_dir as dirs -- the same two ndarrays twice, so src holds equal pointers."""
+    rt = rrt.RayTracer(teapot, rrt.default_lights())
+    rng = np.random.default_rng(2 * n + 1)
+    A, B = rng.standard_normal((n, 3)), rng.standard_normal((n, 3))
+    assert not np.array_equal(A, B)
+    flag = flag_patterns(n)["a random half"]
+    got = rt.compact_rays(dict(next_origin=A, next_dir=B), "flag", flag=flag, origins=A, dirs=B)
+    assert_compacted(got, compacted(flag != 0, dict(origins=A, dirs=B, next_origin=A, next_dir=B)), f"n = {n}: two host arrays, each named twice")
+
+
 # ------------------------------------------------------------------ 4
 def test_mirror_on_the_mirror_room(rrt):
     A = mirror_room()
