@@ -682,6 +682,44 @@ int rrt_compact_rays(rrt_raytracer *rt, uint32_t n, uint32_t select, const uint8
 int rrt_scatter_rays_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_index, uint32_t elem_bytes, const void *d_src, void *d_dst, void *stream);
 int rrt_scatter_rays(rrt_raytracer *rt, uint32_t n, const uint32_t *index, uint32_t elem_bytes, const void *src, void *dst);
 
+/* Stable sort of ray batches and records by a coherence key: the other half of a wavefront pipeline.  Compaction removes the dead lanes and keeps the caller's
+ * order; this call puts entries that start in the same part of the scene and head the same way next to each other, for batches that are not coherent to begin
+ * with (probes, random rays, second-bounce records, the sources of rotated ambient fans).  The batch KEEPS ITS LENGTH n, dead entries go to the tail, and `index`
+ * is what rrt_scatter_rays[_device] takes to bring a stage's results back to source order.
+ * KEYS, one uint32 per entry; 0xFFFFFFFF means "dead" and sorts last.  key_mode:
+ *   RRT_SORT_KEY_GIVEN   keys[i] as the caller wrote it; keys / d_keys [n] is required (the other modes ignore it), and src and dst may both be NULL;
+ *   RRT_SORT_KEY_RAY     src.origins and src.dirs are required.  Dead if src.max_t is given and !(max_t[i] > 0.0) -- the dead-ray rule of the per-ray calls, NaN
+ *                        counts as dead; otherwise p = origins[i], d = dirs[i];
+ *   RRT_SORT_KEY_RECORD  src.rec.point, .normal and .material are required.  Dead if material[i] >= n_mats -- the hit rule of rrt_shade_rays and rrt_ambient_rays;
+ *                        otherwise p = point[i], d = normal[i].
+ * An alive key is formed with the root box lo, hi in force NOW (node 0 of rrt_raytracer_get_octree; rrt_raytracer_set_triangles may change it).  Per axis a
+ * (x = 0, y = 1, z = 2): s_a = 512.0 / (hi.a - lo.a), one f64 division on the host;  q = (p.a - lo.a) * s_a, two f64 operations, each rounded;
+ * cell_a = q >= 511.0 ? 511 : (q > 0.0 ? (uint32)q : 0), so that a NaN q gives 0, +inf 511 and -inf 0.  Key bit 3 b + a is bit b of cell_a for b = 0..8 (a Morton
+ * code of 512^3 cells), key bit 27 + a is d.a < 0.0 (-0.0 and NaN give 0), bits 30 and 31 are 0.  No value of the caller's arrays is used as an index.
+ * RESULT, a stable sort, ascending:  index is the permutation with key[index[j]] non-decreasing, entries with equal keys -- the dead ones among them, in the tail --
+ * in source order;  keys_out[j] = key[index[j]];  count = the number of keys that are not 0xFFFFFFFF;  element j of every non-NULL array of dst is element index[j]
+ * of the same array of src, copied byte for byte -- NaN payloads and -0.0 are preserved -- the tail like the rest: a pure permutation, nothing is filled in, and
+ * every array of dst needs its array of src (there is no max_t exception here).  index, keys_out, count and the arrays of dst may each be NULL; with n > 0 at least
+ * one of them is set.  Every element of every requested output is written; the result is the same bits on every run.  Arrays of src may alias each other; dst,
+ * index, keys_out, count and scratch must overlap neither src (or keys) nor each other.
+ * Scratch: rrt_sort_scratch_bytes(n) bytes of device memory, 4-byte aligned, whose contents before and after mean nothing: 0 for n == 0, a multiple of 4, never
+ * smaller for a larger n, at most 20 n + 65536 (16 bytes per entry for two (key, index) buffer pairs, 1 KB of digit counts per 4096 entries, 1 KB of totals).  The
+ * device form refuses a smaller scratch_bytes and a NULL d_scratch.
+ * rrt_sort_rays_device: everything but the structs themselves in device memory of rt's device; the kernels of a four-pass radix sort enqueued on `stream`
+ * (hipStream_t, NULL = default): no allocation, no copy to the host, no synchronisation, no measurement.  These are not ray calls: rrt_last_stats stays as it was,
+ * in both forms.
+ * rrt_sort_rays: everything in host memory; blocking.  One device allocation of the call's own; only what the call reads is uploaded, only what was asked for is
+ * downloaded.
+ * RRT_ERR_INVALID_ARG, before any GPU work, before the handle is looked at, and leaving the outputs and the raytracer as they were: NULL rt; an unknown key_mode;
+ * and with n > 0: a NULL array the mode requires, an array of dst without its array of src, every output NULL, a scratch too small or NULL.  n == 0 is RRT_OK with
+ * nothing enqueued; rrt_sort_rays then writes *count = 0. */
+enum { RRT_SORT_KEY_GIVEN = 0, RRT_SORT_KEY_RAY = 1, RRT_SORT_KEY_RECORD = 2 };
+size_t rrt_sort_scratch_bytes(uint32_t n);
+int rrt_sort_rays_device(rrt_raytracer *rt, uint32_t n, uint32_t key_mode, const uint32_t *d_keys, const rrt_ray_set *d_src, const rrt_ray_set *d_dst,
+                         uint32_t *d_index, uint32_t *d_keys_out, uint32_t *d_count, void *d_scratch, size_t scratch_bytes, void *stream);
+int rrt_sort_rays(rrt_raytracer *rt, uint32_t n, uint32_t key_mode, const uint32_t *keys, const rrt_ray_set *src, const rrt_ray_set *dst,
+                  uint32_t *index, uint32_t *keys_out, uint32_t *count);
+
 /* The octree of a raytracer whose set-up ran on the GPU (the default), read back from its device: same layout as rrt_model_get_octree; info (may be
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */
 int rrt_raytracer_get_octree(const rrt_raytracer *rt, rrt_model_info *info, double *aabb, uint32_t *first_child, uint32_t *tri_count,

@@ -108,6 +108,8 @@ class CRaySet(C.Structure):          # rrt_ray_set, 128 bytes: host or device po
 MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
 SELECT_MODES = ("hit", "mirror", "flag")   # RRT_SELECT_HIT, RRT_SELECT_MIRROR, RRT_SELECT_FLAG
 DEAD_INDEX = 0xFFFFFFFF              # index of a tail slot of a compacted batch
+SORT_KEY_MODES = ("given", "ray", "record")   # RRT_SORT_KEY_GIVEN, RRT_SORT_KEY_RAY, RRT_SORT_KEY_RECORD
+DEAD_KEY = 0xFFFFFFFF                # sort key of a dead entry: it sorts last
 
 # The plane table: every plane of rrt_visibility, rrt_surface and rrt_ambient, in the struct's order, as (dtype, elements per sub-sample, True = one value per
 # sub-sample, [h][w][4](...), False = one per pixel, [h][w]).  Everything else the binding knows about a plane is derived from it.
@@ -234,6 +236,9 @@ SYMBOLS = {
     "rrt_compact_rays": (C.c_int, [_P, C.c_uint32, C.c_uint32, _u8p, C.POINTER(CRaySet), C.POINTER(CRaySet), _u32p, _u32p]),
     "rrt_scatter_rays_device": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     "rrt_scatter_rays": (C.c_int, [_P, C.c_uint32, _u32p, C.c_uint32, _P, _P]),
+    "rrt_sort_scratch_bytes": (C.c_size_t, [C.c_uint32]),
+    "rrt_sort_rays_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.POINTER(CRaySet), C.POINTER(CRaySet), _P, _P, _P, _P, C.c_size_t, _P]),
+    "rrt_sort_rays": (C.c_int, [_P, C.c_uint32, C.c_uint32, _u32p, C.POINTER(CRaySet), C.POINTER(CRaySet), _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
@@ -519,6 +524,20 @@ def _select(select: str, what: str) -> int:
 def compact_scratch_bytes(n: int) -> int:
     """rrt_compact_scratch_bytes: the device scratch compact_rays_into needs for a batch of n entries."""
     return int(lib().rrt_compact_scratch_bytes(int(n)))
+
+
+def _key_mode(key: str, what: str) -> int:
+    if key not in SORT_KEY_MODES:
+        raise ValueError(f"{what}: unknown key {key!r}, want one of {SORT_KEY_MODES}")
+    return SORT_KEY_MODES.index(key)
+
+
+_SORT_KEY_READS = ((), ("origins", "dirs"), ("point", "normal", "material"))   # the arrays of src a key mode needs, per mode of SORT_KEY_MODES
+
+
+def sort_scratch_bytes(n: int) -> int:
+    """rrt_sort_scratch_bytes: the device scratch sort_rays_into needs for a batch of n entries."""
+    return int(lib().rrt_sort_scratch_bytes(int(n)))
 
 
 def _bound(name: str, *args):
@@ -1014,6 +1033,58 @@ class RayTracer(_Handle):
         _call("rrt_scatter_rays_device", self._h, n, _ptr(index_t), per * src_t.element_size(), _ptr(src_t), _ptr(dst_t), _P(_stream(stream)))
 
     compact_scratch_bytes = staticmethod(compact_scratch_bytes)
+
+    # stable sort of ray batches and records by a coherence key (rrt.h: rrt_sort_rays): entries that start in the same cell and head the same way become neighbours
+    def sort_rays(self, planes: dict, key: str = "ray", keys=None, origins=None, dirs=None, max_t=None, rot=None) -> dict:
+        """rrt_sort_rays: {"index": uint32 [n], "keys": uint32 [n] (sorted), "count": int, name: the gathered array} for every array given -- `planes` ({name:
+        array} as surface_rays returns it, any of RAY_SURFACE_PLANES; may be empty) and origins / dirs [n][3], max_t [n], rot [n][2].  key: "given" (keys, uint32
+        [n]), "ray" (origins and dirs; dead where max_t is not above 0) or "record" (point and normal; dead where material is no material).  Ascending and stable;
+        dead entries (key DEAD_KEY) form the tail, in source order, and are gathered like the rest."""
+        mode = _key_mode(key, "sort_rays")
+        src = {name: np.ascontiguousarray(a, dtype) for name, (a, dtype, width) in _ray_records("sort_rays", planes, RAY_SURFACE_PLANES).items()}
+        for name, a in (("origins", origins), ("dirs", dirs), ("max_t", max_t), ("rot", rot)):
+            if a is not None:
+                src[name] = np.ascontiguousarray(a, np.float64)
+        k = None if keys is None else np.ascontiguousarray(keys, np.uint32)
+        for name in _SORT_KEY_READS[mode]:
+            assert name in src, f"sort_rays: key {key!r} needs the array {name}"
+        assert mode != 0 or k is not None, "sort_rays: key 'given' needs a keys array"
+        n = k.size if mode == 0 else src["origins"].size // 3 if mode == 1 else src["material"].size
+        assert k is None or k.size == n, f"sort_rays: keys has {k.size} elements for {n} entries"
+        for name, a in src.items():
+            assert a.size == n * _ray_plane(name, CRaySet, "sort_rays")[1], f"sort_rays: array {name} has {a.size} elements for {n} entries"
+        out = {name: np.empty_like(a) for name, a in src.items()}
+        index, keys_out, count = np.empty(n, np.uint32), np.empty(n, np.uint32), C.c_uint32(0)
+        _call("rrt_sort_rays", self._h, n, mode, _u32(k), _ray_set(src), _ray_set(out), _u32(index), _u32(keys_out), C.byref(count))
+        return dict(out, index=index, keys=keys_out, count=int(count.value))
+
+    def sort_rays_into(self, out: dict, src: dict, key: str, index_t, keys_out_t, count_t, scratch_t, keys_t=None, stream: Optional[int] = None):
+        """rrt_sort_rays_device: out / src = {name: contiguous device tensor} with names from RAY_SET_ARRAYS -- n elements of the array's item size, 3 n for the
+        vectors, 2 n for rot; every array of out needs its array of src.  index_t, keys_out_t: n four-byte elements or None; count_t: one four-byte element or
+        None; scratch_t: a device tensor of at least sort_scratch_bytes(n) bytes (None for n == 0); keys_t: n four-byte elements, for key "given".  n is the length
+        of keys_t for "given", of src["origins"] for "ray", of src["material"] for "record".  Enqueued, not synchronised; last_stats stays as it was."""
+        mode = _key_mode(key, "sort_rays_into")
+        for name in _SORT_KEY_READS[mode]:
+            assert src.get(name) is not None, f"sort_rays_into: key {key!r} needs the tensor {name}"
+        assert mode != 0 or keys_t is not None, "sort_rays_into: key 'given' needs a keys tensor"
+        n = _batch_size(keys_t, 1, "keys") if mode == 0 else _batch_size(src["origins"], 3, "origins") if mode == 1 else _batch_size(src["material"], 1, "material")
+        if keys_t is not None:
+            _device_tensor(keys_t, n, 4, "keys")
+        for what, arrays in (("src", src), ("out", out)):
+            for name, t in arrays.items():
+                dtype, width = _ray_plane(name, CRaySet, "sort_rays_into")
+                _device_tensor(t, width * n, np.dtype(dtype).itemsize, f"{what} {name}")
+        for name, t, size in (("index", index_t, n), ("keys_out", keys_out_t, n), ("count", count_t, 1)):
+            if t is not None:
+                _device_tensor(t, size, 4, name)
+        scratch_bytes = 0
+        if scratch_t is not None:
+            assert getattr(scratch_t, "is_cuda", False) and scratch_t.is_contiguous(), "scratch: not a contiguous device tensor"
+            scratch_bytes = scratch_t.numel() * scratch_t.element_size()
+        _call("rrt_sort_rays_device", self._h, n, mode, _ptr(keys_t), _ray_set(src), _ray_set(out), _ptr(index_t), _ptr(keys_out_t), _ptr(count_t), _ptr(scratch_t),
+              scratch_bytes, _P(_stream(stream)))
+
+    sort_scratch_bytes = staticmethod(sort_scratch_bytes)
 
     # engine.rs:196-253: chunked draw with an update after every chunk (on_update(fb, first_row, n_rows) stands in for canvas.update())
     def render_progressive(self, width: int, height: int, on_update=None, chunk_rows: int = 50) -> np.ndarray:

@@ -12,6 +12,7 @@
 // no arithmetic touches them, so NaN payloads and -0.0 survive.  Which arrays are present is uniform across a launch (kernel arguments).
 #include <hip/hip_runtime.h>
 
+#include "batch_words.hpp"
 #include "device_scene.hpp"
 
 namespace rrt {
@@ -26,6 +27,7 @@ constexpr uint64_t kNaNBits = 0x7FF8000000000000ull, kInfBits = 0x7FF00000000000
 static_assert(kCompactTile % 64 == 0 && kCompactTile <= 1024 && kWaves <= 64, "a tile is a whole number of waves of one block");
 static_assert(sizeof(CompactParams) < 4096, "the arguments of the compaction kernels must fit the 4 KB kernel-argument segment");
 
+// (lanes_below and move_words: batch_words.hpp, shared with sort.hip)
 // sel[i] of rrt.h, for i < n
 __device__ __forceinline__ bool selected(const CompactParams& P, size_t i) {
     if (P.select == 2u) return P.flag[i] != 0;
@@ -34,21 +36,6 @@ __device__ __forceinline__ bool selected(const CompactParams& P, size_t i) {
     return P.select == 0u || P.mats[m].kr > 0.0;
 }
 
-// the number of selected lanes of this wave below the calling lane
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// element `from` of src to element `to` of dst, K 8-byte words each
-template <int K> __device__ __forceinline__ void move_words(const double* src, size_t from, double* dst, size_t to) {
-    const uint64_t* s = reinterpret_cast<const uint64_t*>(src) + (size_t)K * from;
-    uint64_t* d = reinterpret_cast<uint64_t*>(dst) + (size_t)K * to;
-    uint64_t w[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) w[k] = s[k];
-#pragma unroll
-    for (int k = 0; k < K; k++) d[k] = w[k];
-}
 template <int K> __device__ __forceinline__ void fill_words(double* dst, size_t to, uint64_t first, uint64_t rest) {
     uint64_t* d = reinterpret_cast<uint64_t*>(dst) + (size_t)K * to;
 #pragma unroll

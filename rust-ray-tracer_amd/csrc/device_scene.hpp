@@ -241,6 +241,23 @@ int launch_compact(const CompactParams& q, uint32_t* d_count, void* stream);
 // d_dst[d_index[j]] = d_src[j], elem_bytes (1, 4, 8, 16 or 24) each, for every j in [0, n) with d_index[j] < n
 int launch_scatter(uint32_t n, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream);
 
+// Argument of the sort kernels (sort.hip; rrt.h: rrt_sort_rays_device).  A hist / place block covers a tile of kSortTile consecutive entries.  The scratch, in
+// 4-byte words: two (key, index) buffer pairs of n words per array, the digit counts of one pass, digit-major ([256][sort_tiles(n)]), and the 256 digit totals.
+constexpr uint32_t kSortTile = 4096, kSortDigits = 256;
+constexpr uint32_t sort_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + kSortTile - 1) / kSortTile); }
+constexpr size_t sort_scratch_words(uint32_t n) { return n ? 4 * (size_t)n + (size_t)kSortDigits * sort_tiles(n) + kSortDigits : 0; }
+struct SortParams {
+    RaySetPtrs src, dst;         // src: what the key mode and dst read; dst: the gathered arrays, null = not wanted
+    const uint32_t* keys;        // RRT_SORT_KEY_GIVEN
+    uint32_t *index, *keys_out;  // [n] each, or null
+    uint32_t* count;             // [1], or null
+    uint32_t* scratch;           // [sort_scratch_words(n)]
+    uint32_t n, key_mode, n_mats, _pad;
+    double lo[3], scale[3];      // the root box's lower corner and 512 / its extent, per axis (RAY and RECORD)
+};
+// key, four radix passes (hist, two scans, place) and the gather of q on `stream`
+int launch_sort(const SortParams& q, void* stream);
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);

@@ -2,7 +2,8 @@
 //   Frames: into a device framebuffer or a rank's tiles, into host memory, progressively.
 //   Regions of a frame: visibility and surface buffers, frames shaded and ambient occlusion from kept buffers, the pick of one pixel.
 //   Per-ray queries, the choice of the traversal variant, and the statistics of the last launch.
-//   Compaction of ray batches and records between two per-ray stages, and its inverse (compact.hip): no ray is traced, so these go past timed_launch and record.
+//   Compaction of ray batches and records between two per-ray stages, its inverse (compact.hip) and their sort by a coherence key (sort.hip): no ray is traced, so
+//   these go past timed_launch and record.
 // Every launch goes through ONE seam: timed_launch (the raytracer's two events around it) and record (what it traced, into rrt_stats).  Every measurement of the
 // variants goes through fastest_variant.  The region calls share one check of the region (region_in_force), one launch (launch_region_frame) and, for their host
 // forms, one routine that carves the kept device allocation and copies the planes up and down (with_kept_planes).  The host forms of the per-ray calls, of compaction
@@ -545,6 +546,19 @@ RaySetPtrs ray_set_ptrs(const RaySetArrays& a) {
     std::memcpy(&q, a.p, sizeof q);
     return q;
 }
+// The planes of two ray sets of N entries into pl[at_src, at_src + 16) and pl[at_dst, at_dst + 16): of src what the call reads (read[k], and the array is there) goes
+// up, of dst what is set comes down.  A host array that src names twice goes up once: the later entry is no plane of the list and reads the device copy of the
+// earlier one, from[k] (its own plane otherwise).
+void ray_set_planes(HostPlane* pl, size_t at_src, size_t at_dst, const RaySetArrays& src, const RaySetArrays& dst, const bool (&read)[kRaySetArrays], size_t N,
+                    size_t (&from)[kRaySetArrays]) {
+    for (size_t k = 0; k < kRaySetArrays; k++) {
+        const bool up = src.p[k] && read[k];
+        from[k] = at_src + k;
+        for (size_t e = 0; up && e < k; e++) if (pl[at_src + e].host == src.p[k] && kRaySetElem[e] == kRaySetElem[k]) from[k] = at_src + e;
+        pl[at_src + k] = plane_up(up && from[k] == at_src + k ? src.p[k] : nullptr, kRaySetElem[k], N);
+        pl[at_dst + k] = plane_down(dst.p[k], kRaySetElem[k], N);
+    }
+}
 size_t compact_scratch_bytes(uint32_t n) { return n ? sizeof(uint32_t) * ((size_t)compact_tiles(n) + 1) : 0; }
 // every check of a compaction but the scratch's, before any GPU work and before the handle is looked at
 void check_compact(const rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* flag, const RaySetArrays& src, const RaySetArrays& dst,
@@ -583,13 +597,9 @@ int compact_from_host(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint
     HostPlane pl[kEnd];
     pl[kScratch] = HostPlane{rt, 1, compact_scratch_bytes(n), kCarve};     // (only carved: a host pointer that is not null says it is wanted)
     size_t from[kRaySetArrays];
-    for (size_t k = 0; k < kRaySetArrays; k++) {
-        const bool read = src.p[k] && (dst.p[k] || (k == kRaySetMaterial && select != RRT_SELECT_FLAG));
-        from[k] = kSrc + k;
-        for (size_t e = 0; read && e < k; e++) if (pl[kSrc + e].host == src.p[k] && kRaySetElem[e] == kRaySetElem[k]) from[k] = kSrc + e;
-        pl[kSrc + k] = plane_up(read && from[k] == kSrc + k ? src.p[k] : nullptr, kRaySetElem[k], N);
-        pl[kDst + k] = plane_down(dst.p[k], kRaySetElem[k], N);
-    }
+    bool read[kRaySetArrays];
+    for (size_t k = 0; k < kRaySetArrays; k++) read[k] = dst.p[k] || (k == kRaySetMaterial && select != RRT_SELECT_FLAG);
+    ray_set_planes(pl, kSrc, kDst, src, dst, read, N, from);
     pl[kFlag] = plane_up(select == RRT_SELECT_FLAG ? flag : nullptr, 1, N); pl[kIndex] = plane_down(index, 4, N); pl[kCount] = plane_down(count, 4, 1);
     with_call_planes(pl, [&] {
         RaySetArrays d_src{}, d_dst{};
@@ -604,6 +614,68 @@ void check_scatter(const rrt_raytracer* rt, uint32_t n, const uint32_t* index, u
     if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
     if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8 && elem_bytes != 16 && elem_bytes != 24) throw Error{RRT_ERR_INVALID_ARG, "bad elem_bytes: want 1, 4, 8, 16 or 24"};
     if (n && (!index || !src || !dst)) throw Error{RRT_ERR_INVALID_ARG, "null array: a scatter takes index, src and dst"};
+}
+
+// ---- stable sort of ray batches and records by a coherence key (rrt.h: rrt_sort_rays; sort.hip).  Not ray calls either.
+constexpr size_t kRaySetOrigins = 0, kRaySetDirs = 1, kRaySetPoint = 4 + 6, kRaySetNormal = 4 + 7;
+size_t sort_scratch_bytes(uint32_t n) { return sizeof(uint32_t) * sort_scratch_words(n); }
+// the arrays of src the key mode reads
+bool sort_key_reads(uint32_t key_mode, size_t k) {
+    if (key_mode == RRT_SORT_KEY_RAY) return k == kRaySetOrigins || k == kRaySetDirs || k == kRaySetMaxT;
+    if (key_mode == RRT_SORT_KEY_RECORD) return k == kRaySetPoint || k == kRaySetNormal || k == kRaySetMaterial;
+    return false;
+}
+// every check of a sort but the scratch's, before any GPU work and before the handle is looked at
+void check_sort(const rrt_raytracer* rt, uint32_t n, uint32_t key_mode, const uint32_t* keys, const RaySetArrays& src, const RaySetArrays& dst, const uint32_t* index,
+                const uint32_t* keys_out, const uint32_t* count) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (key_mode > RRT_SORT_KEY_RECORD) throw Error{RRT_ERR_INVALID_ARG, "unknown key mode: want RRT_SORT_KEY_GIVEN, RRT_SORT_KEY_RAY or RRT_SORT_KEY_RECORD"};
+    if (n == 0) return;
+    if (key_mode == RRT_SORT_KEY_GIVEN && !keys) throw Error{RRT_ERR_INVALID_ARG, "null keys: RRT_SORT_KEY_GIVEN reads them"};
+    if (key_mode == RRT_SORT_KEY_RAY && (!src.p[kRaySetOrigins] || !src.p[kRaySetDirs])) throw Error{RRT_ERR_INVALID_ARG, "null src.origins or src.dirs: RRT_SORT_KEY_RAY reads them"};
+    if (key_mode == RRT_SORT_KEY_RECORD && (!src.p[kRaySetPoint] || !src.p[kRaySetNormal] || !src.p[kRaySetMaterial]))
+        throw Error{RRT_ERR_INVALID_ARG, "null src.rec.point, .normal or .material: RRT_SORT_KEY_RECORD reads them"};
+    bool any_output = index || keys_out || count;
+    for (size_t k = 0; k < kRaySetArrays; k++) {
+        if (dst.p[k] && !src.p[k]) throw Error{RRT_ERR_INVALID_ARG, "an array of dst without its array of src"};
+        any_output = any_output || dst.p[k];
+    }
+    if (!any_output) throw Error{RRT_ERR_INVALID_ARG, "no output requested: index, keys_out, count and every array of dst are null"};
+}
+// the kernels' argument from arrays in device memory (checked): the key is formed with the root box in force now
+SortParams sort_params(const rrt_raytracer* rt, uint32_t n, uint32_t key_mode, const uint32_t* d_keys, const RaySetArrays& d_src, const RaySetArrays& d_dst,
+                       uint32_t* d_index, uint32_t* d_keys_out, uint32_t* d_count, void* d_scratch) {
+    SortParams q{};
+    q.src = ray_set_ptrs(d_src); q.dst = ray_set_ptrs(d_dst);
+    q.keys = d_keys; q.index = d_index; q.keys_out = d_keys_out; q.count = d_count; q.scratch = static_cast<uint32_t*>(d_scratch);
+    q.n = n; q.key_mode = key_mode; q.n_mats = rt->scene.n_mats;
+    for (int a = 0; a < 3; a++) { q.lo[a] = rt->root.lo[a]; q.scale[a] = 512.0 / (rt->root.hi[a] - rt->root.lo[a]); }
+    return q;
+}
+// Host form (checked): what the call reads up -- the src array of every dst array, the arrays the key mode reads, the given keys -- the launches on the null stream,
+// the requested outputs down; blocking (with_call_planes: the scratch is its first plane).
+int sort_from_host(rrt_raytracer* rt, uint32_t n, uint32_t key_mode, const uint32_t* keys, const RaySetArrays& src, const RaySetArrays& dst, uint32_t* index,
+                   uint32_t* keys_out, uint32_t* count) {
+    if (n == 0) { if (count) *count = 0; return RRT_OK; }
+    DeviceGuard guard(rt->device);
+    const size_t N = n;
+    enum : size_t { kScratch, kSrc, kDst = kSrc + kRaySetArrays, kKeys = kDst + kRaySetArrays, kIndex, kKeysOut, kCount, kEnd };
+    HostPlane pl[kEnd];
+    pl[kScratch] = HostPlane{rt, 1, sort_scratch_bytes(n), kCarve};        // (only carved: a host pointer that is not null says it is wanted)
+    size_t from[kRaySetArrays];
+    bool read[kRaySetArrays];
+    for (size_t k = 0; k < kRaySetArrays; k++) read[k] = dst.p[k] || sort_key_reads(key_mode, k);
+    ray_set_planes(pl, kSrc, kDst, src, dst, read, N, from);
+    pl[kKeys] = plane_up(key_mode == RRT_SORT_KEY_GIVEN ? keys : nullptr, 4, N);
+    pl[kIndex] = plane_down(index, 4, N); pl[kKeysOut] = plane_down(keys_out, 4, N); pl[kCount] = plane_down(count, 4, 1);
+    with_call_planes(pl, [&] {
+        RaySetArrays d_src{}, d_dst{};
+        for (size_t k = 0; k < kRaySetArrays; k++) { d_src.p[k] = pl[from[k]].dev; d_dst.p[k] = pl[kDst + k].dev; }
+        const SortParams q = sort_params(rt, n, key_mode, (const uint32_t*)pl[kKeys].dev, d_src, d_dst, (uint32_t*)pl[kIndex].dev, (uint32_t*)pl[kKeysOut].dev,
+                                         (uint32_t*)pl[kCount].dev, pl[kScratch].dev);
+        HIP_TRY((hipError_t)launch_sort(q, nullptr));
+    });
+    return RRT_OK;
 }
 
 }  // namespace
@@ -945,6 +1017,30 @@ int rrt_scatter_rays_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_ind
         if (n == 0) return (int)RRT_OK;
         DeviceGuard guard(rt->device);
         HIP_TRY((hipError_t)launch_scatter(n, d_index, elem_bytes, d_src, d_dst, stream));
+        return (int)RRT_OK;
+    });
+}
+
+size_t rrt_sort_scratch_bytes(uint32_t n) { return sort_scratch_bytes(n); }
+
+int rrt_sort_rays(rrt_raytracer* rt, uint32_t n, uint32_t key_mode, const uint32_t* keys, const rrt_ray_set* src, const rrt_ray_set* dst, uint32_t* index,
+                  uint32_t* keys_out, uint32_t* count) {
+    return guarded([&]() -> int {
+        const RaySetArrays s = ray_set_arrays(src), d = ray_set_arrays(dst);
+        check_sort(rt, n, key_mode, keys, s, d, index, keys_out, count);
+        return sort_from_host(rt, n, key_mode, keys, s, d, index, keys_out, count);
+    });
+}
+
+int rrt_sort_rays_device(rrt_raytracer* rt, uint32_t n, uint32_t key_mode, const uint32_t* d_keys, const rrt_ray_set* d_src, const rrt_ray_set* d_dst,
+                         uint32_t* d_index, uint32_t* d_keys_out, uint32_t* d_count, void* d_scratch, size_t scratch_bytes, void* stream) {
+    return guarded([&]() -> int {
+        const RaySetArrays s = ray_set_arrays(d_src), d = ray_set_arrays(d_dst);
+        check_sort(rt, n, key_mode, d_keys, s, d, d_index, d_keys_out, d_count);
+        if (n == 0) return (int)RRT_OK;
+        if (scratch_bytes < sort_scratch_bytes(n) || !d_scratch) throw Error{RRT_ERR_INVALID_ARG, "scratch too small or null: want rrt_sort_scratch_bytes(n) bytes of device memory"};
+        DeviceGuard guard(rt->device);
+        HIP_TRY((hipError_t)launch_sort(sort_params(rt, n, key_mode, d_keys, s, d, d_index, d_keys_out, d_count, d_scratch), stream));
         return (int)RRT_OK;
     });
 }
