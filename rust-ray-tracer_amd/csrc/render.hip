@@ -442,8 +442,10 @@ __device__ __noinline__ void band_count(Prof& prof, double v1x, double v1y, doub
     if (in_band) prof.b[prof.secondary ? 1 : 3] += 1ull;
 }
 #define MT_UNIFORM(tri, o, d, t) (mt_uniform(tri, o, d, t) && (band_count(prof, tri.v1x, tri.v1y, tri.v1z, mk(tri.e1x, tri.e1y, tri.e1z), mk(tri.e2x, tri.e2y, tri.e2z), o, d), true))
+#define BAND_FLUSH() do { for (int _k = 0; _k < 4; _k++) if (prof.b[_k]) atomicAdd(S.prof + 24 + _k, prof.b[_k]); } while (0)   /* a per-ray kernel's counts, per lane: band_count events are per ray */
 #else
 #define MT_UNIFORM(tri, o, d, t) mt_uniform(tri, o, d, t)
+#define BAND_FLUSH() ((void)0)
 #endif
 
 // ------------------------------------------------------------------------------------------------ traversal
@@ -1610,6 +1612,189 @@ __device__ __forceinline__ void surface_of_hit(const DevScene& S, uint32_t slot,
     n = normalised(nn);                                                                  // raytracer.rs:161
 }
 
+// ---- what the region kernels and the per-ray kernels share: the walk dispatch and one body per query for its two forms (surface, shade; the ambient pair keeps its
+// restated loops, see ambient_kernel).  The rule of the region helpers holds for these too (visibility_kernel; profiles/shared_query_bodies.txt); render_kernel,
+// trace_colour and ray_colour_kernel call none.
+// The walk a kernel is instantiated for: traverse_ray for kWalkRay, else traverse with the lane or the bundle filter.  Arguments and result are traverse's
+// (traverse_ray has no one_origin).  kFarAnchor = false is occlusion_kernel's.
+template <int kWalk, bool kGroups, bool kFarAnchor = true>
+__device__ __forceinline__ void walk(PROF_DECL const DevScene& S, const Stack& stk, bool active, bool any_ok, bool filter_ok, bool one_origin, V3 o, V3 d, double max_t,
+                                     double& out_t, uint32_t& out_slot) {
+    if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, active, any_ok, filter_ok, o, d, max_t, out_t, out_slot);
+    else traverse<kWalk == kWalkBundle, kGroups, kFarAnchor>(PROF_ARG S, stk, active, any_ok, filter_ok, one_origin, o, d, max_t, out_t, out_slot);
+}
+
+// The surface loop: the first hit of ray (o, d) within first_max_t and what trace_colour holds for it on its way to a colour -- the hit point, the barycentrics, the
+// triangle, the material, the texel, the shading normal and the mask of the lights that reach the point.
+// ONE call site of the walk, as in trace_colour: the first turn of the loop walks the callers' rays (closest hit, guarded by origin_ray_in_suspect_plane; one_origin
+// as the caller says), every later turn the shadow rays of all hit lanes towards ONE point light, with the arguments trace_colour gives a shadow walk (any_ok,
+// filter_ok, not one_origin; the rays of a turn end at one light, so the bundle's anchor is the frame kernels': the far ends).  Which turn it is, and which light, is
+// wave-uniform: the lights are kernel arguments.  Every point light is walked, also those behind the reference's `break` (raytracer.rs:235-237).
+// first_active: the lane's ray takes part in the first walk; a lane whose ray does not is a miss.  The four wants are wave-uniform (tests on kernel-argument
+// pointers, or literals): no want_lights: the loop ends after the first turn; no want_attr: no attribute load (mat, col, n keep their initial values); no want_uv:
+// no second Moller-Trumbore.  A wave without a hit leaves the loop after the first turn.  A miss: t = u = v = 0, tri = mat = kNone, col = col0, p = n = (0, 0, 0), mask = 0.
+// No lane leaves before the last walk: the walks need the whole wave in uniform control flow.
+// The state is plain locals in the order the kernels used to declare them, and the result is put together in the return statement: that order decides the kernels' register
+// allocation (filled field by field, the struct costs surface_kernel<1> 36 B of scratch: profiles/shared_query_bodies.txt, section 3).
+struct SurfaceHit { bool found; double t, u, v; uint32_t tri, mat, mask, col; V3 p, n; };
+template <int kWalk, bool kGroups>
+__device__ __forceinline__ SurfaceHit surface_body(PROF_DECL const DevScene& S, const Stack& stk, bool first_active, bool one_origin, V3 o, V3 d, double first_max_t, uint32_t col0,
+                                                   bool want_uv, bool want_tri, bool want_attr, bool want_lights) {
+    const bool first_ok = !origin_ray_in_suspect_plane(S, o, d);                       // exactness guard of the first walk (visibility_kernel, intersect_kernel)
+    const uint32_t n_lights = want_lights ? S.n_lights : 0u;                           // no lights wanted: no shadow walk
+    bool found = false;
+    bool shadow = false;                                                               // wave-uniform: the walk about to start is a shadow walk, towards light li
+    uint32_t li = 0;
+    double t = 0, u = 0, v = 0;
+    uint32_t tri = kNone, mat = kNone, mask = 0;
+    uint32_t col = col0;
+    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
+    V3 ro = o, rd = d; double rmax = first_max_t;
+    for (;;) {
+        double wt; uint32_t wslot;
+        const bool active = shadow ? found : first_active;
+        walk<kWalk, kGroups>(PROF_ARG S, stk, active, shadow, shadow || first_ok, one_origin && !shadow, ro, rd, rmax, wt, wslot);
+        if (!shadow) {
+            shadow = true;
+            found = first_active && wslot != kNone;
+            if (found) {
+                // --- hit: raytracer.rs:39-57
+                if (want_uv) { double t2; mt_full(S.geom + wslot, o, d, t2, u, v); }
+                t = wt;
+                if (want_tri) tri = S.attr[wslot].orig;
+                p = o + d * wt;                                                          // raytracer.rs:39
+                if (want_attr) surface_of_hit(S, wslot, u, v, mat, col, n);
+            }
+            if (!__any(found)) break;                                                    // no hit in the wave: nothing to ask the lights
+        } else {
+            if (found && wslot == kNone) mask |= 1u << li;                               // triangle_exists_between_points says "lit" for None, raytracer.rs:181-187
+            li++;
+        }
+        // the light list up to the next point light (raytracer.rs:205-255): Ambient and Directional lights reach every hit
+        while (li < n_lights && S.lights[li].kind != 1u) { if (found) mask |= 1u << li; li++; }
+        if (li >= n_lights) break;
+        const V3 dir = ld3(S.lights[li].v) - p;                                          // the shadow ray, raytracer.rs:164-188, as trace_colour forms it
+        ro = p + n * S.surface_offset;
+        rd = dir;
+        rmax = length(dir);
+    }
+    return SurfaceHit{found, t, u, v, tri, mat, mask, col, p, n};
+}
+
+// The shade state machine: trace_colour's, rotated, from a hit that is already known.  A live lane enters holding the hit of a segment of
+// get_ray_colour_recursive -- p, n, mat, col and the segment direction seg_d, as trace_colour holds them after get_normal_at_intersection -- and its place li in
+// the light list; from there on it is trace_colour: the light list, compute_lighting_intensity, the reflection chain with its shadow rays.  A turn SHADES first
+// (the light list of the hit a lane holds, up to the next shadow ray or to the hit's colour and its reflection ray) and WALKS second (the shadow or reflection
+// rays the shading left in flight), so a wave none of whose lanes needs a ray -- non-mirror hits with a mask, misses, dead rays -- leaves without calling the walk
+// at all.  ONE call site of the walk; every ray is a secondary ray (not one_origin, filters on, any_ok for a shadow ray).
+// A kept lights mask enters as (li, n_eval) = (0xFFFF, the lights that count): no shadow ray of the entry hit is formed and the sum adds up [0, n_eval).
+// Otherwise (li = 0) the lights are walked as a frame walks them, the `break` at the first occluded point light included.
+// The caller owns the reflection stack and unwinds it (shade_unwind) behind its own guard, from the level and the `term` that come back.  lvl counts the levels below
+// the entry hit's = the stack slot of the hit the lane holds; `room` levels from the entry hit's on may still reflect (raytracer.rs:76).
+// The scalars of the state come in by value, in the order the kernels used to declare them, and lvl and term go back in the result: for the reason given at surface_body.
+// kRecord (the per-ray form): slot 0 is written for the entry hit whether or not it reflects -- `local`, the unquantised colour of raytracer.rs:67-71, and `kr`,
+// the material's where the reference reflects there, else 0.0 -- and without want_colour (wave-uniform) no reflection ray is formed.  The region form has neither:
+// both fold away.
+struct ShadeEnd { uint32_t lvl, term; };
+template <int kWalk, bool kGroups, bool kRecord>
+__device__ __forceinline__ ShadeEnd shade_body(PROF_DECL const DevScene& S, const Stack& stk, uint32_t room, bool want_colour, bool live, V3 seg_d, V3 p, V3 n, uint32_t col, uint32_t mat,
+                                               uint32_t li, uint32_t lvl, uint32_t n_eval, uint32_t term, double (&st_local)[RRT_MAX_REFLECT][3], double (&st_kr)[RRT_MAX_REFLECT]) {
+    bool in_shadow = false;                 // false: the ray in flight is a reflection ray; true: a shadow ray
+    V3 ro = mk(0, 0, 0), rd = mk(0, 0, 1); double rmax = kInf;
+    for (;;) {
+        // ---- shade: every live lane holds a hit (p, n, mat, col, seg_d) and stands at light li of its list
+        if (live) {
+            // the light list (raytracer.rs:205-255) up to the next point light, whose shadow ray (raytracer.rs:164-188) is walked next: trace_colour's
+            while (li < S.n_lights && !in_shadow) {
+                const DevLight& L = S.lights[li];
+                if (L.kind == 1u) {
+                    const V3 dir = ld3(L.v) - p;
+                    ro = p + n * S.surface_offset;
+                    rd = dir;
+                    rmax = length(dir);
+                    in_shadow = true;
+                } else {
+                    li++;
+                }
+            }
+            if (!in_shadow) {
+                if (li != 0xFFFFu) n_eval = S.n_lights;
+                // --- compute_lighting_intensity, raytracer.rs:192-258
+                const DevMaterial& M = S.mats[mat];
+                const V3 vdir = neg(seg_d);
+                const double len_n = length(n), len_v = length(vdir);
+                V3 I = mk(0.0, 0.0, 0.0);
+                for (uint32_t k = 0; k < n_eval; ++k) {
+                    const DevLight& L = S.lights[k];
+                    if (L.kind == 0u) {                                              // Ambient, raytracer.rs:207-209
+                        I = I + ld3(M.ka) * L.intensity;
+                    } else {                                                         // Directional (raytracer.rs:210-227) / unoccluded Point (raytracer.rs:239-252)
+                        const V3 l = (L.kind == 2u) ? ld3(L.v) : ld3(L.v) - p;
+                        const double n_dot_l = dot(n, l);
+                        I = I + diffuse_term(L.intensity, n_dot_l, len_n, length(l), ld3(M.kd));
+                        I = I + specular_term(PROF_ARG !S.specular_all, M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks), I);
+                    }
+                }
+                // --- raytracer.rs:67-108
+                const V3 local = mk((double)((col >> 16) & 255u) * I.x, (double)((col >> 8) & 255u) * I.y, (double)(col & 255u) * I.z);
+                const double kr = M.kr;
+                const bool reflects = kr > 0.0 && lvl < room;                        // raytracer.rs:76
+                if (reflects || (kRecord && lvl == 0u)) {
+                    st_local[lvl][0] = local.x; st_local[lvl][1] = local.y; st_local[lvl][2] = local.z; st_kr[lvl] = reflects ? kr : 0.0;
+                }
+                if (reflects && (!kRecord || want_colour)) {
+                    const double d_dot_n = dot(seg_d, n);
+                    rd = normalised(seg_d - (n * 2.0) * d_dot_n);                    // raytracer.rs:79
+                    ro = p + n * S.surface_offset;                                   // raytracer.rs:82
+                    rmax = kInf;
+                    lvl++;
+                } else {
+                    term = (clamp_u8(local.x) << 16) | (clamp_u8(local.y) << 8) | clamp_u8(local.z);   // raytracer.rs:104-108
+                    live = false;
+                }
+            }
+        }
+        if (!__any(live)) break;                                                     // no ray in flight in the wave
+        // ---- walk: the shadow and reflection rays in flight, together
+        double t; uint32_t slot;
+        walk<kWalk, kGroups>(PROF_ARG S, stk, live, in_shadow, true, false, ro, rd, rmax, t, slot);
+        if (live) {
+            const bool found = slot != kNone;
+            if (!in_shadow) {
+                if (!found) {
+                    term = 0x00FFFFFFu; live = false;                                // WHITE, raytracer.rs:109-111
+                } else {
+                    // --- hit: raytracer.rs:39-57
+                    double u = 0, v = 0, t2;
+                    mt_full(S.geom + slot, ro, rd, t2, u, v);
+                    seg_d = rd;
+                    p = ro + rd * t;                                                 // raytracer.rs:39
+                    surface_of_hit(S, slot, u, v, mat, col, n);
+                    li = 0;                                                          // compute_lighting_intensity, raytracer.rs:199-203
+                }
+            } else {
+                // --- result of the shadow ray for point light li (raytracer.rs:232-237): occluded -> `break` out of the whole light loop
+                if (found) { n_eval = li; li = 0xFFFFu; }
+                else li++;
+                in_shadow = false;
+            }
+        }
+    }
+    return ShadeEnd{lvl, term};
+}
+// The unwind of the reflection chain shade_body left, innermost first (raytracer.rs:85-101): every level quantises to u8 before blending.
+__device__ __forceinline__ uint32_t shade_unwind(uint32_t term, uint32_t lvl, const double (&st_local)[RRT_MAX_REFLECT][3], const double (&st_kr)[RRT_MAX_REFLECT]) {
+    uint32_t c = term;
+    for (uint32_t k = lvl; k-- > 0;) {
+        const double kr = st_kr[k];
+        const double fx = st_local[k][0] * (1.0 - kr) + (double)((c >> 16) & 255u) * kr;
+        const double fy = st_local[k][1] * (1.0 - kr) + (double)((c >> 8) & 255u) * kr;
+        const double fz = st_local[k][2] * (1.0 - kr) + (double)(c & 255u) * kr;
+        c = (clamp_u8(fx) << 16) | (clamp_u8(fy) << 8) | clamp_u8(fz);
+    }
+    return c;
+}
+
 // ------------------------------------------------------------------------------------------------ kernels
 // One wave per workgroup; workgroup b renders quadrant (b & 3) of this rank's local tile (b >> 2).
 // Waves per SIMD (register budget) per traversal variant, measured on MI355X with the code-generation switches of the Makefile: 4 everywhere
@@ -1750,8 +1935,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const Dev
     Prof prof{}; prof.last = 0;
 #endif
     double t; uint32_t slot;
-    if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, traced, false, !origin_ray_in_suspect_plane(S, o, d), o, d, kInf, t, slot);
-    else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, traced, false, !origin_ray_in_suspect_plane(S, o, d), true, o, d, kInf, t, slot);
+    walk<kWalk, kGroups>(PROF_ARG S, stk, traced, false, !origin_ray_in_suspect_plane(S, o, d), true, o, d, kInf, t, slot);
     if (!in_region) return;
     const bool found = traced && slot != kNone;
     double u = 0, v = 0;
@@ -1791,12 +1975,8 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const Dev
 // Surface buffers (rrt.h: rrt_render_surface_device): per primary ray of a region of the frame the hit point, the shading normal, the material index and
 // the mask of the lights that reach the point -- what trace_colour holds for the primary segment on its way to a colour -- and, if asked for, the
 // visibility planes of the same rays from the same launch.  Waves, rays, guard, region and plane layout are visibility_kernel's (point and normal: three
-// doubles per sub-sample, 384 B per pixel row of a wave).
-// ONE call site of the walk, as in trace_colour: the first turn of the loop walks the primary rays (one_origin, guarded), every later turn the shadow rays
-// of all hit lanes towards ONE point light, with the arguments trace_colour gives a shadow walk (any_ok, filter_ok, not one_origin, far anchor).  Which
-// turn it is, and which light, is wave-uniform: the lights are kernel arguments.  Every point light is walked, also those behind the reference's `break`
-// (raytracer.rs:235-237).  Without a lights plane (a kernel argument: wave-uniform) the loop ends after the first turn.
-// No lane leaves before the last walk: the walks need the whole wave in uniform control flow.
+// doubles per sub-sample, 384 B per pixel row of a wave).  The loop is surface_body's: the primary rays are the traced lanes', from the one origin, unbounded;
+// everything is wanted but the lights, which follow the lights plane (a kernel argument: wave-uniform).  0 as Canvas::new for the texel where nothing is traced.
 template <int kWalk, bool kGroups>
 __global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevScene S, const SurfaceParams Q) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -1810,70 +1990,27 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevSce
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    const bool first_ok = !origin_ray_in_suspect_plane(S, o, d);                      // exactness guard of the primary walk (visibility_kernel)
-    const uint32_t n_lights = Q.lights ? S.n_lights : 0u;                              // no lights plane: no shadow walk
-    bool found = false;
-    bool shadow = false;                                                               // wave-uniform: the walk about to start is a shadow walk, towards light li
-    uint32_t li = 0;
-    double t = 0, u = 0, v = 0;
-    uint32_t tri = kNone, mat = kNone, mask = 0;
-    uint32_t col = traced ? 0x00FFFFFFu : 0u;                                          // WHITE, raytracer.rs:109-111; 0 as Canvas::new where nothing is traced
-    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
-    V3 ro = o, rd = d; double rmax = kInf;
-    for (;;) {
-        double wt; uint32_t wslot;
-        const bool active = shadow ? found : traced;
-        if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, active, shadow, shadow || first_ok, ro, rd, rmax, wt, wslot);
-        else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, active, shadow, shadow || first_ok, !shadow, ro, rd, rmax, wt, wslot);
-        if (!shadow) {
-            shadow = true;
-            found = traced && wslot != kNone;
-            if (found) {
-                // --- hit: raytracer.rs:39-57
-                double t2;
-                mt_full(S.geom + wslot, o, d, t2, u, v);
-                t = wt;
-                tri = S.attr[wslot].orig;
-                p = o + d * wt;                                                          // raytracer.rs:39
-                surface_of_hit(S, wslot, u, v, mat, col, n);
-            }
-            if (!__any(found)) break;                                                    // no hit in the wave: nothing to ask the lights
-        } else {
-            if (found && wslot == kNone) mask |= 1u << li;                               // triangle_exists_between_points says "lit" for None, raytracer.rs:181-187
-            li++;
-        }
-        // the light list up to the next point light (raytracer.rs:205-255): Ambient and Directional lights reach every hit
-        while (li < n_lights && S.lights[li].kind != 1u) { if (found) mask |= 1u << li; li++; }
-        if (li >= n_lights) break;
-        const V3 dir = ld3(S.lights[li].v) - p;                                          // the shadow ray, raytracer.rs:164-188, as trace_colour forms it
-        ro = p + n * S.surface_offset;
-        rd = dir;
-        rmax = length(dir);
-    }
+    const SurfaceHit h = surface_body<kWalk, kGroups>(PROF_ARG S, stk, traced, true, o, d, kInf, traced ? 0x00FFFFFFu : 0u, true, true, true, Q.lights != nullptr);
     if (!in_region) return;
     const size_t i = region_pixel(P, L) * 4 + sub;
-    if (Q.point) { Q.point[3 * i] = p.x; Q.point[3 * i + 1] = p.y; Q.point[3 * i + 2] = p.z; }
-    if (Q.normal) { Q.normal[3 * i] = n.x; Q.normal[3 * i + 1] = n.y; Q.normal[3 * i + 2] = n.z; }
-    if (Q.material) Q.material[i] = mat;
-    if (Q.lights) Q.lights[i] = mask;
+    if (Q.point) { Q.point[3 * i] = h.p.x; Q.point[3 * i + 1] = h.p.y; Q.point[3 * i + 2] = h.p.z; }
+    if (Q.normal) { Q.normal[3 * i] = h.n.x; Q.normal[3 * i + 1] = h.n.y; Q.normal[3 * i + 2] = h.n.z; }
+    if (Q.material) Q.material[i] = h.mat;
+    if (Q.lights) Q.lights[i] = h.mask;
     // the visibility planes, as visibility_kernel writes them
-    if (P.albedo) P.albedo[i] = col;
-    if (P.hit) P.hit[i] = found ? 1 : 0;
-    if (P.t) P.t[i] = t;
-    if (P.u) P.u[i] = u;
-    if (P.v) P.v[i] = v;
-    if (P.tri) P.tri[i] = tri;
+    if (P.albedo) P.albedo[i] = h.col;
+    if (P.hit) P.hit[i] = h.found ? 1 : 0;
+    if (P.t) P.t[i] = h.t;
+    if (P.u) P.u[i] = h.u;
+    if (P.v) P.v[i] = h.v;
+    if (P.tri) P.tri[i] = h.tri;
 }
 
 // Shading from kept buffers (rrt.h: rrt_shade_surface_device): the colour of every pixel of a region of the frame from the planes surface_kernel wrote for it --
-// point, normal, material, albedo and, if given, the lights mask -- with the lights and materials in force NOW.  No primary ray is walked: a sub-sample starts
-// as the primary segment's hit as trace_colour holds it after get_normal_at_intersection (p, n, mat, col; the segment direction is recomputed from the pixel
-// and the pose), and from there on it is trace_colour: the light list, compute_lighting_intensity, the reflection chain with its shadow rays, the unwind.
-// trace_colour's state machine, rotated: a turn SHADES first (the light list of the hit a lane holds, up to the next shadow ray or to the hit's colour and its
-// reflection ray) and WALKS second (the shadow or reflection rays the shading left in flight), so a wave none of whose lanes needs a ray -- non-mirror hits with
-// a mask, misses -- leaves without calling the walk at all.  ONE call site of the walk; every ray is a secondary ray (not one_origin, filters on, any_ok for a
-// shadow ray).  With a mask the lights the depth-0 sum adds up are [0, min(ctz(~mask), n_lights)) and no depth-0 shadow ray is formed; without one (a kernel
-// argument: wave-uniform) they are walked as a frame walks them, the `break` at the first occluded point light included.
+// point, normal, material, albedo and, if given, the lights mask -- with the lights and materials in force NOW.  No primary ray is walked: a sub-sample enters
+// shade_body as the primary segment's hit (the segment direction is recomputed from the pixel and the pose) at recursion depth 0, so all of
+// max_reflection_depth is its room; the colour is always wanted and no record is kept.  With a mask (a kernel argument: wave-uniform) the lights the depth-0 sum
+// adds up are [0, min(ctz(~mask), n_lights)) and no depth-0 shadow ray is formed.
 // A material index at or beyond the table (0xFFFFFFFF: a miss) is WHITE; no other value of the caller's planes is used as an index.
 template <int kWalk, bool kGroups>
 __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene S, const ShadeParams Q) {
@@ -1884,7 +2021,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
     const RegionLane L = region_lane(P, lane);
     const uint32_t sub = L.sub;
     const bool in_region = L.in_region, traced = L.traced;
-    V3 seg_d = primary_direction(P.F, L.px, L.py, sub);
+    const V3 seg_d = primary_direction(P.F, L.px, L.py, sub);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
@@ -1901,102 +2038,16 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
             live = true;
             p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
             col = Q.albedo[i] & 0x00FFFFFFu;
-            if (Q.lights) {                 // the kept mask answers the depth-0 shadow queries: the light loop below is skipped for this hit
+            if (Q.lights) {                 // the kept mask answers the depth-0 shadow queries: the light loop of shade_body is skipped for this hit
                 const uint32_t first_dark = (uint32_t)__builtin_ctz(~Q.lights[i] | (1u << RRT_MAX_LIGHTS));   // (n_lights <= 16: bits at and above it never count)
                 n_eval = first_dark < S.n_lights ? first_dark : S.n_lights;
                 li = 0xFFFFu;
             }
         }
     }
-    bool in_shadow = false;                 // false: the ray in flight is a reflection ray; true: a shadow ray
-    V3 ro = mk(0, 0, 0), rd = mk(0, 0, 1); double rmax = kInf;
     double st_local[RRT_MAX_REFLECT][3]; double st_kr[RRT_MAX_REFLECT];
-    for (;;) {
-        // ---- shade: every live lane holds a hit (p, n, mat, col, seg_d) and stands at light li of its list
-        if (live) {
-            // the light list (raytracer.rs:205-255) up to the next point light, whose shadow ray (raytracer.rs:164-188) is walked next: trace_colour's
-            while (li < S.n_lights && !in_shadow) {
-                const DevLight& L = S.lights[li];
-                if (L.kind == 1u) {
-                    const V3 dir = ld3(L.v) - p;
-                    ro = p + n * S.surface_offset;
-                    rd = dir;
-                    rmax = length(dir);
-                    in_shadow = true;
-                } else {
-                    li++;
-                }
-            }
-            if (!in_shadow) {
-                if (li != 0xFFFFu) n_eval = S.n_lights;
-                // --- compute_lighting_intensity, raytracer.rs:192-258
-                const DevMaterial& M = S.mats[mat];
-                const V3 vdir = neg(seg_d);
-                const double len_n = length(n), len_v = length(vdir);
-                V3 I = mk(0.0, 0.0, 0.0);
-                for (uint32_t k = 0; k < n_eval; ++k) {
-                    const DevLight& L = S.lights[k];
-                    if (L.kind == 0u) {                                              // Ambient, raytracer.rs:207-209
-                        I = I + ld3(M.ka) * L.intensity;
-                    } else {                                                         // Directional (raytracer.rs:210-227) / unoccluded Point (raytracer.rs:239-252)
-                        const V3 l = (L.kind == 2u) ? ld3(L.v) : ld3(L.v) - p;
-                        const double n_dot_l = dot(n, l);
-                        I = I + diffuse_term(L.intensity, n_dot_l, len_n, length(l), ld3(M.kd));
-                        I = I + specular_term(PROF_ARG !S.specular_all, M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks), I);
-                    }
-                }
-                // --- raytracer.rs:67-108
-                const V3 local = mk((double)((col >> 16) & 255u) * I.x, (double)((col >> 8) & 255u) * I.y, (double)(col & 255u) * I.z);
-                const double kr = M.kr;
-                if (kr > 0.0 && depth < S.max_reflection_depth) {                    // raytracer.rs:76
-                    st_local[depth][0] = local.x; st_local[depth][1] = local.y; st_local[depth][2] = local.z; st_kr[depth] = kr;
-                    const double d_dot_n = dot(seg_d, n);
-                    rd = normalised(seg_d - (n * 2.0) * d_dot_n);                    // raytracer.rs:79
-                    ro = p + n * S.surface_offset;                                   // raytracer.rs:82
-                    rmax = kInf;
-                    depth++;
-                } else {
-                    term = (clamp_u8(local.x) << 16) | (clamp_u8(local.y) << 8) | clamp_u8(local.z);   // raytracer.rs:104-108
-                    live = false;
-                }
-            }
-        }
-        if (!__any(live)) break;                                                     // no ray in flight in the wave
-        // ---- walk: the shadow and reflection rays in flight, together
-        double t; uint32_t slot;
-        if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, live, in_shadow, true, ro, rd, rmax, t, slot);
-        else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, live, in_shadow, true, false, ro, rd, rmax, t, slot);
-        if (live) {
-            const bool found = slot != kNone;
-            if (!in_shadow) {
-                if (!found) {
-                    term = 0x00FFFFFFu; live = false;                                // WHITE, raytracer.rs:109-111
-                } else {
-                    // --- hit: raytracer.rs:39-57
-                    double u = 0, v = 0, t2;
-                    mt_full(S.geom + slot, ro, rd, t2, u, v);
-                    seg_d = rd;
-                    p = ro + rd * t;                                                 // raytracer.rs:39
-                    surface_of_hit(S, slot, u, v, mat, col, n);
-                    li = 0;                                                          // compute_lighting_intensity, raytracer.rs:199-203
-                }
-            } else {
-                // --- result of the shadow ray for point light li (raytracer.rs:232-237): occluded -> `break` out of the whole light loop
-                if (found) { n_eval = li; li = 0xFFFFu; }
-                else li++;
-                in_shadow = false;
-            }
-        }
-    }
-    // unwind the reflection chain, innermost first (raytracer.rs:85-101): every level quantises to u8 before blending
-    uint32_t c = term;
-    for (uint32_t k = depth; k-- > 0;) {
-        const double kr = st_kr[k];
-        const double fx = st_local[k][0] * (1.0 - kr) + (double)((c >> 16) & 255u) * kr;
-        const double fy = st_local[k][1] * (1.0 - kr) + (double)((c >> 8) & 255u) * kr;
-        const double fz = st_local[k][2] * (1.0 - kr) + (double)(c & 255u) * kr;
-        c = (clamp_u8(fx) << 16) | (clamp_u8(fy) << 8) | clamp_u8(fz);
-    }
+    const ShadeEnd E = shade_body<kWalk, kGroups, false>(PROF_ARG S, stk, S.max_reflection_depth, true, live, seg_d, p, n, col, mat, li, depth, n_eval, term, st_local, st_kr);
+    const uint32_t c = shade_unwind(E.term, E.lvl, st_local, st_kr);
     // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
     uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
     r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
@@ -2011,9 +2062,11 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
 // the SAMPLES: sample k of the table -- kernel arguments, wave-uniform, scalar registers -- gives every hit lane of the wave its ray k, so a turn walks the 64
 // rays that share a direction in their tangent frames (neighbouring hits of one surface: nearly parallel rays from nearly the same place, a tight bundle) and
 // keeps one bit per lane.  The rays live in registers only.
-// ONE call site of the walk, with the arguments surface_kernel gives a shadow turn (any_ok, filters on, not one_origin, active = the lane holds a hit).  A wave
+// ONE call site of the walk, with the arguments surface_body gives a shadow turn (any_ok, filters on, not one_origin, active = the lane holds a hit).  A wave
 // with no hit writes its zeros and leaves without calling the walk; no lane leaves before the last walk.
 // A material index at or beyond the table (0xFFFFFFFF: a miss) is a miss; no value of the caller's planes is used as an index.
+// The sample loop is restated in ambient_rays_kernel, unlike the surface and shade loops, which have one body for both forms: with one body ambient_rays_kernel<0> gains scratch, and
+// the timing that would then decide was not taken (profiles/shared_query_bodies.txt, section 3).
 template <int kWalk, bool kGroups>
 __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevScene S, const AmbientParams Q) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -2047,6 +2100,8 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevSce
             // ray is a harmless one)
             const V3 rd = hit ? mk((tg.x * sx + bt.x * sy) + n.x * sz, (tg.y * sx + bt.y * sy) + n.y * sz, (tg.z * sx + bt.z * sy) + n.z * sz) : mk(0, 0, 1);
             double wt; uint32_t wslot;
+            // (the dispatch restated, not walk<>: with the wrapper four of this kernel's six instantiations change 21-29 lines of assembly and would have to be timed
+            // like a shared body -- profiles/shared_query_bodies.txt)
             if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, hit, true, true, ro, rd, Q.max_t, wt, wslot);
             else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, hit, true, true, false, ro, rd, Q.max_t, wt, wslot);
             if (hit && wslot != kNone) mask |= 1u << k;
@@ -2092,10 +2147,20 @@ __global__ __launch_bounds__(64) void ray_colour_kernel(const DevScene S, uint32
     Prof prof{}; prof.last = 0;
 #endif
     const uint32_t c = trace_colour<kWalk, true, false>(PROF_ARG S, stk, ok, o, d);
-#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
-    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
-#endif
+    BAND_FLUSH();
     if (ok) colours[i] = c;
+}
+
+// A lane of a per-ray launch that takes rays: ray i of n, its origin, direction and bound (no max_t array: unbounded).  Lanes beyond the batch (not ok) hold a
+// harmless ray, take part in no walk and store nothing.
+struct RayLane { uint32_t i; bool ok; V3 o, d; double mt; };
+__device__ __forceinline__ RayLane ray_lane(uint32_t n, const double* __restrict__ origins, const double* __restrict__ dirs, const double* __restrict__ max_t) {
+    RayLane R;
+    R.i = blockIdx.x * 64 + threadIdx.x;
+    R.ok = R.i < n;
+    R.o = R.ok ? ld3(origins + 3 * (size_t)R.i) : mk(0, 0, 0); R.d = R.ok ? ld3(dirs + 3 * (size_t)R.i) : mk(0, 0, 1);
+    R.mt = (R.ok && max_t) ? max_t[R.i] : kInf;
+    return R;
 }
 
 template <int kWalk>
@@ -2104,19 +2169,16 @@ __global__ __launch_bounds__(64) void intersect_kernel(const DevScene S, uint32_
                                                        double* __restrict__ u_out, double* __restrict__ v_out, uint32_t* __restrict__ tri_out) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    const bool ok = i < n;
-    const V3 o = ok ? ld3(origins + 3 * (size_t)i) : mk(0, 0, 0), d = ok ? ld3(dirs + 3 * (size_t)i) : mk(0, 0, 1);
-    const double mt = (ok && max_t) ? max_t[i] : kInf;
+    const RayLane R = ray_lane(n, origins, dirs, max_t);
+    const uint32_t i = R.i;
+    const bool ok = R.ok;
+    const V3 o = R.o, d = R.d;
     double t; uint32_t slot;
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, ok, false, !origin_ray_in_suspect_plane(S, o, d), o, d, mt, t, slot);
-    else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, ok, false, !origin_ray_in_suspect_plane(S, o, d), false, o, d, mt, t, slot);
-#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
-    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
-#endif
+    walk<kWalk, true>(PROF_ARG S, stk, ok, false, !origin_ray_in_suspect_plane(S, o, d), false, o, d, R.mt, t, slot);
+    BAND_FLUSH();
     if (!ok) return;
     // Any output may be null (rrt.h: rrt_intersect_rays_device): the pointers are kernel arguments, so every test below is wave-uniform.
     if (slot == kNone) {
@@ -2138,38 +2200,28 @@ __global__ __launch_bounds__(64) void intersect_kernel(const DevScene S, uint32_
 
 // Some/None of the same walk (rrt.h: rrt_occluded_rays): one byte per ray.  The walk runs as a shadow query (any_ok: traverse / traverse_ray stop at the
 // first node whose own list proves Some, see the comment at that rule), with intersect_kernel's guard; no second Moller-Trumbore, no t, no attribute load.
+// kFarAnchor = false: the frame kernels anchor the bundle of a tile's shadow rays at the light, where they end together; a caller's batch need not end
+// anywhere together, and on the rays of tools/ray_batch_bench.py that do, the anchor at the origins is the faster one: DESIGN.md section 4.
 template <int kWalk>
 __global__ __launch_bounds__(64) void occlusion_kernel(const DevScene S, uint32_t n, const double* __restrict__ origins, const double* __restrict__ dirs,
                                                        const double* __restrict__ max_t, uint8_t* __restrict__ occluded) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    const bool ok = i < n;
-    const V3 o = ok ? ld3(origins + 3 * (size_t)i) : mk(0, 0, 0), d = ok ? ld3(dirs + 3 * (size_t)i) : mk(0, 0, 1);
-    const double mt = (ok && max_t) ? max_t[i] : kInf;
+    const RayLane R = ray_lane(n, origins, dirs, max_t);
     double t; uint32_t slot;
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, ok, true, !origin_ray_in_suspect_plane(S, o, d), o, d, mt, t, slot);
-    // (kFarAnchor = false: the frame kernels anchor the bundle of a tile's shadow rays at the light, where they end together; a caller's batch need not end
-    // anywhere together, and on the rays of tools/ray_batch_bench.py that do, the anchor at the origins is the faster one: DESIGN.md section 4)
-    else traverse<kWalk == kWalkBundle, true, false>(PROF_ARG S, stk, ok, true, !origin_ray_in_suspect_plane(S, o, d), false, o, d, mt, t, slot);
-#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
-    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
-#endif
-    if (ok) occluded[i] = slot != kNone ? 1 : 0;
+    walk<kWalk, true, false>(PROF_ARG S, stk, R.ok, true, !origin_ray_in_suspect_plane(S, R.o, R.d), false, R.o, R.d, R.mt, t, slot);
+    BAND_FLUSH();
+    if (R.ok) occluded[R.i] = slot != kNone ? 1 : 0;
 }
 
-// The full surface record of an arbitrary ray's first hit and the reference's next ray from there (rrt.h: rrt_surface_rays_device): surface_kernel's loop behind
-// the front end of the per-ray kernels.  ONE call site of the walk.  The first turn walks the caller's rays with intersect_kernel's arguments (closest hit, its
-// guard, not one_origin); every later turn walks the shadow rays of all hit lanes towards ONE point light with the arguments surface_kernel gives a shadow walk
-// (any_ok, filters on, not one_origin; the rays of a turn end at one light, so the bundle's anchor is the frame kernels': the far ends).  Which turn it is, and
-// which light, is wave-uniform: the lights are kernel arguments.  Every point light is walked, also those behind the reference's `break` (raytracer.rs:235-237).
-// A ray whose bound is NaN or not positive is a miss of intersect_kernel's walk whatever the scene holds; it takes part in no walk here.
+// The full surface record of an arbitrary ray's first hit and the reference's next ray from there (rrt.h: rrt_surface_rays_device): surface_body behind the front
+// end of the per-ray kernels.  The first walk takes the caller's rays with intersect_kernel's arguments (closest hit within the caller's bound, not one_origin);
+// a ray whose bound is NaN or not positive is a miss of that walk whatever the scene holds, and takes part in no walk here.
 // The twelve output pointers are kernel arguments, so each test on them is wave-uniform: no `lights`: no shadow walk; none of albedo, normal, material, lights,
-// next_origin, next_dir: no attribute load; none of those nor u nor v: no second Moller-Trumbore.  A wave without a hit leaves the loop after the first turn.
-// No lane leaves before the last walk: the walks need the whole wave in uniform control flow.
+// next_origin, next_dir: no attribute load; none of those nor u nor v: no second Moller-Trumbore.
 // Four waves per SIMD like the frame kernels, unlike the other per-ray kernels: uncapped it takes 134-149 VGPRs and runs at 3 waves; capped it spills 16-38 VGPRs
 // (36-92 B of scratch) and is 5-18 % faster on 11 of the 12 measured cases (profiles/ray_surface_kernel_resources.txt, profiles/ray_surface.json).
 template <int kWalk>
@@ -2177,88 +2229,44 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_rays_kernel(const D
                                                           const double* __restrict__ max_t, const RaySurfaceParams Q) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    const bool ok = i < n_rays;
-    const V3 o = ok ? ld3(origins + 3 * (size_t)i) : mk(0, 0, 0), d = ok ? ld3(dirs + 3 * (size_t)i) : mk(0, 0, 1);
-    const double mt = (ok && max_t) ? max_t[i] : kInf;
-    const bool alive = ok && mt > 0.0;                                                 // (false for a NaN bound too)
+    const RayLane R = ray_lane(n_rays, origins, dirs, max_t);
+    const uint32_t i = R.i;
+    const V3 d = R.d;
+    const bool alive = R.ok && R.mt > 0.0;                                             // (false for a NaN bound too)
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    const bool first_ok = !origin_ray_in_suspect_plane(S, o, d);                       // exactness guard of the first walk (intersect_kernel)
     const bool want_attr = Q.albedo || Q.normal || Q.material || Q.lights || Q.next_origin || Q.next_dir;
-    const bool want_uv = Q.u || Q.v || want_attr;
-    const uint32_t n_lights = Q.lights ? S.n_lights : 0u;                              // no lights array: no shadow walk
-    bool found = false;
-    bool shadow = false;                                                               // wave-uniform: the walk about to start is a shadow walk, towards light li
-    uint32_t li = 0;
-    double t = 0, u = 0, v = 0;
-    uint32_t tri = kNone, mat = kNone, mask = 0, col = 0x00FFFFFFu;                    // WHITE, raytracer.rs:109-111
-    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
-    V3 ro = o, rd = d; double rmax = mt;
-    for (;;) {
-        double wt; uint32_t wslot;
-        const bool active = shadow ? found : alive;
-        if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, active, shadow, shadow || first_ok, ro, rd, rmax, wt, wslot);
-        else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, active, shadow, shadow || first_ok, false, ro, rd, rmax, wt, wslot);
-        if (!shadow) {
-            shadow = true;
-            found = alive && wslot != kNone;
-            if (found) {
-                // --- hit: raytracer.rs:39-57
-                t = wt;
-                p = o + d * wt;                                                          // raytracer.rs:39
-                if (Q.tri) tri = S.attr[wslot].orig;
-                if (want_uv) { double t2; mt_full(S.geom + wslot, o, d, t2, u, v); }
-                if (want_attr) surface_of_hit(S, wslot, u, v, mat, col, n);
-            }
-            if (!__any(found)) break;                                                    // no hit in the wave: nothing to ask the lights
-        } else {
-            if (found && wslot == kNone) mask |= 1u << li;                               // triangle_exists_between_points says "lit" for None, raytracer.rs:181-187
-            li++;
-        }
-        // the light list up to the next point light (raytracer.rs:205-255): Ambient and Directional lights reach every hit
-        while (li < n_lights && S.lights[li].kind != 1u) { if (found) mask |= 1u << li; li++; }
-        if (li >= n_lights) break;
-        const V3 dir = ld3(S.lights[li].v) - p;                                          // the shadow ray, raytracer.rs:164-188, as trace_colour forms it
-        ro = p + n * S.surface_offset;
-        rd = dir;
-        rmax = length(dir);
-    }
-#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
-    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
-#endif
-    if (!ok) return;
-    if (Q.hit) Q.hit[i] = found ? 1 : 0;
-    if (Q.t) Q.t[i] = t;
-    if (Q.u) Q.u[i] = u;
-    if (Q.v) Q.v[i] = v;
-    if (Q.tri) Q.tri[i] = tri;
-    if (Q.albedo) Q.albedo[i] = col;
+    const SurfaceHit h = surface_body<kWalk, true>(PROF_ARG S, stk, alive, false, R.o, d, R.mt, 0x00FFFFFFu, Q.u || Q.v || want_attr, Q.tri != nullptr, want_attr, Q.lights != nullptr);
+    BAND_FLUSH();
+    if (!R.ok) return;
+    if (Q.hit) Q.hit[i] = h.found ? 1 : 0;
+    if (Q.t) Q.t[i] = h.t;
+    if (Q.u) Q.u[i] = h.u;
+    if (Q.v) Q.v[i] = h.v;
+    if (Q.tri) Q.tri[i] = h.tri;
+    if (Q.albedo) Q.albedo[i] = h.col;
     const size_t j = 3 * (size_t)i;
-    if (Q.point) { Q.point[j] = p.x; Q.point[j + 1] = p.y; Q.point[j + 2] = p.z; }
-    if (Q.normal) { Q.normal[j] = n.x; Q.normal[j + 1] = n.y; Q.normal[j + 2] = n.z; }
-    if (Q.material) Q.material[i] = mat;
-    if (Q.lights) Q.lights[i] = mask;
+    if (Q.point) { Q.point[j] = h.p.x; Q.point[j + 1] = h.p.y; Q.point[j + 2] = h.p.z; }
+    if (Q.normal) { Q.normal[j] = h.n.x; Q.normal[j + 1] = h.n.y; Q.normal[j + 2] = h.n.z; }
+    if (Q.material) Q.material[i] = h.mat;
+    if (Q.lights) Q.lights[i] = h.mask;
     if (Q.next_origin) {
-        const V3 q = found ? p + n * S.surface_offset : mk(0, 0, 0);                     // raytracer.rs:82
+        const V3 q = h.found ? h.p + h.n * S.surface_offset : mk(0, 0, 0);               // raytracer.rs:82
         Q.next_origin[j] = q.x; Q.next_origin[j + 1] = q.y; Q.next_origin[j + 2] = q.z;
     }
     if (Q.next_dir) {
         V3 r = mk(0, 0, 0);
-        if (found) { const double d_dot_n = dot(d, n); r = normalised(d - (n * 2.0) * d_dot_n); }   // raytracer.rs:78-79, as trace_colour forms it
+        if (h.found) { const double d_dot_n = dot(d, h.n); r = normalised(d - (h.n * 2.0) * d_dot_n); }   // raytracer.rs:78-79, as trace_colour forms it
         Q.next_dir[j] = r.x; Q.next_dir[j + 1] = r.y; Q.next_dir[j + 2] = r.z;
     }
 }
 
-// Shading of arbitrary rays from kept records (rrt.h: rrt_shade_rays_device): shade_kernel's state machine behind the front end of the per-ray kernels.  A ray
-// starts as the hit its record holds -- point, normal, material, the low 24 bits of albedo, and the caller's direction as the segment direction -- of a segment of
-// get_ray_colour_recursive that stands at recursion depth Q.depth, with the lights and materials in force NOW.  A turn SHADES first and WALKS second, as in
-// shade_kernel: a wave none of whose lanes has a ray in flight -- matte hits with a mask, dead rays -- leaves without calling the walk.  ONE call site of the walk
-// with shade_kernel's arguments: every ray is a secondary ray (filters on, not one_origin, any_ok for a shadow ray).
-// What the batch's first level yields is kept in slot 0 of the stack: `local`, the unquantised colour of raytracer.rs:67-71, and `kr`, the material's where the
-// reference reflects there (kr > 0 and Q.depth below max_reflection_depth), else 0.0.  Slots are indexed by level - Q.depth; `room` levels may still reflect, so a
-// Q.depth at or beyond max_reflection_depth gives direct lighting only, whatever its value.
+// Shading of arbitrary rays from kept records (rrt.h: rrt_shade_rays_device): shade_body behind the front end of the per-ray kernels.  A ray enters as the hit its
+// record holds -- point, normal, material, the low 24 bits of albedo, and the caller's direction as the segment direction -- of a segment of
+// get_ray_colour_recursive that stands at recursion depth Q.depth, with the lights and materials in force NOW.
+// What the batch's first level yields is kept in slot 0 of the stack (shade_body: kRecord) and stored as `local` and `kr`.  Slots are indexed by level - Q.depth;
+// `room` levels may still reflect, so a Q.depth at or beyond max_reflection_depth gives direct lighting only, whatever its value.
 // The pointers and Q.depth are kernel arguments, so each test on them is wave-uniform: with a mask no shadow ray of the record's hit is formed; without `colour` no
 // reflection ray is formed, and with both no lane ever has a ray in flight: the walk is not called.
 // A material index at or beyond the table (0xFFFFFFFF: a miss or a dead ray) is WHITE, (0, 0, 0) and 0.0; no value of the caller's arrays is used as an index.
@@ -2281,7 +2289,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_rays_kernel(const Dev
     // ---- the record: the hit of the batch's own segment
     bool live = false;                      // the lane holds a hit whose colour is not known yet
     V3 seg_d = mk(0, 0, 1), p = mk(0, 0, 0), n = mk(0, 0, 0);
-    uint32_t col = 0, mat = 0, li = 0, lvl = 0;   // lvl: levels below the batch's own = the stack slot of the hit the lane holds
+    uint32_t col = 0, mat = 0, li = 0, lvl = 0;
     uint32_t n_eval = 0;                    // lights [0, n_eval) contribute (an occluded point light ends the loop, raytracer.rs:235-237)
     uint32_t term = 0x00FFFFFFu;            // colour of the last segment; WHITE for a miss, raytracer.rs:109-111
     if (ok) {
@@ -2290,117 +2298,23 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_rays_kernel(const Dev
             live = true;
             seg_d = ld3(Q.dirs + j); p = ld3(Q.point + j); n = ld3(Q.normal + j);
             col = Q.albedo[i] & 0x00FFFFFFu;
-            if (Q.lights) {                 // the kept mask answers the shadow queries of this hit: the light loop below is skipped for it
+            if (Q.lights) {                 // the kept mask answers the shadow queries of this hit: the light loop of shade_body is skipped for it
                 const uint32_t first_dark = (uint32_t)__builtin_ctz(~Q.lights[i] | (1u << RRT_MAX_LIGHTS));   // (n_lights <= 16: bits at and above it never count)
                 n_eval = first_dark < S.n_lights ? first_dark : S.n_lights;
                 li = 0xFFFFu;
             }
         }
     }
-    bool in_shadow = false;                 // false: the ray in flight is a reflection ray; true: a shadow ray
-    V3 ro = mk(0, 0, 0), rd = mk(0, 0, 1); double rmax = kInf;
     double st_local[RRT_MAX_REFLECT][3]; double st_kr[RRT_MAX_REFLECT];
     st_local[0][0] = st_local[0][1] = st_local[0][2] = 0.0; st_kr[0] = 0.0;             // what a dead ray reports
-    for (;;) {
-        // ---- shade: every live lane holds a hit (p, n, mat, col, seg_d) and stands at light li of its list
-        if (live) {
-            // the light list (raytracer.rs:205-255) up to the next point light, whose shadow ray (raytracer.rs:164-188) is walked next: trace_colour's
-            while (li < S.n_lights && !in_shadow) {
-                const DevLight& L = S.lights[li];
-                if (L.kind == 1u) {
-                    const V3 dir = ld3(L.v) - p;
-                    ro = p + n * S.surface_offset;
-                    rd = dir;
-                    rmax = length(dir);
-                    in_shadow = true;
-                } else {
-                    li++;
-                }
-            }
-            if (!in_shadow) {
-                if (li != 0xFFFFu) n_eval = S.n_lights;
-                // --- compute_lighting_intensity, raytracer.rs:192-258
-                const DevMaterial& M = S.mats[mat];
-                const V3 vdir = neg(seg_d);
-                const double len_n = length(n), len_v = length(vdir);
-                V3 I = mk(0.0, 0.0, 0.0);
-                for (uint32_t k = 0; k < n_eval; ++k) {
-                    const DevLight& L = S.lights[k];
-                    if (L.kind == 0u) {                                              // Ambient, raytracer.rs:207-209
-                        I = I + ld3(M.ka) * L.intensity;
-                    } else {                                                         // Directional (raytracer.rs:210-227) / unoccluded Point (raytracer.rs:239-252)
-                        const V3 l = (L.kind == 2u) ? ld3(L.v) : ld3(L.v) - p;
-                        const double n_dot_l = dot(n, l);
-                        I = I + diffuse_term(L.intensity, n_dot_l, len_n, length(l), ld3(M.kd));
-                        I = I + specular_term(PROF_ARG !S.specular_all, M.ns, L.intensity, n, vdir, len_v, l, ld3(M.ks), I);
-                    }
-                }
-                // --- raytracer.rs:67-108
-                const V3 local = mk((double)((col >> 16) & 255u) * I.x, (double)((col >> 8) & 255u) * I.y, (double)(col & 255u) * I.z);
-                const double kr = M.kr;
-                const bool reflects = kr > 0.0 && lvl < room;                        // raytracer.rs:76
-                if (reflects || lvl == 0u) {                                         // (slot 0 also carries the `local` and `kr` outputs)
-                    st_local[lvl][0] = local.x; st_local[lvl][1] = local.y; st_local[lvl][2] = local.z; st_kr[lvl] = reflects ? kr : 0.0;
-                }
-                if (reflects && Q.colour) {                                          // (no colour asked for: no reflection ray)
-                    const double d_dot_n = dot(seg_d, n);
-                    rd = normalised(seg_d - (n * 2.0) * d_dot_n);                    // raytracer.rs:79
-                    ro = p + n * S.surface_offset;                                   // raytracer.rs:82
-                    rmax = kInf;
-                    lvl++;
-                } else {
-                    term = (clamp_u8(local.x) << 16) | (clamp_u8(local.y) << 8) | clamp_u8(local.z);   // raytracer.rs:104-108
-                    live = false;
-                }
-            }
-        }
-        if (!__any(live)) break;                                                     // no ray in flight in the wave
-        // ---- walk: the shadow and reflection rays in flight, together
-        double t; uint32_t slot;
-        if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, live, in_shadow, true, ro, rd, rmax, t, slot);
-        else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, live, in_shadow, true, false, ro, rd, rmax, t, slot);
-        if (live) {
-            const bool found = slot != kNone;
-            if (!in_shadow) {
-                if (!found) {
-                    term = 0x00FFFFFFu; live = false;                                // WHITE, raytracer.rs:109-111
-                } else {
-                    // --- hit: raytracer.rs:39-57
-                    double u = 0, v = 0, t2;
-                    mt_full(S.geom + slot, ro, rd, t2, u, v);
-                    seg_d = rd;
-                    p = ro + rd * t;                                                 // raytracer.rs:39
-                    surface_of_hit(S, slot, u, v, mat, col, n);
-                    li = 0;                                                          // compute_lighting_intensity, raytracer.rs:199-203
-                }
-            } else {
-                // --- result of the shadow ray for point light li (raytracer.rs:232-237): occluded -> `break` out of the whole light loop
-                if (found) { n_eval = li; li = 0xFFFFu; }
-                else li++;
-                in_shadow = false;
-            }
-        }
-    }
-#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
-    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
-#endif
+    const ShadeEnd E = shade_body<kWalk, true, true>(PROF_ARG S, stk, room, Q.colour != nullptr, live, seg_d, p, n, col, mat, li, lvl, n_eval, term, st_local, st_kr);
+    BAND_FLUSH();
     if (!ok) return;
     if (Q.local) { Q.local[j] = st_local[0][0]; Q.local[j + 1] = st_local[0][1]; Q.local[j + 2] = st_local[0][2]; }
     if (Q.kr) Q.kr[i] = st_kr[0];
-    if (Q.colour) {
-        // unwind the reflection chain, innermost first (raytracer.rs:85-101): every level quantises to u8 before blending
-        uint32_t c = term;
-        for (uint32_t k = lvl; k-- > 0;) {
-            const double kr = st_kr[k];
-            const double fx = st_local[k][0] * (1.0 - kr) + (double)((c >> 16) & 255u) * kr;
-            const double fy = st_local[k][1] * (1.0 - kr) + (double)((c >> 8) & 255u) * kr;
-            const double fz = st_local[k][2] * (1.0 - kr) + (double)(c & 255u) * kr;
-            c = (clamp_u8(fx) << 16) | (clamp_u8(fy) << 8) | clamp_u8(fz);
-        }
-        Q.colour[i] = c;
-    }
+    if (Q.colour) Q.colour[i] = shade_unwind(E.term, E.lvl, st_local, st_kr);
 }
-// Ambient occlusion for arbitrary ray records (rrt.h: rrt_ambient_rays_device): ambient_kernel's sample loop behind the front end of the per-ray kernels.  A lane
+// Ambient occlusion for arbitrary ray records (rrt.h: rrt_ambient_rays_device): ambient_kernel's sample loop -- restated, see there -- behind the front end of the per-ray kernels.  A lane
 // loads its record -- point, normal, material, as the per-ray surface launch wrote them -- and builds the reference's tangent frame (raytracer.rs:137-152) ONCE;
 // the loop is over the SAMPLES: sample k of the table -- kernel arguments, wave-uniform -- gives every hit lane of the wave its ray k, and a turn keeps one bit
 // per lane.  The rays live in registers only.
@@ -2447,14 +2361,11 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_rays_kernel(const D
             // (tg*sx + bt*sy) + n*sz, ambient_kernel's five operations per component.  (a lane without a hit takes no part; its ray is a harmless one)
             const V3 rd = hit ? mk((tg.x * sx + bt.x * sy) + n.x * sz, (tg.y * sx + bt.y * sy) + n.y * sz, (tg.z * sx + bt.z * sy) + n.z * sz) : mk(0, 0, 1);
             double wt; uint32_t wslot;
-            if constexpr (kWalk == kWalkRay) traverse_ray<true>(PROF_ARG S, stk, hit, true, true, ro, rd, Q.max_t, wt, wslot);
-            else traverse<kWalk == kWalkBundle, true>(PROF_ARG S, stk, hit, true, true, false, ro, rd, Q.max_t, wt, wslot);
+            walk<kWalk, true>(PROF_ARG S, stk, hit, true, true, false, ro, rd, Q.max_t, wt, wslot);
             if (hit && wslot != kNone) mask |= 1u << k;
         }
     }
-#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
-    for (int k = 0; k < 4; k++) if (prof.b[k]) atomicAdd(S.prof + 24 + k, prof.b[k]);
-#endif
+    BAND_FLUSH();
     if (!ok) return;
     if (Q.occluded) Q.occluded[i] = mask;
     if (Q.open) Q.open[i] = n_samples - (uint32_t)__popc(mask);                          // (a miss: mask 0, every ray open -- the rule of ambient_kernel's grey)
