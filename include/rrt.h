@@ -720,6 +720,95 @@ int rrt_sort_rays_device(rrt_raytracer *rt, uint32_t n, uint32_t key_mode, const
 int rrt_sort_rays(rrt_raytracer *rt, uint32_t n, uint32_t key_mode, const uint32_t *keys, const rrt_ray_set *src, const rrt_ray_set *dst,
                   uint32_t *index, uint32_t *keys_out, uint32_t *count);
 
+/* The two ends of the per-ray pipeline, and a frame traced as ray generations.  rrt_surface_rays_device -> rrt_shade_rays_device -> rrt_compact_rays_device (->
+ * rrt_sort_rays_device) take a batch of rays from a first hit to `local` and `kr` per level of a reflection chain.  These calls supply what stands before and behind
+ * them: the rays a frame traces, as a batch; the finish of one level of the chain; the pixels.  rrt_render_wavefront strings all of it together.
+ *
+ * FRAME RAYS.  rrt_frame_rays[_device]: the primary rays of a region of a frame in the pose in force (rrt_camera; the vp_* options apply), as a batch of
+ * n = rrt_frame_ray_count(width, height, region, order) entries.  region as rrt_region: NULL = the whole frame.  Entry e is sub-sample s (the order of rrt_visibility)
+ * of canvas pixel (px, py), region = {x0, y0, w, h}:
+ *   RRT_ORDER_ROWS   n = 4 * w * h;  e = ((py - y0) * w + (px - x0)) * 4 + s -- the element order of a [h][w][4] plane of the region calls;
+ *   RRT_ORDER_TILES  n = 64 * tiles_w * tiles_h;  e = (((ty - y0 / 4) * tiles_w + (tx - x0 / 4)) * 16 + (py & 3) * 4 + (px & 3)) * 4 + s with tx = px / 4, ty = py / 4:
+ *                    4x4-pixel tiles anchored at multiples of 4 of the FRAME, not of the region -- tiles_w = (x0 + w + 3) / 4 - x0 / 4, tiles_h likewise -- row-major
+ *                    over that tile rectangle.  One aligned run of 64 entries is the 4x4 pixels x 4 sub-samples that one wave of the frame kernels holds, so a
+ *                    per-ray stage (64 consecutive entries per wave) walks the frame's own waves; planes flattened in ROWS order cost 1.02-1.33x of that
+ *                    (profiles/ambient_rays.json).
+ * n is a multiple of 4.  A traced pixel's entry: origins[e] = the eye in force, dirs[e] = the direction the frame kernels form for it, bit for bit -- per component
+ * (right.k*a + up.k*b) + forward.k*c, five operations each rounded on its own (rrt_camera) -- and max_t[e] = +inf.  A DEAD entry -- a pixel the reference never traces
+ * (canvas row 0, row 1 of an odd height, the last column of an odd width) and, in TILES order, a pixel outside the region or the frame -- gets origins = dirs =
+ * (0.0, 0.0, 0.0) and max_t = NaN (0x7FF8000000000000, the dead value of rrt_compact_rays): with max_t the batch can go to every per-ray call as it is, and a dead
+ * ray takes part in no walk.  Any of the three arrays may be NULL (not written), at least one is set; WITHOUT max_t THE CALLER GETS NO DEAD MARKER -- a dead entry's
+ * zero direction is then an ordinary (degenerate) ray to the per-ray calls.  Every element of every requested array is written; the same bits on every run.  The
+ * arrays are 8-byte aligned; 16-byte aligned arrays (any device allocation) are written with 16-byte stores.
+ * rrt_frame_ray_count: 0 for arguments the calls refuse, and for a region of more than 2^32 - 1 entries (refused too: n is the uint32 of the per-ray calls).
+ * rrt_frame_rays_device: arrays in device memory of rt's device; one kernel enqueued on `stream` (hipStream_t, NULL = default): no allocation, no copy, no
+ * synchronisation.  rrt_frame_rays: arrays in host memory; blocking, one device allocation of the call's own.  These are not ray calls: rrt_last_stats stays as it
+ * was, in both forms (the precedent of rrt_compact_rays).
+ * RRT_ERR_INVALID_ARG, before any GPU work and before the handle is looked at: NULL rt; a bad frame size; a region with w == 0 or h == 0 or one that sticks out of
+ * the frame; an unknown order; all three arrays NULL.
+ *
+ * CHAIN RESOLVE.  rrt_mix_rays[_device]: one level of the unwind of get_ray_colour_recursive (raytracer.rs:89-108), in source order.  Per entry i of n:
+ *   material[i] >= n_mats (the hit rule of rrt_shade_rays; a miss or a dead entry):          colour[i] = 0x00FFFFFF, the reference's background;
+ *   a hit, and kr == NULL or reflected == NULL or !(kr[i] > 0.0):                             the three channels of local[i], each clamped to [0, 255] and truncated
+ *                                                                                             (raytracer.rs:104-108; NaN gives 0), 0x00RRGGBB;
+ *   a hit with kr[i] > 0.0, kr and reflected given:                                           per channel clamp(local * (1.0 - kr) + (double)channel(reflected[i]) * kr)
+ *                                                                                             -- the f64 operations of raytracer.rs:89-101, each rounded on its own.
+ * local [n][3] and kr [n] are what rrt_shade_rays* wrote for the level; reflected [n] holds the colours of the level BELOW in this level's order: the caller brings
+ * them there with rrt_scatter_rays_device (4-byte elements) and the `index` of this level's compaction.  reflected[i] is read only for the entries that mix, and only
+ * its low 24 bits count.  material may be NULL: every entry is then a hit.  No value of the caller's arrays is used as an index.  Inputs and output must not overlap.
+ * RRT_ERR_INVALID_ARG, before any GPU work and before the handle is looked at: NULL rt; local or colour NULL with n > 0.  n == 0 is RRT_OK with nothing enqueued.
+ * rrt_mix_rays_device: one kernel on `stream`, no allocation, no copy, no synchronisation; rrt_mix_rays: host arrays, blocking, one allocation of the call's own.
+ * rrt_last_stats stays as it was.
+ *
+ * PIXELS.  rrt_mix_pixels[_device]: colours [rrt_frame_ray_count(...)] in the given order -> fb / out_fb [region.h][region.w] pixels, 0x00RRGGBB.  A traced pixel is
+ * the reference's Color::mix (entities.rs:49-69) of its four sub-sample colours as the frame kernels compute it: channel sums, truncating / 4 (only the low 24 bits
+ * of a colour count); a pixel the reference never traces is 0; every pixel of the region is written; dead entries are not read.  With region == NULL the layout is
+ * the framebuffer of rrt_render_device.  Refusals as rrt_frame_rays, with "colours or the
+ * framebuffer NULL" for its last one; the two forms as above; rrt_last_stats stays as it was.
+ *
+ * THE FRAME BY RAY GENERATIONS.  rrt_render_wavefront[_device]: CONTRACT -- the output is the same region of the frame rrt_render produces in the pose and with the
+ * lights and materials in force, bit for bit -- traced level by level instead of ray by ray:
+ *   1. the frame rays of the region in `order`, with max_t;
+ *   2. for depth k = 0 .. max_reflection_depth: the surface records of the level's rays (rrt_surface_rays_device: albedo, point, normal, material, lights, and for
+ *      k < max next_origin / next_dir); local and kr of the level (rrt_shade_rays_device at depth k, with the mask: this launch walks nothing); for k < max the
+ *      compaction of the mirror hits' next rays into the rays of level k + 1 (rrt_compact_rays_device, RRT_SELECT_MIRROR, max_t synthesised), its index kept;
+ *   3. back up, for k = max .. 0: the colours of level k + 1 scattered through the index of level k (rrt_scatter_rays_device), then rrt_mix_rays_device;
+ *   4. rrt_mix_pixels_device.
+ * Everything is enqueued on `stream`: no allocation, no copy to the host, no read-back of a count, no synchronisation.  Every level runs at the same
+ * n = rrt_frame_ray_count(...): the dead tail of a compacted level walks nothing.  The launches are those of the calls named above -- no kernel of its own.
+ * Traversal variant: the rule of rrt_intersect_rays_device -- the forced one, else the one kept for per-ray calls, else the frame variant; nothing is measured, and the
+ * call does not count as a frame of that size for the frame variant's measurement (RRT_FLAG_LANE_FILTER above).
+ * Work memory: d_work = device memory of at least rrt_wavefront_work_bytes(rt, width, height, region, order) bytes, 256-byte aligned, whose contents before and after
+ * mean nothing.  The size is 0 for arguments the call refuses, never smaller for a larger region, and at most
+ *   n * (229 + 40 * (max_reflection_depth + 1)) + 16384   bytes, n = rrt_frame_ray_count(...)
+ * -- per entry two generations of rays (2 x 56), one level's record arrays (104), two levels' colours and the scattered ones (12), the compaction's scratch, and per
+ * level what the way back up needs: local, kr, material and index (40).  About 1.2 GB for a 1920 x 1080 frame at the default depth of 5.
+ * rrt_last_stats afterwards: kernel_ms = the time between two events around the whole sequence, filter_variant = the variant used, width / height = the frame size,
+ * rays_primary = 4 * the traced pixels inside the region.
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer as it was: the refusals of rrt_frame_rays for rt, the frame size, the region and the order; a
+ * NULL framebuffer; a d_work that is NULL, not 256-byte aligned or smaller than rrt_wavefront_work_bytes says.
+ * rrt_render_wavefront: framebuffer in host memory; blocking; it owns and frees its work memory and downloads the region's pixels.
+ * rrt_raytracer_set_camera, set_lights, set_materials and set_triangles[_device] apply to every call made after they return, and must not overlap one in flight.
+ * Not covered, as for the other region calls: the rank/world tile partition, the rrt_multi_* path and the progressive path; sorting between levels. */
+enum { RRT_ORDER_ROWS = 0, RRT_ORDER_TILES = 1 };
+uint32_t rrt_frame_ray_count(uint32_t width, uint32_t height, const rrt_region *region, uint32_t order);   /* 0 for bad arguments */
+int rrt_frame_rays_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order,
+                          double *d_origins, double *d_dirs, double *d_max_t, void *stream);
+int rrt_frame_rays(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order,
+                   double *origins, double *dirs, double *max_t);
+int rrt_mix_rays_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_material, const double *d_local, const double *d_kr,
+                        const uint32_t *d_reflected, uint32_t *d_colour, void *stream);
+int rrt_mix_rays(rrt_raytracer *rt, uint32_t n, const uint32_t *material, const double *local, const double *kr,
+                 const uint32_t *reflected, uint32_t *colour);
+int rrt_mix_pixels_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order,
+                          const uint32_t *d_colours, void *d_fb, void *stream);
+int rrt_mix_pixels(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order,
+                   const uint32_t *colours, uint32_t *out_fb);
+size_t rrt_wavefront_work_bytes(const rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order);
+int rrt_render_wavefront_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order,
+                                void *d_fb, void *d_work, size_t work_bytes, void *stream);
+int rrt_render_wavefront(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order, uint32_t *out_fb);
+
 /* The octree of a raytracer whose set-up ran on the GPU (the default), read back from its device: same layout as rrt_model_get_octree; info (may be
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */
 int rrt_raytracer_get_octree(const rrt_raytracer *rt, rrt_model_info *info, double *aabb, uint32_t *first_child, uint32_t *tri_count,

@@ -110,6 +110,8 @@ SELECT_MODES = ("hit", "mirror", "flag")   # RRT_SELECT_HIT, RRT_SELECT_MIRROR, 
 DEAD_INDEX = 0xFFFFFFFF              # index of a tail slot of a compacted batch
 SORT_KEY_MODES = ("given", "ray", "record")   # RRT_SORT_KEY_GIVEN, RRT_SORT_KEY_RAY, RRT_SORT_KEY_RECORD
 DEAD_KEY = 0xFFFFFFFF                # sort key of a dead entry: it sorts last
+ORDER_ROWS, ORDER_TILES = 0, 1       # RRT_ORDER_ROWS, RRT_ORDER_TILES: the entry order of a frame's ray batch
+FRAME_RAY_ARRAYS = ("origins", "dirs", "max_t")   # what rrt_frame_rays writes, in its order: [n][3], [n][3], [n] float64
 
 # The plane table: every plane of rrt_visibility, rrt_surface and rrt_ambient, in the struct's order, as (dtype, elements per sub-sample, True = one value per
 # sub-sample, [h][w][4](...), False = one per pixel, [h][w]).  Everything else the binding knows about a plane is derived from it.
@@ -239,6 +241,16 @@ SYMBOLS = {
     "rrt_sort_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "rrt_sort_rays_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.POINTER(CRaySet), C.POINTER(CRaySet), _P, _P, _P, _P, C.c_size_t, _P]),
     "rrt_sort_rays": (C.c_int, [_P, C.c_uint32, C.c_uint32, _u32p, C.POINTER(CRaySet), C.POINTER(CRaySet), _u32p, _u32p, _u32p]),
+    "rrt_frame_ray_count": (C.c_uint32, [C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32]),
+    "rrt_frame_rays_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32, _P, _P, _P, _P]),
+    "rrt_frame_rays": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32, _dp, _dp, _dp]),
+    "rrt_mix_rays_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "rrt_mix_rays": (C.c_int, [_P, C.c_uint32, _u32p, _dp, _dp, _u32p, _u32p]),
+    "rrt_mix_pixels_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32, _P, _P, _P]),
+    "rrt_mix_pixels": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32, _u32p, _u32p]),
+    "rrt_wavefront_work_bytes": (C.c_size_t, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32]),
+    "rrt_render_wavefront_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32, _P, _P, C.c_size_t, _P]),
+    "rrt_render_wavefront": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32, _u32p]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
@@ -538,6 +550,25 @@ _SORT_KEY_READS = ((), ("origins", "dirs"), ("point", "normal", "material"))   #
 def sort_scratch_bytes(n: int) -> int:
     """rrt_sort_scratch_bytes: the device scratch sort_rays_into needs for a batch of n entries."""
     return int(lib().rrt_sort_scratch_bytes(int(n)))
+
+
+def _order(order: int, what: str) -> int:
+    if order not in (ORDER_ROWS, ORDER_TILES):
+        raise ValueError(f"{what}: unknown order {order!r}, want ORDER_ROWS ({ORDER_ROWS}) or ORDER_TILES ({ORDER_TILES})")
+    return int(order)
+
+
+def frame_ray_count(width: int, height: int, region=None, order: int = ORDER_ROWS) -> int:
+    """rrt_frame_ray_count: the entries of the ray batch of a region of a frame in `order` -- 4 per pixel in rows order, 64 per 4x4 tile of the frame the region
+    touches in tiles order; 0 for arguments the library refuses."""
+    return int(lib().rrt_frame_ray_count(int(width), int(height), _region(width, height, region)[0], _order(order, "frame_ray_count")))
+
+
+def _frame_ray_array(name: str, what: str):
+    """(dtype, elements per entry) of an array of rrt_frame_rays; an unknown name is a ValueError"""
+    if name not in FRAME_RAY_ARRAYS:
+        raise ValueError(f"{what}: unknown array {name!r}, want names from {FRAME_RAY_ARRAYS}")
+    return _PLANES_OF[CRaySet][name][:2]
 
 
 def _bound(name: str, *args):
@@ -1085,6 +1116,94 @@ class RayTracer(_Handle):
               scratch_bytes, _P(_stream(stream)))
 
     sort_scratch_bytes = staticmethod(sort_scratch_bytes)
+
+    # the two ends of the per-ray pipeline (rrt.h: rrt_frame_rays, rrt_mix_rays, rrt_mix_pixels) and the frame by ray generations (rrt_render_wavefront)
+    frame_ray_count = staticmethod(frame_ray_count)
+
+    def frame_rays(self, width: int, height: int, region=None, order: int = ORDER_ROWS, arrays=FRAME_RAY_ARRAYS) -> dict:
+        """rrt_frame_rays: {name: array} for the names asked for, from FRAME_RAY_ARRAYS -- origins, dirs float64 [n][3], max_t float64 [n] -- of the primary rays a
+        frame traces in the region in the pose in force, n = frame_ray_count(...).  A dead entry (a pixel the reference never traces; in tiles order a pixel outside
+        the region) has a zero origin and direction and max_t NaN."""
+        reg, o = _region(width, height, region)[0], _order(order, "frame_rays")
+        n = frame_ray_count(width, height, region, o)
+        out = {name: np.empty((n, w) if w > 1 else (n,), dtype) for name, (dtype, w) in ((name, _frame_ray_array(name, "frame_rays")) for name in arrays)}
+        _call("rrt_frame_rays", self._h, width, height, reg, o, *(_d(out.get(name)) for name in FRAME_RAY_ARRAYS))
+        return out
+
+    def frame_rays_into(self, out: dict, width: int, height: int, region=None, order: int = ORDER_ROWS, stream: Optional[int] = None):
+        """rrt_frame_rays_device: out = {name: contiguous float64 device tensor} for any subset of FRAME_RAY_ARRAYS -- 3 n elements for origins and dirs, n for max_t,
+        n = frame_ray_count(...).  Enqueued, not synchronised; last_stats stays as it was."""
+        reg, o = _region(width, height, region)[0], _order(order, "frame_rays_into")
+        n = frame_ray_count(width, height, region, o)
+        for name, t in out.items():
+            dtype, w = _frame_ray_array(name, "frame_rays_into")
+            _device_tensor(t, w * n, np.dtype(dtype).itemsize, name)
+        _call("rrt_frame_rays_device", self._h, width, height, reg, o, *(_ptr(out.get(name)) for name in FRAME_RAY_ARRAYS), _P(_stream(stream)))
+
+    def mix_rays(self, local, kr=None, reflected=None, material=None) -> np.ndarray:
+        """rrt_mix_rays: colour uint32 [n] of one level of the unwind -- 0x00FFFFFF where material is no material, the clamped `local` (float64 [n][3]) where
+        kr (float64 [n]) is not above 0 or kr or reflected is None, local * (1 - kr) + reflected * kr per channel, clamped, elsewhere.  reflected: uint32 [n], the
+        colours of the level below in this level's order.  material None: every entry is a hit."""
+        l = np.ascontiguousarray(local, np.float64).reshape(-1, 3)
+        n = l.shape[0]
+        k, r, m = (None if a is None else np.ascontiguousarray(a, dtype).reshape(-1) for a, dtype in ((kr, np.float64), (reflected, np.uint32), (material, np.uint32)))
+        for name, a in (("kr", k), ("reflected", r), ("material", m)):
+            assert a is None or a.size == n, f"mix_rays: {name} has {a.size} elements for {n} entries"
+        colour = np.empty(n, np.uint32)
+        _call("rrt_mix_rays", self._h, n, _u32(m), _d(l), _d(k), _u32(r), _u32(colour))
+        return colour
+
+    def mix_rays_into(self, colour_t, local_t, kr_t=None, reflected_t=None, material_t=None, stream: Optional[int] = None):
+        """rrt_mix_rays_device: colour_t n four-byte elements; local_t float64 of 3 n elements; kr_t float64 of n, reflected_t and material_t n four-byte elements,
+        each or None.  Enqueued, not synchronised; last_stats stays as it was."""
+        n = _batch_size(local_t, 3, "local")
+        _device_tensor(local_t, 3 * n, 8, "local"); _device_tensor(colour_t, n, 4, "colour")
+        for name, t, size in (("kr", kr_t, 8), ("reflected", reflected_t, 4), ("material", material_t, 4)):
+            if t is not None:
+                _device_tensor(t, n, size, name)
+        _call("rrt_mix_rays_device", self._h, n, _ptr(material_t), _ptr(local_t), _ptr(kr_t), _ptr(reflected_t), _ptr(colour_t), _P(_stream(stream)))
+
+    def mix_pixels(self, colours, width: int, height: int, region=None, order: int = ORDER_ROWS) -> np.ndarray:
+        """rrt_mix_pixels: the region's pixels, [h][w] uint32 0x00RRGGBB, from the colours of its ray batch (uint32, frame_ray_count(...) of them, in `order`):
+        Color::mix of a pixel's four sub-samples, 0 for a pixel the reference never traces."""
+        reg, w, h = _region(width, height, region)
+        o = _order(order, "mix_pixels")
+        c = np.ascontiguousarray(colours, np.uint32).reshape(-1)
+        n = frame_ray_count(width, height, region, o)
+        assert c.size == n, f"mix_pixels: colours has {c.size} elements for {n} entries"
+        fb = np.empty((h, w), np.uint32)
+        _call("rrt_mix_pixels", self._h, width, height, reg, o, _u32(c), _u32(fb))
+        return fb
+
+    def mix_pixels_into(self, fb_tensor, colours_t, width: int, height: int, region=None, order: int = ORDER_ROWS, stream: Optional[int] = None):
+        """rrt_mix_pixels_device: colours_t = frame_ray_count(...) four-byte elements in `order`; fb_tensor = w*h four-byte elements of the region.  Enqueued, not
+        synchronised; last_stats stays as it was."""
+        reg, w, h = _region(width, height, region)
+        o = _order(order, "mix_pixels_into")
+        _device_tensor(colours_t, frame_ray_count(width, height, region, o), 4, "colours")
+        _device_tensor(fb_tensor, w * h, 4, "fb")
+        _call("rrt_mix_pixels_device", self._h, width, height, reg, o, _ptr(colours_t), _ptr(fb_tensor), _P(_stream(stream)))
+
+    def wavefront_work_bytes(self, width: int, height: int, region=None, order: int = ORDER_ROWS) -> int:
+        """rrt_wavefront_work_bytes: the device work memory render_wavefront_into needs for this region and order; 0 for arguments the library refuses."""
+        return int(lib().rrt_wavefront_work_bytes(self._h, int(width), int(height), _region(width, height, region)[0], _order(order, "wavefront_work_bytes")))
+
+    def render_wavefront(self, width: int, height: int, region=None, order: int = ORDER_ROWS) -> np.ndarray:
+        """rrt_render_wavefront: the region of the frame render() produces, [h][w] uint32, traced as compacted ray generations -- frame rays, then per reflection
+        level surface records, local and kr, compaction of the mirror hits; the unwind back up; the pixels."""
+        reg, w, h = _region(width, height, region)
+        fb = np.empty((h, w), np.uint32)
+        _call("rrt_render_wavefront", self._h, width, height, reg, _order(order, "render_wavefront"), _u32(fb))
+        return fb
+
+    def render_wavefront_into(self, fb_tensor, work_t, width: int, height: int, region=None, order: int = ORDER_ROWS, stream: Optional[int] = None):
+        """rrt_render_wavefront_device: fb_tensor = w*h four-byte elements of the region; work_t = a contiguous device tensor of at least
+        wavefront_work_bytes(...) bytes, 256-byte aligned, whose contents mean nothing.  Enqueued, not synchronised."""
+        reg, w, h = _region(width, height, region)
+        o = _order(order, "render_wavefront_into")
+        _device_tensor(fb_tensor, w * h, 4, "fb")
+        assert getattr(work_t, "is_cuda", False) and work_t.is_contiguous(), "work: not a contiguous device tensor"
+        _call("rrt_render_wavefront_device", self._h, width, height, reg, o, _ptr(fb_tensor), _ptr(work_t), work_t.numel() * work_t.element_size(), _P(_stream(stream)))
 
     # engine.rs:196-253: chunked draw with an update after every chunk (on_update(fb, first_row, n_rows) stands in for canvas.update())
     def render_progressive(self, width: int, height: int, on_update=None, chunk_rows: int = 50) -> np.ndarray:

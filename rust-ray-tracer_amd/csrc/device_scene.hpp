@@ -258,6 +258,36 @@ struct SortParams {
 // key, four radix passes (hist, two scans, place) and the gather of q on `stream`
 int launch_sort(const SortParams& q, void* stream);
 
+// Arguments of the three kernels of wavefront.hip (rrt.h: rrt_frame_rays_device, rrt_mix_rays_device, rrt_mix_pixels_device).  A region of a frame as a batch of
+// entries in one of two orders: order 0 (RRT_ORDER_ROWS), [h][w][4 sub-samples] over the region's pixels; order 1 (RRT_ORDER_TILES), the 4x4-pixel tiles of the FRAME
+// that the region touches -- tiles_w per row from tile (tile_x0, tile_y0), row-major -- each [4][4][4 sub-samples].
+// FrameRaysParams: what render_kernel forms a primary ray from (FrameParams: the size, the scales, the view basis) and the eye; a null output array is not written.
+struct FrameRaysParams {
+    uint32_t width, height;
+    double x_scale, y_scale, z_value;       // engine.rs:189-191
+    double right[3], up[3], forward[3], eye[3];
+    uint32_t x0, y0, w, h;                  // the region, inside the frame
+    uint32_t tile_x0, tile_y0, tiles_w, order;
+    uint32_t n, _pad;                       // entries: 4 * w * h, or 64 * the tiles of the rectangle
+    double *origins, *dirs, *max_t;         // [n][3], [n][3], [n]
+};
+// MixRaysParams: one level of the unwind over n entries; material, kr and reflected may be null.
+struct MixRaysParams {
+    const uint32_t* material; const double *local, *kr; const uint32_t* reflected;
+    uint32_t* colour;
+    uint32_t n, n_mats;
+};
+// MixPixelsParams: colours in the given order -> fb [h][w], the region's pixels.
+struct MixPixelsParams {
+    uint32_t width, height, x0, y0, w, h;
+    uint32_t tile_x0, tile_y0, tiles_w, order;
+    const uint32_t* colours; uint32_t* fb;
+};
+// kernel launches (wavefront.hip).  All return hipError_t cast to int; nothing is synchronised; n == 0 launches nothing.
+int launch_frame_rays(const FrameRaysParams& q, void* stream);
+int launch_mix_rays(const MixRaysParams& q, void* stream);
+int launch_mix_pixels(const MixPixelsParams& q, void* stream);
+
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
 int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);

@@ -4,6 +4,8 @@
 //   Per-ray queries, the choice of the traversal variant, and the statistics of the last launch.
 //   Compaction of ray batches and records between two per-ray stages, its inverse (compact.hip) and their sort by a coherence key (sort.hip): no ray is traced, so
 //   these go past timed_launch and record.
+//   The two ends of that pipeline -- a frame's primary rays as a batch, the unwind of one level, the pixels (wavefront.hip) -- and the frame by ray generations
+//   that strings the stages together.
 // Every launch goes through ONE seam: timed_launch (the raytracer's two events around it) and record (what it traced, into rrt_stats).  Every measurement of the
 // variants goes through fastest_variant.  The region calls share one check of the region (region_in_force), one launch (launch_region_frame) and, for their host
 // forms, one routine that carves the kept device allocation and copies the planes up and down (with_kept_planes).  The host forms of the per-ray calls, of compaction
@@ -678,6 +680,119 @@ int sort_from_host(rrt_raytracer* rt, uint32_t n, uint32_t key_mode, const uint3
     return RRT_OK;
 }
 
+// ---- the two ends of the per-ray pipeline (rrt.h: rrt_frame_rays, rrt_mix_rays, rrt_mix_pixels; wavefront.hip) and the frame by ray generations that closes it
+// (rrt_render_wavefront).  The first three are not ray calls: no timed_launch, no record.
+// A region of a frame as a batch of entries: the region in force, the rectangle of 4x4-pixel tiles of the FRAME it touches, and the number of entries in the order.
+struct FrameBatch { rrt_region r; uint32_t order, tile_x0, tile_y0, tiles_w; uint64_t n; };
+// no handle is looked at; throws what the region calls throw, and for an unknown order or a batch beyond the uint32 n of the per-ray calls
+FrameBatch frame_batch(uint32_t width, uint32_t height, const rrt_region* region, uint32_t order) {
+    if (width == 0 || height == 0 || (uint64_t)width * height > 0x7FFFFFFFull) throw Error{RRT_ERR_INVALID_ARG, "bad frame size"};
+    if (order > RRT_ORDER_TILES) throw Error{RRT_ERR_INVALID_ARG, "unknown order: want RRT_ORDER_ROWS or RRT_ORDER_TILES"};
+    FrameBatch b{};
+    b.r = region_in_force(width, height, region);
+    b.order = order; b.tile_x0 = b.r.x0 / 4; b.tile_y0 = b.r.y0 / 4;
+    b.tiles_w = (b.r.x0 + b.r.w + 3) / 4 - b.tile_x0;
+    const uint32_t tiles_h = (b.r.y0 + b.r.h + 3) / 4 - b.tile_y0;
+    b.n = order == RRT_ORDER_ROWS ? 4ull * b.r.w * b.r.h : 64ull * b.tiles_w * tiles_h;
+    if (b.n > 0xFFFFFFFFull) throw Error{RRT_ERR_INVALID_ARG, "the region has more entries than a ray batch can hold (2^32 - 1)"};
+    return b;
+}
+// every check of a call that takes a frame, a region and an order, before any GPU work
+FrameBatch check_frame_batch(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order) {
+    check_frame(rt, width, height);
+    return frame_batch(width, height, region, order);
+}
+// the kernels' arguments (checked): the frame as launch_frame forms it, the eye in force
+FrameRaysParams frame_rays_params(const rrt_raytracer* rt, uint32_t width, uint32_t height, const FrameBatch& b, double* d_origins, double* d_dirs, double* d_max_t) {
+    const FrameParams f = frame_params(rt, width, height, 0, 1, false);
+    FrameRaysParams q{};
+    q.width = width; q.height = height; q.x_scale = f.x_scale; q.y_scale = f.y_scale; q.z_value = f.z_value;
+    for (int k = 0; k < 3; k++) { q.right[k] = f.right[k]; q.up[k] = f.up[k]; q.forward[k] = f.forward[k]; q.eye[k] = rt->scene.origin[k]; }
+    q.x0 = b.r.x0; q.y0 = b.r.y0; q.w = b.r.w; q.h = b.r.h;
+    q.tile_x0 = b.tile_x0; q.tile_y0 = b.tile_y0; q.tiles_w = b.tiles_w; q.order = b.order;
+    q.n = (uint32_t)b.n;
+    q.origins = d_origins; q.dirs = d_dirs; q.max_t = d_max_t;
+    return q;
+}
+MixPixelsParams mix_pixels_params(uint32_t width, uint32_t height, const FrameBatch& b, const uint32_t* d_colours, void* d_fb) {
+    return MixPixelsParams{width, height, b.r.x0, b.r.y0, b.r.w, b.r.h, b.tile_x0, b.tile_y0, b.tiles_w, b.order, d_colours, static_cast<uint32_t*>(d_fb)};
+}
+void check_mix_rays(const rrt_raytracer* rt, uint32_t n, const double* local, const uint32_t* colour) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (n && (!local || !colour)) throw Error{RRT_ERR_INVALID_ARG, "null array: a mix takes local and writes colour"};
+}
+
+// The frame by ray generations.  Its work memory, as byte offsets into the caller's allocation, every array in a slot of its own (device_memory.hpp: slot_bytes):
+// the rays of the level in hand and of the next one (origins, dirs, max_t, twice), the record arrays a level's surface launch writes and its shade launch reads, the
+// colours of two levels and the scattered colours of the level below, the compaction's scratch -- 228 bytes per entry -- and, KEPT PER LEVEL for the way back up,
+// local, kr, material and the compaction's index: 40 bytes per entry and level.
+constexpr uint32_t kMaxLevels = RRT_MAX_REFLECT + 1;
+struct WavefrontWork {
+    size_t origins[2], dirs[2], max_t[2];
+    size_t albedo, point, normal, lights, next_origin, next_dir;
+    size_t colour[2], reflected, scratch;
+    size_t local[kMaxLevels], kr[kMaxLevels], material[kMaxLevels], index[kMaxLevels];
+    size_t bytes;
+};
+WavefrontWork wavefront_work(uint64_t n, uint32_t levels) {
+    WavefrontWork w{};
+    size_t used = 0;
+    auto take = [&](size_t bytes) { const size_t at = used; used += slot_bytes(bytes ? bytes : 1); return at; };
+    for (int i = 0; i < 2; i++) { w.origins[i] = take(24 * n); w.dirs[i] = take(24 * n); w.max_t[i] = take(8 * n); w.colour[i] = take(4 * n); }
+    w.albedo = take(4 * n); w.point = take(24 * n); w.normal = take(24 * n); w.lights = take(4 * n); w.next_origin = take(24 * n); w.next_dir = take(24 * n);
+    w.reflected = take(4 * n); w.scratch = take(compact_scratch_bytes((uint32_t)n));
+    for (uint32_t k = 0; k < levels; k++) { w.local[k] = take(24 * n); w.kr[k] = take(8 * n); w.material[k] = take(4 * n); w.index[k] = take(4 * n); }
+    w.bytes = used;
+    return w;
+}
+uint32_t wavefront_levels(const rrt_raytracer* rt) { return std::min(rt->scene.max_reflection_depth, (uint32_t)RRT_MAX_REFLECT) + 1; }
+
+// every check but the work memory's, before any GPU work
+FrameBatch check_wavefront(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order, const void* fb) {
+    const FrameBatch b = check_frame_batch(rt, width, height, region, order);
+    if (!fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
+    return b;
+}
+// The pipeline of batch b (checked) on `stream`, with d_work (checked) carved as wavefront_work says: generate; per level surface -> shade (local and kr only, with
+// the mask: it walks nothing) -> compaction of the mirror hits' next rays into the next level's rays; back up, per level the colours of the level below scattered
+// into source order and mixed in; the pixels.  Every level runs at the same n: the dead tail of a compacted level walks nothing.  Only launchers that the per-ray
+// entry points use are called; one pair of events around all of it, one record.
+void launch_wavefront(rrt_raytracer* rt, uint32_t width, uint32_t height, const FrameBatch& b, void* d_fb, void* d_work, void* stream) {
+    const uint32_t n = (uint32_t)b.n, levels = wavefront_levels(rt), last = levels - 1;
+    const WavefrontWork w = wavefront_work(n, levels);
+    char* base = static_cast<char*>(d_work);
+    auto f64 = [&](size_t at) { return reinterpret_cast<double*>(base + at); };
+    auto u32 = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
+    const int variant = device_rays_variant(rt);
+    timed_launch(rt, stream, [&]() -> int {
+        HIP_TRY((hipError_t)launch_frame_rays(frame_rays_params(rt, width, height, b, f64(w.origins[0]), f64(w.dirs[0]), f64(w.max_t[0])), stream));
+        for (uint32_t k = 0; k <= last; k++) {
+            const uint32_t cur = k & 1u, nxt = cur ^ 1u;
+            RaySurfaceParams rec{};
+            rec.albedo = u32(w.albedo); rec.point = f64(w.point); rec.normal = f64(w.normal); rec.material = u32(w.material[k]); rec.lights = u32(w.lights);
+            if (k < last) { rec.next_origin = f64(w.next_origin); rec.next_dir = f64(w.next_dir); }
+            HIP_TRY((hipError_t)launch_surface_rays(rt->scene, n, f64(w.origins[cur]), f64(w.dirs[cur]), f64(w.max_t[cur]), rec, stream, variant));
+            const ShadeRaysParams shade{f64(w.dirs[cur]), rec.point, rec.normal, rec.material, rec.albedo, rec.lights, nullptr, f64(w.local[k]), f64(w.kr[k]), k, 0u};
+            HIP_TRY((hipError_t)launch_shade_rays(rt->scene, n, shade, stream, variant));
+            if (k == last) break;
+            RaySetArrays src{}, dst{};                                     // the next rays of the mirror hits become the rays of level k + 1; max_t is synthesised
+            src.p[kRaySetOrigins] = rec.next_origin; src.p[kRaySetDirs] = rec.next_dir; src.p[kRaySetMaterial] = rec.material;
+            dst.p[kRaySetOrigins] = f64(w.origins[nxt]); dst.p[kRaySetDirs] = f64(w.dirs[nxt]); dst.p[kRaySetMaxT] = f64(w.max_t[nxt]);
+            HIP_TRY((hipError_t)launch_compact(compact_params(rt, n, RRT_SELECT_MIRROR, nullptr, src, dst, u32(w.index[k]), base + w.scratch), nullptr, stream));
+        }
+        for (uint32_t k = levels; k-- > 0;) {                              // the unwind, innermost level first (raytracer.rs:85-101)
+            const uint32_t* reflected = nullptr;
+            if (k < last) {
+                HIP_TRY((hipError_t)launch_scatter(n, u32(w.index[k]), 4, u32(w.colour[(k + 1) & 1u]), u32(w.reflected), stream));
+                reflected = u32(w.reflected);
+            }
+            HIP_TRY((hipError_t)launch_mix_rays(MixRaysParams{u32(w.material[k]), f64(w.local[k]), f64(w.kr[k]), reflected, u32(w.colour[k & 1u]), n, rt->scene.n_mats}, stream));
+        }
+        return launch_mix_pixels(mix_pixels_params(width, height, b, u32(w.colour[0]), d_fb), stream);
+    });
+    record(rt, width, height, 4 * traced_pixels_in(b.r, width, height), variant);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1042,6 +1157,111 @@ int rrt_sort_rays_device(rrt_raytracer* rt, uint32_t n, uint32_t key_mode, const
         DeviceGuard guard(rt->device);
         HIP_TRY((hipError_t)launch_sort(sort_params(rt, n, key_mode, d_keys, s, d, d_index, d_keys_out, d_count, d_scratch), stream));
         return (int)RRT_OK;
+    });
+}
+
+uint32_t rrt_frame_ray_count(uint32_t width, uint32_t height, const rrt_region* region, uint32_t order) {
+    uint32_t n = 0;
+    (void)guarded([&]() -> int { n = (uint32_t)frame_batch(width, height, region, order).n; return RRT_OK; });
+    return n;
+}
+
+int rrt_frame_rays_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order, double* d_origins, double* d_dirs, double* d_max_t,
+                          void* stream) {
+    return guarded([&]() -> int {
+        const FrameBatch b = check_frame_batch(rt, width, height, region, order);
+        if (!d_origins && !d_dirs && !d_max_t) throw Error{RRT_ERR_INVALID_ARG, "no array requested: origins, dirs and max_t are all null"};
+        DeviceGuard guard(rt->device);
+        HIP_TRY((hipError_t)launch_frame_rays(frame_rays_params(rt, width, height, b, d_origins, d_dirs, d_max_t), stream));
+        return RRT_OK;
+    });
+}
+
+int rrt_frame_rays(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order, double* origins, double* dirs, double* max_t) {
+    return guarded([&]() -> int {
+        const FrameBatch b = check_frame_batch(rt, width, height, region, order);
+        if (!origins && !dirs && !max_t) throw Error{RRT_ERR_INVALID_ARG, "no array requested: origins, dirs and max_t are all null"};
+        DeviceGuard guard(rt->device);
+        HostPlane pl[] = {plane_down(origins, 24, b.n), plane_down(dirs, 24, b.n), plane_down(max_t, 8, b.n)};
+        with_call_planes(pl, [&] {
+            HIP_TRY((hipError_t)launch_frame_rays(frame_rays_params(rt, width, height, b, (double*)pl[0].dev, (double*)pl[1].dev, (double*)pl[2].dev), nullptr));
+        });
+        return RRT_OK;
+    });
+}
+
+int rrt_mix_rays_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_material, const double* d_local, const double* d_kr, const uint32_t* d_reflected, uint32_t* d_colour,
+                        void* stream) {
+    return guarded([&]() -> int {
+        check_mix_rays(rt, n, d_local, d_colour);
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        HIP_TRY((hipError_t)launch_mix_rays(MixRaysParams{d_material, d_local, d_kr, d_reflected, d_colour, n, rt->scene.n_mats}, stream));
+        return (int)RRT_OK;
+    });
+}
+
+int rrt_mix_rays(rrt_raytracer* rt, uint32_t n, const uint32_t* material, const double* local, const double* kr, const uint32_t* reflected, uint32_t* colour) {
+    return guarded([&]() -> int {
+        check_mix_rays(rt, n, local, colour);
+        if (n == 0) return (int)RRT_OK;
+        DeviceGuard guard(rt->device);
+        HostPlane pl[] = {plane_up(material, 4, n), plane_up(local, 24, n), plane_up(kr, 8, n), plane_up(reflected, 4, n), plane_down(colour, 4, n)};
+        with_call_planes(pl, [&] {
+            HIP_TRY((hipError_t)launch_mix_rays(MixRaysParams{(const uint32_t*)pl[0].dev, (const double*)pl[1].dev, (const double*)pl[2].dev, (const uint32_t*)pl[3].dev,
+                                                              (uint32_t*)pl[4].dev, n, rt->scene.n_mats}, nullptr));
+        });
+        return (int)RRT_OK;
+    });
+}
+
+int rrt_mix_pixels_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order, const uint32_t* d_colours, void* d_fb, void* stream) {
+    return guarded([&]() -> int {
+        const FrameBatch b = check_frame_batch(rt, width, height, region, order);
+        if (!d_colours || !d_fb) throw Error{RRT_ERR_INVALID_ARG, "null array: the pixels take colours and write a framebuffer"};
+        DeviceGuard guard(rt->device);
+        HIP_TRY((hipError_t)launch_mix_pixels(mix_pixels_params(width, height, b, d_colours, d_fb), stream));
+        return RRT_OK;
+    });
+}
+
+int rrt_mix_pixels(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order, const uint32_t* colours, uint32_t* out_fb) {
+    return guarded([&]() -> int {
+        const FrameBatch b = check_frame_batch(rt, width, height, region, order);
+        if (!colours || !out_fb) throw Error{RRT_ERR_INVALID_ARG, "null array: the pixels take colours and write a framebuffer"};
+        DeviceGuard guard(rt->device);
+        HostPlane pl[] = {plane_up(colours, 4, b.n), plane_down(out_fb, 4, (size_t)b.r.w * b.r.h)};
+        with_call_planes(pl, [&] { HIP_TRY((hipError_t)launch_mix_pixels(mix_pixels_params(width, height, b, (const uint32_t*)pl[0].dev, pl[1].dev), nullptr)); });
+        return RRT_OK;
+    });
+}
+
+size_t rrt_wavefront_work_bytes(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order) {
+    size_t bytes = 0;
+    (void)guarded([&]() -> int { bytes = wavefront_work(check_frame_batch(rt, width, height, region, order).n, wavefront_levels(rt)).bytes; return RRT_OK; });
+    return bytes;
+}
+
+int rrt_render_wavefront_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order, void* d_fb, void* d_work, size_t work_bytes,
+                                void* stream) {
+    return guarded([&]() -> int {
+        const FrameBatch b = check_wavefront(rt, width, height, region, order, d_fb);
+        if (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 255u) || work_bytes < wavefront_work(b.n, wavefront_levels(rt)).bytes)
+            throw Error{RRT_ERR_INVALID_ARG, "work memory null, not 256-byte aligned or too small: want rrt_wavefront_work_bytes(...) bytes of device memory"};
+        DeviceGuard guard(rt->device);
+        launch_wavefront(rt, width, height, b, d_fb, d_work, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_wavefront(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t order, uint32_t* out_fb) {
+    return guarded([&]() -> int {
+        const FrameBatch b = check_wavefront(rt, width, height, region, order, out_fb);
+        DeviceGuard guard(rt->device);
+        HostPlane pl[] = {HostPlane{rt, 1, wavefront_work(b.n, wavefront_levels(rt)).bytes, kCarve},   // (only carved: a host pointer that is not null says it is wanted)
+                          plane_down(out_fb, 4, (size_t)b.r.w * b.r.h)};
+        with_call_planes(pl, [&] { launch_wavefront(rt, width, height, b, pl[1].dev, pl[0].dev, nullptr); });
+        return RRT_OK;
     });
 }
 
