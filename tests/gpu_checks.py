@@ -70,13 +70,15 @@ def assert_walks_match(make_rt, frames, sizes, what, modes=ALL_MODES, rays=None,
 
 
 # ------------------------------------------------------------------ rays
-def row_dirs(w, h, r, xs):
-    """Directions of the 4 sub-sample rays (engine.rs:207-236) of the pixels `xs` (canvas columns) of canvas row r: [4, len(xs), 3]."""
+def row_dirs(w, h, r, xs, viewport=(1.0, 1.0, 1.0)):
+    """Directions of the 4 sub-sample rays (engine.rs:207-236) of the pixels `xs` (canvas columns) of canvas row r: [4, len(xs), 3].  viewport = (width,
+    height, depth) of engine.rs:113-119: the scales are one division each (engine.rs:189-190), a component is one product with its scale, z is the depth."""
+    vp_w, vp_h, vp_d = (float(v) for v in viewport)
     y = (h - h // 2) - r                                    # put_pixel: new_y = h - (y + h/2), engine.rs:147-150
     x = np.asarray(xs, np.float64) - (w // 2)
-    d = np.empty((4, len(x), 3)); d[..., 2] = 1.0
-    d[0, :, 0] = x * (1.0 / w); d[1, :, 0] = (x + 0.5) * (1.0 / w); d[2, :, 0] = d[0, :, 0]; d[3, :, 0] = d[1, :, 0]
-    d[0, :, 1] = y * (1.0 / h); d[1, :, 1] = d[0, :, 1]; d[2, :, 1] = (y + 0.5) * (1.0 / h); d[3, :, 1] = d[2, :, 1]
+    d = np.empty((4, len(x), 3)); d[..., 2] = vp_d
+    d[0, :, 0] = x * (vp_w / w); d[1, :, 0] = (x + 0.5) * (vp_w / w); d[2, :, 0] = d[0, :, 0]; d[3, :, 0] = d[1, :, 0]
+    d[0, :, 1] = y * (vp_h / h); d[1, :, 1] = d[0, :, 1]; d[2, :, 1] = (y + 0.5) * (vp_h / h); d[3, :, 1] = d[2, :, 1]
     return d
 
 
@@ -367,12 +369,12 @@ def chain_main_rays():
 MIN_PIXELS = 512                                   # compared with the oracle per pose, at least
 
 
-def pose_dirs(cam, w, h, rows, xs):
+def pose_dirs(cam, w, h, rows, xs, viewport=(1.0, 1.0, 1.0)):
     """[len(rows), 4, len(xs), 3]: the four sub-sample directions of the pixels (row, x) of a w x h frame in the pose `cam`, in the contract's order."""
     R, U, F = (np.asarray(cam[k], np.float64) for k in ("right", "up", "forward"))
     out = np.empty((len(rows), 4, len(xs), 3))
     for i, r in enumerate(rows):
-        abc = row_dirs(w, h, r, xs)                # (a, b, c) of engine.rs:207-236 with the default viewport: c = 1.0
+        abc = row_dirs(w, h, r, xs, viewport)      # (a, b, c) of engine.rs:207-236; with the default viewport c = 1.0
         a, b, c = abc[..., 0:1], abc[..., 1:2], abc[..., 2:3]
         out[i] = (R * a + U * b) + F * c
     return out
@@ -388,11 +390,11 @@ def traced_rows(h):
     return np.arange(h - 2 * (h // 2) + 1, h)     # rows the reference writes (engine.rs:146-158)
 
 
-def oracle_pixels(osc, cam, w, h, rows, xs, what):
+def oracle_pixels(osc, cam, w, h, rows, xs, what, viewport=(1.0, 1.0, 1.0)):
     """The oracle's pixels (rows, xs) of a w x h frame in the pose `cam`: get_ray_colour of the four sub-sample rays + Color::mix.  Asserts that there are at
     least MIN_PIXELS of them and that at least half have a sub-sample ray the oracle's intersector says hits."""
     eye = cam["eye"]
-    d = pose_dirs(cam, w, h, rows, xs)
+    d = pose_dirs(cam, w, h, rows, xs, viewport)
     flat = d.reshape(-1, 3)
     cols = np.fromiter(POOL.map(lambda v: osc.get_ray_colour(eye, v), flat), np.uint32, len(flat)).reshape(d.shape[:3])
     hits = np.fromiter(POOL.map(lambda v: osc.intersect(eye, v)[0], flat), bool, len(flat)).reshape(d.shape[:3])

@@ -46,9 +46,9 @@ def traced_cols(w):
     return np.arange(2 * (w // 2))
 
 
-def frame_dirs(cam, w, h):
+def frame_dirs(cam, w, h, viewport=(1.0, 1.0, 1.0)):
     """[len(rows)][len(cols)][4][3]: directions of the traced pixels' sub-sample rays, in the planes' index order."""
-    return pose_dirs(cam, w, h, traced_rows(h), traced_cols(w)).transpose(0, 2, 1, 3)
+    return pose_dirs(cam, w, h, traced_rows(h), traced_cols(w), viewport).transpose(0, 2, 1, 3)
 
 
 def traced_part(planes, w, h):

@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 
 from conftest import channels
-from gpu_checks import (FORCED_MODES, N_THREADS, ORIGIN, ROOT_BOX, assert_frame_close, assert_walks_match, checker, closed_box, flat_normals,
-                        in_noise_band, oracle_for, quad, row_dirs, sample_rays)
+from gpu_checks import FORCED_MODES, N_THREADS, ORIGIN, ROOT_BOX, assert_frame_close, assert_walks_match, in_noise_band, oracle_for, row_dirs, sample_rays
+from lighting_scenes import CORRIDOR_ORIGIN, SHADOW_ORIGIN, _corridor_lights, _corridor_scene, _shadow_box_scene
 
 pytestmark = pytest.mark.gpu
 SIZES = ((160, 120), (97, 61))
@@ -190,34 +190,6 @@ def test_invalid_lights_and_depth_are_rejected(rrt, teapot):
 
 
 # ------------------------------------------------------------------ hand-built scenes
-def _scene(rrt, groups, towards, materials, textures):
-    """groups: [(triangles, material id)]; uv from x/z (or x/y) so that textures vary across every surface."""
-    tris = [t for g, _ in groups for t in g]
-    mat = np.array([m for g, m in groups for _ in g], np.uint32)
-    pos = np.asarray(tris, np.float64)
-    uv = np.zeros_like(pos); uv[..., 0] = pos[..., 0] * 0.13 + pos[..., 2] * 0.07; uv[..., 1] = pos[..., 1] * 0.11 + pos[..., 2] * 0.05
-    nrm = flat_normals(tris, towards)
-    A = dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=materials, textures=textures, root=ROOT_BOX)
-    return rrt.SceneData.from_arrays(pos, uv, nrm, mat, materials, textures), A
-
-
-SHADOW_ORIGIN = (0.0, 3.0, -10.0)
-
-
-def _shadow_box_scene(rrt):
-    """Floor, back and left walls, a thin blocker 2 above the floor, and a closed box."""
-    mats = [dict(ka=(1, 1, 1), kd=(0.9, 0.9, 0.9), ks=(0.3, 0.3, 0.3), ns=20.0, kr=0.0, tex=0, bump=-1),
-            dict(ka=(0.8, 0.8, 0.8), kd=(0.7, 0.7, 0.7), ks=(0.5, 0.5, 0.5), ns=60.0, kr=0.0, tex=1, bump=-1),
-            dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=2, bump=-1)]
-    tex = [checker((200, 180, 150), (90, 110, 140)), checker((150, 220, 120), (60, 60, 60), 4), np.full((2, 2, 3), 230, np.uint8)]
-    groups = [(quad((-6, 0, -4), (6, 0, -4), (6, 0, 8), (-6, 0, 8)), 0),            # floor
-              (quad((-6, 0, 8), (6, 0, 8), (6, 7, 8), (-6, 7, 8)), 1),              # back wall
-              (quad((-6, 0, -4), (-6, 0, 8), (-6, 7, 8), (-6, 7, -4)), 1),          # left wall
-              (quad((-1.5, 2, 0), (1.5, 2, 0), (1.5, 2, 2.5), (-1.5, 2, 2.5)), 2),  # blocker, 2 above the floor
-              (closed_box((2, 0, 3), (4, 2, 5)), 1)]                                 # closed box
-    return _scene(rrt, groups, (0.0, 3.0, 1.0), mats, tex)
-
-
 @pytest.fixture(scope="module")
 def shadow_box(rrt):
     return _shadow_box_scene(rrt)
@@ -245,32 +217,9 @@ def test_shadow_box(rrt, ob, shadow_box, case):
     run_case(rrt, ob, sd, A, f"shadow_box/{case}", SHADOW_CASES[case](L, V), SHADOW_ORIGIN, (SHADOW_NEIGHBOURS[case](L, V), {}), 1000)
 
 
-CORRIDOR_ORIGIN = (0.0, 1.0, -8.0)
-
-
-def _corridor_scene(rrt):
-    """Two facing mirrors (z = 8 and z = -12) with different kr and textures, an oblique mirror on the right and a floor."""
-    mats = [dict(ka=(1, 1, 1), kd=(0.8, 0.8, 0.8), ks=(0.6, 0.6, 0.6), ns=40.0, kr=0.85, tex=0, bump=-1),
-            dict(ka=(1, 1, 1), kd=(0.8, 0.8, 0.8), ks=(0.6, 0.6, 0.6), ns=40.0, kr=0.75, tex=1, bump=-1),
-            dict(ka=(1, 1, 1), kd=(0.7, 0.7, 0.7), ks=(0.2, 0.2, 0.2), ns=10.0, kr=0.6, tex=2, bump=-1),
-            dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=3, bump=-1)]
-    tex = [checker((250, 40, 30), (200, 20, 60), 4), checker((20, 40, 250), (60, 20, 200), 4), checker((30, 240, 40), (90, 200, 20), 4),
-           checker((180, 180, 180), (90, 90, 90))]
-    groups = [(quad((-15, -10, 8), (15, -10, 8), (15, 10, 8), (-15, 10, 8)), 0),
-              (quad((-15, -10, -12), (15, -10, -12), (15, 10, -12), (-15, 10, -12)), 1),
-              (quad((4, -3, -6), (9, -3, 0), (9, 6, 0), (4, 6, -6)), 2),                # oblique, 50 degrees to the corridor's axis
-              (quad((-15, -3, -12), (15, -3, -12), (15, -3, 8), (-15, -3, 8)), 3)]       # floor
-    return _scene(rrt, groups, (0.0, 1.0, -2.0), mats, tex)
-
-
 @pytest.fixture(scope="module")
 def corridor(rrt):
     return _corridor_scene(rrt)
-
-
-def _corridor_lights(rrt):
-    L, V = rrt.Light, rrt.Vector3d
-    return [L.Ambient(0.3), L.Point(0.4, V(-5.0, 4.0, 4.0)), L.Point(0.4, V(5.0, 3.0, -9.0)), L.Directional(0.2, V(0.0, 1.0, -0.3))]
 
 
 @pytest.mark.parametrize("depth", range(9))

@@ -13,14 +13,13 @@ from gpu_checks import ALL_MODES, chain_rrt_lights, chain_scene
 from ray_surface_checks import WHITE
 from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, TARGET, assert_same_frame, mirror_room, soup_scene
 from surface_checks import bits, same, traced_pixels_in
-from wavefront_checks import (ARRAYS, DEAD_BOUND, FRAMES, ORDERS, REGIONS, ROWS, SENTINEL, TILES, WIDTHS, alive_entries, expected_pixels, expected_rays, mix_level,
-                              ray_count, region_of)
+from wavefront_checks import (ARRAYS, DEAD_BOUND, FRAMES, ORDERS, REGIONS, ROWS, SENTINEL, TILES, WIDTHS, alive_entries, assert_wavefront_is_render, expected_pixels,
+                              expected_rays, host, mix_level, ray_count, region_of)
 
 pytestmark = pytest.mark.gpu
 
 MOVED_EYE = (9.0, 2.0, 1.0)
 RW, RH = 32, 24                                                  # the mirror room's and the soup's frame
-VARIANT = dict(lane=0, bundle=1, ray=2)
 RECORDS = ("hit", "t", "u", "v", "tri", "albedo", "point", "normal", "material", "lights")   # what rrt_render_surface gives with its visibility planes
 
 
@@ -39,10 +38,6 @@ def device(torch, a):
     """A host array as a flat device tensor of the same bits (uint32 travels as int32)"""
     a = np.ascontiguousarray(a)
     return torch.tensor(a.view(np.int32) if a.dtype == np.uint32 else a, device="cuda").reshape(-1)
-
-
-def host(t, dtype, shape):
-    return t.cpu().numpy().view(dtype).reshape(shape)
 
 
 @pytest.fixture(scope="module")
@@ -228,40 +223,6 @@ def test_the_pixels(rrt, teapot, w, h):
 
 
 # ------------------------------------------------------------------ 4: the frame by generations is rrt_render's frame
-def assert_wavefront_is_render(rrt, torch, rt, w, h, region, what, forced=None):
-    """render_wavefront of the whole frame (host form) and of `region` (device form: a stream of the test's own, exactly wavefront_work_bytes of work memory
-    prefilled with 0xA5) in both orders is rt's own frame; rrt_last_stats as rrt.h says; afterwards render gives the same frame from the same kept variant."""
-    rt.render(w, h)
-    want = rt.render(w, h)                                         # (the second frame of a size: an unforced raytracer has measured now)
-    kept = rt.last_stats()["filter_variant"]
-    assert forced is None or kept == VARIANT[forced]
-    stream = torch.cuda.Stream()
-    x0, y0, rw, rh = region
-    for order in ORDERS:
-        got = rt.render_wavefront(w, h, order=order)
-        assert_same_frame(got, want, f"{what}, order {order}: render_wavefront vs render")
-        s = rt.last_stats()
-        assert (s["width"], s["height"], s["rays_primary"], s["filter_variant"]) == (w, h, 4 * traced_pixels_in((0, 0, w, h), w, h), kept) and s["kernel_ms"] > 0, s
-        need = rt.wavefront_work_bytes(w, h, region, order)
-        n = rrt.frame_ray_count(w, h, region, order)
-        depth = rt.max_reflection_depth
-        assert 0 < need <= n * (229 + 40 * (depth + 1)) + 16384, f"{what}: {need} bytes of work memory for {n} entries at depth {depth}"
-        with torch.cuda.stream(stream):
-            work = torch.full((need,), 0xA5, dtype=torch.uint8, device="cuda")
-            fb = torch.full((rw * rh,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-            assert work.data_ptr() % 256 == 0
-            rt.render_wavefront_into(fb, work, w, h, region=region, order=order, stream=stream.cuda_stream)
-        stream.synchronize()
-        assert_same_frame(host(fb, np.uint32, (rh, rw)), want[y0:y0 + rh, x0:x0 + rw], f"{what}, order {order}, region {region}: render_wavefront_into vs render")
-        s = rt.last_stats()
-        assert (s["width"], s["height"], s["rays_primary"], s["filter_variant"]) == (w, h, 4 * traced_pixels_in(region, w, h), kept) and s["kernel_ms"] > 0, s
-        with pytest.raises(rrt.RrtError):                          # one byte less is refused, and the framebuffer stays
-            rt.render_wavefront_into(fb, work[:need - 1], w, h, region=region, order=order, stream=stream.cuda_stream)
-    assert_same_frame(rt.render(w, h), want, f"{what}: render after render_wavefront")
-    assert rt.last_stats()["filter_variant"] == kept, f"{what}: render runs another variant after render_wavefront"
-    return want
-
-
 def tracer(rrt, sd, lights, mode, depth=5, **kw):
     rt = rrt.RayTracer(sd, lights, box_filter=mode, max_reflection_depth=depth, **kw)
     rt.max_reflection_depth = depth

@@ -5,11 +5,13 @@ surface_checks.traced_cols, the restatements the other tests use -- one level of
 Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  It holds no fixtures.
 """
 import numpy as np
+import pytest
 
 from gpu_checks import mix4, pose_dirs, traced_rows
 from ray_surface_checks import WHITE, clamp_u8, pack
+from shade_checks import assert_same_frame
 from shade_rays_checks import mixed
-from surface_checks import traced_cols
+from surface_checks import traced_cols, traced_pixels_in
 
 ROWS, TILES = 0, 1                                               # RRT_ORDER_ROWS, RRT_ORDER_TILES
 ORDERS = (ROWS, TILES)
@@ -17,6 +19,7 @@ ARRAYS = ("origins", "dirs", "max_t")                             # what rrt_fra
 WIDTHS = dict(origins=3, dirs=3, max_t=1)
 DEAD_BOUND = 0x7FF8000000000000                                   # max_t of a dead entry: compaction's dead value
 SENTINEL = -12345.5
+VARIANT = dict(lane=0, bundle=1, ray=2)                           # filter_variant of rrt_last_stats per forced walk
 
 # the frames of the GPU tests and, per frame, the whole frame and two regions cut off the 4x4 tile boundaries; the second has a tile straddling each of its edges
 FRAMES = ((64, 48), (97, 61), (2, 2), (5, 3))
@@ -73,14 +76,14 @@ def alive_entries(w, h, region, order):
     return inside & traced_mask(w, h)[np.minimum(py, h - 1), np.minimum(px, w - 1)]
 
 
-def expected_rays(cam, w, h, region, order):
+def expected_rays(cam, w, h, region, order, viewport=(1.0, 1.0, 1.0)):
     """The batch rrt_frame_rays writes: origins [n][3], dirs [n][3], max_t [n]; a dead entry is zeros and the NaN 0x7FF8000000000000"""
     px, py, sub, _ = entries(w, h, region, order)
     alive = alive_entries(w, h, region, order)
     full = np.zeros((h, w, 4, 3))
     rows, cols = traced_rows(h), traced_cols(w)
     if len(rows) and len(cols):
-        full[np.ix_(rows, cols)] = pose_dirs(cam, w, h, rows, cols).transpose(0, 2, 1, 3)
+        full[np.ix_(rows, cols)] = pose_dirs(cam, w, h, rows, cols, viewport).transpose(0, 2, 1, 3)
     n = len(px)
     dirs, origins = np.zeros((n, 3)), np.zeros((n, 3))
     dirs[alive] = full[py[alive], px[alive], sub[alive]]
@@ -113,3 +116,43 @@ def expected_pixels(colours, w, h, region, order):
     fb = mix4(planes.reshape(-1, 4)).reshape(rh, rw)
     fb[~traced_mask(w, h)[y0:y0 + rh, x0:x0 + rw]] = 0
     return fb
+
+
+def host(t, dtype, shape):
+    """A device tensor as a host array of `dtype` and `shape` with the same bits"""
+    return t.cpu().numpy().view(dtype).reshape(shape)
+
+
+def assert_wavefront_is_render(rrt, torch, rt, w, h, region, what, forced=None):
+    """render_wavefront of the whole frame (host form) and of `region` (device form: a stream of the test's own, exactly wavefront_work_bytes of work memory
+    prefilled with 0xA5) in both orders is rt's own frame; rrt_last_stats as rrt.h says; afterwards render gives the same frame from the same kept variant.
+    rt.max_reflection_depth: the depth rt was created with (the caller sets the attribute)."""
+    rt.render(w, h)
+    want = rt.render(w, h)                                         # (the second frame of a size: an unforced raytracer has measured now)
+    kept = rt.last_stats()["filter_variant"]
+    assert forced is None or kept == VARIANT[forced], f"{what}: variant {kept} runs, {forced} = {VARIANT[forced]} was forced"
+    stream = torch.cuda.Stream()
+    x0, y0, rw, rh = region
+    for order in ORDERS:
+        got = rt.render_wavefront(w, h, order=order)
+        assert_same_frame(got, want, f"{what}, order {order}: render_wavefront vs render")
+        s = rt.last_stats()
+        assert (s["width"], s["height"], s["rays_primary"], s["filter_variant"]) == (w, h, 4 * traced_pixels_in((0, 0, w, h), w, h), kept) and s["kernel_ms"] > 0, s
+        need = rt.wavefront_work_bytes(w, h, region, order)
+        n = rrt.frame_ray_count(w, h, region, order)
+        depth = rt.max_reflection_depth
+        assert 0 < need <= n * (229 + 40 * (depth + 1)) + 16384, f"{what}: {need} bytes of work memory for {n} entries at depth {depth}"
+        with torch.cuda.stream(stream):
+            work = torch.full((need,), 0xA5, dtype=torch.uint8, device="cuda")
+            fb = torch.full((rw * rh,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+            assert work.data_ptr() % 256 == 0, f"{what}: the work memory lies at {work.data_ptr():#x}"
+            rt.render_wavefront_into(fb, work, w, h, region=region, order=order, stream=stream.cuda_stream)
+        stream.synchronize()
+        assert_same_frame(host(fb, np.uint32, (rh, rw)), want[y0:y0 + rh, x0:x0 + rw], f"{what}, order {order}, region {region}: render_wavefront_into vs render")
+        s = rt.last_stats()
+        assert (s["width"], s["height"], s["rays_primary"], s["filter_variant"]) == (w, h, 4 * traced_pixels_in(region, w, h), kept) and s["kernel_ms"] > 0, s
+        with pytest.raises(rrt.RrtError):                          # one byte less is refused, and the framebuffer stays
+            rt.render_wavefront_into(fb, work[:need - 1], w, h, region=region, order=order, stream=stream.cuda_stream)
+    assert_same_frame(rt.render(w, h), want, f"{what}: render after render_wavefront")
+    assert rt.last_stats()["filter_variant"] == kept, f"{what}: render runs another variant after render_wavefront"
+    return want
