@@ -774,15 +774,19 @@ int rrt_sort_rays(rrt_raytracer *rt, uint32_t n, uint32_t key_mode, const uint32
  *      compaction of the mirror hits' next rays into the rays of level k + 1 (rrt_compact_rays_device, RRT_SELECT_MIRROR, max_t synthesised), its index kept;
  *   3. back up, for k = max .. 0: the colours of level k + 1 scattered through the index of level k (rrt_scatter_rays_device), then rrt_mix_rays_device;
  *   4. rrt_mix_pixels_device.
- * Everything is enqueued on `stream`: no allocation, no copy to the host, no read-back of a count, no synchronisation.  Every level runs at the same
- * n = rrt_frame_ray_count(...): the dead tail of a compacted level walks nothing.  The launches are those of the calls named above -- no kernel of its own.
+ * Everything is enqueued on `stream`: no allocation, no copy to the host, no read-back of a count, no synchronisation.  Every launch has the grid of
+ * n = rrt_frame_ray_count(...), because the host never learns a count; but from level 1 on the stages are the COUNTED forms below, bound by the count the level
+ * above's compaction left in the work memory: surface, shade and compaction of level k by the count of level k - 1, the scatter of level k by the count of level k,
+ * the mix of level k by the count of level k - 1.  The dead tail of a compacted level is neither read nor written, its blocks leave at once, and a level whose
+ * predecessor left nothing alive costs its launches and nothing else.  Level 0, its mix and the pixels run uncounted.  The launches are those of the calls named
+ * above and of their counted forms -- no kernel of its own.
  * Traversal variant: the rule of rrt_intersect_rays_device -- the forced one, else the one kept for per-ray calls, else the frame variant; nothing is measured, and the
  * call does not count as a frame of that size for the frame variant's measurement (RRT_FLAG_LANE_FILTER above).
  * Work memory: d_work = device memory of at least rrt_wavefront_work_bytes(rt, width, height, region, order) bytes, 256-byte aligned, whose contents before and after
  * mean nothing.  The size is 0 for arguments the call refuses, never smaller for a larger region, and at most
  *   n * (229 + 40 * (max_reflection_depth + 1)) + 16384   bytes, n = rrt_frame_ray_count(...)
  * -- per entry two generations of rays (2 x 56), one level's record arrays (104), two levels' colours and the scattered ones (12), the compaction's scratch, and per
- * level what the way back up needs: local, kr, material and index (40).  About 1.2 GB for a 1920 x 1080 frame at the default depth of 5.
+ * level what the way back up needs: local, kr, material and index (40); one uint32 per level for the counts.  About 1.2 GB for a 1920 x 1080 frame at the default depth of 5.
  * rrt_last_stats afterwards: kernel_ms = the time between two events around the whole sequence, filter_variant = the variant used, width / height = the frame size,
  * rays_primary = 4 * the traced pixels inside the region.
  * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer as it was: the refusals of rrt_frame_rays for rt, the frame size, the region and the order; a
@@ -808,6 +812,49 @@ size_t rrt_wavefront_work_bytes(const rrt_raytracer *rt, uint32_t width, uint32_
 int rrt_render_wavefront_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order,
                                 void *d_fb, void *d_work, size_t work_bytes, void *stream);
 int rrt_render_wavefront(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order, uint32_t *out_fb);
+
+/* COUNTED DEVICE FORMS.  A batch whose length was decided on the GPU -- the `count` of a compaction, the survivors of a kernel of the caller's -- need not be padded
+ * with dead entries that every later stage pays for, nor read back (which synchronises).  Each of the nine calls below is the `_device` call of the same name with
+ * ONE more argument, `const uint32_t *d_count`, directly after n: a launch bound that lives in device memory.
+ * CONTRACT, the same for all nine:
+ *   - d_count points to one uint32 in device memory of rt's device, 4-byte aligned.  The host never reads it; the kernels read it when they run, in stream order.  It
+ *     may therefore be the `count` output of a compaction enqueued earlier on the same stream, with nothing in between.  It is only ever read.
+ *   - Let m = min(n, *d_count): a *d_count above n is n.  Entries [0, m) are processed exactly as the uncounted call with n = m processes them, byte for byte.
+ *     Entries [m, n) of every input and of every output are neither read nor written.  m == 0 writes nothing.
+ *   - The arrays still hold n entries and the grid is still sized by n, because the host does not know m.  A block whose first entry is at or beyond m ends after one
+ *     scalar load and one compare, before it touches LDS, a barrier or memory.  No atomics, no block that waits on another: the same bits on every run.
+ *   - d_count == NULL: the call IS the uncounted one, through the same kernels.
+ *   - Refusals are those of the uncounted form, made at the same point: before any GPU work, and for compaction, scatter and mix before the handle is looked at.
+ *     n == 0 is RRT_OK with nothing enqueued.
+ *   - rrt_last_stats after a counted ray call (intersect, get_ray_colours, occluded, surface, shade, ambient): as after the uncounted one, with
+ *     width = rays_primary = n -- the host does not know m.  Counted compaction, scatter and mix leave it alone, as the uncounted ones do.
+ * rrt_compact_rays_counted_device, in addition: the selection is evaluated over [0, m) only; *d_count_out, d_index and the arrays of d_dst are those of the uncounted
+ * call with n = m -- survivors in [0, count_out), the dead fill in [count_out, m), nothing in [m, n); with m == 0 the output count is 0 and nothing else is written.
+ * scratch_bytes is still checked against rrt_compact_scratch_bytes(n), and all of that scratch may be written.  d_count and d_count_out must not be the same word:
+ * equal non-NULL pointers are refused with RRT_ERR_INVALID_ARG (neighbouring words of one allocation are fine).
+ * rrt_scatter_rays_counted_device: j runs over [0, m); d_index[j] for j >= m is not read.  An index is a position in the caller's arrays of n elements, so the rule
+ * for one that is skipped stays "at or above n" (NOT m): the index of a counted compaction names source positions up to its own bound, which may exceed its count.
+ * rrt_mix_rays_counted_device: entries [0, m).
+ * NOT covered: rrt_sort_rays_device (a counted sort needs a rule for the tail that a pure permutation has not got), the region calls (their size is the host's), and
+ * rrt_tune_rays_device (it measures, and synchronises to do so).  There are no host forms: a host caller knows its n. */
+int rrt_intersect_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const double *d_origins, const double *d_dirs, const double *d_max_t,
+                                      uint8_t *d_hit, double *d_t, double *d_u, double *d_v, uint32_t *d_tri, void *stream);
+int rrt_get_ray_colours_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const double *d_origins, const double *d_dirs, uint32_t *d_colours,
+                                       void *stream);
+int rrt_occluded_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const double *d_origins, const double *d_dirs, const double *d_max_t,
+                                     uint8_t *d_occluded, void *stream);
+int rrt_surface_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const double *d_origins, const double *d_dirs, const double *d_max_t,
+                                    const rrt_ray_surface *d_out, void *stream);
+int rrt_shade_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const double *d_dirs, const rrt_ray_surface *d_rec, uint32_t depth,
+                                  const rrt_ray_shade *d_out, void *stream);
+int rrt_ambient_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const rrt_ray_surface *d_rec, const double *d_rot,
+                                    const rrt_ambient_samples *samples, const rrt_ray_ambient *d_out, void *stream);
+int rrt_compact_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, uint32_t select, const uint8_t *d_flag, const rrt_ray_set *d_src,
+                                    const rrt_ray_set *d_dst, uint32_t *d_index, uint32_t *d_count_out, void *d_scratch, size_t scratch_bytes, void *stream);
+int rrt_scatter_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const uint32_t *d_index, uint32_t elem_bytes, const void *d_src,
+                                    void *d_dst, void *stream);
+int rrt_mix_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const uint32_t *d_material, const double *d_local, const double *d_kr,
+                                const uint32_t *d_reflected, uint32_t *d_colour, void *stream);
 
 /* The octree of a raytracer whose set-up ran on the GPU (the default), read back from its device: same layout as rrt_model_get_octree; info (may be
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */

@@ -251,6 +251,16 @@ SYMBOLS = {
     "rrt_wavefront_work_bytes": (C.c_size_t, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32]),
     "rrt_render_wavefront_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32, _P, _P, C.c_size_t, _P]),
     "rrt_render_wavefront": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.c_uint32, _u32p]),
+    # the counted device forms (rrt.h: COUNTED DEVICE FORMS): the device form with the bound, a device pointer, directly after n
+    "rrt_intersect_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rrt_get_ray_colours_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "rrt_occluded_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "rrt_surface_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.POINTER(CRaySurface), _P]),
+    "rrt_shade_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, C.POINTER(CRaySurface), C.c_uint32, C.POINTER(CRayShade), _P]),
+    "rrt_ambient_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(CRaySurface), _P, C.POINTER(CAmbientSamples), C.POINTER(CRayAmbient), _P]),
+    "rrt_compact_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.POINTER(CRaySet), C.POINTER(CRaySet), _P, _P, _P, C.c_size_t, _P]),
+    "rrt_scatter_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P]),
+    "rrt_mix_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "rrt_raytracer_get_octree": (C.c_int, [_P, C.POINTER(CModelInfo), _dp, _u32p, _u32p, _u32p, _u32p]),
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
@@ -433,6 +443,16 @@ def _device_tensor(t, n: int, itemsize: int, name: str):
     """What every _into form asserts of a tensor before the library sees its pointer (a numpy array fails here, without a GPU)."""
     assert getattr(t, "is_cuda", False), f"{name}: not a device tensor"
     assert t.is_contiguous() and t.element_size() == itemsize and t.numel() == n, f"{name}: want {n} contiguous elements of {itemsize} bytes"
+
+
+def _bounded(symbol: str, bound_t, handle, n: int) -> tuple:
+    """The head of a device-form call -- symbol, handle, n -- and with a bound (rrt.h: COUNTED DEVICE FORMS; a device tensor of one 4-byte element) the counted symbol
+    and the bound's pointer behind n.  Without one the call is the uncounted one, untouched."""
+    if bound_t is None:
+        return symbol, handle, n
+    _device_tensor(bound_t, 1, 4, "bound")
+    assert symbol.endswith("_device"), symbol
+    return symbol[:-len("_device")] + "_counted_device", handle, n, _ptr(bound_t)
 
 
 def _batch_size(t, per: int, name: str) -> int:
@@ -871,27 +891,29 @@ class RayTracer(_Handle):
         return out.astype(bool)
 
     # device-resident ray batches (rrt.h: rrt_intersect_rays_device): origins_t / dirs_t are float64 device tensors of 3 n elements, max_t_t of n; enqueued, not synchronised
-    def occluded_into(self, origins_t, dirs_t, out_t, max_t_t=None, stream: Optional[int] = None):
-        """rrt_occluded_rays_device: out_t = device tensor of n one-byte elements, 1 = occluded."""
+    # bound_t, in all nine _into forms that have it: None, or a device tensor of one 4-byte element -- the launch bound of the counted form (rrt.h: COUNTED DEVICE
+    # FORMS), read on the device in stream order: only the first min(n, bound) entries of every array are read and written.
+    def occluded_into(self, origins_t, dirs_t, out_t, max_t_t=None, stream: Optional[int] = None, bound_t=None):
+        """rrt_occluded_rays_device: out_t = device tensor of n one-byte elements, 1 = occluded.  bound_t: rrt_occluded_rays_counted_device."""
         n = _ray_batch(origins_t, dirs_t, max_t_t)
         _device_tensor(out_t, n, 1, "out")
-        _call("rrt_occluded_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), _ptr(out_t), _P(_stream(stream)))
+        _call(*_bounded("rrt_occluded_rays_device", bound_t, self._h, n), _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), _ptr(out_t), _P(_stream(stream)))
 
-    def intersect_rays_into(self, origins_t, dirs_t, out: dict, max_t_t=None, stream: Optional[int] = None):
+    def intersect_rays_into(self, origins_t, dirs_t, out: dict, max_t_t=None, stream: Optional[int] = None, bound_t=None):
         """rrt_intersect_rays_device: out = {name: device tensor of n elements} for any subset of hit (1 byte), t, u, v (float64), tri (4 bytes); the others are not
-        computed."""
+        computed.  bound_t: rrt_intersect_rays_counted_device."""
         n = _ray_batch(origins_t, dirs_t, max_t_t)
         assert set(out) <= set(PLANES[:5]), sorted(out)
         for name, t in out.items():
             _device_tensor(t, n, np.dtype(PLANE_DTYPES[name]).itemsize, name)
-        _call("rrt_intersect_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), *(_ptr(out.get(name)) for name in PLANES[:5]),
+        _call(*_bounded("rrt_intersect_rays_device", bound_t, self._h, n), _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), *(_ptr(out.get(name)) for name in PLANES[:5]),
               _P(_stream(stream)))
 
-    def get_ray_colours_into(self, origins_t, dirs_t, colours_t, stream: Optional[int] = None):
-        """rrt_get_ray_colours_device: colours_t = device tensor of n four-byte elements, 0x00RRGGBB."""
+    def get_ray_colours_into(self, origins_t, dirs_t, colours_t, stream: Optional[int] = None, bound_t=None):
+        """rrt_get_ray_colours_device: colours_t = device tensor of n four-byte elements, 0x00RRGGBB.  bound_t: rrt_get_ray_colours_counted_device."""
         n = _ray_batch(origins_t, dirs_t, None)
         _device_tensor(colours_t, n, 4, "colours")
-        _call("rrt_get_ray_colours_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(colours_t), _P(_stream(stream)))
+        _call(*_bounded("rrt_get_ray_colours_device", bound_t, self._h, n), _ptr(origins_t), _ptr(dirs_t), _ptr(colours_t), _P(_stream(stream)))
 
     def tune_rays(self, origins_t, dirs_t, max_t_t=None) -> int:
         """rrt_tune_rays_device (blocking): measures the three traversal variants on this device-resident batch and keeps the fastest for later per-ray calls;
@@ -914,14 +936,14 @@ class RayTracer(_Handle):
         _call("rrt_surface_rays", self._h, n, _d(o), _d(d), _d(mt), _plane_struct(CRaySurface, out))
         return out
 
-    def surface_rays_into(self, origins_t, dirs_t, out: dict, max_t_t=None, stream: Optional[int] = None):
+    def surface_rays_into(self, origins_t, dirs_t, out: dict, max_t_t=None, stream: Optional[int] = None, bound_t=None):
         """rrt_surface_rays_device: out = {name: contiguous device tensor} for any subset of RAY_SURFACE_PLANES -- n elements of the array's item size, 3 n for
-        point / normal / next_origin / next_dir; the others are not computed.  Enqueued, not synchronised."""
+        point / normal / next_origin / next_dir; the others are not computed.  Enqueued, not synchronised.  bound_t: rrt_surface_rays_counted_device."""
         n = _ray_batch(origins_t, dirs_t, max_t_t)
         for name, t in out.items():
             dtype, width = _ray_plane(name)
             _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
-        _call("rrt_surface_rays_device", self._h, n, _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), _plane_struct(CRaySurface, out), _P(_stream(stream)))
+        _call(*_bounded("rrt_surface_rays_device", bound_t, self._h, n), _ptr(origins_t), _ptr(dirs_t), _ptr(max_t_t), _plane_struct(CRaySurface, out), _P(_stream(stream)))
 
     # shading of arbitrary rays from kept records (rrt.h: rrt_shade_rays): what shade() does for a frame's planes, for the arrays surface_rays wrote
     def shade_rays(self, dirs, planes: dict, depth: int = 0, outputs=("colour",)) -> dict:
@@ -938,10 +960,10 @@ class RayTracer(_Handle):
         _call("rrt_shade_rays", self._h, n, _d(d), _plane_struct(CRaySurface, rec), int(depth), _plane_struct(CRayShade, out))
         return out
 
-    def shade_rays_into(self, out: dict, dirs_t, planes: dict, depth: int = 0, stream: Optional[int] = None):
+    def shade_rays_into(self, out: dict, dirs_t, planes: dict, depth: int = 0, stream: Optional[int] = None, bound_t=None):
         """rrt_shade_rays_device: out = {name: contiguous device tensor} for any subset of RAY_SHADE_OUTPUTS (n four-byte elements, 3 n and n float64; the others
         are not computed -- without colour no reflection ray is walked); dirs_t float64 of 3 n elements; planes = {name: device tensor} as surface_rays_into
-        filled them (albedo, point, normal, material, and lights or not).  Enqueued, not synchronised."""
+        filled them (albedo, point, normal, material, and lights or not).  Enqueued, not synchronised.  bound_t: rrt_shade_rays_counted_device."""
         n = _batch_size(dirs_t, 3, "dirs")
         _device_tensor(dirs_t, 3 * n, 8, "dirs")
         rec = _ray_records("shade_rays_into", planes)
@@ -950,7 +972,7 @@ class RayTracer(_Handle):
         for name, t in out.items():
             dtype, width = _ray_plane(name, CRayShade, "shade_rays_into")
             _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
-        _call("rrt_shade_rays_device", self._h, n, _ptr(dirs_t), _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), int(depth),
+        _call(*_bounded("rrt_shade_rays_device", bound_t, self._h, n), _ptr(dirs_t), _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), int(depth),
               _plane_struct(CRayShade, out), _P(_stream(stream)))
 
     # ambient occlusion for ray records (rrt.h: rrt_ambient_rays): what ambient() does for a frame's planes, for the arrays surface_rays wrote, with a rotation per record
@@ -971,10 +993,10 @@ class RayTracer(_Handle):
         _call("rrt_ambient_rays", self._h, n, _plane_struct(CRaySurface, rec), _d(r), C.byref(samples), _plane_struct(CRayAmbient, out))
         return out
 
-    def ambient_rays_into(self, out: dict, planes: dict, dirs, max_t: float, rot_t=None, stream: Optional[int] = None):
+    def ambient_rays_into(self, out: dict, planes: dict, dirs, max_t: float, rot_t=None, stream: Optional[int] = None, bound_t=None):
         """rrt_ambient_rays_device: out = {name: contiguous device tensor of n four-byte elements} for any subset of RAY_AMBIENT_OUTPUTS; planes = {name: device
         tensor} as surface_rays_into filled them (point, normal, material); rot_t None or a float64 device tensor of 2 n elements.  The sample table `dirs` is a
-        host array.  Enqueued, not synchronised."""
+        host array.  Enqueued, not synchronised.  bound_t: rrt_ambient_rays_counted_device."""
         rec = _ray_records("ambient_rays_into", planes, RAY_AMBIENT_INPUTS)
         assert "material" in rec, "ambient_rays_into: the records have no material array"
         n = _batch_size(rec["material"][0], 1, "material")
@@ -986,7 +1008,7 @@ class RayTracer(_Handle):
             dtype, width = _ray_plane(name, CRayAmbient, "ambient_rays_into")
             _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
         _d_keep, samples = _ambient_samples(dirs, max_t)
-        _call("rrt_ambient_rays_device", self._h, n, _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), _ptr(rot_t), C.byref(samples),
+        _call(*_bounded("rrt_ambient_rays_device", bound_t, self._h, n), _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), _ptr(rot_t), C.byref(samples),
               _plane_struct(CRayAmbient, out), _P(_stream(stream)))
 
     # compaction of ray batches and records, and its inverse (rrt.h: rrt_compact_rays, rrt_scatter_rays): the survivors to the front of a batch that keeps its length
@@ -1014,11 +1036,12 @@ class RayTracer(_Handle):
         _call("rrt_compact_rays", self._h, n, sel, _u8(f), _ray_set(src), _ray_set(out), _u32(index), C.byref(count))
         return dict(out, index=index, count=int(count.value))
 
-    def compact_rays_into(self, out: dict, src: dict, select: str, index_t, count_t, scratch_t, flag_t=None, stream: Optional[int] = None):
+    def compact_rays_into(self, out: dict, src: dict, select: str, index_t, count_t, scratch_t, flag_t=None, stream: Optional[int] = None, bound_t=None):
         """rrt_compact_rays_device: out / src = {name: contiguous device tensor} with names from RAY_SET_ARRAYS -- n elements of the array's item size, 3 n for the
         vectors, 2 n for rot; every array of out but max_t needs its array of src.  index_t: n four-byte elements or None; count_t: one four-byte element or None;
         scratch_t: a device tensor of at least compact_scratch_bytes(n) bytes (None for n == 0); flag_t: n bytes, for select "flag".  n is the length of flag_t
-        for "flag", of src["material"] otherwise.  Enqueued, not synchronised; last_stats stays as it was."""
+        for "flag", of src["material"] otherwise.  Enqueued, not synchronised; last_stats stays as it was.  bound_t: rrt_compact_rays_counted_device (count_t is the
+        OUTPUT count; the two must not be the same word)."""
         sel = _select(select, "compact_rays_into")
         lead = flag_t if sel == 2 else src.get("material")
         assert lead is not None, f"compact_rays_into: select {select!r} needs {'a flag tensor' if sel == 2 else 'a material tensor'}"
@@ -1037,7 +1060,7 @@ class RayTracer(_Handle):
         if scratch_t is not None:
             assert getattr(scratch_t, "is_cuda", False) and scratch_t.is_contiguous(), "scratch: not a contiguous device tensor"
             scratch_bytes = scratch_t.numel() * scratch_t.element_size()
-        _call("rrt_compact_rays_device", self._h, n, sel, _ptr(flag_t), _ray_set(src), _ray_set(out), _ptr(index_t), _ptr(count_t), _ptr(scratch_t),
+        _call(*_bounded("rrt_compact_rays_device", bound_t, self._h, n), sel, _ptr(flag_t), _ray_set(src), _ray_set(out), _ptr(index_t), _ptr(count_t), _ptr(scratch_t),
               scratch_bytes, _P(_stream(stream)))
 
     def scatter_rays(self, index, src, dst) -> np.ndarray:
@@ -1051,9 +1074,9 @@ class RayTracer(_Handle):
         _call("rrt_scatter_rays", self._h, n, _u32(idx), s.nbytes // n if n else s.itemsize, _P(s.ctypes.data), _P(dst.ctypes.data))
         return dst
 
-    def scatter_rays_into(self, index_t, src_t, dst_t, stream: Optional[int] = None):
+    def scatter_rays_into(self, index_t, src_t, dst_t, stream: Optional[int] = None, bound_t=None):
         """rrt_scatter_rays_device: index_t n four-byte elements, src_t and dst_t contiguous device tensors of n elements of 1, 4, 8, 16 or 24 bytes (k n elements
-        of a k-wide array).  Enqueued, not synchronised."""
+        of a k-wide array).  Enqueued, not synchronised.  bound_t: rrt_scatter_rays_counted_device."""
         n = _batch_size(index_t, 1, "index")
         _device_tensor(index_t, n, 4, "index")
         assert getattr(src_t, "is_cuda", False), "src: not a device tensor"
@@ -1061,7 +1084,7 @@ class RayTracer(_Handle):
         assert rem == 0 and per >= 1, f"src: {src_t.numel()} elements for {n} entries"
         _device_tensor(src_t, per * n, src_t.element_size(), "src")
         _device_tensor(dst_t, per * n, src_t.element_size(), "dst")
-        _call("rrt_scatter_rays_device", self._h, n, _ptr(index_t), per * src_t.element_size(), _ptr(src_t), _ptr(dst_t), _P(_stream(stream)))
+        _call(*_bounded("rrt_scatter_rays_device", bound_t, self._h, n), _ptr(index_t), per * src_t.element_size(), _ptr(src_t), _ptr(dst_t), _P(_stream(stream)))
 
     compact_scratch_bytes = staticmethod(compact_scratch_bytes)
 
@@ -1153,15 +1176,15 @@ class RayTracer(_Handle):
         _call("rrt_mix_rays", self._h, n, _u32(m), _d(l), _d(k), _u32(r), _u32(colour))
         return colour
 
-    def mix_rays_into(self, colour_t, local_t, kr_t=None, reflected_t=None, material_t=None, stream: Optional[int] = None):
+    def mix_rays_into(self, colour_t, local_t, kr_t=None, reflected_t=None, material_t=None, stream: Optional[int] = None, bound_t=None):
         """rrt_mix_rays_device: colour_t n four-byte elements; local_t float64 of 3 n elements; kr_t float64 of n, reflected_t and material_t n four-byte elements,
-        each or None.  Enqueued, not synchronised; last_stats stays as it was."""
+        each or None.  Enqueued, not synchronised; last_stats stays as it was.  bound_t: rrt_mix_rays_counted_device."""
         n = _batch_size(local_t, 3, "local")
         _device_tensor(local_t, 3 * n, 8, "local"); _device_tensor(colour_t, n, 4, "colour")
         for name, t, size in (("kr", kr_t, 8), ("reflected", reflected_t, 4), ("material", material_t, 4)):
             if t is not None:
                 _device_tensor(t, n, size, name)
-        _call("rrt_mix_rays_device", self._h, n, _ptr(material_t), _ptr(local_t), _ptr(kr_t), _ptr(reflected_t), _ptr(colour_t), _P(_stream(stream)))
+        _call(*_bounded("rrt_mix_rays_device", bound_t, self._h, n), _ptr(material_t), _ptr(local_t), _ptr(kr_t), _ptr(reflected_t), _ptr(colour_t), _P(_stream(stream)))
 
     def mix_pixels(self, colours, width: int, height: int, region=None, order: int = ORDER_ROWS) -> np.ndarray:
         """rrt_mix_pixels: the region's pixels, [h][w] uint32 0x00RRGGBB, from the colours of its ray batch (uint32, frame_ray_count(...) of them, in `order`):

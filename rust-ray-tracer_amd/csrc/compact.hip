@@ -10,6 +10,11 @@
 //                  values and index = 0xFFFFFFFF to slot i if i >= total: survivors fill [0, total), dead entries [total, n), so no slot is written twice.
 // No block waits on another block and no atomic decides a position: the result is the same bits on every run.  Values are moved as 1-, 4- and 8-byte integers;
 // no arithmetic touches them, so NaN payloads and -0.0 survive.  Which arrays are present is uniform across a launch (kernel arguments).
+//
+// The counted forms (rrt.h: COUNTED DEVICE FORMS): count_kernel, place_kernel and scatter_kernel have a kCounted instantiation with ONE more argument, the bound -- a
+// pack of no or one `const uint32_t*`, so the uncounted instantiation keeps the argument list it had.  The length of the batch becomes m = min(n, *bound), one scalar
+// load, and a block whose first entry lies at or beyond m leaves before its first barrier and before it touches LDS or the arrays -- the whole block, because m is
+// uniform.  The grids stay those of n, so scan_kernel is as it was: a count block beyond m still writes its tile's zero.  The bound is only ever read.
 #include <hip/hip_runtime.h>
 
 #include "batch_words.hpp"
@@ -36,16 +41,32 @@ __device__ __forceinline__ bool selected(const CompactParams& P, size_t i) {
     return P.select == 0u || P.mats[m].kr > 0.0;
 }
 
+// m of a counted launch
+__device__ __forceinline__ uint32_t counted_length(uint32_t n, const uint32_t* __restrict__ bound) {
+    const uint32_t c = *bound;                                            // uniform: a kernel-argument pointer
+    return c < n ? c : n;
+}
+
 template <int K> __device__ __forceinline__ void fill_words(double* dst, size_t to, uint64_t first, uint64_t rest) {
     uint64_t* d = reinterpret_cast<uint64_t*>(dst) + (size_t)K * to;
 #pragma unroll
     for (int k = 0; k < K; k++) d[k] = k == 0 ? first : rest;
 }
 
-__global__ __launch_bounds__(kCompactTile) void count_kernel(const CompactParams P) {
+template <bool kCounted = false, class... Bound>
+__global__ __launch_bounds__(kCompactTile) void count_kernel(const CompactParams P, Bound... bound) {
+    static_assert(sizeof...(Bound) == (kCounted ? 1 : 0), "a counted kernel takes one bound");
+    uint32_t n = P.n;
+    if constexpr (kCounted) {
+        n = counted_length(n, bound...);
+        if ((uint64_t)blockIdx.x * kCompactTile >= n) {                    // a tile wholly beyond the bound: its zero for scan_kernel, nothing else
+            if (threadIdx.x == 0) P.tiles[blockIdx.x] = 0;
+            return;
+        }
+    }
     __shared__ uint32_t wave_count[kWaves];
     const size_t i = (size_t)blockIdx.x * kCompactTile + threadIdx.x;
-    const bool s = i < P.n && selected(P, i);
+    const bool s = i < n && selected(P, i);
     const unsigned long long ballot = __ballot(s);
     if ((threadIdx.x & 63u) == 0) wave_count[threadIdx.x >> 6] = (uint32_t)__popcll(ballot);
     __syncthreads();
@@ -86,10 +107,17 @@ __global__ __launch_bounds__(kScanBlock) void scan_kernel(uint32_t* tiles, uint3
     }
 }
 
-__global__ __launch_bounds__(kCompactTile) void place_kernel(const CompactParams P) {
+template <bool kCounted = false, class... Bound>
+__global__ __launch_bounds__(kCompactTile) void place_kernel(const CompactParams P, Bound... bound) {
+    static_assert(sizeof...(Bound) == (kCounted ? 1 : 0), "a counted kernel takes one bound");
+    uint32_t n = P.n;
+    if constexpr (kCounted) {
+        n = counted_length(n, bound...);
+        if ((uint64_t)blockIdx.x * kCompactTile >= n) return;              // neither a survivor nor a dead slot below the bound in this tile
+    }
     __shared__ uint32_t wave_count[kWaves];
     const size_t i = (size_t)blockIdx.x * kCompactTile + threadIdx.x;
-    const bool in = i < P.n;
+    const bool in = i < n;
     const bool s = in && selected(P, i);
     const unsigned long long ballot = __ballot(s);
     const uint32_t wave = threadIdx.x >> 6;
@@ -142,15 +170,22 @@ __global__ __launch_bounds__(kCompactTile) void place_kernel(const CompactParams
     }
 }
 
-// dst[index[j]] = src[j] for every j whose index is below n; kBytes per element
+// dst[index[j]] = src[j] for every j -- of a counted launch: every j below the bound -- whose index is below n; kBytes per element
 template <int kBytes> __device__ __forceinline__ void scatter_one(const void* src, size_t j, void* dst, size_t to) {
     if constexpr (kBytes == 1) static_cast<uint8_t*>(dst)[to] = static_cast<const uint8_t*>(src)[j];
     else if constexpr (kBytes == 4) static_cast<uint32_t*>(dst)[to] = static_cast<const uint32_t*>(src)[j];
     else move_words<kBytes / 8>(static_cast<const double*>(src), j, static_cast<double*>(dst), to);
 }
-__global__ __launch_bounds__(256) void scatter_kernel(uint32_t n, const uint32_t* index, uint32_t elem_bytes, const void* src, void* dst) {
+template <bool kCounted = false, class... Bound>
+__global__ __launch_bounds__(256) void scatter_kernel(uint32_t n, const uint32_t* index, uint32_t elem_bytes, const void* src, void* dst, Bound... bound) {
+    static_assert(sizeof...(Bound) == (kCounted ? 1 : 0), "a counted kernel takes one bound");
+    uint32_t m = n;                                     // j runs below m; an index is a position in the caller's arrays of n
+    if constexpr (kCounted) {
+        m = counted_length(n, bound...);
+        if ((uint64_t)blockIdx.x * 256 >= m) return;
+    }
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
+    if (j >= m) return;
     const uint32_t to = index[j];
     if (to >= n) return;
     switch (elem_bytes) {                               // uniform across the launch
@@ -165,18 +200,23 @@ __global__ __launch_bounds__(256) void scatter_kernel(uint32_t n, const uint32_t
 
 }  // namespace
 
-int launch_compact(const CompactParams& q, uint32_t* d_count, void* stream) {
+int launch_compact(const CompactParams& q, const uint32_t* d_bound, uint32_t* d_count, void* stream) {
     if (q.n == 0) return 0;
     const uint32_t n_tiles = compact_tiles(q.n);
-    hipLaunchKernelGGL(count_kernel, dim3(n_tiles), dim3(kCompactTile), 0, (hipStream_t)stream, q);
+    const bool place = q.index || q.any_dst;
+    if (d_bound) hipLaunchKernelGGL((count_kernel<true, const uint32_t*>), dim3(n_tiles), dim3(kCompactTile), 0, (hipStream_t)stream, q, d_bound);
+    else hipLaunchKernelGGL(count_kernel<>, dim3(n_tiles), dim3(kCompactTile), 0, (hipStream_t)stream, q);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScanBlock), 0, (hipStream_t)stream, q.tiles, n_tiles, d_count);
-    if (q.index || q.any_dst) hipLaunchKernelGGL(place_kernel, dim3(n_tiles), dim3(kCompactTile), 0, (hipStream_t)stream, q);
+    if (place && d_bound) hipLaunchKernelGGL((place_kernel<true, const uint32_t*>), dim3(n_tiles), dim3(kCompactTile), 0, (hipStream_t)stream, q, d_bound);
+    else if (place) hipLaunchKernelGGL(place_kernel<>, dim3(n_tiles), dim3(kCompactTile), 0, (hipStream_t)stream, q);
     return (int)hipGetLastError();
 }
 
-int launch_scatter(uint32_t n, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream) {
+int launch_scatter(uint32_t n, const uint32_t* d_bound, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(scatter_kernel, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, d_index, elem_bytes, d_src, d_dst);
+    const dim3 grid((uint32_t)(((uint64_t)n + 255) / 256));
+    if (d_bound) hipLaunchKernelGGL((scatter_kernel<true, const uint32_t*>), grid, dim3(256), 0, (hipStream_t)stream, n, d_index, elem_bytes, d_src, d_dst, d_bound);
+    else hipLaunchKernelGGL(scatter_kernel<>, grid, dim3(256), 0, (hipStream_t)stream, n, d_index, elem_bytes, d_src, d_dst);
     return (int)hipGetLastError();
 }
 

@@ -210,7 +210,7 @@ struct AmbientRaysParams {
     double max_t;
     double dirs[RRT_MAX_AMBIENT_SAMPLES][3];
 };
-static_assert(sizeof(DevScene) + sizeof(uint64_t) + sizeof(AmbientRaysParams) < 4096, "the arguments of ambient_rays_kernel must fit the 4 KB kernel-argument segment");
+static_assert(sizeof(DevScene) + 2 * sizeof(uint64_t) + sizeof(AmbientRaysParams) < 4096, "the arguments of ambient_rays_kernel, the bound of its counted form included, must fit the 4 KB kernel-argument segment");
 
 // Argument of the compaction kernels (compact.hip; rrt.h: rrt_compact_rays_device).  RaySetPtrs mirrors rrt_ray_set: the rays, their bounds and rotations and the
 // twelve record arrays of a batch, [n] each with the element widths of rrt.h; a null array of `dst` is not written, and only the arrays `dst` asks for are read of
@@ -236,10 +236,11 @@ struct CompactParams {
 };
 
 // kernel launches (compact.hip).  Both return hipError_t cast to int; nothing is synchronised.
+// d_bound: null, or the bound of a counted launch (rrt.h: COUNTED DEVICE FORMS) -- one uint32 in device memory, read by the kernels when they run; grids are those of n.
 // count, scan and place of q on `stream`; the total goes to q.tiles[compact_tiles(q.n)] and, if it is not null, to *d_count
-int launch_compact(const CompactParams& q, uint32_t* d_count, void* stream);
-// d_dst[d_index[j]] = d_src[j], elem_bytes (1, 4, 8, 16 or 24) each, for every j in [0, n) with d_index[j] < n
-int launch_scatter(uint32_t n, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream);
+int launch_compact(const CompactParams& q, const uint32_t* d_bound, uint32_t* d_count, void* stream);
+// d_dst[d_index[j]] = d_src[j], elem_bytes (1, 4, 8, 16 or 24) each, for every j in [0, n) -- with a bound [0, min(n, *d_bound)) -- with d_index[j] < n
+int launch_scatter(uint32_t n, const uint32_t* d_bound, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream);
 
 // Argument of the sort kernels (sort.hip; rrt.h: rrt_sort_rays_device).  A hist / place block covers a tile of kSortTile consecutive entries.  The scratch, in
 // 4-byte words: two (key, index) buffer pairs of n words per array, the digit counts of one pass, digit-major ([256][sort_tiles(n)]), and the 256 digit totals.
@@ -285,7 +286,7 @@ struct MixPixelsParams {
 };
 // kernel launches (wavefront.hip).  All return hipError_t cast to int; nothing is synchronised; n == 0 launches nothing.
 int launch_frame_rays(const FrameRaysParams& q, void* stream);
-int launch_mix_rays(const MixRaysParams& q, void* stream);
+int launch_mix_rays(const MixRaysParams& q, const uint32_t* d_bound, void* stream);   // (d_bound: as launch_compact's)
 int launch_mix_pixels(const MixPixelsParams& q, void* stream);
 
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
@@ -297,18 +298,19 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
 template <class Params> int launch_region(const DevScene& s, const Params& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
 // The six per-ray launchers (render.hip: each is launch_per_ray with its kernel): one lane per ray, 64 rays per block; n == 0 launches nothing.
-int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk);
+// d_count: null, or the bound of a counted launch (rrt.h: COUNTED DEVICE FORMS) -- one uint32 in device memory, read by the kernel when it runs; the grid is that of n.
+int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, const uint32_t* d_count, void* stream, int walk);
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
-                     uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream, int walk);
+                     uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, const uint32_t* d_count, void* stream, int walk);
 // (any of the five outputs of launch_intersect may be null: that array is not written)
 // Some/None of the same walk as a shadow query (render.hip: occlusion_kernel): d_occluded[n] = 1 / 0
-int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream, int walk);
+int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, const uint32_t* d_count, void* stream, int walk);
 // The full surface record of every ray's first hit and the reference's next ray (render.hip: surface_rays_kernel); any array of q may be null, not all
-int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, void* stream, int walk);
+int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, const uint32_t* d_count, void* stream, int walk);
 // The colour, the unquantised local colour and the kr of every ray from its kept record (render.hip: shade_rays_kernel); any output of q may be null, not all
-int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, void* stream, int walk);
+int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, const uint32_t* d_count, void* stream, int walk);
 // The occlusion mask and the count of open rays of every record's hemisphere fan (render.hip: ambient_rays_kernel); either output of q may be null, not both
-int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, void* stream, int walk);
+int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, const uint32_t* d_count, void* stream, int walk);
 // Exactness guard for a new eye (scene_build.hip: k_suspects_resident): searches the resident list slots geom[0, n_list_slots) and appends up to
 // RRT_MAX_SUSPECTS + 1 records {push index, suspect} to d_out, counting every find in *d_count (zeroed here, on `stream`).  Not synchronised.
 struct SuspectRecord { uint32_t tri; uint32_t _pad; DevSuspect s; };

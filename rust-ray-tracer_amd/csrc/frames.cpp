@@ -491,7 +491,7 @@ int shade_rays_from_host(rrt_raytracer* rt, uint32_t n, const double* dirs, cons
         rrt_ray_surface d_rec{};
         d_rec.point = (double*)pl[1].dev; d_rec.normal = (double*)pl[2].dev; d_rec.material = (uint32_t*)pl[3].dev; d_rec.albedo = (uint32_t*)pl[4].dev; d_rec.lights = (uint32_t*)pl[5].dev;
         const ShadeRaysParams q = shade_rays_params((const double*)pl[0].dev, d_rec, depth, rrt_ray_shade{(uint32_t*)pl[6].dev, (double*)pl[7].dev, (double*)pl[8].dev});
-        recorded_ray_launch(rt, n, nullptr, [&](int variant) { return launch_shade_rays(rt->scene, n, q, nullptr, variant); });
+        recorded_ray_launch(rt, n, nullptr, [&](int variant) { return launch_shade_rays(rt->scene, n, q, nullptr, nullptr, variant); });
     });
     return RRT_OK;
 }
@@ -526,7 +526,7 @@ int ambient_rays_from_host(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface&
         rrt_ray_surface d_rec{};
         d_rec.point = (double*)pl[0].dev; d_rec.normal = (double*)pl[1].dev; d_rec.material = (uint32_t*)pl[2].dev;
         const AmbientRaysParams q = ambient_rays_params(d_rec, (const double*)pl[3].dev, samples, rrt_ray_ambient{(uint32_t*)pl[4].dev, (uint32_t*)pl[5].dev});
-        recorded_ray_launch(rt, n, nullptr, [&](int variant) { return launch_ambient_rays(rt->scene, n, q, nullptr, variant); });
+        recorded_ray_launch(rt, n, nullptr, [&](int variant) { return launch_ambient_rays(rt->scene, n, q, nullptr, nullptr, variant); });
     });
     return RRT_OK;
 }
@@ -607,7 +607,7 @@ int compact_from_host(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint
         RaySetArrays d_src{}, d_dst{};
         for (size_t k = 0; k < kRaySetArrays; k++) { d_src.p[k] = pl[from[k]].dev; d_dst.p[k] = pl[kDst + k].dev; }
         const CompactParams q = compact_params(rt, n, select, (const uint8_t*)pl[kFlag].dev, d_src, d_dst, (uint32_t*)pl[kIndex].dev, pl[kScratch].dev);
-        HIP_TRY((hipError_t)launch_compact(q, (uint32_t*)pl[kCount].dev, nullptr));
+        HIP_TRY((hipError_t)launch_compact(q, nullptr, (uint32_t*)pl[kCount].dev, nullptr));
     });
     return RRT_OK;
 }
@@ -725,13 +725,14 @@ void check_mix_rays(const rrt_raytracer* rt, uint32_t n, const double* local, co
 // The frame by ray generations.  Its work memory, as byte offsets into the caller's allocation, every array in a slot of its own (device_memory.hpp: slot_bytes):
 // the rays of the level in hand and of the next one (origins, dirs, max_t, twice), the record arrays a level's surface launch writes and its shade launch reads, the
 // colours of two levels and the scattered colours of the level below, the compaction's scratch -- 228 bytes per entry -- and, KEPT PER LEVEL for the way back up,
-// local, kr, material and the compaction's index: 40 bytes per entry and level.
+// local, kr, material and the compaction's index: 40 bytes per entry and level.  The compactions' counts, a uint32 per level, share the scratch's slot.
 constexpr uint32_t kMaxLevels = RRT_MAX_REFLECT + 1;
 struct WavefrontWork {
     size_t origins[2], dirs[2], max_t[2];
     size_t albedo, point, normal, lights, next_origin, next_dir;
     size_t colour[2], reflected, scratch;
     size_t local[kMaxLevels], kr[kMaxLevels], material[kMaxLevels], index[kMaxLevels];
+    size_t counts;                          // one uint32 per level, behind the scratch in its slot: c[k], the count of level k's compaction -- the bound of level k + 1
     size_t bytes;
 };
 WavefrontWork wavefront_work(uint64_t n, uint32_t levels) {
@@ -740,7 +741,9 @@ WavefrontWork wavefront_work(uint64_t n, uint32_t levels) {
     auto take = [&](size_t bytes) { const size_t at = used; used += slot_bytes(bytes ? bytes : 1); return at; };
     for (int i = 0; i < 2; i++) { w.origins[i] = take(24 * n); w.dirs[i] = take(24 * n); w.max_t[i] = take(8 * n); w.colour[i] = take(4 * n); }
     w.albedo = take(4 * n); w.point = take(24 * n); w.normal = take(24 * n); w.lights = take(4 * n); w.next_origin = take(24 * n); w.next_dir = take(24 * n);
-    w.reflected = take(4 * n); w.scratch = take(compact_scratch_bytes((uint32_t)n));
+    w.reflected = take(4 * n);
+    const size_t scratch = compact_scratch_bytes((uint32_t)n);                 // (a multiple of 4: the counts behind it, in its slot, are aligned)
+    w.scratch = take(scratch + sizeof(uint32_t) * kMaxLevels); w.counts = w.scratch + scratch;
     for (uint32_t k = 0; k < levels; k++) { w.local[k] = take(24 * n); w.kr[k] = take(8 * n); w.material[k] = take(4 * n); w.index[k] = take(4 * n); }
     w.bytes = used;
     return w;
@@ -755,14 +758,18 @@ FrameBatch check_wavefront(const rrt_raytracer* rt, uint32_t width, uint32_t hei
 }
 // The pipeline of batch b (checked) on `stream`, with d_work (checked) carved as wavefront_work says: generate; per level surface -> shade (local and kr only, with
 // the mask: it walks nothing) -> compaction of the mirror hits' next rays into the next level's rays; back up, per level the colours of the level below scattered
-// into source order and mixed in; the pixels.  Every level runs at the same n: the dead tail of a compacted level walks nothing.  Only launchers that the per-ray
-// entry points use are called; one pair of events around all of it, one record.
+// into source order and mixed in; the pixels.  Every launch has the grid of n, but from level 1 on each is COUNTED (rrt.h: COUNTED DEVICE FORMS) by a count the
+// pipeline itself left in the work memory, c[k] = the count of level k's compaction: surface, shade and compaction of level k by c[k - 1] (the compaction writes
+// c[k]), the scatter of level k by c[k], the mix of level k by c[k - 1].  Blocks beyond a bound leave at once, and what lies beyond it in the arrays is neither
+// written nor read: a level whose predecessor left nothing alive costs its launches and nothing else.  Level 0, its mix and the pixels run uncounted.  Only
+// launchers that the per-ray entry points use are called; one pair of events around all of it, one record.
 void launch_wavefront(rrt_raytracer* rt, uint32_t width, uint32_t height, const FrameBatch& b, void* d_fb, void* d_work, void* stream) {
     const uint32_t n = (uint32_t)b.n, levels = wavefront_levels(rt), last = levels - 1;
     const WavefrontWork w = wavefront_work(n, levels);
     char* base = static_cast<char*>(d_work);
     auto f64 = [&](size_t at) { return reinterpret_cast<double*>(base + at); };
     auto u32 = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
+    uint32_t* const counts = u32(w.counts);
     const int variant = device_rays_variant(rt);
     timed_launch(rt, stream, [&]() -> int {
         HIP_TRY((hipError_t)launch_frame_rays(frame_rays_params(rt, width, height, b, f64(w.origins[0]), f64(w.dirs[0]), f64(w.max_t[0])), stream));
@@ -771,22 +778,24 @@ void launch_wavefront(rrt_raytracer* rt, uint32_t width, uint32_t height, const 
             RaySurfaceParams rec{};
             rec.albedo = u32(w.albedo); rec.point = f64(w.point); rec.normal = f64(w.normal); rec.material = u32(w.material[k]); rec.lights = u32(w.lights);
             if (k < last) { rec.next_origin = f64(w.next_origin); rec.next_dir = f64(w.next_dir); }
-            HIP_TRY((hipError_t)launch_surface_rays(rt->scene, n, f64(w.origins[cur]), f64(w.dirs[cur]), f64(w.max_t[cur]), rec, stream, variant));
+            const uint32_t* alive = k ? counts + (k - 1) : nullptr;          // the entries of this level: c[k - 1]; all n at level 0
+            HIP_TRY((hipError_t)launch_surface_rays(rt->scene, n, f64(w.origins[cur]), f64(w.dirs[cur]), f64(w.max_t[cur]), rec, alive, stream, variant));
             const ShadeRaysParams shade{f64(w.dirs[cur]), rec.point, rec.normal, rec.material, rec.albedo, rec.lights, nullptr, f64(w.local[k]), f64(w.kr[k]), k, 0u};
-            HIP_TRY((hipError_t)launch_shade_rays(rt->scene, n, shade, stream, variant));
+            HIP_TRY((hipError_t)launch_shade_rays(rt->scene, n, shade, alive, stream, variant));
             if (k == last) break;
             RaySetArrays src{}, dst{};                                     // the next rays of the mirror hits become the rays of level k + 1; max_t is synthesised
             src.p[kRaySetOrigins] = rec.next_origin; src.p[kRaySetDirs] = rec.next_dir; src.p[kRaySetMaterial] = rec.material;
             dst.p[kRaySetOrigins] = f64(w.origins[nxt]); dst.p[kRaySetDirs] = f64(w.dirs[nxt]); dst.p[kRaySetMaxT] = f64(w.max_t[nxt]);
-            HIP_TRY((hipError_t)launch_compact(compact_params(rt, n, RRT_SELECT_MIRROR, nullptr, src, dst, u32(w.index[k]), base + w.scratch), nullptr, stream));
+            HIP_TRY((hipError_t)launch_compact(compact_params(rt, n, RRT_SELECT_MIRROR, nullptr, src, dst, u32(w.index[k]), base + w.scratch), alive, counts + k, stream));
         }
         for (uint32_t k = levels; k-- > 0;) {                              // the unwind, innermost level first (raytracer.rs:85-101)
             const uint32_t* reflected = nullptr;
             if (k < last) {
-                HIP_TRY((hipError_t)launch_scatter(n, u32(w.index[k]), 4, u32(w.colour[(k + 1) & 1u]), u32(w.reflected), stream));
+                HIP_TRY((hipError_t)launch_scatter(n, counts + k, u32(w.index[k]), 4, u32(w.colour[(k + 1) & 1u]), u32(w.reflected), stream));
                 reflected = u32(w.reflected);
             }
-            HIP_TRY((hipError_t)launch_mix_rays(MixRaysParams{u32(w.material[k]), f64(w.local[k]), f64(w.kr[k]), reflected, u32(w.colour[k & 1u]), n, rt->scene.n_mats}, stream));
+            HIP_TRY((hipError_t)launch_mix_rays(MixRaysParams{u32(w.material[k]), f64(w.local[k]), f64(w.kr[k]), reflected, u32(w.colour[k & 1u]), n, rt->scene.n_mats},
+                                                k ? counts + (k - 1) : nullptr, stream));
         }
         return launch_mix_pixels(mix_pixels_params(width, height, b, u32(w.colour[0]), d_fb), stream);
     });
@@ -986,7 +995,7 @@ int rrt_get_ray_colours(rrt_raytracer* rt, uint32_t n, const double* origins, co
     return guarded([&]() -> int {
         const HostPlane out[] = {plane_down(colours, 4, n)};
         return host_ray_query(rt, n, origins, dirs, nullptr, out, [&](uint32_t m, const double* o, const double* d, const double*, void* const* x, int variant) {
-            return launch_ray_colours(rt->scene, m, o, d, (uint32_t*)x[0], nullptr, variant);
+            return launch_ray_colours(rt->scene, m, o, d, (uint32_t*)x[0], nullptr, nullptr, variant);
         });
     });
 }
@@ -997,7 +1006,7 @@ int rrt_intersect_rays(rrt_raytracer* rt, uint32_t n, const double* origins, con
     return guarded([&]() -> int {
         const HostPlane out[] = {plane_down(hit, 1, n), plane_down(t, 8, n), plane_down(u, 8, n), plane_down(v, 8, n), plane_down(tri, 4, n)};
         return host_ray_query(rt, n, origins, dirs, max_t, out, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
-            return launch_intersect(rt->scene, m, o, d, mt, (uint8_t*)x[0], (double*)x[1], (double*)x[2], (double*)x[3], (uint32_t*)x[4], nullptr, variant);
+            return launch_intersect(rt->scene, m, o, d, mt, (uint8_t*)x[0], (double*)x[1], (double*)x[2], (double*)x[3], (uint32_t*)x[4], nullptr, nullptr, variant);
         });
     });
 }
@@ -1006,34 +1015,47 @@ int rrt_occluded_rays(rrt_raytracer* rt, uint32_t n, const double* origins, cons
     return guarded([&]() -> int {
         const HostPlane out[] = {plane_down(occluded, 1, n)};
         return host_ray_query(rt, n, origins, dirs, max_t, out, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
-            return launch_occlusion(rt->scene, m, o, d, mt, (uint8_t*)x[0], nullptr, variant);
+            return launch_occlusion(rt->scene, m, o, d, mt, (uint8_t*)x[0], nullptr, nullptr, variant);
         });
     });
 }
 
-int rrt_intersect_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
-                              uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream) {
+// The device forms of the per-ray calls, and behind them their counted forms (rrt.h: COUNTED DEVICE FORMS): ONE body per call, the uncounted entry point gives it a
+// null bound.  The bound is never looked at on the host: the same checks, the same grid, the same record.
+int rrt_intersect_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const double* d_origins, const double* d_dirs, const double* d_max_t,
+                                      uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream) {
     return guarded([&]() -> int {
         return device_ray_query(rt, n, d_origins, d_dirs, d_hit || d_t || d_u || d_v || d_tri, stream, [&](int variant) {
-            return launch_intersect(rt->scene, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri, stream, variant);
+            return launch_intersect(rt->scene, n, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri, d_count, stream, variant);
         });
     });
 }
+int rrt_intersect_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
+                              uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream) {
+    return rrt_intersect_rays_counted_device(rt, n, nullptr, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri, stream);
+}
 
-int rrt_get_ray_colours_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream) {
+int rrt_get_ray_colours_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream) {
     return guarded([&]() -> int {
         return device_ray_query(rt, n, d_origins, d_dirs, d_colours != nullptr, stream, [&](int variant) {
-            return launch_ray_colours(rt->scene, n, d_origins, d_dirs, d_colours, stream, variant);
+            return launch_ray_colours(rt->scene, n, d_origins, d_dirs, d_colours, d_count, stream, variant);
         });
     });
 }
+int rrt_get_ray_colours_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream) {
+    return rrt_get_ray_colours_counted_device(rt, n, nullptr, d_origins, d_dirs, d_colours, stream);
+}
 
-int rrt_occluded_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream) {
+int rrt_occluded_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const double* d_origins, const double* d_dirs, const double* d_max_t,
+                                     uint8_t* d_occluded, void* stream) {
     return guarded([&]() -> int {
         return device_ray_query(rt, n, d_origins, d_dirs, d_occluded != nullptr, stream, [&](int variant) {
-            return launch_occlusion(rt->scene, n, d_origins, d_dirs, d_max_t, d_occluded, stream, variant);
+            return launch_occlusion(rt->scene, n, d_origins, d_dirs, d_max_t, d_occluded, d_count, stream, variant);
         });
     });
+}
+int rrt_occluded_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream) {
+    return rrt_occluded_rays_counted_device(rt, n, nullptr, d_origins, d_dirs, d_max_t, d_occluded, stream);
 }
 
 int rrt_surface_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const double* max_t, const rrt_ray_surface* out) {
@@ -1046,17 +1068,21 @@ int rrt_surface_rays(rrt_raytracer* rt, uint32_t n, const double* origins, const
         return host_ray_query(rt, n, origins, dirs, max_t, arrays, [&](uint32_t m, const double* o, const double* d, const double* mt, void* const* x, int variant) {
             rrt_ray_surface dev;
             std::memcpy(&dev, x, sizeof dev);
-            return launch_surface_rays(rt->scene, m, o, d, mt, ray_surface_params(dev), nullptr, variant);
+            return launch_surface_rays(rt->scene, m, o, d, mt, ray_surface_params(dev), nullptr, nullptr, variant);
         }, kAnyOutput);
     });
 }
 
-int rrt_surface_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const rrt_ray_surface* d_out, void* stream) {
+int rrt_surface_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const double* d_origins, const double* d_dirs, const double* d_max_t,
+                                    const rrt_ray_surface* d_out, void* stream) {
     return guarded([&]() -> int {
         return device_ray_query(rt, n, d_origins, d_dirs, ray_surface_wanted(rt, d_out), stream, [&](int variant) {
-            return launch_surface_rays(rt->scene, n, d_origins, d_dirs, d_max_t, ray_surface_params(*d_out), stream, variant);
+            return launch_surface_rays(rt->scene, n, d_origins, d_dirs, d_max_t, ray_surface_params(*d_out), d_count, stream, variant);
         });
     });
+}
+int rrt_surface_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const rrt_ray_surface* d_out, void* stream) {
+    return rrt_surface_rays_counted_device(rt, n, nullptr, d_origins, d_dirs, d_max_t, d_out, stream);
 }
 
 int rrt_shade_rays(rrt_raytracer* rt, uint32_t n, const double* dirs, const rrt_ray_surface* rec, uint32_t depth, const rrt_ray_shade* out) {
@@ -1066,13 +1092,17 @@ int rrt_shade_rays(rrt_raytracer* rt, uint32_t n, const double* dirs, const rrt_
     });
 }
 
-int rrt_shade_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_dirs, const rrt_ray_surface* d_rec, uint32_t depth, const rrt_ray_shade* d_out, void* stream) {
+int rrt_shade_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const double* d_dirs, const rrt_ray_surface* d_rec, uint32_t depth,
+                                  const rrt_ray_shade* d_out, void* stream) {
     return guarded([&]() -> int {
         check_shade_rays(rt, n, d_dirs, d_rec, d_out);
         return device_ray_launch(rt, n, stream, [&](int variant) {
-            return launch_shade_rays(rt->scene, n, shade_rays_params(d_dirs, *d_rec, depth, *d_out), stream, variant);
+            return launch_shade_rays(rt->scene, n, shade_rays_params(d_dirs, *d_rec, depth, *d_out), d_count, stream, variant);
         });
     });
+}
+int rrt_shade_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_dirs, const rrt_ray_surface* d_rec, uint32_t depth, const rrt_ray_shade* d_out, void* stream) {
+    return rrt_shade_rays_counted_device(rt, n, nullptr, d_dirs, d_rec, depth, d_out, stream);
 }
 
 int rrt_ambient_rays(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface* rec, const double* rot, const rrt_ambient_samples* samples, const rrt_ray_ambient* out) {
@@ -1082,14 +1112,18 @@ int rrt_ambient_rays(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface* rec, 
     });
 }
 
-int rrt_ambient_rays_device(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface* d_rec, const double* d_rot, const rrt_ambient_samples* samples,
-                            const rrt_ray_ambient* d_out, void* stream) {
+int rrt_ambient_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const rrt_ray_surface* d_rec, const double* d_rot,
+                                    const rrt_ambient_samples* samples, const rrt_ray_ambient* d_out, void* stream) {
     return guarded([&]() -> int {
         check_ambient_rays(rt, n, d_rec, samples, d_out);
         return device_ray_launch(rt, n, stream, [&](int variant) {
-            return launch_ambient_rays(rt->scene, n, ambient_rays_params(*d_rec, d_rot, *samples, *d_out), stream, variant);
+            return launch_ambient_rays(rt->scene, n, ambient_rays_params(*d_rec, d_rot, *samples, *d_out), d_count, stream, variant);
         });
     });
+}
+int rrt_ambient_rays_device(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface* d_rec, const double* d_rot, const rrt_ambient_samples* samples,
+                            const rrt_ray_ambient* d_out, void* stream) {
+    return rrt_ambient_rays_counted_device(rt, n, nullptr, d_rec, d_rot, samples, d_out, stream);
 }
 
 size_t rrt_compact_scratch_bytes(uint32_t n) { return compact_scratch_bytes(n); }
@@ -1102,17 +1136,23 @@ int rrt_compact_rays(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8
     });
 }
 
-int rrt_compact_rays_device(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* d_flag, const rrt_ray_set* d_src, const rrt_ray_set* d_dst,
-                            uint32_t* d_index, uint32_t* d_count, void* d_scratch, size_t scratch_bytes, void* stream) {
+// (d_bound: the bound of the counted form, d_count_out: the call's output; the uncounted entry point gives a null bound)
+int rrt_compact_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_bound, uint32_t select, const uint8_t* d_flag, const rrt_ray_set* d_src,
+                                    const rrt_ray_set* d_dst, uint32_t* d_index, uint32_t* d_count_out, void* d_scratch, size_t scratch_bytes, void* stream) {
     return guarded([&]() -> int {
         const RaySetArrays s = ray_set_arrays(d_src), d = ray_set_arrays(d_dst);
-        check_compact(rt, n, select, d_flag, s, d, d_index, d_count);
+        check_compact(rt, n, select, d_flag, s, d, d_index, d_count_out);
+        if (d_bound && d_bound == d_count_out) throw Error{RRT_ERR_INVALID_ARG, "the bound and the output count are the same word: the scan would overwrite what later blocks read"};
         if (n == 0) return (int)RRT_OK;
         if (scratch_bytes < compact_scratch_bytes(n) || !d_scratch) throw Error{RRT_ERR_INVALID_ARG, "scratch too small or null: want rrt_compact_scratch_bytes(n) bytes of device memory"};
         DeviceGuard guard(rt->device);
-        HIP_TRY((hipError_t)launch_compact(compact_params(rt, n, select, d_flag, s, d, d_index, d_scratch), d_count, stream));
+        HIP_TRY((hipError_t)launch_compact(compact_params(rt, n, select, d_flag, s, d, d_index, d_scratch), d_bound, d_count_out, stream));
         return (int)RRT_OK;
     });
+}
+int rrt_compact_rays_device(rrt_raytracer* rt, uint32_t n, uint32_t select, const uint8_t* d_flag, const rrt_ray_set* d_src, const rrt_ray_set* d_dst,
+                            uint32_t* d_index, uint32_t* d_count, void* d_scratch, size_t scratch_bytes, void* stream) {
+    return rrt_compact_rays_counted_device(rt, n, nullptr, select, d_flag, d_src, d_dst, d_index, d_count, d_scratch, scratch_bytes, stream);
 }
 
 int rrt_scatter_rays(rrt_raytracer* rt, uint32_t n, const uint32_t* index, uint32_t elem_bytes, const void* src, void* dst) {
@@ -1121,19 +1161,23 @@ int rrt_scatter_rays(rrt_raytracer* rt, uint32_t n, const uint32_t* index, uint3
         if (n == 0) return (int)RRT_OK;
         DeviceGuard guard(rt->device);
         HostPlane pl[] = {plane_up(index, 4, n), plane_up(src, elem_bytes, n), HostPlane{dst, elem_bytes, n, kUp | kDown}};   // (dst up too: the entries no index names keep their values)
-        with_call_planes(pl, [&] { HIP_TRY((hipError_t)launch_scatter(n, (const uint32_t*)pl[0].dev, elem_bytes, pl[1].dev, pl[2].dev, nullptr)); });
+        with_call_planes(pl, [&] { HIP_TRY((hipError_t)launch_scatter(n, nullptr, (const uint32_t*)pl[0].dev, elem_bytes, pl[1].dev, pl[2].dev, nullptr)); });
         return (int)RRT_OK;
     });
 }
 
-int rrt_scatter_rays_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream) {
+int rrt_scatter_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst,
+                                    void* stream) {
     return guarded([&]() -> int {
         check_scatter(rt, n, d_index, elem_bytes, d_src, d_dst);
         if (n == 0) return (int)RRT_OK;
         DeviceGuard guard(rt->device);
-        HIP_TRY((hipError_t)launch_scatter(n, d_index, elem_bytes, d_src, d_dst, stream));
+        HIP_TRY((hipError_t)launch_scatter(n, d_count, d_index, elem_bytes, d_src, d_dst, stream));
         return (int)RRT_OK;
     });
+}
+int rrt_scatter_rays_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream) {
+    return rrt_scatter_rays_counted_device(rt, n, nullptr, d_index, elem_bytes, d_src, d_dst, stream);
 }
 
 size_t rrt_sort_scratch_bytes(uint32_t n) { return sort_scratch_bytes(n); }
@@ -1190,15 +1234,19 @@ int rrt_frame_rays(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt
     });
 }
 
-int rrt_mix_rays_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_material, const double* d_local, const double* d_kr, const uint32_t* d_reflected, uint32_t* d_colour,
-                        void* stream) {
+int rrt_mix_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const uint32_t* d_material, const double* d_local, const double* d_kr,
+                                const uint32_t* d_reflected, uint32_t* d_colour, void* stream) {
     return guarded([&]() -> int {
         check_mix_rays(rt, n, d_local, d_colour);
         if (n == 0) return (int)RRT_OK;
         DeviceGuard guard(rt->device);
-        HIP_TRY((hipError_t)launch_mix_rays(MixRaysParams{d_material, d_local, d_kr, d_reflected, d_colour, n, rt->scene.n_mats}, stream));
+        HIP_TRY((hipError_t)launch_mix_rays(MixRaysParams{d_material, d_local, d_kr, d_reflected, d_colour, n, rt->scene.n_mats}, d_count, stream));
         return (int)RRT_OK;
     });
+}
+int rrt_mix_rays_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_material, const double* d_local, const double* d_kr, const uint32_t* d_reflected, uint32_t* d_colour,
+                        void* stream) {
+    return rrt_mix_rays_counted_device(rt, n, nullptr, d_material, d_local, d_kr, d_reflected, d_colour, stream);
 }
 
 int rrt_mix_rays(rrt_raytracer* rt, uint32_t n, const uint32_t* material, const double* local, const double* kr, const uint32_t* reflected, uint32_t* colour) {
@@ -1209,7 +1257,7 @@ int rrt_mix_rays(rrt_raytracer* rt, uint32_t n, const uint32_t* material, const 
         HostPlane pl[] = {plane_up(material, 4, n), plane_up(local, 24, n), plane_up(kr, 8, n), plane_up(reflected, 4, n), plane_down(colour, 4, n)};
         with_call_planes(pl, [&] {
             HIP_TRY((hipError_t)launch_mix_rays(MixRaysParams{(const uint32_t*)pl[0].dev, (const double*)pl[1].dev, (const double*)pl[2].dev, (const uint32_t*)pl[3].dev,
-                                                              (uint32_t*)pl[4].dev, n, rt->scene.n_mats}, nullptr));
+                                                              (uint32_t*)pl[4].dev, n, rt->scene.n_mats}, nullptr, nullptr));
         });
         return (int)RRT_OK;
     });
@@ -1276,7 +1324,7 @@ int rrt_tune_rays_device(rrt_raytracer* rt, uint32_t n, const double* d_origins,
             constexpr size_t kBytes = (size_t)kTuneSample * (1 + 8 + 8 + 8 + 4);   // hit, t, u, v, tri of the largest sample (each a multiple of 256 bytes)
             DevArena arena{static_cast<char*>(rt->tune_buf.at_least(kBytes)), kBytes, 0};
             uint8_t* hit = arena.take<uint8_t>(m); double *t = arena.take<double>(m), *u = arena.take<double>(m), *v = arena.take<double>(m); uint32_t* tri = arena.take<uint32_t>(m);
-            measure_rays(rt, [&](int variant) { return launch_intersect(rt->scene, m, d_origins, d_dirs, d_max_t, hit, t, u, v, tri, nullptr, variant); });
+            measure_rays(rt, [&](int variant) { return launch_intersect(rt->scene, m, d_origins, d_dirs, d_max_t, hit, t, u, v, tri, nullptr, nullptr, variant); });
         }
         if (variant_out) *variant_out = (uint32_t)device_rays_variant(rt);
         return (int)RRT_OK;

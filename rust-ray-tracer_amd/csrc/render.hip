@@ -2135,9 +2135,25 @@ __global__ __launch_bounds__(256) void detile_kernel(uint32_t width, uint32_t he
 #endif   // RRT_TU_FRAME
 
 #if RRT_TU_RAYS
-template <int kWalk>
+// The counted forms of the six per-ray kernels (rrt.h: COUNTED DEVICE FORMS).  kCounted adds ONE trailing argument, the bound -- a pack of no or one
+// `const uint32_t*`, so the uncounted instantiation keeps the argument list it had -- and these two lines in front of the body: the length of the batch becomes
+// min(n, *count), one scalar load, and a block whose first entry lies at or beyond it leaves before it touches LDS, a barrier or memory.  What follows is the body
+// of the uncounted kernel with that length: lanes of a partly live wave at or beyond it are the lanes "beyond the batch".  The bound is only ever read.
+__device__ __forceinline__ uint32_t counted_length(uint32_t n, const uint32_t* __restrict__ count) {
+    const uint32_t c = *count;                                             // wave-uniform: a kernel-argument pointer
+    return c < n ? c : n;
+}
+#define RRT_COUNTED_FRONT(n)                                                                   \
+    static_assert(sizeof...(Count) == (kCounted ? 1 : 0), "a counted kernel takes one bound"); \
+    if constexpr (kCounted) {                                                                  \
+        n = counted_length(n, count...);                                                       \
+        if (blockIdx.x * 64 >= n) return;                                                      \
+    }
+
+template <int kWalk, bool kCounted = false, class... Count>
 __global__ __launch_bounds__(64) void ray_colour_kernel(const DevScene S, uint32_t n, const double* __restrict__ origins, const double* __restrict__ dirs,
-                                                        uint32_t* __restrict__ colours) {
+                                                        uint32_t* __restrict__ colours, Count... count) {
+    RRT_COUNTED_FRONT(n)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
@@ -2163,10 +2179,11 @@ __device__ __forceinline__ RayLane ray_lane(uint32_t n, const double* __restrict
     return R;
 }
 
-template <int kWalk>
+template <int kWalk, bool kCounted = false, class... Count>
 __global__ __launch_bounds__(64) void intersect_kernel(const DevScene S, uint32_t n, const double* __restrict__ origins, const double* __restrict__ dirs,
                                                        const double* __restrict__ max_t, uint8_t* __restrict__ hit, double* __restrict__ t_out,
-                                                       double* __restrict__ u_out, double* __restrict__ v_out, uint32_t* __restrict__ tri_out) {
+                                                       double* __restrict__ u_out, double* __restrict__ v_out, uint32_t* __restrict__ tri_out, Count... count) {
+    RRT_COUNTED_FRONT(n)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
     const RayLane R = ray_lane(n, origins, dirs, max_t);
@@ -2202,9 +2219,10 @@ __global__ __launch_bounds__(64) void intersect_kernel(const DevScene S, uint32_
 // first node whose own list proves Some, see the comment at that rule), with intersect_kernel's guard; no second Moller-Trumbore, no t, no attribute load.
 // kFarAnchor = false: the frame kernels anchor the bundle of a tile's shadow rays at the light, where they end together; a caller's batch need not end
 // anywhere together, and on the rays of tools/ray_batch_bench.py that do, the anchor at the origins is the faster one: DESIGN.md section 4.
-template <int kWalk>
+template <int kWalk, bool kCounted = false, class... Count>
 __global__ __launch_bounds__(64) void occlusion_kernel(const DevScene S, uint32_t n, const double* __restrict__ origins, const double* __restrict__ dirs,
-                                                       const double* __restrict__ max_t, uint8_t* __restrict__ occluded) {
+                                                       const double* __restrict__ max_t, uint8_t* __restrict__ occluded, Count... count) {
+    RRT_COUNTED_FRONT(n)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
     const RayLane R = ray_lane(n, origins, dirs, max_t);
@@ -2224,9 +2242,10 @@ __global__ __launch_bounds__(64) void occlusion_kernel(const DevScene S, uint32_
 // next_origin, next_dir: no attribute load; none of those nor u nor v: no second Moller-Trumbore.
 // Four waves per SIMD like the frame kernels, unlike the other per-ray kernels: uncapped it takes 134-149 VGPRs and runs at 3 waves; capped it spills 16-38 VGPRs
 // (36-92 B of scratch) and is 5-18 % faster on 11 of the 12 measured cases (profiles/ray_surface_kernel_resources.txt, profiles/ray_surface.json).
-template <int kWalk>
+template <int kWalk, bool kCounted = false, class... Count>
 __global__ __launch_bounds__(64, kWavesPerSimd) void surface_rays_kernel(const DevScene S, uint32_t n_rays, const double* __restrict__ origins, const double* __restrict__ dirs,
-                                                          const double* __restrict__ max_t, const RaySurfaceParams Q) {
+                                                          const double* __restrict__ max_t, const RaySurfaceParams Q, Count... count) {
+    RRT_COUNTED_FRONT(n_rays)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
     const RayLane R = ray_lane(n_rays, origins, dirs, max_t);
@@ -2275,8 +2294,9 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_rays_kernel(const D
 // (bundle / lane / ray walk) and is 5-18 % faster in every measured case that takes more than 1.4 ms, 18 of 24 cases in all; it loses 2-8 % on the teapot's
 // reflection rays (bundle filter, ray walk) and 0.01-0.07 ms in the ray walk's launches that walk nothing (profiles/shade_rays_kernel_resources.txt,
 // profiles/shade_rays.json).
-template <int kWalk>
-__global__ __launch_bounds__(64, kWavesPerSimd) void shade_rays_kernel(const DevScene S, uint32_t n_rays, const ShadeRaysParams Q) {
+template <int kWalk, bool kCounted = false, class... Count>
+__global__ __launch_bounds__(64, kWavesPerSimd) void shade_rays_kernel(const DevScene S, uint32_t n_rays, const ShadeRaysParams Q, Count... count) {
+    RRT_COUNTED_FRONT(n_rays)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
@@ -2325,8 +2345,9 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_rays_kernel(const Dev
 // the loop, lanes beyond the batch store nothing.
 // A material index at or beyond the table (0xFFFFFFFF: a miss or a dead ray) is a miss; no value of the caller's arrays is used as an index.
 // Registers, scratch and occupancy are recorded, not tuned: profiles/ambient_rays_kernel_resources.txt.
-template <int kWalk>
-__global__ __launch_bounds__(64, kWavesPerSimd) void ambient_rays_kernel(const DevScene S, uint32_t n_rays, const AmbientRaysParams Q) {
+template <int kWalk, bool kCounted = false, class... Count>
+__global__ __launch_bounds__(64, kWavesPerSimd) void ambient_rays_kernel(const DevScene S, uint32_t n_rays, const AmbientRaysParams Q, Count... count) {
+    RRT_COUNTED_FRONT(n_rays)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, threadIdx.x};
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
@@ -2370,6 +2391,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_rays_kernel(const D
     if (Q.occluded) Q.occluded[i] = mask;
     if (Q.open) Q.open[i] = n_samples - (uint32_t)__popc(mask);                          // (a miss: mask 0, every ray open -- the rule of ambient_kernel's grey)
 }
+#undef RRT_COUNTED_FRONT
 #endif   // RRT_TU_RAYS
 
 // ---- host side of the launchers below: a runtime choice of kernel as a compile-time one.  f receives a std::integral_constant and names its instantiation.
@@ -2518,41 +2540,47 @@ template int launch_region_lane_ray(const DevScene&, const AmbientParams&, void*
 #endif   // RRT_TU_LANE
 
 #if RRT_TU_RAYS
-// The per-ray launchers: one lane per ray, 64 rays per block; the bundle filter's fallback is launch_render's.  kernel_of(w) names the kernel's instantiation for
-// walk w; its arguments are the scene, n and args.
+// The per-ray launchers: one lane per ray, 64 rays per block; the bundle filter's fallback is launch_render's.  kernel_of(w, counted) names the kernel's
+// instantiation for walk w; its arguments are the scene, n, args and, with a bound (d_count not null: the counted instantiation, same grid), the bound.
 template <class KernelOf, class... Args>
-int launch_per_ray(const DevScene& s, uint32_t n, void* stream, int walk, KernelOf&& kernel_of, const Args&... args) {
+int launch_per_ray(const DevScene& s, uint32_t n, const uint32_t* d_count, void* stream, int walk, KernelOf&& kernel_of, const Args&... args) {
     if (n == 0) return 0;
     return with_walk(effective_walk(s, walk), [&](auto w) {
-        hipLaunchKernelGGL(kernel_of(w), dim3((n + 63) / 64), dim3(64), stack_bytes_per_wave(s.stack_levels), (hipStream_t)stream, s, n, args...);
+        const dim3 grid((n + 63) / 64);
+        const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
+        if (d_count) hipLaunchKernelGGL(kernel_of(w, std::true_type{}), grid, dim3(64), lds, (hipStream_t)stream, s, n, args..., d_count);
+        else hipLaunchKernelGGL(kernel_of(w, std::false_type{}), grid, dim3(64), lds, (hipStream_t)stream, s, n, args...);
         return (int)hipGetLastError();
     });
 }
+// (kernel_of of a kernel template: K<walk> without a bound, K<walk, true, const uint32_t*> with one)
+#define RRT_PER_RAY_KERNEL(K) [](auto w, auto counted) { if constexpr (counted()) return &K<w(), true, const uint32_t*>; else return &K<w()>; }
 
-int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, void* stream, int walk) {
-    return launch_per_ray(s, n, stream, walk, [](auto w) { return &ray_colour_kernel<w()>; }, d_origins, d_dirs, d_colours);
+int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, const uint32_t* d_count, void* stream, int walk) {
+    return launch_per_ray(s, n, d_count, stream, walk, RRT_PER_RAY_KERNEL(ray_colour_kernel), d_origins, d_dirs, d_colours);
 }
 
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
-                     uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, void* stream, int walk) {
-    return launch_per_ray(s, n, stream, walk, [](auto w) { return &intersect_kernel<w()>; }, d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
+                     uint8_t* d_hit, double* d_t, double* d_u, double* d_v, uint32_t* d_tri, const uint32_t* d_count, void* stream, int walk) {
+    return launch_per_ray(s, n, d_count, stream, walk, RRT_PER_RAY_KERNEL(intersect_kernel), d_origins, d_dirs, d_max_t, d_hit, d_t, d_u, d_v, d_tri);
 }
 
-int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, void* stream, int walk) {
-    return launch_per_ray(s, n, stream, walk, [](auto w) { return &occlusion_kernel<w()>; }, d_origins, d_dirs, d_max_t, d_occluded);
+int launch_occlusion(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, uint8_t* d_occluded, const uint32_t* d_count, void* stream, int walk) {
+    return launch_per_ray(s, n, d_count, stream, walk, RRT_PER_RAY_KERNEL(occlusion_kernel), d_origins, d_dirs, d_max_t, d_occluded);
 }
 
-int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, void* stream, int walk) {
-    return launch_per_ray(s, n, stream, walk, [](auto w) { return &surface_rays_kernel<w()>; }, d_origins, d_dirs, d_max_t, q);
+int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t, const RaySurfaceParams& q, const uint32_t* d_count, void* stream, int walk) {
+    return launch_per_ray(s, n, d_count, stream, walk, RRT_PER_RAY_KERNEL(surface_rays_kernel), d_origins, d_dirs, d_max_t, q);
 }
 
-int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, void* stream, int walk) {
-    return launch_per_ray(s, n, stream, walk, [](auto w) { return &shade_rays_kernel<w()>; }, q);
+int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, const uint32_t* d_count, void* stream, int walk) {
+    return launch_per_ray(s, n, d_count, stream, walk, RRT_PER_RAY_KERNEL(shade_rays_kernel), q);
 }
 
-int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, void* stream, int walk) {
-    return launch_per_ray(s, n, stream, walk, [](auto w) { return &ambient_rays_kernel<w()>; }, q);
+int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, const uint32_t* d_count, void* stream, int walk) {
+    return launch_per_ray(s, n, d_count, stream, walk, RRT_PER_RAY_KERNEL(ambient_rays_kernel), q);
 }
+#undef RRT_PER_RAY_KERNEL
 #endif   // RRT_TU_RAYS
 
 }  // namespace rrt

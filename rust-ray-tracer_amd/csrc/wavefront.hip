@@ -102,9 +102,19 @@ __device__ __forceinline__ uint32_t clamp_u8(double x) {
 }
 // One lane per entry (rrt.h: rrt_mix_rays_device).  material: null = every entry is a hit; kr, reflected: either null = nothing mixes.  `reflected` is read only where
 // an entry mixes, `local` and `kr` only for hits; no value of the caller's arrays is an index.
-__global__ __launch_bounds__(kBlock) void mix_rays_kernel(const MixRaysParams P) {
+// kCounted (rrt.h: COUNTED DEVICE FORMS): ONE more argument, the bound -- a pack of no or one `const uint32_t*`, so the uncounted instantiation keeps the argument list it
+// had.  The length becomes min(n, *bound), one scalar load, and a block whose first entry lies at or beyond it leaves at once.  The bound is only ever read.
+template <bool kCounted = false, class... Bound>
+__global__ __launch_bounds__(kBlock) void mix_rays_kernel(const MixRaysParams P, Bound... bound) {
+    static_assert(sizeof...(Bound) == (kCounted ? 1 : 0), "a counted kernel takes one bound");
+    uint32_t n = P.n;
+    if constexpr (kCounted) {
+        const uint32_t c = *(bound, ...);                                 // uniform: a kernel-argument pointer
+        n = c < n ? c : n;
+        if ((uint64_t)blockIdx.x * kBlock >= n) return;
+    }
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= P.n) return;
+    if (i >= n) return;
     uint32_t c = kWhite;
     if (!P.material || P.material[i] < P.n_mats) {                         // the hit rule of rrt_shade_rays
         const double lx = P.local[3u * i], ly = P.local[3u * i + 1u], lz = P.local[3u * i + 2u];
@@ -158,9 +168,10 @@ int launch_frame_rays(const FrameRaysParams& q, void* stream) {
     return (int)hipGetLastError();
 }
 
-int launch_mix_rays(const MixRaysParams& q, void* stream) {
+int launch_mix_rays(const MixRaysParams& q, const uint32_t* d_bound, void* stream) {
     if (q.n == 0) return 0;
-    hipLaunchKernelGGL(mix_rays_kernel, dim3(blocks_for(q.n)), dim3(kBlock), 0, (hipStream_t)stream, q);
+    if (d_bound) hipLaunchKernelGGL((mix_rays_kernel<true, const uint32_t*>), dim3(blocks_for(q.n)), dim3(kBlock), 0, (hipStream_t)stream, q, d_bound);
+    else hipLaunchKernelGGL(mix_rays_kernel<>, dim3(blocks_for(q.n)), dim3(kBlock), 0, (hipStream_t)stream, q);
     return (int)hipGetLastError();
 }
 
