@@ -638,6 +638,45 @@ int rrt_ambient_rays(rrt_raytracer *rt, uint32_t n, const rrt_ray_surface *rec, 
 int rrt_ambient_rays_device(rrt_raytracer *rt, uint32_t n, const rrt_ray_surface *d_rec, const double *d_rot,
                             const rrt_ambient_samples *samples, const rrt_ray_ambient *d_out, void *stream);
 
+/* Surface records from kept hits, with no primary walk: turns the compact answer of an earlier walk -- t, u, v, tri as rrt_intersect_rays*, rrt_surface_rays* or a
+ * frame's rrt_render_visibility* wrote them -- into the shading record rrt_shade_rays* and rrt_ambient_rays* read, without walking the rays again.  For refreshing
+ * albedo and normal after a changed `tex` or `bump` binding, or `lights` after a moved point light, and for a per-ray pipeline of library calls alone:
+ * rrt_intersect_rays_device (the cheap kernel) -> rrt_compact_rays_device (RRT_SELECT_FLAG on the hit bytes; rrt_ray_set.rec carries t, u, v, tri) ->
+ * rrt_resolve_hits_counted_device, whose shadow walks then run in full waves.
+ * rec / d_rec is the struct the caller gave rrt_intersect_rays' arrays a place in, or rrt_surface_rays[_device], or one built from a frame's visibility planes, in
+ * that layout.  READ: t, u, v, tri; `hit` is ignored.  WRITTEN: any of albedo, point, normal, material, lights, next_origin, next_dir; any of the seven may be
+ * NULL (that array is not written), at least one is set.  origins / dirs, [n][3]: the rays the hits belong to.
+ * Hit rule.  Entry i is a hit iff tri[i] < n_tris of the scene in force.  Anything else (0xFFFFFFFF, a miss or a dead entry, included) gets the miss values of
+ * rrt_surface_rays -- albedo 0x00FFFFFF, the vectors (0.0, 0.0, 0.0), material 0xFFFFFFFF, lights 0 -- and takes part in no walk.  tri is the only value of the
+ * caller's arrays that is ever used as an index, and only after that compare.  t, u and v are used as given: point = o + d * t (raytracer.rs:39), the attributes
+ * at (u, v); a non-finite one gives unspecified bits for that entry, and no fault: the texel indices go through the saturating cast and the modulo of
+ * raytracer.rs:52-53 as in every other call.
+ * CONTRACT.  If t, u, v, tri are what rrt_intersect_rays[_device], rrt_surface_rays[_device] or rrt_render_visibility[_device] wrote for the rays (o, d) in the scene
+ * in force, every requested output is what rrt_surface_rays writes for those rays with the same bound, byte for byte.  For a frame the rays are those of
+ * rrt_frame_rays in RRT_ORDER_ROWS in the same pose.  The lights, the materials and the surface_offset in force NOW apply.
+ * Required: origins, dirs, rec, rec->t and rec->tri always; rec->u and rec->v unless only point and / or material are asked for.
+ * What is not asked for is not computed.  Without `lights` nothing is walked at all: the launch is a gather of one 128-byte attribute record and up to two texels
+ * per hit, in ONE kernel whatever traversal variant is in force.  With `lights` the shadow walks are those of rrt_surface_rays: every point light tested, one per
+ * turn, all hits of a wave together -- default mode, not guarded, the band documented under RRT_FLAG_NO_CULL; a wave of 64 consecutive entries without a hit walks
+ * nothing.  Inputs and outputs must not overlap.
+ * Keeping t, u, v, tri valid is the caller's business:
+ *
+ *   change since t, u, v, tri were written                                            what is stale
+ *   rrt_raytracer_set_triangles[_device]                                              t, u, v, tri: nothing can be resolved from them
+ *   rrt_raytracer_set_materials, rrt_raytracer_set_lights                             nothing: resolving again is what brings albedo, normal and lights up to date
+ *   rrt_raytracer_set_camera                                                          nothing: the rays are the caller's
+ *
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer and the outputs as they were: NULL rt; NULL rec; all seven outputs NULL with n > 0; NULL
+ * origins, dirs or a NULL required array with n > 0.  n = 0 is RRT_OK with nothing enqueued.
+ * rrt_last_stats afterwards: as after the other per-ray calls (width = n, height = 1, rays_primary = n; shadow rays are not counted).
+ * rrt_resolve_hits_device: arrays in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default): no allocation, no copy, no synchronisation and
+ * no measurement; the traversal variant of the shadow walks by the rule of rrt_intersect_rays_device.
+ * rrt_resolve_hits: arrays in host memory; blocking.  One device allocation of the call's own; only what is read is uploaded (u and v only where an output reads
+ * them), only the requested outputs are downloaded.  It never measures the variants and picks its variant by the device form's rule, as rrt_shade_rays does.
+ * Not covered: a region form (rrt_frame_rays in RRT_ORDER_ROWS serves a frame), the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+int rrt_resolve_hits(rrt_raytracer *rt, uint32_t n, const double *origins, const double *dirs, const rrt_ray_surface *rec);
+int rrt_resolve_hits_device(rrt_raytracer *rt, uint32_t n, const double *d_origins, const double *d_dirs, const rrt_ray_surface *d_rec, void *stream);
+
 /* Stable compaction of ray batches and records, and its inverse: between two stages of a per-ray pipeline (rrt_surface_rays_device -> rrt_shade_rays_device ->
  * rrt_ambient_rays_device) a batch thins out -- misses drop out, only mirror hits reflect, only hits have an ambient fan.  These calls move the survivors to the
  * front of a batch that KEEPS ITS LENGTH n and fill the tail with dead entries, on the device and without a read-back of the count: the next stage is enqueued with
@@ -814,9 +853,9 @@ int rrt_render_wavefront_device(rrt_raytracer *rt, uint32_t width, uint32_t heig
 int rrt_render_wavefront(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region, uint32_t order, uint32_t *out_fb);
 
 /* COUNTED DEVICE FORMS.  A batch whose length was decided on the GPU -- the `count` of a compaction, the survivors of a kernel of the caller's -- need not be padded
- * with dead entries that every later stage pays for, nor read back (which synchronises).  Each of the nine calls below is the `_device` call of the same name with
+ * with dead entries that every later stage pays for, nor read back (which synchronises).  Each of the ten calls below is the `_device` call of the same name with
  * ONE more argument, `const uint32_t *d_count`, directly after n: a launch bound that lives in device memory.
- * CONTRACT, the same for all nine:
+ * CONTRACT, the same for all ten:
  *   - d_count points to one uint32 in device memory of rt's device, 4-byte aligned.  The host never reads it; the kernels read it when they run, in stream order.  It
  *     may therefore be the `count` output of a compaction enqueued earlier on the same stream, with nothing in between.  It is only ever read.
  *   - Let m = min(n, *d_count): a *d_count above n is n.  Entries [0, m) are processed exactly as the uncounted call with n = m processes them, byte for byte.
@@ -826,7 +865,7 @@ int rrt_render_wavefront(rrt_raytracer *rt, uint32_t width, uint32_t height, con
  *   - d_count == NULL: the call IS the uncounted one, through the same kernels.
  *   - Refusals are those of the uncounted form, made at the same point: before any GPU work, and for compaction, scatter and mix before the handle is looked at.
  *     n == 0 is RRT_OK with nothing enqueued.
- *   - rrt_last_stats after a counted ray call (intersect, get_ray_colours, occluded, surface, shade, ambient): as after the uncounted one, with
+ *   - rrt_last_stats after a counted ray call (intersect, get_ray_colours, occluded, surface, shade, ambient, resolve): as after the uncounted one, with
  *     width = rays_primary = n -- the host does not know m.  Counted compaction, scatter and mix leave it alone, as the uncounted ones do.
  * rrt_compact_rays_counted_device, in addition: the selection is evaluated over [0, m) only; *d_count_out, d_index and the arrays of d_dst are those of the uncounted
  * call with n = m -- survivors in [0, count_out), the dead fill in [count_out, m), nothing in [m, n); with m == 0 the output count is 0 and nothing else is written.
@@ -849,6 +888,8 @@ int rrt_shade_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t 
                                   const rrt_ray_shade *d_out, void *stream);
 int rrt_ambient_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const rrt_ray_surface *d_rec, const double *d_rot,
                                     const rrt_ambient_samples *samples, const rrt_ray_ambient *d_out, void *stream);
+int rrt_resolve_hits_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const double *d_origins, const double *d_dirs,
+                                    const rrt_ray_surface *d_rec, void *stream);
 int rrt_compact_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, uint32_t select, const uint8_t *d_flag, const rrt_ray_set *d_src,
                                     const rrt_ray_set *d_dst, uint32_t *d_index, uint32_t *d_count_out, void *d_scratch, size_t scratch_bytes, void *stream);
 int rrt_scatter_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d_count, const uint32_t *d_index, uint32_t elem_bytes, const void *d_src,
@@ -860,9 +901,12 @@ int rrt_mix_rays_counted_device(rrt_raytracer *rt, uint32_t n, const uint32_t *d
  * NULL) as rrt_model_get_info.  Any pointer may be NULL.  RRT_ERR_UNSUPPORTED for a RRT_FLAG_HOST_SETUP raytracer (ask the model). */
 int rrt_raytracer_get_octree(const rrt_raytracer *rt, rrt_model_info *info, double *aabb, uint32_t *first_child, uint32_t *tri_count,
                              uint32_t *own_off, uint32_t *own_idx);
-/* Test / developer introspection: the bytes of one scene buffer in HBM.  out == NULL asks for the size only. */
+/* Test / developer introspection: the bytes of one scene buffer in HBM.  out == NULL asks for the size only.
+ * RRT_BUF_TRI_SLOT: uint32 [n_tris], the table rrt_resolve_hits reads -- per triangle the lowest slot of RRT_BUF_ATTR / RRT_BUF_SLOT_TRI that is the triangle's
+ * (0xFFFFFFFF for a triangle outside the tree); kept by both set-up paths, the same bits on every run. */
 enum { RRT_BUF_NODES = 0, RRT_BUF_GEOM, RRT_BUF_ATTR, RRT_BUF_SUPERS, RRT_BUF_CBOXES, RRT_BUF_CHILD_BOXES, RRT_BUF_TBOXES, RRT_BUF_SUSPECTS,
-       RRT_BUF_OCT_BOX, RRT_BUF_OCT_FIRST_CHILD, RRT_BUF_OCT_TRI_COUNT, RRT_BUF_OCT_OWN_OFF, RRT_BUF_OCT_OWN_IDX, RRT_BUF_SLOT_TRI, RRT_BUF_SLOT_POS, RRT_BUF_CHAINS };
+       RRT_BUF_OCT_BOX, RRT_BUF_OCT_FIRST_CHILD, RRT_BUF_OCT_TRI_COUNT, RRT_BUF_OCT_OWN_OFF, RRT_BUF_OCT_OWN_IDX, RRT_BUF_SLOT_TRI, RRT_BUF_SLOT_POS, RRT_BUF_CHAINS,
+       RRT_BUF_TRI_SLOT };
 int rrt_raytracer_get_buffer(const rrt_raytracer *rt, uint32_t which, void *out, size_t capacity, size_t *bytes);
 
 /* Chain records of this raytracer's scene (see RRT_FLAG_NO_CHAIN_SHORTCUT): the number of chains that have one and the number of chain nodes they

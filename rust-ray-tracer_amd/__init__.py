@@ -33,7 +33,7 @@ class RrtError(RuntimeError):
 
 FLAG_NO_CULL, FLAG_LANE_FILTER, FLAG_BUNDLE_FILTER, FLAG_RAY_WALK, FLAG_HOST_SETUP, FLAG_NO_CHAIN_SHORTCUT, FLAG_NO_SPECULAR_SKIP = 1, 2, 4, 8, 16, 32, 64   # RRT_FLAG_*, include/rrt.h
 BUFFERS = ("nodes", "geom", "attr", "supers", "cboxes", "child_boxes", "tboxes", "suspects", "oct_box", "oct_first_child", "oct_tri_count", "oct_own_off",
-           "oct_own_idx", "slot_tri", "slot_pos", "chains")   # RRT_BUF_*
+           "oct_own_idx", "slot_tri", "slot_pos", "chains", "tri_slot")   # RRT_BUF_*
 VARIANT_NAMES = ("lane", "bundle", "ray")   # rrt_stats.filter_variant
 
 # status codes, include/rrt.h
@@ -141,6 +141,8 @@ RAY_SHADE_INPUTS = SHADE_INPUTS                                               # 
 _PLANES_OF[CRayAmbient] = dict(occluded=(np.uint32, 1, True), open=(np.uint32, 1, True))
 RAY_AMBIENT_OUTPUTS = tuple(_PLANES_OF[CRayAmbient])                          # the arrays of rrt_ray_ambient, in its order
 RAY_AMBIENT_INPUTS = AMBIENT_INPUTS                                           # what rrt_ambient_rays reads of an rrt_ray_surface
+RESOLVE_INPUTS = ("t", "u", "v", "tri")                                       # what rrt_resolve_hits reads of an rrt_ray_surface (u, v: not for point and material alone)
+RESOLVE_OUTPUTS = RAY_SURFACE_PLANES[5:]                                      # ... and what it writes there: albedo, point, normal, material, lights, next_origin, next_dir
 # rrt_ray_set: per ENTRY of a batch the ray, its bound, the rotation of its ambient fan and the twelve arrays of its record
 _PLANES_OF[CRaySet] = dict(origins=(np.float64, 3, True), dirs=(np.float64, 3, True), max_t=(np.float64, 1, True), rot=(np.float64, 2, True), **_PLANES_OF[CRaySurface])
 RAY_SET_ARRAYS = tuple(_PLANES_OF[CRaySet])                                   # the arrays of rrt_ray_set, in its order
@@ -233,6 +235,8 @@ SYMBOLS = {
     "rrt_shade_rays_device": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(CRaySurface), C.c_uint32, C.POINTER(CRayShade), _P]),
     "rrt_ambient_rays": (C.c_int, [_P, C.c_uint32, C.POINTER(CRaySurface), _dp, C.POINTER(CAmbientSamples), C.POINTER(CRayAmbient)]),
     "rrt_ambient_rays_device": (C.c_int, [_P, C.c_uint32, C.POINTER(CRaySurface), _P, C.POINTER(CAmbientSamples), C.POINTER(CRayAmbient), _P]),
+    "rrt_resolve_hits": (C.c_int, [_P, C.c_uint32, _dp, _dp, C.POINTER(CRaySurface)]),
+    "rrt_resolve_hits_device": (C.c_int, [_P, C.c_uint32, _P, _P, C.POINTER(CRaySurface), _P]),
     "rrt_compact_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "rrt_compact_rays_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.POINTER(CRaySet), C.POINTER(CRaySet), _P, _P, _P, C.c_size_t, _P]),
     "rrt_compact_rays": (C.c_int, [_P, C.c_uint32, C.c_uint32, _u8p, C.POINTER(CRaySet), C.POINTER(CRaySet), _u32p, _u32p]),
@@ -258,6 +262,7 @@ SYMBOLS = {
     "rrt_surface_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, C.POINTER(CRaySurface), _P]),
     "rrt_shade_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, C.POINTER(CRaySurface), C.c_uint32, C.POINTER(CRayShade), _P]),
     "rrt_ambient_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(CRaySurface), _P, C.POINTER(CAmbientSamples), C.POINTER(CRayAmbient), _P]),
+    "rrt_resolve_hits_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.POINTER(CRaySurface), _P]),
     "rrt_compact_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.POINTER(CRaySet), C.POINTER(CRaySet), _P, _P, _P, C.c_size_t, _P]),
     "rrt_scatter_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P]),
     "rrt_mix_rays_counted_device": (C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
@@ -536,6 +541,13 @@ def _ray_records(what: str, planes: dict, inputs=RAY_SHADE_INPUTS) -> dict:
     out (NULL for the library)."""
     rows = {name: (a,) + _ray_plane(name, what=what) for name, a in planes.items()}
     return {name: row for name, row in rows.items() if row[0] is not None and name in inputs}
+
+
+def _resolve_output(name: str, what: str):
+    """(dtype, elements per ray) of an array rrt_resolve_hits writes; any other name is a ValueError"""
+    if name not in RESOLVE_OUTPUTS:
+        raise ValueError(f"{what}: unknown output {name!r}, want names from {RESOLVE_OUTPUTS}")
+    return _ray_plane(name, what=what)
 
 
 def _ray_set(arrays: dict):
@@ -891,7 +903,7 @@ class RayTracer(_Handle):
         return out.astype(bool)
 
     # device-resident ray batches (rrt.h: rrt_intersect_rays_device): origins_t / dirs_t are float64 device tensors of 3 n elements, max_t_t of n; enqueued, not synchronised
-    # bound_t, in all nine _into forms that have it: None, or a device tensor of one 4-byte element -- the launch bound of the counted form (rrt.h: COUNTED DEVICE
+    # bound_t, in all ten _into forms that have it: None, or a device tensor of one 4-byte element -- the launch bound of the counted form (rrt.h: COUNTED DEVICE
     # FORMS), read on the device in stream order: only the first min(n, bound) entries of every array are read and written.
     def occluded_into(self, origins_t, dirs_t, out_t, max_t_t=None, stream: Optional[int] = None, bound_t=None):
         """rrt_occluded_rays_device: out_t = device tensor of n one-byte elements, 1 = occluded.  bound_t: rrt_occluded_rays_counted_device."""
@@ -1010,6 +1022,35 @@ class RayTracer(_Handle):
         _d_keep, samples = _ambient_samples(dirs, max_t)
         _call(*_bounded("rrt_ambient_rays_device", bound_t, self._h, n), _plane_struct(CRaySurface, {name: row[0] for name, row in rec.items()}), _ptr(rot_t), C.byref(samples),
               _plane_struct(CRayAmbient, out), _P(_stream(stream)))
+
+    # surface records from kept hits (rrt.h: rrt_resolve_hits): what surface_rays gives, from the t, u, v and tri an earlier walk of the rays left, with no primary walk
+    def resolve_hits(self, origins, dirs, planes: dict, outputs=RESOLVE_OUTPUTS) -> dict:
+        """rrt_resolve_hits: {name: array} for the names asked for, from RESOLVE_OUTPUTS -- as surface_rays returns them -- of the rays (origins, dirs) whose kept
+        hits `planes` holds ({name: array} as intersect_rays, surface_rays or visibility wrote them: t and tri are read, u and v unless only point and / or material
+        are asked for; the others are ignored), with the lights and materials in force now.  An entry whose tri is not a triangle of the scene is a miss."""
+        o, d, _ = _host_rays(origins, dirs)
+        n = o.shape[0]
+        rec = {name: np.ascontiguousarray(a, dtype) for name, (a, dtype, width) in _ray_records("resolve_hits", planes, RESOLVE_INPUTS).items()}
+        for name, a in rec.items():
+            assert a.size == n, f"resolve_hits: array {name} has {a.size} elements for {n} rays"
+        out = {name: np.empty((n, width) if width > 1 else (n,), dtype) for name, (dtype, width) in ((name, _resolve_output(name, "resolve_hits")) for name in outputs)}
+        _call("rrt_resolve_hits", self._h, n, _d(o), _d(d), _plane_struct(CRaySurface, {**rec, **out}))
+        return out
+
+    def resolve_hits_into(self, out: dict, origins_t, dirs_t, planes: dict, stream: Optional[int] = None, bound_t=None):
+        """rrt_resolve_hits_device: out = {name: contiguous device tensor} for any subset of RESOLVE_OUTPUTS (n elements of the array's item size, 3 n for point /
+        normal / next_origin / next_dir; the others are not computed -- without lights nothing is walked); origins_t / dirs_t float64 of 3 n elements; planes =
+        {name: device tensor} as intersect_rays_into or surface_rays_into filled them (t, tri, and u, v or not).  Enqueued, not synchronised.  bound_t:
+        rrt_resolve_hits_counted_device."""
+        n = _ray_batch(origins_t, dirs_t, None)
+        rec = _ray_records("resolve_hits_into", planes, RESOLVE_INPUTS)
+        for name, (t, dtype, width) in rec.items():
+            _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
+        for name, t in out.items():
+            dtype, width = _resolve_output(name, "resolve_hits_into")
+            _device_tensor(t, width * n, np.dtype(dtype).itemsize, name)
+        _call(*_bounded("rrt_resolve_hits_device", bound_t, self._h, n), _ptr(origins_t), _ptr(dirs_t),
+              _plane_struct(CRaySurface, {**{name: row[0] for name, row in rec.items()}, **out}), _P(_stream(stream)))
 
     # compaction of ray batches and records, and its inverse (rrt.h: rrt_compact_rays, rrt_scatter_rays): the survivors to the front of a batch that keeps its length
     def compact_rays(self, planes: dict, select: str = "hit", flag=None, origins=None, dirs=None, max_t=None, rot=None) -> dict:

@@ -43,7 +43,7 @@ struct rrt_raytracer {
     uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records in use (built.n_chains, or 0 where the shortcut's precondition fails: create_raytracer)
     double upload_ms = 0, hip_init_ms = 0, create_ms = 0;   // set-up stages of rrt_raytracer_create besides built.ms_octree / ms_index; wall time of the whole call
     bool gpu_setup = false;          // scene built on the device (default) or on the host (RRT_FLAG_HOST_SETUP)
-    struct Buf { const void* p = nullptr; size_t bytes = 0; } bufs[16];   // rrt_raytracer_get_buffer
+    struct Buf { const void* p = nullptr; size_t bytes = 0; } bufs[17];   // rrt_raytracer_get_buffer (RRT_BUF_*)
     hipStream_t own_stream = nullptr;   // the stream of the calls that bring results into host memory (frames.cpp: own_stream), set at the first of them
     uint32_t tuned_w = 0, tuned_h = 0, tuned_world = 0;   // frame size the variant below belongs to
     uint32_t size_frames = 0;        // frames rendered at that size so far

@@ -212,7 +212,20 @@ struct AmbientRaysParams {
 };
 static_assert(sizeof(DevScene) + 2 * sizeof(uint64_t) + sizeof(AmbientRaysParams) < 4096, "the arguments of ambient_rays_kernel, the bound of its counted form included, must fit the 4 KB kernel-argument segment");
 
-// Argument of the compaction kernels (compact.hip; rrt.h: rrt_compact_rays_device).  RaySetPtrs mirrors rrt_ray_set: the rays, their bounds and rotations and the
+// Argument of the resolve kernels (render.hip: resolve_hits_kernel; rrt.h: rrt_resolve_hits_device): the rays and the four arrays of kept hits the kernel READS
+// -- [n] each, origins / dirs [n][3]; u and v may be null when only point and / or material are asked for -- the triangle -> slot table of the scene in force
+// (BuiltScene::tri_slot: the lowest slot of every triangle, 0xFFFFFFFF for a triangle outside the tree; here and not in DevScene, whose layout every other kernel's
+// arguments follow) and the seven arrays it writes, in the order and layout of rrt_ray_surface.  A null output is not written; a null `lights` also means that
+// nothing is walked.  tri[i] is used as an index only after tri[i] < n_tris, tri_slot[tri[i]] only after the compare with n_slots.
+struct ResolveParams {
+    const double *origins, *dirs;
+    const double *t, *u, *v; const uint32_t* tri;
+    const uint32_t* tri_slot; uint32_t n_tris, n_slots;
+    uint32_t* albedo; double *point, *normal; uint32_t *material, *lights;
+    double *next_origin, *next_dir;
+};
+
+// Argument of the compaction kernels (compact.hip; rrt.h: rrt_compact_rays_device). RaySetPtrs mirrors rrt_ray_set: the rays, their bounds and rotations and the
 // twelve record arrays of a batch, [n] each with the element widths of rrt.h; a null array of `dst` is not written, and only the arrays `dst` asks for are read of
 // `src` -- besides `material`, which the HIT and MIRROR selections read.  dst.max_t with a null src.max_t: +inf for the survivors.
 struct RaySetPtrs {
@@ -297,7 +310,7 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
 // kept planes).  Defined and instantiated for these four in render.hip.
 template <class Params> int launch_region(const DevScene& s, const Params& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
-// The six per-ray launchers (render.hip: each is launch_per_ray with its kernel): one lane per ray, 64 rays per block; n == 0 launches nothing.
+// The seven per-ray launchers (render.hip: each is launch_per_ray with its kernel): one lane per ray, 64 rays per block; n == 0 launches nothing.
 // d_count: null, or the bound of a counted launch (rrt.h: COUNTED DEVICE FORMS) -- one uint32 in device memory, read by the kernel when it runs; the grid is that of n.
 int launch_ray_colours(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, uint32_t* d_colours, const uint32_t* d_count, void* stream, int walk);
 int launch_intersect(const DevScene& s, uint32_t n, const double* d_origins, const double* d_dirs, const double* d_max_t,
@@ -311,6 +324,9 @@ int launch_surface_rays(const DevScene& s, uint32_t n, const double* d_origins, 
 int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, const uint32_t* d_count, void* stream, int walk);
 // The occlusion mask and the count of open rays of every record's hemisphere fan (render.hip: ambient_rays_kernel); either output of q may be null, not both
 int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, const uint32_t* d_count, void* stream, int walk);
+// The surface record of every kept hit, with no primary walk (render.hip: resolve_hits_kernel); any output of q may be null, not all.  With q.lights the shadow
+// walks run in `walk`; without it the one walk-free instantiation runs, whatever `walk` is, with no dynamic LDS.
+int launch_resolve_hits(const DevScene& s, uint32_t n, const ResolveParams& q, const uint32_t* d_count, void* stream, int walk);
 // Exactness guard for a new eye (scene_build.hip: k_suspects_resident): searches the resident list slots geom[0, n_list_slots) and appends up to
 // RRT_MAX_SUSPECTS + 1 records {push index, suspect} to d_out, counting every find in *d_count (zeroed here, on `stream`).  Not synchronised.
 struct SuspectRecord { uint32_t tri; uint32_t _pad; DevSuspect s; };

@@ -531,6 +531,45 @@ int ambient_rays_from_host(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface&
     return RRT_OK;
 }
 
+// ---- surface records from kept hits (rrt.h: rrt_resolve_hits).  u and v are read for everything but point and material
+bool resolve_reads_uv(const rrt_ray_surface& rec) { return rec.albedo || rec.normal || rec.lights || rec.next_origin || rec.next_dir; }
+// every check, before any GPU work; n == 0 is a no-op for a valid handle and struct
+void check_resolve_hits(const rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const rrt_ray_surface* rec) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (!rec) throw Error{RRT_ERR_INVALID_ARG, "null struct: resolving hits reads t, u, v and tri of the ray surface struct and writes its other arrays"};
+    if (n && !rec->albedo && !rec->point && !rec->normal && !rec->material && !rec->lights && !rec->next_origin && !rec->next_dir)
+        throw Error{RRT_ERR_INVALID_ARG, "no output requested: albedo, point, normal, material, lights, next_origin and next_dir are all null"};
+    if (n && (!origins || !dirs)) throw Error{RRT_ERR_INVALID_ARG, "null ray origins or directions"};
+    if (n && (!rec->t || !rec->tri)) throw Error{RRT_ERR_INVALID_ARG, "null array: t and tri are required"};
+    if (n && resolve_reads_uv(*rec) && (!rec->u || !rec->v)) throw Error{RRT_ERR_INVALID_ARG, "null array: u and v are required for every output but point and material"};
+}
+// the kernels' argument from arrays in device memory, with the triangle -> slot table of the scene in force
+ResolveParams resolve_params(const rrt_raytracer* rt, const double* d_origins, const double* d_dirs, const rrt_ray_surface& d_rec) {
+    const BuiltScene& G = rt->built;
+    return ResolveParams{d_origins, d_dirs, d_rec.t, d_rec.u, d_rec.v, d_rec.tri, G.tri_slot, G.n_tris, G.n_slots_total,
+                         d_rec.albedo, d_rec.point, d_rec.normal, d_rec.material, d_rec.lights, d_rec.next_origin, d_rec.next_dir};
+}
+// Host form (checked): the rays, t, tri and -- where something asked for reads them -- u and v up, one launch on the null stream in the variant of the device
+// forms -- nothing is measured -- the requested outputs down; blocking (with_call_planes).
+int resolve_hits_from_host(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const rrt_ray_surface& rec) {
+    if (n == 0) return RRT_OK;
+    DeviceGuard guard(rt->device);
+    const size_t N = n;
+    const bool uv = resolve_reads_uv(rec);
+    HostPlane pl[] = {plane_up(origins, 24, N), plane_up(dirs, 24, N), plane_up(rec.t, 8, N), plane_up(uv ? rec.u : nullptr, 8, N), plane_up(uv ? rec.v : nullptr, 8, N),
+                      plane_up(rec.tri, 4, N), plane_down(rec.albedo, 4, N), plane_down(rec.point, 24, N), plane_down(rec.normal, 24, N), plane_down(rec.material, 4, N),
+                      plane_down(rec.lights, 4, N), plane_down(rec.next_origin, 24, N), plane_down(rec.next_dir, 24, N)};
+    with_call_planes(pl, [&] {
+        rrt_ray_surface d_rec{};
+        d_rec.t = (double*)pl[2].dev; d_rec.u = (double*)pl[3].dev; d_rec.v = (double*)pl[4].dev; d_rec.tri = (uint32_t*)pl[5].dev;
+        d_rec.albedo = (uint32_t*)pl[6].dev; d_rec.point = (double*)pl[7].dev; d_rec.normal = (double*)pl[8].dev; d_rec.material = (uint32_t*)pl[9].dev;
+        d_rec.lights = (uint32_t*)pl[10].dev; d_rec.next_origin = (double*)pl[11].dev; d_rec.next_dir = (double*)pl[12].dev;
+        const ResolveParams q = resolve_params(rt, (const double*)pl[0].dev, (const double*)pl[1].dev, d_rec);
+        recorded_ray_launch(rt, n, nullptr, [&](int variant) { return launch_resolve_hits(rt->scene, n, q, nullptr, nullptr, variant); });
+    });
+    return RRT_OK;
+}
+
 // ---- compaction of ray batches and records, and its inverse (rrt.h: rrt_compact_rays, rrt_scatter_rays).  These are not ray calls: no timed_launch, no record.
 // The sixteen arrays of an rrt_ray_set in its order, as bytes per entry ...
 constexpr size_t kRaySetArrays = 16, kRaySetMaxT = 2, kRaySetMaterial = 4 + 8;
@@ -1124,6 +1163,26 @@ int rrt_ambient_rays_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_
 int rrt_ambient_rays_device(rrt_raytracer* rt, uint32_t n, const rrt_ray_surface* d_rec, const double* d_rot, const rrt_ambient_samples* samples,
                             const rrt_ray_ambient* d_out, void* stream) {
     return rrt_ambient_rays_counted_device(rt, n, nullptr, d_rec, d_rot, samples, d_out, stream);
+}
+
+int rrt_resolve_hits(rrt_raytracer* rt, uint32_t n, const double* origins, const double* dirs, const rrt_ray_surface* rec) {
+    return guarded([&]() -> int {
+        check_resolve_hits(rt, n, origins, dirs, rec);
+        return resolve_hits_from_host(rt, n, origins, dirs, *rec);
+    });
+}
+
+int rrt_resolve_hits_counted_device(rrt_raytracer* rt, uint32_t n, const uint32_t* d_count, const double* d_origins, const double* d_dirs, const rrt_ray_surface* d_rec,
+                                    void* stream) {
+    return guarded([&]() -> int {
+        check_resolve_hits(rt, n, d_origins, d_dirs, d_rec);
+        return device_ray_launch(rt, n, stream, [&](int variant) {
+            return launch_resolve_hits(rt->scene, n, resolve_params(rt, d_origins, d_dirs, *d_rec), d_count, stream, variant);
+        });
+    });
+}
+int rrt_resolve_hits_device(rrt_raytracer* rt, uint32_t n, const double* d_origins, const double* d_dirs, const rrt_ray_surface* d_rec, void* stream) {
+    return rrt_resolve_hits_counted_device(rt, n, nullptr, d_origins, d_dirs, d_rec, stream);
 }
 
 size_t rrt_compact_scratch_bytes(uint32_t n) { return compact_scratch_bytes(n); }

@@ -120,10 +120,13 @@ void host_build_scene(const Model& M, bool enable_cull, const double origin[3], 
     if (enable_cull) find_origin_suspects(M, origin, CS.pad, sus);
     out.n_suspects = (uint32_t)sus.size();
     if (sus.size() > RRT_MAX_SUSPECTS) sus.clear();   // beyond the cap every ray from the origin runs unfiltered; the list is not read
+    // the triangle -> slot table (scene_build.hpp: tri_slot): slots in ascending order, the first one of a triangle stays -- the lowest, as the GPU set-up's minimum
+    std::vector<uint32_t> tri_slot(M.triangles.size(), kPadSlot);
+    for (size_t s = 0; s < n_slots; s++) { const uint32_t tri = CS.slot_tri[s]; if (tri != kPadSlot && tri_slot[tri] == kPadSlot) tri_slot[tri] = (uint32_t)s; }
 
     const size_t bytes[] = {n_nodes * sizeof(DevNode), n_slots * sizeof(DevTriGeom), n_slots * sizeof(DevTriAttr), CS.supers.size() * sizeof(DevSuper),
                             CS.cboxes.size() * sizeof(DevClusterBox), CS.child_boxes.size() * sizeof(DevClusterBox), CS.tboxes.size() * sizeof(DevClusterBox),
-                            CS.chains.size() * sizeof(DevChain), sus.size() * sizeof(DevSuspect)};
+                            CS.chains.size() * sizeof(DevChain), sus.size() * sizeof(DevSuspect), tri_slot.size() * sizeof(uint32_t)};
     size_t need = 0;
     for (size_t b : bytes) need += b + 512;   // (each buffer starts on a 256-byte boundary and is at least one record long)
     out.alloc = dev_alloc(need);
@@ -132,6 +135,7 @@ void host_build_scene(const Model& M, bool enable_cull, const double origin[3], 
     upload_records(A, out.supers, CS.supers.data(), CS.supers.size()); upload_records(A, out.cboxes, CS.cboxes.data(), CS.cboxes.size());
     upload_records(A, out.child_boxes, CS.child_boxes.data(), CS.child_boxes.size()); upload_records(A, out.tboxes, CS.tboxes.data(), CS.tboxes.size());
     upload_records(A, out.chains, CS.chains.data(), CS.chains.size()); upload_records(A, out.suspects, sus.data(), sus.size());
+    upload_records(A, out.tri_slot, tri_slot.data(), tri_slot.size());
     HIP_TRY(hipDeviceSynchronize());
     out.ms_octree = M.octree_ms;
     out.ms_index = std::chrono::duration<double, std::milli>(t_index1 - t_index0).count();

@@ -18,7 +18,7 @@ namespace {
 using namespace rrt;
 
 // ids of rrt_raytracer_get_buffer (rrt.h: RRT_BUF_*)
-enum { kBufNodes = 0, kBufGeom, kBufAttr, kBufSupers, kBufCboxes, kBufChildBoxes, kBufTboxes, kBufSuspects, kBufOctBox, kBufOctFirstChild, kBufOctTriCount, kBufOctOwnOff, kBufOctOwnIdx, kBufSlotTri, kBufSlotPos, kBufChains, kBufCount };
+enum { kBufNodes = 0, kBufGeom, kBufAttr, kBufSupers, kBufCboxes, kBufChildBoxes, kBufTboxes, kBufSuspects, kBufOctBox, kBufOctFirstChild, kBufOctTriCount, kBufOctOwnOff, kBufOctOwnIdx, kBufSlotTri, kBufSlotPos, kBufChains, kBufTriSlot, kBufCount };
 
 // Textures, the material table and the texture table live in ONE allocation of their own, sized here.
 void alloc_tables(rrt_raytracer* rt, const SceneTables& T) {
@@ -81,7 +81,7 @@ void adopt_built_scene(rrt_raytracer* rt) {
         {kBufOctBox, G.oct_box, (size_t)G.n_nodes * 48}, {kBufOctFirstChild, G.oct_first_child, (size_t)G.n_nodes * 4}, {kBufOctTriCount, G.oct_tri_count, (size_t)G.n_nodes * 4},
         {kBufOctOwnOff, G.oct_own_off, ((size_t)G.n_nodes + 1) * 4}, {kBufOctOwnIdx, G.oct_own_idx, (size_t)G.n_in_tree * 4},
         {kBufSlotTri, G.slot_tri, (size_t)G.n_slots_total * 4}, {kBufSlotPos, G.slot_pos, (size_t)G.n_slots_total * 4},
-        {kBufChains, G.chains, (size_t)G.n_chains * sizeof(DevChain)}};
+        {kBufChains, G.chains, (size_t)G.n_chains * sizeof(DevChain)}, {kBufTriSlot, G.tri_slot, (size_t)G.n_tris * 4}};
     for (const auto& k : kept) { rt->bufs[k.id].p = k.p; rt->bufs[k.id].bytes = k.p ? k.bytes : 0; }
     S.cull_enabled = (o.flags & RRT_FLAG_NO_CULL) ? 0u : 1u;
     S.cull_half_over_limit = S.cull_limit > 0.0f ? 0.5f / S.cull_limit : 0.0f;

@@ -35,7 +35,7 @@
 //   -DRRT_TU=1  the bundle-filter frame, visibility, surface, shade and ambient kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
 //   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility, surface, shade and ambient kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
-//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel, surface_rays_kernel, shade_rays_kernel, ambient_rays_kernel (default scheduler: max-ILP costs scattered rays 17 %).
+//   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel, surface_rays_kernel, shade_rays_kernel, ambient_rays_kernel, resolve_hits_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
 #ifndef RRT_TU
 #define RRT_TU 0
@@ -2135,7 +2135,7 @@ __global__ __launch_bounds__(256) void detile_kernel(uint32_t width, uint32_t he
 #endif   // RRT_TU_FRAME
 
 #if RRT_TU_RAYS
-// The counted forms of the six per-ray kernels (rrt.h: COUNTED DEVICE FORMS).  kCounted adds ONE trailing argument, the bound -- a pack of no or one
+// The counted forms of the seven per-ray kernels (rrt.h: COUNTED DEVICE FORMS).  kCounted adds ONE trailing argument, the bound -- a pack of no or one
 // `const uint32_t*`, so the uncounted instantiation keeps the argument list it had -- and these two lines in front of the body: the length of the batch becomes
 // min(n, *count), one scalar load, and a block whose first entry lies at or beyond it leaves before it touches LDS, a barrier or memory.  What follows is the body
 // of the uncounted kernel with that length: lanes of a partly live wave at or beyond it are the lanes "beyond the batch".  The bound is only ever read.
@@ -2391,6 +2391,82 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_rays_kernel(const D
     if (Q.occluded) Q.occluded[i] = mask;
     if (Q.open) Q.open[i] = n_samples - (uint32_t)__popc(mask);                          // (a miss: mask 0, every ray open -- the rule of ambient_kernel's grey)
 }
+// The surface record of kept hits, with no primary walk (rrt.h: rrt_resolve_hits_device): what surface_rays_kernel stores for a ray, from the t, u, v and tri an
+// earlier walk of that ray left -- intersect_kernel's, surface_rays_kernel's or a frame's visibility planes -- behind the front end of the per-ray kernels.  A
+// lane loads its entry; it is a hit iff tri < n_tris and the triangle has a slot (Q.tri_slot: the lowest of its slots, which all hold the same attribute
+// bytes): tri is the only caller value used as an index, and only after that compare.  Then surface_body's hit block on the kept values -- p = o + d * t
+// (raytracer.rs:39), surface_of_hit at (u, v) -- and, with Q.lights, surface_body's loop FROM THE POINT WHERE `shadow` BECOMES TRUE, restated (sharing it would
+// split surface_body, whose register allocation follows its text: see there): the light list up to the next point light, one light per turn, the shadow rays of
+// all hit lanes with the arguments trace_colour gives a shadow walk (any_ok, filters on, not one_origin).  ONE call site of the walk.  A wave with no hit walks
+// nothing; no lane leaves before the last walk, the stores come after the loop, lanes beyond the batch store nothing.
+// The eleven pointers are kernel arguments, so each test on them is wave-uniform: without u and v (point and / or material alone) no texel and no normal;
+// kWalk == kNoWalk is the ONE instantiation of a launch without `lights`, whatever variant the raytracer runs: no walk is compiled in, it declares no dynamic
+// LDS and has no four-waves cap -- a gather of one 128-byte attribute record and up to two texels per hit.  The walking ones are capped like surface_rays_kernel.
+// Registers, scratch and occupancy are recorded, not tuned: profiles/resolve_kernel_resources.txt.
+constexpr int kNoWalk = -1;
+template <int kWalk, bool kCounted = false, class... Count>
+__global__ __launch_bounds__(64, kWalk == kNoWalk ? 1 : kWavesPerSimd) void resolve_hits_kernel(const DevScene S, uint32_t n_rays, const ResolveParams Q, Count... count) {
+    RRT_COUNTED_FRONT(n_rays)
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    const bool ok = i < n_rays;
+    const size_t j = 3 * (size_t)i;
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const bool want_uv = Q.albedo || Q.normal || Q.lights || Q.next_origin || Q.next_dir;   // what needs the texel or the normal, and with them u and v
+    // ---- the lane's entry
+    bool found = false;
+    uint32_t slot = 0;
+    if (ok) {
+        const uint32_t tri = Q.tri[i];
+        if (tri < Q.n_tris) { slot = Q.tri_slot[tri]; found = slot < Q.n_slots; }        // (0xFFFFFFFF, a miss or a dead entry, and anything else beyond the scene: a miss)
+    }
+    V3 d = mk(0, 0, 1), p = mk(0, 0, 0), n = mk(0, 0, 0);
+    uint32_t mat = kNone, mask = 0, col = 0x00FFFFFFu;
+    if (found) {
+        // --- hit: raytracer.rs:39-57, surface_body's hit block
+        const V3 o = ld3(Q.origins + j);
+        d = ld3(Q.dirs + j);
+        p = o + d * Q.t[i];                                                              // raytracer.rs:39
+        if (want_uv) surface_of_hit(S, slot, Q.u[i], Q.v[i], mat, col, n);
+        else if (Q.material) mat = S.attr[slot].mat;
+    }
+    if constexpr (kWalk != kNoWalk) {
+        extern __shared__ __attribute__((aligned(16))) char lds[];
+        const Stack stk{lds + kParkBytes, threadIdx.x};
+        if (Q.lights && __any(found)) {                                                  // no hit in the wave: nothing to ask the lights
+            const uint32_t n_lights = S.n_lights;
+            uint32_t li = 0;
+            for (;;) {
+                // the light list up to the next point light (raytracer.rs:205-255): Ambient and Directional lights reach every hit
+                while (li < n_lights && S.lights[li].kind != 1u) { if (found) mask |= 1u << li; li++; }
+                if (li >= n_lights) break;
+                const V3 dir = ld3(S.lights[li].v) - p;                                  // the shadow ray, raytracer.rs:164-188, as trace_colour forms it
+                const V3 ro = p + n * S.surface_offset;
+                double wt; uint32_t wslot;
+                walk<kWalk, true>(PROF_ARG S, stk, found, true, true, false, ro, dir, length(dir), wt, wslot);
+                if (found && wslot == kNone) mask |= 1u << li;                           // triangle_exists_between_points says "lit" for None, raytracer.rs:181-187
+                li++;
+            }
+        }
+    }
+    BAND_FLUSH();
+    if (!ok) return;
+    if (Q.albedo) Q.albedo[i] = col;
+    if (Q.point) { Q.point[j] = p.x; Q.point[j + 1] = p.y; Q.point[j + 2] = p.z; }
+    if (Q.normal) { Q.normal[j] = n.x; Q.normal[j + 1] = n.y; Q.normal[j + 2] = n.z; }
+    if (Q.material) Q.material[i] = mat;
+    if (Q.lights) Q.lights[i] = mask;
+    if (Q.next_origin) {
+        const V3 q = found ? p + n * S.surface_offset : mk(0, 0, 0);                     // raytracer.rs:82
+        Q.next_origin[j] = q.x; Q.next_origin[j + 1] = q.y; Q.next_origin[j + 2] = q.z;
+    }
+    if (Q.next_dir) {
+        V3 r = mk(0, 0, 0);
+        if (found) { const double d_dot_n = dot(d, n); r = normalised(d - (n * 2.0) * d_dot_n); }   // raytracer.rs:78-79, as trace_colour forms it
+        Q.next_dir[j] = r.x; Q.next_dir[j + 1] = r.y; Q.next_dir[j + 2] = r.z;
+    }
+}
 #undef RRT_COUNTED_FRONT
 #endif   // RRT_TU_RAYS
 
@@ -2579,6 +2655,16 @@ int launch_shade_rays(const DevScene& s, uint32_t n, const ShadeRaysParams& q, c
 
 int launch_ambient_rays(const DevScene& s, uint32_t n, const AmbientRaysParams& q, const uint32_t* d_count, void* stream, int walk) {
     return launch_per_ray(s, n, d_count, stream, walk, RRT_PER_RAY_KERNEL(ambient_rays_kernel), q);
+}
+
+// (without q.lights nothing is walked: the one walk-free instantiation, same grid, no walk stack in dynamic LDS -- launch_per_ray's launch with those two differences)
+int launch_resolve_hits(const DevScene& s, uint32_t n, const ResolveParams& q, const uint32_t* d_count, void* stream, int walk) {
+    if (q.lights) return launch_per_ray(s, n, d_count, stream, walk, RRT_PER_RAY_KERNEL(resolve_hits_kernel), q);
+    if (n == 0) return 0;
+    const dim3 grid((n + 63) / 64);
+    if (d_count) hipLaunchKernelGGL((&resolve_hits_kernel<kNoWalk, true, const uint32_t*>), grid, dim3(64), 0, (hipStream_t)stream, s, n, q, d_count);
+    else hipLaunchKernelGGL((&resolve_hits_kernel<kNoWalk>), grid, dim3(64), 0, (hipStream_t)stream, s, n, q);
+    return (int)hipGetLastError();
 }
 #undef RRT_PER_RAY_KERNEL
 #endif   // RRT_TU_RAYS

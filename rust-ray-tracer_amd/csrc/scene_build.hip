@@ -425,6 +425,16 @@ __global__ void __launch_bounds__(kBlock) k_idx_slots(Idx X) {   // per slot: ge
     }
 }
 
+// The triangle -> slot table (scene_build.hpp: BuiltScene::tri_slot), one thread per slot over a table filled with 0xFFFFFFFF: the LOWEST slot of every triangle.
+// A triangle can own two slots (an inline leaf's list slot and its dense one, k_idx_leaf_slots); a minimum does not depend on the order the slots arrive in, so
+// the table holds the same bits on every run and equals the host set-up's.  Arguments of its own: Idx, the argument of the kernels around it, stays as it is.
+__global__ void __launch_bounds__(kBlock) k_tri_slot(const uint32_t* __restrict__ slot_tri, uint32_t n_slots_total, uint32_t n_tris, uint32_t* __restrict__ tri_slot) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_slots_total) return;
+    const uint32_t tri = slot_tri[s];
+    if (tri < n_tris) atomicMin(&tri_slot[tri], s);             // (kNone: a padding slot)
+}
+
 __global__ void __launch_bounds__(kBlock) k_idx_clusters(Idx X) {   // per cluster of 8 slots: its padded box; the node's own bounds
     const uint32_t c = blockIdx.x * kBlock + threadIdx.x, n_cl = X.n_list_slots >> 3;
     if (c >= n_cl + 8u) return;
@@ -857,6 +867,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
         need += (size_t)n_nodes * sizeof(DevNode) + (size_t)(n_slots_total + 1) * (sizeof(DevTriGeom) + sizeof(DevTriAttr));
         need += ((size_t)n_sup + 1 + n_cl + 8 + n_nodes + 8 + n_list_slots + 8) * 32 + (RRT_MAX_SUSPECTS + 2) * sizeof(DevSuspect);
         need += oct_bytes + (size_t)(n_slots_total + 8) * 8 + 17 * 256 + ((size_t)n_chains + 1) * sizeof(DevChain);
+        need += ((size_t)n + 1) * 4 + 256;                                // tri_slot
         if (keep && keep->scene.buf.h && keep->scene.bytes >= need) { out.alloc = std::move(keep->scene.buf); out.alloc_bytes = keep->scene.bytes; keep->scene.bytes = 0; }
         else { if (keep) keep->scene.release(); out.alloc = dev_alloc(need); out.alloc_bytes = need; }
         A3.base = static_cast<char*>(out.alloc.h); A3.cap = need;
@@ -868,6 +879,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     out.oct_own_off = A3.take<uint32_t>(n_nodes + 1); out.oct_own_idx = A3.take<uint32_t>(n_in);
     out.slot_tri = A3.take<uint32_t>(n_slots_total + 8); out.slot_pos = A3.take<uint32_t>(n_slots_total + 8);
     out.chains = A3.take<DevChain>(n_chains); X.chains = out.chains;
+    out.tri_slot = A3.take<uint32_t>(n);
     HIP_TRY(hipMemcpyAsync(out.oct_box, R.fbox, sizeof(double) * 6 * n_nodes, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(out.oct_first_child, R.ffc, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(out.oct_tri_count, R.ftc, 4 * (size_t)n_nodes, hipMemcpyDeviceToDevice, st));
@@ -897,6 +909,10 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
         hipLaunchKernelGGL(k_idx_scatter, dim3(grid_for(n_in)), dim3(kBlock), 0, st, X, flip);
     }
     hipLaunchKernelGGL(k_idx_leaf_slots, dim3(grid_for(n_nodes)), dim3(kBlock), 0, st, X);
+    if (n) {                                                           // slot_tri is complete: its inverse
+        HIP_TRY(hipMemsetAsync(out.tri_slot, 0xFF, 4 * (size_t)n, st));
+        if (n_slots_total) hipLaunchKernelGGL(k_tri_slot, dim3(grid_for(n_slots_total)), dim3(kBlock), 0, st, out.slot_tri, n_slots_total, n, out.tri_slot);
+    }
     if (attr_task) {                                                   // the records are needed from here on (k_idx_slots, k_suspects)
         attr_task->wait();
         HIP_TRY(hipStreamWaitEvent(st, ev_attr, 0));

@@ -27,6 +27,8 @@ struct BuiltScene {
     double* oct_box = nullptr;          // [n_nodes][6] lo xyz, hi xyz
     uint32_t* oct_first_child = nullptr, *oct_tri_count = nullptr, *oct_own_off = nullptr /* n_nodes + 1 */, *oct_own_idx = nullptr /* n_in_tree */;
     uint32_t* slot_tri = nullptr, *slot_pos = nullptr;   // per device slot (tests)
+    uint32_t* tri_slot = nullptr;       // [n_tris]: the LOWEST slot whose attr.orig is the triangle -- an inline leaf's triangle owns two (clusters.cpp) --, 0xFFFFFFFF for a
+                                        // triangle outside the tree.  The inverse of attr.orig that rrt_resolve_hits reads; both builders keep it
     uint32_t n_tris = 0, n_nodes = 0, n_in_tree = 0, n_list_slots = 0, n_slots_total = 0, n_sup_records = 0, n_clusters = 0, max_depth = 0;
     uint32_t has_groups = 0, inline_leaves = 0, bounds_plain = 1, n_suspects = 0, all_inside_root = 0;   // all_inside_root: no triangle of the tree pokes out of the root box
     double scene_magnitude = 0, pad = 0;
@@ -66,7 +68,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n_tris, const Box& root, boo
 // hipError_t cast to int.
 int launch_count_bad_materials(const uint32_t* d_mat, uint32_t n, uint32_t n_mats, uint32_t* d_count, void* stream);
 
-// The same scene from the model's host octree (host_tree(m)).  Keeps no octree, slot_tri or slot_pos on the device.  Returns after a
+// The same scene from the model's host octree (host_tree(m)).  Keeps no octree, slot_tri or slot_pos on the device (tri_slot it keeps: a kernel reads it).  Returns after a
 // hipDeviceSynchronize: the host arrays it uploaded from are gone.  Same exceptions.
 void host_build_scene(const Model& m, bool enable_cull, const double origin[3], BuiltScene& out);
 
