@@ -1,6 +1,6 @@
 // api.cpp -- the process-wide part of the extern "C" surface declared in include/rrt.h (status strings, error detail, device count, the warm-up
 // thread) and the model API.  No CPU rendering path exists in this library; every compute entry point launches the HIP kernels of render.hip
-// (raytracer.cpp: scene set-up; frames.cpp: launches; multi.cpp: N GPUs).
+// (raytracer.cpp: scene set-up; frames.cpp, regions.cpp, ray_queries.cpp, ray_batches.cpp: launches; multi.cpp: N GPUs).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>

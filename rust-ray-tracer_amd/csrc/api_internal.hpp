@@ -1,6 +1,6 @@
 // api_internal.hpp -- what the units behind include/rrt.h share: the two handle types, the one place that turns exceptions into status codes, and
 // the few helpers more than one of them needs.  api.cpp: models and process-wide calls; raytracer.cpp: creation and scene set-up; scene_update.cpp: lights, materials and
-// triangles of a living raytracer; frames.cpp: every launch; multi.cpp: N GPUs of one node.
+// triangles of a living raytracer; frames.cpp, regions.cpp, ray_queries.cpp, ray_batches.cpp: every launch (launches.hpp is what those four share); multi.cpp: N GPUs of one node.
 #pragma once
 #include <cstdint>
 #include <new>
@@ -34,21 +34,21 @@ struct rrt_raytracer {
     bool stats_pending = false;
     bool launched = false;           // some launch has been recorded in `stats`
     int walk = 0;                    // traversal variant used by this raytracer's frame launches: 0 lane filter, 1 bundle filter, 2 ray walk (see rrt.h)
-    int walk_rays = -1;              // ... and by its per-ray entry points (rrt_get_ray_colours / rrt_intersect_rays / rrt_occluded_rays and their _device forms): -1 = not measured yet (frames.cpp: measure_rays)
+    int walk_rays = -1;              // ... and by its per-ray entry points (rrt_get_ray_colours / rrt_intersect_rays / rrt_occluded_rays and their _device forms): -1 = not measured yet (launches.hpp: measure_rays)
     bool variant_forced = false;
     rrt::KeptBuf host_fb;            // device framebuffer kept between rrt_render / rrt_render_progressive calls (host-framebuffer entry points), grown when a larger frame comes
     rrt::KeptBuf vis_buf;            // device planes kept between the host forms of the region calls: rrt_render_visibility, rrt_pick, rrt_render_surface,
-                                     // rrt_shade_surface, rrt_ambient_surface (frames.cpp: with_kept_planes carves it anew in every call; the per-ray host forms keep nothing: with_call_planes)
+                                     // rrt_shade_surface, rrt_ambient_surface (launches.hpp: with_kept_planes carves it anew in every call; the per-ray host forms keep nothing: with_call_planes)
     rrt::KeptBuf tune_buf;           // outputs of the measurement launches of rrt_tune_rays_device
     uint32_t n_chains = 0, n_chain_nodes = 0;   // chain records in use (built.n_chains, or 0 where the shortcut's precondition fails: create_raytracer)
     double upload_ms = 0, hip_init_ms = 0, create_ms = 0;   // set-up stages of rrt_raytracer_create besides built.ms_octree / ms_index; wall time of the whole call
     bool gpu_setup = false;          // scene built on the device (default) or on the host (RRT_FLAG_HOST_SETUP)
     struct Buf { const void* p = nullptr; size_t bytes = 0; } bufs[17];   // rrt_raytracer_get_buffer (RRT_BUF_*)
-    hipStream_t own_stream = nullptr;   // the stream of the calls that bring results into host memory (frames.cpp: own_stream), set at the first of them
+    hipStream_t own_stream = nullptr;   // the stream of the calls that bring results into host memory (launches.hpp: own_stream), set at the first of them
     uint32_t tuned_w = 0, tuned_h = 0, tuned_world = 0;   // frame size the variant below belongs to
     uint32_t size_frames = 0;        // frames rendered at that size so far
     bool size_measured = false;      // ... and whether the variants have been timed on it (second frame of a size)
-    // Camera (rrt_raytracer_set_camera, camera.cpp).  The eye is scene.origin; the basis goes into every FrameParams (frames.cpp: frame_params).
+    // Camera (rrt_raytracer_set_camera, camera.cpp).  The eye is scene.origin; the basis goes into every FrameParams (launches.hpp: frame_params).
     rrt_camera cam{};                // pose in force
     rrt_vec3 origin0{};              // the eye this raytracer was created with (the creation pose)
     // The exactness guard of an eye other than the creation one: list, counter and search records in an allocation of the raytracer's own, made when the

@@ -1,5 +1,5 @@
 // camera.cpp -- rrt_raytracer_set_camera / _get_camera and rrt_camera_look_at: the pose a raytracer's frames are taken from.  The view basis is only
-// stored (frames.cpp puts it into every FrameParams).  The eye is DevScene::origin, and the one thing besides it that depends on the eye is the index's
+// stored (frame_params, frames.cpp, puts it into every FrameParams).  The eye is DevScene::origin, and the one thing besides it that depends on the eye is the index's
 // exactness guard: the list of triangles whose plane passes through the eye.  The build computed it for the creation eye from the
 // triangle array, which is gone; for a new eye it is searched again in the resident device records (scene_build.hip: k_suspects_resident).
 #include <algorithm>

@@ -4,6 +4,7 @@
 
 #include "hip_check.hpp"
 #include "model.hpp"
+#include "slots.hpp"
 
 namespace rrt {
 
@@ -31,9 +32,7 @@ struct KeptBuf {
 };
 
 // Scene buffers are carved out of ONE device allocation (a hipMalloc per buffer costs milliseconds each: 15 of them were most of the teapot's
-// upload time).  Every buffer starts on a 256-byte boundary; an empty one still gets an address of its own.  The arena does not own `base`.
-// what a buffer of `bytes` bytes occupies: a whole number of 256-byte slots
-constexpr size_t slot_bytes(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// upload time).  Every buffer starts on a 256-byte boundary (slots.hpp: slot_bytes); an empty one still gets an address of its own.  The arena does not own `base`.
 struct DevArena {
     char* base = nullptr; size_t cap = 0, used = 0;
     template <class T> T* take(size_t count) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/rrt.h"
+#include "error.hpp"
 
 namespace rrt {
 
@@ -90,8 +91,7 @@ const FlatOctree& host_tree(const Model& m);
 // octree.cpp
 void build_octree(const Triangle* tris, size_t n_tris, const Box& root, FlatOctree& out);
 
-// obj_loader.cpp -- throws rrt::Error
-struct Error { int status; std::string detail; };
+// obj_loader.cpp -- throws rrt::Error (error.hpp)
 void load_obj(const std::string& obj_path, const Box& root, Model& out);
 
 // image_decode.cpp -- native-layout bytes as `DynamicImage::as_bytes()` would hand out (utils.rs:353);

@@ -35,7 +35,7 @@ void rebuild(rrt_raytracer* rt, const TriSource& src, uint32_t n_tris, const Box
     adopt_built_scene(rt);
     rt->upload_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count() - rt->built.ms_octree - rt->built.ms_index;
     // What was measured on the old scene is forgotten: the variant kept for a frame size with that size's frame counter, and the variant kept for
-    // per-ray calls.  A forced variant stays; the first-frame rule (frames.cpp) then sees the new triangle count.
+    // per-ray calls.  A forced variant stays; the first-frame rule (frames.cpp: first_frame_variant) then sees the new triangle count.
     rt->tuned_w = rt->tuned_h = rt->tuned_world = 0; rt->size_frames = 0; rt->size_measured = false;
     rt->walk_rays = -1;
     if (!rt->variant_forced) rt->walk = 0;

@@ -1,5 +1,5 @@
 // staging.hpp -- process-wide transfer infrastructure: one ring of page-locked chunks and two non-blocking streams per device, shared by the
-// scene set-up's uploads (scene_build.hip, raytracer.cpp) and by every download of a frame or of its visibility planes into host memory (frames.cpp).  A failed HIP call throws HipFail.
+// scene set-up's uploads (scene_build.hip, raytracer.cpp) and by every download of a frame or of its planes into host memory (frames.cpp; launches.hpp: with_kept_planes).  A failed HIP call throws HipFail.
 #pragma once
 #include <cstddef>
 

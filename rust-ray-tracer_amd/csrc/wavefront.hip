@@ -1,6 +1,6 @@
 // wavefront.hip -- the two ends of the per-ray pipeline (rrt.h: rrt_frame_rays_device, rrt_mix_rays_device, rrt_mix_pixels_device): the primary rays of a frame as a
 // ray batch, one level of the reflection chain's unwind, and Color::mix of the sub-sample colours into pixels.  The stages between them are render.hip's per-ray
-// kernels, compact.hip and sort.hip; frames.cpp strings all of them into rrt_render_wavefront_device.
+// kernels, compact.hip and sort.hip; ray_batches.cpp strings all of them into rrt_render_wavefront_device.
 //
 // Three bandwidth kernels, one lane per entry (mix_pixels_kernel: per pixel), no LDS, no atomics, no block that waits on another: the same bits on every run.
 // They live here and not in render.hip because a helper shared with the frame kernels changes their register allocation (render.hip, above region_lane); the dozen

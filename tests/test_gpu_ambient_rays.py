@@ -283,6 +283,9 @@ def test_the_device_form(rrt, teapot, kept, mode):
         assert (out[other].cpu().numpy() == SENTINEL).all(), f"{asked} alone: {other} was written"
         ref = want if asked == "occluded" else open_of(want, hit, 8)
         assert_same_array(out[asked].cpu().numpy()[G:-G].view(np.uint32), ref, f"walk {mode}: {asked} alone, device form")
+        one = rt.ambient_rays(rec, T8, T8_MAX_T, outputs=(asked,))                  # the host form with ONE output asked for and the other NULL, against the device form's
+        assert set(one) == {asked}
+        assert_same_array(one[asked], out[asked].cpu().numpy()[G:-G].view(np.uint32), f"walk {mode}: {asked} alone, host form vs device form")
 
 
 # ------------------------------------------------------------------ 6

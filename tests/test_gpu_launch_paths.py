@@ -1,4 +1,4 @@
-"""The paths every entry point of frames.cpp shares -- the timed launch and its record in rrt_stats, the device buffers a raytracer keeps between calls, the
+"""The paths every entry point of frames.cpp, regions.cpp, ray_queries.cpp and ray_batches.cpp shares (launches.hpp) -- the timed launch and its record in rrt_stats, the device buffers a raytracer keeps between calls, the
 way back into page-locked or pageable host memory, and the measurement of the variants on a rank's share -- on the GPU, where nothing else pins them.
 
 Scene: assets/model.obj under the default lights.  The traced pixels of a W x H frame are the columns [0, 2*(W/2)) of the rows [H - 2*(H/2) + 1, H)

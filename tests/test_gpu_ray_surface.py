@@ -274,6 +274,15 @@ def test_the_device_form(rrt, room):
     rt.surface_rays_into(o_t, d_t, out, torch.tensor(bound, device="cuda"), stream=stream.cuda_stream)
     stream.synchronize()
     assert_arrays_equal(to_host(out, n), rt.surface_rays(O, d, bound), NAMES, "surface_rays_into, twelve outputs and max_t")
+    # the host form with ONE array asked for and eleven NULL, against the device form's twelve
+    out = device_arrays(torch, n)
+    rt.surface_rays_into(o_t, d_t, out, stream=stream.cuda_stream)
+    stream.synchronize()
+    twelve = to_host(out, n)
+    for name in NAMES:
+        one = rt.surface_rays(O, d, planes=(name,))
+        assert set(one) == {name}
+        assert_arrays_equal(one, twelve, (name,), f"array {name} alone, host form vs surface_rays_into")
     # the chain of part 4 on the device, joined by a boolean index and by a max_t of 0.0 for the dead rays
     host_cols, host_alive = follow_chain(HostChain(rt, O, d), A, lights)
     for compact in (True, False):

@@ -304,6 +304,10 @@ def test_without_colour_and_with_a_mask_only_what_is_asked_is_written(rrt, room,
                 got = out[name].cpu().numpy().view(OUT_DTYPES[name]).reshape(want[name].shape)
                 if name in asked:
                     assert same(got, want[name]), f"asked for {asked}, mask {masked}: {name} differs from the host form's"
+                    if len(asked) == 1:                                                    # the host form with ONE output asked for and two NULL, against the device form's
+                        one = rt.shade_rays(d, planes if masked else without_mask(planes), outputs=asked)
+                        assert set(one) == set(asked)
+                        assert same(one[name], got), f"{name} alone, mask {masked}: the host form differs from the device form"
                 else:
                     assert (out[name].cpu().numpy() == np.array(OUT_SENTINEL[name]).astype(out[name].cpu().numpy().dtype)).all(), f"asked for {asked}: {name} was written"
 

@@ -205,6 +205,10 @@ def test_a_region_is_a_slice_of_the_frame(rrt, frame3, region):
         inside = a[G:-G]
         assert not (inside == sentinel).any(), f"region {region}: {int((inside == sentinel).sum())} elements of plane {name} were not written"
         assert same(inside.view(want[name].dtype).reshape(want[name].shape), want[name]), f"region {region}: plane {name} of surface_into differs from the host form"
+        if name in rrt.SURFACE_PLANES:                                             # the host form with ONE surface plane asked for and the rest NULL, against the device form's
+            one = rt.surface(W3, H3, region=region, planes=(name,))
+            assert set(one) == {name}
+            assert same(one[name], inside.view(want[name].dtype).reshape(want[name].shape)), f"region {region}: plane {name} alone, host form vs surface_into"
 
 
 # ------------------------------------------------------------------ 5

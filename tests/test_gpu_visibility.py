@@ -235,6 +235,10 @@ def test_device_tensors_equal_the_host_form(rrt, frame3):
         torch.cuda.synchronize()
         got = {n: t.cpu().numpy().view(full[n].dtype) for n, t in tensors.items()}
         assert_planes_equal(got, {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, full.keys(), f"visibility_into, region {region}")
+    for name in kinds:                                                             # the host form with ONE plane asked for and five NULL, against the device form's
+        one = rt.visibility(W3, H3, region=region, planes=(name,))
+        assert set(one) == {name}
+        assert_planes_equal(one, got, (name,), f"region {region}: plane {name} alone, host form vs visibility_into")
 
 
 @pytest.mark.parametrize("frames_before", (0, 1, 2))

@@ -1,4 +1,4 @@
-"""Developer tool: kernel time of the three traversal variants over scenes x frame sizes: the evidence behind the first-frame rule of frames.cpp (tune_variant).
+"""Developer tool: kernel time of the three traversal variants over scenes x frame sizes: the evidence behind the first-frame rule of frames.cpp (first_frame_variant, under tune_variant).
    python tools/variant_sweep.py [out.json]"""
 import importlib, json, os, sys
 import numpy as np
