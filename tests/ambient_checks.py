@@ -94,10 +94,9 @@ def grey_of(occluded, material, n_mats, n, traced):
     return np.where(traced, g * 0x010101, 0).astype(np.uint32)
 
 
-def assert_same_plane(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype}{got.shape} vs {want.dtype}{want.shape}"
-    bad = got != want
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} elements differ, first at {np.argwhere(bad)[0].tolist()}: {int(got[bad][0]):#010x} vs {int(want[bad][0]):#010x}"
+def freeze(*arrays):
+    for a in arrays:
+        a.setflags(write=False)
 
 
 def crop(planes, region):

@@ -1,15 +1,19 @@
 """Helpers of the tests of ambient occlusion for ray records (include/rrt.h: rrt_ambient_rays): the hemisphere fan of a record set, restated in numpy from the
-arrays of rt.surface_rays() in the contract's operation order -- with and without a rotation per record -- the masks a shadow query gives for it, and `open`.
+arrays of rt.surface_rays() in the contract's operation order -- with and without a rotation per record -- the masks a shadow query gives for it, and `open`; and the level-1 record set of the teapot frame that the
+ambient, compaction and sort tests share (level1, and the fixture kept_records).
 
-Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  It holds no fixtures.
+Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  Its one fixture, kept_records, has module scope and requests
+scenes.teapot_arrays: a test module imports both by name.
 
 numpy's elementwise +, -, *, / and sqrt are IEEE operations, each rounded once and never fused; sums are written with the contract's parentheses, and cross,
 length and normalised are those of surface_checks.py (engine.rs:85-103).  The class has the shape of ambient_checks.Rays: hit, O, D, fallback, flat(), plane().
 """
 import numpy as np
+import pytest
 
-from ambient_checks import popcount
+from ambient_checks import H, T8, T8_MAX_T, W, freeze, popcount
 from gpu_checks import POOL
+from scenes import CREATION, rays_of
 from surface_checks import cross, length, normalised
 
 INPUTS = ("point", "normal", "material")          # what rrt_ambient_rays reads of an rrt_ray_surface
@@ -88,13 +92,31 @@ def mask_figures(mask, fan):
     return float(popcount(m).sum()) / (m.size * fan.n), per
 
 
-def assert_same_array(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype}{got.shape} vs {want.dtype}{want.shape}"
-    bad = got != want
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} elements differ, first at {np.argwhere(bad)[0].tolist()}: {int(got[bad][0]):#010x} vs {int(want[bad][0]):#010x}"
-
-
 def rows(rec, sel):
     """The records `sel` (a slice, indices or a bool array) of the three input arrays, contiguous."""
     return {n: np.ascontiguousarray(np.asarray(rec[n])[sel]) for n in INPUTS}
+
+
+# ------------------------------------------------------------------ the record sets the tests share
+def level1(rt, cam, w, h):
+    """(level-0 arrays of the w x h frame's primary rays, the level-1 records of ALL its level-0 hits: INPUTS of rrt_surface_rays on their next_origin / next_dir)"""
+    O, D = rays_of(cam, w, h)
+    l0 = rt.surface_rays(O, D, planes=("hit", "next_origin", "next_dir"))
+    h0 = l0["hit"].astype(bool)
+    rec = rt.surface_rays(np.ascontiguousarray(l0["next_origin"][h0]), np.ascontiguousarray(l0["next_dir"][h0]), planes=INPUTS)
+    freeze(*rec.values())
+    return l0, rec
+
+
+@pytest.fixture(scope="module")
+def kept_records(rrt, teapot, teapot_arrays):
+    """The level-1 records of the teapot's 64 x 48 frame at the creation pose and what the tests share of them (read-only): the raytracer in the default mode, the
+    level-0 arrays, the level-1 records, ROT, the fans without and with it, and the masks of T8 at max_t 2.0 by rt.occluded for both."""
+    rt = rrt.RayTracer(teapot, rrt.default_lights())
+    l0, rec = level1(rt, CREATION, W, H)
+    n_mats = len(teapot_arrays["materials"])
+    rot = standard_rot(len(rec["material"]))
+    fans = {False: Fan(rec, n_mats, T8), True: Fan(rec, n_mats, T8, rot)}
+    want = {r: by_shadow_query(rt, fans[r], T8_MAX_T) for r in (False, True)}
+    freeze(*want.values(), *l0.values())
+    return dict(rt=rt, l0=l0, rec=rec, rot=rot, fans=fans, want=want, n_mats=n_mats)

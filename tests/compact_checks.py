@@ -1,11 +1,14 @@
 """Helpers of the tests of the compaction of ray batches and records (include/rrt.h: rrt_compact_rays, rrt_scatter_rays): the contract restated in numpy -- the
-stable partition (np.flatnonzero of the selection), the gather, the table of dead values, the scatter -- and byte-for-byte comparisons.
+stable partition (np.flatnonzero of the selection), the gather, the table of dead values, the scatter -- compared bit for bit (bitwise.py), and the device
+buffers the compaction, sort and counted tests pass to the library: to_device, Guarded outputs between guard elements, ceil_div, mixed_waves.
 
 Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  It holds no fixtures.
 
-Doubles are compared through a uint64 view: the tail's max_t is NaN, and NaN payloads and -0.0 have to survive a gather.
+Doubles are compared through their integer bits: the tail's max_t is NaN, and NaN payloads and -0.0 have to survive a gather.
 """
 import numpy as np
+
+from bitwise import assert_same_bits, bits
 
 DEAD_INDEX = 0xFFFFFFFF
 SELECTS = ("hit", "mirror", "flag")                # RRT_SELECT_HIT, RRT_SELECT_MIRROR, RRT_SELECT_FLAG, in their order
@@ -23,20 +26,9 @@ RECORD_NAMES = NAMES[4:]                           # the twelve arrays of rrt_ra
 ELEM_BYTES = {name: np.dtype(dtype).itemsize * width for name, (dtype, width, _) in ARRAYS.items()}
 OFFSETS = {name: 8 * k for k, name in enumerate(NAMES)}   # of the pointer in rrt_ray_set (rec starts at 32)
 NAN_BITS = 0x7FF8000000000000                      # the tail's max_t
-
-
-def bits(a):
-    """An array as unsigned integers of its item size, for comparisons that see NaN payloads and the sign of zero."""
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def assert_same_bytes(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype}{got.shape} vs {want.dtype}{want.shape}"
-    g, w = bits(got), bits(want)
-    bad = g != w
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} elements differ, first at {np.argwhere(bad)[0].tolist()}: {int(g[bad][0]):#x} vs {int(w[bad][0]):#x}"
+G = 64                                             # guard elements on both sides of a device output
+# the batch sizes of the scratch-size tests of compaction and sorting: the edge sizes of tests/test_gpu_compact.py, and 2^16, 2^20
+SCRATCH_SIZES = (1, 2, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2047, 2049, 4097, 70001, 2 ** 16, 2 ** 20, 2 ** 20 + 4097)
 
 
 def selection(select, n_mats=None, material=None, kr=None, flag=None):
@@ -88,7 +80,7 @@ def assert_compacted(got, want, what):
     assert int(got["count"]) == int(want["count"]), f"{what}: count {int(got['count'])} vs {int(want['count'])}"
     for name in want:
         if name != "count":
-            assert_same_bytes(np.asarray(got[name]).reshape(np.asarray(want[name]).shape), want[name], f"{what}: {name}")
+            assert_same_bits(np.asarray(got[name]).reshape(np.asarray(want[name]).shape), want[name], f"{what}: {name}")
 
 
 def scattered(index, src, dst):
@@ -110,3 +102,42 @@ def flag_patterns(n, seed=20240607):
     last[-1] = 7                                    # any non-zero byte selects
     half = (np.random.default_rng(seed + n).random(n) < 0.5).astype(np.uint8)
     return {"all 0": np.zeros(n, np.uint8), "all 1": np.ones(n, np.uint8), "alternating": alt, "only the first": first, "only the last": last, "a random half": half}
+
+
+# ------------------------------------------------------------------ device buffers (torch is the caller's: this module imports none)
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+def mixed_waves(sel):
+    """The number of whole 64-entry waves of a batch that hold both selected and unselected entries."""
+    w = np.asarray(sel, bool)[:len(sel) // 64 * 64].reshape(-1, 64)
+    return int((w.any(1) & ~w.all(1)).sum())
+
+
+def torch_dtype(torch, dtype):
+    return {np.dtype(np.float64): torch.float64, np.dtype(np.uint32): torch.int32, np.dtype(np.uint8): torch.uint8}[np.dtype(dtype)]
+
+
+def to_device(torch, a):
+    """A host array as a flat device tensor of the same bits (uint32 travels as int32)"""
+    a = np.ascontiguousarray(a)
+    return torch.tensor(a.view(np.int32) if a.dtype == np.uint32 else a, device="cuda").reshape(-1)
+
+
+class Guarded:
+    """A device output of `count` elements of `dtype` between G guard elements of 0xA5 bytes on both sides."""
+
+    def __init__(self, torch, dtype, count):
+        self.dtype, self.size = np.dtype(dtype), np.dtype(dtype).itemsize
+        self.raw = torch.full(((2 * G + count) * self.size,), 0xA5, dtype=torch.uint8, device="cuda")
+        self.t = self.raw[G * self.size:(G + count) * self.size].view(torch_dtype(torch, dtype))
+
+    def read(self, what):
+        a = self.raw.cpu().numpy()
+        g = G * self.size
+        assert (a[:g] == 0xA5).all() and (a[len(a) - g:] == 0xA5).all(), f"{what}: an element outside the output was written"
+        return a[g:len(a) - g].view(self.dtype).copy()
+
+    def untouched(self):
+        return bool((self.raw == 0xA5).all().item())

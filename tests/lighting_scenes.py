@@ -1,11 +1,12 @@
 """The hand-built scenes and light lists of the lighting tests (tests/test_gpu_lighting.py, tests/test_gpu_option_limits.py): a shadow box, a corridor of mirrors,
-the shadow box with the corridor's oblique mirror in it, and a 16-light list for the shadow box whose kept masks use every bit.
+the shadow box with the corridor's oblique mirror in it, a 16-light list for the shadow box whose kept masks use every bit, and the scene, lights and rays of the
+shadow-exit tests (tests/test_gpu_shadow_exit.py, tests/test_gpu_ray_queries.py).
 
 Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  It holds no fixtures.
 """
 import numpy as np
 
-from gpu_checks import ROOT_BOX, checker, closed_box, flat_normals, quad
+from gpu_checks import ROOT_BOX, PlainLight, checker, closed_box, flat_normals, quad
 
 
 def _scene(rrt, groups, towards, materials, textures):
@@ -97,3 +98,51 @@ def _shadow_box_mirror_scene(rrt):
     moved = (np.asarray(OBLIQUE_MIRROR, np.float64) + np.asarray(MIRROR_SHIFT)).tolist()
     groups.append((moved, len(mats) - 1))
     return _scene(rrt, groups, SHADOW_TOWARDS, mats, tex)
+
+
+# ------------------------------------------------------------------ the scene of the shadow-exit tests (tests/test_gpu_shadow_exit.py describes its classes of rays)
+SHADOW_EXIT_OFFSET = 1e-4                                # SURFACE_OFFSET, raytracer.rs:17
+SHADOW_EXIT_LIGHT_ABOVE = (-2.0, -2.75, 6.0)             # classes (a), (b), (c): a quarter above the floor
+SHADOW_EXIT_LIGHT_ON_FLOOR = (3.0, -3.0, 7.0)            # class (d): a point of the floor that rays hit exactly
+SHADOW_EXIT_CAMERA = (0.0, 2.0, -10.0)
+
+
+def shadow_exit_arrays():
+    """Floor y = -3 (root list: it straddles the root's planes) and, in the root's children 1 (x < 0, y < 0, z > 0) and 2 (x > 0, y < 0, z > 0):
+    FAR, a wall at x = -19 that straddles child 1's z plane (own list of a depth-1 node with children); ROOF, a ceiling at y = -2 over the light
+    (own list of a depth-2 node); NEAR, a low wall at x = 1 in child 2; and two pairs of small triangles that open deeper levels."""
+    groups = {"floor": quad((-16, -3, -16), (16, -3, -16), (16, -3, 16), (-16, -3, 16)),
+              "far": quad((-19, -3.5, 1), (-19, -3.5, 11), (-19, -0.5, 11), (-19, -0.5, 1)),
+              "roof": quad((-4.9, -2, 3), (-0.1, -2, 3), (-0.1, -2, 9), (-4.9, -2, 9)),
+              "near": quad((1, -3.4, 4.5), (1, -3.4, 7.5), (1, -2.5, 7.5), (1, -2.5, 4.5)),
+              "deep": [[(-7, -8, 2), (-6.8, -8, 2), (-7, -7.8, 2)], [(-7.3, -8, 2.2), (-7.1, -8, 2.2), (-7.3, -7.8, 2.2)],
+                       [(7, -8, 2), (7.2, -8, 2), (7, -7.8, 2)], [(7.3, -8, 2.2), (7.5, -8, 2.2), (7.3, -7.8, 2.2)]]}
+    names = [n for n, g in groups.items() for _ in g]
+    pos = np.asarray([t for g in groups.values() for t in g], np.float64)
+    nrm = np.tile([0.0, 1.0, 0.0], (len(pos), 3, 1))                        # the rays below only ever shade the floor
+    uv = np.zeros_like(pos); uv[..., 0] = pos[..., 0] * 0.13 + pos[..., 2] * 0.07; uv[..., 1] = pos[..., 1] * 0.11 + pos[..., 2] * 0.05
+    mats = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=0, bump=-1)]
+    A = dict(pos=pos, uv=uv, nrm=nrm, mat=np.zeros(len(pos), np.uint32), materials=mats, textures=[checker((230, 200, 170), (120, 140, 160))], root=ROOT_BOX)
+    return A, {n: np.flatnonzero(np.array(names) == n) for n in groups}
+
+
+def shadow_exit_rays():
+    """Straight down onto the floor from y = -2.6 (under the roof).  Receivers: right of NEAR and far from it (a), under the roof within 1 of the
+    light (b), just right of NEAR (c); and rays that reach SHADOW_EXIT_LIGHT_ON_FLOOR exactly, from several directions and distances (d)."""
+    grid = lambda xs, zs: [(x, z) for x in xs for z in zs]
+    recv = {"a": grid(np.linspace(3.5, 6.0, 6), np.linspace(5.2, 6.8, 5)),
+            "b": grid(-2.0 + np.linspace(-0.4, 0.4, 5), 6.0 + np.linspace(-0.4, 0.4, 5)),
+            "c": grid(np.linspace(1.3, 2.3, 6), np.linspace(5.2, 6.8, 5))}
+    O = [(x, -2.6, z) for k in "abc" for x, z in recv[k]]
+    D = [(0.0, -1.0, 0.0)] * len(O)
+    for d in ((0, -1, 0), (1, -1, 0), (-1, -1, 0), (0, -1, 1), (0, -1, -1), (1, -1, 1)):
+        for k in (0.5, 1.0, 2.0, 4.0):
+            O.append(tuple(np.array(SHADOW_EXIT_LIGHT_ON_FLOOR) - k * np.array(d, np.float64))); D.append(tuple(map(float, d)))
+    return np.asarray(O, np.float64), np.asarray(D, np.float64)
+
+
+def shadow_exit_lights(rrt, light):
+    """Ambient + the one point light; rrt = None: for the oracle only (what conftest.lights_tuple reads of a light, without loading the product library)."""
+    if rrt is None:
+        return [PlainLight(0, 0.25, (0.0, 0.0, 0.0)), PlainLight(1, 0.7, light)]
+    return [rrt.Light.Ambient(0.25), rrt.Light.Point(0.7, rrt.Vector3d(*light))]

@@ -1,5 +1,6 @@
 """Helpers of the tests of the per-ray surface query (include/rrt.h: rrt_surface_rays): the expected arrays of arbitrary rays, restated on the host from the
-reference around the oracle's intersector, and the reference's reflection recursion followed level by level from those arrays.
+reference around the oracle's intersector, the reference's reflection recursion followed level by level from those arrays, and the record's arrays as device
+tensors filled with sentinels (device_arrays, to_host).
 
 Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  It holds no fixtures.
 
@@ -10,9 +11,10 @@ One rounded f64 operation per reference operation, with surface_checks' dot / le
 """
 import numpy as np
 
+from bitwise import bits
 from conftest import channels
 from gpu_checks import POOL
-from surface_checks import NO_MATERIAL, as_usize, bits, cross, dot, length, light_vec, lights_added_up, normalised, shade
+from surface_checks import NO_MATERIAL, as_usize, cross, dot, length, light_vec, lights_added_up, normalised, shade
 
 NAMES = ("hit", "t", "u", "v", "tri", "albedo", "point", "normal", "material", "lights", "next_origin", "next_dir")   # rrt_ray_surface, in its order
 VECTORS = ("point", "normal", "next_origin", "next_dir")
@@ -20,6 +22,8 @@ WHITE = 0x00FFFFFF
 RAY_MISS = dict(hit=0, t=0.0, u=0.0, v=0.0, tri=0xFFFFFFFF, albedo=WHITE, point=0.0, normal=0.0, material=NO_MATERIAL, lights=0, next_origin=0.0, next_dir=0.0)
 DTYPES = dict(hit=np.uint8, t=np.float64, u=np.float64, v=np.float64, tri=np.uint32, albedo=np.uint32, point=np.float64, normal=np.float64, material=np.uint32,
               lights=np.uint32, next_origin=np.float64, next_dir=np.float64)
+SENTINEL = dict(hit=0xA5, t=-12345.5, u=-12345.5, v=-12345.5, tri=-1515870811, albedo=-1515870811, point=-12345.5, normal=-12345.5, material=-1515870811,
+                lights=-1515870811, next_origin=-12345.5, next_dir=-12345.5)                 # what device_arrays fills an output with (0xA5A5A5A5 as int32)
 
 
 def reflected(D, Nn):
@@ -102,15 +106,6 @@ def expected_ray_planes(osc, A, lights, O, D, M=None, surface_offset=1e-4):
     for a in out.values():
         a.setflags(write=False)
     return out
-
-
-def assert_arrays_equal(got, want, names, what):
-    """Bit for bit (f64 through its integer bits), with dtype and shape."""
-    for n in names:
-        g, w = np.asarray(got[n]), np.asarray(want[n])
-        assert g.shape == w.shape and g.dtype == w.dtype, f"{what}: array {n} is {g.dtype}{g.shape}, want {w.dtype}{w.shape}"
-        bad = bits(g) != bits(w)
-        assert not bad.any(), f"{what}: array {n} differs on {int(bad.sum())} of {bad.size} elements, first at {np.argwhere(bad)[0].tolist()}: {g[bad][0]!r} vs {w[bad][0]!r}"
 
 
 def assert_miss_values(got, sel, what):
@@ -235,3 +230,14 @@ def follow_chain(chain, A, lights, max_depth=5, compact=True):
         out[go] = pack(clamp_u8(mixed))                                                                # raytracer.rs:97-101
         c = out
     return c, alive
+
+
+# ------------------------------------------------------------------ the arrays on the device (torch is the caller's: this module imports none)
+def device_arrays(torch, n, names=NAMES):
+    """{name: flat device tensor for n rays, filled with SENTINEL[name]}"""
+    kinds = {np.uint8: torch.uint8, np.float64: torch.float64, np.uint32: torch.int32}
+    return {name: torch.full((n * (3 if name in VECTORS else 1),), SENTINEL[name], dtype=kinds[DTYPES[name]], device="cuda") for name in names}
+
+
+def to_host(tensors, n):
+    return {name: t.cpu().numpy().view(DTYPES[name]).reshape((n, 3) if name in VECTORS else (n,)) for name, t in tensors.items()}

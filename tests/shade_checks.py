@@ -1,5 +1,6 @@
 """Helpers of the tests of shading from kept buffers (include/rrt.h: rrt_shade_surface, rrt_raytracer_set_materials): the oracle's frame of a posed camera
-with what its first hits are, the scenes the tests build, and the comparisons they repeat.
+with what its first hits are, the scenes the tests build (mirror room, soup), and the comparison of shade with render they repeat.  The poses and the
+frame of the region tests are in scenes.py.
 
 Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  It holds no fixtures.
 """
@@ -7,19 +8,12 @@ import importlib
 
 import numpy as np
 
+from bitwise import assert_same_bits
 from conftest import channels
-from gpu_checks import ORIGIN, POOL, checker, closed_box, flat_normals, mix4, traced_rows
+from gpu_checks import POOL, checker, closed_box, flat_normals, mix4, traced_rows
 from surface_checks import frame_dirs, traced_cols
 
-IDENTITY = dict(right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0))
-CREATION = dict(eye=ORIGIN, **IDENTITY)
-TARGET = (0.0, 1.0, 0.0)
 SHADE_INPUTS = ("point", "normal", "material", "albedo", "lights")          # what rrt_shade_surface reads; lights is optional
-
-# the frame and the regions of tests/test_gpu_surface.py, part 4
-W3, H3 = 203, 117
-EYE3 = (-7.0, 4.0, -6.0)
-REGIONS = ((0, 0, 203, 117), (5, 3, 1, 1), (200, 0, 3, 2), (8, 8, 8, 8), (13, 50, 77, 31))
 
 
 def oracle_frame(osc, A, cam, w, h):
@@ -48,20 +42,14 @@ def without(planes, *names):
     return {n: a for n, a in planes.items() if n not in names}
 
 
-def assert_same_frame(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype}{got.shape} vs {want.dtype}{want.shape}"
-    bad = got != want
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} pixels differ, first at {np.argwhere(bad)[0].tolist()}: {int(got[bad][0]):#08x} vs {int(want[bad][0]):#08x}"
-
-
 def assert_shade_is_render(rt, w, h, what, region=None):
     """shade of the planes rt's surface call returns, with the mask and without it, is rt's own frame (its region) bit for bit.  Returns (frame, planes)."""
     planes = rt.surface(w, h, region=region, visibility=("albedo",))
     frame = rt.render(w, h)
     x0, y0, rw, rh = region or (0, 0, w, h)
     want = frame[y0:y0 + rh, x0:x0 + rw]
-    assert_same_frame(rt.shade(w, h, planes, region=region), want, f"{what}: shade with the mask vs render")
-    assert_same_frame(rt.shade(w, h, without(planes, "lights"), region=region), want, f"{what}: shade without the mask vs render")
+    assert_same_bits(rt.shade(w, h, planes, region=region), want, f"{what}: shade with the mask vs render")
+    assert_same_bits(rt.shade(w, h, without(planes, "lights"), region=region), want, f"{what}: shade without the mask vs render")
     return frame, planes
 
 

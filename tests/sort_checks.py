@@ -3,11 +3,12 @@ entry, one rounded f64 operation at a time; the stable ascending sort (np.argsor
 
 Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  It holds no fixtures.
 
-Doubles are compared through their integer bits (compact_checks.assert_same_bytes): NaN payloads and -0.0 have to survive a gather.
+Doubles are compared through their integer bits (bitwise.assert_same_bits): NaN payloads and -0.0 have to survive a gather.
 """
 import numpy as np
 
-from compact_checks import ARRAYS, assert_same_bytes
+from bitwise import assert_same_bits
+from compact_checks import ARRAYS
 
 DEAD_KEY = 0xFFFFFFFF
 KEY_MODES = ("given", "ray", "record")             # RRT_SORT_KEY_GIVEN, RRT_SORT_KEY_RAY, RRT_SORT_KEY_RECORD, in their order
@@ -71,7 +72,7 @@ def assert_sorted(got, want, what):
     assert int(got["count"]) == int(want["count"]), f"{what}: count {int(got['count'])} vs {int(want['count'])}"
     for name in want:
         if name != "count":
-            assert_same_bytes(np.asarray(got[name]).reshape(np.asarray(want[name]).shape), want[name], f"{what}: {name}")
+            assert_same_bits(np.asarray(got[name]).reshape(np.asarray(want[name]).shape), want[name], f"{what}: {name}")
 
 
 def has_ties(keys):

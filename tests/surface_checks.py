@@ -14,31 +14,12 @@ the oracle's get_ray_colour on every non-mirror hit of the teapot frames with ze
 """
 import numpy as np
 
+from bitwise import same
 from gpu_checks import POOL, pose_dirs, traced_rows
 
 NO_MATERIAL = 0xFFFFFFFF
 MISS = dict(point=0.0, normal=0.0, material=NO_MATERIAL, lights=0)          # a miss and a pixel the reference never traces, rrt.h
 VIS_NEVER_TRACED = dict(hit=0, t=0.0, u=0.0, v=0.0, tri=0xFFFFFFFF, albedo=0)
-
-
-# ------------------------------------------------------------------ bits
-def bits(a):
-    """An array as unsigned integers of its element size: equality of these is equality bit for bit."""
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and bool((bits(a) == bits(b)).all())
-
-
-def assert_planes_equal(got, want, names, what):
-    for n in names:
-        assert got[n].shape == want[n].shape and got[n].dtype == want[n].dtype, f"{what}: plane {n} is {got[n].dtype}{got[n].shape}, want {want[n].dtype}{want[n].shape}"
-        bad = bits(got[n]) != bits(want[n])
-        assert not bad.any(), \
-            f"{what}: plane {n} differs on {int(bad.sum())} of {bad.size} elements, first at {np.argwhere(bad)[0].tolist()}: {got[n][bad][0]!r} vs {want[n][bad][0]!r}"
 
 
 # ------------------------------------------------------------------ the frame's rays

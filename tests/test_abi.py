@@ -5,6 +5,7 @@ import re
 
 import pytest
 
+from abi_checks import compiled_values, host_compiler
 from conftest import ROOT
 
 
@@ -44,27 +45,19 @@ def header_structs():
 def test_struct_layouts_match_what_the_compiler_gives_the_header(rrt, tmp_path):
     """The size of every struct of include/rrt.h and the offset and size of each of its fields, printed by a C program compiled against the header itself,
     are those of the ctypes mirror."""
-    import shutil
-    import subprocess
-    cc = shutil.which("gcc") or shutil.which("cc") or shutil.which("clang")
-    if cc is None:
+    if host_compiler() is None:
         pytest.skip("no host C compiler")
     structs = header_structs()
     assert len(structs) >= 15 and structs["rrt_vec3"] == ["x", "y", "z"] and structs["rrt_ambient_samples"] == ["dirs", "n", "_pad", "max_t"]
     assert set(structs) == set(rrt.STRUCTS), "the binding's STRUCTS table and the header's structs disagree"
-    lines = [f'    printf("{s} %zu\\n", sizeof({s}));' for s in structs]
-    lines += [f'    printf("{s}.{f} %zu,%zu\\n", offsetof({s}, {f}), sizeof((({s} *)0)->{f}));' for s, fields in structs.items() for f in fields]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "rrt.h"\nint main(void) {\n' + "\n".join(lines) + "\n    return 0;\n}\n")
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(src)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
     want = {}
     for s, fields in structs.items():
         cls = rrt.STRUCTS[s]
         assert [n for n, _ in cls._fields_] == fields, s
-        want[s] = str(ctypes.sizeof(cls))
-        want.update({f"{s}.{f}": f"{getattr(cls, f).offset},{getattr(cls, f).size}" for f in fields})
-    assert got == want
+        want[f"sizeof({s})"] = ctypes.sizeof(cls)
+        for f in fields:
+            want[f"offsetof({s}, {f})"], want[f"sizeof((({s} *)0)->{f})"] = getattr(cls, f).offset, getattr(cls, f).size
+    assert dict(zip(want, compiled_values(tmp_path, list(want)))) == want
 
 
 def test_strerror_and_build_info(rrt):

@@ -2,6 +2,8 @@
 rrt_ambient_surface_device): the struct layouts, the exports, and the argument checks that are made before any HIP call."""
 import ctypes as C
 
+from abi_checks import assert_refused
+
 EXPORTS = ("rrt_ambient_surface_device", "rrt_ambient_surface")
 
 
@@ -33,11 +35,7 @@ def test_ambient_calls_refuse_a_null_raytracer(rrt):
     samples = rrt.CAmbientSamples(dirs=dirs, n=1, max_t=2.0)
     out = rrt.CAmbient(occluded=C.addressof(occluded), grey=C.addressof(grey))
     region = rrt.CRegion(0, 0, 1, 1)
-    for what, call in (("rrt_ambient_surface", lambda: L.rrt_ambient_surface(None, 64, 48, C.byref(region), C.byref(planes), C.byref(samples), C.byref(out))),
-                       ("rrt_ambient_surface, whole frame", lambda: L.rrt_ambient_surface(None, 64, 48, None, C.byref(planes), C.byref(samples), C.byref(out))),
-                       ("rrt_ambient_surface_device", lambda: L.rrt_ambient_surface_device(None, 64, 48, C.byref(region), C.byref(planes), C.byref(samples), C.byref(out), None))):
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
+    assert_refused(rrt, L, (("rrt_ambient_surface", lambda: L.rrt_ambient_surface(None, 64, 48, C.byref(region), C.byref(planes), C.byref(samples), C.byref(out))),
+                            ("rrt_ambient_surface, whole frame", lambda: L.rrt_ambient_surface(None, 64, 48, None, C.byref(planes), C.byref(samples), C.byref(out))),
+                            ("rrt_ambient_surface_device", lambda: L.rrt_ambient_surface_device(None, 64, 48, C.byref(region), C.byref(planes), C.byref(samples), C.byref(out), None))))
     assert list(occluded) == [0xA5A5A5A5] * 4 and grey[0] == 0xA5A5A5A5, "an output of a refused ambient call was written"

@@ -2,22 +2,19 @@
 struct layout on both sides, the exported symbols, the argument checks the library makes before any HIP call, the checks the Python mirror makes before it calls
 the library, and what it hands to the library."""
 import ctypes as C
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_checks import PATTERN, CallRecorder, NoLibrary, assert_refused, bare_raytracer, compiled_layout, fake_device
 from ambient_checks import T8, T8_MAX_T
 from ambient_rays_checks import INPUTS, OUTPUTS
-from conftest import ROOT
 from ray_surface_checks import NAMES
 
 SIGNATURES = {"rrt_ambient_rays": lambda rrt: [C.c_void_p, C.c_uint32, C.POINTER(rrt.CRaySurface), C.POINTER(C.c_double), C.POINTER(rrt.CAmbientSamples),
                                                C.POINTER(rrt.CRayAmbient)],
               "rrt_ambient_rays_device": lambda rrt: [C.c_void_p, C.c_uint32, C.POINTER(rrt.CRaySurface), C.c_void_p, C.POINTER(rrt.CAmbientSamples),
                                                       C.POINTER(rrt.CRayAmbient), C.c_void_p]}
-PATTERN = 0xA5A5A5A5
 
 
 def test_the_struct_is_16_bytes_on_both_sides(rrt, tmp_path):
@@ -26,13 +23,7 @@ def test_the_struct_is_16_bytes_on_both_sides(rrt, tmp_path):
     assert [getattr(rrt.CRayAmbient, n).offset for n in OUTPUTS] == [0, 8]
     assert rrt.STRUCTS["rrt_ray_ambient"] is rrt.CRayAmbient
     assert tuple(rrt.RAY_AMBIENT_INPUTS) == INPUTS and set(INPUTS) < set(NAMES)
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc is not None, "no host C compiler (build() needs one for the oracle)"
-    src = tmp_path / "size.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "rrt.h"\nint main(void) { printf("%zu %zu %zu\\n", sizeof(rrt_ray_ambient), '
-                   'offsetof(rrt_ray_ambient, occluded), offsetof(rrt_ray_ambient, open)); return 0; }\n')
-    subprocess.run([cc, "-std=c99", "-I", f"{ROOT}/include", "-o", str(tmp_path / "size"), str(src)], check=True)
-    assert subprocess.run([str(tmp_path / "size")], check=True, capture_output=True, text=True).stdout.split() == ["16", "0", "8"]
+    assert compiled_layout(tmp_path, "rrt_ray_ambient", ("occluded", "open")) == (16, [0, 8])
 
 
 def test_both_symbols_are_exported_and_bound(rrt):
@@ -90,53 +81,17 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
             calls.append((f"{form}, NULL {name}", lambda call=call, less=less: call(fake, 1, C.byref(less), C.byref(good), C.byref(out))))
         calls.append((f"{form}, both outputs NULL", lambda call=call: call(fake, 1, C.byref(rec), C.byref(good), C.byref(rrt.CRayAmbient()))))
     assert len(calls) == 2 * (3 + 2 * 12 + 3 + 1)
-    for what, call in calls:
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
-        assert (buf == PATTERN).all(), f"{what}: an output of a refused call was written"
+    assert_refused(rrt, L, calls, dict(buf=buf))
     assert bytes(blank) == bytes(4096), "a refused call wrote through the handle"
-
-
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was called ({name}) with arguments the binding has to refuse")
-
-
-class _Recorder:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append((name, args))
-            return 0
-        return entry
-
-
-def _fake_device(t):
-    class FakeDeviceTensor:
-        """What _device_tensor asks of a tensor, with is_cuda forced (as in tests/test_binding_calls.py)."""
-        is_cuda = True
-        def __getattr__(self, k):
-            return getattr(t, k)
-    return FakeDeviceTensor()
-
-
-def _bare_raytracer(rrt):
-    rt = rrt.RayTracer.__new__(rrt.RayTracer)                                # no handle: nothing may get as far as needing one
-    rt._h = None
-    return rt
 
 
 def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    monkeypatch.setattr(rrt, "lib", lambda: _NoLibrary())
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    f4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float32))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
+    rt = bare_raytracer(rrt)
+    monkeypatch.setattr(rrt, "lib", lambda: NoLibrary())
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    f4 = lambda n: fake_device(torch.zeros(n, dtype=torch.float32))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
     rec = dict(point=f8(12), normal=f8(12), material=i4(4))
     into = lambda out, planes=rec, rot_t=None: rt.ambient_rays_into(out, planes, T8, T8_MAX_T, rot_t=rot_t, stream=0)
     # not a device tensor
@@ -198,17 +153,17 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
 
 def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    rec = _Recorder()
+    rt = bare_raytracer(rrt)
+    rec = CallRecorder()
     monkeypatch.setattr(rrt, "lib", lambda: rec)
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
 
     def table_of(s):
         return s.n, s.max_t, [s.dirs[i] for i in range(3 * s.n)]
     # the device form: all twelve arrays of a surface_rays_into call are passed, the three that are read arrive, the nine others are NULL
     twelve = {n: (f8(12) if n in ("point", "normal", "next_origin", "next_dir") else f8(4) if n in ("t", "u", "v") else
-                  _fake_device(torch.zeros(4, dtype=torch.uint8)) if n == "hit" else i4(4)) for n in NAMES}
+                  fake_device(torch.zeros(4, dtype=torch.uint8)) if n == "hit" else i4(4)) for n in NAMES}
     out = dict(occluded=i4(4), open=i4(4))
     rot = f8(8)
     rt.ambient_rays_into(out, twelve, T8, T8_MAX_T, rot_t=rot, stream=0x51)

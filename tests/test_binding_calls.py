@@ -15,6 +15,8 @@ from collections import namedtuple
 import numpy as np
 import pytest
 
+from abi_checks import fake_device
+
 RT, SCENE, MULTI, STREAM = 0x1000, 0x2000, 0x3000, 0x51          # made-up handles and a made-up stream
 W, H = 8, 4
 REGION = (2, 1, 3, 2)                                            # x0, y0, w, h
@@ -134,15 +136,7 @@ class Env:
                            lights=np.ones((self.h, self.w, 4), np.uint32), albedo=np.zeros((self.h, self.w, 4), np.uint32), junk="ignored")
 
     def dev(self, t):
-        torch = self.torch
-
-        class FakeDeviceTensor:
-            """What _device_tensor asks of a tensor, with is_cuda forced (as in tests/test_scene_update_abi.py)."""
-            is_cuda = True
-            device = torch.device("cuda", 0)
-            def __getattr__(self, k):
-                return getattr(t, k)
-        return FakeDeviceTensor()
+        return fake_device(t, self.torch.device("cuda", 0))
 
     def scene_data(self):
         self.made.append(self.rrt.SceneData(SCENE))

@@ -4,7 +4,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-TARGET = (0.0, 1.0, 0.0)
+from scenes import TARGET
+
 EYES = ((6, 3, -8), (-7, 4, -6), (9, 2, 1), (0, 9, -4), (4, 1.5, 7), (0, 2, -6))   # the poses of tests/test_gpu_camera.py
 
 

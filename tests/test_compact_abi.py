@@ -2,17 +2,12 @@
 as far as no GPU is needed: the struct layout on both sides, the exported symbols, the scratch size, the argument checks the library makes before any HIP call and
 before it looks at the handle, and the checks the Python mirror makes before it calls the library."""
 import ctypes as C
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from compact_checks import ELEM_BYTES, NAMES, OFFSETS, RECORD_NAMES, SELECTS
-from conftest import ROOT
-
-PATTERN = 0xA5A5A5A5
-SIZES = (1, 2, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2047, 2049, 4097, 70001, 2 ** 16, 2 ** 20, 2 ** 20 + 4097)   # those of tests/test_gpu_compact.py, and 2^16, 2^20
+from abi_checks import PATTERN, CallRecorder, NoLibrary, assert_refused, bare_raytracer, compiled_layout, compiled_values, fake_device
+from compact_checks import ELEM_BYTES, NAMES, OFFSETS, RECORD_NAMES, SCRATCH_SIZES as SIZES, SELECTS
 
 
 def test_the_struct_is_128_bytes_on_both_sides(rrt, tmp_path):
@@ -24,15 +19,9 @@ def test_the_struct_is_128_bytes_on_both_sides(rrt, tmp_path):
     assert mirror == OFFSETS
     assert {n: np.dtype(rrt._ray_plane(n, rrt.CRaySet)[0]).itemsize * rrt._ray_plane(n, rrt.CRaySet)[1] for n in NAMES} == ELEM_BYTES
     assert tuple(rrt.SELECT_MODES) == SELECTS
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc is not None, "no host C compiler (build() needs one for the oracle)"
     fields = [n if n in NAMES[:4] else f"rec.{n}" for n in NAMES]
-    src = tmp_path / "size.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "rrt.h"\nint main(void) { printf("%zu %d %d %d", sizeof(rrt_ray_set), RRT_SELECT_HIT, RRT_SELECT_MIRROR, '
-                   'RRT_SELECT_FLAG);\n' + "".join(f'    printf(" %zu", offsetof(rrt_ray_set, {f}));\n' for f in fields) + '    printf("\\n"); return 0; }\n')
-    subprocess.run([cc, "-std=c99", "-I", f"{ROOT}/include", "-o", str(tmp_path / "size"), str(src)], check=True)
-    got = subprocess.run([str(tmp_path / "size")], check=True, capture_output=True, text=True).stdout.split()
-    assert got == ["128", "0", "1", "2"] + [str(OFFSETS[n]) for n in NAMES]
+    assert compiled_layout(tmp_path, "rrt_ray_set", fields) == (128, [OFFSETS[n] for n in NAMES])
+    assert compiled_values(tmp_path, ("RRT_SELECT_HIT", "RRT_SELECT_MIRROR", "RRT_SELECT_FLAG")) == [0, 1, 2]
 
 
 def test_the_symbols_are_exported_and_bound(rrt):
@@ -128,13 +117,7 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
         calls += [(f"{form}, elem_bytes {e}", lambda call=call, e=e: call(fake, n, mat, e, mat, D)) for e in (0, 2, 3, 5, 12, 32, 0xFFFFFFFF)]
         calls += [(f"{form}, elem_bytes 2, n = 0", lambda call=call: call(fake, 0, mat, 2, mat, D))]
     assert len(calls) == 2 * 14 + 3 + 2 * (5 + 7 + 1)
-    for what, call in calls:
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
-        for name, a in outs.items():
-            assert (a == PATTERN).all(), f"{what}: {name} of a refused call was written"
+    assert_refused(rrt, L, calls, outs)
     # n == 0 with valid arguments: RRT_OK, nothing enqueued (the handle is not a raytracer); the host form writes *count = 0 and nothing else
     assert dev(fake, 0, 0, flag, src, dst, I, Cn, scratch=None, sb=0) == rrt.OK and (Cn == PATTERN).all()
     assert host(fake, 0, 2, None, None, None, I, Cn) == rrt.OK
@@ -146,45 +129,14 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
     assert bytes(blank) == bytes(4096), "a refused call wrote through the handle"
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was called ({name}) with arguments the binding has to refuse")
-
-
-class _Recorder:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append((name, args))
-            return 0
-        return entry
-
-
-def _fake_device(t):
-    class FakeDeviceTensor:
-        """What _device_tensor asks of a tensor, with is_cuda forced (as in tests/test_binding_calls.py)."""
-        is_cuda = True
-        def __getattr__(self, k):
-            return getattr(t, k)
-    return FakeDeviceTensor()
-
-
-def _bare_raytracer(rrt):
-    rt = rrt.RayTracer.__new__(rrt.RayTracer)                                # no handle: nothing may get as far as needing one
-    rt._h = None
-    return rt
-
-
 def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    monkeypatch.setattr(rrt, "lib", lambda: _NoLibrary())
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    f4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float32))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
-    u1 = lambda n: _fake_device(torch.zeros(n, dtype=torch.uint8))
+    rt = bare_raytracer(rrt)
+    monkeypatch.setattr(rrt, "lib", lambda: NoLibrary())
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    f4 = lambda n: fake_device(torch.zeros(n, dtype=torch.float32))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
+    u1 = lambda n: fake_device(torch.zeros(n, dtype=torch.uint8))
     src = dict(point=f8(12), material=i4(4), rot=f8(8))
 
     def into(out, src=src, select="hit", index_t=None, count_t=None, scratch_t=None, flag_t=None):
@@ -268,12 +220,12 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
 
 def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    rec = _Recorder()
+    rt = bare_raytracer(rrt)
+    rec = CallRecorder()
     monkeypatch.setattr(rrt, "lib", lambda: rec)
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
-    u1 = lambda n: _fake_device(torch.zeros(n, dtype=torch.uint8))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
+    u1 = lambda n: fake_device(torch.zeros(n, dtype=torch.uint8))
 
     def pointers(s):
         return {n: (getattr(s, n) if n in NAMES[:4] else getattr(s.rec, n)) for n in NAMES}
@@ -292,7 +244,7 @@ def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     # FLAG with index and count alone: both structs NULL
     rec.calls.clear()
     flag = u1(5)
-    rt.compact_rays_into({}, {}, "flag", i4(5), None, _fake_device(torch.zeros(4, dtype=torch.int64)), flag_t=flag, stream=7)
+    rt.compact_rays_into({}, {}, "flag", i4(5), None, fake_device(torch.zeros(4, dtype=torch.int64)), flag_t=flag, stream=7)
     (name, args), = rec.calls
     assert args[1:3] == (5, 2) and args[3].value == flag.data_ptr() and args[4] is None and args[5] is None and args[7] is None and args[9] == 32
     # the host form

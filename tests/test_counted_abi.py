@@ -8,9 +8,9 @@ import os
 import numpy as np
 import pytest
 
+from abi_checks import PATTERN, CallRecorder, NoLibrary, assert_refused, bare_raytracer, fake_device
 from conftest import ROOT
 
-PATTERN = 0xA5A5A5A5
 COUNTED = ("intersect_rays", "get_ray_colours", "occluded_rays", "surface_rays", "shade_rays", "ambient_rays", "compact_rays", "scatter_rays", "mix_rays")
 
 
@@ -162,14 +162,7 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
               ("mix, a NULL colour", lambda: mix(fake, n, vec, None))]
 
     assert len(calls) == 4 * 5 + 2 + 11 + (3 + 2 * 10 + 3) + 19 + 13 + 4
-    for what, call in calls:
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
-        for name, a in outs.items():
-            assert (a == PATTERN).all(), f"{what}: {name} of a refused call was written"
-        assert (bound == 3).all(), f"{what}: the bound was written"
+    assert_refused(rrt, L, calls, dict(outs, bound=bound))
 
     # n == 0 with valid arguments and a bound: RRT_OK, nothing enqueued (the handle is not a raytracer), nothing written
     oks = [intersect(fake, 0, vec, vec, five), colours(fake, 0, vec, vec, at(A)), occluded(fake, 0, vec, vec, at(A)), surface(fake, 0, vec, vec, surf_out),
@@ -184,42 +177,11 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
     assert bytes(blank) == bytes(4096), "a refused call wrote through the handle"
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was called ({name}) with arguments the binding has to refuse")
-
-
-class _Recorder:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append((name, args))
-            return 0
-        return entry
-
-
-def _fake_device(t):
-    class FakeDeviceTensor:
-        """What _device_tensor asks of a tensor, with is_cuda forced (as in tests/test_binding_calls.py)."""
-        is_cuda = True
-        def __getattr__(self, k):
-            return getattr(t, k)
-    return FakeDeviceTensor()
-
-
-def _bare_raytracer(rrt):
-    rt = rrt.RayTracer.__new__(rrt.RayTracer)                                # no handle: nothing may get as far as needing one
-    rt._h = None
-    return rt
-
-
 def _nine_calls(rrt, rt, torch):
     """{call: into(bound_t)} -- each of the nine _into methods with valid fake device tensors of a batch of 4 and the given bound."""
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
-    u1 = lambda n: _fake_device(torch.zeros(n, dtype=torch.uint8))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
+    u1 = lambda n: fake_device(torch.zeros(n, dtype=torch.uint8))
     o, d, b1, w4, w1, d4, e4, scratch = f8(12), f8(12), u1(4), i4(4), i4(1), f8(4), f8(4), u1(64)      # (made once: both calls of a pair see the same tensors)
     rec = dict(albedo=i4(4), point=f8(12), normal=f8(12), material=i4(4))
     table = np.array([[0.0, 0.0, 1.0]])
@@ -238,8 +200,8 @@ def _nine_calls(rrt, rt, torch):
 
 def test_the_binding_refuses_a_bad_bound_before_it_calls_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    monkeypatch.setattr(rrt, "lib", lambda: _NoLibrary())
+    rt = bare_raytracer(rrt)
+    monkeypatch.setattr(rrt, "lib", lambda: NoLibrary())
     calls = _nine_calls(rrt, rt, torch)
     assert tuple(calls) == COUNTED
     for name, into in calls.items():
@@ -250,15 +212,15 @@ def test_the_binding_refuses_a_bad_bound_before_it_calls_the_library(rrt, monkey
         for bad in (torch.zeros(1, dtype=torch.int64), torch.zeros(1, dtype=torch.uint8), torch.zeros(1, dtype=torch.float64),   # a wrong dtype
                     torch.zeros(2, dtype=torch.int32), torch.zeros(0, dtype=torch.int32), torch.zeros(4, dtype=torch.int32)[::2]):   # a wrong length, not contiguous
             with pytest.raises(AssertionError, match="bound: want 1 contiguous elements of 4 bytes"):
-                into(_fake_device(bad))
+                into(fake_device(bad))
 
 
 def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     """With a bound: the counted symbol, the bound's pointer in position 2, and around it the arguments of the uncounted call.  Without one: the old symbol with
     the old arguments."""
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    rec = _Recorder()
+    rt = bare_raytracer(rrt)
+    rec = CallRecorder()
     monkeypatch.setattr(rrt, "lib", lambda: rec)
 
     def plain(v):                                                            # an argument as something comparable: pointers by value, structs by their bytes
@@ -268,7 +230,7 @@ def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
             return ("struct", bytes(v._obj))
         return v
     for name, into in _nine_calls(rrt, rt, torch).items():
-        bound = _fake_device(torch.zeros(1, dtype=torch.int32))
+        bound = fake_device(torch.zeros(1, dtype=torch.int32))
         rec.calls.clear()
         into(None)
         into(bound)
@@ -283,9 +245,9 @@ def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
             assert (t1.n, t1.max_t, t1.dirs[2]) == (t0.n, t0.max_t, t0.dirs[2]) == (1, 3.0, 1.0)
         assert [plain(v) for v in rest1] == [plain(v) for v in rest0], name
     # the compaction keeps its output count where it was, two places behind the bound's neighbours: n, BOUND, select, flag, src, dst, index, COUNT
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
-    u1 = lambda n: _fake_device(torch.zeros(n, dtype=torch.uint8))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
+    u1 = lambda n: fake_device(torch.zeros(n, dtype=torch.uint8))
     rec.calls.clear()
     src, out, index, count, scratch, bound = dict(material=i4(4), point=f8(12)), dict(point=f8(12)), i4(4), i4(1), u1(48), i4(1)
     rt.compact_rays_into(out, src, "mirror", index, count, scratch, stream=0x51, bound_t=bound)

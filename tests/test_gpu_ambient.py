@@ -17,10 +17,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from ambient_checks import (H, T8, T8_MAX_T, W, Rays, assert_same_plane, by_oracle, by_shadow_query, crop, grey_of, popcount, traced_mask)
+from ambient_checks import H, T8, T8_MAX_T, W, Rays, by_oracle, by_shadow_query, crop, freeze, grey_of, popcount, traced_mask
+from bitwise import assert_same_arrays, assert_same_bits
 from gpu_checks import ALL_MODES, CHAIN_LIGHTS, FORCED_MODES, chain_rrt_lights, chain_scene, oracle_for
+from scenes import teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
 from shade_checks import soup_scene
-from surface_checks import NO_MATERIAL, assert_planes_equal, traced_pixels_in
+from surface_checks import NO_MATERIAL, traced_pixels_in
 
 pytestmark = pytest.mark.gpu
 
@@ -32,12 +34,6 @@ REGION = (5, 3, 41, 30)
 
 
 @pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
 def scenes(rrt, teapot, teapot_arrays):
     """name -> (SceneData, arrays): the teapot as loaded, and with bump = -1 in every material."""
     A = teapot_arrays
@@ -46,11 +42,6 @@ def scenes(rrt, teapot, teapot_arrays):
     for m in flat:
         m["bump"] = -1
     return {SCENES[0]: (teapot, A), SCENES[1]: (rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], flat, A["textures"]), dict(A, materials=flat))}
-
-
-def freeze(*arrays):
-    for a in arrays:
-        a.setflags(write=False)
 
 
 @pytest.fixture(scope="module")
@@ -93,17 +84,17 @@ def test_the_mask_is_the_shadow_query(rrt, ob, scenes, kept, name, max_t):
         assert rays.fallback.sum() >= 1000, f"{name}: {int(rays.fallback.sum())} hits take the length(tg) == 0 branch (< 1000)"
     for mode in ALL_MODES:
         rt = rrt.RayTracer(sd, rrt.default_lights(), box_filter=mode)
-        assert_planes_equal(rt.surface(W, H, planes=INPUTS), planes, INPUTS, f"{name}, walk {mode}: the planes the rays were formed from")
+        assert_same_arrays(rt.surface(W, H, planes=INPUTS), planes, INPUTS, f"{name}, walk {mode}: the planes the rays were formed from")
         want = by_shadow_query(rt, rays, max_t)
         if max_t == T8_MAX_T:
             assert_caps(want, rays, f"{name}, walk {mode}, by rrt_occluded_rays")
         assert (want != 0).any() and (popcount(want[rays.hit]) < rays.n).any(), f"{name}, walk {mode}, max_t {max_t}: the reference masks are all empty or all full"
         got = rt.ambient(W, H, planes, T8, max_t, outputs=("occluded",))
-        assert_same_plane(got["occluded"], want, f"{name}, walk {mode}, max_t {max_t}: occluded vs rrt_occluded_rays")
+        assert_same_bits(got["occluded"], want, f"{name}, walk {mode}, max_t {max_t}: occluded vs rrt_occluded_rays")
         if mode == "lane" and max_t == T8_MAX_T and name == SCENES[0]:
             ref = by_oracle(oracle_for(ob, A, rrt.default_lights()), rays, max_t)
             assert_caps(ref, rays, f"{name}, by the oracle")
-            assert_same_plane(got["occluded"], ref, f"{name}, walk {mode}, max_t {max_t}: occluded vs the oracle's intersector")
+            assert_same_bits(got["occluded"], ref, f"{name}, walk {mode}, max_t {max_t}: occluded vs the oracle's intersector")
 
 
 # ------------------------------------------------------------------ 2
@@ -111,10 +102,10 @@ def test_sample_counts(kept):
     rt, planes, rays, want = kept[SCENES[0]]
     one = rt.ambient(W, H, planes, T8[:1], T8_MAX_T, outputs=("occluded",))["occluded"]
     assert (want & np.uint32(1)).any() and not (want[rays.hit] & np.uint32(1)).all()
-    assert_same_plane(one, want & np.uint32(1), "n = 1: bit 0 of the mask of T8")
+    assert_same_bits(one, want & np.uint32(1), "n = 1: bit 0 of the mask of T8")
     full = rt.ambient(W, H, planes, np.tile(T8, (4, 1)), T8_MAX_T, outputs=("occluded",))["occluded"]
     assert (want >> np.uint32(7)).any(), "sample 7 is never occluded: bit 31 would show nothing"
-    assert_same_plane(full, want * np.uint32(0x01010101), "n = 32, T8 four times: the mask of T8 in every byte")
+    assert_same_bits(full, want * np.uint32(0x01010101), "n = 32, T8 four times: the mask of T8 in every byte")
 
 
 # ------------------------------------------------------------------ 3
@@ -133,12 +124,12 @@ def test_an_odd_frame(odd_frame, teapot_arrays):
     rays = Rays(planes, len(teapot_arrays["materials"]), T8)
     want = by_shadow_query(rt, rays, T8_MAX_T)
     assert rays.hit.mean() >= 0.4 and (want != 0).sum() >= 1000, (rays.hit.mean(), int((want != 0).sum()))
-    assert_same_plane(out["occluded"], want, f"{W2}x{H2}: occluded vs rrt_occluded_rays")
+    assert_same_bits(out["occluded"], want, f"{W2}x{H2}: occluded vs rrt_occluded_rays")
     traced = traced_mask(W2, H2)
     assert not traced[0].any() and not traced[1].any() and not traced[:, -1].any() and traced[2:, :-1].all()
     assert (out["occluded"][~traced] == 0).all() and (out["grey"][~traced] == 0).all(), "row 0, row 1 and the last column of an odd-sized frame are 0 in both outputs"
     assert (out["grey"][traced] != 0).any()
-    assert_same_plane(out["grey"], grey_of(want, planes["material"], len(teapot_arrays["materials"]), 8, traced), f"{W2}x{H2}: grey vs the integer formula")
+    assert_same_bits(out["grey"], grey_of(want, planes["material"], len(teapot_arrays["materials"]), 8, traced), f"{W2}x{H2}: grey vs the integer formula")
 
 
 def test_a_region_is_a_crop_of_the_frame(odd_frame):
@@ -149,11 +140,11 @@ def test_a_region_is_a_crop_of_the_frame(odd_frame):
     for region in (REGION, (px, py, 1, 1), (W2 - 3, 0, 3, 3)):
         x0, y0, w, h = region
         part = rt.surface(W2, H2, region=region, planes=INPUTS)
-        assert_planes_equal(part, crop(full_planes, region), INPUTS, f"region {region}: planes")
+        assert_same_arrays(part, crop(full_planes, region), INPUTS, f"region {region}: planes")
         got = rt.ambient(W2, H2, part, T8, T8_MAX_T, region=region)
         stats = rt.last_stats()
         for n in ("occluded", "grey"):
-            assert_same_plane(got[n], full[n][y0:y0 + h, x0:x0 + w], f"region {region}: {n} vs the crop of the whole frame")
+            assert_same_bits(got[n], full[n][y0:y0 + h, x0:x0 + w], f"region {region}: {n} vs the crop of the whole frame")
         assert (stats["width"], stats["height"], stats["rays_primary"]) == (W2, H2, 4 * traced_pixels_in(region, W2, H2)) and stats["kernel_ms"] > 0, (region, stats)
     assert (full["occluded"][3:33, 5:46] != 0).sum() >= 500, "the region of the test shows few occluded rays"
 
@@ -164,11 +155,11 @@ def test_grey(kept, teapot_arrays):
     n_mats = len(teapot_arrays["materials"])
     traced = traced_mask(W, H)
     got = rt.ambient(W, H, planes, T8, T8_MAX_T)
-    assert_same_plane(got["occluded"], want, "both outputs asked for: occluded")
-    assert_same_plane(got["grey"], grey_of(got["occluded"], planes["material"], n_mats, 8, traced), "grey vs the integer formula of the occluded and material planes")
+    assert_same_bits(got["occluded"], want, "both outputs asked for: occluded")
+    assert_same_bits(got["grey"], grey_of(got["occluded"], planes["material"], n_mats, 8, traced), "grey vs the integer formula of the occluded and material planes")
     only = rt.ambient(W, H, planes, T8, T8_MAX_T, outputs=("grey",))
     assert set(only) == {"grey"}
-    assert_same_plane(only["grey"], got["grey"], "grey alone vs grey beside occluded")
+    assert_same_bits(only["grey"], got["grey"], "grey alone vs grey beside occluded")
     levels = np.unique(got["grey"][traced])
     print(f"grey: {len(levels)} levels among the traced pixels, {levels.min():#08x} to {levels.max():#08x}")
     assert len(levels) >= 16 and levels.max() == 0x00FFFFFF
@@ -188,8 +179,8 @@ def test_grey(kept, teapot_arrays):
     want_edit[a] = 0
     want_edit[b] = 0
     again = rt.ambient(W, H, edited, T8, T8_MAX_T)
-    assert_same_plane(again["occluded"], want_edit, "material = n_mats and 0xFFFFFFFF in two blocks: occluded")
-    assert_same_plane(again["grey"], grey_of(want_edit, edited["material"], n_mats, 8, traced), "material = n_mats and 0xFFFFFFFF in two blocks: grey")
+    assert_same_bits(again["occluded"], want_edit, "material = n_mats and 0xFFFFFFFF in two blocks: occluded")
+    assert_same_bits(again["grey"], grey_of(want_edit, edited["material"], n_mats, 8, traced), "material = n_mats and 0xFFFFFFFF in two blocks: grey")
     assert (again["grey"][a] == 0x00FFFFFF).all() and (again["grey"][b] == 0x00FFFFFF).all()
 
 
@@ -200,14 +191,14 @@ def assert_walks(rrt, make_rt, n_mats, what, modes):
     rays = Rays(planes, n_mats, T8)
     for mode, kw in modes:
         rt = make_rt(mode, kw)
-        assert_planes_equal(rt.surface(W, H, planes=INPUTS), planes, INPUTS, f"{what}, walk {mode} {kw}: the planes the rays were formed from")
+        assert_same_arrays(rt.surface(W, H, planes=INPUTS), planes, INPUTS, f"{what}, walk {mode} {kw}: the planes the rays were formed from")
         want = by_shadow_query(rt, rays, T8_MAX_T)
         n_bits = int(popcount(want).sum())
         print(f"{what}, walk {mode} {kw}: {int(rays.hit.sum())} hits, {n_bits} of {int(rays.hit.sum()) * 8} rays occluded by rrt_occluded_rays")
         assert n_bits >= 100 and n_bits < int(rays.hit.sum()) * 8, f"{what}, walk {mode}: {n_bits} occluded rays by the reference"
         got = rt.ambient(W, H, planes, T8, T8_MAX_T)
-        assert_same_plane(got["occluded"], want, f"{what}, walk {mode} {kw}: occluded vs rrt_occluded_rays")
-        assert_same_plane(got["grey"], grey_of(want, planes["material"], n_mats, 8, traced_mask(W, H)), f"{what}, walk {mode} {kw}: grey")
+        assert_same_bits(got["occluded"], want, f"{what}, walk {mode} {kw}: occluded vs rrt_occluded_rays")
+        assert_same_bits(got["grey"], grey_of(want, planes["material"], n_mats, 8, traced_mask(W, H)), f"{what}, walk {mode} {kw}: grey")
         yield rt
 
 
@@ -268,7 +259,7 @@ def test_the_device_form(rrt, teapot, kept, mode):
     for name, t, shape in (("occluded", occluded, (h, w, 4)), ("grey", grey, (h, w))):
         a = t.cpu().numpy()
         assert (a[:G] == SENTINEL).all() and (a[-G:] == SENTINEL).all(), f"{name}: an element outside the output was written"
-        assert_same_plane(a[G:-G].view(np.uint32).reshape(shape), host[name], f"walk {mode}: {name} of the device form vs the host form")
+        assert_same_bits(a[G:-G].view(np.uint32).reshape(shape), host[name], f"walk {mode}: {name} of the device form vs the host form")
     assert (stats["width"], stats["height"], stats["rays_primary"]) == (W, H, 4 * traced_pixels_in(REGION, W, H)), stats
     assert stats["filter_variant"] == rrt.VARIANT_NAMES.index(mode) and stats["kernel_ms"] > 0, stats
     # one output only: the other tensor is not touched
@@ -277,7 +268,7 @@ def test_the_device_form(rrt, teapot, kept, mode):
     rt.ambient_into(dict(grey=grey[G:-G]), tensors, T8, T8_MAX_T, W, H, region=REGION, stream=stream.cuda_stream)
     stream.synchronize()
     assert (occluded.cpu().numpy() == SENTINEL).all()
-    assert_same_plane(grey.cpu().numpy()[G:-G].view(np.uint32).reshape(h, w), host["grey"], f"walk {mode}: grey alone, device form")
+    assert_same_bits(grey.cpu().numpy()[G:-G].view(np.uint32).reshape(h, w), host["grey"], f"walk {mode}: grey alone, device form")
 
 
 @pytest.mark.parametrize("frames_before", (0, 1, 2))
@@ -292,12 +283,12 @@ def test_the_tuning_state_is_untouched(rrt, teapot, kept, odd_frame, frames_befo
         variant = rt.last_stats()["filter_variant"]
     got = rt.ambient(W, H, planes, T8, T8_MAX_T, outputs=("occluded",))
     stats = rt.last_stats()
-    assert_same_plane(got["occluded"], want, f"after {frames_before} frames")
+    assert_same_bits(got["occluded"], want, f"after {frames_before} frames")
     assert (stats["width"], stats["height"], stats["rays_primary"]) == (W, H, 4 * traced_pixels_in((0, 0, W, H), W, H)) and stats["kernel_ms"] > 0, stats
-    assert_same_plane(rt.ambient(W2, H2, odd_planes, T8, T8_MAX_T, outputs=("occluded",))["occluded"], odd["occluded"], "another size")   # must not become "the" size either
+    assert_same_bits(rt.ambient(W2, H2, odd_planes, T8, T8_MAX_T, outputs=("occluded",))["occluded"], odd["occluded"], "another size")   # must not become "the" size either
     again = rt.ambient(W, H, planes, T8, T8_MAX_T, outputs=("occluded",))
     assert rt.last_stats()["filter_variant"] == stats["filter_variant"]
-    assert_same_plane(again["occluded"], want, "after a call of another size")
+    assert_same_bits(again["occluded"], want, "after a call of another size")
     after = rt.render(W, H)
     if frames_before:
         assert stats["filter_variant"] == variant, (stats["filter_variant"], variant)
@@ -372,4 +363,4 @@ def test_refusals_leave_the_outputs_as_they_were(rrt, teapot, kept):
     raw(C.byref(cs), C.byref(samples(max_t=INF)), C.byref(out()))                  # +inf is a valid max_t
     assert not (occluded == PATTERN).any() and not (grey == PATTERN).any(), "an accepted call leaves elements of its outputs unwritten"
     raw(C.byref(cs), C.byref(samples()), C.byref(out()))
-    assert_same_plane(occluded, want[y0:y0 + h, x0:x0 + w], "after the refusals: occluded of the region")
+    assert_same_bits(occluded, want[y0:y0 + h, x0:x0 + w], "after the refusals: occluded of the region")

@@ -18,11 +18,13 @@ import numpy as np
 import pytest
 
 from ambient_checks import T8, T8_MAX_T, popcount
-from ambient_rays_checks import INPUTS, OUTPUTS, Fan, assert_same_array, by_oracle, by_shadow_query, mask_figures, open_of, rows, standard_rot
+from ambient_rays_checks import INPUTS, OUTPUTS, Fan, by_oracle, by_shadow_query, kept_records as kept, level1, mask_figures, open_of, rows, standard_rot  # noqa: F401  (fixtures: kept)
+from bitwise import assert_same_arrays, assert_same_bits
+from compact_checks import G
 from gpu_checks import ALL_MODES, CHAIN_LIGHTS, FORCED_MODES, ORIGIN, chain_rrt_lights, chain_scene, oracle_for
-from ray_surface_checks import assert_arrays_equal
-from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, mirror_room, soup_scene
-from surface_checks import NO_MATERIAL, frame_dirs
+from scenes import CREATION, rays_of, teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
+from shade_checks import MIRROR_ROOM_LIGHTS, mirror_room, soup_scene
+from surface_checks import NO_MATERIAL
 
 pytestmark = pytest.mark.gpu
 
@@ -31,27 +33,6 @@ W, H = 64, 48
 RW, RH = 32, 24                                                  # the mirror room's, the soup's and the chain scene's frame
 SENTINEL = -1515870811                                           # 0xA5A5A5A5 as int32
 PATTERN = 0xA5A5A5A5
-G = 64                                                           # guard elements on both sides of a device output
-
-
-def rays_of(cam, w, h):
-    d = frame_dirs(cam, w, h).reshape(-1, 3)
-    return np.ascontiguousarray(np.broadcast_to(np.asarray(cam["eye"], np.float64), d.shape)), d
-
-
-def freeze(*arrays):
-    for a in arrays:
-        a.setflags(write=False)
-
-
-def level1(rt, cam, w, h):
-    """(level-0 arrays of the w x h frame's primary rays, the level-1 records of ALL its level-0 hits: INPUTS of rrt_surface_rays on their next_origin / next_dir)"""
-    O, D = rays_of(cam, w, h)
-    l0 = rt.surface_rays(O, D, planes=("hit", "next_origin", "next_dir"))
-    h0 = l0["hit"].astype(bool)
-    rec = rt.surface_rays(np.ascontiguousarray(l0["next_origin"][h0]), np.ascontiguousarray(l0["next_dir"][h0]), planes=INPUTS)
-    freeze(*rec.values())
-    return l0, rec
 
 
 def assert_ambient_is_the_shadow_query(rt, rec, fan, rot, max_t, what, dirs=T8):
@@ -61,34 +42,14 @@ def assert_ambient_is_the_shadow_query(rt, rec, fan, rot, max_t, what, dirs=T8):
     assert hits > 0 and (want != 0).any() and (popcount(want[fan.hit]) < fan.n).any(), f"{what}: the reference masks are all empty or all full"
     got = rt.ambient_rays(rec, dirs, max_t, rot=rot)
     stats = rt.last_stats()
-    assert_same_array(got["occluded"], want, f"{what}: occluded vs rrt_occluded_rays")
-    assert_same_array(got["open"], open_of(want, fan.hit, fan.n), f"{what}: open vs n - popcount on hits and n on misses")
+    assert_same_bits(got["occluded"], want, f"{what}: occluded vs rrt_occluded_rays")
+    assert_same_bits(got["open"], open_of(want, fan.hit, fan.n), f"{what}: open vs n - popcount on hits and n on misses")
     assert (stats["width"], stats["height"], stats["rays_primary"]) == (len(want), 1, len(want)) and stats["kernel_ms"] > 0, (what, stats)
     return want
 
 
 def device_records(torch, rec):
     return {n: torch.tensor(np.ascontiguousarray(rec[n]).view(np.int32 if rec[n].dtype == np.uint32 else rec[n].dtype), device="cuda").reshape(-1) for n in INPUTS}
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
-def kept(rrt, teapot, teapot_arrays):
-    """Part 1's records and what the later parts share of them (read-only): the raytracer in the default mode, the level-0 arrays, the level-1 records, ROT, the
-    fans without and with it, and the masks of T8 at max_t 2.0 by rt.occluded for both."""
-    rt = rrt.RayTracer(teapot, rrt.default_lights())
-    l0, rec = level1(rt, CREATION, W, H)
-    n_mats = len(teapot_arrays["materials"])
-    rot = standard_rot(len(rec["material"]))
-    fans = {False: Fan(rec, n_mats, T8), True: Fan(rec, n_mats, T8, rot)}
-    want = {r: by_shadow_query(rt, fans[r], T8_MAX_T) for r in (False, True)}
-    freeze(*want.values(), *l0.values())
-    return dict(rt=rt, l0=l0, rec=rec, rot=rot, fans=fans, want=want, n_mats=n_mats)
 
 
 # ------------------------------------------------------------------ 1
@@ -101,7 +62,7 @@ def test_the_mask_is_the_shadow_query_at_level_1(rrt, ob, teapot, teapot_arrays,
     for mode in ALL_MODES:
         rt = rrt.RayTracer(teapot, rrt.default_lights(), box_filter=mode)
         _, again = level1(rt, CREATION, W, H)
-        assert_arrays_equal(again, rec, INPUTS, f"walk {mode}: the records the rays were formed from")
+        assert_same_arrays(again, rec, INPUTS, f"walk {mode}: the records the rays were formed from")
         want = {}
         for r in (False, True):
             what = f"teapot level 1, walk {mode}, max_t {max_t}, {'ROT' if r else 'no rot'}"
@@ -119,7 +80,7 @@ def test_the_mask_is_the_shadow_query_at_level_1(rrt, ob, teapot, teapot_arrays,
             frac, per = mask_figures(ref, fans[True])
             print(f"by the oracle, ROT: occluded fraction {frac:.3f}, per sample {per.min():.3f}-{per.max():.3f}")
             assert frac >= 0.15 and per.min() >= 0.10 and (1.0 - per).min() >= 0.50, (frac, per.tolist())
-            assert_same_array(want[True], ref, f"walk {mode}, max_t {max_t}, ROT: rrt_occluded_rays (= occluded) vs the oracle's intersector")
+            assert_same_bits(want[True], ref, f"walk {mode}, max_t {max_t}, ROT: rrt_occluded_rays (= occluded) vs the oracle's intersector")
 
 
 # ------------------------------------------------------------------ 2
@@ -139,7 +100,7 @@ def test_the_fallback_branch_of_the_tangent_frame(rrt, ob):
             n_fb = int(fans[False].fallback.sum())
             print(f"mirror room level 1: {len(fans[False].hit)} records, {int(fans[False].hit.sum())} hits, {n_fb} in the length(tg) == 0 branch")
             assert n_fb >= 400, f"{n_fb} hits take the length(tg) == 0 branch (< 400)"
-        assert_arrays_equal(again, rec, INPUTS, f"mirror room, walk {mode}: the records the rays were formed from")
+        assert_same_arrays(again, rec, INPUTS, f"mirror room, walk {mode}: the records the rays were formed from")
         for r in (False, True):
             what = f"mirror room level 1, walk {mode}, {'ROT' if r else 'no rot'}"
             want = assert_ambient_is_the_shadow_query(rt, rec, fans[r], rot if r else None, T8_MAX_T, what)
@@ -150,7 +111,7 @@ def test_the_fallback_branch_of_the_tangent_frame(rrt, ob):
             fb[fans[r].hit] = fans[r].fallback
             assert (want[fb] != 0).any() and (popcount(want[fb]) < 8).any(), f"{what}: the fallback hits' masks are all empty or all full"
             if mode == "lane" and r:
-                assert_same_array(want, by_oracle(oracle_for(ob, A, lights), fans[r], T8_MAX_T), f"{what}: rrt_occluded_rays (= occluded) vs the oracle's intersector")
+                assert_same_bits(want, by_oracle(oracle_for(ob, A, lights), fans[r], T8_MAX_T), f"{what}: rrt_occluded_rays (= occluded) vs the oracle's intersector")
 
 
 # ------------------------------------------------------------------ 3
@@ -176,8 +137,8 @@ def test_the_planes_of_a_frame_are_records(rrt, teapot, teapot_arrays, bump):
         assert fan.fallback.sum() >= 1000, f"{int(fan.fallback.sum())} hits take the length(tg) == 0 branch (< 1000)"
     assert (planes["material"][0] == NO_MATERIAL).all(), "row 0 of the frame is never traced: its records are misses"
     got = rt.ambient_rays(rec, T8, T8_MAX_T)
-    assert_same_array(got["occluded"], frame.reshape(-1), "occluded of the flattened planes vs the occluded plane of rt.ambient")
-    assert_same_array(got["open"], open_of(frame.reshape(-1), fan.hit, 8), "open of the flattened planes")
+    assert_same_bits(got["occluded"], frame.reshape(-1), "occluded of the flattened planes vs the occluded plane of rt.ambient")
+    assert_same_bits(got["open"], open_of(frame.reshape(-1), fan.hit, 8), "open of the flattened planes")
     assert (got["occluded"][:4 * W] == 0).all() and (got["open"][:4 * W] == 8).all(), "the records of pixels the reference never traces: mask 0, open n"
 
 
@@ -189,11 +150,11 @@ def test_sample_counts(kept):
         assert (want >> np.uint32(7)).any(), "sample 7 is never occluded: bit 31 would show nothing"
         assert (want & np.uint32(1)).any() and not (want[hit] & np.uint32(1)).all()
         one = rt.ambient_rays(rec, T8[:1], T8_MAX_T, rot=rot if r else None)
-        assert_same_array(one["occluded"], want & np.uint32(1), f"n = 1, rot {r}: bit 0 of the mask of T8")
-        assert_same_array(one["open"], open_of(want & np.uint32(1), hit, 1), f"n = 1, rot {r}: open")
+        assert_same_bits(one["occluded"], want & np.uint32(1), f"n = 1, rot {r}: bit 0 of the mask of T8")
+        assert_same_bits(one["open"], open_of(want & np.uint32(1), hit, 1), f"n = 1, rot {r}: open")
         full = rt.ambient_rays(rec, np.tile(T8, (4, 1)), T8_MAX_T, rot=rot if r else None)
-        assert_same_array(full["occluded"], want * np.uint32(0x01010101), f"n = 32, T8 four times, rot {r}: the mask of T8 in every byte")
-        assert_same_array(full["open"], np.where(hit, 4 * open_of(want, hit, 8), 32).astype(np.uint32), f"n = 32, rot {r}: open is 4 x T8's")
+        assert_same_bits(full["occluded"], want * np.uint32(0x01010101), f"n = 32, T8 four times, rot {r}: the mask of T8 in every byte")
+        assert_same_bits(full["open"], np.where(hit, 4 * open_of(want, hit, 8), 32).astype(np.uint32), f"n = 32, rot {r}: open is 4 x T8's")
 
 
 # ------------------------------------------------------------------ 5
@@ -207,7 +168,7 @@ def test_edges_of_the_batch(rrt, teapot, kept):
     for mode in FORCED_MODES:
         rt = rrt.RayTracer(teapot, rrt.default_lights(), box_filter=mode)
         whole = rt.ambient_rays(rec, T8, T8_MAX_T, rot=rot)
-        assert_same_array(whole["occluded"], want, f"walk {mode}: the whole batch")
+        assert_same_bits(whole["occluded"], want, f"walk {mode}: the whole batch")
         for n in (1, 63, 64, 65, 129):
             for start in (first, len(hit) - n):
                 sl = slice(start, start + n)
@@ -217,13 +178,13 @@ def test_edges_of_the_batch(rrt, teapot, kept):
                 stats = rt.last_stats()
                 assert (stats["width"], stats["height"], stats["rays_primary"]) == (n, 1, n), stats
                 for name in OUTPUTS:
-                    assert_same_array(part[name], whole[name][sl], f"walk {mode}: {n} records from {start}: {name} is not the batch's slice")
+                    assert_same_bits(part[name], whole[name][sl], f"walk {mode}: {n} records from {start}: {name} is not the batch's slice")
         # 64 misses, then one hit: the first wave walks nothing.  63 misses and a hit in lane 63.  Both with a hit whose reference mask has a bit set.
         for what, idx in (("64 misses, then one hit", np.concatenate([misses[:64], shadowed[5:6]])), ("a wave whose only hit is lane 63", np.concatenate([misses[:63], shadowed[7:8]]))):
             got = rt.ambient_rays(rows(rec, idx), T8, T8_MAX_T, rot=rot[idx])
             assert want[idx][-1] != 0 and (want[idx][:-1] == 0).all()
-            assert_same_array(got["occluded"], want[idx], f"walk {mode}: {what}: occluded")
-            assert_same_array(got["open"], open_of(want[idx], hit[idx], 8), f"walk {mode}: {what}: open")
+            assert_same_bits(got["occluded"], want[idx], f"walk {mode}: {what}: occluded")
+            assert_same_bits(got["open"], open_of(want[idx], hit[idx], 8), f"walk {mode}: {what}: open")
         # material == n_mats and 0xFFFFFFFF in records that were hits: mask 0, open n, nothing else moves
         edited = {k: rec[k].copy() for k in INPUTS}
         a, b = shadowed[0:len(shadowed):3], shadowed[1:len(shadowed):3]
@@ -236,8 +197,8 @@ def test_edges_of_the_batch(rrt, teapot, kept):
         gone[a] = False
         gone[b] = False
         got = rt.ambient_rays(edited, T8, T8_MAX_T, rot=rot)
-        assert_same_array(got["occluded"], want_edit, f"walk {mode}: material = n_mats and 0xFFFFFFFF in hit records: occluded")
-        assert_same_array(got["open"], open_of(want_edit, gone, 8), f"walk {mode}: material = n_mats and 0xFFFFFFFF in hit records: open")
+        assert_same_bits(got["occluded"], want_edit, f"walk {mode}: material = n_mats and 0xFFFFFFFF in hit records: occluded")
+        assert_same_bits(got["open"], open_of(want_edit, gone, 8), f"walk {mode}: material = n_mats and 0xFFFFFFFF in hit records: open")
         assert (got["open"][a] == 8).all() and (got["open"][b] == 8).all() and (want_edit != 0).sum() >= 100
         # n == 0: RRT_OK, nothing enqueued, the statistics stay
         stats = rt.last_stats()
@@ -269,7 +230,7 @@ def test_the_device_form(rrt, teapot, kept, mode):
         for name, t, ref in (("occluded", occluded, want), ("open", open_, open_of(want, hit, 8))):
             a = t.cpu().numpy()
             assert (a[:G] == SENTINEL).all() and (a[-G:] == SENTINEL).all(), f"{name}: an element outside the output was written"
-            assert_same_array(a[G:-G].view(np.uint32), ref, f"walk {mode}, rot {r}: {name} of the device form")
+            assert_same_bits(a[G:-G].view(np.uint32), ref, f"walk {mode}, rot {r}: {name} of the device form")
         assert (stats["width"], stats["height"], stats["rays_primary"]) == (n, 1, n), stats
         assert stats["filter_variant"] == rrt.VARIANT_NAMES.index(mode) and stats["kernel_ms"] > 0, stats
     # one output only: the other tensor is not touched
@@ -282,10 +243,10 @@ def test_the_device_form(rrt, teapot, kept, mode):
         stream.synchronize()
         assert (out[other].cpu().numpy() == SENTINEL).all(), f"{asked} alone: {other} was written"
         ref = want if asked == "occluded" else open_of(want, hit, 8)
-        assert_same_array(out[asked].cpu().numpy()[G:-G].view(np.uint32), ref, f"walk {mode}: {asked} alone, device form")
+        assert_same_bits(out[asked].cpu().numpy()[G:-G].view(np.uint32), ref, f"walk {mode}: {asked} alone, device form")
         one = rt.ambient_rays(rec, T8, T8_MAX_T, outputs=(asked,))                  # the host form with ONE output asked for and the other NULL, against the device form's
         assert set(one) == {asked}
-        assert_same_array(one[asked], out[asked].cpu().numpy()[G:-G].view(np.uint32), f"walk {mode}: {asked} alone, host form vs device form")
+        assert_same_bits(one[asked], out[asked].cpu().numpy()[G:-G].view(np.uint32), f"walk {mode}: {asked} alone, host form vs device form")
 
 
 # ------------------------------------------------------------------ 6
@@ -300,7 +261,7 @@ def assert_walks(make_rt, cam, n_mats, what, modes):
             rec = again
             rot = standard_rot(len(rec["material"]))
             fan = Fan(rec, n_mats, T8, rot)
-        assert_arrays_equal(again, rec, INPUTS, f"{what}, walk {mode} {kw}: the records the rays were formed from")
+        assert_same_arrays(again, rec, INPUTS, f"{what}, walk {mode} {kw}: the records the rays were formed from")
         want = assert_ambient_is_the_shadow_query(rt, rec, fan, rot, T8_MAX_T, f"{what}, walk {mode} {kw}")
         n_bits = int(popcount(want).sum())
         print(f"{what}, walk {mode} {kw}: {int(fan.hit.sum())} hits, {n_bits} of {int(fan.hit.sum()) * 8} rays occluded by rrt_occluded_rays")
@@ -364,8 +325,8 @@ def test_the_chain_from_library_calls_alone_on_the_device(rrt, teapot, kept):
     got = {name: t.cpu().numpy().view(np.uint32) for name, t in out.items()}
     assert np.array_equal(l0["hit"].cpu().numpy().astype(bool), h0)
     want, hit1 = kept["want"][True], kept["fans"][True].hit
-    assert_same_array(got["occluded"][h0], want, "the chain on the device, with ROT: occluded of the level-0 hits vs the host forms'")
-    assert_same_array(got["open"][h0], open_of(want, hit1, 8), "the chain on the device, with ROT: open of the level-0 hits")
+    assert_same_bits(got["occluded"][h0], want, "the chain on the device, with ROT: occluded of the level-0 hits vs the host forms'")
+    assert_same_bits(got["open"][h0], open_of(want, hit1, 8), "the chain on the device, with ROT: open of the level-0 hits")
     assert (~h0).sum() >= 1000 and (got["occluded"][~h0] == 0).all() and (got["open"][~h0] == 8).all(), "a dead record: mask 0, open n"
 
 
@@ -430,8 +391,8 @@ def test_refusals_leave_the_outputs_as_they_were(rrt, teapot, kept):
     assert not (occluded == PATTERN).any() and not (open_ == PATTERN).any(), "an accepted call leaves elements of its outputs unwritten"
     assert ((open_ <= 8) & (occluded < 256)).all()
     raw(C.byref(cs), C.byref(samples()), C.byref(out()))
-    assert_same_array(occluded, kept["want"][True][sl], "after the refusals: occluded")
-    assert_same_array(open_, open_of(kept["want"][True][sl], kept["fans"][True].hit[sl], 8), "after the refusals: open")
+    assert_same_bits(occluded, kept["want"][True][sl], "after the refusals: occluded")
+    assert_same_bits(open_, open_of(kept["want"][True][sl], kept["fans"][True].hit[sl], 8), "after the refusals: open")
 
 
 # ------------------------------------------------------------------ 9
@@ -451,7 +412,7 @@ def test_state_is_untouched(rrt, teapot, kept):
     big = rt.ambient_rays({k: np.tile(rec[k], (reps,) + (1,) * (rec[k].ndim - 1)) for k in INPUTS}, T8, T8_MAX_T, rot=np.tile(rot, (reps, 1)), outputs=("occluded",))
     stats = rt.last_stats()
     assert (stats["width"], stats["filter_variant"]) == (reps * len(want), small_variant), stats
-    assert_same_array(big["occluded"], np.tile(want, reps), "the batch four times over")
+    assert_same_bits(big["occluded"], np.tile(want, reps), "the batch four times over")
     rt.intersect_rays(O[:64], D[:64])
     assert rt.last_stats()["filter_variant"] == small_variant, "an ambient_rays call of 28568 records kept a per-ray variant"
     assert np.array_equal(rt.render(W, H), frame) and rt.last_stats()["filter_variant"] == variant
@@ -467,7 +428,7 @@ def test_state_is_untouched(rrt, teapot, kept):
             torch.cuda.synchronize()
             got = out.cpu().numpy().view(np.uint32)
         assert rt.last_stats()["filter_variant"] == tuned, (form, rt.last_stats(), tuned)
-        assert_same_array(got, want, f"the {form} form in the tuned variant")
+        assert_same_bits(got, want, f"the {form} form in the tuned variant")
     rt.intersect_rays(O[:64], D[:64])
     assert rt.last_stats()["filter_variant"] == tuned, "the variant kept by tune_rays changed"
     assert np.array_equal(rt.render(W, H), frame) and rt.last_stats()["filter_variant"] == variant, "the next frame, or its variant, differs"

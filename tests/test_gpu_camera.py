@@ -23,12 +23,11 @@ import pytest
 from conftest import GOLDEN
 from gpu_checks import (ALL_MODES, FORCED_MODES, MATS, N_THREADS, ORIGIN, TEX, assert_frame_close, coplanar_rays, mix4, oracle_for, oracle_pixels, plane_scene,
                         plane_scene_data, pose_dirs, traced_rows)
+from scenes import IDENTITY, TARGET, teapot_arrays, teapot_osc  # noqa: F401  (fixtures: teapot_arrays, teapot_osc)
 
 pytestmark = pytest.mark.gpu
 
-TARGET = (0.0, 1.0, 0.0)
 EYES = ((6.0, 3.0, -8.0), (-7.0, 4.0, -6.0), (9.0, 2.0, 1.0), (0.0, 9.0, -4.0), (4.0, 1.5, 7.0), (0.0, 2.0, -6.0))
-IDENTITY = dict(right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0))
 
 
 def frame_from_own_rays(rt, cam, w, h):
@@ -39,17 +38,6 @@ def frame_from_own_rays(rt, cam, w, h):
     fb = np.zeros((h, w), np.uint32)
     fb[np.ix_(rows, xs)] = mix4(cols)
     return fb
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
-def teapot_osc(ob, rrt, teapot_arrays):
-    return oracle_for(ob, teapot_arrays, rrt.default_lights())
 
 
 # ------------------------------------------------------------------ 1

@@ -12,49 +12,23 @@ import numpy as np
 import pytest
 
 from ambient_checks import T8, T8_MAX_T
-from ambient_rays_checks import INPUTS, OUTPUTS, Fan, by_shadow_query, open_of, standard_rot
-from compact_checks import (ARRAYS, DEAD_INDEX, ELEM_BYTES, NAMES, RECORD_NAMES, assert_compacted, assert_same_bytes, bits, compacted, dead, flag_patterns,
-                            scattered, selection)
+from ambient_rays_checks import INPUTS, OUTPUTS, Fan, by_shadow_query, kept_records as kept, level1, open_of, standard_rot  # noqa: F401  (fixtures: kept)
+from bitwise import assert_same_bits, bits
+from compact_checks import (ARRAYS, DEAD_INDEX, ELEM_BYTES, NAMES, RECORD_NAMES, Guarded, assert_compacted, ceil_div, compacted, dead, flag_patterns, mixed_waves,
+                            scattered, selection, to_device)
 from gpu_checks import FORCED_MODES, chain_rrt_lights, chain_scene
 from ray_surface_checks import kr_of
-from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, mirror_room, soup_scene
-from test_gpu_ambient_rays import kept, level1, rays_of, teapot_arrays  # noqa: F401  (kept, teapot_arrays: fixtures, shared with that module's tests by name)
+from scenes import CREATION, rays_of, teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
+from shade_checks import MIRROR_ROOM_LIGHTS, mirror_room, soup_scene
 
 pytestmark = pytest.mark.gpu
 
 W, H = 64, 48
 RW, RH = 32, 24
-G = 64                                                           # guard elements on both sides of a device output
+
 TILE, SCAN = 1024, 256                                           # csrc/device_scene.hpp: kCompactTile; csrc/compact.hip: kScanBlock
 BIG = 2 ** 20 + 4097                                             # 1029 tiles: five passes of the scan block
 EDGE_SIZES = (1, 2, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2047, 2049, 4097, 70001, BIG)
-
-
-def torch_dtype(torch, dtype):
-    return {np.dtype(np.float64): torch.float64, np.dtype(np.uint32): torch.int32, np.dtype(np.uint8): torch.uint8}[np.dtype(dtype)]
-
-
-def to_device(torch, a):
-    a = np.ascontiguousarray(a)
-    return torch.tensor(a.view(np.int32) if a.dtype == np.uint32 else a, device="cuda").reshape(-1)
-
-
-class Guarded:
-    """A device output of `count` elements of `dtype` between G guard elements of 0xA5 bytes on both sides."""
-
-    def __init__(self, torch, dtype, count):
-        self.dtype, self.size = np.dtype(dtype), np.dtype(dtype).itemsize
-        self.raw = torch.full(((2 * G + count) * self.size,), 0xA5, dtype=torch.uint8, device="cuda")
-        self.t = self.raw[G * self.size:(G + count) * self.size].view(torch_dtype(torch, dtype))
-
-    def read(self, what):
-        a = self.raw.cpu().numpy()
-        g = G * self.size
-        assert (a[:g] == 0xA5).all() and (a[len(a) - g:] == 0xA5).all(), f"{what}: an element outside the output was written"
-        return a[g:len(a) - g].view(self.dtype).copy()
-
-    def untouched(self):
-        return bool((self.raw == 0xA5).all().item())
 
 
 def device_compact(torch, rt, n, select, src, out_names, stream, flag=None, index=True, count=True):
@@ -75,16 +49,6 @@ def device_compact(torch, rt, n, select, src, out_names, stream, flag=None, inde
     if count:
         got["count"] = int(count_g.read("count")[0])
     return got
-
-
-def ceil_div(a, b):
-    return -(-a // b)
-
-
-def mixed_waves(sel):
-    """The number of whole 64-entry waves of a batch that hold both selected and unselected entries."""
-    w = np.asarray(sel, bool)[:len(sel) // 64 * 64].reshape(-1, 64)
-    return int((w.any(1) & ~w.all(1)).sum())
 
 
 # ------------------------------------------------------------------ 1
@@ -127,11 +91,11 @@ def test_edges_of_the_flag_mode(rrt, teapot, n):
         flag = flag_patterns(n)["a random half"]
         want = compacted(flag != 0, dict(tri=tri))
         got = device_compact(torch, rt, n, "flag", dict(tri=tri), ("tri",), stream, flag=flag, index=False, count=False)
-        assert_same_bytes(got["tri"], want["tri"], f"n = {n}: tri alone")
+        assert_same_bits(got["tri"], want["tri"], f"n = {n}: tri alone")
         got = device_compact(torch, rt, n, "flag", {}, (), stream, flag=flag, index=False)
         assert got == dict(count=want["count"]), f"n = {n}: count alone"
         got = device_compact(torch, rt, n, "flag", {}, (), stream, flag=flag, count=False)
-        assert_same_bytes(got["index"], want["index"], f"n = {n}: index alone")
+        assert_same_bits(got["index"], want["index"], f"n = {n}: index alone")
 
 
 # ------------------------------------------------------------------ 3
@@ -155,8 +119,8 @@ def test_the_synthesised_bound(rrt, teapot):
     O[keep[5]] = (-0.0, np.nan, -np.inf)
     got = rt.compact_rays({}, "flag", flag=flag, origins=O, max_t=max_t)
     assert_compacted(got, compacted(flag != 0, dict(origins=O, max_t=max_t)), "max_t given")
-    assert_same_bytes(got["max_t"][:5], special, "the special bounds, first among the survivors")
-    assert_same_bytes(got["origins"][5], np.array([-0.0, np.nan, -np.inf]), "the special origin")
+    assert_same_bits(got["max_t"][:5], special, "the special bounds, first among the survivors")
+    assert_same_bits(got["origins"][5], np.array([-0.0, np.nan, -np.inf]), "the special origin")
     assert int(bits(got["max_t"])[-1]) == 0x7FF8000000000000
 
 
@@ -228,12 +192,12 @@ def assert_padded_batch_feeds_the_ambient_stage(torch, rt, rec, rot, n_mats, wan
     assert int(count_t.cpu().numpy().view(np.uint32)[0]) == count, what
     model = compacted(hit, {k: rec[k] for k in names} if rot is None else dict({k: rec[k] for k in INPUTS}, rot=np.asarray(rot)))
     for k in names:
-        assert_same_bytes(packed[k].cpu().numpy().view(ARRAYS[k][0]).reshape(model[k].shape), model[k], f"{what}: the packed {k}")
+        assert_same_bits(packed[k].cpu().numpy().view(ARRAYS[k][0]).reshape(model[k].shape), model[k], f"{what}: the packed {k}")
     got_padded = {k: padded[k].cpu().numpy().view(np.uint32) for k in OUTPUTS}
     assert (got_padded["occluded"][count:] == 0).all() and (got_padded["open"][count:] == len(T8)).all(), f"{what}: the tail of the padded outputs is not 0 / n"
-    assert_same_bytes(got_padded["occluded"][:count], want[hit], f"{what}: the padded masks vs the original records' masks, in order")
-    assert_same_bytes(final["occluded"].cpu().numpy().view(np.uint32), want, f"{what}: occluded, scattered back")
-    assert_same_bytes(final["open"].cpu().numpy().view(np.uint32), open_of(want, hit, len(T8)), f"{what}: open, scattered back")
+    assert_same_bits(got_padded["occluded"][:count], want[hit], f"{what}: the padded masks vs the original records' masks, in order")
+    assert_same_bits(final["occluded"].cpu().numpy().view(np.uint32), want, f"{what}: occluded, scattered back")
+    assert_same_bits(final["open"].cpu().numpy().view(np.uint32), open_of(want, hit, len(T8)), f"{what}: open, scattered back")
 
 
 @pytest.mark.parametrize("mode", FORCED_MODES)
@@ -245,7 +209,7 @@ def test_the_padded_batch_feeds_the_ambient_stage(rrt, teapot, kept, mode):
         want = kept["want"][r]
         assert (want != 0).any()
         direct = rt.ambient_rays(rec, T8, T8_MAX_T, rot=kept["rot"] if r else None)
-        assert_same_bytes(direct["occluded"], want, f"walk {mode}, rot {r}: rt.ambient_rays on the original records vs the shadow query")
+        assert_same_bits(direct["occluded"], want, f"walk {mode}, rot {r}: rt.ambient_rays on the original records vs the shadow query")
         assert_padded_batch_feeds_the_ambient_stage(torch, rt, rec, kept["rot"] if r else None, kept["n_mats"], want, f"teapot level 1, walk {mode}, rot {r}")
 
 
@@ -266,7 +230,7 @@ def test_a_soup_with_group_records(rrt, teapot_arrays):
     rec = two_levels_of_records(rt, CREATION)
     rot = standard_rot(len(rec["material"]))
     want = rt.ambient_rays(rec, T8, T8_MAX_T, rot=rot)["occluded"]
-    assert_same_bytes(want, by_shadow_query(rt, Fan(rec, len(A["materials"]), T8, rot), T8_MAX_T), "soup: rt.ambient_rays vs the shadow query")
+    assert_same_bits(want, by_shadow_query(rt, Fan(rec, len(A["materials"]), T8, rot), T8_MAX_T), "soup: rt.ambient_rays vs the shadow query")
     assert (want != 0).sum() >= 50
     assert_padded_batch_feeds_the_ambient_stage(torch, rt, rec, rot, len(A["materials"]), want, "soup, levels 0 and 1")
 
@@ -282,7 +246,7 @@ def test_the_chain_shortcut_scene(rrt):
     rec = two_levels_of_records(rt, cam)
     rot = standard_rot(len(rec["material"]))
     want = rt.ambient_rays(rec, T8, T8_MAX_T, rot=rot)["occluded"]
-    assert_same_bytes(want, by_shadow_query(rt, Fan(rec, len(A["materials"]), T8, rot), T8_MAX_T), "chain scene: rt.ambient_rays vs the shadow query")
+    assert_same_bits(want, by_shadow_query(rt, Fan(rec, len(A["materials"]), T8, rot), T8_MAX_T), "chain scene: rt.ambient_rays vs the shadow query")
     assert (want != 0).sum() >= 50
     assert_padded_batch_feeds_the_ambient_stage(torch, rt, rec, rot, len(A["materials"]), want, "chain scene, levels 0 and 1")
 
@@ -321,19 +285,19 @@ def test_a_chain_on_the_device_alone(rrt, teapot, kept):
     stream.synchronize()
     assert counts.cpu().numpy().view(np.uint32).tolist() == [c1, c2]
     want_index1 = compacted(h0, {})["index"]
-    assert_same_bytes(index1.cpu().numpy().view(np.uint32), want_index1, "level 0 -> 1: index")
+    assert_same_bits(index1.cpu().numpy().view(np.uint32), want_index1, "level 0 -> 1: index")
     got1 = {k: t.cpu().numpy().view(ARRAYS[k][0]).reshape((n, 3) if ARRAYS[k][1] == 3 else (n,)) for k, t in rec1.items()}
     for k in INPUTS:
-        assert_same_bytes(got1[k][:c1], np.asarray(kept["rec"][k]), f"the first count level-1 records vs the host path's: {k}")
-        assert_same_bytes(got1[k][c1:], dead(k, n - c1), f"the tail of the level-1 records holds the miss values: {k}")
+        assert_same_bits(got1[k][:c1], np.asarray(kept["rec"][k]), f"the first count level-1 records vs the host path's: {k}")
+        assert_same_bits(got1[k][c1:], dead(k, n - c1), f"the tail of the level-1 records holds the miss values: {k}")
     full_hit1 = np.zeros(n, bool)
     full_hit1[:c1] = hit1
-    assert_same_bytes(index2.cpu().numpy().view(np.uint32), compacted(full_hit1, {})["index"], "level 1 -> 2: index")
+    assert_same_bits(index2.cpu().numpy().view(np.uint32), compacted(full_hit1, {})["index"], "level 1 -> 2: index")
     want = kept["want"][True]
     got = {k: t.cpu().numpy().view(np.uint32) for k, t in out.items()}
     assert (want[hit1] != 0).any()
-    assert_same_bytes(got["occluded"][:c2], want[hit1], "the final masks of the survivors vs the shadow query's, in order")
-    assert_same_bytes(got["open"][:c2], open_of(want, hit1, len(T8))[hit1], "the final open counts of the survivors")
+    assert_same_bits(got["occluded"][:c2], want[hit1], "the final masks of the survivors vs the shadow query's, in order")
+    assert_same_bits(got["open"][:c2], open_of(want, hit1, len(T8))[hit1], "the final open counts of the survivors")
     assert (got["occluded"][c2:] == 0).all() and (got["open"][c2:] == len(T8)).all(), "the dead tail: mask 0, open n"
 
 
@@ -357,7 +321,7 @@ def test_scatter(rrt, teapot, elem):
     named[index[index < n]] = True
     assert 1000 < named.sum() < n - 1000 and (bits(want[~named]) == bits(dst[~named])).all()
     got = rt.scatter_rays(index, src, dst.copy())
-    assert_same_bytes(got, want, f"elem_bytes {elem}: the host form")
+    assert_same_bits(got, want, f"elem_bytes {elem}: the host form")
     stream = torch.cuda.Stream()
     g = Guarded(torch, dtype, n * width)
     g.t.copy_(to_device(torch, dst))
@@ -365,14 +329,14 @@ def test_scatter(rrt, teapot, elem):
     torch.cuda.synchronize()
     rt.scatter_rays_into(index_t, src_t, g.t, stream=stream.cuda_stream)
     stream.synchronize()
-    assert_same_bytes(g.read(f"elem_bytes {elem}").reshape(shape), want, f"elem_bytes {elem}: the device form")
+    assert_same_bits(g.read(f"elem_bytes {elem}").reshape(shape), want, f"elem_bytes {elem}: the device form")
     # scatter after compact puts the selected elements back where they were
     flag = flag_patterns(n)["a random half"]
     index = rt.compact_rays({}, "flag", flag=flag)["index"]
     packed = np.concatenate([src[flag != 0], np.zeros_like(src[flag == 0])])
     back = rt.scatter_rays(index, packed, dst.copy())
-    assert_same_bytes(back[flag != 0], src[flag != 0], f"elem_bytes {elem}: scatter after compact, the selected elements")
-    assert_same_bytes(back[flag == 0], dst[flag == 0], f"elem_bytes {elem}: scatter after compact, the others keep their pattern")
+    assert_same_bits(back[flag != 0], src[flag != 0], f"elem_bytes {elem}: scatter after compact, the selected elements")
+    assert_same_bits(back[flag == 0], dst[flag == 0], f"elem_bytes {elem}: scatter after compact, the others keep their pattern")
     # an index that occurs twice: one of the two values, and no fault
     twice = np.array([2, 2, DEAD_INDEX, 0], np.uint32)
     got = rt.scatter_rays(twice, src[:4], dst[:4].copy())
@@ -397,7 +361,7 @@ def test_state_is_untouched(rrt, teapot, kept):
     assert_compacted(rt.compact_rays({k: rec[k] for k in INPUTS}, "mirror"), compacted(hit & (kr_of(dict(materials=before["materials"]), rec["material"]) > 0.0),
                                                                                          {k: rec[k] for k in INPUTS}), "MIRROR, the host form")
     back = rt.scatter_rays(first["index"], first["material"], np.full(n, 0xFFFFFFFF, np.uint32))
-    assert_same_bytes(back, np.where(hit, rec["material"], 0xFFFFFFFF).astype(np.uint32), "material, scattered back")
+    assert_same_bits(back, np.where(hit, rec["material"], 0xFFFFFFFF).astype(np.uint32), "material, scattered back")
     # refusals of the device form with a real raytracer leave the guarded outputs as they were
     src_t = {k: to_device(torch, rec[k]) for k in INPUTS}
     out = {k: Guarded(torch, ARRAYS[k][0], ARRAYS[k][1] * n) for k in INPUTS}

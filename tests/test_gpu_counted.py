@@ -11,13 +11,12 @@ import pytest
 
 from ambient_checks import T8, T8_MAX_T
 from ambient_rays_checks import INPUTS, OUTPUTS, standard_rot
-from compact_checks import ARRAYS, DEAD_INDEX, NAMES, RECORD_NAMES, assert_same_bytes, compacted, flag_patterns, scattered, selection
+from bitwise import assert_same_bits
+from compact_checks import ARRAYS, DEAD_INDEX, NAMES, RECORD_NAMES, Guarded, compacted, flag_patterns, mixed_waves, scattered, selection, to_device
 from gpu_checks import FORCED_MODES, chain_rrt_lights, chain_scene
-from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, assert_same_frame, mirror_room, soup_scene
-from test_gpu_ambient_rays import rays_of, teapot_arrays  # noqa: F401  (teapot_arrays: a fixture, shared with that module's tests by name)
-from test_gpu_compact import Guarded, mixed_waves, to_device
-from test_gpu_wavefront import mix_case
-from wavefront_checks import ORDERS, host, mix_level
+from scenes import CREATION, rays_of, teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
+from shade_checks import MIRROR_ROOM_LIGHTS, mirror_room, soup_scene
+from wavefront_checks import ORDERS, host, mix_case, mix_level
 
 pytestmark = pytest.mark.gpu
 
@@ -103,7 +102,7 @@ def assert_bounded(got, want, m, n, what):
         width = SHAPES[k][1]
         assert len(a) == width * n
         if m:
-            assert_same_bytes(a[:width * m], want[k], f"{what}: {k} of the first {m} entries vs the uncounted call with n = {m}")
+            assert_same_bits(a[:width * m], want[k], f"{what}: {k} of the first {m} entries vs the uncounted call with n = {m}")
         tail = a[width * m:].view(np.uint8)
         assert (tail == 0xA5).all(), f"{what}: {k} was written at or beyond entry {m} ({int((tail != 0xA5).sum())} bytes)"
 
@@ -137,7 +136,7 @@ def test_a_counted_ray_call(rrt, teapot, batch, name, mode):
             assert_bounded(got, want, mm, n, f"{what}, tail of the inputs = {tail}")
             runs.append(got)
         for k in out_names:
-            assert_same_bytes(runs[0][k], runs[1][k], f"{what}: {k}, the two runs")
+            assert_same_bits(runs[0][k], runs[1][k], f"{what}: {k}, the two runs")
         stats = rt.last_stats()
         assert (stats["width"], stats["height"], stats["rays_primary"]) == (n, 1, n), (what, stats)      # the host does not know m
 
@@ -199,7 +198,7 @@ def assert_counted_compaction(got, sel, src, n, m, what, synth_max_t=False):
             continue
         width = 1 if k == "index" else ARRAYS[k][1]
         if mm:
-            assert_same_bytes(a[:width * mm].reshape(np.asarray(want[k]).shape), want[k], f"{what}: {k} below the bound")
+            assert_same_bits(a[:width * mm].reshape(np.asarray(want[k]).shape), want[k], f"{what}: {k} below the bound")
         tail = a[width * mm:].view(np.uint8)
         assert (tail == 0xA5).all(), f"{what}: {k} was written at or beyond entry {mm}"
     return want.get("count", 0)
@@ -283,7 +282,7 @@ def test_a_counted_scatter(rrt, teapot, elem):
         torch.cuda.synchronize()
         rt.scatter_rays_into(index_t, src_t, g.t, stream=stream.cuda_stream, bound_t=bound_tensor(torch, m))
         stream.synchronize()
-        assert_same_bytes(g.read(f"elem_bytes {elem}").reshape(shape), want, f"elem_bytes {elem}, bound {m}")
+        assert_same_bits(g.read(f"elem_bytes {elem}").reshape(shape), want, f"elem_bytes {elem}, bound {m}")
 
 
 # ------------------------------------------------------------------ 5
@@ -308,7 +307,7 @@ def test_a_counted_mix(rrt, teapot, batch):
                              bound_t=bound_tensor(torch, m))
             stream.synchronize()
             got = g.read("colour")
-            assert_same_bytes(got[:mm], want, f"mix, {what}, bound {m}: the first {mm} entries vs the restatement")
+            assert_same_bits(got[:mm], want, f"mix, {what}, bound {m}: the first {mm} entries vs the restatement")
             assert (got[mm:] == 0xA5A5A5A5).all(), f"mix, {what}, bound {m}: an entry at or beyond the bound was written"
 
 
@@ -345,9 +344,9 @@ def assert_counted_pipeline(torch, rrt, make_rt, O, D, n_mats, what):
         stream.synchronize()
         assert int(count.cpu().numpy().view(U4)[0]) == c, f"{what}, walk {mode}"
         for k in OUTPUTS:
-            assert_same_bytes(host(final[k], U4, (n,)), want[k], f"{what}, walk {mode}: {k}, scattered back, vs rrt_ambient_rays on the raw records")
+            assert_same_bits(host(final[k], U4, (n,)), want[k], f"{what}, walk {mode}: {k}, scattered back, vs rrt_ambient_rays on the raw records")
             got = padded[k].read(k)
-            assert_same_bytes(got[:c], want[k][hit], f"{what}, walk {mode}: the padded {k} below the count")
+            assert_same_bits(got[:c], want[k][hit], f"{what}, walk {mode}: the padded {k} below the count")
             assert (got[c:] == 0xA5A5A5A5).all(), f"{what}, walk {mode}: the padded {k} was written beyond the count"
 
 
@@ -421,7 +420,7 @@ def assert_the_driver_reads_only_what_it_wrote(torch, rrt, rt, what):
                     rt.render_wavefront_into(fb, work, w, h, order=order, stream=stream.cuda_stream)
                 stream.synchronize()
                 frames.append(host(fb, U4, (h, w)))
-                assert_same_frame(frames[-1], want, f"{what}, {w}x{h}, order {order}, work memory of {fill:#04x} bytes: render_wavefront_into vs render")
+                assert_same_bits(frames[-1], want, f"{what}, {w}x{h}, order {order}, work memory of {fill:#04x} bytes: render_wavefront_into vs render")
             assert (frames[0] == frames[1]).all() and (frames[1] == frames[2]).all()
 
 

@@ -18,9 +18,8 @@ import numpy as np
 import pytest
 
 from conftest import channels
-from gpu_checks import (ALL_MODES, COLOUR_TOL, N_THREADS, POOL, ROOT_BOX, assert_frame_close, assert_walks_match, check_scene, checker,
+from gpu_checks import (ALL_MODES, COLOUR_TOL, N_THREADS, ORIGIN as TEAPOT_ORIGIN, POOL, ROOT_BOX, assert_frame_close, assert_walks_match, check_scene, checker,
                         closed_box, flat_normals, oracle_for, quad, row_dirs)
-from gpu_checks import ORIGIN as TEAPOT_ORIGIN
 
 pytestmark = pytest.mark.gpu
 W, H = 96, 72

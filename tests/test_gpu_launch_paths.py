@@ -11,8 +11,10 @@ import numpy as np
 import pytest
 
 from ambient_checks import T8, T8_MAX_T
+from bitwise import assert_same_arrays, bits
 from conftest import ASSETS
 from gpu_checks import traced_rows
+from surface_checks import traced_pixels_in
 
 pytestmark = pytest.mark.gpu
 
@@ -21,23 +23,6 @@ W2, H2 = 40, 33          # more than one row and column of tiles, and larger tha
 REGION = (3, 2, 9, 7)
 N_RAYS = 100
 GEOMETRY = ("hit", "t", "u", "v", "tri")
-
-
-def traced_pixels_in(region, w, h):
-    x0, y0, rw, rh = region
-    rows, cols = traced_rows(h), np.arange(2 * (w // 2))
-    return int(((rows >= y0) & (rows < y0 + rh)).sum()) * int(((cols >= x0) & (cols < x0 + rw)).sum())
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def assert_same_planes(got, want, what):
-    assert set(got) == set(want), what
-    for n in want:
-        assert got[n].shape == want[n].shape and (bits(got[n]) == bits(want[n])).all(), f"{what}: plane {n} differs"
 
 
 def random_rays(n, seed):
@@ -170,15 +155,15 @@ def test_the_kept_planes_grow_and_are_reused(rrt, torch, model):
     x0, y0, w, h = REGION
     crop = lambda planes: {n: np.ascontiguousarray(a[y0:y0 + h, x0:x0 + w]) for n, a in planes.items()}
     host = rrt.RayTracer(model, rrt.default_lights())
-    assert_same_planes(host.visibility(W2, H2, region=REGION), crop(full), "a small region first")
-    assert_same_planes(host.visibility(W2, H2), full, "then the whole frame")
+    assert_same_arrays(host.visibility(W2, H2, region=REGION), crop(full), what="a small region first")
+    assert_same_arrays(host.visibility(W2, H2), full, what="then the whole frame")
     # surface of the whole frame, all ten planes: the largest layout
     surf_t = device_surface_planes(torch, rrt, W2, H2, rrt.PLANES)
     rt.surface_into(surf_t, W2, H2)
     surf = planes_to_host(torch, rrt, surf_t)
-    assert_same_planes({n: surf[n] for n in rrt.PLANES}, full, "the visibility planes of the surface launch")
+    assert_same_arrays({n: surf[n] for n in rrt.PLANES}, full, what="the visibility planes of the surface launch")
     assert (surf["lights"] != 0).any() and (surf["material"] != 0xFFFFFFFF).any(), "an empty frame proves nothing"
-    assert_same_planes(host.surface(W2, H2, visibility=rrt.PLANES), surf, "all ten planes of the whole frame")
+    assert_same_arrays(host.surface(W2, H2, visibility=rrt.PLANES), surf, what="all ten planes of the whole frame")
     ys, xs = np.nonzero(full["hit"][:, :, 0])
     px, py = int(xs[0]), int(ys[0])
     got = host.pick(W2, H2, px, py)
@@ -192,16 +177,16 @@ def test_the_kept_planes_grow_and_are_reused(rrt, torch, model):
     torch.cuda.synchronize()
     fb = fb_t.cpu().numpy().view(np.uint32)
     assert (fb != 0).any() and (fb != 0x00FFFFFF).any(), "an empty region proves nothing"
-    assert_same_planes(dict(fb=host.shade(W2, H2, kept_r, region=REGION)), dict(fb=fb), "shade of the region after the pick")
+    assert_same_arrays(dict(fb=host.shade(W2, H2, kept_r, region=REGION)), dict(fb=fb), what="shade of the region after the pick")
     # ambient occlusion of the whole frame, both outputs: three inputs up, two outputs of different sizes down
     amb_t = device_ambient_outputs(torch, W2, H2)
     rt.ambient_into(amb_t, surf_t, T8, T8_MAX_T, W2, H2)
     torch.cuda.synchronize()
     amb = {n: t.cpu().numpy().view(np.uint32) for n, t in amb_t.items()}
     assert (amb["occluded"] != 0).any() and (amb["grey"] != 0).any(), "an empty frame proves nothing"
-    assert_same_planes(host.ambient(W2, H2, surf, T8, T8_MAX_T), amb, "ambient occlusion of the whole frame")
-    assert_same_planes(host.visibility(W2, H2, region=REGION, planes=("t", "tri")),
-                       {n: full[n][y0:y0 + h, x0:x0 + w] for n in ("t", "tri")}, "a small region after the rest")
+    assert_same_arrays(host.ambient(W2, H2, surf, T8, T8_MAX_T), amb, what="ambient occlusion of the whole frame")
+    assert_same_arrays(host.visibility(W2, H2, region=REGION, planes=("t", "tri")),
+                       {n: full[n][y0:y0 + h, x0:x0 + w] for n in ("t", "tri")}, what="a small region after the rest")
 
 
 def test_tune_rays_below_and_above_the_sample(rrt, torch, model):
@@ -224,7 +209,7 @@ def test_tune_rays_below_and_above_the_sample(rrt, torch, model):
         hit, t, u, v, tri = rt.intersect_rays(o, d)
         want = dict(hit=hit.astype(np.uint8), t=t, u=u, v=v, tri=tri)
         assert want["hit"].any(), "rays that all miss prove nothing"
-        assert_same_planes({k: x.cpu().numpy().view(want[k].dtype) for k, x in five.items()}, want, f"{n} rays")
+        assert_same_arrays({k: x.cpu().numpy().view(want[k].dtype) for k, x in five.items()}, want, what=f"{n} rays")
         assert np.array_equal(occ.cpu().numpy(), want["hit"]), n
 
 
@@ -246,7 +231,7 @@ def test_page_locked_and_pageable_planes_in_one_call(rrt, model):
     finally:
         for n in locked:
             assert L.rrt_host_buffer_unregister(C.c_void_p(out[n].ctypes.data)) == rrt.OK, n
-    assert_same_planes(out, want, "t and tri page-locked")
+    assert_same_arrays(out, want, what="t and tri page-locked")
 
 
 # ------------------------------------------------------------------ 4

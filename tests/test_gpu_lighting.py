@@ -15,17 +15,12 @@ import numpy as np
 import pytest
 
 from conftest import channels
-from gpu_checks import FORCED_MODES, N_THREADS, ORIGIN, ROOT_BOX, assert_frame_close, assert_walks_match, in_noise_band, oracle_for, row_dirs, sample_rays
+from gpu_checks import FORCED_MODES, N_THREADS, ORIGIN, assert_frame_close, assert_walks_match, in_noise_band, oracle_for, row_dirs, sample_rays
 from lighting_scenes import CORRIDOR_ORIGIN, SHADOW_ORIGIN, _corridor_lights, _corridor_scene, _shadow_box_scene
+from scenes import teapot_arrays_with_root as teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
 
 pytestmark = pytest.mark.gpu
 SIZES = ((160, 120), (97, 61))
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures(), root=ROOT_BOX)
 
 
 def _oracle_frame(ob, A, lights, origin, w, h, **opt):

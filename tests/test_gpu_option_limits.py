@@ -10,17 +10,15 @@ minimums sit below counts made on the CPU with the oracle alone, which are writt
 import numpy as np
 import pytest
 
-from ambient_checks import T8, T8_MAX_T, Rays, assert_same_plane
-from ambient_checks import by_oracle as plane_by_oracle
-from ambient_rays_checks import Fan, assert_same_array, open_of, standard_rot
-from ambient_rays_checks import by_oracle as fan_by_oracle
+from ambient_checks import T8, T8_MAX_T, Rays, by_oracle as plane_by_oracle
+from ambient_rays_checks import Fan, by_oracle as fan_by_oracle, open_of, standard_rot
+from bitwise import assert_same_arrays, assert_same_bits, same
 from gpu_checks import ALL_MODES, N_THREADS, POOL, assert_frame_close, mix4, oracle_for, oracle_pixels, traced_rows
 from lighting_scenes import (CORRIDOR_ORIGIN, SHADOW_ORIGIN, SIXTEEN, _corridor_lights, _corridor_scene, _shadow_box_mirror_scene, _shadow_box_scene, lights_of)
-from ray_surface_checks import assert_arrays_equal
-from shade_checks import CREATION, IDENTITY, TARGET, assert_same_frame, assert_shade_is_render
+from scenes import CREATION, IDENTITY, TARGET, rays_of, teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
+from shade_checks import assert_shade_is_render
 from shade_rays_checks import OUTPUTS, chain_levels, oracle_colours, without_mask
-from surface_checks import (EXPECTED, NO_MATERIAL, assert_planes_equal, assert_untraced_pixels, expected_planes, frame_dirs, lights_added_up, same, shade, traced_cols,
-                            traced_part)
+from surface_checks import EXPECTED, NO_MATERIAL, assert_untraced_pixels, expected_planes, frame_dirs, lights_added_up, shade, traced_cols, traced_part
 from wavefront_checks import ARRAYS, ORDERS, ROWS, alive_entries, assert_wavefront_is_render, expected_rays
 
 pytestmark = pytest.mark.gpu
@@ -35,11 +33,6 @@ REGION = {(64, 48): (6, 9, 21, 18), (97, 61): (90, 1, 7, 58), (32, 24): (5, 3, 1
 def traced_region(w, h):
     """The pixels the reference traces, as a region: its rows-order ray batch is the traced sub-samples in the planes' index order, none of them dead."""
     return (0, int(traced_rows(h)[0]), 2 * (w // 2), h - int(traced_rows(h)[0]))
-
-
-def rays_of(cam, w, h, viewport=DEFAULT_VIEWPORT):
-    d = frame_dirs(cam, w, h, viewport).reshape(-1, 3)
-    return np.ascontiguousarray(np.broadcast_to(np.asarray(cam["eye"], np.float64), d.shape)), d
 
 
 def oracle_frame(osc, cam, w, h, what, viewport=DEFAULT_VIEWPORT, neighbour=False):
@@ -71,7 +64,7 @@ def tracer(rrt, sd, lights, mode, cam=None, **opt):
 def check_planes(rt, want, w, h, what):
     """rt's surface planes, with the hit plane, are `want` on the traced pixels and the never-traced values elsewhere.  Returns the planes."""
     got = rt.surface(w, h, visibility=("hit",))
-    assert_planes_equal(traced_part(got, w, h), want, EXPECTED, what)
+    assert_same_arrays(traced_part(got, w, h), want, EXPECTED, what)
     assert_untraced_pixels(got, w, h, what)
     return got
 
@@ -88,21 +81,15 @@ def check_frame_rays_are_the_planes(rt, w, h, what, names=RECORDS):
     for name in names:
         flat = planes[name].reshape(got[name].shape)
         sel = alive if name == "albedo" else slice(None)         # (albedo of a never-traced pixel: 0 in a plane, the miss value in a ray record, rrt.h)
-        assert_arrays_equal({name: got[name][sel]}, {name: flat[sel]}, (name,), f"{what}: surface_rays(frame_rays) vs the surface planes")
+        assert_same_arrays({name: got[name][sel]}, {name: flat[sel]}, (name,), f"{what}: surface_rays(frame_rays) vs the surface planes")
     return rays, got
 
 
 def wavefront_frames(rt, w, h, frame, what):
     for order in ORDERS:
-        assert_same_frame(rt.render_wavefront(w, h, order=order), frame, f"{what}, order {order}: render_wavefront vs render")
+        assert_same_bits(rt.render_wavefront(w, h, order=order), frame, f"{what}, order {order}: render_wavefront vs render")
         x0, y0, rw, rh = REGION[(w, h)]
-        assert_same_frame(rt.render_wavefront(w, h, region=REGION[(w, h)], order=order), frame[y0:y0 + rh, x0:x0 + rw], f"{what}, order {order}, region {REGION[(w, h)]}")
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
+        assert_same_bits(rt.render_wavefront(w, h, region=REGION[(w, h)], order=order), frame[y0:y0 + rh, x0:x0 + rw], f"{what}, order {order}, region {REGION[(w, h)]}")
 
 
 # ------------------------------------------------------------------ A: the viewport in every kernel that forms a primary ray
@@ -162,11 +149,11 @@ def test_viewport_rays_and_planes(rrt, teapot, teapot_oracle_answers, vp, w, h, 
         rt = tracer(rrt, teapot, rrt.default_lights(), mode, cam, viewport=vp)
         for order in ORDERS:
             for region in (None, REGION[(w, h)]):
-                assert_arrays_equal(rt.frame_rays(w, h, region=region, order=order), expected_rays(cam, w, h, region, order, viewport=vp), ARRAYS,
+                assert_same_arrays(rt.frame_rays(w, h, region=region, order=order), expected_rays(cam, w, h, region, order, viewport=vp), ARRAYS,
                                     f"{what}, order {order}, region {region}: frame_rays vs the restatement")
         check_frame_rays_are_the_planes(rt, w, h, what)
         check_planes(rt, ref, w, h, what)
-        assert_planes_equal(traced_part(rt.visibility(w, h, planes=VISIBLE), w, h), ref, VISIBLE, f"{what}: visibility")
+        assert_same_arrays(traced_part(rt.visibility(w, h, planes=VISIBLE), w, h), ref, VISIBLE, f"{what}: visibility")
         for px, py in pixels:
             got, want = rt.pick(w, h, px, py), {n: ref[n][py - rows[0], px, 0] for n in VISIBLE}
             assert got["hit"] == bool(want["hit"]) and got["tri"] == want["tri"] and all(same(np.float64(got[n]), want[n]) for n in "tuv"), \
@@ -195,7 +182,7 @@ def test_viewport_frames(rrt, teapot, teapot_oracle_answers, vp, w, h, k):
         d = assert_frame_close(frame, ref, f"{what}: render vs the oracle")
         print(f"{what}: {int((d > 0).sum())} pixels not bit-equal to the oracle")
         wavefront_frames(rt, w, h, frame, what)
-        assert_same_frame(rt.render_progressive(w, h, chunk_rows=13), frame, f"{what}: render_progressive vs render")
+        assert_same_bits(rt.render_progressive(w, h, chunk_rows=13), frame, f"{what}: render_progressive vs render")
         for world in (2, 3):
             gathered = torch.empty((world, rrt.tiles_per_rank(w, h, world) * 64), dtype=torch.int32, device="cuda")
             for r in range(world):
@@ -203,7 +190,7 @@ def test_viewport_frames(rrt, teapot, teapot_oracle_answers, vp, w, h, k):
             fb = torch.empty((h, w), dtype=torch.int32, device="cuda")
             rt.detile_into(gathered, fb, w, h, world)
             torch.cuda.synchronize()
-            assert_same_frame(fb.cpu().numpy().view(np.uint32), frame, f"{what}: the tiles of {world} ranks, detiled, vs render")
+            assert_same_bits(fb.cpu().numpy().view(np.uint32), frame, f"{what}: the tiles of {world} ranks, detiled, vs render")
 
 
 # ------------------------------------------------------------------ B: sixteen lights through the kept masks
@@ -279,7 +266,7 @@ def test_sixteen_lights_in_the_kept_masks(rrt, shadow_box, k):
         check_planes(rt, ref, W, H, what)
         _, rec = check_frame_rays_are_the_planes(rt, W, H, what)
         alive = alive_entries(W, H, None, ROWS)
-        assert_arrays_equal({"lights": rec["lights"][alive]}, {"lights": ref["lights"].reshape(-1)}, ("lights",), f"{what}: lights of surface_rays(frame_rays) vs the oracle")
+        assert_same_arrays({"lights": rec["lights"][alive]}, {"lights": ref["lights"].reshape(-1)}, ("lights",), f"{what}: lights of surface_rays(frame_rays) vs the oracle")
 
 
 @pytest.mark.parametrize("k", (0, 1), ids=SHADOW_IDS)
@@ -302,13 +289,13 @@ def test_sixteen_lights_shaded_from_the_kept_masks(rrt, shadow_box, k):
         rec = rt.surface_rays(rays["origins"], rays["dirs"], rays["max_t"])
         for name, p in (("with the mask", rec), ("without the mask", without_mask(rec))):
             colours = rt.shade_rays(rays["dirs"], p)["colour"]
-            assert_same_frame(rt.mix_pixels(colours, W, H), frame, f"{what}: mix_pixels(shade_rays {name}) vs render")
+            assert_same_bits(rt.mix_pixels(colours, W, H), frame, f"{what}: mix_pixels(shade_rays {name}) vs render")
         # bits 16 to 31 are no lights, in a plane and in a ray record
         junk = np.uint32(0xFFFF0000) & (np.arange(planes["lights"].size, dtype=np.uint32).reshape(planes["lights"].shape) * np.uint32(0x9E3779B1))
         junk |= np.uint32(0x00010000)                                                             # (bit 16, the one above the last light, everywhere)
-        assert_same_frame(rt.shade(W, H, dict(planes, lights=planes["lights"] | junk)), frame, f"{what}: shade with junk in bits 16 to 31 of the mask")
+        assert_same_bits(rt.shade(W, H, dict(planes, lights=planes["lights"] | junk)), frame, f"{what}: shade with junk in bits 16 to 31 of the mask")
         colours = rt.shade_rays(rays["dirs"], dict(rec, lights=rec["lights"] | junk.reshape(-1)))["colour"]
-        assert_same_frame(rt.mix_pixels(colours, W, H), frame, f"{what}: shade_rays with junk in bits 16 to 31 of the mask")
+        assert_same_bits(rt.mix_pixels(colours, W, H), frame, f"{what}: shade_rays with junk in bits 16 to 31 of the mask")
         # the planes suffice: numpy Phong over the lights [0, ctz(~mask)) is the frame
         seen = traced_part(planes, W, H)
         assert not any(m["kr"] > 0.0 for m in A["materials"]), "the shadow box has a mirror: the numpy shader does not follow reflections"
@@ -332,11 +319,11 @@ def test_set_lights_between_sixteen_fifteen_and_none(rrt, shadow_box, k):
             rt.set_lights(lights[:n])
             fresh = tracer(rrt, sd, lights[:n], mode, cam)
             frame, planes = assert_shade_is_render(rt, W, H, what)
-            assert_same_frame(frame, fresh.render(W, H), f"{what}: render vs a fresh raytracer's")
+            assert_same_bits(frame, fresh.render(W, H), f"{what}: render vs a fresh raytracer's")
             want = fresh.surface(W, H, visibility=("albedo",))
-            assert_planes_equal(planes, want, want.keys(), f"{what}: planes vs a fresh raytracer's")
+            assert_same_arrays(planes, want, want.keys(), f"{what}: planes vs a fresh raytracer's")
             if n:
-                assert_planes_equal(traced_part(planes, W, H), get("planes", k, n), ("lights",), f"{what}: the lights plane vs the oracle")
+                assert_same_arrays(traced_part(planes, W, H), get("planes", k, n), ("lights",), f"{what}: the lights plane vs the oracle")
                 assert_frame_close(frame, get("frame", k, n), f"{what}: render vs the oracle")
             else:
                 assert (planes["lights"] == 0).all(), f"{what}: {int((planes['lights'] != 0).sum())} masks are not 0"
@@ -395,7 +382,7 @@ def test_deep_reflections_from_kept_buffers_and_by_generations(rrt, corridor, de
         d = assert_frame_close(frame, ref, f"{what}: render vs the oracle")
         print(f"{what}: {int((d > 0).sum())} pixels not bit-equal to the oracle")
         assert_frame_close(rt.get_ray_colours(O, D), ray_ref, f"{what}: get_ray_colours of the frame's rays vs the oracle's get_ray_colour")
-        assert_same_frame(assert_wavefront_is_render(rrt, torch, rt, w, h, REGION[(w, h)], what, mode), frame, f"{what}: the frame of assert_wavefront_is_render")
+        assert_same_bits(assert_wavefront_is_render(rrt, torch, rt, w, h, REGION[(w, h)], what, mode), frame, f"{what}: the frame of assert_wavefront_is_render")
 
 
 def test_every_level_of_a_depth_8_chain(rrt, corridor):
@@ -434,7 +421,7 @@ def test_every_level_of_a_depth_8_chain(rrt, corridor):
             bad = colour != want
             assert not bad.any(), f"walk {mode}, level {k}: mix_rays of local, kr and the level below differs from get_ray_colours on {int(bad.sum())} of {bad.size} rays"
             below = colour
-        assert_same_frame(rt.mix_pixels(below, W, H, region=region), frame[y0:y0 + rh, x0:x0 + rw], f"walk {mode}: the unwind by mix_rays and mix_pixels vs render")
+        assert_same_bits(rt.mix_pixels(below, W, H, region=region), frame[y0:y0 + rh, x0:x0 + rw], f"walk {mode}: the unwind by mix_rays and mix_pixels vs render")
         if mode is None:                                                                          # depth is read: level 1 at depth 1 is not level 1 at depth 0
             o, d, planes, _ = levels[1]
             n = unequal(rt.shade_rays(d, planes, depth=1)["colour"], rt.shade_rays(d, planes, depth=0)["colour"])
@@ -473,7 +460,7 @@ def test_everything_at_once(rrt, ob):
         frame, _ = assert_shade_is_render(rt, W, H, f"{what}, walk {mode}")
         d = assert_frame_close(frame, ref, f"{what}, walk {mode}: render vs the oracle")
         print(f"walk {mode}: {int((d > 0).sum())} pixels not bit-equal to the oracle")
-        assert_same_frame(assert_wavefront_is_render(rrt, torch, rt, W, H, REGION[(W, H)], f"{what}, walk {mode}", mode), frame, f"walk {mode}: the frame of assert_wavefront_is_render")
+        assert_same_bits(assert_wavefront_is_render(rrt, torch, rt, W, H, REGION[(W, H)], f"{what}, walk {mode}", mode), frame, f"walk {mode}: the frame of assert_wavefront_is_render")
 
 
 # ------------------------------------------------------------------ E: ambient occlusion at another surface offset
@@ -489,7 +476,7 @@ def ambient_answers(osc, planes, n_mats, offset, rotated):
     """The oracle's T8 masks of the hits of `planes` -- rt.surface's, [h][w][4] -- at `offset`, without or with the standard rotation per record, computed once
     per (offset, rotated) and shared by the cases (read-only).  The offset option moves no plane the rays are formed from: every call's planes are the first's."""
     kept = _ambient.setdefault("planes", {n: planes[n].copy() for n in AMBIENT_INPUTS})
-    assert_planes_equal(planes, kept, AMBIENT_INPUTS, f"the planes at offset {offset} vs the planes of the first case")
+    assert_same_arrays(planes, kept, AMBIENT_INPUTS, f"the planes at offset {offset} vs the planes of the first case")
     if (offset, rotated) not in _ambient:
         if rotated:
             rec = {n: kept[n].reshape((-1, 3) if n != "material" else (-1,)) for n in AMBIENT_INPUTS}
@@ -525,10 +512,10 @@ def test_ambient_occlusion_at_another_offset(rrt, ob, teapot, teapot_arrays, off
             assert moved >= least, f"by the oracle the mask differs from the {'unrotated' if rotated else 'offset-1e-4'} mask on {moved} samples (< {least})"
         if rotated:
             got = rt.ambient_rays(rec, T8, T8_MAX_T, rot=standard_rot(len(rec["material"])))
-            assert_same_array(got["occluded"], want.reshape(-1), f"{what}: ambient_rays with a rotation vs the oracle's intersector")
+            assert_same_bits(got["occluded"], want.reshape(-1), f"{what}: ambient_rays with a rotation vs the oracle's intersector")
         else:
             got = rt.ambient(W, H, planes, T8, T8_MAX_T, outputs=("occluded",))["occluded"]
-            assert_same_plane(got, want, f"{what}: ambient vs the oracle's intersector")
+            assert_same_bits(got, want, f"{what}: ambient vs the oracle's intersector")
             got = rt.ambient_rays(rec, T8, T8_MAX_T)
-            assert_same_array(got["occluded"], want.reshape(-1), f"{what}: ambient_rays of the flattened planes vs the oracle's intersector, and so ambient")
-        assert_same_array(got["open"], open_of(want.reshape(-1), hit.reshape(-1), len(T8)), f"{what}: open")
+            assert_same_bits(got["occluded"], want.reshape(-1), f"{what}: ambient_rays of the flattened planes vs the oracle's intersector, and so ambient")
+        assert_same_bits(got["open"], open_of(want.reshape(-1), hit.reshape(-1), len(T8)), f"{what}: open")

@@ -9,19 +9,16 @@ All comparisons are bit for bit.  Oracle answers are computed once per module an
 import numpy as np
 import pytest
 
+from bitwise import bits
 from gpu_checks import ALL_MODES, FORCED_MODES, POOL, oracle_for, row_dirs, sample_rays, traced_rows
-from test_gpu_shadow_exit import CAMERA, LIGHT_ABOVE, LIGHT_ON_FLOOR, OFFSET, _arrays, _lights, _primary_rays
+from lighting_scenes import (SHADOW_EXIT_CAMERA as CAMERA, SHADOW_EXIT_LIGHT_ABOVE as LIGHT_ABOVE, SHADOW_EXIT_LIGHT_ON_FLOOR as LIGHT_ON_FLOOR,
+                             SHADOW_EXIT_OFFSET as OFFSET, shadow_exit_arrays as _arrays, shadow_exit_lights as _lights, shadow_exit_rays as _primary_rays)
 
 pytestmark = pytest.mark.gpu
 
 NO_TRI = 0xFFFFFFFF
 # rays of part 1, counted with the CPU oracle: light -> (rays, occluded with max_t, occluded with +inf)
 CLASS_COUNTS = {LIGHT_ABOVE: (109, 54, 109), LIGHT_ON_FLOOR: (109, 27, 32)}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
 def oracle_hits(osc, O, D, M=None):

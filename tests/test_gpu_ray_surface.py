@@ -14,28 +14,20 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from bitwise import assert_same_arrays, same
 from gpu_checks import (ALL_MODES, CHAIN_CAMERA, CHAIN_LIGHTS, FORCED_MODES, ORIGIN, assert_frame_close, chain_main_rays, chain_rrt_lights, chain_scene, mix4,
                         oracle_for, sample_rays, traced_rows)
-from ray_surface_checks import (DTYPES, NAMES, VECTORS, HostChain, assert_arrays_equal, assert_miss_values, expected_ray_planes, follow_chain, kr_of, kr_table,
-                                reflected, rows)
-from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, TARGET, mirror_room, soup_scene
-from surface_checks import frame_dirs, length, light_vec, same, traced_cols, traced_part
+from ray_surface_checks import (NAMES, SENTINEL, VECTORS, HostChain, assert_miss_values, device_arrays, expected_ray_planes, follow_chain, kr_of, kr_table, reflected,
+                                rows, to_host)
+from scenes import CREATION, MOVED_EYE, pose, posed, room, teapot_arrays, teapot_osc  # noqa: F401  (fixtures: room, teapot_arrays, teapot_osc)
+from shade_checks import soup_scene
+from surface_checks import frame_dirs, length, light_vec, traced_cols, traced_part
 
 pytestmark = pytest.mark.gpu
 
-MOVED_EYE = (9.0, 2.0, 1.0)
 W, H = 64, 48
 RW, RH = 32, 24                                                  # the mirror room's frame
 SHARED = ("hit", "t", "u", "v", "tri", "albedo", "point", "normal", "material", "lights")   # what rrt_surface_rays shares with the frame planes
-
-
-def pose(rrt, k):
-    return CREATION if k == 0 else rrt.look_at(MOVED_EYE, TARGET)
-
-
-def posed(rt, cam):
-    rt.set_camera(**cam)
-    return rt
 
 
 def flat(planes):
@@ -49,26 +41,6 @@ def only(planes, names=NAMES):
 
 def mirrors(A, planes):
     return planes["hit"].astype(bool) & (kr_of(A, planes["material"]) > 0.0)
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
-def teapot_osc(ob, rrt, teapot_arrays):
-    return oracle_for(ob, teapot_arrays, rrt.default_lights())
-
-
-@pytest.fixture(scope="module")
-def room(rrt, ob):
-    """(arrays, lights, SceneData, oracle scene) of shade_checks.mirror_room with MIRROR_ROOM_LIGHTS"""
-    A = mirror_room()
-    lights = [rrt.Light(k, i, rrt.Vector3d(*v)) for k, i, v in MIRROR_ROOM_LIGHTS]
-    sd = rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"])
-    return A, lights, sd, oracle_for(ob, A, lights)
 
 
 # ------------------------------------------------------------------ 1
@@ -88,7 +60,7 @@ def test_primary_rays_of_a_frame_are_the_surface_planes(rrt, teapot, w, h, k):
         assert behind_break >= 40 and before_break >= 15, (behind_break, before_break)
         got = rt.surface_rays(np.broadcast_to(np.asarray(cam["eye"]), d.shape), d)
         assert set(got) == set(NAMES)
-        assert_arrays_equal(flat(only(got, SHARED)), flat(only(want, SHARED)), SHARED, f"{w}x{h}, pose {k}, walk {mode}")
+        assert_same_arrays(flat(only(got, SHARED)), flat(only(want, SHARED)), SHARED, f"{w}x{h}, pose {k}, walk {mode}")
         stats = rt.last_stats()
         assert (stats["width"], stats["height"], stats["rays_primary"]) == (hit.size, 1, hit.size) and stats["kernel_ms"] > 0, stats
 
@@ -104,7 +76,7 @@ def check_two_levels(rrt, make_rt, osc, A, lights, eye, d, what, min_rays, min_h
         l0 = rt.surface_rays(np.broadcast_to(np.asarray(eye, np.float64), d.shape), d)
         if ref0 is None:
             ref0 = expected_ray_planes(osc, A, lights, eye, d)
-        assert_arrays_equal(l0, ref0, NAMES, f"{what}, level 0, walk {mode}")
+        assert_same_arrays(l0, ref0, NAMES, f"{what}, level 0, walk {mode}")
         on = mirrors(A, ref0)
         o1, d1 = l0["next_origin"][on], l0["next_dir"][on]
         assert same(d1, reflected(d[on], l0["normal"][on])) and same(o1, l0["point"][on] + l0["normal"][on] * 1e-4), f"{what}, walk {mode}: the next ray is not the restatement"
@@ -116,7 +88,7 @@ def check_two_levels(rrt, make_rt, osc, A, lights, eye, d, what, min_rays, min_h
             print(f"{what}: level 0 {len(d)} rays, {int(ref0['hit'].sum())} hit, {int(on.sum())} on a mirror; level 1 {len(d1)} rays, {int(hit1.sum())} hit by the oracle, "
                   f"{n_mirror} of them on a mirror again, masks {np.unique(ref1['lights'][hit1]).tolist()}")
             assert len(d1) >= min_rays and hit1.sum() >= min_hits and n_mirror >= min_mirror, (len(d1), int(hit1.sum()), n_mirror)
-        assert_arrays_equal(l1, ref1, NAMES, f"{what}, level 1, walk {mode}")
+        assert_same_arrays(l1, ref1, NAMES, f"{what}, level 1, walk {mode}")
 
 
 def test_rays_that_do_not_start_at_the_eye_equal_the_oracle(rrt, teapot, teapot_arrays, teapot_osc):
@@ -150,7 +122,7 @@ def test_it_is_the_other_per_ray_calls(rrt, teapot, teapot_osc):
         rt = rrt.RayTracer(teapot, lights, box_filter=mode)
         got = rt.surface_rays(O, D, B)
         hit, t, u, v, tri = rt.intersect_rays(O, D, B)
-        assert_arrays_equal(got, dict(hit=hit.astype(np.uint8), t=t, u=u, v=v, tri=tri), ("hit", "t", "u", "v", "tri"), f"walk {mode}: against intersect_rays")
+        assert_same_arrays(got, dict(hit=hit.astype(np.uint8), t=t, u=u, v=v, tri=tri), ("hit", "t", "u", "v", "tri"), f"walk {mode}: against intersect_rays")
         assert same(hit, by_oracle), f"walk {mode}: hit differs from the oracle's on {int((hit != by_oracle).sum())} rays"
         assert_miss_values(rows(got, dead), slice(None), f"walk {mode}: a NaN or non-positive bound")
         assert_miss_values(rows(got, ~hit), slice(None), f"walk {mode}: a miss")
@@ -198,17 +170,6 @@ def test_the_outputs_suffice_to_follow_the_recursion(rrt, teapot, teapot_arrays,
 
 
 # ------------------------------------------------------------------ 5
-SENTINEL = dict(hit=0xA5, t=-12345.5, u=-12345.5, v=-12345.5, tri=-1515870811, albedo=-1515870811, point=-12345.5, normal=-12345.5, material=-1515870811,
-                lights=-1515870811, next_origin=-12345.5, next_dir=-12345.5)
-
-
-def device_arrays(torch, n, names=NAMES):
-    kinds = {np.uint8: torch.uint8, np.float64: torch.float64, np.uint32: torch.int32}
-    return {name: torch.full((n * (3 if name in VECTORS else 1),), SENTINEL[name], dtype=kinds[DTYPES[name]], device="cuda") for name in names}
-
-
-def to_host(tensors, n):
-    return {name: t.cpu().numpy().view(DTYPES[name]).reshape((n, 3) if name in VECTORS else (n,)) for name, t in tensors.items()}
 
 
 class DeviceChain:
@@ -264,7 +225,7 @@ def test_the_device_form(rrt, room):
     stats = rt.last_stats()                                                                # (waits for the launch's second event)
     stream.synchronize()
     got = to_host(out, n)
-    assert_arrays_equal(got, want, subset, "surface_rays_into, three outputs")
+    assert_same_arrays(got, want, subset, "surface_rays_into, three outputs")
     for name in set(NAMES) - set(subset):
         assert (out[name].cpu().numpy() == np.array(SENTINEL[name]).astype(out[name].cpu().numpy().dtype)).all(), f"array {name} was not passed and was written"
     assert (stats["width"], stats["height"], stats["rays_primary"], stats["filter_variant"]) == (n, 1, n, ray_variant) and stats["kernel_ms"] > 0, stats
@@ -273,7 +234,7 @@ def test_the_device_form(rrt, room):
     out = device_arrays(torch, n)
     rt.surface_rays_into(o_t, d_t, out, torch.tensor(bound, device="cuda"), stream=stream.cuda_stream)
     stream.synchronize()
-    assert_arrays_equal(to_host(out, n), rt.surface_rays(O, d, bound), NAMES, "surface_rays_into, twelve outputs and max_t")
+    assert_same_arrays(to_host(out, n), rt.surface_rays(O, d, bound), NAMES, "surface_rays_into, twelve outputs and max_t")
     # the host form with ONE array asked for and eleven NULL, against the device form's twelve
     out = device_arrays(torch, n)
     rt.surface_rays_into(o_t, d_t, out, stream=stream.cuda_stream)
@@ -282,7 +243,7 @@ def test_the_device_form(rrt, room):
     for name in NAMES:
         one = rt.surface_rays(O, d, planes=(name,))
         assert set(one) == {name}
-        assert_arrays_equal(one, twelve, (name,), f"array {name} alone, host form vs surface_rays_into")
+        assert_same_arrays(one, twelve, (name,), f"array {name} alone, host form vs surface_rays_into")
     # the chain of part 4 on the device, joined by a boolean index and by a max_t of 0.0 for the dead rays
     host_cols, host_alive = follow_chain(HostChain(rt, O, d), A, lights)
     for compact in (True, False):
@@ -316,7 +277,7 @@ def rays4096(rrt, teapot):
 
 def assert_follows(rt, fresh, O, D, what):
     got, want = rt.surface_rays(O, D), fresh.surface_rays(O, D)
-    assert_arrays_equal(got, want, NAMES, what)
+    assert_same_arrays(got, want, NAMES, what)
     return got
 
 
@@ -336,7 +297,7 @@ def test_scene_changes_are_followed(rrt, teapot, teapot_arrays, rays4096):
             rt.set_lights(new)
             got = assert_follows(rt, rrt.RayTracer(teapot, new, box_filter=mode), O, D, f"walk {mode}: {what}")
             assert (got["lights"] != base["lights"]).sum() >= 100, f"{what} changes the mask on {int((got['lights'] != base['lights']).sum())} rays only"
-            assert_arrays_equal(got, base, [n for n in NAMES if n != "lights"], f"walk {mode}: {what} changes the mask only")
+            assert_same_arrays(got, base, [n for n in NAMES if n != "lights"], f"walk {mode}: {what} changes the mask only")
         rt.set_lights(lights)
         # materials: a bump map removed, a colour texture changed
         mats = [dict(m) for m in A["materials"]]                                          # (the rays see materials 0, 2 and 3 of the teapot's four)
@@ -347,9 +308,9 @@ def test_scene_changes_are_followed(rrt, teapot, teapot_arrays, rays4096):
         fresh = rrt.RayTracer(rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], mats, A["textures"]), lights, box_filter=mode)
         got = assert_follows(rt, fresh, O, D, f"walk {mode}: new materials")
         assert (got["albedo"] != base["albedo"]).sum() >= 50 and (got["normal"] != base["normal"]).any(1).sum() >= 50
-        assert_arrays_equal(got, base, ("hit", "t", "u", "v", "tri", "point", "material"), f"walk {mode}: new materials leave the geometry alone")
+        assert_same_arrays(got, base, ("hit", "t", "u", "v", "tri", "point", "material"), f"walk {mode}: new materials leave the geometry alone")
         rt.set_materials(A["materials"])
-        assert_arrays_equal(rt.surface_rays(O, D), base, NAMES, f"walk {mode}: the first materials again")
+        assert_same_arrays(rt.surface_rays(O, D), base, NAMES, f"walk {mode}: the first materials again")
         # triangles: the teapot shifted
         shifted = A["pos"] + np.array([0.25, -0.125, 0.5])
         rt.set_triangles(shifted, A["uv"], A["nrm"], A["mat"])
@@ -366,7 +327,7 @@ def test_the_surface_offset_option_is_followed(rrt, teapot, rays4096):
         rt = rrt.RayTracer(teapot, lights, surface_offset=1e-2, box_filter=mode)
         got = rt.surface_rays(O, D)
         hit = got["hit"].astype(bool)
-        assert_arrays_equal(got, base, [n for n in NAMES if n not in ("lights", "next_origin")], f"walk {mode}: the offset moves next_origin and the shadow rays only")
+        assert_same_arrays(got, base, [n for n in NAMES if n not in ("lights", "next_origin")], f"walk {mode}: the offset moves next_origin and the shadow rays only")
         assert same(got["next_origin"][hit], got["point"][hit] + got["normal"][hit] * 1e-2), f"walk {mode}: next_origin is not point + normal * 1e-2"
         assert (got["lights"] != base["lights"]).sum() >= 1, "the larger offset changes no mask"
         P, Q, m = got["point"][hit], got["next_origin"][hit], got["lights"][hit]
@@ -413,8 +374,8 @@ def test_the_chain_scene_equals_the_oracle(rrt, ob):
         rt = rrt.RayTracer(sd, chain_rrt_lights(rrt), rrt.Vector3d(*CHAIN_CAMERA), box_filter=mode, chain_shortcut=shortcut)
         assert rt.chain_info["n_chains"] >= 1, rt.chain_info
         l0 = rt.surface_rays(O, D, M)
-        assert_arrays_equal(l0, ref0, NAMES, f"chain scene, level 0, walk {mode}, shortcut {shortcut}")
-        assert_arrays_equal(rt.surface_rays(l0["next_origin"][hit0], l0["next_dir"][hit0]), ref1, NAMES, f"chain scene, level 1, walk {mode}, shortcut {shortcut}")
+        assert_same_arrays(l0, ref0, NAMES, f"chain scene, level 0, walk {mode}, shortcut {shortcut}")
+        assert_same_arrays(rt.surface_rays(l0["next_origin"][hit0], l0["next_dir"][hit0]), ref1, NAMES, f"chain scene, level 1, walk {mode}, shortcut {shortcut}")
 
 
 CHAIN_MIN = (600, 300)                                            # rays and level-0 hits (the oracle counts 644 and 309; the level-1 rays leave the scene: 309 misses)
@@ -433,7 +394,7 @@ def test_edges_of_the_batch(rrt, teapot):
         for n in (1, 63, 64, 65, 129):
             for start in (0, 300 - n):
                 part = rt.surface_rays(o[start:start + n], d[start:start + n])
-                assert_arrays_equal(part, rows(whole, slice(start, start + n)), NAMES, f"walk {mode}: {n} rays from {start}")
+                assert_same_arrays(part, rows(whole, slice(start, start + n)), NAMES, f"walk {mode}: {n} rays from {start}")
         # misses only
         up = np.tile([0.0, 1.0, 0.0], (130, 1))
         away = rt.surface_rays(o[:130], up)

@@ -9,21 +9,23 @@ comparison asserts that its batch holds hits, misses and lights that are and are
 import numpy as np
 import pytest
 
+from bitwise import assert_same_arrays, same
+from compact_checks import to_device
 from gpu_checks import CHAIN_CAMERA, CHAIN_LIGHTS, FORCED_MODES, ORIGIN, chain_main_rays, chain_rrt_lights, chain_scene, oracle_for, traced_rows
-from ray_surface_checks import DTYPES, NAMES, VECTORS, assert_arrays_equal, assert_miss_values, expected_ray_planes, rows
-from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, TARGET, mirror_room, soup_scene
-from surface_checks import frame_dirs, same, traced_cols
+from ray_surface_checks import DTYPES, NAMES, SENTINEL, VECTORS, assert_miss_values, device_arrays, expected_ray_planes, rows, to_host
+from scenes import CREATION, MOVED_EYE, TARGET, teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
+from shade_checks import MIRROR_ROOM_LIGHTS, mirror_room, soup_scene
+from surface_checks import frame_dirs, traced_cols
 
 pytestmark = pytest.mark.gpu
 
 KEPT = ("t", "u", "v", "tri")                                    # what the call reads
 OUTPUTS = NAMES[5:]                                              # what it writes: albedo, point, normal, material, lights, next_origin, next_dir
 WALK_FREE = tuple(n for n in OUTPUTS if n != "lights")
-MOVED_EYE = (9.0, 2.0, 1.0)
+
 W, H = 64, 48
 RW, RH = 32, 24
-SENTINEL = dict(hit=0xA5, t=-12345.5, u=-12345.5, v=-12345.5, tri=-1515870811, albedo=-1515870811, point=-12345.5, normal=-12345.5, material=-1515870811,
-                lights=-1515870811, next_origin=-12345.5, next_dir=-12345.5)
+
 T8 = np.array([[0.0, 0.0, 1.0], [0.6, 0.0, 0.8], [-0.6, 0.0, 0.8], [0.0, 0.6, 0.8], [0.0, -0.6, 0.8], [0.8, 0.0, 0.6], [0.0, 0.8, 0.6], [-0.48, -0.64, 0.6]])
 
 
@@ -38,20 +40,14 @@ def assert_resolves_to_the_fused_call(rt, O, D, M, what, min_hits, min_misses=1)
     want = rt.surface_rays(O, D, M)
     kept = kept_of(rt, O, D, M)
     hit = want["hit"].astype(bool)
-    assert_arrays_equal(kept, want, ("hit",) + KEPT, f"{what}: intersect_rays vs surface_rays")
+    assert_same_arrays(kept, want, ("hit",) + KEPT, f"{what}: intersect_rays vs surface_rays")
     assert hit.sum() >= min_hits and (~hit).sum() >= min_misses, f"{what}: {int(hit.sum())} hits, {int((~hit).sum())} misses"
     got = rt.resolve_hits(O, D, kept)
     assert tuple(got) == OUTPUTS
-    assert_arrays_equal(got, want, OUTPUTS, what)
+    assert_same_arrays(got, want, OUTPUTS, what)
     stats = rt.last_stats()
     assert (stats["width"], stats["height"], stats["rays_primary"]) == (len(D), 1, len(D)) and stats["kernel_ms"] > 0, stats
     return kept, want
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
 
 
 @pytest.fixture(scope="module")
@@ -92,7 +88,7 @@ def test_teapot_rays_resolve_to_the_fused_call_and_to_the_oracle(rrt, teapot, ra
     dark = int((hit & ((m >> 1) & 1 == 0)).sum()), int((hit & ((m >> 2) & 1 == 0)).sum())
     assert bounded_away >= 100 and min(dark) >= 5, (bounded_away, dark)
     got = rt.resolve_hits(O, D, kept)
-    assert_arrays_equal(dict(kept, **got), teapot_expected, NAMES, f"teapot, walk {mode}: against the oracle")
+    assert_same_arrays(dict(kept, **got), teapot_expected, NAMES, f"teapot, walk {mode}: against the oracle")
     assert teapot_expected["bumped"].sum() >= 50, "no hit of the batch goes through a bump map"
 
 
@@ -126,7 +122,7 @@ def test_the_mirror_room_the_soup_and_the_chain_scene(rrt, ob, teapot_arrays):
     for mode, shortcut in [(m, True) for m in FORCED_MODES] + [("bundle", False)]:
         rt = rrt.RayTracer(sd, chain_rrt_lights(rrt), rrt.Vector3d(*CHAIN_CAMERA), box_filter=mode, chain_shortcut=shortcut)
         kept, _ = assert_resolves_to_the_fused_call(rt, O, D, M, f"chain scene, walk {mode}, shortcut {shortcut}", 300)
-        assert_arrays_equal(rt.resolve_hits(O, D, kept), ref, OUTPUTS, f"chain scene, walk {mode}, shortcut {shortcut}: against the oracle")
+        assert_same_arrays(rt.resolve_hits(O, D, kept), ref, OUTPUTS, f"chain scene, walk {mode}, shortcut {shortcut}: against the oracle")
 
 
 # ------------------------------------------------------------------ 2: a frame's visibility buffer
@@ -147,7 +143,7 @@ def test_a_frames_visibility_buffer_resolves_to_its_surface_buffer(rrt, teapot, 
         ix = np.ix_(traced_rows(h), traced_cols(w))
         hit = vis["hit"][ix].astype(bool)
         assert hit.mean() >= 0.4 and not hit.all(), f"{hit.mean():.3f} of the traced sub-samples hit"
-        assert_arrays_equal({n: a[ix] for n, a in got.items()}, {n: a[ix] for n, a in want.items()}, names, f"{w}x{h}, pose {k}, walk {mode}")
+        assert_same_arrays({n: a[ix] for n, a in got.items()}, {n: a[ix] for n, a in want.items()}, names, f"{w}x{h}, pose {k}, walk {mode}")
         untraced = np.ones((h, w), bool)
         untraced[ix] = False
         assert untraced.sum() == w * h - len(traced_rows(h)) * len(traced_cols(w)) and untraced[0].all() and (w % 2 == 0 or untraced[:, -1].all())
@@ -155,18 +151,6 @@ def test_a_frames_visibility_buffer_resolves_to_its_surface_buffer(rrt, teapot, 
 
 
 # ------------------------------------------------------------------ 3: the device forms
-def device_arrays(torch, n, names):
-    kinds = {np.uint8: torch.uint8, np.float64: torch.float64, np.uint32: torch.int32}
-    return {name: torch.full((n * (3 if name in VECTORS else 1),), SENTINEL[name], dtype=kinds[DTYPES[name]], device="cuda") for name in names}
-
-
-def to_device(torch, a):
-    a = np.ascontiguousarray(a)
-    return torch.tensor(a.view(np.int32) if a.dtype == np.uint32 else a, device="cuda").reshape(-1)
-
-
-def to_host(tensors, n):
-    return {name: t.cpu().numpy().view(DTYPES[name]).reshape((n, 3) if name in VECTORS else (n,)) for name, t in tensors.items()}
 
 
 def sentinel_of(name, shape):
@@ -193,13 +177,13 @@ def test_what_is_not_asked_for_is_neither_written_nor_computed(rrt, teapot, rays
             rt.resolve_hits_into({name: out[name] for name in subset}, o_t, d_t, planes, stream=stream.cuda_stream)
             stream.synchronize()
             got = to_host(out, n)
-            assert_arrays_equal(got, want, subset, f"walk {mode}, outputs {subset}")
+            assert_same_arrays(got, want, subset, f"walk {mode}, outputs {subset}")
             for name in set(OUTPUTS) - set(subset):
                 assert same(got[name], sentinel_of(name, got[name].shape)), f"walk {mode}, outputs {subset}: array {name} was not passed and was written"
             if subset == WALK_FREE:
                 walk_free[mode] = got
     for mode in FORCED_MODES[1:]:
-        assert_arrays_equal(walk_free[mode], walk_free[FORCED_MODES[0]], WALK_FREE, f"without lights, walk {mode} vs walk {FORCED_MODES[0]}")
+        assert_same_arrays(walk_free[mode], walk_free[FORCED_MODES[0]], WALK_FREE, f"without lights, walk {mode} vs walk {FORCED_MODES[0]}")
 
 
 SMALL_BOUNDS = (0, 1, 63, 64, 65, 128, 129, 130, 2 ** 32 - 1)    # on a batch of 129: n - 1, n, n + 1 among them
@@ -231,7 +215,7 @@ def test_the_counted_form_on_a_stream_of_its_own(rrt, teapot, rays4096):
             stats = rt.last_stats()
             stream.synchronize()
             got = to_host(out, n)
-            assert_arrays_equal(rows(got, slice(0, mm)), rows(want, slice(0, mm)), OUTPUTS, f"walk {mode}, bound {m}: the first {mm} entries")
+            assert_same_arrays(rows(got, slice(0, mm)), rows(want, slice(0, mm)), OUTPUTS, f"walk {mode}, bound {m}: the first {mm} entries")
             for name in OUTPUTS:
                 assert same(got[name][mm:], sentinel_of(name, got[name][mm:].shape)), f"walk {mode}, bound {m}: {name} was written at or beyond the bound"
             assert (stats["width"], stats["height"], stats["rays_primary"]) == (n, 1, n), stats
@@ -271,7 +255,7 @@ def test_intersect_compact_resolve_scatter_is_the_fused_call(rrt, teapot, rays40
             rt.scatter_rays_into(index, padded[name], final[name], stream=s, bound_t=count)
         stream.synchronize()
         assert int(count.cpu().numpy().view(np.uint32)[0]) == c, f"walk {mode}"
-        assert_arrays_equal(to_host(final, n), want, OUTPUTS, f"walk {mode}: the split pipeline, scattered back, vs the fused call")
+        assert_same_arrays(to_host(final, n), want, OUTPUTS, f"walk {mode}: the split pipeline, scattered back, vs the fused call")
         got = to_host(padded, n)
         for name in OUTPUTS:
             assert same(got[name][c:], sentinel_of(name, got[name][c:].shape)), f"walk {mode}: the packed {name} was written beyond the count"
@@ -291,9 +275,9 @@ def test_edits_are_followed_from_the_old_hits(rrt, teapot, teapot_arrays, rays40
         moved = [lights[0], L.Point(0.4, V(6.0, 8.0, -12.0)), lights[2], lights[3]]
         rt.set_lights(moved)
         got = rt.resolve_hits(O, D, old)
-        assert_arrays_equal(got, rt.surface_rays(O, D, M), OUTPUTS, f"walk {mode}: a moved point light")
+        assert_same_arrays(got, rt.surface_rays(O, D, M), OUTPUTS, f"walk {mode}: a moved point light")
         assert (got["lights"] != base["lights"]).sum() >= 100
-        assert_arrays_equal(rt.resolve_hits(O, D, old, outputs=("lights",)), got, ("lights",), f"walk {mode}: lights alone")
+        assert_same_arrays(rt.resolve_hits(O, D, old, outputs=("lights",)), got, ("lights",), f"walk {mode}: lights alone")
         rt.set_lights(lights)
         # a bump map removed, a colour texture changed: albedo and normal were stale
         mats = [dict(m) for m in A["materials"]]
@@ -302,13 +286,13 @@ def test_edits_are_followed_from_the_old_hits(rrt, teapot, teapot_arrays, rays40
         mats[2]["tex"] = mats[0]["tex"]
         rt.set_materials(mats)
         got = rt.resolve_hits(O, D, old)
-        assert_arrays_equal(got, rt.surface_rays(O, D, M), OUTPUTS, f"walk {mode}: new materials")
+        assert_same_arrays(got, rt.surface_rays(O, D, M), OUTPUTS, f"walk {mode}: new materials")
         assert (got["albedo"] != base["albedo"]).sum() >= 50 and (got["normal"] != base["normal"]).any(1).sum() >= 50
         rt.set_materials(A["materials"])
         # a new pose: the rays are the caller's
         rt.set_camera(**rrt.look_at(MOVED_EYE, TARGET))
-        assert_arrays_equal(rt.resolve_hits(O, D, old), rt.surface_rays(O, D, M), OUTPUTS, f"walk {mode}: a new pose")
-        assert_arrays_equal(rt.resolve_hits(O, D, old), base, OUTPUTS, f"walk {mode}: everything as it was")
+        assert_same_arrays(rt.resolve_hits(O, D, old), rt.surface_rays(O, D, M), OUTPUTS, f"walk {mode}: a new pose")
+        assert_same_arrays(rt.resolve_hits(O, D, old), base, OUTPUTS, f"walk {mode}: everything as it was")
 
 
 # ------------------------------------------------------------------ 5: edges
@@ -323,7 +307,7 @@ def test_edges_of_the_batch_and_of_the_values(rrt, teapot, teapot_arrays, rays40
         for n in (1, 63, 64, 65, 129):
             for start in (0, 300 - n):
                 sl = slice(start, start + n)
-                assert_arrays_equal(rt.resolve_hits(O[sl], D[sl], rows(whole, sl)), rows(whole, sl), OUTPUTS, f"walk {mode}: {n} entries from {start}")
+                assert_same_arrays(rt.resolve_hits(O[sl], D[sl], rows(whole, sl)), rows(whole, sl), OUTPUTS, f"walk {mode}: {n} entries from {start}")
         # misses only: nothing is walked, every array holds the miss values
         miss = np.flatnonzero(~hit)[:130]
         got = rt.resolve_hits(O[miss], D[miss], rows(whole, miss))
@@ -335,7 +319,7 @@ def test_edges_of_the_batch_and_of_the_values(rrt, teapot, teapot_arrays, rays40
         got = rt.resolve_hits(O[on], D[on], kept)
         assert got["material"][0] == teapot_arrays["mat"][n_tris - 1] and same(got["point"][0], O[on][0] + D[on][0] * kept["t"][0]), f"walk {mode}: tri = n_tris - 1 is a hit"
         assert_miss_values(got, slice(1, 4), f"walk {mode}: tri = n_tris, n_tris + 1, 0xFFFFFFFF")
-        assert_arrays_equal(rows(got, slice(4, 8)), rows(whole, on[4:]), OUTPUTS, f"walk {mode}: the entries behind them")
+        assert_same_arrays(rows(got, slice(4, 8)), rows(whole, on[4:]), OUTPUTS, f"walk {mode}: the entries behind them")
         # NaN and infinities in t, u, v of some entries: the call returns, the other entries are exact
         kept = {name: whole[name].copy() for name in KEPT}
         bad = np.flatnonzero(hit)[::3]
@@ -346,7 +330,7 @@ def test_edges_of_the_batch_and_of_the_values(rrt, teapot, teapot_arrays, rays40
         good[bad] = False
         got = rt.resolve_hits(O, D, kept)
         assert len(bad) >= 20 and (hit & good).sum() >= 40
-        assert_arrays_equal(rows(got, good), rows(whole, good), OUTPUTS, f"walk {mode}: the entries beside non-finite ones")
+        assert_same_arrays(rows(got, good), rows(whole, good), OUTPUTS, f"walk {mode}: the entries beside non-finite ones")
         assert same(got["material"][bad], whole["material"][bad]), f"walk {mode}: the material of an entry does not depend on t, u, v"
 
 

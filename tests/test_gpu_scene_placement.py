@@ -40,12 +40,15 @@ Input conditions (test_placements_hold_on_the_cpu, from the oracle alone), thres
 import numpy as np
 import pytest
 
+from bitwise import assert_same_arrays
 from gpu_checks import (ALL_MODES, CHAIN_CAMERA, CHAIN_LIGHTS, FORCED_MODES, N_THREADS, ORIGIN, POOL, ROOT_BOX, PlainLight, assert_frame_close,
                         assert_rays_match_oracle, chain_main_rays, chain_scene, check_scene, coplanar_rays, oracle_for, oracle_pixels, origin_within_delta,
                         plane_scene, plane_scene_data, rrt_lights_of, traced_rows)
+from scenes import IDENTITY, TARGET
 
 W, H = 96, 72
 N_RAYS, N_COLOURS = 4096, 1024
+RESULTS = ("hit", "t", "u", "v", "tri")                        # what intersect_rays returns, in its order
 MIN_FRAME, MIN_HITS, MIN_DEPTH, MIN_GUARD = 0.4, 0.5, 9, 50      # measured: 0.603, 0.647 .. 0.671, 11, 60 (module docstring)
 
 
@@ -80,7 +83,6 @@ PLACEMENTS = {p.id: p for p in (
 ALL_IDS = list(PLACEMENTS)
 CAMERA_IDS = ("small_pow2", "shifted", "f32_denormal_scale")
 SCENE_IDS = ("small_pow2", "large", "shifted")                    # the guard and the chains
-
 
 
 # ------------------------------------------------------------------ the placed teapot, its oracle and its ray batch: built once per placement
@@ -152,12 +154,6 @@ def in_filter_range(P, O, D):
         o, d = O.astype(np.float32), D.astype(np.float32)
     dmax = np.abs(d).max(1)
     return (np.abs(o) < limit).all(1) & ~np.isnan(d).any(1) & (dmax < limit) & (dmax > np.float32(1e-10)) & (dmax < np.float32(1e8))
-
-
-def assert_same_results(got, want, what):
-    for name, x, y in zip(("hit", "t", "u", "v", "tri"), got, want):
-        bad = x != y
-        assert not bad.any(), f"{what}: {name} differs from the reference-order walk on {bad.sum()} of {len(bad)} rays (first: ray {int(np.argmax(bad))})"
 
 
 # ------------------------------------------------------------------ 1: the inputs, from the oracle alone
@@ -244,8 +240,6 @@ def test_rays_match_the_oracle(rrt, ob, teapot, pid):
 
 # ------------------------------------------------------------------ 5: the camera
 EYES = ((6.0, 3.0, -8.0), (-7.0, 4.0, -6.0))
-TARGET = (0.0, 1.0, 0.0)
-IDENTITY = dict(right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0))
 
 
 @pytest.mark.gpu
@@ -289,7 +283,7 @@ def test_the_guard_at_other_scales(rrt, pid):
     for mode in ("lane", "bundle", None):
         rt = rrt.RayTracer(sd, lights, E, box_filter=mode)
         counts.append(rt.last_stats()["origin_plane_triangles"])
-        assert_same_results(rt.intersect_rays(O, D), exact, f"placement {pid}, walk {mode}")
+        assert_same_arrays(dict(zip(RESULTS, rt.intersect_rays(O, D))), dict(zip(RESULTS, exact)), what=f"placement {pid}, walk {mode} vs the reference-order walk")
     assert len(set(counts)) == 1, counts
     if P.pow2:                                                   # the construction scales exactly: unit normal, squared-sine threshold and alpha are scale-free, delta ~ s
         t0, a0, _, _ = guard_scene(Placement("reference"))

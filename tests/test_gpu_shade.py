@@ -10,30 +10,15 @@ import copy
 import numpy as np
 import pytest
 
+from bitwise import assert_same_arrays, assert_same_bits
 from gpu_checks import (ALL_MODES, CHAIN_LIGHTS, FORCED_MODES, ORIGIN, assert_frame_close, chain_rrt_lights, chain_scene, mix4, oracle_for, traced_rows)
-from shade_checks import (CREATION, EYE3, H3, MIRROR_ROOM_LIGHTS, REGIONS, TARGET, W3, assert_same_frame, assert_shade_is_render, mirror_room, oracle_frame,
-                          pixels_apart, soup_scene, without)
-from surface_checks import (NO_MATERIAL, assert_planes_equal, expected_planes, frame_dirs, shade, traced_cols, traced_part, traced_pixels_in)
+from scenes import CREATION, EYE3, H3, MOVED_EYE, REGIONS, TARGET, W3, pose, shade_frame3 as frame3, teapot_arrays, teapot_osc  # noqa: F401  (fixtures: frame3, teapot_arrays, teapot_osc)
+from shade_checks import MIRROR_ROOM_LIGHTS, assert_shade_is_render, mirror_room, oracle_frame, pixels_apart, soup_scene, without
+from surface_checks import NO_MATERIAL, expected_planes, frame_dirs, shade, traced_cols, traced_part, traced_pixels_in
 
 pytestmark = pytest.mark.gpu
 
-MOVED_EYE = (9.0, 2.0, 1.0)
 W, H = 64, 48
-
-
-def pose(rrt, k):
-    return CREATION if k == 0 else rrt.look_at(MOVED_EYE, TARGET)
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
-def teapot_osc(ob, rrt, teapot_arrays):
-    return oracle_for(ob, teapot_arrays, rrt.default_lights())
 
 
 @pytest.fixture(scope="module")
@@ -93,7 +78,7 @@ def test_relighting_with_a_kept_mask(rrt, ob, teapot, teapot_arrays, default_fra
         old = rt.surface(W, H, visibility=("albedo",))
         rt.set_lights(new)
         fresh = rt.render(W, H)
-        assert_same_frame(rt.shade(W, H, old), fresh, f"walk {mode}: shade of the old planes, mask included, vs a fresh render")
+        assert_same_bits(rt.shade(W, H, old), fresh, f"walk {mode}: shade of the old planes, mask included, vs a fresh render")
         assert_frame_close(fresh, ref, f"walk {mode}: render with the new lights vs the oracle")
 
 
@@ -115,7 +100,7 @@ def test_a_moved_point_light(rrt, ob, teapot, teapot_arrays, teapot_osc, default
         old = rt.surface(W, H, visibility=("albedo",))
         rt.set_lights(new)
         fresh = rt.render(W, H)
-        assert_same_frame(rt.shade(W, H, without(old, "lights")), fresh, f"walk {mode}: shade of the old planes without the mask vs a fresh render")
+        assert_same_bits(rt.shade(W, H, without(old, "lights")), fresh, f"walk {mode}: shade of the old planes without the mask vs a fresh render")
         assert_frame_close(fresh, ref, f"walk {mode}: render with the moved light vs the oracle")
         stale = rt.shade(W, H, old)
         print(f"walk {mode}: shading with the stale mask differs from the frame on {int((stale != fresh).sum())} pixels")
@@ -138,10 +123,10 @@ def test_the_planes_are_read_not_walked_again(rrt, teapot, teapot_arrays):
     want[24:32, 24:32] = 0x00FFFFFF
     assert (want != frame).sum() >= 32, "the blocks lie on background pixels: the edit shows nothing"
     for what, p in (("with the mask", edited), ("without the mask", without(edited, "lights"))):
-        assert_same_frame(rt.shade(W, H, p), want, f"material 0xFFFFFFFF and n_mats in two 8x8 blocks, {what}")
+        assert_same_bits(rt.shade(W, H, p), want, f"material 0xFFFFFFFF and n_mats in two 8x8 blocks, {what}")
     # bits of the mask at and above n_lights are not lights
     noisy = dict(planes, lights=planes["lights"] | np.uint32((0xFFFFFFFF << len(lights)) & 0xFFFFFFFF))
-    assert_same_frame(rt.shade(W, H, noisy), frame, "bits at and above n_lights set in the mask")
+    assert_same_bits(rt.shade(W, H, noisy), frame, "bits at and above n_lights set in the mask")
     # another albedo: the numpy shader of surface_checks on the same planes, wherever no sub-sample hits a mirror
     flat = dict(planes, albedo=np.full_like(planes["albedo"], 0x00C86432))
     got = rt.shade(W, H, flat)
@@ -158,16 +143,6 @@ def test_the_planes_are_read_not_walked_again(rrt, teapot, teapot_arrays):
 
 
 # ------------------------------------------------------------------ 6
-@pytest.fixture(scope="module")
-def frame3(rrt, teapot):
-    """A raytracer at the pose of part 6, its frame and its whole-frame planes (read-only)."""
-    rt = rrt.RayTracer(teapot, rrt.default_lights())
-    rt.look_at(EYE3, TARGET)
-    full = rt.surface(W3, H3, visibility=("albedo",))
-    frame = rt.render(W3, H3)
-    for a in list(full.values()) + [frame]:
-        a.setflags(write=False)
-    return rt, frame, full
 
 
 @pytest.mark.parametrize("region", REGIONS)
@@ -181,9 +156,9 @@ def test_a_region_is_a_slice_of_the_frame(rrt, frame3, region):
         assert 0.2 <= miss.mean() <= 0.8, miss.mean()
         assert (frame[0] == 0).all() and (frame[1] == 0).all() and (frame[:, -1] == 0).all() and (frame[2:, :-1] != 0).any(), "row 0, row 1 and the last column of an odd-sized frame are 0"
     part = rt.surface(W3, H3, region=region, visibility=("albedo",))
-    assert_planes_equal(part, {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, part.keys(), f"region {region}: planes")
+    assert_same_arrays(part, {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, part.keys(), f"region {region}: planes")
     for what, p in (("with the mask", part), ("without the mask", without(part, "lights"))):
-        assert_same_frame(rt.shade(W3, H3, p, region=region), want, f"region {region}, {what}")
+        assert_same_bits(rt.shade(W3, H3, p, region=region), want, f"region {region}, {what}")
         stats = rt.last_stats()
         assert (stats["width"], stats["height"], stats["rays_primary"]) == (W3, H3, 4 * traced_pixels_in(region, W3, H3)) and stats["kernel_ms"] > 0, (region, stats)
     # device form: exactly region.h x region.w elements are written, and every one of them
@@ -195,7 +170,7 @@ def test_a_region_is_a_slice_of_the_frame(rrt, frame3, region):
     a = whole.cpu().numpy()
     assert (a[:G] == SENTINEL).all() and (a[-G:] == SENTINEL).all(), f"region {region}: an element outside the output was written"
     assert not (a[G:-G] == SENTINEL).any(), f"region {region}: {int((a[G:-G] == SENTINEL).sum())} pixels were not written"
-    assert_same_frame(a[G:-G].view(np.uint32).reshape(h, w), want, f"region {region}: shade_into vs the slice of the frame")
+    assert_same_bits(a[G:-G].view(np.uint32).reshape(h, w), want, f"region {region}: shade_into vs the slice of the frame")
 
 
 # ------------------------------------------------------------------ 7
@@ -257,14 +232,14 @@ def test_the_tuning_state_is_untouched(rrt, teapot, frame3, frames_before):
         variant = rt.last_stats()["filter_variant"]
     got = rt.shade(W3, H3, full)
     stats = rt.last_stats()
-    assert_same_frame(got, frame, f"after {frames_before} frames")
+    assert_same_bits(got, frame, f"after {frames_before} frames")
     assert (stats["width"], stats["height"], stats["rays_primary"]) == (W3, H3, 4 * traced_pixels_in(REGIONS[0], W3, H3)) and stats["kernel_ms"] > 0, stats
     x0, y0, w, h = REGIONS[3]
     rt.shade(W3, H3, {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, region=REGIONS[3])
     small = rt.surface(64, 48, visibility=("albedo",))
     rt.shade(64, 48, small)                                                        # another size must not become "the" size either
     after = rt.render(W3, H3)
-    assert_same_frame(after, frame, f"render after the shade calls, {frames_before} frames before them")
+    assert_same_bits(after, frame, f"render after the shade calls, {frames_before} frames before them")
     if frames_before:
         assert stats["filter_variant"] == variant, (stats["filter_variant"], variant)
         assert np.array_equal(after, before)
@@ -308,8 +283,8 @@ def test_refusals_leave_the_raytracer_as_it_was(rrt, frame3, teapot):
             call()
         assert e.value.status == rrt.ERR_INVALID_ARG, what
         assert (fb == 0xA5A5A5A5).all(), f"{what}: the output of a refused call was written"
-        assert_same_frame(rt.shade(W3, H3, part, region=region), frame[y0:y0 + h, x0:x0 + w], f"after the refusal of: {what}")
-    assert_same_frame(rt.render(W3, H3), frame, "render after the refusals")
+        assert_same_bits(rt.shade(W3, H3, part, region=region), frame[y0:y0 + h, x0:x0 + w], f"after the refusal of: {what}")
+    assert_same_bits(rt.render(W3, H3), frame, "render after the refusals")
 
 
 # ------------------------------------------------------------------ 10
@@ -344,19 +319,19 @@ def test_a_new_material_table(rrt, ob, teapot, teapot_arrays, default_frame):
         assert rt.materials() == new
         frame = rt.render(W, H)
         assert pixels_apart(frame, old_frame) >= 400, f"walk {mode}: the new table changes {pixels_apart(frame, old_frame)} pixels only"
-        assert_same_frame(frame, from_arrays(rrt, A, new, mode).render(W, H), f"walk {mode}: render after set_materials vs a raytracer created with the new table")
+        assert_same_bits(frame, from_arrays(rrt, A, new, mode).render(W, H), f"walk {mode}: render after set_materials vs a raytracer created with the new table")
         assert_frame_close(frame, ref, f"walk {mode}: render after set_materials vs the oracle")
         after = rt.surface(W, H, visibility=("albedo",))
-        assert_planes_equal(after, before, before.keys(), f"walk {mode}: ka, kd, ks, ns and kr leave the planes as they were")
-        assert_same_frame(rt.shade(W, H, before), frame, f"walk {mode}: shade of the planes taken before the edit vs the new frame")
-        assert_same_frame(rt.shade(W, H, without(before, "lights")), frame, f"walk {mode}: the same without the mask")
+        assert_same_arrays(after, before, before.keys(), f"walk {mode}: ka, kd, ks, ns and kr leave the planes as they were")
+        assert_same_bits(rt.shade(W, H, before), frame, f"walk {mode}: shade of the planes taken before the edit vs the new frame")
+        assert_same_bits(rt.shade(W, H, without(before, "lights")), frame, f"walk {mode}: the same without the mask")
         # tex and bump: albedo and normal planes follow, as on a raytracer created with that table
         rt.set_materials(swapped)
         assert rt.materials() == swapped
         fresh = from_arrays(rrt, A, swapped, mode)
-        assert_same_frame(rt.render(W, H), fresh.render(W, H), f"walk {mode}: render after swapping tex and bump of materials 0 and 1")
+        assert_same_bits(rt.render(W, H), fresh.render(W, H), f"walk {mode}: render after swapping tex and bump of materials 0 and 1")
         planes, want = rt.surface(W, H, visibility=("albedo",)), fresh.surface(W, H, visibility=("albedo",))
-        assert_planes_equal(planes, want, want.keys(), f"walk {mode}: planes after swapping tex and bump of materials 0 and 1")
+        assert_same_arrays(planes, want, want.keys(), f"walk {mode}: planes after swapping tex and bump of materials 0 and 1")
         assert not np.array_equal(planes["albedo"], before["albedo"]) and not np.array_equal(planes["normal"], before["normal"]), "the swap shows in neither albedo nor normal"
 
 
@@ -377,7 +352,7 @@ def test_a_refused_material_table_changes_nothing(rrt, teapot, teapot_arrays):
             call()
         assert e.value.status == rrt.ERR_INVALID_ARG, what
         assert rt.materials() == new, f"after the refusal of {what}"
-        assert_same_frame(rt.render(W, H), frame, f"render after the refusal of {what}")
+        assert_same_bits(rt.render(W, H), frame, f"render after the refusal of {what}")
     n = rrt.lib().rrt_raytracer_get_materials(rt._h, (rrt.CMaterial * 2)(), 2, None)
     assert n == rrt.ERR_INVALID_ARG, "a capacity below the count with a non-NULL array"
 
@@ -390,4 +365,4 @@ def test_materials_of_a_host_setup_raytracer(rrt, teapot, teapot_arrays):
     assert rt.materials() == new
     frame = rt.render(W, H)
     assert pixels_apart(frame, old) >= 400
-    assert_same_frame(frame, from_arrays(rrt, teapot_arrays, new, None).render(W, H), "host_setup: render after set_materials vs a raytracer created with the new table")
+    assert_same_bits(frame, from_arrays(rrt, teapot_arrays, new, None).render(W, H), "host_setup: render after set_materials vs a raytracer created with the new table")

@@ -14,41 +14,21 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from bitwise import assert_same_bits, bits, same
 from conftest import channels
 from gpu_checks import (ALL_MODES, CHAIN_CAMERA, CHAIN_LIGHTS, COLOUR_TOL, FORCED_MODES, ORIGIN, POOL, assert_frame_close, chain_main_rays, chain_rrt_lights,
                         chain_scene, oracle_for)
 from ray_surface_checks import VECTORS, WHITE, clamp_u8, expected_ray_planes, kr_of, local_colour, pack
-from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, TARGET, mirror_room, soup_scene
+from scenes import CREATION, MOVED_EYE, TARGET, pose, posed, rays_of, room, teapot_arrays, teapot_osc  # noqa: F401  (fixtures: room, teapot_arrays, teapot_osc)
+from shade_checks import soup_scene
 from shade_rays_checks import (INPUTS, OUT_DTYPES, OUT_SENTINEL, OUTPUTS, chain_levels, mixed, oracle_colours, reflecting, unwind, without_mask)
-from surface_checks import bits, frame_dirs, same
+from surface_checks import frame_dirs
 
 pytestmark = pytest.mark.gpu
 
-MOVED_EYE = (9.0, 2.0, 1.0)
 W, H = 64, 48
 RW, RH = 32, 24                                                  # the mirror room's and the soup's frame
 M = 5                                                            # the default max_reflection_depth
-
-
-def pose(rrt, k):
-    return CREATION if k == 0 else rrt.look_at(MOVED_EYE, TARGET)
-
-
-def posed(rt, cam):
-    rt.set_camera(**cam)
-    return rt
-
-
-def rays_of(cam, w, h):
-    d = frame_dirs(cam, w, h).reshape(-1, 3)
-    return np.ascontiguousarray(np.broadcast_to(np.asarray(cam["eye"], np.float64), d.shape)), d
-
-
-def assert_same_colours(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype == np.uint32, f"{what}: {got.dtype}{got.shape} vs {want.dtype}{want.shape}"
-    bad = got != want
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} colours differ, first at {int(np.flatnonzero(bad)[0])}: {int(got[bad][0]):#08x} vs {int(want[bad][0]):#08x}"
 
 
 def assert_shade_is_get_ray_colours(rt, O, D, what, planes=None):
@@ -56,31 +36,11 @@ def assert_shade_is_get_ray_colours(rt, O, D, what, planes=None):
     Returns (the colours, the records)."""
     planes = rt.surface_rays(O, D) if planes is None else planes
     want = rt.get_ray_colours(O, D)
-    assert_same_colours(rt.shade_rays(D, planes)["colour"], want, f"{what}: shade_rays with the mask vs get_ray_colours")
+    assert_same_bits(rt.shade_rays(D, planes)["colour"], want, f"{what}: shade_rays with the mask vs get_ray_colours", np.uint32)
     stats = rt.last_stats()
     assert (stats["width"], stats["height"], stats["rays_primary"]) == (len(D), 1, len(D)) and stats["kernel_ms"] > 0, stats
-    assert_same_colours(rt.shade_rays(D, without_mask(planes))["colour"], want, f"{what}: shade_rays without the mask vs get_ray_colours")
+    assert_same_bits(rt.shade_rays(D, without_mask(planes))["colour"], want, f"{what}: shade_rays without the mask vs get_ray_colours", np.uint32)
     return want, planes
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
-def teapot_osc(ob, rrt, teapot_arrays):
-    return oracle_for(ob, teapot_arrays, rrt.default_lights())
-
-
-@pytest.fixture(scope="module")
-def room(rrt, ob):
-    """(arrays, lights, SceneData, oracle scene) of shade_checks.mirror_room with MIRROR_ROOM_LIGHTS"""
-    A = mirror_room()
-    lights = [rrt.Light(k, i, rrt.Vector3d(*v)) for k, i, v in MIRROR_ROOM_LIGHTS]
-    sd = rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"])
-    return A, lights, sd, oracle_for(ob, A, lights)
 
 
 @pytest.fixture(scope="module")
@@ -184,7 +144,7 @@ def test_depth(rrt, room, room_chain):
             o, d, planes, _ = levels[k]
             want = rrt.RayTracer(sd, lights, max_reflection_depth=M - k, box_filter=mode).get_ray_colours(o, d)
             for what, p in (("with the mask", planes), ("without the mask", without_mask(planes))):
-                assert_same_colours(rt.shade_rays(d, p, depth=k)["colour"], want, f"walk {mode}, level {k} at depth {k} {what} vs max_reflection_depth {M - k}")
+                assert_same_bits(rt.shade_rays(d, p, depth=k)["colour"], want, f"walk {mode}, level {k} at depth {k} {what} vs max_reflection_depth {M - k}", np.uint32)
             if k < 5:
                 assert (want != rt.get_ray_colours(o, d)).sum() >= 500, f"level {k}: depth {k} and depth 0 give the same colours: depth is not read"
         o, d, planes, _ = levels[5]
@@ -208,9 +168,9 @@ def check_local_and_kr(rt, A, lights, levels, what):
         assert_frame_close(pack(clamp_u8(out["local"])), want, f"{what}, level {k}: local, clamped, vs ray_surface_checks.local_colour", tol=COLOUR_TOL)
         assert (bits(out["local"][~hit]) == 0).all() and (out["colour"][~hit] == WHITE).all(), f"{what}, level {k}: a miss is not WHITE / (0, 0, 0)"
         matte = hit & ~go
-        assert_same_colours(out["colour"][matte], pack(clamp_u8(out["local"][matte])), f"{what}, level {k}: colour where kr == 0")
+        assert_same_bits(out["colour"][matte], pack(clamp_u8(out["local"][matte])), f"{what}, level {k}: colour where kr == 0", np.uint32)
         if go.any():
-            assert_same_colours(out["colour"][go], mixed(out["local"][go], out["kr"][go], below), f"{what}, level {k}: colour where kr > 0 from the level below")
+            assert_same_bits(out["colour"][go], mixed(out["local"][go], out["kr"][go], below), f"{what}, level {k}: colour where kr > 0 from the level below", np.uint32)
         below = out["colour"]
     return below
 
@@ -219,7 +179,7 @@ def test_local_and_kr(rrt, teapot, teapot_arrays, room, room_chain):
     A, lights, sd, _ = room
     rt, levels = room_chain
     top = check_local_and_kr(rt, A, lights, levels, "mirror room")
-    assert_same_colours(top, rt.get_ray_colours(levels[0][0], levels[0][1]), "mirror room: level 0 vs get_ray_colours")
+    assert_same_bits(top, rt.get_ray_colours(levels[0][0], levels[0][1]), "mirror room: level 0 vs get_ray_colours", np.uint32)
     cam = pose(rrt, 1)
     trt = posed(rrt.RayTracer(teapot, rrt.default_lights()), cam)
     O, D = rays_of(cam, W, H)
@@ -242,7 +202,7 @@ def test_the_recursion_from_library_calls_alone(rrt, room, room_chain):
     def host_level(k, d, planes):
         out = rt.shade_rays(d, planes, depth=k, outputs=("local", "kr"))
         return out["local"], out["kr"]
-    assert_same_colours(unwind(levels, host_level), want, "the recursion followed on the host")
+    assert_same_bits(unwind(levels, host_level), want, "the recursion followed on the host", np.uint32)
     # on the device: surface_rays_into and shade_rays_into per level on a stream of the test's own; the rays of a level are the reflecting rays of the level above
     stream = torch.cuda.Stream()
     kinds = {np.uint8: torch.uint8, np.float64: torch.float64, np.uint32: torch.int32}
@@ -275,7 +235,7 @@ def test_the_recursion_from_library_calls_alone(rrt, room, room_chain):
             below = c
     stream.synchronize()
     assert [int(go.sum()) for _, _, go in kept[:-1]] == [len(l[1]) for l in levels[1:]] and not bool(kept[-1][2].any())
-    assert_same_colours(below.cpu().numpy().astype(np.uint32), want, "the recursion followed on the device")
+    assert_same_bits(below.cpu().numpy().astype(np.uint32), want, "the recursion followed on the device", np.uint32)
     for rec, out, go in kept:
         assert bool((out["colour"] == OUT_SENTINEL["colour"]).all()), "colour was not passed and was written"
 
@@ -357,25 +317,25 @@ def test_relighting_and_material_edits(rrt, ob, teapot, teapot_arrays, teapot_os
         # intensities and the directional light's vector: the kept mask is still the mask
         rt.set_lights(dimmed)
         fresh = rt.get_ray_colours(O, D)
-        assert_same_colours(rt.shade_rays(D, old)["colour"], fresh, f"walk {mode}: dimmed lights, the old records with their mask")
+        assert_same_bits(rt.shade_rays(D, old)["colour"], fresh, f"walk {mode}: dimmed lights, the old records with their mask", np.uint32)
         assert_frame_close(fresh, refs["dimmed"], f"walk {mode}: get_ray_colours with the dimmed lights vs the oracle")
         # a camera change in between leaves ray records valid
         rt.look_at(MOVED_EYE, TARGET)
-        assert_same_colours(rt.shade_rays(D, old)["colour"], fresh, f"walk {mode}: the same after set_camera")
+        assert_same_bits(rt.shade_rays(D, old)["colour"], fresh, f"walk {mode}: the same after set_camera", np.uint32)
         rt.reset_camera()
         # a moved point light: the mask is stale, the other arrays are not
         rt.set_lights(moved)
         fresh = rt.get_ray_colours(O, D)
-        assert_same_colours(rt.shade_rays(D, without_mask(old))["colour"], fresh, f"walk {mode}: a moved point light, the old records without their mask")
+        assert_same_bits(rt.shade_rays(D, without_mask(old))["colour"], fresh, f"walk {mode}: a moved point light, the old records without their mask", np.uint32)
         assert_frame_close(fresh, refs["moved"], f"walk {mode}: get_ray_colours with the moved light vs the oracle")
         assert (rt.shade_rays(D, old)["colour"] != fresh).any(), f"walk {mode}: shading with the stale mask gives the fresh colours: the mask is not read"
         rt.set_lights(lights)
-        assert_same_colours(rt.shade_rays(D, old)["colour"], before, f"walk {mode}: the first lights again")
+        assert_same_bits(rt.shade_rays(D, old)["colour"], before, f"walk {mode}: the first lights again", np.uint32)
         # ka, kd, ks, ns, kr
         rt.set_materials(new)
         fresh = rt.get_ray_colours(O, D)
         for what, p in (("with their mask", old), ("without their mask", without_mask(old))):
-            assert_same_colours(rt.shade_rays(D, p)["colour"], fresh, f"walk {mode}: new materials, the old records {what}")
+            assert_same_bits(rt.shade_rays(D, p)["colour"], fresh, f"walk {mode}: new materials, the old records {what}", np.uint32)
         assert_frame_close(fresh, refs["materials"], f"walk {mode}: get_ray_colours with the new materials vs the oracle")
         out = rt.shade_rays(D, old, outputs=("kr",))
         assert same(out["kr"], np.where(old["hit"].astype(bool), kr_of(dict(A, materials=new), old["material"]), 0.0)), f"walk {mode}: kr is not the new table's"
@@ -464,7 +424,7 @@ def test_edges_of_the_batch(rrt, teapot, teapot_arrays):
         whole = rt.shade_rays(d, planes, outputs=OUTPUTS)
         hit = planes["hit"].astype(bool)
         assert 150 <= hit.sum() <= 250 and (whole["kr"] > 0.0).sum() >= 50, (int(hit.sum()), int((whole["kr"] > 0.0).sum()))
-        assert_same_colours(whole["colour"], rt.get_ray_colours(o, d), f"walk {mode}: the slice of the frame")
+        assert_same_bits(whole["colour"], rt.get_ray_colours(o, d), f"walk {mode}: the slice of the frame", np.uint32)
         for n in (1, 63, 64, 65):
             for start in (0, 300 - n):
                 sl = slice(start, start + n)
@@ -525,7 +485,7 @@ def test_refusals_leave_everything_as_it_was(rrt, teapot):
     rt.shade_rays_into({"colour": out["colour"]}, d_t, rec)
     torch.cuda.synchronize()
     assert rt.last_stats()["filter_variant"] == ray_variant
-    assert_same_colours(out["colour"].cpu().numpy().view(np.uint32), want, "the device form")
+    assert_same_bits(out["colour"].cpu().numpy().view(np.uint32), want, "the device form", np.uint32)
     out["colour"].fill_(OUT_SENTINEL["colour"])
     torch.cuda.synchronize()
     frame_again = rt.render(W, H)
@@ -563,4 +523,4 @@ def test_refusals_leave_everything_as_it_was(rrt, teapot):
         a = t.cpu().numpy()
         assert (a == np.array(OUT_SENTINEL[name]).astype(a.dtype)).all(), f"a refused call wrote {name}"
     # ... and the call still works
-    assert_same_colours(rt.shade_rays(d, planes)["colour"], want, "after the refusals")
+    assert_same_bits(rt.shade_rays(d, planes)["colour"], want, "after the refusals", np.uint32)

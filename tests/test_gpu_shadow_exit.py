@@ -20,49 +20,13 @@ below the root, without `own_t < max_t`, turns the rays of (b) and (c) from lit 
 import numpy as np
 import pytest
 
-from gpu_checks import ALL_MODES, N_THREADS, ROOT_BOX, assert_walks_match, checker, oracle_for, quad
+from gpu_checks import ALL_MODES, N_THREADS, assert_walks_match, oracle_for
+from lighting_scenes import (SHADOW_EXIT_CAMERA as CAMERA, SHADOW_EXIT_LIGHT_ABOVE as LIGHT_ABOVE, SHADOW_EXIT_LIGHT_ON_FLOOR as LIGHT_ON_FLOOR,
+                             SHADOW_EXIT_OFFSET as OFFSET, shadow_exit_arrays as _arrays, shadow_exit_lights as _lights, shadow_exit_rays as _primary_rays)
 
 EPS = 2.220446049250313e-16
-OFFSET = 1e-4                                            # SURFACE_OFFSET, raytracer.rs:17
-LIGHT_ABOVE = (-2.0, -2.75, 6.0)                         # classes (a), (b), (c): a quarter above the floor
-LIGHT_ON_FLOOR = (3.0, -3.0, 7.0)                        # class (d): a point of the floor that rays hit exactly
-CAMERA = (0.0, 2.0, -10.0)
 SIZES = ((160, 120), (97, 61))
 MIN_RAYS = {"a": 25, "b": 20, "c": 25, "d": 16}
-
-
-def _arrays():
-    """Floor y = -3 (root list: it straddles the root's planes) and, in the root's children 1 (x < 0, y < 0, z > 0) and 2 (x > 0, y < 0, z > 0):
-    FAR, a wall at x = -19 that straddles child 1's z plane (own list of a depth-1 node with children); ROOF, a ceiling at y = -2 over the light
-    (own list of a depth-2 node); NEAR, a low wall at x = 1 in child 2; and two pairs of small triangles that open deeper levels."""
-    groups = {"floor": quad((-16, -3, -16), (16, -3, -16), (16, -3, 16), (-16, -3, 16)),
-              "far": quad((-19, -3.5, 1), (-19, -3.5, 11), (-19, -0.5, 11), (-19, -0.5, 1)),
-              "roof": quad((-4.9, -2, 3), (-0.1, -2, 3), (-0.1, -2, 9), (-4.9, -2, 9)),
-              "near": quad((1, -3.4, 4.5), (1, -3.4, 7.5), (1, -2.5, 7.5), (1, -2.5, 4.5)),
-              "deep": [[(-7, -8, 2), (-6.8, -8, 2), (-7, -7.8, 2)], [(-7.3, -8, 2.2), (-7.1, -8, 2.2), (-7.3, -7.8, 2.2)],
-                       [(7, -8, 2), (7.2, -8, 2), (7, -7.8, 2)], [(7.3, -8, 2.2), (7.5, -8, 2.2), (7.3, -7.8, 2.2)]]}
-    names = [n for n, g in groups.items() for _ in g]
-    pos = np.asarray([t for g in groups.values() for t in g], np.float64)
-    nrm = np.tile([0.0, 1.0, 0.0], (len(pos), 3, 1))                        # the rays below only ever shade the floor
-    uv = np.zeros_like(pos); uv[..., 0] = pos[..., 0] * 0.13 + pos[..., 2] * 0.07; uv[..., 1] = pos[..., 1] * 0.11 + pos[..., 2] * 0.05
-    mats = [dict(ka=(1, 1, 1), kd=(1, 1, 1), ks=(0, 0, 0), ns=-1.0, kr=0.0, tex=0, bump=-1)]
-    A = dict(pos=pos, uv=uv, nrm=nrm, mat=np.zeros(len(pos), np.uint32), materials=mats, textures=[checker((230, 200, 170), (120, 140, 160))], root=ROOT_BOX)
-    return A, {n: np.flatnonzero(np.array(names) == n) for n in groups}
-
-
-def _primary_rays():
-    """Straight down onto the floor from y = -2.6 (under the roof).  Receivers: right of NEAR and far from it (a), under the roof within 1 of the
-    light (b), just right of NEAR (c); and rays that reach LIGHT_ON_FLOOR exactly, from several directions and distances (d)."""
-    grid = lambda xs, zs: [(x, z) for x in xs for z in zs]
-    recv = {"a": grid(np.linspace(3.5, 6.0, 6), np.linspace(5.2, 6.8, 5)),
-            "b": grid(-2.0 + np.linspace(-0.4, 0.4, 5), 6.0 + np.linspace(-0.4, 0.4, 5)),
-            "c": grid(np.linspace(1.3, 2.3, 6), np.linspace(5.2, 6.8, 5))}
-    O = [(x, -2.6, z) for k in "abc" for x, z in recv[k]]
-    D = [(0.0, -1.0, 0.0)] * len(O)
-    for d in ((0, -1, 0), (1, -1, 0), (-1, -1, 0), (0, -1, 1), (0, -1, -1), (1, -1, 1)):
-        for k in (0.5, 1.0, 2.0, 4.0):
-            O.append(tuple(np.array(LIGHT_ON_FLOOR) - k * np.array(d, np.float64))); D.append(tuple(map(float, d)))
-    return np.asarray(O, np.float64), np.asarray(D, np.float64)
 
 
 def _brute_force(pos, o, d):
@@ -115,20 +79,6 @@ def _classify(osc, A, parts, light, O, D):
         elif not occluded and len(nearer) and free[0] and free[4] in beyond and depth[_own_node_of(tree, free[4])] >= 1:
             found["c"].append(i)
     return found, tree
-
-
-class _Light:
-    """What conftest.lights_tuple reads of a light, for the oracle alone (the CPU test does not load the product library)."""
-    def __init__(self, kind, intensity, v):
-        self.kind, self.intensity, self.v = kind, intensity, self
-        self.x, self.y, self.z = v
-
-
-def _lights(rrt, light):
-    """Ambient + the one point light; rrt = None: for the oracle only."""
-    if rrt is None:
-        return [_Light(0, 0.25, (0.0, 0.0, 0.0)), _Light(1, 0.7, light)]
-    return [rrt.Light.Ambient(0.25), rrt.Light.Point(0.7, rrt.Vector3d(*light))]
 
 
 def _checked_classes(ob):

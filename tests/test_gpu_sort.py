@@ -13,13 +13,13 @@ import numpy as np
 import pytest
 
 from ambient_checks import T8, T8_MAX_T
-from ambient_rays_checks import INPUTS, OUTPUTS, open_of, standard_rot
-from compact_checks import ARRAYS, NAMES, RECORD_NAMES, assert_same_bytes, selection
+from ambient_rays_checks import INPUTS, OUTPUTS, kept_records as kept, open_of, standard_rot  # noqa: F401  (fixtures: kept)
+from bitwise import assert_same_bits
+from compact_checks import ARRAYS, NAMES, RECORD_NAMES, Guarded, ceil_div, selection, to_device
 from gpu_checks import FORCED_MODES, chain_rrt_lights, chain_scene
-from shade_checks import CREATION, soup_scene
+from scenes import CREATION, rays_of, teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
+from shade_checks import soup_scene
 from sort_checks import DEAD_KEY, assert_sorted, dead_rays, has_ties, key_patterns, ray_key, root_box_of, sorted_batch
-from test_gpu_ambient_rays import kept, rays_of, teapot_arrays  # noqa: F401  (kept, teapot_arrays: fixtures, shared with that module's tests by name)
-from test_gpu_compact import Guarded, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +30,6 @@ BIG = 2 ** 20 + 4097                                             # 258 tiles: tw
 EDGE_SIZES = (1, 2, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2047, 2049, 4095, 4096, 4097, 8191, 8193, 70001, BIG)
 HOST_TOO = 4097                                                  # up to this size the host form is checked as well
 SENTINEL = -1515870811                                           # 0xA5A5A5A5 as int32
-
-
-def ceil_div(a, b):
-    return -(-a // b)
 
 
 def shaped(name, a, n):
@@ -91,12 +87,12 @@ def test_given_keys(rrt, teapot, n):
         keys = key_patterns(n)["every 11th dead"]
         want = sorted_batch(keys, src)
         got = device_sort(torch, rt, n, "given", dict(tri=tri), ("tri",), stream, keys=keys, index=False, keys_out=False, count=False)
-        assert_same_bytes(got["tri"], want["tri"], f"n = {n}: tri alone")
+        assert_same_bits(got["tri"], want["tri"], f"n = {n}: tri alone")
         assert device_sort(torch, rt, n, "given", {}, (), stream, keys=keys, index=False, keys_out=False) == dict(count=want["count"]), f"n = {n}: count alone"
         got = device_sort(torch, rt, n, "given", {}, (), stream, keys=keys, keys_out=False, count=False)
-        assert_same_bytes(got["index"], want["index"], f"n = {n}: index alone")
+        assert_same_bits(got["index"], want["index"], f"n = {n}: index alone")
         got = device_sort(torch, rt, n, "given", {}, (), stream, keys=keys, index=False, count=False)
-        assert_same_bytes(got["keys"], want["keys"], f"n = {n}: keys_out alone")
+        assert_same_bits(got["keys"], want["keys"], f"n = {n}: keys_out alone")
 
 
 # ------------------------------------------------------------------ 2
@@ -243,7 +239,7 @@ def assert_sorted_rays_feed_the_surface_stage(torch, rt, O, D, max_t, what):
     assert np.array_equal(np.sort(idx), np.arange(n)), f"{what}: index is no permutation"
     assert not np.array_equal(idx, np.arange(n)), f"{what}: the sort left the batch in its order"
     for k in RECORD_NAMES:
-        assert_same_bytes(shaped(k, final[k].cpu().numpy().view(ARRAYS[k][0]), n), want[k], f"{what}: {k} of the sorted rays, scattered back")
+        assert_same_bits(shaped(k, final[k].cpu().numpy().view(ARRAYS[k][0]), n), want[k], f"{what}: {k} of the sorted rays, scattered back")
 
 
 def assert_sorted_records_feed_the_ambient_stage(torch, rt, rec, rot, n_mats, want, what):
@@ -267,8 +263,8 @@ def assert_sorted_records_feed_the_ambient_stage(torch, rt, rec, rot, n_mats, wa
         rt.scatter_rays_into(index, mid[k], final[k], stream=s)
     stream.synchronize()
     assert int(count_t.cpu().numpy().view(np.uint32)[0]) == int(hit.sum()), what
-    assert_same_bytes(final["occluded"].cpu().numpy().view(np.uint32), want, f"{what}: occluded of the sorted records, scattered back")
-    assert_same_bytes(final["open"].cpu().numpy().view(np.uint32), open_of(want, hit, len(T8)), f"{what}: open of the sorted records, scattered back")
+    assert_same_bits(final["occluded"].cpu().numpy().view(np.uint32), want, f"{what}: occluded of the sorted records, scattered back")
+    assert_same_bits(final["open"].cpu().numpy().view(np.uint32), open_of(want, hit, len(T8)), f"{what}: open of the sorted records, scattered back")
 
 
 def records_of(rt, O, D, max_t):
@@ -282,7 +278,7 @@ def test_the_sorted_batch_feeds_the_stages_on_the_teapot(rrt, teapot, kept, mode
     O, D, max_t = two_levels(rt, CREATION, W, H, kept["l0"])
     assert_sorted_rays_feed_the_surface_stage(torch, rt, O, D, max_t, f"teapot, walk {mode}")
     want = rt.ambient_rays(kept["rec"], T8, T8_MAX_T, rot=kept["rot"])["occluded"]
-    assert_same_bytes(want, kept["want"][True], f"walk {mode}: rt.ambient_rays on the original records vs the shadow query")
+    assert_same_bits(want, kept["want"][True], f"walk {mode}: rt.ambient_rays on the original records vs the shadow query")
     assert_sorted_records_feed_the_ambient_stage(torch, rt, kept["rec"], kept["rot"], kept["n_mats"], want, f"teapot level 1, walk {mode}")
 
 
@@ -360,9 +356,9 @@ def test_a_chain_on_the_device_alone(rrt, teapot, kept):
     stream.synchronize()
     assert int(count.cpu().numpy().view(np.uint32)[0]) == int(hit1.sum())
     keys = ray_key(l0["next_origin"], l0["next_dir"], np.zeros(n, bool), root_box_of(rt.octree()))
-    assert_same_bytes(index1.cpu().numpy().view(np.uint32), sorted_batch(keys, {})["index"], "level 0 -> 1: index of the sort")
+    assert_same_bits(index1.cpu().numpy().view(np.uint32), sorted_batch(keys, {})["index"], "level 0 -> 1: index of the sort")
     for k in OUTPUTS:
-        assert_same_bytes(final[k].cpu().numpy().view(np.uint32), want[k], f"{k}: the device chain, scattered back twice, vs the host forms in source order")
+        assert_same_bits(final[k].cpu().numpy().view(np.uint32), want[k], f"{k}: the device chain, scattered back twice, vs the host forms in source order")
 
 
 # ------------------------------------------------------------------ 7
@@ -384,7 +380,7 @@ def test_state_is_untouched(rrt, teapot, kept):
     assert_sorted(rt.sort_rays(rec, key="record"), want, "the host form")
     assert rt.last_stats() == before["stats"], "the host form changed the statistics"
     back = rt.scatter_rays(first["index"], first["material"], np.full(n, 0x5A5A5A5A, np.uint32))
-    assert_same_bytes(back, np.asarray(rec["material"]), "material, scattered back: the inverse of the sort")
+    assert_same_bits(back, np.asarray(rec["material"]), "material, scattered back: the inverse of the sort")
     # refusals of the device form with a real raytracer leave the guarded outputs as they were
     src_t = {k: to_device(torch, rec[k]) for k in INPUTS}
     out = {k: Guarded(torch, ARRAYS[k][0], ARRAYS[k][1] * n) for k in INPUTS}

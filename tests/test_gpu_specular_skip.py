@@ -15,9 +15,11 @@ evaluated, and nothing that reaches a pixel may change.  RRT_FLAG_NO_SPECULAR_SK
 import numpy as np
 import pytest
 
+from bitwise import assert_same_bits
 from conftest import channels
 from gpu_checks import ALL_MODES, N_THREADS, ORIGIN, ROOT_BOX, assert_frame_close, oracle_for, quad, flat_normals, row_dirs
-from shade_checks import assert_same_frame, assert_shade_is_render
+from scenes import teapot_arrays_with_root as teapot_arrays  # noqa: F401  (fixtures: teapot_arrays)
+from shade_checks import assert_shade_is_render
 from shade_rays_checks import oracle_colours
 
 pytestmark = pytest.mark.gpu
@@ -102,12 +104,6 @@ SIZES = ((160, 120), (97, 61))
 REGION = (48, 36, 64, 48)            # of the 160x120 frame: the teapot's body
 
 
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures(), root=ROOT_BOX)
-
-
 @pytest.mark.parametrize("which", ("default", "default_reversed"))
 def test_teapot_frames(rrt, ob, teapot, teapot_arrays, which):
     lights = rrt.default_lights() if which == "default" else rrt.default_lights()[::-1]
@@ -118,9 +114,9 @@ def test_teapot_frames(rrt, ob, teapot, teapot_arrays, which):
     for w, h in SIZES:
         ref = exact[False].render(w, h)
         assert_frame_close(ref, osc.render(w, h, n_threads=N_THREADS)[0], f"teapot {which} {w}x{h}: no-cull frame vs the oracle")
-        assert_same_frame(exact[True].render(w, h), ref, f"teapot {which} {w}x{h}, no-cull: with the skip vs without")
+        assert_same_bits(exact[True].render(w, h), ref, f"teapot {which} {w}x{h}, no-cull: with the skip vs without")
         for (mode, skip), rt in rts.items():
-            assert_same_frame(rt.render(w, h), ref, f"teapot {which} {w}x{h}, walk {mode}, skip {skip}: vs the no-cull frame")
+            assert_same_bits(rt.render(w, h), ref, f"teapot {which} {w}x{h}, walk {mode}, skip {skip}: vs the no-cull frame")
     # the shade kernel and the per-ray shade kernel, on a region
     w, h = SIZES[0]
     x0, y0, rw, rh = REGION
@@ -136,6 +132,6 @@ def test_teapot_frames(rrt, ob, teapot, teapot_arrays, which):
             n = int((shaded != colours).sum())
             assert n == 0, f"teapot {which}, walk {mode}, skip {skip}: {n} of {len(d)} colours of shade_rays differ from get_ray_colours"
             frames[skip] = (frames[skip], colours)
-        assert_same_frame(frames[True][0], frames[False][0], f"teapot {which}, walk {mode}: frame with the skip vs without")
+        assert_same_bits(frames[True][0], frames[False][0], f"teapot {which}, walk {mode}: frame with the skip vs without")
         n = int((frames[True][1] != frames[False][1]).sum())
         assert n == 0, f"teapot {which}, walk {mode}: {n} of {len(d)} ray colours change with the skip"

@@ -13,27 +13,16 @@ import importlib
 import numpy as np
 import pytest
 
+from bitwise import assert_same_arrays, same
 from gpu_checks import (ALL_MODES, CHAIN_LIGHTS, COLOUR_TOL, FORCED_MODES, MATS, ORIGIN, chain_rrt_lights, chain_scene, checker, closed_box, flat_normals, mix4,
                         oracle_for, quad, traced_rows)
-from surface_checks import (EXPECTED, MISS, NO_MATERIAL, assert_planes_equal, assert_untraced_pixels, bits, expected_planes, frame_dirs, length, light_vec, same, shade,
-                            traced_cols, traced_part, traced_pixels_in)
+from scenes import CREATION, EYE3, H3, MOVED_EYE, REGIONS, TARGET, W3, pose, posed, surface_frame3 as frame3, teapot_arrays, teapot_osc  # noqa: F401  (fixtures: frame3, teapot_arrays, teapot_osc)
+from surface_checks import (EXPECTED, MISS, NO_MATERIAL, assert_untraced_pixels, expected_planes, frame_dirs, length, light_vec, shade, traced_cols, traced_part,
+                            traced_pixels_in)
 
 pytestmark = pytest.mark.gpu
 
-TARGET = (0.0, 1.0, 0.0)
-IDENTITY = dict(right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0))
-CREATION = dict(eye=ORIGIN, **IDENTITY)
-MOVED_EYE = (9.0, 2.0, 1.0)
 W, H = 64, 48
-
-
-def pose(rrt, k):
-    return CREATION if k == 0 else rrt.look_at(MOVED_EYE, TARGET)
-
-
-def posed(rt, cam):
-    rt.set_camera(**cam)
-    return rt
 
 
 def check_against(rt, want, w, h, what, names=EXPECTED):
@@ -41,7 +30,7 @@ def check_against(rt, want, w, h, what, names=EXPECTED):
     got = rt.surface(w, h, visibility=("hit",))
     assert set(got) == set(EXPECTED), sorted(got)
     assert all(got[n].shape == ((h, w, 4, 3) if n in ("point", "normal") else (h, w, 4)) for n in got), {n: a.shape for n, a in got.items()}
-    assert_planes_equal(traced_part(got, w, h), want, names, what)
+    assert_same_arrays(traced_part(got, w, h), want, names, what)
     assert_untraced_pixels(got, w, h, what)
     return got
 
@@ -50,18 +39,6 @@ def mask_counts(ref):
     """(hit samples with bit 1 = 0 and bit 2 = 1, with bit 1 = 1 and bit 2 = 0): with the default lights, point lights 1 and 2."""
     hit, m = ref["hit"].astype(bool), ref["lights"]
     return int((hit & ((m >> 1) & 1 == 0) & ((m >> 2) & 1 == 1)).sum()), int((hit & ((m >> 1) & 1 == 1) & ((m >> 2) & 1 == 0)).sum())
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
-def teapot_osc(ob, rrt, teapot_arrays):
-    return oracle_for(ob, teapot_arrays, rrt.default_lights())
-
 
 _answers = {}
 
@@ -148,21 +125,8 @@ def test_the_planes_suffice_to_shade(rrt, teapot, teapot_arrays):
 
 
 # ------------------------------------------------------------------ 4
-W3, H3 = 203, 117
-EYE3 = (-7.0, 4.0, -6.0)
-REGIONS = ((0, 0, 203, 117), (5, 3, 1, 1), (200, 0, 3, 2), (8, 8, 8, 8), (13, 50, 77, 31))
+
 ALL_PLANES = ("hit", "t", "u", "v", "tri", "albedo", "point", "normal", "material", "lights")
-
-
-@pytest.fixture(scope="module")
-def frame3(rrt, teapot):
-    """A raytracer at the pose of part 4 that has rendered no frame, and its whole-frame planes, surface and visibility (read-only)."""
-    rt = rrt.RayTracer(teapot, rrt.default_lights())
-    rt.look_at(EYE3, TARGET)
-    full = rt.surface(W3, H3, visibility=rrt.PLANES)
-    for a in full.values():
-        a.setflags(write=False)
-    return rt, full
 
 
 def test_untraced_pixels_and_misses_carry_the_stated_values(rrt, frame3):
@@ -185,7 +149,7 @@ def test_a_region_is_a_slice_of_the_frame(rrt, frame3, region):
     want = {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}
     part = rt.surface(W3, H3, region=region, visibility=rrt.PLANES)
     stats = rt.last_stats()
-    assert_planes_equal(part, want, ALL_PLANES, f"region {region}")
+    assert_same_arrays(part, want, ALL_PLANES, f"region {region}")
     assert (stats["width"], stats["height"]) == (W3, H3)
     assert stats["rays_primary"] == 4 * traced_pixels_in(region, W3, H3), (region, stats["rays_primary"])
     assert stats["kernel_ms"] > 0
@@ -217,16 +181,16 @@ def test_the_combined_launch(rrt, frame3):
     for region in (None, REGIONS[4]):
         x0, y0, w, h = region or (0, 0, W3, H3)
         vis = rt.visibility(W3, H3, region=region)
-        assert_planes_equal({n: full[n][y0:y0 + h, x0:x0 + w] for n in rrt.PLANES}, vis, rrt.PLANES, f"region {region}: visibility planes of the combined launch")
+        assert_same_arrays({n: full[n][y0:y0 + h, x0:x0 + w] for n in rrt.PLANES}, vis, rrt.PLANES, f"region {region}: visibility planes of the combined launch")
         alone = rt.surface(W3, H3, region=region)
         assert set(alone) == set(rrt.SURFACE_PLANES)
-        assert_planes_equal(alone, {n: full[n][y0:y0 + h, x0:x0 + w] for n in rrt.SURFACE_PLANES}, rrt.SURFACE_PLANES, f"region {region}: surface planes without visibility planes")
+        assert_same_arrays(alone, {n: full[n][y0:y0 + h, x0:x0 + w] for n in rrt.SURFACE_PLANES}, rrt.SURFACE_PLANES, f"region {region}: surface planes without visibility planes")
         three = rt.surface(W3, H3, region=region, planes=("point", "normal", "material"))
         assert set(three) == {"point", "normal", "material"}
-        assert_planes_equal(three, alone, three.keys(), f"region {region}: without the lights plane")
+        assert_same_arrays(three, alone, three.keys(), f"region {region}: without the lights plane")
         two = rt.surface(W3, H3, region=region, planes=("lights",), visibility=("tri",))
         assert set(two) == {"lights", "tri"}
-        assert_planes_equal(two, dict(lights=alone["lights"], tri=vis["tri"]), two.keys(), f"region {region}: lights and tri only")
+        assert_same_arrays(two, dict(lights=alone["lights"], tri=vis["tri"]), two.keys(), f"region {region}: lights and tri only")
 
 
 # ------------------------------------------------------------------ 6
@@ -249,7 +213,7 @@ def test_a_new_light_list_is_followed(rrt, ob, teapot, teapot_arrays, teapot_ans
         rt.set_lights([])
         got = traced_part(rt.surface(W, H), W, H)
         assert (got["lights"] == 0).all(), "an empty light list gives an empty mask"
-        assert_planes_equal(got, ref, ("point", "normal", "material"), f"no lights, walk {mode}")
+        assert_same_arrays(got, ref, ("point", "normal", "material"), f"no lights, walk {mode}")
 
 
 def box_scene():
@@ -291,7 +255,7 @@ def test_the_surface_offset_option_is_followed(rrt, ob, teapot, teapot_arrays, t
     n_diff = int((ref["lights"] != default["lights"]).sum())
     print(f"surface_offset 1e-2: the mask differs from the default's on {n_diff} samples")
     assert n_diff >= 1
-    assert_planes_equal(ref, default, ("hit", "point", "normal", "material"), "the offset moves shadow rays only")
+    assert_same_arrays(ref, default, ("hit", "point", "normal", "material"), "the offset moves shadow rays only")
     for mode in FORCED_MODES:
         check_against(rrt.RayTracer(teapot, lights, surface_offset=1e-2, box_filter=mode), ref, W, H, f"surface_offset 1e-2, walk {mode}")
 
@@ -364,7 +328,7 @@ def test_the_tuning_state_is_untouched(rrt, teapot, frame3, frames_before):
         variant = rt.last_stats()["filter_variant"]
     got = rt.surface(W3, H3, visibility=rrt.PLANES)
     stats = rt.last_stats()
-    assert_planes_equal(got, full, ALL_PLANES, f"after {frames_before} frames")
+    assert_same_arrays(got, full, ALL_PLANES, f"after {frames_before} frames")
     assert (stats["width"], stats["height"], stats["rays_primary"]) == (W3, H3, 4 * traced_pixels_in(REGIONS[0], W3, H3)) and stats["kernel_ms"] > 0, stats
     rt.surface(W3, H3, region=REGIONS[3], planes=("lights",))
     rt.surface(64, 48)                                                             # another size must not become "the" size either
@@ -395,4 +359,4 @@ def test_refusals_leave_the_raytracer_as_it_was(rrt, frame3, teapot):
         with pytest.raises(rrt.RrtError) as e:
             call()
         assert e.value.status == rrt.ERR_INVALID_ARG, what
-        assert_planes_equal(rt.surface(W3, H3, region=region, visibility=rrt.PLANES), want, ALL_PLANES, f"after the refusal of: {what}")
+        assert_same_arrays(rt.surface(W3, H3, region=region, visibility=rrt.PLANES), want, ALL_PLANES, f"after the refusal of: {what}")

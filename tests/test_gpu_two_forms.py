@@ -12,10 +12,11 @@ import numpy as np
 import pytest
 
 from ambient_checks import table8
+from bitwise import assert_same_bits
 from gpu_checks import FORCED_MODES, ORIGIN, mix4
 from ray_surface_checks import kr_of
-from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, mirror_room
-from surface_checks import bits, frame_dirs, traced_part
+from scenes import CREATION, room_without_oracle as room  # noqa: F401  (fixtures: room)
+from surface_checks import frame_dirs, traced_part
 
 pytestmark = pytest.mark.gpu
 
@@ -61,23 +62,10 @@ def flat_traced(planes, w, h, names):
     return {name: np.ascontiguousarray(a.reshape((-1, 3) if name in VECTORS else (-1,))) for name, a in part.items()}
 
 
-def assert_same_bits(got, want, what):
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype}{got.shape} vs {want.dtype}{want.shape}"
-    bad = bits(got) != bits(want)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} elements differ, first at {np.argwhere(bad)[0].tolist()}: {got[bad][0]!r} vs {want[bad][0]!r}"
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _torch():
     global torch
     torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def room(rrt):
-    A = mirror_room()
-    lights = [rrt.Light(k, i, rrt.Vector3d(*v)) for k, i, v in MIRROR_ROOM_LIGHTS]
-    return A, lights, rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"])
 
 
 # ------------------------------------------------------------------ surface

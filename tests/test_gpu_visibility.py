@@ -14,46 +14,16 @@ Every comparison with the oracle asserts the fraction of rays that hit BY THE OR
 import numpy as np
 import pytest
 
-from gpu_checks import (FORCED_MODES, ORIGIN, POOL, chain_rrt_lights, chain_scene, oracle_for, plane_scene, plane_scene_data, pose_dirs, traced_rows, CHAIN_LIGHTS)
+from bitwise import assert_same_arrays, same
+from gpu_checks import CHAIN_LIGHTS, FORCED_MODES, POOL, chain_rrt_lights, chain_scene, oracle_for, plane_scene, plane_scene_data
+from scenes import EYE3, H3, REGIONS, TARGET, W3, pose, posed, teapot_arrays, teapot_osc, visibility_frame3 as frame3  # noqa: F401  (fixtures: frame3, teapot_arrays, teapot_osc)
+from surface_checks import assert_untraced_pixels, frame_dirs, traced_part, traced_pixels_in
 
 pytestmark = pytest.mark.gpu
 
-TARGET = (0.0, 1.0, 0.0)
-IDENTITY = dict(right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0))
-CREATION = dict(eye=ORIGIN, **IDENTITY)
 EYES = ((6.0, 3.0, -8.0), (9.0, 2.0, 1.0), (0.0, 9.0, -4.0))
 GEOMETRY = ("hit", "t", "u", "v", "tri")
-NEVER_TRACED = dict(hit=0, t=0.0, u=0.0, v=0.0, tri=0xFFFFFFFF, albedo=0)
 NO_TRI = 0xFFFFFFFF
-
-
-def bits(a):
-    """An array as unsigned integers of its element size: equality of these is equality bit for bit."""
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and bool((bits(a) == bits(b)).all())
-
-
-def traced_cols(w):
-    return np.arange(2 * (w // 2))
-
-
-def frame_dirs(cam, w, h):
-    """[len(rows)][len(cols)][4][3]: directions of the traced pixels' sub-sample rays, in the planes' index order."""
-    return pose_dirs(cam, w, h, traced_rows(h), traced_cols(w)).transpose(0, 2, 1, 3)
-
-
-def pose(rrt, k):
-    return CREATION if k == 0 else rrt.look_at(EYES[k - 1], TARGET)
-
-
-def posed(rt, cam):
-    rt.set_camera(**cam)
-    return rt
 
 
 def oracle_planes(osc, cam, w, h):
@@ -67,40 +37,6 @@ def oracle_planes(osc, cam, w, h):
                 u=np.array([a[2] for a in ans], np.float64).reshape(shape), v=np.array([a[3] for a in ans], np.float64).reshape(shape),
                 tri=np.array([a[4] for a in ans], np.uint32).reshape(shape))
 
-
-def assert_planes_equal(got, want, names, what):
-    for n in names:
-        bad = bits(got[n]) != bits(want[n])
-        assert got[n].shape == want[n].shape and not bad.any(), \
-            f"{what}: plane {n} differs on {int(bad.sum())} of {bad.size} rays, first at {np.argwhere(bad)[0].tolist()}: {got[n][bad][0]!r} vs {want[n][bad][0]!r}"
-
-
-def traced_part(planes, w, h):
-    ix = np.ix_(traced_rows(h), traced_cols(w))
-    return {n: a[ix] for n, a in planes.items()}
-
-
-def assert_untraced_pixels(planes, w, h, what):
-    """Row 0, row 1 of an odd height and the last column of an odd width hold the "never traced" values in every plane."""
-    mask = np.ones((h, w), bool)
-    mask[np.ix_(traced_rows(h), traced_cols(w))] = False
-    assert mask[0].all() and mask.sum() == w * h - len(traced_rows(h)) * len(traced_cols(w))
-    for n, a in planes.items():
-        want = np.full((int(mask.sum()), 4), NEVER_TRACED[n], a.dtype)
-        assert same(a[mask], want), f"{what}: plane {n} of the pixels the reference never traces is not all {NEVER_TRACED[n]!r}"
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
-def teapot_osc(ob, rrt, teapot_arrays):
-    return oracle_for(ob, teapot_arrays, rrt.default_lights())
-
-
 _answers = {}
 
 
@@ -109,7 +45,7 @@ def teapot_answers(rrt, teapot_osc):
     """(pose index, w, h) -> the oracle's planes, computed once per pose and size and shared by the tests; never modified."""
     def get(k, w, h):
         if (k, w, h) not in _answers:
-            ref = oracle_planes(teapot_osc, pose(rrt, k), w, h)
+            ref = oracle_planes(teapot_osc, pose(rrt, k, EYES), w, h)
             for a in ref.values():
                 a.setflags(write=False)
             _answers[(k, w, h)] = ref
@@ -121,7 +57,7 @@ def teapot_answers(rrt, teapot_osc):
 @pytest.mark.parametrize("k", range(4), ids=["creation pose"] + [f"eye {e}" for e in EYES])
 @pytest.mark.parametrize("w,h", [(64, 48), (97, 61)])
 def test_geometry_planes_equal_the_oracles_intersector(rrt, teapot, teapot_answers, w, h, k):
-    cam = pose(rrt, k)
+    cam = pose(rrt, k, EYES)
     ref = teapot_answers(k, w, h)
     n_rays = ref["hit"].size
     assert n_rays == {(64, 48): 12032, (97, 61): 22656}[(w, h)]
@@ -132,7 +68,7 @@ def test_geometry_planes_equal_the_oracles_intersector(rrt, teapot, teapot_answe
         rt = posed(rrt.RayTracer(teapot, rrt.default_lights(), box_filter=mode), cam)
         planes = rt.visibility(w, h)
         assert set(planes) == set(rrt.PLANES) and all(a.shape == (h, w, 4) for a in planes.values())
-        assert_planes_equal(traced_part(planes, w, h), ref, GEOMETRY, f"{w}x{h}, pose {k}, walk {mode}")
+        assert_same_arrays(traced_part(planes, w, h), ref, GEOMETRY, f"{w}x{h}, pose {k}, walk {mode}")
         assert_untraced_pixels(planes, w, h, f"{w}x{h}, pose {k}, walk {mode}")
 
 
@@ -140,7 +76,7 @@ def test_geometry_planes_equal_the_oracles_intersector(rrt, teapot, teapot_answe
 @pytest.mark.parametrize("k", (1, 0), ids=[f"eye {EYES[0]}", "creation pose"])
 def test_albedo_plane_equals_the_oracles_shader(rrt, ob, teapot, teapot_arrays, teapot_answers, k):
     w, h = 64, 48
-    cam = pose(rrt, k)
+    cam = pose(rrt, k, EYES)
     flat_mats = [dict(m, ka=(1.0, 1.0, 1.0), kr=0.0) for m in teapot_arrays["materials"]]
     osc = oracle_for(ob, dict(teapot_arrays, materials=flat_mats), [rrt.Light.Ambient(1.0)])
     d = frame_dirs(cam, w, h)
@@ -154,31 +90,11 @@ def test_albedo_plane_equals_the_oracles_shader(rrt, ob, teapot, teapot_arrays, 
     for mode in FORCED_MODES:
         rt = posed(rrt.RayTracer(teapot, rrt.default_lights(), box_filter=mode), cam)            # the real materials, the default lights
         planes = rt.visibility(w, h, planes=("albedo", "hit"))
-        assert_planes_equal(traced_part(planes, w, h), dict(albedo=want, hit=hit.astype(np.uint8)), ("albedo", "hit"), f"pose {k}, walk {mode}")
+        assert_same_arrays(traced_part(planes, w, h), dict(albedo=want, hit=hit.astype(np.uint8)), ("albedo", "hit"), f"pose {k}, walk {mode}")
         assert_untraced_pixels(planes, w, h, f"pose {k}, walk {mode}")
 
 
 # ------------------------------------------------------------------ 3
-W3, H3 = 203, 117
-EYE3 = (-7.0, 4.0, -6.0)
-REGIONS = ((0, 0, 203, 117), (5, 3, 1, 1), (200, 0, 3, 2), (8, 8, 8, 8), (13, 50, 77, 31))
-
-
-def traced_pixels_in(region, w, h):
-    x0, y0, rw, rh = region
-    rows, cols = traced_rows(h), traced_cols(w)
-    return int(((rows >= y0) & (rows < y0 + rh)).sum()) * int(((cols >= x0) & (cols < x0 + rw)).sum())
-
-
-@pytest.fixture(scope="module")
-def frame3(rrt, teapot):
-    """A raytracer at the pose of part 3 that has rendered no frame, and its whole-frame planes (left unchanged by the tests that share them)."""
-    rt = rrt.RayTracer(teapot, rrt.default_lights())
-    rt.look_at(EYE3, TARGET)
-    full = rt.visibility(W3, H3)
-    for a in full.values():
-        a.setflags(write=False)
-    return rt, full
 
 
 def test_whole_frame_equals_the_per_ray_entry_point(rrt, frame3):
@@ -188,7 +104,7 @@ def test_whole_frame_equals_the_per_ray_entry_point(rrt, frame3):
     hit, t, u, v, tri = rt.intersect_rays(np.tile(cam["eye"], (d.size // 3, 1)), d.reshape(-1, 3))
     own = dict(hit=hit.astype(np.uint8), t=t, u=u, v=v, tri=tri)
     assert own["hit"].mean() >= 0.5, own["hit"].mean()
-    assert_planes_equal(traced_part(full, W3, H3), {n: a.reshape(d.shape[:3]) for n, a in own.items()}, GEOMETRY, "visibility vs intersect_rays")
+    assert_same_arrays(traced_part(full, W3, H3), {n: a.reshape(d.shape[:3]) for n, a in own.items()}, GEOMETRY, "visibility vs intersect_rays")
     assert_untraced_pixels(full, W3, H3, "whole frame")
     seen = traced_part(full, W3, H3)
     assert (seen["albedo"][seen["hit"] == 0] == 0xFFFFFF).all(), "a traced ray that misses has the background's albedo"
@@ -200,13 +116,13 @@ def test_a_region_is_a_slice_of_the_frame(frame3, region):
     x0, y0, w, h = region
     part = rt.visibility(W3, H3, region=region)
     stats = rt.last_stats()
-    assert_planes_equal(part, {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, full.keys(), f"region {region}")
+    assert_same_arrays(part, {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, full.keys(), f"region {region}")
     assert (stats["width"], stats["height"]) == (W3, H3)
     assert stats["rays_primary"] == 4 * traced_pixels_in(region, W3, H3), (region, stats["rays_primary"])
     assert stats["kernel_ms"] > 0
     two = rt.visibility(W3, H3, region=region, planes=("t", "tri"))
     assert set(two) == {"t", "tri"}
-    assert_planes_equal(two, part, ("t", "tri"), f"region {region}, t and tri only")
+    assert_same_arrays(two, part, ("t", "tri"), f"region {region}, t and tri only")
 
 
 def test_pick_is_sub_sample_0_of_the_pixel(frame3):
@@ -234,11 +150,11 @@ def test_device_tensors_equal_the_host_form(rrt, frame3):
         rt.visibility_into(tensors, W3, H3, region=region)
         torch.cuda.synchronize()
         got = {n: t.cpu().numpy().view(full[n].dtype) for n, t in tensors.items()}
-        assert_planes_equal(got, {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, full.keys(), f"visibility_into, region {region}")
+        assert_same_arrays(got, {n: a[y0:y0 + h, x0:x0 + w] for n, a in full.items()}, full.keys(), f"visibility_into, region {region}")
     for name in kinds:                                                             # the host form with ONE plane asked for and five NULL, against the device form's
         one = rt.visibility(W3, H3, region=region, planes=(name,))
         assert set(one) == {name}
-        assert_planes_equal(one, got, (name,), f"region {region}: plane {name} alone, host form vs visibility_into")
+        assert_same_arrays(one, got, (name,), f"region {region}: plane {name} alone, host form vs visibility_into")
 
 
 @pytest.mark.parametrize("frames_before", (0, 1, 2))
@@ -255,7 +171,7 @@ def test_the_tuning_state_is_untouched(rrt, teapot, frame3, frames_before):
         variant = rt.last_stats()["filter_variant"]
     got = rt.visibility(W3, H3)
     vis_variant = rt.last_stats()["filter_variant"]
-    assert_planes_equal(got, full, full.keys(), f"after {frames_before} frames")
+    assert_same_arrays(got, full, full.keys(), f"after {frames_before} frames")
     rt.visibility(W3, H3, region=REGIONS[3], planes=("hit",))
     rt.pick(W3, H3, 100, 60)
     rt.visibility(64, 48)                                                          # another size must not become "the" size either
@@ -286,7 +202,7 @@ def test_chain_shortcut_scene_equals_the_oracle(rrt, ob):
         rt = posed(rrt.RayTracer(sd, chain_rrt_lights(rrt), rrt.Vector3d(*eye), box_filter=mode, chain_shortcut=shortcut), cam)
         assert rt.chain_info["n_chains"] >= 1, rt.chain_info
         planes = rt.visibility(w, h)
-        assert_planes_equal(traced_part(planes, w, h), ref, GEOMETRY, f"chain scene, walk {mode}, shortcut {shortcut}")
+        assert_same_arrays(traced_part(planes, w, h), ref, GEOMETRY, f"chain scene, walk {mode}, shortcut {shortcut}")
         assert_untraced_pixels(planes, w, h, f"chain scene, walk {mode}")
 
 
@@ -310,7 +226,7 @@ def test_the_guard_of_a_moved_eye(rrt):
         assert rt.last_stats()["origin_plane_triangles"] == 0
         rt.set_camera(**cam)
         assert rt.last_stats()["origin_plane_triangles"] == 60
-        assert_planes_equal(rt.visibility(w, h), exact, exact.keys(), f"guard scene, walk {mode} vs no_cull")
+        assert_same_arrays(rt.visibility(w, h), exact, exact.keys(), f"guard scene, walk {mode} vs no_cull")
 
 
 # ------------------------------------------------------------------ 6

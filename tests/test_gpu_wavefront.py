@@ -9,49 +9,25 @@ integer bits.
 import numpy as np
 import pytest
 
+from bitwise import assert_same_bits, bits, same
 from gpu_checks import ALL_MODES, chain_rrt_lights, chain_scene
 from ray_surface_checks import WHITE
-from shade_checks import CREATION, MIRROR_ROOM_LIGHTS, TARGET, assert_same_frame, mirror_room, soup_scene
-from surface_checks import bits, same, traced_pixels_in
+from scenes import MOVED_EYE, TARGET, pose, room_without_oracle as room, teapot_arrays  # noqa: F401  (fixtures: room, teapot_arrays)
+from shade_checks import MIRROR_ROOM_LIGHTS, soup_scene
+from surface_checks import traced_pixels_in
 from wavefront_checks import (ARRAYS, DEAD_BOUND, FRAMES, ORDERS, REGIONS, ROWS, SENTINEL, TILES, WIDTHS, alive_entries, assert_wavefront_is_render, expected_pixels,
-                              expected_rays, host, mix_level, ray_count, region_of)
+                              expected_rays, host, mix_case, mix_level, ray_count, region_of)
 
 pytestmark = pytest.mark.gpu
 
-MOVED_EYE = (9.0, 2.0, 1.0)
 RW, RH = 32, 24                                                  # the mirror room's and the soup's frame
 RECORDS = ("hit", "t", "u", "v", "tri", "albedo", "point", "normal", "material", "lights")   # what rrt_render_surface gives with its visibility planes
-
-
-def pose(rrt, k):
-    return CREATION if k == 0 else rrt.look_at(MOVED_EYE, TARGET)
-
-
-def assert_same_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype}{got.shape} vs {want.dtype}{want.shape}"
-    bad = bits(got) != bits(want)
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} elements differ, first at {np.argwhere(bad)[0].tolist()}: {got[bad][0]!r} vs {want[bad][0]!r}"
 
 
 def device(torch, a):
     """A host array as a flat device tensor of the same bits (uint32 travels as int32)"""
     a = np.ascontiguousarray(a)
     return torch.tensor(a.view(np.int32) if a.dtype == np.uint32 else a, device="cuda").reshape(-1)
-
-
-@pytest.fixture(scope="module")
-def teapot_arrays(teapot):
-    pos, uv, nrm, mat = teapot.triangles()
-    return dict(pos=pos, uv=uv, nrm=nrm, mat=mat, materials=teapot.materials(), textures=teapot.textures())
-
-
-@pytest.fixture(scope="module")
-def room(rrt):
-    """(arrays, lights, SceneData) of shade_checks.mirror_room with MIRROR_ROOM_LIGHTS"""
-    A = mirror_room()
-    lights = [rrt.Light(k, i, rrt.Vector3d(*v)) for k, i, v in MIRROR_ROOM_LIGHTS]
-    return A, lights, rrt.SceneData.from_arrays(A["pos"], A["uv"], A["nrm"], A["mat"], A["materials"], A["textures"])
 
 
 # ------------------------------------------------------------------ 1: the generator
@@ -153,23 +129,6 @@ def test_the_frame_rays_beyond_4_GiB(rrt, teapot):
 
 
 # ------------------------------------------------------------------ 2: one level of the unwind
-def mix_case(n, n_mats):
-    """A third misses, a third with kr = 0, a third with kr in (0, 1]; local with negatives, values above 255, exact integers, NaN and +-inf; junk in reflected's top byte"""
-    rng = np.random.default_rng(n)
-    local = rng.uniform(-40.0, 320.0, (n, 3))
-    whole = rng.random((n, 3)) < 0.25
-    local[whole] = np.round(local[whole])
-    for j, v in enumerate((np.nan, np.inf, -np.inf, 255.0, 256.0, 0.0, -0.0, 254.99999999999997)):
-        local[(3 * j + 1) % n, j % 3] = v
-    kind = np.arange(n) % 3
-    material = np.where(kind == 0, 0xFFFFFFFF, rng.integers(0, n_mats, n)).astype(np.uint32)
-    material[np.flatnonzero(kind == 0)[::2]] = n_mats               # (misses by the first index that is no material, and by 0xFFFFFFFF)
-    kr = np.where(kind == 2, 1.0 - rng.random(n), 0.0)
-    kr[(kind == 2) & (np.arange(n) % 5 == 0)] = 1.0
-    kr[(kind == 1) & (np.arange(n) % 7 == 0)] = -0.5
-    kr[(kind == 1) & (np.arange(n) % 11 == 0)] = np.nan
-    reflected = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
-    return local, kr, reflected, material
 
 
 @pytest.mark.parametrize("n", (1, 63, 64, 65, 129, 4097))
@@ -211,14 +170,14 @@ def test_the_pixels(rrt, teapot, w, h):
             colours = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
             want = expected_pixels(colours, w, h, region, order)
             got = rt.mix_pixels(colours, w, h, region=region, order=order)
-            assert_same_frame(got, want, f"{what}: host form vs the restatement")
+            assert_same_bits(got, want, f"{what}: host form vs the restatement")
             for shift in (0, 1):                                   # colours at a 16-byte aligned address, and at one that is only 4-byte aligned
                 fb = torch.full((want.size,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
                 c = torch.zeros(n + shift, dtype=torch.int32, device="cuda")
                 c[shift:] = device(torch, colours)
                 rt.mix_pixels_into(fb, c[shift:], w, h, region=region, order=order)
                 torch.cuda.synchronize()
-                assert_same_frame(host(fb, np.uint32, want.shape), want, f"{what}: device form, colours shifted by {shift}")
+                assert_same_bits(host(fb, np.uint32, want.shape), want, f"{what}: device form, colours shifted by {shift}")
     assert rt.last_stats() == stats, "rrt_mix_pixels touched rrt_last_stats"
 
 
@@ -322,7 +281,7 @@ def test_the_pieces_compose(rrt, room, order):
         fb = i4(RW * RH)
         rt.mix_pixels_into(fb, colour, RW, RH, order=order, stream=s)
     stream.synchronize()
-    assert_same_frame(host(fb, np.uint32, (RH, RW)), want, f"order {order}: the pipeline from library calls vs render")
+    assert_same_bits(host(fb, np.uint32, (RH, RW)), want, f"order {order}: the pipeline from library calls vs render")
     alive = [4 * traced_pixels_in((0, 0, RW, RH), RW, RH)] + [int(c.cpu().numpy().view(np.uint32)[0]) for _, _, _, c in levels[:-1]]
     print(f"order {order}: rays alive per level {alive}")
     assert alive[0] == 2944 and alive[5] >= 1000 and all(a >= b for a, b in zip(alive, alive[1:])), alive
@@ -337,11 +296,11 @@ def test_scene_changes_are_followed(rrt, room):
     def check(what):
         want = rt.render(RW, RH)
         for order in ORDERS:
-            assert_same_frame(rt.render_wavefront(RW, RH, order=order), want, f"after {what}, order {order}: render_wavefront vs render")
-            assert_same_frame(rt.render_wavefront(RW, RH, region=(5, 3, 18, 14), order=order), want[3:17, 5:23], f"after {what}, order {order}, a region")
+            assert_same_bits(rt.render_wavefront(RW, RH, order=order), want, f"after {what}, order {order}: render_wavefront vs render")
+            assert_same_bits(rt.render_wavefront(RW, RH, region=(5, 3, 18, 14), order=order), want[3:17, 5:23], f"after {what}, order {order}, a region")
         assert not any((want == f).all() for f in seen), f"{what} did not change the frame"
         seen.append(want)
-    check_first = [assert_same_frame(rt.render_wavefront(RW, RH, order=o), seen[0], f"before any change, order {o}") for o in ORDERS]
+    check_first = [assert_same_bits(rt.render_wavefront(RW, RH, order=o), seen[0], f"before any change, order {o}") for o in ORDERS]
     assert len(check_first) == 2
     rt.look_at((2.0, 3.0, -9.0), TARGET)
     check("set_camera")

@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_checks import NoLibrary, assert_refused
+
 
 def test_ray_query_calls_refuse_a_null_raytracer(rrt):
     L = rrt.lib()
@@ -13,15 +15,11 @@ def test_ray_query_calls_refuse_a_null_raytracer(rrt):
     out = (C.c_double * 4)()
     variant = C.c_uint32(7)
     p, o = C.addressof(rays), C.addressof(out)
-    for what, call in (("rrt_intersect_rays_device", lambda: L.rrt_intersect_rays_device(None, 1, p, p + 24, None, o, o, o, o, o, None)),
-                       ("rrt_get_ray_colours_device", lambda: L.rrt_get_ray_colours_device(None, 1, p, p + 24, o, None)),
-                       ("rrt_occluded_rays", lambda: L.rrt_occluded_rays(None, 1, C.cast(p, rrt._dp), C.cast(p + 24, rrt._dp), None, C.cast(o, rrt._u8p))),
-                       ("rrt_occluded_rays_device", lambda: L.rrt_occluded_rays_device(None, 1, p, p + 24, None, o, None)),
-                       ("rrt_tune_rays_device", lambda: L.rrt_tune_rays_device(None, 1, p, p + 24, None, C.byref(variant)))):
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
+    assert_refused(rrt, L, (("rrt_intersect_rays_device", lambda: L.rrt_intersect_rays_device(None, 1, p, p + 24, None, o, o, o, o, o, None)),
+                            ("rrt_get_ray_colours_device", lambda: L.rrt_get_ray_colours_device(None, 1, p, p + 24, o, None)),
+                            ("rrt_occluded_rays", lambda: L.rrt_occluded_rays(None, 1, C.cast(p, rrt._dp), C.cast(p + 24, rrt._dp), None, C.cast(o, rrt._u8p))),
+                            ("rrt_occluded_rays_device", lambda: L.rrt_occluded_rays_device(None, 1, p, p + 24, None, o, None)),
+                            ("rrt_tune_rays_device", lambda: L.rrt_tune_rays_device(None, 1, p, p + 24, None, C.byref(variant)))))
     assert list(out) == [0.0] * 4 and variant.value == 7
 
 
@@ -30,15 +28,10 @@ def test_the_mirror_has_the_device_forms(rrt):
         assert callable(getattr(rrt.RayTracer, name)), name
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was called ({name}) with arguments that are not device tensors")
-
-
 def test_into_forms_refuse_numpy_arrays_before_any_library_call(rrt, monkeypatch):
     rt = rrt.RayTracer.__new__(rrt.RayTracer)                                # no handle: nothing below may get as far as needing one
     rt._h = None
-    monkeypatch.setattr(rrt, "lib", lambda: _NoLibrary())
+    monkeypatch.setattr(rrt, "lib", lambda: NoLibrary())
     o = np.zeros((4, 3)); d = np.ones((4, 3)); m = np.ones(4)
     with pytest.raises(AssertionError, match="not a device tensor"):
         rt.occluded_into(o, d, np.zeros(4, np.uint8), m, stream=0)

@@ -2,19 +2,16 @@
 layout on both sides, the exported symbols, the argument checks the library makes before any HIP call, the checks the Python mirror makes before it calls the
 library, and -- on the CPU, with the oracle -- that tests/ray_surface_checks.py restates tests/surface_checks.py."""
 import ctypes as C
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from abi_checks import CallRecorder, NoLibrary, assert_refused, bare_raytracer, compiled_layout, fake_device
+from bitwise import assert_same_arrays
 from gpu_checks import ORIGIN, oracle_for
-from ray_surface_checks import DTYPES, NAMES, VECTORS, assert_arrays_equal, assert_miss_values, expected_ray_planes, kr_of, rows
+from ray_surface_checks import DTYPES, NAMES, VECTORS, assert_miss_values, expected_ray_planes, kr_of, rows
+from scenes import CREATION
 from surface_checks import expected_planes, frame_dirs
-
-IDENTITY = dict(right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), forward=(0.0, 0.0, 1.0))
-CREATION = dict(eye=ORIGIN, **IDENTITY)
 
 
 def test_the_struct_is_96_bytes_on_both_sides(rrt, tmp_path):
@@ -22,13 +19,7 @@ def test_the_struct_is_96_bytes_on_both_sides(rrt, tmp_path):
     assert tuple(n for n, _ in rrt.CRaySurface._fields_) == rrt.RAY_SURFACE_PLANES == NAMES
     assert [getattr(rrt.CRaySurface, n).offset for n in NAMES] == list(range(0, 96, 8))
     assert rrt.STRUCTS["rrt_ray_surface"] is rrt.CRaySurface
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc is not None, "no host C compiler (build() needs one for the oracle)"
-    src = tmp_path / "size.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "rrt.h"\nint main(void) { printf("%zu %zu %zu\\n", sizeof(rrt_ray_surface), '
-                   'offsetof(rrt_ray_surface, point), offsetof(rrt_ray_surface, next_dir)); return 0; }\n')
-    subprocess.run([cc, "-std=c99", "-I", f"{ROOT}/include", "-o", str(tmp_path / "size"), str(src)], check=True)
-    assert subprocess.run([str(tmp_path / "size")], check=True, capture_output=True, text=True).stdout.split() == ["96", "48", "88"]
+    assert compiled_layout(tmp_path, "rrt_ray_surface", ("point", "next_dir")) == (96, [48, 88])
 
 
 def test_both_symbols_are_exported_and_bound(rrt):
@@ -47,66 +38,31 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
     p = C.addressof(rays)
     out = rrt.CRaySurface(t=C.addressof(buf))
     host = lambda *a: L.rrt_surface_rays(None, 1, C.cast(p, rrt._dp), C.cast(p + 24, rrt._dp), None, *a)
-    for what, call in (("rrt_surface_rays", lambda: host(C.byref(out))),
-                       ("rrt_surface_rays, NULL struct", lambda: host(None)),
-                       ("rrt_surface_rays_device", lambda: L.rrt_surface_rays_device(None, 1, p, p + 24, None, C.byref(out), None)),
-                       ("rrt_surface_rays_device, n = 0", lambda: L.rrt_surface_rays_device(None, 0, None, None, None, C.byref(out), None))):
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
+    assert_refused(rrt, L, (("rrt_surface_rays", lambda: host(C.byref(out))),
+                            ("rrt_surface_rays, NULL struct", lambda: host(None)),
+                            ("rrt_surface_rays_device", lambda: L.rrt_surface_rays_device(None, 1, p, p + 24, None, C.byref(out), None)),
+                            ("rrt_surface_rays_device, n = 0", lambda: L.rrt_surface_rays_device(None, 0, None, None, None, C.byref(out), None))))
     assert list(buf) == [0.0] * 4
-
-
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was called ({name}) with arguments the binding has to refuse")
-
-
-class _Recorder:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append((name, args))
-            return 0
-        return entry
-
-
-def _fake_device(t):
-    class FakeDeviceTensor:
-        """What _device_tensor asks of a tensor, with is_cuda forced (as in tests/test_binding_calls.py)."""
-        is_cuda = True
-        def __getattr__(self, k):
-            return getattr(t, k)
-    return FakeDeviceTensor()
-
-
-def _bare_raytracer(rrt):
-    rt = rrt.RayTracer.__new__(rrt.RayTracer)                                # no handle: nothing may get as far as needing one
-    rt._h = None
-    return rt
 
 
 def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    monkeypatch.setattr(rrt, "lib", lambda: _NoLibrary())
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
+    rt = bare_raytracer(rrt)
+    monkeypatch.setattr(rrt, "lib", lambda: NoLibrary())
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
     o, d = f8(12), f8(12)
     with pytest.raises(AssertionError, match="not a device tensor"):
         rt.surface_rays_into(np.zeros((4, 3)), np.ones((4, 3)), {"t": np.zeros(4)}, stream=0)
     with pytest.raises(AssertionError, match="not a device tensor"):
         rt.surface_rays_into(o, d, {"t": np.zeros(4)}, stream=0)
     with pytest.raises(AssertionError, match="t: want 4 contiguous elements of 8 bytes"):                  # a wrong dtype
-        rt.surface_rays_into(o, d, {"t": _fake_device(torch.zeros(4, dtype=torch.float32))}, stream=0)
+        rt.surface_rays_into(o, d, {"t": fake_device(torch.zeros(4, dtype=torch.float32))}, stream=0)
     with pytest.raises(AssertionError, match="hit: want 4 contiguous elements of 1 bytes"):
-        rt.surface_rays_into(o, d, {"hit": _fake_device(torch.zeros(4, dtype=torch.int32))}, stream=0)
+        rt.surface_rays_into(o, d, {"hit": fake_device(torch.zeros(4, dtype=torch.int32))}, stream=0)
     with pytest.raises(AssertionError, match="normal: want 12 contiguous elements of 8 bytes"):           # a wrong length: n where 3 n are wanted
         rt.surface_rays_into(o, d, {"normal": f8(4)}, stream=0)
     with pytest.raises(AssertionError, match="lights: want 4 contiguous elements of 4 bytes"):
-        rt.surface_rays_into(o, d, {"lights": _fake_device(torch.zeros(5, dtype=torch.int32))}, stream=0)
+        rt.surface_rays_into(o, d, {"lights": fake_device(torch.zeros(5, dtype=torch.int32))}, stream=0)
     with pytest.raises(AssertionError, match="max_t: want 4 contiguous elements"):
         rt.surface_rays_into(o, d, {"t": f8(4)}, max_t_t=f8(3), stream=0)
     with pytest.raises(AssertionError, match="not a multiple of 3"):
@@ -121,12 +77,12 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
 
 def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    rec = _Recorder()
+    rt = bare_raytracer(rrt)
+    rec = CallRecorder()
     monkeypatch.setattr(rrt, "lib", lambda: rec)
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
     o, d, m = f8(12), f8(12), f8(4)
-    out = dict(normal=f8(12), lights=_fake_device(torch.zeros(4, dtype=torch.int32)), next_dir=f8(12))
+    out = dict(normal=f8(12), lights=fake_device(torch.zeros(4, dtype=torch.int32)), next_dir=f8(12))
     rt.surface_rays_into(o, d, out, max_t_t=m, stream=0x51)
     (name, args), = rec.calls
     assert name == "rrt_surface_rays_device" and args[1] == 4
@@ -161,9 +117,9 @@ def test_for_one_eye_the_restatement_is_surface_checks(rrt, ob, teapot):
     old = expected_planes(osc, A, lights, ORIGIN, d)
     new = expected_ray_planes(osc, A, lights, ORIGIN, d)
     assert set(new) == set(NAMES) | {"bumped"} and set(old) == set(new) - {"albedo", "next_origin", "next_dir"}
-    assert_arrays_equal(new, old, sorted(old), "one eye")
+    assert_same_arrays(new, old, sorted(old), "one eye")
     per_ray = expected_ray_planes(osc, A, lights, np.broadcast_to(np.asarray(ORIGIN), d.shape), d, np.full(d.shape[:-1], np.inf))
-    assert_arrays_equal(per_ray, new, sorted(new), "the eye and +inf repeated per ray")
+    assert_same_arrays(per_ray, new, sorted(new), "the eye and +inf repeated per ray")
     hit = new["hit"].astype(bool)
     mirror = hit & (kr_of(A, new["material"]) > 0.0)
     masks = set(np.unique(new["lights"][hit]).tolist())

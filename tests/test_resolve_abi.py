@@ -6,9 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_compact_abi import _NoLibrary, _Recorder, _bare_raytracer, _fake_device
+from abi_checks import PATTERN, CallRecorder, NoLibrary, assert_refused, bare_raytracer, fake_device
 
-PATTERN = 0xA5A5A5A5
 OUTPUTS = ("albedo", "point", "normal", "material", "lights", "next_origin", "next_dir")
 READS_UV = ("albedo", "normal", "lights", "next_origin", "next_dir")
 
@@ -76,13 +75,7 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
             calls += [(f"{form}, {name} without u", lambda call=call, name=name: call(fake, n, vec, vec, rec((name,), u=None))),
                       (f"{form}, {name} and point without v", lambda call=call, name=name: call(fake, n, vec, vec, rec((name, "point"), v=None)))]
     assert len(calls) == 3 * (11 + 2 * 5)
-    for what, call in calls:
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
-        for name, a in outs.items():
-            assert (a == PATTERN).all(), f"{what}: {name} of a refused call was written"
+    assert_refused(rrt, L, calls, outs)
     # n == 0 with a valid struct: RRT_OK, nothing enqueued (the handle is not a raytracer), also without rays and without the arrays a longer batch would need
     for call in (host, dev, counted):
         assert call(fake, 0, vec, vec, rec()) == rrt.OK
@@ -94,11 +87,11 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
 
 def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    monkeypatch.setattr(rrt, "lib", lambda: _NoLibrary())
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    f4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float32))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
+    rt = bare_raytracer(rrt)
+    monkeypatch.setattr(rrt, "lib", lambda: NoLibrary())
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    f4 = lambda n: fake_device(torch.zeros(n, dtype=torch.float32))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
     planes = dict(t=f8(4), u=f8(4), v=f8(4), tri=i4(4))
 
     def into(out, o=None, d=None, planes=planes, bound_t=None):
@@ -132,12 +125,12 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
 
 def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    rec = _Recorder()
+    rt = bare_raytracer(rrt)
+    rec = CallRecorder()
     monkeypatch.setattr(rrt, "lib", lambda: rec)
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
-    u1 = lambda n: _fake_device(torch.zeros(n, dtype=torch.uint8))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
+    u1 = lambda n: fake_device(torch.zeros(n, dtype=torch.uint8))
     names = tuple(n for n, _ in rrt.CRaySurface._fields_)
     pointers = lambda s: {n: getattr(s, n) for n in names}
     o, d = f8(15), f8(15)

@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_checks import fake_device
+
 
 def test_the_five_calls_reject_a_null_handle(rrt):
     L = rrt.lib()
@@ -46,14 +48,7 @@ def test_set_triangles_from_rejects_tensors_before_any_call(rrt, monkeypatch):
     with pytest.raises(ValueError):
         rt.set_triangles_from(np.zeros((4, 3, 3)), np.zeros((4, 3, 3)), np.zeros((4, 3, 3)), np.zeros(4, np.uint32))
 
-    class FakeDeviceTensor:
-        """What _device_tensor asks of a tensor, with is_cuda forced: the contiguity and dtype checks can then be reached without a GPU."""
-        def __init__(self, t):
-            self.t = t
-        is_cuda = True
-        device = torch.device("cuda", 0)
-        def __getattr__(self, k):
-            return getattr(self.t, k)
+    FakeDeviceTensor = lambda t: fake_device(t, torch.device("cuda", 0))
     ok = FakeDeviceTensor(pos)
     with pytest.raises(ValueError, match="contiguous"):
         rt.set_triangles_from(FakeDeviceTensor(torch.zeros((4, 3, 6), dtype=torch.float64)[:, :, ::2]), ok, ok, FakeDeviceTensor(mat))

@@ -2,13 +2,11 @@
 struct layout on both sides, the exported symbols, the argument checks the library makes before any HIP call, the checks the Python mirror makes before it calls
 the library, and what it hands to the library."""
 import ctypes as C
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from abi_checks import CallRecorder, NoLibrary, assert_refused, bare_raytracer, compiled_layout, fake_device
 from ray_surface_checks import NAMES
 from shade_rays_checks import INPUTS, OUTPUTS, OUT_DTYPES
 
@@ -22,13 +20,7 @@ def test_the_struct_is_24_bytes_on_both_sides(rrt, tmp_path):
     assert [getattr(rrt.CRayShade, n).offset for n in OUTPUTS] == [0, 8, 16]
     assert rrt.STRUCTS["rrt_ray_shade"] is rrt.CRayShade
     assert set(rrt.RAY_SHADE_INPUTS) == set(INPUTS) and set(INPUTS) < set(NAMES)
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc is not None, "no host C compiler (build() needs one for the oracle)"
-    src = tmp_path / "size.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "rrt.h"\nint main(void) { printf("%zu %zu %zu %zu\\n", sizeof(rrt_ray_shade), '
-                   'offsetof(rrt_ray_shade, colour), offsetof(rrt_ray_shade, local), offsetof(rrt_ray_shade, kr)); return 0; }\n')
-    subprocess.run([cc, "-std=c99", "-I", f"{ROOT}/include", "-o", str(tmp_path / "size"), str(src)], check=True)
-    assert subprocess.run([str(tmp_path / "size")], check=True, capture_output=True, text=True).stdout.split() == ["24", "0", "8", "16"]
+    assert compiled_layout(tmp_path, "rrt_ray_shade", ("colour", "local", "kr")) == (24, [0, 8, 16])
 
 
 def test_both_symbols_are_exported_and_bound(rrt):
@@ -50,60 +42,25 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
     rec = rrt.CRaySurface(point=p + 24, normal=p, material=C.addressof(words), albedo=C.addressof(words) + 4)
     out = rrt.CRayShade(kr=C.addressof(buf), local=C.addressof(buf) + 8)
     host = lambda r, o: L.rrt_shade_rays(None, 1, C.cast(p, rrt._dp), r, 0, o)
-    for what, call in (("rrt_shade_rays", lambda: host(C.byref(rec), C.byref(out))),
-                       ("rrt_shade_rays, NULL structs", lambda: host(None, None)),
-                       ("rrt_shade_rays_device", lambda: L.rrt_shade_rays_device(None, 1, p, C.byref(rec), 0, C.byref(out), None)),
-                       ("rrt_shade_rays_device, n = 0", lambda: L.rrt_shade_rays_device(None, 0, None, C.byref(rec), 7, C.byref(out), None))):
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
+    assert_refused(rrt, L, (("rrt_shade_rays", lambda: host(C.byref(rec), C.byref(out))),
+                            ("rrt_shade_rays, NULL structs", lambda: host(None, None)),
+                            ("rrt_shade_rays_device", lambda: L.rrt_shade_rays_device(None, 1, p, C.byref(rec), 0, C.byref(out), None)),
+                            ("rrt_shade_rays_device, n = 0", lambda: L.rrt_shade_rays_device(None, 0, None, C.byref(rec), 7, C.byref(out), None))))
     assert list(buf) == [0.0] * 4
 
 
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError(f"the library was called ({name}) with arguments the binding has to refuse")
-
-
-class _Recorder:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append((name, args))
-            return 0
-        return entry
-
-
-def _fake_device(t):
-    class FakeDeviceTensor:
-        """What _device_tensor asks of a tensor, with is_cuda forced (as in tests/test_binding_calls.py)."""
-        is_cuda = True
-        def __getattr__(self, k):
-            return getattr(t, k)
-    return FakeDeviceTensor()
-
-
-def _bare_raytracer(rrt):
-    rt = rrt.RayTracer.__new__(rrt.RayTracer)                                # no handle: nothing may get as far as needing one
-    rt._h = None
-    return rt
-
-
 def _records(torch, n):
-    f8 = lambda k: _fake_device(torch.zeros(k, dtype=torch.float64))
-    i4 = lambda k: _fake_device(torch.zeros(k, dtype=torch.int32))
+    f8 = lambda k: fake_device(torch.zeros(k, dtype=torch.float64))
+    i4 = lambda k: fake_device(torch.zeros(k, dtype=torch.int32))
     return dict(point=f8(3 * n), normal=f8(3 * n), material=i4(n), albedo=i4(n), lights=i4(n))
 
 
 def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    monkeypatch.setattr(rrt, "lib", lambda: _NoLibrary())
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
+    rt = bare_raytracer(rrt)
+    monkeypatch.setattr(rrt, "lib", lambda: NoLibrary())
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
     d, rec = f8(12), _records(torch, 4)
     with pytest.raises(AssertionError, match="dirs: not a device tensor"):
         rt.shade_rays_into({"colour": i4(4)}, np.ones((4, 3)), rec, stream=0)
@@ -114,7 +71,7 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
     with pytest.raises(AssertionError, match="not a multiple of 3"):
         rt.shade_rays_into({"colour": i4(4)}, f8(11), rec, stream=0)
     with pytest.raises(AssertionError, match="dirs: want 12 contiguous elements of 8 bytes"):              # a wrong dtype
-        rt.shade_rays_into({"colour": i4(4)}, _fake_device(torch.zeros(12, dtype=torch.float32)), rec, stream=0)
+        rt.shade_rays_into({"colour": i4(4)}, fake_device(torch.zeros(12, dtype=torch.float32)), rec, stream=0)
     with pytest.raises(AssertionError, match="colour: want 4 contiguous elements of 4 bytes"):
         rt.shade_rays_into({"colour": f8(4)}, d, rec, stream=0)
     with pytest.raises(AssertionError, match="local: want 12 contiguous elements of 8 bytes"):             # a wrong length: n where 3 n are wanted
@@ -144,15 +101,15 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
 
 def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    rec = _Recorder()
+    rt = bare_raytracer(rrt)
+    rec = CallRecorder()
     monkeypatch.setattr(rrt, "lib", lambda: rec)
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
     # the device form: all twelve arrays of a surface_rays_into call are passed, the five that are read arrive, the seven others are NULL
     d = f8(12)
     twelve = {n: (f8(12) if n in ("point", "normal", "next_origin", "next_dir") else f8(4) if n in ("t", "u", "v") else
-                  _fake_device(torch.zeros(4, dtype=torch.uint8)) if n == "hit" else i4(4)) for n in NAMES}
+                  fake_device(torch.zeros(4, dtype=torch.uint8)) if n == "hit" else i4(4)) for n in NAMES}
     out = dict(local=f8(12), kr=f8(4))
     rt.shade_rays_into(out, d, twelve, depth=3, stream=0x51)
     (name, args), = rec.calls

@@ -2,28 +2,20 @@
 sides, the exported symbols, the scratch size, the argument checks the library makes before any HIP call and before it looks at the handle, the checks the Python
 mirror makes before it calls the library, and the numpy restatement of the key (tests/sort_checks.py) on values worked out by hand."""
 import ctypes as C
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from abi_checks import PATTERN, CallRecorder, NoLibrary, assert_refused, bare_raytracer, compiled_values, fake_device
+from compact_checks import SCRATCH_SIZES as SIZES
 from sort_checks import DEAD_KEY, KEY_MODES, dead_rays, key_patterns, ray_key, sorted_batch
-from test_compact_abi import SIZES, _NoLibrary, _Recorder, _bare_raytracer, _fake_device
 
-PATTERN = 0xA5A5A5A5
 ROOT20 = (np.full(3, -20.0), np.full(3, 20.0))
 
 
 def test_the_enum_on_both_sides(rrt, tmp_path):
     assert tuple(rrt.SORT_KEY_MODES) == KEY_MODES == ("given", "ray", "record") and rrt.DEAD_KEY == DEAD_KEY
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc is not None, "no host C compiler (build() needs one for the oracle)"
-    src = tmp_path / "enum.c"
-    src.write_text('#include <stdio.h>\n#include "rrt.h"\nint main(void) { printf("%d %d %d\\n", RRT_SORT_KEY_GIVEN, RRT_SORT_KEY_RAY, RRT_SORT_KEY_RECORD); return 0; }\n')
-    subprocess.run([cc, "-std=c99", "-I", f"{ROOT}/include", "-o", str(tmp_path / "enum"), str(src)], check=True)
-    assert subprocess.run([str(tmp_path / "enum")], check=True, capture_output=True, text=True).stdout.split() == ["0", "1", "2"]
+    assert compiled_values(tmp_path, ("RRT_SORT_KEY_GIVEN", "RRT_SORT_KEY_RAY", "RRT_SORT_KEY_RECORD")) == [0, 1, 2]
 
 
 def test_the_symbols_are_exported_and_bound(rrt):
@@ -113,13 +105,7 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
               ("rrt_sort_rays_device, scratch_bytes 0", lambda: dev(fake, n, 0, keys, None, None, I, K, Cn, sb=0)),
               ("rrt_sort_rays_device, a NULL scratch", lambda: dev(fake, n, 2, keys, ray, dst, I, K, Cn, scratch=None))]
     assert len(calls) == 2 * 18 + 3
-    for what, call in calls:
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
-        for name, a in outs.items():
-            assert (a == PATTERN).all(), f"{what}: {name} of a refused call was written"
+    assert_refused(rrt, L, calls, outs)
     # n == 0 with valid arguments: RRT_OK, nothing enqueued (the handle is not a raytracer); the host form writes *count = 0 and nothing else
     assert dev(fake, 0, 1, None, ray, dst, I, K, Cn, scratch=None, sb=0) == rrt.OK and (Cn == PATTERN).all()
     assert host(fake, 0, 0, None, None, None, I, K, Cn) == rrt.OK
@@ -133,12 +119,12 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
 
 def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    monkeypatch.setattr(rrt, "lib", lambda: _NoLibrary())
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    f4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float32))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
-    u1 = lambda n: _fake_device(torch.zeros(n, dtype=torch.uint8))
+    rt = bare_raytracer(rrt)
+    monkeypatch.setattr(rrt, "lib", lambda: NoLibrary())
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    f4 = lambda n: fake_device(torch.zeros(n, dtype=torch.float32))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
+    u1 = lambda n: fake_device(torch.zeros(n, dtype=torch.uint8))
     src = dict(origins=f8(12), dirs=f8(12), point=f8(12), normal=f8(12), material=i4(4))
 
     def into(out, src=src, key="ray", index_t=None, keys_out_t=None, count_t=None, scratch_t=None, keys_t=None):
@@ -198,12 +184,12 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
 def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
     from compact_checks import NAMES
-    rt = _bare_raytracer(rrt)
-    rec = _Recorder()
+    rt = bare_raytracer(rrt)
+    rec = CallRecorder()
     monkeypatch.setattr(rrt, "lib", lambda: rec)
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
-    u1 = lambda n: _fake_device(torch.zeros(n, dtype=torch.uint8))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
+    u1 = lambda n: fake_device(torch.zeros(n, dtype=torch.uint8))
 
     def pointers(s):
         return {n: (getattr(s, n) if n in NAMES[:4] else getattr(s.rec, n)) for n in NAMES}
@@ -220,7 +206,7 @@ def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     # GIVEN with index alone: both structs NULL
     rec.calls.clear()
     keys = i4(5)
-    rt.sort_rays_into({}, {}, "given", i4(5), None, None, _fake_device(torch.zeros(512, dtype=torch.int64)), keys_t=keys, stream=7)
+    rt.sort_rays_into({}, {}, "given", i4(5), None, None, fake_device(torch.zeros(512, dtype=torch.int64)), keys_t=keys, stream=7)
     (name, args), = rec.calls
     assert args[1:3] == (5, 0) and args[3].value == keys.data_ptr() and args[4] is None and args[5] is None and args[7] is None and args[8] is None and args[10] == 4096
     # the host form

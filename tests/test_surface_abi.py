@@ -2,6 +2,8 @@
 argument checks that are made before any HIP call."""
 import ctypes as C
 
+from abi_checks import assert_refused
+
 
 def test_surface_struct_has_the_header_size(rrt):
     assert C.sizeof(rrt.CSurface) == 32
@@ -16,12 +18,8 @@ def test_surface_calls_refuse_a_null_raytracer(rrt):
     planes = rrt.CSurface(point=C.addressof(buf))
     vis = rrt.CVisibility(t=C.addressof(tbuf))
     region = rrt.CRegion(0, 0, 1, 1)
-    for what, call in (("rrt_render_surface", lambda: L.rrt_render_surface(None, 64, 48, C.byref(region), None, C.byref(planes))),
-                       ("rrt_render_surface, whole frame, with visibility planes", lambda: L.rrt_render_surface(None, 64, 48, None, C.byref(vis), C.byref(planes))),
-                       ("rrt_render_surface_device", lambda: L.rrt_render_surface_device(None, 64, 48, C.byref(region), None, C.byref(planes), None)),
-                       ("rrt_render_surface_device, with visibility planes", lambda: L.rrt_render_surface_device(None, 64, 48, C.byref(region), C.byref(vis), C.byref(planes), None))):
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
+    assert_refused(rrt, L, (("rrt_render_surface", lambda: L.rrt_render_surface(None, 64, 48, C.byref(region), None, C.byref(planes))),
+                            ("rrt_render_surface, whole frame, with visibility planes", lambda: L.rrt_render_surface(None, 64, 48, None, C.byref(vis), C.byref(planes))),
+                            ("rrt_render_surface_device", lambda: L.rrt_render_surface_device(None, 64, 48, C.byref(region), None, C.byref(planes), None)),
+                            ("rrt_render_surface_device, with visibility planes", lambda: L.rrt_render_surface_device(None, 64, 48, C.byref(region), C.byref(vis), C.byref(planes), None))))
     assert list(buf) == [0.0] * 12 and list(tbuf) == [0.0] * 4

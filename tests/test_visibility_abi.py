@@ -2,6 +2,8 @@
 that are made before any HIP call."""
 import ctypes as C
 
+from abi_checks import assert_refused
+
 
 def test_visibility_structs_have_the_header_sizes(rrt):
     assert C.sizeof(rrt.CRegion) == 16 and C.sizeof(rrt.CVisibility) == 48 and C.sizeof(rrt.CPickResult) == 40
@@ -17,12 +19,8 @@ def test_visibility_calls_refuse_a_null_raytracer(rrt):
     planes = rrt.CVisibility(t=C.addressof(buf))
     region = rrt.CRegion(0, 0, 1, 1)
     out = rrt.CPickResult()
-    for what, call in (("rrt_render_visibility", lambda: L.rrt_render_visibility(None, 64, 48, C.byref(region), C.byref(planes))),
-                       ("rrt_render_visibility, whole frame", lambda: L.rrt_render_visibility(None, 64, 48, None, C.byref(planes))),
-                       ("rrt_render_visibility_device", lambda: L.rrt_render_visibility_device(None, 64, 48, C.byref(region), C.byref(planes), None)),
-                       ("rrt_pick", lambda: L.rrt_pick(None, 64, 48, 0, 0, C.byref(out)))):
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
+    assert_refused(rrt, L, (("rrt_render_visibility", lambda: L.rrt_render_visibility(None, 64, 48, C.byref(region), C.byref(planes))),
+                            ("rrt_render_visibility, whole frame", lambda: L.rrt_render_visibility(None, 64, 48, None, C.byref(planes))),
+                            ("rrt_render_visibility_device", lambda: L.rrt_render_visibility_device(None, 64, 48, C.byref(region), C.byref(planes), None)),
+                            ("rrt_pick", lambda: L.rrt_pick(None, 64, 48, 0, 0, C.byref(out)))))
     assert list(buf) == [0.0] * 4

@@ -3,27 +3,17 @@ rrt_mix_pixels, rrt_wavefront_work_bytes, rrt_render_wavefront and their _device
 the entry count against the numpy restatement (tests/wavefront_checks.py), the argument checks the library makes before any HIP call and before it looks at the
 handle, the work size for bad arguments, and what the Python mirror checks and hands to the library."""
 import ctypes as C
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from test_compact_abi import _NoLibrary, _Recorder, _bare_raytracer, _fake_device
+from abi_checks import PATTERN, CallRecorder, NoLibrary, assert_refused, bare_raytracer, compiled_values, fake_device
 from wavefront_checks import ORDERS, ROWS, TILES, alive_entries, entries, expected_pixels, mix_level, ray_count, tile_rectangle
-
-PATTERN = 0xA5A5A5A5
 
 
 def test_the_enum_on_both_sides(rrt, tmp_path):
     assert (rrt.ORDER_ROWS, rrt.ORDER_TILES) == (ROWS, TILES) == (0, 1) and rrt.FRAME_RAY_ARRAYS == ("origins", "dirs", "max_t")
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc is not None, "no host C compiler (build() needs one for the oracle)"
-    src = tmp_path / "enum.c"
-    src.write_text('#include <stdio.h>\n#include "rrt.h"\nint main(void) { printf("%d %d %zu\\n", RRT_ORDER_ROWS, RRT_ORDER_TILES, sizeof(rrt_region)); return 0; }\n')
-    subprocess.run([cc, "-std=c99", "-I", f"{ROOT}/include", "-o", str(tmp_path / "enum"), str(src)], check=True)
-    assert subprocess.run([str(tmp_path / "enum")], check=True, capture_output=True, text=True).stdout.split() == ["0", "1", "16"]
+    assert compiled_values(tmp_path, ("RRT_ORDER_ROWS", "RRT_ORDER_TILES", "sizeof(rrt_region)")) == [0, 1, 16]
     assert C.sizeof(rrt.CRegion) == 16
 
 
@@ -142,13 +132,7 @@ def test_the_library_refuses_before_any_gpu_work(rrt):
               ("rrt_mix_rays_device, NULL colour", lambda: L.rrt_mix_rays_device(fake, n, None, at(local), None, None, None, None))]
     assert len(calls) == 6 * 11 + 18
     assert 0 < L.rrt_wavefront_work_bytes(fake, 2, 2, None, 0) <= work_bytes and WORK.ctypes.data % 8 == 0
-    for what, call in calls:
-        assert L.rrt_host_buffer_register(None, 0) == rrt.ERR_INVALID_ARG     # (another failure's text first, so that a detail left unchanged would show)
-        other = L.rrt_last_error_detail()
-        assert call() == rrt.ERR_INVALID_ARG, what
-        assert L.rrt_last_error_detail() not in (b"", None, other), (what, L.rrt_last_error_detail())
-        for name, a in outs.items():
-            assert (a == PATTERN).all(), f"{what}: {name} of a refused call was written"
+    assert_refused(rrt, L, calls, outs)
     # the count and the work size of the same arguments
     for what, (rt, fw, fh, r, o) in bad_frames:
         assert L.rrt_wavefront_work_bytes(rt, fw, fh, ref(r), o) == 0, f"rrt_wavefront_work_bytes, {what}"
@@ -205,10 +189,10 @@ def test_the_restatements_on_values_worked_out_by_hand():
 
 def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
-    u1 = lambda n: _fake_device(torch.zeros(n, dtype=torch.uint8))
+    rt = bare_raytracer(rrt)
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
+    u1 = lambda n: fake_device(torch.zeros(n, dtype=torch.uint8))
     n = rrt.frame_ray_count(8, 6, None, ROWS)                      # (the one library call the _into forms make first: no handle, no GPU)
     assert n == 192
     for call in (lambda: rt.frame_rays_into({}, 8, 6, order=2), lambda: rt.mix_pixels_into(i4(48), i4(n), 8, 6, order="tiles"), lambda: rt.render_wavefront(8, 6, order=-1),
@@ -217,7 +201,7 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
             call()
     count = rrt.lib().rrt_frame_ray_count
 
-    class _CountOnly(_NoLibrary):
+    class _CountOnly(NoLibrary):
         rrt_frame_ray_count = staticmethod(count)
     monkeypatch.setattr(rrt, "lib", lambda: _CountOnly())
     with pytest.raises(ValueError, match="unknown array 'rot'"):
@@ -258,15 +242,15 @@ def test_the_binding_refuses_before_it_calls_the_library(rrt, monkeypatch):
 
 def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     torch = pytest.importorskip("torch")
-    rt = _bare_raytracer(rrt)
+    rt = bare_raytracer(rrt)
     count = rrt.lib().rrt_frame_ray_count
 
-    class _Rec(_Recorder):
+    class _Rec(CallRecorder):
         rrt_frame_ray_count = staticmethod(count)
     rec = _Rec()
     monkeypatch.setattr(rrt, "lib", lambda: rec)
-    f8 = lambda n: _fake_device(torch.zeros(n, dtype=torch.float64))
-    i4 = lambda n: _fake_device(torch.zeros(n, dtype=torch.int32))
+    f8 = lambda n: fake_device(torch.zeros(n, dtype=torch.float64))
+    i4 = lambda n: fake_device(torch.zeros(n, dtype=torch.int32))
     region_of = lambda arg: None if arg is None else tuple(getattr(arg._obj, k) for k in ("x0", "y0", "w", "h"))
     val = lambda p: None if p is None else p.value
     # frame rays, device form: a region in tiles order, two of the three arrays
@@ -310,7 +294,7 @@ def test_what_the_binding_hands_to_the_library(rrt, monkeypatch):
     assert name_h == "rrt_mix_pixels" and b[3] is None and b[4] == 0 and out.shape == (6, 8) and C.cast(b[6], C.c_void_p).value == out.ctypes.data
     # the frame by generations
     rec.calls.clear()
-    work = _fake_device(torch.zeros(512, dtype=torch.int64))
+    work = fake_device(torch.zeros(512, dtype=torch.int64))
     rt.render_wavefront_into(fb, work, 8, 6, region=(3, 1, 2, 4), order=TILES, stream=11)
     out = rt.render_wavefront(8, 6, region=(1, 1, 4, 3))
     rt.wavefront_work_bytes(8, 6, region=(1, 1, 4, 3), order=TILES)

@@ -1,15 +1,15 @@
 """Helpers of the tests of the two ends of the per-ray pipeline and of the frame by ray generations (include/rrt.h: rrt_frame_rays, rrt_mix_rays, rrt_mix_pixels,
 rrt_render_wavefront): the numpy restatement of both entry orders and of a frame's ray batch -- built on gpu_checks.pose_dirs / traced_rows and
-surface_checks.traced_cols, the restatements the other tests use -- one level of the unwind by shade_rays_checks.mixed, and the pixels by gpu_checks.mix4.
+surface_checks.traced_cols, the restatements the other tests use -- one level of the unwind by shade_rays_checks.mixed with its inputs (mix_case), and the pixels by gpu_checks.mix4.
 
 Plain module, not a test module: pytest does not rewrite its asserts, so every assert here states both values in its message.  It holds no fixtures.
 """
 import numpy as np
 import pytest
 
+from bitwise import assert_same_bits
 from gpu_checks import mix4, pose_dirs, traced_rows
 from ray_surface_checks import WHITE, clamp_u8, pack
-from shade_checks import assert_same_frame
 from shade_rays_checks import mixed
 from surface_checks import traced_cols, traced_pixels_in
 
@@ -135,7 +135,7 @@ def assert_wavefront_is_render(rrt, torch, rt, w, h, region, what, forced=None):
     x0, y0, rw, rh = region
     for order in ORDERS:
         got = rt.render_wavefront(w, h, order=order)
-        assert_same_frame(got, want, f"{what}, order {order}: render_wavefront vs render")
+        assert_same_bits(got, want, f"{what}, order {order}: render_wavefront vs render")
         s = rt.last_stats()
         assert (s["width"], s["height"], s["rays_primary"], s["filter_variant"]) == (w, h, 4 * traced_pixels_in((0, 0, w, h), w, h), kept) and s["kernel_ms"] > 0, s
         need = rt.wavefront_work_bytes(w, h, region, order)
@@ -148,11 +148,31 @@ def assert_wavefront_is_render(rrt, torch, rt, w, h, region, what, forced=None):
             assert work.data_ptr() % 256 == 0, f"{what}: the work memory lies at {work.data_ptr():#x}"
             rt.render_wavefront_into(fb, work, w, h, region=region, order=order, stream=stream.cuda_stream)
         stream.synchronize()
-        assert_same_frame(host(fb, np.uint32, (rh, rw)), want[y0:y0 + rh, x0:x0 + rw], f"{what}, order {order}, region {region}: render_wavefront_into vs render")
+        assert_same_bits(host(fb, np.uint32, (rh, rw)), want[y0:y0 + rh, x0:x0 + rw], f"{what}, order {order}, region {region}: render_wavefront_into vs render")
         s = rt.last_stats()
         assert (s["width"], s["height"], s["rays_primary"], s["filter_variant"]) == (w, h, 4 * traced_pixels_in(region, w, h), kept) and s["kernel_ms"] > 0, s
         with pytest.raises(rrt.RrtError):                          # one byte less is refused, and the framebuffer stays
             rt.render_wavefront_into(fb, work[:need - 1], w, h, region=region, order=order, stream=stream.cuda_stream)
-    assert_same_frame(rt.render(w, h), want, f"{what}: render after render_wavefront")
+    assert_same_bits(rt.render(w, h), want, f"{what}: render after render_wavefront")
     assert rt.last_stats()["filter_variant"] == kept, f"{what}: render runs another variant after render_wavefront"
     return want
+
+
+# ------------------------------------------------------------------ the inputs of one level of the unwind
+def mix_case(n, n_mats):
+    """A third misses, a third with kr = 0, a third with kr in (0, 1]; local with negatives, values above 255, exact integers, NaN and +-inf; junk in reflected's top byte"""
+    rng = np.random.default_rng(n)
+    local = rng.uniform(-40.0, 320.0, (n, 3))
+    whole = rng.random((n, 3)) < 0.25
+    local[whole] = np.round(local[whole])
+    for j, v in enumerate((np.nan, np.inf, -np.inf, 255.0, 256.0, 0.0, -0.0, 254.99999999999997)):
+        local[(3 * j + 1) % n, j % 3] = v
+    kind = np.arange(n) % 3
+    material = np.where(kind == 0, 0xFFFFFFFF, rng.integers(0, n_mats, n)).astype(np.uint32)
+    material[np.flatnonzero(kind == 0)[::2]] = n_mats               # (misses by the first index that is no material, and by 0xFFFFFFFF)
+    kr = np.where(kind == 2, 1.0 - rng.random(n), 0.0)
+    kr[(kind == 2) & (np.arange(n) % 5 == 0)] = 1.0
+    kr[(kind == 1) & (np.arange(n) % 7 == 0)] = -0.5
+    kr[(kind == 1) & (np.arange(n) % 11 == 0)] = np.nan
+    reflected = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    return local, kr, reflected, material
