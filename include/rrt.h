@@ -84,6 +84,13 @@ typedef struct { const uint8_t *rgb; uint32_t width, height; } rrt_texture;
  * from an fp32 upper bound (csrc/specular_skip.hpp) -- is not evaluated: no pow, no sqrt, no divide.  Same results; this flag evaluates every term
  * (tests, A/B timing). */
 #define RRT_FLAG_NO_SPECULAR_SKIP (1u << 6)    /* 64; a developer switch like the one above */
+/* Coverage pass: in front of every WHOLE frame of one GPU (rrt_render_device, rrt_render) a small kernel projects the padded box of
+ * every triangle onto the frame and marks the 4x4-pixel waves it can reach; a wave no box reaches stores WHITE and walks nothing.  The pass runs again in
+ * every frame, on the frame's stream and inside its timing (rrt_stats.kernel_ms): nothing is kept between frames, so the setters need no care.  Same
+ * results; it is off by itself wherever the index's exactness guarantee is not in force for every primary ray (rrt_raytracer_get_coverage_info says
+ * why), and for a rank's tiles and progressive frames.  This flag turns it off (tests, A/B timing). */
+#define RRT_FLAG_NO_COVERAGE (1u << 7)         /* 128; a developer switch like the two above */
+#define RRT_FLAG_COVERAGE_ALWAYS (1u << 8)     /* 256; a developer switch: the pass also runs where it is judged not to pay (RRT_COVERAGE_OFF_SMALL_FRAME); tests and timing at small sizes */
 
 /* Render constants that the reference hard-codes; NULL => these defaults. */
 typedef struct {
@@ -913,6 +920,21 @@ int rrt_raytracer_get_buffer(const rrt_raytracer *rt, uint32_t which, void *out,
  * cover.  Both 0 when the shortcut cannot apply (RRT_FLAG_NO_CULL, a triangle poking out of the root box, 2^24 nodes or more); the flag that turns
  * the shortcut off does not change them.  Either pointer may be NULL. */
 int rrt_raytracer_get_chain_info(const rrt_raytracer *rt, uint32_t *n_chains, uint32_t *n_chain_nodes);
+
+/* The coverage pass of this raytracer's LAST frame launch (see RRT_FLAG_NO_COVERAGE).  state: RRT_COVERAGE_ON when that frame ran with a mask, else why not.
+ * n_waves: the 4x4-pixel waves of that frame (0 without a mask).  n_proved_empty: how many of them the mask proved empty -- asked for with a non-NULL
+ * pointer only, and then BLOCKING: it waits for that frame and reads its mask back (the launch path never does).  Any pointer may be NULL. */
+#define RRT_COVERAGE_ON 0u
+#define RRT_COVERAGE_OFF_NO_FRAME 1u     /* no frame has been launched yet */
+#define RRT_COVERAGE_OFF_FLAG 2u         /* RRT_FLAG_NO_COVERAGE */
+#define RRT_COVERAGE_OFF_NO_CULL 3u      /* RRT_FLAG_NO_CULL, or an index without padding: there are no boxes to trust */
+#define RRT_COVERAGE_OFF_SUSPECTS 4u     /* rrt_stats.origin_plane_triangles != 0: some primary rays run unfiltered */
+#define RRT_COVERAGE_OFF_EYE_RANGE 5u    /* the eye, or a primary direction of the frame, lies outside the range of the index filters */
+#define RRT_COVERAGE_OFF_CAMERA 6u       /* a view basis that is singular, ill-conditioned (condition above 256) or not finite, or a viewport depth <= 0 */
+#define RRT_COVERAGE_OFF_POOL 7u         /* more than eight frames of this raytracer in flight on different streams */
+#define RRT_COVERAGE_OFF_NOT_WHOLE 8u    /* a rank's tiles (rrt_render_tiles_device) or a progressive frame */
+#define RRT_COVERAGE_OFF_SMALL_FRAME 9u  /* the pass would cost more than it saves: fewer than 49 152 waves (1024 x 768 pixels), or more than four triangle slots per wave (RRT_FLAG_COVERAGE_ALWAYS lifts both) */
+int rrt_raytracer_get_coverage_info(const rrt_raytracer *rt, uint32_t *state, uint64_t *n_waves, uint64_t *n_proved_empty);
 
 int rrt_last_stats(const rrt_raytracer *rt, rrt_stats *out);
 /* Time of the set-up stages that run once per scene (the reference does all of them inside parse_obj_file_lines, utils.rs:139-213, before its one

@@ -59,6 +59,16 @@ struct rrt_raytracer {
     rrt::Box root{};
     uint64_t built_bytes = 0;
     rrt::BuildMemory update_mem;
+    // Coverage pass of whole single-GPU frames (frames.cpp: launch_whole_frame; coverage.hip).  A buffer is a place for ONE frame's mask: cleared, filled and read by
+    // that frame's own launches; nothing in it outlives the frame, and nothing here describes a scene or a camera.  `done` is recorded behind the render_kernel that
+    // read the mask, on `stream`: a frame on another stream takes the buffer only once that event has completed.  Several frames of one handle may be in flight on
+    // different streams, hence a small pool; a frame that finds no free buffer renders without a mask.
+    struct CoverBuf { rrt::KeptBuf mask; rrt::HipOwned<hipEvent_t, hipEventDestroy> done; void* stream = nullptr; bool used = false; };
+    static constexpr int kCoverBufs = 8;
+    CoverBuf cover[kCoverBufs];
+    int cover_last = -1;             // the buffer of the last whole frame, or -1: it ran without a mask ...
+    uint32_t cover_off = RRT_COVERAGE_OFF_NO_FRAME;   // ... for this reason (RRT_COVERAGE_OFF_*; RRT_COVERAGE_ON with a buffer)
+    uint32_t cover_tiles_x = 0, cover_tiles_y = 0;   // the tiles of that frame (rrt_raytracer_get_coverage_info counts its waves on request)
 };
 
 namespace rrt {

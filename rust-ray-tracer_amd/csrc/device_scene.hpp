@@ -304,7 +304,14 @@ int launch_mix_pixels(const MixPixelsParams& q, void* stream);
 
 // kernel launches (render.hip).  All return hipError_t cast to int; stream is a hipStream_t.
 // walk: 0 = node-coherent walk with the lane filter, 1 = node-coherent walk with the bundle filter, 2 = ray walk (render.hip)
-int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk);
+// d_cover: null, or the coverage mask of this WHOLE single-GPU frame (coverage.hip: launch_coverage on the same stream): a wave whose bit is clear stores WHITE
+// and walks nothing.  Not an argument inside FrameParams or DevScene: those are arguments of the other kernels too.
+int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, const uint32_t* d_cover = nullptr);
+// The coverage pass (coverage.hip; the rule: coverage_rule.hpp).  The mask of a frame of tiles_x x tiles_y tiles is coverage_mask_words words, one bit per wave
+// in render_kernel's block order, and one more word behind them.  launch_coverage clears it and marks the waves that boxes[0, n_boxes) can reach, on `stream`.
+struct CoverageFrame;
+uint32_t coverage_mask_words(uint32_t tiles_x, uint32_t tiles_y);
+int launch_coverage(const CoverageFrame& F, const DevClusterBox* boxes, uint32_t n_boxes, uint32_t* mask, void* stream);
 // A region of a frame (render.hip: launch_region), for Params = VisParams (visibility_kernel: the visibility planes), SurfaceParams (surface_kernel: the surface
 // planes and any visibility planes), ShadeParams (shade_kernel: the pixels from kept planes) and AmbientParams (ambient_kernel: occlusion masks and grey pixels from
 // kept planes).  Defined and instantiated for these four in render.hip.

@@ -3,9 +3,12 @@
 // It also holds the part of the launch seam that is no template (launches.hpp): frame_params, elapsed_ms, record, first_frame_variant, own_stream.
 // Regions of a frame are in regions.cpp, per-ray queries in ray_queries.cpp, ray batches and the frame by ray generations in ray_batches.cpp.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
+#include "coverage_rule.hpp"
 #include "launches.hpp"
 
 namespace rrt {
@@ -71,6 +74,68 @@ namespace {
 
 using namespace rrt;
 
+// ---- the coverage pass (coverage.hip, coverage_rule.hpp).
+// Whether the frame f may run with a coverage mask: RRT_COVERAGE_ON and F filled, or the reason why not.  The mask rests on the guarantee the index rests on -- a
+// pair the reference accepts lies inside the triangle's padded box -- so it is off wherever that guarantee is not in force for every primary ray.
+// It is also off where it cannot pay (RRT_FLAG_COVERAGE_ALWAYS lifts these two bounds: tests and timing at small sizes).  The pass costs about 20 us whatever the frame
+// (a clear, a kernel of one lane per box, two more dispatches) and more with the number of boxes; what it saves grows with the waves it proves empty.
+//  * Waves.  Measured on the teapot (profiles/coverage_ab.txt): 640 x 480 = 19 200 waves lost 7.5 us, 1920 x 1080 = 129 600 waves gains 24 us; the line through the
+//    two crosses zero at about 45 000 waves, and nothing in between was measured: on from 49 152 waves (1024 x 768).
+//  * Boxes per wave.  The fullest case measured is the 1 M soup at 3840 x 2160, two list slots per wave: no difference beyond the runs' range.  Beyond four slots per
+//    wave nothing was measured and a frame that full has little to prove empty: off.
+constexpr uint64_t kCoverMinWaves = 49152, kCoverMaxSlotsPerWave = 4;
+uint32_t coverage_state(const rrt_raytracer* rt, const FrameParams& f, CoverageFrame& F) {
+    const DevScene& S = rt->scene;
+    if (rt->opt.flags & RRT_FLAG_NO_COVERAGE) return RRT_COVERAGE_OFF_FLAG;
+    const uint64_t waves = 4ull * f.tiles_x * f.tiles_y;
+    if (!(rt->opt.flags & RRT_FLAG_COVERAGE_ALWAYS) && (waves < kCoverMinWaves || rt->built.n_list_slots > kCoverMaxSlotsPerWave * waves)) return RRT_COVERAGE_OFF_SMALL_FRAME;
+    if (!S.cull_enabled || !(rt->built.pad > 0)) return RRT_COVERAGE_OFF_NO_CULL;
+    if (S.n_suspects != 0) return RRT_COVERAGE_OFF_SUSPECTS;
+    // The filters are also off for a ray with a component of its origin or direction at or beyond cull_limit (render.hip: make_ray32).  The mask's argument is
+    // geometric and does not need them to run, but "off wherever the filters would be off" is the rule, so the largest component a primary direction of this frame
+    // can have is bounded the same way: |right| a + |up| b + |forward| c over the frame's extent.
+    const double a = ((double)(f.width / 2u) + 1.0) * std::fabs(f.x_scale), b = ((double)(f.height - f.height / 2u) + 1.0) * std::fabs(f.y_scale), c = std::fabs(f.z_value);
+    for (int k = 0; k < 3; k++) {
+        if (!(std::fabs(S.origin[k]) < (double)S.cull_limit)) return RRT_COVERAGE_OFF_EYE_RANGE;
+        if (!(std::fabs(f.right[k]) * a + std::fabs(f.up[k]) * b + std::fabs(f.forward[k]) * c < (double)S.cull_limit)) return RRT_COVERAGE_OFF_EYE_RANGE;
+    }
+    if (!coverage_frame(F, f.width, f.height, f.x_scale, f.y_scale, f.z_value, f.right, f.up, f.forward, S.origin)) return RRT_COVERAGE_OFF_CAMERA;
+    return RRT_COVERAGE_ON;
+}
+// A buffer for the mask of a frame on `stream`: the one this stream used last (stream order protects it), else one whose last frame has completed, else one never
+// used; -1 when all kCoverBufs are busy on other streams.  Allocates only when a buffer is new or a larger frame comes.
+int take_cover_buffer(rrt_raytracer* rt, size_t bytes, void* stream) {
+    int pick = -1;
+    for (int i = 0; i < rrt_raytracer::kCoverBufs && pick < 0; i++) if (rt->cover[i].used && rt->cover[i].stream == stream) pick = i;
+    for (int i = 0; i < rrt_raytracer::kCoverBufs && pick < 0; i++) {
+        if (!rt->cover[i].used) pick = i;
+        else if (hipEventQuery(rt->cover[i].done.h) == hipSuccess) pick = i;
+        else (void)hipGetLastError();                                      // (hipErrorNotReady: its frame is still in flight)
+    }
+    if (pick < 0) return -1;
+    rrt_raytracer::CoverBuf& b = rt->cover[pick];
+    if (!b.done.h) HIP_TRY(hipEventCreateWithFlags(&b.done.h, hipEventDisableTiming));
+    b.mask.at_least(bytes);
+    b.stream = stream; b.used = true;
+    return pick;
+}
+// One WHOLE frame of one GPU (f.world == 1, every tile, every row) on `stream`: clear, coverage kernel and render_kernel in stream order, or render_kernel alone where
+// the mask is off.  Every frame pays the pass again: nothing is kept from the frame before.  Called inside timed_launch, so kernel_ms includes the pass.
+int launch_whole_frame(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void* stream, int variant) {
+    CoverageFrame F;
+    rt->cover_last = -1;
+    rt->cover_off = coverage_state(rt, f, F);
+    if (rt->cover_off != RRT_COVERAGE_ON) return launch_render(rt->scene, f, d_out, stream, variant);
+    const int i = take_cover_buffer(rt, sizeof(uint32_t) * ((size_t)coverage_mask_words(F.tiles_x, F.tiles_y) + 1), stream);
+    if (i < 0) { rt->cover_off = RRT_COVERAGE_OFF_POOL; return launch_render(rt->scene, f, d_out, stream, variant); }
+    uint32_t* const mask = static_cast<uint32_t*>(rt->cover[i].mask.mem.h);
+    HIP_TRY((hipError_t)launch_coverage(F, rt->scene.tboxes, rt->built.n_list_slots, mask, stream));
+    HIP_TRY((hipError_t)launch_render(rt->scene, f, d_out, stream, variant, mask));
+    HIP_TRY(hipEventRecord(rt->cover[i].done.h, (hipStream_t)stream));
+    rt->cover_last = i; rt->cover_tiles_x = F.tiles_x; rt->cover_tiles_y = F.tiles_y;
+    return 0;
+}
+
 void tune_variant(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void* stream) {
     if (rt->variant_forced) return;
     if (!(rt->tuned_w == f.width && rt->tuned_h == f.height && rt->tuned_world == f.world)) {
@@ -83,7 +148,7 @@ void tune_variant(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void
     rt->size_measured = true;
     if (f.world == 1) {
         rt->walk = fastest_variant([&](int variant) {
-            timed_launch(rt, stream, [&] { return launch_render(rt->scene, f, d_out, stream, variant); });
+            timed_launch(rt, stream, [&] { return launch_whole_frame(rt, f, d_out, stream, variant); });   // (as the frames will run: with the coverage pass)
             return elapsed_ms(rt);
         });
         return;
@@ -110,7 +175,11 @@ void launch_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t r
     DeviceGuard guard(rt->device);
     const FrameParams f = frame_params(rt, width, height, rank, world, tiled);
     tune_variant(rt, f, static_cast<uint32_t*>(d_out), stream);
-    timed_launch(rt, stream, [&] { return launch_render(rt->scene, f, static_cast<uint32_t*>(d_out), stream, rt->walk); });
+    timed_launch(rt, stream, [&] {
+        if (world == 1) return launch_whole_frame(rt, f, static_cast<uint32_t*>(d_out), stream, rt->walk);
+        rt->cover_last = -1; rt->cover_off = RRT_COVERAGE_OFF_NOT_WHOLE;   // a rank's tiles: no mask
+        return launch_render(rt->scene, f, static_cast<uint32_t*>(d_out), stream, rt->walk);
+    });
     record(rt, width, height, world == 1 ? 4 * traced_pixels(width, height) : 0, rt->walk);
 }
 
@@ -199,6 +268,7 @@ int rrt_render_progressive(rrt_raytracer* rt, uint32_t width, uint32_t height, u
         HIP_TRY(hipMemsetAsync(d_fb, 0, bytes, nullptr));                  // Canvas::new, engine.rs:135
         std::memset(out_fb, 0, bytes);
         const int64_t H = height, half = H / 2;
+        rt->cover_last = -1; rt->cover_off = RRT_COVERAGE_OFF_NOT_WHOLE;   // bands of a frame: no mask
         timed_launch(rt, nullptr, [&] {                                   // ONE pair of events around all the bands
             for (int64_t cs = -half; cs < half; cs += chunk_rows) {        // engine.rs:198-199
                 const int64_t ce = std::min<int64_t>(cs + chunk_rows, half);
@@ -242,6 +312,31 @@ int rrt_prof_band_counters(rrt_raytracer* rt, unsigned long long* out4) {
     });
 }
 #endif
+
+int rrt_raytracer_get_coverage_info(const rrt_raytracer* rt_c, uint32_t* state, uint64_t* n_waves, uint64_t* n_proved_empty) {
+    return guarded([&]() -> int {
+        rrt_raytracer* rt = const_cast<rrt_raytracer*>(rt_c);
+        if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+        const bool on = rt->cover_last >= 0;
+        const uint64_t waves = on ? 4ull * rt->cover_tiles_x * rt->cover_tiles_y : 0ull;
+        if (state) *state = on ? RRT_COVERAGE_ON : rt->cover_off;
+        if (n_waves) *n_waves = waves;
+        if (!n_proved_empty) return RRT_OK;
+        *n_proved_empty = 0;
+        if (!on) return RRT_OK;
+        // on request only: wait for the frame, bring its mask down and count the clear bits (the bits of a last word beyond the frame's waves are never set)
+        DeviceGuard guard(rt->device);
+        const rrt_raytracer::CoverBuf& b = rt->cover[rt->cover_last];
+        std::vector<uint32_t> h(coverage_mask_words(rt->cover_tiles_x, rt->cover_tiles_y));
+        HIP_TRY(hipEventSynchronize(b.done.h));
+        HIP_TRY(hipMemcpy(h.data(), b.mask.mem.h, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost));
+        if (waves % 32u) h.back() &= (1u << (waves % 32u)) - 1u;           // (a box that reaches the whole frame sets whole words)
+        uint64_t set = 0;
+        for (uint32_t w : h) set += (uint64_t)__builtin_popcount(w);
+        *n_proved_empty = waves - set;
+        return RRT_OK;
+    });
+}
 
 int rrt_last_stats(const rrt_raytracer* rt_c, rrt_stats* out) {
     return guarded([&]() -> int {

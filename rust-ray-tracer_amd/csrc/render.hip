@@ -1803,7 +1803,9 @@ __device__ __forceinline__ uint32_t shade_unwind(uint32_t term, uint32_t lvl, co
 constexpr int kWavesPerSimd = 4;
 #if RRT_TU_FRAME || RRT_TU_LANE
 template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScene S, const FrameParams F, uint32_t* __restrict__ out) {
+// cover: null, or the coverage mask of this whole frame (coverage.hip), one bit per block in the order of `blk` below.  A wave whose bit is clear has no
+// sub-sample whose ray meets any padded triangle box (coverage_rule.hpp): every traced pixel of it is WHITE, and it leaves before it forms a ray.
+__global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScene S, const FrameParams F, uint32_t* __restrict__ out, const uint32_t* __restrict__ cover) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const uint32_t lane = threadIdx.x;
     const Stack stk{lds + kParkBytes, lane};
@@ -1828,6 +1830,17 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
     // for odd W, the last column.  The scene row y = -H/2 maps to new_y = H and is rejected (engine.rs:152-155), so it is not traced.
     const bool in_fb = tile_ok && (int32_t)px < W && py >= F.row_begin && py < F.row_end;    // row_end <= height
     const bool traced = in_fb && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;
+#if !(defined(RRT_PROFILE) && defined(RRT_PROF_WAVETIME))
+    // (passing `traced && covered` to trace_colour instead, which then returns its initial WHITE at once, was measured and is slower: profiles/coverage_ab.txt)
+    if (cover && !((cover[blk >> 5] >> (blk & 31u)) & 1u)) {                         // one scalar load: blk is wave-uniform
+        if (sub == 0) {
+            const uint32_t white = traced ? 0x00FFFFFFu : 0u;                         // Color::mix of four WHITE sub-samples; 0 as below where nothing is traced
+            if (F.tiled_output) out[(size_t)local_tile * 64 + ((py & 7u) * 8 + (px & 7u))] = in_fb ? white : 0u;
+            else if (in_fb) out[(size_t)py * F.width + px] = white;
+        }
+        return;
+    }
+#endif
     const int32_t x = (int32_t)px - W / 2;
     const int32_t y = (H - H / 2) - (int32_t)py;
     const double xd = (sub & 1u) ? ((double)x + 0.5) : (double)x;                      // engine.rs:207-236: sub-samples (x,y),(x+.5,y),(x,y+.5),(x+.5,y+.5)
@@ -1852,6 +1865,15 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
         const uint32_t us = (uint32_t)(ticks / kRealtimeTicksPerUs);
         const uint32_t bucket = us < 2u ? 0u : (uint32_t)(31 - __builtin_clz(us));                 // 0: < 2 us, b: [2^b, 2^(b+1)) us
         if (lane == 0) { atomicAdd(S.prof + (bucket < 15u ? bucket : 15u), 1ull); atomicMax(S.prof + 16, ticks); }
+        // ... and what the waves that find nothing hold of it: this build walks every wave, also those the coverage mask proves empty, and counts
+        // [17] the summed ticks of all waves, [18] / [19] the waves with no hit in any lane (no segment ray of theirs found a triangle) and their ticks,
+        // [20] / [21] the waves whose mask bit is clear and their ticks, [22] such waves that did find a hit (must stay 0)
+        const bool no_hit = !__any(prof.c[13] != 0ull), proved = cover && !((cover[blk >> 5] >> (blk & 31u)) & 1u);
+        if (lane == 0) {
+            atomicAdd(S.prof + 17, ticks);
+            if (no_hit) { atomicAdd(S.prof + 18, 1ull); atomicAdd(S.prof + 19, ticks); }
+            if (proved) { atomicAdd(S.prof + 20, 1ull); atomicAdd(S.prof + 21, ticks); if (!no_hit) atomicAdd(S.prof + 22, 1ull); }
+        }
     }
 #elif defined(RRT_PROFILE)
     PROF_T(4);
@@ -2490,7 +2512,7 @@ inline int effective_walk(const DevScene& s, int walk) { return (walk == kWalkBu
 // Forces the code object of this library onto the current device (HIP loads it lazily, ~80 ms for these kernels): called from a helper thread
 // while the host is still parsing the scene (api.cpp, warm_device_async).
 void preload_kernels_lane_ray();
-int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds, const uint32_t* d_cover);
 template <class Params> int launch_region_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
 void preload_kernels() {
     hipFuncAttributes a;
@@ -2517,10 +2539,10 @@ static int dev_hsaco_launch(const DevScene& s, const FrameParams& f, uint32_t* d
         if (hipMalloc((void**)&d_cnt, kCnt * 4) != hipSuccess) abort();
     }
     char name[160];
-    snprintf(name, sizeof name, "_ZN3rrt12_GLOBAL__N_113render_kernelILi%dELb%dEEEvNS_8DevSceneENS_11FrameParamsEPj", walk, s.has_groups ? 1 : 0);
+    snprintf(name, sizeof name, "_ZN3rrt12_GLOBAL__N_113render_kernelILi%dELb%dEEEvNS_8DevSceneENS_11FrameParamsEPjPKj", walk, s.has_groups ? 1 : 0);
     hipFunction_t fn;
     if (hipModuleGetFunction(&fn, mod, name) != hipSuccess) { fprintf(stderr, "RRT_DEV_HSACO: no kernel %s\n", name); abort(); }
-    struct Args { DevScene s; FrameParams f; uint32_t* out; } a{s, f, d_out};
+    struct Args { DevScene s; FrameParams f; uint32_t* out; const uint32_t* cover; } a{s, f, d_out, nullptr};   // (block counts of every wave: no coverage mask)
     a.s.tex = reinterpret_cast<const DevTexture*>(d_cnt);            // the kernels never read DevScene::tex (texture descriptors are inline in the materials)
     (void)hipMemsetAsync(d_cnt, 0, kCnt * 4, stream);
     size_t size = sizeof a;
@@ -2538,7 +2560,7 @@ static int dev_hsaco_launch(const DevScene& s, const FrameParams& f, uint32_t* d
 #endif
 
 // One frame, or the band / the rank's share of it that f describes: one block per quadrant of its tiles.
-int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk) {
+int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, const uint32_t* d_cover) {
     walk = effective_walk(s, walk);
     const uint32_t n_tiles = f.tile_end > f.tile_begin ? f.tile_end - f.tile_begin : 0u;
     const uint32_t local_tiles = (n_tiles + f.world - 1) / f.world;
@@ -2547,9 +2569,9 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
 #ifdef RRT_DEV_HSACO
     if (getenv("RRT_DEV_HSACO")) return dev_hsaco_launch(s, f, d_out, (hipStream_t)stream, walk, dim3(local_tiles * 4), lds);
 #endif
-    if (walk != kWalkBundle) return launch_render_lane_ray(s, f, d_out, stream, walk, local_tiles * 4, lds);
+    if (walk != kWalkBundle) return launch_render_lane_ray(s, f, d_out, stream, walk, local_tiles * 4, lds, d_cover);
     return with_groups(s, [&](auto groups) {
-        hipLaunchKernelGGL((render_kernel<kWalkBundle, groups()>), dim3(local_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, f, d_out);
+        hipLaunchKernelGGL((render_kernel<kWalkBundle, groups()>), dim3(local_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, f, d_out, d_cover);
         return (int)hipGetLastError();
     });
 }
@@ -2593,10 +2615,10 @@ void preload_kernels_lane_ray() {
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_kernel<kWalkRay, false>));
     (void)hipGetLastError();
 }
-int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds, const uint32_t* d_cover) {
     return with_lane_or_ray_walk(walk, [&](auto w) {
         return with_groups(s, [&](auto groups) {
-            hipLaunchKernelGGL((render_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, f, d_out);
+            hipLaunchKernelGGL((render_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, f, d_out, d_cover);
             return (int)hipGetLastError();
         });
     });

@@ -9,5 +9,5 @@ cd "$HERE/../rust-ray-tracer_amd/csrc"
 NAME=$1; EXTRA=$2; RENDER=${3:-render.hip}
 KF=${KFLAGS-$(python3 "$HERE/_kflags.py")}
 HOSTSRC=$(sed -n 's/^HOSTSRC := //p' Makefile)   # the host units, as csrc/Makefile lists them
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math $KF -I. $EXTRA -shared -o ../librrt_hip_$NAME.so $HOSTSRC scene_build.hip compact.hip sort.hip wavefront.hip $RENDER -lz 2>/tmp/build_variant_$NAME.log || { tail -5 /tmp/build_variant_$NAME.log; echo "FAILED librrt_hip_$NAME.so"; exit 1; }
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math $KF -I. $EXTRA -shared -o ../librrt_hip_$NAME.so $HOSTSRC scene_build.hip compact.hip sort.hip wavefront.hip coverage.hip $RENDER -lz 2>/tmp/build_variant_$NAME.log || { tail -5 /tmp/build_variant_$NAME.log; echo "FAILED librrt_hip_$NAME.so"; exit 1; }
 echo built librrt_hip_$NAME.so

@@ -24,3 +24,9 @@ for b in range(16):
     acc += c[b]
     lo = 0 if b == 0 else 2 ** b
     print(f"  {lo:6d} .. {2 ** (b + 1):6d} us: {c[b]:>9,d} waves  {100.0 * c[b] / tot:6.2f} %   (cumulative {100.0 * acc / tot:6.2f} %)")
+# what the waves that find nothing hold of the summed wave time (render.hip: slots 17..22; this build walks every wave, also those the coverage mask proves empty)
+ticks = c[17] or 1
+print(f"summed wave time {c[17] / 100.0:,.0f} us; mean wave {c[17] / 100.0 / tot:.2f} us")
+print(f"waves with no hit in any lane: {c[18]:,d} = {100.0 * c[18] / tot:.2f} % of the waves, {100.0 * c[19] / ticks:.2f} % of the summed wave time, mean {c[19] / 100.0 / (c[18] or 1):.2f} us")
+print(f"waves the coverage mask proves empty ({rt.coverage_info()['state']}): {c[20]:,d} = {100.0 * c[20] / tot:.2f} % of the waves, {100.0 * c[21] / ticks:.2f} % of the summed wave time, "
+      f"mean {c[21] / 100.0 / (c[20] or 1):.2f} us; of them with a hit (must be 0): {c[22]}")
