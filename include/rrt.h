@@ -935,6 +935,12 @@ int rrt_raytracer_get_chain_info(const rrt_raytracer *rt, uint32_t *n_chains, ui
 #define RRT_COVERAGE_OFF_NOT_WHOLE 8u    /* a rank's tiles (rrt_render_tiles_device) or a progressive frame */
 #define RRT_COVERAGE_OFF_SMALL_FRAME 9u  /* the pass would cost more than it saves: fewer than 49 152 waves (1024 x 768 pixels), or more than four triangle slots per wave (RRT_FLAG_COVERAGE_ALWAYS lifts both) */
 int rrt_raytracer_get_coverage_info(const rrt_raytracer *rt, uint32_t *state, uint64_t *n_waves, uint64_t *n_proved_empty);
+/* The mask itself of that frame, BLOCKING like n_proved_empty: n_words = (tiles_x * tiles_y + 7) / 8 words of 32 bits, tiles_x = (width + 7) / 8 and tiles_y =
+ * (height + 7) / 8 of the frame.  Wave (bx, by) -- the pixels [4 bx, 4 bx + 3] x [4 by, 4 by + 3] -- is bit ((((by / 2) * tiles_x + bx / 2) * 4) | ((by & 1) * 2) |
+ * (bx & 1)), counted from bit 0 of word 0; a set bit means the wave walked, a clear bit that it was proved empty.  The bits of the last word beyond the frame's
+ * waves are 0.  RRT_ERR_INVALID_ARG for a NULL pointer, and for an n_words that is not that frame's.  When the last frame ran without a mask (state !=
+ * RRT_COVERAGE_ON) nothing is written and the call returns RRT_OK.  A developer's and tests' view: no launch reads it back. */
+int rrt_raytracer_get_coverage_mask(const rrt_raytracer *rt, uint32_t *words, uint64_t n_words);
 
 int rrt_last_stats(const rrt_raytracer *rt, rrt_stats *out);
 /* Time of the set-up stages that run once per scene (the reference does all of them inside parse_obj_file_lines, utils.rs:139-213, before its one

@@ -272,6 +272,7 @@ SYMBOLS = {
     "rrt_raytracer_get_buffer": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
     "rrt_raytracer_get_coverage_info": (C.c_int, [_P, _u32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "rrt_raytracer_get_coverage_mask": (C.c_int, [_P, _u32p, C.c_uint64]),
     "rrt_last_stats": (C.c_int, [_P, C.POINTER(CStats)]),
     "rrt_get_setup_times": (C.c_int, [_P, _P, C.POINTER(CSetupTimes)]),
     "rrt_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -803,6 +804,20 @@ class RayTracer(_Handle):
         _call("rrt_raytracer_get_coverage_info", self._h, C.byref(state), C.byref(waves), C.byref(empty) if count else None)
         out = {"state": COVERAGE_STATES[state.value], "n_waves": waves.value}
         return dict(out, n_proved_empty=empty.value) if count else out
+
+    def coverage_mask(self) -> Optional[np.ndarray]:
+        """rrt_raytracer_get_coverage_mask: the coverage mask of the last frame launch as a bool array [2 tiles_y, 2 tiles_x] indexed [by, bx] -- True where the
+        4x4-pixel wave (bx, by) walked, False where the mask proved it empty -- or None where that frame ran without a mask (coverage_info()["state"] != "on").
+        Waits for the frame and reads its mask back."""
+        if self.coverage_info()["state"] != "on":
+            return None
+        stats = self.last_stats()
+        tiles_x, tiles_y = (stats["width"] + 7) // 8, (stats["height"] + 7) // 8
+        words = np.zeros((tiles_x * tiles_y + 7) // 8, np.uint32)
+        _call("rrt_raytracer_get_coverage_mask", self._h, _u32(words), words.size)
+        by, bx = np.mgrid[0:2 * tiles_y, 0:2 * tiles_x]
+        bit = (((by >> 1) * tiles_x + (bx >> 1)) << 2) | ((by & 1) << 1) | (bx & 1)      # coverage_wave_index (csrc/coverage_rule.hpp)
+        return ((words[bit >> 5] >> (bit & 31).astype(np.uint32)) & 1).astype(bool)
 
     def octree(self) -> dict:
         """The octree this raytracer's GPU set-up built (rrt_raytracer_get_octree): same dict as SceneData.octree(), plus "info"."""

@@ -33,8 +33,13 @@
 //      at the largest width the library accepts (2^31).
 // The real safety is neither: it is the pad of the box itself (2^-15 of the scene's magnitude), which is what makes "the ray misses the box" imply
 // "the reference finds no hit".  The margin only has to keep the rule from being LESS careful than an exact projection of that box.
+// UNBOUNDED RECORDS.  A half-extent of FLT_MAX is not a length: it is what the index writes, with c = 0, for an axis along which a padded bound left fp32's range
+// (clusters.cpp and scene_build.hip: to_centre_half), and the filters read it as "always hit".  Taken as the box [-FLT_MAX, FLT_MAX] it does not contain a
+// triangle of a scene whose coordinates lie beyond FLT_MAX (a root box scaled by 2^180: the eye is at 1e55, and the "box" projects onto a few waves around the
+// direction of the origin -- tests/test_gpu_coverage_poses.py found 4092 of 6912 pixels WHITE that are not).  Such a box reaches the whole frame.
 // RRT_COVERAGE_MARGIN_SIGN exists for the model test alone: built with -1 the rule must fail the sweep.
 #pragma once
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 
@@ -76,11 +81,12 @@ RRT_COV_HD inline uint32_t coverage_wave_index(uint32_t tiles_x, uint32_t bx, ui
 // x clamped to [lo, hi] and converted; x is finite
 RRT_COV_HD inline int32_t coverage_clamp_i32(double x, double lo, double hi) { return (int32_t)(x < lo ? lo : x > hi ? hi : x); }
 
-// The waves a box in device form (centre c, half-extent h: device_scene.hpp, DevClusterBox) can reach.  The empty box (h < 0) reaches none.
+// The waves a box in device form (centre c, half-extent h: device_scene.hpp, DevClusterBox) can reach.  The empty box (h < 0) reaches none, a box that is
+// unbounded along an axis (h >= FLT_MAX) every one.
 RRT_COV_HD inline CoverageRect coverage_rect(const CoverageFrame& F, const float c[3], const float h[3]) {
     if (h[0] < 0.0f || h[1] < 0.0f || h[2] < 0.0f) return CoverageRect{0, -1, 0, -1};
     double xlo = HUGE_VAL, xhi = -HUGE_VAL, ylo = HUGE_VAL, yhi = -HUGE_VAL;
-    bool whole = false;
+    bool whole = h[0] >= FLT_MAX || h[1] >= FLT_MAX || h[2] >= FLT_MAX;        // unbounded along an axis (the corners below are then of no account)
     for (int k = 0; k < 8; k++) {
         double d[3], ad[3];
         for (int j = 0; j < 3; j++) {

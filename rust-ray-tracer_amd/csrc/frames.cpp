@@ -135,6 +135,17 @@ int launch_whole_frame(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out,
     rt->cover_last = i; rt->cover_tiles_x = F.tiles_x; rt->cover_tiles_y = F.tiles_y;
     return 0;
 }
+// The mask of the last frame (rt->cover_last >= 0) in host memory, coverage_mask_words words: waits for that frame and copies.  The bits of the last word beyond
+// the frame's waves are cleared: a box that reaches the whole frame sets whole words.  The launch path never does this; the two getters below do, on request.
+void read_cover_mask(rrt_raytracer* rt, uint32_t* words) {
+    DeviceGuard guard(rt->device);
+    const rrt_raytracer::CoverBuf& b = rt->cover[rt->cover_last];
+    const uint64_t waves = 4ull * rt->cover_tiles_x * rt->cover_tiles_y;
+    const uint32_t n = coverage_mask_words(rt->cover_tiles_x, rt->cover_tiles_y);
+    HIP_TRY(hipEventSynchronize(b.done.h));
+    HIP_TRY(hipMemcpy(words, b.mask.mem.h, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    if (n && waves % 32u) words[n - 1] &= (1u << (waves % 32u)) - 1u;
+}
 
 void tune_variant(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void* stream) {
     if (rt->variant_forced) return;
@@ -324,16 +335,23 @@ int rrt_raytracer_get_coverage_info(const rrt_raytracer* rt_c, uint32_t* state, 
         if (!n_proved_empty) return RRT_OK;
         *n_proved_empty = 0;
         if (!on) return RRT_OK;
-        // on request only: wait for the frame, bring its mask down and count the clear bits (the bits of a last word beyond the frame's waves are never set)
-        DeviceGuard guard(rt->device);
-        const rrt_raytracer::CoverBuf& b = rt->cover[rt->cover_last];
+        // on request only: bring the mask down and count the clear bits
         std::vector<uint32_t> h(coverage_mask_words(rt->cover_tiles_x, rt->cover_tiles_y));
-        HIP_TRY(hipEventSynchronize(b.done.h));
-        HIP_TRY(hipMemcpy(h.data(), b.mask.mem.h, sizeof(uint32_t) * h.size(), hipMemcpyDeviceToHost));
-        if (waves % 32u) h.back() &= (1u << (waves % 32u)) - 1u;           // (a box that reaches the whole frame sets whole words)
+        read_cover_mask(rt, h.data());
         uint64_t set = 0;
         for (uint32_t w : h) set += (uint64_t)__builtin_popcount(w);
         *n_proved_empty = waves - set;
+        return RRT_OK;
+    });
+}
+
+int rrt_raytracer_get_coverage_mask(const rrt_raytracer* rt_c, uint32_t* words, uint64_t n_words) {
+    return guarded([&]() -> int {
+        rrt_raytracer* rt = const_cast<rrt_raytracer*>(rt_c);
+        if (!rt || !words) throw Error{RRT_ERR_INVALID_ARG, "null argument"};
+        if (rt->cover_last < 0) return RRT_OK;                             // the last frame ran without a mask: nothing is written
+        if (n_words != coverage_mask_words(rt->cover_tiles_x, rt->cover_tiles_y)) throw Error{RRT_ERR_INVALID_ARG, "n_words is not the number of mask words of the last frame"};
+        read_cover_mask(rt, words);
         return RRT_OK;
     });
 }

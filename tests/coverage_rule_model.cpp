@@ -1,5 +1,10 @@
 // Stand-alone host check of csrc/coverage_rule.hpp (tests/test_coverage_rule.py builds and runs it; never linked into the library).
 //   coverage_rule_model N     sweeps about N (box, camera, ray) tuples and prints one line of counts; exit status 0 unless the program itself is broken.
+//   coverage_rule_model --pairs IN OUT     (second mode; "-" is stdin / stdout) reads (frame, box) pairs in binary and writes what the header makes of each:
+//       in, 152 bytes:  uint32 width, height; double x_scale, y_scale, z_value, right[3], up[3], forward[3], eye[3]; float c[3], h[3]
+//       out, 136 bytes: int32 ok (coverage_frame), bx0, bx1, by0, by1 (coverage_rect), whole (coverage_is_whole_frame); uint32 tiles_x, tiles_y;
+//                       double inv[9], kx, ky, half_w, top          (everything after ok is 0 where ok is 0)
+//     tests/test_coverage_restatement.py requires every field to equal tests/coverage_checks.py's.
 // For every tuple: the ray is formed exactly as render_kernel forms the primary ray of a sub-sample; wherever a slab test of that ray against the box [c - h, c + h]
 // says "meets" -- in f64 or in long double -- the rule must have marked the sub-sample's wave.  A failure is counted, not fatal: the test that builds this program
 // with the margin negated expects failures.
@@ -7,6 +12,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 
 #include "coverage_rule.hpp"
@@ -198,9 +204,40 @@ void sweep_exact(Rng& R, uint64_t boxes, Counts& n) {
     }
 }
 
+struct PairIn { uint32_t width, height; double x_scale, y_scale, z_value, right[3], up[3], forward[3], eye[3]; float c[3], h[3]; };
+struct PairOut { int32_t ok, bx0, bx1, by0, by1, whole; uint32_t tiles_x, tiles_y; double inv[9], kx, ky, half_w, top; };
+static_assert(sizeof(PairIn) == 152 && sizeof(PairOut) == 136, "the record layouts tests/test_coverage_restatement.py reads and writes");
+
+int pairs_mode(const char* in_name, const char* out_name) {
+    FILE* in = strcmp(in_name, "-") ? fopen(in_name, "rb") : stdin;
+    FILE* out = strcmp(out_name, "-") ? fopen(out_name, "wb") : stdout;
+    if (!in || !out) { fprintf(stderr, "cannot open %s or %s\n", in_name, out_name); return 2; }
+    PairIn p;
+    uint64_t n = 0;
+    while (fread(&p, sizeof p, 1, in) == 1) {
+        PairOut o;
+        memset(&o, 0, sizeof o);
+        CoverageFrame F;
+        if (coverage_frame(F, p.width, p.height, p.x_scale, p.y_scale, p.z_value, p.right, p.up, p.forward, p.eye)) {
+            const CoverageRect r = coverage_rect(F, p.c, p.h);
+            o.ok = 1; o.bx0 = r.bx0; o.bx1 = r.bx1; o.by0 = r.by0; o.by1 = r.by1; o.whole = coverage_is_whole_frame(F, r) ? 1 : 0;
+            o.tiles_x = F.tiles_x; o.tiles_y = F.tiles_y;
+            for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) o.inv[3 * i + j] = F.inv[i][j];
+            o.kx = F.kx; o.ky = F.ky; o.half_w = F.half_w; o.top = F.top;
+        }
+        if (fwrite(&o, sizeof o, 1, out) != 1) { fprintf(stderr, "short write\n"); return 2; }
+        n++;
+    }
+    if (out != stdout) fclose(out); else fflush(out);
+    if (in != stdin) fclose(in);
+    fprintf(stderr, "pairs=%llu\n", (unsigned long long)n);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc == 4 && !strcmp(argv[1], "--pairs")) return pairs_mode(argv[2], argv[3]);
     const uint64_t N = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1000000ull;
     Rng R{0x5EEDC0DEull};
     Counts n;
@@ -230,6 +267,15 @@ int main(int argc, char** argv) {
         if (!coverage_is_whole_frame(F, coverage_rect(F, c0, bad))) n.failures++;
         if (!coverage_is_whole_frame(F, coverage_rect(F, bad, c0))) n.failures++;
         if (!coverage_is_whole_frame(F, coverage_rect(F, c0, inf3))) n.failures++;
+        // an unbounded record (c = 0, h = FLT_MAX along an axis) seen from an eye far beyond fp32's range: the whole frame, not the few waves around the origin's direction
+        const double far_eye[3] = {0, 0x1p181, -0x1p183};
+        if (!coverage_frame(F, 96, 72, 1.0 / 96, 1.0 / 72, 1.0, X, Y, Z, far_eye)) n.failures++;
+        for (int k = 0; k < 3; k++) {
+            float hk[3] = {1.0f, 1.0f, 1.0f}; hk[k] = 3.4028235e38f;
+            if (!coverage_is_whole_frame(F, coverage_rect(F, c0, hk))) n.failures++;
+        }
+        const float nearly[3] = {3.4028233e38f, 3.4028233e38f, 3.4028233e38f};       // the largest finite extent below the mark is a length
+        if (coverage_is_whole_frame(F, coverage_rect(F, c0, nearly))) n.failures++;
     }
     const uint64_t setup_failures = n.failures;
     sweep_exact(R, N / 16 + 1000, n);

@@ -5,7 +5,7 @@ import re
 
 import pytest
 
-from abi_checks import compiled_values, host_compiler
+from abi_checks import PATTERN, assert_refused, compiled_values, host_compiler
 from conftest import ROOT
 
 
@@ -121,6 +121,22 @@ def test_round2_entry_points_validate_their_arguments_without_a_gpu(rrt, teapot)
     assert L.rrt_raytracer_get_buffer(None, 0, None, 0, None) == rrt.ERR_INVALID_ARG
     assert L.rrt_raytracer_create_from_arrays(3, None, None, None, None, 0, None, 0, None, None, None, 0, rrt.Vec3(0, 0, 0), None, 0, C.byref(out)) == rrt.ERR_INVALID_ARG
     assert L.rrt_get_setup_times(None, None, None) == rrt.ERR_INVALID_ARG
+
+
+def test_coverage_getters_refuse_null_arguments(rrt):
+    """rrt_raytracer_get_coverage_info and rrt_raytracer_get_coverage_mask without a raytracer, and the mask without a place to put it: refused before any HIP
+    call, with a detail of their own, and nothing is written.  (What they refuse of a real raytracer -- an n_words that is not the last frame's -- and the frame
+    without a mask are in tests/test_gpu_coverage_poses.py.)"""
+    import ctypes as C
+    import numpy as np
+    L = rrt.lib()
+    words = np.full(4, PATTERN, np.uint32)
+    state = C.c_uint32(PATTERN); waves = C.c_uint64(PATTERN)
+    wp = words.ctypes.data_as(C.POINTER(C.c_uint32))
+    assert_refused(rrt, L, [("coverage_info(NULL)", lambda: L.rrt_raytracer_get_coverage_info(None, C.byref(state), C.byref(waves), None)),
+                            ("coverage_mask(NULL raytracer)", lambda: L.rrt_raytracer_get_coverage_mask(None, wp, 4)),
+                            ("coverage_mask(NULL, NULL)", lambda: L.rrt_raytracer_get_coverage_mask(None, None, 0))], untouched={"words": words})
+    assert state.value == PATTERN and waves.value == PATTERN
 
 
 def test_flag_constants_match_the_header(rrt):

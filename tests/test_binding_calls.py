@@ -445,6 +445,24 @@ def query_cases():
     yield Case("chain_info", lambda e: e.rt.chain_info, lambda e, r: [("rrt_raytracer_get_chain_info", (RT, 0, 0))],
                replies=lambda e: {"rrt_raytracer_get_chain_info": lambda h, a, b: (setattr(a._obj, "value", 3), setattr(b._obj, "value", 9))},
                check=lambda e, r: r == {"n_chains": 3, "n_chain_nodes": 9})
+    fill_cover = lambda state, waves, empty: lambda h, s_, w_, e_: (setattr(s_._obj, "value", state), setattr(w_._obj, "value", waves),
+                                                                      e_ is not None and setattr(e_._obj, "value", empty))
+    yield Case("coverage_info", lambda e: e.rt.coverage_info(), lambda e, r: [("rrt_raytracer_get_coverage_info", (RT, 0, 0, None))],
+               replies=lambda e: {"rrt_raytracer_get_coverage_info": fill_cover(9, 0, 0)}, check=lambda e, r: r == {"state": "small_frame", "n_waves": 0})
+    yield Case("coverage_info(count)", lambda e: e.rt.coverage_info(count=True), lambda e, r: [("rrt_raytracer_get_coverage_info", (RT, 0, 0, 0))],
+               replies=lambda e: {"rrt_raytracer_get_coverage_info": fill_cover(0, 48, 7)}, check=lambda e, r: r == {"state": "on", "n_waves": 48, "n_proved_empty": 7})
+    # coverage_mask: a 20 x 12 frame has 3 x 2 tiles = 24 waves in ONE word; the reply sets the bits of waves (bx 5, by 0) and (bx 2, by 3):
+    # ((0 * 3 + 2) * 4 | 0 | 1) = 9 and ((1 * 3 + 1) * 4 | 2 | 0) = 18
+    def mask_reply(h, words, n):
+        words[0] = (1 << 9) | (1 << 18)
+    mask_want = np.zeros((4, 6), bool); mask_want[0, 5] = mask_want[3, 2] = True
+    yield Case("coverage_mask", lambda e: e.rt.coverage_mask(),
+               lambda e, r: [("rrt_raytracer_get_coverage_info", (RT, 0, 0, None)), ("rrt_last_stats", (RT, zeros(e.rrt.CStats))), ("rrt_raytracer_get_coverage_mask", (RT, ANY, 1))],
+               replies=lambda e: {"rrt_raytracer_get_coverage_info": fill_cover(0, 24, 0), "rrt_last_stats": out_fields(1, width=20, height=12),
+                                  "rrt_raytracer_get_coverage_mask": mask_reply},
+               check=lambda e, r: r.dtype == bool and r.shape == (4, 6) and np.array_equal(r, mask_want))
+    yield Case("coverage_mask(no mask)", lambda e: e.rt.coverage_mask(), lambda e, r: [("rrt_raytracer_get_coverage_info", (RT, 0, 0, None))],
+               replies=lambda e: {"rrt_raytracer_get_coverage_info": fill_cover(5, 0, 0)}, check=lambda e, r: r is None)
     yield Case("buffer", lambda e: e.rt.buffer("attr"),                                                              # RRT_BUF_ATTR = 2
                lambda e, r: [("rrt_raytracer_get_buffer", (RT, 2, None, 0, 0)), ("rrt_raytracer_get_buffer", (RT, 2, addr(r), 5, None))],
                replies=lambda e: {"rrt_raytracer_get_buffer": out_value(4, 5)}, check=lambda e, r: r.shape == (5,) and r.dtype == np.uint8)

@@ -17,6 +17,7 @@ raytracer, the raytracer without the pass, and the oracle.
 import numpy as np
 import pytest
 
+import coverage_checks
 from bitwise import assert_same_bits
 from gpu_checks import CHAIN_PAD, FORCED_MODES, MATS, ORIGIN, flat_normals, oracle_for
 
@@ -61,37 +62,12 @@ TOP2 = H2 - H2 // 2
 
 
 def rule_waves(tboxes, w, h, eye=ORIGIN):
-    """csrc/coverage_rule.hpp restated for the identity basis and viewport (1, 1, 1), constant for constant: the [waves_y, waves_x] mask of the box records `tboxes`
-    (bytes of RRT_BUF_TBOXES).  Comparing the library's count with this one checks how the kernel MARKS (its word patterns, the copy in LDS, the flush) against the
-    rule; it does not check the rule, whose independent references are the oracle's frames here and the slab tests of tests/test_coverage_rule.py."""
-    rec = np.frombuffer(tboxes.tobytes(), np.float32).reshape(-1, 8)[:-8]          # (behind the slots: eight spare records, never read as boxes of triangles)
-    tiles_x, tiles_y = (w + 7) // 8, (h + 7) // 8
-    mask = np.zeros((2 * tiles_y, 2 * tiles_x), bool)
-    half_w, top, kx, ky = float(w // 2), float(h - h // 2), float(w), float(h)
-    for c, hh in zip(rec[:, 0:3].astype(np.float64), rec[:, 3:6].astype(np.float64)):
-        if (hh < 0).any():
-            continue
-        xs, ys, whole = [], [], False
-        for k in range(8):
-            d = c + np.where([(k >> j) & 1 for j in range(3)], hh, -hh) - np.asarray(eye, np.float64)
-            E = 1e-12 * np.abs(d).sum()
-            g_lo = d[2] - E
-            if not g_lo > 0:
-                whole = True
-                continue
-            qa, qb = d[0] / d[2], d[1] / d[2]
-            xd, yd = qa * kx, qb * ky
-            mx = 1e-6 + 1e-9 * abs(xd) + 2.0 * kx * ((abs(qa) * E + E) / g_lo)
-            my = 1e-6 + 1e-9 * abs(yd) + 2.0 * ky * ((abs(qb) * E + E) / g_lo)
-            xs += [xd - mx, xd + mx]; ys += [yd - my, yd + my]
-        if whole:
-            mask[:] = True
-            continue
-        bx0 = int(max(0.0, np.ceil((min(xs) + half_w - 3.5) * 0.25))); bx1 = int(min(2.0 * tiles_x - 1, np.floor((max(xs) + half_w) * 0.25)))
-        by0 = int(max(0.0, np.ceil((top - 3.0 - max(ys)) * 0.25))); by1 = int(min(2.0 * tiles_y - 1, np.floor((top + 0.5 - min(ys)) * 0.25)))
-        if bx0 <= bx1 and by0 <= by1:
-            mask[by0:by1 + 1, bx0:bx1 + 1] = True
-    return mask
+    """csrc/coverage_rule.hpp restated (tests/coverage_checks.py, held to the header's bits by tests/test_coverage_restatement.py) for the identity basis and
+    viewport (1, 1, 1): the [waves_y, waves_x] mask of the box records `tboxes` (bytes of RRT_BUF_TBOXES).  Comparing the library's count with this one checks
+    how the kernel MARKS (its word patterns, the copy in LDS, the flush) against the rule; it does not check the rule, whose independent references are the
+    oracle's frames here and the slab tests of tests/test_coverage_rule.py."""
+    frame = coverage_checks.frame_of(w, h, (1.0, 1.0, 1.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), eye)
+    return coverage_checks.mask_of(frame, coverage_checks.rects_of(frame, tboxes))
 
 
 def at(xd, yd, z):
