@@ -421,6 +421,51 @@ int rrt_ambient_surface_device(rrt_raytracer *rt, uint32_t width, uint32_t heigh
 int rrt_ambient_surface(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
                         const rrt_surface *planes, const rrt_ambient_samples *samples, const rrt_ambient *out);
 
+/* The fused frame of a region: the COLOURS of a rectangle of the frame from the kernel body that renders whole frames -- primary walk, lights, reflection chain
+ * and unwind in one launch, nothing kept in memory on the way.  For the rectangle under an edited object, a render border, one GPU's share of a frame.
+ * (The same pixels through rrt_render_surface + rrt_shade_surface cost more than a frame and about 120 bytes of planes per sub-sample.)
+ * OUTPUT.  Pixel (px, py) of the region in force -- the whole frame for region == NULL -- is written to out[(py - y0) * pitch + (px - x0)], 0x00RRGGBB.  pitch is
+ * in elements; 0 means region.w, a tight [h][w] array.  With out = fb + y0 * width + x0 and pitch = width the region lands in place in a whole framebuffer.
+ * Nothing outside the region's w elements of each row is read or written: not the gap up to pitch, not a row before or after.
+ * VALUE.  Exactly the one rrt_render writes at [py][px] for the pose, lights, materials and triangles in force, bit for bit, in every traversal variant -- 0
+ * included for the pixels the reference never traces (canvas row 0, row 1 of an odd height, the last column of an odd width).
+ * Traversal variant, tuning state and rrt_last_stats as the visibility calls: the forced variant, else the one kept for this frame size, else the first-frame
+ * rule's; the call is not a frame of that size: it never triggers or alters a measurement and leaves the coverage state of the last frame
+ * (rrt_raytracer_get_coverage_info) as it was; kernel_ms and filter_variant of this launch, width / height = the frame size, rays_primary = 4 * the traced pixels
+ * inside the region.  No coverage pass runs in front of it (its mask is indexed by the whole frame's waves): a region that is the whole frame walks the waves
+ * a frame with RRT_FLAG_NO_COVERAGE walks.
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving the raytracer and the output as they were: NULL rt, NULL out, a bad frame size, a region with w == 0 or
+ * h == 0 or one that sticks out of the frame, a pitch other than 0 that is smaller than the region's width.
+ * rrt_render_region_device: d_out in device memory of rt's device; enqueued on `stream` (hipStream_t, NULL = default): no allocation, no copy, no synchronisation.
+ * Regions of one frame that do not overlap may be in flight on several streams, or on several raytracers of the same scene, into one buffer.
+ * rrt_render_region: out in host memory; blocking: the pixels go through the device allocation the visibility calls keep and arrive in the caller's rows, the
+ * gap between rows untouched; nothing is in flight on return.
+ * Not covered: a coverage pass, lists of rectangles, the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+int rrt_render_region_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                             uint32_t *d_out, uint32_t pitch, void *stream);
+int rrt_render_region(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                      uint32_t *out, uint32_t pitch);
+
+/* The fused frame of a list of 8x8-pixel tiles that lies in DEVICE memory: re-render the tiles a kernel of the caller's flagged (stale after a reprojection, not
+ * yet converged), in the order of the caller's choosing, with no read-back and no synchronisation -- in the style of the COUNTED DEVICE FORMS below.
+ * d_fb is a whole row-major [height][width] framebuffer.  d_tiles[j] is a tile index in the frame kernels' numbering: ty * tiles_x + tx with
+ * tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8.  With m = min(n, *d_count) -- m = n for d_count == NULL -- every pixel of the tiles d_tiles[0..m)
+ * that lies inside the frame is written as rrt_render writes it, bit for bit; every other pixel of d_fb is neither read nor written.  The kernel reads *d_count
+ * when it runs, in stream order: a kernel enqueued before the call on the same stream may write it, and the list.
+ * ENTRIES.  d_tiles[j] is used as an index only after d_tiles[j] < tiles_x * tiles_y; any other value, 0xFFFFFFFF included, is skipped.  Entries [m, n) are never
+ * read.  Duplicates are allowed: both waves store the same bits.  The list and the bound are only ever read.
+ * LAUNCH.  The grid is sized by n, four blocks of 64 threads per entry (the frame kernels' quadrants); a block at or beyond m ends after one scalar load and a
+ * compare.  n == 0: RRT_OK, nothing is launched and rrt_last_stats stays as it was.  n > RRT_MAX_TILE_LIST: RRT_ERR_INVALID_ARG -- HIP launches at most
+ * 2^32 - 1 threads in a grid dimension, and an entry takes 256.
+ * ORDER.  The caller's order is the schedule: block 4 j + q renders quadrant q of entry j; nothing is reordered (no XCD-aware block order).
+ * Traversal variant and tuning state as for a region.  rrt_last_stats: kernel_ms and filter_variant of this launch, width / height = the frame size,
+ * rays_primary = 0 -- the library does not read the list.  No coverage pass.
+ * RRT_ERR_INVALID_ARG, before any GPU work: NULL rt, a bad frame size, NULL d_fb, n > RRT_MAX_TILE_LIST, NULL d_tiles with n > 0.
+ * There is no host form: a host that knows its tiles has regions. */
+#define RRT_MAX_TILE_LIST 16777215u   /* (2^32 - 1) / 256 */
+int rrt_render_tile_list_device(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t *d_count,
+                                const uint32_t *d_tiles, uint32_t *d_fb, void *stream);
+
 /* Screen-tile partition for N GPUs (one process per GPU): the frame is cut into 8x8-pixel tiles, tile k (row-major)
  * belongs to rank k % world.  Renders this rank's tiles into d_tiles[rrt_tiles_per_rank][64] (tile-major, device).
  * After a gather (or all-gather) of the per-rank buffers (RCCL, done by the caller), rrt_detile_device turns

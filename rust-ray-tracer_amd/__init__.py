@@ -108,6 +108,7 @@ class CRaySet(C.Structure):          # rrt_ray_set, 128 bytes: host or device po
 
 
 MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
+MAX_TILE_LIST = 16777215             # RRT_MAX_TILE_LIST: the longest list render_tile_list_into takes
 SELECT_MODES = ("hit", "mirror", "flag")   # RRT_SELECT_HIT, RRT_SELECT_MIRROR, RRT_SELECT_FLAG
 DEAD_INDEX = 0xFFFFFFFF              # index of a tail slot of a compacted batch
 SORT_KEY_MODES = ("given", "ray", "record")   # RRT_SORT_KEY_GIVEN, RRT_SORT_KEY_RAY, RRT_SORT_KEY_RECORD
@@ -211,6 +212,9 @@ SYMBOLS = {
     "rrt_shade_surface": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CVisibility), C.POINTER(CSurface), _u32p]),
     "rrt_ambient_surface_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CSurface), C.POINTER(CAmbientSamples), C.POINTER(CAmbient), _P]),
     "rrt_ambient_surface": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CSurface), C.POINTER(CAmbientSamples), C.POINTER(CAmbient)]),
+    "rrt_render_region_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), _P, C.c_uint32, _P]),
+    "rrt_render_region": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), _u32p, C.c_uint32]),
+    "rrt_render_tile_list_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
     "rrt_pick": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CPickResult)]),
     "rrt_tiles_per_rank": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rrt_render_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
@@ -1347,6 +1351,37 @@ class RayTracer(_Handle):
         _device_tensor(fb_tensor, width * height, 4, "fb")
         return _bound("rrt_detile_device", self._h, C.c_uint32(width), C.c_uint32(height), C.c_uint32(world), _ptr(gathered_tensor), _ptr(fb_tensor),
                       _P(_stream(stream)))
+
+    # the fused frame of a region and of a device-resident tile list (rrt.h: rrt_render_region, rrt_render_tile_list_device): the pixels render() gives, by the same kernel body
+    def render_region(self, width: int, height: int, region=None) -> np.ndarray:
+        """rrt_render_region: the region's pixels, [h][w] uint32 0x00RRGGBB: render(width, height)[y0:y0+h, x0:x0+w] bit for bit, traced for the region alone."""
+        reg, w, h = _region(width, height, region)
+        fb = np.empty((h, w), np.uint32)
+        _call("rrt_render_region", self._h, width, height, reg, _u32(fb), 0)
+        return fb
+
+    def render_region_into(self, fb_tensor, width: int, height: int, region=None, pitch: Optional[int] = None, offset: int = 0, stream: Optional[int] = None):
+        """rrt_render_region_device: the region's pixels into rows of `pitch` four-byte elements (None: the region's width, a tight [h][w] array) that begin `offset`
+        elements into fb_tensor, a contiguous device tensor that holds all of them; nothing else of it is touched.  With fb_tensor a whole [height][width] frame,
+        pitch = width and offset = y0 * width + x0 the region lands in place.  Enqueued, not synchronised."""
+        reg, w, h = _region(width, height, region)
+        pitch, offset = (w if pitch is None else int(pitch)), int(offset)
+        assert getattr(fb_tensor, "is_cuda", False), "fb: not a device tensor"
+        assert fb_tensor.is_contiguous() and fb_tensor.element_size() == 4, "fb: want contiguous four-byte elements"
+        assert pitch >= w and offset >= 0 and offset + (h - 1) * pitch + w <= fb_tensor.numel(), \
+            f"fb: {h} rows of {w} elements at pitch {pitch} from element {offset} do not lie inside {fb_tensor.numel()} elements"
+        _call("rrt_render_region_device", self._h, width, height, reg, _P(fb_tensor.data_ptr() + 4 * offset), pitch, _P(_stream(stream)))
+
+    def render_tile_list_into(self, fb_tensor, tiles_t, width: int, height: int, stream: Optional[int] = None, bound_t=None):
+        """rrt_render_tile_list_device: fb_tensor = a whole frame, width*height four-byte elements; tiles_t = a contiguous device tensor of four-byte tile indices
+        ty * ((width + 7) // 8) + tx, in the order they are to be rendered (an index that names no tile is skipped); bound_t = None or a device tensor of one
+        four-byte element: only the first min(len, bound) entries are read, by the kernel when it runs.  Enqueued, not synchronised."""
+        _device_tensor(fb_tensor, width * height, 4, "fb")
+        n = _batch_size(tiles_t, 1, "tiles")
+        _device_tensor(tiles_t, n, 4, "tiles")
+        if bound_t is not None:
+            _device_tensor(bound_t, 1, 4, "bound")
+        _call("rrt_render_tile_list_device", self._h, width, height, n, _ptr(bound_t), _ptr(tiles_t), _ptr(fb_tensor), _P(_stream(stream)))
 
     # visibility buffers (rrt.h: rrt_render_visibility): first-hit geometry of the frame's primary rays.  region = (x0, y0, w, h) in canvas pixels, None = the frame
     def visibility(self, width: int, height: int, region=None, planes=PLANES) -> dict:

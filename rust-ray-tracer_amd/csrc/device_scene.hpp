@@ -161,6 +161,26 @@ struct ShadeParams {
     uint32_t* out;
 };
 
+// Argument of the region frame kernels (render.hip: render_region_kernel; rrt.h: rrt_render_region_device): a VisParams -- frame, region and tile rectangle; its
+// six plane pointers are null -- plus the pixels it writes: pixel (px, py) of the region goes to out[(py - F.row_begin) * pitch + (px - col_begin)], pitch in
+// elements and at least the region's width.  Nothing else of `out` is touched.
+struct RenderRegionParams {
+    VisParams V;
+    uint32_t* out;
+    uint32_t pitch, _pad;
+};
+
+// Argument of the tile-list frame kernels (render.hip: render_tile_list_kernel; rrt.h: rrt_render_tile_list_device): the whole frame (F.rank / F.world = 0 / 1,
+// F.xcd_chunk = 0: the list's order is the schedule), a list of n tile indices ty * F.tiles_x + tx in device memory, the bound -- null, or one uint32 in device
+// memory: entries [min(n, *count), n) are not read -- and the row-major [height][width] framebuffer.  tiles and count are only ever read; an entry is used as
+// an index only after the compare with F.tile_end.
+struct TileListParams {
+    FrameParams F;
+    const uint32_t *tiles, *count;
+    uint32_t n, _pad;
+    uint32_t* out;
+};
+
 // Argument of the ambient kernels (render.hip: ambient_kernel; rrt.h: rrt_ambient_surface_device): a VisParams -- frame, region and tile rectangle; its six plane
 // pointers are unused -- plus the three planes the kernel READS, laid out as the surface launch wrote them for that region, the two planes it writes (occluded:
 // [rows][columns][4 sub-samples] masks; grey: [rows][columns] pixels; either may be null, not both) and the sample table: n_samples directions in the tangent
@@ -314,8 +334,12 @@ uint32_t coverage_mask_words(uint32_t tiles_x, uint32_t tiles_y);
 int launch_coverage(const CoverageFrame& F, const DevClusterBox* boxes, uint32_t n_boxes, uint32_t* mask, void* stream);
 // A region of a frame (render.hip: launch_region), for Params = VisParams (visibility_kernel: the visibility planes), SurfaceParams (surface_kernel: the surface
 // planes and any visibility planes), ShadeParams (shade_kernel: the pixels from kept planes) and AmbientParams (ambient_kernel: occlusion masks and grey pixels from
-// kept planes).  Defined and instantiated for these four in render.hip.
+// kept planes) and RenderRegionParams (render_region_kernel: the pixels by the fused frame body).  Defined and instantiated for these five in render.hip.
 template <class Params> int launch_region(const DevScene& s, const Params& q, void* stream, int walk);
+// The tiles of a device-resident list (render.hip: render_tile_list_kernel): four blocks per entry of q.n, the frame kernels' quadrants; q.n == 0 launches nothing.
+// kMaxTileList: HIP refuses a launch of more than 2^32 - 1 threads in a grid dimension, and an entry takes 4 blocks of 64.
+constexpr uint32_t kMaxTileList = 0xFFFFFFFFu / 256u;
+int launch_tile_list(const DevScene& s, const TileListParams& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
 // The seven per-ray launchers (render.hip: each is launch_per_ray with its kernel): one lane per ray, 64 rays per block; n == 0 launches nothing.
 // d_count: null, or the bound of a counted launch (rrt.h: COUNTED DEVICE FORMS) -- one uint32 in device memory, read by the kernel when it runs; the grid is that of n.

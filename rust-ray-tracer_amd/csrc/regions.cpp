@@ -1,5 +1,5 @@
 // regions.cpp -- regions of a frame behind include/rrt.h: visibility and surface buffers, frames shaded and ambient occlusion from kept buffers, the pick of one
-// pixel.  The calls share one check of the region (host_planes.hpp: region_in_force), one launch (launch_region_frame) and, for their host forms, the routine that
+// pixel, the fused frame of a region and of a list of tiles in device memory.  The calls share one check of the region (host_planes.hpp: region_in_force), one launch (launch_region_frame) and, for their host forms, the routine that
 // carves the kept device allocation and copies the planes up and down (launches.hpp: with_kept_planes) over the mirrored structs (host_planes.hpp: mirror_planes).
 #include <cmath>
 #include <cstring>
@@ -160,6 +160,49 @@ void shade_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const r
     });
 }
 
+// ---- the fused frame of a region.  every check, before any GPU work; returns the region in force and, through `pitch`, the pitch in force (0: the region's width)
+rrt_region check_render_region(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const void* out, uint32_t& pitch) {
+    check_frame(rt, width, height);
+    if (!out) throw Error{RRT_ERR_INVALID_ARG, "null output"};
+    const rrt_region r = region_in_force(width, height, region);
+    if (pitch == 0) pitch = r.w;
+    if (pitch < r.w) throw Error{RRT_ERR_INVALID_ARG, "pitch is smaller than the region's width (0 = the region's width)"};
+    return r;
+}
+
+// the pixels of region r (checked) into rows of `pitch` elements from d_out
+void launch_render_region_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, uint32_t* d_out, uint32_t pitch, void* stream) {
+    RenderRegionParams q{};
+    q.V = vis_params(rt, width, height, r, rrt_visibility{});            // (the kernel writes no plane)
+    q.out = d_out; q.pitch = pitch;
+    launch_region_frame(rt, width, height, r, q, stream);
+}
+
+// Host form: the region's pixels, tight in the kept allocation, down into the caller's rows.  A tight `out` is a plane like any other; rows with a gap are only
+// carved, and come down row by row in one strided copy behind the launch, so the gap is never written.
+void render_region_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, uint32_t* out, uint32_t pitch) {
+    DeviceGuard guard(rt->device);
+    const bool tight = pitch == r.w;
+    HostPlane pl[1] = {HostPlane{out, sizeof(uint32_t), (size_t)r.w * r.h, tight ? kDown : kCarve}};
+    with_kept_planes(rt, pl, [&](void* stream) {
+        launch_render_region_frame(rt, width, height, r, static_cast<uint32_t*>(pl[0].dev), r.w, stream);
+        if (!tight) HIP_TRY(hipMemcpy2DAsync(out, sizeof(uint32_t) * (size_t)pitch, pl[0].dev, sizeof(uint32_t) * (size_t)r.w, sizeof(uint32_t) * (size_t)r.w, r.h,
+                                             hipMemcpyDeviceToHost, (hipStream_t)stream));
+    });
+}
+
+// ---- the fused frame of a tile list in device memory.  Nothing of the list is read here: the kernel reads it, and the bound, when it runs.
+static_assert(kMaxTileList == RRT_MAX_TILE_LIST, "rrt.h names the launch bound of a tile list");
+void launch_tile_list_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles, uint32_t* d_fb, void* stream) {
+    TileListParams q{};
+    q.F = frame_params(rt, width, height, 0, 1, false);
+    q.F.xcd_chunk = 0;                                                   // the caller's order is the schedule
+    q.tiles = d_tiles; q.count = d_count; q.n = n; q.out = d_fb;
+    const int variant = visibility_variant(rt, width, height);
+    timed_launch(rt, stream, [&] { return launch_tile_list(rt->scene, q, stream, variant); });
+    record(rt, width, height, 0, variant);                               // (the library does not know which tiles the list names)
+}
+
 // every check of a frame's call, before any GPU work; returns the region in force
 rrt_region check_ambient(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* planes, const rrt_ambient_samples* samples,
                          const rrt_ambient* out) {
@@ -251,6 +294,37 @@ int rrt_shade_surface(rrt_raytracer* rt, uint32_t width, uint32_t height, const 
     return guarded([&]() -> int {
         const rrt_region r = check_shade(rt, width, height, region, vis, planes, out_fb);
         shade_from_host(rt, width, height, r, *vis, *planes, out_fb);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_region_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t* d_out, uint32_t pitch, void* stream) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_render_region(rt, width, height, region, d_out, pitch);
+        DeviceGuard guard(rt->device);
+        launch_render_region_frame(rt, width, height, r, d_out, pitch, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_region(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, uint32_t* out, uint32_t pitch) {
+    return guarded([&]() -> int {
+        const rrt_region r = check_render_region(rt, width, height, region, out, pitch);
+        render_region_to_host(rt, width, height, r, out, pitch);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles, uint32_t* d_fb,
+                                void* stream) {
+    return guarded([&]() -> int {
+        check_frame(rt, width, height);
+        if (!d_fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
+        if (n > kMaxTileList) throw Error{RRT_ERR_INVALID_ARG, "the list is longer than RRT_MAX_TILE_LIST entries: its grid would not fit a launch"};
+        if (n == 0) return RRT_OK;                                         // nothing is launched, rrt_last_stats stays as it was
+        if (!d_tiles) throw Error{RRT_ERR_INVALID_ARG, "null tile list"};
+        DeviceGuard guard(rt->device);
+        launch_tile_list_frame(rt, width, height, n, d_count, d_tiles, d_fb, stream);
         return RRT_OK;
     });
 }

@@ -2138,7 +2138,73 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevSce
     if (Q.grey && sub == 0) Q.grey[pixel_i] = traced ? ((510u * open + 4u * n_samples) / (8u * n_samples)) * 0x010101u : 0u;
 }
 
-// For the region launchers below: the kernel that takes a parameter type (device_scene.hpp: VisParams, SurfaceParams, ShadeParams, AmbientParams).
+// The fused frame of a region (rrt.h: rrt_render_region_device): the colour of every pixel of a region of the frame, as render_kernel computes it -- the primary
+// walk, the lights, the reflection chain and the unwind in one body, trace_colour's, nothing kept in memory on the way.  Waves, rays and region are
+// visibility_kernel's (lanes outside the region or the traced area take part in no walk); the mix and the guard of the store are shade_kernel's.  The pixel goes
+// to its place in rows of Q.pitch elements: with pitch = the frame's width and `out` at the region's first pixel, into a whole framebuffer.  Nothing outside the
+// region's pixels is read or written.  No coverage mask: the mask is indexed by the whole frame's block order.  No lane leaves before the walk.
+// Registers, scratch and occupancy are recorded beside render_kernel's, not tuned: profiles/region_render_kernel_resources.txt.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void render_region_kernel(const DevScene S, const RenderRegionParams Q) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t lane = threadIdx.x;
+    const Stack stk{lds + kParkBytes, lane};
+    const VisParams& P = Q.V;
+    const RegionLane L = region_lane(P, lane);
+    const uint32_t sub = L.sub;
+    const bool in_region = L.in_region, traced = L.traced;
+    const V3 dir = primary_direction(P.F, L.px, L.py, sub);
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const uint32_t c = trace_colour<kWalk, kGroups, true>(PROF_ARG S, stk, traced, ld3(S.origin), dir);
+    // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
+    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
+    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
+    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
+    const uint32_t mixed = traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;   // 0 as Canvas::new where nothing is traced
+    if (sub == 0 && in_region) Q.out[(size_t)(L.py - P.F.row_begin) * Q.pitch + (L.px - P.col_begin)] = mixed;
+}
+
+// The fused frame of a list of tiles (rrt.h: rrt_render_tile_list_device): block b renders quadrant (b & 3) of the tile that entry (b >> 2) of a list in device
+// memory names, into its place in the whole framebuffer.  The bound -- min(n, *count), counted_length's rule; n without a count -- and the entry are
+// wave-uniform: scalar loads, only ever read.  A block at or beyond the bound leaves after that load and a compare, before it touches LDS or memory and without
+// reading its entry; an entry that names no tile of the frame (0xFFFFFFFF included) is skipped by the whole wave, before it is used as an index.  From (tx, ty)
+// on it is render_kernel's pixel arithmetic on the whole frame and the body of render_region_kernel.  Two blocks of a duplicate entry store the same bits.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void render_tile_list_kernel(const DevScene S, const TileListParams Q) {
+    const uint32_t entry = blockIdx.x >> 2, quad = blockIdx.x & 3u;
+    uint32_t m = Q.n;
+    if (Q.count) { const uint32_t c = *Q.count; m = c < m ? c : m; }                  // wave-uniform: a kernel-argument pointer
+    if (entry >= m) return;
+    const FrameParams& F = Q.F;
+    const uint32_t tile = Q.tiles[entry];                                              // wave-uniform too
+    if (tile >= F.tile_end) return;                                                    // (tile_end = tiles_x * tiles_y: the whole frame)
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const uint32_t lane = threadIdx.x;
+    const Stack stk{lds + kParkBytes, lane};
+    const uint32_t pix = lane >> 2, sub = lane & 3u;
+    const uint32_t tx = tile % F.tiles_x, ty = tile / F.tiles_x;
+    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
+    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
+    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
+    const bool in_fb = (int32_t)px < W && (int32_t)py < H;
+    const bool traced = in_fb && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;
+    const V3 dir = primary_direction(F, px, py, sub);
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const uint32_t c = trace_colour<kWalk, kGroups, true>(PROF_ARG S, stk, traced, ld3(S.origin), dir);
+    // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
+    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
+    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
+    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
+    const uint32_t mixed = traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;   // 0 as Canvas::new where nothing is traced
+    if (sub == 0 && in_fb) Q.out[(size_t)py * F.width + px] = mixed;
+}
+
+// For the region launchers below: the kernel that takes a parameter type (device_scene.hpp: VisParams, SurfaceParams, ShadeParams, AmbientParams, RenderRegionParams).
+template <int kWalk, bool kGroups> auto region_kernel(const RenderRegionParams&) { return &render_region_kernel<kWalk, kGroups>; }
 template <int kWalk, bool kGroups> auto region_kernel(const VisParams&) { return &visibility_kernel<kWalk, kGroups>; }
 template <int kWalk, bool kGroups> auto region_kernel(const SurfaceParams&) { return &surface_kernel<kWalk, kGroups>; }
 template <int kWalk, bool kGroups> auto region_kernel(const ShadeParams&) { return &shade_kernel<kWalk, kGroups>; }
@@ -2514,6 +2580,7 @@ inline int effective_walk(const DevScene& s, int walk) { return (walk == kWalkBu
 void preload_kernels_lane_ray();
 int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds, const uint32_t* d_cover);
 template <class Params> int launch_region_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+int launch_tile_list_lane_ray(const DevScene& s, const TileListParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
 void preload_kernels() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_kernel<kWalkBundle, false>));
@@ -2596,6 +2663,19 @@ template int launch_region(const DevScene&, const VisParams&, void*, int);
 template int launch_region(const DevScene&, const SurfaceParams&, void*, int);
 template int launch_region(const DevScene&, const ShadeParams&, void*, int);
 template int launch_region(const DevScene&, const AmbientParams&, void*, int);
+template int launch_region(const DevScene&, const RenderRegionParams&, void*, int);
+
+// The tiles of a list in device memory: four blocks per entry of q.n (the caller keeps q.n within kMaxTileList); the dispatch is launch_region's.
+int launch_tile_list(const DevScene& s, const TileListParams& q, void* stream, int walk) {
+    walk = effective_walk(s, walk);
+    if (q.n == 0) return 0;
+    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
+    if (walk != kWalkBundle) return launch_tile_list_lane_ray(s, q, stream, walk, q.n * 4, lds);
+    return with_groups(s, [&](auto groups) {
+        hipLaunchKernelGGL((render_tile_list_kernel<kWalkBundle, groups()>), dim3(q.n * 4), dim3(64), lds, (hipStream_t)stream, s, q);
+        return (int)hipGetLastError();
+    });
+}
 
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
     const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
@@ -2635,6 +2715,15 @@ template int launch_region_lane_ray(const DevScene&, const VisParams&, void*, in
 template int launch_region_lane_ray(const DevScene&, const SurfaceParams&, void*, int, uint32_t, uint32_t);
 template int launch_region_lane_ray(const DevScene&, const ShadeParams&, void*, int, uint32_t, uint32_t);
 template int launch_region_lane_ray(const DevScene&, const AmbientParams&, void*, int, uint32_t, uint32_t);
+template int launch_region_lane_ray(const DevScene&, const RenderRegionParams&, void*, int, uint32_t, uint32_t);
+int launch_tile_list_lane_ray(const DevScene& s, const TileListParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+    return with_lane_or_ray_walk(walk, [&](auto w) {
+        return with_groups(s, [&](auto groups) {
+            hipLaunchKernelGGL((render_tile_list_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
+            return (int)hipGetLastError();
+        });
+    });
+}
 #endif   // RRT_TU_LANE
 
 #if RRT_TU_RAYS
