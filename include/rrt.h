@@ -86,9 +86,14 @@ typedef struct { const uint8_t *rgb; uint32_t width, height; } rrt_texture;
 #define RRT_FLAG_NO_SPECULAR_SKIP (1u << 6)    /* 64; a developer switch like the one above */
 /* Coverage pass: in front of every WHOLE frame of one GPU (rrt_render_device, rrt_render) a small kernel projects the padded box of
  * every triangle onto the frame and marks the 4x4-pixel waves it can reach; a wave no box reaches stores WHITE and walks nothing.  The pass runs again in
- * every frame, on the frame's stream and inside its timing (rrt_stats.kernel_ms): nothing is kept between frames, so the setters need no care.  Same
- * results; it is off by itself wherever the index's exactness guarantee is not in force for every primary ray (rrt_raytracer_get_coverage_info says
- * why), and for a rank's tiles and progressive frames.  This flag turns it off (tests, A/B timing). */
+ * every frame, from the camera and scene in force at the call: nothing is kept between frames, so the setters need no care.  Where it runs is scheduling
+ * alone.  If the frame's stream still has work when the frame is enqueued (a host that enqueues frames without waiting for each), the pass runs on a side
+ * stream of the raytracer -- non-blocking, of the device's highest priority -- beside that work, and the frame's kernel waits for it behind an event: stream
+ * order as the caller sees it is unchanged, the frame is complete when its stream says so.  If the stream is idle (a first frame, rrt_render), the pass goes
+ * in front of the frame's kernel on that stream.  rrt_stats.kernel_ms covers what the frame's stream was held for: the wait for the mask -- the whole pass
+ * on an idle stream, next to nothing in a sequence -- plus the kernel.  Same results; the pass is off by itself wherever the index's exactness guarantee is
+ * not in force for every primary ray (rrt_raytracer_get_coverage_info says why), and for a rank's tiles and progressive frames.  This flag turns it off
+ * (tests, A/B timing). */
 #define RRT_FLAG_NO_COVERAGE (1u << 7)         /* 128; a developer switch like the two above */
 #define RRT_FLAG_COVERAGE_ALWAYS (1u << 8)     /* 256; a developer switch: the pass also runs where it is judged not to pay (RRT_COVERAGE_OFF_SMALL_FRAME); tests and timing at small sizes */
 
@@ -108,7 +113,8 @@ typedef struct {
 } rrt_model_info;
 
 typedef struct {
-    double   kernel_ms;               /* HIP-event time of the last render's trace kernel on its stream */
+    double   kernel_ms;               /* HIP-event time of the last render's trace kernel on its stream; for a whole frame with a coverage pass: the time the
+                                         frame held that stream -- any wait for the mask, then the kernel (see RRT_FLAG_NO_COVERAGE) */
     uint32_t width, height;
     uint64_t rays_primary;            /* 4 * pixels actually traced */
     uint64_t scene_bytes;             /* bytes resident in HBM for this raytracer (geometry+octree+textures) */

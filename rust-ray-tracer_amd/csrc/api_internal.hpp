@@ -60,12 +60,19 @@ struct rrt_raytracer {
     uint64_t built_bytes = 0;
     rrt::BuildMemory update_mem;
     // Coverage pass of whole single-GPU frames (frames.cpp: launch_whole_frame; coverage.hip).  A buffer is a place for ONE frame's mask: cleared, filled and read by
-    // that frame's own launches; nothing in it outlives the frame, and nothing here describes a scene or a camera.  `done` is recorded behind the render_kernel that
-    // read the mask, on `stream`: a frame on another stream takes the buffer only once that event has completed.  Several frames of one handle may be in flight on
-    // different streams, hence a small pool; a frame that finds no free buffer renders without a mask.
-    struct CoverBuf { rrt::KeptBuf mask; rrt::HipOwned<hipEvent_t, hipEventDestroy> done; void* stream = nullptr; bool used = false; };
+    // that frame's own launches; nothing in it outlives the frame, and nothing here describes a scene or a camera.  Two events order its use:
+    //   side stream (cover_stream):  [wait for `done` of the buffer's last frame, if that is still in flight]  clear, coverage_kernel, record `ready`
+    //   caller's stream `stream`:    wait for `ready`, render_kernel, record `done`
+    // so that the pass of a frame runs beside the render_kernel of the frame before it, which reads ANOTHER buffer: a stream alternates between two (cover_pool.hpp
+    // has the choice; `age` is its launch counter).  A frame whose stream is idle at the call has nothing to run beside: its pass goes in front of render_kernel on the
+    // caller's stream, with neither the side stream nor `ready`.  Several frames of one handle may be in flight on different streams, hence a small pool; a frame that
+    // finds no buffer renders without a mask.  All of them share the ONE side stream, which runs in order: a pass that waits for its stream's `done` also holds back
+    // the passes of other caller streams enqueued behind it (correct, but it couples streams that are otherwise independent; not measured).  The host never waits for an event here; rrt_raytracer_destroy waits for every `done` before the events and the stream go.
+    struct CoverBuf { rrt::KeptBuf mask; rrt::HipOwned<hipEvent_t, hipEventDestroy> done, ready; void* stream = nullptr; bool used = false; uint64_t age = 0; };
     static constexpr int kCoverBufs = 8;
     CoverBuf cover[kCoverBufs];
+    uint64_t cover_clock = 0;        // whole frames that took a buffer so far (CoverBuf::age)
+    rrt::OwnedStream cover_stream;   // the side stream of the pass: non-blocking, of the highest priority the device offers; created by the first frame that overlaps
     int cover_last = -1;             // the buffer of the last whole frame, or -1: it ran without a mask ...
     uint32_t cover_off = RRT_COVERAGE_OFF_NO_FRAME;   // ... for this reason (RRT_COVERAGE_OFF_*; RRT_COVERAGE_ON with a buffer)
     uint32_t cover_tiles_x = 0, cover_tiles_y = 0;   // the tiles of that frame (rrt_raytracer_get_coverage_info counts its waves on request)

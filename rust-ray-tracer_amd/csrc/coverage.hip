@@ -1,6 +1,8 @@
 // coverage.hip -- the coverage pass of a whole frame: one bit per 4x4-pixel wave of render_kernel, set when some padded triangle box of the scene can reach
-// the wave (coverage_rule.hpp has the rule, its margin and why a cleared bit means sixteen WHITE pixels).  One small kernel in front of
-// every whole single-GPU frame, on the frame's stream and inside its two events; nothing is kept from one frame to the next.  Plain flags: no traversal here.
+// the wave (coverage_rule.hpp has the rule, its margin and why a cleared bit means sixteen WHITE pixels).  One small kernel for every whole
+// single-GPU frame, computed anew from the camera and scene in force at the frame's call; nothing is kept from one frame to the next.  Where it runs is the host's
+// choice (frames.cpp: launch_whole_frame): in front of render_kernel on the frame's stream when that stream is idle, else on the raytracer's side stream, beside
+// the frame before, with the frame's render_kernel behind an event -- then outside the frame's two events.  Plain flags: no traversal here.
 #include <hip/hip_runtime.h>
 
 #include <atomic>

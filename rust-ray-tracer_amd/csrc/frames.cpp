@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "cover_pool.hpp"
 #include "coverage_rule.hpp"
 #include "launches.hpp"
 
@@ -77,8 +78,9 @@ using namespace rrt;
 // ---- the coverage pass (coverage.hip, coverage_rule.hpp).
 // Whether the frame f may run with a coverage mask: RRT_COVERAGE_ON and F filled, or the reason why not.  The mask rests on the guarantee the index rests on -- a
 // pair the reference accepts lies inside the triangle's padded box -- so it is off wherever that guarantee is not in force for every primary ray.
-// It is also off where it cannot pay (RRT_FLAG_COVERAGE_ALWAYS lifts these two bounds: tests and timing at small sizes).  The pass costs about 20 us whatever the frame
-// (a clear, a kernel of one lane per box, two more dispatches) and more with the number of boxes; what it saves grows with the waves it proves empty.
+// It is also off where it cannot pay (RRT_FLAG_COVERAGE_ALWAYS lifts these two bounds: tests and timing at small sizes).  The pass costs an isolated frame about 20 us
+// whatever its size (a clear, a kernel of one lane per box, two more dispatches) and more with the number of boxes; what it saves grows with the waves it proves empty.
+// In a sequence of frames the pass runs beside the frame before (launch_whole_frame), but the library cannot know that a frame is not isolated: the bounds stay.
 //  * Waves.  Measured on the teapot (profiles/coverage_ab.txt): 640 x 480 = 19 200 waves lost 7.5 us, 1920 x 1080 = 129 600 waves gains 24 us; the line through the
 //    two crosses zero at about 45 000 waves, and nothing in between was measured: on from 49 152 waves (1024 x 768).
 //  * Boxes per wave.  The fullest case measured is the 1 M soup at 3840 x 2160, two list slots per wave: no difference beyond the runs' range.  Beyond four slots per
@@ -102,37 +104,85 @@ uint32_t coverage_state(const rrt_raytracer* rt, const FrameParams& f, CoverageF
     if (!coverage_frame(F, f.width, f.height, f.x_scale, f.y_scale, f.z_value, f.right, f.up, f.forward, S.origin)) return RRT_COVERAGE_OFF_CAMERA;
     return RRT_COVERAGE_ON;
 }
-// A buffer for the mask of a frame on `stream`: the one this stream used last (stream order protects it), else one whose last frame has completed, else one never
-// used; -1 when all kCoverBufs are busy on other streams.  Allocates only when a buffer is new or a larger frame comes.
-int take_cover_buffer(rrt_raytracer* rt, size_t bytes, void* stream) {
-    int pick = -1;
-    for (int i = 0; i < rrt_raytracer::kCoverBufs && pick < 0; i++) if (rt->cover[i].used && rt->cover[i].stream == stream) pick = i;
-    for (int i = 0; i < rrt_raytracer::kCoverBufs && pick < 0; i++) {
-        if (!rt->cover[i].used) pick = i;
-        else if (hipEventQuery(rt->cover[i].done.h) == hipSuccess) pick = i;
-        else (void)hipGetLastError();                                      // (hipErrorNotReady: its frame is still in flight)
+// A buffer for the mask of a frame on `stream`, by the rule of cover_pool.hpp: a free one of this stream, else (while the stream holds fewer than two) one never used or a
+// free one of another stream, else the stream's own least recently used one with `wait` set -- the caller enqueues the pass behind that buffer's `done`; index -1 when
+// the stream holds none and all kCoverBufs are busy on other streams.  The host waits for nothing.  Allocates only when a buffer is new or a larger frame comes.
+CoverPick take_cover_buffer(rrt_raytracer* rt, size_t bytes, void* stream) {
+    CoverSlot slots[rrt_raytracer::kCoverBufs];
+    for (int i = 0; i < rrt_raytracer::kCoverBufs; i++) {
+        const rrt_raytracer::CoverBuf& b = rt->cover[i];
+        slots[i] = CoverSlot{b.stream, b.used, false, b.age};
+        if (!b.used) continue;
+        slots[i].completed = hipEventQuery(b.done.h) == hipSuccess;
+        if (!slots[i].completed) (void)hipGetLastError();                     // (hipErrorNotReady: its frame is still in flight)
     }
-    if (pick < 0) return -1;
-    rrt_raytracer::CoverBuf& b = rt->cover[pick];
+    const CoverPick pick = pick_cover_buffer(slots, rrt_raytracer::kCoverBufs, stream);
+    if (pick.index < 0) return pick;
+    rrt_raytracer::CoverBuf& b = rt->cover[pick.index];
     if (!b.done.h) HIP_TRY(hipEventCreateWithFlags(&b.done.h, hipEventDisableTiming));
-    b.mask.at_least(bytes);
-    b.stream = stream; b.used = true;
+    if (!b.ready.h) HIP_TRY(hipEventCreateWithFlags(&b.ready.h, hipEventDisableTiming));
+    b.mask.at_least(bytes);                                                   // (a buffer that grows is freed first, and hipFree waits for the device: nothing reads it then)
+    b.stream = stream; b.used = true; b.age = ++rt->cover_clock;
     return pick;
 }
-// One WHOLE frame of one GPU (f.world == 1, every tile, every row) on `stream`: clear, coverage kernel and render_kernel in stream order, or render_kernel alone where
-// the mask is off.  Every frame pays the pass again: nothing is kept from the frame before.  Called inside timed_launch, so kernel_ms includes the pass.
-int launch_whole_frame(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void* stream, int variant) {
+// The side stream of the pass, created by the first frame that has something to run beside.  Non-blocking: callers use the null stream, and a blocking stream would
+// synchronise with it.  Of the highest priority the device offers, so that the pass's 25 blocks are not queued behind the 32 400 of the frame before it.
+hipStream_t cover_stream(rrt_raytracer* rt) {
+    if (!rt->cover_stream.h) {
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));          // (numerically lower is higher; both 0 where the device has no priorities)
+        HIP_TRY(hipStreamCreateWithPriority(&rt->cover_stream.h, hipStreamNonBlocking, greatest));
+    }
+    return rt->cover_stream.h;
+}
+// Whether `stream` still has work: launch_whole_frame's `beside`.  Asked BEFORE timed_launch puts its first event on the stream -- behind that record every stream
+// looks busy for some microseconds.
+bool stream_busy(void* stream) {
+    if (hipStreamQuery((hipStream_t)stream) == hipSuccess) return false;
+    (void)hipGetLastError();                                                // (hipErrorNotReady: the frame before is still in flight)
+    return true;
+}
+// One WHOLE frame of one GPU (f.world == 1, every tile, every row) for `stream`: the pass (clear, coverage kernel) and render_kernel, or render_kernel alone where the
+// mask is off.  Every frame pays the pass again: nothing is kept from the frame before.  But the pass reads nothing that the frame before produces, so where the
+// caller's stream still has work at the call -- a sequence of frames enqueued without waiting -- it runs on the side stream, beside that work:
+//   side stream:      [wait for `done` of the buffer's last frame]  clear, coverage_kernel, record `ready`
+//   caller's stream:  wait for `ready`, render_kernel, record `done`
+// With two buffers per stream the pass of frame k+1 waits for frame k-1 at most: it starts when render_kernel of frame k-1 ends, runs while the caller's stream works
+// through the events between two frames, and ends about when render_kernel of frame k starts (profiles/coverage_overlap_ab.txt; a pass that starts INSIDE a
+// render_kernel is starved of wave slots until that kernel's tail, whatever the side stream's priority -- measured, and one more reason for the wait on `done`).
+// Where the caller's stream is idle (`beside` false: a first frame, the blocking rrt_render, tune_variant's counted launches) there is nothing to run beside, and the
+// pass goes in front of render_kernel on the caller's stream as one stream order: an isolated frame pays no dependency across streams.  Called inside timed_launch:
+// kernel_ms is the time the frame held the caller's stream -- the wait for the mask, which is the whole pass on an idle stream and next to nothing in a sequence,
+// plus render_kernel.
+// A call that fails halfway (the catch below) still leaves `done` behind whatever it enqueued that touches the buffer: the pool must not hand out as free a buffer
+// that the side stream is still writing.
+int launch_whole_frame(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void* stream, int variant, bool beside) {
     CoverageFrame F;
     rt->cover_last = -1;
     rt->cover_off = coverage_state(rt, f, F);
     if (rt->cover_off != RRT_COVERAGE_ON) return launch_render(rt->scene, f, d_out, stream, variant);
-    const int i = take_cover_buffer(rt, sizeof(uint32_t) * ((size_t)coverage_mask_words(F.tiles_x, F.tiles_y) + 1), stream);
-    if (i < 0) { rt->cover_off = RRT_COVERAGE_OFF_POOL; return launch_render(rt->scene, f, d_out, stream, variant); }
-    uint32_t* const mask = static_cast<uint32_t*>(rt->cover[i].mask.mem.h);
-    HIP_TRY((hipError_t)launch_coverage(F, rt->scene.tboxes, rt->built.n_list_slots, mask, stream));
-    HIP_TRY((hipError_t)launch_render(rt->scene, f, d_out, stream, variant, mask));
-    HIP_TRY(hipEventRecord(rt->cover[i].done.h, (hipStream_t)stream));
-    rt->cover_last = i; rt->cover_tiles_x = F.tiles_x; rt->cover_tiles_y = F.tiles_y;
+    const CoverPick pick = take_cover_buffer(rt, sizeof(uint32_t) * ((size_t)coverage_mask_words(F.tiles_x, F.tiles_y) + 1), stream);
+    if (pick.index < 0) { rt->cover_off = RRT_COVERAGE_OFF_POOL; return launch_render(rt->scene, f, d_out, stream, variant); }
+    rrt_raytracer::CoverBuf& b = rt->cover[pick.index];
+    uint32_t* const mask = static_cast<uint32_t*>(b.mask.mem.h);
+    const hipStream_t frame_stream = (hipStream_t)stream;
+    const hipStream_t pass_stream = beside ? cover_stream(rt) : frame_stream;
+    hipStream_t last_user = pass_stream;                                     // the stream behind whose work `done` has to lie if the call ends here
+    try {
+        if (pick.wait) HIP_TRY(hipStreamWaitEvent(pass_stream, b.done.h, 0));
+        HIP_TRY((hipError_t)launch_coverage(F, rt->scene.tboxes, rt->built.n_list_slots, mask, pass_stream));
+        if (beside) {
+            HIP_TRY(hipEventRecord(b.ready.h, pass_stream));
+            HIP_TRY(hipStreamWaitEvent(frame_stream, b.ready.h, 0));
+        }
+        last_user = frame_stream;                                            // (render_kernel lies behind the pass: stream order, or `ready`)
+        HIP_TRY((hipError_t)launch_render(rt->scene, f, d_out, stream, variant, mask));
+        HIP_TRY(hipEventRecord(b.done.h, frame_stream));
+    } catch (...) {
+        if (hipEventRecord(b.done.h, last_user) != hipSuccess) (void)hipGetLastError();   // (best effort; the error that is reported is the first one)
+        throw;
+    }
+    rt->cover_last = pick.index; rt->cover_tiles_x = F.tiles_x; rt->cover_tiles_y = F.tiles_y;
     return 0;
 }
 // The mask of the last frame (rt->cover_last >= 0) in host memory, coverage_mask_words words: waits for that frame and copies.  The bits of the last word beyond
@@ -159,7 +209,8 @@ void tune_variant(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out, void
     rt->size_measured = true;
     if (f.world == 1) {
         rt->walk = fastest_variant([&](int variant) {
-            timed_launch(rt, stream, [&] { return launch_whole_frame(rt, f, d_out, stream, variant); });   // (as the frames will run: with the coverage pass)
+            const bool beside = stream_busy(stream);                       // (false in every counted run: elapsed_ms has waited for the one before)
+            timed_launch(rt, stream, [&] { return launch_whole_frame(rt, f, d_out, stream, variant, beside); });   // (as the frames will run: with the coverage pass)
             return elapsed_ms(rt);
         });
         return;
@@ -186,8 +237,9 @@ void launch_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t r
     DeviceGuard guard(rt->device);
     const FrameParams f = frame_params(rt, width, height, rank, world, tiled);
     tune_variant(rt, f, static_cast<uint32_t*>(d_out), stream);
+    const bool beside = world == 1 && stream_busy(stream);                 // whether a whole frame's coverage pass has something to run beside (launch_whole_frame)
     timed_launch(rt, stream, [&] {
-        if (world == 1) return launch_whole_frame(rt, f, static_cast<uint32_t*>(d_out), stream, rt->walk);
+        if (world == 1) return launch_whole_frame(rt, f, static_cast<uint32_t*>(d_out), stream, rt->walk, beside);
         rt->cover_last = -1; rt->cover_off = RRT_COVERAGE_OFF_NOT_WHOLE;   // a rank's tiles: no mask
         return launch_render(rt->scene, f, static_cast<uint32_t*>(d_out), stream, rt->walk);
     });

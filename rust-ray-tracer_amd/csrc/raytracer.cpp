@@ -317,6 +317,10 @@ void rrt_raytracer_destroy(rrt_raytracer* rt) {
     const bool have_device = hipGetDevice(&prev) == hipSuccess;
     if (have_device) {
         (void)hipSetDevice(rt->device);
+        // Frames in flight: every mask buffer's last frame is waited for (its `done` lies behind its `ready`, so the side stream of the pass is idle then too)
+        // before the events, the side stream and the buffers go with the raytracer below.
+        for (const rrt_raytracer::CoverBuf& b : rt->cover) if (b.used && b.done.h) (void)hipEventSynchronize(b.done.h);
+        if (rt->cover_stream.h) (void)hipStreamSynchronize(rt->cover_stream.h);
         if (rt->ev0) (void)hipEventDestroy(rt->ev0);
         if (rt->ev1) (void)hipEventDestroy(rt->ev1);
     }
