@@ -467,10 +467,72 @@ int rrt_render_region(rrt_raytracer *rt, uint32_t width, uint32_t height, const 
  * Traversal variant and tuning state as for a region.  rrt_last_stats: kernel_ms and filter_variant of this launch, width / height = the frame size,
  * rays_primary = 0 -- the library does not read the list.  No coverage pass.
  * RRT_ERR_INVALID_ARG, before any GPU work: NULL rt, a bad frame size, NULL d_fb, n > RRT_MAX_TILE_LIST, NULL d_tiles with n > 0.
- * There is no host form: a host that knows its tiles has regions. */
+ * There is no host form: a host that knows its tiles has regions.
+ * PRODUCER.  rrt_select_tiles_device below writes such a list and its count from planes in device memory, on the same stream: d_tiles and d_count of this call
+ * are its outputs, n its n_tiles; rrt_mark_tiles_device is its first half, for a caller that compacts the marks itself. */
 #define RRT_MAX_TILE_LIST 16777215u   /* (2^32 - 1) / 256 */
 int rrt_render_tile_list_device(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t *d_count,
                                 const uint32_t *d_tiles, uint32_t *d_fb, void *stream);
+
+/* Tile selection on the device: tests over planes of a frame that produce the list rrt_render_tile_list_device reads -- the tiles in which a kept plane shows
+ * what an edit touches, the tiles in which two frames differ, the tiles that are not empty -- with no read-back and no synchronisation.
+ * TILES.  Numbered as rrt_render_tile_list_device numbers them: ty * tiles_x + tx, tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8; n_tiles = tiles_x * tiles_y.
+ * PLANES.  a (and b) hold [region.h][region.w][per_pixel] elements of elem_bytes, tight, for the region in force (NULL = the whole frame): per_pixel 1 is a
+ * framebuffer, 4 a sub-sample plane of rrt_visibility / rrt_surface / rrt_ambient.  They are aligned to elem_bytes; no more is demanded.  The marks overlap no plane.
+ * ELEMENTS.  An element is read as an UNSIGNED INTEGER of elem_bytes (1, 4 or 8); no floating-point comparison happens anywhere: -0.0 is not zero and differs
+ * from 0.0, a NaN equals itself (same payload) and differs from another.
+ *   RRT_TILE_NONZERO   x != 0
+ *   RRT_TILE_RANGE     lo <= x < hi                                 (elem_bytes 4)
+ *   RRT_TILE_SET       x < 256 and bit (x & 31) of set[x >> 5]      (elem_bytes 4; the material plane against a set of materials)
+ *   RRT_TILE_DIFFERS   a[i] != b[i]
+ * A tile is SELECTED when any element of any of its pixels passes.  Only pixels inside both the frame and the region count -- the pixels the reference never
+ * traces (canvas row 0, row 1 of an odd height, the last column of an odd width) included: the planes hold their miss values there, a framebuffer its 0.
+ * MARKS.  marks[n_tiles], one byte per tile of the FRAME.  Without RRT_TILE_KEEP every byte is written: 1 for a selected tile, 0 for any other, a tile the region
+ * does not touch included.  With RRT_TILE_KEEP (or'ed into .test) a selected tile's byte becomes 1 and NO other byte is written: the marks already there are
+ * joined.  Bytes at or beyond n_tiles are never touched.
+ * rrt_select_tiles*: tests[0, n_tests) in order into the marks -- tests[0] as given, every later one as if it had RRT_TILE_KEEP: the union -- and then the
+ * compaction of rrt_compact_rays_device (RRT_SELECT_FLAG) over the marks: d_tiles[0, count) the ascending numbers of the marked tiles, 0xFFFFFFFF in
+ * d_tiles[count, n_tiles), which the tile-list kernel skips; *d_count = count.  d_tiles or d_count may be NULL, not both.  Scratch: rrt_compact_scratch_bytes(n_tiles)
+ * bytes, 4-byte aligned.  rrt_render_tile_list_device(n = n_tiles, d_count, d_tiles, ...) enqueued behind it on the same stream needs nothing from the host.
+ * WHAT THE LIBRARY DOES NOT KNOW: what an edit can reach.  A test sees what a plane holds at a pixel.  A pixel that sees an edited surface only in a mirror, that
+ * gains or loses a shadow, or whose sub-sample hits something new after a geometry edit is the caller's to include.  The worked example is a material edit:
+ * keep the `material` plane of rrt_render_surface_device, call rrt_raytracer_set_materials, select with RRT_TILE_SET holding the edited material AND every material
+ * with kr > 0 (a mirror may show the edited surface; materials do not move shadows), render the list into the old framebuffer: the result is the new frame, bit
+ * for bit.
+ * Device forms: everything but the structs in device memory of rt's device; one launch per test (and the compaction's three) enqueued on `stream` (hipStream_t,
+ * NULL = default): no allocation, no copy, no synchronisation.  A kernel enqueued before the call on the same stream may write the planes.  Not ray calls:
+ * rrt_last_stats, the tuning state and the coverage state stay as they were, as with the compaction.
+ * Host forms: everything in host memory; blocking.  One device allocation of the call's own; only what the call reads is uploaded (the marks only with
+ * RRT_TILE_KEEP), only what was asked for comes down.  rrt_select_tiles: `tiles` has room for n_tiles entries, the valid ones are tiles[0, *count); tiles or
+ * count may be NULL, not both; it has no marks of the caller's, so a RRT_TILE_KEEP of tests[0] has nothing to join and is ignored.
+ * RRT_ERR_INVALID_ARG, before any GPU work and leaving every output as it was: NULL rt, test(s) or marks; a bad frame size; a region with w == 0 or h == 0 or one
+ * that sticks out of the frame; n_tests == 0 or > RRT_MAX_TILE_TESTS; an unknown test; elem_bytes other than 1, 4 or 8; per_pixel other than 1 or 4; RANGE or SET
+ * with elem_bytes != 4; a NULL a, a NULL b for DIFFERS; a plane not aligned to elem_bytes; n_tiles > RRT_MAX_TILE_LIST; both list outputs NULL; a scratch that is
+ * NULL or smaller than rrt_compact_scratch_bytes(n_tiles).
+ * Not covered: growing a selection by a ring of tiles, a schedule-aware order of the list, a test on the coverage mask, counted forms, the rrt_multi_* path. */
+enum { RRT_TILE_NONZERO = 0, RRT_TILE_RANGE = 1, RRT_TILE_SET = 2, RRT_TILE_DIFFERS = 3 };
+#define RRT_TILE_KEEP      0x100u   /* or'ed into .test: join the marks already there */
+#define RRT_MAX_TILE_TESTS 8
+typedef uint32_t rrt_tile_set[8];   /* 256 bits: bit (x & 31) of word x >> 5 stands for the value x */
+typedef struct {
+    uint32_t test;          /* one of the four, optionally | RRT_TILE_KEEP */
+    uint32_t elem_bytes;    /* 1, 4 or 8 */
+    uint32_t per_pixel;     /* 1 (a framebuffer) or 4 (a sub-sample plane) */
+    uint32_t lo, hi;        /* RANGE */
+    rrt_tile_set set;       /* SET: uint32_t set[8] */
+    uint32_t _pad;
+    const void *a, *b;      /* planes [region.h][region.w][per_pixel]; b: DIFFERS only */
+} rrt_tile_test;            /* 72 bytes */
+
+int rrt_mark_tiles_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                          const rrt_tile_test *test, uint8_t *d_marks, void *stream);
+int rrt_mark_tiles(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                   const rrt_tile_test *test, uint8_t *marks);
+int rrt_select_tiles_device(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                            const rrt_tile_test *tests, uint32_t n_tests, uint8_t *d_marks,
+                            uint32_t *d_tiles, uint32_t *d_count, void *d_scratch, size_t scratch_bytes, void *stream);
+int rrt_select_tiles(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
+                     const rrt_tile_test *tests, uint32_t n_tests, uint32_t *tiles, uint32_t *count);
 
 /* Screen-tile partition for N GPUs (one process per GPU): the frame is cut into 8x8-pixel tiles, tile k (row-major)
  * belongs to rank k % world.  Renders this rank's tiles into d_tiles[rrt_tiles_per_rank][64] (tile-major, device).

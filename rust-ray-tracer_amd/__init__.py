@@ -107,7 +107,14 @@ class CRaySet(C.Structure):          # rrt_ray_set, 128 bytes: host or device po
     _fields_ = [(n, C.c_void_p) for n in ("origins", "dirs", "max_t", "rot")] + [("rec", CRaySurface)]
 
 
+class CTileTest(C.Structure):        # rrt_tile_test, 72 bytes: a, b host or device pointers
+    _fields_ = [(n, C.c_uint32) for n in ("test", "elem_bytes", "per_pixel", "lo", "hi")] + [("set", C.c_uint32 * 8), ("_pad", C.c_uint32), ("a", C.c_void_p), ("b", C.c_void_p)]
+
+
 MAX_AMBIENT_SAMPLES = 32             # RRT_MAX_AMBIENT_SAMPLES
+TILE_TESTS = ("nonzero", "range", "set", "differs")   # RRT_TILE_NONZERO, RRT_TILE_RANGE, RRT_TILE_SET, RRT_TILE_DIFFERS
+TILE_KEEP = 0x100                    # RRT_TILE_KEEP, or'ed into rrt_tile_test.test
+MAX_TILE_TESTS = 8                   # RRT_MAX_TILE_TESTS
 MAX_TILE_LIST = 16777215             # RRT_MAX_TILE_LIST: the longest list render_tile_list_into takes
 SELECT_MODES = ("hit", "mirror", "flag")   # RRT_SELECT_HIT, RRT_SELECT_MIRROR, RRT_SELECT_FLAG
 DEAD_INDEX = 0xFFFFFFFF              # index of a tail slot of a compacted batch
@@ -169,7 +176,7 @@ class CSetupTimes(C.Structure):
 STRUCTS = {"rrt_vec3": Vec3, "rrt_light": CLight, "rrt_material": CMaterial, "rrt_texture": CTexture, "rrt_options": COptions, "rrt_camera": CCamera,
            "rrt_region": CRegion, "rrt_visibility": CVisibility, "rrt_pick_result": CPickResult, "rrt_surface": CSurface,
            "rrt_ambient_samples": CAmbientSamples, "rrt_ambient": CAmbient, "rrt_ray_surface": CRaySurface, "rrt_ray_shade": CRayShade, "rrt_ray_ambient": CRayAmbient,
-           "rrt_ray_set": CRaySet,
+           "rrt_ray_set": CRaySet, "rrt_tile_test": CTileTest,
            "rrt_model_info": CModelInfo, "rrt_stats": CStats, "rrt_setup_times": CSetupTimes}
 
 # every symbol include/rrt.h declares: (restype, argtypes)
@@ -215,6 +222,10 @@ SYMBOLS = {
     "rrt_render_region_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), _P, C.c_uint32, _P]),
     "rrt_render_region": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), _u32p, C.c_uint32]),
     "rrt_render_tile_list_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    "rrt_mark_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CTileTest), _P, _P]),
+    "rrt_mark_tiles": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CTileTest), _u8p]),
+    "rrt_select_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CTileTest), C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "rrt_select_tiles": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CTileTest), C.c_uint32, _u32p, _u32p]),
     "rrt_pick": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CPickResult)]),
     "rrt_tiles_per_rank": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rrt_render_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
@@ -576,6 +587,60 @@ def _select(select: str, what: str) -> int:
 def compact_scratch_bytes(n: int) -> int:
     """rrt_compact_scratch_bytes: the device scratch compact_rays_into needs for a batch of n entries."""
     return int(lib().rrt_compact_scratch_bytes(int(n)))
+
+
+def tile_count(width: int, height: int) -> tuple:
+    """(tiles_x, tiles_y) of a frame: the 8x8-pixel tiles rrt_render_tile_list_device numbers ty * tiles_x + tx"""
+    return (int(width) + 7) // 8, (int(height) + 7) // 8
+
+
+def tile_test(kind: str, a, b=None, lo: int = 0, hi: int = 0, values=(), keep: bool = False) -> CTileTest:
+    """An rrt_tile_test over the plane `a` (and `b`, for "differs"): numpy arrays for the host forms, device tensors for the _into forms, [h][w] (a framebuffer)
+    or [h][w][4] (a sub-sample plane) for the region the call names; elem_bytes is the dtype's item size (1, 4 or 8) and elements are compared as unsigned
+    integers.  kind: "nonzero" (x != 0), "range" (lo <= x < hi), "set" (x in `values`, each below 256) or "differs" (a != b).  keep: RRT_TILE_KEEP, the marks
+    already there are joined.  The struct keeps its planes alive."""
+    if kind not in TILE_TESTS:
+        raise ValueError(f"tile_test: unknown kind {kind!r}, want one of {TILE_TESTS}")
+    planes = [a] + ([b] if kind == "differs" else [])
+    if any(p is None for p in planes):
+        raise ValueError(f"tile_test: {kind!r} needs plane {'a' if a is None else 'b'}")
+    device = not isinstance(a, np.ndarray)
+    if not device:
+        planes = [np.ascontiguousarray(p) for p in planes]
+    shape = tuple(planes[0].shape)
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 4)):
+        raise ValueError(f"tile_test: a plane of shape {shape}, want [h][w] or [h][w][4]")
+    size = planes[0].element_size() if device else planes[0].dtype.itemsize
+    for p in planes:
+        if device:
+            assert getattr(p, "is_cuda", False) and p.is_contiguous(), "tile_test: a plane is neither a numpy array nor a contiguous device tensor"
+        if tuple(p.shape) != shape or (p.element_size() if device else p.dtype.itemsize) != size:
+            raise ValueError("tile_test: planes a and b differ in shape or element size")
+    if size not in (1, 4, 8) or (kind in ("range", "set") and size != 4):
+        raise ValueError(f"tile_test: {kind!r} over elements of {size} bytes, want {'4' if kind in ('range', 'set') else '1, 4 or 8'}")
+    t = CTileTest(test=TILE_TESTS.index(kind) | (TILE_KEEP if keep else 0), elem_bytes=size, per_pixel=4 if len(shape) == 3 else 1, lo=int(lo), hi=int(hi))
+    for v in values:
+        if not 0 <= int(v) < 256:
+            raise ValueError(f"tile_test: value {v} of a set, want 0 to 255")
+        t.set[int(v) >> 5] |= 1 << (int(v) & 31)
+    at = [p.data_ptr() if device else p.ctypes.data for p in planes]
+    t.a, t.b = at[0], (at[1] if len(at) == 2 else None)
+    t._planes, t._shape, t._device = planes, shape[:2], device
+    return t
+
+
+def _tile_tests(what: str, tests, w: int, h: int, device: bool):
+    """(rrt_tile_test array, count) of tile_test structs for a w x h region, all host (device False) or all device planes; the array keeps the structs alive."""
+    tests = [tests] if isinstance(tests, CTileTest) else list(tests)
+    if not 1 <= len(tests) <= MAX_TILE_TESTS:
+        raise ValueError(f"{what}: {len(tests)} tests, want 1 to {MAX_TILE_TESTS}")
+    for t in tests:
+        assert getattr(t, "_device", None) is device, f"{what}: a test's planes are {'host arrays' if device else 'device tensors'} (or the struct is not from tile_test)"
+        if t._shape != (h, w):
+            raise ValueError(f"{what}: a plane of {t._shape[0]} x {t._shape[1]} pixels for a region of {h} x {w}")
+    arr = (CTileTest * len(tests))(*tests)
+    arr._tests = tests
+    return arr, len(tests)
 
 
 def _key_mode(key: str, what: str) -> int:
@@ -1382,6 +1447,57 @@ class RayTracer(_Handle):
         if bound_t is not None:
             _device_tensor(bound_t, 1, 4, "bound")
         _call("rrt_render_tile_list_device", self._h, width, height, n, _ptr(bound_t), _ptr(tiles_t), _ptr(fb_tensor), _P(_stream(stream)))
+
+    # tile selection (rrt.h: rrt_mark_tiles, rrt_select_tiles): tests over planes that produce the list render_tile_list_into reads
+    def mark_tiles(self, test: CTileTest, width: int, height: int, region=None, marks=None) -> np.ndarray:
+        """rrt_mark_tiles: [tiles_y][tiles_x] uint8, 1 where a pixel of the tile inside the region passes `test` (tile_test over host arrays).  marks: a
+        contiguous uint8 array of that shape to write into (a test with keep joins what it holds); None: a new array of zeros."""
+        reg, w, h = _region(width, height, region)
+        tests, _ = _tile_tests("mark_tiles", test, w, h, False)
+        tx, ty = tile_count(width, height)
+        if marks is None:
+            marks = np.zeros((ty, tx), np.uint8)
+        assert isinstance(marks, np.ndarray) and marks.dtype == np.uint8 and marks.flags.c_contiguous and marks.flags.writeable and marks.size == tx * ty, \
+            f"mark_tiles: marks is not a contiguous writable uint8 array of {tx * ty} elements"
+        _call("rrt_mark_tiles", self._h, width, height, reg, tests, _u8(marks))
+        return marks
+
+    def select_tiles(self, tests, width: int, height: int, region=None) -> np.ndarray:
+        """rrt_select_tiles: the ascending numbers ty * tiles_x + tx (uint32) of the tiles that some test of `tests` (1 to MAX_TILE_TESTS tile_test structs over
+        host arrays) selects: their union."""
+        reg, w, h = _region(width, height, region)
+        arr, n = _tile_tests("select_tiles", tests, w, h, False)
+        tx, ty = tile_count(width, height)
+        tiles, count = np.empty(tx * ty, np.uint32), C.c_uint32(0)
+        _call("rrt_select_tiles", self._h, width, height, reg, arr, n, _u32(tiles), C.byref(count))
+        return tiles[:count.value].copy()
+
+    def mark_tiles_into(self, marks_t, test: CTileTest, width: int, height: int, region=None, stream: Optional[int] = None):
+        """rrt_mark_tiles_device: marks_t = tiles_x * tiles_y one-byte elements on the device; test = tile_test over device tensors.  Enqueued, not synchronised;
+        last_stats stays as it was."""
+        reg, w, h = _region(width, height, region)
+        tests, _ = _tile_tests("mark_tiles_into", test, w, h, True)
+        tx, ty = tile_count(width, height)
+        _device_tensor(marks_t, tx * ty, 1, "marks")
+        _call("rrt_mark_tiles_device", self._h, width, height, reg, tests, _ptr(marks_t), _P(_stream(stream)))
+
+    def select_tiles_into(self, tiles_t, count_t, marks_t, scratch_t, tests, width: int, height: int, region=None, stream: Optional[int] = None):
+        """rrt_select_tiles_device: tests = 1 to MAX_TILE_TESTS tile_test structs over device tensors; marks_t = n_tiles = tiles_x * tiles_y one-byte elements;
+        tiles_t = n_tiles four-byte elements or None, count_t = one four-byte element or None (not both None); scratch_t = a device tensor of at least
+        compact_scratch_bytes(n_tiles) bytes.  tiles_t and count_t are what render_tile_list_into takes as tiles_t and bound_t, on the same stream with nothing in
+        between.  Enqueued, not synchronised; last_stats stays as it was."""
+        reg, w, h = _region(width, height, region)
+        arr, n = _tile_tests("select_tiles_into", tests, w, h, True)
+        tx, ty = tile_count(width, height)
+        _device_tensor(marks_t, tx * ty, 1, "marks")
+        if tiles_t is not None:
+            _device_tensor(tiles_t, tx * ty, 4, "tiles")
+        if count_t is not None:
+            _device_tensor(count_t, 1, 4, "count")
+        assert tiles_t is not None or count_t is not None, "select_tiles_into: tiles and count are both None"
+        assert getattr(scratch_t, "is_cuda", False) and scratch_t.is_contiguous(), "scratch: not a contiguous device tensor"
+        _call("rrt_select_tiles_device", self._h, width, height, reg, arr, n, _ptr(marks_t), _ptr(tiles_t), _ptr(count_t), _ptr(scratch_t),
+              scratch_t.numel() * scratch_t.element_size(), _P(_stream(stream)))
 
     # visibility buffers (rrt.h: rrt_render_visibility): first-hit geometry of the frame's primary rays.  region = (x0, y0, w, h) in canvas pixels, None = the frame
     def visibility(self, width: int, height: int, region=None, planes=PLANES) -> dict:

@@ -275,6 +275,22 @@ int launch_compact(const CompactParams& q, const uint32_t* d_bound, uint32_t* d_
 // d_dst[d_index[j]] = d_src[j], elem_bytes (1, 4, 8, 16 or 24) each, for every j in [0, n) -- with a bound [0, min(n, *d_bound)) -- with d_index[j] < n
 int launch_scatter(uint32_t n, const uint32_t* d_bound, const uint32_t* d_index, uint32_t elem_bytes, const void* d_src, void* d_dst, void* stream);
 
+// Argument of the tile-test kernel (tiles.hip: mark_tiles_kernel; rrt.h: rrt_mark_tiles_device): one test of rrt_tile_test over the planes a (and b: DIFFERS) of the
+// region (x0, y0, w, h) of a frame of tiles_x x tiles_y 8x8-pixel tiles, into marks[tiles_x * tiles_y].  test: RRT_TILE_* without the KEEP bit, which is `keep`.
+// vec: the host's choice of the 16-byte path, made once per launch (regions.cpp: tile_test_params has the rule).  Everything is checked by the caller.
+struct TileTestParams {
+    const void *a, *b;
+    uint8_t* marks;
+    uint32_t tiles_x, tiles_y;
+    uint32_t x0, y0, w, h;
+    uint32_t test, keep, elem_bytes, per_pixel;
+    uint32_t lo, hi;
+    uint32_t set[8];
+    uint32_t vec, _pad;
+};
+// one launch of q on `stream`; returns hipError_t cast to int; nothing is synchronised
+int launch_mark_tiles(const TileTestParams& q, void* stream);
+
 // Argument of the sort kernels (sort.hip; rrt.h: rrt_sort_rays_device).  A hist / place block covers a tile of kSortTile consecutive entries.  The scratch, in
 // 4-byte words: two (key, index) buffer pairs of n words per array, the digit counts of one pass, digit-major ([256][sort_tiles(n)]), and the 256 digit totals.
 constexpr uint32_t kSortTile = 4096, kSortDigits = 256;

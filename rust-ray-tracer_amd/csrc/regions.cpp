@@ -1,6 +1,7 @@
 // regions.cpp -- regions of a frame behind include/rrt.h: visibility and surface buffers, frames shaded and ambient occlusion from kept buffers, the pick of one
-// pixel, the fused frame of a region and of a list of tiles in device memory.  The calls share one check of the region (host_planes.hpp: region_in_force), one launch (launch_region_frame) and, for their host forms, the routine that
+// pixel, the fused frame of a region and of a list of tiles in device memory, and the tile tests that produce such a list.  The calls share one check of the region (host_planes.hpp: region_in_force), one launch (launch_region_frame) and, for their host forms, the routine that
 // carves the kept device allocation and copies the planes up and down (launches.hpp: with_kept_planes) over the mirrored structs (host_planes.hpp: mirror_planes).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -203,6 +204,102 @@ void launch_tile_list_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, 
     record(rt, width, height, 0, variant);                               // (the library does not know which tiles the list names)
 }
 
+// ---- tile selection: tests over planes that produce the list of a tile-list frame (rrt.h: rrt_mark_tiles, rrt_select_tiles; tiles.hip).  Not ray calls: no
+// timed_launch, no record, and nothing of the tuning or coverage state is looked at.
+static_assert(sizeof(rrt_tile_test) == 72, "rrt_tile_test is 72 bytes");
+struct TileFrame { rrt_region r; uint32_t tiles_x, tiles_y, n_tiles; };
+// the checks of the frame and the region, and the tiles of the frame
+TileFrame check_tile_frame(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region) {
+    check_frame(rt, width, height);
+    TileFrame f{};
+    f.r = region_in_force(width, height, region);
+    f.tiles_x = (width + 7) / 8; f.tiles_y = (height + 7) / 8;
+    const uint64_t n = (uint64_t)f.tiles_x * f.tiles_y;
+    if (n > RRT_MAX_TILE_LIST) throw Error{RRT_ERR_INVALID_ARG, "the frame has more tiles than RRT_MAX_TILE_LIST: its list would not fit a tile-list launch"};
+    f.n_tiles = (uint32_t)n;
+    return f;
+}
+// every check of one test (not null)
+void check_tile_test(const rrt_tile_test& t) {
+    const uint32_t kind = t.test & ~RRT_TILE_KEEP;
+    if (kind > RRT_TILE_DIFFERS) throw Error{RRT_ERR_INVALID_ARG, "unknown tile test: want RRT_TILE_NONZERO, RANGE, SET or DIFFERS, optionally | RRT_TILE_KEEP"};
+    if (t.elem_bytes != 1 && t.elem_bytes != 4 && t.elem_bytes != 8) throw Error{RRT_ERR_INVALID_ARG, "bad elem_bytes of a tile test: want 1, 4 or 8"};
+    if (t.per_pixel != 1 && t.per_pixel != 4) throw Error{RRT_ERR_INVALID_ARG, "bad per_pixel of a tile test: want 1 or 4"};
+    if ((kind == RRT_TILE_RANGE || kind == RRT_TILE_SET) && t.elem_bytes != 4) throw Error{RRT_ERR_INVALID_ARG, "RRT_TILE_RANGE and RRT_TILE_SET read 4-byte elements"};
+    if (!t.a) throw Error{RRT_ERR_INVALID_ARG, "null plane a of a tile test"};
+    if (kind == RRT_TILE_DIFFERS && !t.b) throw Error{RRT_ERR_INVALID_ARG, "null plane b: RRT_TILE_DIFFERS compares a with b"};
+    if ((uintptr_t)t.a % t.elem_bytes || (kind == RRT_TILE_DIFFERS && (uintptr_t)t.b % t.elem_bytes))
+        throw Error{RRT_ERR_INVALID_ARG, "a plane of a tile test is not aligned to elem_bytes"};
+}
+// every check of a select call but those of its outputs: returns the frame
+TileFrame check_tile_tests(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_tile_test* tests, uint32_t n_tests) {
+    if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+    if (!tests) throw Error{RRT_ERR_INVALID_ARG, "null tile tests"};
+    const TileFrame f = check_tile_frame(rt, width, height, region);
+    if (n_tests == 0 || n_tests > RRT_MAX_TILE_TESTS) throw Error{RRT_ERR_INVALID_ARG, "bad n_tests: 1 to RRT_MAX_TILE_TESTS tests"};
+    for (uint32_t k = 0; k < n_tests; k++) check_tile_test(tests[k]);
+    return f;
+}
+bool reads_b(const rrt_tile_test& t) { return (t.test & ~RRT_TILE_KEEP) == RRT_TILE_DIFFERS; }
+size_t tile_plane_bytes(const rrt_tile_test& t, const rrt_region& r) { return (size_t)r.w * r.h * t.per_pixel * t.elem_bytes; }
+// The kernel's argument of test t (checked) over planes d_a, d_b in device memory.  The 16-byte path: every 16-byte chunk of a stretch (tiles.hip) is aligned and
+// wholly inside or outside the region when the planes, the row pitch and the byte at which the region's rows begin in a row of the frame are multiples of 16.
+TileTestParams tile_test_params(const TileFrame& f, const rrt_tile_test& t, const void* d_a, const void* d_b, uint8_t* d_marks, bool keep) {
+    TileTestParams q{};
+    q.a = d_a; q.b = reads_b(t) ? d_b : nullptr; q.marks = d_marks;
+    q.tiles_x = f.tiles_x; q.tiles_y = f.tiles_y;
+    q.x0 = f.r.x0; q.y0 = f.r.y0; q.w = f.r.w; q.h = f.r.h;
+    q.test = t.test & ~RRT_TILE_KEEP; q.keep = keep || (t.test & RRT_TILE_KEEP) ? 1u : 0u;
+    q.elem_bytes = t.elem_bytes; q.per_pixel = t.per_pixel;
+    q.lo = t.lo; q.hi = t.hi;
+    std::memcpy(q.set, t.set, sizeof q.set);
+    const uint64_t pixel_bytes = (uint64_t)t.per_pixel * t.elem_bytes;
+    q.vec = (uintptr_t)q.a % 16 == 0 && (uintptr_t)q.b % 16 == 0 && (f.r.w * pixel_bytes) % 16 == 0 && (f.r.x0 * pixel_bytes) % 16 == 0 ? 1u : 0u;
+    return q;
+}
+// tests[0, n) (checked) into d_marks on `stream`, one launch each: the first as given, the later ones joined
+void launch_tile_tests(const TileFrame& f, const rrt_tile_test* tests, uint32_t n, const void* const* d_a, const void* const* d_b, uint8_t* d_marks, void* stream) {
+    for (uint32_t k = 0; k < n; k++) HIP_TRY((hipError_t)launch_mark_tiles(tile_test_params(f, tests[k], d_a[k], d_b[k], d_marks, k > 0), stream));
+}
+// the marks into the list: compact.hip's launches with the marks as the flags and nothing to move
+void launch_tile_list_of_marks(const TileFrame& f, const uint8_t* d_marks, uint32_t* d_tiles, uint32_t* d_count, void* d_scratch, void* stream) {
+    CompactParams q{};
+    q.flag = d_marks; q.index = d_tiles; q.tiles = static_cast<uint32_t*>(d_scratch);
+    q.n = f.n_tiles; q.select = RRT_SELECT_FLAG;
+    HIP_TRY((hipError_t)launch_compact(q, nullptr, d_count, stream));
+}
+// Host forms (checked): one allocation of the call's own (with_call_planes), the planes the tests read up -- a host plane that several tests name goes up once --
+// the launches on the null stream, what was asked for down.  marks: the caller's (up as well when the first test joins them), or none: then only carved.
+void tiles_from_host(rrt_raytracer* rt, const TileFrame& f, const rrt_tile_test* tests, uint32_t n, uint8_t* marks, bool want_list, uint32_t* tiles, uint32_t* count) {
+    DeviceGuard guard(rt->device);
+    enum : size_t { kScratch, kMarks, kTiles, kCount, kA, kB = kA + RRT_MAX_TILE_TESTS, kEnd = kB + RRT_MAX_TILE_TESTS };
+    HostPlane pl[kEnd];
+    pl[kScratch] = HostPlane{want_list ? rt : nullptr, 1, rrt_compact_scratch_bytes(f.n_tiles), kCarve};   // (only carved: a host pointer that is not null says it is wanted)
+    pl[kMarks] = marks ? HostPlane{marks, 1, f.n_tiles, (tests[0].test & RRT_TILE_KEEP) ? kUp | kDown : kDown} : HostPlane{rt, 1, f.n_tiles, kCarve};
+    pl[kTiles] = plane_down(tiles, 4, f.n_tiles); pl[kCount] = plane_down(count, 4, 1);
+    size_t from_a[RRT_MAX_TILE_TESTS], from_b[RRT_MAX_TILE_TESTS];
+    for (size_t e = kA; e < kEnd; e++) pl[e] = HostPlane{nullptr, 1, 0, kUp};
+    for (size_t k = 0; k < n; k++) {
+        const size_t bytes = tile_plane_bytes(tests[k], f.r);
+        auto place = [&](size_t at, const void* host) {
+            for (size_t e = kA; e < at; e++) if (pl[e].host == host && pl[e].bytes() >= bytes) return e;   // (the longer of two readings of one address went up)
+            pl[at] = plane_up(host, 1, bytes);
+            return at;
+        };
+        from_a[k] = place(kA + k, tests[k].a);
+        from_b[k] = reads_b(tests[k]) ? place(kB + k, tests[k].b) : kB + k;
+    }
+    with_call_planes(pl, [&] {
+        const void *d_a[RRT_MAX_TILE_TESTS], *d_b[RRT_MAX_TILE_TESTS];
+        for (uint32_t k = 0; k < n; k++) { d_a[k] = pl[from_a[k]].dev; d_b[k] = pl[from_b[k]].dev; }
+        rrt_tile_test own[RRT_MAX_TILE_TESTS];
+        std::copy(tests, tests + n, own);
+        if (!marks) own[0].test &= ~RRT_TILE_KEEP;                          // (no marks of the caller's: nothing to join)
+        launch_tile_tests(f, own, n, d_a, d_b, (uint8_t*)pl[kMarks].dev, nullptr);
+        if (want_list) launch_tile_list_of_marks(f, (const uint8_t*)pl[kMarks].dev, (uint32_t*)pl[kTiles].dev, (uint32_t*)pl[kCount].dev, pl[kScratch].dev, nullptr);
+    });
+}
+
 // every check of a frame's call, before any GPU work; returns the region in force
 rrt_region check_ambient(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_surface* planes, const rrt_ambient_samples* samples,
                          const rrt_ambient* out) {
@@ -325,6 +422,51 @@ int rrt_render_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32_t heig
         if (!d_tiles) throw Error{RRT_ERR_INVALID_ARG, "null tile list"};
         DeviceGuard guard(rt->device);
         launch_tile_list_frame(rt, width, height, n, d_count, d_tiles, d_fb, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_mark_tiles_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_tile_test* test, uint8_t* d_marks, void* stream) {
+    return guarded([&]() -> int {
+        const TileFrame f = check_tile_tests(rt, width, height, region, test, 1);
+        if (!d_marks) throw Error{RRT_ERR_INVALID_ARG, "null marks"};
+        DeviceGuard guard(rt->device);
+        launch_tile_tests(f, test, 1, &test->a, &test->b, d_marks, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_mark_tiles(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_tile_test* test, uint8_t* marks) {
+    return guarded([&]() -> int {
+        const TileFrame f = check_tile_tests(rt, width, height, region, test, 1);
+        if (!marks) throw Error{RRT_ERR_INVALID_ARG, "null marks"};
+        tiles_from_host(rt, f, test, 1, marks, false, nullptr, nullptr);
+        return RRT_OK;
+    });
+}
+
+int rrt_select_tiles_device(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_tile_test* tests, uint32_t n_tests, uint8_t* d_marks,
+                            uint32_t* d_tiles, uint32_t* d_count, void* d_scratch, size_t scratch_bytes, void* stream) {
+    return guarded([&]() -> int {
+        const TileFrame f = check_tile_tests(rt, width, height, region, tests, n_tests);
+        if (!d_marks) throw Error{RRT_ERR_INVALID_ARG, "null marks"};
+        if (!d_tiles && !d_count) throw Error{RRT_ERR_INVALID_ARG, "no output requested: the list and the count are both null"};
+        if (!d_scratch || scratch_bytes < rrt_compact_scratch_bytes(f.n_tiles)) throw Error{RRT_ERR_INVALID_ARG, "scratch too small or null: want rrt_compact_scratch_bytes(n_tiles) bytes of device memory"};
+        DeviceGuard guard(rt->device);
+        const void *d_a[RRT_MAX_TILE_TESTS], *d_b[RRT_MAX_TILE_TESTS];
+        for (uint32_t k = 0; k < n_tests; k++) { d_a[k] = tests[k].a; d_b[k] = tests[k].b; }
+        launch_tile_tests(f, tests, n_tests, d_a, d_b, d_marks, stream);
+        launch_tile_list_of_marks(f, d_marks, d_tiles, d_count, d_scratch, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_select_tiles(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region* region, const rrt_tile_test* tests, uint32_t n_tests, uint32_t* tiles,
+                     uint32_t* count) {
+    return guarded([&]() -> int {
+        const TileFrame f = check_tile_tests(rt, width, height, region, tests, n_tests);
+        if (!tiles && !count) throw Error{RRT_ERR_INVALID_ARG, "no output requested: the list and the count are both null"};
+        tiles_from_host(rt, f, tests, n_tests, nullptr, true, tiles, count);
         return RRT_OK;
     });
 }
