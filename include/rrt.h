@@ -534,6 +534,41 @@ int rrt_select_tiles_device(rrt_raytracer *rt, uint32_t width, uint32_t height, 
 int rrt_select_tiles(rrt_raytracer *rt, uint32_t width, uint32_t height, const rrt_region *region,
                      const rrt_tile_test *tests, uint32_t n_tests, uint32_t *tiles, uint32_t *count);
 
+/* The deferred stages over a tile list in DEVICE memory: visibility buffers, surface buffers, shading and ambient occlusion from kept buffers for the 8x8-pixel
+ * tiles a list names -- what rrt_render_visibility_device, rrt_render_surface_device, rrt_shade_surface_device and rrt_ambient_surface_device do for a rectangle.
+ * For the second round of an edit loop (the planes under a tex or bump edit repaired where rrt_select_tiles_device found the material, then shaded from the
+ * repaired planes), for shading a selection without walking its primary rays again, for more ambient samples where an `occluded` plane shows disagreement.
+ * PLANES.  Every plane, input and output, is a WHOLE-FRAME plane, tight: [height][width][4] (point and normal [height][width][4][3]); grey and d_fb are
+ * [height][width].  They are exactly the planes the region call of the same name takes with region == NULL.
+ * LIST.  n, d_count and d_tiles mean what they mean for rrt_render_tile_list_device: tiles numbered ty * tiles_x + tx; m = min(n, *d_count), read by the kernel
+ * when it runs, in stream order; m = n for d_count == NULL.  d_tiles[j] is used as an index only after d_tiles[j] < tiles_x * tiles_y; any other value,
+ * 0xFFFFFFFF included, is skipped.  Entries [m, n) are never read.  Duplicates are allowed.  The list and the bound are only ever read.
+ * LAUNCH.  The grid is sized by n, four blocks of 64 threads per entry, one per quadrant; a block at or beyond m ends after one scalar load and a compare, before
+ * it touches LDS or memory.  n == 0: RRT_OK, nothing is launched and rrt_last_stats stays as it was.  n > RRT_MAX_TILE_LIST: RRT_ERR_INVALID_ARG.  The caller's
+ * order is the schedule (no XCD-aware block order).
+ * WRITTEN.  For a tile in d_tiles[0, m) and a pixel of it inside the frame, every element of every requested output at that pixel holds what the region call
+ * with region == NULL writes there, bit for bit, in every traversal variant -- the miss values of the pixels the reference never traces included.  No other
+ * element of any output is read or written.
+ * READ.  Shading and ambient occlusion read their input planes only at pixels of listed tiles.  A plane value is never used as an index; material >= n_mats is
+ * a miss, as for the region calls.
+ * Traversal variant, tuning state and coverage state as for the region calls.  rrt_last_stats as for rrt_render_tile_list_device: kernel_ms and filter_variant
+ * of this launch, width / height = the frame size, rays_primary = 0 -- the library does not read the list.
+ * RRT_ERR_INVALID_ARG, before any GPU work: what the region call of the same name refuses (NULL rt, a bad frame size, a NULL struct, no output requested, a
+ * missing required plane, a NULL d_fb, a bad sample table), n > RRT_MAX_TILE_LIST, NULL d_tiles with n > 0.
+ * Enqueued on `stream` (hipStream_t, NULL = default): no allocation, no copy, no synchronisation.  There are no host forms: a host that knows its tiles has regions.
+ * Not covered: a coverage pass, counted or tile-list forms of rrt_resolve_hits, the rank/world tile partition, the rrt_multi_* path and the progressive path. */
+int rrt_render_visibility_tile_list_device(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t *d_count,
+                                           const uint32_t *d_tiles, const rrt_visibility *d_planes, void *stream);
+int rrt_render_surface_tile_list_device(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t *d_count,
+                                        const uint32_t *d_tiles, const rrt_visibility *d_vis /* may be NULL */, const rrt_surface *d_planes,
+                                        void *stream);
+int rrt_shade_surface_tile_list_device(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t *d_count,
+                                       const uint32_t *d_tiles, const rrt_visibility *d_vis, const rrt_surface *d_planes, void *d_fb,
+                                       void *stream);
+int rrt_ambient_surface_tile_list_device(rrt_raytracer *rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t *d_count,
+                                         const uint32_t *d_tiles, const rrt_surface *d_planes, const rrt_ambient_samples *samples,
+                                         const rrt_ambient *d_out, void *stream);
+
 /* Screen-tile partition for N GPUs (one process per GPU): the frame is cut into 8x8-pixel tiles, tile k (row-major)
  * belongs to rank k % world.  Renders this rank's tiles into d_tiles[rrt_tiles_per_rank][64] (tile-major, device).
  * After a gather (or all-gather) of the per-rank buffers (RCCL, done by the caller), rrt_detile_device turns

@@ -222,6 +222,10 @@ SYMBOLS = {
     "rrt_render_region_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), _P, C.c_uint32, _P]),
     "rrt_render_region": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), _u32p, C.c_uint32]),
     "rrt_render_tile_list_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    "rrt_render_visibility_tile_list_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(CVisibility), _P]),
+    "rrt_render_surface_tile_list_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(CVisibility), C.POINTER(CSurface), _P]),
+    "rrt_shade_surface_tile_list_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(CVisibility), C.POINTER(CSurface), _P, _P]),
+    "rrt_ambient_surface_tile_list_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.POINTER(CSurface), C.POINTER(CAmbientSamples), C.POINTER(CAmbient), _P]),
     "rrt_mark_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CTileTest), _P, _P]),
     "rrt_mark_tiles": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CTileTest), _u8p]),
     "rrt_select_tiles_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CRegion), C.POINTER(CTileTest), C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
@@ -485,6 +489,15 @@ def _batch_size(t, per: int, name: str) -> int:
     n, rem = divmod(t.numel(), per)
     assert rem == 0, f"{name}: the element count is not a multiple of {per}"
     return n
+
+
+def _tile_list(tiles_t, bound_t) -> tuple:
+    """The size checks render_tile_list_into makes of a device-resident tile list and its bound, for the tile-list stages: (n, bound pointer, list pointer)."""
+    n = _batch_size(tiles_t, 1, "tiles")
+    _device_tensor(tiles_t, n, 4, "tiles")
+    if bound_t is not None:
+        _device_tensor(bound_t, 1, 4, "bound")
+    return n, _ptr(bound_t), _ptr(tiles_t)
 
 
 def _ray_batch(origins_t, dirs_t, max_t_t) -> int:
@@ -1580,6 +1593,39 @@ class RayTracer(_Handle):
         _d_keep, samples = _ambient_samples(dirs, max_t)
         _call("rrt_ambient_surface_device", self._h, width, height, reg, _plane_struct(CSurface, keep), C.byref(samples), _plane_struct(CAmbient, out),
               _P(_stream(stream)))
+
+    # the deferred stages over a device-resident tile list (rrt.h: rrt_render_visibility_tile_list_device and its three neighbours): every plane is a whole
+    # frame, as the *_into twin takes it with region=None; tiles_t and bound_t as render_tile_list_into takes them (select_tiles_into writes both)
+    def visibility_tile_list_into(self, tensors: dict, tiles_t, width: int, height: int, stream: Optional[int] = None, bound_t=None):
+        """rrt_render_visibility_tile_list_device: tensors as visibility_into takes them for the whole frame; only the listed tiles' pixels are written.
+        Enqueued, not synchronised."""
+        keep = _device_planes(tensors, tensors, width, height)
+        _call("rrt_render_visibility_tile_list_device", self._h, width, height, *_tile_list(tiles_t, bound_t), _plane_struct(CVisibility, keep), _P(_stream(stream)))
+
+    def surface_tile_list_into(self, tensors: dict, tiles_t, width: int, height: int, stream: Optional[int] = None, bound_t=None):
+        """rrt_render_surface_tile_list_device: tensors as surface_into takes them for the whole frame; only the listed tiles' pixels are written.
+        Enqueued, not synchronised."""
+        keep = _device_planes(tensors, tensors, width, height)
+        _call("rrt_render_surface_tile_list_device", self._h, width, height, *_tile_list(tiles_t, bound_t), _plane_struct(CVisibility, keep),
+              _plane_struct(CSurface, keep), _P(_stream(stream)))
+
+    def shade_tile_list_into(self, fb_tensor, tensors: dict, tiles_t, width: int, height: int, stream: Optional[int] = None, bound_t=None):
+        """rrt_shade_surface_tile_list_device: fb_tensor and tensors as shade_into takes them for the whole frame; the planes are read and the pixels written in
+        the listed tiles only.  Enqueued, not synchronised."""
+        _device_tensor(fb_tensor, width * height, 4, "fb")
+        keep = _device_planes(tensors, SHADE_INPUTS, width, height)
+        _call("rrt_shade_surface_tile_list_device", self._h, width, height, *_tile_list(tiles_t, bound_t), _plane_struct(CVisibility, keep),
+              _plane_struct(CSurface, keep), _ptr(fb_tensor), _P(_stream(stream)))
+
+    def ambient_tile_list_into(self, out_tensors: dict, plane_tensors: dict, dirs, max_t: float, tiles_t, width: int, height: int, stream: Optional[int] = None,
+                               bound_t=None):
+        """rrt_ambient_surface_tile_list_device: out_tensors, plane_tensors, dirs and max_t as ambient_into takes them for the whole frame; the planes are read
+        and the outputs written in the listed tiles only.  Enqueued, not synchronised."""
+        assert set(out_tensors) <= set(AMBIENT_OUTPUTS), sorted(out_tensors)
+        out, keep = _device_planes(out_tensors, AMBIENT_OUTPUTS, width, height), _device_planes(plane_tensors, AMBIENT_INPUTS, width, height)
+        _d_keep, samples = _ambient_samples(dirs, max_t)
+        _call("rrt_ambient_surface_tile_list_device", self._h, width, height, *_tile_list(tiles_t, bound_t), _plane_struct(CSurface, keep), C.byref(samples),
+              _plane_struct(CAmbient, out), _P(_stream(stream)))
 
     def setup_times(self) -> dict:
         """Wall ms of the once-per-scene stages: read, parse, texture decode, octree (model) + index, upload (this raytracer)."""

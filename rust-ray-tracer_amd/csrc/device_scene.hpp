@@ -198,6 +198,38 @@ struct AmbientParams {
 };
 static_assert(sizeof(DevScene) + sizeof(AmbientParams) < 4096, "the arguments of ambient_kernel must fit the 4 KB kernel-argument segment");
 
+// Arguments of the tile-list stage kernels (render.hip: visibility_tile_list_kernel, surface_tile_list_kernel, shade_tile_list_kernel, ambient_tile_list_kernel;
+// rrt.h: rrt_render_visibility_tile_list_device and its three neighbours): the list fields of TileListParams -- the whole frame, the list, the bound, n; read
+// under the same rules -- plus the planes of the stage's region twin (VisParams, SurfaceParams, ShadeParams, AmbientParams).  Every plane is a WHOLE-FRAME
+// plane, [height][width][4 sub-samples] and its kin, the framebuffer and `grey` [height][width]: what the region twin takes for the whole frame.
+struct TileList {
+    FrameParams F;
+    const uint32_t *tiles, *count;
+    uint32_t n, _pad;
+};
+struct VisTileListParams {
+    TileList L;
+    uint8_t* hit; double *t, *u, *v; uint32_t* tri; uint32_t* albedo;
+};
+struct SurfaceTileListParams {
+    VisTileListParams V;         // every visibility plane may be null here
+    double *point, *normal; uint32_t *material, *lights;
+};
+struct ShadeTileListParams {
+    TileList L;
+    const double *point, *normal; const uint32_t *material, *albedo, *lights;
+    uint32_t* out;
+};
+struct AmbientTileListParams {
+    TileList L;
+    const double *point, *normal; const uint32_t* material;
+    uint32_t *occluded, *grey;
+    uint32_t n_samples, _pad;
+    double max_t;
+    double dirs[RRT_MAX_AMBIENT_SAMPLES][3];
+};
+static_assert(sizeof(DevScene) + sizeof(AmbientTileListParams) < 4096, "the arguments of ambient_tile_list_kernel must fit the 4 KB kernel-argument segment");
+
 // Argument of the per-ray surface kernels (render.hip: surface_rays_kernel; rrt.h: rrt_surface_rays_device): the twelve output arrays of a batch of n rays, in
 // the order and layout of rrt_ray_surface -- [n] each, point / normal / next_origin / next_dir [n][3].  A null array is not written; which are null also decides
 // what the kernel computes at all (no `lights`: no shadow walk).
@@ -356,6 +388,10 @@ template <class Params> int launch_region(const DevScene& s, const Params& q, vo
 // kMaxTileList: HIP refuses a launch of more than 2^32 - 1 threads in a grid dimension, and an entry takes 4 blocks of 64.
 constexpr uint32_t kMaxTileList = 0xFFFFFFFFu / 256u;
 int launch_tile_list(const DevScene& s, const TileListParams& q, void* stream, int walk);
+// A deferred stage over the tiles of a device-resident list (render.hip: launch_tile_stage), for Params = VisTileListParams (visibility_tile_list_kernel),
+// SurfaceTileListParams (surface_tile_list_kernel), ShadeTileListParams (shade_tile_list_kernel) and AmbientTileListParams (ambient_tile_list_kernel): the grid and
+// the dispatch are launch_tile_list's.  Defined and instantiated for these four in render.hip.
+template <class Params> int launch_tile_stage(const DevScene& s, const Params& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
 // The seven per-ray launchers (render.hip: each is launch_per_ray with its kernel): one lane per ray, 64 rays per block; n == 0 launches nothing.
 // d_count: null, or the bound of a counted launch (rrt.h: COUNTED DEVICE FORMS) -- one uint32 in device memory, read by the kernel when it runs; the grid is that of n.

@@ -1,5 +1,5 @@
 // regions.cpp -- regions of a frame behind include/rrt.h: visibility and surface buffers, frames shaded and ambient occlusion from kept buffers, the pick of one
-// pixel, the fused frame of a region and of a list of tiles in device memory, and the tile tests that produce such a list.  The calls share one check of the region (host_planes.hpp: region_in_force), one launch (launch_region_frame) and, for their host forms, the routine that
+// pixel, the fused frame of a region and of a list of tiles in device memory, the four deferred stages over such a list, and the tile tests that produce one.  The calls share one check of the region (host_planes.hpp: region_in_force), one launch (launch_region_frame) and, for their host forms, the routine that
 // carves the kept device allocation and copies the planes up and down (launches.hpp: with_kept_planes) over the mirrored structs (host_planes.hpp: mirror_planes).
 #include <algorithm>
 #include <cmath>
@@ -204,6 +204,49 @@ void launch_tile_list_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, 
     record(rt, width, height, 0, variant);                               // (the library does not know which tiles the list names)
 }
 
+// ---- the deferred stages over a tile list in device memory (rrt.h: rrt_render_visibility_tile_list_device and its three neighbours).  The checks are the region
+// calls' with no region (region_in_force(NULL) is the whole frame and refuses nothing) and the list's; the planes are whole-frame planes.
+// the list fields of a stage's argument
+TileList tile_list_of(const rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles) {
+    TileList l{};
+    l.F = frame_params(rt, width, height, 0, 1, false);
+    l.F.xcd_chunk = 0;                                                   // the caller's order is the schedule
+    l.tiles = d_tiles; l.count = d_count; l.n = n;
+    return l;
+}
+// The checks of a list, behind those of the stage: false for the empty list, which launches nothing.
+bool check_tile_list(uint32_t n, const uint32_t* d_tiles) {
+    if (n > kMaxTileList) throw Error{RRT_ERR_INVALID_ARG, "the list is longer than RRT_MAX_TILE_LIST entries: its grid would not fit a launch"};
+    if (n == 0) return false;                                            // nothing is launched, rrt_last_stats stays as it was
+    if (!d_tiles) throw Error{RRT_ERR_INVALID_ARG, "null tile list"};
+    return true;
+}
+// The one tile-stage launch, shaped like launch_tile_list_frame: the finished kernel argument q on the caller's stream, timed and recorded.
+template <class Params> void launch_tile_stage_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const Params& q, void* stream) {
+    const int variant = visibility_variant(rt, width, height);
+    timed_launch(rt, stream, [&] { return launch_tile_stage(rt->scene, q, stream, variant); });
+    record(rt, width, height, 0, variant);                               // (the library does not know which tiles the list names)
+}
+VisTileListParams vis_tile_list_params(const TileList& l, const rrt_visibility& d_planes) {
+    VisTileListParams p{};
+    p.L = l;
+    p.hit = d_planes.hit; p.t = d_planes.t; p.u = d_planes.u; p.v = d_planes.v; p.tri = d_planes.tri; p.albedo = d_planes.albedo;
+    return p;
+}
+void launch_surface_tile_list(rrt_raytracer* rt, uint32_t width, uint32_t height, const TileList& l, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* stream) {
+    SurfaceTileListParams q{};
+    q.V = vis_tile_list_params(l, d_vis);
+    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.lights = d_planes.lights;
+    launch_tile_stage_frame(rt, width, height, q, stream);
+}
+void launch_shade_tile_list(rrt_raytracer* rt, uint32_t width, uint32_t height, const TileList& l, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* d_fb, void* stream) {
+    ShadeTileListParams q{};
+    q.L = l;
+    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.albedo = d_vis.albedo; q.lights = d_planes.lights;
+    q.out = static_cast<uint32_t*>(d_fb);
+    launch_tile_stage_frame(rt, width, height, q, stream);
+}
+
 // ---- tile selection: tests over planes that produce the list of a tile-list frame (rrt.h: rrt_mark_tiles, rrt_select_tiles; tiles.hip).  Not ray calls: no
 // timed_launch, no record, and nothing of the tuning or coverage state is looked at.
 static_assert(sizeof(rrt_tile_test) == 72, "rrt_tile_test is 72 bytes");
@@ -323,6 +366,18 @@ void launch_ambient_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, co
     launch_region_frame(rt, width, height, r, q, stream);
 }
 
+// the same over a tile list: the table travels as in launch_ambient_frame
+void launch_ambient_tile_list(rrt_raytracer* rt, uint32_t width, uint32_t height, const TileList& l, const rrt_surface& d_planes, const rrt_ambient_samples& samples,
+                              const rrt_ambient& d_out, void* stream) {
+    AmbientTileListParams q{};
+    q.L = l;
+    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material;
+    q.occluded = d_out.occluded; q.grey = d_out.grey;
+    q.n_samples = samples.n; q.max_t = samples.max_t;
+    std::memcpy(q.dirs, samples.dirs, sizeof(double) * 3 * samples.n);
+    launch_tile_stage_frame(rt, width, height, q, stream);
+}
+
 // Host form: the three planes up, the requested outputs down.
 void ambient_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_surface& planes, const rrt_ambient_samples& samples,
                        const rrt_ambient& out) {
@@ -422,6 +477,50 @@ int rrt_render_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32_t heig
         if (!d_tiles) throw Error{RRT_ERR_INVALID_ARG, "null tile list"};
         DeviceGuard guard(rt->device);
         launch_tile_list_frame(rt, width, height, n, d_count, d_tiles, d_fb, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_visibility_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles,
+                                           const rrt_visibility* d_planes, void* stream) {
+    return guarded([&]() -> int {
+        check_visibility(rt, width, height, nullptr, d_planes);
+        if (!check_tile_list(n, d_tiles)) return RRT_OK;
+        DeviceGuard guard(rt->device);
+        launch_tile_stage_frame(rt, width, height, vis_tile_list_params(tile_list_of(rt, width, height, n, d_count, d_tiles), *d_planes), stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_render_surface_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles,
+                                        const rrt_visibility* d_vis, const rrt_surface* d_planes, void* stream) {
+    return guarded([&]() -> int {
+        check_surface(rt, width, height, nullptr, d_planes);
+        if (!check_tile_list(n, d_tiles)) return RRT_OK;
+        DeviceGuard guard(rt->device);
+        launch_surface_tile_list(rt, width, height, tile_list_of(rt, width, height, n, d_count, d_tiles), d_vis ? *d_vis : rrt_visibility{}, *d_planes, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_shade_surface_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles,
+                                       const rrt_visibility* d_vis, const rrt_surface* d_planes, void* d_fb, void* stream) {
+    return guarded([&]() -> int {
+        check_shade(rt, width, height, nullptr, d_vis, d_planes, d_fb);
+        if (!check_tile_list(n, d_tiles)) return RRT_OK;
+        DeviceGuard guard(rt->device);
+        launch_shade_tile_list(rt, width, height, tile_list_of(rt, width, height, n, d_count, d_tiles), *d_vis, *d_planes, d_fb, stream);
+        return RRT_OK;
+    });
+}
+
+int rrt_ambient_surface_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles,
+                                         const rrt_surface* d_planes, const rrt_ambient_samples* samples, const rrt_ambient* d_out, void* stream) {
+    return guarded([&]() -> int {
+        check_ambient(rt, width, height, nullptr, d_planes, samples, d_out);
+        if (!check_tile_list(n, d_tiles)) return RRT_OK;
+        DeviceGuard guard(rt->device);
+        launch_ambient_tile_list(rt, width, height, tile_list_of(rt, width, height, n, d_count, d_tiles), *d_planes, *samples, *d_out, stream);
         return RRT_OK;
     });
 }

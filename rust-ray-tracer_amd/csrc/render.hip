@@ -2203,6 +2203,221 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_tile_list_kernel(con
     if (sub == 0 && in_fb) Q.out[(size_t)py * F.width + px] = mixed;
 }
 
+// ---- the deferred stages over a list of tiles (rrt.h: rrt_render_visibility_tile_list_device, rrt_render_surface_tile_list_device,
+// rrt_shade_surface_tile_list_device, rrt_ambient_surface_tile_list_device): what the region kernels above write for the whole frame, for the tiles of a list in
+// device memory only, into and from WHOLE-FRAME planes.  The front end is render_tile_list_kernel's, in one helper that only these four kernels call (no kernel
+// that existed before them does: the rule at region_lane): the bound and the entry are wave-uniform scalar loads; a block at or beyond the bound leaves after
+// the bound's load and a compare, one whose entry names no tile of the frame after the entry's, both before LDS or memory is touched; then render_kernel's pixel
+// arithmetic on the whole frame.  in_fb: the pixel lies in the frame; only such lanes store anything.  traced: as region_lane's.  The element index of a
+// sub-sample in a [height][width][4] plane is 4 * (py * width + px) + sub, of a pixel in the framebuffer or `grey` py * width + px.
+// The surface and shade kernels call surface_body and shade_body, as their region twins do; the visibility and ambient bodies are restated from
+// visibility_kernel and ambient_kernel, which have no shared body (see ambient_kernel for why its loop is text, not a helper).  No atomics, no LDS beyond the
+// walk's, no block waits on another; two blocks of a duplicate entry store the same bits.
+// Registers, scratch and occupancy are recorded beside the region twins', not tuned: profiles/tile_stage_kernel_resources.txt.
+struct TileLane { uint32_t px, py, sub; bool listed, in_fb, traced; };
+__device__ __forceinline__ TileLane tile_list_lane(const TileList& Q, uint32_t lane) {
+    const uint32_t entry = blockIdx.x >> 2, quad = blockIdx.x & 3u;
+    uint32_t m = Q.n;
+    if (Q.count) { const uint32_t c = *Q.count; m = c < m ? c : m; }                  // wave-uniform: a kernel-argument pointer
+    if (entry >= m) return TileLane{0, 0, 0, false, false, false};
+    const FrameParams& F = Q.F;
+    const uint32_t tile = Q.tiles[entry];                                              // wave-uniform too
+    if (tile >= F.tile_end) return TileLane{0, 0, 0, false, false, false};             // (tile_end = tiles_x * tiles_y: the whole frame)
+    const uint32_t pix = lane >> 2, sub = lane & 3u;
+    const uint32_t tx = tile % F.tiles_x, ty = tile / F.tiles_x;
+    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
+    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
+    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
+    const bool in_fb = (int32_t)px < W && (int32_t)py < H;
+    const bool traced = in_fb && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;
+    return TileLane{px, py, sub, true, in_fb, traced};
+}
+
+// visibility_kernel over a tile list.  The body from the walk on is visibility_kernel's, restated; in_fb stands where in_region stood.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void visibility_tile_list_kernel(const DevScene S, const VisTileListParams P) {
+    const uint32_t lane = threadIdx.x;
+    const TileLane L = tile_list_lane(P.L, lane);
+    if (!L.listed) return;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const Stack stk{lds + kParkBytes, lane};
+    const uint32_t sub = L.sub;
+    const bool in_fb = L.in_fb, traced = L.traced;
+    const V3 o = ld3(S.origin), d = primary_direction(P.L.F, L.px, L.py, sub);
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    double t; uint32_t slot;
+    walk<kWalk, kGroups>(PROF_ARG S, stk, traced, false, !origin_ray_in_suspect_plane(S, o, d), true, o, d, kInf, t, slot);
+    if (!in_fb) return;
+    const bool found = traced && slot != kNone;
+    double u = 0, v = 0;
+    uint32_t tri = kNone;
+    if (found) {
+        double t2;
+        mt_full(S.geom + slot, o, d, t2, u, v);
+        tri = S.attr[slot].orig;
+    } else {
+        t = 0;                                                                           // the miss convention of intersect_kernel; a pixel the reference never traces reads as a miss
+    }
+    const size_t i = ((size_t)L.py * P.L.F.width + L.px) * 4 + sub;
+    if (P.albedo) {
+        uint32_t col = traced ? 0x00FFFFFFu : 0u;                                        // WHITE, raytracer.rs:109-111; 0 as Canvas::new where nothing is traced
+        if (found) {
+            // --- the texel of the hit, raytracer.rs:43-55, as trace_colour reads it
+            const DevTriAttr& A = S.attr[slot];
+            const DevMaterial& M = S.mats[A.mat];
+            const DevTexture T = M.tex_desc;
+            const double w = 1.0 - u - v;                                                // raytracer.rs:43
+            const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;                // raytracer.rs:45-47
+            const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;                // raytracer.rs:48-50
+            const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);    // raytracer.rs:52
+            const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);  // raytracer.rs:53
+            const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);          // raytracer.rs:55
+            col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
+        }
+        P.albedo[i] = col;
+    }
+    if (P.hit) P.hit[i] = found ? 1 : 0;
+    if (P.t) P.t[i] = t;
+    if (P.u) P.u[i] = u;
+    if (P.v) P.v[i] = v;
+    if (P.tri) P.tri[i] = tri;
+}
+
+// surface_kernel over a tile list: surface_body with surface_kernel's arguments, and its stores.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void surface_tile_list_kernel(const DevScene S, const SurfaceTileListParams Q) {
+    const uint32_t lane = threadIdx.x;
+    const VisTileListParams& P = Q.V;
+    const TileLane L = tile_list_lane(P.L, lane);
+    if (!L.listed) return;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const Stack stk{lds + kParkBytes, lane};
+    const uint32_t sub = L.sub;
+    const bool in_fb = L.in_fb, traced = L.traced;
+    const V3 o = ld3(S.origin), d = primary_direction(P.L.F, L.px, L.py, sub);
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const SurfaceHit h = surface_body<kWalk, kGroups>(PROF_ARG S, stk, traced, true, o, d, kInf, traced ? 0x00FFFFFFu : 0u, true, true, true, Q.lights != nullptr);
+    if (!in_fb) return;
+    const size_t i = ((size_t)L.py * P.L.F.width + L.px) * 4 + sub;
+    if (Q.point) { Q.point[3 * i] = h.p.x; Q.point[3 * i + 1] = h.p.y; Q.point[3 * i + 2] = h.p.z; }
+    if (Q.normal) { Q.normal[3 * i] = h.n.x; Q.normal[3 * i + 1] = h.n.y; Q.normal[3 * i + 2] = h.n.z; }
+    if (Q.material) Q.material[i] = h.mat;
+    if (Q.lights) Q.lights[i] = h.mask;
+    // the visibility planes, as visibility_kernel writes them
+    if (P.albedo) P.albedo[i] = h.col;
+    if (P.hit) P.hit[i] = h.found ? 1 : 0;
+    if (P.t) P.t[i] = h.t;
+    if (P.u) P.u[i] = h.u;
+    if (P.v) P.v[i] = h.v;
+    if (P.tri) P.tri[i] = h.tri;
+}
+
+// shade_kernel over a tile list: the five values of a traced lane from the whole-frame planes, shade_body with shade_kernel's arguments, its unwind, mix and store.
+// A lane reads its planes only if it is traced: nothing is read outside the listed tiles.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void shade_tile_list_kernel(const DevScene S, const ShadeTileListParams Q) {
+    const uint32_t lane = threadIdx.x;
+    const TileLane L = tile_list_lane(Q.L, lane);
+    if (!L.listed) return;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const Stack stk{lds + kParkBytes, lane};
+    const uint32_t sub = L.sub;
+    const bool in_fb = L.in_fb, traced = L.traced;
+    const V3 seg_d = primary_direction(Q.L.F, L.px, L.py, sub);
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const size_t pixel_i = (size_t)L.py * Q.L.F.width + L.px, i = pixel_i * 4 + sub;
+    // ---- the five values: the primary segment's hit
+    bool live = false;                      // the lane holds a hit whose colour is not known yet
+    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
+    uint32_t col = 0, mat = 0, li = 0, depth = 0;
+    uint32_t n_eval = 0;                    // lights [0, n_eval) contribute (an occluded point light ends the loop, raytracer.rs:235-237)
+    uint32_t term = 0x00FFFFFFu;            // colour of the last segment; WHITE for a miss, raytracer.rs:109-111
+    if (traced) {
+        mat = Q.material[i];
+        if (mat < S.n_mats) {               // (0xFFFFFFFF, a miss, and anything else beyond the table: WHITE)
+            live = true;
+            p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
+            col = Q.albedo[i] & 0x00FFFFFFu;
+            if (Q.lights) {                 // the kept mask answers the depth-0 shadow queries: the light loop of shade_body is skipped for this hit
+                const uint32_t first_dark = (uint32_t)__builtin_ctz(~Q.lights[i] | (1u << RRT_MAX_LIGHTS));   // (n_lights <= 16: bits at and above it never count)
+                n_eval = first_dark < S.n_lights ? first_dark : S.n_lights;
+                li = 0xFFFFu;
+            }
+        }
+    }
+    double st_local[RRT_MAX_REFLECT][3]; double st_kr[RRT_MAX_REFLECT];
+    const ShadeEnd E = shade_body<kWalk, kGroups, false>(PROF_ARG S, stk, S.max_reflection_depth, true, live, seg_d, p, n, col, mat, li, depth, n_eval, term, st_local, st_kr);
+    const uint32_t c = shade_unwind(E.term, E.lvl, st_local, st_kr);
+    // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
+    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
+    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
+    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
+    const uint32_t mixed = traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;   // 0 as Canvas::new where nothing is traced
+    if (sub == 0 && in_fb) Q.out[pixel_i] = mixed;
+}
+
+// ambient_kernel over a tile list.  The body from the lane's hit on is ambient_kernel's, restated (the sample loop with its one call site of the walk included);
+// in_fb stands where in_region stood.  A lane reads its planes only if it is traced.
+template <int kWalk, bool kGroups>
+__global__ __launch_bounds__(64, kWavesPerSimd) void ambient_tile_list_kernel(const DevScene S, const AmbientTileListParams Q) {
+    const uint32_t lane = threadIdx.x;
+    const TileLane L = tile_list_lane(Q.L, lane);
+    if (!L.listed) return;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const Stack stk{lds + kParkBytes, lane};
+    const uint32_t sub = L.sub;
+    const bool in_fb = L.in_fb, traced = L.traced;
+#ifdef RRT_PROFILE
+    Prof prof{}; prof.last = 0;
+#endif
+    const size_t pixel_i = (size_t)L.py * Q.L.F.width + L.px, i = pixel_i * 4 + sub;
+    // ---- the lane's hit
+    bool hit = false;
+    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
+    if (traced && Q.material[i] < S.n_mats) {   // (0xFFFFFFFF, a miss, and anything else beyond the table: a miss -- shade_kernel's rule)
+        hit = true;
+        p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
+    }
+    const uint32_t n_samples = Q.n_samples;
+    uint32_t mask = 0;
+    if (__any(hit)) {
+        // the tangent frame of the hit, once for all samples
+        V3 tg = mk(0, 0, 0), bt = mk(0, 0, 0);
+        if (hit) tangent_frame(n, tg, bt);
+        const V3 ro = p + n * S.surface_offset;                                          // the origin of a shadow ray, raytracer.rs:170
+        for (uint32_t k = 0; k < n_samples; k++) {
+            const double sx = Q.dirs[k][0], sy = Q.dirs[k][1], sz = Q.dirs[k][2];        // wave-uniform
+            // (tg*sx + bt*sy) + n*sz, per component five operations, each rounded on its own: the shape of rrt_camera.  (a lane without a hit takes no part; its
+            // ray is a harmless one)
+            const V3 rd = hit ? mk((tg.x * sx + bt.x * sy) + n.x * sz, (tg.y * sx + bt.y * sy) + n.y * sz, (tg.z * sx + bt.z * sy) + n.z * sz) : mk(0, 0, 1);
+            double wt; uint32_t wslot;
+            // (the dispatch restated, as in ambient_kernel)
+            if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, hit, true, true, ro, rd, Q.max_t, wt, wslot);
+            else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, hit, true, true, false, ro, rd, Q.max_t, wt, wslot);
+            if (hit && wslot != kNone) mask |= 1u << k;
+        }
+    }
+    // ---- grey: the open rays of the pixel's four sub-samples = 4 consecutive lanes, summed as render_kernel sums Color::mix; 255 * open / (4 n), rounded half up
+    uint32_t open = traced ? (hit ? n_samples - (uint32_t)__popc(mask) : n_samples) : 0u;
+    open += __shfl_xor(open, 1);
+    open += __shfl_xor(open, 2);
+    if (!in_fb) return;
+    if (Q.occluded) Q.occluded[i] = mask;
+    if (Q.grey && sub == 0) Q.grey[pixel_i] = traced ? ((510u * open + 4u * n_samples) / (8u * n_samples)) * 0x010101u : 0u;
+}
+
+// For the tile-stage launchers below: the kernel that takes a parameter type (device_scene.hpp: VisTileListParams and its three neighbours).
+template <int kWalk, bool kGroups> auto tile_stage_kernel(const VisTileListParams&) { return &visibility_tile_list_kernel<kWalk, kGroups>; }
+template <int kWalk, bool kGroups> auto tile_stage_kernel(const SurfaceTileListParams&) { return &surface_tile_list_kernel<kWalk, kGroups>; }
+template <int kWalk, bool kGroups> auto tile_stage_kernel(const ShadeTileListParams&) { return &shade_tile_list_kernel<kWalk, kGroups>; }
+template <int kWalk, bool kGroups> auto tile_stage_kernel(const AmbientTileListParams&) { return &ambient_tile_list_kernel<kWalk, kGroups>; }
+
 // For the region launchers below: the kernel that takes a parameter type (device_scene.hpp: VisParams, SurfaceParams, ShadeParams, AmbientParams, RenderRegionParams).
 template <int kWalk, bool kGroups> auto region_kernel(const RenderRegionParams&) { return &render_region_kernel<kWalk, kGroups>; }
 template <int kWalk, bool kGroups> auto region_kernel(const VisParams&) { return &visibility_kernel<kWalk, kGroups>; }
@@ -2581,6 +2796,7 @@ void preload_kernels_lane_ray();
 int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds, const uint32_t* d_cover);
 template <class Params> int launch_region_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
 int launch_tile_list_lane_ray(const DevScene& s, const TileListParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+template <class Params> int launch_tile_stage_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
 void preload_kernels() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_kernel<kWalkBundle, false>));
@@ -2677,6 +2893,28 @@ int launch_tile_list(const DevScene& s, const TileListParams& q, void* stream, i
     });
 }
 
+// (the list inside a parameter type)
+inline const TileList& list_of(const VisTileListParams& p) { return p.L; }
+inline const TileList& list_of(const SurfaceTileListParams& q) { return q.V.L; }
+inline const TileList& list_of(const ShadeTileListParams& q) { return q.L; }
+inline const TileList& list_of(const AmbientTileListParams& q) { return q.L; }
+// A deferred stage over the tiles of a list in device memory: launch_tile_list's grid and dispatch with the stage's kernel.
+template <class Params> int launch_tile_stage(const DevScene& s, const Params& q, void* stream, int walk) {
+    walk = effective_walk(s, walk);
+    const uint32_t n = list_of(q).n;
+    if (n == 0) return 0;
+    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
+    if (walk != kWalkBundle) return launch_tile_stage_lane_ray(s, q, stream, walk, n * 4, lds);
+    return with_groups(s, [&](auto groups) {
+        hipLaunchKernelGGL((tile_stage_kernel<kWalkBundle, groups()>(q)), dim3(n * 4), dim3(64), lds, (hipStream_t)stream, s, q);
+        return (int)hipGetLastError();
+    });
+}
+template int launch_tile_stage(const DevScene&, const VisTileListParams&, void*, int);
+template int launch_tile_stage(const DevScene&, const SurfaceTileListParams&, void*, int);
+template int launch_tile_stage(const DevScene&, const ShadeTileListParams&, void*, int);
+template int launch_tile_stage(const DevScene&, const AmbientTileListParams&, void*, int);
+
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
     const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
     const uint32_t tpr = (tiles_x * tiles_y + world - 1) / world;
@@ -2724,6 +2962,18 @@ int launch_tile_list_lane_ray(const DevScene& s, const TileListParams& q, void* 
         });
     });
 }
+template <class Params> int launch_tile_stage_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+    return with_lane_or_ray_walk(walk, [&](auto w) {
+        return with_groups(s, [&](auto groups) {
+            hipLaunchKernelGGL((tile_stage_kernel<w(), groups()>(q)), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
+            return (int)hipGetLastError();
+        });
+    });
+}
+template int launch_tile_stage_lane_ray(const DevScene&, const VisTileListParams&, void*, int, uint32_t, uint32_t);
+template int launch_tile_stage_lane_ray(const DevScene&, const SurfaceTileListParams&, void*, int, uint32_t, uint32_t);
+template int launch_tile_stage_lane_ray(const DevScene&, const ShadeTileListParams&, void*, int, uint32_t, uint32_t);
+template int launch_tile_stage_lane_ray(const DevScene&, const AmbientTileListParams&, void*, int, uint32_t, uint32_t);
 #endif   // RRT_TU_LANE
 
 #if RRT_TU_RAYS
