@@ -9,6 +9,7 @@
 //  * one node is one 64-byte record: box + first_child + own run + occupancy flags of its 8 children, read with
 //    wave-uniform (scalar) loads.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace rrt {
@@ -132,103 +133,86 @@ struct FrameParams {
     double right[3], up[3], forward[3];
 };
 
-// Argument of the visibility kernels (render.hip: visibility_kernel; rrt.h: rrt_render_visibility_device): the frame, the region of it that is wanted
-// and the output planes.  Of a kernel of its own, so that FrameParams and DevScene -- arguments of the other kernels -- stay as they are.
-// The launch covers the 8x8-pixel tiles that intersect the region, in row-major order: tiles_w of them per row from tile (tile_x0, tile_y0);
-// F.tile_begin / F.tile_end = [0, their number), F.rank / F.world = 0 / 1.  The region is the columns [col_begin, col_end) of the rows
-// [F.row_begin, F.row_end); every plane is [rows][columns][4 sub-samples], and a null plane is not written.
-struct VisParams {
+// ---- Arguments of the stage kernels (render.hip: visibility_kernel, surface_kernel, shade_kernel, ambient_kernel, colour_kernel; rrt.h: rrt_render_visibility_device
+// and its neighbours, and their *_tile_list_device forms).  Every stage has ONE kernel body and two front ends; its argument is a front-end part -- where the waves
+// of the launch lie in the frame -- plus the planes of the stage, which exist once.  Of kernels of their own, so that FrameParams and DevScene -- arguments of the
+// frame kernels too -- stay as they are.
+// Front end 1, a region of a frame.  The launch covers the 8x8-pixel tiles that intersect the region, in row-major order: tiles_w of them per row from tile
+// (tile_x0, tile_y0); F.tile_begin / F.tile_end = [0, their number), F.rank / F.world = 0 / 1.  The region is the columns [col_begin, col_end) of the rows
+// [F.row_begin, F.row_end); every plane is a plane of the REGION, [rows][columns][4 sub-samples] and its kin, the pixels [rows][columns].
+struct Region {
     FrameParams F;
     uint32_t col_begin, col_end;
     uint32_t tile_x0, tile_y0, tiles_w, _pad;
-    uint8_t* hit; double *t, *u, *v; uint32_t* tri; uint32_t* albedo;
 };
-
-// Argument of the surface kernels (render.hip: surface_kernel; rrt.h: rrt_render_surface_device): a VisParams -- frame, region, tile rectangle and the
-// visibility planes, every one of which may be null here -- plus the four surface planes.  point and normal are [rows][columns][4 sub-samples][3], material and
-// lights [rows][columns][4 sub-samples]; a null plane is not written, and a null `lights` also means that no shadow ray is walked.
-struct SurfaceParams {
-    VisParams V;
-    double *point, *normal; uint32_t *material, *lights;
-};
-
-// Argument of the shade kernels (render.hip: shade_kernel; rrt.h: rrt_shade_surface_device): a VisParams -- frame, region and tile rectangle; its six plane
-// pointers are unused -- plus the five planes the kernel READS, laid out as the surface launch wrote them for that region, and the framebuffer it writes:
-// [rows][columns] pixels of the region.  `lights` may be null: the depth-0 shadow rays are then walked.
-struct ShadeParams {
-    VisParams V;
-    const double *point, *normal; const uint32_t *material, *albedo, *lights;
-    uint32_t* out;
-};
-
-// Argument of the region frame kernels (render.hip: render_region_kernel; rrt.h: rrt_render_region_device): a VisParams -- frame, region and tile rectangle; its
-// six plane pointers are null -- plus the pixels it writes: pixel (px, py) of the region goes to out[(py - F.row_begin) * pitch + (px - col_begin)], pitch in
-// elements and at least the region's width.  Nothing else of `out` is touched.
-struct RenderRegionParams {
-    VisParams V;
-    uint32_t* out;
-    uint32_t pitch, _pad;
-};
-
-// Argument of the tile-list frame kernels (render.hip: render_tile_list_kernel; rrt.h: rrt_render_tile_list_device): the whole frame (F.rank / F.world = 0 / 1,
-// F.xcd_chunk = 0: the list's order is the schedule), a list of n tile indices ty * F.tiles_x + tx in device memory, the bound -- null, or one uint32 in device
-// memory: entries [min(n, *count), n) are not read -- and the row-major [height][width] framebuffer.  tiles and count are only ever read; an entry is used as
-// an index only after the compare with F.tile_end.
-struct TileListParams {
-    FrameParams F;
-    const uint32_t *tiles, *count;
-    uint32_t n, _pad;
-    uint32_t* out;
-};
-
-// Argument of the ambient kernels (render.hip: ambient_kernel; rrt.h: rrt_ambient_surface_device): a VisParams -- frame, region and tile rectangle; its six plane
-// pointers are unused -- plus the three planes the kernel READS, laid out as the surface launch wrote them for that region, the two planes it writes (occluded:
-// [rows][columns][4 sub-samples] masks; grey: [rows][columns] pixels; either may be null, not both) and the sample table: n_samples directions in the tangent
-// frame of a hit, and the max_t of every ray.  The table travels in the kernel arguments, as the lights do: wave-uniform, read with scalar loads.
-#ifndef RRT_MAX_AMBIENT_SAMPLES
-#define RRT_MAX_AMBIENT_SAMPLES 32
-#endif
-struct AmbientParams {
-    VisParams V;
-    const double *point, *normal; const uint32_t* material;
-    uint32_t *occluded, *grey;
-    uint32_t n_samples, _pad;
-    double max_t;
-    double dirs[RRT_MAX_AMBIENT_SAMPLES][3];
-};
-static_assert(sizeof(DevScene) + sizeof(AmbientParams) < 4096, "the arguments of ambient_kernel must fit the 4 KB kernel-argument segment");
-
-// Arguments of the tile-list stage kernels (render.hip: visibility_tile_list_kernel, surface_tile_list_kernel, shade_tile_list_kernel, ambient_tile_list_kernel;
-// rrt.h: rrt_render_visibility_tile_list_device and its three neighbours): the list fields of TileListParams -- the whole frame, the list, the bound, n; read
-// under the same rules -- plus the planes of the stage's region twin (VisParams, SurfaceParams, ShadeParams, AmbientParams).  Every plane is a WHOLE-FRAME
-// plane, [height][width][4 sub-samples] and its kin, the framebuffer and `grey` [height][width]: what the region twin takes for the whole frame.
+// Front end 2, a list of tiles in device memory: the whole frame (F.rank / F.world = 0 / 1, F.xcd_chunk = 0: the list's order is the schedule), a list of n tile
+// indices ty * F.tiles_x + tx and the bound -- null, or one uint32 in device memory: entries [min(n, *count), n) are not read.  tiles and count are only ever
+// read; an entry is used as an index only after the compare with F.tile_end.  Every plane is a WHOLE-FRAME plane, [height][width][4 sub-samples] and its kin, the
+// framebuffer and `grey` [height][width]: what the region form takes for the whole frame.
 struct TileList {
     FrameParams F;
     const uint32_t *tiles, *count;
     uint32_t n, _pad;
 };
-struct VisTileListParams {
-    TileList L;
-    uint8_t* hit; double *t, *u, *v; uint32_t* tri; uint32_t* albedo;
-};
-struct SurfaceTileListParams {
-    VisTileListParams V;         // every visibility plane may be null here
-    double *point, *normal; uint32_t *material, *lights;
-};
-struct ShadeTileListParams {
-    TileList L;
-    const double *point, *normal; const uint32_t *material, *albedo, *lights;
-    uint32_t* out;
-};
-struct AmbientTileListParams {
-    TileList L;
+// The planes.  Visibility: [..][4 sub-samples] each; a null plane is not written.
+struct VisPlanes { uint8_t* hit; double *t, *u, *v; uint32_t* tri; uint32_t* albedo; };
+// Surface: point and normal [..][4 sub-samples][3], material and lights [..][4 sub-samples]; a null plane is not written, and a null `lights` also means that no
+// shadow ray is walked.
+struct SurfacePlanes { double *point, *normal; uint32_t *material, *lights; };
+// Shade: the five planes the kernel READS, laid out as the surface launch wrote them, and the framebuffer it writes.  `lights` may be null: the depth-0 shadow
+// rays are then walked.
+struct ShadePlanes { const double *point, *normal; const uint32_t *material, *albedo, *lights; uint32_t* out; };
+// Ambient: the three planes the kernel READS, the two it writes (occluded: masks per sub-sample; grey: pixels; either may be null, not both) and the sample table:
+// n_samples directions in the tangent frame of a hit, and the max_t of every ray.  The table travels in the kernel arguments, as the lights do: wave-uniform, read
+// with scalar loads.
+#ifndef RRT_MAX_AMBIENT_SAMPLES
+#define RRT_MAX_AMBIENT_SAMPLES 32
+#endif
+struct AmbientPlanes {
     const double *point, *normal; const uint32_t* material;
     uint32_t *occluded, *grey;
     uint32_t n_samples, _pad;
     double max_t;
     double dirs[RRT_MAX_AMBIENT_SAMPLES][3];
 };
-static_assert(sizeof(DevScene) + sizeof(AmbientTileListParams) < 4096, "the arguments of ambient_tile_list_kernel must fit the 4 KB kernel-argument segment");
+
+// The stages.  Visibility: a front end and its six planes.  Surface: the same -- every visibility plane may be null here -- and the four surface planes.
+template <class Front> struct VisStage { Front front; VisPlanes vis; };
+template <class Front> struct SurfaceStage { Front front; VisPlanes vis; SurfacePlanes planes; };
+// The stages that write no visibility plane.  Their region forms keep six unused plane pointers behind the region, as when their argument began with a whole
+// visibility argument: where a pointer sits in the kernel-argument segment shapes a kernel's scalar loads, and no layout moves.
+template <class Front> struct BareFrontOf { using type = Front; };
+template <> struct BareFrontOf<Region> { using type = VisStage<Region>; };
+template <class Front> using BareFront = typename BareFrontOf<Front>::type;
+template <class Front> struct ShadeStage { BareFront<Front> front; ShadePlanes planes; };
+template <class Front> struct AmbientStage { BareFront<Front> front; AmbientPlanes planes; };
+// The fused colour.  Of a region: pixel (px, py) goes to out[(py - F.row_begin) * pitch + (px - col_begin)], pitch in elements and at least the region's width;
+// nothing else of `out` is touched.  The pitch is the region front end's: a list stores into the row-major [height][width] framebuffer.
+struct RenderRegionParams { VisStage<Region> front; uint32_t* out; uint32_t pitch, _pad; };
+struct TileListParams { TileList front; uint32_t* out; };
+// (the front end inside a `front` member)
+__host__ __device__ inline const Region& front_end(const Region& r) { return r; }
+__host__ __device__ inline const Region& front_end(const VisStage<Region>& v) { return v.front; }
+__host__ __device__ inline const TileList& front_end(const TileList& l) { return l; }
+
+using VisParams = VisStage<Region>;
+using SurfaceParams = SurfaceStage<Region>;
+using ShadeParams = ShadeStage<Region>;
+using AmbientParams = AmbientStage<Region>;
+using VisTileListParams = VisStage<TileList>;
+using SurfaceTileListParams = SurfaceStage<TileList>;
+using ShadeTileListParams = ShadeStage<TileList>;
+using AmbientTileListParams = AmbientStage<TileList>;
+static_assert(sizeof(DevScene) + sizeof(AmbientParams) < 4096 && sizeof(DevScene) + sizeof(AmbientTileListParams) < 4096,
+              "the arguments of ambient_kernel, in either form, must fit the 4 KB kernel-argument segment");
+// The byte layout of every argument is pinned: its size and where its first plane lies.
+#define RRT_PIN_LAYOUT(T, first_plane, size, offset) static_assert(sizeof(T) == size && offsetof(T, first_plane) == offset, #T " must keep its layout")
+RRT_PIN_LAYOUT(VisParams, vis.hit, 216, 168);               RRT_PIN_LAYOUT(VisTileListParams, vis.hit, 216, 168);
+RRT_PIN_LAYOUT(SurfaceParams, planes.point, 248, 216);      RRT_PIN_LAYOUT(SurfaceTileListParams, planes.point, 248, 216);
+RRT_PIN_LAYOUT(ShadeParams, planes.point, 264, 216);        RRT_PIN_LAYOUT(ShadeTileListParams, planes.point, 216, 168);
+RRT_PIN_LAYOUT(AmbientParams, planes.point, 1040, 216);     RRT_PIN_LAYOUT(AmbientTileListParams, planes.point, 992, 168);
+RRT_PIN_LAYOUT(RenderRegionParams, out, 232, 216);          RRT_PIN_LAYOUT(TileListParams, out, 176, 168);
+#undef RRT_PIN_LAYOUT
 
 // Argument of the per-ray surface kernels (render.hip: surface_rays_kernel; rrt.h: rrt_surface_rays_device): the twelve output arrays of a batch of n rays, in
 // the order and layout of rrt_ray_surface -- [n] each, point / normal / next_origin / next_dir [n][3].  A null array is not written; which are null also decides
@@ -253,7 +237,7 @@ struct ShadeRaysParams {
 // Argument of the per-ray ambient kernels (render.hip: ambient_rays_kernel; rrt.h: rrt_ambient_rays_device): the three arrays the kernel READS -- the records the
 // per-ray surface launch wrote for a batch of n rays, point / normal [n][3], material [n] -- the optional rotation (rot: [n][2], (c, s) per record; null: the
 // samples enter the tangent frame as they are), the two arrays it writes (occluded [n] masks, open [n] counts; either may be null, not both) and the sample table
-// of AmbientParams, which travels in the kernel arguments in the same way.
+// of AmbientPlanes, which travels in the kernel arguments in the same way.
 struct AmbientRaysParams {
     const double *point, *normal; const uint32_t* material;
     const double* rot;
@@ -380,18 +364,11 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
 struct CoverageFrame;
 uint32_t coverage_mask_words(uint32_t tiles_x, uint32_t tiles_y);
 int launch_coverage(const CoverageFrame& F, const DevClusterBox* boxes, uint32_t n_boxes, uint32_t* mask, void* stream);
-// A region of a frame (render.hip: launch_region), for Params = VisParams (visibility_kernel: the visibility planes), SurfaceParams (surface_kernel: the surface
-// planes and any visibility planes), ShadeParams (shade_kernel: the pixels from kept planes) and AmbientParams (ambient_kernel: occlusion masks and grey pixels from
-// kept planes) and RenderRegionParams (render_region_kernel: the pixels by the fused frame body).  Defined and instantiated for these five in render.hip.
-template <class Params> int launch_region(const DevScene& s, const Params& q, void* stream, int walk);
-// The tiles of a device-resident list (render.hip: render_tile_list_kernel): four blocks per entry of q.n, the frame kernels' quadrants; q.n == 0 launches nothing.
+// One stage launch (render.hip: launch_stage), for Params = any of the ten arguments above: one block per quadrant of the tiles the region touches, or four
+// blocks per entry of a list's n, the frame kernels' quadrants; no tile, or n == 0, launches nothing.  Defined and instantiated for the ten in render.hip.
 // kMaxTileList: HIP refuses a launch of more than 2^32 - 1 threads in a grid dimension, and an entry takes 4 blocks of 64.
 constexpr uint32_t kMaxTileList = 0xFFFFFFFFu / 256u;
-int launch_tile_list(const DevScene& s, const TileListParams& q, void* stream, int walk);
-// A deferred stage over the tiles of a device-resident list (render.hip: launch_tile_stage), for Params = VisTileListParams (visibility_tile_list_kernel),
-// SurfaceTileListParams (surface_tile_list_kernel), ShadeTileListParams (shade_tile_list_kernel) and AmbientTileListParams (ambient_tile_list_kernel): the grid and
-// the dispatch are launch_tile_list's.  Defined and instantiated for these four in render.hip.
-template <class Params> int launch_tile_stage(const DevScene& s, const Params& q, void* stream, int walk);
+template <class Params> int launch_stage(const DevScene& s, const Params& q, void* stream, int walk);
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream);
 // The seven per-ray launchers (render.hip: each is launch_per_ray with its kernel): one lane per ray, 64 rays per block; n == 0 launches nothing.
 // d_count: null, or the bound of a counted launch (rrt.h: COUNTED DEVICE FORMS) -- one uint32 in device memory, read by the kernel when it runs; the grid is that of n.

@@ -1,5 +1,5 @@
 // regions.cpp -- regions of a frame behind include/rrt.h: visibility and surface buffers, frames shaded and ambient occlusion from kept buffers, the pick of one
-// pixel, the fused frame of a region and of a list of tiles in device memory, the four deferred stages over such a list, and the tile tests that produce one.  The calls share one check of the region (host_planes.hpp: region_in_force), one launch (launch_region_frame) and, for their host forms, the routine that
+// pixel, the fused frame of a region and of a list of tiles in device memory, the four deferred stages over such a list, and the tile tests that produce one.  The calls share one check of the region (host_planes.hpp: region_in_force), one check of a list (check_tile_list), one routine per stage that fills its planes, one launch (launch_stage_frame) and, for their host forms, the routine that
 // carves the kept device allocation and copies the planes up and down (launches.hpp: with_kept_planes) over the mirrored structs (host_planes.hpp: mirror_planes).
 #include <algorithm>
 #include <cmath>
@@ -34,24 +34,61 @@ namespace {
 
 using namespace rrt;
 
-// the kernels' argument for region r (checked) of a frame and these planes
-VisParams vis_params(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes) {
-    VisParams p{};
+// ---- where a stage runs: the front end of its kernel argument (device_scene.hpp: Region, TileList) and the primary rays its launch records.
+template <class Front> struct Place { Front front; uint64_t rays_primary; };
+// region r (checked) of a frame: 4 rays per traced pixel of it
+Place<Region> in_region(const rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r) {
+    Region p{};
     p.F = frame_params(rt, width, height, 0, 1, false);
     p.F.row_begin = r.y0; p.F.row_end = r.y0 + r.h;
     p.col_begin = r.x0; p.col_end = r.x0 + r.w;
     p.tile_x0 = r.x0 / 8; p.tile_y0 = r.y0 / 8;
     p.tiles_w = (p.col_end + 7) / 8 - p.tile_x0;
     p.F.tile_begin = 0; p.F.tile_end = p.tiles_w * ((p.F.row_end + 7) / 8 - p.tile_y0);
-    p.hit = d_planes.hit; p.t = d_planes.t; p.u = d_planes.u; p.v = d_planes.v; p.tri = d_planes.tri; p.albedo = d_planes.albedo;
-    return p;
+    return {p, 4 * traced_pixels_in(r, width, height)};
+}
+static_assert(kMaxTileList == RRT_MAX_TILE_LIST, "rrt.h names the launch bound of a tile list");
+// A list (checked) of tiles of a frame in device memory.  Nothing of the list is read here: the kernel reads it, and the bound, when it runs; the library does not
+// know which tiles the list names, and records no ray.
+Place<TileList> in_list(const rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles) {
+    TileList l{};
+    l.F = frame_params(rt, width, height, 0, 1, false);
+    l.F.xcd_chunk = 0;                                                   // the caller's order is the schedule
+    l.tiles = d_tiles; l.count = d_count; l.n = n;
+    return {l, 0};
+}
+// The checks of a list, behind those of the stage: false for the empty list, which launches nothing.
+bool check_tile_list(uint32_t n, const uint32_t* d_tiles) {
+    if (n > kMaxTileList) throw Error{RRT_ERR_INVALID_ARG, "the list is longer than RRT_MAX_TILE_LIST entries: its grid would not fit a launch"};
+    if (n == 0) return false;                                            // nothing is launched, rrt_last_stats stays as it was
+    if (!d_tiles) throw Error{RRT_ERR_INVALID_ARG, "null tile list"};
+    return true;
+}
+// (the front end of a stage that writes no visibility plane: a region carries six null plane pointers, device_scene.hpp: BareFront)
+VisStage<Region> bare(const Region& r) { return {r, VisPlanes{}}; }
+TileList bare(const TileList& l) { return l; }
+
+// The one stage launch: the finished kernel argument q on the caller's stream, timed by the raytracer's events and recorded.
+template <class Params> void launch_stage_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const Params& q, uint64_t rays_primary, void* stream) {
+    const int variant = visibility_variant(rt, width, height);
+    timed_launch(rt, stream, [&] { return launch_stage(rt->scene, q, stream, variant); });
+    record(rt, width, height, rays_primary, variant);
 }
 
-// The one region launch: the finished kernel argument q of region r (checked) on the caller's stream, timed by the raytracer's events and recorded.
-template <class Params> void launch_region_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const Params& q, void* stream) {
-    const int variant = visibility_variant(rt, width, height);
-    timed_launch(rt, stream, [&] { return launch_region(rt->scene, q, stream, variant); });
-    record(rt, width, height, 4 * traced_pixels_in(r, width, height), variant);
+// ---- the planes of each stage, from the structs of rrt.h with planes in device memory: one routine each, for both front ends.
+VisPlanes vis_planes(const rrt_visibility& d) { return {d.hit, d.t, d.u, d.v, d.tri, d.albedo}; }
+SurfacePlanes surface_planes(const rrt_surface& d) { return {d.point, d.normal, d.material, d.lights}; }
+ShadePlanes shade_planes(const rrt_visibility& d_vis, const rrt_surface& d, void* d_fb) {
+    return {d.point, d.normal, d.material, d_vis.albedo, d.lights, static_cast<uint32_t*>(d_fb)};
+}
+// (the sample table is copied into the kernel's argument here: no device memory holds it)
+AmbientPlanes ambient_planes(const rrt_surface& d, const rrt_ambient_samples& samples, const rrt_ambient& d_out) {
+    AmbientPlanes p{};
+    p.point = d.point; p.normal = d.normal; p.material = d.material;
+    p.occluded = d_out.occluded; p.grey = d_out.grey;
+    p.n_samples = samples.n; p.max_t = samples.max_t;
+    std::memcpy(p.dirs, samples.dirs, sizeof(double) * 3 * samples.n);
+    return p;
 }
 
 // ---- the host forms of the region calls.  Their planes live in the raytracer's kept device allocation for one call (with_kept_planes), the structs' planes in
@@ -68,16 +105,16 @@ rrt_region check_visibility(const rrt_raytracer* rt, uint32_t width, uint32_t he
     return region_in_force(width, height, region);
 }
 
-// the planes of region r (checked) into device memory
-void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_planes, void* stream) {
-    launch_region_frame(rt, width, height, r, vis_params(rt, width, height, r, d_planes), stream);
+// the planes of a region or a list (checked) into device memory
+template <class Front> void launch_visibility_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const Place<Front>& at, const rrt_visibility& d_planes, void* stream) {
+    launch_stage_frame(rt, width, height, VisStage<Front>{at.front, vis_planes(d_planes)}, at.rays_primary, stream);
 }
 
 void visibility_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& planes) {
     DeviceGuard guard(rt->device);
     HostPlane pl[kVis];
     mirror_planes(pl, planes, 4 * (size_t)r.w * r.h, VisDirs::every(kDown));
-    with_kept_planes(rt, pl, [&](void* stream) { launch_visibility_frame(rt, width, height, r, mirrored<rrt_visibility>(pl), stream); });
+    with_kept_planes(rt, pl, [&](void* stream) { launch_visibility_frame(rt, width, height, in_region(rt, width, height, r), mirrored<rrt_visibility>(pl), stream); });
 }
 
 // One pixel: a one-tile launch into the kept allocation and ONE copy of its six plane slots back.  All six planes of the pixel's four sub-samples are wanted, carved
@@ -90,7 +127,7 @@ rrt_pick_result pick_pixel(rrt_raytracer* rt, uint32_t width, uint32_t height, u
     rrt_visibility d{};
     with_kept_planes(rt, pl, [&](void* stream) {
         d = mirrored<rrt_visibility>(pl);
-        launch_visibility_frame(rt, width, height, rrt_region{px, py, 1, 1}, d, stream);
+        launch_visibility_frame(rt, width, height, in_region(rt, width, height, rrt_region{px, py, 1, 1}), d, stream);
         HIP_TRY(hipMemcpyAsync(back, d.hit, sizeof back, hipMemcpyDeviceToHost, (hipStream_t)stream));
     });
     auto at = [&](const void* dev) { return back + (static_cast<const char*>(dev) - reinterpret_cast<const char*>(d.hit)); };   // where the copy of a device plane begins
@@ -109,11 +146,9 @@ rrt_region check_surface(const rrt_raytracer* rt, uint32_t width, uint32_t heigh
     return region_in_force(width, height, region);
 }
 
-void launch_surface_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* stream) {
-    SurfaceParams q{};
-    q.V = vis_params(rt, width, height, r, d_vis);
-    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.lights = d_planes.lights;
-    launch_region_frame(rt, width, height, r, q, stream);
+template <class Front>
+void launch_surface_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const Place<Front>& at, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* stream) {
+    launch_stage_frame(rt, width, height, SurfaceStage<Front>{at.front, vis_planes(d_vis), surface_planes(d_planes)}, at.rays_primary, stream);
 }
 
 void surface_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& vis, const rrt_surface& planes) {
@@ -123,7 +158,7 @@ void surface_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const r
     mirror_planes(pl, vis, n, VisDirs::every(kDown));
     mirror_planes(pl + kVis, planes, n, SurfDirs::every(kDown));
     with_kept_planes(rt, pl, [&](void* stream) {
-        launch_surface_frame(rt, width, height, r, mirrored<rrt_visibility>(pl), mirrored<rrt_surface>(pl + kVis), stream);
+        launch_surface_frame(rt, width, height, in_region(rt, width, height, r), mirrored<rrt_visibility>(pl), mirrored<rrt_surface>(pl + kVis), stream);
     });
 }
 
@@ -136,13 +171,10 @@ rrt_region check_shade(const rrt_raytracer* rt, uint32_t width, uint32_t height,
     return region_in_force(width, height, region);
 }
 
-// the pixels of region r (checked) from planes in device memory into d_fb
-void launch_shade_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* d_fb, void* stream) {
-    ShadeParams q{};
-    q.V = vis_params(rt, width, height, r, rrt_visibility{});            // (the kernel writes no plane)
-    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.albedo = d_vis.albedo; q.lights = d_planes.lights;
-    q.out = static_cast<uint32_t*>(d_fb);
-    launch_region_frame(rt, width, height, r, q, stream);
+// the pixels of a region or a list (checked) from planes in device memory into d_fb
+template <class Front>
+void launch_shade_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const Place<Front>& at, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* d_fb, void* stream) {
+    launch_stage_frame(rt, width, height, ShadeStage<Front>{bare(at.front), shade_planes(d_vis, d_planes, d_fb)}, at.rays_primary, stream);
 }
 
 // Host form: the given planes up, the region's pixels down.  The list keeps the order point, normal, material, albedo, lights: the surface struct lies in two runs
@@ -157,7 +189,7 @@ void shade_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const r
     mirror_planes(pl + kSurfB, planes, n, SurfDirs().set(kUp, &rrt_surface::lights));
     pl[kOut] = plane_down(out_fb, sizeof(uint32_t), px);
     with_kept_planes(rt, pl, [&](void* stream) {
-        launch_shade_frame(rt, width, height, r, mirrored<rrt_visibility>(pl + kAlbedo), mirrored<rrt_surface>(pl + kSurfA, pl + kSurfB), pl[kOut].dev, stream);
+        launch_shade_frame(rt, width, height, in_region(rt, width, height, r), mirrored<rrt_visibility>(pl + kAlbedo), mirrored<rrt_surface>(pl + kSurfA, pl + kSurfB), pl[kOut].dev, stream);
     });
 }
 
@@ -173,10 +205,8 @@ rrt_region check_render_region(const rrt_raytracer* rt, uint32_t width, uint32_t
 
 // the pixels of region r (checked) into rows of `pitch` elements from d_out
 void launch_render_region_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, uint32_t* d_out, uint32_t pitch, void* stream) {
-    RenderRegionParams q{};
-    q.V = vis_params(rt, width, height, r, rrt_visibility{});            // (the kernel writes no plane)
-    q.out = d_out; q.pitch = pitch;
-    launch_region_frame(rt, width, height, r, q, stream);
+    const Place<Region> at = in_region(rt, width, height, r);
+    launch_stage_frame(rt, width, height, RenderRegionParams{bare(at.front), d_out, pitch, 0}, at.rays_primary, stream);
 }
 
 // Host form: the region's pixels, tight in the kept allocation, down into the caller's rows.  A tight `out` is a plane like any other; rows with a gap are only
@@ -190,61 +220,6 @@ void render_region_to_host(rrt_raytracer* rt, uint32_t width, uint32_t height, c
         if (!tight) HIP_TRY(hipMemcpy2DAsync(out, sizeof(uint32_t) * (size_t)pitch, pl[0].dev, sizeof(uint32_t) * (size_t)r.w, sizeof(uint32_t) * (size_t)r.w, r.h,
                                              hipMemcpyDeviceToHost, (hipStream_t)stream));
     });
-}
-
-// ---- the fused frame of a tile list in device memory.  Nothing of the list is read here: the kernel reads it, and the bound, when it runs.
-static_assert(kMaxTileList == RRT_MAX_TILE_LIST, "rrt.h names the launch bound of a tile list");
-void launch_tile_list_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles, uint32_t* d_fb, void* stream) {
-    TileListParams q{};
-    q.F = frame_params(rt, width, height, 0, 1, false);
-    q.F.xcd_chunk = 0;                                                   // the caller's order is the schedule
-    q.tiles = d_tiles; q.count = d_count; q.n = n; q.out = d_fb;
-    const int variant = visibility_variant(rt, width, height);
-    timed_launch(rt, stream, [&] { return launch_tile_list(rt->scene, q, stream, variant); });
-    record(rt, width, height, 0, variant);                               // (the library does not know which tiles the list names)
-}
-
-// ---- the deferred stages over a tile list in device memory (rrt.h: rrt_render_visibility_tile_list_device and its three neighbours).  The checks are the region
-// calls' with no region (region_in_force(NULL) is the whole frame and refuses nothing) and the list's; the planes are whole-frame planes.
-// the list fields of a stage's argument
-TileList tile_list_of(const rrt_raytracer* rt, uint32_t width, uint32_t height, uint32_t n, const uint32_t* d_count, const uint32_t* d_tiles) {
-    TileList l{};
-    l.F = frame_params(rt, width, height, 0, 1, false);
-    l.F.xcd_chunk = 0;                                                   // the caller's order is the schedule
-    l.tiles = d_tiles; l.count = d_count; l.n = n;
-    return l;
-}
-// The checks of a list, behind those of the stage: false for the empty list, which launches nothing.
-bool check_tile_list(uint32_t n, const uint32_t* d_tiles) {
-    if (n > kMaxTileList) throw Error{RRT_ERR_INVALID_ARG, "the list is longer than RRT_MAX_TILE_LIST entries: its grid would not fit a launch"};
-    if (n == 0) return false;                                            // nothing is launched, rrt_last_stats stays as it was
-    if (!d_tiles) throw Error{RRT_ERR_INVALID_ARG, "null tile list"};
-    return true;
-}
-// The one tile-stage launch, shaped like launch_tile_list_frame: the finished kernel argument q on the caller's stream, timed and recorded.
-template <class Params> void launch_tile_stage_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const Params& q, void* stream) {
-    const int variant = visibility_variant(rt, width, height);
-    timed_launch(rt, stream, [&] { return launch_tile_stage(rt->scene, q, stream, variant); });
-    record(rt, width, height, 0, variant);                               // (the library does not know which tiles the list names)
-}
-VisTileListParams vis_tile_list_params(const TileList& l, const rrt_visibility& d_planes) {
-    VisTileListParams p{};
-    p.L = l;
-    p.hit = d_planes.hit; p.t = d_planes.t; p.u = d_planes.u; p.v = d_planes.v; p.tri = d_planes.tri; p.albedo = d_planes.albedo;
-    return p;
-}
-void launch_surface_tile_list(rrt_raytracer* rt, uint32_t width, uint32_t height, const TileList& l, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* stream) {
-    SurfaceTileListParams q{};
-    q.V = vis_tile_list_params(l, d_vis);
-    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.lights = d_planes.lights;
-    launch_tile_stage_frame(rt, width, height, q, stream);
-}
-void launch_shade_tile_list(rrt_raytracer* rt, uint32_t width, uint32_t height, const TileList& l, const rrt_visibility& d_vis, const rrt_surface& d_planes, void* d_fb, void* stream) {
-    ShadeTileListParams q{};
-    q.L = l;
-    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material; q.albedo = d_vis.albedo; q.lights = d_planes.lights;
-    q.out = static_cast<uint32_t*>(d_fb);
-    launch_tile_stage_frame(rt, width, height, q, stream);
 }
 
 // ---- tile selection: tests over planes that produce the list of a tile-list frame (rrt.h: rrt_mark_tiles, rrt_select_tiles; tiles.hip).  Not ray calls: no
@@ -354,28 +329,11 @@ rrt_region check_ambient(const rrt_raytracer* rt, uint32_t width, uint32_t heigh
     return region_in_force(width, height, region);
 }
 
-// the masks and grey pixels of region r (checked) from planes in device memory.  The sample table is copied into the kernel's argument here: no device memory holds it.
-void launch_ambient_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const rrt_region& r, const rrt_surface& d_planes, const rrt_ambient_samples& samples,
+// the masks and grey pixels of a region or a list (checked) from planes in device memory
+template <class Front>
+void launch_ambient_frame(rrt_raytracer* rt, uint32_t width, uint32_t height, const Place<Front>& at, const rrt_surface& d_planes, const rrt_ambient_samples& samples,
                           const rrt_ambient& d_out, void* stream) {
-    AmbientParams q{};
-    q.V = vis_params(rt, width, height, r, rrt_visibility{});            // (the kernel writes no visibility plane)
-    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material;
-    q.occluded = d_out.occluded; q.grey = d_out.grey;
-    q.n_samples = samples.n; q.max_t = samples.max_t;
-    std::memcpy(q.dirs, samples.dirs, sizeof(double) * 3 * samples.n);
-    launch_region_frame(rt, width, height, r, q, stream);
-}
-
-// the same over a tile list: the table travels as in launch_ambient_frame
-void launch_ambient_tile_list(rrt_raytracer* rt, uint32_t width, uint32_t height, const TileList& l, const rrt_surface& d_planes, const rrt_ambient_samples& samples,
-                              const rrt_ambient& d_out, void* stream) {
-    AmbientTileListParams q{};
-    q.L = l;
-    q.point = d_planes.point; q.normal = d_planes.normal; q.material = d_planes.material;
-    q.occluded = d_out.occluded; q.grey = d_out.grey;
-    q.n_samples = samples.n; q.max_t = samples.max_t;
-    std::memcpy(q.dirs, samples.dirs, sizeof(double) * 3 * samples.n);
-    launch_tile_stage_frame(rt, width, height, q, stream);
+    launch_stage_frame(rt, width, height, AmbientStage<Front>{bare(at.front), ambient_planes(d_planes, samples, d_out)}, at.rays_primary, stream);
 }
 
 // Host form: the three planes up, the requested outputs down.
@@ -388,7 +346,7 @@ void ambient_from_host(rrt_raytracer* rt, uint32_t width, uint32_t height, const
     const size_t count[kAmb] = {n, px};                                  // occluded per sub-sample, grey per pixel
     mirror_planes(pl + kSurf, out, count, FieldDirs<rrt_ambient>::every(kDown));
     with_kept_planes(rt, pl, [&](void* stream) {
-        launch_ambient_frame(rt, width, height, r, mirrored<rrt_surface>(pl), samples, mirrored<rrt_ambient>(pl + kSurf), stream);
+        launch_ambient_frame(rt, width, height, in_region(rt, width, height, r), mirrored<rrt_surface>(pl), samples, mirrored<rrt_ambient>(pl + kSurf), stream);
     });
 }
 
@@ -400,7 +358,7 @@ int rrt_render_visibility_device(rrt_raytracer* rt, uint32_t width, uint32_t hei
     return guarded([&]() -> int {
         const rrt_region r = check_visibility(rt, width, height, region, d_planes);
         DeviceGuard guard(rt->device);
-        launch_visibility_frame(rt, width, height, r, *d_planes, stream);
+        launch_visibility_frame(rt, width, height, in_region(rt, width, height, r), *d_planes, stream);
         return RRT_OK;
     });
 }
@@ -418,7 +376,7 @@ int rrt_render_surface_device(rrt_raytracer* rt, uint32_t width, uint32_t height
     return guarded([&]() -> int {
         const rrt_region r = check_surface(rt, width, height, region, d_planes);
         DeviceGuard guard(rt->device);
-        launch_surface_frame(rt, width, height, r, d_vis ? *d_vis : rrt_visibility{}, *d_planes, stream);
+        launch_surface_frame(rt, width, height, in_region(rt, width, height, r), d_vis ? *d_vis : rrt_visibility{}, *d_planes, stream);
         return RRT_OK;
     });
 }
@@ -436,7 +394,7 @@ int rrt_shade_surface_device(rrt_raytracer* rt, uint32_t width, uint32_t height,
     return guarded([&]() -> int {
         const rrt_region r = check_shade(rt, width, height, region, d_vis, d_planes, d_fb);
         DeviceGuard guard(rt->device);
-        launch_shade_frame(rt, width, height, r, *d_vis, *d_planes, d_fb, stream);
+        launch_shade_frame(rt, width, height, in_region(rt, width, height, r), *d_vis, *d_planes, d_fb, stream);
         return RRT_OK;
     });
 }
@@ -472,11 +430,10 @@ int rrt_render_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32_t heig
     return guarded([&]() -> int {
         check_frame(rt, width, height);
         if (!d_fb) throw Error{RRT_ERR_INVALID_ARG, "null framebuffer"};
-        if (n > kMaxTileList) throw Error{RRT_ERR_INVALID_ARG, "the list is longer than RRT_MAX_TILE_LIST entries: its grid would not fit a launch"};
-        if (n == 0) return RRT_OK;                                         // nothing is launched, rrt_last_stats stays as it was
-        if (!d_tiles) throw Error{RRT_ERR_INVALID_ARG, "null tile list"};
+        if (!check_tile_list(n, d_tiles)) return RRT_OK;
         DeviceGuard guard(rt->device);
-        launch_tile_list_frame(rt, width, height, n, d_count, d_tiles, d_fb, stream);
+        const Place<TileList> at = in_list(rt, width, height, n, d_count, d_tiles);
+        launch_stage_frame(rt, width, height, TileListParams{at.front, d_fb}, at.rays_primary, stream);
         return RRT_OK;
     });
 }
@@ -487,7 +444,7 @@ int rrt_render_visibility_tile_list_device(rrt_raytracer* rt, uint32_t width, ui
         check_visibility(rt, width, height, nullptr, d_planes);
         if (!check_tile_list(n, d_tiles)) return RRT_OK;
         DeviceGuard guard(rt->device);
-        launch_tile_stage_frame(rt, width, height, vis_tile_list_params(tile_list_of(rt, width, height, n, d_count, d_tiles), *d_planes), stream);
+        launch_visibility_frame(rt, width, height, in_list(rt, width, height, n, d_count, d_tiles), *d_planes, stream);
         return RRT_OK;
     });
 }
@@ -498,7 +455,7 @@ int rrt_render_surface_tile_list_device(rrt_raytracer* rt, uint32_t width, uint3
         check_surface(rt, width, height, nullptr, d_planes);
         if (!check_tile_list(n, d_tiles)) return RRT_OK;
         DeviceGuard guard(rt->device);
-        launch_surface_tile_list(rt, width, height, tile_list_of(rt, width, height, n, d_count, d_tiles), d_vis ? *d_vis : rrt_visibility{}, *d_planes, stream);
+        launch_surface_frame(rt, width, height, in_list(rt, width, height, n, d_count, d_tiles), d_vis ? *d_vis : rrt_visibility{}, *d_planes, stream);
         return RRT_OK;
     });
 }
@@ -509,7 +466,7 @@ int rrt_shade_surface_tile_list_device(rrt_raytracer* rt, uint32_t width, uint32
         check_shade(rt, width, height, nullptr, d_vis, d_planes, d_fb);
         if (!check_tile_list(n, d_tiles)) return RRT_OK;
         DeviceGuard guard(rt->device);
-        launch_shade_tile_list(rt, width, height, tile_list_of(rt, width, height, n, d_count, d_tiles), *d_vis, *d_planes, d_fb, stream);
+        launch_shade_frame(rt, width, height, in_list(rt, width, height, n, d_count, d_tiles), *d_vis, *d_planes, d_fb, stream);
         return RRT_OK;
     });
 }
@@ -520,7 +477,7 @@ int rrt_ambient_surface_tile_list_device(rrt_raytracer* rt, uint32_t width, uint
         check_ambient(rt, width, height, nullptr, d_planes, samples, d_out);
         if (!check_tile_list(n, d_tiles)) return RRT_OK;
         DeviceGuard guard(rt->device);
-        launch_ambient_tile_list(rt, width, height, tile_list_of(rt, width, height, n, d_count, d_tiles), *d_planes, *samples, *d_out, stream);
+        launch_ambient_frame(rt, width, height, in_list(rt, width, height, n, d_count, d_tiles), *d_planes, *samples, *d_out, stream);
         return RRT_OK;
     });
 }
@@ -575,7 +532,7 @@ int rrt_ambient_surface_device(rrt_raytracer* rt, uint32_t width, uint32_t heigh
     return guarded([&]() -> int {
         const rrt_region r = check_ambient(rt, width, height, region, d_planes, samples, d_out);
         DeviceGuard guard(rt->device);
-        launch_ambient_frame(rt, width, height, r, *d_planes, *samples, *d_out, stream);
+        launch_ambient_frame(rt, width, height, in_region(rt, width, height, r), *d_planes, *samples, *d_out, stream);
         return RRT_OK;
     });
 }

@@ -32,8 +32,9 @@
 #include "specular_skip.hpp"
 
 // The library compiles this file THREE times (csrc/Makefile), same device functions, different code-generation switches per group of kernels:
-//   -DRRT_TU=1  the bundle-filter frame, visibility, surface, shade and ambient kernels, detile_kernel and the launchers (issue-bound: max-ILP scheduler);
-//   -DRRT_TU=3  the lane-filter and ray-walk frame, visibility, surface, shade and ambient kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
+//   -DRRT_TU=1  the bundle-filter frame kernel and stage kernels (visibility, surface, shade, ambient, fused colour: a region form and a tile-list form each),
+//               detile_kernel and the launchers (issue-bound: max-ILP scheduler);
+//   -DRRT_TU=3  the lane-filter and ray-walk frame kernels and stage kernels (as 1, plus the structurizer / load-store-vectorizer switches that gain the 1 M soup 5 %
 //               and cost the bundle-filter kernel 2.6 % on the teapot);
 //   -DRRT_TU=2  the per-ray kernels ray_colour_kernel, intersect_kernel, occlusion_kernel, surface_rays_kernel, shade_rays_kernel, ambient_rays_kernel, resolve_hits_kernel (default scheduler: max-ILP costs scattered rays 17 %).
 // Without RRT_TU: everything in one unit (developer builds, tools).
@@ -1896,13 +1897,19 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
     }
 }
 
-// ---- what the region kernels (visibility, surface, shade, ambient) share.  render_kernel and trace_colour do NOT call these: a helper shared with them changes the
-// register allocation of the frame kernels (profiles/visibility_kernel_resources.txt, profiles/region_kernels_shared_setup.txt), so they keep the original text.
+// ---- the stage kernels: visibility, surface, shade, ambient and the fused colour, each ONE body behind two front ends -- a region of a frame and a list of tiles
+// in device memory (device_scene.hpp: Region, TileList).  A front end says which pixel and sub-sample a lane is (px, py, sub), whether its wave takes part at all
+// (listed), whether the lane stores (stores) and whether it is one of the pixels the reference traces (traced), and where the pixel lies in the stage's planes
+// (stage_pixel); everything after that is the stage's, written once.  Both forms are 4x4-pixel waves from the one origin with the same arguments to walk,
+// surface_body and shade_body.  render_kernel and trace_colour do NOT call these: a helper shared with them changes the register allocation of the frame kernels
+// (profiles/visibility_kernel_resources.txt, profiles/region_kernels_shared_setup.txt), so they keep the original text.  Whether a body may be shared is decided per
+// kernel by its resource lines and, where its assembly moves, by its time: profiles/stage_bodies_two_front_ends.txt.
+struct StageLane { uint32_t px, py, sub; bool listed, stores, traced; };
 // A lane of a region launch: block order, tile quadrant, pixel and sub-sample are render_kernel's, but the tiles are those of the region's tile rectangle (tiles_w per
-// row from (tile_x0, tile_y0)) instead of a rank's share of the frame.  in_region: the pixel lies in the region (col_end <= width, row_end <= height); only such lanes
-// store anything.  traced: it is also one of the pixels the reference traces (render_kernel); only such lanes walk a primary ray or read a kept plane.
-struct RegionLane { uint32_t px, py, sub; bool in_region, traced; };
-__device__ __forceinline__ RegionLane region_lane(const VisParams& P, uint32_t lane) {
+// row from (tile_x0, tile_y0)) instead of a rank's share of the frame.  listed: always -- a compile-time true.  stores: the pixel lies in the region (col_end <=
+// width, row_end <= height); only such lanes store anything.  traced: it is also one of the pixels the reference traces (render_kernel); only such lanes walk a
+// primary ray or read a kept plane.
+__device__ __forceinline__ StageLane stage_lane(const Region& P, uint32_t lane) {
     const FrameParams& F = P.F;
     uint32_t blk = blockIdx.x;
     if (F.xcd_chunk) {
@@ -1918,13 +1925,37 @@ __device__ __forceinline__ RegionLane region_lane(const VisParams& P, uint32_t l
     const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
     const bool in_region = tile_ok && px >= P.col_begin && px < P.col_end && py >= F.row_begin && py < F.row_end;
     const bool traced = in_region && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;
-    return RegionLane{px, py, sub, in_region, traced};
+    return StageLane{px, py, sub, true, in_region, traced};
 }
 // The pixel's index inside the region, [rows][columns]; the element index of a sub-sample in a [rows][columns][4] plane is 4 * that + sub.  Only lanes inside the
 // region use either.
-__device__ __forceinline__ size_t region_pixel(const VisParams& P, const RegionLane& L) {
+__device__ __forceinline__ size_t stage_pixel(const Region& P, const StageLane& L) {
     return ((size_t)(L.py - P.F.row_begin) * (P.col_end - P.col_begin)) + (L.px - P.col_begin);
 }
+// A lane of a tile-list launch: block b is quadrant (b & 3) of the tile that entry (b >> 2) names.  The bound -- min(n, *count), counted_length's rule; n without
+// a count -- and the entry are wave-uniform scalar loads, only ever read.  A block at or beyond the bound is not listed, after the bound's load and a compare and
+// without reading its entry; one whose entry names no tile of the frame (0xFFFFFFFF included) is not listed either, before the entry is used as an index.  A
+// kernel leaves a wave that is not listed before it touches LDS, memory or scratch.  Then render_kernel's pixel arithmetic on the whole frame.  stores: the pixel
+// lies in the frame.  traced: as a region's.  Two blocks of a duplicate entry store the same bits.
+__device__ __forceinline__ StageLane stage_lane(const TileList& Q, uint32_t lane) {
+    const uint32_t entry = blockIdx.x >> 2, quad = blockIdx.x & 3u;
+    uint32_t m = Q.n;
+    if (Q.count) { const uint32_t c = *Q.count; m = c < m ? c : m; }                  // wave-uniform: a kernel-argument pointer
+    if (entry >= m) return StageLane{0, 0, 0, false, false, false};
+    const FrameParams& F = Q.F;
+    const uint32_t tile = Q.tiles[entry];                                              // wave-uniform too
+    if (tile >= F.tile_end) return StageLane{0, 0, 0, false, false, false};            // (tile_end = tiles_x * tiles_y: the whole frame)
+    const uint32_t pix = lane >> 2, sub = lane & 3u;
+    const uint32_t tx = tile % F.tiles_x, ty = tile / F.tiles_x;
+    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
+    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
+    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
+    const bool in_fb = (int32_t)px < W && (int32_t)py < H;
+    const bool traced = in_fb && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;
+    return StageLane{px, py, sub, true, in_fb, traced};
+}
+// The pixel's index in the whole frame, [height][width]; a sub-sample's in a [height][width][4] plane is 4 * that + sub.
+__device__ __forceinline__ size_t stage_pixel(const TileList& Q, const StageLane& L) { return (size_t)L.py * Q.F.width + L.px; }
 // The direction of the primary ray of sub-sample `sub` of canvas pixel (px, py), as render_kernel forms it: the sub-samples (x,y),(x+.5,y),(x,y+.5),(x+.5,y+.5) of
 // engine.rs:207-236, then (right*a + up*b) + forward*c, five operations per component, each rounded on its own (rrt.h: rrt_camera).
 __device__ __forceinline__ V3 primary_direction(const FrameParams& F, uint32_t px, uint32_t py, uint32_t sub) {
@@ -1938,27 +1969,38 @@ __device__ __forceinline__ V3 primary_direction(const FrameParams& F, uint32_t p
               (F.right[1] * sa + F.up[1] * sb) + F.forward[1] * sc,
               (F.right[2] * sa + F.up[2] * sb) + F.forward[2] * sc);
 }
-// Visibility buffers (rrt.h: rrt_render_visibility_device): the first hit of every primary ray of a region of the frame -- hit, t, u, v, triangle and the
-// colour-texture texel -- instead of a colour.  The waves, their rays and their guard are render_kernel's; each ray is walked once, as intersect_kernel
-// walks it, but from the one origin (one_origin: the bundle and the parked origin are the frame kernels').  A wave covers the tile quadrant its block index
-// says; lanes outside the region or the frame are inactive for the walk and store nothing.
+// Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel: sums, truncating /4; 0 as Canvas::new where nothing
+// is traced
+__device__ __forceinline__ uint32_t mix_sub_samples(uint32_t c, bool traced) {
+    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
+    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
+    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
+    return traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;
+}
+// Visibility buffers (rrt.h: rrt_render_visibility_device, rrt_render_visibility_tile_list_device): the first hit of every primary ray of a region of the frame, or
+// of the listed tiles -- hit, t, u, v, triangle and the colour-texture texel -- instead of a colour.  The waves, their rays and their guard are render_kernel's; each
+// ray is walked once, as intersect_kernel walks it, but from the one origin (one_origin: the bundle and the parked origin are the frame kernels').  A wave covers
+// the tile quadrant its front end says; lanes outside the region or the frame are inactive for the walk and store nothing.
 // Planes are [row][column][sub-sample]: the 16 lanes of one pixel row of a wave (4 pixels x 4 sub-samples) write one contiguous segment, 128 B of an f64
 // plane, 64 B of tri / albedo, 16 B of hit.  The plane pointers are kernel arguments: each test is wave-uniform.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const DevScene S, const VisParams P) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
+template <int kWalk, bool kGroups, class Params>
+__global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const DevScene S, const Params Q) {
     const uint32_t lane = threadIdx.x;
+    const auto& R = front_end(Q.front);
+    const StageLane L = stage_lane(R, lane);
+    if (!L.listed) return;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, lane};
-    const RegionLane L = region_lane(P, lane);
+    const VisPlanes& P = Q.vis;
     const uint32_t sub = L.sub;
-    const bool in_region = L.in_region, traced = L.traced;
-    const V3 o = ld3(S.origin), d = primary_direction(P.F, L.px, L.py, sub);
+    const bool stores = L.stores, traced = L.traced;
+    const V3 o = ld3(S.origin), d = primary_direction(R.F, L.px, L.py, sub);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
     double t; uint32_t slot;
     walk<kWalk, kGroups>(PROF_ARG S, stk, traced, false, !origin_ray_in_suspect_plane(S, o, d), true, o, d, kInf, t, slot);
-    if (!in_region) return;
+    if (!stores) return;
     const bool found = traced && slot != kNone;
     double u = 0, v = 0;
     uint32_t tri = kNone;
@@ -1969,7 +2011,7 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const Dev
     } else {
         t = 0;                                                                           // the miss convention of intersect_kernel; a pixel the reference never traces reads as a miss
     }
-    const size_t i = region_pixel(P, L) * 4 + sub;
+    const size_t i = stage_pixel(R, L) * 4 + sub;
     if (P.albedo) {
         uint32_t col = traced ? 0x00FFFFFFu : 0u;                                        // WHITE, raytracer.rs:109-111; 0 as Canvas::new where nothing is traced
         if (found) {
@@ -1994,31 +2036,34 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void visibility_kernel(const Dev
     if (P.tri) P.tri[i] = tri;
 }
 
-// Surface buffers (rrt.h: rrt_render_surface_device): per primary ray of a region of the frame the hit point, the shading normal, the material index and
+// Surface buffers (rrt.h: rrt_render_surface_device, rrt_render_surface_tile_list_device): per primary ray the hit point, the shading normal, the material index and
 // the mask of the lights that reach the point -- what trace_colour holds for the primary segment on its way to a colour -- and, if asked for, the
-// visibility planes of the same rays from the same launch.  Waves, rays, guard, region and plane layout are visibility_kernel's (point and normal: three
+// visibility planes of the same rays from the same launch.  Waves, rays, guard, front ends and plane layout are visibility_kernel's (point and normal: three
 // doubles per sub-sample, 384 B per pixel row of a wave).  The loop is surface_body's: the primary rays are the traced lanes', from the one origin, unbounded;
 // everything is wanted but the lights, which follow the lights plane (a kernel argument: wave-uniform).  0 as Canvas::new for the texel where nothing is traced.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevScene S, const SurfaceParams Q) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
+template <int kWalk, bool kGroups, class Params>
+__global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevScene S, const Params Q) {
     const uint32_t lane = threadIdx.x;
+    const auto& R = front_end(Q.front);
+    const StageLane L = stage_lane(R, lane);
+    if (!L.listed) return;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, lane};
-    const VisParams& P = Q.V;
-    const RegionLane L = region_lane(P, lane);
+    const VisPlanes& P = Q.vis;
+    const SurfacePlanes& O = Q.planes;
     const uint32_t sub = L.sub;
-    const bool in_region = L.in_region, traced = L.traced;
-    const V3 o = ld3(S.origin), d = primary_direction(P.F, L.px, L.py, sub);
+    const bool stores = L.stores, traced = L.traced;
+    const V3 o = ld3(S.origin), d = primary_direction(R.F, L.px, L.py, sub);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    const SurfaceHit h = surface_body<kWalk, kGroups>(PROF_ARG S, stk, traced, true, o, d, kInf, traced ? 0x00FFFFFFu : 0u, true, true, true, Q.lights != nullptr);
-    if (!in_region) return;
-    const size_t i = region_pixel(P, L) * 4 + sub;
-    if (Q.point) { Q.point[3 * i] = h.p.x; Q.point[3 * i + 1] = h.p.y; Q.point[3 * i + 2] = h.p.z; }
-    if (Q.normal) { Q.normal[3 * i] = h.n.x; Q.normal[3 * i + 1] = h.n.y; Q.normal[3 * i + 2] = h.n.z; }
-    if (Q.material) Q.material[i] = h.mat;
-    if (Q.lights) Q.lights[i] = h.mask;
+    const SurfaceHit h = surface_body<kWalk, kGroups>(PROF_ARG S, stk, traced, true, o, d, kInf, traced ? 0x00FFFFFFu : 0u, true, true, true, O.lights != nullptr);
+    if (!stores) return;
+    const size_t i = stage_pixel(R, L) * 4 + sub;
+    if (O.point) { O.point[3 * i] = h.p.x; O.point[3 * i + 1] = h.p.y; O.point[3 * i + 2] = h.p.z; }
+    if (O.normal) { O.normal[3 * i] = h.n.x; O.normal[3 * i + 1] = h.n.y; O.normal[3 * i + 2] = h.n.z; }
+    if (O.material) O.material[i] = h.mat;
+    if (O.lights) O.lights[i] = h.mask;
     // the visibility planes, as visibility_kernel writes them
     if (P.albedo) P.albedo[i] = h.col;
     if (P.hit) P.hit[i] = h.found ? 1 : 0;
@@ -2028,26 +2073,29 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void surface_kernel(const DevSce
     if (P.tri) P.tri[i] = h.tri;
 }
 
-// Shading from kept buffers (rrt.h: rrt_shade_surface_device): the colour of every pixel of a region of the frame from the planes surface_kernel wrote for it --
-// point, normal, material, albedo and, if given, the lights mask -- with the lights and materials in force NOW.  No primary ray is walked: a sub-sample enters
+// Shading from kept buffers (rrt.h: rrt_shade_surface_device, rrt_shade_surface_tile_list_device): the colour of every pixel from the planes surface_kernel wrote for
+// it -- point, normal, material, albedo and, if given, the lights mask -- with the lights and materials in force NOW.  No primary ray is walked: a sub-sample enters
 // shade_body as the primary segment's hit (the segment direction is recomputed from the pixel and the pose) at recursion depth 0, so all of
 // max_reflection_depth is its room; the colour is always wanted and no record is kept.  With a mask (a kernel argument: wave-uniform) the lights the depth-0 sum
 // adds up are [0, min(ctz(~mask), n_lights)) and no depth-0 shadow ray is formed.
-// A material index at or beyond the table (0xFFFFFFFF: a miss) is WHITE; no other value of the caller's planes is used as an index.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene S, const ShadeParams Q) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
+// A lane reads its planes only if it is traced: of a list, nothing is read outside the listed tiles.  A material index at or beyond the table (0xFFFFFFFF: a
+// miss) is WHITE; no other value of the caller's planes is used as an index.
+template <int kWalk, bool kGroups, class Params>
+__global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene S, const Params Q) {
     const uint32_t lane = threadIdx.x;
+    const auto& R = front_end(Q.front);
+    const StageLane L = stage_lane(R, lane);
+    if (!L.listed) return;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, lane};
-    const VisParams& P = Q.V;
-    const RegionLane L = region_lane(P, lane);
+    const ShadePlanes& P = Q.planes;
     const uint32_t sub = L.sub;
-    const bool in_region = L.in_region, traced = L.traced;
-    const V3 seg_d = primary_direction(P.F, L.px, L.py, sub);
+    const bool stores = L.stores, traced = L.traced;
+    const V3 seg_d = primary_direction(R.F, L.px, L.py, sub);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    const size_t pixel_i = region_pixel(P, L), i = pixel_i * 4 + sub;
+    const size_t pixel_i = stage_pixel(R, L), i = pixel_i * 4 + sub;
     // ---- the five values: the primary segment's hit
     bool live = false;                      // the lane holds a hit whose colour is not known yet
     V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
@@ -2055,13 +2103,13 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
     uint32_t n_eval = 0;                    // lights [0, n_eval) contribute (an occluded point light ends the loop, raytracer.rs:235-237)
     uint32_t term = 0x00FFFFFFu;            // colour of the last segment; WHITE for a miss, raytracer.rs:109-111
     if (traced) {
-        mat = Q.material[i];
+        mat = P.material[i];
         if (mat < S.n_mats) {               // (0xFFFFFFFF, a miss, and anything else beyond the table: WHITE)
             live = true;
-            p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
-            col = Q.albedo[i] & 0x00FFFFFFu;
-            if (Q.lights) {                 // the kept mask answers the depth-0 shadow queries: the light loop of shade_body is skipped for this hit
-                const uint32_t first_dark = (uint32_t)__builtin_ctz(~Q.lights[i] | (1u << RRT_MAX_LIGHTS));   // (n_lights <= 16: bits at and above it never count)
+            p = ld3(P.point + 3 * i); n = ld3(P.normal + 3 * i);
+            col = P.albedo[i] & 0x00FFFFFFu;
+            if (P.lights) {                 // the kept mask answers the depth-0 shadow queries: the light loop of shade_body is skipped for this hit
+                const uint32_t first_dark = (uint32_t)__builtin_ctz(~P.lights[i] | (1u << RRT_MAX_LIGHTS));   // (n_lights <= 16: bits at and above it never count)
                 n_eval = first_dark < S.n_lights ? first_dark : S.n_lights;
                 li = 0xFFFFu;
             }
@@ -2069,18 +2117,14 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
     }
     double st_local[RRT_MAX_REFLECT][3]; double st_kr[RRT_MAX_REFLECT];
     const ShadeEnd E = shade_body<kWalk, kGroups, false>(PROF_ARG S, stk, S.max_reflection_depth, true, live, seg_d, p, n, col, mat, li, depth, n_eval, term, st_local, st_kr);
-    const uint32_t c = shade_unwind(E.term, E.lvl, st_local, st_kr);
-    // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
-    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
-    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
-    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
-    const uint32_t mixed = traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;   // 0 as Canvas::new where nothing is traced
-    if (sub == 0 && in_region) Q.out[pixel_i] = mixed;
+    const uint32_t mixed = mix_sub_samples(shade_unwind(E.term, E.lvl, st_local, st_kr), traced);
+    if (sub == 0 && stores) P.out[pixel_i] = mixed;
 }
 
-// Ambient occlusion from kept buffers (rrt.h: rrt_ambient_surface_device): per sub-sample of a region of the frame a mask of which of n hemisphere rays from its
-// hit are occluded, and per pixel the share of open rays as a grey value, from the point, normal and material planes surface_kernel wrote.  No primary ray is
-// walked.  A lane loads its hit and builds the reference's tangent frame (raytracer.rs:137-152, the helpers of surface_kernel's bump frame) ONCE; the loop is over
+// Ambient occlusion from kept buffers (rrt.h: rrt_ambient_surface_device, rrt_ambient_surface_tile_list_device): per sub-sample a mask of which of n hemisphere rays
+// from its hit are occluded, and per pixel the share of open rays as a grey value, from the point, normal and material planes surface_kernel wrote.  No primary
+// ray is walked.  A lane loads its hit -- only if it is traced -- and builds the reference's tangent frame (raytracer.rs:137-152, the helpers of surface_kernel's
+// bump frame) ONCE; the loop is over
 // the SAMPLES: sample k of the table -- kernel arguments, wave-uniform, scalar registers -- gives every hit lane of the wave its ray k, so a turn walks the 64
 // rays that share a direction in their tangent frames (neighbouring hits of one surface: nearly parallel rays from nearly the same place, a tight bundle) and
 // keeps one bit per lane.  The rays live in registers only.
@@ -2089,27 +2133,29 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void shade_kernel(const DevScene
 // A material index at or beyond the table (0xFFFFFFFF: a miss) is a miss; no value of the caller's planes is used as an index.
 // The sample loop is restated in ambient_rays_kernel, unlike the surface and shade loops, which have one body for both forms: with one body ambient_rays_kernel<0> gains scratch, and
 // the timing that would then decide was not taken (profiles/shared_query_bodies.txt, section 3).
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevScene S, const AmbientParams Q) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
+template <int kWalk, bool kGroups, class Params>
+__global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevScene S, const Params Q) {
     const uint32_t lane = threadIdx.x;
+    const auto& R = front_end(Q.front);
+    const StageLane L = stage_lane(R, lane);                                             // (no direction is formed from the pixel here)
+    if (!L.listed) return;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, lane};
-    const VisParams& P = Q.V;
-    const RegionLane L = region_lane(P, lane);                                           // (no direction is formed from the pixel here)
+    const AmbientPlanes& P = Q.planes;
     const uint32_t sub = L.sub;
-    const bool in_region = L.in_region, traced = L.traced;
+    const bool stores = L.stores, traced = L.traced;
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    const size_t pixel_i = region_pixel(P, L), i = pixel_i * 4 + sub;
+    const size_t pixel_i = stage_pixel(R, L), i = pixel_i * 4 + sub;
     // ---- the lane's hit
     bool hit = false;
     V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
-    if (traced && Q.material[i] < S.n_mats) {   // (0xFFFFFFFF, a miss, and anything else beyond the table: a miss -- shade_kernel's rule)
+    if (traced && P.material[i] < S.n_mats) {   // (0xFFFFFFFF, a miss, and anything else beyond the table: a miss -- shade_kernel's rule)
         hit = true;
-        p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
+        p = ld3(P.point + 3 * i); n = ld3(P.normal + 3 * i);
     }
-    const uint32_t n_samples = Q.n_samples;
+    const uint32_t n_samples = P.n_samples;
     uint32_t mask = 0;
     if (__any(hit)) {
         // the tangent frame of the hit, once for all samples
@@ -2117,15 +2163,15 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevSce
         if (hit) tangent_frame(n, tg, bt);
         const V3 ro = p + n * S.surface_offset;                                          // the origin of a shadow ray, raytracer.rs:170
         for (uint32_t k = 0; k < n_samples; k++) {
-            const double sx = Q.dirs[k][0], sy = Q.dirs[k][1], sz = Q.dirs[k][2];        // wave-uniform
+            const double sx = P.dirs[k][0], sy = P.dirs[k][1], sz = P.dirs[k][2];        // wave-uniform
             // (tg*sx + bt*sy) + n*sz, per component five operations, each rounded on its own: the shape of rrt_camera.  (a lane without a hit takes no part; its
             // ray is a harmless one)
             const V3 rd = hit ? mk((tg.x * sx + bt.x * sy) + n.x * sz, (tg.y * sx + bt.y * sy) + n.y * sz, (tg.z * sx + bt.z * sy) + n.z * sz) : mk(0, 0, 1);
             double wt; uint32_t wslot;
             // (the dispatch restated, not walk<>: with the wrapper four of this kernel's six instantiations change 21-29 lines of assembly and would have to be timed
             // like a shared body -- profiles/shared_query_bodies.txt)
-            if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, hit, true, true, ro, rd, Q.max_t, wt, wslot);
-            else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, hit, true, true, false, ro, rd, Q.max_t, wt, wslot);
+            if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, hit, true, true, ro, rd, P.max_t, wt, wslot);
+            else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, hit, true, true, false, ro, rd, P.max_t, wt, wslot);
             if (hit && wslot != kNone) mask |= 1u << k;
         }
     }
@@ -2133,297 +2179,49 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void ambient_kernel(const DevSce
     uint32_t open = traced ? (hit ? n_samples - (uint32_t)__popc(mask) : n_samples) : 0u;
     open += __shfl_xor(open, 1);
     open += __shfl_xor(open, 2);
-    if (!in_region) return;
-    if (Q.occluded) Q.occluded[i] = mask;
-    if (Q.grey && sub == 0) Q.grey[pixel_i] = traced ? ((510u * open + 4u * n_samples) / (8u * n_samples)) * 0x010101u : 0u;
+    if (!stores) return;
+    if (P.occluded) P.occluded[i] = mask;
+    if (P.grey && sub == 0) P.grey[pixel_i] = traced ? ((510u * open + 4u * n_samples) / (8u * n_samples)) * 0x010101u : 0u;
 }
 
-// The fused frame of a region (rrt.h: rrt_render_region_device): the colour of every pixel of a region of the frame, as render_kernel computes it -- the primary
-// walk, the lights, the reflection chain and the unwind in one body, trace_colour's, nothing kept in memory on the way.  Waves, rays and region are
-// visibility_kernel's (lanes outside the region or the traced area take part in no walk); the mix and the guard of the store are shade_kernel's.  The pixel goes
-// to its place in rows of Q.pitch elements: with pitch = the frame's width and `out` at the region's first pixel, into a whole framebuffer.  Nothing outside the
-// region's pixels is read or written.  No coverage mask: the mask is indexed by the whole frame's block order.  No lane leaves before the walk.
-// Registers, scratch and occupancy are recorded beside render_kernel's, not tuned: profiles/region_render_kernel_resources.txt.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void render_region_kernel(const DevScene S, const RenderRegionParams Q) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
+// The fused colour (rrt.h: rrt_render_region_device, rrt_render_tile_list_device): the colour of every pixel of a region of the frame, or of the listed tiles, as
+// render_kernel computes it -- the primary walk, the lights, the reflection chain and the unwind in one body, trace_colour's, nothing kept in memory on the way.
+// Waves, rays and front ends are visibility_kernel's (lanes outside the region or the traced area take part in no walk); the mix and the guard of the store are
+// shade_kernel's.  Where the pixel goes is the front end's: of a region, into rows of Q.pitch elements -- with pitch = the frame's width and `out` at the region's
+// first pixel, into a whole framebuffer; of a list, into its place in the whole framebuffer.  Nothing outside the region's or the listed tiles' pixels is read or
+// written.  No coverage mask: the mask is indexed by the whole frame's block order.  No lane leaves before the walk.
+__device__ __forceinline__ size_t colour_pixel(const RenderRegionParams& Q, const StageLane& L) {
+    return (size_t)(L.py - Q.front.front.F.row_begin) * Q.pitch + (L.px - Q.front.front.col_begin);
+}
+__device__ __forceinline__ size_t colour_pixel(const TileListParams& Q, const StageLane& L) { return stage_pixel(Q.front, L); }
+template <int kWalk, bool kGroups, class Params>
+__global__ __launch_bounds__(64, kWavesPerSimd) void colour_kernel(const DevScene S, const Params Q) {
     const uint32_t lane = threadIdx.x;
-    const Stack stk{lds + kParkBytes, lane};
-    const VisParams& P = Q.V;
-    const RegionLane L = region_lane(P, lane);
-    const uint32_t sub = L.sub;
-    const bool in_region = L.in_region, traced = L.traced;
-    const V3 dir = primary_direction(P.F, L.px, L.py, sub);
-#ifdef RRT_PROFILE
-    Prof prof{}; prof.last = 0;
-#endif
-    const uint32_t c = trace_colour<kWalk, kGroups, true>(PROF_ARG S, stk, traced, ld3(S.origin), dir);
-    // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
-    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
-    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
-    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
-    const uint32_t mixed = traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;   // 0 as Canvas::new where nothing is traced
-    if (sub == 0 && in_region) Q.out[(size_t)(L.py - P.F.row_begin) * Q.pitch + (L.px - P.col_begin)] = mixed;
-}
-
-// The fused frame of a list of tiles (rrt.h: rrt_render_tile_list_device): block b renders quadrant (b & 3) of the tile that entry (b >> 2) of a list in device
-// memory names, into its place in the whole framebuffer.  The bound -- min(n, *count), counted_length's rule; n without a count -- and the entry are
-// wave-uniform: scalar loads, only ever read.  A block at or beyond the bound leaves after that load and a compare, before it touches LDS or memory and without
-// reading its entry; an entry that names no tile of the frame (0xFFFFFFFF included) is skipped by the whole wave, before it is used as an index.  From (tx, ty)
-// on it is render_kernel's pixel arithmetic on the whole frame and the body of render_region_kernel.  Two blocks of a duplicate entry store the same bits.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void render_tile_list_kernel(const DevScene S, const TileListParams Q) {
-    const uint32_t entry = blockIdx.x >> 2, quad = blockIdx.x & 3u;
-    uint32_t m = Q.n;
-    if (Q.count) { const uint32_t c = *Q.count; m = c < m ? c : m; }                  // wave-uniform: a kernel-argument pointer
-    if (entry >= m) return;
-    const FrameParams& F = Q.F;
-    const uint32_t tile = Q.tiles[entry];                                              // wave-uniform too
-    if (tile >= F.tile_end) return;                                                    // (tile_end = tiles_x * tiles_y: the whole frame)
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const uint32_t lane = threadIdx.x;
-    const Stack stk{lds + kParkBytes, lane};
-    const uint32_t pix = lane >> 2, sub = lane & 3u;
-    const uint32_t tx = tile % F.tiles_x, ty = tile / F.tiles_x;
-    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
-    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
-    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
-    const bool in_fb = (int32_t)px < W && (int32_t)py < H;
-    const bool traced = in_fb && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;
-    const V3 dir = primary_direction(F, px, py, sub);
-#ifdef RRT_PROFILE
-    Prof prof{}; prof.last = 0;
-#endif
-    const uint32_t c = trace_colour<kWalk, kGroups, true>(PROF_ARG S, stk, traced, ld3(S.origin), dir);
-    // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
-    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
-    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
-    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
-    const uint32_t mixed = traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;   // 0 as Canvas::new where nothing is traced
-    if (sub == 0 && in_fb) Q.out[(size_t)py * F.width + px] = mixed;
-}
-
-// ---- the deferred stages over a list of tiles (rrt.h: rrt_render_visibility_tile_list_device, rrt_render_surface_tile_list_device,
-// rrt_shade_surface_tile_list_device, rrt_ambient_surface_tile_list_device): what the region kernels above write for the whole frame, for the tiles of a list in
-// device memory only, into and from WHOLE-FRAME planes.  The front end is render_tile_list_kernel's, in one helper that only these four kernels call (no kernel
-// that existed before them does: the rule at region_lane): the bound and the entry are wave-uniform scalar loads; a block at or beyond the bound leaves after
-// the bound's load and a compare, one whose entry names no tile of the frame after the entry's, both before LDS or memory is touched; then render_kernel's pixel
-// arithmetic on the whole frame.  in_fb: the pixel lies in the frame; only such lanes store anything.  traced: as region_lane's.  The element index of a
-// sub-sample in a [height][width][4] plane is 4 * (py * width + px) + sub, of a pixel in the framebuffer or `grey` py * width + px.
-// The surface and shade kernels call surface_body and shade_body, as their region twins do; the visibility and ambient bodies are restated from
-// visibility_kernel and ambient_kernel, which have no shared body (see ambient_kernel for why its loop is text, not a helper).  No atomics, no LDS beyond the
-// walk's, no block waits on another; two blocks of a duplicate entry store the same bits.
-// Registers, scratch and occupancy are recorded beside the region twins', not tuned: profiles/tile_stage_kernel_resources.txt.
-struct TileLane { uint32_t px, py, sub; bool listed, in_fb, traced; };
-__device__ __forceinline__ TileLane tile_list_lane(const TileList& Q, uint32_t lane) {
-    const uint32_t entry = blockIdx.x >> 2, quad = blockIdx.x & 3u;
-    uint32_t m = Q.n;
-    if (Q.count) { const uint32_t c = *Q.count; m = c < m ? c : m; }                  // wave-uniform: a kernel-argument pointer
-    if (entry >= m) return TileLane{0, 0, 0, false, false, false};
-    const FrameParams& F = Q.F;
-    const uint32_t tile = Q.tiles[entry];                                              // wave-uniform too
-    if (tile >= F.tile_end) return TileLane{0, 0, 0, false, false, false};             // (tile_end = tiles_x * tiles_y: the whole frame)
-    const uint32_t pix = lane >> 2, sub = lane & 3u;
-    const uint32_t tx = tile % F.tiles_x, ty = tile / F.tiles_x;
-    const uint32_t px = tx * 8 + (quad & 1u) * 4 + (pix & 3u);
-    const uint32_t py = ty * 8 + (quad >> 1) * 4 + (pix >> 2);
-    const int32_t W = (int32_t)F.width, H = (int32_t)F.height;
-    const bool in_fb = (int32_t)px < W && (int32_t)py < H;
-    const bool traced = in_fb && (int32_t)px < 2 * (W / 2) && (int32_t)py >= H - 2 * (H / 2) + 1;
-    return TileLane{px, py, sub, true, in_fb, traced};
-}
-
-// visibility_kernel over a tile list.  The body from the walk on is visibility_kernel's, restated; in_fb stands where in_region stood.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void visibility_tile_list_kernel(const DevScene S, const VisTileListParams P) {
-    const uint32_t lane = threadIdx.x;
-    const TileLane L = tile_list_lane(P.L, lane);
+    const auto& R = front_end(Q.front);
+    const StageLane L = stage_lane(R, lane);
     if (!L.listed) return;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const Stack stk{lds + kParkBytes, lane};
     const uint32_t sub = L.sub;
-    const bool in_fb = L.in_fb, traced = L.traced;
-    const V3 o = ld3(S.origin), d = primary_direction(P.L.F, L.px, L.py, sub);
+    const bool stores = L.stores, traced = L.traced;
+    const V3 dir = primary_direction(R.F, L.px, L.py, sub);
 #ifdef RRT_PROFILE
     Prof prof{}; prof.last = 0;
 #endif
-    double t; uint32_t slot;
-    walk<kWalk, kGroups>(PROF_ARG S, stk, traced, false, !origin_ray_in_suspect_plane(S, o, d), true, o, d, kInf, t, slot);
-    if (!in_fb) return;
-    const bool found = traced && slot != kNone;
-    double u = 0, v = 0;
-    uint32_t tri = kNone;
-    if (found) {
-        double t2;
-        mt_full(S.geom + slot, o, d, t2, u, v);
-        tri = S.attr[slot].orig;
-    } else {
-        t = 0;                                                                           // the miss convention of intersect_kernel; a pixel the reference never traces reads as a miss
-    }
-    const size_t i = ((size_t)L.py * P.L.F.width + L.px) * 4 + sub;
-    if (P.albedo) {
-        uint32_t col = traced ? 0x00FFFFFFu : 0u;                                        // WHITE, raytracer.rs:109-111; 0 as Canvas::new where nothing is traced
-        if (found) {
-            // --- the texel of the hit, raytracer.rs:43-55, as trace_colour reads it
-            const DevTriAttr& A = S.attr[slot];
-            const DevMaterial& M = S.mats[A.mat];
-            const DevTexture T = M.tex_desc;
-            const double w = 1.0 - u - v;                                                // raytracer.rs:43
-            const double tex_x = A.uv[2] * u + A.uv[4] * v + A.uv[0] * w;                // raytracer.rs:45-47
-            const double tex_y = A.uv[3] * u + A.uv[5] * v + A.uv[1] * w;                // raytracer.rs:48-50
-            const uint64_t txi = umod(f64_as_usize(tex_x * (double)T.width), T.width);    // raytracer.rs:52
-            const uint64_t tyi = umod(f64_as_usize(tex_y * (double)T.height), T.height);  // raytracer.rs:53
-            const uint8_t* tp = T.rgb + 3ull * ((uint64_t)T.width * tyi + txi);          // raytracer.rs:55
-            col = ((uint32_t)tp[0] << 16) | ((uint32_t)tp[1] << 8) | (uint32_t)tp[2];
-        }
-        P.albedo[i] = col;
-    }
-    if (P.hit) P.hit[i] = found ? 1 : 0;
-    if (P.t) P.t[i] = t;
-    if (P.u) P.u[i] = u;
-    if (P.v) P.v[i] = v;
-    if (P.tri) P.tri[i] = tri;
+    const uint32_t mixed = mix_sub_samples(trace_colour<kWalk, kGroups, true>(PROF_ARG S, stk, traced, ld3(S.origin), dir), traced);
+    if (sub == 0 && stores) Q.out[colour_pixel(Q, L)] = mixed;
 }
 
-// surface_kernel over a tile list: surface_body with surface_kernel's arguments, and its stores.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void surface_tile_list_kernel(const DevScene S, const SurfaceTileListParams Q) {
-    const uint32_t lane = threadIdx.x;
-    const VisTileListParams& P = Q.V;
-    const TileLane L = tile_list_lane(P.L, lane);
-    if (!L.listed) return;
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const Stack stk{lds + kParkBytes, lane};
-    const uint32_t sub = L.sub;
-    const bool in_fb = L.in_fb, traced = L.traced;
-    const V3 o = ld3(S.origin), d = primary_direction(P.L.F, L.px, L.py, sub);
-#ifdef RRT_PROFILE
-    Prof prof{}; prof.last = 0;
-#endif
-    const SurfaceHit h = surface_body<kWalk, kGroups>(PROF_ARG S, stk, traced, true, o, d, kInf, traced ? 0x00FFFFFFu : 0u, true, true, true, Q.lights != nullptr);
-    if (!in_fb) return;
-    const size_t i = ((size_t)L.py * P.L.F.width + L.px) * 4 + sub;
-    if (Q.point) { Q.point[3 * i] = h.p.x; Q.point[3 * i + 1] = h.p.y; Q.point[3 * i + 2] = h.p.z; }
-    if (Q.normal) { Q.normal[3 * i] = h.n.x; Q.normal[3 * i + 1] = h.n.y; Q.normal[3 * i + 2] = h.n.z; }
-    if (Q.material) Q.material[i] = h.mat;
-    if (Q.lights) Q.lights[i] = h.mask;
-    // the visibility planes, as visibility_kernel writes them
-    if (P.albedo) P.albedo[i] = h.col;
-    if (P.hit) P.hit[i] = h.found ? 1 : 0;
-    if (P.t) P.t[i] = h.t;
-    if (P.u) P.u[i] = h.u;
-    if (P.v) P.v[i] = h.v;
-    if (P.tri) P.tri[i] = h.tri;
-}
-
-// shade_kernel over a tile list: the five values of a traced lane from the whole-frame planes, shade_body with shade_kernel's arguments, its unwind, mix and store.
-// A lane reads its planes only if it is traced: nothing is read outside the listed tiles.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void shade_tile_list_kernel(const DevScene S, const ShadeTileListParams Q) {
-    const uint32_t lane = threadIdx.x;
-    const TileLane L = tile_list_lane(Q.L, lane);
-    if (!L.listed) return;
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const Stack stk{lds + kParkBytes, lane};
-    const uint32_t sub = L.sub;
-    const bool in_fb = L.in_fb, traced = L.traced;
-    const V3 seg_d = primary_direction(Q.L.F, L.px, L.py, sub);
-#ifdef RRT_PROFILE
-    Prof prof{}; prof.last = 0;
-#endif
-    const size_t pixel_i = (size_t)L.py * Q.L.F.width + L.px, i = pixel_i * 4 + sub;
-    // ---- the five values: the primary segment's hit
-    bool live = false;                      // the lane holds a hit whose colour is not known yet
-    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
-    uint32_t col = 0, mat = 0, li = 0, depth = 0;
-    uint32_t n_eval = 0;                    // lights [0, n_eval) contribute (an occluded point light ends the loop, raytracer.rs:235-237)
-    uint32_t term = 0x00FFFFFFu;            // colour of the last segment; WHITE for a miss, raytracer.rs:109-111
-    if (traced) {
-        mat = Q.material[i];
-        if (mat < S.n_mats) {               // (0xFFFFFFFF, a miss, and anything else beyond the table: WHITE)
-            live = true;
-            p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
-            col = Q.albedo[i] & 0x00FFFFFFu;
-            if (Q.lights) {                 // the kept mask answers the depth-0 shadow queries: the light loop of shade_body is skipped for this hit
-                const uint32_t first_dark = (uint32_t)__builtin_ctz(~Q.lights[i] | (1u << RRT_MAX_LIGHTS));   // (n_lights <= 16: bits at and above it never count)
-                n_eval = first_dark < S.n_lights ? first_dark : S.n_lights;
-                li = 0xFFFFu;
-            }
-        }
-    }
-    double st_local[RRT_MAX_REFLECT][3]; double st_kr[RRT_MAX_REFLECT];
-    const ShadeEnd E = shade_body<kWalk, kGroups, false>(PROF_ARG S, stk, S.max_reflection_depth, true, live, seg_d, p, n, col, mat, li, depth, n_eval, term, st_local, st_kr);
-    const uint32_t c = shade_unwind(E.term, E.lvl, st_local, st_kr);
-    // Color::mix over the 4 sub-samples of the pixel = 4 consecutive lanes (entities.rs:49-69), as render_kernel
-    uint32_t r = (c >> 16) & 255u, g = (c >> 8) & 255u, b = c & 255u;
-    r += __shfl_xor(r, 1); g += __shfl_xor(g, 1); b += __shfl_xor(b, 1);
-    r += __shfl_xor(r, 2); g += __shfl_xor(g, 2); b += __shfl_xor(b, 2);
-    const uint32_t mixed = traced ? (((r >> 2) << 16) | ((g >> 2) << 8) | (b >> 2)) : 0u;   // 0 as Canvas::new where nothing is traced
-    if (sub == 0 && in_fb) Q.out[pixel_i] = mixed;
-}
-
-// ambient_kernel over a tile list.  The body from the lane's hit on is ambient_kernel's, restated (the sample loop with its one call site of the walk included);
-// in_fb stands where in_region stood.  A lane reads its planes only if it is traced.
-template <int kWalk, bool kGroups>
-__global__ __launch_bounds__(64, kWavesPerSimd) void ambient_tile_list_kernel(const DevScene S, const AmbientTileListParams Q) {
-    const uint32_t lane = threadIdx.x;
-    const TileLane L = tile_list_lane(Q.L, lane);
-    if (!L.listed) return;
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const Stack stk{lds + kParkBytes, lane};
-    const uint32_t sub = L.sub;
-    const bool in_fb = L.in_fb, traced = L.traced;
-#ifdef RRT_PROFILE
-    Prof prof{}; prof.last = 0;
-#endif
-    const size_t pixel_i = (size_t)L.py * Q.L.F.width + L.px, i = pixel_i * 4 + sub;
-    // ---- the lane's hit
-    bool hit = false;
-    V3 p = mk(0, 0, 0), n = mk(0, 0, 0);
-    if (traced && Q.material[i] < S.n_mats) {   // (0xFFFFFFFF, a miss, and anything else beyond the table: a miss -- shade_kernel's rule)
-        hit = true;
-        p = ld3(Q.point + 3 * i); n = ld3(Q.normal + 3 * i);
-    }
-    const uint32_t n_samples = Q.n_samples;
-    uint32_t mask = 0;
-    if (__any(hit)) {
-        // the tangent frame of the hit, once for all samples
-        V3 tg = mk(0, 0, 0), bt = mk(0, 0, 0);
-        if (hit) tangent_frame(n, tg, bt);
-        const V3 ro = p + n * S.surface_offset;                                          // the origin of a shadow ray, raytracer.rs:170
-        for (uint32_t k = 0; k < n_samples; k++) {
-            const double sx = Q.dirs[k][0], sy = Q.dirs[k][1], sz = Q.dirs[k][2];        // wave-uniform
-            // (tg*sx + bt*sy) + n*sz, per component five operations, each rounded on its own: the shape of rrt_camera.  (a lane without a hit takes no part; its
-            // ray is a harmless one)
-            const V3 rd = hit ? mk((tg.x * sx + bt.x * sy) + n.x * sz, (tg.y * sx + bt.y * sy) + n.y * sz, (tg.z * sx + bt.z * sy) + n.z * sz) : mk(0, 0, 1);
-            double wt; uint32_t wslot;
-            // (the dispatch restated, as in ambient_kernel)
-            if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, hit, true, true, ro, rd, Q.max_t, wt, wslot);
-            else traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, hit, true, true, false, ro, rd, Q.max_t, wt, wslot);
-            if (hit && wslot != kNone) mask |= 1u << k;
-        }
-    }
-    // ---- grey: the open rays of the pixel's four sub-samples = 4 consecutive lanes, summed as render_kernel sums Color::mix; 255 * open / (4 n), rounded half up
-    uint32_t open = traced ? (hit ? n_samples - (uint32_t)__popc(mask) : n_samples) : 0u;
-    open += __shfl_xor(open, 1);
-    open += __shfl_xor(open, 2);
-    if (!in_fb) return;
-    if (Q.occluded) Q.occluded[i] = mask;
-    if (Q.grey && sub == 0) Q.grey[pixel_i] = traced ? ((510u * open + 4u * n_samples) / (8u * n_samples)) * 0x010101u : 0u;
-}
-
-// For the tile-stage launchers below: the kernel that takes a parameter type (device_scene.hpp: VisTileListParams and its three neighbours).
-template <int kWalk, bool kGroups> auto tile_stage_kernel(const VisTileListParams&) { return &visibility_tile_list_kernel<kWalk, kGroups>; }
-template <int kWalk, bool kGroups> auto tile_stage_kernel(const SurfaceTileListParams&) { return &surface_tile_list_kernel<kWalk, kGroups>; }
-template <int kWalk, bool kGroups> auto tile_stage_kernel(const ShadeTileListParams&) { return &shade_tile_list_kernel<kWalk, kGroups>; }
-template <int kWalk, bool kGroups> auto tile_stage_kernel(const AmbientTileListParams&) { return &ambient_tile_list_kernel<kWalk, kGroups>; }
-
-// For the region launchers below: the kernel that takes a parameter type (device_scene.hpp: VisParams, SurfaceParams, ShadeParams, AmbientParams, RenderRegionParams).
-template <int kWalk, bool kGroups> auto region_kernel(const RenderRegionParams&) { return &render_region_kernel<kWalk, kGroups>; }
-template <int kWalk, bool kGroups> auto region_kernel(const VisParams&) { return &visibility_kernel<kWalk, kGroups>; }
-template <int kWalk, bool kGroups> auto region_kernel(const SurfaceParams&) { return &surface_kernel<kWalk, kGroups>; }
-template <int kWalk, bool kGroups> auto region_kernel(const ShadeParams&) { return &shade_kernel<kWalk, kGroups>; }
-template <int kWalk, bool kGroups> auto region_kernel(const AmbientParams&) { return &ambient_kernel<kWalk, kGroups>; }
+// For the launchers below: the kernel that takes a parameter type (device_scene.hpp), and the ten parameter types.
+template <int kWalk, bool kGroups, class Front> auto stage_kernel(const VisStage<Front>&) { return &visibility_kernel<kWalk, kGroups, VisStage<Front>>; }
+template <int kWalk, bool kGroups, class Front> auto stage_kernel(const SurfaceStage<Front>&) { return &surface_kernel<kWalk, kGroups, SurfaceStage<Front>>; }
+template <int kWalk, bool kGroups, class Front> auto stage_kernel(const ShadeStage<Front>&) { return &shade_kernel<kWalk, kGroups, ShadeStage<Front>>; }
+template <int kWalk, bool kGroups, class Front> auto stage_kernel(const AmbientStage<Front>&) { return &ambient_kernel<kWalk, kGroups, AmbientStage<Front>>; }
+template <int kWalk, bool kGroups> auto stage_kernel(const RenderRegionParams&) { return &colour_kernel<kWalk, kGroups, RenderRegionParams>; }
+template <int kWalk, bool kGroups> auto stage_kernel(const TileListParams&) { return &colour_kernel<kWalk, kGroups, TileListParams>; }
+#define RRT_FOR_EACH_STAGE_PARAMS(X) \
+    X(VisParams) X(SurfaceParams) X(ShadeParams) X(AmbientParams) X(RenderRegionParams) \
+    X(VisTileListParams) X(SurfaceTileListParams) X(ShadeTileListParams) X(AmbientTileListParams) X(TileListParams)
 #endif   // RRT_TU_FRAME || RRT_TU_LANE
 #if RRT_TU_FRAME
 __global__ __launch_bounds__(256) void detile_kernel(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t world, uint32_t tiles_per_rank,
@@ -2794,9 +2592,7 @@ inline int effective_walk(const DevScene& s, int walk) { return (walk == kWalkBu
 // while the host is still parsing the scene (api.cpp, warm_device_async).
 void preload_kernels_lane_ray();
 int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_out, void* stream, int walk, uint32_t n_blocks, uint32_t lds, const uint32_t* d_cover);
-template <class Params> int launch_region_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
-int launch_tile_list_lane_ray(const DevScene& s, const TileListParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
-template <class Params> int launch_tile_stage_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
+template <class Params> int launch_stage_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds);
 void preload_kernels() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_kernel<kWalkBundle, false>));
@@ -2859,61 +2655,25 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
     });
 }
 
-// (the region inside a parameter type)
-inline const VisParams& region_of(const VisParams& p) { return p; }
-template <class Params> const VisParams& region_of(const Params& q) { return q.V; }
-// One region launch: one block per quadrant of the tiles the region touches.  This unit instantiates the bundle-filter kernels only; the other walks go to the
-// lane unit's launch_region_lane_ray.
-template <class Params> int launch_region(const DevScene& s, const Params& q, void* stream, int walk) {
+// (the tiles of a launch: those the region touches, or the entries of the list -- the caller keeps n within kMaxTileList)
+inline uint32_t stage_tiles(const Region& r) { return r.F.tile_end; }
+inline uint32_t stage_tiles(const TileList& l) { return l.n; }
+// One stage launch: one block per quadrant of its tiles.  This unit instantiates the bundle-filter kernels only; the other walks go to the lane unit's
+// launch_stage_lane_ray.
+template <class Params> int launch_stage(const DevScene& s, const Params& q, void* stream, int walk) {
     walk = effective_walk(s, walk);
-    const uint32_t n_tiles = region_of(q).F.tile_end;
+    const uint32_t n_tiles = stage_tiles(front_end(q.front));
     if (n_tiles == 0) return 0;
     const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk != kWalkBundle) return launch_region_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
+    if (walk != kWalkBundle) return launch_stage_lane_ray(s, q, stream, walk, n_tiles * 4, lds);
     return with_groups(s, [&](auto groups) {
-        hipLaunchKernelGGL((region_kernel<kWalkBundle, groups()>(q)), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
+        hipLaunchKernelGGL((stage_kernel<kWalkBundle, groups()>(q)), dim3(n_tiles * 4), dim3(64), lds, (hipStream_t)stream, s, q);
         return (int)hipGetLastError();
     });
 }
-template int launch_region(const DevScene&, const VisParams&, void*, int);
-template int launch_region(const DevScene&, const SurfaceParams&, void*, int);
-template int launch_region(const DevScene&, const ShadeParams&, void*, int);
-template int launch_region(const DevScene&, const AmbientParams&, void*, int);
-template int launch_region(const DevScene&, const RenderRegionParams&, void*, int);
-
-// The tiles of a list in device memory: four blocks per entry of q.n (the caller keeps q.n within kMaxTileList); the dispatch is launch_region's.
-int launch_tile_list(const DevScene& s, const TileListParams& q, void* stream, int walk) {
-    walk = effective_walk(s, walk);
-    if (q.n == 0) return 0;
-    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk != kWalkBundle) return launch_tile_list_lane_ray(s, q, stream, walk, q.n * 4, lds);
-    return with_groups(s, [&](auto groups) {
-        hipLaunchKernelGGL((render_tile_list_kernel<kWalkBundle, groups()>), dim3(q.n * 4), dim3(64), lds, (hipStream_t)stream, s, q);
-        return (int)hipGetLastError();
-    });
-}
-
-// (the list inside a parameter type)
-inline const TileList& list_of(const VisTileListParams& p) { return p.L; }
-inline const TileList& list_of(const SurfaceTileListParams& q) { return q.V.L; }
-inline const TileList& list_of(const ShadeTileListParams& q) { return q.L; }
-inline const TileList& list_of(const AmbientTileListParams& q) { return q.L; }
-// A deferred stage over the tiles of a list in device memory: launch_tile_list's grid and dispatch with the stage's kernel.
-template <class Params> int launch_tile_stage(const DevScene& s, const Params& q, void* stream, int walk) {
-    walk = effective_walk(s, walk);
-    const uint32_t n = list_of(q).n;
-    if (n == 0) return 0;
-    const uint32_t lds = stack_bytes_per_wave(s.stack_levels);
-    if (walk != kWalkBundle) return launch_tile_stage_lane_ray(s, q, stream, walk, n * 4, lds);
-    return with_groups(s, [&](auto groups) {
-        hipLaunchKernelGGL((tile_stage_kernel<kWalkBundle, groups()>(q)), dim3(n * 4), dim3(64), lds, (hipStream_t)stream, s, q);
-        return (int)hipGetLastError();
-    });
-}
-template int launch_tile_stage(const DevScene&, const VisTileListParams&, void*, int);
-template int launch_tile_stage(const DevScene&, const SurfaceTileListParams&, void*, int);
-template int launch_tile_stage(const DevScene&, const ShadeTileListParams&, void*, int);
-template int launch_tile_stage(const DevScene&, const AmbientTileListParams&, void*, int);
+#define RRT_INSTANTIATE(Params) template int launch_stage(const DevScene&, const Params&, void*, int);
+RRT_FOR_EACH_STAGE_PARAMS(RRT_INSTANTIATE)
+#undef RRT_INSTANTIATE
 
 int launch_detile(uint32_t width, uint32_t height, uint32_t world, const uint32_t* d_gathered, uint32_t* d_fb, void* stream) {
     const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
@@ -2941,39 +2701,17 @@ int launch_render_lane_ray(const DevScene& s, const FrameParams& f, uint32_t* d_
         });
     });
 }
-template <class Params> int launch_region_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
+template <class Params> int launch_stage_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
     return with_lane_or_ray_walk(walk, [&](auto w) {
         return with_groups(s, [&](auto groups) {
-            hipLaunchKernelGGL((region_kernel<w(), groups()>(q)), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
+            hipLaunchKernelGGL((stage_kernel<w(), groups()>(q)), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
             return (int)hipGetLastError();
         });
     });
 }
-template int launch_region_lane_ray(const DevScene&, const VisParams&, void*, int, uint32_t, uint32_t);
-template int launch_region_lane_ray(const DevScene&, const SurfaceParams&, void*, int, uint32_t, uint32_t);
-template int launch_region_lane_ray(const DevScene&, const ShadeParams&, void*, int, uint32_t, uint32_t);
-template int launch_region_lane_ray(const DevScene&, const AmbientParams&, void*, int, uint32_t, uint32_t);
-template int launch_region_lane_ray(const DevScene&, const RenderRegionParams&, void*, int, uint32_t, uint32_t);
-int launch_tile_list_lane_ray(const DevScene& s, const TileListParams& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
-    return with_lane_or_ray_walk(walk, [&](auto w) {
-        return with_groups(s, [&](auto groups) {
-            hipLaunchKernelGGL((render_tile_list_kernel<w(), groups()>), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
-            return (int)hipGetLastError();
-        });
-    });
-}
-template <class Params> int launch_tile_stage_lane_ray(const DevScene& s, const Params& q, void* stream, int walk, uint32_t n_blocks, uint32_t lds) {
-    return with_lane_or_ray_walk(walk, [&](auto w) {
-        return with_groups(s, [&](auto groups) {
-            hipLaunchKernelGGL((tile_stage_kernel<w(), groups()>(q)), dim3(n_blocks), dim3(64), lds, (hipStream_t)stream, s, q);
-            return (int)hipGetLastError();
-        });
-    });
-}
-template int launch_tile_stage_lane_ray(const DevScene&, const VisTileListParams&, void*, int, uint32_t, uint32_t);
-template int launch_tile_stage_lane_ray(const DevScene&, const SurfaceTileListParams&, void*, int, uint32_t, uint32_t);
-template int launch_tile_stage_lane_ray(const DevScene&, const ShadeTileListParams&, void*, int, uint32_t, uint32_t);
-template int launch_tile_stage_lane_ray(const DevScene&, const AmbientTileListParams&, void*, int, uint32_t, uint32_t);
+#define RRT_INSTANTIATE(Params) template int launch_stage_lane_ray(const DevScene&, const Params&, void*, int, uint32_t, uint32_t);
+RRT_FOR_EACH_STAGE_PARAMS(RRT_INSTANTIATE)
+#undef RRT_INSTANTIATE
 #endif   // RRT_TU_LANE
 
 #if RRT_TU_RAYS
