@@ -1,4 +1,5 @@
-# Developer tool (run on the GPU box): frame time of the single-GPU workloads for block-order chunk sizes (RRT_XCD_CHUNK, blocks per chunk; 0 = plain order).
+# Developer tool (run on the GPU box): frame time of the single-GPU workloads for block-order chunk sizes (RRT_XCD_CHUNK, blocks per chunk; 0 = plain order, and 1 is the plain order too:
+# with one block per chunk the re-labelling is the identity).
 #   gpurun -- bash tools/xcd_chunk_sweep.sh 0 64 256 1024
 # The first bench.py run that fails (or runs out of time) ends the sweep with its exit status.
 set -eo pipefail
