@@ -96,6 +96,12 @@ typedef struct { const uint8_t *rgb; uint32_t width, height; } rrt_texture;
  * (tests, A/B timing). */
 #define RRT_FLAG_NO_COVERAGE (1u << 7)         /* 128; a developer switch like the two above */
 #define RRT_FLAG_COVERAGE_ALWAYS (1u << 8)     /* 256; a developer switch: the pass also runs where it is judged not to pay (RRT_COVERAGE_OFF_SMALL_FRAME); tests and timing at small sizes */
+/* Wide boxes: the pass also lists the up to 16 boxes of the octree root's own triangles that cover at least 1/128 of the frame (and 16
+ * waves) -- a floor, a table, a mirror.  A wave that only listed boxes reach does not walk its primary rays: it tests them against those few triangles
+ * directly, which is what the walk would return (in the bundle-filter kernel; the lane-filter and ray-walk kernels are built without the short way and walk).
+ * Same results; read at creation.  With this flag the pass lists nothing and every covered wave walks
+ * (tests, A/B timing).  rrt_raytracer_get_wide_cover_info counts. */
+#define RRT_FLAG_NO_WIDE_COVER (1u << 9)       /* 512; a developer switch like RRT_FLAG_NO_COVERAGE */
 
 /* Render constants that the reference hard-codes; NULL => these defaults. */
 typedef struct {
@@ -1089,6 +1095,11 @@ int rrt_raytracer_get_coverage_info(const rrt_raytracer *rt, uint32_t *state, ui
  * waves are 0.  RRT_ERR_INVALID_ARG for a NULL pointer, and for an n_words that is not that frame's.  When the last frame ran without a mask (state !=
  * RRT_COVERAGE_ON) nothing is written and the call returns RRT_OK.  A developer's and tests' view: no launch reads it back. */
 int rrt_raytracer_get_coverage_mask(const rrt_raytracer *rt, uint32_t *words, uint64_t n_words);
+/* The wide boxes of that frame (see RRT_FLAG_NO_WIDE_COVER), BLOCKING like n_proved_empty: n_wide = the boxes the pass listed (at most 16), n_simple_waves = the
+ * waves that only listed boxes reach, whose primary rays the bundle-filter kernel tests against those triangles instead of walking.  Both 0 when the last frame ran without a mask
+ * or with RRT_FLAG_NO_WIDE_COVER, and when some box reaches the whole frame (a corner not certainly in front of the eye): every wave is then ordinary and the
+ * list, whatever the pass had put into it by then, is not used.  Either pointer may be NULL. */
+int rrt_raytracer_get_wide_cover_info(const rrt_raytracer *rt, uint32_t *n_wide, uint64_t *n_simple_waves);
 
 int rrt_last_stats(const rrt_raytracer *rt, rrt_stats *out);
 /* Time of the set-up stages that run once per scene (the reference does all of them inside parse_obj_file_lines, utils.rs:139-213, before its one

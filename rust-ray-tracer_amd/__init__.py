@@ -32,6 +32,7 @@ class RrtError(RuntimeError):
 
 
 FLAG_NO_CULL, FLAG_LANE_FILTER, FLAG_BUNDLE_FILTER, FLAG_RAY_WALK, FLAG_HOST_SETUP, FLAG_NO_CHAIN_SHORTCUT, FLAG_NO_SPECULAR_SKIP, FLAG_NO_COVERAGE, FLAG_COVERAGE_ALWAYS = 1, 2, 4, 8, 16, 32, 64, 128, 256   # RRT_FLAG_*, include/rrt.h
+FLAG_NO_WIDE_COVER = 512
 # rrt_raytracer_get_coverage_info: state 0 = the last frame ran with a coverage mask, else why not (RRT_COVERAGE_OFF_*, include/rrt.h)
 COVERAGE_STATES = ("on", "no_frame", "flag", "no_cull", "suspects", "eye_range", "camera", "pool", "not_whole", "small_frame")
 BUFFERS = ("nodes", "geom", "attr", "supers", "cboxes", "child_boxes", "tboxes", "suspects", "oct_box", "oct_first_child", "oct_tri_count", "oct_own_off",
@@ -292,6 +293,7 @@ SYMBOLS = {
     "rrt_raytracer_get_chain_info": (C.c_int, [_P, _u32p, _u32p]),
     "rrt_raytracer_get_coverage_info": (C.c_int, [_P, _u32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "rrt_raytracer_get_coverage_mask": (C.c_int, [_P, _u32p, C.c_uint64]),
+    "rrt_raytracer_get_wide_cover_info": (C.c_int, [_P, _u32p, C.POINTER(C.c_uint64)]),
     "rrt_last_stats": (C.c_int, [_P, C.POINTER(CStats)]),
     "rrt_get_setup_times": (C.c_int, [_P, _P, C.POINTER(CSetupTimes)]),
     "rrt_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -427,9 +429,10 @@ def _counted(name: str, handle, ctype):
     return arr, n.value
 
 
-def _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut, specular_skip=True, coverage=True) -> COptions:
+def _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut, specular_skip=True, coverage=True, wide_cover=True) -> COptions:
     flags = ((FLAG_NO_CULL if no_cull else 0) | (FLAG_HOST_SETUP if host_setup else 0) | (0 if chain_shortcut else FLAG_NO_CHAIN_SHORTCUT)
              | (0 if specular_skip else FLAG_NO_SPECULAR_SKIP) | (FLAG_COVERAGE_ALWAYS if coverage == "always" else 0 if coverage else FLAG_NO_COVERAGE)
+             | (0 if wide_cover else FLAG_NO_WIDE_COVER)
              | {None: 0, "lane": FLAG_LANE_FILTER, "bundle": FLAG_BUNDLE_FILTER, "ray": FLAG_RAY_WALK}[box_filter])
     return COptions(surface_offset, max_reflection_depth, flags, *map(float, viewport))
 
@@ -836,30 +839,32 @@ class RayTracer(_Handle):
 
     def __init__(self, scene_data: SceneData, lights: Iterable[Light], origin: Vector3d = DEFAULT_ORIGIN, device: int = 0,
                  surface_offset: float = SURFACE_OFFSET, max_reflection_depth: int = MAX_REFLECTION_DEPTH, viewport=VIEWPORT, no_cull: bool = False,
-                 box_filter: Optional[str] = None, host_setup: bool = False, chain_shortcut: bool = True, specular_skip: bool = True, coverage: bool = True):
+                 box_filter: Optional[str] = None, host_setup: bool = False, chain_shortcut: bool = True, specular_skip: bool = True, coverage: bool = True, wide_cover: bool = True):
         """no_cull=True (RRT_FLAG_NO_CULL): walk every own list in full, in list order, as ray.rs:119-129; default uses the cluster boxes.
         box_filter: None = rule of thumb on the first frame of a size, measured on the second, "lane" / "bundle" / "ray" = forced (RRT_FLAG_LANE_FILTER / RRT_FLAG_BUNDLE_FILTER /
         RRT_FLAG_RAY_WALK); same pixels.  host_setup=True (RRT_FLAG_HOST_SETUP): octree, index and records built on the host and uploaded (default: built on
         the GPU, csrc/scene_build.hip); same bytes in HBM.  chain_shortcut=False (RRT_FLAG_NO_CHAIN_SHORTCUT): the bundle-filter walk enters every node of a
         one-child chain; same results.  specular_skip=False (RRT_FLAG_NO_SPECULAR_SKIP): every specular term is evaluated, also those the lighting sum absorbs
         bit for bit; same results.  coverage=False (RRT_FLAG_NO_COVERAGE): whole frames run without the coverage pass, every wave walks; coverage="always"
-        (RRT_FLAG_COVERAGE_ALWAYS): also frames for which the pass is judged not to pay run with it; same results."""
+        (RRT_FLAG_COVERAGE_ALWAYS): also frames for which the pass is judged not to pay run with it; same results.  wide_cover=False (RRT_FLAG_NO_WIDE_COVER):
+        the pass lists no wide boxes, every covered wave walks its primary rays; same results."""
         self.scene_data, self.origin, self.device = scene_data, origin, device
         cl, n_lights = _c_lights(lights)                       # (not kept: lights() asks the library for the list in force)
-        opt = _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut, specular_skip, coverage)
+        opt = _options(surface_offset, max_reflection_depth, viewport, no_cull, box_filter, host_setup, chain_shortcut, specular_skip, coverage, wide_cover)
         out = _P()
         _call("rrt_raytracer_create", scene_data._h, cl, n_lights, origin._c(), C.byref(opt), device, C.byref(out))
         self._h = out
 
     @classmethod
     def from_arrays(cls, pos, uv, nrm, mat, materials: Sequence[dict], textures: Sequence[np.ndarray], lights: Iterable[Light], origin: Vector3d = DEFAULT_ORIGIN,
-                    device: int = 0, root=DEFAULT_ROOT, no_cull: bool = False, box_filter: Optional[str] = None, specular_skip: bool = True, coverage: bool = True) -> "RayTracer":
+                    device: int = 0, root=DEFAULT_ROOT, no_cull: bool = False, box_filter: Optional[str] = None, specular_skip: bool = True, coverage: bool = True,
+                    wide_cover: bool = True) -> "RayTracer":
         """rrt_raytracer_create_from_arrays: the raytracer straight from the host's arrays (no SceneData / rrt_model, no host copy of the scene)."""
         self = cls.__new__(cls)
         self.scene_data, self.origin, self.device = None, origin, device
         scene, _keep = _scene_args(pos, uv, nrm, mat, materials, textures, root)
         cl, n_lights = _c_lights(lights)
-        opt = _options(SURFACE_OFFSET, MAX_REFLECTION_DEPTH, VIEWPORT, no_cull, box_filter, False, True, specular_skip, coverage)
+        opt = _options(SURFACE_OFFSET, MAX_REFLECTION_DEPTH, VIEWPORT, no_cull, box_filter, False, True, specular_skip, coverage, wide_cover)
         out = _P()
         _call("rrt_raytracer_create_from_arrays", *scene, cl, n_lights, origin._c(), C.byref(opt), device, C.byref(out))
         self._h = out
@@ -886,6 +891,13 @@ class RayTracer(_Handle):
         _call("rrt_raytracer_get_coverage_info", self._h, C.byref(state), C.byref(waves), C.byref(empty) if count else None)
         out = {"state": COVERAGE_STATES[state.value], "n_waves": waves.value}
         return dict(out, n_proved_empty=empty.value) if count else out
+
+    def wide_cover_info(self) -> dict:
+        """rrt_raytracer_get_wide_cover_info: the wide boxes the coverage pass of the last frame launch listed and the waves only they reach (their primary rays were
+        tested against those triangles, not walked).  Waits for the frame and reads the counts back; both 0 where that frame ran without a mask."""
+        n = C.c_uint32(0); waves = C.c_uint64(0)
+        _call("rrt_raytracer_get_wide_cover_info", self._h, C.byref(n), C.byref(waves))
+        return {"n_wide": n.value, "n_simple_waves": waves.value}
 
     def coverage_mask(self) -> Optional[np.ndarray]:
         """rrt_raytracer_get_coverage_mask: the coverage mask of the last frame launch as a bool array [2 tiles_y, 2 tiles_x] indexed [by, bx] -- True where the

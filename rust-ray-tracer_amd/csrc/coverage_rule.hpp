@@ -78,6 +78,51 @@ RRT_COV_HD inline uint32_t coverage_wave_index(uint32_t tiles_x, uint32_t bx, ui
     return (((by >> 1) * tiles_x + (bx >> 1)) << 2) | ((by & 1u) << 1) | (bx & 1u);
 }
 
+// The words of a mask: one bit per wave, four per tile, 32 per word (coverage.hip fills them, render_kernel and the getters of frames.cpp read them).
+RRT_COV_HD inline uint32_t coverage_words_of(uint32_t tiles_x, uint32_t tiles_y) { return (uint32_t)(((uint64_t)tiles_x * tiles_y + 7u) / 8u); }
+
+// ---- WIDE BOXES AND SIMPLE WAVES (coverage.hip lists them, render_kernel uses them; DESIGN.md section 4, "wide boxes").
+// THE RULE.  The rectangle r of list slot `slot` is WIDE when all of these hold:
+//   * r holds a wave and is not the whole frame (coverage_is_whole_frame: such a box makes every wave ordinary, as before);
+//   * slot < root_end: the slot belongs to the ROOT node's own list, which is the slots [0, root_end) of the built scene (the slots are in node-id order and the
+//     root is node 0; the host passes root_end, and 0 -- nothing is wide -- with RRT_FLAG_NO_WIDE_COVER);
+//   * r covers at least kWideMinWaves waves AND at least 1 / kWideFrameShare of the frame's waves.
+// At most kMaxWide wide boxes are LISTED per frame, whichever the pass comes to first; a wide box that finds the list full is an ordinary box.  Every box that is
+// not listed ORs its rectangle into a second mask, `fine`.  A wave whose bit is set in the mask and clear in `fine` is SIMPLE: the only boxes that reach it are
+// listed ones.  The bundle-filter render_kernel uses them; the lane-filter and ray-walk kernels are compiled without the path (render.hip: kWidePath) and walk.
+// THE THRESHOLD.  A record costs every simple wave one rectangle compare and buys a wave its walk only where NO unlisted box reaches, so the sixteen records
+// should go to the boxes that own large parts of the frame.  The share makes that independent of the resolution: the teapot frame has 14 root-list boxes (table
+// and mirror) that cover more than 1/81 of the frame each and none between 1/324 and 1/81, at 256 x 144 as at 3840 x 2160; 1/128 lies between.  An absolute count
+// alone does not do: 400 waves lists the 14 at 1920 x 1080, but at 3840 x 2160 27 root-list boxes pass it, the list overflows with teapot triangles and no wave is
+// simple (tools/coverage_count.py).  kWideMinWaves is the floor under the share for small frames: a record that could spare fewer than sixteen waves their walk
+// is not worth a compare in all the others.
+// EXACTNESS.  The soundness above says: a (primary ray, triangle) pair the reference accepts has the ray's sub-sample inside the rectangle of the triangle's slot.
+// For a simple wave every accepted pair therefore names a LISTED triangle of the root's own list whose rectangle contains the wave.  At the root, entered with
+// max_t = +inf for a primary ray, the reference (ray.rs:104-168) keeps the own list's smallest t, the first list position winning a tie, and then asks its
+// children; no accepted pair lies below the root, so every child returns None and the walk returns the own-list result.  render_kernel computes exactly that
+// for a simple wave: Moller-Trumbore on the listed triangles whose rectangle contains the wave, keeping (t, position) by  t < own_t || (t == own_t && pos < own_pos)
+// from own_t = +inf -- a minimum over a set, so the order of the records does not matter.  Whatever turns the mask off (frames.cpp: coverage_state --
+// suspects, no cull, eye range, bad basis, small frames; rank tiles, regions and progressive frames have no mask at all) turns this off with it.
+constexpr uint32_t kMaxWide = 16, kWideMinWaves = 16, kWideFrameShare = 128;
+// One listed box: its slot (the index of its DevTriGeom record) and its rectangle.
+struct WideRecord { uint32_t slot; int32_t bx0, bx1, by0, by1; };
+// Behind the mask's words and its `whole` word, in the same buffer: the mask `fine` (n_words words), the number of wide boxes that asked for a record (it can
+// exceed kMaxWide: min(count, kMaxWide) records are valid), and the records.  Word offsets from the start of the buffer.
+RRT_COV_HD inline uint64_t coverage_fine_offset(uint32_t n_words) { return (uint64_t)n_words + 1u; }
+RRT_COV_HD inline uint64_t coverage_wide_count_offset(uint32_t n_words) { return 2ull * n_words + 1u; }
+RRT_COV_HD inline uint64_t coverage_wide_records_offset(uint32_t n_words) { return 2ull * n_words + 2u; }
+RRT_COV_HD inline uint64_t coverage_buffer_words(uint32_t n_words) { return 2ull * n_words + 2u + kMaxWide * (sizeof(WideRecord) / sizeof(uint32_t)); }
+// Waves of a rectangle (0 for an empty one).
+RRT_COV_HD inline uint64_t coverage_rect_waves(const CoverageRect& r) {
+    return r.bx0 <= r.bx1 && r.by0 <= r.by1 ? (uint64_t)(r.bx1 - r.bx0 + 1) * (uint64_t)(r.by1 - r.by0 + 1) : 0ull;
+}
+// Whether the rectangle r of list slot `slot` is wide (the rule above, without the list's capacity).
+RRT_COV_HD inline bool coverage_is_wide(const CoverageFrame& F, const CoverageRect& r, uint32_t slot, uint32_t root_end) {
+    const uint64_t waves = coverage_rect_waves(r), frame_waves = 4ull * F.tiles_x * F.tiles_y;
+    return slot < root_end && waves >= kWideMinWaves && waves * kWideFrameShare >= frame_waves && !coverage_is_whole_frame(F, r);
+}
+RRT_COV_HD inline bool coverage_rect_contains(const WideRecord& w, int32_t bx, int32_t by) { return bx >= w.bx0 && bx <= w.bx1 && by >= w.by0 && by <= w.by1; }
+
 // x clamped to [lo, hi] and converted; x is finite
 RRT_COV_HD inline int32_t coverage_clamp_i32(double x, double lo, double hi) { return (int32_t)(x < lo ? lo : x > hi ? hi : x); }
 

@@ -363,7 +363,7 @@ int launch_render(const DevScene& s, const FrameParams& f, uint32_t* d_out, void
 // in render_kernel's block order, and one more word behind them.  launch_coverage clears it and marks the waves that boxes[0, n_boxes) can reach, on `stream`.
 struct CoverageFrame;
 uint32_t coverage_mask_words(uint32_t tiles_x, uint32_t tiles_y);
-int launch_coverage(const CoverageFrame& F, const DevClusterBox* boxes, uint32_t n_boxes, uint32_t* mask, void* stream);
+int launch_coverage(const CoverageFrame& F, const DevClusterBox* boxes, uint32_t n_boxes, uint32_t root_end, uint32_t* mask, void* stream);
 // One stage launch (render.hip: launch_stage), for Params = any of the ten arguments above: one block per quadrant of the tiles the region touches, or four
 // blocks per entry of a list's n, the frame kernels' quadrants; no tile, or n == 0, launches nothing.  Defined and instantiated for the ten in render.hip.
 // kMaxTileList: HIP refuses a launch of more than 2^32 - 1 threads in a grid dimension, and an entry takes 4 blocks of 64.

@@ -161,7 +161,7 @@ int launch_whole_frame(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out,
     rt->cover_last = -1;
     rt->cover_off = coverage_state(rt, f, F);
     if (rt->cover_off != RRT_COVERAGE_ON) return launch_render(rt->scene, f, d_out, stream, variant);
-    const CoverPick pick = take_cover_buffer(rt, sizeof(uint32_t) * ((size_t)coverage_mask_words(F.tiles_x, F.tiles_y) + 1), stream);
+    const CoverPick pick = take_cover_buffer(rt, sizeof(uint32_t) * (size_t)coverage_buffer_words(coverage_mask_words(F.tiles_x, F.tiles_y)), stream);
     if (pick.index < 0) { rt->cover_off = RRT_COVERAGE_OFF_POOL; return launch_render(rt->scene, f, d_out, stream, variant); }
     rrt_raytracer::CoverBuf& b = rt->cover[pick.index];
     uint32_t* const mask = static_cast<uint32_t*>(b.mask.mem.h);
@@ -170,7 +170,9 @@ int launch_whole_frame(rrt_raytracer* rt, const FrameParams& f, uint32_t* d_out,
     hipStream_t last_user = pass_stream;                                     // the stream behind whose work `done` has to lie if the call ends here
     try {
         if (pick.wait) HIP_TRY(hipStreamWaitEvent(pass_stream, b.done.h, 0));
-        HIP_TRY((hipError_t)launch_coverage(F, rt->scene.tboxes, rt->built.n_list_slots, mask, pass_stream));
+        // (the root's own list is the slots [0, root_slot_end): its boxes may be listed as wide, coverage_rule.hpp; none with RRT_FLAG_NO_WIDE_COVER)
+        const uint32_t root_end = (rt->opt.flags & RRT_FLAG_NO_WIDE_COVER) ? 0u : rt->built.root_slot_end;
+        HIP_TRY((hipError_t)launch_coverage(F, rt->scene.tboxes, rt->built.n_list_slots, root_end, mask, pass_stream));
         if (beside) {
             HIP_TRY(hipEventRecord(b.ready.h, pass_stream));
             HIP_TRY(hipStreamWaitEvent(frame_stream, b.ready.h, 0));
@@ -393,6 +395,29 @@ int rrt_raytracer_get_coverage_info(const rrt_raytracer* rt_c, uint32_t* state, 
         uint64_t set = 0;
         for (uint32_t w : h) set += (uint64_t)__builtin_popcount(w);
         *n_proved_empty = waves - set;
+        return RRT_OK;
+    });
+}
+
+int rrt_raytracer_get_wide_cover_info(const rrt_raytracer* rt_c, uint32_t* n_wide, uint64_t* n_simple_waves) {
+    return guarded([&]() -> int {
+        rrt_raytracer* rt = const_cast<rrt_raytracer*>(rt_c);
+        if (!rt) throw Error{RRT_ERR_INVALID_ARG, "null raytracer"};
+        if (n_wide) *n_wide = 0;
+        if (n_simple_waves) *n_simple_waves = 0;
+        if (rt->cover_last < 0) return RRT_OK;
+        // the mask, then behind it: `whole`, `fine`, the count (coverage_rule.hpp); a simple wave is set in the mask and clear in `fine`
+        const uint32_t n = coverage_mask_words(rt->cover_tiles_x, rt->cover_tiles_y);
+        std::vector<uint32_t> h(n), tail((size_t)n + 2);                   // tail: `whole`, `fine`, the count
+        read_cover_mask(rt, h.data());                                     // (waits for the frame)
+        DeviceGuard guard(rt->device);
+        HIP_TRY(hipMemcpy(tail.data(), static_cast<const uint32_t*>(rt->cover[rt->cover_last].mask.mem.h) + n, sizeof(uint32_t) * ((size_t)n + 2), hipMemcpyDeviceToHost));
+        const uint32_t* fine = tail.data() + 1;
+        uint64_t simple = 0;
+        for (uint32_t w = 0; w < n; w++) simple += (uint64_t)__builtin_popcount(h[w] & ~fine[w]);
+        // a box that reaches the whole frame makes every wave ordinary, and blocks that see its flag leave before they list: the list is then of no use, and reported empty
+        if (n_wide) *n_wide = tail[0] ? 0u : std::min<uint32_t>(fine[n], kMaxWide);
+        if (n_simple_waves) *n_simple_waves = simple;
         return RRT_OK;
     });
 }

@@ -111,6 +111,10 @@ void host_build_scene(const Model& M, bool enable_cull, const double origin[3], 
     out.n_tris = (uint32_t)M.triangles.size(); out.n_nodes = (uint32_t)n_nodes; out.max_depth = T.max_depth;
     out.n_in_tree = (uint32_t)T.own_idx.size();   // every triangle in the tree appears in exactly one own list
     out.n_list_slots = CS.n_list_slots; out.n_slots_total = (uint32_t)n_slots; out.n_sup_records = (uint32_t)CS.supers.size(); out.n_clusters = CS.n_list_slots / 8;
+    for (uint32_t k = 0; n_nodes && k < CS.node_sup_count[0]; k++) {      // the root's slots: its super-clusters' runs, each padded to a multiple of 8 (a group record holds none)
+        const DevSuper& sp = CS.supers[CS.node_sup_begin[0] + k];
+        if (sp.tri_count) out.root_slot_end = std::max(out.root_slot_end, (sp.tri_begin + sp.tri_count + 7u) & ~7u);
+    }
     out.has_groups = CS.has_groups ? 1u : 0u; out.inline_leaves = CS.inline_leaves ? 1u : 0u;
     out.scene_magnitude = CS.scene_magnitude; out.pad = CS.pad;
     out.n_chains = (uint32_t)CS.chains.size(); out.n_chain_nodes = CS.n_chain_nodes;

@@ -28,6 +28,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "coverage_rule.hpp"
 #include "device_scene.hpp"
 #include "specular_skip.hpp"
 
@@ -1439,12 +1440,37 @@ __device__ __forceinline__ V3 specular_term(PROF_DECL bool skip, double sw, doub
     return mk(0.0, 0.0, 0.0);
 }
 
+// SIMPLE WAVES (coverage_rule.hpp, "wide boxes"; render_kernel only).  The primary walk of a wave that only LISTED boxes reach, without the walk: `wide` points at
+// the pass's count of wide boxes, the records {slot, bx0, bx1, by0, by1} follow it.  Every record whose rectangle contains wave (bx, by) names a triangle of the
+// root's own list; the result is the own-list update of own_cluster_lane over those triangles, from own_t = +inf -- what the reference's walk returns for such a
+// ray, in any record order (a minimum over (t, list position)).  Everything but the Moller-Trumbore test is wave-uniform: scalar loads, scalar compares.
+__device__ __forceinline__ void wide_list_hit(PROF_DECL const DevScene& S, const uint32_t* wide, int32_t bx, int32_t by, bool active, V3 o, V3 d, double& out_t, uint32_t& out_slot) {
+    const RRT_CONSTANT uint32_t* w = (const RRT_CONSTANT uint32_t*)own_sgprs(wide);
+    const RRT_CONSTANT DevTriGeom* geom = (const RRT_CONSTANT DevTriGeom*)own_sgprs(S.geom);
+#if defined(RRT_PROFILE) && defined(RRT_BAND_COUNT)
+    prof.secondary = false; prof.pad = (double)S.cull_limit / 131072.0;
+#endif
+    const uint32_t listed = w[0], n = listed < kMaxWide ? listed : kMaxWide;         // (the count goes on past a full list)
+    double own_t = kInf; uint32_t own_slot = kNone, own_pos = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        const RRT_CONSTANT uint32_t* r = w + 1u + 5u * k;
+        const uint32_t slot = r[0];
+        if (bx < (int32_t)r[1] || bx > (int32_t)r[2] || by < (int32_t)r[3] || by > (int32_t)r[4]) continue;
+        const UTri tri = load_utri(geom + slot);
+        double t;
+        if (active && MT_UNIFORM(tri, o, d, t) && (t < own_t || (t == own_t && tri.pos < own_pos))) { own_t = t; own_slot = slot; own_pos = tri.pos; }
+    }
+    out_t = own_t; out_slot = own_slot;
+}
+
 // RayTracer::get_ray_colour (raytracer.rs:29-112) for 64 lanes; wave-uniform call.  Returns 0x00RRGGBB.
 // kWalk: 0 = node-coherent walk, lane filter; 1 = node-coherent walk, bundle filter; 2 = ray walk (one node per lane)
 constexpr int kWalkLane = 0, kWalkBundle = 1, kWalkRay = 2;
 // kOneOrigin: every lane's `origin` is the same point (the frame kernels: the raytracer's origin; the per-ray kernels take the caller's rays).
-template <int kWalk, bool kGroups, bool kOneOrigin>
-__device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, const Stack& stk, bool active, V3 origin, V3 direction) {
+// kWide (render_kernel): `wide` may be non-null (wave-uniform) -- the wave (wbx, wby) is simple, and wide_list_hit stands in for its FIRST walk, the primary one.
+template <int kWalk, bool kGroups, bool kOneOrigin, bool kWide = false>
+__device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, const Stack& stk, bool active, V3 origin, V3 direction, const uint32_t* wide = nullptr,
+                                                 int32_t wbx = 0, int32_t wby = 0) {
     bool live = active;
     bool in_shadow = false;                 // false: the ray in flight is a segment (primary/reflection) ray; true: a shadow ray
     V3 ro = origin, rd = direction; double rmax = kInf;
@@ -1460,7 +1486,8 @@ __device__ __forceinline__ uint32_t trace_colour(PROF_DECL const DevScene& S, co
     while (__any(live)) {
         double t; uint32_t slot;
         PROF_T(4);                                                       // [4] shading / state machine between traversals
-        if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, live, in_shadow, !(first_unfiltered && depth == 0u && !in_shadow), ro, rd, rmax, t, slot);
+        if (kWide && wide != nullptr) { wide_list_hit(PROF_ARG S, wide, wbx, wby, live, ro, rd, t, slot); wide = nullptr; }   // (wave-uniform; the first turn only)
+        else if constexpr (kWalk == kWalkRay) traverse_ray<kGroups>(PROF_ARG S, stk, live, in_shadow, !(first_unfiltered && depth == 0u && !in_shadow), ro, rd, rmax, t, slot);
         else
         traverse<kWalk == kWalkBundle, kGroups>(PROF_ARG S, stk, live, in_shadow, !(first_unfiltered && depth == 0u && !in_shadow), one_origin, ro, rd, rmax, t, slot);
         one_origin = false;                 // later walks mix shadow and reflection rays of the lanes' own hit points
@@ -1806,6 +1833,8 @@ constexpr int kWavesPerSimd = 4;
 template <int kWalk, bool kGroups>
 // cover: null, or the coverage mask of this whole frame (coverage.hip), one bit per block in the order of `blk` below.  A wave whose bit is clear has no
 // sub-sample whose ray meets any padded triangle box (coverage_rule.hpp): every traced pixel of it is WHITE, and it leaves before it forms a ray.
+// Behind the mask lie a second mask, `fine`, and the list of the frame's wide boxes (coverage_rule.hpp, "wide boxes"): a covered wave whose `fine` bit is clear is
+// SIMPLE -- only listed triangles of the root's own list can be hit by its primary rays -- and tests those instead of walking (trace_colour, wide_list_hit).
 __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScene S, const FrameParams F, uint32_t* __restrict__ out, const uint32_t* __restrict__ cover) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const uint32_t lane = threadIdx.x;
@@ -1857,7 +1886,18 @@ __global__ __launch_bounds__(64, kWavesPerSimd) void render_kernel(const DevScen
     Prof prof{}; prof.last = __builtin_amdgcn_s_memtime();
     const unsigned long long wave_rt0 = __builtin_amdgcn_s_memrealtime(); (void)wave_rt0;
 #endif
-    const uint32_t c = trace_colour<kWalk, kGroups, true>(PROF_ARG S, stk, traced, ld3(S.origin), dir);
+    // (two more scalar loads, wave-uniform: `fine` starts behind the mask's words and its `whole` word, the count of wide boxes behind `fine`)
+    // Bundle-filter kernel only.  With the path in it the lane-filter kernel spills six more scalar registers and loses on its own workloads whether or not a wave
+    // is simple (100 k soup 8.22 -> 8.49 ms, teapot 640 x 480 without a mask 0.4065 -> 0.4151 ms: profiles/wide_cover_ab.txt); the ray walk has no measured
+    // workload of its own.  Both are compiled without it and walk every covered wave, as before.
+    constexpr bool kWidePath = kWalk == kWalkBundle;
+    const uint32_t* wide = nullptr;
+    if (kWidePath && cover) {
+        const uint32_t n_words = coverage_words_of(F.tiles_x, F.tiles_y);
+        const bool covered = (cover[blk >> 5] >> (blk & 31u)) & 1u;                  // (true behind the test above; the wave-time developer build walks every wave)
+        if (covered && !((cover[coverage_fine_offset(n_words) + (blk >> 5)] >> (blk & 31u)) & 1u)) wide = cover + coverage_wide_count_offset(n_words);
+    }
+    const uint32_t c = trace_colour<kWalk, kGroups, true, kWidePath>(PROF_ARG S, stk, traced, ld3(S.origin), dir, wide, (int32_t)(2u * tx + (quad & 1u)), (int32_t)(2u * ty + (quad >> 1)));
 #if defined(RRT_PROFILE) && defined(RRT_PROF_WAVETIME)
     {   // developer build: how long each wave lived (s_memrealtime: the constant 100 MHz clock; s_memtime counts shader cycles), one count per wave into
         // power-of-two buckets of microseconds, the longest in slot 16

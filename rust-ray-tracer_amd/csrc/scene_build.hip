@@ -851,6 +851,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     HIP_TRY(hipMemcpyAsync(h_ctr + 3, X.flags, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(h_ctr + 5, X.chain_rank + n_nodes, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(h_ctr + 6, X.flags + 4, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_ctr + 7, X.slot_base + 1, 4, hipMemcpyDeviceToHost, st));   // (n_nodes >= 1: the first slot of node 1, or the total) = the end of the root's slots
     HIP_TRY(hipStreamSynchronize(st));
     const uint32_t n_list_slots = h_ctr[0], n_sup = h_ctr[1], n_leaves = h_ctr[2], has_groups = h_ctr[3], max_own = h_ctr[4];
     const uint32_t n_slots_total = n_list_slots + n_leaves, n_cl = n_list_slots / 8;
@@ -858,6 +859,7 @@ void gpu_build_scene(const TriSource& src, uint32_t n, const Box& root, bool ena
     X.n_list_slots = n_list_slots; X.n_slots_total = n_slots_total;
     const uint32_t n_chains = h_ctr[5];
     out.n_chains = n_chains; out.n_chain_nodes = h_ctr[6];
+    out.root_slot_end = h_ctr[7];
     lap("index sizes + scans");
 
     // ---- third allocation: what the trace kernels read (kept) + the octree (kept) in one piece; slot-sized temporaries in a piece of their own

@@ -31,6 +31,7 @@ struct BuiltScene {
                                         // triangle outside the tree.  The inverse of attr.orig that rrt_resolve_hits reads; both builders keep it
     uint32_t n_tris = 0, n_nodes = 0, n_in_tree = 0, n_list_slots = 0, n_slots_total = 0, n_sup_records = 0, n_clusters = 0, max_depth = 0;
     uint32_t has_groups = 0, inline_leaves = 0, bounds_plain = 1, n_suspects = 0, all_inside_root = 0;   // all_inside_root: no triangle of the tree pokes out of the root box
+    uint32_t root_slot_end = 0;         // the root node's own list is the slots [0, root_slot_end) (its padding slots included): the coverage pass may list boxes of it as wide
     double scene_magnitude = 0, pad = 0;
     // GPU set-up: GPU time of the three stages (HIP events on the build stream).  Host set-up: wall time of the host octree build (whenever it
     // ran for this model), of index + record fills, and of everything after them (scans, allocation, upload).
